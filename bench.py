@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Mray/s (primary+bounce) of the Renderer::Accumulate hot path on MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload, for every N (BASELINE.json configs[3], "cfg4", SURVEY.md §8d — the config the metric is quoted on): the fixed
@@ -14,7 +14,17 @@ slabs after the timed region (timed separately).  --config cfg2|cfg3|cfg5 select
 value = rays handed to closest-hit traversal by all ranks (Renderer.hpp:165: primary + extension rays; shadow rays are
 reported separately) / max-over-ranks wall time of the K timed steps, inputs resident in HBM, no profiling in that pass.
 
-roofline (rank 0's share of the image for N > 1): k_trace, the dominant kernel, is bound by VALU issue, not by HBM (its BVH bytes are
+A plain run does only that: set-up, W warm-up steps, the K timed steps (and the gather for N > 1), the JSON line.  --full adds
+everything else the line can carry (null without it): the roofline passes and rocprofv3 --pmc child passes below,
+value_with_every_primary_ray_walking_the_tree, kernel_ms_per_step, shadow_rays_per_step, the CPU baseline and, for N > 1, group_host.
+--no-counts / --no-pmc / --no-cpu-baseline / --no-group-host leave out parts of a --full run.
+
+--dump-outputs DIR writes what the timed path leaves for its caller after the last timed step: the accumulator ([tile][bucket][rgb][256]
+f32, Renderer.hpp:43-46; for N > 1 the gathered image) as DIR/accumulator_tiles.npy (float32, a fixed sample of whole tiles, drawn with
+seed 0, in ascending tile order) and DIR/accumulator_tile_sums.npy (float64 [tile][rgb], every tile's radiance summed over buckets and
+pixels).  The inputs are fixed by the arguments, so two builds can be compared output for output.
+
+roofline (--full; rank 0's share of the image for N > 1): k_trace, the dominant kernel, is bound by VALU issue, not by HBM (its BVH bytes are
 served from LDS/L2; north_star's ">= 60 % of the HBM roofline" does not apply to a cache-resident tree — roofline.hbm carries the §8d
 figure and the measured traffic as labelled secondaries).
   * per-kernel durations: HIP events on the launch stream, in a second live pass with one batch in flight (policy.profile);
@@ -63,6 +73,7 @@ VALU_PEAK_TLANE = 256 * 4 * 32 * 2.4e9 / 1e12
 # sphere test (intersect_prims, FMA chain + correctly rounded sqrt + the (dist, index) acceptance) = 31; one any-hit sphere test = 32.
 # Dynamic counts: the kernels' own box / sphere counters (policy.count_traffic), equal to the CPU twin's.
 OPS_PER_BOX, OPS_PER_SPHERE, OPS_PER_SHADOW_SPHERE = 17, 31, 32
+DUMP_SAMPLE_TILES, DUMP_SAMPLE_BYTES = 1024, 56 << 20    # --dump-outputs: at most this many whole tiles / bytes of accumulator words
 MIX_COUNTERS = "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU2 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_CVT"
 SQ_COUNTERS = "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAIT_ANY"
 
@@ -234,6 +245,22 @@ def cpu_baseline(mirt, cfg, log):
     return out
 
 
+def dump_outputs(out_dir, acc, log):
+    """--dump-outputs: `acc` = the whole image's accumulator as a torch tensor [tile][bucket][rgb][256] f32 (device or host)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n_tiles = acc.shape[0]
+    tile_bytes = acc[0].numel() * acc.element_size()
+    n = min(n_tiles, DUMP_SAMPLE_TILES, DUMP_SAMPLE_BYTES // tile_bytes)
+    idx = np.sort(np.random.default_rng(0).choice(n_tiles, n, replace=False))
+    sample = acc[torch.from_numpy(idx).to(acc.device)].cpu().numpy()
+    sums = torch.cat([acc[i:i + 4096].double().sum(dim=(1, 3)).cpu() for i in range(0, n_tiles, 4096)]).numpy()
+    np.save(os.path.join(out_dir, "accumulator_tiles.npy"), np.ascontiguousarray(sample, dtype=np.float32))
+    np.save(os.path.join(out_dir, "accumulator_tile_sums.npy"), np.ascontiguousarray(sums, dtype=np.float64))
+    log(f"outputs: {n} of {n_tiles} accumulator tiles and {n_tiles} tile sums written to {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -252,6 +279,9 @@ def main():
     ap.add_argument("--group", action="store_true", help="one process drives --gpus N devices through the library's mirt_group_* entry points (in-library RCCL gather) "
                     "instead of one process per GPU; MIRT_BENCH_DEVICES=0,0 names the devices explicitly (rehearsal with members sharing a device)")
     ap.add_argument("--no-group-host", action="store_true", help="N > 1 under torch.distributed.run: skip the child run of the --group host")
+    ap.add_argument("--full", action="store_true", help="also run every secondary measurement: roofline / PMC passes, the tree-walking comparison, "
+                    "the CPU baseline, the group host child for N > 1 (a plain run times the K steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write the accumulator they produced to DIR/*.npy")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--tile-rows", default="", help=argparse.SUPPRESS)      # --pmc-child: "first,stride" = one rank's share of the image
     args = ap.parse_args()
@@ -259,6 +289,8 @@ def main():
         return pmc_child(args)
     if args.group:
         return group_main(args)
+    if not args.full:                                      # a plain run: set-up, warm-up, the K timed steps, the line
+        args.no_counts = args.no_pmc = args.no_cpu_baseline = args.no_group_host = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -353,7 +385,11 @@ def main():
         gather_ms = (time.perf_counter() - g0) * 1e3
         if rank == 0:
             assert tuple(full.shape) == (tiles, cfg["buckets"], 3, 256)
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, full, log)
         del full
+    elif args.dump_outputs:
+        dump_outputs(args.dump_outputs, mirt.distributed.device_tensor(*r.accumulator_device(), shape=(count, cfg["buckets"], 3, 256)), log)
 
     # ---- the same steps with every camera ray walking the tree by itself (policy.trace_primary_rays = 1), for comparison: by default the
     #      jittered samples of a pixel share one cone traversal per batch (kernels.hpp, k_primary_cand); results are bit-identical ----
@@ -586,6 +622,9 @@ def group_main(args):
     rays = g.counters()["rays"] - rays0
     g.Gather()                                             # the one exchange of the path, outside the timed region like the per-process host's
     gather_ms = g.gather_ms() if len(devices) > 1 else None
+    if args.dump_outputs:
+        import torch
+        dump_outputs(args.dump_outputs, torch.from_numpy(g.accumulator()), log)
     out = {"metric": "Mray/s (primary+bounce)", "value": rays / elapsed / 1e6, "unit": "Mray/s", "n_gpus": len(devices), "steps": K, "warmup": W,
            "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
            "host": "group (one process, mirt_group_*)", "devices": devices,

@@ -861,7 +861,7 @@ def _bench_line(cmd, env, timeout):
 
 def test_bench_two_ranks_rehearsal(tmp_path):
     """bench.py's torch.distributed path (env parsing, tile sharding, barriers, MAX/SUM reductions, gather) with two ranks
-    sharing this box's single GPU over gloo; on the 8-GPU node the driver runs the same code over RCCL.  The N > 1 line carries what the
+    sharing this box's single GPU over gloo; on an 8-GPU node the same code runs over RCCL.  The N > 1 --full line carries what the
     N = 1 line carries: a roofline for rank 0's share from the rocprofv3 --pmc child passes that rank 0 runs before it joins
     the process group, the CPU baseline, and `group_host` — the library's own multi-GPU host run as a child over the same devices."""
     import shutil
@@ -870,7 +870,7 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     env = dict(os.environ, MIRT_BENCH_SHARE_GPU="1", MIRT_BENCH_BACKEND="gloo")
     port = 29700 + os.getpid() % 200
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--config", "cfg2", "--spp", "5"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--config", "cfg2", "--spp", "5", "--full"]
     d, err = _bench_line(cmd, env, 900)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["image"] == "1024x1024" and d["gather_ms"] is not None
     assert d["value"] > 0 and d["roofline"]["bound"] == "valu" and d["roofline"]["hbm"]["frac"] > 0 and d["rays_per_step"] > 9e6
@@ -893,6 +893,31 @@ def test_bench_group_host_rehearsal():
     env = dict(os.environ, MIRT_BENCH_DEVICES="0,0")
     d, _ = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--group", "--gpus", "2", "--steps", "1", "--warmup", "1", "--config", "cfg2", "--spp", "5"], env, 600)
     assert d["n_gpus"] == 2 and d["devices"] == [0, 0] and d["value"] > 0 and d["gather_ms"] > 0 and d["rays_per_step"] > 9e6 and d["scaling"] == "strong"
+
+
+def test_bench_plain_line_and_dump_outputs(mirt, tmp_path):
+    """A plain bench run (no --full) times exactly --steps steps and carries none of the --full legs; --dump-outputs writes the accumulator
+    the timed steps left, bit for bit what a Renderer driven through the same calls holds, and the same from run to run."""
+    import sys
+    from conftest import ROOT
+    cfg = mirt.scene.CONFIGS["cfg2"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--config", "cfg2", "--spp", "5", "--dump-outputs"]
+    d, _ = _bench_line(base + [str(tmp_path / "a")], dict(os.environ), 600)
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "Mray/s" and d["dtype"] == "f32"
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["kernel_ms_per_step"] is None and d["value_with_every_primary_ray_walking_the_tree"] is None
+    tiles, sums = np.load(tmp_path / "a" / "accumulator_tiles.npy"), np.load(tmp_path / "a" / "accumulator_tile_sums.npy")
+    n_tiles = (cfg["width"] // 16) * (cfg["height"] // 16)
+    assert tiles.dtype == np.float32 and tiles.shape == (1024, cfg["buckets"], 3, 256) and sums.dtype == np.float64 and sums.shape == (n_tiles, 3)
+    r = mirt.Renderer(mirt.scene.synthetic(cfg["n"], ambient=cfg["ambient"]), max_bounces=cfg["max_bounces"], buckets=cfg["buckets"], use_bvh=True)
+    r.Resize(cfg["width"], cfg["height"]); r.Accumulate(3 * 5)
+    acc = r.accumulator()
+    r.close()
+    idx = np.sort(np.random.default_rng(0).choice(n_tiles, len(tiles), replace=False))
+    assert_same(tiles, acc[idx], "bench --dump-outputs sample vs a Renderer after the same 15 accumulations")
+    assert np.allclose(sums, acc.astype(np.float64).sum(axis=(1, 3)), rtol=1e-12, atol=0) and sums.sum() > 0
+    _bench_line(base + [str(tmp_path / "b")], dict(os.environ), 600)
+    for name in ("accumulator_tiles.npy", "accumulator_tile_sums.npy"):
+        assert (tmp_path / "a" / name).read_bytes() == (tmp_path / "b" / name).read_bytes(), name
 
 
 def test_cfg2_full_size_properties(mirt):
