@@ -73,7 +73,8 @@ struct StreamBuf {
 };
 // RayStream<>::ShadowStream, DataStreams.hpp:113-126, plus the deferred-add operands.  A record is 32 B for the common case
 // (dir, tfar, NEE radiance, destination): the origin is the surviving ray's own (read from the next stream through `dest`;
-// stored here only for paths that Russian roulette ended), and the path radiance waits in the destination word itself.
+// stored here only for paths that Russian roulette ended), and the path radiance waits in the surviving ray's radiance word
+// (or the path's own result word when the path ended at this hit).
 struct ShadowBuf {
 	float *px, *py, *pz;        // origin — written only when dest is the accumulator (no surviving ray to share it with)
 	float *dx, *dy, *dz, *tfar;
@@ -93,8 +94,8 @@ struct FrameParams {
 	uint32_t pix_mask;          // accumulations fit a batch ((1 << pix_bits) - 1)
 	uint32_t acc_base;          // `accumulations` before this batch
 	uint32_t batch_n;           // accumulations in flight in this batch
-	uint32_t idx_base;          // where the paths' radiance is added (accum_index): straight into the accumulator (idx_base = acc_base,
-	uint32_t idx_buckets;       // idx_buckets = buckets) or into this batch's contribution buffer [tile][slot][rgb][256] (0xffffffff, batch_n)
+	uint32_t idx_base;          // where the paths' radiance goes (path_result): added straight into the accumulator (idx_base = acc_base,
+	uint32_t idx_buckets;       // idx_buckets = buckets) or stored into this batch's contribution buffer [tile][slot][256][rgb] (kIdxContrib, batch_n)
 	uint32_t max_bounces;
 	uint32_t buckets;
 	uint32_t mis;               // MIS && light_count > 0 (Q12 guard)
@@ -838,15 +839,43 @@ MIRT_DI void accumulate_add(float* __restrict__ accum, size_t idx, float r, floa
 	// and each bucket sees its adds in accumulation order exactly like the reference.
 	accum[idx] += r; accum[idx + kTileSize] += g; accum[idx + 2 * kTileSize] += b;
 }
+// Contribution buffer of a batch: [tile][slot][256][rgb] (slot = accumulation index inside the batch), so that a path's three words
+// share a sector.  Every path of the batch ends exactly once (miss, Russian roulette, or dropped after the last bounce: Q5), and there
+// its word receives a plain store of +0 + radiance — the add into a +0 word it stands for (a dropped path: +0) — so the buffer is never
+// cleared: k_merge_contrib reads every word.  Only a pending light record adds to the word afterwards (shadow_finish: R + S).
+constexpr uint32_t kIdxContrib = 0xffffffffu;   // FrameParams::idx_base / ShadowSink::acc_base of a batch that writes a contribution buffer
+MIRT_DI size_t contrib_index(uint32_t batch_n, uint32_t pix_bits, uint32_t path) {
+	const uint32_t slot = path >> pix_bits;
+	const uint32_t pix = path & ((1u << pix_bits) - 1u);
+	return ((static_cast<size_t>(pix >> 8) * batch_n + slot) * kTileSize + (pix & 255u)) * 3u;
+}
+// A finished path's radiance: added into the accumulator word (direct mode, words that hold earlier samples), or stored into its
+// contribution word (idx_base = kIdxContrib, idx_buckets = batch_n).
+MIRT_DI void path_result(float* __restrict__ accum, uint32_t idx_base, uint32_t idx_buckets, uint32_t pix_bits, uint32_t path, float r, float g, float b) {
+	if (idx_base == kIdxContrib) {
+		float* w = accum + contrib_index(idx_buckets, pix_bits, path);
+		w[0] = 0.0f + r; w[1] = 0.0f + g; w[2] = 0.0f + b;                    // (+0 + -0 = +0, like the add into a zeroed word)
+	} else accumulate_add(accum, accum_index(idx_base, idx_buckets, pix_bits, path), r, g, b);
+}
+MIRT_DI void path_result_add(float* __restrict__ accum, uint32_t idx_base, uint32_t idx_buckets, uint32_t pix_bits, uint32_t path, float r, float g, float b) {
+	if (idx_base == kIdxContrib) {                                              // the word holds +0 + R, stored by k_shade
+		float* w = accum + contrib_index(idx_buckets, pix_bits, path);
+		w[0] += r; w[1] += g; w[2] += b;
+	} else accumulate_add(accum, accum_index(idx_base, idx_buckets, pix_bits, path), r, g, b);
+}
+MIRT_DI void path_result(float* __restrict__ accum, const FrameParams& fp, uint32_t path, float r, float g, float b) { path_result(accum, fp.idx_base, fp.idx_buckets, fp.pix_bits, path, r, g, b); }
 // Where a finished shadow ray's radiance goes.  The adds that had to wait for the occlusion test — (R + unoccluded NEE) +
 // emissive, the reference's order (Renderer.hpp:307-311, then 339-341 / 348-350) — are made by the lane that traced the
-// ray, straight into the next stream's radiance planes or the accumulator: k_trace is VALU-bound, so the few memory
+// ray, straight into the next stream's radiance planes or the path's result word: k_trace is VALU-bound, so the few memory
 // instructions per shadow ray ride along for free, where a separate pass over the shadow stream cost 4.8 ms per cfg2 step.
 //   * light record (the common case: the hit was not emissive): k_shade has already put R where the result belongs — the
-//     surviving ray's radiance word, or the path's own word of the zeroed contribution buffer — so an occluded ray (most of
-//     them) touches nothing and an unoccluded one adds its NEE radiance to that word: R + S, and the emissive term is +0;
+//     surviving ray's radiance word, or the path's own word of the contribution buffer (stored there once, as +0 + R) — so
+//     an occluded ray (most of them) touches nothing and an unoccluded one adds its NEE radiance to that word: R + S, and
+//     the emissive term is +0;
 //   * kDestFull record (emissive hit, or a path that ended while batches add straight into the accumulator, whose words hold
 //     earlier samples): R and E travel in the record and (R + S) + E is formed here.
+// (Measured: sending R along for every path that ends — so that shadow_finish stores each result once — moves a load and a
+//  scattered store per such record into k_trace, whose L2 holds the tree: +8 ms of k_trace per cfg4 batch, more than the adds cost.)
 // occ != nullptr (mirt_debug_trace_shadow): only the occlusion flag is stored.
 constexpr uint32_t kDestFull = 0x40000000u;
 constexpr uint32_t kDestSlot = 0x3fffffffu;     // stream slots stay below 2^30 (capacity check in mirt_capi.hip); path ids use bits 0-29 too (batch slot << pix_bits | pixel)
@@ -873,11 +902,11 @@ MIRT_DI void shadow_finish(const ShadowBuf& sh, const ShadowSink& sink, uint32_t
 		const f3 E{ sh.er[i], sh.eg[i], sh.eb[i] };
 		if (!occluded) { R.x += sh.sr[i]; R.y += sh.sg[i]; R.z += sh.sb[i]; }
 		R.x += E.x; R.y += E.y; R.z += E.z;
-		if (dest & kDestAccum) accumulate_add(sink.accum, accum_index(sink.acc_base, sink.buckets, sink.pix_bits, dest & ~kDestAccum), R.x, R.y, R.z);
+		if (dest & kDestAccum) path_result(sink.accum, sink.acc_base, sink.buckets, sink.pix_bits, dest & ~kDestAccum, R.x, R.y, R.z);
 		else { sink.rr[dest] = R.x; sink.rg[dest] = R.y; sink.rb[dest] = R.z; }
 	} else if (!occluded) {
 		const f3 S{ sh.sr[i], sh.sg[i], sh.sb[i] };
-		if (dest & kDestAccum) accumulate_add(sink.accum, accum_index(sink.acc_base, sink.buckets, sink.pix_bits, dest & ~kDestAccum), S.x, S.y, S.z);   // word = R + S
+		if (dest & kDestAccum) path_result_add(sink.accum, sink.acc_base, sink.buckets, sink.pix_bits, dest & ~kDestAccum, S.x, S.y, S.z);   // word = R + S
 		else { sink.rr[dest] += S.x; sink.rg[dest] += S.y; sink.rb[dest] += S.z; }
 	}
 }
@@ -1227,10 +1256,14 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 						const f3 sky = sky_eval(sc, md.x, md.y, md.z);
 						R.x += thr_x * sky.x; R.y += thr_x * sky.y; R.z += thr_x * sky.z;
 					}
-					accumulate_add(accum, accum_index(fp, mpath), R.x + 0.0f, R.y + 0.0f, R.z + 0.0f);   // ACCUMULATION, Renderer.hpp:424-430 (+ the zero emissive term)
+					path_result(accum, fp, mpath, R.x + 0.0f, R.y + 0.0f, R.z + 0.0f);   // ACCUMULATION, Renderer.hpp:424-430 (+ the zero emissive term)
 					c_term++;
 				} else if (last_bounce) {
 					c_drop++;                                                         // Q5: still alive after the last bounce -> never accumulated
+					if (fp.idx_base == kIdxContrib) {                                 // (its contribution word still gets its one store: +0)
+						float* w = accum + contrib_index(fp.idx_buckets, fp.pix_bits, FIRST ? my_path : in.path[i]);
+						w[0] = 0.0f; w[1] = 0.0f; w[2] = 0.0f;
+					}
 				} else is_hit = true;
 			}
 		}
@@ -1350,7 +1383,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 		block_append2(survive, has_shadow, next_queue, shadow_queue, iteration % kSegs, append_scratch, parity, slot, sslot);
 		// (R + unoccluded NEE) + E is finished by k_trace's shadow_finish once the occlusion is known.  Non-emissive hits (E = +0)
 		// leave R where that result belongs and send a light record; the others send R and E along (kDestFull).
-		const bool direct = fp.idx_base != 0xffffffffu;                          // paths add straight into accumulator words that hold earlier samples
+		const bool direct = fp.idx_base != kIdxContrib;                           // paths add straight into accumulator words that hold earlier samples
 		const bool full = has_shadow & (has_E | (terminated & direct));
 		if (survive) {
 			out.px[slot] = P.x; out.py[slot] = P.y; out.pz[slot] = P.z;
@@ -1372,7 +1405,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 		if ((survive | terminated) & !full) {
 			const f3 Rf{ R.x + E.x, R.y + E.y, R.z + E.z };                       // E is +0 when the hit is not emissive (exact no-op); with a light record pending E is +0 too
 			if (survive) { out.rr[slot] = Rf.x; out.rg[slot] = Rf.y; out.rb[slot] = Rf.z; }
-			else accumulate_add(accum, accum_index(fp, path), Rf.x, Rf.y, Rf.z);   // ACCUMULATION, Renderer.hpp:424-430 (a pending light record adds its NEE term to the same word)
+			else path_result(accum, fp, path, Rf.x, Rf.y, Rf.z);                  // ACCUMULATION, Renderer.hpp:424-430 (a pending light record adds its NEE term to the same word)
 		}
 		c_term += (terminated && !has_shadow) ? 1u : 0u;
 	}
@@ -1380,27 +1413,32 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 	wave_sum(c_drop, &ctr->dropped);
 }
 
-// In-order merge of one batch's contribution buffer ([tile][slot][rgb][256], slot = accumulation index inside the batch)
-// into the accumulator (see launch_batch in mirt_capi.hip): exactly the `output_color[px] += radiance` of
-// Renderer.hpp:427-429, one add per (pixel, bucket) per Accumulate() call.  Accumulation acc_base+k+1 lands in bucket
-// (acc_base+k+1) % buckets (Renderer.hpp:82); each accumulator word is owned by one thread, which applies that bucket's
-// contributions in ascending k, i.e. in accumulation order.  Entries a path did not touch hold +0 (exact no-op).
+// In-order merge of one batch's contribution buffer ([tile][slot][256][rgb], slot = accumulation index inside the batch; see
+// contrib_index) into the accumulator ([tile][bucket][rgb][256]; see launch_batch in mirt_capi.hip): exactly the
+// `output_color[px] += radiance` of Renderer.hpp:427-429, one add per (pixel, bucket) per Accumulate() call.  Accumulation
+// acc_base+k+1 lands in bucket (acc_base+k+1) % buckets (Renderer.hpp:82); each accumulator word is owned by one thread, which
+// applies that bucket's contributions in ascending k, i.e. in accumulation order.  A thread owns 4 pixels of a tile: per slot it
+// reads their 12 interleaved words (three float4) and adds them to the 4-pixel float4 of each channel plane.
 __global__ __launch_bounds__(kBlock) void k_merge_contrib(float4* __restrict__ accum, const float4* __restrict__ contrib, uint32_t n_tiles, uint32_t buckets,
                                                           uint32_t batch_n, uint32_t acc_base) {
-	constexpr uint32_t kQuads = 3u * kTileSize / 4u;                            // float4 per (tile, bucket)
+	constexpr uint32_t kQuads = kTileSize / 4u;                                 // 4-pixel groups per tile
 	const size_t n_items = static_cast<size_t>(n_tiles) * kQuads;
 	const uint32_t first = min(buckets, batch_n);
 	for (size_t item = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x; item < n_items; item += static_cast<size_t>(gridDim.x) * kBlock) {
 		const size_t tile = item / kQuads; const uint32_t q = static_cast<uint32_t>(item % kQuads);
 		for (uint32_t k0 = 0; k0 < first; k0++) {
 			const uint32_t bucket = (acc_base + k0 + 1u) % buckets;
-			float4* dst = accum + (tile * buckets + bucket) * kQuads + q;
-			float4 a = *dst;
+			float4* dst = accum + (tile * buckets + bucket) * 3u * kQuads + q;  // channel c of the 4 pixels: dst[c * kQuads]
+			float4 r = dst[0], g = dst[kQuads], b = dst[2u * kQuads];
 			for (uint32_t k = k0; k < batch_n; k += buckets) {
-				const float4 c = contrib[(tile * batch_n + k) * kQuads + q];
-				a.x += c.x; a.y += c.y; a.z += c.z; a.w += c.w;
+				const float4* src = contrib + ((tile * batch_n + k) * kQuads + q) * 3u;
+				const float4 c0 = src[0], c1 = src[1], c2 = src[2];                // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+				r.x += c0.x; g.x += c0.y; b.x += c0.z;
+				r.y += c0.w; g.y += c1.x; b.y += c1.y;
+				r.z += c1.z; g.z += c1.w; b.z += c2.x;
+				r.w += c2.y; g.w += c2.z; b.w += c2.w;
 			}
-			*dst = a;
+			dst[0] = r; dst[kQuads] = g; dst[2u * kQuads] = b;
 		}
 	}
 }
