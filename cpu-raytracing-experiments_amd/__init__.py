@@ -36,7 +36,7 @@ class Policy(C.Structure):
     """mirt_policy — RendererPolicy (Renderer.hpp:19-26) + the path's compile-time switches."""
     _fields_ = [("max_bounces", C.c_uint32), ("buckets", C.c_uint32), ("mis", C.c_uint32), ("use_bvh", C.c_uint32),
                 ("count_traffic", C.c_uint32), ("profile", C.c_uint32), ("max_batch", C.c_uint32), ("reference_tree", C.c_uint32),
-                ("streams", C.c_uint32), ("gpu_build", C.c_uint32), ("trace_primary_rays", C.c_uint32), ("_reserved", C.c_uint32 * 1)]
+                ("streams", C.c_uint32), ("gpu_build", C.c_uint32), ("trace_primary_rays", C.c_uint32), ("brdf", C.c_uint32)]
 
 
 class Counters(C.Structure):
@@ -80,6 +80,7 @@ def load_library():
         "mirt_set_camera": [P, vp, vp, f, f, f, f],
         "mirt_set_policy": [P, C.POINTER(Policy)],
         "mirt_get_policy": [P, C.POINTER(Policy)],
+        "mirt_set_gloss_decay": [P, vp, u32],
         "mirt_resize": [P, u32, u32],
         "mirt_set_tile_range": [P, u32, u32], "mirt_set_tile_rows": [P, u32, u32],
         "mirt_reset": [P],
@@ -112,6 +113,7 @@ def load_library():
         "mirt_group_set_scene": [G, vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, vp, u32, u32],
         "mirt_group_set_camera": [G, vp, vp, f, f, f, f],
         "mirt_group_set_policy": [G, C.POINTER(Policy)],
+        "mirt_group_set_gloss_decay": [G, vp, u32],
         "mirt_group_resize": [G, u32, u32],
         "mirt_group_reset": [G],
         "mirt_group_accumulate": [G, u32],
@@ -170,6 +172,10 @@ def light_list(geometry: np.ndarray, material: np.ndarray) -> np.ndarray:
     return out[: n.value].copy()
 
 
+def _decay_array(decay) -> np.ndarray:
+    return np.ascontiguousarray([] if decay is None else decay, dtype=np.float32).reshape(-1)
+
+
 class Renderer:
     """Mirror of the reference's ``Renderer<Policy>`` (Renderer.hpp:28-68) over the C-ABI.
 
@@ -179,7 +185,8 @@ class Renderer:
 
     def __init__(self, scene: Scene, device: int = 0, max_bounces: int = 16, buckets: int = 5, mis: bool = True,
                  use_bvh: bool = False, count_traffic: bool = False, profile: bool = False, max_batch: int = 0,
-                 allow_half_boxes: bool = True, reference_tree: bool = False, streams: int = 0, gpu_build: bool = False, trace_primary_rays: bool = False):
+                 allow_half_boxes: bool = True, reference_tree: bool = False, streams: int = 0, gpu_build: bool = False, trace_primary_rays: bool = False,
+                 brdf: int = 0, gloss_decay=None):
         self._lib = load_library()
         self._ctx = C.c_void_p()
         rc = self._lib.mirt_create(device, C.byref(self._ctx))
@@ -188,9 +195,12 @@ class Renderer:
         self.scene = scene
         self.width = self.height = 0
         self.framebuffer = None
-        self.policy = Policy(max_bounces, buckets, int(mis), int(use_bvh), int(count_traffic), int(profile), max_batch, int(reference_tree), int(streams), int(gpu_build), int(trace_primary_rays))
+        self.policy = Policy(max_bounces, buckets, int(mis), int(use_bvh), int(count_traffic), int(profile), max_batch, int(reference_tree), int(streams), int(gpu_build), int(trace_primary_rays),
+                             int(brdf))
         self._check(self._lib.mirt_set_policy(self._ctx, C.byref(self.policy)))
         self._check(self._lib.mirt_debug_allow_half_boxes(self._ctx, int(allow_half_boxes)))
+        if gloss_decay is not None:
+            self.set_gloss_decay(gloss_decay)
         self.UpdateScene()
 
     # -- plumbing ---------------------------------------------------------------------------
@@ -222,6 +232,12 @@ class Renderer:
             setattr(p, k, int(v))
         self._check(self._lib.mirt_set_policy(self._ctx, C.byref(p)))
         self.policy = p                                    # only a policy the library accepted becomes this object's
+
+    def set_gloss_decay(self, decay=None):
+        """gloss_decay_table (Renderer.hpp:212) for brdf = 1: decay[b] is mixed into the GGX alpha at bounce b; later bounces use 0.
+        None or an empty sequence resets it to zeros."""
+        d = _decay_array(decay)
+        self._check(self._lib.mirt_set_gloss_decay(self._ctx, _ptr(d) if len(d) else None, len(d)))
 
     # -- scene hand-over (Application.cpp:230-234) -------------------------------------------------
     def UpdateScene(self, nodes=None):
@@ -378,7 +394,8 @@ class GroupRenderer:
     one-GPU box; slabs then move with device copies)."""
 
     def __init__(self, scene: Scene, devices=(0,), max_bounces: int = 16, buckets: int = 5, mis: bool = True, use_bvh: bool = True,
-                 count_traffic: bool = False, max_batch: int = 0, streams: int = 0, reference_tree: bool = False, gpu_build: bool = False):
+                 count_traffic: bool = False, max_batch: int = 0, streams: int = 0, reference_tree: bool = False, gpu_build: bool = False,
+                 brdf: int = 0, gloss_decay=None):
         self._lib = load_library()
         self._g = C.c_void_p()
         dev = (C.c_int * len(devices))(*devices)
@@ -388,8 +405,11 @@ class GroupRenderer:
         self.scene, self.devices = scene, tuple(devices)
         self.width = self.height = 0
         self.framebuffer = None
-        self.policy = Policy(max_bounces, buckets, int(mis), int(use_bvh), int(count_traffic), 0, max_batch, int(reference_tree), int(streams), int(gpu_build))
+        self.policy = Policy(max_bounces, buckets, int(mis), int(use_bvh), int(count_traffic), 0, max_batch, int(reference_tree), int(streams), int(gpu_build), 0,
+                             int(brdf))
         self._check(self._lib.mirt_group_set_policy(self._g, C.byref(self.policy)))
+        if gloss_decay is not None:
+            self.set_gloss_decay(gloss_decay)
         self.UpdateScene()
 
     def _check(self, rc):
@@ -407,6 +427,18 @@ class GroupRenderer:
             self.close()
         except Exception:
             pass
+
+    def set_policy(self, **kw):
+        p = Policy.from_buffer_copy(self.policy)
+        for k, v in kw.items():
+            setattr(p, k, int(v))
+        self._check(self._lib.mirt_group_set_policy(self._g, C.byref(p)))
+        self.policy = p
+
+    def set_gloss_decay(self, decay=None):
+        """Renderer.set_gloss_decay on every member."""
+        d = _decay_array(decay)
+        self._check(self._lib.mirt_group_set_gloss_decay(self._g, _ptr(d) if len(d) else None, len(d)))
 
     def UpdateScene(self):
         s = self.scene

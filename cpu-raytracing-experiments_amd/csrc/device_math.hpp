@@ -154,9 +154,10 @@ MIRT_DI f3 sample_direction_to_sphere(f3 Wc, float sinThetaMax2, float center_di
 	         wcX.z * Ll.x + wcY.z * Ll.y + Wc.z * Ll.z };
 }
 // ---- GGX closure, function level (DataStreams.hpp:184-219, Sampling.hpp:85-91,102-104,254-309) --------------
-// The reference's path with this closure does not build (`#define BRDF 0`; `gloss_decay_table` of Renderer.hpp:212 is declared
-// nowhere) and Closure<GGX>::pdf returns 0 ("TODO"), so these functions are NOT wired into k_shade; they are the defined part of the
-// closure, checked bit for bit against the oracle through mirt_debug_math (fn 8, 9).
+// The reference's path with this closure does not build as shipped (`#define BRDF 0`; `gloss_decay_table` of Renderer.hpp:212 is
+// declared nowhere): the library takes the decay table from the host (mirt_set_gloss_decay) and k_shade<., GGX = true> runs these
+// functions when policy.brdf = 1, with Closure<GGX>::pdf = 0 as written ("TODO").  Checked bit for bit against the oracle through
+// mirt_debug_math (fn 8, 9).
 MIRT_DI float mix_glm(float x, float y, float a) { return x * (1.0f - a) + y * a; }           // glm::mix
 MIRT_DI float clamp_std(float v, float lo, float hi) { return (v < lo) ? lo : (hi < v) ? hi : v; }
 MIRT_DI void disk(float t, float s, float& x, float& y) {                                       // Sampling.hpp:85-91,102-104

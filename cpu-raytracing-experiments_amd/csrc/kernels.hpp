@@ -1169,9 +1169,14 @@ MIRT_DI uint32_t block_compact(bool flag, uint32_t value, uint32_t* scratch, uin
 // seed[ID]) is set up once per chunk.  Its hit records come from k_primary_hits (pixels with a candidate list) or k_trace.
 // (Measured and dropped twice: the candidate tests inside this kernel instead of k_primary_hits — ray-major in round 2, pixel-major in
 // round 3: at 6 waves per SIMD and 80 VGPRs the list's dependent loads cost k_shade<FIRST> 5 ms per cfg4 batch, as much as the kernel saved.)
-template <bool FIRST>
+// GGX = #define BRDF 1 (Renderer.hpp:70): every closure is Closure<GGX> (DataStreams.hpp:184-219) with F0 = material.F0 and
+// alpha = r^2 + (1 - r^2) * gloss_decay (Renderer.hpp:210-212; `gloss_decay` = the host's table at this bounce, one launch per
+// bounce), read from mat_ggx = {F0.xyz, roughness}.  Its pdf() is 0: NEE weighs 1 / light_pdf and emitters hit by an extension
+// ray weigh powerHeuristic(0, .) = 0.  GGX = false does not read the two trailing arguments.
+template <bool FIRST, bool GGX>
 __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
-                                                  Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ accum, DevCounters* ctr) {
+                                                  Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ accum, DevCounters* ctr,
+                                                  const float4* __restrict__ mat_ggx, float gloss_decay) {
 	const QueueView qin = FIRST ? queue_identity(fp.n_pix * fp.batch_n) : queue_view(in_queue);
 	const uint32_t n = qin.pre[kSegs];
 	const uint32_t n_chunks = (fp.n_pix + kShadeBlock - 1u) / kShadeBlock;      // FIRST
@@ -1180,11 +1185,11 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 	__shared__ uint32_t append_scratch[72];
 	__shared__ uint32_t compact_scratch[17];
 	__shared__ uint32_t hit_list[kShadeBlock];
-	__shared__ float4 s_albedo[MIRT_MAX_MATERIALS + 1], s_emission[MIRT_MAX_MATERIALS + 1];      // scene.material: 2 KB, read by every hit
+	__shared__ float4 s_albedo[MIRT_MAX_MATERIALS + 1], s_emission[MIRT_MAX_MATERIALS + 1];      // scene.material: 2 KB, read by every hit (GGX: s_albedo = {F0, roughness})
 	uint32_t c_term = 0, c_drop = 0, parity = 0;
 	const uint32_t n_units = n_chunks * fp.first_groups;                       // FIRST: pieces of work = (chunk, group of accumulations)
 	if (FIRST ? blockIdx.x >= n_units : blockIdx.x * kShadeBlock >= n) return;
-	for (uint32_t m = threadIdx.x; m < sc.n_mat; m += kShadeBlock) { s_albedo[m] = sc.mat_albedo[m]; s_emission[m] = sc.mat_emission[m]; }
+	for (uint32_t m = threadIdx.x; m < sc.n_mat; m += kShadeBlock) { s_albedo[m] = GGX ? mat_ggx[m] : sc.mat_albedo[m]; s_emission[m] = sc.mat_emission[m]; }
 	__syncthreads();            // the table is read by every wave in phase 2; k_shade<FIRST> reaches no other barrier before that (the early return above is block-uniform)
 
 	// !FIRST: this lane's ray of the stream for the block-iteration at hand, and its hit record: requested one iteration ahead, so that the
@@ -1287,7 +1292,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 			if (!FIRST) {
 				R = { in.rr[i], in.rg[i], in.rb[i] };
 				thr = { in.tr[i], in.tg[i], in.tb[i] };
-				pdf_in = MIRT_INV_PI * max_sel(0.0f, D.z);                        // out->pdf of the bounce that sampled D (Q8), bit for bit
+				pdf_in = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, D.z);           // out->pdf of the bounce that sampled D (Q8), bit for bit; Closure<GGX>::pdf = 0
 			}
 			const HitRec hrec = FIRST ? HitRec{ my_tfar, my_prim } : hit_in[i];
 			const int32_t prim = hrec.prim;
@@ -1306,6 +1311,13 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 				const float4 em = s_emission[mat];
 				const float4 alb = s_albedo[mat];
 				const bool is_emissive = max_sel(em.x, max_sel(em.y, em.z)) > MIRT_FLT_EPSILON;
+				f3 F0{0.0f, 0.0f, 0.0f};
+				float alpha = 0.0f;
+				if (GGX) {                                                         // closure set-up, Renderer.hpp:210-212
+					F0 = { alb.x, alb.y, alb.z };
+					float a = alb.w; a *= a;
+					alpha = a + (1.0f - a) * gloss_decay;
+				}
 				const uint32_t acc = fp.acc_base + (path >> fp.pix_bits) + 1u;
 				const uint32_t seed = FIRST ? pix_seed : path_seed(fp, path & fp.pix_mask);
 
@@ -1335,12 +1347,15 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 						const f3 Ll = to_local(T, Ld);
 						if (Ll.z < 0.0f) break;
 						f3 rad{ lem.x * thr.x, lem.y * thr.y, lem.z * thr.z };
-						{   // Closure<LambertianDiffuse>::eval, DataStreams.hpp:169-172
+						if (GGX) {  // Closure<GGX>::eval, DataStreams.hpp:189-195
+							const f3 f = ggx_eval(F0, alpha, Ll, Vl);
+							rad.x *= f.x; rad.y *= f.y; rad.z *= f.z;
+						} else {    // Closure<LambertianDiffuse>::eval, DataStreams.hpp:169-172
 							const float f = MIRT_INV_PI * max_sel(0.0f, Ll.z);
 							rad.x *= alb.x * f; rad.y *= alb.y * f; rad.z *= alb.z * f;
 						}
 						lpdf *= light_selection_pdf;
-						const float brdf_pdf = MIRT_INV_PI * max_sel(0.0f, Ll.z);  // DataStreams.hpp:173-176
+						const float brdf_pdf = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, Ll.z);  // DataStreams.hpp:173-176 / :196-198
 						const float w = powerHeuristic_over_f(lpdf, brdf_pdf);
 						rad.x *= w; rad.y *= w; rad.z *= w;
 						if (max_sel(max_sel(rad.x, rad.y), rad.z) <= 0.0f) break;
@@ -1364,8 +1379,15 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 					uint32_t rng = hash_2d(acc, seed + bounce * 2u + 1u);
 					const float b0 = rand_unit_float(rng);
 					const float b1 = rand_unit_float(rng);
-					f3 sd = hemisphere(b0, b1);                                     // Closure::sample, DataStreams.hpp:177-181
-					thr = { thr.x * alb.x, thr.y * alb.y, thr.z * alb.z };
+					f3 sd;
+					if (GGX) {                                                      // Closure<GGX>::sample, DataStreams.hpp:200-218
+						f3 est;
+						ggx_sample(F0, alpha, Vl, b0, b1, sd, est);
+						thr = { thr.x * est.x, thr.y * est.y, thr.z * est.z };
+					} else {
+						sd = hemisphere(b0, b1);                                    // Closure::sample, DataStreams.hpp:177-181
+						thr = { thr.x * alb.x, thr.y * alb.y, thr.z * alb.z };
+					}
 					const float q = 1.0f - max_sel(thr.x, max_sel(thr.y, thr.z));
 					if (rand_unit_float(rng) < q) {
 						terminated = true;                                          // Russian roulette, Renderer.hpp:377-383

@@ -77,7 +77,7 @@ struct mirt_ctx {
 	hipStream_t stream = nullptr;
 	std::string error;
 
-	mirt_policy policy{ 16, 5, 1, 0, 0, 0, 0, 0, 0, 0, 0, { 0 } };     // RendererPolicy defaults, Renderer.hpp:19-26,41,71; USEBVH false BVH.hpp:307
+	mirt_policy policy{ 16, 5, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0 };         // RendererPolicy defaults, Renderer.hpp:19-26,41,71; USEBVH false BVH.hpp:307; BRDF 0 :70
 	uint32_t width = 0, height = 0, h_tiles = 0, v_tiles = 0;
 	uint32_t first_tile = 0, n_tiles = 0;
 	uint32_t run_tiles = 0, stride_tiles = 0;   // interleaved tile rows (mirt_set_tile_rows); stride 0 = one contiguous range
@@ -85,8 +85,9 @@ struct mirt_ctx {
 	bool have_scene = false, have_camera = false;
 
 	// scene
-	DeviceBuffer recs, recs_wide, spheres, prim_mat, light_sphere, light_emit, mat_albedo, mat_emission, hdri;
+	DeviceBuffer recs, recs_wide, spheres, prim_mat, light_sphere, light_emit, mat_albedo, mat_emission, mat_ggx, hdri;
 	SceneDev scene{};
+	std::vector<float> gloss_decay;  // gloss_decay_table (Renderer.hpp:212) by bounce, read at launch (mirt_set_gloss_decay); missing entries are 0
 	CameraParams camera{};
 	uint32_t trace_lds_bytes = 0;    // dynamic LDS of the BVH trace kernels (staged records + spheres)
 	uint32_t bvh_depth = 0;
@@ -409,6 +410,7 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 	// 1.47e-3, from |D|^2 - 1 of its normalised direction) may exceed the axis ray's by 8.5e-5
 	const float rho = bundle ? bundle_half_angle(c) : 0.0f;
 	DevCounters* ctr = c->counters.as<DevCounters>();
+	const float4* mat_ggx = c->mat_ggx.as<float4>();
 	float* accum = contrib ? sl.contrib.as<float>() : c->accumulator.as<float>();
 	SceneDev sc = c->scene;
 	sc.use_bvh = c->policy.use_bvh;
@@ -463,8 +465,14 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 		  else if (bounce == 0) { if (count) launch_trace((k_trace<true, kPrimaryAll>), (k_trace_fat<true, kPrimaryAll>)); else launch_trace((k_trace<false, kPrimaryAll>), (k_trace_fat<false, kPrimaryAll>)); }
 		  else                  { if (count) launch_trace((k_trace<true, kPrimaryNone>), (k_trace_fat<true, kPrimaryNone>)); else launch_trace((k_trace<false, kPrimaryNone>), (k_trace_fat<false, kPrimaryNone>)); } }
 		{ Bracket t(c, MIRT_K_SHADE, st);
-		  if (bounce == 0) hipLaunchKernelGGL(k_shade<true>, dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce, stream_queue(bounce), stream_queue(bounce + 1), shadow_queue(bounce), accum, ctr);
-		  else             hipLaunchKernelGGL(k_shade<false>, dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce, stream_queue(bounce), stream_queue(bounce + 1), shadow_queue(bounce), accum, ctr); }
+		  // policy.brdf = 1 (#define BRDF 1): Closure<GGX> with this bounce's gloss decay, passed by value
+		  const float decay = bounce < c->gloss_decay.size() ? c->gloss_decay[bounce] : 0.0f;
+		  auto launch_shade = [&](auto kernel) {
+		    hipLaunchKernelGGL(kernel, dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce, stream_queue(bounce), stream_queue(bounce + 1),
+		                       shadow_queue(bounce), accum, ctr, mat_ggx, decay);
+		  };
+		  if (c->policy.brdf) { if (bounce == 0) launch_shade(k_shade<true, true>); else launch_shade(k_shade<false, true>); }
+		  else                { if (bounce == 0) launch_shade(k_shade<true, false>); else launch_shade(k_shade<false, false>); } }
 	}
 	HIP_TRY(c, hipGetLastError());
 	if (contrib) {
@@ -559,7 +567,7 @@ int mirt_destroy(mirt_ctx* c) {
 	c->slots.clear();
 	for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
 	DeviceBuffer* bufs[] = { &c->recs, &c->recs_wide, &c->spheres, &c->prim_mat, &c->light_sphere, &c->light_emit, &c->mat_albedo, &c->mat_emission,
-	                         &c->hdri, &c->accumulator, &c->framebuffer, &c->counters };
+	                         &c->mat_ggx, &c->hdri, &c->accumulator, &c->framebuffer, &c->counters };
 	for (DeviceBuffer* b : bufs) b->release();
 	if (c->frame_host) (void)hipHostFree(c->frame_host);
 	if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -607,7 +615,7 @@ int mirt_set_scene(mirt_ctx* c, const mirt_sphere* geometry, const mirt_sphere* 
 	if (n_spheres && n_nodes == 0) return fail(c, MIRT_ERR_ARG, "spheres without BVH nodes");
 	HIP_TRY(c, hipSetDevice(c->device));
 
-	std::vector<float4> sph(n_spheres), lsp(n_lights), lem(n_lights), alb(n_materials), emi(n_materials), sky(static_cast<size_t>(hdri_w) * hdri_h);
+	std::vector<float4> sph(n_spheres), lsp(n_lights), lem(n_lights), alb(n_materials), emi(n_materials), ggx(n_materials), sky(static_cast<size_t>(hdri_w) * hdri_h);
 	std::vector<int32_t> pm(n_spheres);
 	for (uint32_t i = 0; i < n_spheres; i++) {
 		sph[i] = make_float4(bvh_prims[i].position[0], bvh_prims[i].position[1], bvh_prims[i].position[2], bvh_prims[i].radius_sq);
@@ -625,6 +633,7 @@ int mirt_set_scene(mirt_ctx* c, const mirt_sphere* geometry, const mirt_sphere* 
 	for (uint32_t i = 0; i < n_materials; i++) {
 		alb[i] = make_float4(materials[i].albedo[0], materials[i].albedo[1], materials[i].albedo[2], 0.0f);
 		emi[i] = make_float4(materials[i].emission[0], materials[i].emission[1], materials[i].emission[2], 0.0f);
+		ggx[i] = make_float4(materials[i].F0[0], materials[i].F0[1], materials[i].F0[2], materials[i].roughness);   // Closure<GGX> (policy.brdf = 1)
 	}
 	std::memcpy(sky.data(), hdri_rgba, sky.size() * sizeof(float4));
 	std::vector<float> recs;
@@ -677,7 +686,7 @@ int mirt_set_scene(mirt_ctx* c, const mirt_sphere* geometry, const mirt_sphere* 
 	}
 	if ((r = upload(c, c->prim_mat, pm)) ||
 	    (r = upload(c, c->light_sphere, lsp)) || (r = upload(c, c->light_emit, lem)) || (r = upload(c, c->mat_albedo, alb)) ||
-	    (r = upload(c, c->mat_emission, emi)) || (r = upload(c, c->hdri, sky))) return r;
+	    (r = upload(c, c->mat_emission, emi)) || (r = upload(c, c->mat_ggx, ggx)) || (r = upload(c, c->hdri, sky))) return r;
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 
 	SceneDev& s = c->scene;
@@ -732,6 +741,7 @@ int mirt_set_policy(mirt_ctx* c, const mirt_policy* p) {
 	if (!c || !p) return MIRT_ERR_ARG;
 	if (p->max_bounces < 1 || p->max_bounces > 1024) return fail(c, MIRT_ERR_ARG, "max_bounces %u out of range", p->max_bounces);
 	if (p->buckets < 1 || p->buckets > MIRT_MAX_BUCKETS) return fail(c, MIRT_ERR_ARG, "buckets %u out of range 1..%u", p->buckets, MIRT_MAX_BUCKETS);
+	if (p->brdf > 1) return fail(c, MIRT_ERR_ARG, "brdf %u is neither 0 (Lambertian) nor 1 (GGX)", p->brdf);
 	{ const int fr = flush_deferred(c); if (fr) return fr; }
 	HIP_TRY(c, hipSetDevice(c->device));
 	HIP_TRY(c, sync_all(c));
@@ -742,6 +752,16 @@ int mirt_set_policy(mirt_ctx* c, const mirt_policy* p) {
 	c->policy = *p;
 	if (replan) c->planned_for = 0;
 	if (realloc_acc && c->n_tiles) { int r = alloc_accumulator(c); if (r) return r; }
+	return MIRT_OK;
+}
+int mirt_set_gloss_decay(mirt_ctx* c, const float* decay, uint32_t n) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!decay) n = 0;
+	if (n > 1024) return fail(c, MIRT_ERR_ARG, "gloss decay table of %u entries (at most 1024, the max_bounces limit)", n);
+	for (uint32_t i = 0; i < n; i++)
+		if (!(decay[i] >= 0.0f && decay[i] <= 1.0f)) return fail(c, MIRT_ERR_ARG, "gloss decay[%u] = %g is not in [0, 1]", i, static_cast<double>(decay[i]));
+	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render with the table they were issued under
+	c->gloss_decay.assign(decay, decay + n);
 	return MIRT_OK;
 }
 int mirt_get_policy(const mirt_ctx* c, mirt_policy* p) {

@@ -164,6 +164,12 @@ int mirt_group_set_camera(mirt_group* g, const float pos[3], const float orient_
 	if (g->full) FULL_TRY(g, "mirt_set_camera", mirt_set_camera(g->full, pos, orient_xyzw, half_width, half_height, z, exposure));
 	return MIRT_OK;
 }
+int mirt_group_set_gloss_decay(mirt_group* g, const float* decay, uint32_t n) {
+	if (!g) return MIRT_ERR_ARG;
+	FOR_MEMBERS(g, "mirt_set_gloss_decay", mirt_set_gloss_decay(ctx, decay, n));
+	if (g->full) FULL_TRY(g, "mirt_set_gloss_decay", mirt_set_gloss_decay(g->full, decay, n));
+	return MIRT_OK;
+}
 int mirt_group_set_policy(mirt_group* g, const mirt_policy* p) {
 	if (!g || !p) return MIRT_ERR_ARG;
 	FOR_MEMBERS(g, "mirt_set_policy", mirt_set_policy(ctx, p));

@@ -4,8 +4,9 @@
 // format — Radiance .hdr, flipped vertically like Image::Store (Image.cpp:71-74) — or as a PFM (by the extension of --out).  --hdri loads the
 // environment map the way the constructor does (stbi_loadf(..., 4), Application.cpp:225-231); --ambient sets sky.ambient_color, which scales it.
 //
-//   mirt_headless --scene default9|furnace|bvh_test|synthetic:N [--size WxH] [--spp N | --frames N] [--bounces B] [--buckets K] [--brute] [--devices 0,1,..]
-//                 [--hdri env.hdr] [--ambient A] [--out frame.hdr|frame.pfm]
+//   mirt_headless --scene default9|furnace|bvh_test|brdf_test|synthetic:N [--size WxH] [--spp N | --frames N] [--bounces B] [--buckets K] [--brute] [--devices 0,1,..]
+//                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--out frame.hdr|frame.pfm]
+// --brdf 1 renders every hit with the GGX closure (#define BRDF 1, Renderer.hpp:70), --gloss-decay gives its per-bounce table (:212).
 // --devices: the GPUs the one Renderer object uses (tile rows split over them inside the library, one RCCL gather per frame read).
 // --frames N is the UI loop itself (Application.cpp:373-380): N frames of { Accumulate(); Render(); }; the report lists the frames on
 // which Render() produced output (every `buckets`-th, Renderer.hpp:437) and a hash of the last frame shown.
@@ -26,6 +27,14 @@ static Material make_material(float ar, float ag, float ab, float er = 0, float 
 	m.emission[0] = er; m.emission[1] = eg; m.emission[2] = eb;
 	return m;
 }
+// the members only the GGX closure reads (F0, roughness) and those no closure reads (F80, transmission, IOR_minus_one)
+static Material with_ggx(Material m, vec3 F0, vec3 F80, float roughness, vec3 transmission = vec3{ 0, 0, 0 }, float IOR_minus_one = 0.0f) {
+	m.F0[0] = F0.x; m.F0[1] = F0.y; m.F0[2] = F0.z;
+	m.F80[0] = F80.x; m.F80[1] = F80.y; m.F80[2] = F80.z;
+	m.transmission[0] = transmission.x; m.transmission[1] = transmission.y; m.transmission[2] = transmission.z;
+	m.roughness = roughness; m.IOR_minus_one = IOR_minus_one;
+	return m;
+}
 static Sphere make_sphere(float x, float y, float z, float radius_sq, int32_t mat) {
 	Sphere s{};
 	s.position[0] = x; s.position[1] = y; s.position[2] = z; s.radius_sq = radius_sq; s.material_ID = mat;
@@ -35,14 +44,37 @@ static Sphere make_sphere(float x, float y, float z, float radius_sq, int32_t ma
 // Scenes::Default, Application.cpp:33-101
 static void scene_default9(Scene& sc) {
 	sc.camera = Camera{ vec3{ -0.2f, 0.3f, 1.0f }, vec3{ 0.1f, -0.4f, -1.0f }, 40.0f, 1.0f };
+	const vec3 none{ 0, 0, 0 };
 	sc.material = {
-		make_material(1, 1, 1), make_material(1, 1, 1, 0.1f * 25.0f, 0.1f * 25.0f, 0.1f * 200.0f), make_material(1, 1, 1, 0.1f * 150.0f, 0.1f * 150.0f, 0.1f * 150.0f),
-		make_material(1, 1, 1, 200.0f, 17.0f, 25.0f), make_material(0.793f, 0.793f, 0.664f), make_material(0.05f, 0.05f, 0.05f),
-		make_material(1, 1, 1), make_material(1, 1, 1), make_material(1, 1, 1) };
+		with_ggx(make_material(1, 1, 1), vec3{ 0.8f, 0.8f, 0.8f }, vec3{ 0.9f, 0.9f, 0.9f }, 0.2f),
+		with_ggx(make_material(1, 1, 1, 0.1f * 25.0f, 0.1f * 25.0f, 0.1f * 200.0f), none, none, 1.0f),
+		with_ggx(make_material(1, 1, 1, 0.1f * 150.0f, 0.1f * 150.0f, 0.1f * 150.0f), none, none, 1.0f),
+		with_ggx(make_material(1, 1, 1, 200.0f, 17.0f, 25.0f), none, none, 1.0f),
+		with_ggx(make_material(0.793f, 0.793f, 0.664f), vec3{ 0.04f, 0.04f, 0.04f }, vec3{ 0.5f, 0.5f, 0.5f }, 0.85f),
+		with_ggx(make_material(0.05f, 0.05f, 0.05f), vec3{ 0.03f, 0.03f, 0.03f }, vec3{ 0.5f, 0.5f, 0.5f }, 0.05f, vec3{ 0.95f, 0.95f, 0.95f }, 0.44f),
+		with_ggx(make_material(1, 1, 1), vec3{ 0.944f, 0.776f, 0.373f }, vec3{ 0.8f, 0.8f, 0.6f }, 0.15f),
+		with_ggx(make_material(1, 1, 1), vec3{ 0.076288f, 0.077375f, 0.078887f }, vec3{ 0.47990f, 0.48028f, 0.48080f }, 0.1f, vec3{ 0.670f, 0.764f, 0.855f }, 0.762f),
+		with_ggx(make_material(1, 1, 1), vec3{ 0.04f, 0.04f, 0.04f }, vec3{ 0.5f, 0.5f, 0.5f }, 0.8f) };
 	sc.geometry = {
 		make_sphere(0.3f, -1.47f, 0.0f, 1.5f * 1.5f, 0), make_sphere(0.29999f, 0.0801f, 0.0f, 0.05f * 0.05f, 1), make_sphere(0.3302f, 0.36165f, 0.7119f, 0.05f * 0.05f, 2),
 		make_sphere(-0.4857f, -0.0242f, -0.41383f, 0.05f * 0.05f, 3), make_sphere(0.3f, 1.7f, 0.0f, 1.5f * 1.5f, 4), make_sphere(0.018f, 0.022f, 0.07f, 0.02f * 0.02f, 5),
 		make_sphere(-0.037f, 0.022f, 0.0f, 0.03f * 0.03f, 6), make_sphere(-0.0846f, -0.0334f, 0.283f, 0.012f * 0.012f, 7), make_sphere(0.03863f, -0.00788f, 0.2835f, 0.012f * 0.012f, 8) };
+}
+// Scenes::BRDF_test, Application.cpp:123-217, the Properties::Roughness case the reference hard-codes (scene.py brdf_test)
+static void scene_brdf_test(Scene& sc) {
+	const int32_t gradations = 10;
+	const float cam_offset = static_cast<float>(gradations) * 2.8f;
+	sc.camera = Camera{ vec3{ 0, 0, cam_offset }, vec3{ 0, 0, -1 } };
+	Material floor = make_material(0.1f, 0.1f, 0.1f); floor.roughness = 1.0f;
+	sc.material = { floor, make_material(0, 0, 0, 100.0f, 100.0f, 100.0f) };
+	sc.geometry = { make_sphere(0.0f, -1001.0f, 0.0f, 1000.0f * 1000.0f, 0), make_sphere(0.0f, 10.0f, 0.0f, 5.0f, 1) };
+	for (int32_t i = 0; i < gradations; i++) {
+		const float t = static_cast<float>(i) / static_cast<float>(gradations - 1);
+		const float x = static_cast<float>(i * 2 - gradations) * 1.25f + 1.0f;
+		sc.material.push_back(with_ggx(make_material(0, 0, 0), vec3{ 1, 1, 1 }, vec3{ 1, 1, 1 }, t));
+		sc.geometry.push_back(make_sphere(x, static_cast<float>(i) * 0.1f, 0.0f, 1.0f, static_cast<int32_t>(sc.material.size()) - 1));
+	}
+	sc.sky.ambient_color[0] = sc.sky.ambient_color[1] = sc.sky.ambient_color[2] = 1.0f;
 }
 // Scenes::White_Furnace, Application.cpp:218-223
 static void scene_furnace(Scene& sc) {
@@ -122,6 +154,7 @@ int main(int argc, char** argv) {
 	float ambient = 0.0f;
 	bool ambient_set = false;
 	std::vector<int> devices = { 0 };
+	std::vector<float> gloss_decay;
 	if (argc == 4 && std::string(argv[1]) == "--convert-hdr") {
 		// file-format check without a GPU: read a picture like stbi_loadf does (top-down) and store it again like Image::Store does (which
 		// flips, so the rows are handed over bottom-up): the output decodes to the same texels
@@ -143,6 +176,8 @@ int main(int argc, char** argv) {
 		else if (a == "--ambient") { ambient = static_cast<float>(std::atof(next())); ambient_set = true; }
 		else if (a == "--hdri") hdri = next();
 		else if (a == "--brute") policy.use_bvh = false;
+		else if (a == "--brdf") policy.brdf = static_cast<uint32_t>(std::atoi(next()));
+		else if (a == "--gloss-decay") { for (const char* p = next(); *p;) { gloss_decay.push_back(static_cast<float>(std::atof(p))); while (*p && *p != ',') p++; if (*p == ',') p++; } }
 		else if (a == "--out") out = next();
 		else if (a == "--devices") { devices.clear(); for (const char* p = next(); *p;) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p == ',') p++; } if (devices.empty()) return 2; }
 		else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -151,6 +186,7 @@ int main(int argc, char** argv) {
 		Scene scene;
 		if (scene_name == "default9") scene_default9(scene);
 		else if (scene_name == "furnace") scene_furnace(scene);
+		else if (scene_name == "brdf_test") scene_brdf_test(scene);
 		else if (scene_name == "bvh_test") scene_bvh_test(scene);
 		else if (scene_name.rfind("synthetic:", 0) == 0) { n = static_cast<uint32_t>(std::atoi(scene_name.c_str() + 10)); if (n < 2) return 2; scene_synthetic(scene, n, ambient); }
 		else { std::fprintf(stderr, "unknown scene %s\n", scene_name.c_str()); return 2; }
@@ -162,6 +198,7 @@ int main(int argc, char** argv) {
 		scene.RebuildAcceleration();                                   // Application.cpp:233-234
 
 		Renderer renderer{ scene, policy, devices };
+		renderer.SetGlossDecay(gloss_decay);
 		// pad the viewport to the tile requirement like UIRender does (Application.cpp:365-372)
 		const uint32_t t = static_cast<uint32_t>(Renderer::RequiredTiling());
 		w = (w + t - 1) & ~(t - 1); h = (h + t - 1) & ~(t - 1);

@@ -116,6 +116,7 @@ struct RendererPolicy {                                                    // Re
 	bool use_bvh = true;                                                   // reference ships USEBVH false (BVH.hpp:307); results are identical
 	bool reference_tree = false;                                           // true: traverse scene.acceleration_structure.nodes as is instead of the internal SAH tree
 	bool gpu_build = false;                                                // true: internal tree built on the GPU (LBVH) at SceneChanged(): faster rebuild, slower rays
+	uint32_t brdf = 0;                                                     // #define BRDF, Renderer.hpp:70: 0 = Lambertian, 1 = GGX (F0, roughness; SetGlossDecay)
 };
 
 class Renderer {
@@ -126,8 +127,9 @@ public:
 	// ordinals; the library splits the tile rows over them and gathers the accumulator with one RCCL exchange (mirt.h, mirt_group_*).
 	explicit Renderer(const Scene& scene_ref, RendererPolicy policy = {}, std::vector<int> devices = { 0 }) : scene(scene_ref) {
 		if (mirt_group_create(devices.data(), static_cast<int>(devices.size()), &group_) != MIRT_OK) throw std::runtime_error(std::string("mirt_group_create: ") + mirt_group_last_error(nullptr));
-		mirt_policy p{};
+		mirt_policy& p = policy_;
 		p.max_bounces = policy.max_bounces; p.buckets = policy.buckets; p.mis = policy.mis; p.use_bvh = policy.use_bvh; p.reference_tree = policy.reference_tree; p.gpu_build = policy.gpu_build;
+		p.brdf = policy.brdf;
 		if (mirt_group_set_policy(group_, &p) < 0) {                           // no destructor runs for a constructor that throws: release the group here
 			const std::string why = std::string("mirt_group_set_policy: ") + mirt_group_last_error(group_);
 			mirt_group_destroy(group_); group_ = nullptr;
@@ -159,6 +161,15 @@ public:
 		check(mirt_group_resize(group_, width, height), "mirt_group_resize");
 	}
 	void ResetAccumulator() { check(mirt_group_reset(group_), "mirt_group_reset"); }    // Renderer.hpp:64-67
+	// The closure the reference picks with #define BRDF (Renderer.hpp:70) and its gloss_decay_table (:212), switchable at run time.
+	void SetBRDF(uint32_t brdf) {
+		mirt_policy p = policy_; p.brdf = brdf;
+		check(mirt_group_set_policy(group_, &p), "mirt_group_set_policy");
+		policy_ = p;
+	}
+	void SetGlossDecay(const std::vector<float>& decay) {
+		check(mirt_group_set_gloss_decay(group_, decay.data(), static_cast<uint32_t>(decay.size())), "mirt_group_set_gloss_decay");
+	}
 	// Renderer.hpp:73-434.  Asynchronous: Render() / counters() / the destructor wait for the GPUs; called once per frame the library
 	// still batches the frames between two Render()s that are due (mirt.h, mirt_accumulate_async).
 	void Accumulate(uint32_t n_calls = 1) { check(mirt_group_accumulate_async(group_, n_calls), "mirt_group_accumulate_async"); }
@@ -189,6 +200,7 @@ private:
 		if (rc < 0) throw std::runtime_error(std::string(what) + ": " + mirt_group_last_error(group_));
 	}
 	mirt_group* group_ = nullptr;
+	mirt_policy policy_{};
 };
 
 } // namespace mirt

@@ -129,26 +129,35 @@ def _sphere(pos, radius_sq, mat):
     return s
 
 
-def _material(albedo=(0, 0, 0), emission=(0, 0, 0)):
+def _material(albedo=(0, 0, 0), emission=(0, 0, 0), F0=(0, 0, 0), F80=(0, 0, 0), roughness=0.0, transmission=(0, 0, 0), IOR_minus_one=0.0):
+    """Material{} (Primitives.hpp:18-27, every member zero) with the given members set."""
     m = np.zeros((), dtype=MATERIAL)
     m["albedo"] = np.asarray(albedo, dtype=f32)
     m["emission"] = np.asarray(emission, dtype=f32)
+    m["F0"] = np.asarray(F0, dtype=f32)
+    m["F80"] = np.asarray(F80, dtype=f32)
+    m["roughness"] = f32(roughness)
+    m["transmission"] = np.asarray(transmission, dtype=f32)
+    m["IOR_minus_one"] = f32(IOR_minus_one)
     return m
 
 
 def default9() -> Scene:
-    """Scenes::Default, Application.cpp:33-101 (9 spheres / 9 materials, 3 emissive, ambient 0)."""
+    """Scenes::Default, Application.cpp:33-101 (9 spheres / 9 materials, 3 emissive, ambient 0), every material member as authored
+    (the Lambertian path reads albedo and emission; brdf = 1 reads F0, roughness and emission)."""
     f = f32
     mats = [
-        _material(albedo=(1, 1, 1)),
-        _material(albedo=(1, 1, 1), emission=f(0.1) * np.array([25.0, 25.0, 200.0], dtype=f32)),
-        _material(albedo=(1, 1, 1), emission=f(0.1) * np.array([150.0, 150.0, 150.0], dtype=f32)),
-        _material(albedo=(1, 1, 1), emission=(200.0, 17.0, 25.0)),
-        _material(albedo=(0.793, 0.793, 0.664)),
-        _material(albedo=(0.05, 0.05, 0.05)),
-        _material(albedo=(1, 1, 1)),
-        _material(albedo=(1, 1, 1)),
-        _material(albedo=(1, 1, 1)),
+        _material(albedo=(1, 1, 1), F0=(0.8, 0.8, 0.8), F80=(0.9, 0.9, 0.9), roughness=0.2),
+        _material(albedo=(1, 1, 1), emission=f(0.1) * np.array([25.0, 25.0, 200.0], dtype=f32), roughness=1.0),
+        _material(albedo=(1, 1, 1), emission=f(0.1) * np.array([150.0, 150.0, 150.0], dtype=f32), roughness=1.0),
+        _material(albedo=(1, 1, 1), emission=(200.0, 17.0, 25.0), roughness=1.0),
+        _material(albedo=(0.793, 0.793, 0.664), F0=(0.04, 0.04, 0.04), F80=(0.5, 0.5, 0.5), roughness=0.85),
+        _material(albedo=(0.05, 0.05, 0.05), F0=(0.03, 0.03, 0.03), F80=(0.5, 0.5, 0.5), transmission=(0.95, 0.95, 0.95), IOR_minus_one=0.44,
+                  roughness=0.05),
+        _material(albedo=(1, 1, 1), F0=(0.944, 0.776, 0.373), F80=(0.8, 0.8, 0.6), roughness=0.15),
+        _material(albedo=(1, 1, 1), F0=(0.076288, 0.077375, 0.078887), F80=(0.47990, 0.48028, 0.48080), transmission=(0.670, 0.764, 0.855),
+                  IOR_minus_one=0.762, roughness=0.1),
+        _material(albedo=(1, 1, 1), F0=(0.04, 0.04, 0.04), F80=(0.5, 0.5, 0.5), roughness=0.8),
     ]
     geo = [
         _sphere((0.3, -1.47, 0.0), f(1.5) * f(1.5), 0),
@@ -171,6 +180,26 @@ def white_furnace() -> Scene:
     cam = Camera(eye=(0, 0, 3), direction=(0, 0, -1), focal_length=50.0, exposure=1.0)
     return Scene(np.array([_sphere((0, 0, 0), 1.0, 0)], dtype=SPHERE), np.array([_material(albedo=(1, 1, 1))], dtype=MATERIAL),
                  cam, np.ones(3, dtype=f32), name="white_furnace")
+
+
+def brdf_test() -> Scene:
+    """Scenes::BRDF_test, Application.cpp:123-217, with the Properties::Roughness case the reference hard-codes: a floor, one light and
+    ten metallic spheres (F0 = F80 = 1, albedo 0) whose roughness runs from 0 to 1.  Meant for policy.brdf = 1; under the Lambertian
+    path the spheres are black."""
+    f = f32
+    gradations = 10
+    cam_offset = f(gradations) * f(2.8)
+    mats = [_material(albedo=(0.1, 0.1, 0.1), roughness=1.0),                                   # floor
+            _material(emission=(100.0, 100.0, 100.0))]                                          # light
+    geo = [_sphere((0.0, -1001.0, 0.0), f(1000.0) * f(1000.0), 0),
+           _sphere((0.0, 10.0, 0.0), 5.0, 1)]
+    for i in range(gradations):
+        t = f(i) / f(gradations - 1)
+        x = f(i * 2 - gradations) * f(1.25) + f(1.0)
+        mats.append(_material(albedo=(0, 0, 0), F0=(1, 1, 1), F80=(1, 1, 1), roughness=t))
+        geo.append(_sphere((x, f(i) * f(0.1), 0.0), 1.0, len(mats) - 1))
+    cam = Camera(eye=(0.0, 0.0, cam_offset), direction=(0.0, 0.0, -1.0))
+    return Scene(np.array(geo, dtype=SPHERE), np.array(mats, dtype=MATERIAL), cam, np.ones(3, dtype=f32), name="brdf_test")
 
 
 def pcg_stream(state: int):

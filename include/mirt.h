@@ -45,7 +45,8 @@ typedef struct mirt_sphere {
 	int32_t _pad[3];
 } mirt_sphere;
 
-/* Primitives.hpp:18-27 — alignas(32), 96 B; the path reads albedo and emission only */
+/* Primitives.hpp:18-27 — alignas(32), 96 B.  The path reads albedo and emission with policy.brdf = 0 (Lambertian), F0, roughness
+ * and emission with policy.brdf = 1 (GGX); F80, transmission and IOR_minus_one are read by no closure of the reference. */
 typedef struct mirt_material {
 	float albedo[3];
 	float F0[3];
@@ -90,7 +91,10 @@ typedef struct mirt_policy {
 	uint32_t trace_primary_rays; /* 0 (default): within a batch, the camera rays of a pixel (one jittered sample per accumulation of the batch, up to 256) share ONE cone traversal that lists the
 	                         * spheres they can hit; each sample then tests only those, with the reference's arithmetic.  1: every primary ray walks the
 	                         * tree by itself (measurements; the traversal-twin counter checks).  Results are identical either way. */
-	uint32_t _reserved[1];
+	uint32_t brdf;          /* #define BRDF, Renderer.hpp:70: 0 (default) = Closure<LambertianDiffuse>, 1 = Closure<GGX> for every hit
+	                         * (DataStreams.hpp:184-219) with alpha = roughness^2 + (1 - roughness^2) * gloss decay of the bounce
+	                         * (mirt_set_gloss_decay).  Its pdf() is 0 as in the reference: lights are reached by next-event estimation
+	                         * only (an emitter hit by a sampled ray weighs powerHeuristic(0, .) = 0).  Other values: MIRT_ERR_ARG. */
 } mirt_policy;
 
 typedef struct mirt_counters {
@@ -145,6 +149,10 @@ int mirt_set_camera(mirt_ctx* ctx, const float pos[3], const float orient_xyzw[4
 
 int mirt_set_policy(mirt_ctx* ctx, const mirt_policy* policy);
 int mirt_get_policy(const mirt_ctx* ctx, mirt_policy* policy);   /* with the values in effect for max_batch / streams left at 0 */
+/* gloss_decay_table of Renderer.hpp:212 (policy.brdf = 1): decay[b] is mixed into the GGX alpha of the hits of bounce b; bounces at
+ * or beyond n use 0.  n <= 1024; every value finite and in [0, 1], else MIRT_ERR_ARG.  decay = NULL or n = 0: all zeros (the
+ * default).  Deferred mirt_accumulate_async calls are launched first, with the table they were issued under. */
+int mirt_set_gloss_decay(mirt_ctx* ctx, const float* decay, uint32_t n);
 
 /* Renderer::Resize, Renderer.hpp:53-63: h_tiles = w/16, v_tiles = h/16 (truncating), allocates and zeroes
  * the accumulator, accumulations = 0.  Owns all tiles until mirt_set_tile_range says otherwise. */
@@ -217,6 +225,7 @@ int mirt_group_set_scene(mirt_group* group,
                          const float ambient_color[3], const float* hdri_rgba, uint32_t hdri_w, uint32_t hdri_h);
 int mirt_group_set_camera(mirt_group* group, const float pos[3], const float orient_xyzw[4], float half_width, float half_height, float z, float exposure);
 int mirt_group_set_policy(mirt_group* group, const mirt_policy* policy);
+int mirt_group_set_gloss_decay(mirt_group* group, const float* decay, uint32_t n);
 int mirt_group_resize(mirt_group* group, uint32_t width, uint32_t height);      /* Renderer::Resize + the tile-row split */
 int mirt_group_reset(mirt_group* group);                                         /* Renderer::ResetAccumulator */
 int mirt_group_accumulate(mirt_group* group, uint32_t n_calls);                  /* n x Renderer::Accumulate on every device, then waits */
