@@ -30,6 +30,12 @@
 //                              Mode 1 is NOT equivalent to mode 0 (Q17 + order dependence of the
 //                              stream traversal) and is kept as the reference's own alternative
 //                              path for the CPU baseline and to quantify that discrepancy.
+//
+// Closure (orc_set_brdf): the reference's compile-time `#define BRDF` (Renderer.hpp:70) as oracle state.
+//   0  Closure<LambertianDiffuse> — the reference as shipped (DataStreams.hpp:164-182)
+//   1  Closure<GGX>               — DataStreams.hpp:184-219, with the gloss decay table Renderer.hpp:212 names
+//                                   but never declares supplied by the caller
+// Both are one accumulate_tile body, instantiated once per closure.
 #include <cstdint>
 #include <cstring>
 #include <cstdlib>
@@ -532,8 +538,10 @@ struct alignas(64) RayStream {
 	Hit hit;
 	ShadowStream shadow_rays;
 };
-struct ShaderData {                                                                 // :142-157 (closure: albedo only)
-	float albedo[N][3];
+struct ShaderData {                                                                 // :142-157; closure[ID] of either type, DataStreams.hpp:164-219
+	float albedo[N][3];                                                             // Closure<LambertianDiffuse>
+	float F0[N][3];                                                                 // Closure<GGX>
+	float alpha[N];
 	struct { float x[N], y[N], z[N]; } P, V;
 	struct { float x[N], y[N], z[N], w[N]; } T;
 	Bitset256 is_emissive;
@@ -1027,6 +1035,8 @@ struct Oracle {
 	int mis = 1;                          // Renderer.hpp:71
 	int trav_mode = 0;
 	int threads = 0;
+	int brdf = 0;                         // Renderer.hpp:70 `#define BRDF`: 0 Closure<LambertianDiffuse>, 1 Closure<GGX>
+	std::vector<float> gloss_decay;       // gloss_decay_table by bounce (named at Renderer.hpp:212, never declared); entries beyond its length are 0
 	std::vector<float> accumulator;       // [tile][bucket][channel][256]  (Renderer.hpp:43-46)
 	std::vector<uint32_t> tile_list;      // orc_set_tile_list: only these LaunchIndices are rendered (full-size spot checks); slab j = tile_list[j]
 	Counters counters;
@@ -1086,8 +1096,9 @@ static size_t sort_rayID(uint32_t k, uint32_t count, uint32_t* out, const int32_
 struct PathDebug { bool on = false; uint32_t px = 0; int n = 0; float rec[64][8]; };
 static thread_local PathDebug g_dbg;
 
-// Renderer.hpp:83-432 — one tile, one Accumulate() call
-static void accumulate_tile(const Oracle& o, uint32_t LaunchIndex, size_t slab, uint32_t accumulations, float* accumulator, LocalCounters& lc) {
+// Renderer.hpp:83-432 — one tile, one Accumulate() call, with the closure the reference selects at compile time (Renderer.hpp:70)
+template <bool GGX>
+static void accumulate_tile_closure(const Oracle& o, uint32_t LaunchIndex, size_t slab, uint32_t accumulations, float* accumulator, LocalCounters& lc) {
 	const uint32_t light_count = static_cast<uint32_t>(o.lights.size());
 	const float light_selection_pdf = 1.0f / static_cast<float>(o.lights.size());
 	const bool has_ambient = std_max(o.sky.ambient[0], std_max(o.sky.ambient[1], o.sky.ambient[2])) > 0.0f;
@@ -1136,6 +1147,7 @@ static void accumulate_tile(const Oracle& o, uint32_t LaunchIndex, size_t slab, 
 			r[0] = in->p.x[ID]; r[1] = in->p.y[ID]; r[2] = in->p.z[ID]; r[3] = in->dir.x[ID]; r[4] = in->dir.y[ID]; r[5] = in->dir.z[ID];
 			r[6] = ray_stream.hit.tfar[ID]; r[7] = static_cast<float>(ray_stream.hit.primID[ID]);
 		}
+		const float decay = bounce < o.gloss_decay.size() ? o.gloss_decay[bounce] : 0.0f;
 
 		for (size_t ID = 0; ID < active_rays; ID++) {                           // :169-214 closest-hit shader
 			const int32_t mat_ID = ray_stream.hit.matID[ID];
@@ -1157,7 +1169,13 @@ static void accumulate_tile(const Oracle& o, uint32_t LaunchIndex, size_t slab, 
 			sd.T.x[ID] = T.x; sd.T.y[ID] = T.y; sd.T.z[ID] = T.z; sd.T.w[ID] = T.w;
 			const Material& m = o.material[mat_ID];
 			if (std_max(m.emission[0], std_max(m.emission[1], m.emission[2])) > FLT_EPSILON) sd.is_emissive.set(ID);
-			sd.albedo[ID][0] = m.albedo[0]; sd.albedo[ID][1] = m.albedo[1]; sd.albedo[ID][2] = m.albedo[2];
+			if (GGX) {                                                           // :209-212
+				sd.F0[ID][0] = m.F0[0]; sd.F0[ID][1] = m.F0[1]; sd.F0[ID][2] = m.F0[2];
+				float alpha = m.roughness; alpha *= alpha;
+				sd.alpha[ID] = alpha + (1.0f - alpha) * decay;
+			} else {                                                             // :207-208
+				sd.albedo[ID][0] = m.albedo[0]; sd.albedo[ID][1] = m.albedo[1]; sd.albedo[ID][2] = m.albedo[2];
+			}
 		}
 		const size_t miss_count = sort_rayID(static_cast<uint32_t>(o.material.size()), static_cast<uint32_t>(active_rays),
 		                                     ray_stream.RayID, ray_stream.hit.matID, sort_buffer);   // :235-241
@@ -1195,13 +1213,18 @@ static void accumulate_tile(const Oracle& o, uint32_t LaunchIndex, size_t slab, 
 				if (Llocal.z < 0.0f) continue;
 				const Material& lm = o.material[light_prim.material_ID];
 				v3 radiance{ lm.emission[0] * in->throughput.r[ID], lm.emission[1] * in->throughput.g[ID], lm.emission[2] * in->throughput.b[ID] };
-				{   // Closure<Lambertian>::eval — DataStreams.hpp:169-172
+				float brdf_pdf;
+				if (GGX) {                                                       // Closure<GGX>::eval / pdf, DataStreams.hpp:189-198
+					const v3 f = ggx_eval(v3{ sd.F0[ID][0], sd.F0[ID][1], sd.F0[ID][2] }, sd.alpha[ID], Llocal, v3{ sd.V.x[ID], sd.V.y[ID], sd.V.z[ID] });
+					radiance.x *= f.x; radiance.y *= f.y; radiance.z *= f.z;
+					brdf_pdf = 0.0f;                                             // "TODO" in the reference
+				} else {                                                         // Closure<Lambertian>::eval / pdf, DataStreams.hpp:169-176
 					float NdotL = std_max(0.0f, Llocal.z);
 					float f = kOneOverPi * NdotL;
 					radiance.x *= sd.albedo[ID][0] * f; radiance.y *= sd.albedo[ID][1] * f; radiance.z *= sd.albedo[ID][2] * f;
+					brdf_pdf = kOneOverPi * std_max(0.0f, Llocal.z);
 				}
 				light_pdf *= light_selection_pdf;
-				float brdf_pdf = kOneOverPi * std_max(0.0f, Llocal.z);            // DataStreams.hpp:173-176
 				float w = powerHeuristic_over_f(light_pdf, brdf_pdf);
 				radiance.x *= w; radiance.y *= w; radiance.z *= w;
 				if (std_max(std_max(radiance.x, radiance.y), radiance.z) <= 0.0f) continue;
@@ -1225,7 +1248,7 @@ static void accumulate_tile(const Oracle& o, uint32_t LaunchIndex, size_t slab, 
 				}
 			}
 		}
-		if (MIS && bounce > 0) {                                                 // :319-343
+		if (MIS && bounce > 0) {                                                 // :319-343 (in->pdf: the previous bounce's closure pdf)
 			for (size_t ID = 0; ID < active_rays; ID++) {
 				if (!sd.is_emissive.test(ID)) continue;
 				v3 throughput{ in->throughput.r[ID], in->throughput.g[ID], in->throughput.b[ID] };
@@ -1254,8 +1277,14 @@ static void accumulate_tile(const Oracle& o, uint32_t LaunchIndex, size_t slab, 
 				const int32_t ID = static_cast<int32_t>(ray_stream.RayID[miss_count + i]);
 				uint32_t rng_state = hash_2d(accumulations, ray_stream.seed[in->pixelID[ID]] + static_cast<uint32_t>(bounce) * 2 + 1);
 				float bs[2]; bs[0] = rand_unit_float(&rng_state); bs[1] = rand_unit_float(&rng_state);
-				v3 sdir = hemisphere(bs[0], bs[1]);                              // DataStreams.hpp:177-181
-				v3 throughput{ in->throughput.r[ID] * sd.albedo[ID][0], in->throughput.g[ID] * sd.albedo[ID][1], in->throughput.b[ID] * sd.albedo[ID][2] };
+				v3 sdir, estimator;
+				if (GGX) {                                                       // Closure<GGX>::sample, DataStreams.hpp:200-218
+					ggx_sample(v3{ sd.F0[ID][0], sd.F0[ID][1], sd.F0[ID][2] }, sd.alpha[ID], v3{ sd.V.x[ID], sd.V.y[ID], sd.V.z[ID] }, bs[0], bs[1], &sdir, &estimator);
+				} else {                                                         // DataStreams.hpp:177-181
+					sdir = hemisphere(bs[0], bs[1]);
+					estimator = v3{ sd.albedo[ID][0], sd.albedo[ID][1], sd.albedo[ID][2] };
+				}
+				v3 throughput{ in->throughput.r[ID] * estimator.x, in->throughput.g[ID] * estimator.y, in->throughput.b[ID] * estimator.z };
 				{
 					float q = 1.0f - std_max(throughput.x, std_max(throughput.y, throughput.z));
 					if (rand_unit_float(&rng_state) < q) { ray_stream.termination.set(ID); continue; }
@@ -1269,7 +1298,8 @@ static void accumulate_tile(const Oracle& o, uint32_t LaunchIndex, size_t slab, 
 				outb->throughput.r[output_index] = throughput.x; outb->throughput.g[output_index] = throughput.y; outb->throughput.b[output_index] = throughput.z;
 				outb->radiance.r[output_index] = in->radiance.r[ID]; outb->radiance.g[output_index] = in->radiance.g[ID]; outb->radiance.b[output_index] = in->radiance.b[ID];
 				outb->pixelID[output_index] = in->pixelID[ID];
-				outb->pdf[output_index] = kOneOverPi * std_max(0.0f, sdir.z);     // Q8: pdf of the WORLD-space dir
+				// :401 — Closure<GGX>::pdf = 0 ("TODO", DataStreams.hpp:196-198); Lambertian: Q8, pdf of the WORLD-space dir
+				outb->pdf[output_index] = GGX ? 0.0f : kOneOverPi * std_max(0.0f, sdir.z);
 				output_index++;
 			}
 		}
@@ -1293,6 +1323,12 @@ static void accumulate_tile(const Oracle& o, uint32_t LaunchIndex, size_t slab, 
 		}
 		active_rays = output_index;                                              // :431
 	}
+}
+
+// The reference's `#define BRDF` as oracle state: accumulate() and orc_debug_path both come through here.
+static void accumulate_tile(const Oracle& o, uint32_t LaunchIndex, size_t slab, uint32_t accumulations, float* accumulator, LocalCounters& lc) {
+	if (o.brdf == 1) accumulate_tile_closure<true>(o, LaunchIndex, slab, accumulations, accumulator, lc);
+	else accumulate_tile_closure<false>(o, LaunchIndex, slab, accumulations, accumulator, lc);
 }
 
 static void flush(Counters& c, const LocalCounters& lc) {
@@ -1457,6 +1493,14 @@ void orc_reset(void* h) {                                                       
 	std::fill(o.accumulator.begin(), o.accumulator.end(), 0.0f);
 	o.counters.rays = 0; o.counters.shadow_rays = 0; o.counters.nodes = 0; o.counters.spheres = 0;
 	o.counters.shadow_nodes = 0; o.counters.shadow_spheres = 0; o.counters.terminated = 0;
+}
+// The closure of every later Accumulate() (0 Lambertian, 1 GGX) and its gloss decay table decay[0..n); the accumulator is left alone.
+int orc_set_brdf(void* h, int brdf, const float* decay, uint32_t n) {
+	if (brdf != 0 && brdf != 1) return -1;
+	Oracle& o = *static_cast<Oracle*>(h);
+	o.brdf = brdf;
+	if (decay && n) o.gloss_decay.assign(decay, decay + n); else o.gloss_decay.clear();
+	return 0;
 }
 void orc_accumulate(void* h, uint32_t n_calls) { Oracle& o = *static_cast<Oracle*>(h); for (uint32_t i = 0; i < n_calls; i++) accumulate(o); }
 uint32_t orc_accumulations(void* h) { return static_cast<Oracle*>(h)->accumulations; }

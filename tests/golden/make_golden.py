@@ -21,8 +21,8 @@ import oracle_binding as ob  # noqa: E402
 mirt_scene = importlib.import_module("cpu-raytracing-experiments_amd.scene")
 
 
-def render_case(scene, w, h, spp, max_bounces, buckets=5, mis=True, trav=ob.TRAV_BRUTE):
-    o = ob.Oracle(scene, max_bounces=max_bounces, buckets=buckets, mis=mis, trav_mode=trav, threads=1)
+def render_case(scene, w, h, spp, max_bounces, buckets=5, mis=True, trav=ob.TRAV_BRUTE, brdf=0, gloss_decay=None):
+    o = ob.Oracle(scene, max_bounces=max_bounces, buckets=buckets, mis=mis, trav_mode=trav, threads=1, brdf=brdf, gloss_decay=gloss_decay)
     o.Resize(w, h)
     o.Accumulate(spp)
     img = o.Render()
@@ -54,6 +54,10 @@ def main():
         "S8_cfg1_64x64_1spp_b2": render_case(mirt_scene.synthetic(8, ambient=0.5), 64, 64, 1, 2),
         "S1000_64x64_5spp_b5": render_case(mirt_scene.synthetic(1000, ambient=0.5), 64, 64, 5, 5),
         "S1000_48x32_16buckets_16spp_b3": render_case(mirt_scene.synthetic(1000, ambient=0.0), 48, 32, 16, 3, buckets=16),
+        # Closure<GGX>: first recorded from the separate copy of the tile loop that carried it before it moved into oracle.cpp
+        "ggx_brdf_test_64x32_10spp_b16_decay": render_case(mirt_scene.brdf_test(), 64, 32, 10, 16, brdf=1, gloss_decay=[0.0, 0.1, 0.3, 0.6, 1.0]),
+        "ggx_default9_64x64_5spp_b16": render_case(mirt_scene.default9(), 64, 64, 5, 16, brdf=1),
+        "ggx_brdf_test_64x32_5spp_b6_nomis": render_case(mirt_scene.brdf_test(), 64, 32, 5, 6, mis=False, brdf=1, gloss_decay=[0.0, 0.5]),
     }
     for name, d in cases.items():
         np.savez_compressed(os.path.join(HERE, name + ".npz"), **d)

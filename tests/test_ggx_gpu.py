@@ -1,5 +1,5 @@
-"""policy.brdf = 1 (Closure<GGX>, the reference's `#define BRDF 1`) on the GPU, bit for bit against the CPU twin
-(tests/native/ggx_twin.cpp, itself checked against the oracle in test_ggx_cpu.py)."""
+"""policy.brdf = 1 (Closure<GGX>, the reference's `#define BRDF 1`) on the GPU, bit for bit against the oracle's GGX closure
+(`ob.Oracle(brdf=1)` in its mode-2 traversal, the CPU twin of the HIP kernels'; itself pinned in test_ggx_cpu.py)."""
 import json
 import os
 import subprocess
@@ -7,20 +7,13 @@ import subprocess
 import numpy as np
 import pytest
 
-import ggx_binding as gb
 import oracle_binding as ob
-from test_ggx_cpu import bits, ggx_twin, mirror_furnace   # noqa: F401  (ggx_twin: session fixture)
+from oracle_binding import bits, fnv1a
+from test_ggx_cpu import mirror_furnace
 
 pytestmark = pytest.mark.gpu
 
 DECAY = [0.0, 0.1, 0.3, 0.6, 1.0]
-
-
-def _fnv1a(a):
-    h = 1469598103934665603
-    for b in np.ascontiguousarray(a, dtype=np.float32).view(np.uint8).ravel().tolist():
-        h = ((h ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return f"{h:016x}"
 
 
 def assert_same(got, want, what):
@@ -31,7 +24,7 @@ def assert_same(got, want, what):
 
 
 def twin(sc, w, h, spp, brdf=1, decay=None, mb=16, mis=True, tiles=None):
-    t = gb.GgxTwin(sc, brdf=brdf, gloss_decay=decay, max_bounces=mb, mis=mis, trav_mode=ob.TRAV_PER_RAY_BVH)
+    t = ob.Oracle(sc, brdf=brdf, gloss_decay=decay, max_bounces=mb, mis=mis, trav_mode=ob.TRAV_PER_RAY_BVH)
     t.Resize(w, h, tiles=tiles)
     t.Accumulate(spp)
     return t
@@ -56,7 +49,7 @@ def test_mirror_furnace_on_the_gpu(mirt, use_bvh):
 @pytest.mark.parametrize("decay", [None, DECAY], ids=["decay0", "decay"])
 @pytest.mark.parametrize("mis", [True, False], ids=["mis", "nomis"])
 @pytest.mark.parametrize("scene_name,w,h", [("brdf_test", 160, 96), ("default9", 64, 64)])
-def test_ggx_matches_twin(mirt, ggx_twin, scene_name, w, h, mis, decay):
+def test_ggx_matches_twin(mirt, scene_name, w, h, mis, decay):
     sc = getattr(mirt.scene, scene_name)()
     t = twin(sc, w, h, 10, decay=decay, mis=mis)
     want_acc, want_img = t.accumulator(), t.Render()
@@ -73,7 +66,7 @@ def test_ggx_matches_twin(mirt, ggx_twin, scene_name, w, h, mis, decay):
 
 
 @pytest.mark.parametrize("streams,max_batch", [(1, 0), (3, 16)])
-def test_ggx_full_size_launch_shape(mirt, ggx_twin, streams, max_batch):
+def test_ggx_full_size_launch_shape(mirt, streams, max_batch):
     """default9 with every material member at 1920x1088 x 64 accumulations (contribution-buffer mode), against the twin on a tile subset."""
     w, h, spp = 1920, 1088, 64
     sc = mirt.scene.default9()
@@ -91,7 +84,7 @@ def test_ggx_full_size_launch_shape(mirt, ggx_twin, streams, max_batch):
     assert got.any()
 
 
-def test_ggx_deferred_calls_keep_their_decay_table(mirt, ggx_twin):
+def test_ggx_deferred_calls_keep_their_decay_table(mirt):
     """mirt_set_gloss_decay launches what AccumulateAsync deferred, with the table those calls were issued under."""
     sc = mirt.scene.brdf_test()
     r = mirt.Renderer(sc, max_bounces=16, use_bvh=True, brdf=1, gloss_decay=DECAY)
@@ -102,7 +95,7 @@ def test_ggx_deferred_calls_keep_their_decay_table(mirt, ggx_twin):
     r.set_gloss_decay(None)
     r.AccumulateAsync(3)
     r.Synchronize()
-    t = gb.GgxTwin(sc, brdf=1, gloss_decay=DECAY, max_bounces=16, trav_mode=ob.TRAV_PER_RAY_BVH); t.Resize(64, 48)
+    t = ob.Oracle(sc, brdf=1, gloss_decay=DECAY, max_bounces=16, trav_mode=ob.TRAV_PER_RAY_BVH); t.Resize(64, 48)
     t.Accumulate(3); t.set_gloss_decay([0.5, 0.2]); t.Accumulate(4); t.set_gloss_decay(None); t.Accumulate(3)
     assert_same(r.accumulator(), t.accumulator(), "AccumulateAsync with set_gloss_decay between deferred calls")
     same_counters(r, t, "deferred")
@@ -163,8 +156,8 @@ def test_headless_host_writes_the_python_frame(mirt, tmp_path):
     r = mirt.Renderer(mirt.scene.brdf_test(), max_bounces=16, use_bvh=True, brdf=1, gloss_decay=DECAY)
     r.Resize(160, 96); r.Accumulate(10); assert r.Render()
     assert rep["accumulations"] == 10 and rep["frame_ready"] and rep["rays"] == r.counters()["rays"]
-    assert rep["accumulator_fnv1a"] == _fnv1a(r.accumulator())
-    assert rep["last_frame_fnv1a"] == _fnv1a(r.GetFrame())
+    assert rep["accumulator_fnv1a"] == fnv1a(r.accumulator())
+    assert rep["last_frame_fnv1a"] == fnv1a(r.GetFrame())
     rgb = np.fromfile(pfm, dtype=np.float32, offset=len(b"PF\n160 96\n-1.0\n")).reshape(96, 160, 3)
     assert_same(rgb, r.GetFrame()[:, :, :3], "mirt_headless PFM frame")
     r.close()

@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
-from test_oracle_cpu import CASES, GOLDEN, bits, make_scene
+from oracle_binding import bits, fnv1a
+from test_oracle_cpu import CASES, GOLDEN, make_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -633,13 +634,6 @@ def test_edge_cases_and_errors(mirt):
             mirt.Renderer(bad)
 
 
-def _fnv1a(acc):
-    h = 1469598103934665603
-    for b in np.ascontiguousarray(acc, dtype=np.float32).view(np.uint8).ravel().tolist():
-        h = ((h ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return f"{h:016x}"
-
-
 def test_cpp_host_matches_golden_and_oracle(mirt, tmp_path):
     """The C++ host mirror (csrc/mirt_host.hpp + mirt_headless, reference call protocol: Accumulate(); Render() per frame):
     its accumulator (FNV-1a of the raw words) and its PFM frame must equal the committed golden vector / the live oracle."""
@@ -660,7 +654,7 @@ def test_cpp_host_matches_golden_and_oracle(mirt, tmp_path):
         out = subprocess.run([exe, *args, "--size", f"{w}x{hgt}", "--spp", str(spp), "--out", pfm], check=True, capture_output=True, text=True).stdout
         rep = json.loads(out)
         assert rep["accumulations"] == spp and rep["rays"] == want_rays and rep["frame_ready"], args
-        assert rep["accumulator_fnv1a"] == _fnv1a(want_acc), args
+        assert rep["accumulator_fnv1a"] == fnv1a(want_acc), args
         raw = open(pfm, "rb").read()
         assert raw.startswith(b"PF\n") and len(raw) == len(f"PF\n{w} {hgt}\n-1.0\n") + w * hgt * 12
         img = np.frombuffer(raw[-w * hgt * 12:], dtype="<f4").reshape(hgt, w, 3)
@@ -678,8 +672,8 @@ def test_cpp_host_frame_loop(mirt):
     assert rep["accumulations"] == 12 and rep["frames_due"] == [5, 10] and rep["frame_ready"]
     o = ob.Oracle(mirt.scene.default9(), max_bounces=16, trav_mode=ob.TRAV_BRUTE); o.Resize(64, 48)
     o.Accumulate(10); frame10 = o.Render(); o.Accumulate(2)
-    assert rep["accumulator_fnv1a"] == _fnv1a(o.accumulator())
-    assert rep["last_frame_fnv1a"] == _fnv1a(frame10)
+    assert rep["accumulator_fnv1a"] == fnv1a(o.accumulator())
+    assert rep["last_frame_fnv1a"] == fnv1a(frame10)
 
 
 @pytest.mark.parametrize("n,w,h,spp,mb", [(10000, 256, 192, 5, 9), (100000, 192, 128, 5, 9)])
@@ -834,7 +828,7 @@ def test_cpp_host_on_a_group(mirt):
     out = subprocess.run([exe, "--scene", "default9", "--size", "64x64", "--spp", "10", "--devices", "0,0"], check=True, capture_output=True, text=True).stdout
     rep = json.loads(out)
     assert rep["gpus"] == 2 and rep["accumulations"] == 10 and rep["rays"] == int(g["rays"]) and rep["frame_ready"]
-    assert rep["accumulator_fnv1a"] == _fnv1a(g["accumulator"]) and rep["last_frame_fnv1a"] == _fnv1a(g["frame"])
+    assert rep["accumulator_fnv1a"] == fnv1a(g["accumulator"]) and rep["last_frame_fnv1a"] == fnv1a(g["frame"])
 
 
 def test_accumulator_device_view_for_rccl(mirt):
@@ -1111,7 +1105,7 @@ def test_cpp_host_reads_and_writes_radiance_hdr(mirt, tmp_path):
     o = ob.Oracle(sc, max_bounces=16, trav_mode=ob.TRAV_BRUTE); o.Resize(96, 64); o.Accumulate(10)
     rep = json.loads(subprocess.run([exe, "--scene", "default9", "--size", "96x64", "--spp", "10", "--hdri", env_path, "--ambient", "0.8", "--out", out_path],
                                     check=True, capture_output=True, text=True).stdout)
-    assert rep["accumulator_fnv1a"] == _fnv1a(o.accumulator()) and rep["frame_ready"]
+    assert rep["accumulator_fnv1a"] == fnv1a(o.accumulator()) and rep["frame_ready"]
     frame = o.Render()
     assert frame[..., :3].max() > 0.05
     got = mirt.hdr.read_hdr(out_path)                                       # top-down

@@ -10,12 +10,9 @@ import pytest
 
 import oracle_binding as ob
 from conftest import ROOT, load_mirt
+from oracle_binding import bits
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 # ---- Random.hpp known answers (re-derived from the formulas, not from reference tests) ----
