@@ -117,9 +117,16 @@ inline void split_multi_prim_leaves(std::vector<mirt_bvh_node>& nodes) {
 	}
 }
 
-// 32-B half-precision records from the 64-B ones.  Returns false (and leaves `out` empty) when binary16 is not adequate:
-// a coordinate beyond +-60000, or a leaf box whose smallest extent is under 8 quantisation steps (the box would grow by
-// more than ~25 %).  (With more than 32768 records or spheres the traversal stack keeps u32 entries, see mirt_capi.hip.)
+// binary16 is adequate for a child box unless a coordinate lies beyond +-60000 (amax: the largest magnitude), or it is a leaf box whose
+// smallest extent is under 8 quantisation steps (the box would grow by more than ~25 %).  Also asked for the sphere-derived leaf
+// boxes of a GPU-built tree (mirt_capi.hip), which never pass through build_half_records.
+inline bool half_box_adequate(float amax, float min_extent, bool leaf) {
+	if (amax > 60000.0f) return false;
+	return !(leaf && min_extent < 8.0f * half_ulp_at(amax));
+}
+
+// 32-B half-precision records from the 64-B ones.  Returns false (and leaves `out` empty) when binary16 is not adequate for
+// some child box.  (With more than 32768 records or spheres the traversal stack keeps u32 entries, see mirt_capi.hip.)
 inline bool build_half_records(const std::vector<float>& recs, std::vector<uint32_t>& out) {
 	out.clear();
 	const size_t n = recs.size() / 16;
@@ -135,8 +142,7 @@ inline bool build_half_records(const std::vector<float>& recs, std::vector<uint3
 				amax = std::fmax(amax, std::fmax(std::fabs(lo), std::fabs(hi)));
 				min_extent = std::fmin(min_extent, hi - lo);
 			}
-			if (amax > 60000.0f) return false;
-			if ((ref & kLeafBit) && min_extent < 8.0f * half_ulp_at(amax)) return false;
+			if (!half_box_adequate(amax, min_extent, (ref & kLeafBit) != 0)) return false;
 		}
 	}
 	out.resize(n * 8);

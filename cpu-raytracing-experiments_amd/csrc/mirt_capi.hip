@@ -57,7 +57,7 @@ struct TimedLaunch { int klass; hipEvent_t start, stop; };
 struct PipeSlot {
 	hipStream_t stream = nullptr;
 	DeviceBuffer arena;              // ray streams
-	DeviceBuffer counts;             // ray queues (kSegs counters each): stream[nb+1] | shadow[nb] | one always-empty queue; then work_next[nb] | work_next_shadow[nb] | fat counts[2 nb]
+	DeviceBuffer counts;             // ray queue counters, work counters and fat-ray counts of one batch: addressed through BatchCounters only
 	DeviceBuffer contrib;            // this batch's path results, [tile][slot][256][rgb] (kernels.hpp contrib_index)
 	DeviceBuffer fat;                // fat-ray index lists: [closest kFatCapacity][shadow kFatCapacity]
 	DeviceBuffer cand;               // per local pixel: candidate spheres of its bundle of camera rays (k_primary_cand), kCandStride words
@@ -89,7 +89,6 @@ struct mirt_ctx {
 	SceneDev scene{};
 	std::vector<float> gloss_decay;  // gloss_decay_table (Renderer.hpp:212) by bounce, read at launch (mirt_set_gloss_decay); missing entries are 0
 	CameraParams camera{};
-	uint32_t trace_lds_bytes = 0;    // dynamic LDS of the BVH trace kernels (staged records + spheres)
 	uint32_t bvh_depth = 0;
 	bool allow_half = true;           // binary16 records when adequate (mirt_debug_set(ctx, "half_boxes", 0) forces f32)
 
@@ -180,16 +179,33 @@ constexpr uint32_t kLdsPerCu = 160u * 1024u;
 //   binary16 records, <= 32768 records and spheres: 16 u16 entries (32 KB) + up to 48 KB staged  -> TWO workgroups (32 waves) per CU
 //   binary16 records, more of them:     12 u32 entries (48 KB) + up to 32 KB staged  -> two workgroups per CU
 //   f32 records:                        16 u32 entries (64 KB) + up to 96 KB staged  -> one workgroup per CU
-uint32_t stack_bytes(bool half, bool stack16) { return half ? (stack16 ? kLdsStack * kTraceBlock * 2u : kLdsStackWide * kTraceBlock * 4u) : kLdsStack * kTraceBlock * 4u; }
-uint32_t stack_bytes(const mirt_ctx* c) { return stack_bytes(c->scene.half_boxes != 0, c->scene.stack16 != 0); }
-uint32_t stage_budget(bool half, bool stack16) { return half ? (stack16 ? 48u * 1024u : 32u * 1024u) : 96u * 1024u; }
-uint32_t trace_lds(const mirt_ctx* c) { return c->policy.use_bvh ? c->trace_lds_bytes + stack_bytes(c) : kBruteChunk * 16u; }
+// Staged: the whole tree and every sphere packet when they fit the budget (1k spheres: 64 + 16 KB), otherwise the top of the
+// tree only (records are breadth-first) and spheres from L2.  Brute force (policy.use_bvh = 0) stages one chunk of spheres.
+struct LdsPlan {
+	uint32_t stack16;                  // a stack entry = 15-bit record or prim index + the leaf flag
+	uint32_t rec_bytes, lds_recs, lds_spheres, staged_bytes, stack_bytes;     // one record as fetched; records / sphere packets staged
+	uint32_t launch_bytes;             // dynamic LDS of a trace launch under the current policy
+	uint32_t wgs_per_cu;               // workgroups a CU holds at that footprint, at most tune_trace_wgs (2 x 1024 threads = 32 waves, the CU's limit)
+};
+LdsPlan lds_plan(const mirt_ctx* c) {
+	const SceneDev& s = c->scene;
+	const bool half = s.half_boxes != 0;
+	LdsPlan p{};
+	p.stack16 = (half && s.n_recs <= 32768 && s.n_spheres <= 32768) ? 1u : 0u;
+	p.rec_bytes = (half && !s.wide) ? 32u : 64u;
+	p.stack_bytes = half ? (p.stack16 ? kLdsStack * kTraceBlock * 2u : kLdsStackWide * kTraceBlock * 4u) : kLdsStack * kTraceBlock * 4u;
+	const uint32_t budget = half ? (p.stack16 ? 48u * 1024u : 32u * 1024u) : 96u * 1024u;
+	if (static_cast<uint64_t>(s.n_recs) * p.rec_bytes + static_cast<uint64_t>(s.n_spheres) * 16u <= budget) { p.lds_recs = s.n_recs; p.lds_spheres = s.n_spheres; }
+	else { p.lds_recs = std::min<uint32_t>(s.n_recs, budget / p.rec_bytes); p.lds_spheres = 0; }
+	p.staged_bytes = p.lds_recs * p.rec_bytes + p.lds_spheres * 16u;
+	p.launch_bytes = c->policy.use_bvh ? p.staged_bytes + p.stack_bytes : kBruteChunk * 16u;
+	p.wgs_per_cu = std::min(std::max(kLdsPerCu / p.launch_bytes, 1u), c->tune_trace_wgs);
+	return p;
+}
+uint32_t trace_lds(const mirt_ctx* c) { return lds_plan(c).launch_bytes; }
 uint32_t trace_grid(const mirt_ctx* c, uint64_t work_items) {
-	uint32_t per_cu = kLdsPerCu / trace_lds(c);
-	if (per_cu > c->tune_trace_wgs) per_cu = c->tune_trace_wgs;      // 2 x 1024 threads = 32 waves, the CU's limit
-	if (per_cu < 1) per_cu = 1;
 	uint64_t blocks = (work_items + kTraceBlock - 1) / kTraceBlock;
-	const uint64_t cap = static_cast<uint64_t>(c->n_cu) * per_cu;
+	const uint64_t cap = static_cast<uint64_t>(c->n_cu) * lds_plan(c).wgs_per_cu;
 	if (blocks > cap) blocks = cap;
 	if (blocks < 1) blocks = 1;
 	return static_cast<uint32_t>(blocks);
@@ -199,9 +215,28 @@ hipError_t sync_all(mirt_ctx* c) {
 	for (PipeSlot& sl : c->slots) if (sl.stream) { hipError_t e = hipStreamSynchronize(sl.stream); if (e != hipSuccess) return e; }
 	return hipStreamSynchronize(c->stream);
 }
-constexpr uint32_t kQueueWords = kSegs * kSegPitch;     // one ray queue's counters
-size_t counts_words(uint32_t nb) { return static_cast<size_t>(2 * nb + 2) * kQueueWords + static_cast<size_t>(nb) * 4 + 8; }
+constexpr uint32_t kQueueWords = kSegs * kSegPitch;     // one ray queue's counters: one per 128-B line (kernels.hpp "ray queues"; k_shade's appends are sensitive to it)
 constexpr uint32_t kFatCapacity = 1u << 16;   // rays per list and launch that may take the brute-force detour (a few per million qualify)
+// The counter words of one batch of nb bounces (PipeSlot::counts; the debug trace entry points keep a private one with nb = 1), zeroed before
+// the batch's first launch: 2 nb + 2 queues of kQueueWords, then 4 nb + 3 single words (+ 5 spare).  Every offset is stated here and nowhere else.
+struct BatchCounters {
+	uint32_t* w; uint32_t nb, seg_cap;
+	static size_t words(uint32_t nb) { return static_cast<size_t>(2 * nb + 2) * kQueueWords + static_cast<size_t>(nb) * 4 + 8; }
+	Queue queue(uint32_t k) const { return Queue{ w + static_cast<size_t>(k) * kQueueWords, seg_cap }; }
+	uint32_t* word(uint32_t k) const { return w + static_cast<size_t>(2 * nb + 2) * kQueueWords + k; }
+	Queue stream_queue(uint32_t b) const { return queue(b); }                // b = 0 .. nb: rays entering bounce b (b >= 1)
+	Queue shadow_queue(uint32_t b) const { return queue(nb + 1 + b); }       // b = 0 .. nb - 1: NEE rays emitted at bounce b
+	Queue empty_queue() const { return queue(2 * nb + 1); }                  // "no shadow rays pending"
+	uint32_t* closest_work(uint32_t b) const { return word(b); }             // per-launch work counters of the persistent trace kernels
+	uint32_t* shadow_work(uint32_t b) const { return word(nb + b); }
+	// per-launch fat-ray counts; `lists`: the slot's index lists, [closest kFatCapacity][shadow kFatCapacity]
+	FatList fat_closest(uint32_t b, uint32_t* lists) const { return FatList{ word(2 * nb + b), lists, kFatCapacity }; }
+	FatList fat_shadow(uint32_t b, uint32_t* lists) const { return FatList{ word(3 * nb + b), lists + kFatCapacity, kFatCapacity }; }
+	uint32_t* cand_work() const { return word(4 * nb); }                     // work counter of k_primary_cand
+	uint32_t* unused_fat_count() const { return word(4 * nb + 1); }          // count of the zero-capacity list k_primary_cand is handed
+	uint32_t* listed_pixels() const { return word(4 * nb + 2); }             // pixels without a candidate list (their list: in.path of bounce 0)
+};
+BatchCounters batch_counters(const mirt_ctx* c, const PipeSlot& sl) { return BatchCounters{ sl.counts.as<uint32_t>(), c->policy.max_bounces, c->seg_cap }; }
 uint32_t wanted_slots(const mirt_ctx* c) {
 	if (c->policy.streams) return std::min<uint32_t>(c->policy.streams, 8u);
 	return static_cast<uint64_t>(c->n_tiles) * kTileSize * batch_limit(c) >= kSerialRays ? 1u : 3u;
@@ -266,7 +301,7 @@ int ensure_streams(mirt_ctx* c) {
 		sl.in_use = false;                                                   // (the caller has synchronised every stream)
 		hipError_t e = sl.arena.ensure(planes * plane_bytes);
 		const char* what = "ray streams";
-		if (e == hipSuccess) { e = sl.counts.ensure(counts_words(nb) * sizeof(uint32_t)); what = "queue counters"; }
+		if (e == hipSuccess) { e = sl.counts.ensure(BatchCounters::words(nb) * sizeof(uint32_t)); what = "queue counters"; }
 		if (e == hipSuccess) { e = sl.fat.ensure(2u * kFatCapacity * sizeof(uint32_t)); what = "fat-ray lists"; }
 		if (e == hipSuccess) { e = sl.cand.ensure(static_cast<size_t>(n_pix) * kCandStride * sizeof(uint32_t)); what = "candidate lists"; }
 		if (e == hipSuccess) { if (contrib) { e = sl.contrib.ensure(acc_bytes); what = "contribution buffer"; } else sl.contrib.release(); }
@@ -346,6 +381,8 @@ struct Bracket {
 	}
 };
 
+// half-angle of a pixel's bundle of camera rays: half a pixel diagonal (0.7072) at distance >= |z|; + 1e-4: a sample's own cone half-width
+// (1.38e-3 .. 1.47e-3, from |D|^2 - 1 of its normalised direction) may exceed the axis ray's by 8.5e-5
 float bundle_half_angle(const mirt_ctx* c) { return (0.7072f / std::fabs(c->camera.z)) * 1.01f + 1e-4f; }
 
 FrameParams frame_params(const mirt_ctx* c, uint32_t acc_base, uint32_t batch_n) {
@@ -372,6 +409,49 @@ FrameParams frame_params(const mirt_ctx* c, uint32_t acc_base, uint32_t batch_n)
 	return fp;
 }
 
+// The scene as the trace kernels of a launch see it: what mirt_set_scene left, the policy's use_bvh and the launch-shape knobs.
+SceneDev trace_scene(const mirt_ctx* c) {
+	SceneDev sc = c->scene;
+	sc.use_bvh = c->policy.use_bvh;
+	sc.chunk_max = c->tune_chunk; sc.leaf_batch = c->tune_leaf_batch; sc.refill_idle = c->tune_refill_idle;
+	return sc;
+}
+
+// Every instantiation a launch may pick, by template argument.  kTrace and kPrimaryCand use dynamic LDS: mirt_set_scene raises
+// their limit by walking these tables, so a kernel that can be launched cannot be missed there.
+// Rows indexed by COUNT hold the counting kernels FIRST ([!count]): the order in which k_trace<true, .> and k_trace<false, .> are
+// first named here decides hipcc's register assignment in k_trace<., kPrimaryNone> (same resources, another instruction stream),
+// and with this order the device code is what it has been since the kernels were tuned and measured.
+const decltype(&k_trace<true, kPrimaryNone>) kTrace[2][3] = {            // [!count][primary]
+	{ k_trace<true, kPrimaryNone>, k_trace<true, kPrimaryAll>, k_trace<true, kPrimaryList> },
+	{ k_trace<false, kPrimaryNone>, k_trace<false, kPrimaryAll>, k_trace<false, kPrimaryList> } };
+const decltype(&k_trace_fat<true, kPrimaryNone>) kTraceFat[2][3] = {     // [!count][primary]
+	{ k_trace_fat<true, kPrimaryNone>, k_trace_fat<true, kPrimaryAll>, k_trace_fat<true, kPrimaryList> },
+	{ k_trace_fat<false, kPrimaryNone>, k_trace_fat<false, kPrimaryAll>, k_trace_fat<false, kPrimaryList> } };
+const decltype(&k_primary_cand<true>) kPrimaryCand[2] = { k_primary_cand<true>, k_primary_cand<false> };                                    // [!count]
+const decltype(&k_primary_hits<true>) kPrimaryHits[2] = { k_primary_hits<true>, k_primary_hits<false> };                                    // [!count]
+const decltype(&k_shade<false, false>) kShade[2][2] = { { k_shade<false, false>, k_shade<false, true> }, { k_shade<true, false>, k_shade<true, true> } };   // [first][ggx]
+static_assert(kPrimaryNone == 0 && kPrimaryAll == 1 && kPrimaryList == 2, "kTrace / kTraceFat are indexed by PRIMARY");
+
+// What varies between the launches of the trace stage: a bounce of a batch, or the rays of a debug entry point.
+struct TraceLaunch {
+	StreamBuf in; HitRec* hit;                       // closest-hit rays (no stream with PRIMARY) and their hit records
+	Queue closest_queue; uint32_t* closest_work;
+	ShadowBuf sh; ShadowSink sink;                   // shadow rays and where their outcome goes
+	Queue shadow_queue; uint32_t* shadow_work;
+	FatList fat_closest, fat_shadow;
+	const uint32_t* listed_pixels;                   // kPrimaryList: count of the pixels listed in in.path
+	DevCounters* ctr;
+};
+// k_trace<count, primary> over n_rays, then (with a tree) the few rays too "fat" for it: brute force, one workgroup each.
+void launch_trace(const mirt_ctx* c, hipStream_t st, const SceneDev& sc, const FrameParams& fp, uint64_t n_rays, bool count, int primary, const TraceLaunch& t) {
+	hipLaunchKernelGGL(kTrace[!count][primary], dim3(trace_grid(c, n_rays)), dim3(kTraceBlock), trace_lds(c), st, sc, fp, t.in, t.hit, t.closest_queue, t.closest_work,
+	                   t.sh, t.sink, t.shadow_queue, t.shadow_work, t.fat_closest, t.fat_shadow, t.ctr);
+	// a large scene (100 k spheres: ~100 us per ray) wants as many fat rays in flight as there are (a few hundred per launch); k_trace_fat grid-strides
+	const uint32_t fat_grid = sc.n_spheres > 4096 ? static_cast<uint32_t>(c->n_cu) * 2u : 64u;
+	if (sc.use_bvh) hipLaunchKernelGGL(kTraceFat[!count][primary], dim3(fat_grid), dim3(1024), 0, st, sc, fp, t.in, t.hit, t.fat_closest, t.sh, t.sink, t.fat_shadow, t.ctr, t.listed_pixels);
+}
+
 // One batch = up to batch_limit() consecutive Accumulate() calls traced together (path id = (slot << pix_bits) | pixel).
 // Consecutive accumulation indices land in buckets (acc % buckets, Renderer.hpp:82), and the ORDER of the adds into a
 // bucket word is part of the result.  With at most `buckets` accumulations per batch and one batch at a time every
@@ -391,88 +471,58 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 	hipStream_t st = pipelined ? sl.stream : c->stream;
 	const bool contrib = uses_contrib(c, static_cast<uint32_t>(c->slots.size()));
 	if (contrib) { fp.idx_base = kIdxContrib; fp.idx_buckets = batch_n; }            // slot k of the buffer = accumulation acc_base + k + 1
-	uint32_t* counts = sl.counts.as<uint32_t>();
-	auto stream_queue = [&](uint32_t b) { return Queue{ counts + static_cast<size_t>(b) * kQueueWords, c->seg_cap }; };                 // rays entering bounce b (b >= 1)
-	auto shadow_queue = [&](uint32_t b) { return Queue{ counts + static_cast<size_t>(nb + 1 + b) * kQueueWords, c->seg_cap }; };        // NEE rays emitted at bounce b
-	const Queue empty_queue{ counts + static_cast<size_t>(2 * nb + 1) * kQueueWords, c->seg_cap };                                      // "no shadow rays pending"
-	uint32_t* work_next = counts + static_cast<size_t>(2 * nb + 2) * kQueueWords;     // per-launch work counters of the persistent trace kernels
-	uint32_t* work_next_shadow = work_next + nb;
-	uint32_t* fat_n_closest = work_next_shadow + nb;    // per-launch fat-ray counts (closest-hit list, shadow list)
-	uint32_t* fat_n_shadow = fat_n_closest + nb;
-	uint32_t* misc = fat_n_shadow + nb;                 // [0] work counter of k_primary_cand, [1] an unused fat-ray count, [2] pixels without a candidate list (their list: in.path of bounce 0)
+	const BatchCounters bc = batch_counters(c, sl);
 	// Camera rays of a batch go through per-pixel candidate lists when a pixel is sampled often enough to pay for its cone traversal
 	// (policy.trace_primary_rays = 1 switches that off: every primary ray then walks the tree; results are identical either way).
 	// (The half-angle bound assumes view.orient rotates: a non-unit quaternion, which the reference's View never holds (Camera.hpp:48-50),
 	// would shear the image plane — such a camera gets no lists.)
 	const float qn = c->camera.orient[0] * c->camera.orient[0] + c->camera.orient[1] * c->camera.orient[1] + c->camera.orient[2] * c->camera.orient[2] + c->camera.orient[3] * c->camera.orient[3];
 	const bool bundle = c->policy.use_bvh && c->scene.n_recs != 0 && !c->policy.trace_primary_rays && batch_n >= 3 && c->camera.z != 0.0f && std::fabs(qn - 1.0f) < 1e-4f;
-	// half-angle of a pixel's bundle: half a pixel diagonal (0.7072) at distance >= |z|; + 1e-4: a sample's own cone half-width (1.38e-3 ..
-	// 1.47e-3, from |D|^2 - 1 of its normalised direction) may exceed the axis ray's by 8.5e-5
-	const float rho = bundle ? bundle_half_angle(c) : 0.0f;
 	DevCounters* ctr = c->counters.as<DevCounters>();
 	const float4* mat_ggx = c->mat_ggx.as<float4>();
 	float* accum = contrib ? sl.contrib.as<float>() : c->accumulator.as<float>();
-	SceneDev sc = c->scene;
-	sc.use_bvh = c->policy.use_bvh;
-	sc.chunk_max = c->tune_chunk; sc.leaf_batch = c->tune_leaf_batch; sc.refill_idle = c->tune_refill_idle;
+	uint32_t* fat_lists = sl.fat.as<uint32_t>();
+	const SceneDev sc = trace_scene(c);
 	const bool count = c->policy.count_traffic != 0;
-	const uint32_t tgrid = trace_grid(c, total);
 	const uint32_t sgrid = static_cast<uint32_t>(std::min<uint64_t>((total + kShadeBlock - 1) / kShadeBlock, static_cast<uint64_t>(c->n_cu) * c->tune_shade_wgs));     // three 512-thread workgroups are resident per CU (k_shade: ~80 VGPRs); more only adds passes
-	const uint32_t tlds = trace_lds(c);
 	{	// k_shade<FIRST> hands out (512-pixel chunk, group of accumulations) pieces: at least ~8 per workgroup, so that a small image loads the grid evenly
 		const uint64_t n_chunks = (static_cast<uint64_t>(fp.n_pix) + kShadeBlock - 1) / kShadeBlock;
 		const uint64_t want = (8ull * sgrid + n_chunks - 1) / n_chunks;
 		fp.first_groups = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(want, 1), batch_n));
 	}
-	// one workgroup per fat ray: a large scene (100 k spheres: ~100 us per ray) wants as many of them in flight as there are rays (a few hundred per launch)
-	const uint32_t fat_grid = sc.n_spheres > 4096 ? static_cast<uint32_t>(c->n_cu) * 2u : 64u;
 
 	if (pipelined && sl.in_use) HIP_TRY(c, hipStreamWaitEvent(st, sl.merged, 0));   // the slot's previous batch has been merged: buffers are free
 	// (The contribution buffer needs no clearing: each of its words is stored once by the path it belongs to.)
 	if (contrib && c->debug_poison_contrib)
 		HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sl.contrib.ptr), 0x7fc0deadu, sl.contrib.bytes / sizeof(float), st));   // a quiet NaN
-	HIP_TRY(c, hipMemsetAsync(counts, 0, counts_words(nb) * sizeof(uint32_t), st));
+	HIP_TRY(c, hipMemsetAsync(bc.w, 0, BatchCounters::words(nb) * sizeof(uint32_t), st));
 	// bounce 0 has no ray stream: k_trace<PRIMARY> and k_shade<FIRST> derive the camera ray from its index (RAY GENERATION, Renderer.hpp:113-127)
 	for (uint32_t bounce = 0; bounce < nb; bounce++) {
 		const StreamBuf& in = sl.stream_buf[bounce & 1u];
 		const StreamBuf& out = sl.stream_buf[(bounce & 1u) ^ 1u];
 		const bool shadow_pending = fp.mis && bounce > 0;           // NEE rays emitted by k_shade(bounce-1)
+		const bool lists = bounce == 0 && bundle;
 		{ Bracket t(c, MIRT_K_TRACE, st);
-		  const Queue sq = shadow_pending ? shadow_queue(bounce - 1) : empty_queue;
-		  uint32_t* sc_work = work_next_shadow + (shadow_pending ? bounce - 1 : 0);
-		  const FatList fc{ fat_n_closest + bounce, sl.fat.as<uint32_t>(), kFatCapacity };
-		  const FatList fs{ fat_n_shadow + bounce, sl.fat.as<uint32_t>() + kFatCapacity, kFatCapacity };
+		  if (lists) {
+		    // camera rays through per-pixel candidate lists (kernels.hpp kCollect): one cone traversal per pixel, then k_primary_hits intersects every
+		    // sample with its pixel's list.  Pixels without a list are listed in in.path (count: listed_pixels) and all their samples traced like any other ray.
+		    const FatList none{ bc.unused_fat_count(), fat_lists, 0u };
+		    hipLaunchKernelGGL(kPrimaryCand[!count], dim3(trace_grid(c, fp.n_pix)), dim3(kTraceBlock), trace_lds(c), st, sc, fp, sl.cand.as<uint32_t>(), bundle_half_angle(c),
+		                       bc.cand_work(), none, ctr, in.path, bc.listed_pixels());
+		    const uint32_t hgrid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
+		    hipLaunchKernelGGL(kPrimaryHits[!count], dim3(hgrid), dim3(kBlock), 0, st, sc, fp, sl.cand.as<uint32_t>(), sl.hit, ctr);
+		  }
 		  // the adds of bounce-1 that waited for occlusion land in stream `in` (= out of bounce-1) or the accumulator, before k_shade reads them
 		  const ShadowSink sink{ in.rr, in.rg, in.rb, in.px, in.py, in.pz, accum, fp.idx_base, fp.idx_buckets, fp.pix_bits, nullptr };
-		  const Queue cq = (bounce == 0 && bundle) ? Queue{ misc + 2, 0u } : stream_queue(bounce);      // kPrimaryList: n[0] = listed pixels
-		  auto launch_trace = [&](auto kernel, auto fat_kernel) {
-		    hipLaunchKernelGGL(kernel, dim3(tgrid), dim3(kTraceBlock), tlds, st, sc, fp, in, sl.hit, cq, work_next + bounce,
-		                       sl.shadow_buf, sink, sq, sc_work, fc, fs, ctr);
-		    // the few rays too "fat" for the tree: brute force, one workgroup each
-		    if (sc.use_bvh) hipLaunchKernelGGL(fat_kernel, dim3(fat_grid), dim3(1024), 0, st, sc, fp, in, sl.hit, fc, sl.shadow_buf, sink, fs, ctr, misc + 2);
-		  };
-		  if (bounce == 0 && bundle) {
-		    // camera rays through per-pixel candidate lists (kernels.hpp kCollect): one cone traversal per pixel, then k_primary_hits intersects every
-		    // sample with its pixel's list.  Pixels without a list are listed in in.path (count: misc[2]) and all their samples traced like any other ray
-		    const FatList none{ misc + 1, sl.fat.as<uint32_t>(), 0u };
-		    if (count) hipLaunchKernelGGL(k_primary_cand<true>, dim3(trace_grid(c, fp.n_pix)), dim3(kTraceBlock), tlds, st, sc, fp, sl.cand.as<uint32_t>(), rho, misc, none, ctr, in.path, misc + 2);
-		    else       hipLaunchKernelGGL(k_primary_cand<false>, dim3(trace_grid(c, fp.n_pix)), dim3(kTraceBlock), tlds, st, sc, fp, sl.cand.as<uint32_t>(), rho, misc, none, ctr, in.path, misc + 2);
-		    const uint32_t hgrid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
-		    if (count) hipLaunchKernelGGL(k_primary_hits<true>, dim3(hgrid), dim3(kBlock), 0, st, sc, fp, sl.cand.as<uint32_t>(), sl.hit, ctr);
-		    else       hipLaunchKernelGGL(k_primary_hits<false>, dim3(hgrid), dim3(kBlock), 0, st, sc, fp, sl.cand.as<uint32_t>(), sl.hit, ctr);
-		    if (count) launch_trace((k_trace<true, kPrimaryList>), (k_trace_fat<true, kPrimaryList>)); else launch_trace((k_trace<false, kPrimaryList>), (k_trace_fat<false, kPrimaryList>));
-		  }
-		  else if (bounce == 0) { if (count) launch_trace((k_trace<true, kPrimaryAll>), (k_trace_fat<true, kPrimaryAll>)); else launch_trace((k_trace<false, kPrimaryAll>), (k_trace_fat<false, kPrimaryAll>)); }
-		  else                  { if (count) launch_trace((k_trace<true, kPrimaryNone>), (k_trace_fat<true, kPrimaryNone>)); else launch_trace((k_trace<false, kPrimaryNone>), (k_trace_fat<false, kPrimaryNone>)); } }
+		  const TraceLaunch tl{ in, sl.hit, lists ? Queue{ bc.listed_pixels(), 0u } : bc.stream_queue(bounce), bc.closest_work(bounce),      // kPrimaryList: n[0] = listed pixels
+		                        sl.shadow_buf, sink, shadow_pending ? bc.shadow_queue(bounce - 1) : bc.empty_queue(), bc.shadow_work(shadow_pending ? bounce - 1 : 0),
+		                        bc.fat_closest(bounce, fat_lists), bc.fat_shadow(bounce, fat_lists), bc.listed_pixels(), ctr };
+		  launch_trace(c, st, sc, fp, total, count, lists ? kPrimaryList : bounce == 0 ? kPrimaryAll : kPrimaryNone, tl); }
 		{ Bracket t(c, MIRT_K_SHADE, st);
 		  // policy.brdf = 1 (#define BRDF 1): Closure<GGX> with this bounce's gloss decay, passed by value
 		  const float decay = bounce < c->gloss_decay.size() ? c->gloss_decay[bounce] : 0.0f;
-		  auto launch_shade = [&](auto kernel) {
-		    hipLaunchKernelGGL(kernel, dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce, stream_queue(bounce), stream_queue(bounce + 1),
-		                       shadow_queue(bounce), accum, ctr, mat_ggx, decay);
-		  };
-		  if (c->policy.brdf) { if (bounce == 0) launch_shade(k_shade<true, true>); else launch_shade(k_shade<false, true>); }
-		  else                { if (bounce == 0) launch_shade(k_shade<true, false>); else launch_shade(k_shade<false, false>); } }
+		  hipLaunchKernelGGL(kShade[bounce == 0][c->policy.brdf != 0], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
+		                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), accum, ctr, mat_ggx, decay); }
 	}
 	HIP_TRY(c, hipGetLastError());
 	if (contrib) {
@@ -517,6 +567,196 @@ int flush_deferred(mirt_ctx* c) {
 	HIP_TRY(c, hipSetDevice(c->device));
 	int r = ensure_streams(c); if (r) return r;
 	return launch_batch(c, n);
+}
+
+// ---- mirt_set_scene, step by step --------------------------------------------------------------
+struct SceneArgs {
+	const mirt_sphere *geometry, *bvh_prims; uint32_t n_spheres;
+	const mirt_bvh_node* nodes; uint32_t n_nodes;
+	const mirt_material* materials; uint32_t n_materials;
+	const int32_t* lights; uint32_t n_lights;
+	const float *ambient_color, *hdri_rgba; uint32_t hdri_w, hdri_h;
+};
+
+// Validate everything the kernels index with: an out-of-range id would fault the GPU.
+int check_scene_args(mirt_ctx* c, const SceneArgs& a) {
+	if (a.n_spheres && (!a.geometry || !a.bvh_prims)) return fail(c, MIRT_ERR_ARG, "geometry / bvh_prims is NULL");
+	if (a.n_spheres >= (1u << 26)) return fail(c, MIRT_ERR_ARG, "more than 2^26 spheres");      // 32-bit record offsets in the trace kernels (GPU-built trees do not pass build_records)
+	if (a.n_nodes && !a.nodes) return fail(c, MIRT_ERR_ARG, "nodes is NULL");
+	if (!a.materials || a.n_materials == 0 || a.n_materials > MIRT_MAX_MATERIALS) return fail(c, MIRT_ERR_ARG, "need 1..%u materials, got %u", MIRT_MAX_MATERIALS, a.n_materials);
+	if (a.n_lights && !a.lights) return fail(c, MIRT_ERR_ARG, "lights is NULL");
+	if (!a.ambient_color || !a.hdri_rgba || a.hdri_w == 0 || a.hdri_h == 0) return fail(c, MIRT_ERR_ARG, "sky needs ambient_color and an hdri of at least 1x1");
+	for (uint32_t i = 0; i < a.n_spheres; i++) {
+		if (a.geometry[i].material_ID < 0 || static_cast<uint32_t>(a.geometry[i].material_ID) >= a.n_materials ||
+		    a.bvh_prims[i].material_ID < 0 || static_cast<uint32_t>(a.bvh_prims[i].material_ID) >= a.n_materials)
+			return fail(c, MIRT_ERR_ARG, "sphere %u: material_ID out of range", i);
+		// non-finite centres or radii would reach the tree builders' sorts and the box arithmetic as NaN (the reference has no check; UB there)
+		for (const mirt_sphere* s : { &a.geometry[i], &a.bvh_prims[i] })
+			if (!std::isfinite(s->position[0]) || !std::isfinite(s->position[1]) || !std::isfinite(s->position[2]) || !std::isfinite(s->radius_sq) || s->radius_sq < 0.0f)
+				return fail(c, MIRT_ERR_ARG, "sphere %u: position / radius_sq must be finite, radius_sq >= 0", i);
+	}
+	for (uint32_t i = 0; i < a.n_lights; i++)
+		if (a.lights[i] < 0 || static_cast<uint32_t>(a.lights[i]) >= a.n_spheres) return fail(c, MIRT_ERR_ARG, "light %u: index out of range", i);
+	// children point forward and every node has at most one parent: the node array is a forest, so the breadth-first
+	// re-layout (bvh_layout.hpp) visits at most n_nodes nodes (shared children would make it grow like Fibonacci numbers)
+	std::vector<uint8_t> has_parent(a.n_nodes, 0);
+	for (uint32_t i = 0; i < a.n_nodes; i++) {
+		const mirt_bvh_node& nd = a.nodes[i];
+		if (nd.prim_count == 0) {
+			if (nd.first_id <= i || static_cast<uint64_t>(nd.first_id) + 1 >= a.n_nodes) return fail(c, MIRT_ERR_ARG, "node %u: child index %u invalid", i, nd.first_id);
+			if (has_parent[nd.first_id] || has_parent[nd.first_id + 1]) return fail(c, MIRT_ERR_ARG, "node %u: child pair %u is referenced by more than one parent", i, nd.first_id);
+			has_parent[nd.first_id] = has_parent[nd.first_id + 1] = 1;
+		} else if (static_cast<uint64_t>(nd.first_id) + nd.prim_count > a.n_spheres) return fail(c, MIRT_ERR_ARG, "node %u: prim range out of bounds", i);
+	}
+	if (a.n_spheres && a.n_nodes == 0) return fail(c, MIRT_ERR_ARG, "spheres without BVH nodes");
+	return MIRT_OK;
+}
+
+// The scene's tables as the kernels read them (host copies: they outlive the stream synchronisation that ends their uploads).
+struct SceneTables {
+	std::vector<float4> sph, lsp, lem, alb, emi, ggx, sky;
+	std::vector<int32_t> pm;
+};
+SceneTables flatten_tables(const SceneArgs& a) {
+	SceneTables t;
+	t.sph.resize(a.n_spheres); t.pm.resize(a.n_spheres); t.lsp.resize(a.n_lights); t.lem.resize(a.n_lights);
+	t.alb.resize(a.n_materials); t.emi.resize(a.n_materials); t.ggx.resize(a.n_materials); t.sky.resize(static_cast<size_t>(a.hdri_w) * a.hdri_h);
+	for (uint32_t i = 0; i < a.n_spheres; i++) {
+		t.sph[i] = make_float4(a.bvh_prims[i].position[0], a.bvh_prims[i].position[1], a.bvh_prims[i].position[2], a.bvh_prims[i].radius_sq);
+		t.pm[i] = a.bvh_prims[i].material_ID;
+	}
+	// NEE reads scene.geometry[light], then material[geometry[light].material_ID].emission (Renderer.hpp:261-263,283):
+	// flattened to one table per light so the kernel makes two independent loads instead of four dependent ones
+	for (uint32_t l = 0; l < a.n_lights; l++) {
+		const mirt_sphere& g = a.geometry[a.lights[l]];
+		const float* e = a.materials[g.material_ID].emission;
+		t.lsp[l] = make_float4(g.position[0], g.position[1], g.position[2], g.radius_sq);
+		float id_bits; const int32_t id = a.lights[l]; std::memcpy(&id_bits, &id, 4);
+		t.lem[l] = make_float4(e[0], e[1], e[2], id_bits);
+	}
+	for (uint32_t i = 0; i < a.n_materials; i++) {
+		const mirt_material& m = a.materials[i];
+		t.alb[i] = make_float4(m.albedo[0], m.albedo[1], m.albedo[2], 0.0f);
+		t.emi[i] = make_float4(m.emission[0], m.emission[1], m.emission[2], 0.0f);
+		t.ggx[i] = make_float4(m.F0[0], m.F0[1], m.F0[2], m.roughness);   // Closure<GGX> (policy.brdf = 1)
+	}
+	std::memcpy(t.sky.data(), a.hdri_rgba, t.sky.size() * sizeof(float4));
+	return t;
+}
+
+// The records the kernels walk for this scene, uploaded (a host-built tree) or built in place (the GPU LBVH over c->spheres, uploaded by the caller).
+struct SceneRecords {
+	std::vector<float> f32;                 // host copies, as in SceneTables
+	std::vector<uint32_t> half, wide;
+	uint32_t n_recs = 0, depth = 0;
+	bool is_half = false, is_wide = false;
+	bool in_recs_wide = false;              // the records lie in c->recs_wide instead of c->recs (the GPU builder writes both layouts)
+};
+int build_scene_records(mirt_ctx* c, const SceneArgs& a, const std::vector<float4>& sph, SceneRecords& t) {
+	const uint32_t n_spheres = a.n_spheres;
+	if (c->policy.gpu_build && !c->policy.reference_tree && n_spheres >= 2) {
+		// the tree the kernels walk, built where it is used (lbvh_build.hip); binary16 records under the same conditions as on the host
+		t.n_recs = n_spheres - 1;
+		t.is_half = c->allow_half;
+		for (uint32_t i = 0; t.is_half && i < n_spheres; i++) {
+			const float rad = std::sqrt(sph[i].w);
+			const float amax = std::fmax(std::fmax(std::fabs(sph[i].x), std::fabs(sph[i].y)), std::fabs(sph[i].z)) + rad * 1.0001f;
+			t.is_half = mirt_host::half_box_adequate(amax, 2.0f * rad, true);
+		}
+		HIP_TRY(c, c->recs.ensure(static_cast<size_t>(t.n_recs) * (t.is_half ? 32u : 64u)));
+		const bool want_wide = t.is_half && c->tune_wide;                    // the 4-wide binary16 records as well (used when the tree is shallow enough)
+		if (want_wide) HIP_TRY(c, c->recs_wide.ensure(static_cast<size_t>(t.n_recs) * 64u));
+		std::string why;
+		uint32_t n_wide = 0;
+		if (!mirt_gpu::build_lbvh(c->stream, c->spheres.as<float4>(), n_spheres, t.is_half ? nullptr : c->recs.as<float>(), t.is_half ? c->recs.as<uint32_t>() : nullptr, &t.depth, &why,
+		                          want_wide ? c->recs_wide.as<uint32_t>() : nullptr, &n_wide))
+			return fail(c, MIRT_ERR_HIP, "GPU BVH build: %s", why.c_str());
+		if (t.depth >= kStack) return fail(c, MIRT_ERR_ARG, "GPU-built BVH is %u levels deep (limit %u): set policy.gpu_build = 0 for this scene", t.depth, kStack);
+		if (want_wide && n_wide && 3u * (t.depth / 2u) < kStack) { t.is_wide = t.in_recs_wide = true; t.n_recs = n_wide; }     // depth counts the leaf level: depth / 2 = wide levels, rounded up
+		return MIRT_OK;
+	}
+	std::vector<mirt_bvh_node> own; std::vector<uint32_t> prim_of_slot;
+	const bool caller_tree = c->policy.reference_tree || n_spheres == 0;
+	if (caller_tree) {
+		// traverse the caller's tree exactly as handed over (BVH.hpp:18-31 nodes over the BVH-order prims)
+		own.assign(a.nodes, a.nodes + a.n_nodes);
+		mirt_host::split_multi_prim_leaves(own);                         // the kernels know one-prim leaves only
+	} else {
+		// default: GPU-internal SAH tree over the same BVH-order prims (hit.primID keeps its meaning; results are identical)
+		mirt_host::build_sah_tree(a.bvh_prims, n_spheres, own, prim_of_slot);
+	}
+	const std::vector<uint32_t>* slot_map = caller_tree ? nullptr : &prim_of_slot;
+	const std::string why = mirt_host::build_records(own.data(), static_cast<uint32_t>(own.size()), a.bvh_prims, n_spheres, t.f32, &t.depth, slot_map);
+	if (!why.empty()) return fail(c, MIRT_ERR_ARG, "%s BVH rejected: %s", caller_tree ? "caller's" : "internal", why.c_str());
+	t.n_recs = static_cast<uint32_t>(t.f32.size() / 16);
+	t.is_half = c->allow_half && mirt_host::build_half_records(t.f32, t.half);
+	// 4-wide binary16 records when the tree allows (bvh_layout.hpp build_wide_half_records): half as many dependent fetches per ray
+	uint32_t wide_levels = 0;
+	t.is_wide = t.is_half && c->tune_wide && mirt_host::build_wide_half_records(t.f32, t.wide, &wide_levels);
+	if (t.is_wide) t.n_recs = static_cast<uint32_t>(t.wide.size() / 16);
+	return t.is_wide ? upload(c, c->recs, t.wide) : t.is_half ? upload(c, c->recs, t.half) : upload(c, c->recs, t.f32);
+}
+
+// The LDS staging plan of the scene just stored in c->scene, and room for it in every kernel that uses dynamic LDS.
+int plan_trace_lds(mirt_ctx* c) {
+	const LdsPlan p = lds_plan(c);
+	c->scene.stack16 = p.stack16; c->scene.lds_recs = p.lds_recs; c->scene.lds_spheres = p.lds_spheres;
+	const int lds_max = static_cast<int>(kLdsPerCu);
+	for (const auto& row : kTrace) for (const auto k : row) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+	for (const auto k : kPrimaryCand) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+	return MIRT_OK;
+}
+
+void commit_scene(mirt_ctx* c, const SceneArgs& a, const SceneRecords& t) {
+	SceneDev& s = c->scene;
+	s.recs = t.in_recs_wide ? c->recs_wide.as<float4>() : c->recs.as<float4>(); s.spheres = c->spheres.as<float4>(); s.prim_mat = c->prim_mat.as<int32_t>();
+	s.light_sphere = c->light_sphere.as<float4>(); s.light_emit = c->light_emit.as<float4>();
+	s.mat_albedo = c->mat_albedo.as<float4>(); s.mat_emission = c->mat_emission.as<float4>();
+	s.hdri = c->hdri.as<float4>();
+	s.n_spheres = a.n_spheres; s.n_recs = t.n_recs; s.n_mat = a.n_materials; s.n_lights = a.n_lights;
+	s.half_boxes = t.is_half ? 1u : 0u;
+	s.wide = t.is_wide ? 1u : 0u;
+	c->bvh_depth = t.depth;
+	for (int k = 0; k < 3; k++) s.ambient[k] = a.ambient_color[k];
+	s.hdri_w = static_cast<int32_t>(a.hdri_w); s.hdri_h = static_cast<int32_t>(a.hdri_h);
+	s.hdri_fw = static_cast<float>(static_cast<int32_t>(a.hdri_w) - 1);                 // Application.cpp:230-231
+	s.hdri_fh = static_cast<float>(static_cast<int32_t>(a.hdri_h) - 1);
+	{ const float x = a.ambient_color[0], y = a.ambient_color[1], z = a.ambient_color[2];
+	  const float m1 = (y < z) ? z : y; const float m0 = (x < m1) ? m1 : x; s.has_ambient = (m0 > 0.0f) ? 1u : 0u; }   // Renderer.hpp:79
+}
+
+// Body of mirt_debug_trace_closest (tfar = NULL; result: n HitRec) and mirt_debug_trace_shadow (result: n occlusion words): n caller-supplied
+// rays through the product's own k_trace and fat-ray pass, all of them in segment 0 of one queue (slot = ray number).
+int debug_trace(mirt_ctx* c, const char* who, size_t n, const float* p_xyz, const float* dir_xyz, const float* tfar, void* result) {
+	const bool shadow = tfar != nullptr;
+	const size_t result_bytes = n * (shadow ? sizeof(uint32_t) : sizeof(HitRec));
+	HIP_TRY(c, hipSetDevice(c->device));
+	ScopedBuffer rays, res, cnt, ctr, fat;
+	HIP_TRY(c, rays.ensure(n * (shadow ? 7 : 6) * 4)); HIP_TRY(c, res.ensure(result_bytes)); HIP_TRY(c, cnt.ensure(BatchCounters::words(1) * 4));
+	HIP_TRY(c, ctr.ensure(sizeof(DevCounters))); HIP_TRY(c, fat.ensure(2u * kFatCapacity * sizeof(uint32_t)));
+	float* d = rays.as<float>();
+	HIP_TRY(c, hipMemcpy(d, p_xyz, n * 12, hipMemcpyHostToDevice));
+	HIP_TRY(c, hipMemcpy(d + 3 * n, dir_xyz, n * 12, hipMemcpyHostToDevice));
+	if (shadow) HIP_TRY(c, hipMemcpy(d + 6 * n, tfar, n * 4, hipMemcpyHostToDevice));
+	const BatchCounters bc{ cnt.as<uint32_t>(), 1u, 0u };
+	const uint32_t n32 = static_cast<uint32_t>(n);
+	HIP_TRY(c, hipMemset(cnt.ptr, 0, BatchCounters::words(1) * 4));
+	HIP_TRY(c, hipMemcpy(shadow ? bc.shadow_queue(0).n : bc.stream_queue(0).n, &n32, 4, hipMemcpyHostToDevice));
+	HIP_TRY(c, hipMemset(ctr.ptr, 0, sizeof(DevCounters)));
+	TraceLaunch tl{};
+	if (shadow) { tl.sh.px = d; tl.sh.py = d + n; tl.sh.pz = d + 2 * n; tl.sh.dx = d + 3 * n; tl.sh.dy = d + 4 * n; tl.sh.dz = d + 5 * n; tl.sh.tfar = d + 6 * n; tl.sink.occ = res.as<uint32_t>(); }   // the sink only records the occlusion flags
+	else { tl.in.px = d; tl.in.py = d + n; tl.in.pz = d + 2 * n; tl.in.dx = d + 3 * n; tl.in.dy = d + 4 * n; tl.in.dz = d + 5 * n; tl.hit = res.as<HitRec>(); }
+	tl.closest_queue = bc.stream_queue(0); tl.closest_work = bc.closest_work(0);
+	tl.shadow_queue = bc.shadow_queue(0); tl.shadow_work = bc.shadow_work(0);
+	tl.fat_closest = bc.fat_closest(0, fat.as<uint32_t>()); tl.fat_shadow = bc.fat_shadow(0, fat.as<uint32_t>());
+	tl.ctr = ctr.as<DevCounters>();                                              // scratch: the context's counters stay as they are
+	{ Bracket t(c, MIRT_K_TRACE);                                                // policy.profile: the launch is timed like those of a batch (mirt_get_kernel_times)
+	  launch_trace(c, c->stream, trace_scene(c), FrameParams{}, n, false, kPrimaryNone, tl); }
+	hipError_t e = hipGetLastError();
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	if (e == hipSuccess) e = hipMemcpy(result, res.ptr, result_bytes, hipMemcpyDeviceToHost);
+	if (e != hipSuccess) return fail(c, MIRT_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+	return MIRT_OK;
 }
 
 } // namespace
@@ -581,144 +821,17 @@ int mirt_set_scene(mirt_ctx* c, const mirt_sphere* geometry, const mirt_sphere* 
                    const float* hdri_rgba, uint32_t hdri_w, uint32_t hdri_h) {
 	if (!c) return MIRT_ERR_ARG;
 	{ const int fr = flush_deferred(c); if (fr) return fr; }
-	if (n_spheres && (!geometry || !bvh_prims)) return fail(c, MIRT_ERR_ARG, "geometry / bvh_prims is NULL");
-	if (n_spheres >= (1u << 26)) return fail(c, MIRT_ERR_ARG, "more than 2^26 spheres");      // 32-bit record offsets in the trace kernels (GPU-built trees do not pass build_records)
-	if (n_nodes && !nodes) return fail(c, MIRT_ERR_ARG, "nodes is NULL");
-	if (!materials || n_materials == 0 || n_materials > MIRT_MAX_MATERIALS) return fail(c, MIRT_ERR_ARG, "need 1..%u materials, got %u", MIRT_MAX_MATERIALS, n_materials);
-	if (n_lights && !lights) return fail(c, MIRT_ERR_ARG, "lights is NULL");
-	if (!ambient_color || !hdri_rgba || hdri_w == 0 || hdri_h == 0) return fail(c, MIRT_ERR_ARG, "sky needs ambient_color and an hdri of at least 1x1");
-	// Validate everything the kernels index with: an out-of-range id would fault the GPU.
-	for (uint32_t i = 0; i < n_spheres; i++) {
-		if (geometry[i].material_ID < 0 || static_cast<uint32_t>(geometry[i].material_ID) >= n_materials ||
-		    bvh_prims[i].material_ID < 0 || static_cast<uint32_t>(bvh_prims[i].material_ID) >= n_materials)
-			return fail(c, MIRT_ERR_ARG, "sphere %u: material_ID out of range", i);
-		// non-finite centres or radii would reach the tree builders' sorts and the box arithmetic as NaN (the reference has no check; UB there)
-		for (const mirt_sphere* s : { &geometry[i], &bvh_prims[i] })
-			if (!std::isfinite(s->position[0]) || !std::isfinite(s->position[1]) || !std::isfinite(s->position[2]) || !std::isfinite(s->radius_sq) || s->radius_sq < 0.0f)
-				return fail(c, MIRT_ERR_ARG, "sphere %u: position / radius_sq must be finite, radius_sq >= 0", i);
-	}
-	for (uint32_t i = 0; i < n_lights; i++)
-		if (lights[i] < 0 || static_cast<uint32_t>(lights[i]) >= n_spheres) return fail(c, MIRT_ERR_ARG, "light %u: index out of range", i);
-	{
-		// children point forward and every node has at most one parent: the node array is a forest, so the breadth-first
-		// re-layout (bvh_layout.hpp) visits at most n_nodes nodes (shared children would make it grow like Fibonacci numbers)
-		std::vector<uint8_t> has_parent(n_nodes, 0);
-		for (uint32_t i = 0; i < n_nodes; i++) {
-			const mirt_bvh_node& nd = nodes[i];
-			if (nd.prim_count == 0) {
-				if (nd.first_id <= i || static_cast<uint64_t>(nd.first_id) + 1 >= n_nodes) return fail(c, MIRT_ERR_ARG, "node %u: child index %u invalid", i, nd.first_id);
-				if (has_parent[nd.first_id] || has_parent[nd.first_id + 1]) return fail(c, MIRT_ERR_ARG, "node %u: child pair %u is referenced by more than one parent", i, nd.first_id);
-				has_parent[nd.first_id] = has_parent[nd.first_id + 1] = 1;
-			} else if (static_cast<uint64_t>(nd.first_id) + nd.prim_count > n_spheres) return fail(c, MIRT_ERR_ARG, "node %u: prim range out of bounds", i);
-		}
-	}
-	if (n_spheres && n_nodes == 0) return fail(c, MIRT_ERR_ARG, "spheres without BVH nodes");
+	const SceneArgs a{ geometry, bvh_prims, n_spheres, nodes, n_nodes, materials, n_materials, lights, n_lights, ambient_color, hdri_rgba, hdri_w, hdri_h };
+	int r = check_scene_args(c, a); if (r) return r;
 	HIP_TRY(c, hipSetDevice(c->device));
-
-	std::vector<float4> sph(n_spheres), lsp(n_lights), lem(n_lights), alb(n_materials), emi(n_materials), ggx(n_materials), sky(static_cast<size_t>(hdri_w) * hdri_h);
-	std::vector<int32_t> pm(n_spheres);
-	for (uint32_t i = 0; i < n_spheres; i++) {
-		sph[i] = make_float4(bvh_prims[i].position[0], bvh_prims[i].position[1], bvh_prims[i].position[2], bvh_prims[i].radius_sq);
-		pm[i] = bvh_prims[i].material_ID;
-	}
-	// NEE reads scene.geometry[light], then material[geometry[light].material_ID].emission (Renderer.hpp:261-263,283):
-	// flattened to one table per light so the kernel makes two independent loads instead of four dependent ones
-	for (uint32_t l = 0; l < n_lights; l++) {
-		const mirt_sphere& g = geometry[lights[l]];
-		const float* e = materials[g.material_ID].emission;
-		lsp[l] = make_float4(g.position[0], g.position[1], g.position[2], g.radius_sq);
-		float id_bits; const int32_t id = lights[l]; std::memcpy(&id_bits, &id, 4);
-		lem[l] = make_float4(e[0], e[1], e[2], id_bits);
-	}
-	for (uint32_t i = 0; i < n_materials; i++) {
-		alb[i] = make_float4(materials[i].albedo[0], materials[i].albedo[1], materials[i].albedo[2], 0.0f);
-		emi[i] = make_float4(materials[i].emission[0], materials[i].emission[1], materials[i].emission[2], 0.0f);
-		ggx[i] = make_float4(materials[i].F0[0], materials[i].F0[1], materials[i].F0[2], materials[i].roughness);   // Closure<GGX> (policy.brdf = 1)
-	}
-	std::memcpy(sky.data(), hdri_rgba, sky.size() * sizeof(float4));
-	std::vector<float> recs;
-	std::vector<uint32_t> half_recs, wide_recs;
-	uint32_t depth = 0, n_recs = 0;
-	bool half = false, wide = false, wide_gpu = false;
-	int r;
-	if ((r = upload(c, c->spheres, sph))) return r;
-	const bool gpu_tree = c->policy.gpu_build && !c->policy.reference_tree && n_spheres >= 2;
-	if (gpu_tree) {
-		// the tree the kernels walk, built where it is used (lbvh_build.hip); binary16 records under the same conditions as on the host
-		n_recs = n_spheres - 1;
-		half = c->allow_half;
-		for (uint32_t i = 0; half && i < n_spheres; i++) {
-			const float rad = std::sqrt(sph[i].w);
-			const float amax = std::fmax(std::fmax(std::fabs(sph[i].x), std::fabs(sph[i].y)), std::fabs(sph[i].z)) + rad * 1.0001f;
-			if (amax > 60000.0f || 2.0f * rad < 8.0f * mirt_host::half_ulp_at(amax)) half = false;
-		}
-		HIP_TRY(c, c->recs.ensure(static_cast<size_t>(n_recs) * (half ? 32u : 64u)));
-		const bool want_wide = half && c->tune_wide;                         // the 4-wide binary16 records as well (used when the tree is shallow enough)
-		if (want_wide) HIP_TRY(c, c->recs_wide.ensure(static_cast<size_t>(n_recs) * 64u));
-		std::string why;
-		uint32_t n_wide = 0;
-		if (!mirt_gpu::build_lbvh(c->stream, c->spheres.as<float4>(), n_spheres, half ? nullptr : c->recs.as<float>(), half ? c->recs.as<uint32_t>() : nullptr, &depth, &why,
-		                          want_wide ? c->recs_wide.as<uint32_t>() : nullptr, &n_wide))
-			return fail(c, MIRT_ERR_HIP, "GPU BVH build: %s", why.c_str());
-		if (depth >= kStack) return fail(c, MIRT_ERR_ARG, "GPU-built BVH is %u levels deep (limit %u): set policy.gpu_build = 0 for this scene", depth, kStack);
-		if (want_wide && n_wide && 3u * (depth / 2u) < kStack) { wide = true; wide_gpu = true; n_recs = n_wide; }     // depth counts the leaf level: depth / 2 = wide levels, rounded up
-	} else {
-		std::vector<mirt_bvh_node> own; std::vector<uint32_t> prim_of_slot;
-		const bool caller_tree = c->policy.reference_tree || n_spheres == 0;
-		if (caller_tree) {
-			// traverse the caller's tree exactly as handed over (BVH.hpp:18-31 nodes over the BVH-order prims)
-			own.assign(nodes, nodes + n_nodes);
-			mirt_host::split_multi_prim_leaves(own);                         // the kernels know one-prim leaves only
-		} else {
-			// default: GPU-internal SAH tree over the same BVH-order prims (hit.primID keeps its meaning; results are identical)
-			mirt_host::build_sah_tree(bvh_prims, n_spheres, own, prim_of_slot);
-		}
-		const std::vector<uint32_t>* slot_map = caller_tree ? nullptr : &prim_of_slot;
-		const std::string why = mirt_host::build_records(own.data(), static_cast<uint32_t>(own.size()), bvh_prims, n_spheres, recs, &depth, slot_map);
-		if (!why.empty()) return fail(c, MIRT_ERR_ARG, "%s BVH rejected: %s", caller_tree ? "caller's" : "internal", why.c_str());
-		n_recs = static_cast<uint32_t>(recs.size() / 16);
-		half = c->allow_half && mirt_host::build_half_records(recs, half_recs);
-		// 4-wide binary16 records when the tree allows (bvh_layout.hpp build_wide_half_records): half as many dependent fetches per ray
-		uint32_t wide_levels = 0;
-		wide = half && c->tune_wide && mirt_host::build_wide_half_records(recs, wide_recs, &wide_levels);
-		if (wide) n_recs = static_cast<uint32_t>(wide_recs.size() / 16);
-		if ((r = wide ? upload(c, c->recs, wide_recs) : half ? upload(c, c->recs, half_recs) : upload(c, c->recs, recs))) return r;
-	}
-	if ((r = upload(c, c->prim_mat, pm)) ||
-	    (r = upload(c, c->light_sphere, lsp)) || (r = upload(c, c->light_emit, lem)) || (r = upload(c, c->mat_albedo, alb)) ||
-	    (r = upload(c, c->mat_emission, emi)) || (r = upload(c, c->mat_ggx, ggx)) || (r = upload(c, c->hdri, sky))) return r;
+	const SceneTables t = flatten_tables(a);     // host copies of tables and records: alive until the stream has been synchronised
+	SceneRecords tree;
+	if ((r = upload(c, c->spheres, t.sph)) || (r = build_scene_records(c, a, t.sph, tree)) || (r = upload(c, c->prim_mat, t.pm)) ||
+	    (r = upload(c, c->light_sphere, t.lsp)) || (r = upload(c, c->light_emit, t.lem)) || (r = upload(c, c->mat_albedo, t.alb)) ||
+	    (r = upload(c, c->mat_emission, t.emi)) || (r = upload(c, c->mat_ggx, t.ggx)) || (r = upload(c, c->hdri, t.sky))) return r;
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
-
-	SceneDev& s = c->scene;
-	s.recs = wide_gpu ? c->recs_wide.as<float4>() : c->recs.as<float4>(); s.spheres = c->spheres.as<float4>(); s.prim_mat = c->prim_mat.as<int32_t>();
-	s.light_sphere = c->light_sphere.as<float4>(); s.light_emit = c->light_emit.as<float4>();
-	s.mat_albedo = c->mat_albedo.as<float4>(); s.mat_emission = c->mat_emission.as<float4>();
-	s.hdri = c->hdri.as<float4>();
-	s.n_spheres = n_spheres; s.n_recs = n_recs; s.n_mat = n_materials; s.n_lights = n_lights;
-	c->bvh_depth = depth;
-	// LDS staging plan: the whole tree and every sphere packet when they fit the budget (1k spheres: 64 + 16 KB),
-	// otherwise the top of the tree only (records are breadth-first) and spheres from L2.
-	s.half_boxes = half ? 1u : 0u;
-	s.wide = wide ? 1u : 0u;
-	s.stack16 = (half && n_recs <= 32768 && n_spheres <= 32768) ? 1u : 0u;     // a stack entry = 15-bit record or prim index + the leaf flag
-	const uint32_t rec_bytes = (half && !wide) ? 32u : 64u, budget = stage_budget(half, s.stack16 != 0);
-	if (static_cast<uint64_t>(n_recs) * rec_bytes + static_cast<uint64_t>(n_spheres) * 16u <= budget) { s.lds_recs = n_recs; s.lds_spheres = n_spheres; }
-	else { s.lds_recs = std::min<uint32_t>(n_recs, budget / rec_bytes); s.lds_spheres = 0; }
-	c->trace_lds_bytes = s.lds_recs * rec_bytes + s.lds_spheres * 16u;
-	{
-		const int lds_max = static_cast<int>(kLdsPerCu);
-		const void* dyn_lds_kernels[] = { reinterpret_cast<const void*>(&k_trace<true, kPrimaryNone>), reinterpret_cast<const void*>(&k_trace<false, kPrimaryNone>),
-		                                  reinterpret_cast<const void*>(&k_trace<true, kPrimaryAll>), reinterpret_cast<const void*>(&k_trace<false, kPrimaryAll>),
-		                                  reinterpret_cast<const void*>(&k_trace<true, kPrimaryList>), reinterpret_cast<const void*>(&k_trace<false, kPrimaryList>),
-		                                  reinterpret_cast<const void*>(&k_primary_cand<true>), reinterpret_cast<const void*>(&k_primary_cand<false>) };
-		for (const void* k : dyn_lds_kernels) HIP_TRY(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-	}
-	for (int k = 0; k < 3; k++) s.ambient[k] = ambient_color[k];
-	s.hdri_w = static_cast<int32_t>(hdri_w); s.hdri_h = static_cast<int32_t>(hdri_h);
-	s.hdri_fw = static_cast<float>(static_cast<int32_t>(hdri_w) - 1);                 // Application.cpp:230-231
-	s.hdri_fh = static_cast<float>(static_cast<int32_t>(hdri_h) - 1);
-	{ const float a = ambient_color[0], b = ambient_color[1], d = ambient_color[2];
-	  const float m1 = (b < d) ? d : b; const float m0 = (a < m1) ? m1 : a; s.has_ambient = (m0 > 0.0f) ? 1u : 0u; }   // Renderer.hpp:79
+	commit_scene(c, a, tree);
+	if ((r = plan_trace_lds(c))) return r;
 	c->have_scene = true;
 	return MIRT_OK;
 }
@@ -951,7 +1064,7 @@ int mirt_debug_raygen(mirt_ctx* c, uint32_t accumulations, float* p_xyz, float* 
 	const FrameParams fp = frame_params(c, accumulations - 1, 1);
 	const size_t n = fp.n_pix;
 	HIP_TRY(c, sync_all(c));
-	hipLaunchKernelGGL(k_raygen, dim3(grid_for(c, n)), dim3(kBlock), 0, c->stream, fp, c->slots[0].stream_buf[0], c->slots[0].counts.as<uint32_t>());
+	hipLaunchKernelGGL(k_raygen, dim3(grid_for(c, n)), dim3(kBlock), 0, c->stream, fp, c->slots[0].stream_buf[0], batch_counters(c, c->slots[0]).stream_queue(0).n);
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	const StreamBuf& s = c->slots[0].stream_buf[0];
@@ -967,74 +1080,20 @@ int mirt_debug_trace_closest(mirt_ctx* c, size_t n, const float* p_xyz, const fl
 	if (!c) return MIRT_ERR_ARG;
 	if (!c->have_scene) return fail(c, MIRT_ERR_STATE, "mirt_set_scene has not been called");
 	if (!p_xyz || !dir_xyz || !tfar_out || !prim_out || n == 0 || n >= (1ull << 31)) return fail(c, MIRT_ERR_ARG, "bad arguments");
-	HIP_TRY(c, hipSetDevice(c->device));
-	ScopedBuffer rays, res, cnt, ctr, fat;
-	constexpr size_t kCntWords = 2 * kQueueWords + 8;      // closest queue | shadow queue | work counter x2, fat count x2
-	HIP_TRY(c, rays.ensure(n * 6 * 4)); HIP_TRY(c, res.ensure(n * 8)); HIP_TRY(c, cnt.ensure(kCntWords * 4));
-	HIP_TRY(c, hipMemset(cnt.ptr, 0, kCntWords * 4));
-	float* d = rays.as<float>();
-	HIP_TRY(c, hipMemcpy(d, p_xyz, n * 12, hipMemcpyHostToDevice));
-	HIP_TRY(c, hipMemcpy(d + 3 * n, dir_xyz, n * 12, hipMemcpyHostToDevice));
-	const uint32_t n32 = static_cast<uint32_t>(n);
-	uint32_t* cn = cnt.as<uint32_t>();
-	HIP_TRY(c, hipMemcpy(cn, &n32, 4, hipMemcpyHostToDevice));                 // all n rays in segment 0 of the closest queue: slot = ray number
-	StreamBuf in{};
-	in.px = d; in.py = d + n; in.pz = d + 2 * n; in.dx = d + 3 * n; in.dy = d + 4 * n; in.dz = d + 5 * n;
-	SceneDev sc = c->scene; sc.use_bvh = c->policy.use_bvh; sc.chunk_max = c->tune_chunk; sc.leaf_batch = c->tune_leaf_batch; sc.refill_idle = c->tune_refill_idle;
-	DevCounters* scratch_ctr = nullptr;
-	HIP_TRY(c, ctr.ensure(sizeof(DevCounters))); scratch_ctr = ctr.as<DevCounters>();
-	HIP_TRY(c, hipMemset(scratch_ctr, 0, sizeof(DevCounters)));
-	HIP_TRY(c, fat.ensure(2u * kFatCapacity * sizeof(uint32_t)));
-	uint32_t* misc = cn + 2 * kQueueWords;
-	const FatList fc{ misc + 2, fat.as<uint32_t>(), kFatCapacity }, fs{ misc + 3, fat.as<uint32_t>() + kFatCapacity, kFatCapacity };
-	{ Bracket t(c, MIRT_K_TRACE);                                               // policy.profile: the launch is timed like those of a batch (mirt_get_kernel_times)
-	hipLaunchKernelGGL((k_trace<false, kPrimaryNone>), dim3(trace_grid(c, n)), dim3(kTraceBlock), trace_lds(c), c->stream, sc, FrameParams{}, in, res.as<HitRec>(),
-	                   Queue{ cn, 0u }, misc, ShadowBuf{}, ShadowSink{}, Queue{ cn + kQueueWords, 0u }, misc + 1, fc, fs, scratch_ctr);
-	if (sc.use_bvh) hipLaunchKernelGGL((k_trace_fat<false, kPrimaryNone>), dim3(64), dim3(1024), 0, c->stream, sc, FrameParams{}, in, res.as<HitRec>(), fc, ShadowBuf{}, ShadowSink{}, fs, scratch_ctr, static_cast<const uint32_t*>(nullptr)); }
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-	std::vector<HitRec> host_hits(n);
-	if (e == hipSuccess) e = hipMemcpy(host_hits.data(), res.ptr, n * sizeof(HitRec), hipMemcpyDeviceToHost);
-	if (e == hipSuccess) for (size_t i = 0; i < n; i++) { tfar_out[i] = host_hits[i].tfar; prim_out[i] = host_hits[i].prim; }
-	if (e != hipSuccess) return fail(c, MIRT_ERR_HIP, "debug_trace_closest: %s", hipGetErrorString(e));
-	return MIRT_OK;
+	std::vector<HitRec> hits(n);
+	const int r = debug_trace(c, "debug_trace_closest", n, p_xyz, dir_xyz, nullptr, hits.data());
+	if (r == MIRT_OK) for (size_t i = 0; i < n; i++) { tfar_out[i] = hits[i].tfar; prim_out[i] = hits[i].prim; }
+	return r;
 }
 
 int mirt_debug_trace_shadow(mirt_ctx* c, size_t n, const float* p_xyz, const float* dir_xyz, const float* tfar, uint8_t* occluded_out) {
 	if (!c) return MIRT_ERR_ARG;
 	if (!c->have_scene) return fail(c, MIRT_ERR_STATE, "mirt_set_scene has not been called");
 	if (!p_xyz || !dir_xyz || !tfar || !occluded_out || n == 0 || n >= (1ull << 31)) return fail(c, MIRT_ERR_ARG, "bad arguments");
-	HIP_TRY(c, hipSetDevice(c->device));
-	ScopedBuffer rays, occ, cnt, ctr, fat;
-	constexpr size_t kCntWords = 2 * kQueueWords + 8;      // closest queue (empty) | shadow queue | work counter x2, fat count x2
-	HIP_TRY(c, rays.ensure(n * 7 * 4)); HIP_TRY(c, occ.ensure(n * 4)); HIP_TRY(c, cnt.ensure(kCntWords * 4)); HIP_TRY(c, ctr.ensure(sizeof(DevCounters)));
-	HIP_TRY(c, fat.ensure(2u * kFatCapacity * sizeof(uint32_t)));
-	float* d = rays.as<float>();
-	HIP_TRY(c, hipMemcpy(d, p_xyz, n * 12, hipMemcpyHostToDevice));
-	HIP_TRY(c, hipMemcpy(d + 3 * n, dir_xyz, n * 12, hipMemcpyHostToDevice));
-	HIP_TRY(c, hipMemcpy(d + 6 * n, tfar, n * 4, hipMemcpyHostToDevice));
-	HIP_TRY(c, hipMemset(cnt.ptr, 0, kCntWords * 4));
-	uint32_t* cn = cnt.as<uint32_t>();
-	const uint32_t n32 = static_cast<uint32_t>(n);
-	HIP_TRY(c, hipMemcpy(cn + kQueueWords, &n32, 4, hipMemcpyHostToDevice));   // all n rays in segment 0 of the shadow queue
-	HIP_TRY(c, hipMemset(ctr.ptr, 0, sizeof(DevCounters)));
-	SceneDev sc = c->scene; sc.use_bvh = c->policy.use_bvh; sc.chunk_max = c->tune_chunk; sc.leaf_batch = c->tune_leaf_batch; sc.refill_idle = c->tune_refill_idle;
-	ShadowBuf sh{}; sh.px = d; sh.py = d + n; sh.pz = d + 2 * n; sh.dx = d + 3 * n; sh.dy = d + 4 * n; sh.dz = d + 5 * n; sh.tfar = d + 6 * n;
-	uint32_t* misc = cn + 2 * kQueueWords;
-	const FatList fc{ misc + 2, fat.as<uint32_t>(), kFatCapacity }, fs{ misc + 3, fat.as<uint32_t>() + kFatCapacity, kFatCapacity };
-	// the product's own kernels: the shadow queue of k_trace, then the fat-ray pass; the sink only records the occlusion flags
-	ShadowSink sink{}; sink.occ = occ.as<uint32_t>();
-	{ Bracket t(c, MIRT_K_TRACE);
-	hipLaunchKernelGGL((k_trace<false, kPrimaryNone>), dim3(trace_grid(c, n)), dim3(kTraceBlock), trace_lds(c), c->stream, sc, FrameParams{}, StreamBuf{}, static_cast<HitRec*>(nullptr),
-	                   Queue{ cn, 0u }, misc, sh, sink, Queue{ cn + kQueueWords, 0u }, misc + 1, fc, fs, ctr.as<DevCounters>());
-	if (sc.use_bvh) hipLaunchKernelGGL((k_trace_fat<false, kPrimaryNone>), dim3(64), dim3(1024), 0, c->stream, sc, FrameParams{}, StreamBuf{}, static_cast<HitRec*>(nullptr), fc, sh, sink, fs, ctr.as<DevCounters>(), static_cast<const uint32_t*>(nullptr)); }
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-	std::vector<uint32_t> host_occ(n);
-	if (e == hipSuccess) e = hipMemcpy(host_occ.data(), occ.ptr, n * 4, hipMemcpyDeviceToHost);
-	if (e == hipSuccess) for (size_t i = 0; i < n; i++) occluded_out[i] = host_occ[i] ? 1 : 0;
-	if (e != hipSuccess) return fail(c, MIRT_ERR_HIP, "debug_trace_shadow: %s", hipGetErrorString(e));
-	return MIRT_OK;
+	std::vector<uint32_t> occ(n);
+	const int r = debug_trace(c, "debug_trace_shadow", n, p_xyz, dir_xyz, tfar, occ.data());
+	if (r == MIRT_OK) for (size_t i = 0; i < n; i++) occluded_out[i] = occ[i] ? 1 : 0;
+	return r;
 }
 
 int mirt_debug_math(mirt_ctx* c, int fn, size_t n, const float* in, float* out) {
@@ -1063,12 +1122,14 @@ int mirt_debug_primary_lists(mirt_ctx* c, uint32_t hist[10]) {
 	HIP_TRY(c, sync_all(c));
 	PipeSlot& sl = c->slots[0];
 	const FrameParams fp = frame_params(c, 0, 1);
-	SceneDev sc = c->scene; sc.use_bvh = 1; sc.chunk_max = c->tune_chunk; sc.leaf_batch = c->tune_leaf_batch; sc.refill_idle = c->tune_refill_idle;
-	uint32_t* misc = sl.counts.as<uint32_t>();
-	HIP_TRY(c, hipMemsetAsync(misc, 0, 64, c->stream));
-	const float rho = bundle_half_angle(c);
-	const FatList none{ misc + 1, sl.fat.as<uint32_t>(), 0u };
-	hipLaunchKernelGGL(k_primary_cand<false>, dim3(trace_grid(c, fp.n_pix)), dim3(kTraceBlock), trace_lds(c), c->stream, sc, fp, sl.cand.as<uint32_t>(), rho, misc, none, c->counters.as<DevCounters>(), static_cast<uint32_t*>(nullptr), misc + 2);
+	SceneDev sc = trace_scene(c);
+	sc.use_bvh = 1;                                                                    // (checked above: the launch's LDS is the tree's either way)
+	const BatchCounters bc = batch_counters(c, sl);
+	HIP_TRY(c, hipMemsetAsync(bc.w, 0, BatchCounters::words(bc.nb) * sizeof(uint32_t), c->stream));
+	const FatList none{ bc.unused_fat_count(), sl.fat.as<uint32_t>(), 0u };
+	const bool count = false;
+	hipLaunchKernelGGL(kPrimaryCand[!count], dim3(trace_grid(c, fp.n_pix)), dim3(kTraceBlock), trace_lds(c), c->stream, sc, fp, sl.cand.as<uint32_t>(), bundle_half_angle(c),
+	                   bc.cand_work(), none, c->counters.as<DevCounters>(), static_cast<uint32_t*>(nullptr), bc.listed_pixels());
 	HIP_TRY(c, hipGetLastError());
 	std::vector<uint32_t> host(static_cast<size_t>(fp.n_pix));                            // plane 0 of the lists: the counts
 	HIP_TRY(c, hipMemcpyAsync(host.data(), sl.cand.ptr, host.size() * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1081,10 +1142,9 @@ int mirt_debug_primary_lists(mirt_ctx* c, uint32_t hist[10]) {
 int mirt_debug_info(mirt_ctx* c, uint32_t out[8]) {
 	if (!c || !out) return MIRT_ERR_ARG;
 	const SceneDev& s = c->scene;
-	uint32_t per_cu = kLdsPerCu / std::max<uint32_t>(trace_lds(c), 1u);
-	per_cu = std::min<uint32_t>(std::max<uint32_t>(per_cu, 1u), c->tune_trace_wgs);
+	const LdsPlan p = lds_plan(c);
 	out[0] = s.n_recs; out[1] = s.lds_recs; out[2] = s.lds_spheres; out[3] = c->bvh_depth; out[4] = s.half_boxes | (s.wide << 1);
-	out[5] = trace_lds(c); out[6] = per_cu; out[7] = static_cast<uint32_t>(c->n_cu);
+	out[5] = p.launch_bytes; out[6] = p.wgs_per_cu; out[7] = static_cast<uint32_t>(c->n_cu);
 	return MIRT_OK;
 }
 int mirt_debug_allow_half_boxes(mirt_ctx* c, int allow) { if (!c) return MIRT_ERR_ARG; c->allow_half = allow != 0; return MIRT_OK; }
