@@ -8,8 +8,8 @@
 //
 //   k_trace           Traverse (BVH.hpp:309-360) for the rays of bounce b: reads p,dir, writes tfar,primID — and, in the
 //                     same launch, Traverse_shadow (BVH.hpp:362-404) for the NEE rays of bounce b-1, each followed by
-//                     Renderer.hpp:304-314 and the deferred radiance finalisation ((R + unoccluded NEE) + emissive) in the
-//                     reference's add order
+//                     Renderer.hpp:304-314 and the deferred adds ((R + unoccluded NEE) + emissive, the reference's order) into
+//                     the path's word of the batch's contribution buffer, where its radiance R lives from bounce 0 on
 //   k_shade           Renderer.hpp:169-431 except the shadow-dependent adds; compacts survivors into the next stream and
 //                     NEE candidates into the shadow stream (wave64 ballot + mbcnt prefix sums, one atomic per workgroup)
 //   k_primary_cand /  bounce 0 only (RAY GENERATION + the first Traverse, Renderer.hpp:113-127,165): the camera rays have no stream — a
@@ -35,7 +35,7 @@ constexpr uint32_t kLeafBit = 0x80000000u;      // child reference flag (bvh_lay
 constexpr uint32_t kTileSize = 256;
 constexpr uint32_t kTileRoot = 16;
 constexpr uint32_t kStack = 64;                 // Stack<StackFrame,64>, BVH.hpp:321
-constexpr uint32_t kDestAccum = 0x80000000u;    // shadow-entry destination flag: accumulator instead of stream slot
+constexpr uint32_t kDestAccum = 0x80000000u;    // shadow-entry destination flag: the path ended at this hit — path id instead of stream slot
 
 struct SceneDev {
 	const float4* recs;         // GPU-internal child-pair records, 4 float4 each, breadth-first (bvh_layout.hpp)
@@ -66,22 +66,20 @@ struct SceneDev {
 struct StreamBuf {
 	float *px, *py, *pz, *dx, *dy, *dz;
 	float *tr, *tg, *tb;        // throughput
-	float *rr, *rg, *rb;        // radiance
+	                            // (radiance has no plane: a path's running sum is its word of the contribution buffer, contrib_index)
 	                            // (`pdf` has no plane: Closure::pdf of the sampled direction is (1/pi) max(0, dir.z) of the WORLD-space dir
 	                            //  (Q8, Renderer.hpp:386,401), a function of the stored direction, recomputed by the bounce that needs it)
 	uint32_t* path;             // (batch slot << FrameParams::pix_bits) | local pixel index (tile_local*256 + ID); stands in for pixelID + seed[]
 };
 // RayStream<>::ShadowStream, DataStreams.hpp:113-126, plus the deferred-add operands.  A record is 32 B for the common case
 // (dir, tfar, NEE radiance, destination): the origin is the surviving ray's own (read from the next stream through `dest`;
-// stored here only for paths that Russian roulette ended), and the path radiance waits in the surviving ray's radiance word
-// (or the path's own result word when the path ended at this hit).
+// stored here only for paths that Russian roulette ended), and the path radiance waits in the path's contribution word.
 struct ShadowBuf {
 	float *px, *py, *pz;        // origin — written only when dest is the accumulator (no surviving ray to share it with)
 	float *dx, *dy, *dz, *tfar;
 	float *sr, *sg, *sb;        // NEE radiance carried by the shadow ray
-	float *rr, *rg, *rb;        // kDestFull records only: path radiance before this bounce's adds
 	float *er, *eg, *eb;        // kDestFull records only: emissive add of this bounce
-	uint32_t* dest;             // next-stream slot, or kDestAccum | path id; | kDestFull
+	uint32_t* dest;             // next-stream slot (the path survived), or kDestAccum | path id (it ended); | kDestFull
 };
 struct FrameParams {
 	CameraParams cam;
@@ -93,9 +91,7 @@ struct FrameParams {
 	uint32_t pix_bits;          // a path id is (batch slot << pix_bits) | local pixel, below 2^30: the fewer pixels a context owns, the more
 	uint32_t pix_mask;          // accumulations fit a batch ((1 << pix_bits) - 1)
 	uint32_t acc_base;          // `accumulations` before this batch
-	uint32_t batch_n;           // accumulations in flight in this batch
-	uint32_t idx_base;          // where the paths' radiance goes (path_result): added straight into the accumulator (idx_base = acc_base,
-	uint32_t idx_buckets;       // idx_buckets = buckets) or stored into this batch's contribution buffer [tile][slot][256][rgb] (kIdxContrib, batch_n)
+	uint32_t batch_n;           // accumulations in flight in this batch = slots of its contribution buffer [tile][slot][256][rgb]
 	uint32_t max_bounces;
 	uint32_t buckets;
 	uint32_t mis;               // MIS && light_count > 0 (Q12 guard)
@@ -825,65 +821,39 @@ MIRT_DI void trace_queue(const SceneDev& sc, const TraceLds tl, const Queue& q, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Accumulator addressing + the deferred shadow-ray adds
+// Contribution words + the deferred shadow-ray adds
 // ------------------------------------------------------------------------------------------------
-MIRT_DI size_t accum_index(uint32_t acc_base, uint32_t buckets, uint32_t pix_bits, uint32_t path) {      // path: below 2^30 (no flag bits)
-	const uint32_t slot = path >> pix_bits;
-	const uint32_t pix = path & ((1u << pix_bits) - 1u);
-	const uint32_t bucket = (acc_base + slot + 1u) % buckets;               // Renderer.hpp:82
-	return (static_cast<size_t>(pix >> 8) * buckets + bucket) * 3u * kTileSize + (pix & 255u);
-}
-MIRT_DI size_t accum_index(const FrameParams& fp, uint32_t path) { return accum_index(fp.idx_base, fp.idx_buckets, fp.pix_bits, path); }
-MIRT_DI void accumulate_add(float* __restrict__ accum, size_t idx, float r, float g, float b) {     // Renderer.hpp:427-429
-	// (pixel, bucket) is unique within a batch and batches are stream-ordered: plain read-modify-write, no atomics,
-	// and each bucket sees its adds in accumulation order exactly like the reference.
-	accum[idx] += r; accum[idx + kTileSize] += g; accum[idx + 2 * kTileSize] += b;
-}
 // Contribution buffer of a batch: [tile][slot][256][rgb] (slot = accumulation index inside the batch), so that a path's three words
-// share a sector.  Every path of the batch ends exactly once (miss, Russian roulette, or dropped after the last bounce: Q5), and there
-// its word receives a plain store of +0 + radiance — the add into a +0 word it stands for (a dropped path: +0) — so the buffer is never
-// cleared: k_merge_contrib reads every word.  Only a pending light record adds to the word afterwards (shadow_finish: R + S).
-constexpr uint32_t kIdxContrib = 0xffffffffu;   // FrameParams::idx_base / ShadowSink::acc_base of a batch that writes a contribution buffer
-MIRT_DI size_t contrib_index(uint32_t batch_n, uint32_t pix_bits, uint32_t path) {
+// share a sector.  A path's word IS its radiance R (Renderer.hpp:98) for the whole batch: k_shade<FIRST> stores it for every path
+// (+0, then what bounce 0 adds at once) — so the buffer is never cleared: k_merge_contrib reads every word — and every later
+// `R += ...` of the reference is a read-modify-write of the word, in the reference's order: shadow_finish adds the NEE term of an
+// unoccluded shadow ray (and the emissive term that had to wait for it), k_shade the emissive term of a hit without a pending
+// light record and the sky term of a miss.  The launches of a batch are stream-ordered and a path has one ray per launch, so the
+// word needs no atomics.  A path that ends touches nothing — the word already holds its result —, except the paths still alive
+// after the last bounce, which are dropped (Q5): their word is overwritten with +0.
+// (The sum starts at +0 and can therefore never be -0: x + 0.0f and 0.0f + x are exact identities on it.)
+MIRT_DI size_t contrib_index(uint32_t batch_n, uint32_t pix_bits, uint32_t path) {      // path: below 2^30 (no flag bits)
 	const uint32_t slot = path >> pix_bits;
 	const uint32_t pix = path & ((1u << pix_bits) - 1u);
 	return ((static_cast<size_t>(pix >> 8) * batch_n + slot) * kTileSize + (pix & 255u)) * 3u;
 }
-// A finished path's radiance: added into the accumulator word (direct mode, words that hold earlier samples), or stored into its
-// contribution word (idx_base = kIdxContrib, idx_buckets = batch_n).
-MIRT_DI void path_result(float* __restrict__ accum, uint32_t idx_base, uint32_t idx_buckets, uint32_t pix_bits, uint32_t path, float r, float g, float b) {
-	if (idx_base == kIdxContrib) {
-		float* w = accum + contrib_index(idx_buckets, pix_bits, path);
-		w[0] = 0.0f + r; w[1] = 0.0f + g; w[2] = 0.0f + b;                    // (+0 + -0 = +0, like the add into a zeroed word)
-	} else accumulate_add(accum, accum_index(idx_base, idx_buckets, pix_bits, path), r, g, b);
-}
-MIRT_DI void path_result_add(float* __restrict__ accum, uint32_t idx_base, uint32_t idx_buckets, uint32_t pix_bits, uint32_t path, float r, float g, float b) {
-	if (idx_base == kIdxContrib) {                                              // the word holds +0 + R, stored by k_shade
-		float* w = accum + contrib_index(idx_buckets, pix_bits, path);
-		w[0] += r; w[1] += g; w[2] += b;
-	} else accumulate_add(accum, accum_index(idx_base, idx_buckets, pix_bits, path), r, g, b);
-}
-MIRT_DI void path_result(float* __restrict__ accum, const FrameParams& fp, uint32_t path, float r, float g, float b) { path_result(accum, fp.idx_base, fp.idx_buckets, fp.pix_bits, path, r, g, b); }
 // Where a finished shadow ray's radiance goes.  The adds that had to wait for the occlusion test — (R + unoccluded NEE) +
 // emissive, the reference's order (Renderer.hpp:307-311, then 339-341 / 348-350) — are made by the lane that traced the
-// ray, straight into the next stream's radiance planes or the path's result word: k_trace is VALU-bound, so the few memory
-// instructions per shadow ray ride along for free, where a separate pass over the shadow stream cost 4.8 ms per cfg2 step.
-//   * light record (the common case: the hit was not emissive): k_shade has already put R where the result belongs — the
-//     surviving ray's radiance word, or the path's own word of the contribution buffer (stored there once, as +0 + R) — so
-//     an occluded ray (most of them) touches nothing and an unoccluded one adds its NEE radiance to that word: R + S, and
-//     the emissive term is +0;
-//   * kDestFull record (emissive hit, or a path that ended while batches add straight into the accumulator, whose words hold
-//     earlier samples): R and E travel in the record and (R + S) + E is formed here.
-// (Measured: sending R along for every path that ends — so that shadow_finish stores each result once — moves a load and a
-//  scattered store per such record into k_trace, whose L2 holds the tree: +8 ms of k_trace per cfg4 batch, more than the adds cost.)
+// ray, straight into the path's contribution word: k_trace is VALU-bound, so the few memory instructions per shadow ray ride
+// along for free, where a separate pass over the shadow stream cost 4.8 ms per cfg2 step.
+//   * light record (the common case: the hit was not emissive): an occluded ray (most of them) touches nothing and an
+//     unoccluded one adds its NEE radiance: R + S;
+//   * kDestFull record (emissive hit): E travels in the record and (R + S) + E, or R + E behind an occluder, is formed here.
+// The record finds its origin through the surviving ray's slot (shadow_origin), so `dest` holds that slot and the path id comes
+// from the slot's `path` word — one more load, for the unoccluded minority only; a path that ended carries its id (kDestAccum).
 // occ != nullptr (mirt_debug_trace_shadow): only the occlusion flag is stored.
 constexpr uint32_t kDestFull = 0x40000000u;
 constexpr uint32_t kDestSlot = 0x3fffffffu;     // stream slots stay below 2^30 (capacity check in mirt_capi.hip); path ids use bits 0-29 too (batch slot << pix_bits | pixel)
 struct ShadowSink {
-	float *rr, *rg, *rb;        // radiance planes of the stream k_shade reads next
+	const uint32_t* path;       // path plane of the stream k_shade reads next
 	const float *px, *py, *pz;  // its origin planes (shared with the shadow rays of the surviving paths)
-	float* accum;
-	uint32_t acc_base, buckets, pix_bits;
+	float* contrib;             // the batch's contribution buffer
+	uint32_t batch_n, pix_bits;
 	uint32_t* occ;
 };
 MIRT_DI void shadow_origin(const ShadowBuf& sh, const ShadowSink& sink, uint32_t i, float& px, float& py, float& pz) {
@@ -895,20 +865,15 @@ MIRT_DI void shadow_origin(const ShadowBuf& sh, const ShadowSink& sink, uint32_t
 MIRT_DI void shadow_finish(const ShadowBuf& sh, const ShadowSink& sink, uint32_t i, bool occluded, uint32_t& c_term) {
 	if (sink.occ) { sink.occ[i] = occluded ? 1u : 0u; return; }
 	const uint32_t dw = sh.dest[i];
-	const uint32_t dest = dw & (kDestSlot | kDestAccum);
 	if (dw & kDestAccum) c_term++;
-	if (dw & kDestFull) {
-		f3 R{ sh.rr[i], sh.rg[i], sh.rb[i] };
-		const f3 E{ sh.er[i], sh.eg[i], sh.eb[i] };
-		if (!occluded) { R.x += sh.sr[i]; R.y += sh.sg[i]; R.z += sh.sb[i]; }
-		R.x += E.x; R.y += E.y; R.z += E.z;
-		if (dest & kDestAccum) path_result(sink.accum, sink.acc_base, sink.buckets, sink.pix_bits, dest & ~kDestAccum, R.x, R.y, R.z);
-		else { sink.rr[dest] = R.x; sink.rg[dest] = R.y; sink.rb[dest] = R.z; }
-	} else if (!occluded) {
-		const f3 S{ sh.sr[i], sh.sg[i], sh.sb[i] };
-		if (dest & kDestAccum) path_result_add(sink.accum, sink.acc_base, sink.buckets, sink.pix_bits, dest & ~kDestAccum, S.x, S.y, S.z);   // word = R + S
-		else { sink.rr[dest] += S.x; sink.rg[dest] += S.y; sink.rb[dest] += S.z; }
-	}
+	const bool full = (dw & kDestFull) != 0u;
+	if (occluded & !full) return;
+	const uint32_t path = (dw & kDestAccum) ? (dw & kDestSlot) : sink.path[dw & kDestSlot];
+	float* w = sink.contrib + contrib_index(sink.batch_n, sink.pix_bits, path);
+	f3 R{ w[0], w[1], w[2] };
+	if (!occluded) { R.x += sh.sr[i]; R.y += sh.sg[i]; R.z += sh.sb[i]; }
+	if (full) { R.x += sh.er[i]; R.y += sh.eg[i]; R.z += sh.eb[i]; }
+	w[0] = R.x; w[1] = R.y; w[2] = R.z;
 }
 
 // INTERSECTION + SHADOW RAY TRACING in one launch: Traverse (BVH.hpp:309-360) for the rays of bounce b and
@@ -1147,7 +1112,8 @@ MIRT_DI f3 sky_eval(const SceneDev& sc, float x, float y, float z) {
 
 // ------------------------------------------------------------------------------------------------
 // SHADE — closest-hit shader, NEE, emissive, BRDF sample + Russian roulette + compaction, miss, accumulate
-// (Renderer.hpp:169-431).  FIRST = bounce 0: radiance 0, throughput 1 (Renderer.hpp:98-101) without reading them.
+// (Renderer.hpp:169-431).  FIRST = bounce 0: throughput 1 (Renderer.hpp:98-101) without reading it, and the path's contribution
+// word — its radiance for the rest of the batch (contrib_index) — is stored here for every path: +0 and what bounce 0 adds at once.
 // ------------------------------------------------------------------------------------------------
 // Dense list of the rays for which `flag` is set, in LDS: list[rank] = value; returns the number of entries.  All threads
 // of the block, converged.  scratch = 17 words.  (Two barriers; the list may be read after return.)
@@ -1175,7 +1141,7 @@ MIRT_DI uint32_t block_compact(bool flag, uint32_t value, uint32_t* scratch, uin
 // ray weigh powerHeuristic(0, .) = 0.  GGX = false does not read the two trailing arguments.
 template <bool FIRST, bool GGX>
 __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
-                                                  Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ accum, DevCounters* ctr,
+                                                  Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
                                                   const float4* __restrict__ mat_ggx, float gloss_decay) {
 	const QueueView qin = FIRST ? queue_identity(fp.n_pix * fp.batch_n) : queue_view(in_queue);
 	const uint32_t n = qin.pre[kSegs];
@@ -1218,6 +1184,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 		f3 my_D{0, 0, 0};
 		uint32_t my_path = 0u;
 		bool lane_on;
+		f3 W0{0.0f, 0.0f, 0.0f};                                               // FIRST: the word this path starts with
 		if (FIRST) {
 			if (new_unit) {                                                      // a new chunk of pixels
 				pix = chunk * kShadeBlock + threadIdx.x;
@@ -1251,22 +1218,24 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 				const uint32_t i = my_slot;
 				const int32_t prim = my_prim;
 				if (prim < 0) {
-					// MISS SHADER, Renderer.hpp:408-420 (Q10: throughput.r scales all three channels)
-					f3 R{0.0f, 0.0f, 0.0f};
-					float thr_x = 1.0f;
-					uint32_t mpath = my_path; f3 md = my_D;
-					if (!FIRST) { R = { in.rr[i], in.rg[i], in.rb[i] }; thr_x = in.tr[i]; mpath = in.path[i]; }
+					// MISS SHADER, Renderer.hpp:408-420 (Q10: throughput.r scales all three channels).  Without ambient light the path just
+					// ends: its word holds its result already (ACCUMULATION, Renderer.hpp:424-430, is k_merge_contrib's)
 					if (sc.has_ambient) {
-						if (!FIRST) md = { in.dx[i], in.dy[i], in.dz[i] };
-						const f3 sky = sky_eval(sc, md.x, md.y, md.z);
-						R.x += thr_x * sky.x; R.y += thr_x * sky.y; R.z += thr_x * sky.z;
+						if (FIRST) {
+							const f3 sky = sky_eval(sc, my_D.x, my_D.y, my_D.z);
+							W0 = { 0.0f + 1.0f * sky.x, 0.0f + 1.0f * sky.y, 0.0f + 1.0f * sky.z };
+						} else {
+							const float thr_x = in.tr[i];
+							const f3 sky = sky_eval(sc, in.dx[i], in.dy[i], in.dz[i]);
+							float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, in.path[i]);
+							w[0] += thr_x * sky.x; w[1] += thr_x * sky.y; w[2] += thr_x * sky.z;
+						}
 					}
-					path_result(accum, fp, mpath, R.x + 0.0f, R.y + 0.0f, R.z + 0.0f);   // ACCUMULATION, Renderer.hpp:424-430 (+ the zero emissive term)
 					c_term++;
 				} else if (last_bounce) {
-					c_drop++;                                                         // Q5: still alive after the last bounce -> never accumulated
-					if (fp.idx_base == kIdxContrib) {                                 // (its contribution word still gets its one store: +0)
-						float* w = accum + contrib_index(fp.idx_buckets, fp.pix_bits, FIRST ? my_path : in.path[i]);
+					c_drop++;                                                         // Q5: still alive after the last bounce -> never accumulated: the word goes back to +0
+					if (!FIRST) {                                                     // (FIRST: W0 is +0)
+						float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, in.path[i]);
 						w[0] = 0.0f; w[1] = 0.0f; w[2] = 0.0f;
 					}
 				} else is_hit = true;
@@ -1281,7 +1250,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 		bool survive = false, has_shadow = false, terminated = false, has_E = false;
 		uint32_t path = 0;
 		f3 P{0, 0, 0}, ndir{0, 0, 0}, L{0, 0, 0}, srad{0, 0, 0}, E{0, 0, 0};
-		f3 R{0.0f, 0.0f, 0.0f}, thr{1.0f, 1.0f, 1.0f};
+		f3 thr{1.0f, 1.0f, 1.0f};
 		float light_distance = 0.0f;
 		if (FIRST ? is_hit : threadIdx.x < n_hits) {
 			const uint32_t i = FIRST ? my_slot : hit_list[threadIdx.x];
@@ -1290,7 +1259,6 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 			if (!FIRST) { path = in.path[i]; D = { in.dx[i], in.dy[i], in.dz[i] }; }
 			float pdf_in = 0.0f;
 			if (!FIRST) {
-				R = { in.rr[i], in.rg[i], in.rb[i] };
 				thr = { in.tr[i], in.tg[i], in.tb[i] };
 				pdf_in = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, D.z);           // out->pdf of the bounce that sampled D (Q8), bit for bit; Closure<GGX>::pdf = 0
 			}
@@ -1403,10 +1371,9 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 		// ---- stream compaction: wave64 ballot + mbcnt prefix inside each wave, one atomic per workgroup and stream ----
 		uint32_t slot, sslot;
 		block_append2(survive, has_shadow, next_queue, shadow_queue, iteration % kSegs, append_scratch, parity, slot, sslot);
-		// (R + unoccluded NEE) + E is finished by k_trace's shadow_finish once the occlusion is known.  Non-emissive hits (E = +0)
-		// leave R where that result belongs and send a light record; the others send R and E along (kDestFull).
-		const bool direct = fp.idx_base != kIdxContrib;                           // paths add straight into accumulator words that hold earlier samples
-		const bool full = has_shadow & (has_E | (terminated & direct));
+		// (R + unoccluded NEE) + E is finished by k_trace's shadow_finish once the occlusion is known: an emissive hit with a light
+		// record pending sends E along (kDestFull); one without adds E to the path's word here.
+		const bool full = has_shadow & has_E;
 		if (survive) {
 			out.px[slot] = P.x; out.py[slot] = P.y; out.pz[slot] = P.z;
 			out.dx[slot] = ndir.x; out.dy[slot] = ndir.y; out.dz[slot] = ndir.z;
@@ -1418,16 +1385,20 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 			sh.dx[sslot] = L.x; sh.dy[sslot] = L.y; sh.dz[sslot] = L.z;
 			sh.tfar[sslot] = light_distance;
 			sh.sr[sslot] = srad.x; sh.sg[sslot] = srad.y; sh.sb[sslot] = srad.z;
-			if (full) {
-				sh.rr[sslot] = R.x; sh.rg[sslot] = R.y; sh.rb[sslot] = R.z;
-				sh.er[sslot] = E.x; sh.eg[sslot] = E.y; sh.eb[sslot] = E.z;
-			}
+			if (full) { sh.er[sslot] = E.x; sh.eg[sslot] = E.y; sh.eb[sslot] = E.z; }
 			sh.dest[sslot] = (survive ? slot : (kDestAccum | path)) | (full ? kDestFull : 0u);
 		}
-		if ((survive | terminated) & !full) {
-			const f3 Rf{ R.x + E.x, R.y + E.y, R.z + E.z };                       // E is +0 when the hit is not emissive (exact no-op); with a light record pending E is +0 too
-			if (survive) { out.rr[slot] = Rf.x; out.rg[slot] = Rf.y; out.rb[slot] = Rf.z; }
-			else path_result(accum, fp, path, Rf.x, Rf.y, Rf.z);                  // ACCUMULATION, Renderer.hpp:424-430 (a pending light record adds its NEE term to the same word)
+		if (has_E & !has_shadow) {
+			if (FIRST) W0 = { 0.0f + E.x, 0.0f + E.y, 0.0f + E.z };
+			else {
+				float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, path);
+				w[0] += E.x; w[1] += E.y; w[2] += E.z;
+			}
+		}
+		// FIRST is pixel-major — this iteration's lanes are 512 consecutive pixels of one slot, i.e. two contiguous 3-KB runs of the buffer
+		if (FIRST && lane_on) {
+			float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, my_path);
+			w[0] = W0.x; w[1] = W0.y; w[2] = W0.z;
 		}
 		c_term += (terminated && !has_shadow) ? 1u : 0u;
 	}

@@ -53,12 +53,12 @@ struct ScopedBuffer : DeviceBuffer {
 
 struct TimedLaunch { int klass; hipEvent_t start, stop; };
 
-// One batch in flight: its own HIP stream, ray streams and (when more than one slot exists) contribution buffer.
+// One batch in flight: its own HIP stream, ray streams and contribution buffer.
 struct PipeSlot {
 	hipStream_t stream = nullptr;
 	DeviceBuffer arena;              // ray streams
 	DeviceBuffer counts;             // ray queue counters, work counters and fat-ray counts of one batch: addressed through BatchCounters only
-	DeviceBuffer contrib;            // this batch's path results, [tile][slot][256][rgb] (kernels.hpp contrib_index)
+	DeviceBuffer contrib;            // this batch's path radiances, [tile][slot][256][rgb] (kernels.hpp contrib_index)
 	DeviceBuffer fat;                // fat-ray index lists: [closest kFatCapacity][shadow kFatCapacity]
 	DeviceBuffer cand;               // per local pixel: candidate spheres of its bundle of camera rays (k_primary_cand), kCandStride words
 	hipEvent_t batch_done = nullptr; // recorded on `stream` after the batch's last kernel
@@ -130,7 +130,7 @@ int fail(mirt_ctx* ctx, int code, const char* fmt, ...) {
 
 // Accumulations traced together as one batch (path id = (slot << pix_bits) | pixel below 2^30: bits 30 and 31 stay free for flags).
 // Every launch of a batch ends in a tail while its longest rays finish and starts with the staging of the tree top, so
-// launches want to be LARGE — and 288 GB of HBM is there to be used for ray streams (180 B per ray and batch in flight).
+// launches want to be LARGE — and 288 GB of HBM is there to be used for ray streams (144 B per ray and batch in flight, + 12 B of contribution buffer).
 // Measured on one MI355X (Mray/s; accumulations per batch x batches in flight on separate HIP streams):
 //   cfg4 4096^2 S(100000):  5 x 3: 4919   8 x 1: 5435   16 x 1: 5726   32 x 1: 5838   16 x 2: 5013
 //   one eighth of cfg4:     16 x 3: 4367  32 x 3: 4981  64 x 3: 5103   64 x 1: 5498
@@ -142,7 +142,7 @@ int fail(mirt_ctx* ctx, int code, const char* fmt, ...) {
 constexpr uint32_t kMaxBatch = 256;         // upper limit of accumulations per batch; a context's own limit is what its path ids hold (max_slots)
 constexpr uint64_t kBatchRays = 1024ull << 20;   // round 3, cfg4 on the whole image (Mray/s, one batch in flight): 32 accumulations per batch 7970, 48: 8154, 63: 8218; 2 x 32: 7232, 2 x 24: 7192
 constexpr uint64_t kSerialRays = 96ull << 20;
-constexpr size_t kStreamPlanes = 2 * 13 + 2 + 17;      // two ray streams, hit (tfar, prim), shadow stream: 4-byte planes per ray of capacity
+constexpr size_t kStreamPlanes = 2 * 10 + 2 + 14;      // two ray streams, hit (tfar, prim), shadow stream: 4-byte planes per ray of capacity
 // Path id = (batch slot << pix_bits) | local pixel, below 2^30 (bits 30 and 31 of the words that carry it are flags): a context that owns
 // all 2^24 pixels of a 4096^2 image has room for 64 slots, one that owns an eighth of it (a rank of an 8-GPU run) for 512.
 uint32_t pix_bits_of(const mirt_ctx* c) { uint32_t b = 8; while ((1ull << b) < static_cast<uint64_t>(c->n_tiles) * kTileSize) b++; return b; }
@@ -160,9 +160,6 @@ uint32_t batch_limit(const mirt_ctx* c) {
 	const uint64_t b = std::max<uint64_t>((kBatchRays + n_pix / 2) / n_pix, batch_floor(c));
 	return static_cast<uint32_t>(std::min<uint64_t>(std::min<uint64_t>(b, max_slots(c)), std::max<uint32_t>(c->batch_mem_cap, 1u)));
 }
-// Paths add straight into the accumulator only when a batch cannot touch a (pixel, bucket) word twice and no other
-// batch is in flight; otherwise every batch adds into its own contribution buffer, merged in accumulation order.
-bool uses_contrib(const mirt_ctx* c, uint32_t n_slots) { return n_slots > 1 || batch_limit(c) > c->policy.buckets; }
 
 uint32_t grid_for(const mirt_ctx* c, uint64_t work_items) {
 	uint64_t blocks = (work_items + kBlock - 1) / kBlock;
@@ -244,7 +241,7 @@ uint32_t wanted_slots(const mirt_ctx* c) {
 // Device bytes of the batches in flight for the current plan (ray streams + contribution buffers).
 uint64_t streams_bytes(const mirt_ctx* c) {
 	const uint64_t rays = static_cast<uint64_t>(c->n_tiles) * kTileSize * batch_limit(c);
-	return wanted_slots(c) * (rays * 4u * kStreamPlanes + (uses_contrib(c, wanted_slots(c)) ? rays * 12u : 0u));
+	return wanted_slots(c) * (rays * 4u * kStreamPlanes + rays * 12u);
 }
 
 // Automatic batch size: as large as kBatchRays asks, but within 80 % of the device memory that is free plus what this context's own ray
@@ -276,9 +273,8 @@ int ensure_streams(mirt_ctx* c) {
 	const uint32_t cap = seg_cap * kSegs;
 	const uint32_t nb = c->policy.max_bounces;
 	const uint32_t want = wanted_slots(c);
-	const bool contrib = uses_contrib(c, want);
 	const size_t acc_bytes = static_cast<size_t>(c->n_tiles) * batch_limit(c) * 3 * kTileSize * sizeof(float);     // contribution buffer: [tile][slot][256][rgb]
-	if (cap == c->capacity && nb == c->arena_bounces && c->slots.size() == want && (!contrib || c->slots[0].contrib.bytes >= acc_bytes)) return MIRT_OK;
+	if (cap == c->capacity && nb == c->arena_bounces && c->slots.size() == want && c->slots[0].contrib.bytes >= acc_bytes) return MIRT_OK;
 	HIP_TRY(c, sync_all(c));
 	while (c->slots.size() > want) {
 		PipeSlot& sl = c->slots.back();
@@ -304,7 +300,7 @@ int ensure_streams(mirt_ctx* c) {
 		if (e == hipSuccess) { e = sl.counts.ensure(BatchCounters::words(nb) * sizeof(uint32_t)); what = "queue counters"; }
 		if (e == hipSuccess) { e = sl.fat.ensure(2u * kFatCapacity * sizeof(uint32_t)); what = "fat-ray lists"; }
 		if (e == hipSuccess) { e = sl.cand.ensure(static_cast<size_t>(n_pix) * kCandStride * sizeof(uint32_t)); what = "candidate lists"; }
-		if (e == hipSuccess) { if (contrib) { e = sl.contrib.ensure(acc_bytes); what = "contribution buffer"; } else sl.contrib.release(); }
+		if (e == hipSuccess) { e = sl.contrib.ensure(acc_bytes); what = "contribution buffer"; }
 		if (e != hipSuccess) {
 			// not enough device memory after all (someone else took it meanwhile — another context or process planning against the same
 			// free memory): halve the automatic batch and plan again
@@ -324,7 +320,6 @@ int ensure_streams(mirt_ctx* c) {
 			s.px = (float*)take(); s.py = (float*)take(); s.pz = (float*)take();
 			s.dx = (float*)take(); s.dy = (float*)take(); s.dz = (float*)take();
 			s.tr = (float*)take(); s.tg = (float*)take(); s.tb = (float*)take();
-			s.rr = (float*)take(); s.rg = (float*)take(); s.rb = (float*)take();
 			s.path = (uint32_t*)take();
 		}
 		sl.hit = (HitRec*)take(); (void)take();                            // planes are adjacent: 8 B per ray
@@ -332,7 +327,6 @@ int ensure_streams(mirt_ctx* c) {
 		h.px = (float*)take(); h.py = (float*)take(); h.pz = (float*)take();
 		h.dx = (float*)take(); h.dy = (float*)take(); h.dz = (float*)take(); h.tfar = (float*)take();
 		h.sr = (float*)take(); h.sg = (float*)take(); h.sb = (float*)take();
-		h.rr = (float*)take(); h.rg = (float*)take(); h.rb = (float*)take();
 		h.er = (float*)take(); h.eg = (float*)take(); h.eb = (float*)take();
 		h.dest = (uint32_t*)take();
 	}
@@ -396,8 +390,6 @@ FrameParams frame_params(const mirt_ctx* c, uint32_t acc_base, uint32_t batch_n)
 	fp.pix_bits = pix_bits_of(c); fp.pix_mask = (1u << fp.pix_bits) - 1u;
 	fp.acc_base = acc_base;
 	fp.batch_n = batch_n;
-	fp.idx_base = acc_base;
-	fp.idx_buckets = c->policy.buckets;
 	fp.max_bounces = c->policy.max_bounces;
 	fp.buckets = c->policy.buckets;
 	fp.n_lights = c->scene.n_lights;
@@ -454,13 +446,13 @@ void launch_trace(const mirt_ctx* c, hipStream_t st, const SceneDev& sc, const F
 
 // One batch = up to batch_limit() consecutive Accumulate() calls traced together (path id = (slot << pix_bits) | pixel).
 // Consecutive accumulation indices land in buckets (acc % buckets, Renderer.hpp:82), and the ORDER of the adds into a
-// bucket word is part of the result.  With at most `buckets` accumulations per batch and one batch at a time every
-// (pixel, bucket) word is touched once per batch and paths add straight into the accumulator.  Otherwise each path of a batch
-// stores its result once into the batch's contribution buffer [tile][slot][256][rgb] (every word is written, so the buffer is
-// never cleared: kernels.hpp contrib_index) and k_merge_contrib, enqueued on the main stream in batch
-// order, applies the slots to their buckets in ascending order — so larger batches (launches several times longer than
-// their tails) and up to policy.streams batches in flight on their own HIP streams (other batches fill those tails)
-// leave every bucket's add order, hence the result, exactly as in the reference.
+// bucket word is part of the result.  Each path of a batch keeps its radiance in its own word of the batch's contribution buffer
+// [tile][slot][256][rgb] — stored at bounce 0 for every path, so the buffer is never cleared, and added to where the reference
+// adds to the path's radiance (kernels.hpp contrib_index) — and k_merge_contrib, enqueued on the main stream in batch order,
+// applies the slots to their buckets in ascending order — so batches of any size (launches several times longer than their
+// tails) and up to policy.streams batches in flight on their own HIP streams (other batches fill those tails) leave every
+// bucket's add order, hence the result, exactly as in the reference.  (A running sum cannot live in an accumulator word, which
+// holds earlier samples: A + R is not ((A + S0) + E0) + ...; hence a buffer for every batch, however small.)
 int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 	FrameParams fp = frame_params(c, c->accumulations, batch_n);
 	const uint32_t nb = c->policy.max_bounces;
@@ -469,8 +461,6 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 	const bool pipelined = c->slots.size() > 1;
 	PipeSlot& sl = c->slots[c->batch_seq % c->slots.size()];
 	hipStream_t st = pipelined ? sl.stream : c->stream;
-	const bool contrib = uses_contrib(c, static_cast<uint32_t>(c->slots.size()));
-	if (contrib) { fp.idx_base = kIdxContrib; fp.idx_buckets = batch_n; }            // slot k of the buffer = accumulation acc_base + k + 1
 	const BatchCounters bc = batch_counters(c, sl);
 	// Camera rays of a batch go through per-pixel candidate lists when a pixel is sampled often enough to pay for its cone traversal
 	// (policy.trace_primary_rays = 1 switches that off: every primary ray then walks the tree; results are identical either way).
@@ -480,7 +470,7 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 	const bool bundle = c->policy.use_bvh && c->scene.n_recs != 0 && !c->policy.trace_primary_rays && batch_n >= 3 && c->camera.z != 0.0f && std::fabs(qn - 1.0f) < 1e-4f;
 	DevCounters* ctr = c->counters.as<DevCounters>();
 	const float4* mat_ggx = c->mat_ggx.as<float4>();
-	float* accum = contrib ? sl.contrib.as<float>() : c->accumulator.as<float>();
+	float* contrib = sl.contrib.as<float>();                                      // slot k of the buffer = accumulation acc_base + k + 1
 	uint32_t* fat_lists = sl.fat.as<uint32_t>();
 	const SceneDev sc = trace_scene(c);
 	const bool count = c->policy.count_traffic != 0;
@@ -492,8 +482,8 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 	}
 
 	if (pipelined && sl.in_use) HIP_TRY(c, hipStreamWaitEvent(st, sl.merged, 0));   // the slot's previous batch has been merged: buffers are free
-	// (The contribution buffer needs no clearing: each of its words is stored once by the path it belongs to.)
-	if (contrib && c->debug_poison_contrib)
+	// (The contribution buffer needs no clearing: bounce 0 stores the word of every path.)
+	if (c->debug_poison_contrib)
 		HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sl.contrib.ptr), 0x7fc0deadu, sl.contrib.bytes / sizeof(float), st));   // a quiet NaN
 	HIP_TRY(c, hipMemsetAsync(bc.w, 0, BatchCounters::words(nb) * sizeof(uint32_t), st));
 	// bounce 0 has no ray stream: k_trace<PRIMARY> and k_shade<FIRST> derive the camera ray from its index (RAY GENERATION, Renderer.hpp:113-127)
@@ -512,8 +502,9 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 		    const uint32_t hgrid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
 		    hipLaunchKernelGGL(kPrimaryHits[!count], dim3(hgrid), dim3(kBlock), 0, st, sc, fp, sl.cand.as<uint32_t>(), sl.hit, ctr);
 		  }
-		  // the adds of bounce-1 that waited for occlusion land in stream `in` (= out of bounce-1) or the accumulator, before k_shade reads them
-		  const ShadowSink sink{ in.rr, in.rg, in.rb, in.px, in.py, in.pz, accum, fp.idx_base, fp.idx_buckets, fp.pix_bits, nullptr };
+		  // the adds of bounce-1 that waited for occlusion land in the paths' contribution words before k_shade adds this bounce's terms;
+		  // a surviving path's record finds its origin and its path id in stream `in` (= out of bounce-1)
+		  const ShadowSink sink{ in.path, in.px, in.py, in.pz, contrib, batch_n, fp.pix_bits, nullptr };
 		  const TraceLaunch tl{ in, sl.hit, lists ? Queue{ bc.listed_pixels(), 0u } : bc.stream_queue(bounce), bc.closest_work(bounce),      // kPrimaryList: n[0] = listed pixels
 		                        sl.shadow_buf, sink, shadow_pending ? bc.shadow_queue(bounce - 1) : bc.empty_queue(), bc.shadow_work(shadow_pending ? bounce - 1 : 0),
 		                        bc.fat_closest(bounce, fat_lists), bc.fat_shadow(bounce, fat_lists), bc.listed_pixels(), ctr };
@@ -522,21 +513,19 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 		  // policy.brdf = 1 (#define BRDF 1): Closure<GGX> with this bounce's gloss decay, passed by value
 		  const float decay = bounce < c->gloss_decay.size() ? c->gloss_decay[bounce] : 0.0f;
 		  hipLaunchKernelGGL(kShade[bounce == 0][c->policy.brdf != 0], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
-		                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), accum, ctr, mat_ggx, decay); }
+		                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay); }
 	}
 	HIP_TRY(c, hipGetLastError());
-	if (contrib) {
-		// merges are enqueued on the main stream in batch order => every bucket receives its adds in accumulation order
-		if (pipelined) {
-			HIP_TRY(c, hipEventRecord(sl.batch_done, st));
-			HIP_TRY(c, hipStreamWaitEvent(c->stream, sl.batch_done, 0));
-		}
-		{ Bracket t(c, MIRT_K_RESOLVE);
-		  hipLaunchKernelGGL(k_merge_contrib, dim3(grid_for(c, static_cast<uint64_t>(c->n_tiles) * (kTileSize / 4u))), dim3(kBlock), 0, c->stream,
-		                     c->accumulator.as<float4>(), sl.contrib.as<float4>(), c->n_tiles, c->policy.buckets, batch_n, fp.acc_base); }
-		HIP_TRY(c, hipGetLastError());
-		if (pipelined) { HIP_TRY(c, hipEventRecord(sl.merged, c->stream)); sl.in_use = true; }
+	// merges are enqueued on the main stream in batch order => every bucket receives its adds in accumulation order
+	if (pipelined) {
+		HIP_TRY(c, hipEventRecord(sl.batch_done, st));
+		HIP_TRY(c, hipStreamWaitEvent(c->stream, sl.batch_done, 0));
 	}
+	{ Bracket t(c, MIRT_K_RESOLVE);
+	  hipLaunchKernelGGL(k_merge_contrib, dim3(grid_for(c, static_cast<uint64_t>(c->n_tiles) * (kTileSize / 4u))), dim3(kBlock), 0, c->stream,
+	                     c->accumulator.as<float4>(), sl.contrib.as<float4>(), c->n_tiles, c->policy.buckets, batch_n, fp.acc_base); }
+	HIP_TRY(c, hipGetLastError());
+	if (pipelined) { HIP_TRY(c, hipEventRecord(sl.merged, c->stream)); sl.in_use = true; }
 	c->batch_seq++;
 	c->accumulations += batch_n;
 	if (c->policy.profile && c->pending.size() > 512) harvest(c);
