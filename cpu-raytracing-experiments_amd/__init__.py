@@ -81,6 +81,7 @@ def load_library():
         "mirt_set_policy": [P, C.POINTER(Policy)],
         "mirt_get_policy": [P, C.POINTER(Policy)],
         "mirt_set_gloss_decay": [P, vp, u32],
+        "mirt_set_stream_order": [P, u32], "mirt_get_stream_order": [P, C.POINTER(u32)],
         "mirt_resize": [P, u32, u32],
         "mirt_set_tile_range": [P, u32, u32], "mirt_set_tile_rows": [P, u32, u32],
         "mirt_reset": [P],
@@ -114,6 +115,7 @@ def load_library():
         "mirt_group_set_camera": [G, vp, vp, f, f, f, f],
         "mirt_group_set_policy": [G, C.POINTER(Policy)],
         "mirt_group_set_gloss_decay": [G, vp, u32],
+        "mirt_group_set_stream_order": [G, u32],
         "mirt_group_resize": [G, u32, u32],
         "mirt_group_reset": [G],
         "mirt_group_accumulate": [G, u32],
@@ -186,7 +188,7 @@ class Renderer:
     def __init__(self, scene: Scene, device: int = 0, max_bounces: int = 16, buckets: int = 5, mis: bool = True,
                  use_bvh: bool = False, count_traffic: bool = False, profile: bool = False, max_batch: int = 0,
                  allow_half_boxes: bool = True, reference_tree: bool = False, streams: int = 0, gpu_build: bool = False, trace_primary_rays: bool = False,
-                 brdf: int = 0, gloss_decay=None):
+                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False):
         self._lib = load_library()
         self._ctx = C.c_void_p()
         rc = self._lib.mirt_create(device, C.byref(self._ctx))
@@ -201,6 +203,8 @@ class Renderer:
         self._check(self._lib.mirt_debug_allow_half_boxes(self._ctx, int(allow_half_boxes)))
         if gloss_decay is not None:
             self.set_gloss_decay(gloss_decay)
+        if exact_stream_order:
+            self.set_stream_order(True)
         self.UpdateScene()
 
     # -- plumbing ---------------------------------------------------------------------------
@@ -238,6 +242,17 @@ class Renderer:
         None or an empty sequence resets it to zeros."""
         d = _decay_array(decay)
         self._check(self._lib.mirt_set_gloss_decay(self._ctx, _ptr(d) if len(d) else None, len(d)))
+
+    def set_stream_order(self, exact: bool = True):
+        """True: replay the reference's stream slots (counting sort by material, in-order compaction) and its scalar intersection tail
+        (BVH.hpp:270-286) — brute-force traversal, a fidelity mode (mirt_set_stream_order).  False: the default wavefront order."""
+        self._check(self._lib.mirt_set_stream_order(self._ctx, int(exact)))
+
+    @property
+    def stream_order(self) -> int:
+        v = C.c_uint32(0)
+        self._check(self._lib.mirt_get_stream_order(self._ctx, C.byref(v)))
+        return v.value
 
     # -- scene hand-over (Application.cpp:230-234) -------------------------------------------------
     def UpdateScene(self, nodes=None):
@@ -395,7 +410,7 @@ class GroupRenderer:
 
     def __init__(self, scene: Scene, devices=(0,), max_bounces: int = 16, buckets: int = 5, mis: bool = True, use_bvh: bool = True,
                  count_traffic: bool = False, max_batch: int = 0, streams: int = 0, reference_tree: bool = False, gpu_build: bool = False,
-                 brdf: int = 0, gloss_decay=None):
+                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False):
         self._lib = load_library()
         self._g = C.c_void_p()
         dev = (C.c_int * len(devices))(*devices)
@@ -410,6 +425,8 @@ class GroupRenderer:
         self._check(self._lib.mirt_group_set_policy(self._g, C.byref(self.policy)))
         if gloss_decay is not None:
             self.set_gloss_decay(gloss_decay)
+        if exact_stream_order:
+            self.set_stream_order(True)
         self.UpdateScene()
 
     def _check(self, rc):
@@ -439,6 +456,10 @@ class GroupRenderer:
         """Renderer.set_gloss_decay on every member."""
         d = _decay_array(decay)
         self._check(self._lib.mirt_group_set_gloss_decay(self._g, _ptr(d) if len(d) else None, len(d)))
+
+    def set_stream_order(self, exact: bool = True):
+        """Renderer.set_stream_order on every member."""
+        self._check(self._lib.mirt_group_set_stream_order(self._g, int(exact)))
 
     def UpdateScene(self):
         s = self.scene

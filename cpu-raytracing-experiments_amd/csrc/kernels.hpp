@@ -18,7 +18,8 @@
 //
 // Per-path results do not depend on stream slot or scheduling: every random draw is re-derived from
 // (accumulations, seed[pixel], bounce) (Renderer.hpp:107,117,255,362), which is what lets the
-// wavefront reorder rays freely and still reproduce the reference bit for bit.
+// wavefront reorder rays freely and still reproduce the reference bit for bit — up to the one thing that does depend on the slot, the
+// scalar tail of intersect_prims (Q14): k_tile_stream below ("EXACT STREAM ORDER", mirt_set_stream_order) replays slots and tail.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -116,6 +117,10 @@ MIRT_DI uint32_t mask_rank(unsigned long long m) {            // set bits of m b
 MIRT_DI void wave_sum(uint32_t v, unsigned long long* counter) {
 	for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
 	if (lane_id() == 0 && v) atomicAdd(counter, static_cast<unsigned long long>(v));
+}
+MIRT_DI void wave_sum(unsigned long long v, unsigned long long* counter) {     // k_tile_stream: a lane's count over a whole bounce loop can pass 2^32
+	for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+	if (lane_id() == 0 && v) atomicAdd(counter, v);
 }
 
 // ---- ray queues -----------------------------------------------------------------------------------------------
@@ -1135,6 +1140,9 @@ MIRT_DI uint32_t block_compact(bool flag, uint32_t value, uint32_t* scratch, uin
 // seed[ID]) is set up once per chunk.  Its hit records come from k_primary_hits (pixels with a candidate list) or k_trace.
 // (Measured and dropped twice: the candidate tests inside this kernel instead of k_primary_hits — ray-major in round 2, pixel-major in
 // round 3: at 6 waves per SIMD and 80 VGPRs the list's dependent loads cost k_shade<FIRST> 5 ms per cfg4 batch, as much as the kernel saved.)
+// TWIN: the arithmetic of phase 2 below (closest-hit shader, NEE, emissive MIS, closure sample, roulette) is restated operation for operation
+// in stream_shade_hit (k_tile_stream, "EXACT STREAM ORDER"); an edit to either must reach the other.  Both are held to the same oracle closure
+// bit for bit (tests/test_gpu_parity.py, test_ggx_gpu.py for this kernel; tests/test_exact_stream_order.py for the twin).
 // GGX = #define BRDF 1 (Renderer.hpp:70): every closure is Closure<GGX> (DataStreams.hpp:184-219) with F0 = material.F0 and
 // alpha = r^2 + (1 - r^2) * gloss_decay (Renderer.hpp:210-212; `gloss_decay` = the host's table at this bounce, one launch per
 // bounce), read from mat_ggx = {F0.xyz, roughness}.  Its pdf() is 0: NEE weighs 1 / light_pdf and emitters hit by an extension
@@ -1404,6 +1412,294 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 	}
 	wave_sum(c_term, &ctr->terminated);
 	wave_sum(c_drop, &ctr->dropped);
+}
+
+// ------------------------------------------------------------------------------------------------
+// EXACT STREAM ORDER (mirt_set_stream_order) — Renderer.hpp:83-432 with the reference's stream slots
+// ------------------------------------------------------------------------------------------------
+// The one thing the wavefront kernels above normalise (Q14): intersect_prims runs the stream eight rays at a time through the FMA
+// body (BVH.hpp:250-268) and the last `active_rays % 8` rays through an unfused scalar tail (BVH.hpp:270-286).  Which rays those are
+// depends on the slot a path holds after the per-bounce counting sort by material (DataStreams.hpp:221-253) and the in-order
+// compaction of the survivors (Renderer.hpp:357-404), so this mode keeps the reference's unit of work: one 256-thread workgroup is
+// one tile's stream of one accumulation, lane ID is stream slot ID, and the whole bounce loop runs inside the kernel.
+//   * the ray of slot ID lives in lane ID's registers; the survivors are written to their new slots in one LDS copy of the stream
+//     (13 dword planes: p, dir, throughput, radiance, pixelID) and read back by the lane of that slot;
+//   * traversal is the reference's as shipped (USEBVH false): every sphere in ascending BVH-order index, packets staged through a
+//     kBruteChunk LDS buffer — for every ray of the mode, since the tree's conservative boxes were argued for the FMA form only;
+//   * a survivor's new slot = survivors with a smaller key (material; a miss never survives) + survivors with the same key in a lower
+//     slot — what the stable counting sort followed by the in-order compaction gives —, from a (key, wave) table of ballot
+//     popcounts and a 256-entry prefix sum; no atomics, no serial lane;
+//   * a path's radiance is stored once, into its word of the batch's contribution buffer, at the bounce where it ends (+0 for a path
+//     dropped after the last bounce, Q5), so every word of the (tile, slot) is written and k_merge_contrib applies the slots as usual.
+// The shading arithmetic is k_shade's, restated (stream_shade_hit) rather than shared: k_shade's body is interleaved with its stream
+// loads and compaction, and its instantiations are kept instruction for instruction as they were tuned and measured.
+// Scalar tail of intersect_prims, BVH.hpp:270-286: separate multiply and add, dimension by dimension (built with -ffp-contract=off).
+MIRT_DI void sphere_closest_scalar_tail(float4 s, int32_t prim, float px, float py, float pz, float dx, float dy, float dz,
+                                        float& tfar, int32_t& primID) {
+	float b = 0.0f;
+	float disc = s.w;
+	float temp = s.x - px;
+	b += dx * temp;
+	disc -= temp * temp;
+	temp = s.y - py;
+	b += dy * temp;
+	disc -= temp * temp;
+	temp = s.z - pz;
+	b += dz * temp;
+	disc -= temp * temp;
+	disc += b * b;
+	if (disc < 0.0f) return;
+	disc = __builtin_sqrtf(disc);
+	const float dist = (b >= disc ? b - disc : b + disc);
+	if (dist < 0.0f || dist >= tfar) return;
+	tfar = dist; primID = prim;
+}
+// What one hit leaves behind: Renderer.hpp:169-404 for the ray (O, D, thr) that hit `prim` at `depth` — k_shade's phase 2, operation for operation.
+// TWIN of that code: an edit to either must reach the other (see the note above k_shade).
+struct StreamHit {
+	bool survive, has_shadow, has_E;
+	f3 P, ndir, L, srad, E, thr;
+	float light_distance;
+};
+template <bool GGX>
+MIRT_DI void stream_shade_hit(const SceneDev& sc, const FrameParams& fp, const float4* s_albedo, const float4* s_emission, uint32_t bounce, float gloss_decay,
+                              uint32_t acc, uint32_t seed, f3 O, f3 D, f3 thr, float depth, int32_t prim, int32_t mat, StreamHit& h) {
+	const float light_selection_pdf = 1.0f / static_cast<float>(fp.n_lights);  // Renderer.hpp:78
+	const float pdf_in = (GGX || bounce == 0u) ? 0.0f : MIRT_INV_PI * max_sel(0.0f, D.z);      // out->pdf of the bounce that sampled D (Q8); Closure<GGX>::pdf = 0
+	// CLOSEST HIT SHADER, Renderer.hpp:169-214
+	const float4 hs = sc.spheres[prim];
+	const f3 hit{ O.x + D.x * depth, O.y + D.y * depth, O.z + D.z * depth };
+	f3 N = normalize3(f3{ hit.x - hs.x, hit.y - hs.y, hit.z - hs.z });
+	if (dot3(N, D) >= 0.0f) N = f3{ -N.x, -N.y, -N.z };
+	const quat T = tangent_space(N);
+	const f3 Vl = to_local(T, f3{ -D.x, -D.y, -D.z });
+	h.P = { hit.x + N.x * 1e-4f, hit.y + N.y * 1e-4f, hit.z + N.z * 1e-4f };
+	const float4 em = s_emission[mat];
+	const float4 alb = s_albedo[mat];
+	const bool is_emissive = max_sel(em.x, max_sel(em.y, em.z)) > MIRT_FLT_EPSILON;
+	f3 F0{0.0f, 0.0f, 0.0f};
+	float alpha = 0.0f;
+	if (GGX) {                                                                 // closure set-up, Renderer.hpp:210-212
+		F0 = { alb.x, alb.y, alb.z };
+		float a = alb.w; a *= a;
+		alpha = a + (1.0f - a) * gloss_decay;
+	}
+	// NEXT EVENT ESTIMATION, Renderer.hpp:247-298
+	h.has_shadow = false;
+	if (fp.mis) {
+		uint32_t rng = hash_2d(acc, seed + bounce * 2u);
+		const float u0 = rand_unit_float(rng);
+		const float u1 = rand_unit_float(rng);
+		const int32_t selected = static_cast<int32_t>(rand_bounded_int(rng, fp.n_lights));
+		const float4 lp = sc.light_sphere[selected];
+		const float4 lem = sc.light_emit[selected];
+		const int32_t light_primID = static_cast<int32_t>(__float_as_uint(lem.w));
+		do {
+			if (light_primID == prim) break;                                     // Q11: geometry-order id vs BVH-order id
+			f3 Wc{ lp.x - h.P.x, lp.y - h.P.y, lp.z - h.P.z };
+			const float center_dist2 = dot3(Wc, Wc);
+			if (center_dist2 <= lp.w) break;
+			const float center_dist = __builtin_sqrtf(center_dist2);
+			{ const float inv = 1.0f / center_dist; Wc.x *= inv; Wc.y *= inv; Wc.z *= inv; }
+			const float sinThetaMax2 = lp.w / center_dist2;
+			{
+				const float NdotW = (2.0f * T.w) * (Wc.z * T.w + Wc.x * T.y - T.x * Wc.y) - Wc.z;
+				if (NdotW < 0.0f && sinThetaMax2 < NdotW * NdotW) break;
+			}
+			float ldist, lpdf;
+			const f3 Ld = sample_direction_to_sphere(Wc, sinThetaMax2, center_dist, lp.w, u0, u1, ldist, lpdf);
+			const f3 Ll = to_local(T, Ld);
+			if (Ll.z < 0.0f) break;
+			f3 rad{ lem.x * thr.x, lem.y * thr.y, lem.z * thr.z };
+			if (GGX) {  // Closure<GGX>::eval, DataStreams.hpp:189-195
+				const f3 f = ggx_eval(F0, alpha, Ll, Vl);
+				rad.x *= f.x; rad.y *= f.y; rad.z *= f.z;
+			} else {    // Closure<LambertianDiffuse>::eval, DataStreams.hpp:169-172
+				const float f = MIRT_INV_PI * max_sel(0.0f, Ll.z);
+				rad.x *= alb.x * f; rad.y *= alb.y * f; rad.z *= alb.z * f;
+			}
+			lpdf *= light_selection_pdf;
+			const float brdf_pdf = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, Ll.z);  // DataStreams.hpp:173-176 / :196-198
+			const float w = powerHeuristic_over_f(lpdf, brdf_pdf);
+			rad.x *= w; rad.y *= w; rad.z *= w;
+			if (max_sel(max_sel(rad.x, rad.y), rad.z) <= 0.0f) break;
+			h.has_shadow = true; h.L = Ld; h.light_distance = ldist; h.srad = rad;
+		} while (false);
+	}
+	// EMISSIVE PRIMITIVE HIT, Renderer.hpp:319-353
+	h.has_E = is_emissive;
+	if (is_emissive) {
+		if (fp.mis && bounce > 0) {
+			const float radius2 = hs.w;
+			const float center_dist2 = depth * (depth + Vl.z * (2.0f * __builtin_sqrtf(radius2))) + radius2;
+			const float weight = powerHeuristic(pdf_in, light_selection_pdf * spherePdf(radius2, center_dist2));
+			h.E = { (thr.x * weight) * em.x, (thr.y * weight) * em.y, (thr.z * weight) * em.z };
+		} else {
+			h.E = { em.x, em.y, em.z };                                          // Q9: no throughput
+		}
+	}
+	// BRDF SAMPLING - BOUNCE, Renderer.hpp:357-404
+	{
+		uint32_t rng = hash_2d(acc, seed + bounce * 2u + 1u);
+		const float b0 = rand_unit_float(rng);
+		const float b1 = rand_unit_float(rng);
+		f3 sd;
+		if (GGX) {                                                             // Closure<GGX>::sample, DataStreams.hpp:200-218
+			f3 est;
+			ggx_sample(F0, alpha, Vl, b0, b1, sd, est);
+			thr = { thr.x * est.x, thr.y * est.y, thr.z * est.z };
+		} else {
+			sd = hemisphere(b0, b1);                                           // Closure::sample, DataStreams.hpp:177-181
+			thr = { thr.x * alb.x, thr.y * alb.y, thr.z * alb.z };
+		}
+		const float q = 1.0f - max_sel(thr.x, max_sel(thr.y, thr.z));
+		h.survive = false;
+		if (!(rand_unit_float(rng) < q)) {                                     // Russian roulette, Renderer.hpp:377-383
+			const float inv = 1.0f / max_sel(MIRT_FLT_EPSILON, 1.0f - q);
+			h.thr = { thr.x * inv, thr.y * inv, thr.z * inv };
+			h.ndir = to_world(T, sd);
+			h.survive = true;
+		}
+	}
+}
+constexpr uint32_t kStreamPlanes = 13;          // p, dir, throughput, radiance, pixelID
+constexpr uint32_t kStreamKeys = 64;            // material keys 0 .. MIRT_MAX_MATERIALS - 1 (Renderer.hpp:23,92)
+// gloss_decay: the host's table by bounce (n_decay entries, the rest 0), GGX only.  count: policy.count_traffic.
+template <bool GGX>
+__global__ __launch_bounds__(kTileSize, 4) void k_tile_stream(SceneDev sc, FrameParams fp, float* __restrict__ contrib, DevCounters* ctr,
+                                                              const float4* __restrict__ mat_ggx, const float* __restrict__ gloss_decay, uint32_t n_decay, uint32_t count) {
+	__shared__ float4 s_chunk[kBruteChunk];
+	__shared__ float s_stream[kStreamPlanes][kTileSize];
+	__shared__ uint32_t s_rank[kStreamKeys * 4u];                              // [key][wave]: survivors of that key in that wave, then their first new slot
+	__shared__ uint32_t s_wave_total[4];
+	__shared__ float4 s_albedo[MIRT_MAX_MATERIALS + 1], s_emission[MIRT_MAX_MATERIALS + 1];      // GGX: s_albedo = {F0, roughness}
+	const uint32_t ID = threadIdx.x, wave = ID >> 6, lane = ID & 63u;
+	const uint32_t tile_local = blockIdx.x / fp.batch_n, slot = blockIdx.x - tile_local * fp.batch_n;      // one workgroup per (local tile, batch slot)
+	float* out = contrib + static_cast<size_t>(blockIdx.x) * (kTileSize * 3u);    // [tile][slot][256][rgb]
+	for (uint32_t m = ID; m < sc.n_mat; m += kTileSize) { s_albedo[m] = GGX ? mat_ggx[m] : sc.mat_albedo[m]; s_emission[m] = sc.mat_emission[m]; }
+
+	// stream init + RAY GENERATION, Renderer.hpp:97-127: slot ID of bounce 0 is pixel ID
+	const uint32_t tile = global_tile(fp, tile_local);
+	const uint32_t tile_row = tile / fp.h_tiles, tile_col = tile - tile_row * fp.h_tiles;
+	const uint32_t seed_stride = fp.max_bounces * 2u + 1u;
+	const uint32_t acc = fp.acc_base + slot + 1u;                                // ++accumulations, Renderer.hpp:74
+	uint32_t pixelID = ID;
+	f3 O{ fp.cam.pos[0], fp.cam.pos[1], fp.cam.pos[2] }, D, thr{ 1.0f, 1.0f, 1.0f }, R{ 0.0f, 0.0f, 0.0f };
+	{
+		uint32_t rng = hash_2d(acc, (tile * kTileSize + ID) * seed_stride);
+		const float s0 = rand_unit_float(rng);
+		const float s1 = rand_unit_float(rng);
+		D = camera_ray_dir(fp.cam, static_cast<int32_t>(kTileRoot * tile_col + (ID & 15u)), static_cast<int32_t>(kTileRoot * tile_row + (ID >> 4)), s0, s1);
+	}
+	uint32_t c_term = 0, c_drop = 0, c_shadow = 0;
+	unsigned long long c_shadow_spheres = 0;                                     // sphere tests of this lane's shadow rays (reported with count_traffic)
+	unsigned long long c_rays = 0;                                               // sum of active_rays over the bounces (uniform)
+	uint32_t active_rays = kTileSize;
+	for (uint32_t bounce = 0; bounce < fp.max_bounces && active_rays > 0u; bounce++) {     // Renderer.hpp:131
+		const bool active = ID < active_rays;
+		const bool tail = ID >= (active_rays & ~7u);                             // BVH.hpp:270: the rays the 8-wide body leaves over
+		const bool last_bounce = !(bounce < fp.max_bounces - 1u);                // Renderer.hpp:358
+		c_rays += active_rays;
+		// INTERSECTION: intersect_prims over all prims, BVH.hpp:236-288,312
+		float tfar = MIRT_FLT_MAX;                                                // hit reset, Renderer.hpp:150-158
+		int32_t prim = -1;
+		for (uint32_t base = 0; base < sc.n_spheres; base += kBruteChunk) {
+			const uint32_t cnt = min(kBruteChunk, sc.n_spheres - base);
+			__syncthreads();
+			for (uint32_t j = ID; j < cnt; j += kTileSize) s_chunk[j] = sc.spheres[base + j];
+			__syncthreads();
+			if (active) {
+				if (tail) { for (uint32_t j = 0; j < cnt; j++) sphere_closest_scalar_tail(s_chunk[j], static_cast<int32_t>(base + j), O.x, O.y, O.z, D.x, D.y, D.z, tfar, prim); }
+				else { for (uint32_t j = 0; j < cnt; j++) sphere_closest(s_chunk[j], static_cast<int32_t>(base + j), O.x, O.y, O.z, D.x, D.y, D.z, tfar, prim); }
+			}
+		}
+		// closest-hit shader .. BRDF sample for the hits; the miss shader; Q5 for what is alive after the last bounce
+		StreamHit h;
+		h.survive = false; h.has_shadow = false; h.has_E = false;
+		bool ended = false;                                                       // this path's radiance is final at this bounce
+		int32_t key = -1;                                                         // matID, DataStreams.hpp:221-253 (-1 = miss)
+		if (active) {
+			if (prim < 0) {
+				if (sc.has_ambient) {                                                // MISS SHADER, Renderer.hpp:408-420 (Q10: throughput.r scales all three channels)
+					const f3 sky = sky_eval(sc, D.x, D.y, D.z);
+					R.x += thr.x * sky.x; R.y += thr.x * sky.y; R.z += thr.x * sky.z;
+				}
+				ended = true; c_term++;
+			} else if (last_bounce) {
+				R = { 0.0f, 0.0f, 0.0f };                                            // Q5: never accumulated
+				ended = true; c_drop++;
+			} else {
+				key = sc.prim_mat[prim];
+				const float decay = (GGX && bounce < n_decay) ? gloss_decay[bounce] : 0.0f;
+				stream_shade_hit<GGX>(sc, fp, s_albedo, s_emission, bounce, decay, acc, (tile * kTileSize + pixelID) * seed_stride, O, D, thr, tfar, prim, key, h);
+			}
+		}
+		// SHADOW RAY TRACING: intersect_prims_shadow over all prims, BVH.hpp:290-305,365 (wave-uniform skip when no lane of the tile has one)
+		if (__syncthreads_or(h.has_shadow ? 1 : 0)) {
+			int32_t unused = -1;
+			uint32_t tested = 0;                                                     // at most n_spheres per ray
+			const bool occluded = traverse_brute<true, true>(sc, s_chunk, h.has_shadow, h.P.x, h.P.y, h.P.z, h.L.x, h.L.y, h.L.z, h.light_distance, unused, tested);
+			c_shadow_spheres += tested;
+			if (h.has_shadow) {
+				c_shadow++;
+				if (!occluded) { R.x += h.srad.x; R.y += h.srad.y; R.z += h.srad.z; } // Renderer.hpp:304-314
+			}
+		}
+		if (h.has_E) { R.x += h.E.x; R.y += h.E.y; R.z += h.E.z; }                    // Renderer.hpp:339-341 / 348-350, after the NEE add
+		if (active && key >= 0 && !h.survive) { ended = true; c_term++; }            // Russian roulette ended it
+		if (ended) { float* w = out + pixelID * 3u; w[0] = R.x; w[1] = R.y; w[2] = R.z; }   // ACCUMULATION, Renderer.hpp:424-430 (the add itself: k_merge_contrib)
+
+		// the survivors' slots in the next stream: (key, old slot) order
+		const uint32_t k = static_cast<uint32_t>(key) & (kStreamKeys - 1u);
+		s_rank[ID] = 0u;
+		__syncthreads();
+		uint32_t rank_in_wave = 0u;
+		for (unsigned long long rem = __ballot(h.survive); rem != 0ull;) {
+			const uint32_t leader = static_cast<uint32_t>(__ffsll(static_cast<long long>(rem))) - 1u;
+			const uint32_t k_now = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int32_t>(k), static_cast<int32_t>(leader)));
+			const bool mine = h.survive & (k == k_now);
+			const unsigned long long m = __ballot(mine);
+			if (mine) rank_in_wave = mask_rank(m);
+			if (lane == leader) s_rank[k_now * 4u + wave] = static_cast<uint32_t>(__popcll(m));
+			rem &= ~m;
+		}
+		__syncthreads();
+		const uint32_t mine_cnt = s_rank[ID];                                      // entry ID = (key ID / 4, wave ID % 4): index order is (key, wave) order
+		uint32_t incl = mine_cnt;
+		for (uint32_t off = 1u; off < 64u; off <<= 1) { const uint32_t t = __shfl_up(incl, off, 64); if (lane >= off) incl += t; }
+		if (lane == 63u) s_wave_total[wave] = incl;
+		__syncthreads();
+		uint32_t before = 0u, total = 0u;
+		for (uint32_t w = 0; w < 4u; w++) { const uint32_t c = s_wave_total[w]; before += (w < wave) ? c : 0u; total += c; }
+		s_rank[ID] = before + incl - mine_cnt;
+		__syncthreads();
+		if (h.survive) {
+			const uint32_t ns = s_rank[k * 4u + wave] + rank_in_wave;
+			s_stream[0][ns] = h.P.x; s_stream[1][ns] = h.P.y; s_stream[2][ns] = h.P.z;
+			s_stream[3][ns] = h.ndir.x; s_stream[4][ns] = h.ndir.y; s_stream[5][ns] = h.ndir.z;
+			s_stream[6][ns] = h.thr.x; s_stream[7][ns] = h.thr.y; s_stream[8][ns] = h.thr.z;
+			s_stream[9][ns] = R.x; s_stream[10][ns] = R.y; s_stream[11][ns] = R.z;
+			s_stream[12][ns] = __uint_as_float(pixelID);
+		}
+		__syncthreads();
+		active_rays = total;                                                       // Renderer.hpp:431
+		if (ID < active_rays) {
+			O = { s_stream[0][ID], s_stream[1][ID], s_stream[2][ID] };
+			D = { s_stream[3][ID], s_stream[4][ID], s_stream[5][ID] };
+			thr = { s_stream[6][ID], s_stream[7][ID], s_stream[8][ID] };
+			R = { s_stream[9][ID], s_stream[10][ID], s_stream[11][ID] };
+			pixelID = __float_as_uint(s_stream[12][ID]);
+		}
+		// (the next write of the stream copy lies behind the barriers of the next bounce's shadow vote and slot table)
+	}
+	if (ID == 0u) {
+		atomicAdd(&ctr->rays, c_rays);
+		if (count) atomicAdd(&ctr->spheres, c_rays * sc.n_spheres);             // every ray meets every sphere, as the brute-force reference counts them
+	}
+	wave_sum(c_term, &ctr->terminated);
+	wave_sum(c_drop, &ctr->dropped);
+	wave_sum(c_shadow, &ctr->shadow_rays);
+	if (count) wave_sum(c_shadow_spheres, &ctr->shadow_spheres);
 }
 
 // In-order merge of one batch's contribution buffer ([tile][slot][256][rgb], slot = accumulation index inside the batch; see

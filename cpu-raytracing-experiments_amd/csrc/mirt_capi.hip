@@ -88,6 +88,9 @@ struct mirt_ctx {
 	DeviceBuffer recs, recs_wide, spheres, prim_mat, light_sphere, light_emit, mat_albedo, mat_emission, mat_ggx, hdri;
 	SceneDev scene{};
 	std::vector<float> gloss_decay;  // gloss_decay_table (Renderer.hpp:212) by bounce, read at launch (mirt_set_gloss_decay); missing entries are 0
+	uint32_t stream_order = 0;       // mirt_set_stream_order: 1 = a batch is one k_tile_stream launch (the reference's stream slots and scalar tail, brute force)
+	DeviceBuffer gloss_decay_dev;    // the table as k_tile_stream reads it (its bounce loop runs inside the kernel); uploaded by the first launch after a change
+	bool gloss_decay_dev_valid = false;
 	CameraParams camera{};
 	uint32_t bvh_depth = 0;
 	bool allow_half = true;           // binary16 records when adequate (mirt_debug_set(ctx, "half_boxes", 0) forces f32)
@@ -423,6 +426,7 @@ const decltype(&k_trace_fat<true, kPrimaryNone>) kTraceFat[2][3] = {     // [!co
 const decltype(&k_primary_cand<true>) kPrimaryCand[2] = { k_primary_cand<true>, k_primary_cand<false> };                                    // [!count]
 const decltype(&k_primary_hits<true>) kPrimaryHits[2] = { k_primary_hits<true>, k_primary_hits<false> };                                    // [!count]
 const decltype(&k_shade<false, false>) kShade[2][2] = { { k_shade<false, false>, k_shade<false, true> }, { k_shade<true, false>, k_shade<true, true> } };   // [first][ggx]
+const decltype(&k_tile_stream<false>) kTileStream[2] = { k_tile_stream<false>, k_tile_stream<true> };                                         // [ggx]
 static_assert(kPrimaryNone == 0 && kPrimaryAll == 1 && kPrimaryList == 2, "kTrace / kTraceFat are indexed by PRIMARY");
 
 // What varies between the launches of the trace stage: a bounce of a batch, or the rays of a debug entry point.
@@ -442,6 +446,21 @@ void launch_trace(const mirt_ctx* c, hipStream_t st, const SceneDev& sc, const F
 	// a large scene (100 k spheres: ~100 us per ray) wants as many fat rays in flight as there are (a few hundred per launch); k_trace_fat grid-strides
 	const uint32_t fat_grid = sc.n_spheres > 4096 ? static_cast<uint32_t>(c->n_cu) * 2u : 64u;
 	if (sc.use_bvh) hipLaunchKernelGGL(kTraceFat[!count][primary], dim3(fat_grid), dim3(1024), 0, st, sc, fp, t.in, t.hit, t.fat_closest, t.sh, t.sink, t.fat_shadow, t.ctr, t.listed_pixels);
+}
+
+// mirt_set_stream_order(1): a batch is ONE launch — the whole bounce loop of a (tile, accumulation) stream runs in one workgroup, in the reference's
+// slot order (kernels.hpp "EXACT STREAM ORDER"); brute force whatever policy.use_bvh says.  Same contribution buffer and merge as the default path.
+int launch_tile_stream(mirt_ctx* c, hipStream_t st, const SceneDev& sc, const FrameParams& fp, uint32_t batch_n, float* contrib, DevCounters* ctr, bool count) {
+	if (!c->gloss_decay_dev_valid) {                                                  // (batches in flight on other streams may still read the old table)
+		HIP_TRY(c, sync_all(c));
+		HIP_TRY(c, c->gloss_decay_dev.ensure(std::max<size_t>(c->gloss_decay.size(), 1) * sizeof(float)));
+		if (!c->gloss_decay.empty()) HIP_TRY(c, hipMemcpy(c->gloss_decay_dev.ptr, c->gloss_decay.data(), c->gloss_decay.size() * sizeof(float), hipMemcpyHostToDevice));
+		c->gloss_decay_dev_valid = true;
+	}
+	Bracket t(c, MIRT_K_TRACE, st);
+	hipLaunchKernelGGL(kTileStream[c->policy.brdf != 0], dim3(c->n_tiles * batch_n), dim3(kTileSize), 0, st, sc, fp, contrib, ctr, c->mat_ggx.as<float4>(),
+	                   c->gloss_decay_dev.as<float>(), static_cast<uint32_t>(c->gloss_decay.size()), count ? 1u : 0u);
+	return MIRT_OK;
 }
 
 // One batch = up to batch_limit() consecutive Accumulate() calls traced together (path id = (slot << pix_bits) | pixel).
@@ -486,34 +505,39 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 	if (c->debug_poison_contrib)
 		HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sl.contrib.ptr), 0x7fc0deadu, sl.contrib.bytes / sizeof(float), st));   // a quiet NaN
 	HIP_TRY(c, hipMemsetAsync(bc.w, 0, BatchCounters::words(nb) * sizeof(uint32_t), st));
-	// bounce 0 has no ray stream: k_trace<PRIMARY> and k_shade<FIRST> derive the camera ray from its index (RAY GENERATION, Renderer.hpp:113-127)
-	for (uint32_t bounce = 0; bounce < nb; bounce++) {
-		const StreamBuf& in = sl.stream_buf[bounce & 1u];
-		const StreamBuf& out = sl.stream_buf[(bounce & 1u) ^ 1u];
-		const bool shadow_pending = fp.mis && bounce > 0;           // NEE rays emitted by k_shade(bounce-1)
-		const bool lists = bounce == 0 && bundle;
-		{ Bracket t(c, MIRT_K_TRACE, st);
-		  if (lists) {
-		    // camera rays through per-pixel candidate lists (kernels.hpp kCollect): one cone traversal per pixel, then k_primary_hits intersects every
-		    // sample with its pixel's list.  Pixels without a list are listed in in.path (count: listed_pixels) and all their samples traced like any other ray.
-		    const FatList none{ bc.unused_fat_count(), fat_lists, 0u };
-		    hipLaunchKernelGGL(kPrimaryCand[!count], dim3(trace_grid(c, fp.n_pix)), dim3(kTraceBlock), trace_lds(c), st, sc, fp, sl.cand.as<uint32_t>(), bundle_half_angle(c),
-		                       bc.cand_work(), none, ctr, in.path, bc.listed_pixels());
-		    const uint32_t hgrid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
-		    hipLaunchKernelGGL(kPrimaryHits[!count], dim3(hgrid), dim3(kBlock), 0, st, sc, fp, sl.cand.as<uint32_t>(), sl.hit, ctr);
-		  }
-		  // the adds of bounce-1 that waited for occlusion land in the paths' contribution words before k_shade adds this bounce's terms;
-		  // a surviving path's record finds its origin and its path id in stream `in` (= out of bounce-1)
-		  const ShadowSink sink{ in.path, in.px, in.py, in.pz, contrib, batch_n, fp.pix_bits, nullptr };
-		  const TraceLaunch tl{ in, sl.hit, lists ? Queue{ bc.listed_pixels(), 0u } : bc.stream_queue(bounce), bc.closest_work(bounce),      // kPrimaryList: n[0] = listed pixels
-		                        sl.shadow_buf, sink, shadow_pending ? bc.shadow_queue(bounce - 1) : bc.empty_queue(), bc.shadow_work(shadow_pending ? bounce - 1 : 0),
-		                        bc.fat_closest(bounce, fat_lists), bc.fat_shadow(bounce, fat_lists), bc.listed_pixels(), ctr };
-		  launch_trace(c, st, sc, fp, total, count, lists ? kPrimaryList : bounce == 0 ? kPrimaryAll : kPrimaryNone, tl); }
-		{ Bracket t(c, MIRT_K_SHADE, st);
-		  // policy.brdf = 1 (#define BRDF 1): Closure<GGX> with this bounce's gloss decay, passed by value
-		  const float decay = bounce < c->gloss_decay.size() ? c->gloss_decay[bounce] : 0.0f;
-		  hipLaunchKernelGGL(kShade[bounce == 0][c->policy.brdf != 0], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
-		                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay); }
+	if (c->stream_order) {
+		const int r = launch_tile_stream(c, st, sc, fp, batch_n, contrib, ctr, count);
+		if (r) return r;
+	} else {
+		// bounce 0 has no ray stream: k_trace<PRIMARY> and k_shade<FIRST> derive the camera ray from its index (RAY GENERATION, Renderer.hpp:113-127)
+		for (uint32_t bounce = 0; bounce < nb; bounce++) {
+			const StreamBuf& in = sl.stream_buf[bounce & 1u];
+			const StreamBuf& out = sl.stream_buf[(bounce & 1u) ^ 1u];
+			const bool shadow_pending = fp.mis && bounce > 0;           // NEE rays emitted by k_shade(bounce-1)
+			const bool lists = bounce == 0 && bundle;
+			{ Bracket t(c, MIRT_K_TRACE, st);
+			  if (lists) {
+			    // camera rays through per-pixel candidate lists (kernels.hpp kCollect): one cone traversal per pixel, then k_primary_hits intersects every
+			    // sample with its pixel's list.  Pixels without a list are listed in in.path (count: listed_pixels) and all their samples traced like any other ray.
+			    const FatList none{ bc.unused_fat_count(), fat_lists, 0u };
+			    hipLaunchKernelGGL(kPrimaryCand[!count], dim3(trace_grid(c, fp.n_pix)), dim3(kTraceBlock), trace_lds(c), st, sc, fp, sl.cand.as<uint32_t>(), bundle_half_angle(c),
+			                       bc.cand_work(), none, ctr, in.path, bc.listed_pixels());
+			    const uint32_t hgrid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
+			    hipLaunchKernelGGL(kPrimaryHits[!count], dim3(hgrid), dim3(kBlock), 0, st, sc, fp, sl.cand.as<uint32_t>(), sl.hit, ctr);
+			  }
+			  // the adds of bounce-1 that waited for occlusion land in the paths' contribution words before k_shade adds this bounce's terms;
+			  // a surviving path's record finds its origin and its path id in stream `in` (= out of bounce-1)
+			  const ShadowSink sink{ in.path, in.px, in.py, in.pz, contrib, batch_n, fp.pix_bits, nullptr };
+			  const TraceLaunch tl{ in, sl.hit, lists ? Queue{ bc.listed_pixels(), 0u } : bc.stream_queue(bounce), bc.closest_work(bounce),      // kPrimaryList: n[0] = listed pixels
+			                        sl.shadow_buf, sink, shadow_pending ? bc.shadow_queue(bounce - 1) : bc.empty_queue(), bc.shadow_work(shadow_pending ? bounce - 1 : 0),
+			                        bc.fat_closest(bounce, fat_lists), bc.fat_shadow(bounce, fat_lists), bc.listed_pixels(), ctr };
+			  launch_trace(c, st, sc, fp, total, count, lists ? kPrimaryList : bounce == 0 ? kPrimaryAll : kPrimaryNone, tl); }
+			{ Bracket t(c, MIRT_K_SHADE, st);
+			  // policy.brdf = 1 (#define BRDF 1): Closure<GGX> with this bounce's gloss decay, passed by value
+			  const float decay = bounce < c->gloss_decay.size() ? c->gloss_decay[bounce] : 0.0f;
+			  hipLaunchKernelGGL(kShade[bounce == 0][c->policy.brdf != 0], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
+			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay); }
+		}
 	}
 	HIP_TRY(c, hipGetLastError());
 	// merges are enqueued on the main stream in batch order => every bucket receives its adds in accumulation order
@@ -796,7 +820,7 @@ int mirt_destroy(mirt_ctx* c) {
 	c->slots.clear();
 	for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
 	DeviceBuffer* bufs[] = { &c->recs, &c->recs_wide, &c->spheres, &c->prim_mat, &c->light_sphere, &c->light_emit, &c->mat_albedo, &c->mat_emission,
-	                         &c->mat_ggx, &c->hdri, &c->accumulator, &c->framebuffer, &c->counters };
+	                         &c->mat_ggx, &c->hdri, &c->accumulator, &c->framebuffer, &c->counters, &c->gloss_decay_dev };
 	for (DeviceBuffer* b : bufs) b->release();
 	if (c->frame_host) (void)hipHostFree(c->frame_host);
 	if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -864,8 +888,18 @@ int mirt_set_gloss_decay(mirt_ctx* c, const float* decay, uint32_t n) {
 		if (!(decay[i] >= 0.0f && decay[i] <= 1.0f)) return fail(c, MIRT_ERR_ARG, "gloss decay[%u] = %g is not in [0, 1]", i, static_cast<double>(decay[i]));
 	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render with the table they were issued under
 	c->gloss_decay.assign(decay, decay + n);
+	c->gloss_decay_dev_valid = false;
 	return MIRT_OK;
 }
+int mirt_set_stream_order(mirt_ctx* c, uint32_t exact) {
+	if (!c) return MIRT_ERR_ARG;
+	if (exact > 1) return fail(c, MIRT_ERR_ARG, "stream order %u is neither 0 (any order, FMA form for every ray) nor 1 (the reference's slots and scalar tail)", exact);
+	if (exact == c->stream_order) return MIRT_OK;
+	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render in the mode they were issued under
+	c->stream_order = exact;
+	return MIRT_OK;
+}
+int mirt_get_stream_order(const mirt_ctx* c, uint32_t* exact) { if (!c || !exact) return MIRT_ERR_ARG; *exact = c->stream_order; return MIRT_OK; }
 int mirt_get_policy(const mirt_ctx* c, mirt_policy* p) {
 	if (!c || !p) return MIRT_ERR_ARG;
 	*p = c->policy;

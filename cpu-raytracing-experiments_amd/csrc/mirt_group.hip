@@ -170,6 +170,12 @@ int mirt_group_set_gloss_decay(mirt_group* g, const float* decay, uint32_t n) {
 	if (g->full) FULL_TRY(g, "mirt_set_gloss_decay", mirt_set_gloss_decay(g->full, decay, n));
 	return MIRT_OK;
 }
+int mirt_group_set_stream_order(mirt_group* g, uint32_t exact) {
+	if (!g) return MIRT_ERR_ARG;
+	FOR_MEMBERS(g, "mirt_set_stream_order", mirt_set_stream_order(ctx, exact));
+	if (g->full) FULL_TRY(g, "mirt_set_stream_order", mirt_set_stream_order(g->full, exact));
+	return MIRT_OK;
+}
 int mirt_group_set_policy(mirt_group* g, const mirt_policy* p) {
 	if (!g || !p) return MIRT_ERR_ARG;
 	FOR_MEMBERS(g, "mirt_set_policy", mirt_set_policy(ctx, p));

@@ -5,8 +5,9 @@
 // environment map the way the constructor does (stbi_loadf(..., 4), Application.cpp:225-231); --ambient sets sky.ambient_color, which scales it.
 //
 //   mirt_headless --scene default9|furnace|bvh_test|brdf_test|synthetic:N [--size WxH] [--spp N | --frames N] [--bounces B] [--buckets K] [--brute] [--devices 0,1,..]
-//                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--out frame.hdr|frame.pfm]
+//                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm]
 // --brdf 1 renders every hit with the GGX closure (#define BRDF 1, Renderer.hpp:70), --gloss-decay gives its per-bounce table (:212).
+// --exact-stream-order replays the reference's stream slots and its scalar intersection tail (BVH.hpp:270-286; brute force, mirt_set_stream_order).
 // --devices: the GPUs the one Renderer object uses (tile rows split over them inside the library, one RCCL gather per frame read).
 // --frames N is the UI loop itself (Application.cpp:373-380): N frames of { Accumulate(); Render(); }; the report lists the frames on
 // which Render() produced output (every `buckets`-th, Renderer.hpp:437) and a hash of the last frame shown.
@@ -155,6 +156,7 @@ int main(int argc, char** argv) {
 	bool ambient_set = false;
 	std::vector<int> devices = { 0 };
 	std::vector<float> gloss_decay;
+	bool exact_stream_order = false;
 	if (argc == 4 && std::string(argv[1]) == "--convert-hdr") {
 		// file-format check without a GPU: read a picture like stbi_loadf does (top-down) and store it again like Image::Store does (which
 		// flips, so the rows are handed over bottom-up): the output decodes to the same texels
@@ -178,6 +180,7 @@ int main(int argc, char** argv) {
 		else if (a == "--brute") policy.use_bvh = false;
 		else if (a == "--brdf") policy.brdf = static_cast<uint32_t>(std::atoi(next()));
 		else if (a == "--gloss-decay") { for (const char* p = next(); *p;) { gloss_decay.push_back(static_cast<float>(std::atof(p))); while (*p && *p != ',') p++; if (*p == ',') p++; } }
+		else if (a == "--exact-stream-order") exact_stream_order = true;
 		else if (a == "--out") out = next();
 		else if (a == "--devices") { devices.clear(); for (const char* p = next(); *p;) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p == ',') p++; } if (devices.empty()) return 2; }
 		else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -199,6 +202,7 @@ int main(int argc, char** argv) {
 
 		Renderer renderer{ scene, policy, devices };
 		renderer.SetGlossDecay(gloss_decay);
+		renderer.SetStreamOrder(exact_stream_order);
 		// pad the viewport to the tile requirement like UIRender does (Application.cpp:365-372)
 		const uint32_t t = static_cast<uint32_t>(Renderer::RequiredTiling());
 		w = (w + t - 1) & ~(t - 1); h = (h + t - 1) & ~(t - 1);

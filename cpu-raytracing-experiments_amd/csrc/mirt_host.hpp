@@ -170,6 +170,9 @@ public:
 	void SetGlossDecay(const std::vector<float>& decay) {
 		check(mirt_group_set_gloss_decay(group_, decay.data(), static_cast<uint32_t>(decay.size())), "mirt_group_set_gloss_decay");
 	}
+	// The reference's stream slots and scalar intersection tail (BVH.hpp:270-286) instead of the wavefront order (mirt.h, mirt_set_stream_order):
+	// brute-force traversal, for comparisons against the shipped binary.
+	void SetStreamOrder(bool exact) { check(mirt_group_set_stream_order(group_, exact ? 1u : 0u), "mirt_group_set_stream_order"); }
 	// Renderer.hpp:73-434.  Asynchronous: Render() / counters() / the destructor wait for the GPUs; called once per frame the library
 	// still batches the frames between two Render()s that are due (mirt.h, mirt_accumulate_async).
 	void Accumulate(uint32_t n_calls = 1) { check(mirt_group_accumulate_async(group_, n_calls), "mirt_group_accumulate_async"); }

@@ -153,6 +153,17 @@ int mirt_get_policy(const mirt_ctx* ctx, mirt_policy* policy);   /* with the val
  * or beyond n use 0.  n <= 1024; every value finite and in [0, 1], else MIRT_ERR_ARG.  decay = NULL or n = 0: all zeros (the
  * default).  Deferred mirt_accumulate_async calls are launched first, with the table they were issued under. */
 int mirt_set_gloss_decay(mirt_ctx* ctx, const float* decay, uint32_t n);
+/* Stream order (Q14).  exact = 0 (default): the wavefront pipeline; a path has no stream slot and every closest-hit test uses the FMA
+ * form of BVH.hpp:250-268.  exact = 1: a fidelity mode that replays the reference's 256-ray stream of every (tile, accumulation) —
+ * slot ID of bounce 0 is pixel ID, the hits are ordered by the stable counting sort on matID (DataStreams.hpp:221-253), the survivors
+ * of Russian roulette are compacted in that order (Renderer.hpp:357-404) — and tests the last `active_rays % 8` slots of a stream
+ * with the unfused scalar tail of BVH.hpp:270-286, as the shipped binary does.  Traversal is brute force over all spheres in this
+ * mode (the reference as shipped, USEBVH false): policy.use_bvh, reference_tree, gpu_build and trace_primary_rays are accepted and
+ * change nothing.  Everything else — closures, NEE, MIS, roulette, buckets, batching, policy.streams, tile ranges — is as in mode 0.
+ * Several times slower than the default path; never the benched one.  Other values: MIRT_ERR_ARG.  Deferred mirt_accumulate_async
+ * calls are launched first, in the mode they were issued under; the accumulator is not reset. */
+int mirt_set_stream_order(mirt_ctx* ctx, uint32_t exact);
+int mirt_get_stream_order(const mirt_ctx* ctx, uint32_t* exact);
 
 /* Renderer::Resize, Renderer.hpp:53-63: h_tiles = w/16, v_tiles = h/16 (truncating), allocates and zeroes
  * the accumulator, accumulations = 0.  Owns all tiles until mirt_set_tile_range says otherwise. */
@@ -226,6 +237,7 @@ int mirt_group_set_scene(mirt_group* group,
 int mirt_group_set_camera(mirt_group* group, const float pos[3], const float orient_xyzw[4], float half_width, float half_height, float z, float exposure);
 int mirt_group_set_policy(mirt_group* group, const mirt_policy* policy);
 int mirt_group_set_gloss_decay(mirt_group* group, const float* decay, uint32_t n);
+int mirt_group_set_stream_order(mirt_group* group, uint32_t exact);             /* mirt_set_stream_order on every member */
 int mirt_group_resize(mirt_group* group, uint32_t width, uint32_t height);      /* Renderer::Resize + the tile-row split */
 int mirt_group_reset(mirt_group* group);                                         /* Renderer::ResetAccumulator */
 int mirt_group_accumulate(mirt_group* group, uint32_t n_calls);                  /* n x Renderer::Accumulate on every device, then waits */
