@@ -25,6 +25,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmirt.so")
 
 MIRT_OK, MIRT_NOT_READY = 0, 1
+AOV_DEPTH, AOV_NORMAL, AOV_ALBEDO = 0, 1, 2       # mirt.h MIRT_AOV_*
+AOV_PLANES = 7
 KERNEL_CLASSES = ("raygen", "trace", "shade", "shadow", "resolve")
 
 
@@ -94,6 +96,12 @@ def load_library():
         "mirt_accumulator_device": [P, C.POINTER(vp), C.POINTER(C.c_size_t)],
         "mirt_load_accumulator": [P, vp, i32, u32],
         "mirt_render": [P, vp],
+        "mirt_set_aov": [P, u32], "mirt_get_aov": [P, C.POINTER(u32)],
+        "mirt_aov_floats": [P, C.POINTER(C.c_size_t)],
+        "mirt_read_aov": [P, vp],
+        "mirt_aov_device": [P, C.POINTER(vp), C.POINTER(C.c_size_t)],
+        "mirt_load_aov": [P, vp, i32],
+        "mirt_render_aov": [P, i32, vp],
         "mirt_get_counters": [P, C.POINTER(Counters)],
         "mirt_get_kernel_times": [P, C.POINTER(KernelTimes), i32],
         "mirt_get_stream": [P, C.POINTER(vp)],
@@ -128,6 +136,10 @@ def load_library():
         "mirt_group_accumulator_floats": [G, C.POINTER(C.c_size_t)],
         "mirt_group_read_accumulator": [G, vp],
         "mirt_group_render": [G, vp],
+        "mirt_group_set_aov": [G, u32],
+        "mirt_group_aov_floats": [G, C.POINTER(C.c_size_t)],
+        "mirt_group_read_aov": [G, vp],
+        "mirt_group_render_aov": [G, i32, vp],
         "mirt_group_rccl_selftest": [i32, C.c_size_t],
     })
     for name, argtypes in sigs.items():
@@ -174,6 +186,16 @@ def light_list(geometry: np.ndarray, material: np.ndarray) -> np.ndarray:
     return out[: n.value].copy()
 
 
+def _aov_image(height: int, width: int, which: int, out):
+    """The buffer mirt_render_aov fills: (height, width) for depth, (height, width, 3) for normal and albedo."""
+    shape = (height, width) if which == AOV_DEPTH else (height, width, 3)
+    if out is None:
+        return np.zeros(shape, dtype=np.float32)
+    if out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous:
+        raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
+    return out
+
+
 def _decay_array(decay) -> np.ndarray:
     return np.ascontiguousarray([] if decay is None else decay, dtype=np.float32).reshape(-1)
 
@@ -188,7 +210,7 @@ class Renderer:
     def __init__(self, scene: Scene, device: int = 0, max_bounces: int = 16, buckets: int = 5, mis: bool = True,
                  use_bvh: bool = False, count_traffic: bool = False, profile: bool = False, max_batch: int = 0,
                  allow_half_boxes: bool = True, reference_tree: bool = False, streams: int = 0, gpu_build: bool = False, trace_primary_rays: bool = False,
-                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False):
+                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False):
         self._lib = load_library()
         self._ctx = C.c_void_p()
         rc = self._lib.mirt_create(device, C.byref(self._ctx))
@@ -205,6 +227,8 @@ class Renderer:
             self.set_gloss_decay(gloss_decay)
         if exact_stream_order:
             self.set_stream_order(True)
+        if aov:
+            self.set_aov(True)
         self.UpdateScene()
 
     # -- plumbing ---------------------------------------------------------------------------
@@ -341,6 +365,43 @@ class Renderer:
         ptr = C.c_void_p(src) if is_device else _ptr(np.ascontiguousarray(src, dtype=np.float32))
         self._check(self._lib.mirt_load_accumulator(self._ctx, ptr, int(is_device), accumulations))
 
+    # -- first-hit AOVs (mirt.h "first-hit AOVs") ---------------------------------------------------------
+    def set_aov(self, on: bool = True):
+        """True: every accumulation also adds each camera ray's depth, normal and albedo into a slab beside the accumulator
+        (the reference's compiled-out FIRST BOUNCE OUTPUTS, Renderer.hpp:216-231).  Only before the first accumulation; not in
+        exact stream order.  False: frees the slab."""
+        self._check(self._lib.mirt_set_aov(self._ctx, int(on)))
+
+    @property
+    def aov_enabled(self) -> bool:
+        v = C.c_uint32(0)
+        self._check(self._lib.mirt_get_aov(self._ctx, C.byref(v)))
+        return bool(v.value)
+
+    def aov(self) -> np.ndarray:
+        """[local tile][plane][256] f32 sums over all accumulations: plane 0 depth, 1-3 normal, 4-6 albedo (F0 with brdf = 1)."""
+        n = C.c_size_t(0)
+        self._check(self._lib.mirt_aov_floats(self._ctx, C.byref(n)))
+        out = np.empty(n.value, dtype=np.float32)
+        self._check(self._lib.mirt_read_aov(self._ctx, _ptr(out)))
+        return out.reshape(n.value // (AOV_PLANES * 256), AOV_PLANES, 256)
+
+    def aov_device(self):
+        p, b = C.c_void_p(), C.c_size_t(0)
+        self._check(self._lib.mirt_aov_device(self._ctx, C.byref(p), C.byref(b)))
+        return p.value, b.value
+
+    def load_aov(self, src, is_device: bool = False):
+        ptr = C.c_void_p(src) if is_device else _ptr(np.ascontiguousarray(src, dtype=np.float32))
+        self._check(self._lib.mirt_load_aov(self._ctx, ptr, int(is_device)))
+
+    def render_aov(self, which: int, out: np.ndarray = None):
+        """One AOV (AOV_DEPTH, AOV_NORMAL, AOV_ALBEDO) resolved over the image, row 0 = y 0: depth (height, width), the others
+        (height, width, 3); only this context's tiles are written.  None (and `out` untouched) before the first accumulation."""
+        img = _aov_image(self.height, self.width, which, out)
+        rc = self._check(self._lib.mirt_render_aov(self._ctx, int(which), _ptr(img)))
+        return img if rc == MIRT_OK else None
+
     def counters(self) -> dict:
         c = Counters()
         self._check(self._lib.mirt_get_counters(self._ctx, C.byref(c)))
@@ -410,7 +471,7 @@ class GroupRenderer:
 
     def __init__(self, scene: Scene, devices=(0,), max_bounces: int = 16, buckets: int = 5, mis: bool = True, use_bvh: bool = True,
                  count_traffic: bool = False, max_batch: int = 0, streams: int = 0, reference_tree: bool = False, gpu_build: bool = False,
-                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False):
+                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False):
         self._lib = load_library()
         self._g = C.c_void_p()
         dev = (C.c_int * len(devices))(*devices)
@@ -427,6 +488,8 @@ class GroupRenderer:
             self.set_gloss_decay(gloss_decay)
         if exact_stream_order:
             self.set_stream_order(True)
+        if aov:
+            self.set_aov(True)
         self.UpdateScene()
 
     def _check(self, rc):
@@ -519,6 +582,26 @@ class GroupRenderer:
         out = np.empty(n.value, dtype=np.float32)
         self._check(self._lib.mirt_group_read_accumulator(self._g, _ptr(out)))
         return out.reshape(n.value // (self.policy.buckets * 768), self.policy.buckets, 3, 256)
+
+    def set_aov(self, on: bool = True):
+        """Renderer.set_aov on every member."""
+        self._check(self._lib.mirt_group_set_aov(self._g, int(on)))
+
+    def aov(self) -> np.ndarray:
+        """The whole image's [tile][plane][256] AOV sums in LaunchIndex order (gathers first)."""
+        n = C.c_size_t(0)
+        self._check(self._lib.mirt_group_aov_floats(self._g, C.byref(n)))
+        out = np.empty(n.value, dtype=np.float32)
+        self._check(self._lib.mirt_group_read_aov(self._g, _ptr(out)))
+        return out.reshape(n.value // (AOV_PLANES * 256), AOV_PLANES, 256)
+
+    read_aov = aov
+
+    def render_aov(self, which: int, out: np.ndarray = None):
+        """Renderer.render_aov of the whole frame (gathers first)."""
+        img = _aov_image(self.height, self.width, which, out)
+        rc = self._check(self._lib.mirt_group_render_aov(self._g, int(which), _ptr(img)))
+        return img if rc == MIRT_OK else None
 
     def counters(self) -> dict:
         c = Counters()

@@ -1105,6 +1105,69 @@ __global__ __launch_bounds__(kBlock) void k_primary_hits(SceneDev sc, FrameParam
 }
 
 // ------------------------------------------------------------------------------------------------
+// FIRST BOUNCE OUTPUTS — Renderer.hpp:216-231 (written down in the reference, compiled out there): per pixel, the running sums of the
+// camera ray's hit distance (1e4 on a miss), its world-space shading normal and the colour its closure is set up with (:208-210).
+// Slab [local tile][plane 0..6][256] f32 (AccumulationTile with seven planes instead of buckets x 3; not bucketed): plane 0 depth,
+// 1-3 N.xyz, 4-6 albedo (policy.brdf = 0) or F0 (policy.brdf = 1) — `mat_colour` is that table.
+// One lane per local pixel, as in k_primary_hits: tile, x, y and seed[ID] are set up once, the seven sums live in registers over the
+// batch's accumulations — added in accumulation order, which is part of the result — and are stored once.  A sample costs its ray
+// (regenerated as k_shade<FIRST> does) + its 8-B hit record, read for 64 neighbouring pixels at a time; the sphere and colour of a hit
+// are fetched again only when the prim differs from the previous sample's (the samples of a pixel mostly hit the same sphere).
+// The hit arithmetic is the closest-hit shader's of k_shade, operation for operation.  Counts nothing into DevCounters.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t kAovPlanes = 7;
+constexpr float kAovMissDepth = 1e4f;             // Renderer.hpp:228
+__global__ __launch_bounds__(kBlock) void k_first_hit_aov(SceneDev sc, FrameParams fp, const HitRec* __restrict__ hit_in, const float4* __restrict__ mat_colour, float* __restrict__ aov) {
+	const f3 O{ fp.cam.pos[0], fp.cam.pos[1], fp.cam.pos[2] };
+	for (uint32_t pix = blockIdx.x * kBlock + threadIdx.x; pix < fp.n_pix; pix += gridDim.x * kBlock) {
+		uint32_t tile; int32_t x, y;
+		pixel_xy(fp, pix, tile, x, y);
+		const uint32_t seed = (tile * kTileSize + (pix & 255u)) * (fp.max_bounces * 2u + 1u);      // seed[ID], Renderer.hpp:107
+		float* w = aov + static_cast<size_t>(pix >> 8) * (kAovPlanes * kTileSize) + (pix & 255u);
+		float sum[kAovPlanes];
+		for (uint32_t k = 0; k < kAovPlanes; k++) sum[k] = w[k * kTileSize];
+		int32_t cached = -1;
+		float4 hs = make_float4(0.0f, 0.0f, 0.0f, 0.0f), colour = hs;
+		for (uint32_t slot = 0; slot < fp.batch_n; slot++) {
+			uint32_t rng = hash_2d(fp.acc_base + slot + 1u, seed);                 // ++accumulations, Renderer.hpp:74,117
+			const float s0 = rand_unit_float(rng);
+			const float s1 = rand_unit_float(rng);
+			const f3 D = camera_ray_dir(fp.cam, x, y, s0, s1);
+			const HitRec h = hit_in[static_cast<size_t>(slot) * fp.n_pix + pix];
+			if (h.prim < 0) { sum[0] += kAovMissDepth; continue; }
+			if (h.prim != cached) { hs = sc.spheres[h.prim]; colour = mat_colour[sc.prim_mat[h.prim]]; cached = h.prim; }
+			const float depth = h.tfar;
+			const f3 hit{ O.x + D.x * depth, O.y + D.y * depth, O.z + D.z * depth };      // CLOSEST HIT SHADER, Renderer.hpp:169-214 (k_shade)
+			f3 N = normalize3(f3{ hit.x - hs.x, hit.y - hs.y, hit.z - hs.z });
+			if (dot3(N, D) >= 0.0f) N = f3{ -N.x, -N.y, -N.z };
+			sum[0] += depth;
+			sum[1] += N.x; sum[2] += N.y; sum[3] += N.z;
+			sum[4] += colour.x; sum[5] += colour.y; sum[6] += colour.z;
+		}
+		for (uint32_t k = 0; k < kAovPlanes; k++) w[k * kTileSize] = sum[k];
+	}
+}
+// mirt_render_aov: one of the three outputs of the slab above, row-major over the image (row 0 = y 0), 1 (depth) or 3 floats per pixel.
+// Depth and colour: sum / accumulations; normal: normalize3(sum), (0,0,0) where the sum has no length.  IEEE division and sqrt.
+constexpr int kAovDepth = 0, kAovNormal = 1, kAovAlbedo = 2;
+__global__ __launch_bounds__(kBlock) void k_resolve_aov(const float* __restrict__ aov, float* __restrict__ out, uint32_t n_pix, uint32_t first_tile, uint32_t run_tiles,
+                                                        uint32_t stride_tiles, uint32_t h_tiles, uint32_t width, int which, float accumulations) {
+	for (uint32_t pix = blockIdx.x * kBlock + threadIdx.x; pix < n_pix; pix += gridDim.x * kBlock) {
+		const float* src = aov + static_cast<size_t>(pix >> 8) * (kAovPlanes * kTileSize) + (pix & 255u);
+		const uint32_t tile = global_tile(first_tile, run_tiles, stride_tiles, pix >> 8), ID = pix & 255u;
+		const uint32_t x = kTileRoot * (tile % h_tiles) + (ID & 15u);
+		const uint32_t y = kTileRoot * (tile / h_tiles) + (ID >> 4);
+		const size_t at = static_cast<size_t>(y) * width + x;
+		if (which == kAovDepth) { out[at] = src[0] / accumulations; continue; }
+		const uint32_t first = which == kAovNormal ? 1u : 4u;
+		f3 v{ src[first * kTileSize], src[(first + 1u) * kTileSize], src[(first + 2u) * kTileSize] };
+		if (which == kAovNormal) v = dot3(v, v) == 0.0f ? f3{ 0.0f, 0.0f, 0.0f } : normalize3(v);
+		else v = { v.x / accumulations, v.y / accumulations, v.z / accumulations };
+		out[at * 3u] = v.x; out[at * 3u + 1u] = v.y; out[at * 3u + 2u] = v.z;
+	}
+}
+
+// ------------------------------------------------------------------------------------------------
 // Accumulator addressing — AccumulationTile<k>, Renderer.hpp:43-46,84: [tile][bucket][r,g,b][256]
 // ------------------------------------------------------------------------------------------------
 // Sky::operator(), Primitives.hpp:35-46

@@ -63,6 +63,7 @@ struct PipeSlot {
 	DeviceBuffer cand;               // per local pixel: candidate spheres of its bundle of camera rays (k_primary_cand), kCandStride words
 	hipEvent_t batch_done = nullptr; // recorded on `stream` after the batch's last kernel
 	hipEvent_t merged = nullptr;     // recorded on the main stream after the batch was merged (slot reusable)
+	hipEvent_t aov_done = nullptr;   // mirt_set_aov(1) only: recorded on `stream` after the batch's k_first_hit_aov (created by the first such batch)
 	bool in_use = false;
 	StreamBuf stream_buf[2]{};
 	ShadowBuf shadow_buf{};
@@ -97,6 +98,9 @@ struct mirt_ctx {
 
 	// frame state
 	DeviceBuffer accumulator;        // [local tile][bucket][3][256] f32
+	uint32_t aov_on = 0;             // mirt_set_aov: every batch also sums its camera rays' depth, normal and closure colour
+	DeviceBuffer aov;                // [local tile][plane 0..6][256] f32 (kernels.hpp k_first_hit_aov); allocated while aov_on
+	hipEvent_t aov_prev = nullptr;   // aov_done of the latest pipelined batch: the next batch's k_first_hit_aov waits for it (borrowed from its slot)
 	DeviceBuffer framebuffer;        // width*height float4
 	float* frame_host = nullptr;     // pinned staging copy of the framebuffer for mirt_render (pageable memory halves the copy rate)
 	size_t frame_host_bytes = 0;
@@ -279,11 +283,13 @@ int ensure_streams(mirt_ctx* c) {
 	const size_t acc_bytes = static_cast<size_t>(c->n_tiles) * batch_limit(c) * 3 * kTileSize * sizeof(float);     // contribution buffer: [tile][slot][256][rgb]
 	if (cap == c->capacity && nb == c->arena_bounces && c->slots.size() == want && c->slots[0].contrib.bytes >= acc_bytes) return MIRT_OK;
 	HIP_TRY(c, sync_all(c));
+	c->aov_prev = nullptr;                                                   // (every batch has finished; the event's slot may go away below)
 	while (c->slots.size() > want) {
 		PipeSlot& sl = c->slots.back();
 		sl.arena.release(); sl.counts.release(); sl.contrib.release(); sl.fat.release(); sl.cand.release();
 		if (sl.batch_done) (void)hipEventDestroy(sl.batch_done);
 		if (sl.merged) (void)hipEventDestroy(sl.merged);
+		if (sl.aov_done) (void)hipEventDestroy(sl.aov_done);
 		if (sl.stream) (void)hipStreamDestroy(sl.stream);
 		c->slots.pop_back();
 	}
@@ -339,11 +345,21 @@ int ensure_streams(mirt_ctx* c) {
 	return MIRT_OK;
 }
 
+size_t aov_floats(const mirt_ctx* c) { return c->aov_on ? static_cast<size_t>(c->n_tiles) * kAovPlanes * kTileSize : 0; }
+// The AOV slab of the current tile set, zeroed (nothing while AOVs are off).  The caller has synchronised every stream.
+int alloc_aov(mirt_ctx* c) {
+	const size_t floats = aov_floats(c);
+	HIP_TRY(c, c->aov.ensure(floats * sizeof(float)));
+	if (floats) HIP_TRY(c, hipMemsetAsync(c->aov.ptr, 0, floats * sizeof(float), c->stream));
+	return MIRT_OK;
+}
+
 int alloc_accumulator(mirt_ctx* c) {
 	const size_t floats = static_cast<size_t>(c->n_tiles) * c->policy.buckets * 3 * kTileSize;
 	HIP_TRY(c, sync_all(c));
 	HIP_TRY(c, c->accumulator.ensure(floats * sizeof(float)));
 	if (floats) HIP_TRY(c, hipMemsetAsync(c->accumulator.ptr, 0, floats * sizeof(float), c->stream));
+	if (c->aov_on) { const int r = alloc_aov(c); if (r) return r; }
 	HIP_TRY(c, hipMemsetAsync(c->counters.ptr, 0, sizeof(DevCounters), c->stream));
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	for (PipeSlot& sl : c->slots) sl.in_use = false;
@@ -463,6 +479,23 @@ int launch_tile_stream(mirt_ctx* c, hipStream_t st, const SceneDev& sc, const Fr
 	return MIRT_OK;
 }
 
+// mirt_set_aov(1): the camera rays' hit records of the batch lie in sl.hit (slot * n_pix + pixel) from the bounce-0 trace launches until the
+// bounce-1 trace overwrites them; k_first_hit_aov runs in between, on the batch's own stream.  The slab holds running sums and float
+// addition does not associate, so batches in flight on different streams must reach it in batch order: each waits for the event recorded
+// after the previous batch's kernel.  (One batch at a time: everything is on the main stream already.)
+int launch_first_hit_aov(mirt_ctx* c, PipeSlot& sl, hipStream_t st, const SceneDev& sc, const FrameParams& fp) {
+	const bool pipelined = c->slots.size() > 1;
+	if (pipelined) {
+		if (!sl.aov_done) HIP_TRY(c, hipEventCreateWithFlags(&sl.aov_done, hipEventDisableTiming));
+		if (c->aov_prev && c->aov_prev != sl.aov_done) HIP_TRY(c, hipStreamWaitEvent(st, c->aov_prev, 0));   // (the slot's own previous batch is ahead on this very stream)
+	}
+	{ Bracket t(c, MIRT_K_RESOLVE, st);
+	  const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
+	  hipLaunchKernelGGL(k_first_hit_aov, dim3(grid), dim3(kBlock), 0, st, sc, fp, sl.hit, c->policy.brdf ? c->mat_ggx.as<float4>() : c->scene.mat_albedo, c->aov.as<float>()); }
+	if (pipelined) { HIP_TRY(c, hipEventRecord(sl.aov_done, st)); c->aov_prev = sl.aov_done; }
+	return MIRT_OK;
+}
+
 // One batch = up to batch_limit() consecutive Accumulate() calls traced together (path id = (slot << pix_bits) | pixel).
 // Consecutive accumulation indices land in buckets (acc % buckets, Renderer.hpp:82), and the ORDER of the adds into a
 // bucket word is part of the result.  Each path of a batch keeps its radiance in its own word of the batch's contribution buffer
@@ -532,6 +565,7 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			                        sl.shadow_buf, sink, shadow_pending ? bc.shadow_queue(bounce - 1) : bc.empty_queue(), bc.shadow_work(shadow_pending ? bounce - 1 : 0),
 			                        bc.fat_closest(bounce, fat_lists), bc.fat_shadow(bounce, fat_lists), bc.listed_pixels(), ctr };
 			  launch_trace(c, st, sc, fp, total, count, lists ? kPrimaryList : bounce == 0 ? kPrimaryAll : kPrimaryNone, tl); }
+			if (bounce == 0 && c->aov_on) { const int r = launch_first_hit_aov(c, sl, st, sc, fp); if (r) return r; }
 			{ Bracket t(c, MIRT_K_SHADE, st);
 			  // policy.brdf = 1 (#define BRDF 1): Closure<GGX> with this bounce's gloss decay, passed by value
 			  const float decay = bounce < c->gloss_decay.size() ? c->gloss_decay[bounce] : 0.0f;
@@ -815,12 +849,13 @@ int mirt_destroy(mirt_ctx* c) {
 		sl.arena.release(); sl.counts.release(); sl.contrib.release(); sl.fat.release(); sl.cand.release();
 		if (sl.batch_done) (void)hipEventDestroy(sl.batch_done);
 		if (sl.merged) (void)hipEventDestroy(sl.merged);
+		if (sl.aov_done) (void)hipEventDestroy(sl.aov_done);
 		if (sl.stream) (void)hipStreamDestroy(sl.stream);
 	}
 	c->slots.clear();
 	for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
 	DeviceBuffer* bufs[] = { &c->recs, &c->recs_wide, &c->spheres, &c->prim_mat, &c->light_sphere, &c->light_emit, &c->mat_albedo, &c->mat_emission,
-	                         &c->mat_ggx, &c->hdri, &c->accumulator, &c->framebuffer, &c->counters, &c->gloss_decay_dev };
+	                         &c->mat_ggx, &c->hdri, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev };
 	for (DeviceBuffer* b : bufs) b->release();
 	if (c->frame_host) (void)hipHostFree(c->frame_host);
 	if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -895,6 +930,7 @@ int mirt_set_stream_order(mirt_ctx* c, uint32_t exact) {
 	if (!c) return MIRT_ERR_ARG;
 	if (exact > 1) return fail(c, MIRT_ERR_ARG, "stream order %u is neither 0 (any order, FMA form for every ray) nor 1 (the reference's slots and scalar tail)", exact);
 	if (exact == c->stream_order) return MIRT_OK;
+	if (exact && c->aov_on) return fail(c, MIRT_ERR_STATE, "exact stream order keeps no hit records (k_tile_stream runs a tile's whole bounce loop in one launch), so it cannot feed the first-hit AOVs: call mirt_set_aov(ctx, 0) first");
 	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render in the mode they were issued under
 	c->stream_order = exact;
 	return MIRT_OK;
@@ -1022,6 +1058,91 @@ int mirt_load_accumulator(mirt_ctx* c, const float* src, int src_is_device, uint
 	if (n && src != c->accumulator.ptr)                                                // src == the slab itself (filled in place by mirt_group_gather): only `accumulations` changes
 		HIP_TRY(c, hipMemcpy(c->accumulator.ptr, src, n * sizeof(float), src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
 	c->accumulations = accumulations;
+	return MIRT_OK;
+}
+
+// ---- first-hit AOVs ----------------------------------------------------------------------------
+int mirt_set_aov(mirt_ctx* c, uint32_t on) {
+	if (!c) return MIRT_ERR_ARG;
+	if (on > 1) return fail(c, MIRT_ERR_ARG, "aov %u is neither 0 (off) nor 1 (sum depth, normal and albedo of every camera ray)", on);
+	if (on == c->aov_on) return MIRT_OK;
+	if (on) {
+		if (c->stream_order) return fail(c, MIRT_ERR_STATE, "first-hit AOVs read the hit records of the wavefront pipeline; exact stream order (k_tile_stream) keeps none: call mirt_set_stream_order(ctx, 0) first");
+		if (c->accumulations + c->deferred) return fail(c, MIRT_ERR_STATE, "AOVs can be turned on only before the first accumulation (%u issued): the sums would cover fewer samples than the frame; mirt_reset first", c->accumulations + c->deferred);
+		HIP_TRY(c, hipSetDevice(c->device));
+		HIP_TRY(c, sync_all(c));
+		c->aov_on = 1;
+		int r = alloc_aov(c);
+		if (r == MIRT_OK && hipStreamSynchronize(c->stream) != hipSuccess) r = fail(c, MIRT_ERR_HIP, "zeroing the AOV slab failed");
+		if (r) { c->aov_on = 0; c->aov.release(); }
+		return r;
+	}
+	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations were issued with AOVs on
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, sync_all(c));
+	c->aov_on = 0;
+	c->aov.release();
+	return MIRT_OK;
+}
+int mirt_get_aov(const mirt_ctx* c, uint32_t* on) { if (!c || !on) return MIRT_ERR_ARG; *on = c->aov_on; return MIRT_OK; }
+int mirt_aov_floats(const mirt_ctx* c, size_t* n) { if (!c || !n) return MIRT_ERR_ARG; *n = aov_floats(c); return MIRT_OK; }
+int mirt_read_aov(mirt_ctx* c, float* dst) {
+	if (!c || !dst) return MIRT_ERR_ARG;
+	if (!c->aov_on) return fail(c, MIRT_ERR_STATE, "AOVs are off (mirt_set_aov)");
+	{ const int fr = flush_deferred(c); if (fr) return fr; }
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, sync_all(c));
+	if (aov_floats(c)) HIP_TRY(c, hipMemcpy(dst, c->aov.ptr, aov_floats(c) * sizeof(float), hipMemcpyDeviceToHost));
+	return MIRT_OK;
+}
+int mirt_aov_device(mirt_ctx* c, void** ptr, size_t* bytes) {
+	if (!c || !ptr || !bytes) return MIRT_ERR_ARG;
+	if (!c->aov_on) return fail(c, MIRT_ERR_STATE, "AOVs are off (mirt_set_aov)");
+	{ const int fr = flush_deferred(c); if (fr) return fr; }
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, sync_all(c));
+	*ptr = c->aov.ptr; *bytes = aov_floats(c) * sizeof(float);
+	return MIRT_OK;
+}
+int mirt_load_aov(mirt_ctx* c, const float* src, int src_is_device) {
+	if (!c || !src) return MIRT_ERR_ARG;
+	if (!c->aov_on) return fail(c, MIRT_ERR_STATE, "AOVs are off (mirt_set_aov)");
+	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // (their sums are overwritten below; their accumulator adds are not)
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, sync_all(c));
+	if (aov_floats(c) && src != c->aov.ptr)                                         // src == the slab itself (filled in place by mirt_group_gather)
+		HIP_TRY(c, hipMemcpy(c->aov.ptr, src, aov_floats(c) * sizeof(float), src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+	return MIRT_OK;
+}
+int mirt_render_aov(mirt_ctx* c, int which, float* out) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!c->aov_on) return fail(c, MIRT_ERR_STATE, "AOVs are off (mirt_set_aov)");
+	if (which != MIRT_AOV_DEPTH && which != MIRT_AOV_NORMAL && which != MIRT_AOV_ALBEDO) return fail(c, MIRT_ERR_ARG, "no AOV %d (MIRT_AOV_DEPTH, _NORMAL, _ALBEDO)", which);
+	if (!out) return fail(c, MIRT_ERR_ARG, "out is NULL");
+	if (c->accumulations + c->deferred == 0) return MIRT_NOT_READY;
+	{ const int fr = flush_deferred(c); if (fr) return fr; }
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, sync_all(c));
+	const uint32_t n_pix = c->n_tiles * kTileSize, ch = which == MIRT_AOV_DEPTH ? 1u : 3u;
+	if (n_pix == 0) return MIRT_OK;
+	const size_t image_floats = static_cast<size_t>(c->width) * c->height * ch;
+	ScopedBuffer image;
+	HIP_TRY(c, image.ensure(image_floats * sizeof(float)));
+	{ Bracket t(c, MIRT_K_RESOLVE);
+	  hipLaunchKernelGGL(k_resolve_aov, dim3(grid_for(c, n_pix)), dim3(kBlock), 0, c->stream, c->aov.as<float>(), image.as<float>(), n_pix, c->first_tile,
+	                     c->run_tiles ? c->run_tiles : 1u, c->stride_tiles, c->h_tiles, c->width, which, static_cast<float>(c->accumulations)); }
+	HIP_TRY(c, hipGetLastError());
+	std::vector<float> host(image_floats);                                           // pixels of other contexts' tiles are never written: copy ours only
+	HIP_TRY(c, hipMemcpyAsync(host.data(), image.ptr, image_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	for (uint32_t local = 0; local < c->n_tiles; local++) {
+		const uint32_t t = c->stride_tiles ? c->first_tile + (local / c->run_tiles) * c->stride_tiles + local % c->run_tiles : c->first_tile + local;
+		const uint32_t x0 = MIRT_TILE_ROOT * (t % c->h_tiles), y0 = MIRT_TILE_ROOT * (t / c->h_tiles);
+		for (uint32_t row = 0; row < MIRT_TILE_ROOT; row++) {
+			const size_t off = (static_cast<size_t>(y0 + row) * c->width + x0) * ch;
+			std::memcpy(out + off, host.data() + off, MIRT_TILE_ROOT * ch * sizeof(float));
+		}
+	}
 	return MIRT_OK;
 }
 

@@ -56,7 +56,7 @@ Rccl g_rccl;
 thread_local std::string g_group_create_error;
 
 // Member r's slab holds its tile rows r, r+n, ... in ascending order: local row j is tile row r + j*n of the image.
-// One thread per float4 of the slab; a tile row is h_tiles * buckets * 3 * 256 floats in both layouts.
+// One thread per float4 of the slab; a tile row is h_tiles * buckets * 3 * 256 floats in both layouts (AOV slabs: h_tiles * 7 * 256).
 __global__ __launch_bounds__(256) void k_uninterleave(float4* __restrict__ full, const float4* __restrict__ slab, size_t quads_per_row, uint32_t rows, uint32_t member, uint32_t n_members) {
 	const size_t total = quads_per_row * rows;
 	for (size_t q = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; q < total; q += static_cast<size_t>(gridDim.x) * 256) {
@@ -75,6 +75,9 @@ struct mirt_group {
 	bool distinct = true;                  // every member on a device of its own (RCCL); otherwise plain device copies
 	std::vector<void*> staging;            // on devices[0]: where member r's slab lands (r >= 1)
 	std::vector<size_t> staging_bytes;
+	std::vector<void*> aov_staging;        // likewise for the members' AOV slabs (mirt_group_set_aov)
+	std::vector<size_t> aov_staging_bytes;
+	uint32_t aov = 0;
 	uint32_t width = 0, height = 0, buckets = 5;
 	bool gathered = false;                 // `full` holds the members' current accumulators
 	double last_gather_ms = 0.0;
@@ -120,6 +123,7 @@ int mirt_group_create(const int* devices, int n, mirt_group** out) {
 		const int rc = mirt_create(devices[0], &g->full);
 		if (rc != MIRT_OK) return bail(rc, std::string("mirt_create(gather context): ") + mirt_last_error(nullptr));
 		g->staging.assign(n, nullptr); g->staging_bytes.assign(n, 0);
+		g->aov_staging.assign(n, nullptr); g->aov_staging_bytes.assign(n, 0);
 		if (g->distinct) {
 			const std::string why = g_rccl.load();
 			if (!why.empty()) return bail(MIRT_ERR_HIP, why);
@@ -135,7 +139,7 @@ int mirt_group_create(const int* devices, int n, mirt_group** out) {
 int mirt_group_destroy(mirt_group* g) {
 	if (!g) return MIRT_ERR_ARG;
 	for (ncclComm_t c : g->comms) if (c) (void)g_rccl.CommDestroy(c);
-	if (!g->staging.empty()) { (void)hipSetDevice(g->devices[0]); for (void* p : g->staging) if (p) (void)hipFree(p); }
+	if (!g->staging.empty()) { (void)hipSetDevice(g->devices[0]); for (void* p : g->staging) if (p) (void)hipFree(p); for (void* p : g->aov_staging) if (p) (void)hipFree(p); }
 	for (mirt_ctx* c : g->members) mirt_destroy(c);
 	if (g->full) mirt_destroy(g->full);
 	delete g;
@@ -174,6 +178,18 @@ int mirt_group_set_stream_order(mirt_group* g, uint32_t exact) {
 	if (!g) return MIRT_ERR_ARG;
 	FOR_MEMBERS(g, "mirt_set_stream_order", mirt_set_stream_order(ctx, exact));
 	if (g->full) FULL_TRY(g, "mirt_set_stream_order", mirt_set_stream_order(g->full, exact));
+	return MIRT_OK;
+}
+int mirt_group_set_aov(mirt_group* g, uint32_t on) {
+	if (!g) return MIRT_ERR_ARG;
+	FOR_MEMBERS(g, "mirt_set_aov", mirt_set_aov(ctx, on));
+	if (g->full) {
+		// the gather context counts the accumulations of the last gather; the members (accepted above) hold none, so neither does it any more
+		if (on) FULL_TRY(g, "mirt_reset", mirt_reset(g->full));
+		FULL_TRY(g, "mirt_set_aov", mirt_set_aov(g->full, on));
+	}
+	g->aov = on;
+	g->gathered = false;
 	return MIRT_OK;
 }
 int mirt_group_set_policy(mirt_group* g, const mirt_policy* p) {
@@ -241,22 +257,31 @@ int mirt_group_gather(mirt_group* g) {
 	if (n == 1 || g->gathered) return MIRT_OK;
 	if (g->width == 0) return gfail(g, MIRT_ERR_STATE, "mirt_group_resize has not been called");
 	const uint32_t h_tiles = g->width / MIRT_TILE_ROOT, v_tiles = g->height / MIRT_TILE_ROOT;
-	std::vector<void*> slab(n, nullptr); std::vector<size_t> bytes(n, 0); std::vector<void*> stream(n, nullptr);
+	// What the exchange moves: the accumulator slabs and, with AOVs on, the AOV slabs — the same tile rows, another row size.
+	struct Part { std::vector<void*> slab; std::vector<size_t> bytes; void* full_ptr; size_t row_bytes; std::vector<void*>* staging; std::vector<size_t>* staging_bytes; };
+	std::vector<Part> parts;
+	parts.push_back(Part{ std::vector<void*>(n, nullptr), std::vector<size_t>(n, 0), nullptr, static_cast<size_t>(h_tiles) * g->buckets * 3 * MIRT_TILE_SIZE * sizeof(float), &g->staging, &g->staging_bytes });
+	if (g->aov) parts.push_back(Part{ std::vector<void*>(n, nullptr), std::vector<size_t>(n, 0), nullptr, static_cast<size_t>(h_tiles) * MIRT_AOV_PLANES * MIRT_TILE_SIZE * sizeof(float), &g->aov_staging, &g->aov_staging_bytes });
+	std::vector<void*> stream(n, nullptr);
 	for (uint32_t i = 0; i < n; i++) {
-		int rc = mirt_accumulator_device(g->members[i], &slab[i], &bytes[i]);               // launches anything deferred and waits for the member's GPU
+		int rc = mirt_accumulator_device(g->members[i], &parts[0].slab[i], &parts[0].bytes[i]);   // launches anything deferred and waits for the member's GPU
+		if (rc >= 0 && g->aov) rc = mirt_aov_device(g->members[i], &parts[1].slab[i], &parts[1].bytes[i]);
 		if (rc >= 0) rc = mirt_get_stream(g->members[i], &stream[i]);
 		if (rc < 0) return gfail(g, rc, "accumulator of member %u: %s", i, mirt_last_error(g->members[i]));
 	}
-	void* full_ptr = nullptr; size_t full_bytes = 0; void* full_stream = nullptr;
-	FULL_TRY(g, "mirt_accumulator_device", mirt_accumulator_device(g->full, &full_ptr, &full_bytes));
+	size_t full_bytes = 0; void* full_stream = nullptr;
+	FULL_TRY(g, "mirt_accumulator_device", mirt_accumulator_device(g->full, &parts[0].full_ptr, &full_bytes));
+	if (full_bytes != parts[0].row_bytes * v_tiles) return gfail(g, MIRT_ERR_STATE, "gather context holds %zu bytes, the image needs %zu", full_bytes, parts[0].row_bytes * v_tiles);
+	if (g->aov) {
+		FULL_TRY(g, "mirt_aov_device", mirt_aov_device(g->full, &parts[1].full_ptr, &full_bytes));
+		if (full_bytes != parts[1].row_bytes * v_tiles) return gfail(g, MIRT_ERR_STATE, "gather context holds %zu bytes of AOVs, the image needs %zu", full_bytes, parts[1].row_bytes * v_tiles);
+	}
 	FULL_TRY(g, "mirt_get_stream", mirt_get_stream(g->full, &full_stream));
-	const size_t row_bytes = static_cast<size_t>(h_tiles) * g->buckets * 3 * MIRT_TILE_SIZE * sizeof(float);
-	if (full_bytes != row_bytes * v_tiles) return gfail(g, MIRT_ERR_STATE, "gather context holds %zu bytes, the image needs %zu", full_bytes, row_bytes * v_tiles);
 	GHIP(g, hipSetDevice(g->devices[0]));
-	for (uint32_t i = 1; i < n; i++) if (g->staging_bytes[i] < bytes[i]) {
-		if (g->staging[i]) (void)hipFree(g->staging[i]);
-		g->staging[i] = nullptr; g->staging_bytes[i] = 0;
-		if (bytes[i]) { GHIP(g, hipMalloc(&g->staging[i], bytes[i])); g->staging_bytes[i] = bytes[i]; }
+	for (Part& p : parts) for (uint32_t i = 1; i < n; i++) if ((*p.staging_bytes)[i] < p.bytes[i]) {
+		if ((*p.staging)[i]) (void)hipFree((*p.staging)[i]);
+		(*p.staging)[i] = nullptr; (*p.staging_bytes)[i] = 0;
+		if (p.bytes[i]) { GHIP(g, hipMalloc(&(*p.staging)[i], p.bytes[i])); (*p.staging_bytes)[i] = p.bytes[i]; }
 	}
 	// From here on every failure is recorded in `rc` and the sequence runs to its end: an ncclGroupStart is always matched by its
 	// ncclGroupEnd and both events are destroyed whatever happened in between.
@@ -268,15 +293,15 @@ int mirt_group_gather(mirt_group* g) {
 	hstep(hipEventCreate(&t0), "hipEventCreate"); hstep(hipEventCreate(&t1), "hipEventCreate");
 	if (rc == MIRT_OK) hstep(hipEventRecord(t0, root), "hipEventRecord");
 	if (rc == MIRT_OK && g->distinct) {
-		// ncclGather spelled as its point-to-point form (rccl.h:700,722): the root posts one receive per peer, every peer one send;
-		// each transfer rides the xGMI link between that peer and the root
+		// ncclGather spelled as its point-to-point form (rccl.h:700,722): the root posts one receive per peer and slab, every peer one send
+		// per slab, in the same order on both sides; each transfer rides the xGMI link between that peer and the root
 		if (nstep(g_rccl.GroupStart(), "ncclGroupStart")) {
-			for (uint32_t i = 1; i < n && rc == MIRT_OK; i++) {
-				if (!bytes[i]) continue;
+			for (uint32_t i = 1; i < n && rc == MIRT_OK; i++) for (const Part& p : parts) {
+				if (!p.bytes[i] || rc != MIRT_OK) continue;
 				if (hstep(hipSetDevice(g->devices[0]), "hipSetDevice"))
-					nstep(g_rccl.Recv(g->staging[i], bytes[i] / sizeof(float), ncclFloat, static_cast<int>(i), g->comms[0], root), "ncclRecv");
+					nstep(g_rccl.Recv((*p.staging)[i], p.bytes[i] / sizeof(float), ncclFloat, static_cast<int>(i), g->comms[0], root), "ncclRecv");
 				if (rc == MIRT_OK && hstep(hipSetDevice(g->devices[i]), "hipSetDevice"))
-					nstep(g_rccl.Send(slab[i], bytes[i] / sizeof(float), ncclFloat, 0, g->comms[i], static_cast<hipStream_t>(stream[i])), "ncclSend");
+					nstep(g_rccl.Send(p.slab[i], p.bytes[i] / sizeof(float), ncclFloat, 0, g->comms[i], static_cast<hipStream_t>(stream[i])), "ncclSend");
 			}
 			const ncclResult_t end = g_rccl.GroupEnd();                              // always: an open group would swallow every later RCCL call of this thread
 			nstep(end, "ncclGroupEnd");
@@ -284,16 +309,18 @@ int mirt_group_gather(mirt_group* g) {
 		for (uint32_t i = 1; i < n && rc == MIRT_OK; i++) if (hstep(hipSetDevice(g->devices[i]), "hipSetDevice")) hstep(hipStreamSynchronize(static_cast<hipStream_t>(stream[i])), "hipStreamSynchronize");
 		(void)hipSetDevice(g->devices[0]);
 	} else if (rc == MIRT_OK) {
-		for (uint32_t i = 1; i < n && rc == MIRT_OK; i++) if (bytes[i]) hstep(hipMemcpyAsync(g->staging[i], slab[i], bytes[i], hipMemcpyDeviceToDevice, root), "hipMemcpyAsync");
+		for (const Part& p : parts) for (uint32_t i = 1; i < n && rc == MIRT_OK; i++) if (p.bytes[i]) hstep(hipMemcpyAsync((*p.staging)[i], p.slab[i], p.bytes[i], hipMemcpyDeviceToDevice, root), "hipMemcpyAsync");
 	}
-	const size_t quads_per_row = row_bytes / sizeof(float4);
-	for (uint32_t i = 0; i < n && rc == MIRT_OK; i++) {
-		const uint32_t rows = static_cast<uint32_t>(bytes[i] / row_bytes);
-		if (!rows) continue;
-		const float4* src = static_cast<const float4*>(i == 0 ? slab[0] : g->staging[i]);
-		const size_t total = quads_per_row * rows;
-		const uint32_t grid = static_cast<uint32_t>(std::min<size_t>((total + 255) / 256, 256u * 16u));
-		hipLaunchKernelGGL(k_uninterleave, dim3(grid), dim3(256), 0, root, static_cast<float4*>(full_ptr), src, quads_per_row, rows, i, n);
+	for (const Part& p : parts) {
+		const size_t quads_per_row = p.row_bytes / sizeof(float4);
+		for (uint32_t i = 0; i < n && rc == MIRT_OK; i++) {
+			const uint32_t rows = static_cast<uint32_t>(p.bytes[i] / p.row_bytes);
+			if (!rows) continue;
+			const float4* src = static_cast<const float4*>(i == 0 ? p.slab[0] : (*p.staging)[i]);
+			const size_t total = quads_per_row * rows;
+			const uint32_t grid = static_cast<uint32_t>(std::min<size_t>((total + 255) / 256, 256u * 16u));
+			hipLaunchKernelGGL(k_uninterleave, dim3(grid), dim3(256), 0, root, static_cast<float4*>(p.full_ptr), src, quads_per_row, rows, i, n);
+		}
 	}
 	if (rc == MIRT_OK) hstep(hipGetLastError(), "k_uninterleave");
 	if (rc == MIRT_OK) hstep(hipEventRecord(t1, root), "hipEventRecord");
@@ -304,7 +331,7 @@ int mirt_group_gather(mirt_group* g) {
 	if (rc != MIRT_OK) return rc;
 	uint32_t acc = 0;
 	(void)mirt_get_accumulations(g->members[0], &acc);
-	FULL_TRY(g, "mirt_load_accumulator", mirt_load_accumulator(g->full, static_cast<const float*>(full_ptr), 1, acc));   // in place: only `accumulations` changes
+	FULL_TRY(g, "mirt_load_accumulator", mirt_load_accumulator(g->full, static_cast<const float*>(parts[0].full_ptr), 1, acc));   // in place: only `accumulations` changes
 	g->gathered = true;
 	return MIRT_OK;
 }
@@ -355,6 +382,33 @@ int mirt_group_read_accumulator(mirt_group* g, float* host_dst) {
 	if (rc) return rc;
 	FULL_TRY(g, "mirt_read_accumulator", mirt_read_accumulator(g->full, host_dst));
 	return MIRT_OK;
+}
+int mirt_group_aov_floats(const mirt_group* g, size_t* n) {
+	if (!g || !n) return MIRT_ERR_ARG;
+	*n = g->aov ? static_cast<size_t>(g->width / MIRT_TILE_ROOT) * (g->height / MIRT_TILE_ROOT) * MIRT_AOV_PLANES * MIRT_TILE_SIZE : 0;
+	return MIRT_OK;
+}
+int mirt_group_read_aov(mirt_group* g, float* host_dst) {
+	if (!g || !host_dst) return MIRT_ERR_ARG;
+	if (g->members.size() == 1) { const int rc = mirt_read_aov(g->members[0], host_dst); return rc < 0 ? gfail(g, rc, "%s", mirt_last_error(g->members[0])) : rc; }
+	if (!g->aov) return gfail(g, MIRT_ERR_STATE, "AOVs are off (mirt_group_set_aov)");
+	const int rc = mirt_group_gather(g);
+	if (rc) return rc;
+	FULL_TRY(g, "mirt_read_aov", mirt_read_aov(g->full, host_dst));
+	return MIRT_OK;
+}
+int mirt_group_render_aov(mirt_group* g, int which, float* out) {
+	if (!g) return MIRT_ERR_ARG;
+	if (g->members.size() == 1) { const int rc = mirt_render_aov(g->members[0], which, out); return rc < 0 ? gfail(g, rc, "%s", mirt_last_error(g->members[0])) : rc; }
+	if (!g->aov) return gfail(g, MIRT_ERR_STATE, "AOVs are off (mirt_group_set_aov)");
+	if (!out) return gfail(g, MIRT_ERR_ARG, "out is NULL");
+	uint32_t acc = 0;
+	(void)mirt_get_accumulations(g->members[0], &acc);
+	if (acc == 0) return MIRT_NOT_READY;                                                   // nothing is gathered for it
+	const int rc = mirt_group_gather(g);
+	if (rc) return rc;
+	const int rr = mirt_render_aov(g->full, which, out);
+	return rr < 0 ? gfail(g, rr, "mirt_render_aov on the gather context: %s", mirt_last_error(g->full)) : rr;
 }
 int mirt_group_render(mirt_group* g, float* rgba_host) {
 	if (!g || !rgba_host) return MIRT_ERR_ARG;

@@ -5,9 +5,11 @@
 // environment map the way the constructor does (stbi_loadf(..., 4), Application.cpp:225-231); --ambient sets sky.ambient_color, which scales it.
 //
 //   mirt_headless --scene default9|furnace|bvh_test|brdf_test|synthetic:N [--size WxH] [--spp N | --frames N] [--bounces B] [--buckets K] [--brute] [--devices 0,1,..]
-//                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm]
+//                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm] [--aov PREFIX]
 // --brdf 1 renders every hit with the GGX closure (#define BRDF 1, Renderer.hpp:70), --gloss-decay gives its per-bounce table (:212).
 // --exact-stream-order replays the reference's stream slots and its scalar intersection tail (BVH.hpp:270-286; brute force, mirt_set_stream_order).
+// --aov PREFIX sums the first-hit AOVs beside the frame (mirt_set_aov) and writes PREFIX.depth.pfm (one channel, `Pf`), PREFIX.normal.pfm and
+// PREFIX.albedo.pfm (`PF`) after the last frame.
 // --devices: the GPUs the one Renderer object uses (tile rows split over them inside the library, one RCCL gather per frame read).
 // --frames N is the UI loop itself (Application.cpp:373-380): N frames of { Accumulate(); Render(); }; the report lists the frames on
 // which Render() produced output (every `buckets`-th, Renderer.hpp:437) and a hash of the last frame shown.
@@ -135,6 +137,15 @@ static uint64_t fnv1a(const std::vector<float>& v) {
 	return hsh;
 }
 
+// An AOV image as mirt_render_aov leaves it: `channels` (1: `Pf`, 3: `PF`) floats per pixel, row 0 = y 0 = the bottom row PFM starts with.
+static bool write_pfm_planes(const std::string& path, const std::vector<float>& img, uint32_t w, uint32_t h, uint32_t channels) {
+	FILE* f = std::fopen(path.c_str(), "wb");
+	if (!f) return false;
+	std::fprintf(f, "%s\n%u %u\n-1.0\n", channels == 1 ? "Pf" : "PF", w, h);
+	const bool ok = img.size() == static_cast<size_t>(w) * h * channels && std::fwrite(img.data(), sizeof(float), img.size(), f) == img.size();
+	return (std::fclose(f) == 0) && ok;
+}
+
 static bool write_pfm(const std::string& path, const std::vector<float>& rgba, uint32_t w, uint32_t h) {
 	FILE* f = std::fopen(path.c_str(), "wb");
 	if (!f) return false;
@@ -149,7 +160,7 @@ static bool write_pfm(const std::string& path, const std::vector<float>& rgba, u
 }
 
 int main(int argc, char** argv) {
-	std::string scene_name = "default9", out, hdri;
+	std::string scene_name = "default9", out, hdri, aov_prefix;
 	uint32_t w = 512, h = 512, spp = 10, n = 0;
 	RendererPolicy policy;
 	float ambient = 0.0f;
@@ -182,6 +193,7 @@ int main(int argc, char** argv) {
 		else if (a == "--gloss-decay") { for (const char* p = next(); *p;) { gloss_decay.push_back(static_cast<float>(std::atof(p))); while (*p && *p != ',') p++; if (*p == ',') p++; } }
 		else if (a == "--exact-stream-order") exact_stream_order = true;
 		else if (a == "--out") out = next();
+		else if (a == "--aov") aov_prefix = next();
 		else if (a == "--devices") { devices.clear(); for (const char* p = next(); *p;) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p == ',') p++; } if (devices.empty()) return 2; }
 		else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
 	}
@@ -203,6 +215,7 @@ int main(int argc, char** argv) {
 		Renderer renderer{ scene, policy, devices };
 		renderer.SetGlossDecay(gloss_decay);
 		renderer.SetStreamOrder(exact_stream_order);
+		if (!aov_prefix.empty()) renderer.SetAOV(true);
 		// pad the viewport to the tile requirement like UIRender does (Application.cpp:365-372)
 		const uint32_t t = static_cast<uint32_t>(Renderer::RequiredTiling());
 		w = (w + t - 1) & ~(t - 1); h = (h + t - 1) & ~(t - 1);
@@ -235,6 +248,13 @@ int main(int argc, char** argv) {
 			const bool as_hdr = out.size() >= 4 && out.compare(out.size() - 4, 4, ".hdr") == 0;
 			const bool ok = as_hdr ? mirt_hdr::write_flipped(out, renderer.GetFrame().data(), w, h) : write_pfm(out, renderer.GetFrame(), w, h);
 			if (!ok) { std::fprintf(stderr, "cannot write %s\n", out.c_str()); return 1; }
+		}
+		if (!aov_prefix.empty()) {
+			const struct { int which; const char* name; uint32_t channels; } outputs[3] = { { MIRT_AOV_DEPTH, "depth", 1 }, { MIRT_AOV_NORMAL, "normal", 3 }, { MIRT_AOV_ALBEDO, "albedo", 3 } };
+			for (const auto& o : outputs) {
+				const std::string path = aov_prefix + "." + o.name + ".pfm";
+				if (!write_pfm_planes(path, renderer.RenderAOV(o.which), w, h, o.channels)) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+			}
 		}
 	} catch (const std::exception& e) {
 		std::fprintf(stderr, "mirt_headless: %s\n", e.what());

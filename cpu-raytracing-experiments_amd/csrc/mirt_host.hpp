@@ -191,6 +191,23 @@ public:
 		check(mirt_group_read_accumulator(group_, acc.data()), "mirt_group_read_accumulator");
 		return acc;
 	}
+	// First-hit AOVs (mirt.h): the reference's compiled-out FIRST BOUNCE OUTPUTS (Renderer.hpp:216-231) summed beside the accumulator.
+	// SetAOV(true) only before the first Accumulate(); RenderAOV returns width * height * (1 for MIRT_AOV_DEPTH, else 3) floats,
+	// row 0 = y 0, empty before the first accumulation.
+	void SetAOV(bool on) { check(mirt_group_set_aov(group_, on ? 1u : 0u), "mirt_group_set_aov"); }
+	std::vector<float> aov() {                                             // the whole image's [tile][plane 0..6][256] sums
+		size_t n = 0; mirt_group_aov_floats(group_, &n);
+		std::vector<float> sums(n);
+		check(mirt_group_read_aov(group_, sums.data()), "mirt_group_read_aov");
+		return sums;
+	}
+	std::vector<float> RenderAOV(int which) {
+		std::vector<float> img(static_cast<size_t>(width) * height * (which == MIRT_AOV_DEPTH ? 1 : 3), 0.0f);
+		const int rc = mirt_group_render_aov(group_, which, img.data());
+		check(rc, "mirt_group_render_aov");
+		if (rc != MIRT_OK) img.clear();
+		return img;
+	}
 	double gather_ms() const { double ms = 0; mirt_group_last_gather_ms(group_, &ms); return ms; }
 	mirt_group* handle() { return group_; }
 

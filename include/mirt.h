@@ -207,6 +207,40 @@ int mirt_load_accumulator(mirt_ctx* ctx, const float* src, int src_is_device, ui
  * when accumulations % buckets != 0.  Only the context's own tiles are written. */
 int mirt_render(mirt_ctx* ctx, float* rgba_host);
 
+/* ---- first-hit AOVs: depth, normal and albedo of the camera rays, summed beside the accumulator ---------------------
+ * The reference's `FIRST BOUNCE OUTPUTS` (Renderer.hpp:216-231, written down but compiled out): on bounce 0 every pixel adds its hit
+ * distance (1e4 on a miss), its world-space shading normal (flipped to face the ray, as the closest-hit shader leaves it) and the
+ * colour its closure is set up with (Renderer.hpp:208-210: material.albedo with policy.brdf = 0, material.F0 with brdf = 1; nothing
+ * on a miss) into extra planes.  Slab: [local tile][plane 0..6][256] f32 — plane 0 depth, 1-3 normal, 4-6 albedo; the shape of
+ * AccumulationTile with seven planes instead of buckets x 3.  Not bucketed: ONE f32 sum over the accumulations 1, 2, 3, ... since the
+ * last reset, added in that order, so the words do not depend on policy.max_batch / streams / trace_primary_rays / use_bvh /
+ * reference_tree / gpu_build, on mirt_accumulate vs mirt_accumulate_async, or on the tile partition.  The accumulator, the frame and
+ * the counters are the same with AOVs on or off; off (the default) costs nothing.
+ * Not available in exact stream order: that mode runs a tile's whole bounce loop in one launch and keeps no hit records to read, so
+ * mirt_set_aov(ctx, 1) with stream order 1, and mirt_set_stream_order(ctx, 1) with AOVs on, return MIRT_ERR_STATE. */
+enum { MIRT_AOV_DEPTH = 0, MIRT_AOV_NORMAL = 1, MIRT_AOV_ALBEDO = 2 };
+#define MIRT_AOV_PLANES 7u
+/* on = 1: allocates and zeroes the slab; accepted only while accumulations == 0 (the sums would cover fewer samples than the frame:
+ * MIRT_ERR_STATE; mirt_reset first).  on = 0: any time; deferred mirt_accumulate_async calls are launched first, under the old
+ * setting, then the slab is freed.  Other values: MIRT_ERR_ARG.  mirt_reset zeroes the slab; mirt_resize, mirt_set_tile_range,
+ * mirt_set_tile_rows (and a mirt_set_policy that changes `buckets`) reallocate and zero it with the accumulator. */
+int mirt_set_aov(mirt_ctx* ctx, uint32_t on);
+int mirt_get_aov(const mirt_ctx* ctx, uint32_t* on);
+int mirt_aov_floats(const mirt_ctx* ctx, size_t* n_floats);       /* local tiles x 7 x 256; 0 while AOVs are off */
+/* The raw sums.  Launches anything deferred and waits for the GPU first.  MIRT_ERR_STATE while AOVs are off (as the three below). */
+int mirt_read_aov(mirt_ctx* ctx, float* host_dst);
+/* Device address of the slab, as mirt_accumulator_device (mirt_group_gather uses it). */
+int mirt_aov_device(mirt_ctx* ctx, void** device_ptr, size_t* bytes);
+/* Companion of mirt_load_accumulator (checkpoint/resume, post-gather resolve): overwrites the slab, src on host or device. */
+int mirt_load_aov(mirt_ctx* ctx, const float* src, int src_is_device);
+/* One AOV resolved row-major over width x height (row 0 = y 0); only the context's own tiles are written.
+ *   MIRT_AOV_DEPTH   1 float per pixel    sum / (float)accumulations
+ *   MIRT_AOV_NORMAL  3 floats per pixel   normalize(sum) — v * (1 / sqrt(dot(v, v))), dot = (x*x + y*y) + z*z — or (0,0,0) where dot is 0
+ *   MIRT_AOV_ALBEDO  3 floats per pixel   sum / (float)accumulations
+ * IEEE division and square root.  Unlike mirt_render it needs no multiple of `buckets`; returns MIRT_NOT_READY and leaves `out`
+ * untouched while accumulations == 0. */
+int mirt_render_aov(mirt_ctx* ctx, int which, float* out);
+
 int mirt_get_counters(mirt_ctx* ctx, mirt_counters* out);
 int mirt_get_kernel_times(mirt_ctx* ctx, mirt_kernel_times* out, int reset);
 /* HIP stream the context launches on (hipStream_t), for callers that time with their own events. */
@@ -252,6 +286,14 @@ int mirt_group_last_gather_ms(const mirt_group* group, double* ms);             
 int mirt_group_accumulator_floats(const mirt_group* group, size_t* n_floats);    /* of the whole image */
 int mirt_group_read_accumulator(mirt_group* group, float* host_dst);             /* whole image, [tile][bucket][r,g,b][256] in LaunchIndex order */
 int mirt_group_render(mirt_group* group, float* rgba_host);                      /* Renderer::Render of the whole frame; MIRT_NOT_READY as mirt_render */
+/* First-hit AOVs of the whole image.  mirt_group_gather moves the members' AOV slabs in the same exchange as their accumulator slabs
+ * and un-interleaves them with the same tile-row mapping; the sums equal the single-context ones bit for bit.  Both branches of the
+ * exchange carry them — device copies when one device is named several times, RCCL between distinct devices — but only the first
+ * can be run on a one-GPU box: the RCCL branch for the AOV slabs is built and has not been run. */
+int mirt_group_set_aov(mirt_group* group, uint32_t on);                          /* mirt_set_aov on every member (and the gather context) */
+int mirt_group_aov_floats(const mirt_group* group, size_t* n_floats);            /* of the whole image: tiles x 7 x 256; 0 while off */
+int mirt_group_read_aov(mirt_group* group, float* host_dst);                     /* whole image, [tile][plane 0..6][256] in LaunchIndex order */
+int mirt_group_render_aov(mirt_group* group, int which, float* out);             /* mirt_render_aov of the whole frame */
 /* Diagnostic: one-device RCCL communicator on `device`, n_floats sent to itself through a grouped ncclSend / ncclRecv. */
 int mirt_group_rccl_selftest(int device, size_t n_floats);
 
