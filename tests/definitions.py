@@ -1,0 +1,311 @@
+"""Float64 definitions of the operations on the path, written from their textbook statements.
+
+A third statement beside oracle/oracle.cpp (CPU) and csrc/kernels.hpp (GPU): plain numpy, float64 throughout, no fast-math
+polynomials, no operation ordering, no fused multiply-adds.  tests/test_definitions_cpu.py holds the oracle to it,
+tests/test_definitions_gpu.py the kernels.  Where the reference deliberately departs from the textbook (the Q rows,
+plus the few listed here) the departure is a NAMED argument or a named expectation in the tests, never folded silently into a formula:
+
+  D1  ray-sphere roots are those of  t^2 - 2 b t + (|oc|^2 - r^2) = 0  with the leading coefficient taken as 1 whatever |D| is
+      (BVH.hpp:251-286 never divides by |D|^2; exact for unit directions, a "fat" sphere for stretched ones).
+  D2  the sky image is addressed with (width - 1, height - 1) as scale and truncation (Application.cpp:230-231, Primitives.hpp:35-46),
+      so the last column / row is reached only at u = 1 / v = 1 exactly.
+  D3  GGX D takes max(alpha^2, 1e-5) while the masking term takes alpha^2 itself (Sampling.hpp:295).
+  D4  the cone pdf divides by max(1 - cos(theta_max), 1e-6) (Sampling.hpp:192-194).
+
+Every function takes and returns float64 arrays; `u` is the binary32 unit roundoff the error models are written in."""
+import numpy as np
+
+u = 2.0 ** -24                                     # binary32 unit roundoff (round to nearest)
+CHI2_255_P1E6 = 377.08                             # upper 1e-6 quantile of chi-square with 255 degrees of freedom (16 x 16 cells - 1)
+
+
+# ---- A. ray / sphere ------------------------------------------------------------------------------------------------------------
+def sphere_roots(P, D, centre, radius_sq):
+    """Quadratic of |P + t D - c|^2 = r^2 under D1, for rays (n, 3) against spheres (m, 3): -> b, oc2, disc as (n, m) arrays.
+    Roots are b -+ sqrt(disc), disc = b^2 - (|oc|^2 - r^2)  (any textbook on ray tracing; e.g. Glassner 1989, ch. 2)."""
+    oc = centre[None, :, :] - P[:, None, :]
+    b = np.einsum("nmk,nk->nm", oc, D)
+    oc2 = np.einsum("nmk,nmk->nm", oc, oc)
+    return b, oc2, b * b - oc2 + radius_sq[None, :]
+
+
+def sphere_error_model(P, D, centre, radius_sq, b, oc2, disc):
+    """Bound of the binary32 rounding error of b, disc and of a root b -+ sqrt(disc) as the path evaluates them, from the float64
+    magnitudes.  Derivation, e = u(1 + O(u)):
+      oc_k = fl(c_k - p_k): relative error e each.
+      b = sum of three products d_k oc_k, accumulated (fused or not): at most 3 roundings on top of oc's ->  E_b = 4 e sum|d_k oc_k|.
+      disc = r^2 - sum oc_k^2 + b^2 in four accumulation steps, every partial sum bounded by M = r^2 + |oc|^2 + b^2: 4 e M for the
+        steps, 2 e |oc|^2 for oc's own rounding, 2|b| E_b + E_b^2 for b's ->  E_disc = 6 e M + 2|b| E_b + E_b^2.
+      s = sqrt(disc): |sqrt(x + h) - sqrt(x)| = |h| / (sqrt(x + h) + sqrt(x)) <= min(sqrt|h|, |h| / sqrt(x)), plus e s for the sqrt.
+      t = b -+ s: E_t = E_b + E_s + e |t|.
+    -> E_b, E_disc, E_root (n, m); E_root is for either root up to the e|t| term, which the caller adds."""
+    oc = np.abs(centre[None, :, :] - P[:, None, :])
+    sabs = np.einsum("nmk,nk->nm", oc, np.abs(D))
+    E_b = 4 * u * sabs
+    M = radius_sq[None, :] + oc2 + b * b
+    E_disc = 6 * u * M + 2 * np.abs(b) * E_b + E_b * E_b
+    s = np.sqrt(np.maximum(disc, 0.0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        E_s = np.minimum(np.sqrt(E_disc), np.where(s > 0, E_disc / s, np.inf)) + u * s
+    return E_b, E_disc, E_b + E_s
+
+
+def closest_hit(P, D, centre, radius_sq, chunk=2048):
+    """Closest hit in words (BVH.hpp:261-266, 279-285 as shipped with USEBVH false): a sphere is hit when its discriminant is not
+    negative; its distance is the smaller root, or the larger one when the smaller is negative (the origin is inside); a distance is
+    accepted when it is not negative and strictly below the best so far, spheres taken in array order - so the answer is the
+    smallest non-negative root over all spheres, the lowest array index among equals, +inf / -1 when there is none.
+
+    -> dict of per-ray arrays: t, prim; E (error bound of t); unsure (bool: some sphere whose own hit / miss / root choice lies within
+    its error bound could change the answer); rivals (list of index arrays: spheres whose root is within the summed error bounds of
+    the best one, bit-identical copies of the best sphere left out since equal inputs give equal roots and the index decides)."""
+    n = len(P)
+    out = dict(t=np.full(n, np.inf), prim=np.full(n, -1, dtype=np.int64), E=np.zeros(n), unsure=np.zeros(n, dtype=bool), rivals=[None] * n)
+    key = np.concatenate([centre, radius_sq[:, None]], axis=1)
+    for lo in range(0, n, chunk):
+        p, d = P[lo:lo + chunk], D[lo:lo + chunk]
+        b, oc2, disc = sphere_roots(p, d, centre, radius_sq)
+        E_b, E_disc, E_root = sphere_error_model(p, d, centre, radius_sq, b, oc2, disc)
+        s = np.sqrt(np.maximum(disc, 0.0))
+        near, far = b - s, b + s
+        t = np.where(near >= 0.0, near, far)
+        hit = (disc >= 0.0) & (t >= 0.0)
+        E = E_root + u * np.abs(t)
+        t_hit = np.where(hit, t, np.inf)
+        best = np.argmin(t_hit, axis=1)
+        rows = np.arange(len(p))
+        t_best, E_best = t_hit[rows, best], np.where(np.isfinite(t_hit[rows, best]), E[rows, best], 0.0)
+        # a sphere's own status is in doubt when disc, or either root, is within its error of zero - and it matters only if the
+        # distance it could then report is not certainly beyond the best one
+        doubt = (np.abs(disc) <= E_disc) | (np.abs(near) <= E) | (np.abs(far) <= E)
+        could_report = np.maximum(np.where(near + E >= 0.0, near, far) - E, 0.0)
+        reachable = (far + E >= 0.0) & (disc + E_disc >= 0.0)
+        matters = doubt & reachable & (could_report <= (t_best + E_best)[:, None])
+        out["unsure"][lo:lo + chunk] = matters.any(axis=1)
+        close = hit & (t_hit - E <= (t_best + E_best)[:, None])
+        close[rows, best] = False
+        same = (key[None, :, :] == key[best][:, None, :]).all(axis=2)
+        close &= ~same
+        for r in np.flatnonzero(close.any(axis=1)):
+            out["rivals"][lo + r] = np.flatnonzero(close[r])
+        out["t"][lo:lo + chunk], out["E"][lo:lo + chunk] = t_best, E_best
+        out["prim"][lo:lo + chunk] = np.where(np.isfinite(t_best), best, -1)
+    return out
+
+
+def root_of(P, D, centre, radius_sq, prim):
+    """The accepted root and its error bound for ray i against sphere prim[i] alone (prim >= 0)."""
+    oc = centre[prim] - P
+    b = np.einsum("nk,nk->n", oc, D)
+    oc2 = np.einsum("nk,nk->n", oc, oc)
+    disc = b * b - oc2 + radius_sq[prim]
+    sabs = np.einsum("nk,nk->n", np.abs(oc), np.abs(D))
+    E_b = 4 * u * sabs
+    E_disc = 6 * u * (radius_sq[prim] + oc2 + b * b) + 2 * np.abs(b) * E_b + E_b * E_b
+    s = np.sqrt(np.maximum(disc, 0.0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        E_s = np.minimum(np.sqrt(E_disc), np.where(s > 0, E_disc / s, np.inf)) + u * s
+    near, far = b - s, b + s
+    E = E_b + E_s
+    return near, far, E + u * np.maximum(np.abs(near), np.abs(far))
+
+
+def occluded(P, D, tmax, centre, radius_sq, chunk=2048):
+    """Any-hit in words (BVH.hpp:294-300): occluded when some sphere's accepted distance (as in closest_hit) lies in [0, tmax).
+    -> occ (bool), unsure (bool: no sphere occludes for certain and at least one might, within its error bound)."""
+    n = len(P)
+    occ, unsure = np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
+    for lo in range(0, n, chunk):
+        p, d, tm = P[lo:lo + chunk], D[lo:lo + chunk], tmax[lo:lo + chunk, None]
+        b, oc2, disc = sphere_roots(p, d, centre, radius_sq)
+        E_b, E_disc, E_root = sphere_error_model(p, d, centre, radius_sq, b, oc2, disc)
+        s = np.sqrt(np.maximum(disc, 0.0))
+        near, far = b - s, b + s
+        t = np.where(near >= 0.0, near, far)
+        E = E_root + u * np.abs(t)
+        yes = (disc >= 0.0) & (t >= 0.0) & (t < tm)
+        doubt = (np.abs(disc) <= E_disc) | (np.abs(near) <= E) | (np.abs(far) <= E) | (np.abs(t - tm) <= E + u * tm)
+        # certain: the status cannot flip.  possible: it might occlude if an error went the right way
+        possible = (disc + E_disc >= 0.0) & (far + E >= 0.0) & (np.where(near + E >= 0, near, far) - E < tm)
+        certain = yes & ~doubt
+        occ[lo:lo + chunk] = yes.any(axis=1)
+        unsure[lo:lo + chunk] = ~certain.any(axis=1) & (doubt & possible).any(axis=1)
+    return occ, unsure
+
+
+# ---- B. frames and sampling -----------------------------------------------------------------------------------------------------
+def rotation_of_quaternion(q):
+    """3x3 of v -> q v q* for q = (x, y, z, w) (n, 4), NOT normalised: the matrix is |q|^2 times a rotation (Shoemake 1985).
+    -> (n, 3, 3)."""
+    x, y, z, w = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    R = np.empty((len(q), 3, 3))
+    R[:, 0, 0] = w * w + x * x - y * y - z * z; R[:, 0, 1] = 2 * (x * y - w * z); R[:, 0, 2] = 2 * (x * z + w * y)
+    R[:, 1, 0] = 2 * (x * y + w * z); R[:, 1, 1] = w * w - x * x + y * y - z * z; R[:, 1, 2] = 2 * (y * z - w * x)
+    R[:, 2, 0] = 2 * (x * z - w * y); R[:, 2, 1] = 2 * (y * z + w * x); R[:, 2, 2] = w * w - x * x - y * y + z * z
+    return R
+
+
+def frame_defect_bound(N):
+    """The shortest-arc quaternion from +z to N is q = (-N.y, N.x, 0, 1 + N.z) / sqrt(2 (1 + N.z)); for an input that is not exactly of
+    unit length, |q|^2 - 1 = (|N|^2 - 1) / (2 (1 + N.z)) exactly.  The matrix of q then has R^T R = |q|^4 I, so its defect from
+    orthonormality is | |q|^4 - 1 |, and R e_z - N = (0, 0, (1 - |N|^2) / (1 + N.z)).  -> (n,) bound on both, rounding left to the caller."""
+    n2 = (N * N).sum(axis=1)
+    k = np.abs(n2 - 1.0) / (2.0 * (1.0 + N[:, 2]))
+    return 2.0 * k + k * k
+
+
+def cone_pdf(sin2_theta_max, floor=1e-6):
+    """Uniform sampling of the cone of directions that a sphere subtends: 1 / (2 pi (1 - cos theta_max)) (Shirley & Wang 1996;
+    PBRT 3rd ed. 14.2.2).  `floor` is D4."""
+    one_minus_cos = sin2_theta_max / (1.0 + np.sqrt(1.0 - sin2_theta_max))          # cancellation-free form of 1 - cos
+    return 1.0 / (2.0 * np.pi * np.maximum(one_minus_cos, floor)), one_minus_cos
+
+
+def cosine_upper_share(normal_y):
+    """Share of a cosine-weighted hemisphere about a normal that lies in the half space y > 0: (1 + n.y) / 2 (the view factor of a
+    small surface patch to a half plane, Nusselt's analogue; checked by quadrature in the tests)."""
+    return 0.5 * (1.0 + normal_y)
+
+
+def cosine_upper_share_quadrature(normal, n_r=400, n_phi=800):
+    """The same by midpoint quadrature: cosine-weighted directions about `normal` are a uniform disk (Malley's method), so the share is
+    the part of the unit disk whose lifted direction has y > 0."""
+    n = normal / np.linalg.norm(normal)
+    a = np.array([1.0, 0.0, 0.0]) if abs(n[0]) < 0.9 else np.array([0.0, 1.0, 0.0])
+    t = np.cross(n, a); t /= np.linalg.norm(t)
+    b = np.cross(n, t)
+    r2 = (np.arange(n_r) + 0.5) / n_r                                               # equal-area rings: r^2 uniform
+    phi = 2 * np.pi * (np.arange(n_phi) + 0.5) / n_phi
+    r = np.sqrt(r2)[:, None]
+    y = r * np.cos(phi)[None, :] * t[1] + r * np.sin(phi)[None, :] * b[1] + np.sqrt(1.0 - r2)[:, None] * n[1]
+    return float((y > 0).mean())
+
+
+# ---- C. GGX ---------------------------------------------------------------------------------------------------------------------
+def ggx_lambda(alpha2, cos_theta):
+    """Smith Lambda of the GGX distribution (Heitz 2014, eq. 72): (-1 + sqrt(1 + alpha^2 tan^2 theta)) / 2."""
+    c2 = cos_theta * cos_theta
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tan2 = np.where(c2 > 0, (1.0 - c2) / c2, np.inf)
+    return 0.5 * (-1.0 + np.sqrt(1.0 + alpha2 * tan2))
+
+
+def ggx_d(alpha2, cos_h):
+    """GGX / Trowbridge-Reitz normal distribution (Walter et al. 2007, eq. 33): alpha^2 / (pi ((alpha^2 - 1) cos^2 + 1)^2)."""
+    k = (alpha2 - 1.0) * cos_h * cos_h + 1.0
+    return alpha2 / (np.pi * k * k), k
+
+
+def schlick(F0, cos_hv):
+    """Schlick 1994: F0 + (1 - F0)(1 - cos)^5."""
+    return F0 + (1.0 - F0) * np.clip(1.0 - cos_hv, 0.0, 1.0)[..., None] ** 5
+
+
+def ggx_eval_cos(F0, alpha, L, V, d_floor=1e-5):
+    """f(L, V) cos(theta_L) of the microfacet BRDF with the height-correlated Smith masking-shadowing (Heitz 2014, eq. 99):
+    F D G2 / (4 cos_V),  G2 = 1 / (1 + Lambda(V) + Lambda(L)).  Directions in the local frame (normal = +z), cosines clamped at 0.
+    `d_floor` is D3.  -> value (n, 3), k = the cancelling term of D (for the error model)."""
+    nl, nv = np.maximum(L[:, 2], 0.0), np.maximum(V[:, 2], 0.0)
+    H = L + V
+    H = H / np.linalg.norm(H, axis=1, keepdims=True)
+    nh, hv = np.maximum(H[:, 2], 0.0), np.maximum((H * V).sum(axis=1), 0.0)
+    a2 = alpha * alpha
+    D, k = ggx_d(np.maximum(a2, d_floor), nh)
+    G2 = 1.0 / (1.0 + ggx_lambda(a2, nv) + ggx_lambda(a2, nl))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        val = np.where((nl > 0) & (nv > 0), D * G2 / (4.0 * nv), 0.0)
+    return schlick(F0, hv) * val[:, None], k
+
+
+def ggx_vndf_weight(F0, alpha, L, V):
+    """Weight of a sample drawn from the distribution of visible normals (Heitz 2018, eq. 19 with the height-correlated G2):
+    F G2 / G1(V) = F (1 + Lambda(V)) / (1 + Lambda(V) + Lambda(L)); 0 when L is below the surface.
+    -> value (n, 3), the half vector H rebuilt from L + V, the scalar weight, H.V."""
+    nl, nv = np.maximum(L[:, 2], 0.0), np.maximum(V[:, 2], 0.0)
+    H = L + V
+    H = H / np.linalg.norm(H, axis=1, keepdims=True)
+    hv = np.maximum((H * V).sum(axis=1), 0.0)
+    a2 = alpha * alpha
+    lv, ll = ggx_lambda(a2, nv), ggx_lambda(a2, nl)
+    w = np.where(nl > 0, (1.0 + lv) / (1.0 + lv + ll), 0.0)
+    return schlick(F0, hv) * w[:, None], H, w, hv
+
+
+def hemisphere_grid(n_theta, n_phi):
+    """Midpoint grid on the upper hemisphere in (theta, phi): -> directions (n, 3), solid-angle weights (n,)."""
+    th = (np.arange(n_theta) + 0.5) * (0.5 * np.pi / n_theta)
+    ph = (np.arange(n_phi) + 0.5) * (2 * np.pi / n_phi)
+    T, Pp = np.meshgrid(th, ph, indexing="ij")
+    d = np.stack([np.sin(T) * np.cos(Pp), np.sin(T) * np.sin(Pp), np.cos(T)], axis=-1).reshape(-1, 3)
+    w = (np.sin(T) * (0.5 * np.pi / n_theta) * (2 * np.pi / n_phi)).reshape(-1)
+    return d, w
+
+
+# ---- D. camera, sky, resolve ----------------------------------------------------------------------------------------------------
+def lens_z(height, focal_length):
+    """Pinhole with a 24 mm high sensor: the image plane, in pixels, lies at z = -(height / 2) * focal_length / 12."""
+    return -(height * 0.5) * focal_length / 12.0
+
+
+def project(direction, orient, half_width, half_height, z):
+    """Where a world-space direction pierces the image plane of a pinhole looking down -z in its own frame: rotate back by the
+    conjugate of the orientation quaternion (x, y, z, w), scale to the plane.  -> pixel coordinates x, y (float)."""
+    R = rotation_of_quaternion(np.asarray(orient, dtype=np.float64)[None, :])[0]
+    R = R / np.cbrt(np.linalg.det(R))
+    local = direction @ R                                                           # R^T d, row-vector form
+    s = z / local[:, 2]
+    return local[:, 0] * s + half_width, local[:, 1] * s + half_height, local[:, 2]
+
+
+def pixel_of_slot(index, width):
+    """Ray / accumulator slot -> pixel: slots are tile-major, 256 per 16 x 16 tile, tiles row by row, 16 pixels a row in the tile."""
+    tile, ID = index // 256, index % 256
+    h_tiles = width // 16
+    return 16 * (tile % h_tiles) + ID % 16, 16 * (tile // h_tiles) + ID // 16
+
+
+def equirect_texel(d, width, height):
+    """Latitude-longitude lookup (Debevec's convention turned so that u = 1/2 + atan2(z, x) / 2 pi, v = 1/2 - asin(y) / pi) under D2:
+    -> column, row (int), and the continuous coordinates ex, ey they were truncated from."""
+    ex = (width - 1) * (0.5 + np.arctan2(d[:, 2], d[:, 0]) / (2 * np.pi))
+    ey = (height - 1) * (0.5 - np.arcsin(np.clip(d[:, 1], -1.0, 1.0)) / np.pi)
+    return np.floor(ex).astype(np.int64), np.floor(ey).astype(np.int64), ex, ey
+
+
+ACES_IN = np.array([[0.59719, 0.35458, 0.04823], [0.07600, 0.90834, 0.01566], [0.02840, 0.13383, 0.83777]])
+ACES_OUT = np.array([[1.60475, -0.53108, -0.07367], [-0.10208, 1.10813, -0.00605], [-0.00327, -0.07276, 1.07602]])
+
+
+def aces_fitted(rgb):
+    """Stephen Hill's published fit of the ACES RRT + ODT (BakingLab ACES.hlsl): input matrix, rational fit, output matrix, saturate."""
+    v = rgb @ ACES_IN.T
+    v = (v * (v + 0.0245786) - 0.000090537) / (v * (0.983729 * v + 0.4329510) + 0.238081)
+    return np.clip(v @ ACES_OUT.T, 0.0, 1.0)
+
+
+def resolve(acc, accumulations, exposure, width, height):
+    """Median of means (Renderer.hpp:436-478) from the accumulator [tile][bucket][rgb][256] alone: per-bucket mean, np.median across the
+    buckets (even counts: the mean of the two middle values, numpy's convention), exposure, ACES, alpha 1.  -> (height, width, 4)."""
+    acc = np.asarray(acc, dtype=np.float64)
+    k = acc.shape[1]
+    mean = acc / (accumulations / k)
+    med = np.median(mean, axis=1) * exposure                                        # [tile][rgb][256]
+    rgb = aces_fitted(np.moveaxis(med, 1, 2).reshape(-1, 3))
+    x, y = pixel_of_slot(np.arange(acc.shape[0] * 256), width)
+    out = np.zeros((height, width, 4))
+    out[y, x, :3] = rgb
+    out[y, x, 3] = 1.0
+    return out
+
+
+def sphere_depth_normal(ix, iy, half_width, half_height, z, eye_z, radius=1.0):
+    """A pinhole at (0, 0, eye_z) looking down -z (identity orientation) at a sphere about the origin: image-plane point (ix, iy) ->
+    distance to the first hit (inf on a miss) and the unit normal there."""
+    d = np.stack([ix - half_width, iy - half_height, np.full_like(ix, z)], axis=-1)
+    d = d / np.linalg.norm(d, axis=-1, keepdims=True)
+    b = -eye_z * d[..., 2]
+    disc = b * b - (eye_z * eye_z - radius * radius)
+    t = np.where(disc >= 0, b - np.sqrt(np.maximum(disc, 0.0)), np.inf)
+    with np.errstate(invalid="ignore"):
+        n = (np.array([0.0, 0.0, eye_z]) + d * np.where(np.isfinite(t), t, 0.0)[..., None]) / radius
+    return t, n

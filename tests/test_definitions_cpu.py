@@ -1,0 +1,765 @@
+"""The CPU oracle against float64 definitions of each operation (tests/definitions.py), operation by operation.
+
+Every other test compares the HIP path with oracle/oracle.cpp bit for bit; both were written from the same reference lines, so a shared
+misreading passes all of them.  Here each operation is held to a statement of what it is meant to compute, in float64 numpy, written from
+the textbook formula.  The `check_*` functions take a backend (this file: the oracle through oracle_binding; test_definitions_gpu.py:
+the kernels through the debug entry points) so that both sides face the same inputs, the same definitions and the same bounds.
+
+Bounds are never taken from the code under test.  Each is either derived (the derivation is at the constant or in definitions.py) or
+measured on the CPU oracle and given a stated margin; the measured figure is in the docstring of the check and in DESIGN.md §2.
+Reference departures from the textbook are named expectations (D1-D4 in definitions.py, Q rows of SURVEY.md §8a).
+
+Left out on purpose: MIS-on multi-bounce scenes and MIS-off emissive scenes against physics.  Q8 (the MIS pdf is taken of the world-space
+direction) and Q9 (emission added without throughput) bias them by design, so no closed form of the physics applies; stream order and
+Q14 (fused body, unfused tail) are arithmetic, not definitions.  Those rows stay pinned by parity alone."""
+import math
+
+import numpy as np
+import pytest
+
+import definitions as df
+import oracle_binding as ob
+from definitions import u
+
+f32, f64 = np.float32, np.float64
+
+# ---- bounds ---------------------------------------------------------------------------------------------------------------------
+EXCLUDED_CAP = 0.005                  # part A: share of rays per scene that may be set aside as undecidable in binary32 (set by the issue)
+SINCOS_ABS = 2e-6                     # asserted by test_fast_math_properties against float64 sin / cos
+ATAN2_ABS, ASIN_ABS = 2e-3, 1e-3      # likewise
+# azimuth: sincos bound + rounding of the argument 2 pi s (constant, product: 3 roundings of a value <= 2 pi) + sqrt and product
+AZIMUTH_ABS = SINCOS_ABS + 2 * math.pi * 3 * u + 2 * u
+# unit length of a sampled direction: |len^2 - 1| <= rho^2 |s^2 + c^2 - 1| <= 2 * 2 * SINCOS_ABS, so |len - 1| <= 2 * SINCOS_ABS; + roundings
+UNIT_ABS = 2 * SINCOS_ABS + 8 * u
+FRAME_ROUNDING = 24 * u               # q's three components carry <= 3 roundings each: |q|^2 to 6u, |q|^4 to 12u; doubled
+CONE_ANGLE_ABS = SINCOS_ABS + 16 * u  # direction components: sincos bound + basis / combination roundings; angle error <= component error
+# GGX eval: D's denominator k = 1 + (a^2 - 1) cos^2 cancels.  cos^2 of the normalised half vector carries 7u, the product 9u (value <= 1),
+# the sum one more: |dk| <= 10u, D = a^2 / (pi k^2) -> 20u / k relative; 24u / k taken.  The rest (F, G2, H.V, products: about 30 roundings): 64u.
+GGX_EVAL_K, GGX_EVAL_REL = 24 * u, 64 * u
+GGX_WEIGHT_REL = 64 * u               # measured 1.0e-6 on the oracle where H.V > 0.1 (two G1, their ratio, Schlick), margin x 3.7
+# F is a function of H.V, and H.V is known from the binary32 direction only through (H.V)^2 = (1 + L.V) / 2: L's components carry u / 2 each,
+# so d(H.V)^2 <= u and d(H.V) <= u / (2 H.V); Schlick's slope is <= 5 -> dF <= 2.5u / (H.V); 10u / (H.V) taken (grazing V: H.V ~ 1e-3)
+GGX_HV_COND = 10 * u
+GGX_UPPER_ABS = 16 * u                # H.z >= 0 and V.H >= 0 up to the rounding of the reflected direction
+RESOLVE_ABS = 32 * u                  # ACES in binary32: fit to ~10u relative, output matrix row sums of |m| <= 2.21 -> < 30u; measured 2.7e-7
+PROJECT_REL = 32 * u                  # rotation + normalisation: < 16 roundings of values <= the image-plane distance; doubled
+SIGMA = 5.0                           # whole-path closed forms: 5 sigma with the analytic sigma (a bound for the reference itself)
+
+
+def report(name, **figures):
+    print(f"[definitions] {name}: " + ", ".join(f"{k}={v:.4g}" if isinstance(v, float) else f"{k}={v}" for k, v in figures.items()))
+
+
+# ---- the oracle as a backend ----------------------------------------------------------------------------------------------------
+class OracleBackend:
+    name = "oracle"
+    variants = (("brute", dict(trav_mode=ob.TRAV_BRUTE)), ("twin_bvh", dict(trav_mode=ob.TRAV_PER_RAY_BVH)))
+
+    def __init__(self, mirt):
+        self.mirt, self.lib = mirt, ob.load()
+
+    @staticmethod
+    def _c(a):
+        return np.ascontiguousarray(a, dtype=f32)
+
+    def hemisphere(self, t, s):
+        out = np.empty((len(t), 3), dtype=f32); base = out.ctypes.data
+        for i in range(len(t)):
+            self.lib.orc_hemisphere(float(t[i]), float(s[i]), base + 12 * i)
+        return out
+
+    def frame(self, N, v):
+        N, v = self._c(N), self._c(v)
+        q, l, w = (np.empty((len(N), k), dtype=f32) for k in (4, 3, 3))
+        nb, vb, qb, lb, wb = (a.ctypes.data for a in (N, v, q, l, w))
+        for i in range(len(N)):
+            self.lib.orc_tangent_space(nb + 12 * i, qb + 16 * i)
+            self.lib.orc_to_local(qb + 16 * i, vb + 12 * i, lb + 12 * i)
+            self.lib.orc_to_world(qb + 16 * i, vb + 12 * i, wb + 12 * i)
+        return q, l, w
+
+    def sample_sphere(self, Wc, sin2, dist, r2, t, s):
+        Wc = self._c(Wc); out = np.empty((len(Wc), 5), dtype=f32); wb, base = Wc.ctypes.data, out.ctypes.data
+        for i in range(len(Wc)):
+            self.lib.orc_sample_direction_to_sphere(wb + 12 * i, float(sin2[i]), float(dist[i]), float(r2[i]), float(t[i]), float(s[i]), base + 20 * i)
+        return out
+
+    def ggx_eval(self, F0, alpha, L, V):
+        F0, L, V = self._c(F0), self._c(L), self._c(V); out = np.empty((len(L), 3), dtype=f32)
+        fb, lb, vb, base = (a.ctypes.data for a in (F0, L, V, out))
+        for i in range(len(L)):
+            self.lib.orc_ggx_eval(fb + 12 * i, float(alpha[i]), lb + 12 * i, vb + 12 * i, base + 12 * i)
+        return out
+
+    def ggx_sample(self, F0, alpha, V, u0, u1):
+        F0, V = self._c(F0), self._c(V); d, e = np.empty((len(V), 3), dtype=f32), np.empty((len(V), 3), dtype=f32)
+        fb, vb, db, eb = (a.ctypes.data for a in (F0, V, d, e))
+        for i in range(len(V)):
+            self.lib.orc_ggx_sample(fb + 12 * i, float(alpha[i]), vb + 12 * i, float(u0[i]), float(u1[i]), db + 12 * i, eb + 12 * i)
+        return d, e
+
+    def raygen(self, sc, w, h, acc, max_bounces=16):
+        o = ob.Oracle(sc, max_bounces=max_bounces); o.Resize(w, h)
+        p, d = o.raygen(acc); o.close()
+        return p, d
+
+    def tracers(self, sc):
+        for label, kw in self.variants:
+            o = ob.Oracle(sc); o.Resize(16, 16)
+            mode = kw["trav_mode"]
+            yield label, (lambda P, D, o=o, m=mode: o.trace_closest(P, D, m)), (lambda P, D, T, o=o, m=mode: o.trace_shadow(P, D, T, m))
+            o.close()
+
+    def render(self, sc, w, h, n_acc, max_bounces, buckets=5, mis=True, variant=0):
+        o = ob.Oracle(sc, max_bounces=max_bounces, buckets=buckets, mis=mis, **self.variants[variant][1])
+        o.Resize(w, h); o.Accumulate(n_acc)
+        out = dict(acc=o.accumulator(), frame=o.Render() if n_acc % buckets == 0 else None, counters=o.counters())
+        o.close()
+        return out
+
+
+@pytest.fixture(scope="module")
+def be(mirt):
+    return OracleBackend(mirt)
+
+
+def pcg(mirt, seed, n):
+    """n draws of the project's own generator (Random.hpp:20-29 as restated in scene.py), binary32 in [0, 1]."""
+    return mirt.scene.pcg_floats(mirt.scene.hash_u32(seed), n)
+
+
+def unit_f32(v):
+    """glm::normalize in binary32: v * (1 / sqrt(dot)) - the way normals reach the frame on the path."""
+    v = np.asarray(v, dtype=f32)
+    d = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+    return v * (f32(1.0) / np.sqrt(d))[:, None]
+
+
+# ---- A. intersection and occlusion ----------------------------------------------------------------------------------------------
+def awkward_scene(mirt):
+    """Exact duplicates, a concentric shell, a sphere around the camera, tiny and huge radii, half the centres on one plane."""
+    S = mirt.scene
+    rng = np.random.default_rng(5)
+    n = 65
+    geo = np.zeros(n, dtype=S.SPHERE)
+    geo["position"] = rng.uniform(-6, 6, (n, 3)).astype(f32)
+    geo["radius_sq"] = (rng.uniform(0.05, 1.2, n) ** 2).astype(f32)
+    geo["position"][1] = geo["position"][0]; geo["radius_sq"][1] = geo["radius_sq"][0]
+    geo["position"][2] = geo["position"][0]; geo["radius_sq"][2] = geo["radius_sq"][0] * 4
+    geo["position"][3] = (0.0, 1.0, 14.0); geo["radius_sq"][3] = 4.0
+    geo["radius_sq"][4] = 1e-6; geo["radius_sq"][5] = 400.0
+    geo["position"][n // 2:, 1] = 0.5
+    mats = np.zeros(2, dtype=S.MATERIAL); mats["albedo"] = 0.5; mats["emission"][1] = 15.0
+    geo["material_ID"][::16] = 1
+    cam = S.Camera(eye=(0.0, 1.0, 14.0), direction=(0.0, -0.05, -1.0), focal_length=35.0, exposure=1.0)
+    return S.Scene(geo, mats, cam, np.full(3, 0.3, dtype=f32), name="awkward")
+
+
+TRACE_SCENES = {"default9": (lambda m: m.scene.default9(), 20000), "S8a": (lambda m: m.scene.synthetic(8, ambient=0.5), 20000),
+                "S1000a": (lambda m: m.scene.synthetic(1000, ambient=0.5), 20000), "awkward": (awkward_scene, 20000)}
+
+
+def ray_mix(sc, n_rays):
+    """The ray mix of test_trace_kernels_bit_exact: the 128 x 128 camera rays, then rays from points at 0.5, 1 -+ 1e-3, 1.5 and 3 radii
+    off sphere centres in random directions; five axis-parallel; a quarter with non-unit directions (|D| 0.9 ... 1.5, D1).  One change,
+    reasoned: that test starts a fifth of its rays ON the surface (factor 1.0).  Such a ray has a root that is zero up to rounding, so whether
+    binary32 reports 0, the far root or a miss is undecidable for every one of them - 20 % of the mix against a 0.5 % cap - and they are
+    moved to 1e-3 radii either side of the surface."""
+    o = ob.Oracle(sc); o.Resize(128, 128)
+    cp, cd = o.raygen(1)
+    prims = o.bvh()[1]
+    o.close()
+    rng = np.random.default_rng(3)
+    geo = sc.geometry
+    pick = rng.integers(0, len(geo), n_rays)
+    nrm = rng.normal(size=(n_rays, 3)); nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    rad = np.sqrt(geo["radius_sq"][pick])[:, None] * rng.choice([0.5, 1.0 - 1e-3, 1.0 + 1e-3, 1.5, 3.0], size=(n_rays, 1))
+    p = (geo["position"][pick] + nrm * rad).astype(f32).T
+    d = rng.normal(size=(n_rays, 3)); d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(f32).T
+    d[0, :5] = 0.0
+    q = n_rays // 4
+    d[:, :q] *= rng.choice(np.array([0.9, 0.999, 1.00001, 1.00004, 1.0002, 1.002, 1.06, 1.125, 1.5], dtype=f32), size=q)[None, :]
+    P = np.ascontiguousarray(np.concatenate([cp, p], axis=1)); D = np.ascontiguousarray(np.concatenate([cd, d], axis=1))
+    return P, D, prims
+
+
+_reference_cache = {}
+
+
+def trace_reference(mirt, scene_name):
+    if scene_name not in _reference_cache:
+        make, n_rays = TRACE_SCENES[scene_name]
+        sc = make(mirt)
+        P, D, prims = ray_mix(sc, n_rays)
+        centre, r2 = prims["position"].astype(f64), prims["radius_sq"].astype(f64)
+        P64, D64 = P.T.astype(f64), D.T.astype(f64)
+        ref = df.closest_hit(P64, D64, centre, r2)
+        rng = np.random.default_rng(11)
+        tmax = np.where(np.isfinite(ref["t"]), ref["t"] * rng.uniform(0.5, 1.5, len(P64)), 10.0).astype(f32)
+        occ, occ_unsure = df.occluded(P64, D64, tmax.astype(f64), centre, r2)
+        _reference_cache[scene_name] = (sc, P, D, P64, D64, centre, r2, ref, tmax, occ, occ_unsure)
+    return _reference_cache[scene_name]
+
+
+def check_intersection(be, mirt, scene_name):
+    """Closest hit and any-hit against the float64 nearest non-negative root over all spheres (definitions.closest_hit states the acceptance
+    rule in words).  (1) hit / miss equal, (2) sphere equal, (3) |t - t64| within the per-ray bound derived in
+    definitions.sphere_error_model.  Set aside: rays on which some sphere's own status is within its derived error of flipping (1), and rays
+    with a second root within the summed bounds of the nearest (2) - those must still report one of the rivals, at that rival's float64
+    distance.  Together <= 0.5 % per scene.
+
+    Measured on the oracle (brute force and the twin BVH alike), 36 384 rays a scene: set aside default9 0.005 %, S8a 0.055 %, S1000a 0.21 %,
+    awkward 0.21 % (shadow rays 0.05 / 0.20 / 0.07 / 0.23 %); largest |t - t64| / bound 0.27 (awkward); wrong class / sphere / distance among
+    the rest: 0.  S1000a shows two sphere disagreements in all (rays 10485 and 15247 of the mix: binary32 reports a grazing hit on a small
+    sphere at t = 50.0 / 70.9 where float64 has the ray pass it and reach t = 74.2 / 72.4).  Both are explained by the derived error - the
+    small sphere's own discriminant lies inside E_disc - and are set aside under (1), not tolerated by a flat bound."""
+    sc, P, D, P64, D64, centre, r2, ref, tmax, occ, occ_unsure = trace_reference(mirt, scene_name)
+    n = len(P64)
+    has_rival = np.array([r is not None for r in ref["rivals"]])
+    aside = ref["unsure"] | has_rival
+    assert aside.mean() <= EXCLUDED_CAP, f"{scene_name}: {aside.mean():.4%} of the rays set aside"
+    assert occ_unsure.mean() <= EXCLUDED_CAP, f"{scene_name}: {occ_unsure.mean():.4%} of the shadow rays set aside"
+    clean = ~aside
+    want_hit = ref["prim"] >= 0
+    assert want_hit.mean() > 0.2 and (~want_hit).sum() > 100
+    for label, closest, shadow in be.tracers(sc):
+        t32, id32 = closest(P, D)
+        t32 = t32.astype(f64)
+        what = f"{be.name}/{label}/{scene_name}"
+        wrong_class = clean & ((id32 >= 0) != want_hit)
+        assert not wrong_class.any(), f"{what}: hit/miss differs on {wrong_class.sum()} rays, first {np.flatnonzero(wrong_class)[:5]}"
+        wrong_prim = clean & (id32 != ref["prim"])
+        assert not wrong_prim.any(), f"{what}: sphere differs on {wrong_prim.sum()} rays, first {np.flatnonzero(wrong_prim)[:5]}"
+        k = clean & want_hit
+        ratio = np.abs(t32[k] - ref["t"][k]) / ref["E"][k]
+        assert ratio.max() <= 1.0, f"{what}: |t - t64| is {ratio.max():.3g} x the derived bound"
+        # rays with rivals (and no doubtful sphere): one of the rivals, at its own float64 distance
+        rv = np.flatnonzero(has_rival & ~ref["unsure"])
+        for i in rv:
+            allowed = set(ref["rivals"][i].tolist()) | {int(ref["prim"][i])}
+            assert int(id32[i]) in allowed, f"{what}: ray {i} reports sphere {id32[i]}, candidates {sorted(allowed)}"
+        if len(rv):
+            near, far, E = df.root_of(P64[rv], D64[rv], centre, r2, id32[rv])
+            t64 = np.where(near >= -E, np.maximum(near, 0.0), far)
+            assert (np.minimum(np.abs(t32[rv] - t64), np.abs(t32[rv] - far)) <= E).all(), f"{what}: a rival's distance is off"
+        got_occ = shadow(P, D, tmax).astype(bool)
+        bad = ~occ_unsure & (got_occ != occ)
+        assert not bad.any(), f"{what}: occlusion differs on {bad.sum()} rays, first {np.flatnonzero(bad)[:5]}"
+        report(what, rays=n, set_aside=float(aside.mean()), shadow_set_aside=float(occ_unsure.mean()), worst_t_over_bound=float(ratio.max()),
+               occluded=float(occ.mean()))
+
+
+@pytest.mark.parametrize("scene_name", list(TRACE_SCENES))
+def test_intersection(be, mirt, scene_name):
+    check_intersection(be, mirt, scene_name)
+
+
+# ---- B. sampling and frames -----------------------------------------------------------------------------------------------------
+def check_hemisphere(be, mirt):
+    """hemisphere(t, s): unit, z >= 0, z^2 = 1 - t (found from the outputs: t is the squared radius of Malley's disk, not the squared
+    cosine), azimuth 2 pi s, cosine-weighted - chi-square on a 16 x 16 grid of equal-probability cells in (z^2, phi), 20 000 inputs from the
+    project's own PCG, critical value 377.08 (p = 1e-6, 255 degrees of freedom).
+    Measured on the oracle: chi-square 208.8; |len - 1| <= 1.3e-7; x, y within 5.9e-7 of sqrt(t) cos / sin(2 pi s)."""
+    n = 20000
+    r = pcg(mirt, 2024, 2 * n)
+    t = np.concatenate([r[0::2], f32([0.0, 1.0, 1.0, 0.5])]); s = np.concatenate([r[1::2], f32([0.0, 1.0, 0.25, 1.0])])
+    out = be.hemisphere(t, s).astype(f64)
+    t64, s64 = t.astype(f64), s.astype(f64)
+    length = np.linalg.norm(out, axis=1)
+    assert np.abs(length - 1.0).max() <= UNIT_ABS
+    assert (out[:, 2] >= 0.0).all()
+    z2 = out[:, 2] ** 2
+    fit_cos, fit_sin = np.abs(z2 - (1.0 - t64)).max(), np.abs(z2 - t64).max()
+    assert fit_cos <= 4 * u and fit_sin > 0.5, (fit_cos, fit_sin)             # named: z^2 = 1 - t
+    rho = np.sqrt(t64)
+    ex = np.abs(out[:, 0] - rho * np.cos(2 * np.pi * s64)).max(); ey = np.abs(out[:, 1] - rho * np.sin(2 * np.pi * s64)).max()
+    assert max(ex, ey) <= AZIMUTH_ABS, (ex, ey)
+    o = out[:n]
+    i = np.minimum((16 * o[:, 2] ** 2).astype(int), 15)
+    j = np.minimum((16 * (np.arctan2(o[:, 1], o[:, 0]) % (2 * np.pi)) / (2 * np.pi)).astype(int), 15)
+    counts = np.bincount(i * 16 + j, minlength=256).astype(f64)
+    chi2 = float(((counts - n / 256.0) ** 2 / (n / 256.0)).sum())
+    report(f"{be.name}/hemisphere", chi2=chi2, unit=float(np.abs(length - 1).max()), azimuth=float(max(ex, ey)))
+    assert chi2 < df.CHI2_255_P1E6, chi2
+
+
+def test_hemisphere(be, mirt):
+    check_hemisphere(be, mirt)
+
+
+SMALL_ANGLE = 0.00068523              # sin^2(theta_max) below which the sampler switches to its small-angle form
+
+
+def check_sample_sphere(be, mirt):
+    """sample_direction_to_sphere: of the five outputs the LAST is the pdf (the only column that tracks 1 / (2 pi (1 - cos theta_max)));
+    the first three are a unit direction inside the cone about Wc.  pdf bound, derived: cos = sqrt(fl(1 - sin^2)) carries <= u absolute
+    (half an ulp of a value in [1/2, 1] through a sqrt of slope <= 0.71, plus the sqrt's own half ulp), 1 - cos is then exact or one more
+    rounding, so the relative error is <= 2u / (1 - cos theta_max) + 4u.  Below sin^2 ~ 2e-6 the floor D4 takes over.
+    Measured on the oracle, pdf relative error: small-angle side (sin^2 in [1e-5, 0.000685)) max 8.6e-3 at sin^2 = 1.0e-5, where the bound
+    is 2.4e-2; just below / above the switch 1.3e-4 / 1.3e-4 (bound 3.5e-4); larger angles <= 5.1e-5; error / bound <= 0.40 throughout.
+    Direction: |len - 1| <= 2.7e-7; angle beyond the cone <= 7.3e-8 rad; large-angle branch cos(theta) within 2.5e-7 of 1 - t (1 - cos theta_max)."""
+    n = 20000
+    rng = np.random.default_rng(17)
+    Wc = unit_f32(rng.normal(size=(n, 3)))
+    Wc[:3] = [(0, 0, 1), (0, 0, -1), (1, 0, 0)]
+    dist = rng.uniform(0.2, 50, n).astype(f32)
+    sin2 = rng.uniform(0.001, 0.9, n).astype(f32)
+    q = n // 4
+    sin2[:q] = np.exp(rng.uniform(np.log(1e-5), np.log(SMALL_ANGLE), q)).astype(f32)
+    sin2[q:q + 2000] = (SMALL_ANGLE * (1.0 + rng.uniform(-1e-3, 1e-3, 2000))).astype(f32)
+    th = f32(SMALL_ANGLE)
+    sin2[q:q + 3] = [np.nextafter(th, f32(0)), th, np.nextafter(th, f32(1))]
+    r2 = (sin2 * (dist * dist)).astype(f32)
+    r = pcg(mirt, 77, 2 * n); t, s = r[0::2].copy(), r[1::2].copy()
+    out = be.sample_sphere(Wc, sin2, dist, r2, t, s).astype(f64)
+    s2 = sin2.astype(f64)
+    pdf64, omc = df.cone_pdf(s2)
+    tracks = [float(np.median(np.abs(out[:, k] / pdf64 - 1.0))) < 1e-2 for k in range(5)]
+    assert tracks == [False, False, False, False, True], tracks                 # named: out[4] is the pdf, out[3] the distance
+    rel = np.abs(out[:, 4] / pdf64 - 1.0)
+    bound = 2 * u / omc + 4 * u
+    assert (rel <= bound).all(), f"pdf off by {(rel / bound).max():.3g} x the derived bound"
+    small = sin2 < th
+    L = out[:, :3]; W = Wc.astype(f64)
+    length = np.linalg.norm(L, axis=1)
+    assert np.abs(length - 1.0).max() <= UNIT_ABS
+    angle = np.arctan2(np.linalg.norm(np.cross(L, W), axis=1), (L * W).sum(axis=1))
+    beyond = angle - np.arcsin(np.sqrt(s2))
+    assert beyond.max() <= CONE_ANGLE_ABS, beyond.max()
+    cos_want = 1.0 - t.astype(f64) * omc
+    cos_err = np.abs(np.cos(angle) * 1.0 - cos_want)[~small]
+    assert cos_err.max() <= CONE_ANGLE_ABS, cos_err.max()                       # uniform in the cone's solid angle: cos(theta) linear in t
+    # D4: the floor
+    tiny = np.full(4, 1e-7, dtype=f32)
+    o4 = be.sample_sphere(Wc[:4], tiny, dist[:4], tiny * dist[:4] ** 2, t[:4], s[:4]).astype(f64)
+    assert np.abs(o4[:, 4] * (2 * np.pi * 1e-6) - 1.0).max() <= 8 * u
+    edge = (np.abs(s2 / SMALL_ANGLE - 1.0) < 2e-3)
+    report(f"{be.name}/sample_sphere", pdf_rel_small=float(rel[small].max()), at_sin2=float(s2[small][rel[small].argmax()]),
+           pdf_rel_below_switch=float(rel[edge & small].max()), pdf_rel_above_switch=float(rel[edge & ~small].max()), pdf_rel_large=float(rel[~small & ~edge].max()),
+           worst_over_bound=float((rel / bound).max()), unit=float(np.abs(length - 1).max()), beyond_cone=float(beyond.max()), cos_err=float(cos_err.max()))
+
+
+def test_sample_direction_to_sphere(be, mirt):
+    check_sample_sphere(be, mirt)
+
+
+def check_frame(be, mirt):
+    """tangent_space / to_local / to_world for 20 000 normals, among them (0, 0, +-1) and 4 000 with N.z -> -1.  The quaternion is rebuilt as
+    a 3 x 3 in float64.  A REFERENCE PROPERTY, not a bug: the shortest-arc formula never normalises, so for an input of length |N| != 1 it
+    has |q|^2 - 1 = (|N|^2 - 1) / (2 (1 + N.z)) exactly, the matrix is |q|^2 times a rotation, and both its defect from orthonormality
+    max|R^T R - I| and |R e_z - N| are bounded by B = 2k + k^2, k = | |N|^2 - 1 | / (2 (1 + N.z)) (+ 24u (1 + B)^2 of rounding).  Binary32-normalised
+    normals have | |N|^2 - 1 | ~ 1e-7, so the defect grows like 1e-7 / (1 + N.z) towards the pole; below N.z = -1 + 2^-23 the frame of
+    (0, 0, -1) is returned outright.  to_world / to_local agree with R v / R^T v within (that bound + 32u) |v|.
+    Measured on the oracle, largest defect by 1 + N.z: [1e-7, 1e-6) 2.5, [1e-6, 1e-5) 0.22, [1e-5, 1e-4) 2.0e-2, [1e-4, 1e-3) 2.1e-3,
+    [1e-3, 1e-2) 2.0e-4, [1e-2, 0.1) 2.2e-5, [0.1, 2] 2.1e-6; defect / bound <= 1.00 (the bound is the exact algebra, so it is met tightly)."""
+    n = 20000
+    rng = np.random.default_rng(23)
+    eps = np.exp(rng.uniform(np.log(3e-4), np.log(0.3), 4000)); phi = rng.uniform(0, 2 * np.pi, 4000)
+    near_pole = np.stack([np.sin(eps) * np.cos(phi), np.sin(eps) * np.sin(phi), -np.cos(eps)], axis=1)
+    N = unit_f32(np.concatenate([rng.normal(size=(n - 4000 - 4, 3)), near_pole, [(0, 0, 1), (0, 0, -1), (1e-4, 0, -1), (0, -3e-4, -1)]]))
+    v = rng.normal(size=(n, 3)).astype(f32)
+    q, l, w = (a.astype(f64) for a in be.frame(N, v))
+    N64, v64 = N.astype(f64), v.astype(f64)
+    pole = N[:, 2] < f32(-1.0) + f32(2.0 ** -23)
+    assert pole.sum() >= 1 and (q[pole] == [0.0, 1.0, 0.0, 0.0]).all()          # named: the pole branch
+    k = ~pole
+    R = df.rotation_of_quaternion(q[k])
+    defect = np.abs(np.einsum("nji,njk->nik", R, R) - np.eye(3)).max(axis=(1, 2))
+    bound = df.frame_defect_bound(N64[k])
+    bound = bound + FRAME_ROUNDING * (1.0 + bound) ** 2                         # the roundings are relative to |q|^4
+    assert (defect <= bound).all(), f"defect is {(defect / bound).max():.3g} x the derived bound"
+    to_n = np.abs(R[:, :, 2] - N64[k]).max(axis=1)
+    assert (to_n <= bound).all(), f"R e_z misses N by {(to_n / bound).max():.3g} x the derived bound"
+    vb = (bound + 32 * u) * np.linalg.norm(v64[k], axis=1)
+    assert (np.abs(w[k] - np.einsum("nij,nj->ni", R, v64[k])).max(axis=1) <= vb).all()
+    assert (np.abs(l[k] - np.einsum("nji,nj->ni", R, v64[k])).max(axis=1) <= vb).all()
+    one_plus = 1.0 + N64[k][:, 2]
+    edges = [1e-7, 1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 0.1, 2.01]
+    table = {f"[{a:g},{b:g})": float(defect[(one_plus >= a) & (one_plus < b)].max()) for a, b in zip(edges, edges[1:]) if ((one_plus >= a) & (one_plus < b)).any()}
+    report(f"{be.name}/frame", worst_over_bound=float((defect / bound).max()), **table)
+    assert len(table) >= 6                                                       # the sweep reaches the pole
+
+
+def test_tangent_frame(be, mirt):
+    check_frame(be, mirt)
+
+
+# ---- C. GGX ---------------------------------------------------------------------------------------------------------------------
+def upper_dirs(rng, n, z_min=1e-3):
+    z = np.exp(rng.uniform(np.log(z_min), 0.0, n)); phi = rng.uniform(0, 2 * np.pi, n)
+    rho = np.sqrt(1.0 - z * z)
+    return unit_f32(np.stack([rho * np.cos(phi), rho * np.sin(phi), z], axis=1))
+
+
+def check_ggx_eval(be, mirt):
+    """Closure<GGX>::eval = F D G2 cos_L / (4 cos_L cos_V) with Schlick's F, the GGX D and the HEIGHT-CORRELATED Smith G2 (the variant
+    Sampling.hpp:287-291 uses, written here from Heitz 2014 eq. 99 with Lambda, not from its Lagarde form), alpha from 1e-4 to 1, V and L
+    down to cos = 1e-3.  D3 (D's alpha^2 floored at 1e-5) is a named argument of the definition.  Bound per sample, derived at GGX_EVAL_K:
+    24u / k + 64u with k = 1 + (alpha^2 - 1) cos^2(theta_h) from float64.
+    Measured on the oracle: error / bound <= 0.33; away from the cancellation (k > 0.1) the relative error is <= 3.5e-6."""
+    n = 6000
+    rng = np.random.default_rng(31)
+    F0 = rng.uniform(0.02, 1.0, (n, 3)).astype(f32)
+    alpha = np.exp(rng.uniform(np.log(1e-4), 0.0, n)).astype(f32)
+    alpha[:8] = [1e-4, 1e-3, 1e-2, 0.1, 0.3, 1.0, 3.2e-3, 0.5]
+    L, V = upper_dirs(rng, n), upper_dirs(rng, n)
+    L[: n // 4] = unit_f32(V[: n // 4] * f32([-1, -1, 1]) + rng.normal(size=(n // 4, 3)).astype(f32) * alpha[: n // 4, None])   # near the mirror direction: the lobe
+    L[:, 2] = np.abs(L[:, 2])
+    got = be.ggx_eval(F0, alpha, L, V).astype(f64)
+    want, k = df.ggx_eval_cos(F0.astype(f64), alpha.astype(f64), L.astype(f64), V.astype(f64))
+    assert np.isfinite(got).all() and (got >= 0).all() and want.max() > 10.0
+    rel = np.abs(got - want).max(axis=1) / np.maximum(want.max(axis=1), 1e-300)
+    bound = GGX_EVAL_K / k + GGX_EVAL_REL
+    sig = want.max(axis=1) > 1e-30
+    assert (rel[sig] <= bound[sig]).all(), f"eval off by {(rel[sig] / bound[sig]).max():.3g} x the derived bound"
+    report(f"{be.name}/ggx_eval", worst_over_bound=float((rel[sig] / bound[sig]).max()), rel_where_k_large=float(rel[sig & (k > 0.1)].max()), smallest_k=float(k.min()))
+
+
+def check_ggx_sample(be, mirt):
+    """Closure<GGX>::sample: the direction is the reflection of V about a visible normal - the half vector rebuilt from (V, L) lies in the
+    upper hemisphere and faces V - and the estimator is F G2 / G1(V) (Heitz 2018 eq. 19, height-correlated G2), 0 below the surface.
+    alpha = 0 is the mirror about the normal with weight F(cos_V).  Bound: 64u relative (measured 1.0e-6 on the oracle where H.V > 0.1, x 3.7)
+    + 10u / (H.V) for the conditioning of F on the binary32 direction (derived at GGX_HV_COND) + 1e-7 absolute.
+    Measured on the oracle: error / bound <= 0.14; 15 % of the samples (grazing V down to cos = 1e-3) leave below the surface with weight 0."""
+    n = 6000
+    rng = np.random.default_rng(37)
+    F0 = rng.uniform(0.02, 1.0, (n, 3)).astype(f32)
+    alpha = np.exp(rng.uniform(np.log(1e-4), 0.0, n)).astype(f32)
+    alpha[:6] = [1e-4, 1e-3, 1e-2, 0.1, 1.0, 0.0]
+    V = upper_dirs(rng, n)
+    V[:2] = [(0, 0, 1), (0.6, 0.0, 0.8)]
+    r = pcg(mirt, 99, 2 * n); u0, u1 = r[0::2].copy(), r[1::2].copy()
+    d, e = (a.astype(f64) for a in be.ggx_sample(F0, alpha, V, u0, u1))
+    V64, a64 = V.astype(f64), alpha.astype(f64)
+    mirror = alpha == 0
+    assert (d[mirror] == V64[mirror] * [-1, -1, 1]).all()
+    assert np.abs(e[mirror] - df.schlick(F0[mirror].astype(f64), V64[mirror][:, 2])).max() <= 16 * u
+    k = ~mirror
+    assert np.abs(np.linalg.norm(d[k], axis=1) - 1.0).max() <= 16 * u
+    want, H, weight, hv = df.ggx_vndf_weight(F0[k].astype(f64), a64[k], d[k], V64[k])
+    assert (H[:, 2] >= -GGX_UPPER_ABS).all() and ((H * V64[k]).sum(axis=1) >= -GGX_UPPER_ABS).all()
+    err = np.abs(e[k] - want).max(axis=1)
+    tol = GGX_WEIGHT_REL * want.max(axis=1) + GGX_HV_COND / np.maximum(hv, 1e-30) * weight + 1e-7
+    assert (err <= tol).all(), f"estimator off by {(err / tol).max():.3g} x the bound"
+    assert (d[k][:, 2] > 0).mean() > 0.5 and ((e[k] == 0).all(axis=1) == (d[k][:, 2] <= 0)).all()
+    well = (hv > 0.1) & (want.max(axis=1) > 1e-3)
+    report(f"{be.name}/ggx_sample", worst_over_bound=float((err / tol).max()), rel_where_hv_large=float((err[well] / want.max(axis=1)[well]).max()), below_surface=float((d[k][:, 2] <= 0).mean()))
+
+
+ENERGY_PAIRS = [(0.15, 0.9), (0.15, 0.3), (0.3, 0.9), (0.3, 0.3), (0.6, 0.9), (0.6, 0.2), (1.0, 0.9), (1.0, 0.3)]       # (alpha, cos_V)
+
+
+def check_ggx_energy(be, mirt):
+    """For F0 = 1 the hemispherical integral of eval (which carries the cosine) is the directional albedo of single scattering, <= 1.
+    Midpoint quadrature on 96 x 192 cells in (theta, phi) of the backend's eval; the quadrature error is taken as twice the change of the
+    float64 definition's integral between this grid and the 192 x 384 one, + 1e-4.
+    Measured on the oracle: integrals 0.33 (alpha 1, cos 0.9) ... 0.97 (alpha 0.15, cos 0.9), each within 1e-5 relative of the definition's on the same grid."""
+    d1, w1 = df.hemisphere_grid(96, 192)
+    d2, w2 = df.hemisphere_grid(192, 384)
+    worst = {}
+    for alpha, cv in ENERGY_PAIRS:
+        V = np.array([math.sqrt(1 - cv * cv), 0.0, cv])
+        one = np.ones((len(d1), 3))
+        got = be.ggx_eval(one, np.full(len(d1), alpha), d1, np.tile(V, (len(d1), 1))).astype(f64)[:, 0]
+        q_got = float((got * w1).sum())
+        q1 = float((df.ggx_eval_cos(one, np.full(len(d1), alpha), d1, np.tile(V, (len(d1), 1)))[0][:, 0] * w1).sum())
+        q2 = float((df.ggx_eval_cos(np.ones((len(d2), 3)), np.full(len(d2), alpha), d2, np.tile(V, (len(d2), 1)))[0][:, 0] * w2).sum())
+        quad_err = 2 * abs(q1 - q2) + 1e-4
+        assert q_got <= 1.0 + quad_err, (alpha, cv, q_got)
+        assert abs(q_got - q1) <= 1e-5 * q1, (alpha, cv, q_got, q1)               # binary32 inputs of the grid + the eval bound, summed
+        assert q2 > 0.3
+        worst[f"a{alpha}_c{cv}"] = q_got
+    report(f"{be.name}/ggx_energy", **worst)
+
+
+def test_ggx_eval(be, mirt):
+    check_ggx_eval(be, mirt)
+
+
+def test_ggx_sample(be, mirt):
+    check_ggx_sample(be, mirt)
+
+
+def test_ggx_energy(be, mirt):
+    check_ggx_energy(be, mirt)
+
+
+# ---- D. camera, sky, resolve ----------------------------------------------------------------------------------------------------
+def turned_camera_scene(mirt):
+    """default9 seen through a camera whose orientation is set as a quaternion outright (a roll as well as a turn)."""
+    sc = mirt.scene.default9()
+    sc.camera.focal_length = 20.0
+    q = np.array([0.2, -0.5, 0.3, 0.7]); sc.camera.orient = (q / np.linalg.norm(q)).astype(f32)
+    return sc
+
+
+def check_raygen(be, mirt):
+    """Every camera ray, projected through the float64 pinhole (conjugate of the orientation quaternion, image plane at
+    z = -(height / 2) focal / 12), lands in the footprint [x, x + 1] x [y, y + 1] of the pixel that its slot stands for (tile-major slots,
+    16 x 16 tiles), within 32u of the image-plane distance; it starts at the eye and looks forward.  The jitter fills the footprint: its
+    mean is 1/2 within 5 sigma of a uniform variable.
+    Measured on the oracle: no ray outside its footprint at all (tolerance 4.7e-4 px at 96 x 64, focal 40)."""
+    worst = 0.0
+    for make, w, h in ((mirt.scene.default9, 96, 64), (lambda: turned_camera_scene(mirt), 64, 96)):
+        for acc in (1, 2, 77):
+            sc = make()
+            p, d = be.raygen(sc, w, h, acc)
+            cam = sc.camera
+            z = df.lens_z(h, cam.focal_length)
+            assert abs(float(cam.z) - z) <= 4 * u * abs(z)
+            assert (p == np.asarray(cam.pos, dtype=f32)[:, None]).all()
+            d64 = d.T.astype(f64)
+            assert np.abs(np.linalg.norm(d64, axis=1) - 1.0).max() <= 4 * u
+            x, y, lz = df.project(d64, cam.orient, w / 2.0, h / 2.0, z)
+            px, py = df.pixel_of_slot(np.arange(len(x)), w)
+            assert (lz < 0).all()
+            tol = PROJECT_REL * math.hypot(abs(z), w)
+            out = max((px - x).max(), (x - px - 1).max(), (py - y).max(), (y - py - 1).max())
+            assert out <= tol, f"{w}x{h} accumulation {acc}: a ray leaves its pixel by {out:.3g} px (tolerance {tol:.3g})"
+            worst = max(worst, out)
+            fx, fy = x - px, y - py
+            five_sigma = SIGMA * math.sqrt(1.0 / 12.0 / len(x))
+            assert abs(fx.mean() - 0.5) <= five_sigma and abs(fy.mean() - 0.5) <= five_sigma
+            assert sorted(set(zip(px.tolist(), py.tolist()))) == [(a, b) for a in range(w) for b in range(h)]
+    report(f"{be.name}/raygen", worst_excursion_px=float(worst))
+
+
+def test_raygen(be, mirt):
+    check_raygen(be, mirt)
+
+
+SKY_H, SKY_W = 19, 37
+CUBE_FACES = [(0, 0, 0, 1), (0, 1, 0, 0), (0, math.sqrt(0.5), 0, math.sqrt(0.5)), (0, -math.sqrt(0.5), 0, math.sqrt(0.5)),
+              (math.sqrt(0.5), 0, 0, math.sqrt(0.5)), (-math.sqrt(0.5), 0, 0, math.sqrt(0.5))]      # orientations (x, y, z, w): -z, +z, -x, +x, +y, -y
+
+
+def check_sky(be, mirt, variants=(0,)):
+    """The sky lookup through the path: six 128 x 128 cameras with a 90 degree field (focal 12) cover the sphere as a cube map - 98 304 unit
+    directions - over a 19 x 37 image whose texel (row, column) holds (row + 1, column + 1, id); one bounce, one bucket, one accumulation,
+    the only sphere behind the camera, so each accumulator word is the texel its ray picked.  It must be the float64 equirect texel (D2)
+    unless the direction lies within the asserted fast_atan2 / fast_asin error (2e-3 / 1e-3 rad) of a texel edge.  Cap: the solid-angle-
+    weighted share of set-aside rays (a pixel of a 90 degree pinhole subtends cos^3 of its angle to the axis) <= the share of the sphere
+    those bands cover for this image size, computed below, + 10 %.
+    Measured on the oracle: 3.48 % set aside against a band area of 3.45 %; wrong texels outside the bands 0 (inside them 16 of 98 304)."""
+    S = mirt.scene
+    hdri = np.zeros((SKY_H, SKY_W, 4), dtype=f32)
+    hdri[..., 0] = np.arange(1, SKY_H + 1)[:, None]; hdri[..., 1] = np.arange(1, SKY_W + 1)[None, :]
+    hdri[..., 2] = (np.arange(SKY_H)[:, None] * SKY_W + np.arange(SKY_W)[None, :] + 1); hdri[..., 3] = 1.0
+    w = h = 128
+    bw_phi = ATAN2_ABS + 1e-4 * 2 * math.pi / (SKY_W - 1)                        # + 1e-4 texel for the binary32 scale-and-add
+    bw_lat = ASIN_ABS + 1e-4 * math.pi / (SKY_H - 1)
+    for variant in variants:
+        n_aside = w_aside = w_all = 0.0
+        wrong_inside = 0
+        for q in CUBE_FACES:
+            cam = S.Camera(eye=(0.0, 0.0, 0.0), direction=(0.0, 0.0, -1.0), focal_length=12.0)
+            cam.orient = np.asarray(q, dtype=f32)
+            fwd = df.rotation_of_quaternion(np.asarray(q, dtype=f64)[None])[0] @ np.array([0.0, 0.0, -1.0])
+            geo = np.array([S._sphere(tuple(-3.0 * fwd), 0.01, 0)], dtype=S.SPHERE)
+            sc = S.Scene(geo, np.array([S._material(albedo=(0.5, 0.5, 0.5))], dtype=S.MATERIAL), cam, np.ones(3, dtype=f32), hdri=hdri, name="sky_face")
+            res = be.render(sc, w, h, 1, max_bounces=1, buckets=1, variant=variant)
+            assert res["counters"]["terminated"] == w * h and res["counters"]["rays"] == w * h
+            p, d = be.raygen(sc, w, h, 1, max_bounces=1)
+            d64 = d.T.astype(f64)
+            acc = res["acc"][:, 0]                                               # [tile][rgb][256]
+            row = acc[:, 0].reshape(-1).astype(np.int64) - 1; col = acc[:, 1].reshape(-1).astype(np.int64) - 1
+            assert (acc[:, 2].reshape(-1) == row * SKY_W + col + 1).all()        # one texel, all three channels from it
+            c64, r64, ex, ey = df.equirect_texel(d64, SKY_W, SKY_H)
+            phi = np.arctan2(d64[:, 2], d64[:, 0]); lat = np.arcsin(np.clip(d64[:, 1], -1, 1))
+            edge_phi = (np.arange(SKY_W) / (SKY_W - 1) - 0.5) * 2 * np.pi        # ex = k
+            edge_lat = (0.5 - np.arange(SKY_H) / (SKY_H - 1)) * np.pi            # ey = k
+            d_phi = np.abs((phi[:, None] - edge_phi[None, :] + np.pi) % (2 * np.pi) - np.pi).min(axis=1)
+            d_lat = np.abs(lat[:, None] - edge_lat[None, :]).min(axis=1)
+            aside = (d_phi <= bw_phi) | (d_lat <= bw_lat)
+            wrong = (row != r64) | (col != c64)
+            assert not (wrong & ~aside).any(), f"variant {variant} face {q}: {int((wrong & ~aside).sum())} wrong texels away from any edge"
+            assert (np.abs(row - r64) <= 1).all() and (np.minimum(np.abs(col - c64), SKY_W - 1 - np.abs(col - c64)) <= 1).all()
+            local_z = np.abs(d64 @ fwd)
+            weight = local_z ** 3
+            n_aside += aside.sum(); w_aside += weight[aside].sum(); w_all += weight.sum(); wrong_inside += int(wrong.sum())
+        share_phi = (SKY_W - 1) * 2 * bw_phi / (2 * math.pi)                     # columns 0 and W - 1 share the meridian phi = +-pi
+        share_lat = sum(math.sin(min(l + bw_lat, math.pi / 2)) - math.sin(max(l - bw_lat, -math.pi / 2)) for l in edge_lat) / 2.0
+        band_area = share_phi + share_lat - share_phi * share_lat                # bands in phi and in latitude are independent sets on the sphere
+        report(f"{be.name}/sky/variant{variant}", set_aside=float(w_aside / w_all), band_area=float(band_area), wrong_inside_bands=wrong_inside)
+        assert w_aside / w_all <= 1.1 * band_area
+
+
+def test_sky_lookup(be, mirt):
+    check_sky(be, mirt, variants=(0, 1))
+
+
+def check_resolve(be, mirt, variants=(0,)):
+    """Render() against the frame recomputed from the accumulator alone in float64: per-bucket means, np.median across the buckets,
+    exposure 1.5, the published ACES fit, alpha 1; k = 3, 4, 5, 16 buckets, two accumulations per bucket.  Even k: the reference has only
+    the five-input network (Sampling.hpp:13-21, k = 5 fixed); other k is this project's generalisation (Q19) and even k takes the mean of
+    the two middle values, which is np.median's convention.  Bound 32u absolute on outputs in [0, 1] (derived at RESOLVE_ABS).
+    Measured on the oracle: largest difference 2.7e-7 (k = 4); the mean instead of the median would move this frame by 0.71 ... 0.98."""
+    for variant in variants:
+        for k in (3, 4, 5, 16):
+            sc = mirt.scene.synthetic(8, ambient=0.5)
+            sc.camera.exposure = 1.5
+            res = be.render(sc, 64, 64, 2 * k, max_bounces=4, buckets=k, variant=variant)
+            want = df.resolve(res["acc"], 2 * k, 1.5, 64, 64)
+            got = res["frame"].astype(f64)
+            err = np.abs(got - want).max()
+            assert err <= RESOLVE_ABS, f"k={k}: frame differs from the float64 resolve by {err:.3g}"
+            assert (got[..., 3] == 1.0).all()
+            mean_rgb = df.aces_fitted(np.moveaxis(res["acc"].astype(f64).sum(axis=1) / (2 * k) * 1.5, 1, 2).reshape(-1, 3))
+            x, y = df.pixel_of_slot(np.arange(len(mean_rgb)), 64)
+            by_mean = np.abs(want[y, x, :3] - mean_rgb).max()
+            assert by_mean > 0.05                                                # the input tells the median from the mean
+            report(f"{be.name}/resolve/variant{variant}/k{k}", err=float(err), mean_instead_of_median=float(by_mean))
+
+
+def test_resolve(be, mirt):
+    check_resolve(be, mirt, variants=(0,))
+
+
+def one_sphere(mirt, albedo=(0.5, 0.5, 0.5), emission=(0, 0, 0), eye_z=1.25, focal=35.0, ambient=1.0, hdri=None):
+    S = mirt.scene
+    cam = S.Camera(eye=(0.0, 0.0, eye_z), direction=(0.0, 0.0, -1.0), focal_length=focal, exposure=1.0)
+    sc = S.Scene(np.array([S._sphere((0, 0, 0), 1.0, 0)], dtype=S.SPHERE), np.array([S._material(albedo=albedo, emission=emission)], dtype=S.MATERIAL),
+                 cam, np.full(3, ambient, dtype=f32), name="one_sphere")
+    if hdri is not None:
+        sc.hdri = np.asarray(hdri, dtype=f32)
+    return sc
+
+
+def footprint_depth_bounds(w, h, focal, eye_z):
+    """Per pixel of a pinhole on the axis of a unit sphere: smallest and largest first-hit distance over the footprint [x, x+1] x [y, y+1].
+    The distance grows with the angle to the axis, i.e. with the image-plane distance from the centre, so the extremes sit at the
+    footprint's points nearest to and farthest from the centre.  -> lo, hi (h, w); hi = inf where the footprint leaves the silhouette."""
+    z = df.lens_z(h, focal)
+    xs, ys = np.meshgrid(np.arange(w, dtype=f64), np.arange(h, dtype=f64))
+    cx, cy = w / 2.0, h / 2.0
+    nx, ny = np.clip(cx, xs, xs + 1), np.clip(cy, ys, ys + 1)
+    fx, fy = np.where(np.abs(xs - cx) > np.abs(xs + 1 - cx), xs, xs + 1), np.where(np.abs(ys - cy) > np.abs(ys + 1 - cy), ys, ys + 1)
+    lo = df.sphere_depth_normal(nx, ny, cx, cy, z, eye_z)[0]
+    hi = df.sphere_depth_normal(fx, fy, cx, cy, z, eye_z)[0]
+    return lo, hi
+
+
+def footprint_root_error(be, sc, w, h, accs, max_bounces=16):
+    """Per pixel, the largest part-A bound (definitions.root_of) of the distance along any of its camera rays of accumulations `accs`:
+    towards the silhouette the discriminant cancels and the bound grows.  -> (h, w), and the rays per accumulation."""
+    E = np.zeros((h, w)); rays = []
+    c, r2 = np.zeros((1, 3)), np.ones(1)
+    for acc in accs:
+        p, d = be.raygen(sc, w, h, acc, max_bounces=max_bounces)
+        px, py = df.pixel_of_slot(np.arange(p.shape[1]), w)
+        e = df.root_of(p.T.astype(f64), d.T.astype(f64), c, r2, np.zeros(p.shape[1], dtype=np.int64))[2]
+        np.maximum.at(E, (py, px), e)
+        rays.append((p, d, px, py))
+    return E, rays
+
+
+def check_first_hit_depth(be, mirt):
+    """Camera rays of the one-sphere scene (eye (0, 0, 6), 32 x 32) traced by the backend: each sample's distance lies between the float64
+    ray-sphere distances at the nearest and farthest points of its pixel's footprint, +- the part-A bound of that ray; a footprint wholly
+    outside the silhouette never hits, one wholly inside always does."""
+    sc = one_sphere(mirt, eye_z=6.0, focal=50.0)
+    w = h = 32
+    lo, hi = footprint_depth_bounds(w, h, 50.0, 6.0)
+    E, rays = footprint_root_error(be, sc, w, h, (1, 2, 3))
+    for p, d, px, py in rays:
+        for label, closest, _ in be.tracers(sc):
+            t, prim = closest(p, d)
+            t = np.where(prim >= 0, t.astype(f64), np.inf)
+            assert (t >= lo[py, px] - E[py, px]).all() and (t <= hi[py, px] + E[py, px]).all(), label
+            assert np.isfinite(t).sum() > 50 and np.isinf(t).sum() > 50
+
+
+def test_first_hit_depth(be, mirt):
+    check_first_hit_depth(be, mirt)
+
+
+# ---- E. whole path --------------------------------------------------------------------------------------------------------------
+FILLING = [((0.6, 0.6, 0.6), "grey"), ((0.8, 0.4, 0.2), "red"), ((0.2, 0.4, 0.8), "blue")]
+
+
+def check_filling_sphere(be, mirt, w, h, n_acc, variant=0):
+    """Scene 1: a unit sphere fills the frame (eye (0, 0, 1.25), focal 35), unit sky, no light, 8 bounces.  Every path hits, survives the
+    roulette with p = max(albedo) (Q6), leaves the convex sphere and meets the sky with throughput albedo / p - of which the miss shader
+    takes the RED channel for all three (Q10).  Hence: the three channels are the same words; the mean is p * albedo.r / p = albedo.r;
+    `rays` = n (1 + p) in expectation; `terminated` = n exactly; `shadow_rays` = 0 (Q12 guard).  Bounds: 5 sigma, sigma from the Bernoulli
+    variance p (1 - p).
+    Measured on the oracle, z of the mean = z of `rays` (each survivor is one more ray): 64 x 64 x 50: grey +2.22, red +3.02, blue +3.02;
+    256 x 256 x 20: grey +0.002, red +0.90, blue +0.90 (red and blue share every random number).  z does not grow with
+    the sample count, so the +3 at the small size is a draw, not a bias of the generator, make_unit_float or the roulette."""
+    n = w * h * n_acc
+    for albedo, label in FILLING:
+        res = be.render(one_sphere(mirt, albedo=albedo), w, h, n_acc, max_bounces=8, variant=variant)
+        acc = res["acc"]
+        assert np.array_equal(ob.bits(acc[:, :, 0]), ob.bits(acc[:, :, 1])) and np.array_equal(ob.bits(acc[:, :, 0]), ob.bits(acc[:, :, 2]))   # Q10
+        p = max(albedo)
+        value = albedo[0] / p
+        mean = acc[:, :, 0].astype(f64).sum() / n
+        z_mean = (mean - p * value) / (value * math.sqrt(p * (1 - p) / n))
+        c = res["counters"]
+        z_rays = (c["rays"] - n * (1 + p)) / math.sqrt(n * p * (1 - p))
+        report(f"{be.name}/filling/{w}x{h}x{n_acc}/{label}", mean=float(mean), z_mean=float(z_mean), rays=c["rays"], z_rays=float(z_rays))
+        assert c["terminated"] == n and c["shadow_rays"] == 0
+        assert abs(z_mean) <= SIGMA, f"{label}: mean {mean:.6f} is {z_mean:+.2f} sigma from {p * value}"
+        assert abs(z_rays) <= SIGMA, f"{label}: rays {c['rays']} is {z_rays:+.2f} sigma from {n * (1 + p)}"
+
+
+@pytest.mark.parametrize("w,h,n_acc", [(64, 64, 50), (256, 256, 20)])
+def test_filling_sphere(be, mirt, w, h, n_acc):
+    check_filling_sphere(be, mirt, w, h, n_acc)
+
+
+def check_two_tone_sky(be, mirt, variant=0):
+    """Scene 2: the same grey sphere (0.6), 100 accumulations, under a sky that is 1 above the horizon and 0 below: a 3 x 1 image with rows (1, 0, 0) - under
+    D2 a two-row image would show its second row at y = -1 only.  A surviving path leaves along a cosine-weighted direction about the hit
+    normal n; the share of those with y > 0 is (1 + n.y) / 2 (checked against quadrature here).  Per pixel the expectation is
+    0.6 (1 + n.y) / 2, n averaged over the footprint on a 4 x 4 grid; the upper and the lower half of the image are each held
+    to 5 sigma with the analytic variance of the three-valued sample.  Pins hemisphere + tangent frame + sky row together.
+    Measured on the oracle: z = +1.6 (upper half), +1.5 (lower half); the halves' expectations are 18 sigma apart."""
+    for ny in (-0.7, 0.0, 0.35, 1.0):
+        nrm = np.array([0.3, ny, math.sqrt(max(0.0, 1 - 0.09 - ny * ny))]) if abs(ny) < 1 else np.array([0.0, ny, 0.0])
+        assert abs(df.cosine_upper_share_quadrature(nrm) - df.cosine_upper_share(nrm[1] / np.linalg.norm(nrm))) <= 2e-3
+    w = h = 64; n_acc = 100; rho, A, B = 0.6, 1.0, 0.0
+    hdri = np.ones((3, 1, 4), dtype=f32); hdri[1:, :, :3] = B
+    res = be.render(one_sphere(mirt, albedo=(rho, rho, rho), hdri=hdri), w, h, n_acc, max_bounces=8, variant=variant)
+    sub = (np.arange(4) + 0.5) / 4
+    xs = (np.arange(w)[None, :, None, None] + sub[None, None, :, None]) + np.zeros((h, 1, 1, 4))
+    ys = (np.arange(h)[:, None, None, None] + sub[None, None, None, :]) + np.zeros((1, w, 4, 1))
+    t, nrm = df.sphere_depth_normal(xs, ys, w / 2.0, h / 2.0, df.lens_z(h, 35.0), 1.25)
+    assert np.isfinite(t).all()
+    F = df.cosine_upper_share(nrm[..., 1]).mean(axis=(2, 3))
+    expect = rho * (B + (A - B) * F)
+    var = rho * (F * A * A + (1 - F) * B * B) - expect ** 2
+    px, py = df.pixel_of_slot(np.arange(w * h), w)
+    img = np.zeros((h, w)); img[py, px] = res["acc"][:, :, 0].astype(f64).sum(axis=1).reshape(-1) / n_acc
+    zs = {}
+    for name, rows in (("upper", slice(h // 2, h)), ("lower", slice(0, h // 2))):
+        sigma = math.sqrt(var[rows].sum() / n_acc) / expect[rows].size
+        zs[name] = float((img[rows].mean() - expect[rows].mean()) / sigma)
+    sep = float((expect[h // 2:].mean() - expect[: h // 2].mean()) / (math.sqrt(var.sum() / n_acc) / (expect.size / 2)))
+    report(f"{be.name}/two_tone", z_upper=zs["upper"], z_lower=zs["lower"], halves_apart_in_sigma=sep)
+    assert abs(zs["upper"]) <= SIGMA and abs(zs["lower"]) <= SIGMA, zs
+    assert sep > 2 * SIGMA                                                        # a swapped sky would fail both halves
+
+
+def test_two_tone_sky(be, mirt):
+    check_two_tone_sky(be, mirt)
+
+
+def check_emissive_sphere(be, mirt, variant=0):
+    """Scene 3: one emissive, black sphere fills the frame, MIS on, black sky.  At bounce 0 the emission is added with throughput 1 (Q9 leaves
+    bounce 0 alone); the only light is the sphere just hit, so no shadow ray is cast; nothing else can contribute.  Every bucket word is
+    therefore (accumulations in the bucket) x emission exactly, for 2 and for 8 bounces.  With ONE bounce the hit is on the last bounce and
+    the path is dropped with its radiance (Q5): all zeros, nothing terminated."""
+    em = (2.0, 0.5, 4.0)
+    for mb in (2, 8):
+        res = be.render(one_sphere(mirt, albedo=(0, 0, 0), emission=em, ambient=0.0), 64, 64, 10, max_bounces=mb, variant=variant)
+        acc = res["acc"]
+        for c in range(3):
+            assert (acc[:, :, c] == f32(2 * em[c])).all(), (mb, c)
+        assert res["counters"]["shadow_rays"] == 0 and res["counters"]["terminated"] == 64 * 64 * 10
+    res = be.render(one_sphere(mirt, albedo=(0, 0, 0), emission=em, ambient=0.0), 64, 64, 10, max_bounces=1, variant=variant)
+    assert not res["acc"].any() and res["counters"]["terminated"] == 0             # Q5
+
+
+def test_emissive_sphere(be, mirt):
+    check_emissive_sphere(be, mirt)
