@@ -60,11 +60,11 @@ struct PipeSlot {
 	DeviceBuffer counts;             // ray queue counters, work counters and fat-ray counts of one batch: addressed through BatchCounters only
 	DeviceBuffer contrib;            // this batch's path radiances, [tile][slot][256][rgb] (kernels.hpp contrib_index)
 	DeviceBuffer fat;                // fat-ray index lists: [closest kFatCapacity][shadow kFatCapacity]
-	DeviceBuffer cand;               // per local pixel: candidate spheres of its bundle of camera rays (k_primary_cand), kCandStride words
 	hipEvent_t batch_done = nullptr; // recorded on `stream` after the batch's last kernel
 	hipEvent_t merged = nullptr;     // recorded on the main stream after the batch was merged (slot reusable)
 	hipEvent_t aov_done = nullptr;   // mirt_set_aov(1) only: recorded on `stream` after the batch's k_first_hit_aov (created by the first such batch)
 	bool in_use = false;
+	uint64_t cand_gen = 0;           // the build of the context's candidate lists this slot's stream has waited for (mirt_ctx::cand_gen)
 	StreamBuf stream_buf[2]{};
 	ShadowBuf shadow_buf{};
 	HitRec* hit = nullptr;           // RayStream<>::Hit: one 8-B {tfar, primID} record per ray (two planes' worth of the arena)
@@ -94,6 +94,15 @@ struct mirt_ctx {
 	bool gloss_decay_dev_valid = false;
 	CameraParams camera{};
 	uint32_t bvh_depth = 0;
+	// Candidate lists of the camera rays (k_primary_cand, kernels.hpp kCollect).  They are a function of the scene and its tree, the camera, the image
+	// size and the tiles this context owns — not of the accumulation index, the batch size or any random draw — so the first batch that wants them
+	// builds them on the main stream and every later batch on every slot reads them, until a call that changes one of those clears cand_valid.
+	DeviceBuffer cand;               // per local pixel: candidate spheres of its bundle of camera rays, kCandStride words
+	DeviceBuffer cand_listed;        // the local pixels without a list (more than kCandMax candidates), in any order: k_trace<kPrimaryList> traces all their samples
+	DeviceBuffer cand_words;         // the build's own counter words: addressed through CandWords only
+	hipEvent_t cand_built = nullptr; // recorded on the main stream after the latest build; batches on other streams wait for it
+	uint64_t cand_gen = 0;           // number of builds so far
+	bool cand_valid = false;
 	bool allow_half = true;           // binary16 records when adequate (mirt_debug_set(ctx, "half_boxes", 0) forces f32)
 
 	// frame state
@@ -222,7 +231,7 @@ hipError_t sync_all(mirt_ctx* c) {
 constexpr uint32_t kQueueWords = kSegs * kSegPitch;     // one ray queue's counters: one per 128-B line (kernels.hpp "ray queues"; k_shade's appends are sensitive to it)
 constexpr uint32_t kFatCapacity = 1u << 16;   // rays per list and launch that may take the brute-force detour (a few per million qualify)
 // The counter words of one batch of nb bounces (PipeSlot::counts; the debug trace entry points keep a private one with nb = 1), zeroed before
-// the batch's first launch: 2 nb + 2 queues of kQueueWords, then 4 nb + 3 single words (+ 5 spare).  Every offset is stated here and nowhere else.
+// the batch's first launch: 2 nb + 2 queues of kQueueWords, then 4 nb single words (+ 8 spare).  Every offset is stated here and nowhere else.
 struct BatchCounters {
 	uint32_t* w; uint32_t nb, seg_cap;
 	static size_t words(uint32_t nb) { return static_cast<size_t>(2 * nb + 2) * kQueueWords + static_cast<size_t>(nb) * 4 + 8; }
@@ -236,9 +245,14 @@ struct BatchCounters {
 	// per-launch fat-ray counts; `lists`: the slot's index lists, [closest kFatCapacity][shadow kFatCapacity]
 	FatList fat_closest(uint32_t b, uint32_t* lists) const { return FatList{ word(2 * nb + b), lists, kFatCapacity }; }
 	FatList fat_shadow(uint32_t b, uint32_t* lists) const { return FatList{ word(3 * nb + b), lists + kFatCapacity, kFatCapacity }; }
-	uint32_t* cand_work() const { return word(4 * nb); }                     // work counter of k_primary_cand
-	uint32_t* unused_fat_count() const { return word(4 * nb + 1); }          // count of the zero-capacity list k_primary_cand is handed
-	uint32_t* listed_pixels() const { return word(4 * nb + 2); }             // pixels without a candidate list (their list: in.path of bounce 0)
+};
+// The counter words of one build of the candidate lists (mirt_ctx::cand_words), zeroed before it; listed_pixels is read by every batch that uses the lists.
+struct CandWords {
+	uint32_t* w;
+	static constexpr size_t kWords = 4;
+	uint32_t* work() const { return w; }                                     // work counter of k_primary_cand
+	uint32_t* unused_fat_count() const { return w + 1; }                     // count of the zero-capacity list k_primary_cand is handed
+	uint32_t* listed_pixels() const { return w + 2; }                        // pixels without a candidate list (their list: mirt_ctx::cand_listed)
 };
 BatchCounters batch_counters(const mirt_ctx* c, const PipeSlot& sl) { return BatchCounters{ sl.counts.as<uint32_t>(), c->policy.max_bounces, c->seg_cap }; }
 uint32_t wanted_slots(const mirt_ctx* c) {
@@ -286,7 +300,7 @@ int ensure_streams(mirt_ctx* c) {
 	c->aov_prev = nullptr;                                                   // (every batch has finished; the event's slot may go away below)
 	while (c->slots.size() > want) {
 		PipeSlot& sl = c->slots.back();
-		sl.arena.release(); sl.counts.release(); sl.contrib.release(); sl.fat.release(); sl.cand.release();
+		sl.arena.release(); sl.counts.release(); sl.contrib.release(); sl.fat.release();
 		if (sl.batch_done) (void)hipEventDestroy(sl.batch_done);
 		if (sl.merged) (void)hipEventDestroy(sl.merged);
 		if (sl.aov_done) (void)hipEventDestroy(sl.aov_done);
@@ -308,7 +322,6 @@ int ensure_streams(mirt_ctx* c) {
 		const char* what = "ray streams";
 		if (e == hipSuccess) { e = sl.counts.ensure(BatchCounters::words(nb) * sizeof(uint32_t)); what = "queue counters"; }
 		if (e == hipSuccess) { e = sl.fat.ensure(2u * kFatCapacity * sizeof(uint32_t)); what = "fat-ray lists"; }
-		if (e == hipSuccess) { e = sl.cand.ensure(static_cast<size_t>(n_pix) * kCandStride * sizeof(uint32_t)); what = "candidate lists"; }
 		if (e == hipSuccess) { e = sl.contrib.ensure(acc_bytes); what = "contribution buffer"; }
 		if (e != hipSuccess) {
 			// not enough device memory after all (someone else took it meanwhile — another context or process planning against the same
@@ -452,7 +465,7 @@ struct TraceLaunch {
 	ShadowBuf sh; ShadowSink sink;                   // shadow rays and where their outcome goes
 	Queue shadow_queue; uint32_t* shadow_work;
 	FatList fat_closest, fat_shadow;
-	const uint32_t* listed_pixels;                   // kPrimaryList: count of the pixels listed in in.path
+	const uint32_t* listed_pixels;                   // kPrimaryList: count of the pixels listed in in.path (NULL otherwise)
 	DevCounters* ctr;
 };
 // k_trace<count, primary> over n_rays, then (with a tree) the few rays too "fat" for it: brute force, one workgroup each.
@@ -476,6 +489,28 @@ int launch_tile_stream(mirt_ctx* c, hipStream_t st, const SceneDev& sc, const Fr
 	Bracket t(c, MIRT_K_TRACE, st);
 	hipLaunchKernelGGL(kTileStream[c->policy.brdf != 0], dim3(c->n_tiles * batch_n), dim3(kTileSize), 0, st, sc, fp, contrib, ctr, c->mat_ggx.as<float4>(),
 	                   c->gloss_decay_dev.as<float>(), static_cast<uint32_t>(c->gloss_decay.size()), count ? 1u : 0u);
+	return MIRT_OK;
+}
+
+// Builds the context's candidate lists (mirt_ctx::cand ...) for the current scene, camera and tile set: one cone traversal per local pixel
+// (kernels.hpp kCollect).  The build runs on the main stream.  Every batch launched so far is ahead of it there — the main stream waits for a
+// batch's batch_done before it merges the batch — so a rebuild cannot overtake a batch that still reads the previous lists; batches on
+// other streams wait for cand_built (launch_batch).
+int build_primary_lists(mirt_ctx* c, const SceneDev& sc, const FrameParams& fp, bool count) {
+	HIP_TRY(c, c->cand.ensure(static_cast<size_t>(fp.n_pix) * kCandStride * sizeof(uint32_t)));
+	HIP_TRY(c, c->cand_listed.ensure(static_cast<size_t>(fp.n_pix) * sizeof(uint32_t)));        // at most every pixel is without a list
+	HIP_TRY(c, c->cand_words.ensure(CandWords::kWords * sizeof(uint32_t)));
+	if (!c->cand_built) HIP_TRY(c, hipEventCreateWithFlags(&c->cand_built, hipEventDisableTiming));
+	const CandWords cw{ c->cand_words.as<uint32_t>() };
+	HIP_TRY(c, hipMemsetAsync(cw.w, 0, CandWords::kWords * sizeof(uint32_t), c->stream));
+	{ Bracket t(c, MIRT_K_TRACE);
+	  const FatList none{ cw.unused_fat_count(), nullptr, 0u };
+	  hipLaunchKernelGGL(kPrimaryCand[!count], dim3(trace_grid(c, fp.n_pix)), dim3(kTraceBlock), trace_lds(c), c->stream, sc, fp, c->cand.as<uint32_t>(), bundle_half_angle(c),
+	                     cw.work(), none, c->counters.as<DevCounters>(), c->cand_listed.as<uint32_t>(), cw.listed_pixels()); }
+	HIP_TRY(c, hipGetLastError());
+	HIP_TRY(c, hipEventRecord(c->cand_built, c->stream));
+	c->cand_gen++;
+	c->cand_valid = true;
 	return MIRT_OK;
 }
 
@@ -519,7 +554,7 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 	// (The half-angle bound assumes view.orient rotates: a non-unit quaternion, which the reference's View never holds (Camera.hpp:48-50),
 	// would shear the image plane — such a camera gets no lists.)
 	const float qn = c->camera.orient[0] * c->camera.orient[0] + c->camera.orient[1] * c->camera.orient[1] + c->camera.orient[2] * c->camera.orient[2] + c->camera.orient[3] * c->camera.orient[3];
-	const bool bundle = c->policy.use_bvh && c->scene.n_recs != 0 && !c->policy.trace_primary_rays && batch_n >= 3 && c->camera.z != 0.0f && std::fabs(qn - 1.0f) < 1e-4f;
+	const bool bundle = c->policy.use_bvh && c->scene.n_recs != 0 && !c->policy.trace_primary_rays && batch_n >= 3 && c->camera.z != 0.0f && std::fabs(qn - 1.0f) < 1e-4f && !c->stream_order;
 	DevCounters* ctr = c->counters.as<DevCounters>();
 	const float4* mat_ggx = c->mat_ggx.as<float4>();
 	float* contrib = sl.contrib.as<float>();                                      // slot k of the buffer = accumulation acc_base + k + 1
@@ -538,6 +573,13 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 	if (c->debug_poison_contrib)
 		HIP_TRY(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sl.contrib.ptr), 0x7fc0deadu, sl.contrib.bytes / sizeof(float), st));   // a quiet NaN
 	HIP_TRY(c, hipMemsetAsync(bc.w, 0, BatchCounters::words(nb) * sizeof(uint32_t), st));
+	if (bundle) {
+		// the lists outlive the batch: built by the first batch that wants them, read by all after it.  (A counting pass builds them every time: its
+		// box and sphere counts are those of a batch that does all of its work.)
+		if (!c->cand_valid || count) { const int r = build_primary_lists(c, sc, fp, count); if (r) return r; }
+		if (pipelined && sl.cand_gen != c->cand_gen) { HIP_TRY(c, hipStreamWaitEvent(st, c->cand_built, 0)); sl.cand_gen = c->cand_gen; }
+	}
+	const CandWords cw{ c->cand_words.as<uint32_t>() };
 	if (c->stream_order) {
 		const int r = launch_tile_stream(c, st, sc, fp, batch_n, contrib, ctr, count);
 		if (r) return r;
@@ -550,20 +592,19 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			const bool lists = bounce == 0 && bundle;
 			{ Bracket t(c, MIRT_K_TRACE, st);
 			  if (lists) {
-			    // camera rays through per-pixel candidate lists (kernels.hpp kCollect): one cone traversal per pixel, then k_primary_hits intersects every
-			    // sample with its pixel's list.  Pixels without a list are listed in in.path (count: listed_pixels) and all their samples traced like any other ray.
-			    const FatList none{ bc.unused_fat_count(), fat_lists, 0u };
-			    hipLaunchKernelGGL(kPrimaryCand[!count], dim3(trace_grid(c, fp.n_pix)), dim3(kTraceBlock), trace_lds(c), st, sc, fp, sl.cand.as<uint32_t>(), bundle_half_angle(c),
-			                       bc.cand_work(), none, ctr, in.path, bc.listed_pixels());
+			    // camera rays through the per-pixel candidate lists (kernels.hpp kCollect): k_primary_hits intersects every sample with its pixel's list.
+			    // Pixels without a list are listed in cand_listed (count: listed_pixels) and all their samples traced like any other ray.
 			    const uint32_t hgrid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
-			    hipLaunchKernelGGL(kPrimaryHits[!count], dim3(hgrid), dim3(kBlock), 0, st, sc, fp, sl.cand.as<uint32_t>(), sl.hit, ctr);
+			    hipLaunchKernelGGL(kPrimaryHits[!count], dim3(hgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr);
 			  }
 			  // the adds of bounce-1 that waited for occlusion land in the paths' contribution words before k_shade adds this bounce's terms;
 			  // a surviving path's record finds its origin and its path id in stream `in` (= out of bounce-1)
 			  const ShadowSink sink{ in.path, in.px, in.py, in.pz, contrib, batch_n, fp.pix_bits, nullptr };
-			  const TraceLaunch tl{ in, sl.hit, lists ? Queue{ bc.listed_pixels(), 0u } : bc.stream_queue(bounce), bc.closest_work(bounce),      // kPrimaryList: n[0] = listed pixels
+			  StreamBuf rays = in;
+			  if (lists) rays.path = c->cand_listed.as<uint32_t>();     // kPrimaryList reads nothing else of the stream: camera rays are functions of their index
+			  const TraceLaunch tl{ rays, sl.hit, lists ? Queue{ cw.listed_pixels(), 0u } : bc.stream_queue(bounce), bc.closest_work(bounce),      // kPrimaryList: n[0] = listed pixels
 			                        sl.shadow_buf, sink, shadow_pending ? bc.shadow_queue(bounce - 1) : bc.empty_queue(), bc.shadow_work(shadow_pending ? bounce - 1 : 0),
-			                        bc.fat_closest(bounce, fat_lists), bc.fat_shadow(bounce, fat_lists), bc.listed_pixels(), ctr };
+			                        bc.fat_closest(bounce, fat_lists), bc.fat_shadow(bounce, fat_lists), lists ? cw.listed_pixels() : nullptr, ctr };
 			  launch_trace(c, st, sc, fp, total, count, lists ? kPrimaryList : bounce == 0 ? kPrimaryAll : kPrimaryNone, tl); }
 			if (bounce == 0 && c->aov_on) { const int r = launch_first_hit_aov(c, sl, st, sc, fp); if (r) return r; }
 			{ Bracket t(c, MIRT_K_SHADE, st);
@@ -846,7 +887,7 @@ int mirt_destroy(mirt_ctx* c) {
 	(void)sync_all(c);
 	harvest(c);
 	for (PipeSlot& sl : c->slots) {
-		sl.arena.release(); sl.counts.release(); sl.contrib.release(); sl.fat.release(); sl.cand.release();
+		sl.arena.release(); sl.counts.release(); sl.contrib.release(); sl.fat.release();
 		if (sl.batch_done) (void)hipEventDestroy(sl.batch_done);
 		if (sl.merged) (void)hipEventDestroy(sl.merged);
 		if (sl.aov_done) (void)hipEventDestroy(sl.aov_done);
@@ -855,9 +896,11 @@ int mirt_destroy(mirt_ctx* c) {
 	c->slots.clear();
 	for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
 	DeviceBuffer* bufs[] = { &c->recs, &c->recs_wide, &c->spheres, &c->prim_mat, &c->light_sphere, &c->light_emit, &c->mat_albedo, &c->mat_emission,
-	                         &c->mat_ggx, &c->hdri, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev };
+	                         &c->mat_ggx, &c->hdri, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
+	                         &c->cand, &c->cand_listed, &c->cand_words };
 	for (DeviceBuffer* b : bufs) b->release();
 	if (c->frame_host) (void)hipHostFree(c->frame_host);
+	if (c->cand_built) (void)hipEventDestroy(c->cand_built);
 	if (c->stream) (void)hipStreamDestroy(c->stream);
 	delete c;
 	return MIRT_OK;
@@ -878,6 +921,7 @@ int mirt_set_scene(mirt_ctx* c, const mirt_sphere* geometry, const mirt_sphere* 
 	    (r = upload(c, c->light_sphere, t.lsp)) || (r = upload(c, c->light_emit, t.lem)) || (r = upload(c, c->mat_albedo, t.alb)) ||
 	    (r = upload(c, c->mat_emission, t.emi)) || (r = upload(c, c->mat_ggx, t.ggx)) || (r = upload(c, c->hdri, t.sky))) return r;
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	c->cand_valid = false;                                                             // spheres or tree changed (a node-only update included)
 	commit_scene(c, a, tree);
 	if ((r = plan_trace_lds(c))) return r;
 	c->have_scene = true;
@@ -895,6 +939,7 @@ int mirt_set_camera(mirt_ctx* c, const float pos[3], const float orient_xyzw[4],
 	for (int k = 0; k < 4; k++) c->camera.orient[k] = orient_xyzw[k];
 	c->camera.half_width = half_width; c->camera.half_height = half_height; c->camera.z = z; c->camera.exposure = exposure;
 	c->have_camera = true;
+	c->cand_valid = false;                                                             // every cone has moved
 	return MIRT_OK;
 }
 
@@ -910,6 +955,9 @@ int mirt_set_policy(mirt_ctx* c, const mirt_policy* p) {
 	// batch size / batches in flight are planned again only when something the plan depends on changes (a toggle like trace_primary_rays
 	// leaves the ray-stream arena, tens of GB, where it is)
 	const bool replan = p->max_batch != c->policy.max_batch || p->streams != c->policy.streams || p->buckets != c->policy.buckets || p->max_bounces != c->policy.max_bounces;
+	// what decides the tree the lists were collected from, or whether lists are used at all
+	if (p->use_bvh != c->policy.use_bvh || p->gpu_build != c->policy.gpu_build || p->reference_tree != c->policy.reference_tree || p->trace_primary_rays != c->policy.trace_primary_rays)
+		c->cand_valid = false;
 	c->policy = *p;
 	if (replan) c->planned_for = 0;
 	if (realloc_acc && c->n_tiles) { int r = alloc_accumulator(c); if (r) return r; }
@@ -952,6 +1000,7 @@ int mirt_resize(mirt_ctx* c, uint32_t width, uint32_t height) {
 	HIP_TRY(c, hipSetDevice(c->device));
 	HIP_TRY(c, sync_all(c));
 	c->width = width; c->height = height;
+	c->cand_valid = false;                                                             // other pixels
 	c->h_tiles = width / MIRT_TILE_ROOT; c->v_tiles = height / MIRT_TILE_ROOT;          // Renderer.hpp:59-60
 	c->first_tile = 0; c->n_tiles = c->h_tiles * c->v_tiles; c->run_tiles = 0; c->stride_tiles = 0;
 	HIP_TRY(c, c->framebuffer.ensure(std::max<size_t>(static_cast<size_t>(width) * height, 1) * sizeof(float4)));
@@ -973,6 +1022,7 @@ int mirt_set_tile_range(mirt_ctx* c, uint32_t first_tile, uint32_t n_tiles) {
 	HIP_TRY(c, hipSetDevice(c->device));
 	HIP_TRY(c, sync_all(c));
 	c->first_tile = first_tile; c->n_tiles = n_tiles; c->run_tiles = 0; c->stride_tiles = 0;
+	c->cand_valid = false;                                                             // other local pixels
 	return alloc_accumulator(c);
 }
 
@@ -985,6 +1035,7 @@ int mirt_set_tile_rows(mirt_ctx* c, uint32_t first_row, uint32_t row_stride) {
 	const uint32_t rows = first_row < c->v_tiles ? (c->v_tiles - first_row + row_stride - 1) / row_stride : 0u;
 	c->first_tile = first_row * c->h_tiles; c->n_tiles = rows * c->h_tiles;
 	c->run_tiles = c->h_tiles; c->stride_tiles = row_stride > 1 ? row_stride * c->h_tiles : 0u;
+	c->cand_valid = false;                                                             // other local pixels
 	return alloc_accumulator(c);
 }
 
@@ -1264,19 +1315,10 @@ int mirt_debug_primary_lists(mirt_ctx* c, uint32_t hist[10]) {
 	HIP_TRY(c, hipSetDevice(c->device));
 	if ((r = ensure_streams(c))) return r;
 	HIP_TRY(c, sync_all(c));
-	PipeSlot& sl = c->slots[0];
 	const FrameParams fp = frame_params(c, 0, 1);
-	SceneDev sc = trace_scene(c);
-	sc.use_bvh = 1;                                                                    // (checked above: the launch's LDS is the tree's either way)
-	const BatchCounters bc = batch_counters(c, sl);
-	HIP_TRY(c, hipMemsetAsync(bc.w, 0, BatchCounters::words(bc.nb) * sizeof(uint32_t), c->stream));
-	const FatList none{ bc.unused_fat_count(), sl.fat.as<uint32_t>(), 0u };
-	const bool count = false;
-	hipLaunchKernelGGL(kPrimaryCand[!count], dim3(trace_grid(c, fp.n_pix)), dim3(kTraceBlock), trace_lds(c), c->stream, sc, fp, sl.cand.as<uint32_t>(), bundle_half_angle(c),
-	                   bc.cand_work(), none, c->counters.as<DevCounters>(), static_cast<uint32_t*>(nullptr), bc.listed_pixels());
-	HIP_TRY(c, hipGetLastError());
+	if (!c->cand_valid && (r = build_primary_lists(c, trace_scene(c), fp, false))) return r;   // (the lists of the current view: the ones the next batch reads)
 	std::vector<uint32_t> host(static_cast<size_t>(fp.n_pix));                            // plane 0 of the lists: the counts
-	HIP_TRY(c, hipMemcpyAsync(host.data(), sl.cand.ptr, host.size() * 4, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(c, hipMemcpyAsync(host.data(), c->cand.ptr, host.size() * 4, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	for (int k = 0; k < 10; k++) hist[k] = 0;
 	for (size_t p = 0; p < fp.n_pix; p++) { const uint32_t n = host[p]; hist[n == kCandOverflow ? 9 : std::min<uint32_t>(n, 8u)]++; }     // hist[8]: 8 or more
