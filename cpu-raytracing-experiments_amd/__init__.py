@@ -80,6 +80,8 @@ def load_library():
         "mirt_light_list": [vp, u32, vp, u32, vp, C.POINTER(u32)],
         "mirt_set_scene": [P, vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, vp, u32, u32],
         "mirt_set_camera": [P, vp, vp, f, f, f, f],
+        "mirt_set_lens": [P, f, f], "mirt_get_lens": [P, C.POINTER(f), C.POINTER(f)],
+        "mirt_pick_focus": [P, u32, u32, C.POINTER(f), C.POINTER(f)],
         "mirt_set_policy": [P, C.POINTER(Policy)],
         "mirt_get_policy": [P, C.POINTER(Policy)],
         "mirt_set_gloss_decay": [P, vp, u32],
@@ -121,6 +123,8 @@ def load_library():
         "mirt_group_member": [G, i32, C.POINTER(P)],
         "mirt_group_set_scene": [G, vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, vp, u32, u32],
         "mirt_group_set_camera": [G, vp, vp, f, f, f, f],
+        "mirt_group_set_lens": [G, f, f],
+        "mirt_group_pick_focus": [G, u32, u32, C.POINTER(f), C.POINTER(f)],
         "mirt_group_set_policy": [G, C.POINTER(Policy)],
         "mirt_group_set_gloss_decay": [G, vp, u32],
         "mirt_group_set_stream_order": [G, u32],
@@ -196,6 +200,13 @@ def _aov_image(height: int, width: int, which: int, out):
     return out
 
 
+def _lens_arguments(camera: Camera, aperture_radius, focus_depth):
+    """Arguments of mirt_set_lens: what the caller gave, else the scene camera's (aperture_radius in world units, focus_distance)."""
+    a = camera.aperture_radius if aperture_radius is None else aperture_radius
+    d = camera.focus_distance if focus_depth is None else focus_depth
+    return float(np.float32(a)), float(np.float32(d))
+
+
 def _decay_array(decay) -> np.ndarray:
     return np.ascontiguousarray([] if decay is None else decay, dtype=np.float32).reshape(-1)
 
@@ -210,9 +221,10 @@ class Renderer:
     def __init__(self, scene: Scene, device: int = 0, max_bounces: int = 16, buckets: int = 5, mis: bool = True,
                  use_bvh: bool = False, count_traffic: bool = False, profile: bool = False, max_batch: int = 0,
                  allow_half_boxes: bool = True, reference_tree: bool = False, streams: int = 0, gpu_build: bool = False, trace_primary_rays: bool = False,
-                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False):
+                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False):
         self._lib = load_library()
         self._ctx = C.c_void_p()
+        self._lens_follows_camera = bool(lens)          # lens=True: the scene camera's f_number / focus_distance / unit_mm drive a thin lens
         rc = self._lib.mirt_create(device, C.byref(self._ctx))
         if rc != MIRT_OK:
             raise MirtError(f"mirt_create failed ({rc}): {self._lib.mirt_last_error(None).decode()}")
@@ -302,6 +314,28 @@ class Renderer:
         pos = np.ascontiguousarray(cam.pos, dtype=np.float32)
         ori = np.ascontiguousarray(cam.orient, dtype=np.float32)
         self._check(self._lib.mirt_set_camera(self._ctx, _ptr(pos), _ptr(ori), float(cam.half_width), float(cam.half_height), float(cam.z), float(cam.exposure)))
+        if self._lens_follows_camera:                      # UpdateLens, Camera.hpp:21-26
+            self.set_lens()
+
+    # -- thin lens (mirt.h "thin lens") -------------------------------------------------------------
+    def set_lens(self, aperture_radius=None, focus_depth=None):
+        """Thin-lens depth of field: lens radius and axial depth of the plane of focus, both in world units; None = the scene camera's
+        (focal_length / (2 f_number) / unit_mm, focus_distance).  aperture_radius = 0 is the pinhole path.  Does not reset the accumulator."""
+        a, d = _lens_arguments(self.scene.camera, aperture_radius, focus_depth)
+        self._check(self._lib.mirt_set_lens(self._ctx, a, d))
+
+    def lens(self):
+        """(aperture_radius, focus_depth) in effect."""
+        a, d = C.c_float(0), C.c_float(0)
+        self._check(self._lib.mirt_get_lens(self._ctx, C.byref(a), C.byref(d)))
+        return a.value, d.value
+
+    def pick_focus(self, x: int, y: int):
+        """The reference's right-click pick (Application.cpp:271-304): the un-jittered pinhole ray of pixel (x, y) -> (distance, depth);
+        distance is inf on a miss, depth is the axial depth to hand to set_lens.  Changes no state."""
+        dist, depth = C.c_float(0), C.c_float(0)
+        self._check(self._lib.mirt_pick_focus(self._ctx, int(x), int(y), C.byref(dist), C.byref(depth)))
+        return dist.value, depth.value
 
     # -- the reference interface ---------------------------------------------------------------
     @staticmethod
@@ -471,9 +505,10 @@ class GroupRenderer:
 
     def __init__(self, scene: Scene, devices=(0,), max_bounces: int = 16, buckets: int = 5, mis: bool = True, use_bvh: bool = True,
                  count_traffic: bool = False, max_batch: int = 0, streams: int = 0, reference_tree: bool = False, gpu_build: bool = False,
-                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False):
+                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False):
         self._lib = load_library()
         self._g = C.c_void_p()
+        self._lens_follows_camera = bool(lens)
         dev = (C.c_int * len(devices))(*devices)
         rc = self._lib.mirt_group_create(dev, len(devices), C.byref(self._g))
         if rc != MIRT_OK:
@@ -543,6 +578,27 @@ class GroupRenderer:
         pos = np.ascontiguousarray(cam.pos, dtype=np.float32)
         ori = np.ascontiguousarray(cam.orient, dtype=np.float32)
         self._check(self._lib.mirt_group_set_camera(self._g, _ptr(pos), _ptr(ori), float(cam.half_width), float(cam.half_height), float(cam.z), float(cam.exposure)))
+        if self._lens_follows_camera:
+            self.set_lens()
+
+    def set_lens(self, aperture_radius=None, focus_depth=None):
+        """Renderer.set_lens on every member."""
+        a, d = _lens_arguments(self.scene.camera, aperture_radius, focus_depth)
+        self._check(self._lib.mirt_group_set_lens(self._g, a, d))
+
+    def lens(self):
+        """(aperture_radius, focus_depth) in effect (the first member's; all members hold the same)."""
+        ctx = C.c_void_p()
+        self._check(self._lib.mirt_group_member(self._g, 0, C.byref(ctx)))
+        a, d = C.c_float(0), C.c_float(0)
+        self._lib.mirt_get_lens(ctx, C.byref(a), C.byref(d))
+        return a.value, d.value
+
+    def pick_focus(self, x: int, y: int):
+        """Renderer.pick_focus on the first member."""
+        dist, depth = C.c_float(0), C.c_float(0)
+        self._check(self._lib.mirt_group_pick_focus(self._g, int(x), int(y), C.byref(dist), C.byref(depth)))
+        return dist.value, depth.value
 
     def Resize(self, new_width: int, new_height: int):
         self.width, self.height = int(new_width), int(new_height)

@@ -16,12 +16,13 @@ struct f3 { float x, y, z; };
 struct quat { float x, y, z, w; };      // glm::quat storage order; T.z is always 0 for tangent frames
 
 #define MIRT_DI __device__ __forceinline__
+#define MIRT_HDI __host__ __device__ __forceinline__     // also evaluated on the host, in binary32 with the same operation order (the host TU is built unfused too)
 
 MIRT_DI float max_sel(float a, float b) { return (a < b) ? b : a; }   // std::max(a,b) == glm::max(a,b)
 MIRT_DI float min_sel(float a, float b) { return (b < a) ? b : a; }   // std::min(a,b) == glm::min(a,b)
-MIRT_DI float dot3(f3 a, f3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }        // glm::dot(vec3, vec3)
-MIRT_DI f3 cross3(f3 x, f3 y) { return { x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y }; }  // glm::cross
-MIRT_DI f3 normalize3(f3 v) { float inv = 1.0f / __builtin_sqrtf(dot3(v, v)); return { v.x * inv, v.y * inv, v.z * inv }; } // glm::normalize
+MIRT_HDI float dot3(f3 a, f3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }        // glm::dot(vec3, vec3)
+MIRT_HDI f3 cross3(f3 x, f3 y) { return { x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y }; }  // glm::cross
+MIRT_HDI f3 normalize3(f3 v) { float inv = 1.0f / __builtin_sqrtf(dot3(v, v)); return { v.x * inv, v.y * inv, v.z * inv }; } // glm::normalize
 
 // glm constants (double literals narrowed to float)
 #define MIRT_PI          3.14159265358979323846264338327950288f
@@ -244,7 +245,7 @@ MIRT_DI void tonemapping(float& r, float& g, float& b) {
 
 // ---- Camera.hpp:80-88 -------------------------------------------------------------------------------
 struct CameraParams { float pos[3]; float orient[4]; float half_width, half_height, z, exposure; };
-MIRT_DI f3 camera_ray_dir(const CameraParams& c, int32_t x, int32_t y, float s0, float s1) {
+MIRT_HDI f3 camera_ray_dir(const CameraParams& c, int32_t x, int32_t y, float s0, float s1) {
 	f3 v{ static_cast<float>(x) + s0 - c.half_width, static_cast<float>(y) + s1 - c.half_height, c.z };
 	f3 qv{ c.orient[0], c.orient[1], c.orient[2] };      // glm operator*(quat, vec3)
 	f3 uv = cross3(qv, v);
@@ -252,6 +253,44 @@ MIRT_DI f3 camera_ray_dir(const CameraParams& c, int32_t x, int32_t y, float s0,
 	const float w = c.orient[3];
 	f3 r{ v.x + ((uv.x * w) + uuv.x) * 2.0f, v.y + ((uv.y * w) + uuv.y) * 2.0f, v.z + ((uv.z * w) + uuv.z) * 2.0f };
 	return normalize3(r);
+}
+
+// ---- thin lens ------------------------------------------------------------------------------------------
+// The reference's camera carries focus_distance / f_number / aperture_radius (Camera.hpp:6-45) and generate_ray ignores them
+// (Camera.hpp:80-88): it defines no lens, so nothing here can be held to the oracle.  The lens ray is DERIVED from the
+// unchanged pinhole direction d = camera_ray_dir(...), whose arithmetic stays the oracle's, and is pinned by a numpy twin that restates the
+// operation order below, by float64 definitions and by invariances (tests/lens_twin.py).
+// Camera axes: the camera's +x, +y and -z rotated by view.orient — glm operator*(quat, vec3) as camera_ray_dir spells it; evaluated once on the
+// host when the lens or the camera is set.
+MIRT_HDI f3 camera_axis(const float orient[4], f3 v) {
+	f3 qv{ orient[0], orient[1], orient[2] };
+	f3 uv = cross3(qv, v);
+	f3 uuv = cross3(qv, uv);
+	const float w = orient[3];
+	return { v.x + ((uv.x * w) + uuv.x) * 2.0f, v.y + ((uv.y * w) + uuv.y) * 2.0f, v.z + ((uv.z * w) + uuv.z) * 2.0f };
+}
+// aperture (the lens radius A) and focus_depth are in world units; aperture == 0 never reaches lens_ray (the pinhole kernels run instead).
+struct LensParams { float right[3], up[3], fwd[3]; float aperture, focus_depth; };
+// Lens draws: rng = hash_2d(acc, seed[ID] + 2 * max_bounces).  seed[ID] = index * (2 * max_bounces + 1) (Renderer.hpp:107, "+1 for camera"), so a
+// path owns the offsets 0 .. 2 * max_bounces: raygen and the NEE of bounce 0 both take offset 0 (Renderer.hpp:117,255), the NEE of bounce b takes 2b
+// and its BRDF draw 2b + 1 for the bounces that draw at all (b <= max_bounces - 1 for NEE, b <= max_bounces - 2 for the BRDF sample: at most
+// 2 * max_bounces - 2 and 2 * max_bounces - 3).  Offset 2 * max_bounces is the one the reference reserves and never uses: the lens draws collide
+// with no draw of this path, and (being below the stride) with no draw of another.
+// Operation order, one rounding each (this TU is built with -ffp-contract=off):
+//   u0, u1 = rand_unit_float(rng) twice;  (lx, ly) = disk(u0, u1): rho = sqrt(u0), sincos(u1 * two_pi), lx = rho * cos, ly = rho * sin
+//   t = focus_depth / dot3(d, fwd);               P = pos + d * t                    (the point of d in the plane of focus: planar, perpendicular
+//   ax = A * lx;  ay = A * ly;                    O = pos + (right * ax + up * ay)    to the optical axis, at axial depth focus_depth)
+//   D = normalize3(P - O)
+MIRT_DI void lens_ray(const CameraParams& c, const LensParams& l, f3 d, uint32_t acc, uint32_t seed, uint32_t max_bounces, f3& O, f3& D) {
+	uint32_t rng = hash_2d(acc, seed + 2u * max_bounces);
+	const float u0 = rand_unit_float(rng);
+	const float u1 = rand_unit_float(rng);
+	float lx, ly; disk(u0, u1, lx, ly);
+	const float t = l.focus_depth / dot3(d, f3{ l.fwd[0], l.fwd[1], l.fwd[2] });
+	const f3 P{ c.pos[0] + d.x * t, c.pos[1] + d.y * t, c.pos[2] + d.z * t };
+	const float ax = l.aperture * lx, ay = l.aperture * ly;
+	O = { c.pos[0] + (l.right[0] * ax + l.up[0] * ay), c.pos[1] + (l.right[1] * ax + l.up[1] * ay), c.pos[2] + (l.right[2] * ax + l.up[2] * ay) };
+	D = normalize3(f3{ P.x - O.x, P.y - O.y, P.z - O.z });
 }
 
 } // namespace mirt

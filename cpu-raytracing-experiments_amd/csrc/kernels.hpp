@@ -789,14 +789,26 @@ MIRT_DI void primary_ray(const FrameParams& fp, uint32_t i, uint32_t& path, floa
 	path = (slot << fp.pix_bits) | pix;
 	dx = d.x; dy = d.y; dz = d.z;
 }
+// The camera ray of stream index i under a lens (mirt_set_lens with a radius above 0; template parameter LENS of the bounce-0 kernels): the
+// thin-lens ray derived from the pinhole direction (device_math.hpp lens_ray) — the one case in which camera rays do not share an origin, so
+// every bounce-0 consumer takes origin and direction from here.  `lens` is the trailing argument of those kernels and is read by LENS code only;
+// the pinhole branches beside each call are the statements the kernels have always had.
+MIRT_DI void lens_camera_ray(const FrameParams& fp, const LensParams& lens, uint32_t i, uint32_t& path, float& px, float& py, float& pz, float& dx, float& dy, float& dz) {
+	f3 O, D;
+	primary_ray(fp, i, path, D.x, D.y, D.z);
+	lens_ray(fp.cam, lens, D, fp.acc_base + (path >> fp.pix_bits) + 1u, path_seed(fp, path & fp.pix_mask), fp.max_bounces, O, D);
+	px = O.x; py = O.y; pz = O.z; dx = D.x; dy = D.y; dz = D.z;
+}
 // The same rays written out as a stream (mirt_debug_raygen only).
-__global__ __launch_bounds__(kBlock) void k_raygen(FrameParams fp, StreamBuf out, uint32_t* stream_count) {
+template <bool LENS = false>
+__global__ __launch_bounds__(kBlock) void k_raygen(FrameParams fp, StreamBuf out, uint32_t* stream_count, LensParams lens) {
 	const uint32_t total = fp.n_pix * fp.batch_n;
 	if (blockIdx.x == 0 && threadIdx.x == 0) stream_count[0] = total;
 	for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock) {
-		uint32_t path; float dx, dy, dz;
-		primary_ray(fp, i, path, dx, dy, dz);
-		out.px[i] = fp.cam.pos[0]; out.py[i] = fp.cam.pos[1]; out.pz[i] = fp.cam.pos[2];
+		uint32_t path; float px, py, pz, dx, dy, dz;
+		if (LENS) lens_camera_ray(fp, lens, i, path, px, py, pz, dx, dy, dz);
+		else { primary_ray(fp, i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
+		out.px[i] = px; out.py[i] = py; out.pz[i] = pz;
 		out.dx[i] = dx; out.dy[i] = dy; out.dz[i] = dz;
 		out.path[i] = path;
 	}
@@ -898,13 +910,14 @@ MIRT_DI uint32_t primary_list_ray(const FrameParams& fp, const uint32_t* __restr
 	const uint32_t slot = udiv_f(j, n_ov, inv_n_ov, k);
 	return slot * fp.n_pix + ov_pix[k];
 }
-template <bool COUNT, int PRIMARY>
+// LENS (with kPrimaryAll only): the camera rays are thin-lens rays (lens_camera_ray); candidate lists are neither built nor read under a lens.
+template <bool COUNT, int PRIMARY, bool LENS = false>
 __global__ __launch_bounds__(kTraceBlock, 8) void k_trace(SceneDev sc, FrameParams fp,
                                                        StreamBuf in, HitRec* __restrict__ hit_out,
                                                        Queue closest_queue, uint32_t* closest_work,
                                                        ShadowBuf sh, ShadowSink sink,
                                                        Queue shadow_queue, uint32_t* shadow_work, FatList fat_closest, FatList fat_shadow,
-                                                       DevCounters* ctr) {
+                                                       DevCounters* ctr, LensParams lens) {
 	extern __shared__ float4 lds[];
 	const uint32_t n_ov = PRIMARY == kPrimaryList ? closest_queue.n[0] : 0u;     // listed pixels (k_primary_cand)
 	const float inv_n_ov = 1.0f / static_cast<float>(n_ov ? n_ov : 1u);
@@ -921,7 +934,8 @@ __global__ __launch_bounds__(kTraceBlock, 8) void k_trace(SceneDev sc, FramePara
 		const TraceLds tl = stage_bvh(sc, lds);
 		{
 			auto load_ray = [&](uint32_t i, float& px, float& py, float& pz, float& dx, float& dy, float& dz, float& tf) {
-				if (PRIMARY) { uint32_t path; primary_ray(fp, PRIMARY == kPrimaryList ? primary_list_ray(fp, in.path, n_ov, inv_n_ov, i) : i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
+				if (PRIMARY && LENS) { uint32_t path; lens_camera_ray(fp, lens, i, path, px, py, pz, dx, dy, dz); }
+				else if (PRIMARY) { uint32_t path; primary_ray(fp, PRIMARY == kPrimaryList ? primary_list_ray(fp, in.path, n_ov, inv_n_ov, i) : i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
 				else { px = in.px[i]; py = in.py[i]; pz = in.pz[i]; dx = in.dx[i]; dy = in.dy[i]; dz = in.dz[i]; }
 				tf = MIRT_FLT_MAX;                                                 // hit reset, Renderer.hpp:150-158
 			};
@@ -944,7 +958,8 @@ __global__ __launch_bounds__(kTraceBlock, 8) void k_trace(SceneDev sc, FramePara
 			const uint32_t i = active ? queue_slot(qc, base, base + threadIdx.x) : 0u;
 			float px = 0, py = 0, pz = 0, dx = 1, dy = 1, dz = 1;
 			if (active) {
-				if (PRIMARY) { uint32_t path; primary_ray(fp, i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
+				if (PRIMARY && LENS) { uint32_t path; lens_camera_ray(fp, lens, i, path, px, py, pz, dx, dy, dz); }
+				else if (PRIMARY) { uint32_t path; primary_ray(fp, i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
 				else { px = in.px[i]; py = in.py[i]; pz = in.pz[i]; dx = in.dx[i]; dy = in.dy[i]; dz = in.dz[i]; }
 			}
 			float tfar = MIRT_FLT_MAX;             // hit reset, Renderer.hpp:150-158
@@ -970,9 +985,9 @@ __global__ __launch_bounds__(kTraceBlock, 8) void k_trace(SceneDev sc, FramePara
 // Fat rays (see trav_begin): one workgroup per ray runs the reference's brute-force loops over ALL prims —
 // intersect_prims (BVH.hpp:236-288; closest = lexicographic minimum of (dist, prim index), i.e. the ascending strict-'<' scan)
 // for the closest-hit list, intersect_prims_shadow (BVH.hpp:290-305) for the shadow list.
-template <bool COUNT, int PRIMARY>
+template <bool COUNT, int PRIMARY, bool LENS = false>
 __global__ __launch_bounds__(1024) void k_trace_fat(SceneDev sc, FrameParams fp, StreamBuf in, HitRec* __restrict__ hit_out, FatList fat_closest,
-                                                    ShadowBuf sh, ShadowSink sink, FatList fat_shadow, DevCounters* ctr, const uint32_t* ov_count) {
+                                                    ShadowBuf sh, ShadowSink sink, FatList fat_shadow, DevCounters* ctr, const uint32_t* ov_count, LensParams lens) {
 	__shared__ float s_t[16];
 	__shared__ int32_t s_p[16];
 	const uint32_t nc = min(*fat_closest.count, fat_closest.capacity), ns = min(*fat_shadow.count, fat_shadow.capacity);
@@ -982,7 +997,8 @@ __global__ __launch_bounds__(1024) void k_trace_fat(SceneDev sc, FrameParams fp,
 	for (uint32_t k = blockIdx.x; k < nc; k += gridDim.x) {
 		const uint32_t i = PRIMARY == kPrimaryList ? primary_list_ray(fp, in.path, n_ov, inv_n_ov, fat_closest.rays[k]) : fat_closest.rays[k];
 		float px, py, pz, dx, dy, dz;
-		if (PRIMARY) { uint32_t path; primary_ray(fp, i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
+		if (PRIMARY && LENS) { uint32_t path; lens_camera_ray(fp, lens, i, path, px, py, pz, dx, dy, dz); }
+		else if (PRIMARY) { uint32_t path; primary_ray(fp, i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
 		else { px = in.px[i]; py = in.py[i]; pz = in.pz[i]; dx = in.dx[i]; dy = in.dy[i]; dz = in.dz[i]; }
 		float tfar = MIRT_FLT_MAX; int32_t prim = -1;
 		for (uint32_t p = threadIdx.x; p < sc.n_spheres; p += blockDim.x) sphere_closest(sc.spheres[p], static_cast<int32_t>(p), px, py, pz, dx, dy, dz, tfar, prim);
@@ -1117,8 +1133,10 @@ __global__ __launch_bounds__(kBlock) void k_primary_hits(SceneDev sc, FrameParam
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t kAovPlanes = 7;
 constexpr float kAovMissDepth = 1e4f;             // Renderer.hpp:228
-__global__ __launch_bounds__(kBlock) void k_first_hit_aov(SceneDev sc, FrameParams fp, const HitRec* __restrict__ hit_in, const float4* __restrict__ mat_colour, float* __restrict__ aov) {
-	const f3 O{ fp.cam.pos[0], fp.cam.pos[1], fp.cam.pos[2] };
+// LENS: the sample's thin-lens ray (lens_ray) instead of the pinhole ray — origin and direction both differ per sample.
+template <bool LENS = false>
+__global__ __launch_bounds__(kBlock) void k_first_hit_aov(SceneDev sc, FrameParams fp, const HitRec* __restrict__ hit_in, const float4* __restrict__ mat_colour, float* __restrict__ aov, LensParams lens) {
+	f3 O{ fp.cam.pos[0], fp.cam.pos[1], fp.cam.pos[2] };
 	for (uint32_t pix = blockIdx.x * kBlock + threadIdx.x; pix < fp.n_pix; pix += gridDim.x * kBlock) {
 		uint32_t tile; int32_t x, y;
 		pixel_xy(fp, pix, tile, x, y);
@@ -1132,7 +1150,8 @@ __global__ __launch_bounds__(kBlock) void k_first_hit_aov(SceneDev sc, FramePara
 			uint32_t rng = hash_2d(fp.acc_base + slot + 1u, seed);                 // ++accumulations, Renderer.hpp:74,117
 			const float s0 = rand_unit_float(rng);
 			const float s1 = rand_unit_float(rng);
-			const f3 D = camera_ray_dir(fp.cam, x, y, s0, s1);
+			f3 D = camera_ray_dir(fp.cam, x, y, s0, s1);
+			if (LENS) lens_ray(fp.cam, lens, D, fp.acc_base + slot + 1u, seed, fp.max_bounces, O, D);
 			const HitRec h = hit_in[static_cast<size_t>(slot) * fp.n_pix + pix];
 			if (h.prim < 0) { sum[0] += kAovMissDepth; continue; }
 			if (h.prim != cached) { hs = sc.spheres[h.prim]; colour = mat_colour[sc.prim_mat[h.prim]]; cached = h.prim; }
@@ -1210,10 +1229,12 @@ MIRT_DI uint32_t block_compact(bool flag, uint32_t value, uint32_t* scratch, uin
 // alpha = r^2 + (1 - r^2) * gloss_decay (Renderer.hpp:210-212; `gloss_decay` = the host's table at this bounce, one launch per
 // bounce), read from mat_ggx = {F0.xyz, roughness}.  Its pdf() is 0: NEE weighs 1 / light_pdf and emitters hit by an extension
 // ray weigh powerHeuristic(0, .) = 0.  GGX = false does not read the two trailing arguments.
-template <bool FIRST, bool GGX>
+// LENS (with FIRST only): bounce 0 re-derives the thin-lens ray (lens_ray) — its origin is the sample's lens point, not cam.pos.  Same launch
+// bounds as the pinhole variants; `lens` is read by LENS code only.
+template <bool FIRST, bool GGX, bool LENS = false>
 __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
                                                   Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
-                                                  const float4* __restrict__ mat_ggx, float gloss_decay) {
+                                                  const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens) {
 	const QueueView qin = FIRST ? queue_identity(fp.n_pix * fp.batch_n) : queue_view(in_queue);
 	const uint32_t n = qin.pre[kSegs];
 	const uint32_t n_chunks = (fp.n_pix + kShadeBlock - 1u) / kShadeBlock;      // FIRST
@@ -1253,6 +1274,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 		int32_t my_prim = next_prim;
 		float my_tfar = 0.0f;
 		f3 my_D{0, 0, 0};
+		f3 my_O{0, 0, 0};                                                       // LENS: the sample's point on the lens
 		uint32_t my_path = 0u;
 		bool lane_on;
 		f3 W0{0.0f, 0.0f, 0.0f};                                               // FIRST: the word this path starts with
@@ -1273,6 +1295,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 				const float s0 = rand_unit_float(rng);
 				const float s1 = rand_unit_float(rng);
 				my_D = camera_ray_dir(fp.cam, pix_x, pix_y, s0, s1);
+				if (LENS) lens_ray(fp.cam, lens, my_D, fp.acc_base + slot_it + 1u, pix_seed, fp.max_bounces, my_O, my_D);
 				my_path = (slot_it << fp.pix_bits) | pix;
 				{ const HitRec h = hit_in[my_slot]; my_prim = h.prim; my_tfar = h.tfar; }      // the hit record of k_primary_hits / k_trace
 			}
@@ -1340,7 +1363,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 				const float depth = hrec.tfar;
 				const float4 hs = sc.spheres[prim];
 				const int32_t mat = sc.prim_mat[prim];
-				const f3 O = FIRST ? f3{ fp.cam.pos[0], fp.cam.pos[1], fp.cam.pos[2] } : f3{ in.px[i], in.py[i], in.pz[i] };
+				const f3 O = FIRST ? (LENS ? my_O : f3{ fp.cam.pos[0], fp.cam.pos[1], fp.cam.pos[2] }) : f3{ in.px[i], in.py[i], in.pz[i] };
 				const f3 hit{ O.x + D.x * depth, O.y + D.y * depth, O.z + D.z * depth };
 				f3 N = normalize3(f3{ hit.x - hs.x, hit.y - hs.y, hit.z - hs.z });
 				if (dot3(N, D) >= 0.0f) N = f3{ -N.x, -N.y, -N.z };

@@ -93,6 +93,7 @@ struct mirt_ctx {
 	DeviceBuffer gloss_decay_dev;    // the table as k_tile_stream reads it (its bounce loop runs inside the kernel); uploaded by the first launch after a change
 	bool gloss_decay_dev_valid = false;
 	CameraParams camera{};
+	LensParams lens{};               // mirt_set_lens: aperture > 0 = every camera ray is a thin-lens ray (the LENS kernels); the axes follow the camera (update_lens_axes)
 	uint32_t bvh_depth = 0;
 	// Candidate lists of the camera rays (k_primary_cand, kernels.hpp kCollect).  They are a function of the scene and its tree, the camera, the image
 	// size and the tiles this context owns — not of the accumulation index, the batch size or any random draw — so the first batch that wants them
@@ -411,6 +412,15 @@ struct Bracket {
 // (1.38e-3 .. 1.47e-3, from |D|^2 - 1 of its normalised direction) may exceed the axis ray's by 8.5e-5
 float bundle_half_angle(const mirt_ctx* c) { return (0.7072f / std::fabs(c->camera.z)) * 1.01f + 1e-4f; }
 
+// The camera's +x, +y and -z in world space, for lens_ray: binary32, the quat * vec3 formula of camera_ray_dir (device_math.hpp camera_axis).
+void update_lens_axes(mirt_ctx* c) {
+	const f3 r = camera_axis(c->camera.orient, f3{ 1.0f, 0.0f, 0.0f }), u = camera_axis(c->camera.orient, f3{ 0.0f, 1.0f, 0.0f }), f = camera_axis(c->camera.orient, f3{ 0.0f, 0.0f, -1.0f });
+	c->lens.right[0] = r.x; c->lens.right[1] = r.y; c->lens.right[2] = r.z;
+	c->lens.up[0] = u.x; c->lens.up[1] = u.y; c->lens.up[2] = u.z;
+	c->lens.fwd[0] = f.x; c->lens.fwd[1] = f.y; c->lens.fwd[2] = f.z;
+}
+bool lens_on(const mirt_ctx* c) { return c->lens.aperture > 0.0f; }
+
 FrameParams frame_params(const mirt_ctx* c, uint32_t acc_base, uint32_t batch_n) {
 	FrameParams fp{};
 	fp.cam = c->camera;
@@ -457,6 +467,10 @@ const decltype(&k_primary_hits<true>) kPrimaryHits[2] = { k_primary_hits<true>, 
 const decltype(&k_shade<false, false>) kShade[2][2] = { { k_shade<false, false>, k_shade<false, true> }, { k_shade<true, false>, k_shade<true, true> } };   // [first][ggx]
 const decltype(&k_tile_stream<false>) kTileStream[2] = { k_tile_stream<false>, k_tile_stream<true> };                                         // [ggx]
 static_assert(kPrimaryNone == 0 && kPrimaryAll == 1 && kPrimaryList == 2, "kTrace / kTraceFat are indexed by PRIMARY");
+// The thin-lens twins of the bounce-0 kernels (mirt_set_lens), named after every table above so that those keep their device code.
+const decltype(&k_trace<true, kPrimaryNone>) kTraceLens[2] = { k_trace<true, kPrimaryAll, true>, k_trace<false, kPrimaryAll, true> };               // [!count]
+const decltype(&k_trace_fat<true, kPrimaryNone>) kTraceFatLens[2] = { k_trace_fat<true, kPrimaryAll, true>, k_trace_fat<false, kPrimaryAll, true> };  // [!count]
+const decltype(&k_shade<false, false>) kShadeLens[2] = { k_shade<true, false, true>, k_shade<true, true, true> };                                    // [ggx]
 
 // What varies between the launches of the trace stage: a bounce of a batch, or the rays of a debug entry point.
 struct TraceLaunch {
@@ -469,12 +483,13 @@ struct TraceLaunch {
 	DevCounters* ctr;
 };
 // k_trace<count, primary> over n_rays, then (with a tree) the few rays too "fat" for it: brute force, one workgroup each.
-void launch_trace(const mirt_ctx* c, hipStream_t st, const SceneDev& sc, const FrameParams& fp, uint64_t n_rays, bool count, int primary, const TraceLaunch& t) {
-	hipLaunchKernelGGL(kTrace[!count][primary], dim3(trace_grid(c, n_rays)), dim3(kTraceBlock), trace_lds(c), st, sc, fp, t.in, t.hit, t.closest_queue, t.closest_work,
-	                   t.sh, t.sink, t.shadow_queue, t.shadow_work, t.fat_closest, t.fat_shadow, t.ctr);
+// lens (with kPrimaryAll only): the thin-lens twins.
+void launch_trace(const mirt_ctx* c, hipStream_t st, const SceneDev& sc, const FrameParams& fp, uint64_t n_rays, bool count, int primary, const TraceLaunch& t, bool lens = false) {
+	hipLaunchKernelGGL(lens ? kTraceLens[!count] : kTrace[!count][primary], dim3(trace_grid(c, n_rays)), dim3(kTraceBlock), trace_lds(c), st, sc, fp, t.in, t.hit, t.closest_queue, t.closest_work,
+	                   t.sh, t.sink, t.shadow_queue, t.shadow_work, t.fat_closest, t.fat_shadow, t.ctr, c->lens);
 	// a large scene (100 k spheres: ~100 us per ray) wants as many fat rays in flight as there are (a few hundred per launch); k_trace_fat grid-strides
 	const uint32_t fat_grid = sc.n_spheres > 4096 ? static_cast<uint32_t>(c->n_cu) * 2u : 64u;
-	if (sc.use_bvh) hipLaunchKernelGGL(kTraceFat[!count][primary], dim3(fat_grid), dim3(1024), 0, st, sc, fp, t.in, t.hit, t.fat_closest, t.sh, t.sink, t.fat_shadow, t.ctr, t.listed_pixels);
+	if (sc.use_bvh) hipLaunchKernelGGL(lens ? kTraceFatLens[!count] : kTraceFat[!count][primary], dim3(fat_grid), dim3(1024), 0, st, sc, fp, t.in, t.hit, t.fat_closest, t.sh, t.sink, t.fat_shadow, t.ctr, t.listed_pixels, c->lens);
 }
 
 // mirt_set_stream_order(1): a batch is ONE launch — the whole bounce loop of a (tile, accumulation) stream runs in one workgroup, in the reference's
@@ -526,7 +541,8 @@ int launch_first_hit_aov(mirt_ctx* c, PipeSlot& sl, hipStream_t st, const SceneD
 	}
 	{ Bracket t(c, MIRT_K_RESOLVE, st);
 	  const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
-	  hipLaunchKernelGGL(k_first_hit_aov, dim3(grid), dim3(kBlock), 0, st, sc, fp, sl.hit, c->policy.brdf ? c->mat_ggx.as<float4>() : c->scene.mat_albedo, c->aov.as<float>()); }
+	  hipLaunchKernelGGL(lens_on(c) ? k_first_hit_aov<true> : k_first_hit_aov<false>, dim3(grid), dim3(kBlock), 0, st, sc, fp, sl.hit, c->policy.brdf ? c->mat_ggx.as<float4>() : c->scene.mat_albedo,
+	                     c->aov.as<float>(), c->lens); }
 	if (pipelined) { HIP_TRY(c, hipEventRecord(sl.aov_done, st)); c->aov_prev = sl.aov_done; }
 	return MIRT_OK;
 }
@@ -554,7 +570,11 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 	// (The half-angle bound assumes view.orient rotates: a non-unit quaternion, which the reference's View never holds (Camera.hpp:48-50),
 	// would shear the image plane — such a camera gets no lists.)
 	const float qn = c->camera.orient[0] * c->camera.orient[0] + c->camera.orient[1] * c->camera.orient[1] + c->camera.orient[2] * c->camera.orient[2] + c->camera.orient[3] * c->camera.orient[3];
-	const bool bundle = c->policy.use_bvh && c->scene.n_recs != 0 && !c->policy.trace_primary_rays && batch_n >= 3 && c->camera.z != 0.0f && std::fabs(qn - 1.0f) < 1e-4f && !c->stream_order;
+	// Under a lens every camera ray walks the tree (the trace_primary_rays = 1 route, whatever that field says): a pixel's rays no longer share an
+	// origin, so its lists — cones from cam.pos — do not bound them; they are neither built nor read, and cand_valid stays what it was (the lists
+	// depend on scene, camera, size and tiles, not on the lens: valid ones serve the next pinhole batch).
+	const bool lens = lens_on(c);
+	const bool bundle = c->policy.use_bvh && c->scene.n_recs != 0 && !c->policy.trace_primary_rays && batch_n >= 3 && c->camera.z != 0.0f && std::fabs(qn - 1.0f) < 1e-4f && !c->stream_order && !lens;
 	DevCounters* ctr = c->counters.as<DevCounters>();
 	const float4* mat_ggx = c->mat_ggx.as<float4>();
 	float* contrib = sl.contrib.as<float>();                                      // slot k of the buffer = accumulation acc_base + k + 1
@@ -605,13 +625,13 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			  const TraceLaunch tl{ rays, sl.hit, lists ? Queue{ cw.listed_pixels(), 0u } : bc.stream_queue(bounce), bc.closest_work(bounce),      // kPrimaryList: n[0] = listed pixels
 			                        sl.shadow_buf, sink, shadow_pending ? bc.shadow_queue(bounce - 1) : bc.empty_queue(), bc.shadow_work(shadow_pending ? bounce - 1 : 0),
 			                        bc.fat_closest(bounce, fat_lists), bc.fat_shadow(bounce, fat_lists), lists ? cw.listed_pixels() : nullptr, ctr };
-			  launch_trace(c, st, sc, fp, total, count, lists ? kPrimaryList : bounce == 0 ? kPrimaryAll : kPrimaryNone, tl); }
+			  launch_trace(c, st, sc, fp, total, count, lists ? kPrimaryList : bounce == 0 ? kPrimaryAll : kPrimaryNone, tl, bounce == 0 && lens); }
 			if (bounce == 0 && c->aov_on) { const int r = launch_first_hit_aov(c, sl, st, sc, fp); if (r) return r; }
 			{ Bracket t(c, MIRT_K_SHADE, st);
 			  // policy.brdf = 1 (#define BRDF 1): Closure<GGX> with this bounce's gloss decay, passed by value
 			  const float decay = bounce < c->gloss_decay.size() ? c->gloss_decay[bounce] : 0.0f;
-			  hipLaunchKernelGGL(kShade[bounce == 0][c->policy.brdf != 0], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
-			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay); }
+			  hipLaunchKernelGGL(bounce == 0 && lens ? kShadeLens[c->policy.brdf != 0] : kShade[bounce == 0][c->policy.brdf != 0], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
+			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens); }
 		}
 	}
 	HIP_TRY(c, hipGetLastError());
@@ -792,6 +812,7 @@ int plan_trace_lds(mirt_ctx* c) {
 	const int lds_max = static_cast<int>(kLdsPerCu);
 	for (const auto& row : kTrace) for (const auto k : row) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
 	for (const auto k : kPrimaryCand) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+	for (const auto k : kTraceLens) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
 	return MIRT_OK;
 }
 
@@ -940,6 +961,41 @@ int mirt_set_camera(mirt_ctx* c, const float pos[3], const float orient_xyzw[4],
 	c->camera.half_width = half_width; c->camera.half_height = half_height; c->camera.z = z; c->camera.exposure = exposure;
 	c->have_camera = true;
 	c->cand_valid = false;                                                             // every cone has moved
+	update_lens_axes(c);
+	return MIRT_OK;
+}
+
+// ---- thin lens ---------------------------------------------------------------------------------
+int mirt_set_lens(mirt_ctx* c, float aperture_radius, float focus_depth) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!std::isfinite(aperture_radius) || !std::isfinite(focus_depth)) return fail(c, MIRT_ERR_ARG, "lens: aperture_radius %g / focus_depth %g must be finite", static_cast<double>(aperture_radius), static_cast<double>(focus_depth));
+	if (aperture_radius < 0.0f) return fail(c, MIRT_ERR_ARG, "lens: aperture_radius %g is negative", static_cast<double>(aperture_radius));
+	if (aperture_radius > 0.0f && !(focus_depth > 0.0f)) return fail(c, MIRT_ERR_ARG, "lens: focus_depth %g must be above 0 with an open aperture", static_cast<double>(focus_depth));
+	if (aperture_radius > 0.0f && c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which has no lens (Camera.hpp:80-88 ignores it): call mirt_set_stream_order(ctx, 0) first");
+	if (aperture_radius == c->lens.aperture && focus_depth == c->lens.focus_depth) return MIRT_OK;
+	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render under the lens they were issued under
+	c->lens.aperture = aperture_radius; c->lens.focus_depth = focus_depth;
+	update_lens_axes(c);
+	return MIRT_OK;
+}
+int mirt_get_lens(const mirt_ctx* c, float* aperture_radius, float* focus_depth) {
+	if (!c || !aperture_radius || !focus_depth) return MIRT_ERR_ARG;
+	*aperture_radius = c->lens.aperture; *focus_depth = c->lens.focus_depth;
+	return MIRT_OK;
+}
+int mirt_pick_focus(mirt_ctx* c, uint32_t x, uint32_t y, float* distance, float* depth) {
+	int r = check_ready(c); if (r) return r;
+	if (!distance || !depth) return fail(c, MIRT_ERR_ARG, "distance / depth is NULL");
+	if (x >= c->width || y >= c->height) return fail(c, MIRT_ERR_ARG, "pixel (%u, %u) outside the %u x %u image", x, y, c->width, c->height);
+	// the un-jittered pinhole ray of the pixel (Application.cpp:288-295), evaluated here with the kernels' own function
+	const f3 d = camera_ray_dir(c->camera, static_cast<int32_t>(x), static_cast<int32_t>(y), 0.5f, 0.5f);
+	const float p[3] = { c->camera.pos[0], c->camera.pos[1], c->camera.pos[2] }, dir[3] = { d.x, d.y, d.z };
+	HitRec hit{};
+	if ((r = debug_trace(c, "pick_focus", 1, p, dir, nullptr, &hit))) return r;     // the context's own closest-hit traversal; touches none of its state
+	const f3 fwd = camera_axis(c->camera.orient, f3{ 0.0f, 0.0f, -1.0f });
+	const float cosine = dot3(d, fwd);
+	*distance = hit.prim >= 0 ? hit.tfar : INFINITY;                                   // Application.cpp:298
+	*depth = *distance * (cosine < 1.0f ? cosine : 1.0f);                              // (a cosine rounded above 1 would put the plane of focus behind the hit)
 	return MIRT_OK;
 }
 
@@ -978,6 +1034,7 @@ int mirt_set_stream_order(mirt_ctx* c, uint32_t exact) {
 	if (!c) return MIRT_ERR_ARG;
 	if (exact > 1) return fail(c, MIRT_ERR_ARG, "stream order %u is neither 0 (any order, FMA form for every ray) nor 1 (the reference's slots and scalar tail)", exact);
 	if (exact == c->stream_order) return MIRT_OK;
+	if (exact && lens_on(c)) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which has no lens (Camera.hpp:80-88 ignores it): call mirt_set_lens(ctx, 0, 0) first");
 	if (exact && c->aov_on) return fail(c, MIRT_ERR_STATE, "exact stream order keeps no hit records (k_tile_stream runs a tile's whole bounce loop in one launch), so it cannot feed the first-hit AOVs: call mirt_set_aov(ctx, 0) first");
 	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render in the mode they were issued under
 	c->stream_order = exact;
@@ -1259,7 +1316,7 @@ int mirt_debug_raygen(mirt_ctx* c, uint32_t accumulations, float* p_xyz, float* 
 	const FrameParams fp = frame_params(c, accumulations - 1, 1);
 	const size_t n = fp.n_pix;
 	HIP_TRY(c, sync_all(c));
-	hipLaunchKernelGGL(k_raygen, dim3(grid_for(c, n)), dim3(kBlock), 0, c->stream, fp, c->slots[0].stream_buf[0], batch_counters(c, c->slots[0]).stream_queue(0).n);
+	hipLaunchKernelGGL(lens_on(c) ? k_raygen<true> : k_raygen<false>, dim3(grid_for(c, n)), dim3(kBlock), 0, c->stream, fp, c->slots[0].stream_buf[0], batch_counters(c, c->slots[0]).stream_queue(0).n, c->lens);
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	const StreamBuf& s = c->slots[0].stream_buf[0];

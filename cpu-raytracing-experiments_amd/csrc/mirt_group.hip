@@ -180,6 +180,19 @@ int mirt_group_set_stream_order(mirt_group* g, uint32_t exact) {
 	if (g->full) FULL_TRY(g, "mirt_set_stream_order", mirt_set_stream_order(g->full, exact));
 	return MIRT_OK;
 }
+int mirt_group_set_lens(mirt_group* g, float aperture_radius, float focus_depth) {
+	if (!g) return MIRT_ERR_ARG;
+	FOR_MEMBERS(g, "mirt_set_lens", mirt_set_lens(ctx, aperture_radius, focus_depth));
+	if (g->full) FULL_TRY(g, "mirt_set_lens", mirt_set_lens(g->full, aperture_radius, focus_depth));
+	return MIRT_OK;
+}
+int mirt_group_pick_focus(mirt_group* g, uint32_t x, uint32_t y, float* distance, float* depth) {
+	if (!g) return MIRT_ERR_ARG;
+	mirt_ctx* ctx = g->members[0];                                                   // one ray: every member holds the whole scene
+	const int rc = mirt_pick_focus(ctx, x, y, distance, depth);
+	if (rc < 0) return gfail(g, rc, "mirt_pick_focus on member 0 (device %d): %s", g->devices[0], mirt_last_error(ctx));
+	return rc;
+}
 int mirt_group_set_aov(mirt_group* g, uint32_t on) {
 	if (!g) return MIRT_ERR_ARG;
 	FOR_MEMBERS(g, "mirt_set_aov", mirt_set_aov(ctx, on));

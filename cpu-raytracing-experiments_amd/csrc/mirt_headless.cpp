@@ -6,6 +6,10 @@
 //
 //   mirt_headless --scene default9|furnace|bvh_test|brdf_test|synthetic:N [--size WxH] [--spp N | --frames N] [--bounces B] [--buckets K] [--brute] [--devices 0,1,..]
 //                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm] [--aov PREFIX]
+//                 [--f-number F] [--focus-distance D] [--unit-mm U] [--focus-pixel X,Y]
+// Any of the four lens options turns the thin lens on (mirt_set_lens): camera.f_number / focus_distance / unit_mm as in Camera.hpp:64 (unit_mm =
+// millimetres per world unit, default 1000); --focus-pixel X,Y is the right-click pick (Application.cpp:271-304): it prints the picked distance and
+// focuses on its axial depth (a pick that meets the sky leaves the focus distance as given).
 // --brdf 1 renders every hit with the GGX closure (#define BRDF 1, Renderer.hpp:70), --gloss-decay gives its per-bounce table (:212).
 // --exact-stream-order replays the reference's stream slots and its scalar intersection tail (BVH.hpp:270-286; brute force, mirt_set_stream_order).
 // --aov PREFIX sums the first-hit AOVs beside the frame (mirt_set_aov) and writes PREFIX.depth.pfm (one channel, `Pf`), PREFIX.normal.pfm and
@@ -168,6 +172,9 @@ int main(int argc, char** argv) {
 	std::vector<int> devices = { 0 };
 	std::vector<float> gloss_decay;
 	bool exact_stream_order = false;
+	float f_number = 16.0f, focus_distance = 1.0f, unit_mm = 1000.0f;          // Camera.hpp:64
+	bool lens = false, pick = false;
+	uint32_t pick_x = 0, pick_y = 0;
 	if (argc == 4 && std::string(argv[1]) == "--convert-hdr") {
 		// file-format check without a GPU: read a picture like stbi_loadf does (top-down) and store it again like Image::Store does (which
 		// flips, so the rows are handed over bottom-up): the output decodes to the same texels
@@ -194,6 +201,10 @@ int main(int argc, char** argv) {
 		else if (a == "--exact-stream-order") exact_stream_order = true;
 		else if (a == "--out") out = next();
 		else if (a == "--aov") aov_prefix = next();
+		else if (a == "--f-number") { f_number = static_cast<float>(std::atof(next())); lens = true; }
+		else if (a == "--focus-distance") { focus_distance = static_cast<float>(std::atof(next())); lens = true; }
+		else if (a == "--unit-mm") { unit_mm = static_cast<float>(std::atof(next())); lens = true; }
+		else if (a == "--focus-pixel") { if (std::sscanf(next(), "%u,%u", &pick_x, &pick_y) != 2) return 2; lens = pick = true; }
 		else if (a == "--devices") { devices.clear(); for (const char* p = next(); *p;) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p == ',') p++; } if (devices.empty()) return 2; }
 		else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
 	}
@@ -222,6 +233,16 @@ int main(int argc, char** argv) {
 		scene.camera.Resize(w, h);                                     // Application.cpp:375-376
 		renderer.SceneChanged();
 		renderer.Resize(w, h);
+		if (lens) {
+			scene.camera.f_number = f_number; scene.camera.focus_distance = focus_distance; scene.camera.unit_mm = unit_mm;
+			if (pick) {                                                     // pick, then set (Application.cpp:298-299)
+				const Renderer::Pick p = renderer.PickFocus(pick_x, pick_y);
+				std::printf("picked focus at pixel (%u, %u): distance %g, depth %g\n", pick_x, pick_y, static_cast<double>(p.distance), static_cast<double>(p.depth));
+				if (std::isfinite(p.depth)) scene.camera.focus_distance = p.depth;
+			}
+			renderer.SetLens(scene.camera.aperture_radius(), scene.camera.focus_distance);
+			renderer.ResetAccumulator();
+		}
 
 		const auto t0 = std::chrono::steady_clock::now();
 		bool have_frame = false;

@@ -25,12 +25,17 @@ static_assert(sizeof(Sphere) == 32 && sizeof(Material) == 96 && sizeof(Node) == 
 struct vec3 { float x = 0, y = 0, z = 0; };
 struct quat { float x = 0, y = 0, z = 0, w = 1; };
 
-// Camera.hpp:5-89 — pinhole camera; aperture / focus fields are unused by the path (Q18) and omitted.
+// Camera.hpp:5-89.  The aperture / focus fields are carried by the reference and read by nothing on its path (Q18): here they drive the
+// thin lens of mirt_set_lens, through Renderer::SetLens / RendererPolicy::lens only — a Renderer made without them is the pinhole camera.
 struct Camera {
 	vec3 pos;
 	quat orient;
 	float half_width = 0.5f, half_height = 0.5f, z = 0.0f;
 	float focal_length = 50.0f, exp = 1.0f;
+	float focus_distance = 1.0f;                                           // Camera.hpp:64; world units (the pick stores a hit distance here, Application.cpp:298)
+	float f_number = 16.0f;                                                // Camera.hpp:64
+	float unit_mm = 1000.0f;                                               // one world unit in millimetres: the reference never connects focal_length's mm to the scene
+	float aperture_radius() const { return (focal_length / (2.0f * f_number)) / unit_mm; }   // Projection::calc_aperture, Camera.hpp:17-19,24, in world units
 
 	Camera() { Resize(1, 1); }
 	Camera(vec3 eye, vec3 direction, float focal_length_mm = 50.0f, float exposure = 1.0f) : pos(eye), focal_length(focal_length_mm), exp(exposure) {
@@ -117,6 +122,7 @@ struct RendererPolicy {                                                    // Re
 	bool reference_tree = false;                                           // true: traverse scene.acceleration_structure.nodes as is instead of the internal SAH tree
 	bool gpu_build = false;                                                // true: internal tree built on the GPU (LBVH) at SceneChanged(): faster rebuild, slower rays
 	uint32_t brdf = 0;                                                     // #define BRDF, Renderer.hpp:70: 0 = Lambertian, 1 = GGX (F0, roughness; SetGlossDecay)
+	bool lens = false;                                                     // true: scene.camera's f_number / focus_distance / unit_mm drive a thin lens (CameraChanged re-sends it)
 };
 
 class Renderer {
@@ -130,6 +136,7 @@ public:
 		mirt_policy& p = policy_;
 		p.max_bounces = policy.max_bounces; p.buckets = policy.buckets; p.mis = policy.mis; p.use_bvh = policy.use_bvh; p.reference_tree = policy.reference_tree; p.gpu_build = policy.gpu_build;
 		p.brdf = policy.brdf;
+		lens_follows_camera_ = policy.lens;
 		if (mirt_group_set_policy(group_, &p) < 0) {                           // no destructor runs for a constructor that throws: release the group here
 			const std::string why = std::string("mirt_group_set_policy: ") + mirt_group_last_error(group_);
 			mirt_group_destroy(group_); group_ = nullptr;
@@ -154,7 +161,15 @@ public:
 	void CameraChanged() {
 		const Camera& c = scene.camera;
 		check(mirt_group_set_camera(group_, &c.pos.x, &c.orient.x, c.half_width, c.half_height, c.z, c.exp), "mirt_group_set_camera");
+		if (lens_follows_camera_) SetLens(c.aperture_radius(), c.focus_distance);     // UpdateLens, Camera.hpp:21-26
 	}
+	// Thin-lens depth of field (mirt.h, mirt_set_lens): lens radius and axial depth of the plane of focus in world units; radius 0 = pinhole.
+	// Like the reference's lens widgets (Application.cpp:413-417) the caller resets the accumulator afterwards.
+	void SetLens(float aperture_radius, float focus_depth) { check(mirt_group_set_lens(group_, aperture_radius, focus_depth), "mirt_group_set_lens"); }
+	// The right-click pick (Application.cpp:271-304): the un-jittered pinhole ray of pixel (x, y); distance is INFINITY on a miss, depth is the
+	// axial depth to hand to SetLens.
+	struct Pick { float distance, depth; };
+	Pick PickFocus(uint32_t x, uint32_t y) { Pick p{}; check(mirt_group_pick_focus(group_, x, y, &p.distance, &p.depth), "mirt_group_pick_focus"); return p; }
 	void Resize(uint32_t new_width, uint32_t new_height) {                 // Renderer.hpp:53-63
 		width = new_width; height = new_height;
 		framebuffer.assign(static_cast<size_t>(width) * height * 4, 0.0f);
@@ -221,6 +236,7 @@ private:
 	}
 	mirt_group* group_ = nullptr;
 	mirt_policy policy_{};
+	bool lens_follows_camera_ = false;
 };
 
 } // namespace mirt

@@ -86,11 +86,15 @@ def quat_look_at(direction, up=(0.0, 1.0, 0.0)) -> np.ndarray:
 
 @dataclass
 class Camera:
-    """Camera / View / Projection fields the hot path reads (Camera.hpp:61-88)."""
+    """Camera / View / Projection fields the hot path reads (Camera.hpp:61-88), and the lens fields the reference carries and never
+    reads (Camera.hpp:6-45,64): they reach the renderer only through Renderer(lens=True) / set_lens()."""
     eye: tuple = (0.0, 0.0, 0.0)
     direction: tuple = (0.0, 0.0, -1.0)
     focal_length: float = 50.0
     exposure: float = 1.0
+    focus_distance: float = 1.0      # Camera.hpp:64; world units (the right-click pick stores a hit distance here, Application.cpp:298)
+    f_number: float = 16.0           # Camera.hpp:64
+    unit_mm: float = 1000.0          # length of one world unit in millimetres: the reference never connects focal_length's mm to the scene
     pos: np.ndarray = field(init=False)
     orient: np.ndarray = field(init=False)     # x, y, z, w
     half_width: np.float32 = field(init=False, default=f32(0.5))
@@ -108,6 +112,11 @@ class Camera:
         self.half_width = f32(width) * f32(0.5)
         inv_half_tan = (f32(-2.0) / f32(24.0)) * f32(self.focal_length)
         self.z = self.half_height * inv_half_tan
+
+    @property
+    def aperture_radius(self) -> np.float32:
+        """Projection::calc_aperture (Camera.hpp:17-19,24), focal_length / (2 * f_number) in mm, divided by unit_mm: world units."""
+        return (f32(self.focal_length) / (f32(2.0) * f32(self.f_number))) / f32(self.unit_mm)
 
 
 @dataclass

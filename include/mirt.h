@@ -147,6 +147,25 @@ int mirt_set_scene(mirt_ctx* ctx,
 int mirt_set_camera(mirt_ctx* ctx, const float pos[3], const float orient_xyzw[4],
                     float half_width, float half_height, float z, float exposure);
 
+/* ---- thin lens: depth of field and focus picking ------------------------------------------------------------------------
+ * The reference's camera carries focus_distance, f_number and aperture_radius (Camera.hpp:6-45), its UI edits them (Application.cpp:413-417) and
+ * a right-click picks the focus distance (Application.cpp:271-304), but generate_ray ignores all of it (Camera.hpp:80-88): the reference defines
+ * no lens, so this mode has no oracle.  Here: a thin lens of radius aperture_radius around view.pos in the camera's x/y plane, focused on the
+ * plane perpendicular to the optical axis at axial depth focus_depth, both in WORLD units (hosts convert the reference's millimetres; see
+ * mirt_host.hpp / scene.py `unit_mm`).  Per sample: the pinhole direction d of Camera::generate_ray, unchanged; a lens point from two draws at the
+ * seed offset the reference reserves and never uses (2 * max_bounces, Renderer.hpp:107) through its own disk mapping (Sampling.hpp:85-104);
+ * the ray runs from the lens point through pos + d * (focus_depth / dot(d, forward)).  Arithmetic: csrc/device_math.hpp lens_ray.
+ * aperture_radius = 0 (the default) IS the pinhole path: the same kernels and the same words as a context that never called this.
+ * With a lens every camera ray walks the tree (the policy.trace_primary_rays = 1 route; mirt_get_policy still reports the caller's value).
+ * Both arguments finite, aperture_radius >= 0, focus_depth > 0 when aperture_radius > 0: else MIRT_ERR_ARG.  Not available in exact stream
+ * order (that mode replays the reference): aperture_radius > 0 under stream order 1, and mirt_set_stream_order(ctx, 1) with a lens on, return
+ * MIRT_ERR_STATE.  Deferred mirt_accumulate_async calls are launched first, under the old lens; the accumulator is NOT reset (the caller
+ * does, as Application.cpp:510). */
+int mirt_set_lens(mirt_ctx* ctx, float aperture_radius, float focus_depth);
+int mirt_get_lens(const mirt_ctx* ctx, float* aperture_radius, float* focus_depth);
+/* The right-click pick, Application.cpp:271-304: one un-jittered (samples = {0.5, 0.5}) PINHOLE ray through pixel (x, y), lens or no lens, through the closest-hit traversal the context is configured with.  distance = tfar, INFINITY on a miss (:298); depth = distance * min(dot(d, forward), 1) is the axial depth of the hit, the value to hand to mirt_set_lens.  Changes no state; any pixel of the image, owned by this context or not; x >= width or y >= height: MIRT_ERR_ARG. */
+int mirt_pick_focus(mirt_ctx* ctx, uint32_t x, uint32_t y, float* distance, float* depth);
+
 int mirt_set_policy(mirt_ctx* ctx, const mirt_policy* policy);
 int mirt_get_policy(const mirt_ctx* ctx, mirt_policy* policy);   /* with the values in effect for max_batch / streams left at 0 */
 /* gloss_decay_table of Renderer.hpp:212 (policy.brdf = 1): decay[b] is mixed into the GGX alpha of the hits of bounce b; bounces at
@@ -269,6 +288,8 @@ int mirt_group_set_scene(mirt_group* group,
                          const int32_t* lights, uint32_t n_lights,
                          const float ambient_color[3], const float* hdri_rgba, uint32_t hdri_w, uint32_t hdri_h);
 int mirt_group_set_camera(mirt_group* group, const float pos[3], const float orient_xyzw[4], float half_width, float half_height, float z, float exposure);
+int mirt_group_set_lens(mirt_group* group, float aperture_radius, float focus_depth);   /* mirt_set_lens on every member */
+int mirt_group_pick_focus(mirt_group* group, uint32_t x, uint32_t y, float* distance, float* depth);   /* mirt_pick_focus on the first member */
 int mirt_group_set_policy(mirt_group* group, const mirt_policy* policy);
 int mirt_group_set_gloss_decay(mirt_group* group, const float* decay, uint32_t n);
 int mirt_group_set_stream_order(mirt_group* group, uint32_t exact);             /* mirt_set_stream_order on every member */

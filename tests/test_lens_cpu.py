@@ -1,0 +1,182 @@
+"""Thin-lens depth of field, the part that needs no device: the interface at every layer, the numpy twin (tests/lens_twin.py) pinned to the
+known answers and golden vectors the oracle tests use, the twin against a float64 thin-lens definition written from the textbook, the seed
+offset of the lens draws, and the host mirror's arithmetic.  The reference defines no lens, so none of this is oracle parity."""
+import ctypes as C
+import inspect
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import definitions as df
+import lens_twin as lt
+import oracle_binding as ob
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+f32, f64 = np.float32, np.float64
+NEW_NAMES = ("mirt_set_lens", "mirt_get_lens", "mirt_pick_focus", "mirt_group_set_lens", "mirt_group_pick_focus")
+LENSES = ((0.02, 0.8), (0.05, 1.5), (0.25, 4.0), (0.004, 12.0))          # (A, focus_depth), world units
+
+
+def cameras(mirt):
+    return (("default9", mirt.scene.default9(), 16), ("S1000", mirt.scene.synthetic(1000, ambient=0.5), 5))
+
+
+def test_lens_interface_is_declared_at_every_layer(mirt):
+    header = open(os.path.join(ROOT, "include", "mirt.h")).read()
+    declared = set(re.findall(r"^int\s+(mirt_\w+)\s*\(", header, flags=re.M))
+    lib = mirt.load_library()
+    raw = C.CDLL(mirt.LIB_PATH)
+    for n in NEW_NAMES:
+        assert n in declared, f"{n} is not declared (on one line) in include/mirt.h"
+        assert "aov" not in n
+        assert hasattr(raw, n), f"{n} is not exported by libmirt.so"
+        assert n in lib._declared, f"{n} is not bound in Python"
+    assert "int mirt_set_camera(mirt_ctx* ctx, const float pos[3], const float orient_xyzw[4],\n                    float half_width, float half_height, float z, float exposure);" in header
+    assert C.sizeof(mirt.Policy) == 48
+    for cls in (mirt.Renderer, mirt.GroupRenderer):
+        assert inspect.signature(cls).parameters["lens"].default is False
+        for method in ("set_lens", "lens", "pick_focus"):
+            assert callable(getattr(cls, method))
+    # null-context calls
+    a, d = C.c_float(0), C.c_float(0)
+    assert lib.mirt_set_lens(None, 0.1, 1.0) < 0 and lib.mirt_get_lens(None, C.byref(a), C.byref(d)) < 0
+    assert lib.mirt_pick_focus(None, 0, 0, C.byref(a), C.byref(d)) < 0
+    assert lib.mirt_group_set_lens(None, 0.1, 1.0) < 0 and lib.mirt_group_pick_focus(None, 0, 0, C.byref(a), C.byref(d)) < 0
+
+
+# ---- the twin's parts against the answers the oracle is held to --------------------------------------------------------------------------
+def test_twin_fast_sincos_equals_the_golden_vectors():
+    d = np.load(os.path.join(GOLDEN, "math_vectors.npz"))
+    s, c = lt.fast_sincos(d["sincos_x"])
+    assert np.array_equal(s.view(np.uint32), d["sincos_s"].view(np.uint32))
+    assert np.array_equal(c.view(np.uint32), d["sincos_c"].view(np.uint32))
+
+
+def test_twin_rng_equals_the_known_answers(oracle_lib):
+    kat = {                                                         # tests/test_oracle_cpu.py test_rng_kat
+        (1, 0): (0xEF386249, [0x244781FE, 0xF6C171EC, 0x519DB614]),
+        (1, 33): (0x56410662, [0x3989A65F, 0xCA475290, 0x6C1A075D]),
+        (1, 8415): (0x733AA5F5, [0x8D032E4D, 0x5E636987, 0x789D5B7E]),
+        (2, 0): (0xF32E75BE, [0x87C870BC, 0xBDC3E819, 0x3F6B7189]),
+        (5, 8455): (0xD9B98C80, [0x77AE2422, 0x286451C6, 0x1F3C4EA1]),
+        (1, 553648095): (0xA71BCD85, [0xA3B1A1D4, 0x420F7B06, 0x251CD6B0]),
+    }
+    xs = np.array([k[0] for k in kat], dtype=np.uint32); ys = np.array([k[1] for k in kat], dtype=np.uint32)
+    state = lt.hash_2d(xs, ys)
+    assert [int(v) for v in state] == [v[0] for v in kat.values()]
+    for k in range(3):
+        out, state = lt.pcg_generate(state)
+        assert [int(v) for v in out] == [v[1][k] for v in kat.values()]
+    f, _ = lt.rand_unit_float(np.array([0xEF386249], dtype=np.uint32))
+    assert f[0] == np.float32(0.1417161226272583)
+    # ... and against the oracle's generator on a sweep
+    rs = np.random.RandomState(7)
+    x = rs.randint(0, 2 ** 32, 500, dtype=np.uint64).astype(np.uint32); y = rs.randint(0, 2 ** 32, 500, dtype=np.uint64).astype(np.uint32)
+    h = lt.hash_2d(x, y)
+    u, _ = lt.rand_unit_float(h)
+    for i in range(500):
+        assert oracle_lib.orc_hash_2d(int(x[i]), int(y[i])) == int(h[i])
+        s = C.c_uint32(int(h[i]))
+        assert np.float32(oracle_lib.orc_make_unit_float(oracle_lib.orc_pcg_generate(C.byref(s)))) == u[i]
+
+
+def test_twin_pinhole_direction_equals_the_oracle(mirt):
+    """pinhole_dir (used for the pick's centre ray) restates Camera::generate_ray: with the oracle's own jitter it gives the oracle's words."""
+    for name, sc, mb in cameras(mirt):
+        o = ob.Oracle(sc, max_bounces=mb); o.Resize(64, 64)
+        p, d = o.raygen(3)
+        seed = lt.seeds(np.arange(16), mb)
+        rng = lt.hash_2d(np.full(seed.shape, 3, dtype=np.uint32), seed)
+        s0, rng = lt.rand_unit_float(rng); s1, rng = lt.rand_unit_float(rng)
+        tile = np.arange(16 * 256) // 256; ID = np.arange(16 * 256) % 256
+        x = 16 * (tile % 4) + (ID & 15); y = 16 * (tile // 4) + (ID >> 4)
+        cam = sc.camera
+        v = [x.astype(f32) + s0 - f32(cam.half_width), y.astype(f32) + s1 - f32(cam.half_height), np.full(x.shape, f32(cam.z), dtype=f32)]
+        got = np.stack(lt.normalize3(lt.quat_rotate(cam.orient, v))).astype(f32)
+        assert np.array_equal(got.view(np.uint32), d.view(np.uint32)), name
+        o.close()
+
+
+# ---- the twin against the float64 thin lens ----------------------------------------------------------------------------------------------
+def test_seed_offset_of_the_lens_draws_collides_with_no_draw_of_the_path():
+    """Stride 2 * max_bounces + 1 ("+1 for camera", Renderer.hpp:107); the path draws at offsets 0 .. 2 * max_bounces - 3 (lens_twin.draw_offsets);
+    the lens at 2 * max_bounces: unused by the path, and below the stride, so it is no other pixel's offset either."""
+    for mb in (1, 2, 16):
+        stride, off = 2 * mb + 1, lt.lens_offset(mb)
+        used = lt.draw_offsets(mb)
+        assert off == 2 * mb and off not in used and max(used) < off < stride
+        assert max(used) == max(0, 2 * mb - 3)
+        path_draws = {i * stride + o for i in range(4096) for o in used}
+        lens_draws = {i * stride + off for i in range(4096)}
+        assert not (path_draws & lens_draws) and len(lens_draws) == 4096
+
+
+@pytest.mark.parametrize("A,fd", LENSES)
+def test_twin_rays_meet_the_float64_thin_lens(mirt, A, fd):
+    """For every sample ray of every pixel of default9's and S(1000)'s cameras at 64 x 64, three accumulations:
+    * the origin lies in the lens plane {x : (x - pos) . fwd = 0}: O_k = fl(pos_k + e_k) carries one rounding at the magnitude of O, u |O_k|, hence
+      |(O - pos) . fwd| <= 2u (|pos| + A), plus A times the 16u by which binary32 right / up can lean out of the float64 plane;
+    * within the disk: |O - pos| <= A (1 + 4e-6) + 2u (|pos| + A) - rho = sqrt(u0) <= 1, fast_sincos is within 2e-6 of sin / cos (asserted in
+      tests/test_oracle_cpu.py), so lx^2 + ly^2 <= (1 + 2.9e-6)^2;
+    * the ray passes the float64 focus point within FOCUS_K u (|pos| + focus_depth / cos(theta)) (lens_twin.FOCUS_K carries the derivation)."""
+    for name, sc, mb in cameras(mirt):
+        o = ob.Oracle(sc, max_bounces=mb); o.Resize(64, 64)
+        cam = sc.camera
+        pos = np.asarray(cam.pos, dtype=f64); npos = np.linalg.norm(pos)
+        right, up, fwd = lt.camera_axes(cam, f64)
+        worst = 0.0
+        for acc in (1, 2, 7):
+            _, d = o.raygen(acc)
+            O, D = lt.oracle_lens_rays(o, acc, A, fd)
+            e = O.astype(f64).T - pos[None, :]
+            assert np.abs(e @ fwd).max() <= 2 * lt.U * (npos + A) + 16 * lt.U * A, name
+            assert np.linalg.norm(e, axis=1).max() <= A * (1 + 4e-6) + 2 * lt.U * (npos + A), name
+            F, cos = lt.focus_points64(cam, d, fd)
+            assert cos.min() >= 0.58
+            dist = lt.distance_to_line(F, O, D)
+            bound = lt.FOCUS_K * lt.U * (npos + fd / cos)
+            worst = max(worst, float((dist / bound).max()))
+            assert (dist <= bound).all(), f"{name}: a ray passes its focus point at {(dist / bound).max():.2f} of the bound"
+            assert np.abs(np.linalg.norm(D.astype(f64), axis=0) - 1).max() <= 4 * lt.U
+        print(f"lens/{name}/A={A}/fd={fd}: worst distance to the focus point = {worst:.3f} of the bound")
+        o.close()
+
+
+def test_lens_points_are_uniform_over_the_disk(mirt):
+    """16 rings of equal area x 16 sectors = 256 cells of equal area, 20 480 lens points (64 x 64 pixels x 5 accumulations of default9): chi-square
+    below the upper 1e-6 quantile for 255 degrees of freedom, 377.08 - the threshold and cell count of the `hemisphere` row of DESIGN.md §2."""
+    seed = lt.seeds(np.arange(16), 16)
+    cells = np.zeros(256)
+    for acc in range(1, 6):
+        lx, ly, _, _ = lt.lens_points(acc, seed, 16)
+        r2 = lx.astype(f64) ** 2 + ly.astype(f64) ** 2
+        ring = np.minimum((r2 * 16).astype(int), 15)
+        sector = np.minimum(((np.arctan2(ly.astype(f64), lx.astype(f64)) / (2 * math.pi)) % 1.0 * 16).astype(int), 15)
+        np.add.at(cells, ring * 16 + sector, 1)
+    n = cells.sum(); assert n == 20480
+    chi2 = float(((cells - n / 256) ** 2 / (n / 256)).sum())
+    print(f"lens/disk chi-square = {chi2:.1f}")
+    assert chi2 < df.CHI2_255_P1E6
+
+
+# ---- host mirror ------------------------------------------------------------------------------------------------------------------------
+def test_camera_lens_fields_and_aperture(mirt):
+    Camera = mirt.scene.Camera
+    c = Camera()
+    assert (c.focus_distance, c.f_number, c.unit_mm, c.focal_length) == (1.0, 16.0, 1000.0, 50.0)          # Camera.hpp:64
+    assert c.aperture_radius == (f32(50.0) / (f32(2.0) * f32(16.0))) / f32(1000.0) and c.aperture_radius.dtype == f32
+    c = Camera(eye=(0, 0, 3), direction=(0, 0, -1), focal_length=85.0, exposure=2.0, f_number=1.4, unit_mm=10.0, focus_distance=7.5)
+    assert c.aperture_radius == (f32(85.0) / (f32(2.0) * f32(1.4))) / f32(10.0)
+    assert abs(float(c.aperture_radius) - 85.0 / 2.8 / 10.0) < 1e-5
+    # the old positional form and every existing scene keep their pinhole fields
+    old = Camera((0, 0, 1), (0, 0, -1), 40.0, 1.0)
+    assert (old.focal_length, old.exposure, old.f_number) == (40.0, 1.0, 16.0)
+    assert mirt._lens_arguments(c, None, None) == (float(c.aperture_radius), 7.5)
+    assert mirt._lens_arguments(c, 0.0, 2.0) == (0.0, 2.0)
+    header = open(os.path.join(ROOT, "cpu-raytracing-experiments_amd", "csrc", "mirt_host.hpp")).read()
+    for text in ("focus_distance = 1.0f", "f_number = 16.0f", "unit_mm = 1000.0f", "aperture_radius()", "SetLens", "PickFocus"):
+        assert text in header, text
