@@ -143,7 +143,13 @@ int mirt_set_scene(mirt_ctx* ctx,
                    const float ambient_color[3], const float* hdri_rgba, uint32_t hdri_w, uint32_t hdri_h);
 
 /* scene.camera fields the path reads (Camera.hpp:80-88; Renderer.hpp:439): view.pos, view.orient (x,y,z,w),
- * projection.half_width / half_height / z, exp. */
+ * projection.half_width / half_height / z, exp.
+ * orient may be any finite quaternion and is used as handed over (glm's quat * vec3, then normalize: for |q| = s that is the
+ * map (1 - s^2) I + s^2 R, a shear unless s = 1; the reference's own look-at returns one of norm sqrt(1/2) for a direction
+ * parallel to up).  The camera rays' candidate lists bound a pixel's samples by a cone that assumes a rotation, with 1 % to
+ * spare: a camera with ||q|^2 - 1| >= 1e-4 gets no lists — its camera rays walk the tree, as with trace_primary_rays = 1 —
+ * and below that the stretch stays under 2.1e-4.  Results are identical to trace_primary_rays = 1 either way
+ * (tests/test_views_and_scales.py). */
 int mirt_set_camera(mirt_ctx* ctx, const float pos[3], const float orient_xyzw[4],
                     float half_width, float half_height, float z, float exposure);
 
