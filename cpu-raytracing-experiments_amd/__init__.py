@@ -112,6 +112,7 @@ def load_library():
         "mirt_debug_trace_shadow": [P, C.c_size_t, vp, vp, vp, vp],
         "mirt_debug_math": [P, i32, C.c_size_t, vp, vp],
         "mirt_debug_info": [P, vp],
+        "mirt_debug_tree": [P, vp, C.c_size_t, vp],
         "mirt_debug_primary_lists": [P, vp],
         "mirt_debug_allow_half_boxes": [P, i32],
     }
@@ -454,6 +455,16 @@ class Renderer:
         d["wide"] = (d["half_boxes"] >> 1) & 1             # 64-B binary16 records of up to four children
         d["half_boxes"] &= 1
         return d
+
+    def debug_tree(self):
+        """The records the trace kernels walk, read back from the device: (uint32 words shaped [records, words per record],
+        {"records", "record_bytes", "layout" (0 f32 child pairs, 1 binary16 child pairs, 2 4-wide binary16), "depth"})."""
+        info = (C.c_uint32 * 4)()
+        self._check(self._lib.mirt_debug_tree(self._ctx, None, 0, info))
+        n, rec_bytes = int(info[0]), int(info[1])
+        words = np.zeros((n, rec_bytes // 4), dtype=np.uint32)
+        self._check(self._lib.mirt_debug_tree(self._ctx, _ptr(words), words.nbytes, info))
+        return words, dict(zip(("records", "record_bytes", "layout", "depth"), [int(v) for v in info]))
 
     def debug_primary_lists(self) -> list:
         """hist[n] = pixels whose candidate list holds n spheres (n = 0..7), hist[8] = 8 or more, hist[9] = pixels without a list."""

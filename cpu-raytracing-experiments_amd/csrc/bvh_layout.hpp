@@ -294,7 +294,7 @@ inline std::string build_records(const mirt_bvh_node* nodes, uint32_t n_nodes, c
 		recs.assign(16, 0.0f);
 		put(0, 0, box[0], leaf_of(nodes[0]));
 		put(0, 1, nothing, leaf_of(nodes[0]));
-		*max_depth_out = 1;
+		*max_depth_out = 2;                               // the record and the leaf level below it, as for every other tree
 		return "";
 	}
 	// breadth-first numbering of inner nodes

@@ -1390,6 +1390,22 @@ int mirt_debug_info(mirt_ctx* c, uint32_t out[8]) {
 	out[5] = p.launch_bytes; out[6] = p.wgs_per_cu; out[7] = static_cast<uint32_t>(c->n_cu);
 	return MIRT_OK;
 }
+int mirt_debug_tree(mirt_ctx* c, void* dst, size_t capacity_bytes, uint32_t info[4]) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!info) return fail(c, MIRT_ERR_ARG, "debug_tree: info is NULL");
+	if (!c->have_scene) return fail(c, MIRT_ERR_STATE, "mirt_set_scene has not been called");
+	const SceneDev& s = c->scene;
+	const uint32_t rec_bytes = (s.half_boxes && !s.wide) ? 32u : 64u;
+	info[0] = s.n_recs; info[1] = rec_bytes; info[2] = s.wide ? 2u : s.half_boxes ? 1u : 0u; info[3] = c->bvh_depth;
+	if (!dst) return MIRT_OK;
+	const size_t bytes = static_cast<size_t>(s.n_recs) * rec_bytes;
+	if (capacity_bytes < bytes) return fail(c, MIRT_ERR_ARG, "debug_tree: %zu bytes of capacity, the records take %zu", capacity_bytes, bytes);
+	if (bytes == 0) return MIRT_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	HIP_TRY(c, hipMemcpy(dst, s.recs, bytes, hipMemcpyDeviceToHost));             // the device copy the kernels walk, not SceneRecords' host vectors
+	return MIRT_OK;
+}
 int mirt_debug_allow_half_boxes(mirt_ctx* c, int allow) { if (!c) return MIRT_ERR_ARG; c->allow_half = allow != 0; return MIRT_OK; }
 
 } // extern "C"

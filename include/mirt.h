@@ -352,6 +352,11 @@ int mirt_debug_math(mirt_ctx* ctx, int fn, size_t n, const float* in, float* out
  * records are in use, bit 1: they are the 64-B records of up to four children (else 32-B child pairs), out[5] dynamic LDS
  * bytes of a trace workgroup, out[6] trace workgroups per CU, out[7] CUs. */
 int mirt_debug_info(mirt_ctx* ctx, uint32_t out[8]);
+/* Read-back of the records the trace kernels walk, copied from the device after the context's stream has been synchronised
+ * (a host-built tree as uploaded, a GPU-built one as built).  info[0] records, info[1] bytes per record (64 / 32 / 64),
+ * info[2] layout: 0 f32 child pairs, 1 binary16 child pairs, 2 binary16 records of up to four children, info[3] tree depth.
+ * dst == NULL: only `info` is filled.  MIRT_ERR_ARG when capacity_bytes < info[0] * info[1]. */
+int mirt_debug_tree(mirt_ctx* ctx, void* dst, size_t capacity_bytes, uint32_t info[4]);
 /* Length histogram of the per-pixel candidate lists of the current scene / camera / size (policy.trace_primary_rays = 0 path):
  * hist[n] = local pixels whose bundle of camera rays can hit n spheres for n = 0..7, hist[8] = 8 or more (lists hold up to 31), hist[9] = pixels without a list (traced normally). */
 int mirt_debug_primary_lists(mirt_ctx* ctx, uint32_t hist[10]);
