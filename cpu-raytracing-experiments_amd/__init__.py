@@ -25,6 +25,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmirt.so")
 
 MIRT_OK, MIRT_NOT_READY = 0, 1
+MIRT_NOT_CONVERGED = 2                            # mirt.h: accumulate_until gave up at max_accumulations
+NOISE_BINS = 2048                                 # mirt.h MIRT_NOISE_BINS
 AOV_DEPTH, AOV_NORMAL, AOV_ALBEDO = 0, 1, 2       # mirt.h MIRT_AOV_*
 AOV_PLANES = 7
 KERNEL_CLASSES = ("raygen", "trace", "shade", "shadow", "resolve")
@@ -50,6 +52,21 @@ class Counters(C.Structure):
 
 class KernelTimes(C.Structure):
     _fields_ = [("ms", C.c_double * 5), ("launches", C.c_uint64 * 5)]
+
+
+class NoiseStats(C.Structure):
+    """mirt_noise_stats"""
+    _fields_ = [("owned_pixels", C.c_uint64), ("finite_pixels", C.c_uint64), ("nonfinite_pixels", C.c_uint64), ("max", C.c_float), ("_pad", C.c_uint32),
+                ("mean", C.c_double)]
+
+    def as_dict(self):
+        return {"owned_pixels": int(self.owned_pixels), "finite_pixels": int(self.finite_pixels), "nonfinite_pixels": int(self.nonfinite_pixels),
+                "max": float(self.max), "mean": float(self.mean)}
+
+
+class StopRule(C.Structure):
+    """mirt_stop_rule"""
+    _fields_ = [("target", C.c_float), ("quantile", C.c_float), ("floor", C.c_float), ("check_every", C.c_uint32), ("max_accumulations", C.c_uint32)]
 
 
 def build(force: bool = False) -> str:
@@ -104,6 +121,9 @@ def load_library():
         "mirt_aov_device": [P, C.POINTER(vp), C.POINTER(C.c_size_t)],
         "mirt_load_aov": [P, vp, i32],
         "mirt_render_aov": [P, i32, vp],
+        "mirt_noise": [P, f, vp, vp, vp, C.POINTER(NoiseStats)],
+        "mirt_noise_quantile": [vp, C.c_double, C.POINTER(f)],
+        "mirt_accumulate_until": [P, C.POINTER(StopRule), C.POINTER(NoiseStats), C.POINTER(u32)],
         "mirt_get_counters": [P, C.POINTER(Counters)],
         "mirt_get_kernel_times": [P, C.POINTER(KernelTimes), i32],
         "mirt_get_stream": [P, C.POINTER(vp)],
@@ -145,6 +165,8 @@ def load_library():
         "mirt_group_aov_floats": [G, C.POINTER(C.c_size_t)],
         "mirt_group_read_aov": [G, vp],
         "mirt_group_render_aov": [G, i32, vp],
+        "mirt_group_noise": [G, f, vp, vp, vp, C.POINTER(NoiseStats)],
+        "mirt_group_accumulate_until": [G, C.POINTER(StopRule), C.POINTER(NoiseStats), C.POINTER(u32)],
         "mirt_group_rccl_selftest": [i32, C.c_size_t],
     })
     for name, argtypes in sigs.items():
@@ -210,6 +232,45 @@ def _lens_arguments(camera: Camera, aperture_radius, focus_depth):
 
 def _decay_array(decay) -> np.ndarray:
     return np.ascontiguousarray([] if decay is None else decay, dtype=np.float32).reshape(-1)
+
+
+def noise_quantile(hist, q: float):
+    """mirt_noise_quantile (host code, no GPU): the UPPER EDGE of the histogram bin that holds the q-quantile (q in (0, 1]) of the usable
+    pixels — at most 12.5 % above the quantile itself.  None for an empty histogram."""
+    lib = load_library()
+    h = np.ascontiguousarray(hist, dtype=np.uint32).reshape(-1)
+    if h.size != NOISE_BINS:
+        raise ValueError(f"hist must hold {NOISE_BINS} words")
+    v = C.c_float(0)
+    rc = lib.mirt_noise_quantile(_ptr(h), float(q), C.byref(v))
+    if rc < 0:
+        raise MirtError(f"mirt_noise_quantile failed ({rc}): q = {q} is not in (0, 1]")
+    return v.value if rc == MIRT_OK else None
+
+
+def _noise(call, check, handle, height, width, n_tiles, floor, want_map, map_out):
+    """Shared by Renderer.noise and GroupRenderer.noise: -> dict, or None while the frame is not due."""
+    img = None
+    if map_out is not None:
+        if map_out.dtype != np.float32 or map_out.shape != (height, width) or not map_out.flags.c_contiguous:
+            raise ValueError(f"map_out must be a C-contiguous float32 array of shape {(height, width)}")
+        img = map_out
+    elif want_map:
+        img = np.zeros((height, width), dtype=np.float32)
+    tiles = np.zeros((n_tiles, 4), dtype=np.float32)
+    hist = np.zeros(NOISE_BINS, dtype=np.uint32)
+    st = NoiseStats()
+    rc = check(call(handle, float(np.float32(floor)), _ptr(img) if img is not None else None, _ptr(tiles) if n_tiles else None, _ptr(hist), C.byref(st)))
+    if rc != MIRT_OK:
+        return None
+    return {**st.as_dict(), "tiles": tiles, "hist": hist, "map": img}
+
+
+def _accumulate_until(call, check, handle, buckets, target, quantile, floor, check_every, max_accumulations):
+    rule = StopRule(float(target), float(quantile), float(floor), int(check_every if check_every is not None else 4 * buckets), int(max_accumulations))
+    st, issued = NoiseStats(), C.c_uint32(0)
+    rc = check(call(handle, C.byref(rule), C.byref(st), C.byref(issued)))
+    return {"converged": rc == MIRT_OK, "issued": issued.value, **st.as_dict()}
 
 
 class Renderer:
@@ -436,6 +497,26 @@ class Renderer:
         img = _aov_image(self.height, self.width, which, out)
         rc = self._check(self._lib.mirt_render_aov(self._ctx, int(which), _ptr(img)))
         return img if rc == MIRT_OK else None
+
+    # -- noise estimate (mirt.h "per-pixel noise estimate") ----------------------------------------------------
+    noise_quantile = staticmethod(noise_quantile)
+
+    def _local_tiles(self) -> int:
+        n = C.c_size_t(0)
+        self._check(self._lib.mirt_accumulator_floats(self._ctx, C.byref(n)))
+        return n.value // (self.policy.buckets * 768)
+
+    def noise(self, floor: float = 0.0, want_map: bool = False, map_out: np.ndarray = None):
+        """Per-pixel relative standard error of the mean of the bucket means (mirt_noise) -> {"owned_pixels", "finite_pixels",
+        "nonfinite_pixels", "max", "mean", "tiles": (local tiles, 4) f32 {max, mean, usable, non-finite}, "hist": 2048 u32, "map": (height,
+        width) f32 or None}; only this context's tiles of the map are written (into `map_out` when given).  None, and nothing written,
+        while accumulations is 0 or not a multiple of `buckets`.  Changes no state."""
+        return _noise(self._lib.mirt_noise, self._check, self._ctx, self.height, self.width, self._local_tiles(), floor, want_map, map_out)
+
+    def accumulate_until(self, target: float, quantile: float = 0.95, floor: float = 0.0, check_every: int = None, max_accumulations: int = 1000):
+        """Accumulate `check_every` (default 4 x buckets) at a time until the `quantile` of the per-pixel noise is <= target and no pixel is
+        non-finite, or `max_accumulations` is reached (mirt_accumulate_until) -> {"converged", "issued", and the stats of the last check}."""
+        return _accumulate_until(self._lib.mirt_accumulate_until, self._check, self._ctx, self.policy.buckets, target, quantile, floor, check_every, max_accumulations)
 
     def counters(self) -> dict:
         c = Counters()
@@ -669,6 +750,16 @@ class GroupRenderer:
         img = _aov_image(self.height, self.width, which, out)
         rc = self._check(self._lib.mirt_group_render_aov(self._g, int(which), _ptr(img)))
         return img if rc == MIRT_OK else None
+
+    noise_quantile = staticmethod(noise_quantile)
+
+    def noise(self, floor: float = 0.0, want_map: bool = False, map_out: np.ndarray = None):
+        """Renderer.noise of the whole image, without a gather: every member reads its own slab; "tiles" is in LaunchIndex order."""
+        return _noise(self._lib.mirt_group_noise, self._check, self._g, self.height, self.width, (self.width // 16) * (self.height // 16), floor, want_map, map_out)
+
+    def accumulate_until(self, target: float, quantile: float = 0.95, floor: float = 0.0, check_every: int = None, max_accumulations: int = 1000):
+        """Renderer.accumulate_until on the whole group."""
+        return _accumulate_until(self._lib.mirt_group_accumulate_until, self._check, self._g, self.policy.buckets, target, quantile, floor, check_every, max_accumulations)
 
     def counters(self) -> dict:
         c = Counters()

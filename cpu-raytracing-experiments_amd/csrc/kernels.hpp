@@ -1849,6 +1849,78 @@ __global__ __launch_bounds__(kBlock) void k_resolve(const float* __restrict__ ac
 }
 
 // ------------------------------------------------------------------------------------------------
+// NOISE ESTIMATE — mirt_noise (mirt.h, "per-pixel noise estimate"): the relative standard error of the mean of the bucket means
+// ------------------------------------------------------------------------------------------------
+// One 256-thread workgroup per owned tile, lane ID = pixel ID: the coalesced plane reads of k_resolve.  Per pixel the quantity of mirt.h, one
+// rounding per operation in the stated order (-ffp-contract=off; IEEE division and square root).  A pixel is usable when the word of e is
+// below 0x7f800000 (finite, sign bit clear); only usable pixels enter what follows:
+//   tile maximum   on the words (for non-negative floats the order of the words is the order of the values): a wave64 xor-butterfly, then
+//                  the four wave partials through LDS — exact, whatever the order;
+//   tile sum       FIXED ORDER: inside a wave the xor-butterfly with strides 32, 16, 8, 4, 2, 1 — at each step a lane adds its partner's
+//                  partial to its own (a + b = b + a, so both lanes of a pair hold the same word), i.e. a balanced binary tree over the 64
+//                  lanes with the pairs (l, l ^ 32) at its leaves; then ((w0 + w1) + w2) + w3 over the four waves; unusable pixels add +0;
+//   tile record    {max, sum / count (0 when count = 0), count, 256 - count} as four floats;
+//   histogram      bin = word >> 20 (< 2040 for a usable pixel): LDS uint32 atomics, then the non-zero bins are added to the 2048-word
+//                  device histogram with integer atomics — integer adds, so the result does not depend on scheduling.
+constexpr uint32_t kNoiseBins = 2048u;
+constexpr uint32_t kNoiseUsableBelow = 0x7f800000u;
+constexpr uint32_t kNoiseMaxBuckets = 16u;     // one y_j per register; mirt_noise asserts that MIRT_MAX_BUCKETS fits
+__global__ __launch_bounds__(kTileSize) void k_noise(const float* __restrict__ accum, float* __restrict__ map, float4* __restrict__ tile_rec, uint32_t* __restrict__ hist,
+                                                     uint32_t first_tile, uint32_t run_tiles, uint32_t stride_tiles, uint32_t h_tiles, uint32_t width, uint32_t buckets,
+                                                     float scale, float floor_) {
+	__shared__ uint32_t bins[kNoiseBins];
+	__shared__ uint32_t w_max[kTileSize / 64u], w_cnt[kTileSize / 64u];
+	__shared__ float w_sum[kTileSize / 64u];
+	const uint32_t local = blockIdx.x, ID = threadIdx.x;
+	for (uint32_t b = ID; b < kNoiseBins; b += kTileSize) bins[b] = 0u;
+	const float* src = accum + static_cast<size_t>(local) * buckets * 3u * kTileSize + ID;
+	float y[kNoiseMaxBuckets];
+	float sum = 0.0f;
+	for (uint32_t j = 0; j < kNoiseMaxBuckets; j++) if (j < buckets) {
+		const float r = src[(static_cast<size_t>(j) * 3u) * kTileSize], g = src[(static_cast<size_t>(j) * 3u + 1u) * kTileSize], b = src[(static_cast<size_t>(j) * 3u + 2u) * kTileSize];
+		y[j] = scale * ((0.2126f * r + 0.7152f * g) + 0.0722f * b);
+		sum = j ? sum + y[j] : y[j];
+	}
+	const float mean = sum / static_cast<float>(buckets);
+	float ss = 0.0f;
+	for (uint32_t j = 0; j < kNoiseMaxBuckets; j++) if (j < buckets) {
+		const float d = y[j] - mean;
+		ss = j ? ss + d * d : d * d;
+	}
+	const float var = ss / static_cast<float>(buckets - 1u);
+	const float se = __builtin_sqrtf(var / static_cast<float>(buckets));
+	const float denom = mean + floor_;
+	const float e = denom == 0.0f ? 0.0f : se / denom;
+	if (map) {
+		const uint32_t tile = global_tile(first_tile, run_tiles, stride_tiles, local);
+		const uint32_t x = kTileRoot * (tile % h_tiles) + (ID & 15u);
+		const uint32_t yy = kTileRoot * (tile / h_tiles) + (ID >> 4);
+		map[static_cast<size_t>(yy) * width + x] = e;
+	}
+	const uint32_t word = __float_as_uint(e);
+	const bool usable = word < kNoiseUsableBelow;
+	uint32_t m = usable ? word : 0u;
+	float s = usable ? e : 0.0f;
+	for (int off = 32; off > 0; off >>= 1) {
+		m = max(m, static_cast<uint32_t>(__shfl_xor(static_cast<int>(m), off, 64)));
+		s = s + __shfl_xor(s, off, 64);
+	}
+	const unsigned long long usable_m = __ballot(usable);
+	const uint32_t wave = ID >> 6;
+	if ((ID & 63u) == 0u) { w_max[wave] = m; w_sum[wave] = s; w_cnt[wave] = static_cast<uint32_t>(__popcll(usable_m)); }
+	__syncthreads();                                                          // bins are zero, wave partials are written
+	if (usable) atomicAdd(&bins[word >> 20], 1u);
+	if (ID == 0u) {
+		const uint32_t t_max = max(max(w_max[0], w_max[1]), max(w_max[2], w_max[3]));
+		const float t_sum = ((w_sum[0] + w_sum[1]) + w_sum[2]) + w_sum[3];
+		const uint32_t n = (w_cnt[0] + w_cnt[1]) + (w_cnt[2] + w_cnt[3]);
+		tile_rec[local] = make_float4(__uint_as_float(t_max), n ? t_sum / static_cast<float>(n) : 0.0f, static_cast<float>(n), static_cast<float>(kTileSize - n));
+	}
+	__syncthreads();
+	for (uint32_t b = ID; b < kNoiseBins; b += kTileSize) { const uint32_t v = bins[b]; if (v) atomicAdd(&hist[b], v); }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Stage-level debug kernels (mirt_debug_*)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_debug_math(int fn, uint32_t n, const float* in, float* out) {

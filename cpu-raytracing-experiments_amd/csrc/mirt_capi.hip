@@ -12,10 +12,12 @@
 #include "bvh_layout.hpp"
 #include "bvh_build.hpp"
 #include "lbvh_build.hpp"
+#include "noise_host.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -115,6 +117,7 @@ struct mirt_ctx {
 	float* frame_host = nullptr;     // pinned staging copy of the framebuffer for mirt_render (pageable memory halves the copy rate)
 	size_t frame_host_bytes = 0;
 	DeviceBuffer counters;           // DevCounters
+	DeviceBuffer noise_rec, noise_hist;   // mirt_noise: one float4 record per local tile, MIRT_NOISE_BINS histogram words (allocated by the first call)
 	std::vector<PipeSlot> slots;     // batches in flight (policy.streams)
 	uint64_t planned_for = 0;        // local pixel count batch_mem_cap was planned for (0 = plan again)
 	uint32_t batch_mem_cap = 256;     // accumulations per batch the device memory allows (lowered by ensure_streams when the plan does not fit)
@@ -918,7 +921,7 @@ int mirt_destroy(mirt_ctx* c) {
 	for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
 	DeviceBuffer* bufs[] = { &c->recs, &c->recs_wide, &c->spheres, &c->prim_mat, &c->light_sphere, &c->light_emit, &c->mat_albedo, &c->mat_emission,
 	                         &c->mat_ggx, &c->hdri, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
-	                         &c->cand, &c->cand_listed, &c->cand_words };
+	                         &c->cand, &c->cand_listed, &c->cand_words, &c->noise_rec, &c->noise_hist };
 	for (DeviceBuffer* b : bufs) b->release();
 	if (c->frame_host) (void)hipHostFree(c->frame_host);
 	if (c->cand_built) (void)hipEventDestroy(c->cand_built);
@@ -1283,6 +1286,77 @@ int mirt_render(mirt_ctx* c, float* rgba_host) {
 		}
 	}
 	return MIRT_OK;
+}
+
+// ---- per-pixel noise estimate ------------------------------------------------------------------
+int mirt_noise(mirt_ctx* c, float floor, float* map_out, float* tile_out, uint32_t* hist_out, mirt_noise_stats* stats) {
+	int r = check_ready(c); if (r) return r;
+	const uint32_t k = c->policy.buckets;
+	char why[256];
+	if ((r = mirt_noise_host::check_noise_args(floor, k, why, sizeof why))) return fail(c, r, "%s", why);
+	const uint32_t issued = c->accumulations + c->deferred;
+	if (issued == 0 || (issued % k) != 0) return MIRT_NOT_READY;                                    // as mirt_render
+	{ const int fr = flush_deferred(c); if (fr) return fr; }
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, sync_all(c));
+	std::vector<float> rec(static_cast<size_t>(c->n_tiles) * 4);
+	std::vector<uint32_t> hist(MIRT_NOISE_BINS, 0u);
+	if (c->n_tiles) {
+		static_assert(kNoiseBins == MIRT_NOISE_BINS, "k_noise bins by the rule of mirt.h");
+		static_assert(MIRT_MAX_BUCKETS <= kNoiseMaxBuckets, "k_noise keeps one bucket luminance per register: every bucket mirt_set_policy accepts must fit");
+		const float scale = c->camera.exposure / static_cast<float>(c->accumulations / k);          // Renderer.hpp:439, as mirt_render
+		const size_t image_floats = static_cast<size_t>(c->width) * c->height;
+		ScopedBuffer image;
+		if (map_out) HIP_TRY(c, image.ensure(image_floats * sizeof(float)));
+		HIP_TRY(c, c->noise_rec.ensure(rec.size() * sizeof(float)));
+		HIP_TRY(c, c->noise_hist.ensure(MIRT_NOISE_BINS * sizeof(uint32_t)));
+		HIP_TRY(c, hipMemsetAsync(c->noise_hist.ptr, 0, MIRT_NOISE_BINS * sizeof(uint32_t), c->stream));
+		{ Bracket t(c, MIRT_K_RESOLVE);
+		  hipLaunchKernelGGL(k_noise, dim3(c->n_tiles), dim3(kTileSize), 0, c->stream, c->accumulator.as<float>(), map_out ? image.as<float>() : nullptr, c->noise_rec.as<float4>(),
+		                     c->noise_hist.as<uint32_t>(), c->first_tile, c->run_tiles ? c->run_tiles : 1u, c->stride_tiles, c->h_tiles, c->width, k, scale, floor); }
+		HIP_TRY(c, hipGetLastError());
+		std::vector<float> host(map_out ? image_floats : 0);                             // pixels of other contexts' tiles are never written: copy ours only
+		auto global_of = [&](uint32_t local) { return c->stride_tiles ? c->first_tile + (local / c->run_tiles) * c->stride_tiles + local % c->run_tiles : c->first_tile + local; };
+		if (map_out) {                                                                   // only the 16-row bands that hold a tile of ours come back (one n-th of the image for a group member)
+			uint32_t band = UINT32_MAX;
+			for (uint32_t local = 0; local < c->n_tiles; local++) {                       // LaunchIndices ascend with the local index: each band is met once
+				const uint32_t b = global_of(local) / c->h_tiles;
+				if (b == band) continue;
+				band = b;
+				const size_t off = static_cast<size_t>(b) * MIRT_TILE_ROOT * c->width;
+				HIP_TRY(c, hipMemcpyAsync(host.data() + off, image.as<float>() + off, static_cast<size_t>(MIRT_TILE_ROOT) * c->width * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+			}
+		}
+		HIP_TRY(c, hipMemcpyAsync(rec.data(), c->noise_rec.ptr, rec.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(c, hipMemcpyAsync(hist.data(), c->noise_hist.ptr, MIRT_NOISE_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(c, hipStreamSynchronize(c->stream));
+		if (map_out) for (uint32_t local = 0; local < c->n_tiles; local++) {
+			const uint32_t t = global_of(local);
+			const uint32_t x0 = MIRT_TILE_ROOT * (t % c->h_tiles), y0 = MIRT_TILE_ROOT * (t / c->h_tiles);
+			for (uint32_t row = 0; row < MIRT_TILE_ROOT; row++) {
+				const size_t off = static_cast<size_t>(y0 + row) * c->width + x0;
+				std::memcpy(map_out + off, host.data() + off, MIRT_TILE_ROOT * sizeof(float));
+			}
+		}
+	}
+	if (tile_out && !rec.empty()) std::memcpy(tile_out, rec.data(), rec.size() * sizeof(float));
+	if (hist_out) std::memcpy(hist_out, hist.data(), MIRT_NOISE_BINS * sizeof(uint32_t));
+	if (stats) mirt_noise_host::stats_from_tiles(rec.data(), c->n_tiles, stats);
+	return MIRT_OK;
+}
+
+int mirt_accumulate_until(mirt_ctx* c, const mirt_stop_rule* rule, mirt_noise_stats* last, uint32_t* issued) {
+	int r = check_ready(c); if (r) return r;
+	const uint32_t k = c->policy.buckets;
+	char why[256];
+	if ((r = mirt_noise_host::check_stop_rule(rule, k, c->accumulations + c->deferred, why, sizeof why))) return fail(c, r, "%s", why);
+	std::vector<uint32_t> hist(MIRT_NOISE_BINS);
+	return mirt_noise_host::accumulate_until(rule, k,
+		[&](uint32_t* a) { return mirt_get_accumulations(c, a); },
+		[&](uint32_t n) { return mirt_accumulate(c, n); },
+		[&](float floor, uint32_t* h, mirt_noise_stats* st) { return mirt_noise(c, floor, nullptr, nullptr, h, st); },
+		[&](int code, const char* text) { return fail(c, code, "%s", text); },
+		last, issued, hist.data());
 }
 
 int mirt_get_counters(mirt_ctx* c, mirt_counters* out) {

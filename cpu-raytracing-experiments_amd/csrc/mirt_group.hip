@@ -13,6 +13,7 @@
 // device (a rehearsal on a one-GPU box; RCCL refuses two ranks on one device) exchange their slabs with plain device copies.
 // Everything else here goes through the public C-ABI of the contexts.
 #include "../../include/mirt.h"
+#include "noise_host.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -347,6 +348,51 @@ int mirt_group_gather(mirt_group* g) {
 	FULL_TRY(g, "mirt_load_accumulator", mirt_load_accumulator(g->full, static_cast<const float*>(parts[0].full_ptr), 1, acc));   // in place: only `accumulations` changes
 	g->gathered = true;
 	return MIRT_OK;
+}
+// The noise estimate of the whole image without a gather: every member reads its own slab (mirt_noise); what comes back is small (16 B per
+// tile, 8 KB of histogram) and is merged here on the host.
+int mirt_group_noise(mirt_group* g, float floor, float* map_out, float* tile_out, uint32_t* hist_out, mirt_noise_stats* stats) {
+	if (!g) return MIRT_ERR_ARG;
+	const uint32_t n = static_cast<uint32_t>(g->members.size());
+	if (n == 1) { const int rc = mirt_noise(g->members[0], floor, map_out, tile_out, hist_out, stats); return rc < 0 ? gfail(g, rc, "%s", mirt_last_error(g->members[0])) : rc; }
+	char why[256];
+	if (const int bad = mirt_noise_host::check_noise_args(floor, g->buckets, why, sizeof why)) return gfail(g, bad, "%s", why);
+	if (g->width == 0) return gfail(g, MIRT_ERR_STATE, "mirt_group_resize has not been called");
+	uint32_t acc = 0;
+	{ const int rc = mirt_get_accumulations(g->members[0], &acc); if (rc < 0) return gfail(g, rc, "mirt_get_accumulations on member 0 failed"); }
+	if (acc == 0 || acc % g->buckets != 0) return MIRT_NOT_READY;                          // before any member is asked: every output untouched
+	const uint32_t h_tiles = g->width / MIRT_TILE_ROOT, v_tiles = g->height / MIRT_TILE_ROOT;
+	std::vector<float> rec(static_cast<size_t>(h_tiles) * v_tiles * 4, 0.0f), part;
+	std::vector<uint32_t> hist(MIRT_NOISE_BINS, 0u), part_hist(MIRT_NOISE_BINS);
+	for (uint32_t i = 0; i < n; i++) {
+		const uint32_t rows = i < v_tiles ? (v_tiles - i + n - 1) / n : 0u;                // member i renders tile rows i, i + n, ... (mirt_group_resize)
+		part.assign(static_cast<size_t>(rows) * h_tiles * 4, 0.0f);
+		const int rc = mirt_noise(g->members[i], floor, map_out, part.data(), part_hist.data(), nullptr);   // writes its own tiles of map_out
+		if (rc != MIRT_OK) return gfail(g, rc < 0 ? rc : MIRT_ERR_STATE, "mirt_noise on member %u (device %d): %s", i, g->devices[i], rc < 0 ? mirt_last_error(g->members[i]) : "not ready");
+		for (uint32_t j = 0; j < rows; j++)                                                 // its local tile row j is tile row i + j * n of the image
+			std::memcpy(&rec[static_cast<size_t>(i + j * n) * h_tiles * 4], &part[static_cast<size_t>(j) * h_tiles * 4], static_cast<size_t>(h_tiles) * 4 * sizeof(float));
+		for (uint32_t b = 0; b < MIRT_NOISE_BINS; b++) hist[b] += part_hist[b];
+	}
+	if (tile_out && !rec.empty()) std::memcpy(tile_out, rec.data(), rec.size() * sizeof(float));
+	if (hist_out) std::memcpy(hist_out, hist.data(), MIRT_NOISE_BINS * sizeof(uint32_t));
+	if (stats) mirt_noise_host::stats_from_tiles(rec.data(), static_cast<size_t>(h_tiles) * v_tiles, stats);
+	return MIRT_OK;
+}
+int mirt_group_accumulate_until(mirt_group* g, const mirt_stop_rule* rule, mirt_noise_stats* last, uint32_t* issued) {
+	if (!g) return MIRT_ERR_ARG;
+	if (g->members.size() == 1) { const int rc = mirt_accumulate_until(g->members[0], rule, last, issued); return rc < 0 ? gfail(g, rc, "%s", mirt_last_error(g->members[0])) : rc; }
+	const uint32_t k = g->buckets;
+	uint32_t acc = 0;
+	{ const int rc = mirt_get_accumulations(g->members[0], &acc); if (rc < 0) return gfail(g, rc, "mirt_get_accumulations on member 0 failed"); }
+	char why[256];
+	if (const int bad = mirt_noise_host::check_stop_rule(rule, k, acc, why, sizeof why)) return gfail(g, bad, "%s", why);
+	std::vector<uint32_t> hist(MIRT_NOISE_BINS);
+	return mirt_noise_host::accumulate_until(rule, k,
+		[&](uint32_t* a) { return mirt_group_get_accumulations(g, a); },
+		[&](uint32_t c) { return mirt_group_accumulate(g, c); },
+		[&](float floor, uint32_t* h, mirt_noise_stats* st) { return mirt_group_noise(g, floor, nullptr, nullptr, h, st); },
+		[&](int code, const char* text) { return gfail(g, code, "%s", text); },
+		last, issued, hist.data());
 }
 // Diagnostic: is RCCL usable from this process?  Loads librccl, makes a one-device communicator on `device` and sends n_floats to
 // itself through a grouped ncclSend / ncclRecv pair (the calls mirt_group_gather makes between distinct devices); 0 = the data arrived intact.

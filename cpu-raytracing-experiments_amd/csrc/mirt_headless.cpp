@@ -7,6 +7,13 @@
 //   mirt_headless --scene default9|furnace|bvh_test|brdf_test|synthetic:N [--size WxH] [--spp N | --frames N] [--bounces B] [--buckets K] [--brute] [--devices 0,1,..]
 //                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm] [--aov PREFIX]
 //                 [--f-number F] [--focus-distance D] [--unit-mm U] [--focus-pixel X,Y]
+//                 [--until-noise T] [--noise-quantile Q] [--noise-floor F] [--check-every N] [--max-accumulations M] [--noise-out map.pfm]
+// --until-noise T renders until converged instead of a fixed --spp (mirt_accumulate_until): N accumulations at a time (--check-every, default 4 x
+// buckets) until the Q-quantile (--noise-quantile, default 0.95) of the per-pixel noise estimate — the relative standard error of the mean of the
+// bucket means over (mean + F), F = --noise-floor — is <= T, or M accumulations (--max-accumulations, default 1000) are reached.  --noise-out writes
+// the estimate of the final accumulator as a one-channel PFM (`Pf`).  Any of these options adds ONE line to stdout after the report:
+// (converged and issued are null unless --until-noise ran the stopping loop; quantile_value is -1 when it is not finite)
+// {"noise": {"converged": ..., "issued": ..., "quantile": Q, "quantile_value": ..., "max": ..., "mean": ..., "finite_pixels": ..., "nonfinite_pixels": ...}}
 // Any of the four lens options turns the thin lens on (mirt_set_lens): camera.f_number / focus_distance / unit_mm as in Camera.hpp:64 (unit_mm =
 // millimetres per world unit, default 1000); --focus-pixel X,Y is the right-click pick (Application.cpp:271-304): it prints the picked distance and
 // focuses on its axial depth (a pick that meets the sky leaves the focus distance as given).
@@ -175,6 +182,10 @@ int main(int argc, char** argv) {
 	float f_number = 16.0f, focus_distance = 1.0f, unit_mm = 1000.0f;          // Camera.hpp:64
 	bool lens = false, pick = false;
 	uint32_t pick_x = 0, pick_y = 0;
+	std::string noise_out;
+	bool until_noise = false, noise_report = false;
+	float noise_target = 0.0f, noise_quantile = 0.95f, noise_floor = 0.0f;
+	uint32_t check_every = 0, max_accumulations = 1000;
 	if (argc == 4 && std::string(argv[1]) == "--convert-hdr") {
 		// file-format check without a GPU: read a picture like stbi_loadf does (top-down) and store it again like Image::Store does (which
 		// flips, so the rows are handed over bottom-up): the output decodes to the same texels
@@ -205,6 +216,12 @@ int main(int argc, char** argv) {
 		else if (a == "--focus-distance") { focus_distance = static_cast<float>(std::atof(next())); lens = true; }
 		else if (a == "--unit-mm") { unit_mm = static_cast<float>(std::atof(next())); lens = true; }
 		else if (a == "--focus-pixel") { if (std::sscanf(next(), "%u,%u", &pick_x, &pick_y) != 2) return 2; lens = pick = true; }
+		else if (a == "--until-noise") { noise_target = static_cast<float>(std::atof(next())); until_noise = noise_report = true; }
+		else if (a == "--noise-quantile") { noise_quantile = static_cast<float>(std::atof(next())); noise_report = true; }
+		else if (a == "--noise-floor") { noise_floor = static_cast<float>(std::atof(next())); noise_report = true; }
+		else if (a == "--check-every") { check_every = static_cast<uint32_t>(std::atoi(next())); noise_report = true; }
+		else if (a == "--max-accumulations") { max_accumulations = static_cast<uint32_t>(std::atoi(next())); noise_report = true; }
+		else if (a == "--noise-out") { noise_out = next(); noise_report = true; }
 		else if (a == "--devices") { devices.clear(); for (const char* p = next(); *p;) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p == ',') p++; } if (devices.empty()) return 2; }
 		else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
 	}
@@ -247,11 +264,22 @@ int main(int argc, char** argv) {
 		const auto t0 = std::chrono::steady_clock::now();
 		bool have_frame = false;
 		std::string frames_due;                                        // 1-based frame numbers on which Render() produced output
-		for (uint32_t frame = 0; frame < spp; frame++) {               // one UIRender per frame: Accumulate(); Render();  (Application.cpp:379-380)
+		Renderer::UntilResult until{};
+		if (until_noise) {                                             // render until converged: the frame is resolved once, at the end
+			const mirt_stop_rule rule{ noise_target, noise_quantile, noise_floor, check_every ? check_every : 4u * policy.buckets, max_accumulations };
+			until = renderer.AccumulateUntil(rule);
+			if (renderer.Render()) { have_frame = true; frames_due = std::to_string(renderer.accumulations()); }
+		}
+		else for (uint32_t frame = 0; frame < spp; frame++) {          // one UIRender per frame: Accumulate(); Render();  (Application.cpp:379-380)
 			renderer.Accumulate();
 			if (renderer.Render()) { have_frame = true; frames_due += (frames_due.empty() ? "" : ", ") + std::to_string(frame + 1); }
 		}
 		const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+		Renderer::NoiseResult nz;                                      // read before anything is printed or written: a frame count that gives no estimate fails the run as a whole
+		if (noise_report) {
+			nz = renderer.Noise(noise_floor, !noise_out.empty());
+			if (!nz.ready) { std::fprintf(stderr, "mirt_headless: no noise estimate: %u accumulations are not a positive multiple of %u buckets\n", renderer.accumulations(), policy.buckets); return 1; }
+		}
 		const mirt_counters c = renderer.counters();
 
 		// FNV-1a over the raw accumulator words: lets a test compare this C++ host against the Python host bit for bit
@@ -276,6 +304,15 @@ int main(int argc, char** argv) {
 				const std::string path = aov_prefix + "." + o.name + ".pfm";
 				if (!write_pfm_planes(path, renderer.RenderAOV(o.which), w, h, o.channels)) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
 			}
+		}
+		if (noise_report) {
+			const float qv = Renderer::NoiseQuantile(nz.hist, static_cast<double>(noise_quantile));
+			const std::string loop = until_noise ? std::string(until.converged ? "true" : "false") + ", \"issued\": " + std::to_string(until.issued) : "null, \"issued\": null";   // null: no stopping loop ran
+			std::printf("{\"noise\": {\"converged\": %s, \"quantile\": %.9g, \"quantile_value\": %.9g, \"max\": %.9g, \"mean\": %.17g, "
+			            "\"finite_pixels\": %llu, \"nonfinite_pixels\": %llu}}\n", loop.c_str(),
+			            static_cast<double>(noise_quantile), std::isfinite(qv) ? static_cast<double>(qv) : -1.0, static_cast<double>(nz.stats.max), nz.stats.mean,
+			            (unsigned long long)nz.stats.finite_pixels, (unsigned long long)nz.stats.nonfinite_pixels);
+			if (!noise_out.empty() && !write_pfm_planes(noise_out, nz.map, w, h, 1)) { std::fprintf(stderr, "cannot write %s\n", noise_out.c_str()); return 1; }
 		}
 	} catch (const std::exception& e) {
 		std::fprintf(stderr, "mirt_headless: %s\n", e.what());

@@ -223,6 +223,42 @@ public:
 		if (rc != MIRT_OK) img.clear();
 		return img;
 	}
+	// Per-pixel noise estimate from the buckets (mirt.h, mirt_noise): the relative standard error of the mean of the bucket means, read from the
+	// members' own slabs without a gather.  ready = false (and nothing filled) while accumulations is 0 or not a multiple of `buckets`.
+	struct NoiseResult {
+		bool ready = false;
+		mirt_noise_stats stats{};
+		std::vector<float> map;                                            // width * height, row 0 = y 0 (want_map)
+		std::vector<float> tiles;                                          // 4 per tile in LaunchIndex order: {max, mean, usable, non-finite}
+		std::vector<uint32_t> hist;                                        // MIRT_NOISE_BINS
+	};
+	NoiseResult Noise(float floor = 0.0f, bool want_map = false) {
+		NoiseResult r;
+		if (want_map) r.map.assign(static_cast<size_t>(width) * height, 0.0f);
+		r.tiles.assign(static_cast<size_t>(width / MIRT_TILE_ROOT) * (height / MIRT_TILE_ROOT) * 4, 0.0f);
+		r.hist.assign(MIRT_NOISE_BINS, 0u);
+		const int rc = mirt_group_noise(group_, floor, want_map ? r.map.data() : nullptr, r.tiles.empty() ? nullptr : r.tiles.data(), r.hist.data(), &r.stats);
+		check(rc, "mirt_group_noise");
+		r.ready = rc == MIRT_OK;
+		return r;
+	}
+	// Upper edge of the histogram bin that holds the q-quantile (mirt_noise_quantile; host code); NaN for an empty histogram.
+	static float NoiseQuantile(const std::vector<uint32_t>& hist, double q) {
+		float v = 0.0f;
+		if (hist.size() != MIRT_NOISE_BINS) throw std::runtime_error("NoiseQuantile: the histogram must hold MIRT_NOISE_BINS words");
+		const int rc = mirt_noise_quantile(hist.data(), q, &v);
+		if (rc < 0) throw std::runtime_error("mirt_noise_quantile: q is not in (0, 1]");
+		return rc == MIRT_OK ? v : std::nanf("");
+	}
+	// Render until converged (mirt_accumulate_until): synchronous; converged = false when max_accumulations was reached first.
+	struct UntilResult { bool converged; uint32_t issued; mirt_noise_stats last; };
+	UntilResult AccumulateUntil(const mirt_stop_rule& rule) {
+		UntilResult r{};
+		const int rc = mirt_group_accumulate_until(group_, &rule, &r.last, &r.issued);
+		check(rc, "mirt_group_accumulate_until");
+		r.converged = rc == MIRT_OK;
+		return r;
+	}
 	double gather_ms() const { double ms = 0; mirt_group_last_gather_ms(group_, &ms); return ms; }
 	mirt_group* handle() { return group_; }
 

@@ -1,0 +1,24 @@
+// noise_host.cpp — mirt_noise_quantile (include/mirt.h): pure host code, no context and no GPU.  Compiled into libmirt.so, and on its own
+// into the sanitizer program of tests/native/noise_sanitize.cpp.
+#include "../../include/mirt.h"
+
+#include <cmath>
+#include <cstring>
+
+extern "C" int mirt_noise_quantile(const uint32_t* hist, double q, float* value) {
+	if (!hist || !value || !(q > 0.0) || !(q <= 1.0)) return MIRT_ERR_ARG;   // (!(q > 0) also refuses NaN)
+	uint64_t total = 0;
+	for (uint32_t b = 0; b < MIRT_NOISE_BINS; b++) total += hist[b];
+	if (total == 0) return MIRT_NOT_READY;
+	// rank of the quantile among the sorted values, 1-based: the smallest integer >= q * total (the double product as it rounds), at least 1
+	const double want = std::ceil(q * static_cast<double>(total));
+	uint64_t rank = want < 1.0 ? 1u : static_cast<uint64_t>(want);
+	if (rank > total) rank = total;
+	uint64_t seen = 0;
+	uint32_t bin = 0;
+	for (; bin < MIRT_NOISE_BINS; bin++) { seen += hist[bin]; if (seen >= rank) break; }
+	// upper edge of bin b = the value whose word is (b + 1) << 20; from bin 0x7f7 (the last below infinity) upwards that is +infinity
+	const uint32_t word = bin >= 0x7f7u ? 0x7f800000u : (bin + 1u) << 20;
+	std::memcpy(value, &word, sizeof word);
+	return MIRT_OK;
+}

@@ -266,6 +266,62 @@ int mirt_load_aov(mirt_ctx* ctx, const float* src, int src_is_device);
  * untouched while accumulations == 0. */
 int mirt_render_aov(mirt_ctx* ctx, int which, float* out);
 
+/* ---- per-pixel noise estimate from the buckets, and render-until-converged -------------------------------------------------
+ * The `buckets` sub-images that Render() takes a median of (Renderer.hpp:41,453-455) are k independent estimates of every pixel, so their
+ * spread estimates the pixel's error.  The reference has no such read-out (its UI plots frame times); nothing of it is replayed here.
+ * THE QUANTITY, for a pixel of an owned tile, when accumulations % buckets == 0 and buckets = k >= 2; r_j, g_j, b_j the raw accumulator
+ * words of bucket j; scale = exposure / (float)(accumulations / k), the value mirt_render uses; every operation binary32, in this order,
+ * unfused, IEEE division and square root:
+ *     y_j  = scale * ((0.2126f * r_j + 0.7152f * g_j) + 0.0722f * b_j)            j = 0 .. k-1
+ *     mean = (((y_0 + y_1) + y_2) + ...) / (float)k
+ *     var  = (((d_0*d_0 + d_1*d_1) + d_2*d_2) + ...) / (float)(k - 1),            d_j = y_j - mean
+ *     se   = sqrt(var / (float)k)
+ *     e    = (mean + floor == 0) ? 0 : se / (mean + floor)
+ * `floor` (finite, >= 0, in exposure-scaled radiance units) keeps black pixels from dominating.  e is the relative standard error of the
+ * MEAN of the bucket means, before tonemapping — deliberately the error of the mean and not of the median that mirt_render shows: a
+ * firefly in one bucket raises e although the median ignores it, so e is conservative there, the safe side for a stopping rule.
+ * A pixel is USABLE when the word of e is below 0x7f800000, i.e. e is finite and its sign bit is clear.  Any non-finite bucket word
+ * gives a non-finite e; a negative mean + floor (negative radiance, which no path produces) gives an e with the sign bit set.  Such
+ * pixels keep their e in the map and are counted as non-finite; they never enter the maximum, the tile means or the histogram.
+ * Reads only the accumulator slab, so it works in every mode (either closure, lens, AOVs, exact stream order, any tile partition). */
+#define MIRT_NOISE_BINS 2048u    /* histogram bin of a usable e: its word >> 20 — eight linear sub-bins per binary octave */
+#define MIRT_NOT_CONVERGED 2     /* mirt_accumulate_until reached max_accumulations */
+typedef struct mirt_noise_stats {
+	uint64_t owned_pixels;       /* 256 x the context's tiles */
+	uint64_t finite_pixels;      /* usable pixels */
+	uint64_t nonfinite_pixels;   /* owned - usable */
+	float    max;                /* largest usable e (0 when there is none) */
+	uint32_t _pad;
+	double   mean;               /* of the usable e: formed on the host in double from the tile records, sum of mean[t] * count[t] over the local
+	                                tiles t in ascending order, divided by finite_pixels (0 when there is none) */
+} mirt_noise_stats;
+/* Any of map_out, tile_out, hist_out may be NULL.  map_out: width * height floats, row-major (row 0 = y 0); only the context's own tiles
+ * are written, the rest of the caller's buffer is left untouched (the rule of mirt_render_aov).  tile_out: 4 floats per local tile,
+ * {max, mean over the usable pixels, usable count, non-finite count} (counts as floats, exact; max and mean 0 for a tile without a usable
+ * pixel).  hist_out: MIRT_NOISE_BINS words.  Launches anything deferred and waits for the GPU first; changes no state (accumulator, frame,
+ * counters); kernel time is booked under MIRT_K_RESOLVE.
+ * MIRT_NOT_READY with every output untouched when accumulations == 0 or accumulations % buckets != 0; MIRT_ERR_STATE when buckets < 2;
+ * MIRT_ERR_ARG when floor is negative or not finite.  A context that owns no tile returns MIRT_OK with zero counts (and a zero histogram). */
+int mirt_noise(mirt_ctx* ctx, float floor, float* map_out, float* tile_out, uint32_t* hist_out, mirt_noise_stats* stats);
+/* Pure host code: no context, no GPU.  *value = the UPPER EDGE of the bin that holds the q-quantile of the usable pixels — the pixel of
+ * rank ceil(q * n) among the n sorted values (rank at least 1).  It overstates the quantile by at most one sub-bin, 12.5 % relative: the
+ * safe side for a stopping rule.  q in (0, 1], else MIRT_ERR_ARG; an empty histogram: MIRT_NOT_READY, *value untouched. */
+int mirt_noise_quantile(const uint32_t* hist, double q, float* value);
+typedef struct mirt_stop_rule {
+	float    target;             /* stop when the quantile's bin edge is <= target ... */
+	float    quantile;           /* ... for this q in (0, 1] of the usable pixels (0.95: nineteen pixels in twenty are below target) */
+	float    floor;              /* mirt_noise's */
+	uint32_t check_every;        /* accumulations between two checks: a positive multiple of `buckets` */
+	uint32_t max_accumulations;  /* total (not additional) accumulations at which to give up */
+} mirt_stop_rule;
+/* A host loop: mirt_accumulate(check_every), then mirt_noise.  MIRT_OK as soon as the quantile is <= target and no pixel is non-finite;
+ * MIRT_NOT_CONVERGED once accumulations >= max_accumulations (the last step is shortened to land on the largest multiple of `buckets`
+ * that does not pass it).  *last: the stats of the last check (zeros if none ran), *issued: accumulations added by this call; either
+ * may be NULL.  MIRT_ERR_ARG unless check_every is a positive multiple of `buckets`, target and floor are finite and >= 0 and quantile
+ * is in (0, 1]; MIRT_ERR_STATE when buckets < 2 or the current count is not a multiple of `buckets`.  The accumulator afterwards is,
+ * word for word, that of the same number of plain mirt_accumulate calls. */
+int mirt_accumulate_until(mirt_ctx* ctx, const mirt_stop_rule* rule, mirt_noise_stats* last, uint32_t* issued);
+
 int mirt_get_counters(mirt_ctx* ctx, mirt_counters* out);
 int mirt_get_kernel_times(mirt_ctx* ctx, mirt_kernel_times* out, int reset);
 /* HIP stream the context launches on (hipStream_t), for callers that time with their own events. */
@@ -321,6 +377,13 @@ int mirt_group_set_aov(mirt_group* group, uint32_t on);                         
 int mirt_group_aov_floats(const mirt_group* group, size_t* n_floats);            /* of the whole image: tiles x 7 x 256; 0 while off */
 int mirt_group_read_aov(mirt_group* group, float* host_dst);                     /* whole image, [tile][plane 0..6][256] in LaunchIndex order */
 int mirt_group_render_aov(mirt_group* group, int which, float* out);             /* mirt_render_aov of the whole frame */
+/* mirt_noise / mirt_accumulate_until of the whole image.  NO gather: every member runs mirt_noise on its own slab; histograms and counts add
+ * as integers, the maximum is exact, the members' tile records are un-interleaved on the host into LaunchIndex order (tile_out: 4 floats per
+ * tile of the image), each member writes its own tiles of map_out, and the mean is the double sum over those records in LaunchIndex order.
+ * Counts, histogram, max, tile records and map equal the single-context ones bit for bit, the mean as the same double sum.  Statuses as the
+ * namesakes'; MIRT_NOT_READY is decided before any member is asked, with every output untouched. */
+int mirt_group_noise(mirt_group* group, float floor, float* map_out, float* tile_out, uint32_t* hist_out, mirt_noise_stats* stats);
+int mirt_group_accumulate_until(mirt_group* group, const mirt_stop_rule* rule, mirt_noise_stats* last, uint32_t* issued);
 /* Diagnostic: one-device RCCL communicator on `device`, n_floats sent to itself through a grouped ncclSend / ncclRecv. */
 int mirt_group_rccl_selftest(int device, size_t n_floats);
 
