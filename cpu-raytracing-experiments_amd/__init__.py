@@ -134,6 +134,7 @@ def load_library():
         "mirt_debug_info": [P, vp],
         "mirt_debug_tree": [P, vp, C.c_size_t, vp],
         "mirt_debug_primary_lists": [P, vp],
+        "mirt_debug_primary_counts": [P, vp, C.c_size_t],
         "mirt_debug_allow_half_boxes": [P, i32],
     }
     G = C.c_void_p
@@ -552,6 +553,14 @@ class Renderer:
         out = (C.c_uint32 * 10)()
         self._check(self._lib.mirt_debug_primary_lists(self._ctx, out))
         return [int(v) for v in out]
+
+    def debug_primary_counts(self) -> np.ndarray:
+        """[local tile][256] uint32: the length of every local pixel's candidate list; 0xffffffff = a pixel without a list."""
+        n = C.c_size_t(0)
+        self._check(self._lib.mirt_accumulator_floats(self._ctx, C.byref(n)))
+        out = np.zeros((n.value // (self.policy.buckets * 768), 256), dtype=np.uint32)
+        self._check(self._lib.mirt_debug_primary_counts(self._ctx, _ptr(out), out.size))
+        return out
 
     def stream_handle(self) -> int:
         p = C.c_void_p()

@@ -474,6 +474,8 @@ static_assert(kPrimaryNone == 0 && kPrimaryAll == 1 && kPrimaryList == 2, "kTrac
 const decltype(&k_trace<true, kPrimaryNone>) kTraceLens[2] = { k_trace<true, kPrimaryAll, true>, k_trace<false, kPrimaryAll, true> };               // [!count]
 const decltype(&k_trace_fat<true, kPrimaryNone>) kTraceFatLens[2] = { k_trace_fat<true, kPrimaryAll, true>, k_trace_fat<false, kPrimaryAll, true> };  // [!count]
 const decltype(&k_shade<false, false>) kShadeLens[2] = { k_shade<true, false, true>, k_shade<true, true, true> };                                    // [ggx]
+// One wave per pixel for the batches that fill a wave (kernels.hpp kWaveHitsMinBatch); named last, for the same reason.
+const decltype(&k_primary_hits_wave<true>) kPrimaryHitsWave[2] = { k_primary_hits_wave<true>, k_primary_hits_wave<false> };                         // [!count]
 
 // What varies between the launches of the trace stage: a bounce of a batch, or the rays of a debug entry point.
 struct TraceLaunch {
@@ -617,8 +619,16 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			  if (lists) {
 			    // camera rays through the per-pixel candidate lists (kernels.hpp kCollect): k_primary_hits intersects every sample with its pixel's list.
 			    // Pixels without a list are listed in cand_listed (count: listed_pixels) and all their samples traced like any other ray.
-			    const uint32_t hgrid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
-			    hipLaunchKernelGGL(kPrimaryHits[!count], dim3(hgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr);
+			    // A batch that fills a wave runs one wave per pixel, lanes = accumulations, over runs of 16 pixels (k_primary_hits_wave); a smaller one keeps one lane per pixel.
+			    if (batch_n >= kWaveHitsMinBatch) {
+			      // 8 KB of LDS per wave: five workgroups per CU are resident; four times that, grid-stride, so that a CU which gets fewer is not the tail
+			      const uint64_t runs = static_cast<uint64_t>(fp.n_pix) / kWaveHitsRun;
+			      const uint32_t wgrid = static_cast<uint32_t>(std::min<uint64_t>((runs + kWaveHitsWaves - 1) / kWaveHitsWaves, static_cast<uint64_t>(c->n_cu) * 20u));
+			      hipLaunchKernelGGL(kPrimaryHitsWave[!count], dim3(wgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr);
+			    } else {
+			      const uint32_t hgrid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
+			      hipLaunchKernelGGL(kPrimaryHits[!count], dim3(hgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr);
+			    }
 			  }
 			  // the adds of bounce-1 that waited for occlusion land in the paths' contribution words before k_shade adds this bounce's terms;
 			  // a surviving path's record finds its origin and its path id in stream `in` (= out of bounce-1)
@@ -1453,6 +1463,22 @@ int mirt_debug_primary_lists(mirt_ctx* c, uint32_t hist[10]) {
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	for (int k = 0; k < 10; k++) hist[k] = 0;
 	for (size_t p = 0; p < fp.n_pix; p++) { const uint32_t n = host[p]; hist[n == kCandOverflow ? 9 : std::min<uint32_t>(n, 8u)]++; }     // hist[8]: 8 or more
+	return MIRT_OK;
+}
+
+int mirt_debug_primary_counts(mirt_ctx* c, uint32_t* counts, size_t capacity) {
+	int r = check_ready(c); if (r) return r;
+	if (!counts) return fail(c, MIRT_ERR_ARG, "counts is NULL");
+	if (!c->policy.use_bvh || c->scene.n_recs == 0 || c->n_tiles == 0) return fail(c, MIRT_ERR_STATE, "needs policy.use_bvh, a tree and at least one tile");
+	{ const int fr = flush_deferred(c); if (fr) return fr; }
+	HIP_TRY(c, hipSetDevice(c->device));
+	if ((r = ensure_streams(c))) return r;
+	HIP_TRY(c, sync_all(c));
+	const FrameParams fp = frame_params(c, 0, 1);
+	if (capacity < fp.n_pix) return fail(c, MIRT_ERR_ARG, "debug_primary_counts: room for %zu counts, %u local pixels", capacity, fp.n_pix);
+	if (!c->cand_valid && (r = build_primary_lists(c, trace_scene(c), fp, false))) return r;   // (as mirt_debug_primary_lists)
+	HIP_TRY(c, hipMemcpyAsync(counts, c->cand.ptr, static_cast<size_t>(fp.n_pix) * 4, hipMemcpyDeviceToHost, c->stream));     // plane 0 of the lists
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	return MIRT_OK;
 }
 

@@ -423,6 +423,9 @@ int mirt_debug_tree(mirt_ctx* ctx, void* dst, size_t capacity_bytes, uint32_t in
 /* Length histogram of the per-pixel candidate lists of the current scene / camera / size (policy.trace_primary_rays = 0 path):
  * hist[n] = local pixels whose bundle of camera rays can hit n spheres for n = 0..7, hist[8] = 8 or more (lists hold up to 31), hist[9] = pixels without a list (traced normally). */
 int mirt_debug_primary_lists(mirt_ctx* ctx, uint32_t hist[10]);
+/* The lists' lengths pixel by pixel, in local pixel order (tile-major, 256 per tile, as every per-pixel buffer of the context): counts[i] = spheres
+ * listed for local pixel i (0..31), 0xffffffff for a pixel without a list.  MIRT_ERR_ARG when `capacity` (in counts) is below the local pixels. */
+int mirt_debug_primary_counts(mirt_ctx* ctx, uint32_t* counts, size_t capacity);
 /* Test knob: forbid (0) / allow (1, default) the binary16 records; takes effect at the next mirt_set_scene. */
 int mirt_debug_allow_half_boxes(mirt_ctx* ctx, int allow);
 
