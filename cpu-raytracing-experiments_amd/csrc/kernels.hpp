@@ -762,8 +762,25 @@ MIRT_DI uint32_t global_tile(const FrameParams& fp, uint32_t local_tile) {
 	const uint32_t run = udiv_f(local_tile, fp.run_tiles, fp.inv_run_tiles, in_run);
 	return fp.first_tile + run * fp.stride_tiles + in_run;
 }
-MIRT_DI uint32_t path_seed(const FrameParams& fp, uint32_t pix) {      // seed[ID], Renderer.hpp:107 (wraps like the int32 cast)
+MIRT_DI uint32_t tile_seed(const FrameParams& fp, uint32_t tile, uint32_t ID) {      // seed[ID], Renderer.hpp:107 (wraps like the int32 cast): global tile, lane of the tile
+	return (tile * kTileSize + ID) * (fp.max_bounces * 2u + 1u);
+}
+MIRT_DI uint32_t path_seed(const FrameParams& fp, uint32_t pix) {      // mirrors tile_seed(fp, global_tile(fp, pix >> 8), pix & 255)
 	return (global_tile(fp, pix >> 8) * kTileSize + (pix & 255u)) * (fp.max_bounces * 2u + 1u);
+}
+// The camera sample of RAY GENERATION, Renderer.hpp:113-127: accumulation `acc` (= ++accumulations, Renderer.hpp:74) of the pixel (x, y) whose
+// seed[ID] is `seed` -> the pinhole direction.
+MIRT_DI f3 camera_sample(const CameraParams& cam, int32_t x, int32_t y, uint32_t acc, uint32_t seed) {
+	uint32_t rng = hash_2d(acc, seed);                                      // Renderer.hpp:117
+	const float s0 = rand_unit_float(rng);
+	const float s1 = rand_unit_float(rng);
+	return camera_ray_dir(cam, x, y, s0, s1);
+}
+// The same with the thin lens on top where LENS (device_math.hpp lens_ray): O is written by LENS code only.
+template <bool LENS>
+MIRT_DI void camera_ray(const FrameParams& fp, const LensParams& lens, int32_t x, int32_t y, uint32_t acc, uint32_t seed, f3& O, f3& D) {
+	D = camera_sample(fp.cam, x, y, acc, seed);
+	if (LENS) lens_ray(fp.cam, lens, D, acc, seed, fp.max_bounces, O, D);
 }
 // RAY GENERATION, Renderer.hpp:97-127, for stream index i = slot * n_pix + pix of a batch: path id and direction (the origin
 // is cam.pos).  Bounce 0 has no ray stream in HBM: k_trace<PRIMARY> and k_shade<FIRST> both derive the ray from its index
@@ -783,10 +800,7 @@ MIRT_DI void primary_ray(const FrameParams& fp, uint32_t i, uint32_t& path, floa
 	pixel_xy(fp, pix, tile, x, y);
 	const uint32_t ID = pix & 255u;
 	const uint32_t acc = fp.acc_base + slot + 1u;                           // ++accumulations, Renderer.hpp:74
-	uint32_t rng = hash_2d(acc, (tile * kTileSize + ID) * (fp.max_bounces * 2u + 1u));
-	const float s0 = rand_unit_float(rng);
-	const float s1 = rand_unit_float(rng);
-	const f3 d = camera_ray_dir(fp.cam, x, y, s0, s1);
+	const f3 d = camera_sample(fp.cam, x, y, acc, tile_seed(fp, tile, ID));
 	path = (slot << fp.pix_bits) | pix;
 	dx = d.x; dy = d.y; dz = d.z;
 }
@@ -1093,17 +1107,14 @@ __global__ __launch_bounds__(kBlock) void k_primary_hits(SceneDev sc, FrameParam
 		if (cnt == kCandOverflow) continue;
 		uint32_t tile; int32_t x, y;
 		pixel_xy(fp, pix, tile, x, y);
-		const uint32_t seed = (tile * kTileSize + (pix & 255u)) * (fp.max_bounces * 2u + 1u);      // seed[ID], Renderer.hpp:107
+		const uint32_t seed = tile_seed(fp, tile, pix & 255u);
 		float4 s[kCandRegs]; int32_t id[kCandRegs];
 		for (uint32_t k = 0; k < kCandRegs; k++) {
 			id[k] = k < cnt ? static_cast<int32_t>(cand[static_cast<size_t>(k + 1u) * fp.n_pix + pix]) : -1;
 			s[k] = sc.spheres[id[k] < 0 ? 0 : id[k]];
 		}
 		for (uint32_t slot = 0; slot < fp.batch_n; slot++) {
-			uint32_t rng = hash_2d(fp.acc_base + slot + 1u, seed);                 // ++accumulations, Renderer.hpp:74,117
-			const float s0 = rand_unit_float(rng);
-			const float s1 = rand_unit_float(rng);
-			const f3 d = camera_ray_dir(fp.cam, x, y, s0, s1);
+			const f3 d = camera_sample(fp.cam, x, y, fp.acc_base + slot + 1u, seed);
 			float tfar = MIRT_FLT_MAX; int32_t prim = -1;                          // hit reset, Renderer.hpp:150-158
 			for (uint32_t k = 0; k < kCandRegs; k++) if (id[k] >= 0) sphere_closest_tie(s[k], id[k], ox, oy, oz, d.x, d.y, d.z, tfar, prim);
 			for (uint32_t k = kCandRegs; k < kCandMax; k++) {                      // the rest of a long list, from L1
@@ -1169,7 +1180,7 @@ __global__ __launch_bounds__(kBlock) void k_primary_hits_wave(SceneDev sc, Frame
 				const uint32_t cnt1 = count_of(p);
 				if (cnt1 != 0u) {
 					const uint32_t cnt = cnt1 - 1u;
-					uint32_t rng = hash_2d(fp.acc_base + slot + 1u, (seed0 + p) * seed_mul);      // ++accumulations and seed[ID], Renderer.hpp:74,107,117
+					uint32_t rng = hash_2d(fp.acc_base + slot + 1u, (seed0 + p) * seed_mul);      // mirrors camera_sample(.., tile_seed(fp, tile, (base & 255) + p)), Renderer.hpp:74,107,117
 					const float s0 = rand_unit_float(rng);
 					const float s1 = rand_unit_float(rng);
 					const f3 d = camera_ray_dir(fp.cam, x0 + static_cast<int32_t>(p), y, s0, s1);
@@ -1221,23 +1232,20 @@ __global__ __launch_bounds__(kBlock) void k_first_hit_aov(SceneDev sc, FramePara
 	for (uint32_t pix = blockIdx.x * kBlock + threadIdx.x; pix < fp.n_pix; pix += gridDim.x * kBlock) {
 		uint32_t tile; int32_t x, y;
 		pixel_xy(fp, pix, tile, x, y);
-		const uint32_t seed = (tile * kTileSize + (pix & 255u)) * (fp.max_bounces * 2u + 1u);      // seed[ID], Renderer.hpp:107
+		const uint32_t seed = tile_seed(fp, tile, pix & 255u);
 		float* w = aov + static_cast<size_t>(pix >> 8) * (kAovPlanes * kTileSize) + (pix & 255u);
 		float sum[kAovPlanes];
 		for (uint32_t k = 0; k < kAovPlanes; k++) sum[k] = w[k * kTileSize];
 		int32_t cached = -1;
 		float4 hs = make_float4(0.0f, 0.0f, 0.0f, 0.0f), colour = hs;
 		for (uint32_t slot = 0; slot < fp.batch_n; slot++) {
-			uint32_t rng = hash_2d(fp.acc_base + slot + 1u, seed);                 // ++accumulations, Renderer.hpp:74,117
-			const float s0 = rand_unit_float(rng);
-			const float s1 = rand_unit_float(rng);
-			f3 D = camera_ray_dir(fp.cam, x, y, s0, s1);
-			if (LENS) lens_ray(fp.cam, lens, D, fp.acc_base + slot + 1u, seed, fp.max_bounces, O, D);
+			f3 D;
+			camera_ray<LENS>(fp, lens, x, y, fp.acc_base + slot + 1u, seed, O, D);
 			const HitRec h = hit_in[static_cast<size_t>(slot) * fp.n_pix + pix];
 			if (h.prim < 0) { sum[0] += kAovMissDepth; continue; }
 			if (h.prim != cached) { hs = sc.spheres[h.prim]; colour = mat_colour[sc.prim_mat[h.prim]]; cached = h.prim; }
 			const float depth = h.tfar;
-			const f3 hit{ O.x + D.x * depth, O.y + D.y * depth, O.z + D.z * depth };      // CLOSEST HIT SHADER, Renderer.hpp:169-214 (k_shade)
+			const f3 hit{ O.x + D.x * depth, O.y + D.y * depth, O.z + D.z * depth };      // mirrors shade_hit_body.inc's hit and N, Renderer.hpp:169-214
 			f3 N = normalize3(f3{ hit.x - hs.x, hit.y - hs.y, hit.z - hs.z });
 			if (dot3(N, D) >= 0.0f) N = f3{ -N.x, -N.y, -N.z };
 			sum[0] += depth;
@@ -1303,9 +1311,7 @@ MIRT_DI uint32_t block_compact(bool flag, uint32_t value, uint32_t* scratch, uin
 // seed[ID]) is set up once per chunk.  Its hit records come from k_primary_hits (pixels with a candidate list) or k_trace.
 // (Measured and dropped twice: the candidate tests inside this kernel instead of k_primary_hits — ray-major in round 2, pixel-major in
 // round 3: at 6 waves per SIMD and 80 VGPRs the list's dependent loads cost k_shade<FIRST> 5 ms per cfg4 batch, as much as the kernel saved.)
-// TWIN: the arithmetic of phase 2 below (closest-hit shader, NEE, emissive MIS, closure sample, roulette) is restated operation for operation
-// in stream_shade_hit (k_tile_stream, "EXACT STREAM ORDER"); an edit to either must reach the other.  Both are held to the same oracle closure
-// bit for bit (tests/test_gpu_parity.py, test_ggx_gpu.py for this kernel; tests/test_exact_stream_order.py for the twin).
+// Phase 2 (closest-hit shader, NEE, emissive MIS, closure sample, roulette) is shade_hit_body.inc, the text k_tile_stream shades its hits with too.
 // GGX = #define BRDF 1 (Renderer.hpp:70): every closure is Closure<GGX> (DataStreams.hpp:184-219) with F0 = material.F0 and
 // alpha = r^2 + (1 - r^2) * gloss_decay (Renderer.hpp:210-212; `gloss_decay` = the host's table at this bounce, one launch per
 // bounce), read from mat_ggx = {F0.xyz, roughness}.  Its pdf() is 0: NEE weighs 1 / light_pdf and emitters hit by an extension
@@ -1365,17 +1371,14 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 				if (pix < fp.n_pix) {
 					uint32_t tile;
 					pixel_xy(fp, pix, tile, pix_x, pix_y);
-					pix_seed = (tile * kTileSize + (pix & 255u)) * (fp.max_bounces * 2u + 1u);      // seed[ID], Renderer.hpp:107
+					pix_seed = tile_seed(fp, tile, pix & 255u);
 				}
 			}
 			lane_on = pix < fp.n_pix;
 			my_slot = slot_it * fp.n_pix + pix;                                 // the ray's index in the batch = where k_trace stored a hit record for it
 			if (lane_on) {
-				// RAY GENERATION, Renderer.hpp:113-127 (primary_ray with the pixel's part taken from the chunk set-up)
-				uint32_t rng = hash_2d(fp.acc_base + slot_it + 1u, pix_seed);
-				const float s0 = rand_unit_float(rng);
-				const float s1 = rand_unit_float(rng);
-				my_D = camera_ray_dir(fp.cam, pix_x, pix_y, s0, s1);
+				// RAY GENERATION, Renderer.hpp:113-127 (primary_ray with the pixel's part taken from the chunk set-up); the two lines mirror camera_ray<LENS>
+				my_D = camera_sample(fp.cam, pix_x, pix_y, fp.acc_base + slot_it + 1u, pix_seed);
 				if (LENS) lens_ray(fp.cam, lens, my_D, fp.acc_base + slot_it + 1u, pix_seed, fp.max_bounces, my_O, my_D);
 				my_path = (slot_it << fp.pix_bits) | pix;
 				{ const HitRec h = hit_in[my_slot]; my_prim = h.prim; my_tfar = h.tfar; }      // the hit record of k_primary_hits / k_trace
@@ -1440,107 +1443,10 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 			const HitRec hrec = FIRST ? HitRec{ my_tfar, my_prim } : hit_in[i];
 			const int32_t prim = hrec.prim;
 			{
-				// CLOSEST HIT SHADER, Renderer.hpp:169-214
-				const float depth = hrec.tfar;
-				const float4 hs = sc.spheres[prim];
-				const int32_t mat = sc.prim_mat[prim];
-				const f3 O = FIRST ? (LENS ? my_O : f3{ fp.cam.pos[0], fp.cam.pos[1], fp.cam.pos[2] }) : f3{ in.px[i], in.py[i], in.pz[i] };
-				const f3 hit{ O.x + D.x * depth, O.y + D.y * depth, O.z + D.z * depth };
-				f3 N = normalize3(f3{ hit.x - hs.x, hit.y - hs.y, hit.z - hs.z });
-				if (dot3(N, D) >= 0.0f) N = f3{ -N.x, -N.y, -N.z };
-				const quat T = tangent_space(N);
-				const f3 Vl = to_local(T, f3{ -D.x, -D.y, -D.z });
-				P = { hit.x + N.x * 1e-4f, hit.y + N.y * 1e-4f, hit.z + N.z * 1e-4f };
-				const float4 em = s_emission[mat];
-				const float4 alb = s_albedo[mat];
-				const bool is_emissive = max_sel(em.x, max_sel(em.y, em.z)) > MIRT_FLT_EPSILON;
-				f3 F0{0.0f, 0.0f, 0.0f};
-				float alpha = 0.0f;
-				if (GGX) {                                                         // closure set-up, Renderer.hpp:210-212
-					F0 = { alb.x, alb.y, alb.z };
-					float a = alb.w; a *= a;
-					alpha = a + (1.0f - a) * gloss_decay;
-				}
-				const uint32_t acc = fp.acc_base + (path >> fp.pix_bits) + 1u;
-				const uint32_t seed = FIRST ? pix_seed : path_seed(fp, path & fp.pix_mask);
-
-				// NEXT EVENT ESTIMATION, Renderer.hpp:247-298
-				if (fp.mis) {
-					uint32_t rng = hash_2d(acc, seed + bounce * 2u);
-					const float u0 = rand_unit_float(rng);
-					const float u1 = rand_unit_float(rng);
-					const int32_t selected = static_cast<int32_t>(rand_bounded_int(rng, fp.n_lights));
-					const float4 lp = sc.light_sphere[selected];                    // scene.geometry[lighting_acceleration.prims[selected]]
-					const float4 lem = sc.light_emit[selected];                     // its material's emission, and the prim id
-					const int32_t light_primID = static_cast<int32_t>(__float_as_uint(lem.w));
-					do {
-						if (light_primID == prim) break;                             // Q11: geometry-order id vs BVH-order id
-						f3 Wc{ lp.x - P.x, lp.y - P.y, lp.z - P.z };
-						const float center_dist2 = dot3(Wc, Wc);
-						if (center_dist2 <= lp.w) break;
-						const float center_dist = __builtin_sqrtf(center_dist2);
-						{ const float inv = 1.0f / center_dist; Wc.x *= inv; Wc.y *= inv; Wc.z *= inv; }
-						const float sinThetaMax2 = lp.w / center_dist2;
-						{
-							const float NdotW = (2.0f * T.w) * (Wc.z * T.w + Wc.x * T.y - T.x * Wc.y) - Wc.z;
-							if (NdotW < 0.0f && sinThetaMax2 < NdotW * NdotW) break;
-						}
-						float ldist, lpdf;
-						const f3 Ld = sample_direction_to_sphere(Wc, sinThetaMax2, center_dist, lp.w, u0, u1, ldist, lpdf);
-						const f3 Ll = to_local(T, Ld);
-						if (Ll.z < 0.0f) break;
-						f3 rad{ lem.x * thr.x, lem.y * thr.y, lem.z * thr.z };
-						if (GGX) {  // Closure<GGX>::eval, DataStreams.hpp:189-195
-							const f3 f = ggx_eval(F0, alpha, Ll, Vl);
-							rad.x *= f.x; rad.y *= f.y; rad.z *= f.z;
-						} else {    // Closure<LambertianDiffuse>::eval, DataStreams.hpp:169-172
-							const float f = MIRT_INV_PI * max_sel(0.0f, Ll.z);
-							rad.x *= alb.x * f; rad.y *= alb.y * f; rad.z *= alb.z * f;
-						}
-						lpdf *= light_selection_pdf;
-						const float brdf_pdf = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, Ll.z);  // DataStreams.hpp:173-176 / :196-198
-						const float w = powerHeuristic_over_f(lpdf, brdf_pdf);
-						rad.x *= w; rad.y *= w; rad.z *= w;
-						if (max_sel(max_sel(rad.x, rad.y), rad.z) <= 0.0f) break;
-						has_shadow = true; L = Ld; light_distance = ldist; srad = rad;
-					} while (false);
-				}
-				// EMISSIVE PRIMITIVE HIT, Renderer.hpp:319-353
-				has_E = is_emissive;
-				if (is_emissive) {
-					if (fp.mis && bounce > 0) {
-						const float radius2 = hs.w;
-						const float center_dist2 = depth * (depth + Vl.z * (2.0f * __builtin_sqrtf(radius2))) + radius2;
-						const float weight = powerHeuristic(pdf_in, light_selection_pdf * spherePdf(radius2, center_dist2));
-						E = { (thr.x * weight) * em.x, (thr.y * weight) * em.y, (thr.z * weight) * em.z };
-					} else {
-						E = { em.x, em.y, em.z };                                   // Q9: no throughput
-					}
-				}
-				// BRDF SAMPLING - BOUNCE, Renderer.hpp:357-404
-				{
-					uint32_t rng = hash_2d(acc, seed + bounce * 2u + 1u);
-					const float b0 = rand_unit_float(rng);
-					const float b1 = rand_unit_float(rng);
-					f3 sd;
-					if (GGX) {                                                      // Closure<GGX>::sample, DataStreams.hpp:200-218
-						f3 est;
-						ggx_sample(F0, alpha, Vl, b0, b1, sd, est);
-						thr = { thr.x * est.x, thr.y * est.y, thr.z * est.z };
-					} else {
-						sd = hemisphere(b0, b1);                                    // Closure::sample, DataStreams.hpp:177-181
-						thr = { thr.x * alb.x, thr.y * alb.y, thr.z * alb.z };
-					}
-					const float q = 1.0f - max_sel(thr.x, max_sel(thr.y, thr.z));
-					if (rand_unit_float(rng) < q) {
-						terminated = true;                                          // Russian roulette, Renderer.hpp:377-383
-					} else {
-						const float inv = 1.0f / max_sel(MIRT_FLT_EPSILON, 1.0f - q);
-						thr = { thr.x * inv, thr.y * inv, thr.z * inv };
-						ndir = to_world(T, sd);
-						survive = true;
-					}
-				}
+#define SHADE_HIT_ORIGIN (FIRST ? (LENS ? my_O : f3{ fp.cam.pos[0], fp.cam.pos[1], fp.cam.pos[2] }) : f3{ in.px[i], in.py[i], in.pz[i] })
+#define SHADE_HIT_ACC (fp.acc_base + (path >> fp.pix_bits) + 1u)
+#define SHADE_HIT_SEED (FIRST ? pix_seed : path_seed(fp, path & fp.pix_mask))
+#include "shade_hit_body.inc"
 			}
 		}
 		// ---- stream compaction: wave64 ballot + mbcnt prefix inside each wave, one atomic per workgroup and stream ----
@@ -1598,8 +1504,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 //     popcounts and a 256-entry prefix sum; no atomics, no serial lane;
 //   * a path's radiance is stored once, into its word of the batch's contribution buffer, at the bounce where it ends (+0 for a path
 //     dropped after the last bounce, Q5), so every word of the (tile, slot) is written and k_merge_contrib applies the slots as usual.
-// The shading arithmetic is k_shade's, restated (stream_shade_hit) rather than shared: k_shade's body is interleaved with its stream
-// loads and compaction, and its instantiations are kept instruction for instruction as they were tuned and measured.
+// The shading of a hit is k_shade's: one text, shade_hit_body.inc, included by both (stream_shade_hit).
 // Scalar tail of intersect_prims, BVH.hpp:270-286: separate multiply and add, dimension by dimension (built with -ffp-contract=off).
 MIRT_DI void sphere_closest_scalar_tail(float4 s, int32_t prim, float px, float py, float pz, float dx, float dy, float dz,
                                         float& tfar, int32_t& primID) {
@@ -1621,8 +1526,7 @@ MIRT_DI void sphere_closest_scalar_tail(float4 s, int32_t prim, float px, float 
 	if (dist < 0.0f || dist >= tfar) return;
 	tfar = dist; primID = prim;
 }
-// What one hit leaves behind: Renderer.hpp:169-404 for the ray (O, D, thr) that hit `prim` at `depth` — k_shade's phase 2, operation for operation.
-// TWIN of that code: an edit to either must reach the other (see the note above k_shade).
+// What one hit leaves behind: shade_hit_body.inc for the ray (O, D, thr) of a stream slot that hit `prim` at `stream_depth`.
 struct StreamHit {
 	bool survive, has_shadow, has_E;
 	f3 P, ndir, L, srad, E, thr;
@@ -1630,104 +1534,19 @@ struct StreamHit {
 };
 template <bool GGX>
 MIRT_DI void stream_shade_hit(const SceneDev& sc, const FrameParams& fp, const float4* s_albedo, const float4* s_emission, uint32_t bounce, float gloss_decay,
-                              uint32_t acc, uint32_t seed, f3 O, f3 D, f3 thr, float depth, int32_t prim, int32_t mat, StreamHit& h) {
+                              uint32_t stream_acc, uint32_t stream_seed, f3 stream_O, f3 D, f3 thr, float stream_depth, int32_t prim, StreamHit& h) {
 	const float light_selection_pdf = 1.0f / static_cast<float>(fp.n_lights);  // Renderer.hpp:78
 	const float pdf_in = (GGX || bounce == 0u) ? 0.0f : MIRT_INV_PI * max_sel(0.0f, D.z);      // out->pdf of the bounce that sampled D (Q8); Closure<GGX>::pdf = 0
-	// CLOSEST HIT SHADER, Renderer.hpp:169-214
-	const float4 hs = sc.spheres[prim];
-	const f3 hit{ O.x + D.x * depth, O.y + D.y * depth, O.z + D.z * depth };
-	f3 N = normalize3(f3{ hit.x - hs.x, hit.y - hs.y, hit.z - hs.z });
-	if (dot3(N, D) >= 0.0f) N = f3{ -N.x, -N.y, -N.z };
-	const quat T = tangent_space(N);
-	const f3 Vl = to_local(T, f3{ -D.x, -D.y, -D.z });
-	h.P = { hit.x + N.x * 1e-4f, hit.y + N.y * 1e-4f, hit.z + N.z * 1e-4f };
-	const float4 em = s_emission[mat];
-	const float4 alb = s_albedo[mat];
-	const bool is_emissive = max_sel(em.x, max_sel(em.y, em.z)) > MIRT_FLT_EPSILON;
-	f3 F0{0.0f, 0.0f, 0.0f};
-	float alpha = 0.0f;
-	if (GGX) {                                                                 // closure set-up, Renderer.hpp:210-212
-		F0 = { alb.x, alb.y, alb.z };
-		float a = alb.w; a *= a;
-		alpha = a + (1.0f - a) * gloss_decay;
-	}
-	// NEXT EVENT ESTIMATION, Renderer.hpp:247-298
-	h.has_shadow = false;
-	if (fp.mis) {
-		uint32_t rng = hash_2d(acc, seed + bounce * 2u);
-		const float u0 = rand_unit_float(rng);
-		const float u1 = rand_unit_float(rng);
-		const int32_t selected = static_cast<int32_t>(rand_bounded_int(rng, fp.n_lights));
-		const float4 lp = sc.light_sphere[selected];
-		const float4 lem = sc.light_emit[selected];
-		const int32_t light_primID = static_cast<int32_t>(__float_as_uint(lem.w));
-		do {
-			if (light_primID == prim) break;                                     // Q11: geometry-order id vs BVH-order id
-			f3 Wc{ lp.x - h.P.x, lp.y - h.P.y, lp.z - h.P.z };
-			const float center_dist2 = dot3(Wc, Wc);
-			if (center_dist2 <= lp.w) break;
-			const float center_dist = __builtin_sqrtf(center_dist2);
-			{ const float inv = 1.0f / center_dist; Wc.x *= inv; Wc.y *= inv; Wc.z *= inv; }
-			const float sinThetaMax2 = lp.w / center_dist2;
-			{
-				const float NdotW = (2.0f * T.w) * (Wc.z * T.w + Wc.x * T.y - T.x * Wc.y) - Wc.z;
-				if (NdotW < 0.0f && sinThetaMax2 < NdotW * NdotW) break;
-			}
-			float ldist, lpdf;
-			const f3 Ld = sample_direction_to_sphere(Wc, sinThetaMax2, center_dist, lp.w, u0, u1, ldist, lpdf);
-			const f3 Ll = to_local(T, Ld);
-			if (Ll.z < 0.0f) break;
-			f3 rad{ lem.x * thr.x, lem.y * thr.y, lem.z * thr.z };
-			if (GGX) {  // Closure<GGX>::eval, DataStreams.hpp:189-195
-				const f3 f = ggx_eval(F0, alpha, Ll, Vl);
-				rad.x *= f.x; rad.y *= f.y; rad.z *= f.z;
-			} else {    // Closure<LambertianDiffuse>::eval, DataStreams.hpp:169-172
-				const float f = MIRT_INV_PI * max_sel(0.0f, Ll.z);
-				rad.x *= alb.x * f; rad.y *= alb.y * f; rad.z *= alb.z * f;
-			}
-			lpdf *= light_selection_pdf;
-			const float brdf_pdf = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, Ll.z);  // DataStreams.hpp:173-176 / :196-198
-			const float w = powerHeuristic_over_f(lpdf, brdf_pdf);
-			rad.x *= w; rad.y *= w; rad.z *= w;
-			if (max_sel(max_sel(rad.x, rad.y), rad.z) <= 0.0f) break;
-			h.has_shadow = true; h.L = Ld; h.light_distance = ldist; h.srad = rad;
-		} while (false);
-	}
-	// EMISSIVE PRIMITIVE HIT, Renderer.hpp:319-353
-	h.has_E = is_emissive;
-	if (is_emissive) {
-		if (fp.mis && bounce > 0) {
-			const float radius2 = hs.w;
-			const float center_dist2 = depth * (depth + Vl.z * (2.0f * __builtin_sqrtf(radius2))) + radius2;
-			const float weight = powerHeuristic(pdf_in, light_selection_pdf * spherePdf(radius2, center_dist2));
-			h.E = { (thr.x * weight) * em.x, (thr.y * weight) * em.y, (thr.z * weight) * em.z };
-		} else {
-			h.E = { em.x, em.y, em.z };                                          // Q9: no throughput
-		}
-	}
-	// BRDF SAMPLING - BOUNCE, Renderer.hpp:357-404
-	{
-		uint32_t rng = hash_2d(acc, seed + bounce * 2u + 1u);
-		const float b0 = rand_unit_float(rng);
-		const float b1 = rand_unit_float(rng);
-		f3 sd;
-		if (GGX) {                                                             // Closure<GGX>::sample, DataStreams.hpp:200-218
-			f3 est;
-			ggx_sample(F0, alpha, Vl, b0, b1, sd, est);
-			thr = { thr.x * est.x, thr.y * est.y, thr.z * est.z };
-		} else {
-			sd = hemisphere(b0, b1);                                           // Closure::sample, DataStreams.hpp:177-181
-			thr = { thr.x * alb.x, thr.y * alb.y, thr.z * alb.z };
-		}
-		const float q = 1.0f - max_sel(thr.x, max_sel(thr.y, thr.z));
-		h.survive = false;
-		if (!(rand_unit_float(rng) < q)) {                                     // Russian roulette, Renderer.hpp:377-383
-			const float inv = 1.0f / max_sel(MIRT_FLT_EPSILON, 1.0f - q);
-			h.thr = { thr.x * inv, thr.y * inv, thr.z * inv };
-			h.ndir = to_world(T, sd);
-			h.survive = true;
-		}
-	}
+	const HitRec hrec{ stream_depth, prim };
+	bool& survive = h.survive; bool& has_shadow = h.has_shadow; bool& has_E = h.has_E;
+	f3& P = h.P; f3& ndir = h.ndir; f3& L = h.L; f3& srad = h.srad; f3& E = h.E;
+	float& light_distance = h.light_distance;
+	bool terminated = false;                                                   // here: a shaded hit that does not survive
+#define SHADE_HIT_ORIGIN stream_O
+#define SHADE_HIT_ACC stream_acc
+#define SHADE_HIT_SEED stream_seed
+#include "shade_hit_body.inc"
+	if (!terminated) h.thr = thr;                                            // the survivor's throughput
 }
 constexpr uint32_t kStreamPlanes = 13;          // p, dir, throughput, radiance, pixelID
 constexpr uint32_t kStreamKeys = 64;            // material keys 0 .. MIRT_MAX_MATERIALS - 1 (Renderer.hpp:23,92)
@@ -1752,12 +1571,7 @@ __global__ __launch_bounds__(kTileSize, 4) void k_tile_stream(SceneDev sc, Frame
 	const uint32_t acc = fp.acc_base + slot + 1u;                                // ++accumulations, Renderer.hpp:74
 	uint32_t pixelID = ID;
 	f3 O{ fp.cam.pos[0], fp.cam.pos[1], fp.cam.pos[2] }, D, thr{ 1.0f, 1.0f, 1.0f }, R{ 0.0f, 0.0f, 0.0f };
-	{
-		uint32_t rng = hash_2d(acc, (tile * kTileSize + ID) * seed_stride);
-		const float s0 = rand_unit_float(rng);
-		const float s1 = rand_unit_float(rng);
-		D = camera_ray_dir(fp.cam, static_cast<int32_t>(kTileRoot * tile_col + (ID & 15u)), static_cast<int32_t>(kTileRoot * tile_row + (ID >> 4)), s0, s1);
-	}
+	D = camera_sample(fp.cam, static_cast<int32_t>(kTileRoot * tile_col + (ID & 15u)), static_cast<int32_t>(kTileRoot * tile_row + (ID >> 4)), acc, tile_seed(fp, tile, ID));
 	uint32_t c_term = 0, c_drop = 0, c_shadow = 0;
 	unsigned long long c_shadow_spheres = 0;                                     // sphere tests of this lane's shadow rays (reported with count_traffic)
 	unsigned long long c_rays = 0;                                               // sum of active_rays over the bounces (uniform)
@@ -1798,7 +1612,7 @@ __global__ __launch_bounds__(kTileSize, 4) void k_tile_stream(SceneDev sc, Frame
 			} else {
 				key = sc.prim_mat[prim];
 				const float decay = (GGX && bounce < n_decay) ? gloss_decay[bounce] : 0.0f;
-				stream_shade_hit<GGX>(sc, fp, s_albedo, s_emission, bounce, decay, acc, (tile * kTileSize + pixelID) * seed_stride, O, D, thr, tfar, prim, key, h);
+				stream_shade_hit<GGX>(sc, fp, s_albedo, s_emission, bounce, decay, acc, (tile * kTileSize + pixelID) * seed_stride, O, D, thr, tfar, prim, h);      // the seed mirrors tile_seed(fp, tile, pixelID)
 			}
 		}
 		// SHADOW RAY TRACING: intersect_prims_shadow over all prims, BVH.hpp:290-305,365 (wave-uniform skip when no lane of the tile has one)

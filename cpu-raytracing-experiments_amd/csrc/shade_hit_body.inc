@@ -1,0 +1,125 @@
+// The per-hit shading, Renderer.hpp:169-404: closest-hit shader, next event estimation, emissive MIS, the closure sample and the Russian
+// roulette for one ray that hit `hrec.prim` at `hrec.tfar`.  ONE text, included as statements (not a function: see DESIGN.md,
+// "One per-hit shading text") by its two users in kernels.hpp:
+//   * k_shade, phase 2 — held to the oracle bit for bit by tests/test_gpu_parity.py, test_ggx_gpu.py, test_lens_gpu.py,
+//     test_radiance_in_contrib.py and test_definitions_gpu.py;
+//   * stream_shade_hit (k_tile_stream, exact stream order) — held by tests/test_exact_stream_order.py.
+// The names are k_shade's.  The including scope provides
+//   template parameter  GGX
+//   read                sc, fp, s_albedo, s_emission (the material tables in LDS), bounce, gloss_decay, light_selection_pdf,
+//                       pdf_in (out->pdf of the bounce that sampled D, Q8), hrec (HitRec), prim (= hrec.prim), D (f3)
+//   read and written    thr (f3: the closure's estimator, then the roulette's 1 / (1 - q), in place)
+//   written             P, L, srad, E, ndir (f3), light_distance (float), has_shadow, has_E, terminated, survive (bool; has_E is always
+//                       assigned, the other three flags are only ever set: the scope starts them at false — k_shade's locals do;
+//                       stream_shade_hit binds survive and has_shadow to its StreamHit, which k_tile_stream zeroes before the call); L, light_distance and srad
+//                       are assigned with has_shadow, E with has_E, ndir with survive
+//   three expressions   SHADE_HIT_ORIGIN (f3), SHADE_HIT_ACC and SHADE_HIT_SEED (uint32_t): the ray's origin, its accumulation number and
+//                       its seed[ID] (Renderer.hpp:74,107), evaluated where they stand below — k_shade loads and derives them from its
+//                       stream at these points, and its registers depend on that order.  #undef'd at the end of this file.
+#if !defined(SHADE_HIT_ORIGIN) || !defined(SHADE_HIT_ACC) || !defined(SHADE_HIT_SEED)
+#error "shade_hit_body.inc: define SHADE_HIT_ORIGIN, SHADE_HIT_ACC and SHADE_HIT_SEED before including it (see the list above)"
+#endif
+// CLOSEST HIT SHADER, Renderer.hpp:169-214
+const float depth = hrec.tfar;
+const float4 hs = sc.spheres[prim];
+const int32_t mat = sc.prim_mat[prim];
+const f3 O = SHADE_HIT_ORIGIN;
+const f3 hit{ O.x + D.x * depth, O.y + D.y * depth, O.z + D.z * depth };
+f3 N = normalize3(f3{ hit.x - hs.x, hit.y - hs.y, hit.z - hs.z });
+if (dot3(N, D) >= 0.0f) N = f3{ -N.x, -N.y, -N.z };
+const quat T = tangent_space(N);
+const f3 Vl = to_local(T, f3{ -D.x, -D.y, -D.z });
+P = { hit.x + N.x * 1e-4f, hit.y + N.y * 1e-4f, hit.z + N.z * 1e-4f };
+const float4 em = s_emission[mat];
+const float4 alb = s_albedo[mat];
+const bool is_emissive = max_sel(em.x, max_sel(em.y, em.z)) > MIRT_FLT_EPSILON;
+f3 F0{0.0f, 0.0f, 0.0f};
+float alpha = 0.0f;
+if (GGX) {                                                         // closure set-up, Renderer.hpp:210-212
+	F0 = { alb.x, alb.y, alb.z };
+	float a = alb.w; a *= a;
+	alpha = a + (1.0f - a) * gloss_decay;
+}
+const uint32_t acc = SHADE_HIT_ACC;
+const uint32_t seed = SHADE_HIT_SEED;
+
+// NEXT EVENT ESTIMATION, Renderer.hpp:247-298
+if (fp.mis) {
+	uint32_t rng = hash_2d(acc, seed + bounce * 2u);
+	const float u0 = rand_unit_float(rng);
+	const float u1 = rand_unit_float(rng);
+	const int32_t selected = static_cast<int32_t>(rand_bounded_int(rng, fp.n_lights));
+	const float4 lp = sc.light_sphere[selected];                    // scene.geometry[lighting_acceleration.prims[selected]]
+	const float4 lem = sc.light_emit[selected];                     // its material's emission, and the prim id
+	const int32_t light_primID = static_cast<int32_t>(__float_as_uint(lem.w));
+	do {
+		if (light_primID == prim) break;                             // Q11: geometry-order id vs BVH-order id
+		f3 Wc{ lp.x - P.x, lp.y - P.y, lp.z - P.z };
+		const float center_dist2 = dot3(Wc, Wc);
+		if (center_dist2 <= lp.w) break;
+		const float center_dist = __builtin_sqrtf(center_dist2);
+		{ const float inv = 1.0f / center_dist; Wc.x *= inv; Wc.y *= inv; Wc.z *= inv; }
+		const float sinThetaMax2 = lp.w / center_dist2;
+		{
+			const float NdotW = (2.0f * T.w) * (Wc.z * T.w + Wc.x * T.y - T.x * Wc.y) - Wc.z;
+			if (NdotW < 0.0f && sinThetaMax2 < NdotW * NdotW) break;
+		}
+		float ldist, lpdf;
+		const f3 Ld = sample_direction_to_sphere(Wc, sinThetaMax2, center_dist, lp.w, u0, u1, ldist, lpdf);
+		const f3 Ll = to_local(T, Ld);
+		if (Ll.z < 0.0f) break;
+		f3 rad{ lem.x * thr.x, lem.y * thr.y, lem.z * thr.z };
+		if (GGX) {  // Closure<GGX>::eval, DataStreams.hpp:189-195
+			const f3 f = ggx_eval(F0, alpha, Ll, Vl);
+			rad.x *= f.x; rad.y *= f.y; rad.z *= f.z;
+		} else {    // Closure<LambertianDiffuse>::eval, DataStreams.hpp:169-172
+			const float f = MIRT_INV_PI * max_sel(0.0f, Ll.z);
+			rad.x *= alb.x * f; rad.y *= alb.y * f; rad.z *= alb.z * f;
+		}
+		lpdf *= light_selection_pdf;
+		const float brdf_pdf = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, Ll.z);  // DataStreams.hpp:173-176 / :196-198
+		const float w = powerHeuristic_over_f(lpdf, brdf_pdf);
+		rad.x *= w; rad.y *= w; rad.z *= w;
+		if (max_sel(max_sel(rad.x, rad.y), rad.z) <= 0.0f) break;
+		has_shadow = true; L = Ld; light_distance = ldist; srad = rad;
+	} while (false);
+}
+// EMISSIVE PRIMITIVE HIT, Renderer.hpp:319-353
+has_E = is_emissive;
+if (is_emissive) {
+	if (fp.mis && bounce > 0) {
+		const float radius2 = hs.w;
+		const float center_dist2 = depth * (depth + Vl.z * (2.0f * __builtin_sqrtf(radius2))) + radius2;
+		const float weight = powerHeuristic(pdf_in, light_selection_pdf * spherePdf(radius2, center_dist2));
+		E = { (thr.x * weight) * em.x, (thr.y * weight) * em.y, (thr.z * weight) * em.z };
+	} else {
+		E = { em.x, em.y, em.z };                                   // Q9: no throughput
+	}
+}
+// BRDF SAMPLING - BOUNCE, Renderer.hpp:357-404
+{
+	uint32_t rng = hash_2d(acc, seed + bounce * 2u + 1u);
+	const float b0 = rand_unit_float(rng);
+	const float b1 = rand_unit_float(rng);
+	f3 sd;
+	if (GGX) {                                                      // Closure<GGX>::sample, DataStreams.hpp:200-218
+		f3 est;
+		ggx_sample(F0, alpha, Vl, b0, b1, sd, est);
+		thr = { thr.x * est.x, thr.y * est.y, thr.z * est.z };
+	} else {
+		sd = hemisphere(b0, b1);                                    // Closure::sample, DataStreams.hpp:177-181
+		thr = { thr.x * alb.x, thr.y * alb.y, thr.z * alb.z };
+	}
+	const float q = 1.0f - max_sel(thr.x, max_sel(thr.y, thr.z));
+	if (rand_unit_float(rng) < q) {
+		terminated = true;                                          // Russian roulette, Renderer.hpp:377-383
+	} else {
+		const float inv = 1.0f / max_sel(MIRT_FLT_EPSILON, 1.0f - q);
+		thr = { thr.x * inv, thr.y * inv, thr.z * inv };
+		ndir = to_world(T, sd);
+		survive = true;
+	}
+}
+#undef SHADE_HIT_ORIGIN
+#undef SHADE_HIT_ACC
+#undef SHADE_HIT_SEED
