@@ -309,3 +309,248 @@ def sphere_depth_normal(ix, iy, half_width, half_height, z, eye_z, radius=1.0):
     with np.errstate(invalid="ignore"):
         n = (np.array([0.0, 0.0, eye_z]) + d * np.where(np.isfinite(t), t, 0.0)[..., None]) / radius
     return t, n
+
+
+# ---- F. next-event estimation and multiple importance sampling ------------------------------------------------------------------
+# The expectation of the estimator the path implements at a Lambertian point lit by sphere lights, from the textbook forms
+# (Veach 1997, ch. 9: multiple importance sampling, the power heuristic with beta = 2; Shirley & Wang 1996: the cone a sphere subtends)
+# plus the named departures
+#   D5  the closure pdf that the NEXT emissive hit weighs itself with is max(0, w.z) / pi of the WORLD-space direction, not of the
+#       direction in the surface's frame (Renderer.hpp:386,401); the light sample's weight uses the local one.
+#   D6  the power heuristic is f^2 / max(1e-6, f^2 + g^2) (Sampling.hpp:241-247).
+# A light is (centre (3,), radius_sq, emission (3,)); blockers are (centres (k, 3), radius_sq (k,)), k >= 0.  Points x with unit normals n
+# are (m, 3).  The light sample and the closure sample of one bounce are drawn from different seeds and are taken as independent.
+OFFSET = 1e-4                                      # the shading point is moved by this along the normal before any ray leaves it
+
+
+def power_heuristic(f, g, floor=1e-6):
+    """Veach's power heuristic with beta = 2; `floor` is D6."""
+    return f * f / np.maximum(floor, f * f + g * g)
+
+
+def basis_about(w):
+    """Two unit vectors that complete unit vectors w (m, 3) to right-handed orthonormal frames (cross products with the axis w is least along)."""
+    a = np.zeros_like(w)
+    a[np.arange(len(w)), np.argmin(np.abs(w), axis=1)] = 1.0
+    t = np.cross(a, w); t /= np.linalg.norm(t, axis=1, keepdims=True)
+    return t, np.cross(w, t)
+
+
+def cone_quadrature(P, centre, radius_sq, n_u, n_phi):
+    """Midpoint rule over the cone that the sphere (centre, radius_sq) subtends from each of the points P (m, 3), in the parameters of
+    uniform cone sampling: cos(theta) = 1 - u (1 - cos theta_max) with u and phi / 2 pi at the midpoints of an n_u x n_phi grid.  Every cell
+    carries the same solid angle, so the constant pdf cone_pdf integrates to 1 exactly - asserted.
+    -> directions (m, q, 3), weight (m,) of one cell, distance (m, q) to the sphere's surface along each direction, sin^2(theta_max) (m,)."""
+    wc = centre[None, :] - P
+    d2 = (wc * wc).sum(axis=1)
+    assert (d2 > radius_sq).all(), "a point inside the sphere sees no cone"
+    d = np.sqrt(d2)
+    wc = wc / d[:, None]
+    sin2 = radius_sq / d2
+    pdf, omc = cone_pdf(sin2, floor=0.0)
+    uu = (np.arange(n_u) + 0.5) / n_u
+    ph = 2.0 * np.pi * (np.arange(n_phi) + 0.5) / n_phi
+    cos_t = 1.0 - uu[None, :] * omc[:, None]                                         # (m, n_u)
+    sin_t = np.sqrt(np.maximum(0.0, 1.0 - cos_t * cos_t))
+    t, b = basis_about(wc)
+    ring = np.cos(ph)[None, :, None] * t[:, None, :] + np.sin(ph)[None, :, None] * b[:, None, :]    # (m, n_phi, 3)
+    dirs = (sin_t[:, :, None, None] * ring[:, None, :, :] + cos_t[:, :, None, None] * wc[:, None, None, :]).reshape(len(P), n_u * n_phi, 3)
+    weight = 2.0 * np.pi * omc / (n_u * n_phi)
+    assert np.abs(pdf * weight * (n_u * n_phi) - 1.0).max() <= 1e-12
+    cq, sq = np.repeat(cos_t, n_phi, axis=1), np.repeat(sin_t, n_phi, axis=1)
+    dist = d[:, None] * cq - np.sqrt(np.maximum(0.0, radius_sq - (d[:, None] * sq) ** 2))
+    return dirs, weight, dist, sin2
+
+
+def visible(P, dirs, dist, others):
+    """V of the rendering equation along dirs (m, q, 3) from P (m, 3) up to dist (m, q): 1 unless `occluded` finds a sphere of `others` on the way."""
+    centres, r2 = others
+    if len(r2) == 0:
+        return np.ones(dist.shape)
+    m, q = dist.shape
+    occ, _ = occluded(np.repeat(P, q, axis=0), dirs.reshape(-1, 3), dist.reshape(-1), np.asarray(centres, dtype=np.float64), np.asarray(r2, dtype=np.float64), chunk=1 << 16)
+    return 1.0 - occ.reshape(m, q)
+
+
+def _others(lights, k, blockers):
+    """Everything that can stand between a point and light k: the blockers and the other lights."""
+    c = [np.asarray(blockers[0], dtype=np.float64).reshape(-1, 3)] + [np.asarray(l[0], dtype=np.float64)[None, :] for j, l in enumerate(lights) if j != k]
+    r = [np.asarray(blockers[1], dtype=np.float64).reshape(-1)] + [np.array([float(l[1])]) for j, l in enumerate(lights) if j != k]
+    return np.concatenate(c), np.concatenate(r)
+
+
+NO_BLOCKERS = (np.zeros((0, 3)), np.zeros(0))
+
+
+def direct_lambert(x, n, rho, lights, blockers=NO_BLOCKERS, q8=True, n_u=16, n_phi=32, n_lights_in_light_pdf=None, n_lights_in_hit_weight=None):
+    """One path's contribution from a Lambertian point of albedo rho (3,) under black lights (albedo 0: a path that reaches one ends
+    there) and black blockers, max_bounces >= 3, MIS on.  Two samples see the light: the light sample, weighted w_l = p_l^2 / (p_l^2 + p_b^2),
+    and the cosine-distributed closure sample that survives the roulette with p = max(rho), carries rho / p and finds the light, weighted
+    w_b = p_b'^2 / (p_b'^2 + p_l^2);  p_l = cone_pdf / n_lights, p_b = max(0, w.n) / pi, p_b' = max(0, w.z) / pi with q8 (D5), = p_b without.
+
+        E  = sum over lights  Le rho / pi  int_cone cos+(w.n) V(w) [w_l(w) + w_b(w)] dw                 (p cancels)
+        M2 = sum over lights  int p_l (Le rho cos+ w_l V / (pi p_l))^2 dw  +  p int cos+ / pi (Le rho w_b V / p)^2 dw  +  2 E_l E_b
+
+    (the last term: the two samples are independent).  Without q8 the weights sum to 1 and E is the form factor of the light.
+    `n_lights_in_*` are there for the guards only: what the expectation would be if the number of lights were left out of one pdf.
+    -> dict E (m, 3), M2 (m, 3), shadow (m,): the probability that the light sample casts a shadow ray (it lies above the horizon and
+    carries a positive contribution), var (m, 3) = M2 - E^2."""
+    x, n, rho = (np.asarray(a, dtype=np.float64) for a in (x, n, rho))
+    P = x + OFFSET * n
+    p = rho.max()
+    nl_l = len(lights) if n_lights_in_light_pdf is None else n_lights_in_light_pdf
+    nl_b = len(lights) if n_lights_in_hit_weight is None else n_lights_in_hit_weight
+    E_l, E_b, M2_l, M2_b, shadow = np.zeros((len(x), 3)), np.zeros((len(x), 3)), np.zeros((len(x), 3)), np.zeros((len(x), 3)), np.zeros(len(x))
+    for k, (c, r2, Le) in enumerate(lights):
+        c, Le = np.asarray(c, dtype=np.float64), np.asarray(Le, dtype=np.float64)
+        dirs, wq, dist, sin2 = cone_quadrature(P, c, float(r2), n_u, n_phi)
+        cos_n = np.maximum(0.0, (dirs * n[:, None, :]).sum(axis=2))
+        V = visible(P, dirs, dist, _others(lights, k, blockers))
+        cone = cone_pdf(sin2)[0][:, None]                                            # D4 inside
+        p_l, p_l_hit = cone / nl_l, cone / nl_b
+        p_b = cos_n / np.pi
+        p_b_hit = np.maximum(0.0, dirs[:, :, 2]) / np.pi if q8 else p_b
+        w_l = power_heuristic(p_l, p_b)
+        w_b = np.where(cos_n > 0.0, power_heuristic(p_b_hit, p_l_hit), 0.0)
+        f_l = (cos_n * V * w_l / np.pi)                                               # per unit Le rho
+        f_b = (cos_n * V * w_b / np.pi)
+        s_l, s_b = (f_l * wq[:, None]).sum(axis=1), (f_b * wq[:, None]).sum(axis=1)
+        E_l += s_l[:, None] * (Le * rho)[None, :]
+        E_b += s_b[:, None] * (Le * rho)[None, :]
+        pick_pdf = cone / len(lights)                                                 # the density the light sample is really drawn with
+        m2_l = ((f_l / pick_pdf) ** 2 * pick_pdf * wq[:, None]).sum(axis=1)
+        m2_b = (cos_n / np.pi * (V * w_b) ** 2 * wq[:, None]).sum(axis=1) / p
+        M2_l += m2_l[:, None] * (Le * rho)[None, :] ** 2
+        M2_b += m2_b[:, None] * (Le * rho)[None, :] ** 2
+        shadow += ((cos_n > 0.0) & (w_l > 0.0)).mean(axis=1) / len(lights)
+    E = E_l + E_b
+    M2 = M2_l + M2_b + 2.0 * E_l * E_b
+    return dict(E=E, M2=M2, var=M2 - E * E, shadow=shadow)
+
+
+def form_factor_sphere(x, n, rho, light):
+    """Radiance leaving a Lambertian point towards any direction under one unoccluded sphere light that lies wholly above the horizon:
+    rho Le (r / d)^2 cos(theta_c), theta_c between the normal and the centre (the sphere's view factor; Howell's catalogue B-43)."""
+    c, r2, Le = light
+    P = np.asarray(x, dtype=np.float64) + OFFSET * np.asarray(n, dtype=np.float64)
+    wc = np.asarray(c, dtype=np.float64)[None, :] - P
+    d2 = (wc * wc).sum(axis=1)
+    cos_c = (wc * n).sum(axis=1) / np.sqrt(d2)
+    assert (cos_c > np.sqrt(r2 / d2)).all(), "the closed form needs the whole sphere above the horizon"
+    return (r2 / d2 * cos_c)[:, None] * (np.asarray(Le, dtype=np.float64) * np.asarray(rho, dtype=np.float64))[None, :]
+
+
+def direct_no_mis(x, n, rho, lights, blockers=NO_BLOCKERS, n_u=16, n_phi=32):
+    """Q9: with MIS off there is no light sample, and an emissive hit adds its RAW emission - no throughput, so neither rho nor the
+    roulette's 1 / p.  The closure sample survives with p = max(rho) and is cosine-distributed:  E = p Le int_cone cos+ / pi V dw,
+    M2 = p Le^2 int_cone cos+ / pi V dw.  No shadow ray is ever cast."""
+    x, n, rho = (np.asarray(a, dtype=np.float64) for a in (x, n, rho))
+    P = x + OFFSET * n
+    p = rho.max()
+    E, M2 = np.zeros((len(x), 3)), np.zeros((len(x), 3))
+    for k, (c, r2, Le) in enumerate(lights):
+        Le = np.asarray(Le, dtype=np.float64)
+        dirs, wq, dist, sin2 = cone_quadrature(P, np.asarray(c, dtype=np.float64), float(r2), n_u, n_phi)
+        cos_n = np.maximum(0.0, (dirs * n[:, None, :]).sum(axis=2))
+        s = (cos_n / np.pi * visible(P, dirs, dist, _others(lights, k, blockers)) * wq[:, None]).sum(axis=1)
+        E += p * s[:, None] * Le[None, :]
+        M2 += p * s[:, None] * (Le * Le)[None, :]
+    return dict(E=E, M2=M2, var=M2 - E * E, shadow=np.zeros(len(x)))
+
+
+def path_sampler(scene, x, n, n_paths, max_bounces, rng, mis=True, q5=True, q8=True, prim0=0):
+    """A plain path tracer in float64 numpy for Lambertian spheres, one light sample and one cosine-distributed closure sample a bounce.
+    scene: dict centre (k, 3), radius_sq (k,), albedo (k, 3), emission (k, 3).  Every row of x, n (m, 3) - a first hit on sphere `prim0`
+    and its unit normal - starts n_paths paths.  Textbook throughout (cosine sampling by Malley's method, uniform cone sampling,
+    sphere_roots for every intersection, its own generator) with the named departures: Q5 (a path that still hits on the last bounce
+    is dropped whole; `q5`), Q6 (roulette from bounce 0 with max(throughput), unclamped), Q8 / D5 (`q8`), Q9 (an emissive hit adds its raw
+    emission at bounce 0 or without MIS), D4, D6.  The sky is black (Q10 cannot appear).
+    -> dict sum, sum_sq (m, 3): over the n_paths contributions of each row; shadow, rays (m,): shadow rays cast and rays traced beyond
+    the given first hit; dropped (m,)."""
+    centre, r2 = np.asarray(scene["centre"], dtype=np.float64), np.asarray(scene["radius_sq"], dtype=np.float64)
+    albedo, emission = np.asarray(scene["albedo"], dtype=np.float64), np.asarray(scene["emission"], dtype=np.float64)
+    lights = np.flatnonzero((emission * emission).sum(axis=1) > 0.0)
+    emissive = emission.max(axis=1) > 0.0
+    m = len(x)
+    row = np.repeat(np.arange(m), n_paths)
+    N = len(row)
+    nrm = np.asarray(n, dtype=np.float64)[row]
+    P = np.asarray(x, dtype=np.float64)[row] + OFFSET * nrm
+    prim = np.full(N, prim0)
+    thr, rad = np.ones((N, 3)), np.zeros((N, 3))
+    pdf_in, origin = np.zeros(N), np.zeros((N, 3))
+    alive = np.arange(N)                                                             # indices of the paths still under way
+    out = dict(sum=np.zeros((m, 3)), sum_sq=np.zeros((m, 3)), shadow=np.zeros(m), rays=np.zeros(m), dropped=np.zeros(m))
+
+    def nearest(p, d, skip=None):
+        b, oc2, disc = sphere_roots(p, d, centre, r2)
+        s = np.sqrt(np.maximum(disc, 0.0))
+        t = np.where(b - s >= 0.0, b - s, b + s)
+        t = np.where((disc >= 0.0) & (t >= 0.0), t, np.inf)
+        if skip is not None:
+            t[np.arange(len(p)), skip] = np.inf
+        k = np.argmin(t, axis=1)
+        return t[np.arange(len(p)), k], k
+
+    for bounce in range(max_bounces):
+        if len(alive) == 0:
+            break
+        a = alive
+        if bounce == max_bounces - 1:
+            if q5:                                                                   # Q5
+                rad[a] = 0.0
+                np.add.at(out["dropped"], row[a], 1.0)
+            break
+        if mis and len(lights):
+            pick = lights[rng.integers(0, len(lights), len(a))]
+            wc = centre[pick] - P[a]
+            d2 = (wc * wc).sum(axis=1)
+            ok = (pick != prim[a]) & (d2 > r2[pick])
+            d = np.sqrt(d2)
+            wc = wc / d[:, None]
+            sin2 = np.minimum(r2[pick] / d2, 1.0)
+            pdf_c, omc = cone_pdf(sin2)                                              # D4
+            cos_t = 1.0 - rng.random(len(a)) * omc
+            sin_t = np.sqrt(np.maximum(0.0, 1.0 - cos_t * cos_t))
+            phi = 2.0 * np.pi * rng.random(len(a))
+            t_, b_ = basis_about(wc)
+            w = sin_t[:, None] * (np.cos(phi)[:, None] * t_ + np.sin(phi)[:, None] * b_) + cos_t[:, None] * wc
+            cos_n = (w * nrm[a]).sum(axis=1)
+            p_l = pdf_c / len(lights)
+            p_b = np.maximum(0.0, cos_n) / np.pi
+            contrib = emission[pick] * thr[a] * albedo[prim[a]] * (p_b * p_l / np.maximum(1e-6, p_l * p_l + p_b * p_b))[:, None]     # D6
+            cast = ok & (cos_n >= 0.0) & (contrib.max(axis=1) > 0.0)
+            reach = d * cos_t - np.sqrt(np.maximum(0.0, r2[pick] - (d * sin_t) ** 2))
+            t_near, _ = nearest(P[a], w, skip=pick)
+            rad[a] += np.where((cast & ~(t_near < reach))[:, None], contrib, 0.0)
+            np.add.at(out["shadow"], row[a], cast.astype(np.float64))
+        em = emissive[prim[a]]
+        if mis and len(lights) and bounce > 0:
+            oc = centre[prim[a]] - origin[a]
+            g = cone_pdf(np.minimum(r2[prim[a]] / (oc * oc).sum(axis=1), 1.0))[0] / len(lights)
+            rad[a] += np.where(em[:, None], thr[a] * power_heuristic(pdf_in[a], g)[:, None] * emission[prim[a]], 0.0)
+        else:
+            rad[a] += np.where(em[:, None], emission[prim[a]], 0.0)                  # Q9
+        thr[a] = thr[a] * albedo[prim[a]]
+        p = thr[a].max(axis=1)
+        live = rng.random(len(a)) < p                                                # Q6
+        a = a[live]
+        thr[a] = thr[a] / p[live][:, None]
+        r_, phi = np.sqrt(rng.random(len(a))), 2.0 * np.pi * rng.random(len(a))      # Malley: a uniform disk, lifted
+        t_, b_ = basis_about(nrm[a])
+        w = (r_ * np.cos(phi))[:, None] * t_ + (r_ * np.sin(phi))[:, None] * b_ + np.sqrt(np.maximum(0.0, 1.0 - r_ * r_))[:, None] * nrm[a]
+        pdf_in[a] = np.maximum(0.0, w[:, 2] if q8 else (w * nrm[a]).sum(axis=1)) / np.pi                                             # D5
+        origin[a] = P[a]
+        np.add.at(out["rays"], row[a], 1.0)
+        t_hit, k = nearest(P[a], w)
+        found = np.isfinite(t_hit)
+        a, w, t_hit, k = a[found], w[found], t_hit[found], k[found]
+        hit = P[a] + w * t_hit[:, None]
+        nn = (hit - centre[k]) / np.sqrt(r2[k])[:, None]
+        nn = np.where(((nn * w).sum(axis=1) >= 0.0)[:, None], -nn, nn)
+        nrm[a], prim[a] = nn, k
+        P[a] = hit + OFFSET * nn
+        alive = a
+    np.add.at(out["sum"], row, rad)
+    np.add.at(out["sum_sq"], row, rad * rad)
+    return out

@@ -9,9 +9,10 @@ Bounds are never taken from the code under test.  Each is either derived (the de
 measured on the CPU oracle and given a stated margin; the measured figure is in the docstring of the check and in DESIGN.md §2.
 Reference departures from the textbook are named expectations (D1-D4 in definitions.py, Q rows of SURVEY.md §8a).
 
-Left out on purpose: MIS-on multi-bounce scenes and MIS-off emissive scenes against physics.  Q8 (the MIS pdf is taken of the world-space
-direction) and Q9 (emission added without throughput) bias them by design, so no closed form of the physics applies; stream order and
-Q14 (fused body, unfused tail) are arithmetic, not definitions.  Those rows stay pinned by parity alone."""
+Part F holds next-event estimation and MIS to float64 expectations of the estimator the reference implements (Q8 and Q9 are named
+departures there, not reasons to look away) for the Lambertian closure.  Left out: the GGX closure inside the path (the density of the
+reference's visible-normal sample is not stated yet) and Q11 under a differing authoring order; stream order and Q14
+(fused body, unfused tail) are arithmetic, not definitions.  Those rows stay pinned by parity alone."""
 import math
 
 import numpy as np
@@ -110,8 +111,8 @@ class OracleBackend:
             yield label, (lambda P, D, o=o, m=mode: o.trace_closest(P, D, m)), (lambda P, D, T, o=o, m=mode: o.trace_shadow(P, D, T, m))
             o.close()
 
-    def render(self, sc, w, h, n_acc, max_bounces, buckets=5, mis=True, variant=0):
-        o = ob.Oracle(sc, max_bounces=max_bounces, buckets=buckets, mis=mis, **self.variants[variant][1])
+    def render(self, sc, w, h, n_acc, max_bounces, buckets=5, mis=True, variant=0, brdf=0, gloss_decay=None):
+        o = ob.Oracle(sc, max_bounces=max_bounces, buckets=buckets, mis=mis, brdf=brdf, gloss_decay=gloss_decay, **self.variants[variant][1])
         o.Resize(w, h); o.Accumulate(n_acc)
         out = dict(acc=o.accumulator(), frame=o.Render() if n_acc % buckets == 0 else None, counters=o.counters())
         o.close()
@@ -763,3 +764,354 @@ def check_emissive_sphere(be, mirt, variant=0):
 
 def test_emissive_sphere(be, mirt):
     check_emissive_sphere(be, mirt)
+
+
+# ---- F. next-event estimation and MIS -------------------------------------------------------------------------------------------
+# The unit sphere fills the frame (eye (0, 0, 1.25), focal 35, 64 x 64, black sky); every other sphere has its centre behind the eye plane
+# and is seen by no camera ray (guard_first_hits).  The frame shows only the part of the sphere whose normal is within 7 degrees of +z
+# (5 at the middle of an edge).  Two consequences for the placing of the lights:
+#   * a light that is fully above the horizon in one row and fully below it in another must subtend less than 5 degrees from behind the
+#     eye plane, i.e. be small and at least 5.7 away.  Binary32 cannot resolve such a light: its own root along the shadow ray is known
+#     to about 2 d^2 u / sqrt(disc) (definitions.sphere_error_model), beyond the 1e-5 by which the reference shortens the shadow ray, and
+#     the light shadows itself at random (measured on the oracle with radius 0.18 at distance 7: the image 100 and more sigma too dark,
+#     `shadow_rays` within one sigma).  That is arithmetic, not definition, so the lights here are large and near: the error stays
+#     below a tenth of the 1e-5 except on a rim that holds less than 1 % of the cone.  The NdotW early-out gets two cases of its own, which
+#     need not lie behind the eye plane (the unit sphere hides them from the camera; guard_first_hits asserts it): BELOW, a large light under
+#     the horizon of every visible point - nothing may arrive and no shadow ray may be cast - and SUNK, whose centre is below the horizon
+#     (NdotW < 0) while a part of it is above: the early-out must NOT be taken.
+#   * a light weighs the closure sample noticeably only when it subtends tens of degrees.
+#   HIGH  radius 1.5 at (0, 1.75, 2.8): 44 degrees off the axis, half angle 37 - wholly above the horizon everywhere, the closure sample
+#         carries 5 - 10 % and D5 shows in it;
+#   LOW   radius 0.75 at (0, 1.8, 1.3): 80 degrees off the axis, half angle 24 - cut by the horizon in every pixel, by an amount that
+#         changes with the row: the `Ll.z < 0` break, and a `shadow_rays` share strictly between 0 and 1;
+#   SIDE  radius 0.434 at (-2.462, 0, 1.434): 80 degrees off the axis along -x, half angle 10 - wholly above the horizon in the left
+#         half of the image and cut by it in the right half.
+F_W = F_H = 64
+F_EYE, F_FOCAL = 1.25, 35.0
+F_RHO = (0.8, 0.4, 0.2)
+F_SUB = 2                                 # sub-pixel grid of the footprint
+F_QUAD = (16, 32)                         # cells of the cone quadrature (a case may ask for more); test_direct_lighting_guards holds it to the refinement condition
+HIGH = ((0.0, 1.75, 2.8), 1.5, (3.0, 2.0, 1.0))
+LOW = ((0.0, 1.8, 1.3), 0.75, (6.0, 8.0, 12.0))
+SIDE = ((-2.462, 0.0, 1.434), 0.434, (10.0, 20.0, 40.0))   # F2's second light: another size and colour
+BLOCKER = ((0.0, 0.0, 1.5), 0.12)                          # F3: between the lower rows of the visible cap and the near edge of HIGH
+SUNK = ((0.0, 1.811, 0.778), 0.75, (6.0, 8.0, 12.0))       # LOW turned to 97 degrees off the axis: its CENTRE is below the horizon, a part of it above
+BELOW = ((0.0, 2.53, -1.12), 1.5, (3.0, 2.0, 1.0))         # HIGH's size, 130 degrees off the axis: wholly below the horizon of every visible point
+DIFFUSE = ((0.0, -0.7, 2.01), 0.75, (0.5, 1.0, 0.75))       # F5: a coloured Lambertian sphere that the cap sees and the camera does not
+
+
+def lit_scene(mirt, lights, blockers=(), diffuse=(), rho=F_RHO):
+    """The unit sphere (albedo rho), the lights (albedo 0), the blockers (albedo 0, no emission) and the diffuse spheres, one material each.
+    Q11: the reference compares a light's index in the authoring order with the hit's index in the tree's order and skips the light sample
+    when they are equal.  The scene is authored in the tree's own order, so the two agree and the comparison is the intended one
+    (guard_first_hits asserts it); what Q11 does under a differing order stays pinned by parity alone."""
+    S = mirt.scene
+    geo, mats = [S._sphere((0, 0, 0), 1.0, 0)], [S._material(albedo=rho)]
+    for c, r, Le in lights:
+        geo.append(S._sphere(c, r * r, len(mats))); mats.append(S._material(emission=Le))
+    for c, r in blockers:
+        geo.append(S._sphere(c, r * r, len(mats))); mats.append(S._material())
+    for c, r, alb in diffuse:
+        geo.append(S._sphere(c, r * r, len(mats))); mats.append(S._material(albedo=alb))
+    cam = S.Camera(eye=(0.0, 0.0, F_EYE), direction=(0.0, 0.0, -1.0), focal_length=F_FOCAL, exposure=1.0)
+    geo, mats = np.array(geo, dtype=S.SPHERE), np.array(mats, dtype=S.MATERIAL)
+    key = geo.tobytes()
+    if key not in _tree_order:
+        o = ob.Oracle(S.Scene(geo, mats, cam, np.zeros(3, dtype=f32), name="part_f")); _tree_order[key] = o.bvh()[1].copy(); o.close()
+    return S.Scene(_tree_order[key].copy(), mats, cam, np.zeros(3, dtype=f32), name="part_f")
+
+
+_tree_order, _f_cache = {}, {}
+
+
+def df_lights(lights):
+    return [(np.array(c, dtype=f64), float(f32(r * r)), np.array(Le, dtype=f64)) for c, r, Le in lights]
+
+
+def df_blockers(blockers):
+    return (np.array([c for c, r in blockers], dtype=f64).reshape(-1, 3), np.array([float(f32(r * r)) for c, r in blockers]))
+
+
+def footprint_points(sub=F_SUB):
+    """First hits of the unit sphere on a sub x sub midpoint grid of every pixel's footprint: x = n, (h * w, sub * sub, 3)."""
+    s = (np.arange(sub) + 0.5) / sub
+    xs = (np.arange(F_W)[None, :, None, None] + s[None, None, :, None]) + np.zeros((F_H, 1, 1, sub))
+    ys = (np.arange(F_H)[:, None, None, None] + s[None, None, None, :]) + np.zeros((1, F_W, sub, 1))
+    t, nrm = df.sphere_depth_normal(xs, ys, F_W / 2.0, F_H / 2.0, df.lens_z(F_H, F_FOCAL), F_EYE)
+    assert np.isfinite(t).all()
+    return nrm.reshape(F_H * F_W, sub * sub, 3)
+
+
+# name -> the scene's pieces, MIS, the cells of the cone quadrature, the accumulations (the smallest multiple of 5, from 100, at which
+# test_direct_lighting_guards holds), and what the second of the three regions is
+F_CASES = {
+    "F1_high": dict(lights=[HIGH], n_acc=345, second="lower"),
+    "F1_low": dict(lights=[LOW], n_acc=100, second="lower"),
+    "F1_sunk": dict(lights=[SUNK], n_acc=135, second="lower"),
+    "F1_below": dict(lights=[BELOW], n_acc=100, second="lower"),
+    "F2_two_lights": dict(lights=[HIGH, SIDE], n_acc=100, second="horizon"),
+    "F3_blocker": dict(lights=[HIGH], blockers=[BLOCKER], n_acc=100, second="shadowed", quad=(32, 64)),
+    "F4_no_mis": dict(lights=[HIGH], n_acc=405, second="lower", mis=False),
+}
+F_LAMBERT = list(F_CASES)
+CENTRE16 = np.zeros((F_H, F_W), dtype=bool); CENTRE16[24:40, 24:40] = True
+CENTRE8 = np.zeros((F_H, F_W), dtype=bool); CENTRE8[28:36, 28:36] = True
+
+
+def f_expectation(name, pixels=None, refine=1, blockers=None, **alt):
+    """The float64 side of a case per pixel - E, var (k, 3), shadow (k,) - computed once a process and shared by every backend and variant.
+    The mean over the sub-pixels; the variance of the mixture (mean of the second moments minus the square of the mean, which adds the
+    between-sub-pixel variance).  `pixels`: flat indices (default all); `refine`: factor on the quadrature's cells; `blockers`, `alt`:
+    a what-if for a guard (direct_lambert's keywords)."""
+    key = (name, None if pixels is None else tuple(pixels), refine, blockers, tuple(sorted(alt.items())))
+    if key in _f_cache:
+        return _f_cache[key]
+    case = F_CASES[name]
+    n_u, n_phi = (refine * c for c in case.get("quad", F_QUAD))
+    lights, blk = df_lights(case["lights"]), df_blockers(case.get("blockers", ()) if blockers is None else blockers)
+    nrm = footprint_points()
+    nrm = nrm if pixels is None else nrm[pixels]
+    k, q = nrm.shape[:2]
+    out = dict(E=np.zeros((k, 3)), var=np.zeros((k, 3)), shadow=np.zeros(k))
+    for lo in range(0, k, 512):
+        pts = nrm[lo:lo + 512].reshape(-1, 3)
+        if case.get("mis", True):
+            r = df.direct_lambert(pts, pts, F_RHO, lights, blk, n_u=n_u, n_phi=n_phi, **alt)
+        else:
+            r = df.direct_no_mis(pts, pts, F_RHO, lights, blk, n_u=n_u, n_phi=n_phi)
+        E = r["E"].reshape(-1, q, 3).mean(axis=1)
+        out["E"][lo:lo + 512] = E
+        out["var"][lo:lo + 512] = r["M2"].reshape(-1, q, 3).mean(axis=1) - E * E
+        out["shadow"][lo:lo + 512] = r["shadow"].reshape(-1, q).mean(axis=1)
+    _f_cache[key] = out
+    return out
+
+
+def f_regions(name):
+    """Three disjoint regions: the central 16 x 16; off it, the lower half / the pixels where SIDE's cone is cut by the horizon / the pixels
+    from which the blocker takes more than a thousandth of the light; the rest."""
+    second = F_CASES[name]["second"]
+    if second == "lower":
+        mask = np.zeros((F_H, F_W), dtype=bool); mask[: F_H // 2] = True
+    elif second == "horizon":
+        nrm = footprint_points()
+        wc = np.array(SIDE[0])[None, None, :] - nrm * (1.0 + df.OFFSET)
+        d = np.linalg.norm(wc, axis=-1)
+        mask = (((wc * nrm).sum(axis=-1) / d) < SIDE[1] / d).any(axis=1).reshape(F_H, F_W)
+    else:
+        mask = (f_expectation(name)["E"][:, 0] < 0.999 * f_expectation(name, blockers=())["E"][:, 0]).reshape(F_H, F_W)
+    mask = mask & ~CENTRE16
+    return {"centre": CENTRE16, second: mask, "rest": ~CENTRE16 & ~mask}
+
+
+def region_stats(exp, mask, n_acc):
+    """Mean expectation and standard error of the mean over a region, per channel."""
+    k = mask.reshape(-1)
+    return exp["E"][k].mean(axis=0), np.sqrt(exp["var"][k].sum(axis=0) / n_acc) / k.sum()
+
+
+def apart(name, region, **alt):
+    """Largest distance over the channels, in standard errors of the region's mean, between a case's expectation and a what-if's."""
+    e0, se = region_stats(f_expectation(name), region, F_CASES[name]["n_acc"])
+    e1, _ = region_stats(f_expectation(name, **alt), region, F_CASES[name]["n_acc"])
+    return float((np.abs(e1 - e0) / se).max())
+
+
+def backend_image(res, n_acc):
+    px, py = df.pixel_of_slot(np.arange(F_W * F_H), F_W)
+    img = np.zeros((F_H, F_W, 3))
+    img[py, px] = np.moveaxis(res["acc"].astype(f64).sum(axis=1), 1, 2).reshape(-1, 3) / n_acc
+    return img
+
+
+def guard_first_hits(be, sc, max_bounces):
+    """No camera ray sees anything but the unit sphere (float64 closest hit on the backend's own camera rays), and Q11 cannot bite."""
+    p, d = be.raygen(sc, F_W, F_H, 1, max_bounces=max_bounces)
+    geo = sc.geometry
+    hit = df.closest_hit(p.T.astype(f64), d.T.astype(f64), geo["position"].astype(f64), geo["radius_sq"].astype(f64))
+    assert (hit["prim"] == int(np.flatnonzero((geo["position"] == 0).all(axis=1))[0])).all()
+    o = ob.Oracle(sc); prims = o.bvh()[1]; o.close()
+    assert prims.tobytes() == np.ascontiguousarray(geo).tobytes()                   # tree order = authoring order
+
+
+def check_direct(be, mirt, name, variant=0, **render_kw):
+    """One case of F_CASES on a backend, max_bounces = 3: the image's mean over each of three disjoint regions, per channel, within SIGMA
+    standard errors of the float64 expectation (the variance is the definition's, never the backend's); `terminated` = n exactly (a black
+    light ends the path); `rays` = n (1 + p) at SIGMA Bernoulli sigma; `shadow_rays` within SIGMA of the definition's share.  A region whose
+    expectation is 0 with variance 0 (F1_below) must be 0 exactly.  Measured on the oracle: DESIGN.md section 2, rows F."""
+    case = F_CASES[name]
+    n_acc = case["n_acc"]
+    exp, regions = f_expectation(name), f_regions(name)
+    sc = lit_scene(mirt, case["lights"], case.get("blockers", ()))
+    guard_first_hits(be, sc, 3)
+    res = be.render(sc, F_W, F_H, n_acc, max_bounces=3, variant=variant, mis=case.get("mis", True), **render_kw)
+    img = backend_image(res, n_acc)
+    n = F_W * F_H * n_acc
+    zs = {}
+    for label, mask in regions.items():
+        want, se = region_stats(exp, mask, n_acc)
+        got = img[mask].mean(axis=0)
+        assert mask.sum() >= 64
+        if not want.any() and not se.any():
+            assert not got.any(), f"{name}/{label}: light where none can arrive"
+            zs[label] = [0.0, 0.0, 0.0]
+            continue
+        assert (want > 0).all() and (se / want < 0.01).all(), (name, label, se / want)
+        zs[label] = [float(v) for v in (got - want) / se]
+    c = res["counters"]
+    p = max(F_RHO)
+    z_rays = (c["rays"] - n * (1 + p)) / math.sqrt(n * p * (1 - p))
+    want_sh = n_acc * exp["shadow"].sum()
+    sigma_sh = math.sqrt(n_acc * (exp["shadow"] * (1 - exp["shadow"])).sum())
+    report(f"{be.name}/{name}/variant{variant}" + "".join(f"/{k}" for k in render_kw), **{f"z_{k}": "/".join(f"{v:+.2f}" for v in z) for k, z in zs.items()},
+           z_rays=float(z_rays), shadow_rays=c["shadow_rays"], shadow_expected=float(want_sh), shadow_sigma=float(sigma_sh))
+    for label, z in zs.items():
+        assert max(abs(v) for v in z) <= SIGMA, f"{name}/{label}: {z} sigma from the expectation"
+    assert c["terminated"] == n
+    assert abs(z_rays) <= SIGMA, f"{name}: rays {c['rays']} is {z_rays:+.2f} sigma from {n * (1 + p)}"
+    assert abs(c["shadow_rays"] - want_sh) <= SIGMA * sigma_sh, f"{name}: {c['shadow_rays']} shadow rays, expected {want_sh:.1f} +- {sigma_sh:.1f}"
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+@pytest.mark.parametrize("name", F_LAMBERT)
+def test_direct_lighting(be, mirt, name, variant):
+    check_direct(be, mirt, name, variant=variant)
+
+
+def test_direct_lighting_guards():
+    """What makes part F a test, from the definitions alone (no backend).  Measured: DESIGN.md section 2, rows F."""
+    figures = {}
+    # the quadrature itself: without D5 the two weights sum to 1 and the light's form factor must come out.  The midpoint rule is exact for
+    # it (cos(w.n) is linear in the rule's cos(theta) and its azimuthal part sums to zero over equal cells), D6's floor is never reached
+    # (p_l^2 > 1), so what is left is rounding: 1536 terms of a few u64 each, 1e-12 taken
+    pts = footprint_points().reshape(-1, 3)[:: 997]
+    quad = df.direct_lambert(pts, pts, F_RHO, df_lights([HIGH]), q8=False, n_u=F_QUAD[0], n_phi=F_QUAD[1])["E"]
+    figures["form_factor_rel"] = float(np.abs(quad / df.form_factor_sphere(pts, pts, F_RHO, df_lights([HIGH])[0]) - 1.0).max())
+    assert figures["form_factor_rel"] <= 1e-12
+    # the resolution: doubling it moves no pixel by more than a tenth of that pixel's standard error (a subsample of pixels), and - since
+    # the bounds are on regional means - their mean over the subsample by no more than a tenth of the standard error of that mean
+    some = np.arange(0, F_W * F_H, 61)
+    for name in F_LAMBERT:
+        n_acc = F_CASES[name]["n_acc"]
+        a, b = f_expectation(name, pixels=some), f_expectation(name, pixels=some, refine=2)
+        se = np.sqrt(a["var"] / n_acc)
+        assert (np.abs(b["E"] - a["E"]) <= 0.1 * se).all(), name
+        se_mean = np.sqrt(a["var"].sum(axis=0) / n_acc) / len(some)
+        assert (np.abs(b["E"].mean(axis=0) - a["E"].mean(axis=0)) <= 0.1 * se_mean).all(), name
+        with np.errstate(divide="ignore", invalid="ignore"):
+            figures[f"refine_{name}"] = float(np.nanmax(np.where(se > 0, np.abs(b["E"] - a["E"]) / se, 0.0)))
+            figures[f"refine_mean_{name}"] = float(np.nanmax(np.where(se_mean > 0, np.abs(b["E"].mean(axis=0) - a["E"].mean(axis=0)) / se_mean, 0.0)))
+    # F1: D5 shows off the centre and not at it
+    regs = f_regions("F1_high")
+    for label in ("lower", "rest"):
+        figures[f"q8_{label}"] = apart("F1_high", regs[label], q8=False)
+        assert figures[f"q8_{label}"] > 2 * SIGMA
+    figures["q8_centre8"] = apart("F1_high", CENTRE8, q8=False)
+    assert figures["q8_centre8"] < 0.5
+    # F2: the number of lights in the light sample's pdf and in the emissive hit's weight
+    for what in ("n_lights_in_light_pdf", "n_lights_in_hit_weight"):
+        figures[what] = apart("F2_two_lights", ~CENTRE16, **{what: 1})
+        assert figures[what] > 2 * SIGMA
+    # F3: the blocker is seen where it shadows, and there is a region it does not reach
+    regs = f_regions("F3_blocker")
+    figures["blocker"] = apart("F3_blocker", regs["shadowed"], blockers=())
+    assert figures["blocker"] > 2 * SIGMA and regs["rest"].sum() >= 256
+    # the horizon: LOW and SUNK are cut in every pixel by an amount that changes over the image, SUNK's centre is below the horizon of every
+    # point (so NdotW < 0 there and only the comparison with sin^2 keeps the light), BELOW is wholly below, HIGH wholly above
+    for name in ("F1_low", "F1_sunk"):
+        sh = f_expectation(name)["shadow"]
+        figures[f"{name}_share"] = f"{sh.min():.3f}..{sh.max():.3f}"
+        assert 0.05 < sh.min() and sh.max() < 0.95 and sh.max() - sh.min() > 0.1
+    pts = footprint_points().reshape(-1, 3)
+    assert (((np.array(SUNK[0])[None, :] - pts * (1 + df.OFFSET)) * pts).sum(axis=1) < 0).all()
+    below = f_expectation("F1_below")
+    assert not below["E"].any() and not below["var"].any() and not below["shadow"].any()
+    assert (f_expectation("F1_high")["shadow"] == 1.0).all()
+    report("guards/F", **figures)
+
+
+# ---- F5. several bounces against the float64 path sampler -----------------------------------------------------------------------
+F5_ACC, F5_REF = 50, 200                  # accumulations of the backend; paths per pixel of the sampler (at least four times as many)
+_sampler_cache = {}
+
+
+def sampler_scene(lights, diffuse=()):
+    spheres = [((0, 0, 0), 1.0, F_RHO, (0, 0, 0))] + [(c, r, (0, 0, 0), Le) for c, r, Le in lights] + [(c, r, alb, (0, 0, 0)) for c, r, alb in diffuse]
+    return dict(centre=np.array([s[0] for s in spheres], dtype=f64), radius_sq=np.array([float(f32(s[1] * s[1])) for s in spheres]),
+                albedo=np.array([s[2] for s in spheres], dtype=f64), emission=np.array([s[3] for s in spheres], dtype=f64))
+
+
+def sampler_run(lights, diffuse, max_bounces, per_pixel, seed, **kw):
+    """path_sampler from jittered first hits, `per_pixel` paths a pixel, fixed seed -> per-pixel mean and sample variance (h * w, 3), the
+    share of dropped paths, computed once a process."""
+    key = (repr(lights), repr(diffuse), max_bounces, per_pixel, seed, tuple(sorted(kw.items())))
+    if key not in _sampler_cache:
+        rng = np.random.default_rng(seed)
+        jit = rng.random((F_H, F_W, per_pixel, 2))
+        xs, ys = np.arange(F_W)[None, :, None] + jit[..., 0], np.arange(F_H)[:, None, None] + jit[..., 1]
+        pts = df.sphere_depth_normal(xs, ys, F_W / 2.0, F_H / 2.0, df.lens_z(F_H, F_FOCAL), F_EYE)[1].reshape(-1, 3)
+        out = df.path_sampler(sampler_scene(lights, diffuse), pts, pts, 1, max_bounces, rng, **kw)
+        x = out["sum"].reshape(F_H * F_W, per_pixel, 3)
+        mean = x.mean(axis=1)
+        _sampler_cache[key] = dict(E=mean, var=(x * x).mean(axis=1) - mean * mean, dropped=float(out["dropped"].mean()))
+    return _sampler_cache[key]
+
+
+def test_path_sampler_meets_the_quadrature():
+    """The sampler itself against F0, max_bounces = 3, MIS on (HIGH, LOW) and off: its regional means within SIGMA of its own standard error."""
+    for name in ("F1_high", "F1_low", "F4_no_mis"):
+        ref = sampler_run(F_CASES[name]["lights"], (), 3, 40, 2027, mis=F_CASES[name].get("mis", True))
+        exp = f_expectation(name)
+        for label, mask in f_regions(name).items():
+            k = mask.reshape(-1)
+            z = (ref["E"][k].mean(axis=0) - exp["E"][k].mean(axis=0)) / (np.sqrt(ref["var"][k].sum(axis=0) / 40) / k.sum())
+            report(f"sampler/{name}/{label}", z="/".join(f"{v:+.2f}" for v in z))
+            assert np.abs(z).max() <= SIGMA, (name, label, z)
+        assert ref["dropped"] == 0.0
+
+
+def check_several_bounces(be, mirt, max_bounces, variant=0):
+    """F5: F1's HIGH scene plus a coloured diffuse sphere behind the eye plane, so that light reaches the visible cap by one, two and more
+    diffuse bounces: `pdf_in` carried from bounce to bounce (D5), the emissive hit's weight past bounce 1, the roulette on coloured throughput
+    (Q6) and, at max_bounces = 4, the drop of Q5.  Each region's mean within SIGMA sqrt(s^2 / n_backend + s^2 / n_ref) of the sampler's, s^2
+    the SAMPLER's per-pixel sample variance, summed over the region; `terminated` = n - dropped against the sampler's share of dropped paths,
+    SIGMA binomial sigma of both counts."""
+    sc = lit_scene(mirt, [HIGH], diffuse=[DIFFUSE])
+    guard_first_hits(be, sc, max_bounces)
+    ref = sampler_run([HIGH], [DIFFUSE], max_bounces, F5_REF, 4242)
+    res = be.render(sc, F_W, F_H, F5_ACC, max_bounces=max_bounces, variant=variant)
+    img = backend_image(res, F5_ACC)
+    zs = {}
+    for label, mask in f_regions("F1_high").items():
+        k = mask.reshape(-1)
+        se = np.sqrt(ref["var"][k].sum(axis=0) * (1.0 / F5_ACC + 1.0 / F5_REF)) / k.sum()
+        zs[label] = [float(v) for v in (img[mask].mean(axis=0) - ref["E"][k].mean(axis=0)) / se]
+    n, q = F_W * F_H * F5_ACC, ref["dropped"]
+    sigma_term = math.sqrt(n * q * (1 - q) * (1.0 + F5_ACC / F5_REF))
+    z_term = (res["counters"]["terminated"] - n * (1 - q)) / sigma_term if sigma_term > 0 else float(res["counters"]["terminated"] - n)
+    report(f"{be.name}/F5/bounces{max_bounces}/variant{variant}", **{f"z_{k}": "/".join(f"{v:+.2f}" for v in z) for k, z in zs.items()}, dropped_share=q, z_terminated=float(z_term))
+    for label, z in zs.items():
+        assert max(abs(v) for v in z) <= SIGMA, f"F5/{label}: {z} sigma from the sampler"
+    assert abs(z_term) <= SIGMA, z_term
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+@pytest.mark.parametrize("max_bounces", [4, 16])
+def test_several_bounces(be, mirt, max_bounces, variant):
+    check_several_bounces(be, mirt, max_bounces, variant=variant)
+
+
+def test_several_bounces_guards():
+    """From the sampler alone: at max_bounces = 4 the drop of Q5 is what is measured (the sampler without it is more than 2 SIGMA of the
+    check's own standard error away in some region), and the second diffuse sphere matters (F1's one-bounce expectation is as far away)."""
+    on, off = sampler_run([HIGH], [DIFFUSE], 4, F5_REF, 4242), sampler_run([HIGH], [DIFFUSE], 4, F5_REF, 4242, q5=False)
+    direct = f_expectation("F1_high")
+    far_q5 = far_direct = 0.0
+    for label, mask in f_regions("F1_high").items():
+        k = mask.reshape(-1)
+        se = np.sqrt(on["var"][k].sum(axis=0) * (1.0 / F5_ACC + 1.0 / F5_REF)) / k.sum()
+        far_q5 = max(far_q5, float((np.abs(off["E"][k].mean(axis=0) - on["E"][k].mean(axis=0)) / se).max()))
+        far_direct = max(far_direct, float((np.abs(direct["E"][k].mean(axis=0) - on["E"][k].mean(axis=0)) / se).max()))
+    report("guards/F5", q5_off_apart=far_q5, one_bounce_apart=far_direct, dropped_share=on["dropped"])
+    assert on["dropped"] > 0.0 and off["dropped"] == 0.0
+    assert far_q5 > 2 * SIGMA and far_direct > 2 * SIGMA

@@ -55,8 +55,9 @@ class GpuBackend:
             yield label, r.debug_trace_closest, r.debug_trace_shadow
             r.close()
 
-    def render(self, sc, w, h, n_acc, max_bounces, buckets=5, mis=True, variant=0):
-        r = self.mirt.Renderer(sc, max_bounces=max_bounces, buckets=buckets, mis=mis, **self.variants[variant][1])
+    def render(self, sc, w, h, n_acc, max_bounces, buckets=5, mis=True, variant=0, brdf=0, gloss_decay=None, exact_stream_order=False, trace_primary_rays=False):
+        r = self.mirt.Renderer(sc, max_bounces=max_bounces, buckets=buckets, mis=mis, brdf=brdf, gloss_decay=gloss_decay, exact_stream_order=exact_stream_order,
+                               trace_primary_rays=trace_primary_rays, **self.variants[variant][1])
         r.Resize(w, h); r.Accumulate(n_acc)
         frame = r.GetFrame().copy() if (n_acc % buckets == 0 and r.Render()) else None
         out = dict(acc=r.accumulator(), frame=frame, counters=r.counters())
@@ -181,3 +182,27 @@ def test_two_tone_sky(be, mirt, variant):
 @pytest.mark.parametrize("variant", [0, 1])
 def test_emissive_sphere(be, mirt, variant):
     cpu.check_emissive_sphere(be, mirt, variant=variant)
+
+
+# ---- F ----
+@pytest.mark.parametrize("variant", [0, 1])
+@pytest.mark.parametrize("name", cpu.F_LAMBERT)
+def test_direct_lighting(be, mirt, name, variant):
+    cpu.check_direct(be, mirt, name, variant=variant)
+
+
+@pytest.mark.parametrize("name", ["F1_high", "F1_low", "F1_sunk"])
+def test_direct_lighting_exact_stream_order(be, mirt, name):
+    """The second user of the per-hit shading text: k_tile_stream."""
+    cpu.check_direct(be, mirt, name, variant=0, exact_stream_order=True)
+
+
+@pytest.mark.parametrize("name", ["F1_high", "F1_low", "F1_below"])
+def test_direct_lighting_traced_primary_rays(be, mirt, name):
+    cpu.check_direct(be, mirt, name, variant=1, trace_primary_rays=True)
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+@pytest.mark.parametrize("max_bounces", [4, 16])
+def test_several_bounces(be, mirt, max_bounces, variant):
+    cpu.check_several_bounces(be, mirt, max_bounces, variant=variant)
