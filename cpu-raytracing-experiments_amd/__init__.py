@@ -231,10 +231,6 @@ def _lens_arguments(camera: Camera, aperture_radius, focus_depth):
     return float(np.float32(a)), float(np.float32(d))
 
 
-def _decay_array(decay) -> np.ndarray:
-    return np.ascontiguousarray([] if decay is None else decay, dtype=np.float32).reshape(-1)
-
-
 def noise_quantile(hist, q: float):
     """mirt_noise_quantile (host code, no GPU): the UPPER EDGE of the histogram bin that holds the q-quantile (q in (0, 1]) of the usable
     pixels — at most 12.5 % above the quantile itself.  None for an empty histogram."""
@@ -249,37 +245,218 @@ def noise_quantile(hist, q: float):
     return v.value if rc == MIRT_OK else None
 
 
-def _noise(call, check, handle, height, width, n_tiles, floor, want_map, map_out):
-    """Shared by Renderer.noise and GroupRenderer.noise: -> dict, or None while the frame is not due."""
-    img = None
-    if map_out is not None:
-        if map_out.dtype != np.float32 or map_out.shape != (height, width) or not map_out.flags.c_contiguous:
-            raise ValueError(f"map_out must be a C-contiguous float32 array of shape {(height, width)}")
-        img = map_out
-    elif want_map:
-        img = np.zeros((height, width), dtype=np.float32)
-    tiles = np.zeros((n_tiles, 4), dtype=np.float32)
-    hist = np.zeros(NOISE_BINS, dtype=np.uint32)
-    st = NoiseStats()
-    rc = check(call(handle, float(np.float32(floor)), _ptr(img) if img is not None else None, _ptr(tiles) if n_tiles else None, _ptr(hist), C.byref(st)))
-    if rc != MIRT_OK:
-        return None
-    return {**st.as_dict(), "tiles": tiles, "hist": hist, "map": img}
+class _Binding:
+    """What ``Renderer`` and ``GroupRenderer`` share: the methods that differ only in the handle (``_ctx`` / ``_g``) and in the prefix of
+    the entry point (``mirt_`` / ``mirt_group_``).  A subclass names both and creates the handle."""
+    _prefix = _handle = None
+
+    # -- plumbing ---------------------------------------------------------------------------
+    def _check(self, rc):
+        if rc < 0:
+            last_error = getattr(self._lib, self._prefix + "last_error")
+            raise MirtError(f"{self._prefix[:-1]} call failed ({rc}): {last_error(getattr(self, self._handle)).decode()}")
+        return rc
+
+    def _call(self, name, *args):
+        """mirt_<name> or mirt_group_<name> on this object's handle, checked."""
+        return self._check(getattr(self._lib, self._prefix + name)(getattr(self, self._handle), *args))
+
+    def _configure(self, gloss_decay, exact_stream_order, aov):
+        """The end of both constructors, after the policy is set."""
+        if gloss_decay is not None:
+            self.set_gloss_decay(gloss_decay)
+        if exact_stream_order:
+            self.set_stream_order(True)
+        if aov:
+            self.set_aov(True)
+        self.UpdateScene()
+
+    def close(self):
+        h = getattr(self, self._handle, None)
+        if h and h.value:
+            getattr(self._lib, self._prefix + "destroy")(h)
+            setattr(self, self._handle, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_policy(self, **kw):
+        p = Policy.from_buffer_copy(self.policy)
+        for k, v in kw.items():
+            setattr(p, k, int(v))
+        self._call("set_policy", C.byref(p))
+        self.policy = p                                    # only a policy the library accepted becomes this object's
+
+    def set_gloss_decay(self, decay=None):
+        """gloss_decay_table (Renderer.hpp:212) for brdf = 1: decay[b] is mixed into the GGX alpha at bounce b; later bounces use 0.
+        None or an empty sequence resets it to zeros.  (A group: on every member.)"""
+        d = np.ascontiguousarray([] if decay is None else decay, dtype=np.float32).reshape(-1)
+        self._call("set_gloss_decay", _ptr(d) if len(d) else None, len(d))
+
+    def set_stream_order(self, exact: bool = True):
+        """True: replay the reference's stream slots (counting sort by material, in-order compaction) and its scalar intersection tail
+        (BVH.hpp:270-286) — brute-force traversal, a fidelity mode (mirt_set_stream_order).  False: the default wavefront order.
+        (A group: on every member.)"""
+        self._call("set_stream_order", int(exact))
+
+    # -- scene hand-over (Application.cpp:230-234) -------------------------------------------------
+    def _hand_over_scene(self, nodes=None):
+        s = self.scene
+        self.geometry = np.ascontiguousarray(s.geometry, dtype=SPHERE)
+        self.material = np.ascontiguousarray(s.material, dtype=MATERIAL)
+        self.nodes, self.prims = bvh_build(self.geometry)
+        if nodes is not None:
+            self.nodes = np.ascontiguousarray(nodes, dtype=NODE)
+        self.lights = light_list(self.geometry, self.material)
+        hdri = np.ascontiguousarray(s.hdri, dtype=np.float32)
+        amb = np.ascontiguousarray(s.ambient, dtype=np.float32)
+        lights = self.lights if len(self.lights) else np.zeros(1, dtype=np.int32)
+        self._call("set_scene", _ptr(self.geometry), _ptr(self.prims), len(self.geometry), _ptr(self.nodes), len(self.nodes),
+                   _ptr(self.material), len(self.material), _ptr(lights), len(self.lights), _ptr(amb), _ptr(hdri), hdri.shape[1], hdri.shape[0])
+        self.UpdateCamera()
+
+    def UpdateCamera(self):
+        cam: Camera = self.scene.camera
+        pos = np.ascontiguousarray(cam.pos, dtype=np.float32)
+        ori = np.ascontiguousarray(cam.orient, dtype=np.float32)
+        self._call("set_camera", _ptr(pos), _ptr(ori), float(cam.half_width), float(cam.half_height), float(cam.z), float(cam.exposure))
+        if self._lens_follows_camera:                      # UpdateLens, Camera.hpp:21-26
+            self.set_lens()
+
+    # -- thin lens (mirt.h "thin lens") -------------------------------------------------------------
+    def set_lens(self, aperture_radius=None, focus_depth=None):
+        """Thin-lens depth of field: lens radius and axial depth of the plane of focus, both in world units; None = the scene camera's
+        (focal_length / (2 f_number) / unit_mm, focus_distance).  aperture_radius = 0 is the pinhole path.  Does not reset the accumulator.
+        (A group: on every member.)"""
+        self._call("set_lens", *_lens_arguments(self.scene.camera, aperture_radius, focus_depth))
+
+    def pick_focus(self, x: int, y: int):
+        """The reference's right-click pick (Application.cpp:271-304): the un-jittered pinhole ray of pixel (x, y) -> (distance, depth);
+        distance is inf on a miss, depth is the axial depth to hand to set_lens.  Changes no state.  (A group: on the first member.)"""
+        dist, depth = C.c_float(0), C.c_float(0)
+        self._call("pick_focus", int(x), int(y), C.byref(dist), C.byref(depth))
+        return dist.value, depth.value
+
+    # -- the reference interface ---------------------------------------------------------------
+    def Resize(self, new_width: int, new_height: int):     # Renderer.hpp:53-63 (+ camera.Resize, Application.cpp:375-376)
+        self.width, self.height = int(new_width), int(new_height)
+        self.scene.camera.resize(self.width, self.height)
+        self.UpdateCamera()
+        self._call("resize", self.width, self.height)
+        self.framebuffer = np.zeros((self.height, self.width, 4), dtype=np.float32)
+
+    def ResetAccumulator(self):            # Renderer.hpp:64-67
+        self._call("reset")
+
+    def Accumulate(self, n_calls: int = 1):   # Renderer.hpp:73-434
+        self._call("accumulate", n_calls)
+
+    def AccumulateAsync(self, n_calls: int = 1):
+        self._call("accumulate_async", n_calls)
+
+    def Synchronize(self):
+        self._call("synchronize")
+
+    def Render(self) -> bool:              # Renderer.hpp:436-478; False = not a multiple of `buckets` yet, frame unchanged
+        return self._call("render", _ptr(self.framebuffer)) == MIRT_OK
+
+    def GetFrame(self) -> np.ndarray:      # Renderer.hpp:68 — RGBA32F rows, row 0 = y 0 (bottom on screen)
+        return self.framebuffer
+
+    # -- state access ------------------------------------------------------------------------------
+    @property
+    def accumulations(self) -> int:
+        v = C.c_uint32(0)
+        self._call("get_accumulations", C.byref(v))
+        return v.value
+
+    def _read_slab(self, what: str, *tile_shape) -> np.ndarray:
+        """<what>_floats, then read_<what> -> [tile] + tile_shape f32."""
+        n = C.c_size_t(0)
+        self._call(what + "_floats", C.byref(n))
+        out = np.empty(n.value, dtype=np.float32)
+        self._call("read_" + what, _ptr(out))
+        return out.reshape((n.value // int(np.prod(tile_shape)),) + tile_shape)      # (a context may own no tile at all)
+
+    def _tiles(self) -> int:
+        """Tiles of accumulator() and of noise()["tiles"]: the context's own, or the whole image's for a group."""
+        n = C.c_size_t(0)
+        self._call("accumulator_floats", C.byref(n))
+        return n.value // (self.policy.buckets * 768)
+
+    def accumulator(self) -> np.ndarray:
+        """[local tile][bucket][rgb][256] f32 — AccumulationTile layout (Renderer.hpp:43-46).  A group: the whole image's slab in
+        LaunchIndex order (gathers first)."""
+        return self._read_slab("accumulator", self.policy.buckets, 3, 256)
+
+    # -- first-hit AOVs (mirt.h "first-hit AOVs") ---------------------------------------------------------
+    def set_aov(self, on: bool = True):
+        """True: every accumulation also adds each camera ray's depth, normal and albedo into a slab beside the accumulator
+        (the reference's compiled-out FIRST BOUNCE OUTPUTS, Renderer.hpp:216-231).  Only before the first accumulation; not in
+        exact stream order.  False: frees the slab.  (A group: on every member.)"""
+        self._call("set_aov", int(on))
+
+    def aov(self) -> np.ndarray:
+        """[local tile][plane][256] f32 sums over all accumulations: plane 0 depth, 1-3 normal, 4-6 albedo (F0 with brdf = 1).  A group: the
+        whole image's sums in LaunchIndex order (gathers first)."""
+        return self._read_slab("aov", AOV_PLANES, 256)
+
+    def render_aov(self, which: int, out: np.ndarray = None):
+        """One AOV (AOV_DEPTH, AOV_NORMAL, AOV_ALBEDO) resolved over the image, row 0 = y 0: depth (height, width), the others
+        (height, width, 3); only this context's tiles are written (a group: the whole frame, gathered first).  None (and `out` untouched)
+        before the first accumulation."""
+        img = _aov_image(self.height, self.width, which, out)
+        return img if self._call("render_aov", int(which), _ptr(img)) == MIRT_OK else None
+
+    # -- noise estimate (mirt.h "per-pixel noise estimate") ----------------------------------------------------
+    noise_quantile = staticmethod(noise_quantile)
+
+    def noise(self, floor: float = 0.0, want_map: bool = False, map_out: np.ndarray = None):
+        """Per-pixel relative standard error of the mean of the bucket means (mirt_noise) -> {"owned_pixels", "finite_pixels",
+        "nonfinite_pixels", "max", "mean", "tiles": (local tiles, 4) f32 {max, mean, usable, non-finite}, "hist": 2048 u32, "map": (height,
+        width) f32 or None}; only this context's tiles of the map are written (into `map_out` when given).  None, and nothing written,
+        while accumulations is 0 or not a multiple of `buckets`.  Changes no state.  A group: the whole image, without a gather — every
+        member reads its own slab; "tiles" is in LaunchIndex order."""
+        shape = (self.height, self.width)
+        img = None
+        if map_out is not None:
+            if map_out.dtype != np.float32 or map_out.shape != shape or not map_out.flags.c_contiguous:
+                raise ValueError(f"map_out must be a C-contiguous float32 array of shape {shape}")
+            img = map_out
+        elif want_map:
+            img = np.zeros(shape, dtype=np.float32)
+        tiles = np.zeros((self._tiles(), 4), dtype=np.float32)
+        hist = np.zeros(NOISE_BINS, dtype=np.uint32)
+        st = NoiseStats()
+        rc = self._call("noise", float(np.float32(floor)), _ptr(img) if img is not None else None, _ptr(tiles) if len(tiles) else None, _ptr(hist), C.byref(st))
+        if rc != MIRT_OK:
+            return None
+        return {**st.as_dict(), "tiles": tiles, "hist": hist, "map": img}
+
+    def accumulate_until(self, target: float, quantile: float = 0.95, floor: float = 0.0, check_every: int = None, max_accumulations: int = 1000):
+        """Accumulate `check_every` (default 4 x buckets) at a time until the `quantile` of the per-pixel noise is <= target and no pixel is
+        non-finite, or `max_accumulations` is reached (mirt_accumulate_until) -> {"converged", "issued", and the stats of the last check}."""
+        rule = StopRule(float(target), float(quantile), float(floor), int(check_every if check_every is not None else 4 * self.policy.buckets), int(max_accumulations))
+        st, issued = NoiseStats(), C.c_uint32(0)
+        rc = self._call("accumulate_until", C.byref(rule), C.byref(st), C.byref(issued))
+        return {"converged": rc == MIRT_OK, "issued": issued.value, **st.as_dict()}
+
+    def counters(self) -> dict:
+        c = Counters()
+        self._call("get_counters", C.byref(c))
+        return c.as_dict()
 
 
-def _accumulate_until(call, check, handle, buckets, target, quantile, floor, check_every, max_accumulations):
-    rule = StopRule(float(target), float(quantile), float(floor), int(check_every if check_every is not None else 4 * buckets), int(max_accumulations))
-    st, issued = NoiseStats(), C.c_uint32(0)
-    rc = check(call(handle, C.byref(rule), C.byref(st), C.byref(issued)))
-    return {"converged": rc == MIRT_OK, "issued": issued.value, **st.as_dict()}
-
-
-class Renderer:
+class Renderer(_Binding):
     """Mirror of the reference's ``Renderer<Policy>`` (Renderer.hpp:28-68) over the C-ABI.
 
     ``Renderer(scene)`` keeps a reference to the scene like the original; call ``UpdateScene`` after
     editing it (the reference rebuilds BVH + light list and resets, Application.cpp:508-510).
     """
+    _prefix, _handle = "mirt_", "_ctx"
 
     def __init__(self, scene: Scene, device: int = 0, max_bounces: int = 16, buckets: int = 5, mis: bool = True,
                  use_bvh: bool = False, count_traffic: bool = False, profile: bool = False, max_batch: int = 0,
@@ -296,242 +473,77 @@ class Renderer:
         self.framebuffer = None
         self.policy = Policy(max_bounces, buckets, int(mis), int(use_bvh), int(count_traffic), int(profile), max_batch, int(reference_tree), int(streams), int(gpu_build), int(trace_primary_rays),
                              int(brdf))
-        self._check(self._lib.mirt_set_policy(self._ctx, C.byref(self.policy)))
-        self._check(self._lib.mirt_debug_allow_half_boxes(self._ctx, int(allow_half_boxes)))
-        if gloss_decay is not None:
-            self.set_gloss_decay(gloss_decay)
-        if exact_stream_order:
-            self.set_stream_order(True)
-        if aov:
-            self.set_aov(True)
-        self.UpdateScene()
-
-    # -- plumbing ---------------------------------------------------------------------------
-    def _check(self, rc):
-        if rc < 0:
-            raise MirtError(f"mirt call failed ({rc}): {self._lib.mirt_last_error(self._ctx).decode()}")
-        return rc
-
-    def close(self):
-        if getattr(self, "_ctx", None) and self._ctx.value:
-            self._lib.mirt_destroy(self._ctx)
-            self._ctx = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("set_policy", C.byref(self.policy))
+        self._call("debug_allow_half_boxes", int(allow_half_boxes))
+        self._configure(gloss_decay, exact_stream_order, aov)
 
     def get_policy(self) -> dict:
         """The policy in effect (max_batch / streams resolved where they were left at 0 = auto)."""
         p = Policy()
-        self._check(self._lib.mirt_get_policy(self._ctx, C.byref(p)))
+        self._call("get_policy", C.byref(p))
         return {name: int(getattr(p, name)) for name, _ in Policy._fields_ if not name.startswith("_")}
-
-    def set_policy(self, **kw):
-        p = Policy.from_buffer_copy(self.policy)
-        for k, v in kw.items():
-            setattr(p, k, int(v))
-        self._check(self._lib.mirt_set_policy(self._ctx, C.byref(p)))
-        self.policy = p                                    # only a policy the library accepted becomes this object's
-
-    def set_gloss_decay(self, decay=None):
-        """gloss_decay_table (Renderer.hpp:212) for brdf = 1: decay[b] is mixed into the GGX alpha at bounce b; later bounces use 0.
-        None or an empty sequence resets it to zeros."""
-        d = _decay_array(decay)
-        self._check(self._lib.mirt_set_gloss_decay(self._ctx, _ptr(d) if len(d) else None, len(d)))
-
-    def set_stream_order(self, exact: bool = True):
-        """True: replay the reference's stream slots (counting sort by material, in-order compaction) and its scalar intersection tail
-        (BVH.hpp:270-286) — brute-force traversal, a fidelity mode (mirt_set_stream_order).  False: the default wavefront order."""
-        self._check(self._lib.mirt_set_stream_order(self._ctx, int(exact)))
 
     @property
     def stream_order(self) -> int:
         v = C.c_uint32(0)
-        self._check(self._lib.mirt_get_stream_order(self._ctx, C.byref(v)))
+        self._call("get_stream_order", C.byref(v))
         return v.value
 
-    # -- scene hand-over (Application.cpp:230-234) -------------------------------------------------
     def UpdateScene(self, nodes=None):
         """Hands the scene over again (after an edit).  `nodes`: a caller-made tree over the reference-order prims instead of the
         reference builder's (BVH.hpp:18-31 layout, children at first_id / first_id+1, leaves first_id..first_id+prim_count-1)."""
-        s = self.scene
-        self.geometry = np.ascontiguousarray(s.geometry, dtype=SPHERE)
-        self.material = np.ascontiguousarray(s.material, dtype=MATERIAL)
-        self.nodes, self.prims = bvh_build(self.geometry)
-        if nodes is not None:
-            self.nodes = np.ascontiguousarray(nodes, dtype=NODE)
-        self.lights = light_list(self.geometry, self.material)
-        hdri = np.ascontiguousarray(s.hdri, dtype=np.float32)
-        amb = np.ascontiguousarray(s.ambient, dtype=np.float32)
-        lights = self.lights if len(self.lights) else np.zeros(1, dtype=np.int32)
-        self._check(self._lib.mirt_set_scene(self._ctx, _ptr(self.geometry), _ptr(self.prims), len(self.geometry), _ptr(self.nodes), len(self.nodes),
-                                             _ptr(self.material), len(self.material), _ptr(lights), len(self.lights), _ptr(amb),
-                                             _ptr(hdri), hdri.shape[1], hdri.shape[0]))
-        self.UpdateCamera()
-
-    def UpdateCamera(self):
-        cam: Camera = self.scene.camera
-        pos = np.ascontiguousarray(cam.pos, dtype=np.float32)
-        ori = np.ascontiguousarray(cam.orient, dtype=np.float32)
-        self._check(self._lib.mirt_set_camera(self._ctx, _ptr(pos), _ptr(ori), float(cam.half_width), float(cam.half_height), float(cam.z), float(cam.exposure)))
-        if self._lens_follows_camera:                      # UpdateLens, Camera.hpp:21-26
-            self.set_lens()
-
-    # -- thin lens (mirt.h "thin lens") -------------------------------------------------------------
-    def set_lens(self, aperture_radius=None, focus_depth=None):
-        """Thin-lens depth of field: lens radius and axial depth of the plane of focus, both in world units; None = the scene camera's
-        (focal_length / (2 f_number) / unit_mm, focus_distance).  aperture_radius = 0 is the pinhole path.  Does not reset the accumulator."""
-        a, d = _lens_arguments(self.scene.camera, aperture_radius, focus_depth)
-        self._check(self._lib.mirt_set_lens(self._ctx, a, d))
+        self._hand_over_scene(nodes)
 
     def lens(self):
         """(aperture_radius, focus_depth) in effect."""
         a, d = C.c_float(0), C.c_float(0)
-        self._check(self._lib.mirt_get_lens(self._ctx, C.byref(a), C.byref(d)))
+        self._call("get_lens", C.byref(a), C.byref(d))
         return a.value, d.value
 
-    def pick_focus(self, x: int, y: int):
-        """The reference's right-click pick (Application.cpp:271-304): the un-jittered pinhole ray of pixel (x, y) -> (distance, depth);
-        distance is inf on a miss, depth is the axial depth to hand to set_lens.  Changes no state."""
-        dist, depth = C.c_float(0), C.c_float(0)
-        self._check(self._lib.mirt_pick_focus(self._ctx, int(x), int(y), C.byref(dist), C.byref(depth)))
-        return dist.value, depth.value
-
-    # -- the reference interface ---------------------------------------------------------------
     @staticmethod
     def RequiredTiling() -> int:          # Renderer.hpp:36
         return 16
 
-    def Resize(self, new_width: int, new_height: int):     # Renderer.hpp:53-63 (+ camera.Resize, Application.cpp:375-376)
-        self.width, self.height = int(new_width), int(new_height)
-        self.scene.camera.resize(self.width, self.height)
-        self.UpdateCamera()
-        self._check(self._lib.mirt_resize(self._ctx, self.width, self.height))
-        self.framebuffer = np.zeros((self.height, self.width, 4), dtype=np.float32)
-
-    def ResetAccumulator(self):            # Renderer.hpp:64-67
-        self._check(self._lib.mirt_reset(self._ctx))
-
-    def Accumulate(self, n_calls: int = 1):   # Renderer.hpp:73-434
-        self._check(self._lib.mirt_accumulate(self._ctx, n_calls))
-
-    def AccumulateAsync(self, n_calls: int = 1):
-        self._check(self._lib.mirt_accumulate_async(self._ctx, n_calls))
-
-    def Synchronize(self):
-        self._check(self._lib.mirt_synchronize(self._ctx))
-
-    def Render(self) -> bool:              # Renderer.hpp:436-478; False = not a multiple of `buckets` yet, frame unchanged
-        rc = self._check(self._lib.mirt_render(self._ctx, _ptr(self.framebuffer)))
-        return rc == MIRT_OK
-
-    def GetFrame(self) -> np.ndarray:      # Renderer.hpp:68 — RGBA32F rows, row 0 = y 0 (bottom on screen)
-        return self.framebuffer
-
     # -- sharding / state access -------------------------------------------------------------------
     def SetTileRange(self, first_tile: int, n_tiles: int):
-        self._check(self._lib.mirt_set_tile_range(self._ctx, first_tile, n_tiles))
+        self._call("set_tile_range", first_tile, n_tiles)
 
     def SetTileRows(self, first_row: int, row_stride: int):
         """Multi-GPU sharding by interleaved tile rows: this context renders tile rows first_row, first_row + row_stride, ..."""
-        self._check(self._lib.mirt_set_tile_rows(self._ctx, first_row, row_stride))
-
-    @property
-    def accumulations(self) -> int:
-        v = C.c_uint32(0)
-        self._check(self._lib.mirt_get_accumulations(self._ctx, C.byref(v)))
-        return v.value
-
-    def accumulator(self) -> np.ndarray:
-        """[local tile][bucket][rgb][256] f32 — AccumulationTile layout (Renderer.hpp:43-46)."""
-        n = C.c_size_t(0)
-        self._check(self._lib.mirt_accumulator_floats(self._ctx, C.byref(n)))
-        out = np.empty(n.value, dtype=np.float32)
-        self._check(self._lib.mirt_read_accumulator(self._ctx, _ptr(out)))
-        return out.reshape(n.value // (self.policy.buckets * 768), self.policy.buckets, 3, 256)      # (a context may own no tile at all)
+        self._call("set_tile_rows", first_row, row_stride)
 
     def accumulator_device(self):
         p, b = C.c_void_p(), C.c_size_t(0)
-        self._check(self._lib.mirt_accumulator_device(self._ctx, C.byref(p), C.byref(b)))
+        self._call("accumulator_device", C.byref(p), C.byref(b))
         return p.value, b.value
 
     def load_accumulator(self, src, accumulations: int, is_device: bool = False):
         ptr = C.c_void_p(src) if is_device else _ptr(np.ascontiguousarray(src, dtype=np.float32))
-        self._check(self._lib.mirt_load_accumulator(self._ctx, ptr, int(is_device), accumulations))
-
-    # -- first-hit AOVs (mirt.h "first-hit AOVs") ---------------------------------------------------------
-    def set_aov(self, on: bool = True):
-        """True: every accumulation also adds each camera ray's depth, normal and albedo into a slab beside the accumulator
-        (the reference's compiled-out FIRST BOUNCE OUTPUTS, Renderer.hpp:216-231).  Only before the first accumulation; not in
-        exact stream order.  False: frees the slab."""
-        self._check(self._lib.mirt_set_aov(self._ctx, int(on)))
+        self._call("load_accumulator", ptr, int(is_device), accumulations)
 
     @property
     def aov_enabled(self) -> bool:
         v = C.c_uint32(0)
-        self._check(self._lib.mirt_get_aov(self._ctx, C.byref(v)))
+        self._call("get_aov", C.byref(v))
         return bool(v.value)
-
-    def aov(self) -> np.ndarray:
-        """[local tile][plane][256] f32 sums over all accumulations: plane 0 depth, 1-3 normal, 4-6 albedo (F0 with brdf = 1)."""
-        n = C.c_size_t(0)
-        self._check(self._lib.mirt_aov_floats(self._ctx, C.byref(n)))
-        out = np.empty(n.value, dtype=np.float32)
-        self._check(self._lib.mirt_read_aov(self._ctx, _ptr(out)))
-        return out.reshape(n.value // (AOV_PLANES * 256), AOV_PLANES, 256)
 
     def aov_device(self):
         p, b = C.c_void_p(), C.c_size_t(0)
-        self._check(self._lib.mirt_aov_device(self._ctx, C.byref(p), C.byref(b)))
+        self._call("aov_device", C.byref(p), C.byref(b))
         return p.value, b.value
 
     def load_aov(self, src, is_device: bool = False):
         ptr = C.c_void_p(src) if is_device else _ptr(np.ascontiguousarray(src, dtype=np.float32))
-        self._check(self._lib.mirt_load_aov(self._ctx, ptr, int(is_device)))
-
-    def render_aov(self, which: int, out: np.ndarray = None):
-        """One AOV (AOV_DEPTH, AOV_NORMAL, AOV_ALBEDO) resolved over the image, row 0 = y 0: depth (height, width), the others
-        (height, width, 3); only this context's tiles are written.  None (and `out` untouched) before the first accumulation."""
-        img = _aov_image(self.height, self.width, which, out)
-        rc = self._check(self._lib.mirt_render_aov(self._ctx, int(which), _ptr(img)))
-        return img if rc == MIRT_OK else None
-
-    # -- noise estimate (mirt.h "per-pixel noise estimate") ----------------------------------------------------
-    noise_quantile = staticmethod(noise_quantile)
-
-    def _local_tiles(self) -> int:
-        n = C.c_size_t(0)
-        self._check(self._lib.mirt_accumulator_floats(self._ctx, C.byref(n)))
-        return n.value // (self.policy.buckets * 768)
-
-    def noise(self, floor: float = 0.0, want_map: bool = False, map_out: np.ndarray = None):
-        """Per-pixel relative standard error of the mean of the bucket means (mirt_noise) -> {"owned_pixels", "finite_pixels",
-        "nonfinite_pixels", "max", "mean", "tiles": (local tiles, 4) f32 {max, mean, usable, non-finite}, "hist": 2048 u32, "map": (height,
-        width) f32 or None}; only this context's tiles of the map are written (into `map_out` when given).  None, and nothing written,
-        while accumulations is 0 or not a multiple of `buckets`.  Changes no state."""
-        return _noise(self._lib.mirt_noise, self._check, self._ctx, self.height, self.width, self._local_tiles(), floor, want_map, map_out)
-
-    def accumulate_until(self, target: float, quantile: float = 0.95, floor: float = 0.0, check_every: int = None, max_accumulations: int = 1000):
-        """Accumulate `check_every` (default 4 x buckets) at a time until the `quantile` of the per-pixel noise is <= target and no pixel is
-        non-finite, or `max_accumulations` is reached (mirt_accumulate_until) -> {"converged", "issued", and the stats of the last check}."""
-        return _accumulate_until(self._lib.mirt_accumulate_until, self._check, self._ctx, self.policy.buckets, target, quantile, floor, check_every, max_accumulations)
-
-    def counters(self) -> dict:
-        c = Counters()
-        self._check(self._lib.mirt_get_counters(self._ctx, C.byref(c)))
-        return c.as_dict()
+        self._call("load_aov", ptr, int(is_device))
 
     def kernel_times(self, reset: bool = True) -> dict:
         t = KernelTimes()
-        self._check(self._lib.mirt_get_kernel_times(self._ctx, C.byref(t), int(reset)))
+        self._call("get_kernel_times", C.byref(t), int(reset))
         return {k: {"ms": t.ms[i], "launches": int(t.launches[i])} for i, k in enumerate(KERNEL_CLASSES)}
 
     def debug_info(self) -> dict:
         out = (C.c_uint32 * 8)()
-        self._check(self._lib.mirt_debug_info(self._ctx, out))
+        self._call("debug_info", out)
         keys = ("records", "lds_records", "lds_spheres", "depth", "half_boxes", "trace_lds_bytes", "trace_workgroups_per_cu", "cus")
         d = dict(zip(keys, [int(v) for v in out]))
         d["wide"] = (d["half_boxes"] >> 1) & 1             # 64-B binary16 records of up to four children
@@ -542,29 +554,27 @@ class Renderer:
         """The records the trace kernels walk, read back from the device: (uint32 words shaped [records, words per record],
         {"records", "record_bytes", "layout" (0 f32 child pairs, 1 binary16 child pairs, 2 4-wide binary16), "depth"})."""
         info = (C.c_uint32 * 4)()
-        self._check(self._lib.mirt_debug_tree(self._ctx, None, 0, info))
+        self._call("debug_tree", None, 0, info)
         n, rec_bytes = int(info[0]), int(info[1])
         words = np.zeros((n, rec_bytes // 4), dtype=np.uint32)
-        self._check(self._lib.mirt_debug_tree(self._ctx, _ptr(words), words.nbytes, info))
+        self._call("debug_tree", _ptr(words), words.nbytes, info)
         return words, dict(zip(("records", "record_bytes", "layout", "depth"), [int(v) for v in info]))
 
     def debug_primary_lists(self) -> list:
         """hist[n] = pixels whose candidate list holds n spheres (n = 0..7), hist[8] = 8 or more, hist[9] = pixels without a list."""
         out = (C.c_uint32 * 10)()
-        self._check(self._lib.mirt_debug_primary_lists(self._ctx, out))
+        self._call("debug_primary_lists", out)
         return [int(v) for v in out]
 
     def debug_primary_counts(self) -> np.ndarray:
         """[local tile][256] uint32: the length of every local pixel's candidate list; 0xffffffff = a pixel without a list."""
-        n = C.c_size_t(0)
-        self._check(self._lib.mirt_accumulator_floats(self._ctx, C.byref(n)))
-        out = np.zeros((n.value // (self.policy.buckets * 768), 256), dtype=np.uint32)
-        self._check(self._lib.mirt_debug_primary_counts(self._ctx, _ptr(out), out.size))
+        out = np.zeros((self._tiles(), 256), dtype=np.uint32)
+        self._call("debug_primary_counts", _ptr(out), out.size)
         return out
 
     def stream_handle(self) -> int:
         p = C.c_void_p()
-        self._check(self._lib.mirt_get_stream(self._ctx, C.byref(p)))
+        self._call("get_stream", C.byref(p))
         return p.value
 
     # -- stage-level (parity tests) ---------------------------------------------------------------
@@ -572,14 +582,14 @@ class Renderer:
         n = (self.width // 16) * (self.height // 16) * 256
         p = np.empty((3, n), dtype=np.float32)
         d = np.empty((3, n), dtype=np.float32)
-        self._check(self._lib.mirt_debug_raygen(self._ctx, accumulations, _ptr(p), _ptr(d)))
+        self._call("debug_raygen", accumulations, _ptr(p), _ptr(d))
         return p, d
 
     def debug_trace_closest(self, p: np.ndarray, d: np.ndarray):
         p = np.ascontiguousarray(p, dtype=np.float32); d = np.ascontiguousarray(d, dtype=np.float32)
         n = p.shape[1]
         tfar = np.empty(n, dtype=np.float32); prim = np.empty(n, dtype=np.int32)
-        self._check(self._lib.mirt_debug_trace_closest(self._ctx, n, _ptr(p), _ptr(d), _ptr(tfar), _ptr(prim)))
+        self._call("debug_trace_closest", n, _ptr(p), _ptr(d), _ptr(tfar), _ptr(prim))
         return tfar, prim
 
     def debug_trace_shadow(self, p: np.ndarray, d: np.ndarray, tfar: np.ndarray):
@@ -587,22 +597,23 @@ class Renderer:
         tfar = np.ascontiguousarray(tfar, dtype=np.float32)
         n = p.shape[1]
         occ = np.empty(n, dtype=np.uint8)
-        self._check(self._lib.mirt_debug_trace_shadow(self._ctx, n, _ptr(p), _ptr(d), _ptr(tfar), _ptr(occ)))
+        self._call("debug_trace_shadow", n, _ptr(p), _ptr(d), _ptr(tfar), _ptr(occ))
         return occ
 
     def debug_math(self, fn: int, inputs: np.ndarray, n_out: int) -> np.ndarray:
         inputs = np.ascontiguousarray(inputs, dtype=np.float32)
         n = inputs.shape[-1]
         out = np.empty((n_out, n), dtype=np.float32)
-        self._check(self._lib.mirt_debug_math(self._ctx, fn, n, _ptr(inputs), _ptr(out)))
+        self._call("debug_math", fn, n, _ptr(inputs), _ptr(out))
         return out
 
 
-class GroupRenderer:
+class GroupRenderer(_Binding):
     """The same `Renderer<Policy>` interface on several GPUs of one node, driven by this one process through the library's
     mirt_group_* entry points (include/mirt.h): scene replicated, tile rows interleaved over the devices, one RCCL gather of the
     accumulator slabs to devices[0] when a frame or the accumulator is read.  `devices` may repeat a device (rehearsal on a
     one-GPU box; slabs then move with device copies)."""
+    _prefix, _handle = "mirt_group_", "_g"
 
     def __init__(self, scene: Scene, devices=(0,), max_bounces: int = 16, buckets: int = 5, mis: bool = True, use_bvh: bool = True,
                  count_traffic: bool = False, max_batch: int = 0, streams: int = 0, reference_tree: bool = False, gpu_build: bool = False,
@@ -619,169 +630,29 @@ class GroupRenderer:
         self.framebuffer = None
         self.policy = Policy(max_bounces, buckets, int(mis), int(use_bvh), int(count_traffic), 0, max_batch, int(reference_tree), int(streams), int(gpu_build), 0,
                              int(brdf))
-        self._check(self._lib.mirt_group_set_policy(self._g, C.byref(self.policy)))
-        if gloss_decay is not None:
-            self.set_gloss_decay(gloss_decay)
-        if exact_stream_order:
-            self.set_stream_order(True)
-        if aov:
-            self.set_aov(True)
-        self.UpdateScene()
-
-    def _check(self, rc):
-        if rc < 0:
-            raise MirtError(f"mirt_group call failed ({rc}): {self._lib.mirt_group_last_error(self._g).decode()}")
-        return rc
-
-    def close(self):
-        if getattr(self, "_g", None) and self._g.value:
-            self._lib.mirt_group_destroy(self._g)
-            self._g = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_policy(self, **kw):
-        p = Policy.from_buffer_copy(self.policy)
-        for k, v in kw.items():
-            setattr(p, k, int(v))
-        self._check(self._lib.mirt_group_set_policy(self._g, C.byref(p)))
-        self.policy = p
-
-    def set_gloss_decay(self, decay=None):
-        """Renderer.set_gloss_decay on every member."""
-        d = _decay_array(decay)
-        self._check(self._lib.mirt_group_set_gloss_decay(self._g, _ptr(d) if len(d) else None, len(d)))
-
-    def set_stream_order(self, exact: bool = True):
-        """Renderer.set_stream_order on every member."""
-        self._check(self._lib.mirt_group_set_stream_order(self._g, int(exact)))
+        self._call("set_policy", C.byref(self.policy))
+        self._configure(gloss_decay, exact_stream_order, aov)
 
     def UpdateScene(self):
-        s = self.scene
-        self.geometry = np.ascontiguousarray(s.geometry, dtype=SPHERE)
-        self.material = np.ascontiguousarray(s.material, dtype=MATERIAL)
-        self.nodes, self.prims = bvh_build(self.geometry)
-        self.lights = light_list(self.geometry, self.material)
-        hdri = np.ascontiguousarray(s.hdri, dtype=np.float32)
-        amb = np.ascontiguousarray(s.ambient, dtype=np.float32)
-        lights = self.lights if len(self.lights) else np.zeros(1, dtype=np.int32)
-        self._check(self._lib.mirt_group_set_scene(self._g, _ptr(self.geometry), _ptr(self.prims), len(self.geometry), _ptr(self.nodes), len(self.nodes),
-                                                   _ptr(self.material), len(self.material), _ptr(lights), len(self.lights), _ptr(amb),
-                                                   _ptr(hdri), hdri.shape[1], hdri.shape[0]))
-        self.UpdateCamera()
-
-    def UpdateCamera(self):
-        cam: Camera = self.scene.camera
-        pos = np.ascontiguousarray(cam.pos, dtype=np.float32)
-        ori = np.ascontiguousarray(cam.orient, dtype=np.float32)
-        self._check(self._lib.mirt_group_set_camera(self._g, _ptr(pos), _ptr(ori), float(cam.half_width), float(cam.half_height), float(cam.z), float(cam.exposure)))
-        if self._lens_follows_camera:
-            self.set_lens()
-
-    def set_lens(self, aperture_radius=None, focus_depth=None):
-        """Renderer.set_lens on every member."""
-        a, d = _lens_arguments(self.scene.camera, aperture_radius, focus_depth)
-        self._check(self._lib.mirt_group_set_lens(self._g, a, d))
+        self._hand_over_scene()
 
     def lens(self):
         """(aperture_radius, focus_depth) in effect (the first member's; all members hold the same)."""
         ctx = C.c_void_p()
-        self._check(self._lib.mirt_group_member(self._g, 0, C.byref(ctx)))
+        self._call("member", 0, C.byref(ctx))
         a, d = C.c_float(0), C.c_float(0)
         self._lib.mirt_get_lens(ctx, C.byref(a), C.byref(d))
         return a.value, d.value
 
-    def pick_focus(self, x: int, y: int):
-        """Renderer.pick_focus on the first member."""
-        dist, depth = C.c_float(0), C.c_float(0)
-        self._check(self._lib.mirt_group_pick_focus(self._g, int(x), int(y), C.byref(dist), C.byref(depth)))
-        return dist.value, depth.value
-
-    def Resize(self, new_width: int, new_height: int):
-        self.width, self.height = int(new_width), int(new_height)
-        self.scene.camera.resize(self.width, self.height)
-        self.UpdateCamera()
-        self._check(self._lib.mirt_group_resize(self._g, self.width, self.height))
-        self.framebuffer = np.zeros((self.height, self.width, 4), dtype=np.float32)
-
-    def ResetAccumulator(self):
-        self._check(self._lib.mirt_group_reset(self._g))
-
-    def Accumulate(self, n_calls: int = 1):
-        self._check(self._lib.mirt_group_accumulate(self._g, n_calls))
-
-    def AccumulateAsync(self, n_calls: int = 1):
-        self._check(self._lib.mirt_group_accumulate_async(self._g, n_calls))
-
-    def Synchronize(self):
-        self._check(self._lib.mirt_group_synchronize(self._g))
-
-    def Render(self) -> bool:
-        return self._check(self._lib.mirt_group_render(self._g, _ptr(self.framebuffer))) == MIRT_OK
-
-    def GetFrame(self) -> np.ndarray:
-        return self.framebuffer
-
-    @property
-    def accumulations(self) -> int:
-        v = C.c_uint32(0)
-        self._check(self._lib.mirt_group_get_accumulations(self._g, C.byref(v)))
-        return v.value
-
-    def accumulator(self) -> np.ndarray:
-        """The whole image's [tile][bucket][rgb][256] slab in LaunchIndex order (gathers first)."""
-        n = C.c_size_t(0)
-        self._check(self._lib.mirt_group_accumulator_floats(self._g, C.byref(n)))
-        out = np.empty(n.value, dtype=np.float32)
-        self._check(self._lib.mirt_group_read_accumulator(self._g, _ptr(out)))
-        return out.reshape(n.value // (self.policy.buckets * 768), self.policy.buckets, 3, 256)
-
-    def set_aov(self, on: bool = True):
-        """Renderer.set_aov on every member."""
-        self._check(self._lib.mirt_group_set_aov(self._g, int(on)))
-
-    def aov(self) -> np.ndarray:
-        """The whole image's [tile][plane][256] AOV sums in LaunchIndex order (gathers first)."""
-        n = C.c_size_t(0)
-        self._check(self._lib.mirt_group_aov_floats(self._g, C.byref(n)))
-        out = np.empty(n.value, dtype=np.float32)
-        self._check(self._lib.mirt_group_read_aov(self._g, _ptr(out)))
-        return out.reshape(n.value // (AOV_PLANES * 256), AOV_PLANES, 256)
-
-    read_aov = aov
-
-    def render_aov(self, which: int, out: np.ndarray = None):
-        """Renderer.render_aov of the whole frame (gathers first)."""
-        img = _aov_image(self.height, self.width, which, out)
-        rc = self._check(self._lib.mirt_group_render_aov(self._g, int(which), _ptr(img)))
-        return img if rc == MIRT_OK else None
-
-    noise_quantile = staticmethod(noise_quantile)
-
-    def noise(self, floor: float = 0.0, want_map: bool = False, map_out: np.ndarray = None):
-        """Renderer.noise of the whole image, without a gather: every member reads its own slab; "tiles" is in LaunchIndex order."""
-        return _noise(self._lib.mirt_group_noise, self._check, self._g, self.height, self.width, (self.width // 16) * (self.height // 16), floor, want_map, map_out)
-
-    def accumulate_until(self, target: float, quantile: float = 0.95, floor: float = 0.0, check_every: int = None, max_accumulations: int = 1000):
-        """Renderer.accumulate_until on the whole group."""
-        return _accumulate_until(self._lib.mirt_group_accumulate_until, self._check, self._g, self.policy.buckets, target, quantile, floor, check_every, max_accumulations)
-
-    def counters(self) -> dict:
-        c = Counters()
-        self._check(self._lib.mirt_group_get_counters(self._g, C.byref(c)))
-        return c.as_dict()
+    read_aov = _Binding.aov
 
     def Gather(self):
         """The one exchange of the path: every member's accumulator slab to devices[0] (implied by accumulator() and Render())."""
-        self._check(self._lib.mirt_group_gather(self._g))
+        self._call("gather")
 
     def gather_ms(self) -> float:
         v = C.c_double(0.0)
-        self._check(self._lib.mirt_group_last_gather_ms(self._g, C.byref(v)))
+        self._call("last_gather_ms", C.byref(v))
         return v.value
 
 

@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include "device_math.hpp"
 #include "hits_wave_map.hpp"
+#include "tile_map.hpp"
 
 namespace mirt {
 
@@ -34,8 +35,6 @@ constexpr uint32_t kTraceBlock = 1024;          // trace kernels: one workgroup 
 constexpr uint32_t kLdsStack = 16;              // traversal-stack entries per lane kept in LDS (deeper ones spill to scratch)
 constexpr uint32_t kLdsStackWide = 12;          // ... with binary16 records but u32 entries (> 32768 records or spheres): 48 KB, so that two workgroups still share a CU
 constexpr uint32_t kLeafBit = 0x80000000u;      // child reference flag (bvh_layout.hpp)
-constexpr uint32_t kTileSize = 256;
-constexpr uint32_t kTileRoot = 16;
 constexpr uint32_t kStack = 64;                 // Stack<StackFrame,64>, BVH.hpp:321
 constexpr uint32_t kDestAccum = 0x80000000u;    // shadow-entry destination flag: the path ended at this hit — path id instead of stream slot
 
@@ -750,12 +749,7 @@ MIRT_DI uint32_t udiv_f(uint32_t n, uint32_t d, float inv_d, uint32_t& rem) {
 	rem = static_cast<uint32_t>(r);
 	return q;
 }
-// Global LaunchIndex (Renderer.hpp:75,84-88) of this context's local tile.
-MIRT_DI uint32_t global_tile(uint32_t first_tile, uint32_t run_tiles, uint32_t stride_tiles, uint32_t local_tile) {     // k_resolve (once per pixel and frame)
-	if (stride_tiles == 0u) return first_tile + local_tile;
-	const uint32_t run = local_tile / run_tiles;
-	return first_tile + run * stride_tiles + (local_tile - run * run_tiles);
-}
+// Global LaunchIndex (Renderer.hpp:75,84-88) of this context's local tile: TileMap::global_tile (tile_map.hpp) without its integer division.
 MIRT_DI uint32_t global_tile(const FrameParams& fp, uint32_t local_tile) {
 	if (fp.stride_tiles == 0u) return fp.first_tile + local_tile;             // wave-uniform branch
 	uint32_t in_run;
@@ -1258,14 +1252,10 @@ __global__ __launch_bounds__(kBlock) void k_first_hit_aov(SceneDev sc, FramePara
 // mirt_render_aov: one of the three outputs of the slab above, row-major over the image (row 0 = y 0), 1 (depth) or 3 floats per pixel.
 // Depth and colour: sum / accumulations; normal: normalize3(sum), (0,0,0) where the sum has no length.  IEEE division and sqrt.
 constexpr int kAovDepth = 0, kAovNormal = 1, kAovAlbedo = 2;
-__global__ __launch_bounds__(kBlock) void k_resolve_aov(const float* __restrict__ aov, float* __restrict__ out, uint32_t n_pix, uint32_t first_tile, uint32_t run_tiles,
-                                                        uint32_t stride_tiles, uint32_t h_tiles, uint32_t width, int which, float accumulations) {
+__global__ __launch_bounds__(kBlock) void k_resolve_aov(const float* __restrict__ aov, float* __restrict__ out, uint32_t n_pix, TileMap tiles, int which, float accumulations) {
 	for (uint32_t pix = blockIdx.x * kBlock + threadIdx.x; pix < n_pix; pix += gridDim.x * kBlock) {
 		const float* src = aov + static_cast<size_t>(pix >> 8) * (kAovPlanes * kTileSize) + (pix & 255u);
-		const uint32_t tile = global_tile(first_tile, run_tiles, stride_tiles, pix >> 8), ID = pix & 255u;
-		const uint32_t x = kTileRoot * (tile % h_tiles) + (ID & 15u);
-		const uint32_t y = kTileRoot * (tile / h_tiles) + (ID >> 4);
-		const size_t at = static_cast<size_t>(y) * width + x;
+		const size_t at = tiles.pixel_offset(pix >> 8, pix & 255u, 1u);
 		if (which == kAovDepth) { out[at] = src[0] / accumulations; continue; }
 		const uint32_t first = which == kAovNormal ? 1u : 4u;
 		f3 v{ src[first * kTileSize], src[(first + 1u) * kTileSize], src[(first + 2u) * kTileSize] };
@@ -1725,8 +1715,7 @@ MIRT_DI float median_k(float* v, uint32_t k) {
 	}
 	return (k & 1u) ? v[k / 2] : (v[k / 2 - 1] + v[k / 2]) * 0.5f;
 }
-__global__ __launch_bounds__(kBlock) void k_resolve(const float* __restrict__ accum, float4* __restrict__ fb, uint32_t n_pix, uint32_t first_tile,
-                                                    uint32_t run_tiles, uint32_t stride_tiles, uint32_t h_tiles, uint32_t width, uint32_t buckets, float scale) {
+__global__ __launch_bounds__(kBlock) void k_resolve(const float* __restrict__ accum, float4* __restrict__ fb, uint32_t n_pix, TileMap tiles, uint32_t buckets, float scale) {
 	for (uint32_t pix = blockIdx.x * kBlock + threadIdx.x; pix < n_pix; pix += gridDim.x * kBlock) {
 		const float* src = accum + static_cast<size_t>(pix >> 8) * buckets * 3u * kTileSize + (pix & 255u);
 		float ch[3];
@@ -1736,10 +1725,7 @@ __global__ __launch_bounds__(kBlock) void k_resolve(const float* __restrict__ ac
 			ch[c] = scale * median_k(v, buckets);                               // Renderer.hpp:453-455
 		}
 		tonemapping(ch[0], ch[1], ch[2]);                                       // Renderer.hpp:461
-		const uint32_t tile = global_tile(first_tile, run_tiles, stride_tiles, pix >> 8), ID = pix & 255u;
-		const uint32_t x = kTileRoot * (tile % h_tiles) + (ID & 15u);
-		const uint32_t y = kTileRoot * (tile / h_tiles) + (ID >> 4);
-		fb[static_cast<size_t>(y) * width + x] = make_float4(ch[0], ch[1], ch[2], 1.0f);   // Renderer.hpp:447,465
+		fb[tiles.pixel_offset(pix >> 8, pix & 255u, 1u)] = make_float4(ch[0], ch[1], ch[2], 1.0f);   // Renderer.hpp:447,465
 	}
 }
 
@@ -1761,8 +1747,7 @@ constexpr uint32_t kNoiseBins = 2048u;
 constexpr uint32_t kNoiseUsableBelow = 0x7f800000u;
 constexpr uint32_t kNoiseMaxBuckets = 16u;     // one y_j per register; mirt_noise asserts that MIRT_MAX_BUCKETS fits
 __global__ __launch_bounds__(kTileSize) void k_noise(const float* __restrict__ accum, float* __restrict__ map, float4* __restrict__ tile_rec, uint32_t* __restrict__ hist,
-                                                     uint32_t first_tile, uint32_t run_tiles, uint32_t stride_tiles, uint32_t h_tiles, uint32_t width, uint32_t buckets,
-                                                     float scale, float floor_) {
+                                                     TileMap tiles, uint32_t buckets, float scale, float floor_) {
 	__shared__ uint32_t bins[kNoiseBins];
 	__shared__ uint32_t w_max[kTileSize / 64u], w_cnt[kTileSize / 64u];
 	__shared__ float w_sum[kTileSize / 64u];
@@ -1786,12 +1771,7 @@ __global__ __launch_bounds__(kTileSize) void k_noise(const float* __restrict__ a
 	const float se = __builtin_sqrtf(var / static_cast<float>(buckets));
 	const float denom = mean + floor_;
 	const float e = denom == 0.0f ? 0.0f : se / denom;
-	if (map) {
-		const uint32_t tile = global_tile(first_tile, run_tiles, stride_tiles, local);
-		const uint32_t x = kTileRoot * (tile % h_tiles) + (ID & 15u);
-		const uint32_t yy = kTileRoot * (tile / h_tiles) + (ID >> 4);
-		map[static_cast<size_t>(yy) * width + x] = e;
-	}
+	if (map) map[tiles.pixel_offset(local, ID, 1u)] = e;
 	const uint32_t word = __float_as_uint(e);
 	const bool usable = word < kNoiseUsableBelow;
 	uint32_t m = usable ? word : 0u;

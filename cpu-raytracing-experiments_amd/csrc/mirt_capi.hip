@@ -70,6 +70,13 @@ struct PipeSlot {
 	StreamBuf stream_buf[2]{};
 	ShadowBuf shadow_buf{};
 	HitRec* hit = nullptr;           // RayStream<>::Hit: one 8-B {tfar, primID} record per ray (two planes' worth of the arena)
+	// Buffers, events and stream.  The caller has synchronised every stream.
+	void release() {
+		arena.release(); counts.release(); contrib.release(); fat.release();
+		for (hipEvent_t* e : { &batch_done, &merged, &aov_done }) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+		if (stream) (void)hipStreamDestroy(stream);
+		stream = nullptr;
+	}
 };
 
 } // namespace
@@ -83,7 +90,7 @@ struct mirt_ctx {
 	mirt_policy policy{ 16, 5, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0 };         // RendererPolicy defaults, Renderer.hpp:19-26,41,71; USEBVH false BVH.hpp:307; BRDF 0 :70
 	uint32_t width = 0, height = 0, h_tiles = 0, v_tiles = 0;
 	uint32_t first_tile = 0, n_tiles = 0;
-	uint32_t run_tiles = 0, stride_tiles = 0;   // interleaved tile rows (mirt_set_tile_rows); stride 0 = one contiguous range
+	uint32_t run_tiles = 1, stride_tiles = 0;   // interleaved tile rows (mirt_set_tile_rows); stride 0 = one contiguous range: see tile_map()
 	uint32_t accumulations = 0;
 	bool have_scene = false, have_camera = false;
 
@@ -302,15 +309,7 @@ int ensure_streams(mirt_ctx* c) {
 	if (cap == c->capacity && nb == c->arena_bounces && c->slots.size() == want && c->slots[0].contrib.bytes >= acc_bytes) return MIRT_OK;
 	HIP_TRY(c, sync_all(c));
 	c->aov_prev = nullptr;                                                   // (every batch has finished; the event's slot may go away below)
-	while (c->slots.size() > want) {
-		PipeSlot& sl = c->slots.back();
-		sl.arena.release(); sl.counts.release(); sl.contrib.release(); sl.fat.release();
-		if (sl.batch_done) (void)hipEventDestroy(sl.batch_done);
-		if (sl.merged) (void)hipEventDestroy(sl.merged);
-		if (sl.aov_done) (void)hipEventDestroy(sl.aov_done);
-		if (sl.stream) (void)hipStreamDestroy(sl.stream);
-		c->slots.pop_back();
-	}
+	while (c->slots.size() > want) { c->slots.back().release(); c->slots.pop_back(); }
 	while (c->slots.size() < want) {
 		PipeSlot sl;
 		HIP_TRY(c, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
@@ -424,13 +423,18 @@ void update_lens_axes(mirt_ctx* c) {
 }
 bool lens_on(const mirt_ctx* c) { return c->lens.aperture > 0.0f; }
 
+// The context's n_tiles local tiles in the image (tile_map.hpp).
+TileMap tile_map(const mirt_ctx* c) { return TileMap{ c->first_tile, c->run_tiles, c->stride_tiles, c->h_tiles, c->width }; }
+void set_tile_map(mirt_ctx* c, const TileMap& m, uint32_t n_tiles) { c->first_tile = m.first_tile; c->run_tiles = m.run_tiles; c->stride_tiles = m.stride_tiles; c->n_tiles = n_tiles; }
+
 FrameParams frame_params(const mirt_ctx* c, uint32_t acc_base, uint32_t batch_n) {
 	FrameParams fp{};
+	const TileMap m = tile_map(c);
 	fp.cam = c->camera;
-	fp.h_tiles = c->h_tiles;
-	fp.first_tile = c->first_tile;
-	fp.run_tiles = c->run_tiles ? c->run_tiles : 1u;
-	fp.stride_tiles = c->stride_tiles;
+	fp.h_tiles = m.h_tiles;
+	fp.first_tile = m.first_tile;
+	fp.run_tiles = m.run_tiles;
+	fp.stride_tiles = m.stride_tiles;
 	fp.n_pix = c->n_tiles * kTileSize;
 	fp.pix_bits = pix_bits_of(c); fp.pix_mask = (1u << fp.pix_bits) - 1u;
 	fp.acc_base = acc_base;
@@ -690,6 +694,23 @@ int flush_deferred(mirt_ctx* c) {
 	return launch_batch(c, n);
 }
 
+// The two preambles of an entry point.  The order of their steps is what keeps deferral invisible, so it is stated here and nowhere else.
+// An entry point that observes results, or changes what they are read with: what is deferred is launched, the context's device is the
+// current one, and every stream has finished — the accumulator, the AOV slab and the counters hold every accumulation issued so far.
+int flush_and_wait(mirt_ctx* c) {
+	{ const int fr = flush_deferred(c); if (fr) return fr; }
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, sync_all(c));
+	return MIRT_OK;
+}
+// An entry point that zeroes or overwrites the accumulator: what is deferred is dropped instead (it would be wiped anyway), then as above.
+int drop_and_wait(mirt_ctx* c) {
+	c->deferred = 0;
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, sync_all(c));
+	return MIRT_OK;
+}
+
 // ---- mirt_set_scene, step by step --------------------------------------------------------------
 struct SceneArgs {
 	const mirt_sphere *geometry, *bvh_prims; uint32_t n_spheres;
@@ -920,13 +941,7 @@ int mirt_destroy(mirt_ctx* c) {
 	(void)hipSetDevice(c->device);
 	(void)sync_all(c);
 	harvest(c);
-	for (PipeSlot& sl : c->slots) {
-		sl.arena.release(); sl.counts.release(); sl.contrib.release(); sl.fat.release();
-		if (sl.batch_done) (void)hipEventDestroy(sl.batch_done);
-		if (sl.merged) (void)hipEventDestroy(sl.merged);
-		if (sl.aov_done) (void)hipEventDestroy(sl.aov_done);
-		if (sl.stream) (void)hipStreamDestroy(sl.stream);
-	}
+	for (PipeSlot& sl : c->slots) sl.release();
 	c->slots.clear();
 	for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
 	DeviceBuffer* bufs[] = { &c->recs, &c->recs_wide, &c->spheres, &c->prim_mat, &c->light_sphere, &c->light_emit, &c->mat_albedo, &c->mat_emission,
@@ -1017,9 +1032,7 @@ int mirt_set_policy(mirt_ctx* c, const mirt_policy* p) {
 	if (p->max_bounces < 1 || p->max_bounces > 1024) return fail(c, MIRT_ERR_ARG, "max_bounces %u out of range", p->max_bounces);
 	if (p->buckets < 1 || p->buckets > MIRT_MAX_BUCKETS) return fail(c, MIRT_ERR_ARG, "buckets %u out of range 1..%u", p->buckets, MIRT_MAX_BUCKETS);
 	if (p->brdf > 1) return fail(c, MIRT_ERR_ARG, "brdf %u is neither 0 (Lambertian) nor 1 (GGX)", p->brdf);
-	{ const int fr = flush_deferred(c); if (fr) return fr; }
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }
 	const bool realloc_acc = p->buckets != c->policy.buckets;
 	// batch size / batches in flight are planned again only when something the plan depends on changes (a toggle like trace_primary_rays
 	// leaves the ray-stream arena, tens of GB, where it is)
@@ -1066,13 +1079,11 @@ int mirt_get_policy(const mirt_ctx* c, mirt_policy* p) {
 int mirt_resize(mirt_ctx* c, uint32_t width, uint32_t height) {
 	if (!c) return MIRT_ERR_ARG;
 	if (width > 65536 || height > 65536) return fail(c, MIRT_ERR_ARG, "size %ux%u too large", width, height);
-	c->deferred = 0;                                                                   // the accumulator is about to be zeroed (Renderer.hpp:61-62)
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));
+	{ const int dr = drop_and_wait(c); if (dr) return dr; }                         // the accumulator is about to be zeroed (Renderer.hpp:61-62)
 	c->width = width; c->height = height;
 	c->cand_valid = false;                                                             // other pixels
 	c->h_tiles = width / MIRT_TILE_ROOT; c->v_tiles = height / MIRT_TILE_ROOT;          // Renderer.hpp:59-60
-	c->first_tile = 0; c->n_tiles = c->h_tiles * c->v_tiles; c->run_tiles = 0; c->stride_tiles = 0;
+	set_tile_map(c, TileMap::of_range(0u, c->h_tiles, width), c->h_tiles * c->v_tiles);
 	HIP_TRY(c, c->framebuffer.ensure(std::max<size_t>(static_cast<size_t>(width) * height, 1) * sizeof(float4)));
 	HIP_TRY(c, hipMemsetAsync(c->framebuffer.ptr, 0, c->framebuffer.bytes, c->stream));
 	if (c->frame_host_bytes < c->framebuffer.bytes) {
@@ -1088,10 +1099,8 @@ int mirt_set_tile_range(mirt_ctx* c, uint32_t first_tile, uint32_t n_tiles) {
 	if (!c) return MIRT_ERR_ARG;
 	const uint64_t all = static_cast<uint64_t>(c->h_tiles) * c->v_tiles;
 	if (static_cast<uint64_t>(first_tile) + n_tiles > all) return fail(c, MIRT_ERR_ARG, "tile range [%u,+%u) exceeds %llu tiles", first_tile, n_tiles, (unsigned long long)all);
-	c->deferred = 0;                                                                   // zeroes the accumulator
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));
-	c->first_tile = first_tile; c->n_tiles = n_tiles; c->run_tiles = 0; c->stride_tiles = 0;
+	{ const int dr = drop_and_wait(c); if (dr) return dr; }                         // zeroes the accumulator
+	set_tile_map(c, TileMap::of_range(first_tile, c->h_tiles, c->width), n_tiles);
 	c->cand_valid = false;                                                             // other local pixels
 	return alloc_accumulator(c);
 }
@@ -1099,12 +1108,8 @@ int mirt_set_tile_range(mirt_ctx* c, uint32_t first_tile, uint32_t n_tiles) {
 int mirt_set_tile_rows(mirt_ctx* c, uint32_t first_row, uint32_t row_stride) {
 	if (!c) return MIRT_ERR_ARG;
 	if (row_stride == 0) return fail(c, MIRT_ERR_ARG, "row_stride must be at least 1");
-	c->deferred = 0;                                                                   // zeroes the accumulator
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));
-	const uint32_t rows = first_row < c->v_tiles ? (c->v_tiles - first_row + row_stride - 1) / row_stride : 0u;
-	c->first_tile = first_row * c->h_tiles; c->n_tiles = rows * c->h_tiles;
-	c->run_tiles = c->h_tiles; c->stride_tiles = row_stride > 1 ? row_stride * c->h_tiles : 0u;
+	{ const int dr = drop_and_wait(c); if (dr) return dr; }                         // zeroes the accumulator
+	set_tile_map(c, TileMap::of_rows(first_row, row_stride, c->h_tiles, c->width), TileMap::tile_rows_owned(c->v_tiles, first_row, row_stride) * c->h_tiles);
 	c->cand_valid = false;                                                             // other local pixels
 	return alloc_accumulator(c);
 }
@@ -1135,10 +1140,7 @@ int mirt_accumulate_async(mirt_ctx* c, uint32_t n_calls) {
 }
 int mirt_synchronize(mirt_ctx* c) {
 	if (!c) return MIRT_ERR_ARG;
-	{ const int fr = flush_deferred(c); if (fr) return fr; }
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));
-	return MIRT_OK;
+	return flush_and_wait(c);
 }
 int mirt_accumulate(mirt_ctx* c, uint32_t n_calls) {
 	int r = mirt_accumulate_async(c, n_calls);
@@ -1155,27 +1157,21 @@ int mirt_accumulator_floats(const mirt_ctx* c, size_t* n) {
 int mirt_read_accumulator(mirt_ctx* c, float* dst) {
 	if (!c || !dst) return MIRT_ERR_ARG;
 	size_t n = 0; mirt_accumulator_floats(c, &n);
-	{ const int fr = flush_deferred(c); if (fr) return fr; }
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }
 	if (n) HIP_TRY(c, hipMemcpy(dst, c->accumulator.ptr, n * sizeof(float), hipMemcpyDeviceToHost));
 	return MIRT_OK;
 }
 int mirt_accumulator_device(mirt_ctx* c, void** ptr, size_t* bytes) {
 	if (!c || !ptr || !bytes) return MIRT_ERR_ARG;
 	size_t n = 0; mirt_accumulator_floats(c, &n);
-	{ const int fr = flush_deferred(c); if (fr) return fr; }
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));                                                           // the caller reads the slab on a stream of its own (RCCL gather): everything enqueued here has landed
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }                        // the caller reads the slab on a stream of its own (RCCL gather): everything enqueued here has landed
 	*ptr = c->accumulator.ptr; *bytes = n * sizeof(float);
 	return MIRT_OK;
 }
 int mirt_load_accumulator(mirt_ctx* c, const float* src, int src_is_device, uint32_t accumulations) {
 	if (!c || !src) return MIRT_ERR_ARG;
 	size_t n = 0; mirt_accumulator_floats(c, &n);
-	c->deferred = 0;                                                                   // overwritten below
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));
+	{ const int dr = drop_and_wait(c); if (dr) return dr; }                         // overwritten below
 	if (n && src != c->accumulator.ptr)                                                // src == the slab itself (filled in place by mirt_group_gather): only `accumulations` changes
 		HIP_TRY(c, hipMemcpy(c->accumulator.ptr, src, n * sizeof(float), src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
 	c->accumulations = accumulations;
@@ -1198,9 +1194,7 @@ int mirt_set_aov(mirt_ctx* c, uint32_t on) {
 		if (r) { c->aov_on = 0; c->aov.release(); }
 		return r;
 	}
-	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations were issued with AOVs on
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }                        // deferred accumulations were issued with AOVs on
 	c->aov_on = 0;
 	c->aov.release();
 	return MIRT_OK;
@@ -1210,27 +1204,21 @@ int mirt_aov_floats(const mirt_ctx* c, size_t* n) { if (!c || !n) return MIRT_ER
 int mirt_read_aov(mirt_ctx* c, float* dst) {
 	if (!c || !dst) return MIRT_ERR_ARG;
 	if (!c->aov_on) return fail(c, MIRT_ERR_STATE, "AOVs are off (mirt_set_aov)");
-	{ const int fr = flush_deferred(c); if (fr) return fr; }
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }
 	if (aov_floats(c)) HIP_TRY(c, hipMemcpy(dst, c->aov.ptr, aov_floats(c) * sizeof(float), hipMemcpyDeviceToHost));
 	return MIRT_OK;
 }
 int mirt_aov_device(mirt_ctx* c, void** ptr, size_t* bytes) {
 	if (!c || !ptr || !bytes) return MIRT_ERR_ARG;
 	if (!c->aov_on) return fail(c, MIRT_ERR_STATE, "AOVs are off (mirt_set_aov)");
-	{ const int fr = flush_deferred(c); if (fr) return fr; }
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }
 	*ptr = c->aov.ptr; *bytes = aov_floats(c) * sizeof(float);
 	return MIRT_OK;
 }
 int mirt_load_aov(mirt_ctx* c, const float* src, int src_is_device) {
 	if (!c || !src) return MIRT_ERR_ARG;
 	if (!c->aov_on) return fail(c, MIRT_ERR_STATE, "AOVs are off (mirt_set_aov)");
-	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // (their sums are overwritten below; their accumulator adds are not)
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }                        // (their sums are overwritten below; their accumulator adds are not)
 	if (aov_floats(c) && src != c->aov.ptr)                                         // src == the slab itself (filled in place by mirt_group_gather)
 		HIP_TRY(c, hipMemcpy(c->aov.ptr, src, aov_floats(c) * sizeof(float), src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
 	return MIRT_OK;
@@ -1241,29 +1229,20 @@ int mirt_render_aov(mirt_ctx* c, int which, float* out) {
 	if (which != MIRT_AOV_DEPTH && which != MIRT_AOV_NORMAL && which != MIRT_AOV_ALBEDO) return fail(c, MIRT_ERR_ARG, "no AOV %d (MIRT_AOV_DEPTH, _NORMAL, _ALBEDO)", which);
 	if (!out) return fail(c, MIRT_ERR_ARG, "out is NULL");
 	if (c->accumulations + c->deferred == 0) return MIRT_NOT_READY;
-	{ const int fr = flush_deferred(c); if (fr) return fr; }
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }
 	const uint32_t n_pix = c->n_tiles * kTileSize, ch = which == MIRT_AOV_DEPTH ? 1u : 3u;
 	if (n_pix == 0) return MIRT_OK;
 	const size_t image_floats = static_cast<size_t>(c->width) * c->height * ch;
 	ScopedBuffer image;
 	HIP_TRY(c, image.ensure(image_floats * sizeof(float)));
 	{ Bracket t(c, MIRT_K_RESOLVE);
-	  hipLaunchKernelGGL(k_resolve_aov, dim3(grid_for(c, n_pix)), dim3(kBlock), 0, c->stream, c->aov.as<float>(), image.as<float>(), n_pix, c->first_tile,
-	                     c->run_tiles ? c->run_tiles : 1u, c->stride_tiles, c->h_tiles, c->width, which, static_cast<float>(c->accumulations)); }
+	  hipLaunchKernelGGL(k_resolve_aov, dim3(grid_for(c, n_pix)), dim3(kBlock), 0, c->stream, c->aov.as<float>(), image.as<float>(), n_pix, tile_map(c), which,
+	                     static_cast<float>(c->accumulations)); }
 	HIP_TRY(c, hipGetLastError());
 	std::vector<float> host(image_floats);                                           // pixels of other contexts' tiles are never written: copy ours only
 	HIP_TRY(c, hipMemcpyAsync(host.data(), image.ptr, image_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
-	for (uint32_t local = 0; local < c->n_tiles; local++) {
-		const uint32_t t = c->stride_tiles ? c->first_tile + (local / c->run_tiles) * c->stride_tiles + local % c->run_tiles : c->first_tile + local;
-		const uint32_t x0 = MIRT_TILE_ROOT * (t % c->h_tiles), y0 = MIRT_TILE_ROOT * (t / c->h_tiles);
-		for (uint32_t row = 0; row < MIRT_TILE_ROOT; row++) {
-			const size_t off = (static_cast<size_t>(y0 + row) * c->width + x0) * ch;
-			std::memcpy(out + off, host.data() + off, MIRT_TILE_ROOT * ch * sizeof(float));
-		}
-	}
+	copy_owned_tiles(tile_map(c), c->n_tiles, ch, host.data(), out);
 	return MIRT_OK;
 }
 
@@ -1273,28 +1252,19 @@ int mirt_render(mirt_ctx* c, float* rgba_host) {
 	const uint32_t k = c->policy.buckets;
 	const uint32_t issued = c->accumulations + c->deferred;
 	if (issued == 0 || (issued % k) != 0) return MIRT_NOT_READY;                                    // Renderer.hpp:437 (nothing is launched for this)
-	{ const int fr = flush_deferred(c); if (fr) return fr; }
-	HIP_TRY(c, hipSetDevice(c->device));
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }
 	const float scale = c->camera.exposure / static_cast<float>(c->accumulations / k);              // Renderer.hpp:439
 	const uint32_t n_pix = c->n_tiles * kTileSize;
-	HIP_TRY(c, sync_all(c));
 	{ Bracket t(c, MIRT_K_RESOLVE);
 	  hipLaunchKernelGGL(k_resolve, dim3(grid_for(c, n_pix)), dim3(kBlock), 0, c->stream, c->accumulator.as<float>(), c->framebuffer.as<float4>(),
-	                     n_pix, c->first_tile, c->run_tiles ? c->run_tiles : 1u, c->stride_tiles, c->h_tiles, c->width, k, scale); }
+	                     n_pix, tile_map(c), k, scale); }
 	HIP_TRY(c, hipGetLastError());
 	const size_t frame_floats = static_cast<size_t>(c->width) * c->height * 4;
 	const bool whole = c->n_tiles == c->h_tiles * c->v_tiles && c->width == c->h_tiles * MIRT_TILE_ROOT && c->height == c->v_tiles * MIRT_TILE_ROOT;
 	HIP_TRY(c, hipMemcpyAsync(c->frame_host, c->framebuffer.ptr, frame_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	if (whole) std::memcpy(rgba_host, c->frame_host, frame_floats * sizeof(float));   // every pixel is this context's
-	else for (uint32_t local = 0; local < c->n_tiles; local++) {                                    // only this context's tiles
-		const uint32_t t = c->stride_tiles ? c->first_tile + (local / c->run_tiles) * c->stride_tiles + local % c->run_tiles : c->first_tile + local;
-		const uint32_t x0 = MIRT_TILE_ROOT * (t % c->h_tiles), y0 = MIRT_TILE_ROOT * (t / c->h_tiles);
-		for (uint32_t row = 0; row < MIRT_TILE_ROOT; row++) {
-			const size_t off = (static_cast<size_t>(y0 + row) * c->width + x0) * 4;
-			std::memcpy(rgba_host + off, c->frame_host + off, MIRT_TILE_ROOT * 4 * sizeof(float));
-		}
-	}
+	else copy_owned_tiles(tile_map(c), c->n_tiles, 4u, c->frame_host, rgba_host);                 // only this context's tiles
 	return MIRT_OK;
 }
 
@@ -1306,15 +1276,14 @@ int mirt_noise(mirt_ctx* c, float floor, float* map_out, float* tile_out, uint32
 	if ((r = mirt_noise_host::check_noise_args(floor, k, why, sizeof why))) return fail(c, r, "%s", why);
 	const uint32_t issued = c->accumulations + c->deferred;
 	if (issued == 0 || (issued % k) != 0) return MIRT_NOT_READY;                                    // as mirt_render
-	{ const int fr = flush_deferred(c); if (fr) return fr; }
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }
 	std::vector<float> rec(static_cast<size_t>(c->n_tiles) * 4);
 	std::vector<uint32_t> hist(MIRT_NOISE_BINS, 0u);
 	if (c->n_tiles) {
 		static_assert(kNoiseBins == MIRT_NOISE_BINS, "k_noise bins by the rule of mirt.h");
 		static_assert(MIRT_MAX_BUCKETS <= kNoiseMaxBuckets, "k_noise keeps one bucket luminance per register: every bucket mirt_set_policy accepts must fit");
 		const float scale = c->camera.exposure / static_cast<float>(c->accumulations / k);          // Renderer.hpp:439, as mirt_render
+		const TileMap m = tile_map(c);
 		const size_t image_floats = static_cast<size_t>(c->width) * c->height;
 		ScopedBuffer image;
 		if (map_out) HIP_TRY(c, image.ensure(image_floats * sizeof(float)));
@@ -1323,14 +1292,13 @@ int mirt_noise(mirt_ctx* c, float floor, float* map_out, float* tile_out, uint32
 		HIP_TRY(c, hipMemsetAsync(c->noise_hist.ptr, 0, MIRT_NOISE_BINS * sizeof(uint32_t), c->stream));
 		{ Bracket t(c, MIRT_K_RESOLVE);
 		  hipLaunchKernelGGL(k_noise, dim3(c->n_tiles), dim3(kTileSize), 0, c->stream, c->accumulator.as<float>(), map_out ? image.as<float>() : nullptr, c->noise_rec.as<float4>(),
-		                     c->noise_hist.as<uint32_t>(), c->first_tile, c->run_tiles ? c->run_tiles : 1u, c->stride_tiles, c->h_tiles, c->width, k, scale, floor); }
+		                     c->noise_hist.as<uint32_t>(), m, k, scale, floor); }
 		HIP_TRY(c, hipGetLastError());
 		std::vector<float> host(map_out ? image_floats : 0);                             // pixels of other contexts' tiles are never written: copy ours only
-		auto global_of = [&](uint32_t local) { return c->stride_tiles ? c->first_tile + (local / c->run_tiles) * c->stride_tiles + local % c->run_tiles : c->first_tile + local; };
 		if (map_out) {                                                                   // only the 16-row bands that hold a tile of ours come back (one n-th of the image for a group member)
 			uint32_t band = UINT32_MAX;
 			for (uint32_t local = 0; local < c->n_tiles; local++) {                       // LaunchIndices ascend with the local index: each band is met once
-				const uint32_t b = global_of(local) / c->h_tiles;
+				const uint32_t b = m.global_tile(local) / m.h_tiles;
 				if (b == band) continue;
 				band = b;
 				const size_t off = static_cast<size_t>(b) * MIRT_TILE_ROOT * c->width;
@@ -1340,14 +1308,7 @@ int mirt_noise(mirt_ctx* c, float floor, float* map_out, float* tile_out, uint32
 		HIP_TRY(c, hipMemcpyAsync(rec.data(), c->noise_rec.ptr, rec.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(c, hipMemcpyAsync(hist.data(), c->noise_hist.ptr, MIRT_NOISE_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(c, hipStreamSynchronize(c->stream));
-		if (map_out) for (uint32_t local = 0; local < c->n_tiles; local++) {
-			const uint32_t t = global_of(local);
-			const uint32_t x0 = MIRT_TILE_ROOT * (t % c->h_tiles), y0 = MIRT_TILE_ROOT * (t / c->h_tiles);
-			for (uint32_t row = 0; row < MIRT_TILE_ROOT; row++) {
-				const size_t off = static_cast<size_t>(y0 + row) * c->width + x0;
-				std::memcpy(map_out + off, host.data() + off, MIRT_TILE_ROOT * sizeof(float));
-			}
-		}
+		if (map_out) copy_owned_tiles(m, c->n_tiles, 1u, host.data(), map_out);
 	}
 	if (tile_out && !rec.empty()) std::memcpy(tile_out, rec.data(), rec.size() * sizeof(float));
 	if (hist_out) std::memcpy(hist_out, hist.data(), MIRT_NOISE_BINS * sizeof(uint32_t));
@@ -1371,9 +1332,7 @@ int mirt_accumulate_until(mirt_ctx* c, const mirt_stop_rule* rule, mirt_noise_st
 
 int mirt_get_counters(mirt_ctx* c, mirt_counters* out) {
 	if (!c || !out) return MIRT_ERR_ARG;
-	{ const int fr = flush_deferred(c); if (fr) return fr; }
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, sync_all(c));
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }
 	DevCounters d;
 	HIP_TRY(c, hipMemcpy(&d, c->counters.ptr, sizeof d, hipMemcpyDeviceToHost));
 	out->rays = d.rays; out->shadow_rays = d.shadow_rays; out->nodes = d.nodes; out->spheres = d.spheres;

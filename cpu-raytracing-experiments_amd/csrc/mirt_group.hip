@@ -14,6 +14,7 @@
 // Everything else here goes through the public C-ABI of the contexts.
 #include "../../include/mirt.h"
 #include "noise_host.hpp"
+#include "tile_map.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -97,8 +98,13 @@ int gfail(mirt_group* g, int code, const char* fmt, ...) {
 #define FOR_MEMBERS(g, what, call) do { for (size_t _i = 0; _i < (g)->members.size(); _i++) { mirt_ctx* ctx = (g)->members[_i]; const int _rc = (call); \
 	if (_rc < 0) return gfail((g), _rc, "%s on member %zu (device %d): %s", (what), _i, (g)->devices[_i], mirt_last_error(ctx)); } } while (0)
 #define FULL_TRY(g, what, call) do { const int _rc = (call); if (_rc < 0) return gfail((g), _rc, "%s on the gather context: %s", (what), mirt_last_error((g)->full)); } while (0)
+// Runs `call` on every member, then on the gather context if the group has one.
+#define FOR_MEMBERS_AND_FULL(g, what, call) do { FOR_MEMBERS(g, what, call); if ((g)->full) { mirt_ctx* ctx = (g)->full; FULL_TRY(g, what, call); } } while (0)
+// A group of one is its member: `call` on it is the whole entry point, and the member's error text the group's.
+#define RETURN_IF_SINGLE(g, call) do { if ((g)->members.size() == 1) { mirt_ctx* ctx = (g)->members[0]; const int _rc = (call); return _rc < 0 ? gfail((g), _rc, "%s", mirt_last_error(ctx)) : _rc; } } while (0)
 #define GHIP(g, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return gfail((g), MIRT_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); } while (0)
 #define GNCCL(g, expr) do { ncclResult_t _r = (expr); if (_r != ncclSuccess) return gfail((g), MIRT_ERR_HIP, "%s: %s", #expr, g_rccl.GetErrorString(_r)); } while (0)
+uint32_t accumulations_of(const mirt_group* g) { uint32_t acc = 0; (void)mirt_get_accumulations(g->members[0], &acc); return acc; }   // every member holds the same count
 
 } // namespace
 
@@ -165,26 +171,22 @@ int mirt_group_set_scene(mirt_group* g, const mirt_sphere* geometry, const mirt_
 }
 int mirt_group_set_camera(mirt_group* g, const float pos[3], const float orient_xyzw[4], float half_width, float half_height, float z, float exposure) {
 	if (!g) return MIRT_ERR_ARG;
-	FOR_MEMBERS(g, "mirt_set_camera", mirt_set_camera(ctx, pos, orient_xyzw, half_width, half_height, z, exposure));
-	if (g->full) FULL_TRY(g, "mirt_set_camera", mirt_set_camera(g->full, pos, orient_xyzw, half_width, half_height, z, exposure));
+	FOR_MEMBERS_AND_FULL(g, "mirt_set_camera", mirt_set_camera(ctx, pos, orient_xyzw, half_width, half_height, z, exposure));
 	return MIRT_OK;
 }
 int mirt_group_set_gloss_decay(mirt_group* g, const float* decay, uint32_t n) {
 	if (!g) return MIRT_ERR_ARG;
-	FOR_MEMBERS(g, "mirt_set_gloss_decay", mirt_set_gloss_decay(ctx, decay, n));
-	if (g->full) FULL_TRY(g, "mirt_set_gloss_decay", mirt_set_gloss_decay(g->full, decay, n));
+	FOR_MEMBERS_AND_FULL(g, "mirt_set_gloss_decay", mirt_set_gloss_decay(ctx, decay, n));
 	return MIRT_OK;
 }
 int mirt_group_set_stream_order(mirt_group* g, uint32_t exact) {
 	if (!g) return MIRT_ERR_ARG;
-	FOR_MEMBERS(g, "mirt_set_stream_order", mirt_set_stream_order(ctx, exact));
-	if (g->full) FULL_TRY(g, "mirt_set_stream_order", mirt_set_stream_order(g->full, exact));
+	FOR_MEMBERS_AND_FULL(g, "mirt_set_stream_order", mirt_set_stream_order(ctx, exact));
 	return MIRT_OK;
 }
 int mirt_group_set_lens(mirt_group* g, float aperture_radius, float focus_depth) {
 	if (!g) return MIRT_ERR_ARG;
-	FOR_MEMBERS(g, "mirt_set_lens", mirt_set_lens(ctx, aperture_radius, focus_depth));
-	if (g->full) FULL_TRY(g, "mirt_set_lens", mirt_set_lens(g->full, aperture_radius, focus_depth));
+	FOR_MEMBERS_AND_FULL(g, "mirt_set_lens", mirt_set_lens(ctx, aperture_radius, focus_depth));
 	return MIRT_OK;
 }
 int mirt_group_pick_focus(mirt_group* g, uint32_t x, uint32_t y, float* distance, float* depth) {
@@ -208,8 +210,7 @@ int mirt_group_set_aov(mirt_group* g, uint32_t on) {
 }
 int mirt_group_set_policy(mirt_group* g, const mirt_policy* p) {
 	if (!g || !p) return MIRT_ERR_ARG;
-	FOR_MEMBERS(g, "mirt_set_policy", mirt_set_policy(ctx, p));
-	if (g->full) FULL_TRY(g, "mirt_set_policy", mirt_set_policy(g->full, p));
+	FOR_MEMBERS_AND_FULL(g, "mirt_set_policy", mirt_set_policy(ctx, p));
 	g->buckets = p->buckets;
 	g->gathered = false;
 	return MIRT_OK;
@@ -343,9 +344,7 @@ int mirt_group_gather(mirt_group* g) {
 	if (t0) (void)hipEventDestroy(t0);
 	if (t1) (void)hipEventDestroy(t1);
 	if (rc != MIRT_OK) return rc;
-	uint32_t acc = 0;
-	(void)mirt_get_accumulations(g->members[0], &acc);
-	FULL_TRY(g, "mirt_load_accumulator", mirt_load_accumulator(g->full, static_cast<const float*>(parts[0].full_ptr), 1, acc));   // in place: only `accumulations` changes
+	FULL_TRY(g, "mirt_load_accumulator", mirt_load_accumulator(g->full, static_cast<const float*>(parts[0].full_ptr), 1, accumulations_of(g)));   // in place: only `accumulations` changes
 	g->gathered = true;
 	return MIRT_OK;
 }
@@ -354,7 +353,7 @@ int mirt_group_gather(mirt_group* g) {
 int mirt_group_noise(mirt_group* g, float floor, float* map_out, float* tile_out, uint32_t* hist_out, mirt_noise_stats* stats) {
 	if (!g) return MIRT_ERR_ARG;
 	const uint32_t n = static_cast<uint32_t>(g->members.size());
-	if (n == 1) { const int rc = mirt_noise(g->members[0], floor, map_out, tile_out, hist_out, stats); return rc < 0 ? gfail(g, rc, "%s", mirt_last_error(g->members[0])) : rc; }
+	RETURN_IF_SINGLE(g, mirt_noise(ctx, floor, map_out, tile_out, hist_out, stats));
 	char why[256];
 	if (const int bad = mirt_noise_host::check_noise_args(floor, g->buckets, why, sizeof why)) return gfail(g, bad, "%s", why);
 	if (g->width == 0) return gfail(g, MIRT_ERR_STATE, "mirt_group_resize has not been called");
@@ -365,7 +364,7 @@ int mirt_group_noise(mirt_group* g, float floor, float* map_out, float* tile_out
 	std::vector<float> rec(static_cast<size_t>(h_tiles) * v_tiles * 4, 0.0f), part;
 	std::vector<uint32_t> hist(MIRT_NOISE_BINS, 0u), part_hist(MIRT_NOISE_BINS);
 	for (uint32_t i = 0; i < n; i++) {
-		const uint32_t rows = i < v_tiles ? (v_tiles - i + n - 1) / n : 0u;                // member i renders tile rows i, i + n, ... (mirt_group_resize)
+		const uint32_t rows = mirt::TileMap::tile_rows_owned(v_tiles, i, n);               // member i renders tile rows i, i + n, ... (mirt_group_resize)
 		part.assign(static_cast<size_t>(rows) * h_tiles * 4, 0.0f);
 		const int rc = mirt_noise(g->members[i], floor, map_out, part.data(), part_hist.data(), nullptr);   // writes its own tiles of map_out
 		if (rc != MIRT_OK) return gfail(g, rc < 0 ? rc : MIRT_ERR_STATE, "mirt_noise on member %u (device %d): %s", i, g->devices[i], rc < 0 ? mirt_last_error(g->members[i]) : "not ready");
@@ -380,7 +379,7 @@ int mirt_group_noise(mirt_group* g, float floor, float* map_out, float* tile_out
 }
 int mirt_group_accumulate_until(mirt_group* g, const mirt_stop_rule* rule, mirt_noise_stats* last, uint32_t* issued) {
 	if (!g) return MIRT_ERR_ARG;
-	if (g->members.size() == 1) { const int rc = mirt_accumulate_until(g->members[0], rule, last, issued); return rc < 0 ? gfail(g, rc, "%s", mirt_last_error(g->members[0])) : rc; }
+	RETURN_IF_SINGLE(g, mirt_accumulate_until(ctx, rule, last, issued));
 	const uint32_t k = g->buckets;
 	uint32_t acc = 0;
 	{ const int rc = mirt_get_accumulations(g->members[0], &acc); if (rc < 0) return gfail(g, rc, "mirt_get_accumulations on member 0 failed"); }
@@ -436,7 +435,7 @@ int mirt_group_accumulator_floats(const mirt_group* g, size_t* n) {
 }
 int mirt_group_read_accumulator(mirt_group* g, float* host_dst) {
 	if (!g || !host_dst) return MIRT_ERR_ARG;
-	if (g->members.size() == 1) { const int rc = mirt_read_accumulator(g->members[0], host_dst); return rc < 0 ? gfail(g, rc, "%s", mirt_last_error(g->members[0])) : rc; }
+	RETURN_IF_SINGLE(g, mirt_read_accumulator(ctx, host_dst));
 	const int rc = mirt_group_gather(g);
 	if (rc) return rc;
 	FULL_TRY(g, "mirt_read_accumulator", mirt_read_accumulator(g->full, host_dst));
@@ -449,7 +448,7 @@ int mirt_group_aov_floats(const mirt_group* g, size_t* n) {
 }
 int mirt_group_read_aov(mirt_group* g, float* host_dst) {
 	if (!g || !host_dst) return MIRT_ERR_ARG;
-	if (g->members.size() == 1) { const int rc = mirt_read_aov(g->members[0], host_dst); return rc < 0 ? gfail(g, rc, "%s", mirt_last_error(g->members[0])) : rc; }
+	RETURN_IF_SINGLE(g, mirt_read_aov(ctx, host_dst));
 	if (!g->aov) return gfail(g, MIRT_ERR_STATE, "AOVs are off (mirt_group_set_aov)");
 	const int rc = mirt_group_gather(g);
 	if (rc) return rc;
@@ -458,12 +457,10 @@ int mirt_group_read_aov(mirt_group* g, float* host_dst) {
 }
 int mirt_group_render_aov(mirt_group* g, int which, float* out) {
 	if (!g) return MIRT_ERR_ARG;
-	if (g->members.size() == 1) { const int rc = mirt_render_aov(g->members[0], which, out); return rc < 0 ? gfail(g, rc, "%s", mirt_last_error(g->members[0])) : rc; }
+	RETURN_IF_SINGLE(g, mirt_render_aov(ctx, which, out));
 	if (!g->aov) return gfail(g, MIRT_ERR_STATE, "AOVs are off (mirt_group_set_aov)");
 	if (!out) return gfail(g, MIRT_ERR_ARG, "out is NULL");
-	uint32_t acc = 0;
-	(void)mirt_get_accumulations(g->members[0], &acc);
-	if (acc == 0) return MIRT_NOT_READY;                                                   // nothing is gathered for it
+	if (accumulations_of(g) == 0) return MIRT_NOT_READY;                                             // nothing is gathered for it
 	const int rc = mirt_group_gather(g);
 	if (rc) return rc;
 	const int rr = mirt_render_aov(g->full, which, out);
@@ -471,10 +468,9 @@ int mirt_group_render_aov(mirt_group* g, int which, float* out) {
 }
 int mirt_group_render(mirt_group* g, float* rgba_host) {
 	if (!g || !rgba_host) return MIRT_ERR_ARG;
-	if (g->members.size() == 1) { const int rc = mirt_render(g->members[0], rgba_host); return rc < 0 ? gfail(g, rc, "%s", mirt_last_error(g->members[0])) : rc; }
-	uint32_t acc = 0;
-	(void)mirt_get_accumulations(g->members[0], &acc);
-	if (acc == 0 || acc % g->buckets != 0) return MIRT_NOT_READY;                          // Renderer.hpp:437: nothing is gathered for a frame that is not due
+	RETURN_IF_SINGLE(g, mirt_render(ctx, rgba_host));
+	const uint32_t acc = accumulations_of(g);
+	if (acc == 0 || acc % g->buckets != 0) return MIRT_NOT_READY;       // Renderer.hpp:437: nothing is gathered for a frame that is not due
 	const int rc = mirt_group_gather(g);
 	if (rc) return rc;
 	const int rr = mirt_render(g->full, rgba_host);
