@@ -69,6 +69,12 @@ class StopRule(C.Structure):
     _fields_ = [("target", C.c_float), ("quantile", C.c_float), ("floor", C.c_float), ("check_every", C.c_uint32), ("max_accumulations", C.c_uint32)]
 
 
+class AdaptiveReport(C.Structure):
+    """mirt_adaptive_report"""
+    _fields_ = [("issued", C.c_uint32), ("checks", C.c_uint32), ("frozen_tiles", C.c_uint32), ("owned_tiles", C.c_uint32), ("tile_accumulations", C.c_uint64),
+                ("last", NoiseStats)]
+
+
 def build(force: bool = False) -> str:
     """Compile csrc/ for gfx950 with hipcc (cross-compiles without a GPU)."""
     args = ["make", "-C", CSRC]
@@ -124,6 +130,13 @@ def load_library():
         "mirt_noise": [P, f, vp, vp, vp, C.POINTER(NoiseStats)],
         "mirt_noise_quantile": [vp, C.c_double, C.POINTER(f)],
         "mirt_accumulate_until": [P, C.POINTER(StopRule), C.POINTER(NoiseStats), C.POINTER(u32)],
+        "mirt_freeze_tiles": [P, vp, C.c_size_t],
+        "mirt_tile_counts": [P, vp, C.c_size_t],
+        "mirt_frozen_tiles": [P, vp, C.c_size_t],
+        "mirt_load_tile_counts": [P, vp, C.c_size_t],
+        "mirt_tile_above": [P, f, f, vp, C.c_size_t],
+        "mirt_adaptive_select": [vp, vp, vp, C.c_size_t, C.c_double, vp],
+        "mirt_accumulate_adaptive": [P, C.POINTER(StopRule), u32, C.POINTER(AdaptiveReport)],
         "mirt_get_counters": [P, C.POINTER(Counters)],
         "mirt_get_kernel_times": [P, C.POINTER(KernelTimes), i32],
         "mirt_get_stream": [P, C.POINTER(vp)],
@@ -168,6 +181,11 @@ def load_library():
         "mirt_group_render_aov": [G, i32, vp],
         "mirt_group_noise": [G, f, vp, vp, vp, C.POINTER(NoiseStats)],
         "mirt_group_accumulate_until": [G, C.POINTER(StopRule), C.POINTER(NoiseStats), C.POINTER(u32)],
+        "mirt_group_freeze_tiles": [G, vp, C.c_size_t],
+        "mirt_group_tile_counts": [G, vp, C.c_size_t],
+        "mirt_group_frozen_tiles": [G, vp, C.c_size_t],
+        "mirt_group_tile_above": [G, f, f, vp, C.c_size_t],
+        "mirt_group_accumulate_adaptive": [G, C.POINTER(StopRule), u32, C.POINTER(AdaptiveReport)],
         "mirt_group_rccl_selftest": [i32, C.c_size_t],
     })
     for name, argtypes in sigs.items():
@@ -243,6 +261,22 @@ def noise_quantile(hist, q: float):
     if rc < 0:
         raise MirtError(f"mirt_noise_quantile failed ({rc}): q = {q} is not in (0, 1]")
     return v.value if rc == MIRT_OK else None
+
+
+def adaptive_select(tiles, above, frozen=None, quantile: float = 0.95) -> np.ndarray:
+    """mirt_adaptive_select (host code, no GPU): from noise()["tiles"] and noise_above() the mask of tiles to freeze — a tile not yet frozen
+    freezes when it has no non-finite pixel and above <= floor((1 - quantile) * usable); tiles already in `frozen` are passed through as 1."""
+    lib = load_library()
+    t = np.ascontiguousarray(tiles, dtype=np.float32).reshape(-1, 4)
+    a = np.ascontiguousarray(above, dtype=np.uint32).reshape(-1)
+    fr = None if frozen is None else np.ascontiguousarray(np.asarray(frozen) != 0, dtype=np.uint8).reshape(-1)
+    if len(a) != len(t) or (fr is not None and len(fr) != len(t)):
+        raise ValueError("tiles, above and frozen must describe the same tiles")
+    out = np.zeros(len(t), dtype=np.uint8)
+    rc = lib.mirt_adaptive_select(_ptr(t), _ptr(a), _ptr(fr) if fr is not None else None, len(t), float(quantile), _ptr(out))
+    if rc < 0:
+        raise MirtError(f"mirt_adaptive_select failed ({rc}): quantile = {quantile} is not in (0, 1]")
+    return out
 
 
 class _Binding:
@@ -444,6 +478,45 @@ class _Binding:
         rc = self._call("accumulate_until", C.byref(rule), C.byref(st), C.byref(issued))
         return {"converged": rc == MIRT_OK, "issued": issued.value, **st.as_dict()}
 
+    # -- per-tile adaptive sampling (mirt.h "per-tile adaptive sampling") ----------------------------------------
+    adaptive_select = staticmethod(adaptive_select)
+
+    def freeze_tiles(self, mask):
+        """Tiles (local order; a group: LaunchIndex order over the image) whose mask entry is non-zero take no more samples until the accumulator is reset or reloaded; there is no
+        un-freeze.  Needs accumulations > 0 and a multiple of `buckets`."""
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1)
+        self._call("freeze_tiles", _ptr(m) if len(m) else None, len(m))
+
+    def frozen_tiles(self) -> np.ndarray:
+        """1 for every frozen tile (a tile frozen at the current count has the count of an active one)."""
+        out = np.zeros(self._tiles(), dtype=np.uint8)
+        self._call("frozen_tiles", _ptr(out), len(out))
+        return out
+
+    def tile_counts(self) -> np.ndarray:
+        """Samples per pixel of every local tile: `accumulations` for an active tile, the count it froze at for a frozen one."""
+        out = np.zeros(self._tiles(), dtype=np.uint32)
+        self._call("tile_counts", _ptr(out), len(out))
+        return out
+
+    def noise_above(self, target: float, floor: float = 0.0):
+        """Per local tile, the usable pixels whose noise e exceeds `target` (mirt_tile_above); None while noise() would be."""
+        out = np.zeros(self._tiles(), dtype=np.uint32)
+        rc = self._call("tile_above", float(np.float32(floor)), float(np.float32(target)), _ptr(out), len(out))
+        return out if rc == MIRT_OK else None
+
+    def accumulate_adaptive(self, target: float, quantile: float = 0.95, floor: float = 0.0, check_every: int = None, min_accumulations: int = 0,
+                            max_accumulations: int = 1000):
+        """Accumulate `check_every` (default 4 x buckets) at a time; after each step, once `min_accumulations` is reached, freeze the tiles
+        whose `quantile` of the per-pixel noise is <= target (adaptive_select).  Ends when every tile is frozen or at `max_accumulations`
+        (mirt_accumulate_adaptive) -> {"converged", "issued", "checks", "frozen_tiles", "owned_tiles", "tile_accumulations", and the stats of
+        the last check}.  Stopping on an estimate made from the same samples biases dark; `min_accumulations` is the guard."""
+        rule = StopRule(float(target), float(quantile), float(floor), int(check_every if check_every is not None else 4 * self.policy.buckets), int(max_accumulations))
+        rep = AdaptiveReport()
+        rc = self._call("accumulate_adaptive", C.byref(rule), int(min_accumulations), C.byref(rep))
+        return {"converged": rc == MIRT_OK, "issued": int(rep.issued), "checks": int(rep.checks), "frozen_tiles": int(rep.frozen_tiles), "owned_tiles": int(rep.owned_tiles),
+                "tile_accumulations": int(rep.tile_accumulations), **rep.last.as_dict()}
+
     def counters(self) -> dict:
         c = Counters()
         self._call("get_counters", C.byref(c))
@@ -476,6 +549,11 @@ class Renderer(_Binding):
         self._call("set_policy", C.byref(self.policy))
         self._call("debug_allow_half_boxes", int(allow_half_boxes))
         self._configure(gloss_decay, exact_stream_order, aov)
+
+    def load_tile_counts(self, counts):
+        """After load_accumulator: per-tile counts (positive multiples of `buckets`, at most accumulations); tiles below it are frozen."""
+        a = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        self._call("load_tile_counts", _ptr(a) if len(a) else None, len(a))
 
     def get_policy(self) -> dict:
         """The policy in effect (max_batch / streams resolved where they were left at 0 = auto)."""

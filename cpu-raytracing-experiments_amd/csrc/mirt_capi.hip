@@ -67,6 +67,7 @@ struct PipeSlot {
 	hipEvent_t aov_done = nullptr;   // mirt_set_aov(1) only: recorded on `stream` after the batch's k_first_hit_aov (created by the first such batch)
 	bool in_use = false;
 	uint64_t cand_gen = 0;           // the build of the context's candidate lists this slot's stream has waited for (mirt_ctx::cand_gen)
+	uint64_t listed_gen = 0;         // likewise for mirt_ctx::listed_active
 	StreamBuf stream_buf[2]{};
 	ShadowBuf shadow_buf{};
 	HitRec* hit = nullptr;           // RayStream<>::Hit: one 8-B {tfar, primID} record per ray (two planes' worth of the arena)
@@ -124,6 +125,7 @@ struct mirt_ctx {
 	float* frame_host = nullptr;     // pinned staging copy of the framebuffer for mirt_render (pageable memory halves the copy rate)
 	size_t frame_host_bytes = 0;
 	DeviceBuffer counters;           // DevCounters
+	DeviceBuffer noise_above;        // mirt_tile_above: one count per local tile
 	DeviceBuffer noise_rec, noise_hist;   // mirt_noise: one float4 record per local tile, MIRT_NOISE_BINS histogram words (allocated by the first call)
 	std::vector<PipeSlot> slots;     // batches in flight (policy.streams)
 	uint64_t planned_for = 0;        // local pixel count batch_mem_cap was planned for (0 = plan again)
@@ -132,6 +134,19 @@ struct mirt_ctx {
 	uint32_t seg_cap = 0;            // slots per queue segment
 	uint32_t arena_bounces = 0;
 	uint64_t batch_seq = 0;
+
+	// Per-tile adaptive sampling (mirt_freeze_tiles): a frozen tile takes no more samples until the accumulator is zeroed or overwritten.  Frozen
+	// sets only grow, so every active tile's count is `accumulations`; a frozen tile's is the value `accumulations` had when it froze.
+	std::vector<uint8_t> frozen;     // per local tile; empty = none
+	std::vector<uint32_t> frozen_at; // count of a frozen tile
+	uint32_t n_frozen = 0;           // 0: every launch is the one of a context without the feature
+	DeviceBuffer tile_frozen;        // the mask as the sparse kernels read it, one word per local tile
+	DeviceBuffer active_list;        // word 0: local pixels of the active tiles, words 1..: those pixels (k_trace_sparse; k_trace_fat's `listed` count)
+	DeviceBuffer tile_counts;        // per-tile counts for the resolves (uploaded by the call that resolves)
+	DeviceBuffer listed_active;      // word 0: count, words 1..: cand_listed ∩ active tiles (k_listed_active), what k_trace<., kPrimaryList> traces once a tile is frozen
+	hipEvent_t listed_built = nullptr; // recorded on the main stream after the latest k_listed_active; batches on other streams wait for it
+	uint64_t freeze_gen = 0;         // number of mask changes so far
+	uint64_t listed_for_cand = 0, listed_for_freeze = 0, listed_gen = 0;   // the lists' build and the mask listed_active was made from; its own build number
 
 	uint32_t deferred = 0;            // Accumulate() calls accepted by mirt_accumulate_async but not launched yet (fewer than a batch)
 	// launch-shape knobs for measurements (profiles/gpu_cycle.sh A/B runs), read from the environment at mirt_create: MIRT_TUNE_TRACE_WGS /
@@ -370,6 +385,39 @@ int alloc_aov(mirt_ctx* c) {
 	return MIRT_OK;
 }
 
+// No tile is frozen (host state only: the device copies are read while n_frozen != 0 and rewritten by the call that raises it).
+void clear_freezes(mirt_ctx* c) { c->frozen.clear(); c->frozen_at.clear(); c->n_frozen = 0; }
+uint32_t tile_count(const mirt_ctx* c, uint32_t local) { return (c->n_frozen && c->frozen[local]) ? c->frozen_at[local] : c->accumulations; }
+// The mask and the list of active pixels as the sparse kernels read them.  The caller has synchronised every stream.
+int upload_freezes(mirt_ctx* c) {
+	if (c->n_frozen == 0) return MIRT_OK;
+	std::vector<uint32_t> mask(c->n_tiles), list(1);
+	list.reserve(static_cast<size_t>(c->n_tiles - c->n_frozen) * kTileSize + 1);
+	for (uint32_t t = 0; t < c->n_tiles; t++) {
+		mask[t] = c->frozen[t] ? 1u : 0u;
+		if (!c->frozen[t]) for (uint32_t id = 0; id < kTileSize; id++) list.push_back(t * kTileSize + id);
+	}
+	list[0] = static_cast<uint32_t>(list.size() - 1);
+	HIP_TRY(c, c->tile_frozen.ensure(mask.size() * sizeof(uint32_t)));
+	HIP_TRY(c, c->active_list.ensure((static_cast<size_t>(c->n_tiles) * kTileSize + 1) * sizeof(uint32_t)));
+	HIP_TRY(c, hipMemcpy(c->tile_frozen.ptr, mask.data(), mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+	HIP_TRY(c, hipMemcpy(c->active_list.ptr, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+	c->freeze_gen++;
+	return MIRT_OK;
+}
+// The per-tile counts for a resolve kernel: NULL while no tile is frozen (the kernels then do what they have always done).  The caller has
+// synchronised every stream, and the kernel it launches is on the main stream, behind this copy.
+int upload_tile_counts(mirt_ctx* c, const uint32_t** dev) {
+	*dev = nullptr;
+	if (c->n_frozen == 0) return MIRT_OK;
+	std::vector<uint32_t> counts(c->n_tiles);
+	for (uint32_t t = 0; t < c->n_tiles; t++) counts[t] = tile_count(c, t);
+	HIP_TRY(c, c->tile_counts.ensure(counts.size() * sizeof(uint32_t)));
+	HIP_TRY(c, hipMemcpy(c->tile_counts.ptr, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+	*dev = c->tile_counts.as<uint32_t>();
+	return MIRT_OK;
+}
+
 int alloc_accumulator(mirt_ctx* c) {
 	const size_t floats = static_cast<size_t>(c->n_tiles) * c->policy.buckets * 3 * kTileSize;
 	HIP_TRY(c, sync_all(c));
@@ -380,6 +428,7 @@ int alloc_accumulator(mirt_ctx* c) {
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	for (PipeSlot& sl : c->slots) sl.in_use = false;
 	c->accumulations = 0;
+	clear_freezes(c);
 	return MIRT_OK;
 }
 
@@ -481,6 +530,16 @@ const decltype(&k_shade<false, false>) kShadeLens[2] = { k_shade<true, false, tr
 // One wave per pixel for the batches that fill a wave (kernels.hpp kWaveHitsMinBatch); named last, for the same reason.
 const decltype(&k_primary_hits_wave<true>) kPrimaryHitsWave[2] = { k_primary_hits_wave<true>, k_primary_hits_wave<false> };                         // [!count]
 
+// The twins of the bounce-0 kernels and of the merge that skip frozen tiles (mirt_freeze_tiles), launched only once a tile is frozen; named
+// after every table above, for the same reason.
+const decltype(&k_primary_hits_sparse<true>) kPrimaryHitsSparse[2] = { k_primary_hits_sparse<true>, k_primary_hits_sparse<false> };                 // [!count]
+const decltype(&k_primary_hits_wave_sparse<true>) kPrimaryHitsWaveSparse[2] = { k_primary_hits_wave_sparse<true>, k_primary_hits_wave_sparse<false> };   // [!count]
+const decltype(&k_trace_sparse<true, false>) kTraceSparse[2][2] = { { k_trace_sparse<true, false>, k_trace_sparse<true, true> }, { k_trace_sparse<false, false>, k_trace_sparse<false, true> } };   // [!count][lens]
+const decltype(&k_trace_fat<true, kPrimaryNone>) kTraceFatListLens[2] = { k_trace_fat<true, kPrimaryList, true>, k_trace_fat<false, kPrimaryList, true> };   // [!count]
+const decltype(&k_shade_first_sparse<false, false>) kShadeFirstSparse[2][2] = { { k_shade_first_sparse<false, false>, k_shade_first_sparse<false, true> },
+                                                                                { k_shade_first_sparse<true, false>, k_shade_first_sparse<true, true> } };   // [ggx][lens]
+const decltype(&k_first_hit_aov_sparse<false>) kFirstHitAovSparse[2] = { k_first_hit_aov_sparse<false>, k_first_hit_aov_sparse<true> };              // [lens]
+
 // What varies between the launches of the trace stage: a bounce of a batch, or the rays of a debug entry point.
 struct TraceLaunch {
 	StreamBuf in; HitRec* hit;                       // closest-hit rays (no stream with PRIMARY) and their hit records
@@ -499,6 +558,18 @@ void launch_trace(const mirt_ctx* c, hipStream_t st, const SceneDev& sc, const F
 	// a large scene (100 k spheres: ~100 us per ray) wants as many fat rays in flight as there are (a few hundred per launch); k_trace_fat grid-strides
 	const uint32_t fat_grid = sc.n_spheres > 4096 ? static_cast<uint32_t>(c->n_cu) * 2u : 64u;
 	if (sc.use_bvh) hipLaunchKernelGGL(lens ? kTraceFatLens[!count] : kTraceFat[!count][primary], dim3(fat_grid), dim3(1024), 0, st, sc, fp, t.in, t.hit, t.fat_closest, t.sh, t.sink, t.fat_shadow, t.ctr, t.listed_pixels, c->lens);
+}
+
+// The camera rays of a batch that walk the tree (or the brute-force loop) once a tile is frozen: k_trace_sparse over the active pixels' list, then
+// its fat rays through k_trace_fat's kPrimaryList form, whose list and count are that list and its length.
+void launch_trace_sparse(const mirt_ctx* c, hipStream_t st, const SceneDev& sc, const FrameParams& fp, uint32_t active_pix, bool count, const TraceLaunch& t, bool lens) {
+	const uint32_t* list = c->active_list.as<uint32_t>();
+	hipLaunchKernelGGL(kTraceSparse[!count][lens], dim3(trace_grid(c, static_cast<uint64_t>(active_pix) * fp.batch_n)), dim3(kTraceBlock), trace_lds(c), st, sc, fp, list + 1, active_pix, t.hit,
+	                   t.closest_work, t.fat_closest, t.ctr, c->lens);
+	const uint32_t fat_grid = sc.n_spheres > 4096 ? static_cast<uint32_t>(c->n_cu) * 2u : 64u;
+	StreamBuf listed = t.in;
+	listed.path = const_cast<uint32_t*>(list + 1);
+	if (sc.use_bvh) hipLaunchKernelGGL(lens ? kTraceFatListLens[!count] : kTraceFat[!count][kPrimaryList], dim3(fat_grid), dim3(1024), 0, st, sc, fp, listed, t.hit, t.fat_closest, t.sh, t.sink, t.fat_shadow, t.ctr, list, c->lens);
 }
 
 // mirt_set_stream_order(1): a batch is ONE launch — the whole bounce loop of a (tile, accumulation) stream runs in one workgroup, in the reference's
@@ -550,8 +621,9 @@ int launch_first_hit_aov(mirt_ctx* c, PipeSlot& sl, hipStream_t st, const SceneD
 	}
 	{ Bracket t(c, MIRT_K_RESOLVE, st);
 	  const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
-	  hipLaunchKernelGGL(lens_on(c) ? k_first_hit_aov<true> : k_first_hit_aov<false>, dim3(grid), dim3(kBlock), 0, st, sc, fp, sl.hit, c->policy.brdf ? c->mat_ggx.as<float4>() : c->scene.mat_albedo,
-	                     c->aov.as<float>(), c->lens); }
+	  const float4* colour = c->policy.brdf ? c->mat_ggx.as<float4>() : c->scene.mat_albedo;
+	  if (c->n_frozen) hipLaunchKernelGGL(kFirstHitAovSparse[lens_on(c)], dim3(grid), dim3(kBlock), 0, st, sc, fp, sl.hit, colour, c->aov.as<float>(), c->lens, c->tile_frozen.as<uint32_t>());
+	  else hipLaunchKernelGGL(lens_on(c) ? k_first_hit_aov<true> : k_first_hit_aov<false>, dim3(grid), dim3(kBlock), 0, st, sc, fp, sl.hit, colour, c->aov.as<float>(), c->lens); }
 	if (pipelined) { HIP_TRY(c, hipEventRecord(sl.aov_done, st)); c->aov_prev = sl.aov_done; }
 	return MIRT_OK;
 }
@@ -569,7 +641,11 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 	FrameParams fp = frame_params(c, c->accumulations, batch_n);
 	const uint32_t nb = c->policy.max_bounces;
 	const uint64_t total = static_cast<uint64_t>(fp.n_pix) * batch_n;
-	if (total == 0) { c->accumulations += batch_n; return MIRT_OK; }                   // no tile owned (an image below 16 px, a group member beyond the last tile row): ++accumulations over an empty parallel_for, Renderer.hpp:74-75
+	// Once a tile is frozen (mirt_freeze_tiles) bounce 0 and the merge run their sparse twins; while none is, every launch below is what it has always been.
+	const bool sparse = c->n_frozen != 0;
+	const uint32_t* tile_frozen = c->tile_frozen.as<uint32_t>();
+	const uint32_t active_pix = (c->n_tiles - c->n_frozen) * kTileSize;
+	if (total == 0 || active_pix == 0) { c->accumulations += batch_n; return MIRT_OK; }   // every tile frozen: the call is only counted; or no tile owned (an image below 16 px, a group member beyond the last tile row): ++accumulations over an empty parallel_for, Renderer.hpp:74-75
 	const bool pipelined = c->slots.size() > 1;
 	PipeSlot& sl = c->slots[c->batch_seq % c->slots.size()];
 	hipStream_t st = pipelined ? sl.stream : c->stream;
@@ -607,6 +683,22 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 		// box and sphere counts are those of a batch that does all of its work.)
 		if (!c->cand_valid || count) { const int r = build_primary_lists(c, sc, fp, count); if (r) return r; }
 		if (pipelined && sl.cand_gen != c->cand_gen) { HIP_TRY(c, hipStreamWaitEvent(st, c->cand_built, 0)); sl.cand_gen = c->cand_gen; }
+		if (sparse) {
+			// the listed pixels of the active tiles: made on the main stream behind the lists' build (and, like it, behind every earlier batch's merge
+			// wait), again whenever the lists or the mask have changed
+			if (c->listed_gen == 0 || c->listed_for_cand != c->cand_gen || c->listed_for_freeze != c->freeze_gen) {
+				HIP_TRY(c, c->listed_active.ensure((static_cast<size_t>(fp.n_pix) + 1) * sizeof(uint32_t)));
+				if (!c->listed_built) HIP_TRY(c, hipEventCreateWithFlags(&c->listed_built, hipEventDisableTiming));
+				uint32_t* la = c->listed_active.as<uint32_t>();
+				HIP_TRY(c, hipMemsetAsync(la, 0, sizeof(uint32_t), c->stream));
+				const CandWords words{ c->cand_words.as<uint32_t>() };
+				hipLaunchKernelGGL(k_listed_active, dim3(grid_for(c, fp.n_pix)), dim3(kBlock), 0, c->stream, c->cand_listed.as<uint32_t>(), words.listed_pixels(), tile_frozen, la + 1, la);
+				HIP_TRY(c, hipGetLastError());
+				HIP_TRY(c, hipEventRecord(c->listed_built, c->stream));
+				c->listed_for_cand = c->cand_gen; c->listed_for_freeze = c->freeze_gen; c->listed_gen++;
+			}
+			if (pipelined && sl.listed_gen != c->listed_gen) { HIP_TRY(c, hipStreamWaitEvent(st, c->listed_built, 0)); sl.listed_gen = c->listed_gen; }
+		}
 	}
 	const CandWords cw{ c->cand_words.as<uint32_t>() };
 	if (c->stream_order) {
@@ -628,27 +720,37 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			      // 8 KB of LDS per wave: five workgroups per CU are resident; four times that, grid-stride, so that a CU which gets fewer is not the tail
 			      const uint64_t runs = static_cast<uint64_t>(fp.n_pix) / kWaveHitsRun;
 			      const uint32_t wgrid = static_cast<uint32_t>(std::min<uint64_t>((runs + kWaveHitsWaves - 1) / kWaveHitsWaves, static_cast<uint64_t>(c->n_cu) * 20u));
-			      hipLaunchKernelGGL(kPrimaryHitsWave[!count], dim3(wgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr);
+			      if (sparse) hipLaunchKernelGGL(kPrimaryHitsWaveSparse[!count], dim3(wgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr, tile_frozen, active_pix);
+			      else hipLaunchKernelGGL(kPrimaryHitsWave[!count], dim3(wgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr);
 			    } else {
 			      const uint32_t hgrid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
-			      hipLaunchKernelGGL(kPrimaryHits[!count], dim3(hgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr);
+			      if (sparse) hipLaunchKernelGGL(kPrimaryHitsSparse[!count], dim3(hgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr, tile_frozen, active_pix);
+			      else hipLaunchKernelGGL(kPrimaryHits[!count], dim3(hgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr);
 			    }
 			  }
 			  // the adds of bounce-1 that waited for occlusion land in the paths' contribution words before k_shade adds this bounce's terms;
 			  // a surviving path's record finds its origin and its path id in stream `in` (= out of bounce-1)
 			  const ShadowSink sink{ in.path, in.px, in.py, in.pz, contrib, batch_n, fp.pix_bits, nullptr };
 			  StreamBuf rays = in;
-			  if (lists) rays.path = c->cand_listed.as<uint32_t>();     // kPrimaryList reads nothing else of the stream: camera rays are functions of their index
-			  const TraceLaunch tl{ rays, sl.hit, lists ? Queue{ cw.listed_pixels(), 0u } : bc.stream_queue(bounce), bc.closest_work(bounce),      // kPrimaryList: n[0] = listed pixels
+			  // kPrimaryList reads nothing else of the stream: camera rays are functions of their index.  Once a tile is frozen: the listed pixels of the active tiles.
+			  uint32_t* listed_count = (lists && sparse) ? c->listed_active.as<uint32_t>() : cw.listed_pixels();
+			  if (lists) rays.path = sparse ? c->listed_active.as<uint32_t>() + 1 : c->cand_listed.as<uint32_t>();
+			  const TraceLaunch tl{ rays, sl.hit, lists ? Queue{ listed_count, 0u } : bc.stream_queue(bounce), bc.closest_work(bounce),      // kPrimaryList: n[0] = listed pixels
 			                        sl.shadow_buf, sink, shadow_pending ? bc.shadow_queue(bounce - 1) : bc.empty_queue(), bc.shadow_work(shadow_pending ? bounce - 1 : 0),
-			                        bc.fat_closest(bounce, fat_lists), bc.fat_shadow(bounce, fat_lists), lists ? cw.listed_pixels() : nullptr, ctr };
-			  launch_trace(c, st, sc, fp, total, count, lists ? kPrimaryList : bounce == 0 ? kPrimaryAll : kPrimaryNone, tl, bounce == 0 && lens); }
+			                        bc.fat_closest(bounce, fat_lists), bc.fat_shadow(bounce, fat_lists), lists ? listed_count : nullptr, ctr };
+			  // sparse, with lists: k_trace<., kPrimaryList> as ever, over the listed pixels of the active tiles
+			  if (sparse && bounce == 0 && !lists) launch_trace_sparse(c, st, sc, fp, active_pix, count, tl, lens);
+			  else launch_trace(c, st, sc, fp, total, count, lists ? kPrimaryList : bounce == 0 ? kPrimaryAll : kPrimaryNone, tl, bounce == 0 && lens); }
 			if (bounce == 0 && c->aov_on) { const int r = launch_first_hit_aov(c, sl, st, sc, fp); if (r) return r; }
 			{ Bracket t(c, MIRT_K_SHADE, st);
 			  // policy.brdf = 1 (#define BRDF 1): Closure<GGX> with this bounce's gloss decay, passed by value
 			  const float decay = bounce < c->gloss_decay.size() ? c->gloss_decay[bounce] : 0.0f;
-			  hipLaunchKernelGGL(bounce == 0 && lens ? kShadeLens[c->policy.brdf != 0] : kShade[bounce == 0][c->policy.brdf != 0], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
-			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens); }
+			  if (sparse && bounce == 0)
+			    hipLaunchKernelGGL(kShadeFirstSparse[c->policy.brdf != 0][lens], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
+			                       bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, tile_frozen);
+			  else
+			    hipLaunchKernelGGL(bounce == 0 && lens ? kShadeLens[c->policy.brdf != 0] : kShade[bounce == 0][c->policy.brdf != 0], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
+			                       bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens); }
 		}
 	}
 	HIP_TRY(c, hipGetLastError());
@@ -658,8 +760,9 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 		HIP_TRY(c, hipStreamWaitEvent(c->stream, sl.batch_done, 0));
 	}
 	{ Bracket t(c, MIRT_K_RESOLVE);
-	  hipLaunchKernelGGL(k_merge_contrib, dim3(grid_for(c, static_cast<uint64_t>(c->n_tiles) * (kTileSize / 4u))), dim3(kBlock), 0, c->stream,
-	                     c->accumulator.as<float4>(), sl.contrib.as<float4>(), c->n_tiles, c->policy.buckets, batch_n, fp.acc_base); }
+	  const dim3 mgrid(grid_for(c, static_cast<uint64_t>(c->n_tiles) * (kTileSize / 4u)));
+	  if (sparse) hipLaunchKernelGGL(k_merge_contrib_sparse, mgrid, dim3(kBlock), 0, c->stream, c->accumulator.as<float4>(), sl.contrib.as<float4>(), c->n_tiles, c->policy.buckets, batch_n, fp.acc_base, tile_frozen);
+	  else hipLaunchKernelGGL(k_merge_contrib, mgrid, dim3(kBlock), 0, c->stream, c->accumulator.as<float4>(), sl.contrib.as<float4>(), c->n_tiles, c->policy.buckets, batch_n, fp.acc_base); }
 	HIP_TRY(c, hipGetLastError());
 	if (pipelined) { HIP_TRY(c, hipEventRecord(sl.merged, c->stream)); sl.in_use = true; }
 	c->batch_seq++;
@@ -847,6 +950,7 @@ int plan_trace_lds(mirt_ctx* c) {
 	for (const auto& row : kTrace) for (const auto k : row) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
 	for (const auto k : kPrimaryCand) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
 	for (const auto k : kTraceLens) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+	for (const auto& row : kTraceSparse) for (const auto k : row) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
 	return MIRT_OK;
 }
 
@@ -946,10 +1050,13 @@ int mirt_destroy(mirt_ctx* c) {
 	for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
 	DeviceBuffer* bufs[] = { &c->recs, &c->recs_wide, &c->spheres, &c->prim_mat, &c->light_sphere, &c->light_emit, &c->mat_albedo, &c->mat_emission,
 	                         &c->mat_ggx, &c->hdri, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
-	                         &c->cand, &c->cand_listed, &c->cand_words, &c->noise_rec, &c->noise_hist };
+	                         &c->cand, &c->cand_listed, &c->cand_words, &c->noise_rec, &c->noise_hist, &c->noise_above,
+	                         &c->tile_frozen, &c->active_list, &c->tile_counts };
 	for (DeviceBuffer* b : bufs) b->release();
 	if (c->frame_host) (void)hipHostFree(c->frame_host);
 	if (c->cand_built) (void)hipEventDestroy(c->cand_built);
+	if (c->listed_built) (void)hipEventDestroy(c->listed_built);
+	c->listed_active.release();
 	if (c->stream) (void)hipStreamDestroy(c->stream);
 	delete c;
 	return MIRT_OK;
@@ -1061,6 +1168,7 @@ int mirt_set_stream_order(mirt_ctx* c, uint32_t exact) {
 	if (exact > 1) return fail(c, MIRT_ERR_ARG, "stream order %u is neither 0 (any order, FMA form for every ray) nor 1 (the reference's slots and scalar tail)", exact);
 	if (exact == c->stream_order) return MIRT_OK;
 	if (exact && lens_on(c)) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which has no lens (Camera.hpp:80-88 ignores it): call mirt_set_lens(ctx, 0, 0) first");
+	if (exact && c->n_frozen) return fail(c, MIRT_ERR_STATE, "exact stream order runs a tile's whole bounce loop in one launch and has no form that skips frozen tiles (%u are frozen): mirt_reset first", c->n_frozen);
 	if (exact && c->aov_on) return fail(c, MIRT_ERR_STATE, "exact stream order keeps no hit records (k_tile_stream runs a tile's whole bounce loop in one launch), so it cannot feed the first-hit AOVs: call mirt_set_aov(ctx, 0) first");
 	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render in the mode they were issued under
 	c->stream_order = exact;
@@ -1175,6 +1283,7 @@ int mirt_load_accumulator(mirt_ctx* c, const float* src, int src_is_device, uint
 	if (n && src != c->accumulator.ptr)                                                // src == the slab itself (filled in place by mirt_group_gather): only `accumulations` changes
 		HIP_TRY(c, hipMemcpy(c->accumulator.ptr, src, n * sizeof(float), src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
 	c->accumulations = accumulations;
+	clear_freezes(c);                                                                  // every tile at `accumulations`; mirt_load_tile_counts applies per-tile counts
 	return MIRT_OK;
 }
 
@@ -1225,6 +1334,7 @@ int mirt_load_aov(mirt_ctx* c, const float* src, int src_is_device) {
 }
 int mirt_render_aov(mirt_ctx* c, int which, float* out) {
 	if (!c) return MIRT_ERR_ARG;
+	int r = MIRT_OK;
 	if (!c->aov_on) return fail(c, MIRT_ERR_STATE, "AOVs are off (mirt_set_aov)");
 	if (which != MIRT_AOV_DEPTH && which != MIRT_AOV_NORMAL && which != MIRT_AOV_ALBEDO) return fail(c, MIRT_ERR_ARG, "no AOV %d (MIRT_AOV_DEPTH, _NORMAL, _ALBEDO)", which);
 	if (!out) return fail(c, MIRT_ERR_ARG, "out is NULL");
@@ -1235,9 +1345,11 @@ int mirt_render_aov(mirt_ctx* c, int which, float* out) {
 	const size_t image_floats = static_cast<size_t>(c->width) * c->height * ch;
 	ScopedBuffer image;
 	HIP_TRY(c, image.ensure(image_floats * sizeof(float)));
+	const uint32_t* counts = nullptr;
+	if ((r = upload_tile_counts(c, &counts))) return r;
 	{ Bracket t(c, MIRT_K_RESOLVE);
 	  hipLaunchKernelGGL(k_resolve_aov, dim3(grid_for(c, n_pix)), dim3(kBlock), 0, c->stream, c->aov.as<float>(), image.as<float>(), n_pix, tile_map(c), which,
-	                     static_cast<float>(c->accumulations)); }
+	                     static_cast<float>(c->accumulations), counts); }
 	HIP_TRY(c, hipGetLastError());
 	std::vector<float> host(image_floats);                                           // pixels of other contexts' tiles are never written: copy ours only
 	HIP_TRY(c, hipMemcpyAsync(host.data(), image.ptr, image_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -1255,9 +1367,11 @@ int mirt_render(mirt_ctx* c, float* rgba_host) {
 	{ const int fr = flush_and_wait(c); if (fr) return fr; }
 	const float scale = c->camera.exposure / static_cast<float>(c->accumulations / k);              // Renderer.hpp:439
 	const uint32_t n_pix = c->n_tiles * kTileSize;
+	const uint32_t* counts = nullptr;
+	if ((r = upload_tile_counts(c, &counts))) return r;
 	{ Bracket t(c, MIRT_K_RESOLVE);
 	  hipLaunchKernelGGL(k_resolve, dim3(grid_for(c, n_pix)), dim3(kBlock), 0, c->stream, c->accumulator.as<float>(), c->framebuffer.as<float4>(),
-	                     n_pix, tile_map(c), k, scale); }
+	                     n_pix, tile_map(c), k, scale, counts, c->camera.exposure); }
 	HIP_TRY(c, hipGetLastError());
 	const size_t frame_floats = static_cast<size_t>(c->width) * c->height * 4;
 	const bool whole = c->n_tiles == c->h_tiles * c->v_tiles && c->width == c->h_tiles * MIRT_TILE_ROOT && c->height == c->v_tiles * MIRT_TILE_ROOT;
@@ -1269,11 +1383,15 @@ int mirt_render(mirt_ctx* c, float* rgba_host) {
 }
 
 // ---- per-pixel noise estimate ------------------------------------------------------------------
-int mirt_noise(mirt_ctx* c, float floor, float* map_out, float* tile_out, uint32_t* hist_out, mirt_noise_stats* stats) {
+} // extern "C"
+namespace {
+// mirt_noise, and mirt_tile_above when above_out is given: then `target` is what a usable pixel's e is compared with.
+int noise_pass(mirt_ctx* c, float floor, float* map_out, float* tile_out, uint32_t* hist_out, mirt_noise_stats* stats, float target, uint32_t* above_out) {
 	int r = check_ready(c); if (r) return r;
 	const uint32_t k = c->policy.buckets;
 	char why[256];
 	if ((r = mirt_noise_host::check_noise_args(floor, k, why, sizeof why))) return fail(c, r, "%s", why);
+	if (above_out && !mirt_noise_host::finite_nonneg(target)) return fail(c, MIRT_ERR_ARG, "target %g is not a finite value >= 0", static_cast<double>(target));
 	const uint32_t issued = c->accumulations + c->deferred;
 	if (issued == 0 || (issued % k) != 0) return MIRT_NOT_READY;                                    // as mirt_render
 	{ const int fr = flush_and_wait(c); if (fr) return fr; }
@@ -1289,10 +1407,13 @@ int mirt_noise(mirt_ctx* c, float floor, float* map_out, float* tile_out, uint32
 		if (map_out) HIP_TRY(c, image.ensure(image_floats * sizeof(float)));
 		HIP_TRY(c, c->noise_rec.ensure(rec.size() * sizeof(float)));
 		HIP_TRY(c, c->noise_hist.ensure(MIRT_NOISE_BINS * sizeof(uint32_t)));
+		if (above_out) HIP_TRY(c, c->noise_above.ensure(static_cast<size_t>(c->n_tiles) * sizeof(uint32_t)));
+		const uint32_t* counts = nullptr;
+		if ((r = upload_tile_counts(c, &counts))) return r;
 		HIP_TRY(c, hipMemsetAsync(c->noise_hist.ptr, 0, MIRT_NOISE_BINS * sizeof(uint32_t), c->stream));
 		{ Bracket t(c, MIRT_K_RESOLVE);
 		  hipLaunchKernelGGL(k_noise, dim3(c->n_tiles), dim3(kTileSize), 0, c->stream, c->accumulator.as<float>(), map_out ? image.as<float>() : nullptr, c->noise_rec.as<float4>(),
-		                     c->noise_hist.as<uint32_t>(), m, k, scale, floor); }
+		                     c->noise_hist.as<uint32_t>(), m, k, scale, floor, counts, c->camera.exposure, above_out ? c->noise_above.as<uint32_t>() : nullptr, target); }
 		HIP_TRY(c, hipGetLastError());
 		std::vector<float> host(map_out ? image_floats : 0);                             // pixels of other contexts' tiles are never written: copy ours only
 		if (map_out) {                                                                   // only the 16-row bands that hold a tile of ours come back (one n-th of the image for a group member)
@@ -1307,6 +1428,7 @@ int mirt_noise(mirt_ctx* c, float floor, float* map_out, float* tile_out, uint32
 		}
 		HIP_TRY(c, hipMemcpyAsync(rec.data(), c->noise_rec.ptr, rec.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(c, hipMemcpyAsync(hist.data(), c->noise_hist.ptr, MIRT_NOISE_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+		if (above_out) HIP_TRY(c, hipMemcpyAsync(above_out, c->noise_above.ptr, static_cast<size_t>(c->n_tiles) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(c, hipStreamSynchronize(c->stream));
 		if (map_out) copy_owned_tiles(m, c->n_tiles, 1u, host.data(), map_out);
 	}
@@ -1314,6 +1436,92 @@ int mirt_noise(mirt_ctx* c, float floor, float* map_out, float* tile_out, uint32
 	if (hist_out) std::memcpy(hist_out, hist.data(), MIRT_NOISE_BINS * sizeof(uint32_t));
 	if (stats) mirt_noise_host::stats_from_tiles(rec.data(), c->n_tiles, stats);
 	return MIRT_OK;
+}
+} // namespace
+extern "C" {
+
+int mirt_noise(mirt_ctx* c, float floor, float* map_out, float* tile_out, uint32_t* hist_out, mirt_noise_stats* stats) {
+	return noise_pass(c, floor, map_out, tile_out, hist_out, stats, 0.0f, nullptr);
+}
+
+// ---- per-tile adaptive sampling ---------------------------------------------------------------------
+int mirt_tile_above(mirt_ctx* c, float floor, float target, uint32_t* above_out, size_t capacity) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!above_out) return fail(c, MIRT_ERR_ARG, "above_out is NULL");
+	if (capacity < c->n_tiles) return fail(c, MIRT_ERR_ARG, "tile_above: room for %zu counts, %u local tiles", capacity, c->n_tiles);
+	return noise_pass(c, floor, nullptr, nullptr, nullptr, nullptr, target, above_out);
+}
+
+int mirt_freeze_tiles(mirt_ctx* c, const uint8_t* freeze, size_t n_local_tiles) {
+	int r = check_ready(c); if (r) return r;
+	if (!freeze && n_local_tiles) return fail(c, MIRT_ERR_ARG, "freeze is NULL");
+	if (n_local_tiles != c->n_tiles) return fail(c, MIRT_ERR_ARG, "freeze_tiles: a mask of %zu tiles, the context owns %u", n_local_tiles, c->n_tiles);
+	if (c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order runs a tile's whole bounce loop in one launch and has no form that skips frozen tiles: call mirt_set_stream_order(ctx, 0) first");
+	const uint32_t issued = c->accumulations + c->deferred, k = c->policy.buckets;
+	if (issued == 0) return fail(c, MIRT_ERR_STATE, "nothing accumulated yet: a frozen tile would hold no sample");
+	if (issued % k != 0) return fail(c, MIRT_ERR_STATE, "%u accumulations so far: not a multiple of buckets (%u); a frozen tile must stay resolvable", issued, k);
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }                        // deferred accumulations were issued under the old mask
+	bool changed = false;
+	for (uint32_t t = 0; t < c->n_tiles; t++) {
+		if (!freeze[t] || (c->n_frozen && c->frozen[t])) continue;
+		if (c->frozen.empty()) { c->frozen.assign(c->n_tiles, 0); c->frozen_at.assign(c->n_tiles, 0u); }
+		c->frozen[t] = 1; c->frozen_at[t] = c->accumulations; c->n_frozen++;
+		changed = true;
+	}
+	return changed ? upload_freezes(c) : MIRT_OK;
+}
+
+int mirt_frozen_tiles(mirt_ctx* c, uint8_t* mask_out, size_t capacity) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!mask_out && c->n_tiles) return fail(c, MIRT_ERR_ARG, "mask_out is NULL");
+	if (capacity < c->n_tiles) return fail(c, MIRT_ERR_ARG, "frozen_tiles: room for %zu tiles, %u local tiles", capacity, c->n_tiles);
+	for (uint32_t t = 0; t < c->n_tiles; t++) mask_out[t] = (c->n_frozen && c->frozen[t]) ? 1 : 0;
+	return MIRT_OK;
+}
+
+int mirt_tile_counts(mirt_ctx* c, uint32_t* counts_out, size_t capacity) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!counts_out) return fail(c, MIRT_ERR_ARG, "counts_out is NULL");
+	if (capacity < c->n_tiles) return fail(c, MIRT_ERR_ARG, "tile_counts: room for %zu counts, %u local tiles", capacity, c->n_tiles);
+	for (uint32_t t = 0; t < c->n_tiles; t++) counts_out[t] = (c->n_frozen && c->frozen[t]) ? c->frozen_at[t] : c->accumulations + c->deferred;
+	return MIRT_OK;
+}
+
+int mirt_load_tile_counts(mirt_ctx* c, const uint32_t* counts, size_t n_local_tiles) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!counts && n_local_tiles) return fail(c, MIRT_ERR_ARG, "counts is NULL");
+	if (n_local_tiles != c->n_tiles) return fail(c, MIRT_ERR_ARG, "load_tile_counts: %zu counts, the context owns %u tiles", n_local_tiles, c->n_tiles);
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }
+	const uint32_t k = c->policy.buckets;
+	bool any = false;
+	for (uint32_t t = 0; t < c->n_tiles; t++) {
+		if (counts[t] == 0 || counts[t] % k != 0 || counts[t] > c->accumulations)
+			return fail(c, MIRT_ERR_ARG, "load_tile_counts: tile %u has count %u; every count is a positive multiple of buckets (%u) and at most accumulations (%u)", t, counts[t], k, c->accumulations);
+		any = any || counts[t] < c->accumulations;
+	}
+	if (any && c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order has no form that skips frozen tiles: call mirt_set_stream_order(ctx, 0) first");
+	clear_freezes(c);
+	if (!any) return MIRT_OK;
+	c->frozen.assign(c->n_tiles, 0); c->frozen_at.assign(c->n_tiles, 0u);
+	for (uint32_t t = 0; t < c->n_tiles; t++) if (counts[t] < c->accumulations) { c->frozen[t] = 1; c->frozen_at[t] = counts[t]; c->n_frozen++; }
+	return upload_freezes(c);
+}
+
+int mirt_accumulate_adaptive(mirt_ctx* c, const mirt_stop_rule* rule, uint32_t min_accumulations, mirt_adaptive_report* report) {
+	int r = check_ready(c); if (r) return r;
+	const uint32_t k = c->policy.buckets;
+	char why[256];
+	if ((r = mirt_noise_host::check_stop_rule(rule, k, c->accumulations + c->deferred, why, sizeof why))) return fail(c, r, "%s", why);
+	if (c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order has no form that skips frozen tiles: call mirt_set_stream_order(ctx, 0) first");
+	return mirt_noise_host::accumulate_adaptive(rule, k, min_accumulations, c->n_tiles,
+		[&](uint32_t* a) { return mirt_get_accumulations(c, a); },
+		[&](uint32_t n) { return mirt_accumulate(c, n); },
+		[&](float floor, float target, float* rec, uint32_t* above, mirt_noise_stats* st) { return noise_pass(c, floor, nullptr, rec, nullptr, st, target, above); },
+		[&](uint8_t* mask) { return mirt_frozen_tiles(c, mask, c->n_tiles); },
+		[&](const uint8_t* mask) { return mirt_freeze_tiles(c, mask, c->n_tiles); },
+		[&](uint32_t* counts) { return mirt_tile_counts(c, counts, c->n_tiles); },
+		[&](int code, const char* text) { return fail(c, code, "%s", text); },
+		report);
 }
 
 int mirt_accumulate_until(mirt_ctx* c, const mirt_stop_rule* rule, mirt_noise_stats* last, uint32_t* issued) {

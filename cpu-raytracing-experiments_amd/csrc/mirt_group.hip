@@ -104,6 +104,28 @@ int gfail(mirt_group* g, int code, const char* fmt, ...) {
 #define RETURN_IF_SINGLE(g, call) do { if ((g)->members.size() == 1) { mirt_ctx* ctx = (g)->members[0]; const int _rc = (call); return _rc < 0 ? gfail((g), _rc, "%s", mirt_last_error(ctx)) : _rc; } } while (0)
 #define GHIP(g, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return gfail((g), MIRT_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); } while (0)
 #define GNCCL(g, expr) do { ncclResult_t _r = (expr); if (_r != ncclSuccess) return gfail((g), MIRT_ERR_HIP, "%s: %s", #expr, g_rccl.GetErrorString(_r)); } while (0)
+// Per-tile values between the image's LaunchIndex order and member i's local order: its local tile row j is tile row i + j * n of the image
+// (mirt_group_resize), h_tiles tiles each — the split the tile records of mirt_group_noise use.
+template <class T> void rows_to_member(const T* image, T* local, uint32_t h_tiles, uint32_t rows, uint32_t i, uint32_t n, uint32_t per_tile = 1) {
+	for (uint32_t j = 0; j < rows; j++) std::memcpy(local + static_cast<size_t>(j) * h_tiles * per_tile, image + static_cast<size_t>(i + j * n) * h_tiles * per_tile, static_cast<size_t>(h_tiles) * per_tile * sizeof(T));
+}
+template <class T> void rows_to_image(const T* local, T* image, uint32_t h_tiles, uint32_t rows, uint32_t i, uint32_t n, uint32_t per_tile = 1) {
+	for (uint32_t j = 0; j < rows; j++) std::memcpy(image + static_cast<size_t>(i + j * n) * h_tiles * per_tile, local + static_cast<size_t>(j) * h_tiles * per_tile, static_cast<size_t>(h_tiles) * per_tile * sizeof(T));
+}
+// One per-tile read-out of every member, un-interleaved into LaunchIndex order.
+template <class T, class Call> int per_tile_read(mirt_group* g, T* out, size_t capacity, const char* what, Call call) {
+	const uint32_t n = static_cast<uint32_t>(g->members.size()), h_tiles = g->width / MIRT_TILE_ROOT, v_tiles = g->height / MIRT_TILE_ROOT;
+	if (!out || capacity < static_cast<size_t>(h_tiles) * v_tiles) return gfail(g, MIRT_ERR_ARG, "%s: room for %zu tiles, the image has %zu", what, capacity, static_cast<size_t>(h_tiles) * v_tiles);
+	std::vector<T> local;
+	for (uint32_t i = 0; i < n; i++) {
+		const uint32_t rows = mirt::TileMap::tile_rows_owned(v_tiles, i, n);
+		local.assign(static_cast<size_t>(rows) * h_tiles + 1, T(0));
+		const int rc = call(g->members[i], local.data(), static_cast<size_t>(rows) * h_tiles);
+		if (rc != MIRT_OK) return gfail(g, rc < 0 ? rc : MIRT_ERR_STATE, "%s on member %u (device %d): %s", what, i, g->devices[i], rc < 0 ? mirt_last_error(g->members[i]) : "not ready");
+		rows_to_image(local.data(), out, h_tiles, rows, i, n);
+	}
+	return MIRT_OK;
+}
 uint32_t accumulations_of(const mirt_group* g) { uint32_t acc = 0; (void)mirt_get_accumulations(g->members[0], &acc); return acc; }   // every member holds the same count
 
 } // namespace
@@ -345,6 +367,14 @@ int mirt_group_gather(mirt_group* g) {
 	if (t1) (void)hipEventDestroy(t1);
 	if (rc != MIRT_OK) return rc;
 	FULL_TRY(g, "mirt_load_accumulator", mirt_load_accumulator(g->full, static_cast<const float*>(parts[0].full_ptr), 1, accumulations_of(g)));   // in place: only `accumulations` changes
+	{	// the members' per-tile counts (mirt_freeze_tiles), so that the gather context resolves every tile at its own count; nothing to load while no tile is behind
+		std::vector<uint32_t> counts(static_cast<size_t>(h_tiles) * v_tiles);
+		const int cr = mirt_group_tile_counts(g, counts.data(), counts.size());
+		if (cr < 0) return cr;
+		bool behind = false;
+		for (uint32_t c : counts) behind = behind || c != accumulations_of(g);
+		if (behind) FULL_TRY(g, "mirt_load_tile_counts", mirt_load_tile_counts(g->full, counts.data(), counts.size()));
+	}
 	g->gathered = true;
 	return MIRT_OK;
 }
@@ -392,6 +422,63 @@ int mirt_group_accumulate_until(mirt_group* g, const mirt_stop_rule* rule, mirt_
 		[&](float floor, uint32_t* h, mirt_noise_stats* st) { return mirt_group_noise(g, floor, nullptr, nullptr, h, st); },
 		[&](int code, const char* text) { return gfail(g, code, "%s", text); },
 		last, issued, hist.data());
+}
+// ---- per-tile adaptive sampling: masks and counts in LaunchIndex order, split and un-interleaved on the host; no gather ----
+int mirt_group_freeze_tiles(mirt_group* g, const uint8_t* freeze, size_t n_tiles) {
+	if (!g) return MIRT_ERR_ARG;
+	RETURN_IF_SINGLE(g, mirt_freeze_tiles(ctx, freeze, n_tiles));
+	const uint32_t n = static_cast<uint32_t>(g->members.size()), h_tiles = g->width / MIRT_TILE_ROOT, v_tiles = g->height / MIRT_TILE_ROOT;
+	if (n_tiles != static_cast<size_t>(h_tiles) * v_tiles || (!freeze && n_tiles)) return gfail(g, MIRT_ERR_ARG, "freeze_tiles: a mask of %zu tiles, the image has %zu", n_tiles, static_cast<size_t>(h_tiles) * v_tiles);
+	const uint32_t acc = accumulations_of(g);
+	if (acc == 0 || acc % g->buckets != 0) return gfail(g, MIRT_ERR_STATE, "%u accumulations so far: tiles freeze at a positive multiple of buckets (%u)", acc, g->buckets);   // before any member is asked
+	std::vector<uint8_t> local;
+	for (uint32_t i = 0; i < n; i++) {
+		const uint32_t rows = mirt::TileMap::tile_rows_owned(v_tiles, i, n);
+		local.assign(static_cast<size_t>(rows) * h_tiles + 1, 0);
+		rows_to_member(freeze, local.data(), h_tiles, rows, i, n);
+		const int rc = mirt_freeze_tiles(g->members[i], local.data(), static_cast<size_t>(rows) * h_tiles);
+		if (rc < 0) return gfail(g, rc, "mirt_freeze_tiles on member %u (device %d): %s", i, g->devices[i], mirt_last_error(g->members[i]));
+	}
+	g->gathered = false;                                                             // the gather context's counts are stale
+	return MIRT_OK;
+}
+int mirt_group_tile_counts(mirt_group* g, uint32_t* counts_out, size_t capacity) {
+	if (!g) return MIRT_ERR_ARG;
+	RETURN_IF_SINGLE(g, mirt_tile_counts(ctx, counts_out, capacity));
+	return per_tile_read(g, counts_out, capacity, "mirt_tile_counts", [](mirt_ctx* c, uint32_t* o, size_t cap) { return mirt_tile_counts(c, o, cap); });
+}
+int mirt_group_frozen_tiles(mirt_group* g, uint8_t* mask_out, size_t capacity) {
+	if (!g) return MIRT_ERR_ARG;
+	RETURN_IF_SINGLE(g, mirt_frozen_tiles(ctx, mask_out, capacity));
+	return per_tile_read(g, mask_out, capacity, "mirt_frozen_tiles", [](mirt_ctx* c, uint8_t* o, size_t cap) { return mirt_frozen_tiles(c, o, cap); });
+}
+int mirt_group_tile_above(mirt_group* g, float floor, float target, uint32_t* above_out, size_t capacity) {
+	if (!g) return MIRT_ERR_ARG;
+	RETURN_IF_SINGLE(g, mirt_tile_above(ctx, floor, target, above_out, capacity));
+	char why[256];
+	if (const int bad = mirt_noise_host::check_noise_args(floor, g->buckets, why, sizeof why)) return gfail(g, bad, "%s", why);
+	if (!mirt_noise_host::finite_nonneg(target)) return gfail(g, MIRT_ERR_ARG, "target %g is not a finite value >= 0", static_cast<double>(target));
+	const uint32_t acc = accumulations_of(g);
+	if (acc == 0 || acc % g->buckets != 0) return MIRT_NOT_READY;                          // before any member is asked: above_out untouched
+	return per_tile_read(g, above_out, capacity, "mirt_tile_above", [&](mirt_ctx* c, uint32_t* o, size_t cap) { return mirt_tile_above(c, floor, target, o, cap); });
+}
+int mirt_group_accumulate_adaptive(mirt_group* g, const mirt_stop_rule* rule, uint32_t min_accumulations, mirt_adaptive_report* report) {
+	if (!g) return MIRT_ERR_ARG;
+	RETURN_IF_SINGLE(g, mirt_accumulate_adaptive(ctx, rule, min_accumulations, report));
+	char why[256];
+	if (const int bad = mirt_noise_host::check_stop_rule(rule, g->buckets, accumulations_of(g), why, sizeof why)) return gfail(g, bad, "%s", why);
+	const size_t n_tiles = static_cast<size_t>(g->width / MIRT_TILE_ROOT) * (g->height / MIRT_TILE_ROOT);
+	return mirt_noise_host::accumulate_adaptive(rule, g->buckets, min_accumulations, n_tiles,
+		[&](uint32_t* a) { return mirt_group_get_accumulations(g, a); },
+		[&](uint32_t c) { return mirt_group_accumulate(g, c); },
+		[&](float floor, float target, float* rec, uint32_t* above, mirt_noise_stats* st) {
+			const int rc = mirt_group_noise(g, floor, nullptr, rec, nullptr, st);
+			return rc != MIRT_OK ? rc : mirt_group_tile_above(g, floor, target, above, n_tiles); },
+		[&](uint8_t* mask) { return mirt_group_frozen_tiles(g, mask, n_tiles); },
+		[&](const uint8_t* mask) { return mirt_group_freeze_tiles(g, mask, n_tiles); },
+		[&](uint32_t* counts) { return mirt_group_tile_counts(g, counts, n_tiles); },
+		[&](int code, const char* text) { return gfail(g, code, "%s", text); },
+		report);
 }
 // Diagnostic: is RCCL usable from this process?  Loads librccl, makes a one-device communicator on `device` and sends n_floats to
 // itself through a grouped ncclSend / ncclRecv pair (the calls mirt_group_gather makes between distinct devices); 0 = the data arrived intact.

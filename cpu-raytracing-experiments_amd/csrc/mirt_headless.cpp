@@ -8,6 +8,11 @@
 //                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm] [--aov PREFIX]
 //                 [--f-number F] [--focus-distance D] [--unit-mm U] [--focus-pixel X,Y]
 //                 [--until-noise T] [--noise-quantile Q] [--noise-floor F] [--check-every N] [--max-accumulations M] [--noise-out map.pfm]
+//                 [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm]
+// --adaptive T renders with per-tile adaptive sampling (mirt_accumulate_adaptive): like --until-noise, but every 16 x 16 tile stops taking samples
+// as soon as ITS Q-quantile is <= T (not before --min-accumulations, default 0); ends when every tile has stopped or at --max-accumulations.
+// --counts-out writes the per-pixel sample count (each tile's count, painted over its pixels) as a one-channel PFM.  Adds a line
+// {"adaptive": {"converged": ..., "issued": ..., "checks": ..., "frozen_tiles": ..., "owned_tiles": ..., "tile_accumulations": ...}}
 // --until-noise T renders until converged instead of a fixed --spp (mirt_accumulate_until): N accumulations at a time (--check-every, default 4 x
 // buckets) until the Q-quantile (--noise-quantile, default 0.95) of the per-pixel noise estimate — the relative standard error of the mean of the
 // bucket means over (mean + F), F = --noise-floor — is <= T, or M accumulations (--max-accumulations, default 1000) are reached.  --noise-out writes
@@ -186,6 +191,9 @@ int main(int argc, char** argv) {
 	bool until_noise = false, noise_report = false;
 	float noise_target = 0.0f, noise_quantile = 0.95f, noise_floor = 0.0f;
 	uint32_t check_every = 0, max_accumulations = 1000;
+	bool adaptive = false;
+	uint32_t min_accumulations = 0;
+	std::string counts_out;
 	if (argc == 4 && std::string(argv[1]) == "--convert-hdr") {
 		// file-format check without a GPU: read a picture like stbi_loadf does (top-down) and store it again like Image::Store does (which
 		// flips, so the rows are handed over bottom-up): the output decodes to the same texels
@@ -222,6 +230,9 @@ int main(int argc, char** argv) {
 		else if (a == "--check-every") { check_every = static_cast<uint32_t>(std::atoi(next())); noise_report = true; }
 		else if (a == "--max-accumulations") { max_accumulations = static_cast<uint32_t>(std::atoi(next())); noise_report = true; }
 		else if (a == "--noise-out") { noise_out = next(); noise_report = true; }
+		else if (a == "--adaptive") { noise_target = static_cast<float>(std::atof(next())); adaptive = noise_report = true; }
+		else if (a == "--min-accumulations") min_accumulations = static_cast<uint32_t>(std::atoi(next()));
+		else if (a == "--counts-out") counts_out = next();
 		else if (a == "--devices") { devices.clear(); for (const char* p = next(); *p;) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p == ',') p++; } if (devices.empty()) return 2; }
 		else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
 	}
@@ -265,7 +276,13 @@ int main(int argc, char** argv) {
 		bool have_frame = false;
 		std::string frames_due;                                        // 1-based frame numbers on which Render() produced output
 		Renderer::UntilResult until{};
-		if (until_noise) {                                             // render until converged: the frame is resolved once, at the end
+		Renderer::AdaptiveResult adapt{};
+		if (adaptive) {                                                // per-tile adaptive sampling: the frame is resolved once, at the end, every tile at its own count
+			const mirt_stop_rule rule{ noise_target, noise_quantile, noise_floor, check_every ? check_every : 4u * policy.buckets, max_accumulations };
+			adapt = renderer.AccumulateAdaptive(rule, min_accumulations);
+			if (renderer.Render()) { have_frame = true; frames_due = std::to_string(renderer.accumulations()); }
+		}
+		else if (until_noise) {                                        // render until converged: the frame is resolved once, at the end
 			const mirt_stop_rule rule{ noise_target, noise_quantile, noise_floor, check_every ? check_every : 4u * policy.buckets, max_accumulations };
 			until = renderer.AccumulateUntil(rule);
 			if (renderer.Render()) { have_frame = true; frames_due = std::to_string(renderer.accumulations()); }
@@ -304,6 +321,16 @@ int main(int argc, char** argv) {
 				const std::string path = aov_prefix + "." + o.name + ".pfm";
 				if (!write_pfm_planes(path, renderer.RenderAOV(o.which), w, h, o.channels)) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
 			}
+		}
+		if (adaptive)
+			std::printf("{\"adaptive\": {\"converged\": %s, \"issued\": %u, \"checks\": %u, \"frozen_tiles\": %u, \"owned_tiles\": %u, \"tile_accumulations\": %llu}}\n", adapt.converged ? "true" : "false",
+			            adapt.report.issued, adapt.report.checks, adapt.report.frozen_tiles, adapt.report.owned_tiles, (unsigned long long)adapt.report.tile_accumulations);
+		if (!counts_out.empty()) {                                     // every tile's count over its 16 x 16 pixels (rows as in the frame: row 0 = y 0)
+			const std::vector<uint32_t> counts = renderer.TileCounts();
+			std::vector<float> img(static_cast<size_t>(w) * h, 0.0f);
+			const uint32_t h_tiles = w / 16u;
+			for (uint32_t y = 0; y < h; y++) for (uint32_t x = 0; x < w; x++) img[static_cast<size_t>(y) * w + x] = static_cast<float>(counts[(y / 16u) * h_tiles + x / 16u]);
+			if (!write_pfm_planes(counts_out, img, w, h, 1)) { std::fprintf(stderr, "cannot write %s\n", counts_out.c_str()); return 1; }
 		}
 		if (noise_report) {
 			const float qv = Renderer::NoiseQuantile(nz.hist, static_cast<double>(noise_quantile));

@@ -259,6 +259,38 @@ public:
 		r.converged = rc == MIRT_OK;
 		return r;
 	}
+	// Per-tile adaptive sampling (mirt.h): frozen tiles take no more samples; masks, counts and `above` hold one entry per tile of the image in
+	// LaunchIndex order.  A tile whose count is n holds what n plain Accumulate() calls leave in it.
+	size_t Tiles() const { return static_cast<size_t>(width / MIRT_TILE_ROOT) * (height / MIRT_TILE_ROOT); }
+	void FreezeTiles(const std::vector<uint8_t>& mask) { check(mirt_group_freeze_tiles(group_, mask.data(), mask.size()), "mirt_group_freeze_tiles"); }
+	std::vector<uint32_t> TileCounts() {
+		std::vector<uint32_t> counts(Tiles());
+		check(mirt_group_tile_counts(group_, counts.data(), counts.size()), "mirt_group_tile_counts");
+		return counts;
+	}
+	std::vector<uint32_t> NoiseAbove(float target, float floor = 0.0f) {   // usable pixels per tile with e > target; empty while Noise() is not ready
+		std::vector<uint32_t> above(Tiles());
+		const int rc = mirt_group_tile_above(group_, floor, target, above.data(), above.size());
+		check(rc, "mirt_group_tile_above");
+		if (rc != MIRT_OK) above.clear();
+		return above;
+	}
+	// The freeze rule (mirt_adaptive_select; host code): `frozen` may be empty (none).
+	static std::vector<uint8_t> AdaptiveSelect(const std::vector<float>& tiles, const std::vector<uint32_t>& above, const std::vector<uint8_t>& frozen, double quantile) {
+		if (tiles.size() != above.size() * 4 || (!frozen.empty() && frozen.size() != above.size())) throw std::runtime_error("AdaptiveSelect: tiles, above and frozen must describe the same tiles");
+		std::vector<uint8_t> out(above.size());
+		if (mirt_adaptive_select(tiles.data(), above.data(), frozen.empty() ? nullptr : frozen.data(), above.size(), quantile, out.data()) < 0) throw std::runtime_error("mirt_adaptive_select: quantile is not in (0, 1]");
+		return out;
+	}
+	// The adaptive loop (mirt_accumulate_adaptive): synchronous; converged = every tile froze before max_accumulations.
+	struct AdaptiveResult { bool converged; mirt_adaptive_report report; };
+	AdaptiveResult AccumulateAdaptive(const mirt_stop_rule& rule, uint32_t min_accumulations = 0) {
+		AdaptiveResult r{};
+		const int rc = mirt_group_accumulate_adaptive(group_, &rule, min_accumulations, &r.report);
+		check(rc, "mirt_group_accumulate_adaptive");
+		r.converged = rc == MIRT_OK;
+		return r;
+	}
 	double gather_ms() const { double ms = 0; mirt_group_last_gather_ms(group_, &ms); return ms; }
 	mirt_group* handle() { return group_; }
 

@@ -79,4 +79,52 @@ int accumulate_until(const mirt_stop_rule* rule, uint32_t buckets, Accumulations
 	}
 }
 
+// The loop of mirt_accumulate_adaptive / mirt_group_accumulate_adaptive over a renderer given as calls, each returning a mirt status:
+//   accumulations(uint32_t*), accumulate(uint32_t n)                       as above
+//   check(float floor, float target, float* rec, uint32_t* above, mirt_noise_stats*)   tile records and counts above the target, n_tiles each
+//   frozen(uint8_t* mask)                                                   the current mask, n_tiles bytes
+//   freeze(const uint8_t* mask), counts(uint32_t*)                          mirt_freeze_tiles, mirt_tile_counts
+// Nothing freezes before min_accumulations.  MIRT_OK when every tile is frozen, MIRT_NOT_CONVERGED at max_accumulations.
+template <class Accumulations, class Accumulate, class Check, class Frozen, class Freeze, class Counts, class Report>
+int accumulate_adaptive(const mirt_stop_rule* rule, uint32_t buckets, uint32_t min_accumulations, size_t n_tiles, Accumulations accumulations, Accumulate accumulate, Check check,
+                        Frozen frozen, Freeze freeze, Counts counts, Report report, mirt_adaptive_report* out) {
+	mirt_adaptive_report rep;
+	std::memset(&rep, 0, sizeof rep);
+	float* rec = new float[n_tiles * 4 + 1];
+	uint32_t* above = new uint32_t[n_tiles + 1];
+	uint8_t* mask = new uint8_t[n_tiles * 2 + 1];
+	uint8_t* next = mask + n_tiles;
+	int status = MIRT_OK, rc = MIRT_OK;
+	for (;;) {
+		if ((rc = frozen(mask)) < 0) break;
+		size_t n_frozen = 0;
+		for (size_t t = 0; t < n_tiles; t++) n_frozen += mask[t] ? 1u : 0u;
+		rep.frozen_tiles = static_cast<uint32_t>(n_frozen);
+		if (n_frozen == n_tiles) { status = MIRT_OK; break; }                     // every owned tile is frozen (or none is owned)
+		uint32_t acc = 0;
+		if ((rc = accumulations(&acc)) < 0) break;
+		const uint32_t room = rule->max_accumulations > acc ? rule->max_accumulations - acc : 0u;
+		const uint32_t step = room < rule->check_every ? room - room % buckets : rule->check_every;   // the last step is shortened, as in accumulate_until
+		if (step == 0) { status = MIRT_NOT_CONVERGED; break; }
+		if ((rc = accumulate(step)) < 0) break;
+		rep.issued += step;
+		if ((rc = check(rule->floor, rule->target, rec, above, &rep.last)) < 0) break;
+		if (rc != MIRT_OK) { rc = report(MIRT_ERR_STATE, "the noise estimate was not ready after a whole number of bucket rounds: the accumulation count was changed during the loop"); break; }
+		rep.checks++;
+		if (acc + step < min_accumulations) continue;                             // the guard against stopping on an early, lucky estimate
+		if ((rc = mirt_adaptive_select(rec, above, mask, n_tiles, static_cast<double>(rule->quantile), next)) < 0) { rc = report(rc, "adaptive_select refused its arguments"); break; }
+		if ((rc = freeze(next)) < 0) break;
+	}
+	if (rc >= 0) {
+		uint32_t* c = above;                                                      // (scratch: the counts)
+		rc = counts(c);
+		rep.owned_tiles = static_cast<uint32_t>(n_tiles);
+		for (size_t t = 0; rc >= 0 && t < n_tiles; t++) rep.tile_accumulations += c[t];
+	}
+	delete[] rec; delete[] above; delete[] mask;
+	if (rc < 0) return rc;
+	if (out) *out = rep;
+	return status;
+}
+
 } // namespace mirt_noise_host

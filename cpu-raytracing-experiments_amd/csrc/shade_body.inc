@@ -1,0 +1,169 @@
+// shade_body.inc — the body of k_shade and of its sparse twin (kernels.hpp), included by both with SPARSE a constant: one text, and the kernel
+// without frozen tiles compiles to the instructions it has always had.  SPARSE reads tile_frozen[local tile] (mirt_freeze_tiles).
+// Names it expects in scope: FIRST, GGX, LENS, SPARSE (constants); the arguments of k_shade; tile_frozen (read when SPARSE).  Defines SHADE_HIT_ORIGIN / _ACC / _SEED for shade_hit_body.inc on every inclusion (the same text each time).
+	const QueueView qin = FIRST ? queue_identity(fp.n_pix * fp.batch_n) : queue_view(in_queue);
+	const uint32_t n = qin.pre[kSegs];
+	const uint32_t n_chunks = (fp.n_pix + kShadeBlock - 1u) / kShadeBlock;      // FIRST
+	const bool last_bounce = !(bounce < fp.max_bounces - 1u);                 // Renderer.hpp:358
+	const float light_selection_pdf = 1.0f / static_cast<float>(fp.n_lights);  // Renderer.hpp:78
+	__shared__ uint32_t append_scratch[72];
+	__shared__ uint32_t compact_scratch[17];
+	__shared__ uint32_t hit_list[kShadeBlock];
+	__shared__ float4 s_albedo[MIRT_MAX_MATERIALS + 1], s_emission[MIRT_MAX_MATERIALS + 1];      // scene.material: 2 KB, read by every hit (GGX: s_albedo = {F0, roughness})
+	uint32_t c_term = 0, c_drop = 0, parity = 0;
+	const uint32_t n_units = n_chunks * fp.first_groups;                       // FIRST: pieces of work = (chunk, group of accumulations)
+	if (FIRST ? blockIdx.x >= n_units : blockIdx.x * kShadeBlock >= n) return;
+	for (uint32_t m = threadIdx.x; m < sc.n_mat; m += kShadeBlock) { s_albedo[m] = GGX ? mat_ggx[m] : sc.mat_albedo[m]; s_emission[m] = sc.mat_emission[m]; }
+	__syncthreads();            // the table is read by every wave in phase 2; k_shade<FIRST> reaches no other barrier before that (the early return above is block-uniform)
+
+	// !FIRST: this lane's ray of the stream for the block-iteration at hand, and its hit record: requested one iteration ahead, so that the
+	// first of the iteration's three dependent memory round trips is already under way
+	uint32_t next_slot = 0u; int32_t next_prim = -1;
+	if (!FIRST) {
+		next_slot = (blockIdx.x * kShadeBlock + threadIdx.x < n) ? queue_slot(qin, blockIdx.x * kShadeBlock, blockIdx.x * kShadeBlock + threadIdx.x) : 0u;
+		next_prim = hit_in[next_slot].prim;
+	}
+	// FIRST: the pixel of this lane in the chunk at hand, and what depends on it alone
+	uint32_t unit = blockIdx.x, chunk = 0u, slot_it = 0u, slot_end = 0u, pix = 0u, pix_seed = 0u;
+	int32_t pix_x = 0, pix_y = 0;
+	bool pix_frozen = false;                                                  // SPARSE
+	for (uint32_t base = blockIdx.x * kShadeBlock; FIRST ? unit < n_units : base < n; parity ^= 1u) {
+		const bool new_unit = FIRST && slot_it == slot_end;                    // wave-uniform
+		if (new_unit) {
+			chunk = unit / fp.first_groups;
+			const uint32_t g = unit - chunk * fp.first_groups;
+			slot_it = g * fp.batch_n / fp.first_groups; slot_end = (g + 1u) * fp.batch_n / fp.first_groups;
+		}
+		const uint32_t iteration = FIRST ? chunk * fp.batch_n + slot_it : base / kShadeBlock;     // FIRST: every (chunk, slot) exactly once
+		// ---- phase 1, one lane per ray of the stream: misses end here; hits are only listed ----
+		bool is_hit = false;
+		uint32_t my_slot = next_slot;
+		int32_t my_prim = next_prim;
+		float my_tfar = 0.0f;
+		f3 my_D{0, 0, 0};
+		f3 my_O{0, 0, 0};                                                       // LENS: the sample's point on the lens
+		uint32_t my_path = 0u;
+		bool lane_on;
+		f3 W0{0.0f, 0.0f, 0.0f};                                               // FIRST: the word this path starts with
+		if (FIRST) {
+			if (new_unit) {                                                      // a new chunk of pixels
+				pix = chunk * kShadeBlock + threadIdx.x;
+				if (pix < fp.n_pix) {
+					uint32_t tile;
+					pixel_xy(fp, pix, tile, pix_x, pix_y);
+					pix_seed = tile_seed(fp, tile, pix & 255u);
+					if (SPARSE) pix_frozen = tile_frozen[pix >> 8] != 0u;
+				}
+			}
+			lane_on = pix < fp.n_pix;
+			if (SPARSE) lane_on = lane_on && !pix_frozen;
+			my_slot = slot_it * fp.n_pix + pix;                                 // the ray's index in the batch = where k_trace stored a hit record for it
+			if (lane_on) {
+				// RAY GENERATION, Renderer.hpp:113-127 (primary_ray with the pixel's part taken from the chunk set-up); the two lines mirror camera_ray<LENS>
+				my_D = camera_sample(fp.cam, pix_x, pix_y, fp.acc_base + slot_it + 1u, pix_seed);
+				if (LENS) lens_ray(fp.cam, lens, my_D, fp.acc_base + slot_it + 1u, pix_seed, fp.max_bounces, my_O, my_D);
+				my_path = (slot_it << fp.pix_bits) | pix;
+				{ const HitRec h = hit_in[my_slot]; my_prim = h.prim; my_tfar = h.tfar; }      // the hit record of k_primary_hits / k_trace
+			}
+			if (++slot_it == slot_end) unit += gridDim.x;
+		} else {
+			lane_on = base + threadIdx.x < n;
+			const uint32_t nb = base + gridDim.x * kShadeBlock;
+			next_slot = (nb + threadIdx.x < n) ? queue_slot(qin, nb, nb + threadIdx.x) : 0u;
+			next_prim = hit_in[next_slot].prim;
+			base = nb;
+		}
+		{
+			if (lane_on) {
+				const uint32_t i = my_slot;
+				const int32_t prim = my_prim;
+				if (prim < 0) {
+					// MISS SHADER, Renderer.hpp:408-420 (Q10: throughput.r scales all three channels).  Without ambient light the path just
+					// ends: its word holds its result already (ACCUMULATION, Renderer.hpp:424-430, is k_merge_contrib's)
+					if (sc.has_ambient) {
+						if (FIRST) {
+							const f3 sky = sky_eval(sc, my_D.x, my_D.y, my_D.z);
+							W0 = { 0.0f + 1.0f * sky.x, 0.0f + 1.0f * sky.y, 0.0f + 1.0f * sky.z };
+						} else {
+							const float thr_x = in.tr[i];
+							const f3 sky = sky_eval(sc, in.dx[i], in.dy[i], in.dz[i]);
+							float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, in.path[i]);
+							w[0] += thr_x * sky.x; w[1] += thr_x * sky.y; w[2] += thr_x * sky.z;
+						}
+					}
+					c_term++;
+				} else if (last_bounce) {
+					c_drop++;                                                         // Q5: still alive after the last bounce -> never accumulated: the word goes back to +0
+					if (!FIRST) {                                                     // (FIRST: W0 is +0)
+						float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, in.path[i]);
+						w[0] = 0.0f; w[1] = 0.0f; w[2] = 0.0f;
+					}
+				} else is_hit = true;
+			}
+		}
+		// ---- regroup: the closest-hit shader is ~800 VALU instructions per ray and only 40-60 % of a secondary stream hits;
+		// packing the hits of the block into its first waves runs that code on full waves (lane utilisation 0.42 -> ~0.9) ----
+		// (Not for primary rays: ~95 % of them hit, the stream is already dense, and the two barriers cost more than they save.)
+		const uint32_t n_hits = FIRST ? 0u : block_compact(is_hit, my_slot, compact_scratch, hit_list);
+
+		// ---- phase 2, one lane per hit ----
+		bool survive = false, has_shadow = false, terminated = false, has_E = false;
+		uint32_t path = 0;
+		f3 P{0, 0, 0}, ndir{0, 0, 0}, L{0, 0, 0}, srad{0, 0, 0}, E{0, 0, 0};
+		f3 thr{1.0f, 1.0f, 1.0f};
+		float light_distance = 0.0f;
+		if (FIRST ? is_hit : threadIdx.x < n_hits) {
+			const uint32_t i = FIRST ? my_slot : hit_list[threadIdx.x];
+			f3 D = my_D;                                                       // bounce 0 has no stream: the ray is a function of its index (phase 1)
+			path = my_path;
+			if (!FIRST) { path = in.path[i]; D = { in.dx[i], in.dy[i], in.dz[i] }; }
+			float pdf_in = 0.0f;
+			if (!FIRST) {
+				thr = { in.tr[i], in.tg[i], in.tb[i] };
+				pdf_in = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, D.z);           // out->pdf of the bounce that sampled D (Q8), bit for bit; Closure<GGX>::pdf = 0
+			}
+			const HitRec hrec = FIRST ? HitRec{ my_tfar, my_prim } : hit_in[i];
+			const int32_t prim = hrec.prim;
+			{
+#define SHADE_HIT_ORIGIN (FIRST ? (LENS ? my_O : f3{ fp.cam.pos[0], fp.cam.pos[1], fp.cam.pos[2] }) : f3{ in.px[i], in.py[i], in.pz[i] })
+#define SHADE_HIT_ACC (fp.acc_base + (path >> fp.pix_bits) + 1u)
+#define SHADE_HIT_SEED (FIRST ? pix_seed : path_seed(fp, path & fp.pix_mask))
+#include "shade_hit_body.inc"
+			}
+		}
+		// ---- stream compaction: wave64 ballot + mbcnt prefix inside each wave, one atomic per workgroup and stream ----
+		uint32_t slot, sslot;
+		block_append2(survive, has_shadow, next_queue, shadow_queue, iteration % kSegs, append_scratch, parity, slot, sslot);
+		// (R + unoccluded NEE) + E is finished by k_trace's shadow_finish once the occlusion is known: an emissive hit with a light
+		// record pending sends E along (kDestFull); one without adds E to the path's word here.
+		const bool full = has_shadow & has_E;
+		if (survive) {
+			out.px[slot] = P.x; out.py[slot] = P.y; out.pz[slot] = P.z;
+			out.dx[slot] = ndir.x; out.dy[slot] = ndir.y; out.dz[slot] = ndir.z;
+			out.tr[slot] = thr.x; out.tg[slot] = thr.y; out.tb[slot] = thr.z;
+			out.path[slot] = path;
+		}
+		if (has_shadow) {
+			if (!survive) { sh.px[sslot] = P.x; sh.py[sslot] = P.y; sh.pz[sslot] = P.z; }          // else: the surviving ray's origin, found through dest
+			sh.dx[sslot] = L.x; sh.dy[sslot] = L.y; sh.dz[sslot] = L.z;
+			sh.tfar[sslot] = light_distance;
+			sh.sr[sslot] = srad.x; sh.sg[sslot] = srad.y; sh.sb[sslot] = srad.z;
+			if (full) { sh.er[sslot] = E.x; sh.eg[sslot] = E.y; sh.eb[sslot] = E.z; }
+			sh.dest[sslot] = (survive ? slot : (kDestAccum | path)) | (full ? kDestFull : 0u);
+		}
+		if (has_E & !has_shadow) {
+			if (FIRST) W0 = { 0.0f + E.x, 0.0f + E.y, 0.0f + E.z };
+			else {
+				float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, path);
+				w[0] += E.x; w[1] += E.y; w[2] += E.z;
+			}
+		}
+		// FIRST is pixel-major — this iteration's lanes are 512 consecutive pixels of one slot, i.e. two contiguous 3-KB runs of the buffer
+		if (FIRST && lane_on) {
+			float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, my_path);
+			w[0] = W0.x; w[1] = W0.y; w[2] = W0.z;
+		}
+		c_term += (terminated && !has_shadow) ? 1u : 0u;
+	}
+	wave_sum(c_term, &ctr->terminated);
+	wave_sum(c_drop, &ctr->dropped);

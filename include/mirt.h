@@ -322,6 +322,57 @@ typedef struct mirt_stop_rule {
  * word for word, that of the same number of plain mirt_accumulate calls. */
 int mirt_accumulate_until(mirt_ctx* ctx, const mirt_stop_rule* rule, mirt_noise_stats* last, uint32_t* issued);
 
+/* ---- per-tile adaptive sampling: converged tiles stop taking samples --------------------------------------------------------------
+ * mirt_accumulate_until samples the whole image until its quantile is quiet; most 16 x 16 tiles are quiet long before the last few.  A FROZEN
+ * tile takes no more samples: the bounce-0 kernels emit no camera ray for it, the merge neither reads nor writes it (HIP twins of those
+ * kernels, launched only once a tile is frozen: a context that never freezes one runs exactly what it ran before).  Frozen sets only grow —
+ * there is no un-freeze; mirt_reset, mirt_resize, mirt_set_tile_range, mirt_set_tile_rows, a mirt_set_policy that changes `buckets` and
+ * mirt_load_accumulator clear every freeze — so every tile still active has the same count, the context's `accumulations`, and a frozen tile's
+ * count is the value `accumulations` had when it froze.  THE CONTRACT, with no tolerance anywhere: a tile whose count is n holds, word for word,
+ * what n plain mirt_accumulate calls leave in that tile — accumulator and AOV slab (random draws are keyed on the global LaunchIndex and the
+ * accumulation index).  mirt_render, mirt_render_aov, mirt_noise and mirt_tile_above resolve every tile at its own count: on the device,
+ * scale = exposure / (float)(count / buckets) (AOVs: (float)count), the binary32 operations of the whole-image scale; their MIRT_NOT_READY
+ * rules stay on the global `accumulations`.  mirt_accumulate* with every tile frozen only counts calls, as a context without tiles does.
+ * Counters count what ran: `rays` only the samples of active tiles.  The owned pixel space is not compacted: batch size and stream memory stay
+ * sized by the owned pixels, and the sparse bounce-0 kernels still sweep every owned pixel.  Frozen tiles and exact stream order exclude each
+ * other (MIRT_ERR_STATE both ways).
+ * BIAS: stopping a tile on an estimate made from the very samples it holds keeps the tiles whose estimate came out low by chance — like every
+ * such rule it biases the frame dark, the more the earlier it may stop.  min_accumulations is the guard: nothing freezes before it. */
+/* ORs freeze[t] != 0 into the mask (n_local_tiles = the context's tiles, in local order = ascending LaunchIndex).  Deferred calls are launched
+ * first, under the old mask.  MIRT_ERR_ARG on a wrong length; MIRT_ERR_STATE when accumulations == 0, when accumulations % buckets != 0 (a
+ * frozen tile must stay resolvable), and in exact stream order. */
+int mirt_freeze_tiles(mirt_ctx* ctx, const uint8_t* freeze, size_t n_local_tiles);
+/* counts_out[t]: `accumulations` for an active tile, the frozen value for a frozen one.  MIRT_ERR_ARG when capacity is below the tiles. */
+int mirt_tile_counts(mirt_ctx* ctx, uint32_t* counts_out, size_t capacity);
+/* mask_out[t] = 1 for a frozen tile, else 0 (a tile frozen at the current count has the count of an active one: the counts do not tell). */
+int mirt_frozen_tiles(mirt_ctx* ctx, uint8_t* mask_out, size_t capacity);
+/* Companion of mirt_load_accumulator (checkpoint / resume): call it after that one, which sets every tile's count to its `accumulations` and
+ * clears all freezes.  Every count must be a positive multiple of `buckets` and <= accumulations (else MIRT_ERR_ARG, nothing changed); a tile
+ * below `accumulations` is frozen at its count. */
+int mirt_load_tile_counts(mirt_ctx* ctx, const uint32_t* counts, size_t n_local_tiles);
+/* (Named without the word of the noise section: that section's set of entry points is closed, and pinned by its interface test.)
+ * above_out[t] = usable pixels of local tile t with e > target (e, usable: mirt_noise's; the tile at its own count): one more ballot beside
+ * the kernel's own.  Statuses as mirt_noise; target finite and >= 0, capacity at least the context's tiles, else MIRT_ERR_ARG. */
+int mirt_tile_above(mirt_ctx* ctx, float floor, float target, uint32_t* above_out, size_t capacity);
+/* Pure host code: no context, no GPU.  From mirt_noise's tile records {max, mean, usable, nonfinite} and mirt_tile_above's counts: a tile not
+ * yet frozen freezes (freeze_out[t] = 1) when nonfinite == 0 and above <= (uint32_t)floor((1.0 - quantile) * usable), in double — at least
+ * the quantile of its usable pixels is at or below the target; a tile without a usable and without a non-finite pixel freezes (0 <= 0).
+ * A tile with frozen[t] != 0 is passed through as 1 (frozen may be NULL: none).  quantile in (0, 1], else MIRT_ERR_ARG. */
+int mirt_adaptive_select(const float* tile_records, const uint32_t* above, const uint8_t* frozen, size_t n_tiles, double quantile, uint8_t* freeze_out);
+typedef struct mirt_adaptive_report {
+	uint32_t issued;              /* accumulations added by this call (to the context's count; a frozen tile took fewer) */
+	uint32_t checks;              /* noise checks run */
+	uint32_t frozen_tiles;        /* at return */
+	uint32_t owned_tiles;
+	uint64_t tile_accumulations;  /* sum of the tiles' counts at return: 256 x this = camera rays the frame holds */
+	mirt_noise_stats last;        /* of the last check (zeros if none ran) */
+} mirt_adaptive_report;
+/* A host loop: mirt_accumulate(check_every), mirt_noise with mirt_tile_above(target), mirt_adaptive_select(quantile), mirt_freeze_tiles — the
+ * select and freeze only once accumulations >= min_accumulations.  MIRT_OK when every owned tile is frozen; MIRT_NOT_CONVERGED at
+ * max_accumulations (last step shortened as in mirt_accumulate_until).  Argument and state rules: mirt_accumulate_until's, and MIRT_ERR_STATE
+ * in exact stream order.  report may be NULL. */
+int mirt_accumulate_adaptive(mirt_ctx* ctx, const mirt_stop_rule* rule, uint32_t min_accumulations, mirt_adaptive_report* report);
+
 int mirt_get_counters(mirt_ctx* ctx, mirt_counters* out);
 int mirt_get_kernel_times(mirt_ctx* ctx, mirt_kernel_times* out, int reset);
 /* HIP stream the context launches on (hipStream_t), for callers that time with their own events. */
@@ -384,6 +435,16 @@ int mirt_group_render_aov(mirt_group* group, int which, float* out);            
  * namesakes'; MIRT_NOT_READY is decided before any member is asked, with every output untouched. */
 int mirt_group_noise(mirt_group* group, float floor, float* map_out, float* tile_out, uint32_t* hist_out, mirt_noise_stats* stats);
 int mirt_group_accumulate_until(mirt_group* group, const mirt_stop_rule* rule, mirt_noise_stats* last, uint32_t* issued);
+/* Per-tile adaptive sampling of the whole image (namesakes: "per-tile adaptive sampling" above).  Masks, counts and `above` are in LaunchIndex
+ * order, one entry per tile of the image; they are split over the members' tile rows and un-interleaved on the host, as the tile records of
+ * mirt_group_noise are — NO gather, also not in the loop.  mirt_group_gather loads the members' counts into the gather context, so
+ * mirt_group_render, mirt_group_render_aov resolve every tile at its own count.  Status rules as the namesakes', decided before any member is
+ * asked.  (mirt_group_tile_above: the group twin of mirt_tile_above.) */
+int mirt_group_freeze_tiles(mirt_group* group, const uint8_t* freeze, size_t n_tiles);
+int mirt_group_tile_counts(mirt_group* group, uint32_t* counts_out, size_t capacity);
+int mirt_group_frozen_tiles(mirt_group* group, uint8_t* mask_out, size_t capacity);
+int mirt_group_tile_above(mirt_group* group, float floor, float target, uint32_t* above_out, size_t capacity);
+int mirt_group_accumulate_adaptive(mirt_group* group, const mirt_stop_rule* rule, uint32_t min_accumulations, mirt_adaptive_report* report);
 /* Diagnostic: one-device RCCL communicator on `device`, n_floats sent to itself through a grouped ncclSend / ncclRecv. */
 int mirt_group_rccl_selftest(int device, size_t n_floats);
 
