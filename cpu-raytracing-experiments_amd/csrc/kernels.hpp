@@ -36,7 +36,7 @@ constexpr uint32_t kLdsStack = 16;              // traversal-stack entries per l
 constexpr uint32_t kLdsStackWide = 12;          // ... with binary16 records but u32 entries (> 32768 records or spheres): 48 KB, so that two workgroups still share a CU
 constexpr uint32_t kLeafBit = 0x80000000u;      // child reference flag (bvh_layout.hpp)
 constexpr uint32_t kStack = 64;                 // Stack<StackFrame,64>, BVH.hpp:321
-constexpr uint32_t kDestAccum = 0x80000000u;    // shadow-entry destination flag: the path ended at this hit — path id instead of stream slot
+constexpr uint32_t kDestAccum = 0x80000000u;    // shadow-entry destination flag: the path ended at this hit (counted as terminated once its shadow ray is done)
 
 struct SceneDev {
 	const float4* recs;         // GPU-internal child-pair records, 4 float4 each, breadth-first (bvh_layout.hpp)
@@ -63,24 +63,25 @@ struct SceneDev {
 	uint32_t use_bvh;
 };
 
-// RayStream<>::Buffer, DataStreams.hpp:75-88 — one SoA plane per member, `capacity` rays each.
+// RayStream<>::Buffer, DataStreams.hpp:75-88 — 16-byte records, `capacity` rays per plane: a lane moves a ray with two dwordx4 (and one dwordx2)
+// instead of one dword per member.  40 B per ray.
 struct StreamBuf {
-	float *px, *py, *pz, *dx, *dy, *dz;
-	float *tr, *tg, *tb;        // throughput
+	float4* a;                  // {p.xyz, bits of path}: path = (batch slot << FrameParams::pix_bits) | local pixel index (tile_local*256 + ID); stands in for pixelID + seed[]
+	float4* b;                  // {dir.xyz, throughput.r}
+	float2* c;                  // {throughput.g, throughput.b} — read by the hits only (the miss shader scales by throughput.r, Q10)
 	                            // (radiance has no plane: a path's running sum is its word of the contribution buffer, contrib_index)
 	                            // (`pdf` has no plane: Closure::pdf of the sampled direction is (1/pi) max(0, dir.z) of the WORLD-space dir
 	                            //  (Q8, Renderer.hpp:386,401), a function of the stored direction, recomputed by the bounce that needs it)
-	uint32_t* path;             // (batch slot << FrameParams::pix_bits) | local pixel index (tile_local*256 + ID); stands in for pixelID + seed[]
 };
-// RayStream<>::ShadowStream, DataStreams.hpp:113-126, plus the deferred-add operands.  A record is 32 B for the common case
-// (dir, tfar, NEE radiance, destination): the origin is the surviving ray's own (read from the next stream through `dest`;
-// stored here only for paths that Russian roulette ended), and the path radiance waits in the path's contribution word.
+// kPrimaryList launches have no ray stream: the words at `a` are the list of pixels instead (k_primary_cand's, or the active tiles' part of it).
+MIRT_DI const uint32_t* stream_pixel_list(const StreamBuf& in) { return reinterpret_cast<const uint32_t*>(in.a); }
+// RayStream<>::ShadowStream, DataStreams.hpp:113-126, plus the deferred-add operands.  A record holds its own ray — k_trace's refill is two
+// independent dwordx4 — and is 48 B for the common case (64 B with the emissive add); the path radiance waits in the path's contribution word.
 struct ShadowBuf {
-	float *px, *py, *pz;        // origin — written only when dest is the accumulator (no surviving ray to share it with)
-	float *dx, *dy, *dz, *tfar;
-	float *sr, *sg, *sb;        // NEE radiance carried by the shadow ray
-	float *er, *eg, *eb;        // kDestFull records only: emissive add of this bounce
-	uint32_t* dest;             // next-stream slot (the path survived), or kDestAccum | path id (it ended); | kDestFull
+	float4* a;                  // {origin.xyz, tfar}
+	float4* b;                  // {dir.xyz, bits of dest}: dest = path id | kDestAccum (the path ended at this hit) | kDestFull
+	float4* c;                  // {NEE radiance carried by the shadow ray, unused}
+	float4* d;                  // kDestFull records only: {emissive add of this bounce, unused}
 };
 struct FrameParams {
 	CameraParams cam;
@@ -817,9 +818,8 @@ __global__ __launch_bounds__(kBlock) void k_raygen(FrameParams fp, StreamBuf out
 		uint32_t path; float px, py, pz, dx, dy, dz;
 		if (LENS) lens_camera_ray(fp, lens, i, path, px, py, pz, dx, dy, dz);
 		else { primary_ray(fp, i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
-		out.px[i] = px; out.py[i] = py; out.pz[i] = pz;
-		out.dx[i] = dx; out.dy[i] = dy; out.dz[i] = dz;
-		out.path[i] = path;
+		out.a[i] = make_float4(px, py, pz, __uint_as_float(path));
+		out.b[i] = make_float4(dx, dy, dz, 1.0f);
 	}
 }
 
@@ -870,35 +870,31 @@ MIRT_DI size_t contrib_index(uint32_t batch_n, uint32_t pix_bits, uint32_t path)
 //   * light record (the common case: the hit was not emissive): an occluded ray (most of them) touches nothing and an
 //     unoccluded one adds its NEE radiance: R + S;
 //   * kDestFull record (emissive hit): E travels in the record and (R + S) + E, or R + E behind an occluder, is formed here.
-// The record finds its origin through the surviving ray's slot (shadow_origin), so `dest` holds that slot and the path id comes
-// from the slot's `path` word — one more load, for the unoccluded minority only; a path that ended carries its id (kDestAccum).
+// The record carries the path id in every case, so nothing here is found through another stream.
 // occ != nullptr (mirt_debug_trace_shadow): only the occlusion flag is stored.
 constexpr uint32_t kDestFull = 0x40000000u;
-constexpr uint32_t kDestSlot = 0x3fffffffu;     // stream slots stay below 2^30 (capacity check in mirt_capi.hip); path ids use bits 0-29 too (batch slot << pix_bits | pixel)
+constexpr uint32_t kDestPath = 0x3fffffffu;     // path ids use bits 0-29 (batch slot << pix_bits | pixel; capacity check in mirt_capi.hip)
 struct ShadowSink {
-	const uint32_t* path;       // path plane of the stream k_shade reads next
-	const float *px, *py, *pz;  // its origin planes (shared with the shadow rays of the surviving paths)
 	float* contrib;             // the batch's contribution buffer
 	uint32_t batch_n, pix_bits;
 	uint32_t* occ;
 };
-MIRT_DI void shadow_origin(const ShadowBuf& sh, const ShadowSink& sink, uint32_t i, float& px, float& py, float& pz) {
-	if (sink.occ) { px = sh.px[i]; py = sh.py[i]; pz = sh.pz[i]; return; }        // stage-level entry point: plain ray list
-	const uint32_t dw = sh.dest[i];
-	if (dw & kDestAccum) { px = sh.px[i]; py = sh.py[i]; pz = sh.pz[i]; }
-	else { const uint32_t d = dw & kDestSlot; px = sink.px[d]; py = sink.py[d]; pz = sink.pz[d]; }
+// A shadow ray of the queue: two independent 16-B loads.
+MIRT_DI void shadow_ray(const ShadowBuf& sh, uint32_t i, float& px, float& py, float& pz, float& dx, float& dy, float& dz, float& tfar) {
+	const float4 a = sh.a[i], b = sh.b[i];
+	px = a.x; py = a.y; pz = a.z; tfar = a.w; dx = b.x; dy = b.y; dz = b.z;
 }
+// (`dest` is read again here rather than kept from the refill: k_trace has no register to hold it across the walk.)
 MIRT_DI void shadow_finish(const ShadowBuf& sh, const ShadowSink& sink, uint32_t i, bool occluded, uint32_t& c_term) {
 	if (sink.occ) { sink.occ[i] = occluded ? 1u : 0u; return; }
-	const uint32_t dw = sh.dest[i];
+	const uint32_t dw = __float_as_uint(sh.b[i].w);
 	if (dw & kDestAccum) c_term++;
 	const bool full = (dw & kDestFull) != 0u;
 	if (occluded & !full) return;
-	const uint32_t path = (dw & kDestAccum) ? (dw & kDestSlot) : sink.path[dw & kDestSlot];
-	float* w = sink.contrib + contrib_index(sink.batch_n, sink.pix_bits, path);
+	float* w = sink.contrib + contrib_index(sink.batch_n, sink.pix_bits, dw & kDestPath);
 	f3 R{ w[0], w[1], w[2] };
-	if (!occluded) { R.x += sh.sr[i]; R.y += sh.sg[i]; R.z += sh.sb[i]; }
-	if (full) { R.x += sh.er[i]; R.y += sh.eg[i]; R.z += sh.eb[i]; }
+	if (!occluded) { const float4 S = sh.c[i]; R.x += S.x; R.y += S.y; R.z += S.z; }
+	if (full) { const float4 E = sh.d[i]; R.x += E.x; R.y += E.y; R.z += E.z; }
 	w[0] = R.x; w[1] = R.y; w[2] = R.z;
 }
 
@@ -910,7 +906,7 @@ MIRT_DI void shadow_finish(const ShadowBuf& sh, const ShadowSink& sink, uint32_t
 // 8 waves/SIMD (= two 16-wave workgroups per CU, the LDS plan of the binary16 layout) caps the kernel at 64 VGPRs.
 // PRIMARY != 0 = bounce 0: the rays are generated from their index (primary_ray), nothing is read; no shadow rays are pending.
 //   kPrimaryAll: every ray i of the batch, numbered 0 .. n_pix * batch_n - 1;  kPrimaryList: every sample of the pixels k_primary_cand
-//   listed in in.path (pixels without a candidate list; closest_queue.n[0] = how many); results are stored under the ray's index.
+//   listed at in.a (stream_pixel_list: pixels without a candidate list; closest_queue.n[0] = how many); results are stored under the ray's index.
 constexpr int kPrimaryNone = 0, kPrimaryAll = 1, kPrimaryList = 2;
 // kPrimaryList numbering: ray j of n_ov * batch_n is sample slot j / n_ov of the j % n_ov-th listed pixel (slot-major: the lanes of a wave
 // take neighbouring pixels of one accumulation, like everywhere else); returns its index in the batch, slot * n_pix + pixel.
@@ -944,16 +940,16 @@ __global__ __launch_bounds__(kTraceBlock, 8) void k_trace(SceneDev sc, FramePara
 		{
 			auto load_ray = [&](uint32_t i, float& px, float& py, float& pz, float& dx, float& dy, float& dz, float& tf) {
 				if (PRIMARY && LENS) { uint32_t path; lens_camera_ray(fp, lens, i, path, px, py, pz, dx, dy, dz); }
-				else if (PRIMARY) { uint32_t path; primary_ray(fp, PRIMARY == kPrimaryList ? primary_list_ray(fp, in.path, n_ov, inv_n_ov, i) : i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
-				else { px = in.px[i]; py = in.py[i]; pz = in.pz[i]; dx = in.dx[i]; dy = in.dy[i]; dz = in.dz[i]; }
+				else if (PRIMARY) { uint32_t path; primary_ray(fp, PRIMARY == kPrimaryList ? primary_list_ray(fp, stream_pixel_list(in), n_ov, inv_n_ov, i) : i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
+				else { const float4 a = in.a[i], b = in.b[i]; px = a.x; py = a.y; pz = a.z; dx = b.x; dy = b.y; dz = b.z; }
 				tf = MIRT_FLT_MAX;                                                 // hit reset, Renderer.hpp:150-158
 			};
-			auto store_result = [&](uint32_t i, const Trav& t, bool) { const uint32_t o = PRIMARY == kPrimaryList ? primary_list_ray(fp, in.path, n_ov, inv_n_ov, i) : i; hit_out[o] = HitRec{ t.tfar, t.prim }; };
+			auto store_result = [&](uint32_t i, const Trav& t, bool) { const uint32_t o = PRIMARY == kPrimaryList ? primary_list_ray(fp, stream_pixel_list(in), n_ov, inv_n_ov, i) : i; hit_out[o] = HitRec{ t.tfar, t.prim }; };
 			trace_queue<kClosest, COUNT>(sc, tl, closest_queue, nc, closest_work, fat_closest, c_nodes, c_spheres, load_ray, store_result);
 		}
 		if (!PRIMARY) {
 			auto load_ray = [&](uint32_t i, float& px, float& py, float& pz, float& dx, float& dy, float& dz, float& tf) {
-				shadow_origin(sh, sink, i, px, py, pz); dx = sh.dx[i]; dy = sh.dy[i]; dz = sh.dz[i]; tf = sh.tfar[i];
+				shadow_ray(sh, i, px, py, pz, dx, dy, dz, tf);
 			};
 			auto store_result = [&](uint32_t i, const Trav&, bool occluded) { shadow_finish(sh, sink, i, occluded, c_term); };
 			trace_queue<kAnyHit, COUNT>(sc, tl, shadow_queue, ns, shadow_work, fat_shadow, s_nodes, s_spheres, load_ray, store_result);
@@ -969,7 +965,7 @@ __global__ __launch_bounds__(kTraceBlock, 8) void k_trace(SceneDev sc, FramePara
 			if (active) {
 				if (PRIMARY && LENS) { uint32_t path; lens_camera_ray(fp, lens, i, path, px, py, pz, dx, dy, dz); }
 				else if (PRIMARY) { uint32_t path; primary_ray(fp, i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
-				else { px = in.px[i]; py = in.py[i]; pz = in.pz[i]; dx = in.dx[i]; dy = in.dy[i]; dz = in.dz[i]; }
+				else { const float4 a = in.a[i], b = in.b[i]; px = a.x; py = a.y; pz = a.z; dx = b.x; dy = b.y; dz = b.z; }
 			}
 			float tfar = MIRT_FLT_MAX;             // hit reset, Renderer.hpp:150-158
 			int32_t prim = -1;
@@ -980,7 +976,7 @@ __global__ __launch_bounds__(kTraceBlock, 8) void k_trace(SceneDev sc, FramePara
 			const bool active = base + threadIdx.x < ns;
 			const uint32_t i = active ? queue_slot(qs, base, base + threadIdx.x) : 0u;
 			float px = 0, py = 0, pz = 0, dx = 1, dy = 1, dz = 1, tfar = 0;
-			if (active) { shadow_origin(sh, sink, i, px, py, pz); dx = sh.dx[i]; dy = sh.dy[i]; dz = sh.dz[i]; tfar = sh.tfar[i]; }
+			if (active) shadow_ray(sh, i, px, py, pz, dx, dy, dz, tfar);
 			bool occluded = false;
 			int32_t dummy = -1;
 			if (sc.use_bvh == 0) occluded = traverse_brute<true, COUNT>(sc, lds, active, px, py, pz, dx, dy, dz, tfar, dummy, s_spheres);
@@ -1004,11 +1000,11 @@ __global__ __launch_bounds__(1024) void k_trace_fat(SceneDev sc, FrameParams fp,
 	const uint32_t n_ov = PRIMARY == kPrimaryList ? *ov_count : 0u;
 	const float inv_n_ov = 1.0f / static_cast<float>(n_ov ? n_ov : 1u);
 	for (uint32_t k = blockIdx.x; k < nc; k += gridDim.x) {
-		const uint32_t i = PRIMARY == kPrimaryList ? primary_list_ray(fp, in.path, n_ov, inv_n_ov, fat_closest.rays[k]) : fat_closest.rays[k];
+		const uint32_t i = PRIMARY == kPrimaryList ? primary_list_ray(fp, stream_pixel_list(in), n_ov, inv_n_ov, fat_closest.rays[k]) : fat_closest.rays[k];
 		float px, py, pz, dx, dy, dz;
 		if (PRIMARY && LENS) { uint32_t path; lens_camera_ray(fp, lens, i, path, px, py, pz, dx, dy, dz); }
 		else if (PRIMARY) { uint32_t path; primary_ray(fp, i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
-		else { px = in.px[i]; py = in.py[i]; pz = in.pz[i]; dx = in.dx[i]; dy = in.dy[i]; dz = in.dz[i]; }
+		else { const float4 a = in.a[i], b = in.b[i]; px = a.x; py = a.y; pz = a.z; dx = b.x; dy = b.y; dz = b.z; }
 		float tfar = MIRT_FLT_MAX; int32_t prim = -1;
 		for (uint32_t p = threadIdx.x; p < sc.n_spheres; p += blockDim.x) sphere_closest(sc.spheres[p], static_cast<int32_t>(p), px, py, pz, dx, dy, dz, tfar, prim);
 		// lexicographic (dist, prim) minimum across the workgroup; prim -1 = no hit, always loses (its tfar is FLT_MAX and every hit is < FLT_MAX)
@@ -1032,9 +1028,8 @@ __global__ __launch_bounds__(1024) void k_trace_fat(SceneDev sc, FrameParams fp,
 	}
 	for (uint32_t k = blockIdx.x; k < ns; k += gridDim.x) {
 		const uint32_t i = fat_shadow.rays[k];
-		float px, py, pz;
-		shadow_origin(sh, sink, i, px, py, pz);
-		const float dx = sh.dx[i], dy = sh.dy[i], dz = sh.dz[i], tfar = sh.tfar[i];
+		float px, py, pz, dx, dy, dz, tfar;
+		shadow_ray(sh, i, px, py, pz, dx, dy, dz, tfar);
 		bool occ = false;
 		for (uint32_t p = threadIdx.x; p < sc.n_spheres && !occ; p += blockDim.x) occ = sphere_occludes(sc.spheres[p], px, py, pz, dx, dy, dz, tfar);
 		const int any = __syncthreads_or(occ ? 1 : 0);
@@ -1052,7 +1047,7 @@ __global__ __launch_bounds__(1024) void k_trace_fat(SceneDev sc, FrameParams fp,
 // the host when the mask changes — in kPrimaryList's numbering (primary_list_ray), with what k_trace<., kPrimaryList> leaves out: the
 // brute-force loop of a context without a tree, the thin-lens ray, and ctr->rays (here n_active x batch_n; no k_primary_hits runs beside it).
 // Hit records go to slot * n_pix + pixel as ever; those of frozen pixels are neither written nor read.  Its fat rays (numbers in this
-// numbering) are k_trace_fat<., kPrimaryList, LENS>'s, with in.path = active_pix.  No shadow rays are pending at bounce 0.
+// numbering) are k_trace_fat<., kPrimaryList, LENS>'s, with in.a = active_pix.  No shadow rays are pending at bounce 0.
 template <bool COUNT, bool LENS>
 __global__ __launch_bounds__(kTraceBlock, 8) void k_trace_sparse(SceneDev sc, FrameParams fp, const uint32_t* __restrict__ active_pix, uint32_t n_active, HitRec* __restrict__ hit_out,
                                                               uint32_t* work, FatList fat, DevCounters* ctr, LensParams lens) {

@@ -184,7 +184,7 @@ int fail(mirt_ctx* ctx, int code, const char* fmt, ...) {
 constexpr uint32_t kMaxBatch = 256;         // upper limit of accumulations per batch; a context's own limit is what its path ids hold (max_slots)
 constexpr uint64_t kBatchRays = 1024ull << 20;   // round 3, cfg4 on the whole image (Mray/s, one batch in flight): 32 accumulations per batch 7970, 48: 8154, 63: 8218; 2 x 32: 7232, 2 x 24: 7192
 constexpr uint64_t kSerialRays = 96ull << 20;
-constexpr size_t kStreamPlanes = 2 * 10 + 2 + 14;      // two ray streams, hit (tfar, prim), shadow stream: 4-byte planes per ray of capacity
+constexpr size_t kStreamPlanes = 2 * 10 + 2 + 16;      // two ray streams (40 B), hit (tfar, prim), shadow stream (four 16-B records): in 4-byte planes per ray of capacity
 // Path id = (batch slot << pix_bits) | local pixel, below 2^30 (bits 30 and 31 of the words that carry it are flags): a context that owns
 // all 2^24 pixels of a 4096^2 image has room for 64 slots, one that owns an eighth of it (a rank of an 8-GPU run) for 512.
 uint32_t pix_bits_of(const mirt_ctx* c) { uint32_t b = 8; while ((1ull << b) < static_cast<uint64_t>(c->n_tiles) * kTileSize) b++; return b; }
@@ -313,7 +313,7 @@ int ensure_streams(mirt_ctx* c) {
 	plan_batches(c);
 	const uint64_t cap64 = n_pix * batch_limit(c);
 	if (n_pix > (1u << 24)) return fail(c, MIRT_ERR_ARG, "more than 2^24 pixels per context (%llu); shard the tile range", (unsigned long long)n_pix);
-	if (cap64 + 3ull * kSegs * kShadeBlock > (1ull << 30)) return fail(c, MIRT_ERR_ARG, "stream capacity %llu too large", (unsigned long long)cap64);   // stream slots carry two flag bits (kDestAccum, kDestFull)
+	if (cap64 + 3ull * kSegs * kShadeBlock > (1ull << 30)) return fail(c, MIRT_ERR_ARG, "stream capacity %llu too large", (unsigned long long)cap64);   // path ids and stream slots stay below 2^30 (a shadow record's dest word carries two flag bits: kDestAccum, kDestFull)
 	// a ray queue is kSegs segments of seg_cap slots (kernels.hpp "ray queues"): a plane holds kSegs * seg_cap entries
 	// (+ 2 blocks: k_shade<FIRST> iterates pixel-major, and when the pixel count is an odd multiple of 256 its half-filled last chunk adds iterations)
 	const uint32_t seg_cap = static_cast<uint32_t>((((cap64 + kShadeBlock - 1) / kShadeBlock + kSegs - 1) / kSegs + 2) * kShadeBlock);
@@ -354,21 +354,14 @@ int ensure_streams(mirt_ctx* c) {
 			return fail(c, MIRT_ERR_HIP, "%s (%zu bytes of ray streams per batch in flight): %s", what, planes * plane_bytes, hipGetErrorString(e));
 		}
 		char* p = sl.arena.as<char>();
-		auto take = [&]() { void* r = p; p += plane_bytes; return r; };
+		auto take = [&](size_t n_planes) { void* r = p; p += n_planes * plane_bytes; return r; };     // plane_bytes is a multiple of 256: every record plane is 16-B-aligned
 		for (int b = 0; b < 2; b++) {
 			StreamBuf& s = sl.stream_buf[b];
-			s.px = (float*)take(); s.py = (float*)take(); s.pz = (float*)take();
-			s.dx = (float*)take(); s.dy = (float*)take(); s.dz = (float*)take();
-			s.tr = (float*)take(); s.tg = (float*)take(); s.tb = (float*)take();
-			s.path = (uint32_t*)take();
+			s.a = (float4*)take(4); s.b = (float4*)take(4); s.c = (float2*)take(2);
 		}
-		sl.hit = (HitRec*)take(); (void)take();                            // planes are adjacent: 8 B per ray
+		sl.hit = (HitRec*)take(2);                                         // 8 B per ray
 		ShadowBuf& h = sl.shadow_buf;
-		h.px = (float*)take(); h.py = (float*)take(); h.pz = (float*)take();
-		h.dx = (float*)take(); h.dy = (float*)take(); h.dz = (float*)take(); h.tfar = (float*)take();
-		h.sr = (float*)take(); h.sg = (float*)take(); h.sb = (float*)take();
-		h.er = (float*)take(); h.eg = (float*)take(); h.eb = (float*)take();
-		h.dest = (uint32_t*)take();
+		h.a = (float4*)take(4); h.b = (float4*)take(4); h.c = (float4*)take(4); h.d = (float4*)take(4);
 	}
 	c->capacity = cap;
 	c->seg_cap = seg_cap;
@@ -547,7 +540,7 @@ struct TraceLaunch {
 	ShadowBuf sh; ShadowSink sink;                   // shadow rays and where their outcome goes
 	Queue shadow_queue; uint32_t* shadow_work;
 	FatList fat_closest, fat_shadow;
-	const uint32_t* listed_pixels;                   // kPrimaryList: count of the pixels listed in in.path (NULL otherwise)
+	const uint32_t* listed_pixels;                   // kPrimaryList: count of the pixels listed at in.a (NULL otherwise)
 	DevCounters* ctr;
 };
 // k_trace<count, primary> over n_rays, then (with a tree) the few rays too "fat" for it: brute force, one workgroup each.
@@ -568,7 +561,7 @@ void launch_trace_sparse(const mirt_ctx* c, hipStream_t st, const SceneDev& sc, 
 	                   t.closest_work, t.fat_closest, t.ctr, c->lens);
 	const uint32_t fat_grid = sc.n_spheres > 4096 ? static_cast<uint32_t>(c->n_cu) * 2u : 64u;
 	StreamBuf listed = t.in;
-	listed.path = const_cast<uint32_t*>(list + 1);
+	listed.a = reinterpret_cast<float4*>(const_cast<uint32_t*>(list + 1));             // kernels.hpp stream_pixel_list
 	if (sc.use_bvh) hipLaunchKernelGGL(lens ? kTraceFatListLens[!count] : kTraceFat[!count][kPrimaryList], dim3(fat_grid), dim3(1024), 0, st, sc, fp, listed, t.hit, t.fat_closest, t.sh, t.sink, t.fat_shadow, t.ctr, list, c->lens);
 }
 
@@ -729,12 +722,11 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			    }
 			  }
 			  // the adds of bounce-1 that waited for occlusion land in the paths' contribution words before k_shade adds this bounce's terms;
-			  // a surviving path's record finds its origin and its path id in stream `in` (= out of bounce-1)
-			  const ShadowSink sink{ in.path, in.px, in.py, in.pz, contrib, batch_n, fp.pix_bits, nullptr };
+			  const ShadowSink sink{ contrib, batch_n, fp.pix_bits, nullptr };
 			  StreamBuf rays = in;
 			  // kPrimaryList reads nothing else of the stream: camera rays are functions of their index.  Once a tile is frozen: the listed pixels of the active tiles.
 			  uint32_t* listed_count = (lists && sparse) ? c->listed_active.as<uint32_t>() : cw.listed_pixels();
-			  if (lists) rays.path = sparse ? c->listed_active.as<uint32_t>() + 1 : c->cand_listed.as<uint32_t>();
+			  if (lists) rays.a = reinterpret_cast<float4*>(sparse ? c->listed_active.as<uint32_t>() + 1 : c->cand_listed.as<uint32_t>());   // kernels.hpp stream_pixel_list
 			  const TraceLaunch tl{ rays, sl.hit, lists ? Queue{ listed_count, 0u } : bc.stream_queue(bounce), bc.closest_work(bounce),      // kPrimaryList: n[0] = listed pixels
 			                        sl.shadow_buf, sink, shadow_pending ? bc.shadow_queue(bounce - 1) : bc.empty_queue(), bc.shadow_work(shadow_pending ? bounce - 1 : 0),
 			                        bc.fat_closest(bounce, fat_lists), bc.fat_shadow(bounce, fat_lists), lists ? listed_count : nullptr, ctr };
@@ -979,20 +971,24 @@ int debug_trace(mirt_ctx* c, const char* who, size_t n, const float* p_xyz, cons
 	const size_t result_bytes = n * (shadow ? sizeof(uint32_t) : sizeof(HitRec));
 	HIP_TRY(c, hipSetDevice(c->device));
 	ScopedBuffer rays, res, cnt, ctr, fat;
-	HIP_TRY(c, rays.ensure(n * (shadow ? 7 : 6) * 4)); HIP_TRY(c, res.ensure(result_bytes)); HIP_TRY(c, cnt.ensure(BatchCounters::words(1) * 4));
+	HIP_TRY(c, rays.ensure(n * 2 * sizeof(float4))); HIP_TRY(c, res.ensure(result_bytes)); HIP_TRY(c, cnt.ensure(BatchCounters::words(1) * 4));
 	HIP_TRY(c, ctr.ensure(sizeof(DevCounters))); HIP_TRY(c, fat.ensure(2u * kFatCapacity * sizeof(uint32_t)));
-	float* d = rays.as<float>();
-	HIP_TRY(c, hipMemcpy(d, p_xyz, n * 12, hipMemcpyHostToDevice));
-	HIP_TRY(c, hipMemcpy(d + 3 * n, dir_xyz, n * 12, hipMemcpyHostToDevice));
-	if (shadow) HIP_TRY(c, hipMemcpy(d + 6 * n, tfar, n * 4, hipMemcpyHostToDevice));
+	// the caller's planes as the records k_trace reads: plane a = {p, tfar} (closest-hit: {p, path}, unused), plane b = {dir, unused}
+	float4* d = rays.as<float4>();
+	{ std::vector<float4> rec(2 * n);
+	  for (size_t i = 0; i < n; i++) {
+	    rec[i] = make_float4(p_xyz[i], p_xyz[n + i], p_xyz[2 * n + i], shadow ? tfar[i] : 0.0f);
+	    rec[n + i] = make_float4(dir_xyz[i], dir_xyz[n + i], dir_xyz[2 * n + i], 0.0f);
+	  }
+	  HIP_TRY(c, hipMemcpy(d, rec.data(), 2 * n * sizeof(float4), hipMemcpyHostToDevice)); }
 	const BatchCounters bc{ cnt.as<uint32_t>(), 1u, 0u };
 	const uint32_t n32 = static_cast<uint32_t>(n);
 	HIP_TRY(c, hipMemset(cnt.ptr, 0, BatchCounters::words(1) * 4));
 	HIP_TRY(c, hipMemcpy(shadow ? bc.shadow_queue(0).n : bc.stream_queue(0).n, &n32, 4, hipMemcpyHostToDevice));
 	HIP_TRY(c, hipMemset(ctr.ptr, 0, sizeof(DevCounters)));
 	TraceLaunch tl{};
-	if (shadow) { tl.sh.px = d; tl.sh.py = d + n; tl.sh.pz = d + 2 * n; tl.sh.dx = d + 3 * n; tl.sh.dy = d + 4 * n; tl.sh.dz = d + 5 * n; tl.sh.tfar = d + 6 * n; tl.sink.occ = res.as<uint32_t>(); }   // the sink only records the occlusion flags
-	else { tl.in.px = d; tl.in.py = d + n; tl.in.pz = d + 2 * n; tl.in.dx = d + 3 * n; tl.in.dy = d + 4 * n; tl.in.dz = d + 5 * n; tl.hit = res.as<HitRec>(); }
+	if (shadow) { tl.sh.a = d; tl.sh.b = d + n; tl.sink.occ = res.as<uint32_t>(); }   // the sink only records the occlusion flags
+	else { tl.in.a = d; tl.in.b = d + n; tl.hit = res.as<HitRec>(); }
 	tl.closest_queue = bc.stream_queue(0); tl.closest_work = bc.closest_work(0);
 	tl.shadow_queue = bc.shadow_queue(0); tl.shadow_work = bc.shadow_work(0);
 	tl.fat_closest = bc.fat_closest(0, fat.as<uint32_t>()); tl.fat_shadow = bc.fat_shadow(0, fat.as<uint32_t>());
@@ -1571,10 +1567,12 @@ int mirt_debug_raygen(mirt_ctx* c, uint32_t accumulations, float* p_xyz, float* 
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	const StreamBuf& s = c->slots[0].stream_buf[0];
-	float* srcs[6] = { s.px, s.py, s.pz, s.dx, s.dy, s.dz };
-	for (int k = 0; k < 3; k++) {
-		HIP_TRY(c, hipMemcpy(p_xyz + k * n, srcs[k], n * 4, hipMemcpyDeviceToHost));
-		HIP_TRY(c, hipMemcpy(dir_xyz + k * n, srcs[3 + k], n * 4, hipMemcpyDeviceToHost));
+	std::vector<float4> rec(2 * n);                                          // records {p, path}, {dir, throughput.r} -> the caller's planes
+	HIP_TRY(c, hipMemcpy(rec.data(), s.a, n * sizeof(float4), hipMemcpyDeviceToHost));
+	HIP_TRY(c, hipMemcpy(rec.data() + n, s.b, n * sizeof(float4), hipMemcpyDeviceToHost));
+	for (size_t i = 0; i < n; i++) {
+		p_xyz[i] = rec[i].x; p_xyz[n + i] = rec[i].y; p_xyz[2 * n + i] = rec[i].z;
+		dir_xyz[i] = rec[n + i].x; dir_xyz[n + i] = rec[n + i].y; dir_xyz[2 * n + i] = rec[n + i].z;
 	}
 	return MIRT_OK;
 }

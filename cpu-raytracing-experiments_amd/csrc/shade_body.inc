@@ -85,9 +85,10 @@
 							const f3 sky = sky_eval(sc, my_D.x, my_D.y, my_D.z);
 							W0 = { 0.0f + 1.0f * sky.x, 0.0f + 1.0f * sky.y, 0.0f + 1.0f * sky.z };
 						} else {
-							const float thr_x = in.tr[i];
-							const f3 sky = sky_eval(sc, in.dx[i], in.dy[i], in.dz[i]);
-							float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, in.path[i]);
+							const float4 b = in.b[i];                                      // {dir, throughput.r}
+							const float thr_x = b.w;
+							const f3 sky = sky_eval(sc, b.x, b.y, b.z);
+							float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, __float_as_uint(in.a[i].w));
 							w[0] += thr_x * sky.x; w[1] += thr_x * sky.y; w[2] += thr_x * sky.z;
 						}
 					}
@@ -95,7 +96,7 @@
 				} else if (last_bounce) {
 					c_drop++;                                                         // Q5: still alive after the last bounce -> never accumulated: the word goes back to +0
 					if (!FIRST) {                                                     // (FIRST: W0 is +0)
-						float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, in.path[i]);
+						float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, __float_as_uint(in.a[i].w));
 						w[0] = 0.0f; w[1] = 0.0f; w[2] = 0.0f;
 					}
 				} else is_hit = true;
@@ -116,16 +117,20 @@
 			const uint32_t i = FIRST ? my_slot : hit_list[threadIdx.x];
 			f3 D = my_D;                                                       // bounce 0 has no stream: the ray is a function of its index (phase 1)
 			path = my_path;
-			if (!FIRST) { path = in.path[i]; D = { in.dx[i], in.dy[i], in.dz[i] }; }
+			f3 O_in{0, 0, 0};
 			float pdf_in = 0.0f;
-			if (!FIRST) {
-				thr = { in.tr[i], in.tg[i], in.tb[i] };
+			if (!FIRST) {                                                      // the ray's three records
+				const float4 a = in.a[i], b = in.b[i];
+				const float2 c = in.c[i];
+				O_in = { a.x, a.y, a.z }; path = __float_as_uint(a.w);
+				D = { b.x, b.y, b.z };
+				thr = { b.w, c.x, c.y };
 				pdf_in = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, D.z);           // out->pdf of the bounce that sampled D (Q8), bit for bit; Closure<GGX>::pdf = 0
 			}
 			const HitRec hrec = FIRST ? HitRec{ my_tfar, my_prim } : hit_in[i];
 			const int32_t prim = hrec.prim;
 			{
-#define SHADE_HIT_ORIGIN (FIRST ? (LENS ? my_O : f3{ fp.cam.pos[0], fp.cam.pos[1], fp.cam.pos[2] }) : f3{ in.px[i], in.py[i], in.pz[i] })
+#define SHADE_HIT_ORIGIN (FIRST ? (LENS ? my_O : f3{ fp.cam.pos[0], fp.cam.pos[1], fp.cam.pos[2] }) : O_in)
 #define SHADE_HIT_ACC (fp.acc_base + (path >> fp.pix_bits) + 1u)
 #define SHADE_HIT_SEED (FIRST ? pix_seed : path_seed(fp, path & fp.pix_mask))
 #include "shade_hit_body.inc"
@@ -138,18 +143,16 @@
 		// record pending sends E along (kDestFull); one without adds E to the path's word here.
 		const bool full = has_shadow & has_E;
 		if (survive) {
-			out.px[slot] = P.x; out.py[slot] = P.y; out.pz[slot] = P.z;
-			out.dx[slot] = ndir.x; out.dy[slot] = ndir.y; out.dz[slot] = ndir.z;
-			out.tr[slot] = thr.x; out.tg[slot] = thr.y; out.tb[slot] = thr.z;
-			out.path[slot] = path;
+			out.a[slot] = make_float4(P.x, P.y, P.z, __uint_as_float(path));
+			out.b[slot] = make_float4(ndir.x, ndir.y, ndir.z, thr.x);
+			out.c[slot] = make_float2(thr.y, thr.z);
 		}
 		if (has_shadow) {
-			if (!survive) { sh.px[sslot] = P.x; sh.py[sslot] = P.y; sh.pz[sslot] = P.z; }          // else: the surviving ray's origin, found through dest
-			sh.dx[sslot] = L.x; sh.dy[sslot] = L.y; sh.dz[sslot] = L.z;
-			sh.tfar[sslot] = light_distance;
-			sh.sr[sslot] = srad.x; sh.sg[sslot] = srad.y; sh.sb[sslot] = srad.z;
-			if (full) { sh.er[sslot] = E.x; sh.eg[sslot] = E.y; sh.eb[sslot] = E.z; }
-			sh.dest[sslot] = (survive ? slot : (kDestAccum | path)) | (full ? kDestFull : 0u);
+			// the record holds its own ray and its path id (kernels.hpp ShadowBuf): k_trace reads nothing of the surviving ray
+			sh.a[sslot] = make_float4(P.x, P.y, P.z, light_distance);
+			sh.b[sslot] = make_float4(L.x, L.y, L.z, __uint_as_float(path | (survive ? 0u : kDestAccum) | (full ? kDestFull : 0u)));
+			sh.c[sslot] = make_float4(srad.x, srad.y, srad.z, 0.0f);
+			if (full) sh.d[sslot] = make_float4(E.x, E.y, E.z, 0.0f);
 		}
 		if (has_E & !has_shadow) {
 			if (FIRST) W0 = { 0.0f + E.x, 0.0f + E.y, 0.0f + E.z };
