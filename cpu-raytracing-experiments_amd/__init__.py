@@ -29,6 +29,7 @@ MIRT_NOT_CONVERGED = 2                            # mirt.h: accumulate_until gav
 NOISE_BINS = 2048                                 # mirt.h MIRT_NOISE_BINS
 AOV_DEPTH, AOV_NORMAL, AOV_ALBEDO = 0, 1, 2       # mirt.h MIRT_AOV_*
 AOV_PLANES = 7
+MAX_LIGHT_RIS = 32                                # mirt.h MIRT_MAX_LIGHT_RIS
 KERNEL_CLASSES = ("raygen", "trace", "shade", "shadow", "resolve")
 
 
@@ -109,6 +110,7 @@ def load_library():
         "mirt_get_policy": [P, C.POINTER(Policy)],
         "mirt_set_gloss_decay": [P, vp, u32],
         "mirt_set_stream_order": [P, u32], "mirt_get_stream_order": [P, C.POINTER(u32)],
+        "mirt_set_light_ris": [P, u32], "mirt_get_light_ris": [P, C.POINTER(u32)],
         "mirt_resize": [P, u32, u32],
         "mirt_set_tile_range": [P, u32, u32], "mirt_set_tile_rows": [P, u32, u32],
         "mirt_reset": [P],
@@ -163,6 +165,7 @@ def load_library():
         "mirt_group_set_policy": [G, C.POINTER(Policy)],
         "mirt_group_set_gloss_decay": [G, vp, u32],
         "mirt_group_set_stream_order": [G, u32],
+        "mirt_group_set_light_ris": [G, u32],
         "mirt_group_resize": [G, u32, u32],
         "mirt_group_reset": [G],
         "mirt_group_accumulate": [G, u32],
@@ -295,8 +298,10 @@ class _Binding:
         """mirt_<name> or mirt_group_<name> on this object's handle, checked."""
         return self._check(getattr(self._lib, self._prefix + name)(getattr(self, self._handle), *args))
 
-    def _configure(self, gloss_decay, exact_stream_order, aov):
+    def _configure(self, gloss_decay, exact_stream_order, aov, light_ris=0):
         """The end of both constructors, after the policy is set."""
+        if light_ris:
+            self.set_light_ris(light_ris)
         if gloss_decay is not None:
             self.set_gloss_decay(gloss_decay)
         if exact_stream_order:
@@ -335,6 +340,13 @@ class _Binding:
         (BVH.hpp:270-286) — brute-force traversal, a fidelity mode (mirt_set_stream_order).  False: the default wavefront order.
         (A group: on every member.)"""
         self._call("set_stream_order", int(exact))
+
+    def set_light_ris(self, candidates: int = 8):
+        """Next event estimation picks its light among `candidates` uniform draws by resampled importance sampling (the reference's unused
+        RIS<count>, Sampling.hpp:25-54): same expectation, less noise where many lights are wasted draws, still one shadow ray per hit.
+        0 = off (the default, the uniform draw); at most MAX_LIGHT_RIS; not in exact stream order.  Does not reset the accumulator.
+        (A group: on every member.)"""
+        self._call("set_light_ris", int(candidates))
 
     # -- scene hand-over (Application.cpp:230-234) -------------------------------------------------
     def _hand_over_scene(self, nodes=None):
@@ -534,7 +546,7 @@ class Renderer(_Binding):
     def __init__(self, scene: Scene, device: int = 0, max_bounces: int = 16, buckets: int = 5, mis: bool = True,
                  use_bvh: bool = False, count_traffic: bool = False, profile: bool = False, max_batch: int = 0,
                  allow_half_boxes: bool = True, reference_tree: bool = False, streams: int = 0, gpu_build: bool = False, trace_primary_rays: bool = False,
-                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False):
+                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False, light_ris: int = 0):
         self._lib = load_library()
         self._ctx = C.c_void_p()
         self._lens_follows_camera = bool(lens)          # lens=True: the scene camera's f_number / focus_distance / unit_mm drive a thin lens
@@ -548,7 +560,7 @@ class Renderer(_Binding):
                              int(brdf))
         self._call("set_policy", C.byref(self.policy))
         self._call("debug_allow_half_boxes", int(allow_half_boxes))
-        self._configure(gloss_decay, exact_stream_order, aov)
+        self._configure(gloss_decay, exact_stream_order, aov, light_ris)
 
     def load_tile_counts(self, counts):
         """After load_accumulator: per-tile counts (positive multiples of `buckets`, at most accumulations); tiles below it are frozen."""
@@ -560,6 +572,11 @@ class Renderer(_Binding):
         p = Policy()
         self._call("get_policy", C.byref(p))
         return {name: int(getattr(p, name)) for name, _ in Policy._fields_ if not name.startswith("_")}
+
+    def light_ris(self) -> int:
+        v = C.c_uint32(0)
+        self._call("get_light_ris", C.byref(v))
+        return v.value
 
     @property
     def stream_order(self) -> int:
@@ -695,7 +712,7 @@ class GroupRenderer(_Binding):
 
     def __init__(self, scene: Scene, devices=(0,), max_bounces: int = 16, buckets: int = 5, mis: bool = True, use_bvh: bool = True,
                  count_traffic: bool = False, max_batch: int = 0, streams: int = 0, reference_tree: bool = False, gpu_build: bool = False,
-                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False):
+                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False, light_ris: int = 0):
         self._lib = load_library()
         self._g = C.c_void_p()
         self._lens_follows_camera = bool(lens)
@@ -709,7 +726,15 @@ class GroupRenderer(_Binding):
         self.policy = Policy(max_bounces, buckets, int(mis), int(use_bvh), int(count_traffic), 0, max_batch, int(reference_tree), int(streams), int(gpu_build), 0,
                              int(brdf))
         self._call("set_policy", C.byref(self.policy))
-        self._configure(gloss_decay, exact_stream_order, aov)
+        self._configure(gloss_decay, exact_stream_order, aov, light_ris)
+
+    def light_ris(self) -> int:
+        """The members' setting (they all hold the same: set_light_ris sets every one)."""
+        ctx, v = C.c_void_p(), C.c_uint32(0)
+        self._call("member", 0, C.byref(ctx))
+        if self._lib.mirt_get_light_ris(ctx, C.byref(v)) < 0:
+            raise MirtError("mirt_get_light_ris failed on member 0")
+        return v.value
 
     def UpdateScene(self):
         self._hand_over_scene()

@@ -1288,14 +1288,31 @@ template <bool FIRST, bool GGX, bool LENS = false>
 __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
                                                   Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
                                                   const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens) {
-	constexpr bool SPARSE = false; const uint32_t* const tile_frozen = nullptr;
+	constexpr bool SPARSE = false, RIS = false; const uint32_t* const tile_frozen = nullptr; constexpr uint32_t ris_m = 0u;
 #include "shade_body.inc"
 }
 template <bool GGX, bool LENS>
 __global__ __launch_bounds__(kShadeBlock, 6) void k_shade_first_sparse(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
                                                   Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
                                                   const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens, const uint32_t* __restrict__ tile_frozen) {
-	constexpr bool SPARSE = true, FIRST = true;
+	constexpr bool SPARSE = true, FIRST = true, RIS = false; constexpr uint32_t ris_m = 0u;
+#include "shade_body.inc"
+}
+// RIS (mirt_set_light_ris): the twins whose next event estimation picks its light among ris_m candidates by resampled importance sampling
+// (shade_hit_body.inc) — ris_m is 1 .. MIRT_MAX_LIGHT_RIS, the same for every lane.  Twins, not a template parameter of the kernels above, so that
+// those keep their names, their arguments and their device code; the same text, the same launch bounds.
+template <bool FIRST, bool GGX, bool LENS = false>
+__global__ __launch_bounds__(kShadeBlock, 6) void k_shade_ris(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
+                                                  Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
+                                                  const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens, uint32_t ris_m) {
+	constexpr bool SPARSE = false, RIS = true; const uint32_t* const tile_frozen = nullptr;
+#include "shade_body.inc"
+}
+template <bool GGX, bool LENS>
+__global__ __launch_bounds__(kShadeBlock, 6) void k_shade_first_sparse_ris(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
+                                                  Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
+                                                  const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens, const uint32_t* __restrict__ tile_frozen, uint32_t ris_m) {
+	constexpr bool SPARSE = true, FIRST = true, RIS = true;
 #include "shade_body.inc"
 }
 
@@ -1354,6 +1371,7 @@ MIRT_DI void stream_shade_hit(const SceneDev& sc, const FrameParams& fp, const f
 	f3& P = h.P; f3& ndir = h.ndir; f3& L = h.L; f3& srad = h.srad; f3& E = h.E;
 	float& light_distance = h.light_distance;
 	bool terminated = false;                                                   // here: a shaded hit that does not survive
+	constexpr bool RIS = false; constexpr uint32_t ris_m = 0u;                 // exact stream order replays the reference: one uniform draw
 #define SHADE_HIT_ORIGIN stream_O
 #define SHADE_HIT_ACC stream_acc
 #define SHADE_HIT_SEED stream_seed

@@ -99,6 +99,7 @@ struct mirt_ctx {
 	DeviceBuffer recs, recs_wide, spheres, prim_mat, light_sphere, light_emit, mat_albedo, mat_emission, mat_ggx, hdri;
 	SceneDev scene{};
 	std::vector<float> gloss_decay;  // gloss_decay_table (Renderer.hpp:212) by bounce, read at launch (mirt_set_gloss_decay); missing entries are 0
+	uint32_t light_ris = 0;          // mirt_set_light_ris: candidates per NEE light pick; 0 = the uniform draw, the kernels without the candidate loop
 	uint32_t stream_order = 0;       // mirt_set_stream_order: 1 = a batch is one k_tile_stream launch (the reference's stream slots and scalar tail, brute force)
 	DeviceBuffer gloss_decay_dev;    // the table as k_tile_stream reads it (its bounce loop runs inside the kernel); uploaded by the first launch after a change
 	bool gloss_decay_dev_valid = false;
@@ -532,6 +533,12 @@ const decltype(&k_trace_fat<true, kPrimaryNone>) kTraceFatListLens[2] = { k_trac
 const decltype(&k_shade_first_sparse<false, false>) kShadeFirstSparse[2][2] = { { k_shade_first_sparse<false, false>, k_shade_first_sparse<false, true> },
                                                                                 { k_shade_first_sparse<true, false>, k_shade_first_sparse<true, true> } };   // [ggx][lens]
 const decltype(&k_first_hit_aov_sparse<false>) kFirstHitAovSparse[2] = { k_first_hit_aov_sparse<false>, k_first_hit_aov_sparse<true> };              // [lens]
+// The twins of every k_shade above whose next event estimation resamples its light (mirt_set_light_ris), launched only while the setting is
+// above 0; named after every table above, for the same reason.
+const decltype(&k_shade_ris<false, false>) kShadeRis[2][2] = { { k_shade_ris<false, false>, k_shade_ris<false, true> }, { k_shade_ris<true, false>, k_shade_ris<true, true> } };   // [first][ggx]
+const decltype(&k_shade_ris<false, false>) kShadeRisLens[2] = { k_shade_ris<true, false, true>, k_shade_ris<true, true, true> };                            // [ggx]
+const decltype(&k_shade_first_sparse_ris<false, false>) kShadeFirstSparseRis[2][2] = { { k_shade_first_sparse_ris<false, false>, k_shade_first_sparse_ris<false, true> },
+                                                                                        { k_shade_first_sparse_ris<true, false>, k_shade_first_sparse_ris<true, true> } };   // [ggx][lens]
 
 // What varies between the launches of the trace stage: a bounce of a batch, or the rays of a debug entry point.
 struct TraceLaunch {
@@ -737,7 +744,15 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			{ Bracket t(c, MIRT_K_SHADE, st);
 			  // policy.brdf = 1 (#define BRDF 1): Closure<GGX> with this bounce's gloss decay, passed by value
 			  const float decay = bounce < c->gloss_decay.size() ? c->gloss_decay[bounce] : 0.0f;
-			  if (sparse && bounce == 0)
+			  // mirt_set_light_ris: the candidate loop is worth its twins only where NEE runs; without it every launch below is what it has always been
+			  const uint32_t ris = fp.mis ? c->light_ris : 0u;
+			  if (ris && sparse && bounce == 0)
+			    hipLaunchKernelGGL(kShadeFirstSparseRis[c->policy.brdf != 0][lens], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
+			                       bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, tile_frozen, ris);
+			  else if (ris)
+			    hipLaunchKernelGGL(bounce == 0 && lens ? kShadeRisLens[c->policy.brdf != 0] : kShadeRis[bounce == 0][c->policy.brdf != 0], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
+			                       bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, ris);
+			  else if (sparse && bounce == 0)
 			    hipLaunchKernelGGL(kShadeFirstSparse[c->policy.brdf != 0][lens], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
 			                       bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, tile_frozen);
 			  else
@@ -1165,11 +1180,23 @@ int mirt_set_stream_order(mirt_ctx* c, uint32_t exact) {
 	if (exact == c->stream_order) return MIRT_OK;
 	if (exact && lens_on(c)) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which has no lens (Camera.hpp:80-88 ignores it): call mirt_set_lens(ctx, 0, 0) first");
 	if (exact && c->n_frozen) return fail(c, MIRT_ERR_STATE, "exact stream order runs a tile's whole bounce loop in one launch and has no form that skips frozen tiles (%u are frozen): mirt_reset first", c->n_frozen);
+	if (exact && c->light_ris) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which draws its NEE light uniformly (Renderer.hpp:259): call mirt_set_light_ris(ctx, 0) first");
 	if (exact && c->aov_on) return fail(c, MIRT_ERR_STATE, "exact stream order keeps no hit records (k_tile_stream runs a tile's whole bounce loop in one launch), so it cannot feed the first-hit AOVs: call mirt_set_aov(ctx, 0) first");
 	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render in the mode they were issued under
 	c->stream_order = exact;
 	return MIRT_OK;
 }
+// ---- NEE light by resampled importance sampling -------------------------------------------------
+int mirt_set_light_ris(mirt_ctx* c, uint32_t candidates) {
+	if (!c) return MIRT_ERR_ARG;
+	if (candidates > MIRT_MAX_LIGHT_RIS) return fail(c, MIRT_ERR_ARG, "light RIS: %u candidates (0 = off, at most %u)", candidates, MIRT_MAX_LIGHT_RIS);
+	if (candidates && c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which draws its NEE light uniformly (Renderer.hpp:259): call mirt_set_stream_order(ctx, 0) first");
+	if (candidates == c->light_ris) return MIRT_OK;
+	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render under the setting they were issued under
+	c->light_ris = candidates;                                                      // the expectation is the same: no reset; the lists do not depend on it
+	return MIRT_OK;
+}
+int mirt_get_light_ris(const mirt_ctx* c, uint32_t* candidates) { if (!c || !candidates) return MIRT_ERR_ARG; *candidates = c->light_ris; return MIRT_OK; }
 int mirt_get_stream_order(const mirt_ctx* c, uint32_t* exact) { if (!c || !exact) return MIRT_ERR_ARG; *exact = c->stream_order; return MIRT_OK; }
 int mirt_get_policy(const mirt_ctx* c, mirt_policy* p) {
 	if (!c || !p) return MIRT_ERR_ARG;

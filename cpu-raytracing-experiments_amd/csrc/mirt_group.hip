@@ -211,6 +211,11 @@ int mirt_group_set_lens(mirt_group* g, float aperture_radius, float focus_depth)
 	FOR_MEMBERS_AND_FULL(g, "mirt_set_lens", mirt_set_lens(ctx, aperture_radius, focus_depth));
 	return MIRT_OK;
 }
+int mirt_group_set_light_ris(mirt_group* g, uint32_t candidates) {
+	if (!g) return MIRT_ERR_ARG;
+	FOR_MEMBERS_AND_FULL(g, "mirt_set_light_ris", mirt_set_light_ris(ctx, candidates));
+	return MIRT_OK;
+}
 int mirt_group_pick_focus(mirt_group* g, uint32_t x, uint32_t y, float* distance, float* depth) {
 	if (!g) return MIRT_ERR_ARG;
 	mirt_ctx* ctx = g->members[0];                                                   // one ray: every member holds the whole scene

@@ -5,7 +5,7 @@
 // environment map the way the constructor does (stbi_loadf(..., 4), Application.cpp:225-231); --ambient sets sky.ambient_color, which scales it.
 //
 //   mirt_headless --scene default9|furnace|bvh_test|brdf_test|synthetic:N [--size WxH] [--spp N | --frames N] [--bounces B] [--buckets K] [--brute] [--devices 0,1,..]
-//                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm] [--aov PREFIX]
+//                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm] [--aov PREFIX] [--light-ris M]
 //                 [--f-number F] [--focus-distance D] [--unit-mm U] [--focus-pixel X,Y]
 //                 [--until-noise T] [--noise-quantile Q] [--noise-floor F] [--check-every N] [--max-accumulations M] [--noise-out map.pfm]
 //                 [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm]
@@ -24,6 +24,7 @@
 // focuses on its axial depth (a pick that meets the sky leaves the focus distance as given).
 // --brdf 1 renders every hit with the GGX closure (#define BRDF 1, Renderer.hpp:70), --gloss-decay gives its per-bounce table (:212).
 // --exact-stream-order replays the reference's stream slots and its scalar intersection tail (BVH.hpp:270-286; brute force, mirt_set_stream_order).
+// --light-ris M picks the NEE light among M uniform candidates by resampled importance sampling (mirt_set_light_ris; 0 = off, at most 32).
 // --aov PREFIX sums the first-hit AOVs beside the frame (mirt_set_aov) and writes PREFIX.depth.pfm (one channel, `Pf`), PREFIX.normal.pfm and
 // PREFIX.albedo.pfm (`PF`) after the last frame.
 // --devices: the GPUs the one Renderer object uses (tile rows split over them inside the library, one RCCL gather per frame read).
@@ -192,7 +193,7 @@ int main(int argc, char** argv) {
 	float noise_target = 0.0f, noise_quantile = 0.95f, noise_floor = 0.0f;
 	uint32_t check_every = 0, max_accumulations = 1000;
 	bool adaptive = false;
-	uint32_t min_accumulations = 0;
+	uint32_t min_accumulations = 0, light_ris = 0;
 	std::string counts_out;
 	if (argc == 4 && std::string(argv[1]) == "--convert-hdr") {
 		// file-format check without a GPU: read a picture like stbi_loadf does (top-down) and store it again like Image::Store does (which
@@ -220,6 +221,7 @@ int main(int argc, char** argv) {
 		else if (a == "--exact-stream-order") exact_stream_order = true;
 		else if (a == "--out") out = next();
 		else if (a == "--aov") aov_prefix = next();
+		else if (a == "--light-ris") light_ris = static_cast<uint32_t>(std::atoi(next()));
 		else if (a == "--f-number") { f_number = static_cast<float>(std::atof(next())); lens = true; }
 		else if (a == "--focus-distance") { focus_distance = static_cast<float>(std::atof(next())); lens = true; }
 		else if (a == "--unit-mm") { unit_mm = static_cast<float>(std::atof(next())); lens = true; }
@@ -255,6 +257,7 @@ int main(int argc, char** argv) {
 		renderer.SetGlossDecay(gloss_decay);
 		renderer.SetStreamOrder(exact_stream_order);
 		if (!aov_prefix.empty()) renderer.SetAOV(true);
+		renderer.SetLightRis(light_ris);
 		// pad the viewport to the tile requirement like UIRender does (Application.cpp:365-372)
 		const uint32_t t = static_cast<uint32_t>(Renderer::RequiredTiling());
 		w = (w + t - 1) & ~(t - 1); h = (h + t - 1) & ~(t - 1);

@@ -188,6 +188,9 @@ public:
 	// The reference's stream slots and scalar intersection tail (BVH.hpp:270-286) instead of the wavefront order (mirt.h, mirt_set_stream_order):
 	// brute-force traversal, for comparisons against the shipped binary.
 	void SetStreamOrder(bool exact) { check(mirt_group_set_stream_order(group_, exact ? 1u : 0u), "mirt_group_set_stream_order"); }
+	// The NEE light picked among `candidates` uniform draws by the reference's unused RIS<count> (Sampling.hpp:25-54; mirt.h, mirt_set_light_ris):
+	// 0 = off, the uniform draw of Renderer.hpp:259.  Same expectation, so the accumulator is not reset.
+	void SetLightRis(uint32_t candidates) { check(mirt_group_set_light_ris(group_, candidates), "mirt_group_set_light_ris"); }
 	// Renderer.hpp:73-434.  Asynchronous: Render() / counters() / the destructor wait for the GPUs; called once per frame the library
 	// still batches the frames between two Render()s that are due (mirt.h, mirt_accumulate_async).
 	void Accumulate(uint32_t n_calls = 1) { check(mirt_group_accumulate_async(group_, n_calls), "mirt_group_accumulate_async"); }

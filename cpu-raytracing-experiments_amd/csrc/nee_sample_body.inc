@@ -1,0 +1,38 @@
+// One light sample of next event estimation, Renderer.hpp:261-296: from the gather of light `selected` to the MIS-weighted radiance a shadow ray
+// towards it would carry.  Included as statements by shade_hit_body.inc, once for the plain draw and once inside the RIS candidate loop, so both
+// run ONE text.  Reads selected, u0, u1 and everything shade_hit_body.inc has in scope at that point; a sample that survives every early-out
+// ends in NEE_ACCEPT(direction, distance, radiance), which the including scope defines; one that does not leaves nothing behind.
+const float4 lp = sc.light_sphere[selected];                    // scene.geometry[lighting_acceleration.prims[selected]]
+const float4 lem = sc.light_emit[selected];                     // its material's emission, and the prim id
+const int32_t light_primID = static_cast<int32_t>(__float_as_uint(lem.w));
+do {
+	if (light_primID == prim) break;                             // Q11: geometry-order id vs BVH-order id
+	f3 Wc{ lp.x - P.x, lp.y - P.y, lp.z - P.z };
+	const float center_dist2 = dot3(Wc, Wc);
+	if (center_dist2 <= lp.w) break;
+	const float center_dist = __builtin_sqrtf(center_dist2);
+	{ const float inv = 1.0f / center_dist; Wc.x *= inv; Wc.y *= inv; Wc.z *= inv; }
+	const float sinThetaMax2 = lp.w / center_dist2;
+	{
+		const float NdotW = (2.0f * T.w) * (Wc.z * T.w + Wc.x * T.y - T.x * Wc.y) - Wc.z;
+		if (NdotW < 0.0f && sinThetaMax2 < NdotW * NdotW) break;
+	}
+	float ldist, lpdf;
+	const f3 Ld = sample_direction_to_sphere(Wc, sinThetaMax2, center_dist, lp.w, u0, u1, ldist, lpdf);
+	const f3 Ll = to_local(T, Ld);
+	if (Ll.z < 0.0f) break;
+	f3 rad{ lem.x * thr.x, lem.y * thr.y, lem.z * thr.z };
+	if (GGX) {  // Closure<GGX>::eval, DataStreams.hpp:189-195
+		const f3 f = ggx_eval(F0, alpha, Ll, Vl);
+		rad.x *= f.x; rad.y *= f.y; rad.z *= f.z;
+	} else {    // Closure<LambertianDiffuse>::eval, DataStreams.hpp:169-172
+		const float f = MIRT_INV_PI * max_sel(0.0f, Ll.z);
+		rad.x *= alb.x * f; rad.y *= alb.y * f; rad.z *= alb.z * f;
+	}
+	lpdf *= light_selection_pdf;
+	const float brdf_pdf = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, Ll.z);  // DataStreams.hpp:173-176 / :196-198
+	const float w = powerHeuristic_over_f(lpdf, brdf_pdf);
+	rad.x *= w; rad.y *= w; rad.z *= w;
+	if (max_sel(max_sel(rad.x, rad.y), rad.z) <= 0.0f) break;
+	NEE_ACCEPT(Ld, ldist, rad)
+} while (false);

@@ -1,6 +1,6 @@
 // shade_body.inc — the body of k_shade and of its sparse twin (kernels.hpp), included by both with SPARSE a constant: one text, and the kernel
 // without frozen tiles compiles to the instructions it has always had.  SPARSE reads tile_frozen[local tile] (mirt_freeze_tiles).
-// Names it expects in scope: FIRST, GGX, LENS, SPARSE (constants); the arguments of k_shade; tile_frozen (read when SPARSE).  Defines SHADE_HIT_ORIGIN / _ACC / _SEED for shade_hit_body.inc on every inclusion (the same text each time).
+// Names it expects in scope: FIRST, GGX, LENS, SPARSE, RIS (constants); the arguments of k_shade; tile_frozen (read when SPARSE); ris_m (read when RIS).  Defines SHADE_HIT_ORIGIN / _ACC / _SEED for shade_hit_body.inc on every inclusion (the same text each time).
 	const QueueView qin = FIRST ? queue_identity(fp.n_pix * fp.batch_n) : queue_view(in_queue);
 	const uint32_t n = qin.pre[kSegs];
 	const uint32_t n_chunks = (fp.n_pix + kShadeBlock - 1u) / kShadeBlock;      // FIRST

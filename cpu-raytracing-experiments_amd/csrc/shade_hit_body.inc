@@ -5,7 +5,7 @@
 //     test_radiance_in_contrib.py and test_definitions_gpu.py;
 //   * stream_shade_hit (k_tile_stream, exact stream order) — held by tests/test_exact_stream_order.py.
 // The names are k_shade's.  The including scope provides
-//   template parameter  GGX
+//   constants           GGX; RIS (true: the NEE light is picked among ris_m candidates, a uint32_t the scope provides too)
 //   read                sc, fp, s_albedo, s_emission (the material tables in LDS), bounce, gloss_decay, light_selection_pdf,
 //                       pdf_in (out->pdf of the bounce that sampled D, Q8), hrec (HitRec), prim (= hrec.prim), D (f3)
 //   read and written    thr (f3: the closure's estimator, then the roulette's 1 / (1 - q), in place)
@@ -46,43 +46,34 @@ const uint32_t seed = SHADE_HIT_SEED;
 // NEXT EVENT ESTIMATION, Renderer.hpp:247-298
 if (fp.mis) {
 	uint32_t rng = hash_2d(acc, seed + bounce * 2u);
-	const float u0 = rand_unit_float(rng);
-	const float u1 = rand_unit_float(rng);
-	const int32_t selected = static_cast<int32_t>(rand_bounded_int(rng, fp.n_lights));
-	const float4 lp = sc.light_sphere[selected];                    // scene.geometry[lighting_acceleration.prims[selected]]
-	const float4 lem = sc.light_emit[selected];                     // its material's emission, and the prim id
-	const int32_t light_primID = static_cast<int32_t>(__float_as_uint(lem.w));
-	do {
-		if (light_primID == prim) break;                             // Q11: geometry-order id vs BVH-order id
-		f3 Wc{ lp.x - P.x, lp.y - P.y, lp.z - P.z };
-		const float center_dist2 = dot3(Wc, Wc);
-		if (center_dist2 <= lp.w) break;
-		const float center_dist = __builtin_sqrtf(center_dist2);
-		{ const float inv = 1.0f / center_dist; Wc.x *= inv; Wc.y *= inv; Wc.z *= inv; }
-		const float sinThetaMax2 = lp.w / center_dist2;
-		{
-			const float NdotW = (2.0f * T.w) * (Wc.z * T.w + Wc.x * T.y - T.x * Wc.y) - Wc.z;
-			if (NdotW < 0.0f && sinThetaMax2 < NdotW * NdotW) break;
+	if (RIS) {
+		// RIS<count>, Sampling.hpp:25-54: ris_m candidates from the plain draw's own stream, one kept by a weighted reservoir.  A candidate's weight is
+		// the largest channel of its radiance (integrand x MIS weight / source pdf); one that leaves the text early weighs 0 and still counts.
+		// ris_m is a kernel argument: the counter stays scalar and only the body diverges.
+		float weight_sum = 0.0f, w_sel = 0.0f;
+		for (uint32_t cand = 0u; cand < ris_m; cand++) {
+			const float u0 = rand_unit_float(rng);
+			const float u1 = rand_unit_float(rng);
+			const int32_t selected = static_cast<int32_t>(rand_bounded_int(rng, fp.n_lights));
+			const float r = rand_unit_float(rng);                      // Reservoir::Update's draw, taken for every candidate
+#define NEE_ACCEPT(Ld, ldist, rad) { const float w = max_sel(max_sel(rad.x, rad.y), rad.z); weight_sum += w; \
+			if (weight_sum == w || r < w / weight_sum) { w_sel = w; L = Ld; light_distance = ldist; srad = rad; } }   /* w > 0 here: the text left on w <= 0; the first positive candidate is taken whatever r (rand_unit_float reaches 1.0f) */
+#include "nee_sample_body.inc"
+#undef NEE_ACCEPT
 		}
-		float ldist, lpdf;
-		const f3 Ld = sample_direction_to_sphere(Wc, sinThetaMax2, center_dist, lp.w, u0, u1, ldist, lpdf);
-		const f3 Ll = to_local(T, Ld);
-		if (Ll.z < 0.0f) break;
-		f3 rad{ lem.x * thr.x, lem.y * thr.y, lem.z * thr.z };
-		if (GGX) {  // Closure<GGX>::eval, DataStreams.hpp:189-195
-			const f3 f = ggx_eval(F0, alpha, Ll, Vl);
-			rad.x *= f.x; rad.y *= f.y; rad.z *= f.z;
-		} else {    // Closure<LambertianDiffuse>::eval, DataStreams.hpp:169-172
-			const float f = MIRT_INV_PI * max_sel(0.0f, Ll.z);
-			rad.x *= alb.x * f; rad.y *= alb.y * f; rad.z *= alb.z * f;
+		if (w_sel > 0.0f) {
+			has_shadow = true;
+			const float k = weight_sum / (static_cast<float>(ris_m) * w_sel);      // one candidate: w / (1 * w) = 1, the plain draw word for word
+			srad = { srad.x * k, srad.y * k, srad.z * k };
 		}
-		lpdf *= light_selection_pdf;
-		const float brdf_pdf = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, Ll.z);  // DataStreams.hpp:173-176 / :196-198
-		const float w = powerHeuristic_over_f(lpdf, brdf_pdf);
-		rad.x *= w; rad.y *= w; rad.z *= w;
-		if (max_sel(max_sel(rad.x, rad.y), rad.z) <= 0.0f) break;
-		has_shadow = true; L = Ld; light_distance = ldist; srad = rad;
-	} while (false);
+	} else {
+		const float u0 = rand_unit_float(rng);
+		const float u1 = rand_unit_float(rng);
+		const int32_t selected = static_cast<int32_t>(rand_bounded_int(rng, fp.n_lights));
+#define NEE_ACCEPT(Ld, ldist, rad) has_shadow = true; L = Ld; light_distance = ldist; srad = rad;
+#include "nee_sample_body.inc"
+#undef NEE_ACCEPT
+	}
 }
 // EMISSIVE PRIMITIVE HIT, Renderer.hpp:319-353
 has_E = is_emissive;

@@ -190,6 +190,25 @@ int mirt_set_gloss_decay(mirt_ctx* ctx, const float* decay, uint32_t n);
 int mirt_set_stream_order(mirt_ctx* ctx, uint32_t exact);
 int mirt_get_stream_order(const mirt_ctx* ctx, uint32_t* exact);
 
+/* ---- the NEE light by resampled importance sampling ------------------------------------------------------------------------
+ * Next event estimation draws ONE light per hit, uniformly (Renderer.hpp:259; its author's note at :260 asks for something better), and with many
+ * lights most draws are wasted: below the horizon, behind the surface, too far.  The reference ships RIS<count> and Reservoir::Update
+ * (Sampling.hpp:25-54) and never calls them.  candidates = M > 0: per hit, M candidates are drawn from the NEE stream exactly as the plain
+ * draw is (u0, u1, light; the stream just continues), each is carried to its MIS-weighted radiance rad_i by the unchanged NEE text, its weight is
+ * w_i = max(rad_i.rgb) (0 if it left the text early; it still counts), and a weighted reservoir keeps one (one more draw per candidate:
+ * replace when w_i > 0 and r < w_i / sum; the first candidate with w_i > 0 is taken whatever r, because the generator's r reaches 1.0f).  Still ONE shadow ray per hit, carrying rad_sel * (sum / (M * w_sel)); none if every w_i = 0.
+ * Every candidate is distributed as the plain draw, so the estimator's expectation is exactly the plain path's: only the variance changes,
+ * and the accumulator is NOT reset.  The emissive-hit MIS weight, the closure sample and the roulette are untouched: `rays` and `terminated`
+ * do not change, `shadow_rays` does.  M = 1 is the plain path word for word (the one candidate is taken, sum / (1 * w) = 1), computed by the
+ * RIS kernels.
+ * candidates = 0 (the default): off — the same device code as a context that never called this.  1 .. MIRT_MAX_LIGHT_RIS: on.  Above:
+ * MIRT_ERR_ARG.  Accepted and without effect with policy.mis = 0 or a scene without lights.  Not available in exact stream order (that mode
+ * replays the reference): candidates > 0 under stream order 1, and mirt_set_stream_order(ctx, 1) with candidates > 0, return MIRT_ERR_STATE.
+ * Deferred mirt_accumulate_async calls are launched first, under the old setting; the camera-ray candidate lists stay valid. */
+#define MIRT_MAX_LIGHT_RIS 32u
+int mirt_set_light_ris(mirt_ctx* ctx, uint32_t candidates);
+int mirt_get_light_ris(const mirt_ctx* ctx, uint32_t* candidates);
+
 /* Renderer::Resize, Renderer.hpp:53-63: h_tiles = w/16, v_tiles = h/16 (truncating), allocates and zeroes
  * the accumulator, accumulations = 0.  Owns all tiles until mirt_set_tile_range says otherwise. */
 int mirt_resize(mirt_ctx* ctx, uint32_t width, uint32_t height);
@@ -402,6 +421,7 @@ int mirt_group_set_scene(mirt_group* group,
                          const float ambient_color[3], const float* hdri_rgba, uint32_t hdri_w, uint32_t hdri_h);
 int mirt_group_set_camera(mirt_group* group, const float pos[3], const float orient_xyzw[4], float half_width, float half_height, float z, float exposure);
 int mirt_group_set_lens(mirt_group* group, float aperture_radius, float focus_depth);   /* mirt_set_lens on every member */
+int mirt_group_set_light_ris(mirt_group* group, uint32_t candidates);             /* mirt_set_light_ris on every member */
 int mirt_group_pick_focus(mirt_group* group, uint32_t x, uint32_t y, float* distance, float* depth);   /* mirt_pick_focus on the first member */
 int mirt_group_set_policy(mirt_group* group, const mirt_policy* policy);
 int mirt_group_set_gloss_decay(mirt_group* group, const float* decay, uint32_t n);
