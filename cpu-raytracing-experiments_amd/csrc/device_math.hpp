@@ -257,9 +257,10 @@ MIRT_HDI f3 camera_ray_dir(const CameraParams& c, int32_t x, int32_t y, float s0
 
 // ---- thin lens ------------------------------------------------------------------------------------------
 // The reference's camera carries focus_distance / f_number / aperture_radius (Camera.hpp:6-45) and generate_ray ignores them
-// (Camera.hpp:80-88): it defines no lens, so nothing here can be held to the oracle.  The lens ray is DERIVED from the
-// unchanged pinhole direction d = camera_ray_dir(...), whose arithmetic stays the oracle's, and is pinned by a numpy twin that restates the
-// operation order below, by float64 definitions and by invariances (tests/lens_twin.py).
+// (Camera.hpp:80-88): it defines no lens, so the oracle has no reference text to restate here.  The lens ray is DERIVED from the
+// unchanged pinhole direction d = camera_ray_dir(...), whose arithmetic stays the reference's; the oracle carries a CPU twin of the operation order
+// below (orc_set_lens), pinned bit for bit to the numpy twin and through it to float64 definitions, and every LENS kernel is held to that oracle
+// word for word over the whole path (tests/lens_twin.py, tests/test_lens_gpu.py).
 // Camera axes: the camera's +x, +y and -z rotated by view.orient — glm operator*(quat, vec3) as camera_ray_dir spells it; evaluated once on the
 // host when the lens or the camera is set.
 MIRT_HDI f3 camera_axis(const float orient[4], f3 v) {

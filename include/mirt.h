@@ -156,7 +156,7 @@ int mirt_set_camera(mirt_ctx* ctx, const float pos[3], const float orient_xyzw[4
 /* ---- thin lens: depth of field and focus picking ------------------------------------------------------------------------
  * The reference's camera carries focus_distance, f_number and aperture_radius (Camera.hpp:6-45), its UI edits them (Application.cpp:413-417) and
  * a right-click picks the focus distance (Application.cpp:271-304), but generate_ray ignores all of it (Camera.hpp:80-88): the reference defines
- * no lens, so this mode has no oracle.  Here: a thin lens of radius aperture_radius around view.pos in the camera's x/y plane, focused on the
+ * no lens, so this mode has no reference text behind it (the test oracle carries the project's own: DESIGN.md section 2).  Here: a thin lens of radius aperture_radius around view.pos in the camera's x/y plane, focused on the
  * plane perpendicular to the optical axis at axial depth focus_depth, both in WORLD units (hosts convert the reference's millimetres; see
  * mirt_host.hpp / scene.py `unit_mm`).  Per sample: the pinhole direction d of Camera::generate_ray, unchanged; a lens point from two draws at the
  * seed offset the reference reserves and never uses (2 * max_bounces, Renderer.hpp:107) through its own disk mapping (Sampling.hpp:85-104);

@@ -1037,6 +1037,8 @@ struct Oracle {
 	int threads = 0;
 	int brdf = 0;                         // Renderer.hpp:70 `#define BRDF`: 0 Closure<LambertianDiffuse>, 1 Closure<GGX>
 	std::vector<float> gloss_decay;       // gloss_decay_table by bounce (named at Renderer.hpp:212, never declared); entries beyond its length are 0
+	uint32_t light_ris = 0;               // orc_set_light_ris: 0 = the reference's one light sample; 1..32 = candidates of the project's RIS (below)
+	float lens_aperture = 0.0f, lens_focus_depth = 0.0f;   // orc_set_lens: aperture 0 = the reference's pinhole camera
 	std::vector<float> accumulator;       // [tile][bucket][channel][256]  (Renderer.hpp:43-46)
 	std::vector<uint32_t> tile_list;      // orc_set_tile_list: only these LaunchIndices are rendered (full-size spot checks); slab j = tile_list[j]
 	Counters counters;
@@ -1093,8 +1095,30 @@ static size_t sort_rayID(uint32_t k, uint32_t count, uint32_t* out, const int32_
 }
 
 // Debug hook (orc_debug_path): records, for one pixel of one tile, the ray and its hit at every bounce.
-struct PathDebug { bool on = false; uint32_t px = 0; int n = 0; float rec[64][8]; };
+// With light RIS it also records every candidate of that pixel: bounce, candidate, the reservoir draw r, the weight w (0: left early).
+struct PathDebug { bool on = false; uint32_t px = 0; int n = 0; float rec[64][8]; int n_cand = 0; float cand[256][4]; };
 static thread_local PathDebug g_dbg;
+
+// THE PROJECT'S OWN DEFINITION, not a restatement of the reference (Camera.hpp:80-88 ignores its lens fields): the thin-lens
+// ray of csrc/device_math.hpp lens_ray, derived from the pinhole direction d of generate_ray_dir.  Binary32, one rounding per operation
+// (-ffp-contract=off), spelled as tests/lens_twin.py's docstring spells it:
+//   rng = hash_2d(acc, seed + 2 * max_bounces);  u0, u1 = rand_unit_float twice;  (lx, ly) = disk(u0, u1)
+//   t = focus_depth / dot3(d, fwd);  P = pos + d * t;  ax = A * lx;  ay = A * ly;  O = pos + (right * ax + up * ay);  D = normalize3(P - O)
+// right / up / fwd = the camera's +x, +y, -z under quat_rotate, the same formula generate_ray_dir rotates with.
+static inline void lens_ray(const Oracle& o, v3 d, uint32_t accumulations, uint32_t seed, v3* O, v3* D) {
+	const v3 right = quat_rotate(o.camera.orient, v3{ 1.0f, 0.0f, 0.0f }), up = quat_rotate(o.camera.orient, v3{ 0.0f, 1.0f, 0.0f });
+	const v3 fwd = quat_rotate(o.camera.orient, v3{ 0.0f, 0.0f, -1.0f });
+	uint32_t rng = hash_2d(accumulations, seed + 2u * o.max_bounces);
+	const float u0 = rand_unit_float(&rng);
+	const float u1 = rand_unit_float(&rng);
+	float lx, ly; disk(u0, u1, &lx, &ly);
+	const float t = o.lens_focus_depth / dot3(d, fwd);
+	const v3 pos = o.camera.pos;
+	const v3 P{ pos.x + d.x * t, pos.y + d.y * t, pos.z + d.z * t };
+	const float ax = o.lens_aperture * lx, ay = o.lens_aperture * ly;
+	*O = v3{ pos.x + (right.x * ax + up.x * ay), pos.y + (right.y * ax + up.y * ay), pos.z + (right.z * ax + up.z * ay) };
+	*D = normalize3(v3{ P.x - O->x, P.y - O->y, P.z - O->z });
+}
 
 // Renderer.hpp:83-432 — one tile, one Accumulate() call, with the closure the reference selects at compile time (Renderer.hpp:70)
 template <bool GGX>
@@ -1130,8 +1154,10 @@ static void accumulate_tile_closure(const Oracle& o, uint32_t LaunchIndex, size_
 		uint32_t rng_state = hash_2d(accumulations, ray_stream.seed[ID]);
 		float cs[2]; cs[0] = rand_unit_float(&rng_state); cs[1] = rand_unit_float(&rng_state);
 		v3 dir = generate_ray_dir(o.camera, x, y, cs);
+		v3 origin = o.camera.pos;
+		if (o.lens_aperture > 0.0f) lens_ray(o, dir, accumulations, ray_stream.seed[ID], &origin, &dir);   // the project's lens; 0 = the line above alone
 		in->dir.x[ID] = dir.x; in->dir.y[ID] = dir.y; in->dir.z[ID] = dir.z;
-		in->p.x[ID] = o.camera.pos.x; in->p.y[ID] = o.camera.pos.y; in->p.z[ID] = o.camera.pos.z;
+		in->p.x[ID] = origin.x; in->p.y[ID] = origin.y; in->p.z[ID] = origin.z;
 	}
 	size_t active_rays = N;
 	for (size_t bounce = 0; bounce < o.max_bounces && active_rays > 0; bounce++, std::swap(in, outb)) {   // :131
@@ -1188,31 +1214,29 @@ static void accumulate_tile_closure(const Oracle& o, uint32_t LaunchIndex, size_
 		if (MIS && !skip_dropped_nee) {                                          // :247-315
 			size_t shadow_index = 0;
 			ShadowStream& sh = ray_stream.shadow_rays;
-			for (size_t i = 0; i < hit_count; i++) {
-				const int32_t ID = static_cast<int32_t>(ray_stream.RayID[miss_count + i]);
-				uint32_t rng_state = hash_2d(accumulations, ray_stream.seed[in->pixelID[ID]] + static_cast<uint32_t>(bounce) * 2);
-				float ls[2]; ls[0] = rand_unit_float(&rng_state); ls[1] = rand_unit_float(&rng_state);
-				int32_t selected_light = static_cast<int32_t>(rand_bounded_int(&rng_state, light_count));
+			// The light sample of one hit, Renderer.hpp:261-296: ONE text for the plain draw and for every RIS candidate (as csrc/nee_sample_body.inc
+			// is on the device).  false: the sample left early and weighs nothing; true: direction, distance and MIS-weighted radiance of its shadow ray.
+			auto light_sample = [&](int32_t ID, int32_t selected_light, float u0, float u1, v3& L, float& light_distance, v3& radiance) -> bool {
 				int32_t light_primID = o.lights[selected_light];
 				const Sphere& light_prim = o.geometry[light_primID];
-				if (light_primID == ray_stream.hit.primID[ID]) continue;          // Q11: geometry-order vs BVH-order index
+				if (light_primID == ray_stream.hit.primID[ID]) return false;          // Q11: geometry-order vs BVH-order index
 				v3 Wc{ light_prim.px - sd.P.x[ID], light_prim.py - sd.P.y[ID], light_prim.pz - sd.P.z[ID] };
 				float center_dist2 = dot3(Wc, Wc);
-				if (center_dist2 <= light_prim.radius_sq) continue;
+				if (center_dist2 <= light_prim.radius_sq) return false;
 				float center_dist = sqrtf(center_dist2);
 				{ float inv = 1.0f / center_dist; Wc.x *= inv; Wc.y *= inv; Wc.z *= inv; }
 				float sinThetaMax2 = light_prim.radius_sq / center_dist2;
 				{
 					float NdotW = (2.0f * sd.T.w[ID]) * (Wc.z * sd.T.w[ID] + Wc.x * sd.T.y[ID] - sd.T.x[ID] * Wc.y) - Wc.z;
-					if (NdotW < 0.0f && sinThetaMax2 < NdotW * NdotW) continue;
+					if (NdotW < 0.0f && sinThetaMax2 < NdotW * NdotW) return false;
 				}
-				float light_distance, light_pdf;
-				v3 L = sample_direction_to_sphere(Wc, sinThetaMax2, center_dist, light_prim.radius_sq, ls[0], ls[1], &light_distance, &light_pdf);
+				float light_pdf;
+				L = sample_direction_to_sphere(Wc, sinThetaMax2, center_dist, light_prim.radius_sq, u0, u1, &light_distance, &light_pdf);
 				q4 T{ sd.T.x[ID], sd.T.y[ID], sd.T.z[ID], sd.T.w[ID] };
 				v3 Llocal = to_local(T, L);
-				if (Llocal.z < 0.0f) continue;
+				if (Llocal.z < 0.0f) return false;
 				const Material& lm = o.material[light_prim.material_ID];
-				v3 radiance{ lm.emission[0] * in->throughput.r[ID], lm.emission[1] * in->throughput.g[ID], lm.emission[2] * in->throughput.b[ID] };
+				radiance = v3{ lm.emission[0] * in->throughput.r[ID], lm.emission[1] * in->throughput.g[ID], lm.emission[2] * in->throughput.b[ID] };
 				float brdf_pdf;
 				if (GGX) {                                                       // Closure<GGX>::eval / pdf, DataStreams.hpp:189-198
 					const v3 f = ggx_eval(v3{ sd.F0[ID][0], sd.F0[ID][1], sd.F0[ID][2] }, sd.alpha[ID], Llocal, v3{ sd.V.x[ID], sd.V.y[ID], sd.V.z[ID] });
@@ -1227,7 +1251,45 @@ static void accumulate_tile_closure(const Oracle& o, uint32_t LaunchIndex, size_
 				light_pdf *= light_selection_pdf;
 				float w = powerHeuristic_over_f(light_pdf, brdf_pdf);
 				radiance.x *= w; radiance.y *= w; radiance.z *= w;
-				if (std_max(std_max(radiance.x, radiance.y), radiance.z) <= 0.0f) continue;
+				if (std_max(std_max(radiance.x, radiance.y), radiance.z) <= 0.0f) return false;
+				return true;
+			};
+			for (size_t i = 0; i < hit_count; i++) {
+				const int32_t ID = static_cast<int32_t>(ray_stream.RayID[miss_count + i]);
+				uint32_t rng_state = hash_2d(accumulations, ray_stream.seed[in->pixelID[ID]] + static_cast<uint32_t>(bounce) * 2);
+				v3 L{ 0.0f, 0.0f, 0.0f }, radiance{ 0.0f, 0.0f, 0.0f }; float light_distance = 0.0f;
+				if (o.light_ris == 0) {
+					float ls[2]; ls[0] = rand_unit_float(&rng_state); ls[1] = rand_unit_float(&rng_state);
+					int32_t selected_light = static_cast<int32_t>(rand_bounded_int(&rng_state, light_count));
+					if (!light_sample(ID, selected_light, ls[0], ls[1], L, light_distance, radiance)) continue;
+				} else {
+					// THE PROJECT'S OWN DEFINITION, not a line-cited restatement of the reference:
+					// DESIGN.md "NEE light by resampled importance sampling", Estimator and Anchor; the device text is csrc/shade_hit_body.inc.
+					// M candidates continue the plain draw's generator; each draws u0, u1, the light and the reservoir's r, in that order, whether or
+					// not it survives.  Binary32 weighted reservoir: w = max(rad.rgb); weight_sum += w; take it when weight_sum == w (the first
+					// positive one, whatever r: rand_unit_float reaches 1.0f) or r < w / weight_sum; the kept radiance is scaled by
+					// weight_sum / (float(M) * w_sel).  Nothing kept: no shadow ray.
+					float weight_sum = 0.0f, w_sel = 0.0f;
+					for (uint32_t cand = 0; cand < o.light_ris; cand++) {
+						const float u0 = rand_unit_float(&rng_state);
+						const float u1 = rand_unit_float(&rng_state);
+						const int32_t selected_light = static_cast<int32_t>(rand_bounded_int(&rng_state, light_count));
+						const float r = rand_unit_float(&rng_state);
+						v3 Lc{ 0.0f, 0.0f, 0.0f }, rc{ 0.0f, 0.0f, 0.0f }; float dc = 0.0f, w = 0.0f;
+						if (light_sample(ID, selected_light, u0, u1, Lc, dc, rc)) {
+							w = std_max(std_max(rc.x, rc.y), rc.z);
+							weight_sum += w;
+							if (weight_sum == w || r < w / weight_sum) { w_sel = w; L = Lc; light_distance = dc; radiance = rc; }
+						}
+						if (g_dbg.on && in->pixelID[ID] == g_dbg.px && g_dbg.n_cand < 256) {
+							float* c = g_dbg.cand[g_dbg.n_cand++];
+							c[0] = static_cast<float>(bounce); c[1] = static_cast<float>(cand); c[2] = r; c[3] = w;
+						}
+					}
+					if (!(w_sel > 0.0f)) continue;
+					const float k = weight_sum / (static_cast<float>(o.light_ris) * w_sel);
+					radiance = v3{ radiance.x * k, radiance.y * k, radiance.z * k };
+				}
 				sh.dir.x[shadow_index] = L.x; sh.dir.y[shadow_index] = L.y; sh.dir.z[shadow_index] = L.z;
 				sh.p.x[shadow_index] = sd.P.x[ID]; sh.p.y[shadow_index] = sd.P.y[ID]; sh.p.z[shadow_index] = sd.P.z[ID];
 				sh.tfar[shadow_index] = light_distance;
@@ -1502,6 +1564,29 @@ int orc_set_brdf(void* h, int brdf, const float* decay, uint32_t n) {
 	if (decay && n) o.gloss_decay.assign(decay, decay + n); else o.gloss_decay.clear();
 	return 0;
 }
+// Candidates of the NEE light's resampled importance sampling in every later Accumulate(): 0 = the reference's one light sample (the old code path),
+// 1..32 as mirt_set_light_ris.  The accumulator is left alone.
+int orc_set_light_ris(void* h, uint32_t candidates) {
+	if (!h || candidates > 32u) return -1;
+	static_cast<Oracle*>(h)->light_ris = candidates;
+	return 0;
+}
+// Thin lens of every later Accumulate() and orc_raygen, refused as mirt_set_lens refuses: aperture 0 = the pinhole camera (focus_depth then unused).
+int orc_set_lens(void* h, float aperture, float focus_depth) {
+	if (!h || !std::isfinite(aperture) || !std::isfinite(focus_depth) || aperture < 0.0f) return -1;
+	if (aperture > 0.0f && !(focus_depth > 0.0f)) return -1;
+	Oracle& o = *static_cast<Oracle*>(h);
+	o.lens_aperture = aperture; o.lens_focus_depth = focus_depth;
+	return 0;
+}
+// Companion of mirt_load_accumulator: overwrite the slab and continue from `accumulations` (the next Accumulate() is number accumulations + 1).
+int orc_load_accumulator(void* h, const float* src, uint32_t accumulations) {
+	if (!h || !src) return -1;
+	Oracle& o = *static_cast<Oracle*>(h);
+	memcpy(o.accumulator.data(), src, o.accumulator.size() * 4);
+	o.accumulations = accumulations;
+	return 0;
+}
 void orc_accumulate(void* h, uint32_t n_calls) { Oracle& o = *static_cast<Oracle*>(h); for (uint32_t i = 0; i < n_calls; i++) accumulate(o); }
 uint32_t orc_accumulations(void* h) { return static_cast<Oracle*>(h)->accumulations; }
 size_t orc_accumulator_floats(void* h) { return static_cast<Oracle*>(h)->accumulator.size(); }
@@ -1527,7 +1612,9 @@ void orc_raygen(void* h, uint32_t accumulations, float* p_xyz /*3 planes*/, floa
 		uint32_t rng = hash_2d(accumulations, seed);
 		float cs[2]; cs[0] = rand_unit_float(&rng); cs[1] = rand_unit_float(&rng);
 		v3 d = generate_ray_dir(o.camera, x, y, cs);
-		p_xyz[g] = o.camera.pos.x; p_xyz[n + g] = o.camera.pos.y; p_xyz[2 * n + g] = o.camera.pos.z;
+		v3 origin = o.camera.pos;
+		if (o.lens_aperture > 0.0f) lens_ray(o, d, accumulations, seed, &origin, &d);
+		p_xyz[g] = origin.x; p_xyz[n + g] = origin.y; p_xyz[2 * n + g] = origin.z;
 		dir_xyz[g] = d.x; dir_xyz[n + g] = d.y; dir_xyz[2 * n + g] = d.z;
 	}
 }
@@ -1564,11 +1651,20 @@ int orc_debug_path(void* h, uint32_t LaunchIndex, uint32_t px, uint32_t accumula
 	Oracle& o = *static_cast<Oracle*>(h);
 	std::vector<float> scratch(o.accumulator.size(), 0.0f);
 	LocalCounters lc;
-	g_dbg.on = true; g_dbg.px = px; g_dbg.n = 0;
+	g_dbg.on = true; g_dbg.px = px; g_dbg.n = 0; g_dbg.n_cand = 0;
 	accumulate_tile(o, LaunchIndex, LaunchIndex, accumulations, scratch.data(), lc);
 	g_dbg.on = false;
 	memcpy(out, g_dbg.rec, sizeof(float) * 8 * g_dbg.n);
 	return g_dbg.n;
+}
+
+// The RIS candidates of the same pixel and call (orc_set_light_ris above 0): out[i*4..] = bounce, candidate, reservoir draw r, weight w (0: it left early).
+int orc_debug_candidates(void* h, uint32_t LaunchIndex, uint32_t px, uint32_t accumulations, float* out, int max_records) {
+	float path[64 * 8];
+	orc_debug_path(h, LaunchIndex, px, accumulations, path);
+	const int n = g_dbg.n_cand < max_records ? g_dbg.n_cand : max_records;
+	memcpy(out, g_dbg.cand, sizeof(float) * 4 * n);
+	return n;
 }
 
 // ---- unit functions (KATs / per-function fixtures) -------------------------------------

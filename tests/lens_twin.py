@@ -1,6 +1,8 @@
 """numpy twin of the thin-lens camera ray (csrc/device_math.hpp lens_ray) and the float64 thin-lens definition it is held to.
 
-The reference defines no lens (Camera.hpp:80-88 ignores focus_distance / f_number), so the oracle cannot pin this mode.
+The reference defines no lens (Camera.hpp:80-88 ignores focus_distance / f_number), so there is no reference text behind this mode.
+The oracle carries the project's own lens all the same (orc_set_lens: the operation order below in C++, as it carries mode 2 and the caller's
+gloss_decay); tests/test_lens_cpu.py holds Oracle.raygen under a lens to this twin bit for bit, and the twin to the float64 thin lens.
 The twin starts from the oracle's own pinhole rays (Oracle.raygen: the unchanged arithmetic of Camera::generate_ray) and restates, in
 binary32 array arithmetic with one rounding per operation, exactly what lens_ray does after them:
 

@@ -51,6 +51,10 @@ def load():
     lib.orc_set_exact_tail.argtypes = [i32]
     lib.orc_reset.argtypes = [vp]
     lib.orc_set_brdf.argtypes = [vp, i32, vp, u32]
+    lib.orc_set_light_ris.argtypes = [vp, u32]
+    lib.orc_set_lens.argtypes = [vp, f, f]
+    lib.orc_load_accumulator.argtypes = [vp, vp, u32]
+    lib.orc_debug_candidates.argtypes = [vp, u32, u32, u32, vp, i32]
     lib.orc_accumulate.argtypes = [vp, u32]
     lib.orc_debug_path.argtypes = [vp, u32, u32, u32, vp]
     lib.orc_accumulations.argtypes = [vp]; lib.orc_accumulations.restype = u32
@@ -102,9 +106,10 @@ COUNTER_NAMES = ("rays", "shadow_rays", "nodes", "spheres", "shadow_nodes", "sha
 
 class Oracle:
     """The reference path on the CPU: same call protocol as the product's Renderer.  `brdf` is the reference's `#define BRDF`
-    (Renderer.hpp:70): 0 Closure<LambertianDiffuse>, 1 Closure<GGX> with the gloss decay table `gloss_decay`."""
+    (Renderer.hpp:70): 0 Closure<LambertianDiffuse>, 1 Closure<GGX> with the gloss decay table `gloss_decay`.  `light_ris` (candidates, 0 = off) and
+    `lens` ((aperture, focus_depth) or None) are the project's own operations, restated in oracle.cpp from DESIGN.md and csrc/device_math.hpp."""
 
-    def __init__(self, scene, max_bounces=16, buckets=5, mis=True, trav_mode=TRAV_BRUTE, threads=0, brdf=0, gloss_decay=None):
+    def __init__(self, scene, max_bounces=16, buckets=5, mis=True, trav_mode=TRAV_BRUTE, threads=0, brdf=0, gloss_decay=None, light_ris=0, lens=None):
         self.lib = load()
         mod = importlib.import_module("cpu-raytracing-experiments_amd.scene")
         self.SPHERE, self.MATERIAL, self.NODE = mod.SPHERE, mod.MATERIAL, mod.NODE
@@ -114,6 +119,9 @@ class Oracle:
         self.width = self.height = 0
         self.brdf = int(brdf)
         self.set_gloss_decay(gloss_decay)
+        self.set_light_ris(light_ris)
+        if lens is not None:
+            self.set_lens(*lens)
         self.update_scene()
 
     def close(self):
@@ -132,6 +140,23 @@ class Oracle:
         d = np.ascontiguousarray([] if decay is None else decay, dtype=np.float32).reshape(-1)
         rc = self.lib.orc_set_brdf(self.h, self.brdf, _p(d) if len(d) else None, len(d))
         assert rc == 0
+
+    def set_light_ris(self, candidates):
+        """Candidates of the NEE light's RIS in every later Accumulate(): 0 = the reference's one light sample, at most 32."""
+        if self.lib.orc_set_light_ris(self.h, int(candidates)) != 0:
+            raise ValueError(f"orc_set_light_ris refuses {candidates} candidates")
+        self.light_ris = int(candidates)
+
+    def set_lens(self, aperture, focus_depth):
+        """Thin lens of every later Accumulate() and raygen(); aperture 0 = the pinhole camera.  Refused as mirt_set_lens refuses."""
+        if self.lib.orc_set_lens(self.h, float(aperture), float(focus_depth)) != 0:
+            raise ValueError(f"orc_set_lens refuses aperture {aperture}, focus depth {focus_depth}")
+
+    def load_accumulator(self, src, accumulations):
+        """Renderer.load_accumulator: overwrite the slab; the next Accumulate() is call number accumulations + 1."""
+        src = np.ascontiguousarray(src, dtype=np.float32)
+        assert src.size == self.lib.orc_accumulator_floats(self.h)
+        assert self.lib.orc_load_accumulator(self.h, _p(src), int(accumulations)) == 0
 
     def update_scene(self):
         s = self.scene
@@ -217,6 +242,12 @@ class Oracle:
         ray origin, ray direction, tfar, primID (as a float).  At most 64 records."""
         out = np.zeros((64, 8), dtype=np.float32)
         n = self.lib.orc_debug_path(self.h, launch_index, px, accumulations, _p(out))
+        return out[:n]
+
+    def debug_candidates(self, launch_index, px, accumulations):
+        """With light_ris on: one record per RIS candidate of that pixel in that call: bounce, candidate, reservoir draw r, weight w (0: it left early)."""
+        out = np.zeros((256, 4), dtype=np.float32)
+        n = self.lib.orc_debug_candidates(self.h, launch_index, px, accumulations, _p(out), 256)
         return out[:n]
 
     def raygen(self, accumulations):

@@ -1,6 +1,7 @@
 """Thin-lens depth of field, the part that needs no device: the interface at every layer, the numpy twin (tests/lens_twin.py) pinned to the
 known answers and golden vectors the oracle tests use, the twin against a float64 thin-lens definition written from the textbook, the seed
-offset of the lens draws, and the host mirror's arithmetic.  The reference defines no lens, so none of this is oracle parity."""
+offset of the lens draws, and the host mirror's arithmetic.  The reference defines no lens; the oracle carries the project's own (orc_set_lens, a
+restatement of device_math.hpp lens_ray), and is held here bit for bit to the twin, which is held to the float64 definition."""
 import ctypes as C
 import inspect
 import math
@@ -13,6 +14,7 @@ import pytest
 import definitions as df
 import lens_twin as lt
 import oracle_binding as ob
+import test_definitions_cpu as cpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -161,6 +163,61 @@ def test_lens_points_are_uniform_over_the_disk(mirt):
     chi2 = float(((cells - n / 256) ** 2 / (n / 256)).sum())
     print(f"lens/disk chi-square = {chi2:.1f}")
     assert chi2 < df.CHI2_255_P1E6
+
+
+# ---- the oracle's lens against the twin -----------------------------------------------------------------------------------------------
+def test_oracle_lens_rays_equal_the_twin(mirt):
+    """Oracle.raygen under orc_set_lens against lens_twin's rays, every word: the views, lenses (smallest and largest aperture included) and
+    accumulation numbers of test_twin_rays_meet_the_float64_thin_lens, and default9 through a turned and rolled camera.  A closed aperture gives the
+    pinhole rays, and so does taking the lens off again."""
+    views = cameras(mirt) + (("turned", cpu.turned_camera_scene(mirt), 16),)
+    assert min(a for a, _ in LENSES) == 0.004 and max(a for a, _ in LENSES) == 0.25
+    for name, sc, mb in views:
+        pin = ob.Oracle(sc, max_bounces=mb); pin.Resize(64, 64)
+        o = ob.Oracle(sc, max_bounces=mb); o.Resize(64, 64)
+        for A, fd in LENSES:
+            o.set_lens(A, fd)
+            for acc in (1, 2, 7):
+                O, D = lt.oracle_lens_rays(pin, acc, A, fd)
+                p, d = o.raygen(acc)
+                assert np.array_equal(p.view(np.uint32), O.view(np.uint32)), (name, A, fd, acc, "origins")
+                assert np.array_equal(d.view(np.uint32), D.view(np.uint32)), (name, A, fd, acc, "directions")
+        assert len(np.unique(p.view(np.uint32)[0])) > 1000
+        for A, fd in ((0.0, 123.0), (0.0, 0.0)):
+            o.set_lens(A, fd)
+            for got, want in zip(o.raygen(3), pin.raygen(3)):
+                assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (name, "closed aperture")
+        o.close(); pin.close()
+
+
+def test_oracle_closed_aperture_is_the_pinhole_path_and_the_lens_is_not(mirt):
+    """Accumulator, frame and counters: aperture 0 is the pinhole code; an open one moves the words, and the twin's traversal (mode 2) still gives the
+    brute-force words from off-centre origins."""
+    sc = mirt.scene.default9()
+    def state(**kw):
+        o = ob.Oracle(sc, max_bounces=5, **kw); o.Resize(64, 64); o.Accumulate(5)
+        out = (o.accumulator(), o.Render(), o.counters()); o.close()
+        return out
+    want, closed, lens, lens2 = state(), state(lens=(0.0, 7.0)), state(lens=(0.05, 1.5)), state(lens=(0.05, 1.5), trav_mode=ob.TRAV_PER_RAY_BVH)
+    assert np.array_equal(closed[0].view(np.uint32), want[0].view(np.uint32)) and np.array_equal(closed[1].view(np.uint32), want[1].view(np.uint32)) and closed[2] == want[2]
+    assert (lens[0].view(np.uint32) != want[0].view(np.uint32)).any()
+    assert np.array_equal(lens2[0].view(np.uint32), lens[0].view(np.uint32)) and np.array_equal(lens2[1].view(np.uint32), lens[1].view(np.uint32))
+
+
+def test_oracle_lens_refusals(mirt, oracle_lib):
+    """orc_set_lens refuses what mirt_set_lens refuses (tests/test_lens_gpu.py test_lens_refusals) and leaves the lens as it was."""
+    assert oracle_lib.orc_set_lens(None, 0.1, 1.0) == -1
+    o = ob.Oracle(mirt.scene.default9()); o.Resize(16, 16)
+    o.set_lens(0.05, 1.5)
+    before = o.raygen(1)
+    for a, d in ((-0.1, 1.0), (0.1, 0.0), (0.1, -2.0), (math.nan, 1.0), (0.1, math.nan), (math.inf, 1.0), (0.1, math.inf), (0.0, math.inf)):
+        assert oracle_lib.orc_set_lens(o.h, a, d) == -1, (a, d)
+    with pytest.raises(ValueError, match="aperture -0.1"):
+        o.set_lens(-0.1, 1.0)
+    for got, want in zip(o.raygen(1), before):
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert oracle_lib.orc_set_lens(o.h, 0.0, 0.0) == 0 and oracle_lib.orc_set_lens(o.h, 0.0, -3.0) == 0       # a closed aperture asks nothing of the depth
+    o.close()
 
 
 # ---- host mirror ------------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """Thin-lens depth of field on the device (mirt_set_lens, mirt_pick_focus): the LENS kernels against the numpy twin of tests/lens_twin.py on
 the raw words, the pinhole path untouched by a closed aperture, the invariances of the lens-on accumulator, closed forms, the circle of
-confusion and the focus pick.  The reference defines no lens: nothing here is oracle parity."""
+confusion and the focus pick.  The reference defines no lens; the oracle carries the project's (orc_set_lens, held to the twin bit for bit in
+tests/test_lens_cpu.py), and the whole path under a lens - every LENS kernel, with and without light RIS, dense and sparse - is held to it word for
+word here.  The AOVs under a lens keep their own twin."""
 import ctypes as C
 import math
 
@@ -11,6 +13,7 @@ import definitions as df
 import lens_twin as lt
 import oracle_binding as ob
 import test_definitions_cpu as cpu
+import test_light_ris_gpu as rg
 from oracle_binding import bits
 
 pytestmark = pytest.mark.gpu
@@ -202,6 +205,40 @@ def test_lens_ggx_with_decay_does_not_depend_on_traversal(mirt):
     assert np.isfinite(accs[0]).all() and accs[0].max() > 0
 
 
+# ---- the whole path under a lens is the oracle's ----------------------------------------------------------------------------------------------
+GGX_DECAY = [0.0, 0.25, 0.5, 1.0]
+LENS_PATHS = {   # scene, width, height, accumulations, max_bounces, lens, keywords shared with the oracle
+    "S1000": (s1000, 64, 64, 10, 5, (0.15, 25.0), {}),
+    "default9": (lambda m: m.scene.default9(), 96, 64, 5, 16, (0.03, 1.1), {}),
+    "brdf_test_ggx": (lambda m: m.scene.brdf_test(), 96, 64, 5, 16, (0.4, 28.0), dict(brdf=1, gloss_decay=GGX_DECAY)),
+}
+LENS_ROUTES = (("tree", dict(use_bvh=True)), ("brute", dict(use_bvh=False)), ("tree built on the device", dict(use_bvh=True, gpu_build=True)))
+
+
+@pytest.mark.parametrize("candidates", [0, 7])
+@pytest.mark.parametrize("name", list(LENS_PATHS))
+def test_whole_path_under_a_lens_is_the_oracle(mirt, name, candidates):
+    """k_trace<*, LENS> / k_shade<FIRST, GGX, LENS> and, with seven candidates, k_shade_ris<FIRST, GGX, LENS>: accumulator, frame and counters."""
+    make, w, h, n, mb, lens, kw = LENS_PATHS[name]
+    sc = make(mirt)
+    want = rg.oracle_states(sc, (name, "lens", candidates), w, h, (n,), max_bounces=mb, lens=lens, light_ris=candidates, **kw)[n]
+    pinhole = rg.oracle_states(sc, (name, "pinhole", candidates), w, h, (n,), max_bounces=mb, light_ris=candidates, **kw)[n]
+    assert (bits(want["acc"]) != bits(pinhole["acc"])).any()
+    for label, route in LENS_ROUTES:
+        r = mirt.Renderer(sc, max_bounces=mb, buckets=5, light_ris=candidates, **route, **kw); r.Resize(w, h)
+        r.set_lens(*lens); r.Accumulate(n)
+        rg.check_against_oracle(r, want, f"{name} under a lens, M = {candidates}, {label}")
+        r.close()
+
+
+@pytest.mark.parametrize("candidates", [0, 7])
+@pytest.mark.parametrize("name", list(LENS_PATHS))
+def test_sparse_lens_kernels_are_the_oracle(mirt, name, candidates):
+    """k_trace_sparse<*, LENS> and the sparse LENS shading twins: 5 accumulations, every third tile frozen, 5 more."""
+    make, w, h, _, mb, lens, kw = LENS_PATHS[name]
+    rg.check_frozen_against_oracle(mirt, make(mirt), (name, "lens", candidates), w, h, LENS_ROUTES, max_bounces=mb, lens=lens, light_ris=candidates, **kw)
+
+
 # ---- closed forms ----------------------------------------------------------------------------------------------------------------------
 def test_white_furnace_under_a_lens_is_exactly_one(mirt):
     for kw in (dict(use_bvh=False), dict(use_bvh=True)):
@@ -209,7 +246,11 @@ def test_white_furnace_under_a_lens_is_exactly_one(mirt):
         r.set_lens(0.2, 2.0); r.Accumulate(5)
         acc = r.accumulator()
         assert (bits(acc) == bits(f32(1.0))).all(), kw
-        r.close()
+        o = ob.Oracle(mirt.scene.white_furnace(), lens=(0.2, 2.0)); o.Resize(32, 32); o.Accumulate(5)
+        assert_same(acc, o.accumulator(), f"white furnace under a lens against the oracle, {kw}")
+        assert r.Render(); assert_same(r.GetFrame(), o.Render(), f"white furnace under a lens, frame, {kw}")
+        assert r.counters()["rays"] == o.counters()["rays"] and r.counters()["terminated"] == o.counters()["terminated"]
+        o.close(); r.close()
 
 
 class LensBackend:

@@ -1,6 +1,8 @@
 """Resampled importance sampling of the NEE light (mirt_set_light_ris), the side that needs no GPU: the float64 estimator of
 tests/ris_definitions.py against the quadrature of definitions.direct_lambert on part F's frame-filling sphere, the guards that make the
-GPU test a test, the figures it reads from tests/golden/light_ris_many.npz, and the C interface's symbols and refusals.
+GPU test a test, the figures it reads from tests/golden/light_ris_many.npz, and the C interface's symbols and refusals.  The oracle's
+candidate loop (orc_set_light_ris, the reference every RIS kernel is held to word for word by tests/test_light_ris_gpu.py) is held here to
+the same float64 estimator, to its own plain draw at one candidate, to a GGX expectation and to the reservoir draw that is exactly 1.0f.
 
 MANY: HIGH and SIDE (F2) and fourteen further lights placed like BELOW - wholly below the horizon of every visible point, so a uniform
 draw among the sixteen is wasted seven times out of eight.  Measured figures: DESIGN.md, "NEE light by resampled importance sampling"."""
@@ -12,9 +14,12 @@ import numpy as np
 import pytest
 
 import definitions as df
+import lens_twin as lt
+import oracle_binding as ob
 import ris_definitions as rd
 import test_definitions_cpu as cpu
-from test_definitions_cpu import F_CASES, F_H, F_RHO, F_W, HIGH, SIDE, SIGMA, df_lights, f_expectation, f_regions, footprint_points, report
+from test_definitions_cpu import (F_CASES, F_H, F_RHO, F_W, HIGH, SIDE, SIGMA, backend_image, df_lights, f_expectation, f_regions, footprint_points,
+                                  guard_first_hits, lit_scene, report)
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "light_ris_many.npz")
 
@@ -227,6 +232,192 @@ def test_golden_figures_are_the_samplers():
     assert abs(float(g["var_ratio"]) / float(want["var_ratio"]) - 1.0) <= 1e-9
     assert g["shadow_probability"].dtype == np.float64 and np.abs(g["shadow_probability"] - want["shadow_probability"]).max() <= 1e-12
     assert int(g["candidates"]) == 8
+
+
+# ---- the oracle's candidate loop ---------------------------------------------------------------------------------------------------
+DECAY = [0.0, 0.3, 0.6, 0.8]
+ANCHOR_CASES = {   # scene, width, height, oracle keywords
+    "default9": (lambda m: m.scene.default9(), 96, 64, {}),
+    "S1000": (lambda m: m.scene.synthetic(1000), 64, 64, {}),
+    "brdf_test": (lambda m: m.scene.brdf_test(), 96, 64, {}),
+    "default9_ggx": (lambda m: m.scene.default9(), 96, 64, dict(brdf=1, gloss_decay=DECAY)),
+}
+
+
+def oracle_state(sc, w, h, n_acc, **kw):
+    o = ob.Oracle(sc, **{"max_bounces": 16, "buckets": 5, **kw})
+    o.Resize(w, h); o.Accumulate(n_acc)
+    out = dict(acc=o.accumulator(), frame=o.Render(), counters=o.counters())
+    o.close()
+    return out
+
+
+def same_state(a, b, what):
+    assert np.array_equal(ob.bits(a["acc"]), ob.bits(b["acc"])), f"{what}: accumulator"
+    assert np.array_equal(ob.bits(a["frame"]), ob.bits(b["frame"])), f"{what}: frame"
+    assert a["counters"] == b["counters"], f"{what}: counters"
+
+
+@pytest.mark.parametrize("name", list(ANCHOR_CASES))
+def test_oracle_one_candidate_is_the_plain_draw(mirt, name):
+    """Anchor: the candidate loop with M = 1 leaves every word and every counter of the plain code path (M = 0, the text every golden file pins),
+    in each of the oracle's three traversal modes.  Seven candidates do not: the loop is reached."""
+    make, w, h, kw = ANCHOR_CASES[name]
+    sc = make(mirt)
+    for mode in (ob.TRAV_BRUTE, ob.TRAV_STREAM_BVH, ob.TRAV_PER_RAY_BVH):
+        plain = oracle_state(sc, w, h, 5, trav_mode=mode, **kw)
+        same_state(oracle_state(sc, w, h, 5, trav_mode=mode, light_ris=1, **kw), plain, f"{name}, mode {mode}: M = 1 against M = 0")
+    seven = oracle_state(sc, w, h, 5, light_ris=7, **kw)
+    assert (ob.bits(seven["acc"]) != ob.bits(plain["acc"])).any()
+    # the twin's traversal returns the brute-force answer bit for bit, with candidates as without
+    twin = oracle_state(sc, w, h, 5, light_ris=7, trav_mode=ob.TRAV_PER_RAY_BVH, **kw)
+    assert np.array_equal(ob.bits(twin["acc"]), ob.bits(seven["acc"])) and np.array_equal(ob.bits(twin["frame"]), ob.bits(seven["frame"]))
+    assert {k: twin["counters"][k] for k in ("rays", "terminated")} == {k: seven["counters"][k] for k in ("rays", "terminated")}
+    assert twin["counters"]["shadow_rays"] <= seven["counters"]["shadow_rays"]         # Q5: the twin casts nothing for hits it then drops
+
+
+@pytest.mark.parametrize("name,candidates", RIS_CASES)
+def test_oracle_unbiased(mirt, name, candidates):
+    """The oracle as a backend of the float64 estimator, with test_light_ris_gpu.py's test_unbiased's bounds: every regional mean within SIGMA
+    standard errors of the quadrature (ris_definitions' variance), `shadow_rays` within SIGMA Bernoulli sigma of 1 - (1 - p)^M, `rays` and
+    `terminated` the plain oracle's.  This is what keeps the oracle's loop from being a copy of the kernels' mistake."""
+    n_acc = MANY_ACC if name == "MANY" else F_CASES[name]["n_acc"]
+    sc = lit_scene(mirt, case_lights(name))
+    exp, var = expectation(name), sampler(name, candidates)
+    guard_first_hits(cpu.OracleBackend(mirt), sc, 3)
+    res = oracle_state(sc, F_W, F_H, n_acc, max_bounces=3, trav_mode=ob.TRAV_PER_RAY_BVH, light_ris=candidates)
+    plain = oracle_state(sc, F_W, F_H, n_acc, max_bounces=3, trav_mode=ob.TRAV_PER_RAY_BVH)
+    img = backend_image(res, n_acc)
+    zs = {}
+    for label, mask in regions(name).items():
+        k = mask.reshape(-1)
+        want = exp["E"][k].mean(axis=0)
+        se = np.sqrt(var["var"][k].sum(axis=0) / n_acc) / k.sum()
+        assert mask.sum() >= 64 and (want > 0).all() and (se / want < 0.01).all(), (name, label, se / want)
+        zs[label] = (img[mask].mean(axis=0) - want) / se
+    c = res["counters"]
+    share = np.load(GOLDEN)["shadow_probability"] if name == "MANY" else shadow_share(name, candidates)
+    want_sh, sigma_sh = n_acc * share.sum(), math.sqrt(n_acc * (share * (1 - share)).sum())
+    report(f"oracle/ris/{name}/M{candidates}", **{f"z_{k}": "/".join(f"{v:+.2f}" for v in z) for k, z in zs.items()},
+           shadow_rays=c["shadow_rays"], shadow_expected=float(want_sh), shadow_sigma=float(sigma_sh), shadow_plain=plain["counters"]["shadow_rays"])
+    for label, z in zs.items():
+        assert np.abs(z).max() <= SIGMA, f"{name}/{label}: {z} sigma from the expectation"
+    assert abs(c["shadow_rays"] - want_sh) <= SIGMA * sigma_sh, f"{name}: {c['shadow_rays']} shadow rays, expected {want_sh:.1f} +- {sigma_sh:.1f}"
+    for k in ("rays", "terminated"):
+        assert c[k] == plain["counters"][k], k
+
+
+GGX_ACC, GGX_GRID = 256, 32          # accumulations (16 in each of 16 buckets); side of a region in pixels: 3 x 2 regions of the 96 x 64 image
+
+
+def ggx_region_means(acc, w, h, n_acc):
+    """[tile][16][3][256] -> per region and channel: the mean, and its standard error from the spread of the 16 independent bucket means."""
+    img = np.zeros((16, h, w, 3))
+    for t in range(acc.shape[0]):
+        y0, x0 = 16 * (t // (w // 16)), 16 * (t % (w // 16))
+        img[:, y0:y0 + 16, x0:x0 + 16, :] = np.moveaxis(acc[t].astype(np.float64), 1, 2).reshape(16, 16, 16, 3)
+    r = img.reshape(16, h // GGX_GRID, GGX_GRID, w // GGX_GRID, GGX_GRID, 3).mean(axis=(2, 4)) / (n_acc / 16)
+    return r.mean(axis=0), r.std(axis=0, ddof=1) / math.sqrt(16)
+
+
+def test_oracle_ggx_expectation(mirt):
+    """ris_definitions is Lambertian; for GGX the oracle's eight candidates are compared with its own plain draw on brdf_test (GGX, a decay
+    table, 16 buckets): per 32 x 32 region and channel z = (mean_8 - mean_0) / sqrt(se_8^2 + se_0^2), each se from the spread of that run's 16
+    independent bucket means, |z| <= SIGMA.  Condition: every region's relative se is below 1 % in both runs; GGX_ACC = 256 is the smallest multiple
+    of 16 at which the plain oracle meets it here (0.0104 at 240, 0.0095 at 256).  Measured at 256: largest |z| 3.22.
+    Not noise alone: |z| grows with the count (5.9 at 512, 8.1 at 2048) and stays below 1.2 through 2048 once the NEE stream is hashed apart from
+    the camera sample's.  The reference draws the camera jitter and the bounce-0 light sample from ONE generator state (Renderer.hpp:117,255), so
+    the plain draw's (u0, u1) ARE the pixel jitter; candidates 2..M are independent of it.  The expectations of M = 0 and M = 8 therefore differ by
+    that correlation's share (about 0.5 % of a region's mean here), which 256 accumulations do not resolve and the 1 % condition allows."""
+    w, h = 96, 64
+    runs = {}
+    for m in (0, 8):
+        o = ob.Oracle(mirt.scene.brdf_test(), max_bounces=16, buckets=16, brdf=1, gloss_decay=DECAY, light_ris=m)
+        o.Resize(w, h); o.Accumulate(GGX_ACC)
+        runs[m] = ggx_region_means(o.accumulator(), w, h, GGX_ACC)
+        o.close()
+    (m0, s0), (m8, s8) = runs[0], runs[8]
+    assert (m0 > 0).all() and (m8 > 0).all()
+    assert (s0 / m0 < 0.01).all() and (s8 / m8 < 0.01).all(), (float((s0 / m0).max()), float((s8 / m8).max()))
+    z = (m8 - m0) / np.sqrt(s8 * s8 + s0 * s0)
+    report("oracle/ris/ggx", accumulations=GGX_ACC, rel_se_0=float((s0 / m0).max()), rel_se_8=float((s8 / m8).max()),
+           z=" ".join("/".join(f"{v:+.2f}" for v in zz) for zz in z.reshape(-1, 3)))
+    assert np.abs(z).max() <= SIGMA, z
+
+
+# ---- the reservoir draw that is exactly 1.0f ----------------------------------------------------------------------------------------
+ONE_W = ONE_H = 16                       # one tile of the F1_high scene (the unit sphere fills the frame and every hit casts), max_bounces = 3
+ONE_BOUNCES = 3
+ONE_ACC, ONE_PIXEL = 26873, 64           # search_unit_draw()[0]; its other two below 2^18: (65193, 104), (200960, 100)
+
+
+def nee_draws(acc, pixels, bounce, count, max_bounces=ONE_BOUNCES):
+    """The first `count` words of the NEE generator hash_2d(acc, seed[ID] + 2 * bounce) of tile 0's pixels, acc = the Accumulate() call's number
+    (the first call is 1: Renderer.hpp:74 increments before it renders): (count, n) uint32."""
+    seed = lt.seeds([0], max_bounces)[np.asarray(pixels)]
+    state = lt.hash_2d(np.broadcast_to(np.asarray(acc, dtype=np.uint32), seed.shape), (seed.astype(np.uint64) + np.uint64(2 * bounce)) & lt.M32)
+    out = []
+    for _ in range(count):
+        word, state = lt.pcg_generate(state)
+        out.append(word)
+    return np.stack(out)
+
+
+def search_unit_draw(limit=1 << 18, chunk=1 << 12):
+    """Every (accumulation number, pixel) below `limit` at which the reservoir draw of the FIRST candidate at bounce 0 - the 4th word of the NEE
+    stream, after u0, u1 and the light - is at least 0xFFFFFF80, the words rand_unit_float turns into exactly 1.0f.  About 12 s; the test
+    keeps its first result as ONE_ACC, ONE_PIXEL."""
+    found = []
+    for lo in range(1, limit, chunk):
+        acc = np.arange(lo, min(limit, lo + chunk), dtype=np.uint32)
+        words = nee_draws(np.repeat(acc, 256), np.tile(np.arange(256), len(acc)), 0, 4)[3]
+        found += [(int(acc[i // 256]), int(i % 256)) for i in np.flatnonzero(words >= np.uint32(0xFFFFFF80))]
+    return found
+
+
+def one_scene(mirt):
+    return lit_scene(mirt, F_CASES["F1_high"]["lights"])
+
+
+def one_run(make_renderer, n_before=ONE_ACC - 1):
+    """The accumulator after call number n_before + 1 alone: both sides are brought to the count by loading an empty slab, not by rendering up to it."""
+    r = make_renderer()
+    r.Resize(ONE_W, ONE_H)
+    r.load_accumulator(np.zeros(ONE_W * ONE_H * 5 * 3, dtype=np.float32), n_before)
+    r.Accumulate(1)
+    assert r.accumulations == n_before + 1
+    acc = r.accumulator().copy()
+    r.close()
+    return acc
+
+
+def test_first_candidate_is_taken_when_the_draw_is_one(mirt):
+    """`weight_sum == w` takes the first positive candidate whatever r; without it `r < w / weight_sum` is 1.0f < 1.0f and the hit casts nothing."""
+    word = nee_draws(ONE_ACC, [ONE_PIXEL], 0, 4)[3]
+    assert word[0] >= 0xFFFFFF80 and (word.astype(np.float32) * np.float32(2.0 ** -32))[0] == np.float32(1.0)
+    sc = one_scene(mirt)
+    o = ob.Oracle(sc, max_bounces=ONE_BOUNCES, light_ris=1); o.Resize(ONE_W, ONE_H)
+    rec = o.debug_candidates(0, ONE_PIXEL, ONE_ACC)
+    o.close()
+    first = rec[(rec[:, 0] == 0) & (rec[:, 1] == 0)]
+    assert len(first) == 1 and first[0, 2] == np.float32(1.0) and first[0, 3] > 0, rec      # the oracle drew 1.0f there, for a candidate that weighs something
+    got = {m: one_run(lambda: ob.Oracle(sc, max_bounces=ONE_BOUNCES, light_ris=m)) for m in (0, 1)}
+    assert got[0][0, ONE_ACC % 5, :, ONE_PIXEL].min() > 0                                   # the plain draw's light arrived in that pixel
+    assert np.array_equal(ob.bits(got[1]), ob.bits(got[0]))
+    assert not got[0][:, [b for b in range(5) if b != ONE_ACC % 5]].any()                   # one call, one bucket: the slab was loaded, not rendered up to
+
+
+# ---- the oracle's interface ----------------------------------------------------------------------------------------------------------
+def test_oracle_light_ris_interface(mirt, oracle_lib):
+    assert oracle_lib.orc_set_light_ris(None, 4) == -1
+    assert oracle_lib.orc_load_accumulator(None, None, 0) == -1
+    o = ob.Oracle(mirt.scene.default9())
+    assert o.light_ris == 0
+    assert oracle_lib.orc_set_light_ris(o.h, 33) == -1 and oracle_lib.orc_set_light_ris(o.h, 32) == 0 and oracle_lib.orc_set_light_ris(o.h, 0) == 0
+    with pytest.raises(ValueError, match="33 candidates"):
+        o.set_light_ris(33)
+    assert oracle_lib.orc_load_accumulator(o.h, None, 3) == -1
+    o.close()
 
 
 # ---- the C interface ---------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """Resampled importance sampling of the NEE light on the device (mirt_set_light_ris; k_shade_ris, shade_hit_body.inc).
 
 1  one candidate is the plain path word for word, so the RIS kernels must give the ORACLE's words;
+1b the oracle carries the candidate loop itself (orc_set_light_ris, held to the float64 estimator in tests/test_light_ris_cpu.py): every RIS twin
+   kernel - first and later bounces, Lambertian and GGX, dense and sparse - gives the oracle's words for M > 1, and at the draw that is 1.0f;
 2  more candidates keep the expectation: part F's quadrature, with the variance of tests/ris_definitions.py;
 3  a hit whose candidates all weigh nothing casts nothing;
 4  on MANY the noise estimate falls, by what the float64 estimator predicts;
@@ -73,6 +75,127 @@ def test_one_candidate_is_the_oracle(mirt, name):
         assert got["shadow_rays"] == pc["shadow_rays"] <= want_c["shadow_rays"] and got["dropped"] == pc["dropped"], (name, label)
         assert got["dropped"] == n * (w // 16) * (h // 16) * 256 - want_c["terminated"], (name, label)
         r.close()
+
+
+# ---- 1b: M > 1 against the oracle's own candidate loop ------------------------------------------------------------------------------------
+ROUTES = (("tree", dict(use_bvh=True)), ("brute", dict(use_bvh=False)), ("tree, traced camera rays", dict(use_bvh=True, trace_primary_rays=True)))
+MANY_CANDIDATES = {   # scene, width, height, keywords shared with the oracle: 5 accumulations, max_bounces 16 - later-bounce launches with partly filled waves
+    "default9": (lambda m: m.scene.default9(), 96, 64, {}),
+    "S1000": (lambda m: m.scene.synthetic(1000), 64, 64, {}),
+    "cloud37": (cloud_compound, 64, 48, {}),
+    "brdf_test_ggx": (lambda m: m.scene.brdf_test(), 96, 64, dict(brdf=1, gloss_decay=DECAY)),
+    "default9_ggx": (lambda m: m.scene.default9(), 96, 64, dict(brdf=1, gloss_decay=DECAY)),
+}
+# 2: the first carried selection; 7: odd; 32: the cap; 16 (default9): where the timing jumps
+CANDIDATE_CASES = [(name, m) for name in MANY_CANDIDATES for m in (2, 7, 32)] + [("default9", 16)]
+_oracle_cache = {}
+
+
+def oracle_states(sc, key, w, h, counts, max_bounces=16, tiles_after=None, **kw):
+    """The oracle after each of `counts` accumulations: acc, frame, counters of the brute-force mode (the reference as shipped) and `twin`, the counters
+    of its mode 2, which casts no shadow ray for a last-bounce hit (Q5) as the pipeline does not - its words must be the brute-force words.
+    tiles_after = (n, tiles): also `active`, both modes' counters of the calls after number n on those tiles alone (what a context with the other tiles
+    frozen at n goes on to trace).  Computed once a process for a key."""
+    key = (key, w, h, tuple(counts), max_bounces, None if tiles_after is None else (tiles_after[0], tuple(tiles_after[1])))
+    if key in _oracle_cache:
+        return _oracle_cache[key]
+    out = {}
+    for mode in (ob.TRAV_BRUTE, ob.TRAV_PER_RAY_BVH):
+        o = ob.Oracle(sc, max_bounces=max_bounces, buckets=5, trav_mode=mode, **kw)
+        o.Resize(w, h)
+        done = 0
+        for n in counts:
+            o.Accumulate(n - done); done = n
+            if mode == ob.TRAV_BRUTE:
+                out[n] = dict(acc=o.accumulator(), frame=o.Render().copy(), counters=o.counters())
+            else:
+                same_words(o.accumulator(), out[n]["acc"], f"oracle, {n} accumulations: mode 2 against brute force")
+                out[n]["twin"] = o.counters()
+        if tiles_after is not None:
+            n, tiles = tiles_after
+            o.Resize(w, h, tiles=tiles)
+            o.ResetAccumulator()
+            o.load_accumulator(np.zeros(len(tiles) * 5 * 3 * 256, dtype=np.float32), n)
+            o.Accumulate(counts[-1] - n)
+            out.setdefault("active", {})[mode] = o.counters()
+        o.close()
+    _oracle_cache[key] = out
+    return out
+
+
+def check_against_oracle(r, want, what):
+    """Accumulator and frame word for word; rays and terminated the oracle's; shadow_rays the twin mode's exactly and at most the brute-force mode's."""
+    assert r.Render()
+    same_words(r.accumulator(), want["acc"], f"{what}: accumulator")
+    same_words(r.GetFrame(), want["frame"], f"{what}: frame")
+    got = r.counters()
+    assert {k: got[k] for k in COUNTERS} == {k: want["counters"][k] for k in COUNTERS}, what
+    assert {k: got[k] for k in COUNTERS} == {k: want["twin"][k] for k in COUNTERS}, what
+    assert got["shadow_rays"] == want["twin"]["shadow_rays"] <= want["counters"]["shadow_rays"], what
+
+
+@pytest.mark.parametrize("name,candidates", CANDIDATE_CASES)
+def test_many_candidates_are_the_oracle(mirt, name, candidates):
+    """What the suite could not see before: a register lost over a spill in the candidate loop, a draw out of order for candidate i >= 2, or
+    weight_sum / (float(M) * w_sel) formed another way would all keep the expectation and the route invariance.  Every word is the oracle's."""
+    make, w, h, kw = MANY_CANDIDATES[name]
+    sc = make(mirt)
+    want = oracle_states(sc, (name, candidates), w, h, (5,), light_ris=candidates, **kw)[5]
+    plain = oracle_states(sc, (name, 0), w, h, (5,), **kw)[5]
+    assert (want["acc"].view(np.uint32) != plain["acc"].view(np.uint32)).any()                     # the candidates change the words
+    for label, route in ROUTES:
+        r = mirt.Renderer(sc, max_bounces=16, buckets=5, light_ris=candidates, **route, **kw)
+        r.Resize(w, h); r.Accumulate(5)
+        check_against_oracle(r, want, f"{name}, M = {candidates}, {label}")
+        r.close()
+
+
+def tile_pixels(mask, w, h):
+    return np.repeat(np.repeat(np.asarray(mask).reshape(h // 16, w // 16), 16, axis=0), 16, axis=1)
+
+
+def check_frozen_against_oracle(mirt, sc, key, w, h, routes, max_bounces=16, setup=None, **kw):
+    """5 accumulations, every third tile frozen, 5 more (the SPARSE kernels): the frozen tiles hold the oracle's words at 5, the active ones its words
+    at 10, in the accumulator and in the frame; the counters are the oracle's first five calls plus its calls 6..10 on the active tiles alone."""
+    mask = np.arange((w // 16) * (h // 16)) % 3 == 0
+    want = oracle_states(sc, key, w, h, (5, 10), max_bounces=max_bounces, tiles_after=(5, np.flatnonzero(~mask)), **kw)
+    five, ten, px = want[5], want[10], tile_pixels(mask, w, h)
+    for label, route in routes:
+        what = f"{key}, frozen tiles, {label}"
+        r = mirt.Renderer(sc, max_bounces=max_bounces, buckets=5, **route, **{k: v for k, v in kw.items() if k != "lens"})
+        r.Resize(w, h)
+        if "lens" in kw:
+            r.set_lens(*kw["lens"])
+        r.Accumulate(5); r.freeze_tiles(mask); r.Accumulate(5)
+        assert r.Render()
+        acc, frame = r.accumulator(), r.GetFrame()
+        same_words(acc[mask], five["acc"][mask], f"{what}: frozen tiles"); same_words(acc[~mask], ten["acc"][~mask], f"{what}: active tiles")
+        same_words(frame[px], five["frame"][px], f"{what}: frame of the frozen tiles"); same_words(frame[~px], ten["frame"][~px], f"{what}: frame of the active tiles")
+        got = r.counters()
+        for k in COUNTERS:
+            assert got[k] == five["counters"][k] + want["active"][ob.TRAV_BRUTE][k] == five["twin"][k] + want["active"][ob.TRAV_PER_RAY_BVH][k], (what, k)
+        assert got["shadow_rays"] == five["twin"]["shadow_rays"] + want["active"][ob.TRAV_PER_RAY_BVH]["shadow_rays"], what
+        assert got["shadow_rays"] <= five["counters"]["shadow_rays"] + want["active"][ob.TRAV_BRUTE]["shadow_rays"], what
+        r.close()
+
+
+@pytest.mark.parametrize("name", ["default9", "brdf_test_ggx"])
+def test_sparse_twins_are_the_oracle(mirt, name):
+    """k_shade_first_sparse_ris<GGX, LENS = false>, through the camera-ray lists and through traced camera rays."""
+    make, w, h, kw = MANY_CANDIDATES[name]
+    check_frozen_against_oracle(mirt, make(mirt), name, w, h, (ROUTES[0], ROUTES[2]), light_ris=7, **kw)
+
+
+def test_the_draw_that_is_one(mirt):
+    """At the call and pixel where the first candidate's reservoir draw is exactly 1.0f (tests/test_light_ris_cpu.py ONE_ACC, ONE_PIXEL, where the
+    oracle's side is asserted): device M = 1 = device M = 0 = the oracle; device M = 7 = the oracle's M = 7.  Both sides load an empty slab at the count."""
+    sc = ris.one_scene(mirt)
+    dev = {m: ris.one_run(lambda: mirt.Renderer(sc, max_bounces=ris.ONE_BOUNCES, buckets=5, use_bvh=True, light_ris=m)) for m in (0, 1, 7)}
+    orc = {m: ris.one_run(lambda: ob.Oracle(sc, max_bounces=ris.ONE_BOUNCES, buckets=5, light_ris=m)) for m in (0, 7)}
+    assert dev[0][0, ris.ONE_ACC % 5, :, ris.ONE_PIXEL].min() > 0
+    same_words(dev[0], orc[0], "plain draw against the oracle"); same_words(dev[1], dev[0], "M = 1 against the plain draw")
+    same_words(dev[7], orc[7], "M = 7 against the oracle")
+    assert (dev[7].view(np.uint32) != dev[0].view(np.uint32)).any()
 
 
 # ---- 2, 3 -------------------------------------------------------------------------------------------------------------------------
@@ -208,7 +331,7 @@ def test_words_do_not_depend_on_the_route(mirt, name):
     g.Resize(w, h); g.Accumulate(n)
     same_words(g.accumulator(), base, f"{name}: a group of three")
     g.close()
-    # a lens: the words of the same lens through the traced-camera-ray route and through brute force (no pinhole run to compare with)
+    # a lens: the words of the same lens through the traced-camera-ray route and through brute force (against the oracle: tests/test_lens_gpu.py)
     lens = dict(setup=lambda q: q.set_lens(0.05, 4.0))
     same_words(run(**lens), run(use_bvh=False, **lens), f"{name}: lens, tree against brute force")
     # frozen tiles: the active tiles go on as if nothing were frozen, the frozen ones keep their words
