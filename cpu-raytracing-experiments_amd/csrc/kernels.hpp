@@ -1152,20 +1152,47 @@ __global__ __launch_bounds__(kBlock) void k_listed_active(const uint32_t* __rest
 // list through three dependent loads — 7.3 ms per cfg4 batch of 537 M rays.)  Pixels without a list are skipped: k_trace<kPrimaryList> traces
 // all their samples.
 constexpr uint32_t kCandRegs = 3;
-// SPARSE (every bounce-0 kernel below has such a twin, launched once a tile is frozen — mirt_freeze_tiles; the kernels without it are the text
-// they have always been): tile_frozen[local tile] != 0 marks a tile that takes no more samples.  Its pixels are skipped — no ray, no hit
+// SPARSE (a template argument of every bounce-0 kernel below and of the merge; launched once a tile is frozen — mirt_freeze_tiles):
+// tile_frozen[local tile] != 0 marks a tile that takes no more samples.  Its pixels are skipped — no ray, no hit
 // record, no store of any kind — and ctr->rays counts active_pix = 256 x the active tiles instead of n_pix.  The owned pixel space, path ids and
 // every buffer's indexing stay what they are; after bounce 0 the streams are compact queues that never held a frozen pixel.
-template <bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_primary_hits(SceneDev sc, FrameParams fp, const uint32_t* __restrict__ cand, HitRec* __restrict__ hit_out, DevCounters* ctr) {
-	constexpr bool SPARSE = false; const uint32_t* const tile_frozen = nullptr; const uint32_t active_pix = 0u;
-#include "primary_hits_body.inc"
-}
-template <bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_primary_hits_sparse(SceneDev sc, FrameParams fp, const uint32_t* __restrict__ cand, HitRec* __restrict__ hit_out, DevCounters* ctr,
-                                                                const uint32_t* __restrict__ tile_frozen, uint32_t active_pix) {
-	constexpr bool SPARSE = true;
-#include "primary_hits_body.inc"
+// The arguments that only SPARSE (tile_frozen, active_pix) or RIS (ris_m) code reads are always present, last, and the other instantiations never
+// load them.  Every instantiation's device code was held to that of the kernel it replaces, listing by listing (profiles/one_kernel_per_stage.txt).
+template <bool COUNT, bool SPARSE = false>
+__global__ __launch_bounds__(kBlock) void k_primary_hits(SceneDev sc, FrameParams fp, const uint32_t* __restrict__ cand, HitRec* __restrict__ hit_out, DevCounters* ctr,
+                                                         const uint32_t* __restrict__ tile_frozen, uint32_t active_pix) {
+	if (blockIdx.x == 0 && threadIdx.x == 0 && fp.n_pix) atomicAdd(&ctr->rays, static_cast<unsigned long long>(SPARSE ? active_pix : fp.n_pix) * fp.batch_n);     // Renderer.hpp:165: every camera ray of the batch
+	uint32_t c_spheres = 0;
+	const float ox = fp.cam.pos[0], oy = fp.cam.pos[1], oz = fp.cam.pos[2];
+	for (uint32_t pix = blockIdx.x * kBlock + threadIdx.x; pix < fp.n_pix; pix += gridDim.x * kBlock) {
+		if (SPARSE && tile_frozen[pix >> 8] != 0u) continue;
+		const uint32_t cnt = cand[pix];
+		if (cnt == kCandOverflow) continue;
+		uint32_t tile; int32_t x, y;
+		pixel_xy(fp, pix, tile, x, y);
+		const uint32_t seed = tile_seed(fp, tile, pix & 255u);
+		float4 s[kCandRegs]; int32_t id[kCandRegs];
+		for (uint32_t k = 0; k < kCandRegs; k++) {
+			id[k] = k < cnt ? static_cast<int32_t>(cand[static_cast<size_t>(k + 1u) * fp.n_pix + pix]) : -1;
+			s[k] = sc.spheres[id[k] < 0 ? 0 : id[k]];
+		}
+		for (uint32_t slot = 0; slot < fp.batch_n; slot++) {
+			const f3 d = camera_sample(fp.cam, x, y, fp.acc_base + slot + 1u, seed);
+			float tfar = MIRT_FLT_MAX; int32_t prim = -1;                          // hit reset, Renderer.hpp:150-158
+			for (uint32_t k = 0; k < kCandRegs; k++) if (id[k] >= 0) sphere_closest_tie(s[k], id[k], ox, oy, oz, d.x, d.y, d.z, tfar, prim);
+			for (uint32_t k = kCandRegs; k < kCandMax; k++) {                      // the rest of a long list, from L1
+				if (__ballot(k < cnt) == 0ull) break;
+				if (k < cnt) {
+					const uint32_t j = cand[static_cast<size_t>(k + 1u) * fp.n_pix + pix];
+					sphere_closest_tie(sc.spheres[j], static_cast<int32_t>(j), ox, oy, oz, d.x, d.y, d.z, tfar, prim);
+				}
+			}
+			if (COUNT) c_spheres += cnt;
+			const size_t i = static_cast<size_t>(slot) * fp.n_pix + pix;
+			hit_out[i] = HitRec{ tfar, prim };
+		}
+	}
+	if (COUNT) wave_sum(c_spheres, &ctr->spheres);
 }
 // The same, turned round for a batch that fills a wave: one wave per PIXEL, one lane per accumulation of the batch.  What the lanes of
 // k_primary_hits wait for — the longest list among 64 pixels, and a list word + a sphere gathered again by every sample — is wave-uniform here:
@@ -1183,16 +1210,72 @@ __global__ __launch_bounds__(kBlock) void k_primary_hits_sparse(SceneDev sc, Fra
 constexpr uint32_t kWaveHitsWaves = kBlock / 64u;
 static_assert(kCandMax < 64u && kTileSize % kWaveHitsRun == 0u && kWaveHitsRun == kTileRoot, "lane k holds list entry k; a run is one row of a tile");
 // SPARSE: a run is one row of ONE tile, so the test of its tile is wave-uniform (a scalar load and branch).
-template <bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_primary_hits_wave(SceneDev sc, FrameParams fp, const uint32_t* __restrict__ cand, HitRec* __restrict__ hit_out, DevCounters* ctr) {
-	constexpr bool SPARSE = false; const uint32_t* const tile_frozen = nullptr; const uint32_t active_pix = 0u;
-#include "primary_hits_wave_body.inc"
-}
-template <bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_primary_hits_wave_sparse(SceneDev sc, FrameParams fp, const uint32_t* __restrict__ cand, HitRec* __restrict__ hit_out, DevCounters* ctr,
-                                                                     const uint32_t* __restrict__ tile_frozen, uint32_t active_pix) {
-	constexpr bool SPARSE = true;
-#include "primary_hits_wave_body.inc"
+template <bool COUNT, bool SPARSE = false>
+__global__ __launch_bounds__(kBlock) void k_primary_hits_wave(SceneDev sc, FrameParams fp, const uint32_t* __restrict__ cand, HitRec* __restrict__ hit_out, DevCounters* ctr,
+                                                              const uint32_t* __restrict__ tile_frozen, uint32_t active_pix) {
+	__shared__ HitRec stage[kWaveHitsWaves][kWaveHitsStage];
+	const uint32_t lane = lane_id();
+	const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)));
+	const uint32_t n_runs = fp.n_pix / kWaveHitsRun, n_groups = hits_wave_groups(fp.batch_n);
+	const uint32_t out_p = hits_wave_out_pixel(lane);                              // write-out: this lane's pixel of the run
+	uint32_t c_spheres = 0;
+	const float ox = fp.cam.pos[0], oy = fp.cam.pos[1], oz = fp.cam.pos[2];
+	for (uint32_t run = blockIdx.x * kWaveHitsWaves + wave; run < n_runs; run += gridDim.x * kWaveHitsWaves) {
+		const uint32_t base = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(run * kWaveHitsRun)));     // first local pixel of the run: wave-uniform
+		if (SPARSE && tile_frozen[base >> 8] != 0u) continue;
+		const uint32_t cnt_v = cand[base + out_p];                                   // lane p (and p + 16, ...): the count of pixel p of the run
+		const uint32_t skip = static_cast<uint32_t>(__ballot(cnt_v == kCandOverflow)) & 0xffffu;      // pixels without a list: k_trace<kPrimaryList> writes their records
+		if (skip == 0xffffu) continue;
+		uint32_t tile; int32_t x0, y;
+		pixel_xy(fp, base, tile, x0, y);                                             // the run's pixels: (x0 + p, y), ID = (base & 255) + p
+		const uint32_t seed0 = tile * kTileSize + (base & 255u), seed_mul = fp.max_bounces * 2u + 1u;
+		auto count_of = [&](uint32_t p) { return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cnt_v), static_cast<int>(p))) + 1u; };   // entries + 1; 0 without a list
+		// Lane k's entry of pixel p's list, and that sphere.  Every lane loads, whatever the list's length — the lanes beyond it read the last entry
+		// again (the count word of an empty list) and sphere 0, and nobody reads what they hold: with loads that some lanes or some passes skip, the
+		// in-order load counter would have to be waited down to zero before the tests, with the next pixel's loads just issued.
+		auto load_ids = [&](uint32_t p) { const uint32_t c1 = count_of(p); return cand[static_cast<size_t>(min(lane + 1u, c1 ? c1 - 1u : 0u)) * fp.n_pix + base + p]; };
+		auto load_sphere = [&](uint32_t p, uint32_t j) { return sc.spheres[lane + 1u < count_of(p) ? j : 0u]; };
+		for (uint32_t g = 0; g < n_groups; g++) {
+			const uint32_t slot = g * 64u + lane;                                     // lanes beyond batch_n compute a ray nobody stores
+			uint32_t id_cur = load_ids(0), id_next = load_ids(1);
+			float4 s_cur = load_sphere(0, id_cur);
+			for (uint32_t p = 0; p < kWaveHitsRun; p++) {
+				// the sphere of pixel p + 1 and the list entry of pixel p + 2 (the run's last pixel again beyond it): in flight during the tests of pixel p
+				const float4 s_next = load_sphere(min(p + 1u, kWaveHitsRun - 1u), id_next);
+				const uint32_t id_next2 = load_ids(min(p + 2u, kWaveHitsRun - 1u));
+				const uint32_t cnt1 = count_of(p);
+				if (cnt1 != 0u) {
+					const uint32_t cnt = cnt1 - 1u;
+					uint32_t rng = hash_2d(fp.acc_base + slot + 1u, (seed0 + p) * seed_mul);      // mirrors camera_sample(.., tile_seed(fp, tile, (base & 255) + p)), Renderer.hpp:74,107,117
+					const float s0 = rand_unit_float(rng);
+					const float s1 = rand_unit_float(rng);
+					const f3 d = camera_ray_dir(fp.cam, x0 + static_cast<int32_t>(p), y, s0, s1);
+					float tfar = MIRT_FLT_MAX; int32_t prim = -1;                          // hit reset, Renderer.hpp:150-158
+					for (uint32_t k = 0; k < cnt; k++) {
+						const int32_t j = __builtin_amdgcn_readlane(static_cast<int>(id_cur), static_cast<int>(k));
+						const float4 s{ __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s_cur.x), static_cast<int>(k))), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s_cur.y), static_cast<int>(k))),
+						                __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s_cur.z), static_cast<int>(k))), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s_cur.w), static_cast<int>(k))) };
+						sphere_closest_tie(s, j, ox, oy, oz, d.x, d.y, d.z, tfar, prim);
+					}
+					if (COUNT && slot < fp.batch_n) c_spheres += cnt;
+					stage[wave][hits_wave_stage_index(p, lane)] = HitRec{ tfar, prim };
+				}
+				id_cur = id_next; id_next = id_next2; s_cur = s_next;
+			}
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+			const uint32_t n_slots = hits_wave_group_slots(fp.batch_n, g);
+			if (!((skip >> out_p) & 1u)) {
+				for (uint32_t pass = 0; pass < kWaveHitsPasses; pass++) {
+					const uint32_t s = hits_wave_out_slot(lane, pass);
+					if (s >= n_slots) break;
+					hit_out[static_cast<size_t>(g * 64u + s) * fp.n_pix + base + out_p] = stage[wave][hits_wave_stage_index(out_p, s)];
+				}
+			}
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		}
+	}
+	if (COUNT) wave_sum(c_spheres, &ctr->spheres);
+	if (blockIdx.x == 0 && threadIdx.x == 0 && fp.n_pix) atomicAdd(&ctr->rays, static_cast<unsigned long long>(SPARSE ? active_pix : fp.n_pix) * fp.batch_n);     // Renderer.hpp:165: every camera ray of the batch
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1210,16 +1293,36 @@ constexpr uint32_t kAovPlanes = 7;
 constexpr float kAovMissDepth = 1e4f;             // Renderer.hpp:228
 // LENS: the sample's thin-lens ray (lens_ray) instead of the pinhole ray — origin and direction both differ per sample.
 // SPARSE: the sums of a frozen tile stop with its accumulator (its hit records are not written either).
-template <bool LENS = false>
-__global__ __launch_bounds__(kBlock) void k_first_hit_aov(SceneDev sc, FrameParams fp, const HitRec* __restrict__ hit_in, const float4* __restrict__ mat_colour, float* __restrict__ aov, LensParams lens) {
-	constexpr bool SPARSE = false; const uint32_t* const tile_frozen = nullptr;
-#include "first_hit_aov_body.inc"
-}
-template <bool LENS>
-__global__ __launch_bounds__(kBlock) void k_first_hit_aov_sparse(SceneDev sc, FrameParams fp, const HitRec* __restrict__ hit_in, const float4* __restrict__ mat_colour, float* __restrict__ aov, LensParams lens,
-                                                                 const uint32_t* __restrict__ tile_frozen) {
-	constexpr bool SPARSE = true;
-#include "first_hit_aov_body.inc"
+template <bool LENS, bool SPARSE = false>
+__global__ __launch_bounds__(kBlock) void k_first_hit_aov(SceneDev sc, FrameParams fp, const HitRec* __restrict__ hit_in, const float4* __restrict__ mat_colour, float* __restrict__ aov, LensParams lens,
+                                                          const uint32_t* __restrict__ tile_frozen) {
+	f3 O{ fp.cam.pos[0], fp.cam.pos[1], fp.cam.pos[2] };
+	for (uint32_t pix = blockIdx.x * kBlock + threadIdx.x; pix < fp.n_pix; pix += gridDim.x * kBlock) {
+		if (SPARSE && tile_frozen[pix >> 8] != 0u) continue;
+		uint32_t tile; int32_t x, y;
+		pixel_xy(fp, pix, tile, x, y);
+		const uint32_t seed = tile_seed(fp, tile, pix & 255u);
+		float* w = aov + static_cast<size_t>(pix >> 8) * (kAovPlanes * kTileSize) + (pix & 255u);
+		float sum[kAovPlanes];
+		for (uint32_t k = 0; k < kAovPlanes; k++) sum[k] = w[k * kTileSize];
+		int32_t cached = -1;
+		float4 hs = make_float4(0.0f, 0.0f, 0.0f, 0.0f), colour = hs;
+		for (uint32_t slot = 0; slot < fp.batch_n; slot++) {
+			f3 D;
+			camera_ray<LENS>(fp, lens, x, y, fp.acc_base + slot + 1u, seed, O, D);
+			const HitRec h = hit_in[static_cast<size_t>(slot) * fp.n_pix + pix];
+			if (h.prim < 0) { sum[0] += kAovMissDepth; continue; }
+			if (h.prim != cached) { hs = sc.spheres[h.prim]; colour = mat_colour[sc.prim_mat[h.prim]]; cached = h.prim; }
+			const float depth = h.tfar;
+			const f3 hit{ O.x + D.x * depth, O.y + D.y * depth, O.z + D.z * depth };      // mirrors shade_hit_body.inc's hit and N, Renderer.hpp:169-214
+			f3 N = normalize3(f3{ hit.x - hs.x, hit.y - hs.y, hit.z - hs.z });
+			if (dot3(N, D) >= 0.0f) N = f3{ -N.x, -N.y, -N.z };
+			sum[0] += depth;
+			sum[1] += N.x; sum[2] += N.y; sum[3] += N.z;
+			sum[4] += colour.x; sum[5] += colour.y; sum[6] += colour.z;
+		}
+		for (uint32_t k = 0; k < kAovPlanes; k++) w[k * kTileSize] = sum[k];
+	}
 }
 // mirt_render_aov: one of the three outputs of the slab above, row-major over the image (row 0 = y 0), 1 (depth) or 3 floats per pixel.
 // Depth and colour: sum / accumulations; normal: normalize3(sum), (0,0,0) where the sum has no length.  IEEE division and sqrt.
@@ -1279,41 +1382,187 @@ MIRT_DI uint32_t block_compact(bool flag, uint32_t value, uint32_t* scratch, uin
 // GGX = #define BRDF 1 (Renderer.hpp:70): every closure is Closure<GGX> (DataStreams.hpp:184-219) with F0 = material.F0 and
 // alpha = r^2 + (1 - r^2) * gloss_decay (Renderer.hpp:210-212; `gloss_decay` = the host's table at this bounce, one launch per
 // bounce), read from mat_ggx = {F0.xyz, roughness}.  Its pdf() is 0: NEE weighs 1 / light_pdf and emitters hit by an extension
-// ray weigh powerHeuristic(0, .) = 0.  GGX = false does not read the two trailing arguments.
+// ray weigh powerHeuristic(0, .) = 0.  GGX = false does not read mat_ggx and gloss_decay.
 // LENS (with FIRST only): bounce 0 re-derives the thin-lens ray (lens_ray) — its origin is the sample's lens point, not cam.pos.  Same launch
 // bounds as the pinhole variants; `lens` is read by LENS code only.
 // SPARSE (with FIRST only): the lanes whose pixel lies in a frozen tile behave as the lanes beyond n_pix do — they take part in the barriers and
 // in the compaction, but read no hit record, emit nothing and store nothing, their path's contribution word included.
-template <bool FIRST, bool GGX, bool LENS = false>
+// RIS (mirt_set_light_ris): next event estimation picks its light among ris_m candidates by resampled importance sampling (shade_hit_body.inc) —
+// ris_m is 1 .. MIRT_MAX_LIGHT_RIS, the same for every lane.  The same text, the same launch bounds.
+template <bool FIRST, bool GGX, bool LENS = false, bool SPARSE = false, bool RIS = false>
 __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
                                                   Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
-                                                  const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens) {
-	constexpr bool SPARSE = false, RIS = false; const uint32_t* const tile_frozen = nullptr; constexpr uint32_t ris_m = 0u;
-#include "shade_body.inc"
-}
-template <bool GGX, bool LENS>
-__global__ __launch_bounds__(kShadeBlock, 6) void k_shade_first_sparse(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
-                                                  Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
-                                                  const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens, const uint32_t* __restrict__ tile_frozen) {
-	constexpr bool SPARSE = true, FIRST = true, RIS = false; constexpr uint32_t ris_m = 0u;
-#include "shade_body.inc"
-}
-// RIS (mirt_set_light_ris): the twins whose next event estimation picks its light among ris_m candidates by resampled importance sampling
-// (shade_hit_body.inc) — ris_m is 1 .. MIRT_MAX_LIGHT_RIS, the same for every lane.  Twins, not a template parameter of the kernels above, so that
-// those keep their names, their arguments and their device code; the same text, the same launch bounds.
-template <bool FIRST, bool GGX, bool LENS = false>
-__global__ __launch_bounds__(kShadeBlock, 6) void k_shade_ris(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
-                                                  Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
-                                                  const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens, uint32_t ris_m) {
-	constexpr bool SPARSE = false, RIS = true; const uint32_t* const tile_frozen = nullptr;
-#include "shade_body.inc"
-}
-template <bool GGX, bool LENS>
-__global__ __launch_bounds__(kShadeBlock, 6) void k_shade_first_sparse_ris(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
-                                                  Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
-                                                  const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens, const uint32_t* __restrict__ tile_frozen, uint32_t ris_m) {
-	constexpr bool SPARSE = true, FIRST = true, RIS = true;
-#include "shade_body.inc"
+                                                  const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens, uint32_t ris_m, const uint32_t* __restrict__ tile_frozen) {
+	static_assert(!(LENS || SPARSE) || FIRST, "the lens and the frozen tiles concern bounce 0 only");
+	const QueueView qin = FIRST ? queue_identity(fp.n_pix * fp.batch_n) : queue_view(in_queue);
+	const uint32_t n = qin.pre[kSegs];
+	const uint32_t n_chunks = (fp.n_pix + kShadeBlock - 1u) / kShadeBlock;      // FIRST
+	const bool last_bounce = !(bounce < fp.max_bounces - 1u);                 // Renderer.hpp:358
+	const float light_selection_pdf = 1.0f / static_cast<float>(fp.n_lights);  // Renderer.hpp:78
+	__shared__ uint32_t append_scratch[72];
+	__shared__ uint32_t compact_scratch[17];
+	__shared__ uint32_t hit_list[kShadeBlock];
+	__shared__ float4 s_albedo[MIRT_MAX_MATERIALS + 1], s_emission[MIRT_MAX_MATERIALS + 1];      // scene.material: 2 KB, read by every hit (GGX: s_albedo = {F0, roughness})
+	uint32_t c_term = 0, c_drop = 0, parity = 0;
+	const uint32_t n_units = n_chunks * fp.first_groups;                       // FIRST: pieces of work = (chunk, group of accumulations)
+	if (FIRST ? blockIdx.x >= n_units : blockIdx.x * kShadeBlock >= n) return;
+	for (uint32_t m = threadIdx.x; m < sc.n_mat; m += kShadeBlock) { s_albedo[m] = GGX ? mat_ggx[m] : sc.mat_albedo[m]; s_emission[m] = sc.mat_emission[m]; }
+	__syncthreads();            // the table is read by every wave in phase 2; k_shade<FIRST> reaches no other barrier before that (the early return above is block-uniform)
+
+	// !FIRST: this lane's ray of the stream for the block-iteration at hand, and its hit record: requested one iteration ahead, so that the
+	// first of the iteration's three dependent memory round trips is already under way
+	uint32_t next_slot = 0u; int32_t next_prim = -1;
+	if (!FIRST) {
+		next_slot = (blockIdx.x * kShadeBlock + threadIdx.x < n) ? queue_slot(qin, blockIdx.x * kShadeBlock, blockIdx.x * kShadeBlock + threadIdx.x) : 0u;
+		next_prim = hit_in[next_slot].prim;
+	}
+	// FIRST: the pixel of this lane in the chunk at hand, and what depends on it alone
+	uint32_t unit = blockIdx.x, chunk = 0u, slot_it = 0u, slot_end = 0u, pix = 0u, pix_seed = 0u;
+	int32_t pix_x = 0, pix_y = 0;
+	bool pix_frozen = false;                                                  // SPARSE
+	for (uint32_t base = blockIdx.x * kShadeBlock; FIRST ? unit < n_units : base < n; parity ^= 1u) {
+		const bool new_unit = FIRST && slot_it == slot_end;                    // wave-uniform
+		if (new_unit) {
+			chunk = unit / fp.first_groups;
+			const uint32_t g = unit - chunk * fp.first_groups;
+			slot_it = g * fp.batch_n / fp.first_groups; slot_end = (g + 1u) * fp.batch_n / fp.first_groups;
+		}
+		const uint32_t iteration = FIRST ? chunk * fp.batch_n + slot_it : base / kShadeBlock;     // FIRST: every (chunk, slot) exactly once
+		// ---- phase 1, one lane per ray of the stream: misses end here; hits are only listed ----
+		bool is_hit = false;
+		uint32_t my_slot = next_slot;
+		int32_t my_prim = next_prim;
+		float my_tfar = 0.0f;
+		f3 my_D{0, 0, 0};
+		f3 my_O{0, 0, 0};                                                       // LENS: the sample's point on the lens
+		uint32_t my_path = 0u;
+		bool lane_on;
+		f3 W0{0.0f, 0.0f, 0.0f};                                               // FIRST: the word this path starts with
+		if (FIRST) {
+			if (new_unit) {                                                      // a new chunk of pixels
+				pix = chunk * kShadeBlock + threadIdx.x;
+				if (pix < fp.n_pix) {
+					uint32_t tile;
+					pixel_xy(fp, pix, tile, pix_x, pix_y);
+					pix_seed = tile_seed(fp, tile, pix & 255u);
+					if (SPARSE) pix_frozen = tile_frozen[pix >> 8] != 0u;
+				}
+			}
+			lane_on = pix < fp.n_pix;
+			if (SPARSE) lane_on = lane_on && !pix_frozen;
+			my_slot = slot_it * fp.n_pix + pix;                                 // the ray's index in the batch = where k_trace stored a hit record for it
+			if (lane_on) {
+				// RAY GENERATION, Renderer.hpp:113-127 (primary_ray with the pixel's part taken from the chunk set-up); the two lines mirror camera_ray<LENS>
+				my_D = camera_sample(fp.cam, pix_x, pix_y, fp.acc_base + slot_it + 1u, pix_seed);
+				if (LENS) lens_ray(fp.cam, lens, my_D, fp.acc_base + slot_it + 1u, pix_seed, fp.max_bounces, my_O, my_D);
+				my_path = (slot_it << fp.pix_bits) | pix;
+				{ const HitRec h = hit_in[my_slot]; my_prim = h.prim; my_tfar = h.tfar; }      // the hit record of k_primary_hits / k_trace
+			}
+			if (++slot_it == slot_end) unit += gridDim.x;
+		} else {
+			lane_on = base + threadIdx.x < n;
+			const uint32_t nb = base + gridDim.x * kShadeBlock;
+			next_slot = (nb + threadIdx.x < n) ? queue_slot(qin, nb, nb + threadIdx.x) : 0u;
+			next_prim = hit_in[next_slot].prim;
+			base = nb;
+		}
+		{
+			if (lane_on) {
+				const uint32_t i = my_slot;
+				const int32_t prim = my_prim;
+				if (prim < 0) {
+					// MISS SHADER, Renderer.hpp:408-420 (Q10: throughput.r scales all three channels).  Without ambient light the path just
+					// ends: its word holds its result already (ACCUMULATION, Renderer.hpp:424-430, is k_merge_contrib's)
+					if (sc.has_ambient) {
+						if (FIRST) {
+							const f3 sky = sky_eval(sc, my_D.x, my_D.y, my_D.z);
+							W0 = { 0.0f + 1.0f * sky.x, 0.0f + 1.0f * sky.y, 0.0f + 1.0f * sky.z };
+						} else {
+							const float4 b = in.b[i];                                      // {dir, throughput.r}
+							const float thr_x = b.w;
+							const f3 sky = sky_eval(sc, b.x, b.y, b.z);
+							float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, __float_as_uint(in.a[i].w));
+							w[0] += thr_x * sky.x; w[1] += thr_x * sky.y; w[2] += thr_x * sky.z;
+						}
+					}
+					c_term++;
+				} else if (last_bounce) {
+					c_drop++;                                                         // Q5: still alive after the last bounce -> never accumulated: the word goes back to +0
+					if (!FIRST) {                                                     // (FIRST: W0 is +0)
+						float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, __float_as_uint(in.a[i].w));
+						w[0] = 0.0f; w[1] = 0.0f; w[2] = 0.0f;
+					}
+				} else is_hit = true;
+			}
+		}
+		// ---- regroup: the closest-hit shader is ~800 VALU instructions per ray and only 40-60 % of a secondary stream hits;
+		// packing the hits of the block into its first waves runs that code on full waves (lane utilisation 0.42 -> ~0.9) ----
+		// (Not for primary rays: ~95 % of them hit, the stream is already dense, and the two barriers cost more than they save.)
+		const uint32_t n_hits = FIRST ? 0u : block_compact(is_hit, my_slot, compact_scratch, hit_list);
+
+		// ---- phase 2, one lane per hit ----
+		bool survive = false, has_shadow = false, terminated = false, has_E = false;
+		uint32_t path = 0;
+		f3 P{0, 0, 0}, ndir{0, 0, 0}, L{0, 0, 0}, srad{0, 0, 0}, E{0, 0, 0};
+		f3 thr{1.0f, 1.0f, 1.0f};
+		float light_distance = 0.0f;
+		if (FIRST ? is_hit : threadIdx.x < n_hits) {
+			const uint32_t i = FIRST ? my_slot : hit_list[threadIdx.x];
+			f3 D = my_D;                                                       // bounce 0 has no stream: the ray is a function of its index (phase 1)
+			path = my_path;
+			f3 O_in{0, 0, 0};
+			float pdf_in = 0.0f;
+			if (!FIRST) {                                                      // the ray's three records
+				const float4 a = in.a[i], b = in.b[i];
+				const float2 c = in.c[i];
+				O_in = { a.x, a.y, a.z }; path = __float_as_uint(a.w);
+				D = { b.x, b.y, b.z };
+				thr = { b.w, c.x, c.y };
+				pdf_in = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, D.z);           // out->pdf of the bounce that sampled D (Q8), bit for bit; Closure<GGX>::pdf = 0
+			}
+			const HitRec hrec = FIRST ? HitRec{ my_tfar, my_prim } : hit_in[i];
+			const int32_t prim = hrec.prim;
+			{
+#define SHADE_HIT_ORIGIN (FIRST ? (LENS ? my_O : f3{ fp.cam.pos[0], fp.cam.pos[1], fp.cam.pos[2] }) : O_in)
+#define SHADE_HIT_ACC (fp.acc_base + (path >> fp.pix_bits) + 1u)
+#define SHADE_HIT_SEED (FIRST ? pix_seed : path_seed(fp, path & fp.pix_mask))
+#include "shade_hit_body.inc"
+			}
+		}
+		// ---- stream compaction: wave64 ballot + mbcnt prefix inside each wave, one atomic per workgroup and stream ----
+		uint32_t slot, sslot;
+		block_append2(survive, has_shadow, next_queue, shadow_queue, iteration % kSegs, append_scratch, parity, slot, sslot);
+		// (R + unoccluded NEE) + E is finished by k_trace's shadow_finish once the occlusion is known: an emissive hit with a light
+		// record pending sends E along (kDestFull); one without adds E to the path's word here.
+		const bool full = has_shadow & has_E;
+		if (survive) {
+			out.a[slot] = make_float4(P.x, P.y, P.z, __uint_as_float(path));
+			out.b[slot] = make_float4(ndir.x, ndir.y, ndir.z, thr.x);
+			out.c[slot] = make_float2(thr.y, thr.z);
+		}
+		if (has_shadow) {
+			// the record holds its own ray and its path id (kernels.hpp ShadowBuf): k_trace reads nothing of the surviving ray
+			sh.a[sslot] = make_float4(P.x, P.y, P.z, light_distance);
+			sh.b[sslot] = make_float4(L.x, L.y, L.z, __uint_as_float(path | (survive ? 0u : kDestAccum) | (full ? kDestFull : 0u)));
+			sh.c[sslot] = make_float4(srad.x, srad.y, srad.z, 0.0f);
+			if (full) sh.d[sslot] = make_float4(E.x, E.y, E.z, 0.0f);
+		}
+		if (has_E & !has_shadow) {
+			if (FIRST) W0 = { 0.0f + E.x, 0.0f + E.y, 0.0f + E.z };
+			else {
+				float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, path);
+				w[0] += E.x; w[1] += E.y; w[2] += E.z;
+			}
+		}
+		// FIRST is pixel-major — this iteration's lanes are 512 consecutive pixels of one slot, i.e. two contiguous 3-KB runs of the buffer
+		if (FIRST && lane_on) {
+			float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, my_path);
+			w[0] = W0.x; w[1] = W0.y; w[2] = W0.z;
+		}
+		c_term += (terminated && !has_shadow) ? 1u : 0u;
+	}
+	wave_sum(c_term, &ctr->terminated);
+	wave_sum(c_drop, &ctr->dropped);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1520,15 +1769,30 @@ __global__ __launch_bounds__(kTileSize, 4) void k_tile_stream(SceneDev sc, Frame
 // applies that bucket's contributions in ascending k, i.e. in accumulation order.  A thread owns 4 pixels of a tile: per slot it
 // reads their 12 interleaved words (three float4) and adds them to the 4-pixel float4 of each channel plane.
 // SPARSE: a frozen tile is neither read nor written — its words of the contribution buffer are stale (the buffer is never cleared).
+template <bool SPARSE = false>
 __global__ __launch_bounds__(kBlock) void k_merge_contrib(float4* __restrict__ accum, const float4* __restrict__ contrib, uint32_t n_tiles, uint32_t buckets,
-                                                          uint32_t batch_n, uint32_t acc_base) {
-	constexpr bool SPARSE = false; const uint32_t* const tile_frozen = nullptr;
-#include "merge_contrib_body.inc"
-}
-__global__ __launch_bounds__(kBlock) void k_merge_contrib_sparse(float4* __restrict__ accum, const float4* __restrict__ contrib, uint32_t n_tiles, uint32_t buckets,
-                                                                 uint32_t batch_n, uint32_t acc_base, const uint32_t* __restrict__ tile_frozen) {
-	constexpr bool SPARSE = true;
-#include "merge_contrib_body.inc"
+                                                          uint32_t batch_n, uint32_t acc_base, const uint32_t* __restrict__ tile_frozen) {
+	constexpr uint32_t kQuads = kTileSize / 4u;                                 // 4-pixel groups per tile
+	const size_t n_items = static_cast<size_t>(n_tiles) * kQuads;
+	const uint32_t first = min(buckets, batch_n);
+	for (size_t item = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x; item < n_items; item += static_cast<size_t>(gridDim.x) * kBlock) {
+		const size_t tile = item / kQuads; const uint32_t q = static_cast<uint32_t>(item % kQuads);
+		if (SPARSE && tile_frozen[tile] != 0u) continue;
+		for (uint32_t k0 = 0; k0 < first; k0++) {
+			const uint32_t bucket = (acc_base + k0 + 1u) % buckets;
+			float4* dst = accum + (tile * buckets + bucket) * 3u * kQuads + q;  // channel c of the 4 pixels: dst[c * kQuads]
+			float4 r = dst[0], g = dst[kQuads], b = dst[2u * kQuads];
+			for (uint32_t k = k0; k < batch_n; k += buckets) {
+				const float4* src = contrib + ((tile * batch_n + k) * kQuads + q) * 3u;
+				const float4 c0 = src[0], c1 = src[1], c2 = src[2];                // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+				r.x += c0.x; g.x += c0.y; b.x += c0.z;
+				r.y += c0.w; g.y += c1.x; b.y += c1.y;
+				r.z += c1.z; g.z += c1.w; b.z += c2.x;
+				r.w += c2.y; g.w += c2.z; b.w += c2.w;
+			}
+			dst[0] = r; dst[kQuads] = g; dst[2u * kQuads] = b;
+		}
+	}
 }
 
 // ------------------------------------------------------------------------------------------------

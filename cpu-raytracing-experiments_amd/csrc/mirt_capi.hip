@@ -513,32 +513,37 @@ const decltype(&k_trace_fat<true, kPrimaryNone>) kTraceFat[2][3] = {     // [!co
 	{ k_trace_fat<true, kPrimaryNone>, k_trace_fat<true, kPrimaryAll>, k_trace_fat<true, kPrimaryList> },
 	{ k_trace_fat<false, kPrimaryNone>, k_trace_fat<false, kPrimaryAll>, k_trace_fat<false, kPrimaryList> } };
 const decltype(&k_primary_cand<true>) kPrimaryCand[2] = { k_primary_cand<true>, k_primary_cand<false> };                                    // [!count]
-const decltype(&k_primary_hits<true>) kPrimaryHits[2] = { k_primary_hits<true>, k_primary_hits<false> };                                    // [!count]
-const decltype(&k_shade<false, false>) kShade[2][2] = { { k_shade<false, false>, k_shade<false, true> }, { k_shade<true, false>, k_shade<true, true> } };   // [first][ggx]
 const decltype(&k_tile_stream<false>) kTileStream[2] = { k_tile_stream<false>, k_tile_stream<true> };                                         // [ggx]
 static_assert(kPrimaryNone == 0 && kPrimaryAll == 1 && kPrimaryList == 2, "kTrace / kTraceFat are indexed by PRIMARY");
-// The thin-lens twins of the bounce-0 kernels (mirt_set_lens), named after every table above so that those keep their device code.
+// The thin-lens twins of the bounce-0 trace kernels (mirt_set_lens), named after every table above so that those keep their device code.
 const decltype(&k_trace<true, kPrimaryNone>) kTraceLens[2] = { k_trace<true, kPrimaryAll, true>, k_trace<false, kPrimaryAll, true> };               // [!count]
 const decltype(&k_trace_fat<true, kPrimaryNone>) kTraceFatLens[2] = { k_trace_fat<true, kPrimaryAll, true>, k_trace_fat<false, kPrimaryAll, true> };  // [!count]
-const decltype(&k_shade<false, false>) kShadeLens[2] = { k_shade<true, false, true>, k_shade<true, true, true> };                                    // [ggx]
-// One wave per pixel for the batches that fill a wave (kernels.hpp kWaveHitsMinBatch); named last, for the same reason.
-const decltype(&k_primary_hits_wave<true>) kPrimaryHitsWave[2] = { k_primary_hits_wave<true>, k_primary_hits_wave<false> };                         // [!count]
-
-// The twins of the bounce-0 kernels and of the merge that skip frozen tiles (mirt_freeze_tiles), launched only once a tile is frozen; named
-// after every table above, for the same reason.
-const decltype(&k_primary_hits_sparse<true>) kPrimaryHitsSparse[2] = { k_primary_hits_sparse<true>, k_primary_hits_sparse<false> };                 // [!count]
-const decltype(&k_primary_hits_wave_sparse<true>) kPrimaryHitsWaveSparse[2] = { k_primary_hits_wave_sparse<true>, k_primary_hits_wave_sparse<false> };   // [!count]
+// The camera rays of the active tiles once a tile is frozen (mirt_freeze_tiles); named after every table above, for the same reason.
 const decltype(&k_trace_sparse<true, false>) kTraceSparse[2][2] = { { k_trace_sparse<true, false>, k_trace_sparse<true, true> }, { k_trace_sparse<false, false>, k_trace_sparse<false, true> } };   // [!count][lens]
 const decltype(&k_trace_fat<true, kPrimaryNone>) kTraceFatListLens[2] = { k_trace_fat<true, kPrimaryList, true>, k_trace_fat<false, kPrimaryList, true> };   // [!count]
-const decltype(&k_shade_first_sparse<false, false>) kShadeFirstSparse[2][2] = { { k_shade_first_sparse<false, false>, k_shade_first_sparse<false, true> },
-                                                                                { k_shade_first_sparse<true, false>, k_shade_first_sparse<true, true> } };   // [ggx][lens]
-const decltype(&k_first_hit_aov_sparse<false>) kFirstHitAovSparse[2] = { k_first_hit_aov_sparse<false>, k_first_hit_aov_sparse<true> };              // [lens]
-// The twins of every k_shade above whose next event estimation resamples its light (mirt_set_light_ris), launched only while the setting is
-// above 0; named after every table above, for the same reason.
-const decltype(&k_shade_ris<false, false>) kShadeRis[2][2] = { { k_shade_ris<false, false>, k_shade_ris<false, true> }, { k_shade_ris<true, false>, k_shade_ris<true, true> } };   // [first][ggx]
-const decltype(&k_shade_ris<false, false>) kShadeRisLens[2] = { k_shade_ris<true, false, true>, k_shade_ris<true, true, true> };                            // [ggx]
-const decltype(&k_shade_first_sparse_ris<false, false>) kShadeFirstSparseRis[2][2] = { { k_shade_first_sparse_ris<false, false>, k_shade_first_sparse_ris<false, true> },
-                                                                                        { k_shade_first_sparse_ris<true, false>, k_shade_first_sparse_ris<true, true> } };   // [ggx][lens]
+
+// One selector per stage that has SPARSE / LENS / RIS instantiations (kernels.hpp), named after the tables above; within each, the
+// instantiations of the default path first.  sparse = a tile is frozen (mirt_freeze_tiles), ris = mirt_set_light_ris above 0 where NEE runs.
+auto primary_hits_kernel(bool count, bool wave, bool sparse) {      // wave: one wave per pixel, for the batches that fill a wave (kernels.hpp kWaveHitsMinBatch)
+	static const decltype(&k_primary_hits<true>) table[2][2][2] = {      // [sparse][wave][!count]
+		{ { k_primary_hits<true>, k_primary_hits<false> }, { k_primary_hits_wave<true>, k_primary_hits_wave<false> } },
+		{ { k_primary_hits<true, true>, k_primary_hits<false, true> }, { k_primary_hits_wave<true, true>, k_primary_hits_wave<false, true> } } };
+	return table[sparse][wave][!count];
+}
+auto shade_kernel(bool first, bool ggx, bool lens, bool sparse, bool ris) {      // lens and sparse concern bounce 0 (first) only
+	static const decltype(&k_shade<false, false>) table[2][2][2][3] = {    // [ris][sparse][ggx][first ? 1 + lens : 0]
+		{ { { k_shade<false, false>, k_shade<true, false>, k_shade<true, false, true> }, { k_shade<false, true>, k_shade<true, true>, k_shade<true, true, true> } },
+		  { { nullptr, k_shade<true, false, false, true>, k_shade<true, false, true, true> }, { nullptr, k_shade<true, true, false, true>, k_shade<true, true, true, true> } } },
+		{ { { k_shade<false, false, false, false, true>, k_shade<true, false, false, false, true>, k_shade<true, false, true, false, true> },
+		    { k_shade<false, true, false, false, true>, k_shade<true, true, false, false, true>, k_shade<true, true, true, false, true> } },
+		  { { nullptr, k_shade<true, false, false, true, true>, k_shade<true, false, true, true, true> }, { nullptr, k_shade<true, true, false, true, true>, k_shade<true, true, true, true, true> } } } };
+	return table[ris][first && sparse][ggx][first ? 1 + lens : 0];
+}
+auto first_hit_aov_kernel(bool lens, bool sparse) {
+	static const decltype(&k_first_hit_aov<false>) table[2][2] = { { k_first_hit_aov<false>, k_first_hit_aov<true> }, { k_first_hit_aov<false, true>, k_first_hit_aov<true, true> } };   // [sparse][lens]
+	return table[sparse][lens];
+}
+auto merge_kernel(bool sparse) { return sparse ? k_merge_contrib<true> : k_merge_contrib<false>; }
 
 // What varies between the launches of the trace stage: a bounce of a batch, or the rays of a debug entry point.
 struct TraceLaunch {
@@ -622,8 +627,7 @@ int launch_first_hit_aov(mirt_ctx* c, PipeSlot& sl, hipStream_t st, const SceneD
 	{ Bracket t(c, MIRT_K_RESOLVE, st);
 	  const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
 	  const float4* colour = c->policy.brdf ? c->mat_ggx.as<float4>() : c->scene.mat_albedo;
-	  if (c->n_frozen) hipLaunchKernelGGL(kFirstHitAovSparse[lens_on(c)], dim3(grid), dim3(kBlock), 0, st, sc, fp, sl.hit, colour, c->aov.as<float>(), c->lens, c->tile_frozen.as<uint32_t>());
-	  else hipLaunchKernelGGL(lens_on(c) ? k_first_hit_aov<true> : k_first_hit_aov<false>, dim3(grid), dim3(kBlock), 0, st, sc, fp, sl.hit, colour, c->aov.as<float>(), c->lens); }
+	  hipLaunchKernelGGL(first_hit_aov_kernel(lens_on(c), c->n_frozen != 0), dim3(grid), dim3(kBlock), 0, st, sc, fp, sl.hit, colour, c->aov.as<float>(), c->lens, c->tile_frozen.as<uint32_t>()); }
 	if (pipelined) { HIP_TRY(c, hipEventRecord(sl.aov_done, st)); c->aov_prev = sl.aov_done; }
 	return MIRT_OK;
 }
@@ -641,7 +645,7 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 	FrameParams fp = frame_params(c, c->accumulations, batch_n);
 	const uint32_t nb = c->policy.max_bounces;
 	const uint64_t total = static_cast<uint64_t>(fp.n_pix) * batch_n;
-	// Once a tile is frozen (mirt_freeze_tiles) bounce 0 and the merge run their sparse twins; while none is, every launch below is what it has always been.
+	// Once a tile is frozen (mirt_freeze_tiles) bounce 0 and the merge run their SPARSE instantiations; while none is, every launch below picks the dense ones.
 	const bool sparse = c->n_frozen != 0;
 	const uint32_t* tile_frozen = c->tile_frozen.as<uint32_t>();
 	const uint32_t active_pix = (c->n_tiles - c->n_frozen) * kTileSize;
@@ -716,17 +720,12 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			    // camera rays through the per-pixel candidate lists (kernels.hpp kCollect): k_primary_hits intersects every sample with its pixel's list.
 			    // Pixels without a list are listed in cand_listed (count: listed_pixels) and all their samples traced like any other ray.
 			    // A batch that fills a wave runs one wave per pixel, lanes = accumulations, over runs of 16 pixels (k_primary_hits_wave); a smaller one keeps one lane per pixel.
-			    if (batch_n >= kWaveHitsMinBatch) {
-			      // 8 KB of LDS per wave: five workgroups per CU are resident; four times that, grid-stride, so that a CU which gets fewer is not the tail
-			      const uint64_t runs = static_cast<uint64_t>(fp.n_pix) / kWaveHitsRun;
-			      const uint32_t wgrid = static_cast<uint32_t>(std::min<uint64_t>((runs + kWaveHitsWaves - 1) / kWaveHitsWaves, static_cast<uint64_t>(c->n_cu) * 20u));
-			      if (sparse) hipLaunchKernelGGL(kPrimaryHitsWaveSparse[!count], dim3(wgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr, tile_frozen, active_pix);
-			      else hipLaunchKernelGGL(kPrimaryHitsWave[!count], dim3(wgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr);
-			    } else {
-			      const uint32_t hgrid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
-			      if (sparse) hipLaunchKernelGGL(kPrimaryHitsSparse[!count], dim3(hgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr, tile_frozen, active_pix);
-			      else hipLaunchKernelGGL(kPrimaryHits[!count], dim3(hgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr);
-			    }
+			    const bool wave = batch_n >= kWaveHitsMinBatch;
+			    // wave: 8 KB of LDS per wave: five workgroups per CU are resident; four times that, grid-stride, so that a CU which gets fewer is not the tail
+			    const uint64_t runs = static_cast<uint64_t>(fp.n_pix) / kWaveHitsRun;
+			    const uint32_t wgrid = static_cast<uint32_t>(std::min<uint64_t>((runs + kWaveHitsWaves - 1) / kWaveHitsWaves, static_cast<uint64_t>(c->n_cu) * 20u));
+			    const uint32_t hgrid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
+			    hipLaunchKernelGGL(primary_hits_kernel(count, wave, sparse), dim3(wave ? wgrid : hgrid), dim3(kBlock), 0, st, sc, fp, c->cand.as<uint32_t>(), sl.hit, ctr, tile_frozen, active_pix);
 			  }
 			  // the adds of bounce-1 that waited for occlusion land in the paths' contribution words before k_shade adds this bounce's terms;
 			  const ShadowSink sink{ contrib, batch_n, fp.pix_bits, nullptr };
@@ -744,20 +743,10 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			{ Bracket t(c, MIRT_K_SHADE, st);
 			  // policy.brdf = 1 (#define BRDF 1): Closure<GGX> with this bounce's gloss decay, passed by value
 			  const float decay = bounce < c->gloss_decay.size() ? c->gloss_decay[bounce] : 0.0f;
-			  // mirt_set_light_ris: the candidate loop is worth its twins only where NEE runs; without it every launch below is what it has always been
+			  // mirt_set_light_ris: the candidate loop is worth running only where NEE runs
 			  const uint32_t ris = fp.mis ? c->light_ris : 0u;
-			  if (ris && sparse && bounce == 0)
-			    hipLaunchKernelGGL(kShadeFirstSparseRis[c->policy.brdf != 0][lens], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
-			                       bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, tile_frozen, ris);
-			  else if (ris)
-			    hipLaunchKernelGGL(bounce == 0 && lens ? kShadeRisLens[c->policy.brdf != 0] : kShadeRis[bounce == 0][c->policy.brdf != 0], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
-			                       bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, ris);
-			  else if (sparse && bounce == 0)
-			    hipLaunchKernelGGL(kShadeFirstSparse[c->policy.brdf != 0][lens], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
-			                       bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, tile_frozen);
-			  else
-			    hipLaunchKernelGGL(bounce == 0 && lens ? kShadeLens[c->policy.brdf != 0] : kShade[bounce == 0][c->policy.brdf != 0], dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
-			                       bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens); }
+			  hipLaunchKernelGGL(shade_kernel(bounce == 0, c->policy.brdf != 0, lens, sparse, ris != 0), dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
+			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, ris, tile_frozen); }
 		}
 	}
 	HIP_TRY(c, hipGetLastError());
@@ -768,8 +757,7 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 	}
 	{ Bracket t(c, MIRT_K_RESOLVE);
 	  const dim3 mgrid(grid_for(c, static_cast<uint64_t>(c->n_tiles) * (kTileSize / 4u)));
-	  if (sparse) hipLaunchKernelGGL(k_merge_contrib_sparse, mgrid, dim3(kBlock), 0, c->stream, c->accumulator.as<float4>(), sl.contrib.as<float4>(), c->n_tiles, c->policy.buckets, batch_n, fp.acc_base, tile_frozen);
-	  else hipLaunchKernelGGL(k_merge_contrib, mgrid, dim3(kBlock), 0, c->stream, c->accumulator.as<float4>(), sl.contrib.as<float4>(), c->n_tiles, c->policy.buckets, batch_n, fp.acc_base); }
+	  hipLaunchKernelGGL(merge_kernel(sparse), mgrid, dim3(kBlock), 0, c->stream, c->accumulator.as<float4>(), sl.contrib.as<float4>(), c->n_tiles, c->policy.buckets, batch_n, fp.acc_base, tile_frozen); }
 	HIP_TRY(c, hipGetLastError());
 	if (pipelined) { HIP_TRY(c, hipEventRecord(sl.merged, c->stream)); sl.in_use = true; }
 	c->batch_seq++;

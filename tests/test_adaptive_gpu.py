@@ -377,7 +377,7 @@ def test_listed_pixels_of_frozen_tiles_are_not_traced(mirt):
             want[k] += c[k]
     assert {k: got[k] for k in keys} == want
     # Are the listed pixels of FROZEN tiles still traced?  Words and the counters above cannot tell (nobody reads those hit records, and `rays` comes
-    # from k_primary_hits_sparse), the camera rays' box tests can: a counting context adds, per batch, the lists' build — the same cones over every
+    # from k_primary_hits<COUNT, SPARSE = true>), the camera rays' box tests can: a counting context adds, per batch, the lists' build — the same cones over every
     # owned pixel, the same number each batch — plus the tree walk of the listed pixels' samples, whose rays differ from batch to batch.  With every
     # tile that holds a listed pixel frozen, nothing is left to walk: `nodes` grows by the same amount in every batch, and by less than in a plain
     # context, whose amounts differ.

@@ -1,4 +1,4 @@
-"""Resampled importance sampling of the NEE light on the device (mirt_set_light_ris; k_shade_ris, shade_hit_body.inc).
+"""Resampled importance sampling of the NEE light on the device (mirt_set_light_ris; k_shade<..., RIS = true>, shade_hit_body.inc).
 
 1  one candidate is the plain path word for word, so the RIS kernels must give the ORACLE's words;
 1b the oracle carries the candidate loop itself (orc_set_light_ris, held to the float64 estimator in tests/test_light_ris_cpu.py): every RIS twin
@@ -181,7 +181,7 @@ def check_frozen_against_oracle(mirt, sc, key, w, h, routes, max_bounces=16, set
 
 @pytest.mark.parametrize("name", ["default9", "brdf_test_ggx"])
 def test_sparse_twins_are_the_oracle(mirt, name):
-    """k_shade_first_sparse_ris<GGX, LENS = false>, through the camera-ray lists and through traced camera rays."""
+    """k_shade<true, GGX, LENS = false, SPARSE = true, RIS = true>, through the camera-ray lists and through traced camera rays."""
     make, w, h, kw = MANY_CANDIDATES[name]
     check_frozen_against_oracle(mirt, make(mirt), name, w, h, (ROUTES[0], ROUTES[2]), light_ris=7, **kw)
 
