@@ -11,6 +11,9 @@ plus the few listed here) the departure is a NAMED argument or a named expectati
       so the last column / row is reached only at u = 1 / v = 1 exactly.
   D3  GGX D takes max(alpha^2, 1e-5) while the masking term takes alpha^2 itself (Sampling.hpp:295).
   D4  the cone pdf divides by max(1 - cos(theta_max), 1e-6) (Sampling.hpp:192-194).
+  D7  the visible-normal sample warps the disk along the second axis of the branch-free basis (Duff et al. 2017) about the stretched view
+      direction, not along the axis in the plane of that direction and the normal (Sampling.hpp:261), and clamps the normals this puts
+      below the surface onto the horizon (Sampling.hpp:268): `axis` and `clamp` of ggx_visible_normal.
 
 Every function takes and returns float64 arrays; `u` is the binary32 unit roundoff the error models are written in."""
 import numpy as np
@@ -229,6 +232,86 @@ def ggx_vndf_weight(F0, alpha, L, V):
     lv, ll = ggx_lambda(a2, nv), ggx_lambda(a2, nl)
     w = np.where(nl > 0, (1.0 + lv) / (1.0 + lv + ll), 0.0)
     return schlick(F0, hv) * w[:, None], H, w, hv
+
+
+def ggx_g1(alpha2, cos_theta):
+    """Smith masking of one direction (Heitz 2014, eq. 43): 1 / (1 + Lambda)."""
+    return 1.0 / (1.0 + ggx_lambda(alpha2, cos_theta))
+
+
+def ggx_vndf(alpha, V, H):
+    """Density, per solid angle of H, of the normals visible from V (Heitz 2014, eq. 2; Heitz 2018, eq. 1):
+    G1(V) max(0, V.H) D(H) / V.z; 0 for H below the surface.  V (3,), H (..., 3), both unit."""
+    a2 = alpha * alpha
+    D = np.where(H[..., 2] > 0.0, ggx_d(a2, np.maximum(H[..., 2], 0.0))[0], 0.0)
+    return ggx_g1(a2, V[2]) * np.maximum(0.0, (H * V).sum(axis=-1)) * D / V[2]
+
+
+def duff_basis(n):
+    """The branch-free orthonormal basis of Duff et al. 2017 (JCGT 6(1), listing 3) about unit vectors n (..., 3):
+    s = copysign(1, n.z), a = -1 / (s + n.z), b = n.x n.y a;  b1 = (1 + s n.x^2 a, s b, -s n.x),  b2 = (b, s + n.y^2 a, -n.y)."""
+    s = np.copysign(1.0, n[..., 2])
+    a = -1.0 / (s + n[..., 2])
+    b = n[..., 0] * n[..., 1] * a
+    return (np.stack([1.0 + s * n[..., 0] ** 2 * a, s * b, -s * n[..., 0]], axis=-1),
+            np.stack([b, s + n[..., 1] ** 2 * a, -n[..., 1]], axis=-1))
+
+
+def ggx_visible_normal(alpha, V, u, v, axis="reference", clamp=True):
+    """A normal sampled from the distribution of visible normals by Heitz 2018's construction (JCGT 7(4), listing 1, with the disk taken
+    as r = sqrt(u), phi = 2 pi v): stretch V by alpha, Vh = normalize(alpha V.x, alpha V.y, V.z); a point (t1, t2) of the unit disk;
+    t2 <- (1 - s) sqrt(1 - t1^2) + s t2 with s = (1 + Vh.z) / 2; lift, Nh = t1 A1 + t2 A2 + sqrt(1 - t1^2 - t2^2) Vh; unstretch,
+    H = normalize(alpha Nh.x, alpha Nh.y, Nh.z).  `axis` names the pair (A1, A2) that spans the disk:
+      "heitz"      T1 = normalize(z x Vh) ((1, 0, 0) at Vh = z), T2 = Vh x T1: the warp acts along T2, the axis in the plane of Vh and the
+                   surface normal, towards the normal.  The push-forward of the uniform square is then ggx_vndf (checked by quadrature in
+                   the tests) and Nh.z >= 0 always.
+      "reference"  D7: (A1, A2) = duff_basis(Vh) (Sampling.hpp:116-130, :261), the Heitz pair turned about Vh by psi:
+                   A1 = cos(psi) T1 + sin(psi) T2, A2 = -sin(psi) T1 + cos(psi) T2.  With phi_V the azimuth of V, psi = -(phi_V + pi / 2):
+                   0 only for V.x = 0 with V.y < 0, pi (the warp pushes AWAY from the normal) for V.x = 0 with V.y > 0.
+    `clamp` is the second half of D7: max(0, Nh.z) before the last normalisation (Sampling.hpp:268), which moves the normals that the turned
+    warp puts below the surface onto the horizon, H.z = 0 exactly.
+    alpha, V[..., 0], u and v broadcast against each other (one view and many samples, or a view per sample); V unit with V.z > 0
+    -> H (..., 3), psi in (-pi, pi] of V's own shape (a float for one view)."""
+    V, u, v, alpha = np.asarray(V, dtype=np.float64), np.asarray(u, dtype=np.float64), np.asarray(v, dtype=np.float64), np.asarray(alpha, dtype=np.float64)
+    Vh = np.stack(np.broadcast_arrays(alpha * V[..., 0], alpha * V[..., 1], V[..., 2]), axis=-1)
+    Vh = Vh / np.linalg.norm(Vh, axis=-1, keepdims=True)
+    T1 = np.stack([-Vh[..., 1], Vh[..., 0], np.zeros(Vh.shape[:-1])], axis=-1)
+    length = np.linalg.norm(T1, axis=-1, keepdims=True)
+    T1 = np.where(length > 0.0, T1 / np.where(length > 0.0, length, 1.0), np.array([1.0, 0.0, 0.0]))
+    T2 = np.cross(Vh, T1)
+    B1, B2 = duff_basis(Vh)
+    psi = np.arctan2((B1 * T2).sum(axis=-1), (B1 * T1).sum(axis=-1))
+    assert np.abs((B2 * T1).sum(axis=-1) + np.sin(psi)).max() <= 1e-9 and np.abs((B2 * T2).sum(axis=-1) - np.cos(psi)).max() <= 1e-9   # a rotation, not a reflection
+    A1, A2 = {"heitz": (T1, T2), "reference": (B1, B2)}[axis]
+    r, phi = np.sqrt(u), 2.0 * np.pi * v
+    t1, t2 = r * np.cos(phi), r * np.sin(phi)
+    s = 0.5 * (1.0 + Vh[..., 2])
+    t2 = (1.0 - s) * np.sqrt(np.maximum(0.0, 1.0 - t1 * t1)) + s * t2
+    Nh = t1[..., None] * A1 + t2[..., None] * A2 + np.sqrt(np.maximum(0.0, 1.0 - t1 * t1 - t2 * t2))[..., None] * Vh
+    H = np.stack(np.broadcast_arrays(alpha * Nh[..., 0], alpha * Nh[..., 1], np.maximum(0.0, Nh[..., 2]) if clamp else Nh[..., 2]), axis=-1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        H = H / np.linalg.norm(H, axis=-1, keepdims=True)
+    H = np.where(np.isfinite(H), H, np.array([0.0, 0.0, 1.0]))                      # alpha = 0 with the clamp at work: the mirror's normal
+    return H, (float(psi) if psi.ndim == 0 else psi)
+
+
+def frame_about(N):
+    """Rotation matrices (m, 3, 3) of the shortest arc that takes +z to the unit vectors N (m, 3): R e_z = N; columns 0 and 1 are the
+    tangent axes of the local frame (to_world(v) = R v, to_local(v) = R^T v).  From the quaternion (-N.y, N.x, 0, 1 + N.z), normalised."""
+    q = np.stack([-N[:, 1], N[:, 0], np.zeros(len(N)), 1.0 + N[:, 2]], axis=1)
+    return rotation_of_quaternion(q / np.linalg.norm(q, axis=1, keepdims=True))
+
+
+def chi2_upper(dof, p):
+    """Upper-p quantile of chi-square with `dof` degrees of freedom: scipy's where it is installed, else Wilson & Hilferty 1931,
+    dof (1 - 2 / (9 dof) + z sqrt(2 / (9 dof)))^3 with z the normal quantile (at p = 1e-6: 0.7 % above scipy's at 30 degrees of freedom, 0.16 % at 100, 0.05 % at 255 - the fallback is the looser one, slightly)."""
+    try:
+        from scipy.stats import chi2
+        return float(chi2.isf(p, dof))
+    except ImportError:
+        from statistics import NormalDist
+        z = NormalDist().inv_cdf(1.0 - p)
+        return float(dof * (1.0 - 2.0 / (9.0 * dof) + z * np.sqrt(2.0 / (9.0 * dof))) ** 3)
 
 
 def hemisphere_grid(n_theta, n_phi):
@@ -458,13 +541,29 @@ def direct_no_mis(x, n, rho, lights, blockers=NO_BLOCKERS, n_u=16, n_phi=32):
     return dict(E=E, M2=M2, var=M2 - E * E, shadow=np.zeros(len(x)))
 
 
-def path_sampler(scene, x, n, n_paths, max_bounces, rng, mis=True, q5=True, q8=True, prim0=0):
+def ggx_vndf_pdf_of_direction(alpha, L, V):
+    """Density, per solid angle of L, of the reflection of V about a visible normal (Heitz 2018, eq. 17): D_V(H) / (4 V.H) =
+    G1(V) D(H) / (4 V.z).  What Closure<GGX>::pdf would be had the reference written it; it returns 0 (DataStreams.hpp:196-198)."""
+    H = L + V
+    H = H / np.linalg.norm(H, axis=-1, keepdims=True)
+    a2 = alpha * alpha
+    return np.where((L[..., 2] > 0.0) & (H[..., 2] > 0.0), ggx_g1(a2, V[..., 2]) * ggx_d(np.maximum(a2, 1e-5), np.maximum(H[..., 2], 0.0))[0] / (4.0 * V[..., 2]), 0.0)
+
+
+def path_sampler(scene, x, n, n_paths, max_bounces, rng, mis=True, q5=True, q8=True, prim0=0, brdf=0, view=None, decay=(), axis="reference", clamp=True,
+                 closure_pdf="zero"):
     """A plain path tracer in float64 numpy for Lambertian spheres, one light sample and one cosine-distributed closure sample a bounce.
     scene: dict centre (k, 3), radius_sq (k,), albedo (k, 3), emission (k, 3).  Every row of x, n (m, 3) - a first hit on sphere `prim0`
     and its unit normal - starts n_paths paths.  Textbook throughout (cosine sampling by Malley's method, uniform cone sampling,
     sphere_roots for every intersection, its own generator) with the named departures: Q5 (a path that still hits on the last bounce
     is dropped whole; `q5`), Q6 (roulette from bounce 0 with max(throughput), unclamped), Q8 / D5 (`q8`), Q9 (an emissive hit adds its raw
     emission at bounce 0 or without MIS), D4, D6.  The sky is black (Q10 cannot appear).
+    brdf = 1 is the GGX closure (part G): scene carries F0 (k, 3) and roughness (k,) as well, `view` (m, 3) the unit directions from the
+    first hits back to the eye, `decay` the gloss-decay table (0 beyond its length).  Per bounce alpha = a^2 + (1 - a^2) decay[bounce] with
+    a the roughness; the light sample carries Le thr f cos / p_l - ggx_eval_cos, and the closure pdf is 0 as the reference wrote it, so D6's
+    floored heuristic p_l / max(1e-6, p_l^2 + 0) is 1 / p_l and an emissive hit past bounce 0 weighs 0; the bounce reflects the view about
+    ggx_visible_normal(axis, clamp) (D7) and multiplies the throughput by ggx_vndf_weight BEFORE the roulette takes max(throughput).
+    `closure_pdf="vndf"` is a what-if for the guards: the true density ggx_vndf_pdf_of_direction in both MIS weights.
     -> dict sum, sum_sq (m, 3): over the n_paths contributions of each row; shadow, rays (m,): shadow rays cast and rays traced beyond
     the given first hit; dropped (m,)."""
     centre, r2 = np.asarray(scene["centre"], dtype=np.float64), np.asarray(scene["radius_sq"], dtype=np.float64)
@@ -475,6 +574,9 @@ def path_sampler(scene, x, n, n_paths, max_bounces, rng, mis=True, q5=True, q8=T
     row = np.repeat(np.arange(m), n_paths)
     N = len(row)
     nrm = np.asarray(n, dtype=np.float64)[row]
+    ggx = brdf == 1
+    if ggx:
+        F0, rough, Vw = np.asarray(scene["F0"], dtype=np.float64), np.asarray(scene["roughness"], dtype=np.float64), np.asarray(view, dtype=np.float64)[row].copy()
     P = np.asarray(x, dtype=np.float64)[row] + OFFSET * nrm
     prim = np.full(N, prim0)
     thr, rad = np.ones((N, 3)), np.zeros((N, 3))
@@ -501,6 +603,11 @@ def path_sampler(scene, x, n, n_paths, max_bounces, rng, mis=True, q5=True, q8=T
                 rad[a] = 0.0
                 np.add.at(out["dropped"], row[a], 1.0)
             break
+        if ggx:
+            R = frame_about(nrm[a])
+            Vl = np.einsum("nji,nj->ni", R, Vw[a])
+            a2r = rough[prim[a]] ** 2
+            alpha = a2r + (1.0 - a2r) * (decay[bounce] if bounce < len(decay) else 0.0)
         if mis and len(lights):
             pick = lights[rng.integers(0, len(lights), len(a))]
             wc = centre[pick] - P[a]
@@ -517,8 +624,16 @@ def path_sampler(scene, x, n, n_paths, max_bounces, rng, mis=True, q5=True, q8=T
             w = sin_t[:, None] * (np.cos(phi)[:, None] * t_ + np.sin(phi)[:, None] * b_) + cos_t[:, None] * wc
             cos_n = (w * nrm[a]).sum(axis=1)
             p_l = pdf_c / len(lights)
-            p_b = np.maximum(0.0, cos_n) / np.pi
-            contrib = emission[pick] * thr[a] * albedo[prim[a]] * (p_b * p_l / np.maximum(1e-6, p_l * p_l + p_b * p_b))[:, None]     # D6
+            if ggx:
+                Ll = np.einsum("nji,nj->ni", R, w)
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    f = ggx_eval_cos(F0[prim[a]], alpha, Ll, Vl)[0]
+                    p_b = ggx_vndf_pdf_of_direction(alpha, Ll, Vl) if closure_pdf == "vndf" else np.zeros(len(a))
+                contrib = emission[pick] * thr[a] * np.nan_to_num(f) * (p_l / np.maximum(1e-6, p_l * p_l + p_b * p_b))[:, None]          # D6
+                cos_n = Ll[:, 2]
+            else:
+                p_b = np.maximum(0.0, cos_n) / np.pi
+                contrib = emission[pick] * thr[a] * albedo[prim[a]] * (p_b * p_l / np.maximum(1e-6, p_l * p_l + p_b * p_b))[:, None]     # D6
             cast = ok & (cos_n >= 0.0) & (contrib.max(axis=1) > 0.0)
             reach = d * cos_t - np.sqrt(np.maximum(0.0, r2[pick] - (d * sin_t) ** 2))
             t_near, _ = nearest(P[a], w, skip=pick)
@@ -531,15 +646,31 @@ def path_sampler(scene, x, n, n_paths, max_bounces, rng, mis=True, q5=True, q8=T
             rad[a] += np.where(em[:, None], thr[a] * power_heuristic(pdf_in[a], g)[:, None] * emission[prim[a]], 0.0)
         else:
             rad[a] += np.where(em[:, None], emission[prim[a]], 0.0)                  # Q9
-        thr[a] = thr[a] * albedo[prim[a]]
-        p = thr[a].max(axis=1)
-        live = rng.random(len(a)) < p                                                # Q6
-        a = a[live]
-        thr[a] = thr[a] / p[live][:, None]
-        r_, phi = np.sqrt(rng.random(len(a))), 2.0 * np.pi * rng.random(len(a))      # Malley: a uniform disk, lifted
-        t_, b_ = basis_about(nrm[a])
-        w = (r_ * np.cos(phi))[:, None] * t_ + (r_ * np.sin(phi))[:, None] * b_ + np.sqrt(np.maximum(0.0, 1.0 - r_ * r_))[:, None] * nrm[a]
-        pdf_in[a] = np.maximum(0.0, w[:, 2] if q8 else (w * nrm[a]).sum(axis=1)) / np.pi                                             # D5
+        if ggx:
+            H = ggx_visible_normal(alpha, Vl, rng.random(len(a)), rng.random(len(a)), axis=axis, clamp=clamp)[0]
+            L = 2.0 * (H * Vl).sum(axis=1)[:, None] * H - Vl
+            L = L / np.linalg.norm(L, axis=1, keepdims=True)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                est = np.where((L[:, 2] > 0.0)[:, None], np.nan_to_num(ggx_vndf_weight(F0[prim[a]], alpha, L, Vl)[0]), 0.0)
+                pdf_new = ggx_vndf_pdf_of_direction(alpha, L, Vl) if closure_pdf == "vndf" else np.zeros(len(a))
+            thr[a] = thr[a] * est
+            p = thr[a].max(axis=1)
+            live = rng.random(len(a)) < p                                            # Q6, on the estimator
+            a = a[live]
+            thr[a] = thr[a] / p[live][:, None]
+            w = np.einsum("nij,nj->ni", R[live], L[live])
+            pdf_in[a] = pdf_new[live]
+            Vw[a] = -w
+        else:
+            thr[a] = thr[a] * albedo[prim[a]]
+            p = thr[a].max(axis=1)
+            live = rng.random(len(a)) < p                                            # Q6
+            a = a[live]
+            thr[a] = thr[a] / p[live][:, None]
+            r_, phi = np.sqrt(rng.random(len(a))), 2.0 * np.pi * rng.random(len(a))  # Malley: a uniform disk, lifted
+            t_, b_ = basis_about(nrm[a])
+            w = (r_ * np.cos(phi))[:, None] * t_ + (r_ * np.sin(phi))[:, None] * b_ + np.sqrt(np.maximum(0.0, 1.0 - r_ * r_))[:, None] * nrm[a]
+            pdf_in[a] = np.maximum(0.0, w[:, 2] if q8 else (w * nrm[a]).sum(axis=1)) / np.pi                                         # D5
         origin[a] = P[a]
         np.add.at(out["rays"], row[a], 1.0)
         t_hit, k = nearest(P[a], w)

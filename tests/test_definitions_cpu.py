@@ -10,9 +10,11 @@ measured on the CPU oracle and given a stated margin; the measured figure is in 
 Reference departures from the textbook are named expectations (D1-D4 in definitions.py, Q rows of SURVEY.md §8a).
 
 Part F holds next-event estimation and MIS to float64 expectations of the estimator the reference implements (Q8 and Q9 are named
-departures there, not reasons to look away) for the Lambertian closure.  Left out: the GGX closure inside the path (the density of the
-reference's visible-normal sample is not stated yet) and Q11 under a differing authoring order; stream order and Q14
-(fused body, unfused tail) are arithmetic, not definitions.  Those rows stay pinned by parity alone."""
+departures there, not reasons to look away) for the Lambertian closure.  Part C holds the GGX closure's sampled normal to its stated
+density (D7) by chi-square; part G holds the GGX closure inside the path (light sample, roulette, per-bounce roughness, Q5 under it) to
+float64 expectations, G3 from a grazing camera.  Left open: inside the path the axis and the clamp of D7 are not told apart under the
+cap of 1 500 accumulations, and Q11 under a differing authoring order; stream order and Q14 (fused body, unfused tail) are
+arithmetic, not definitions.  Those rows stay pinned by parity alone."""
 import math
 
 import numpy as np
@@ -485,6 +487,199 @@ def test_ggx_energy(be, mirt):
     check_ggx_energy(be, mirt)
 
 
+# ---- C, the distribution of the sampled normal (D7) -------------------------------------------------------------------------------
+# (alpha, cos V, azimuth of V in degrees).  psi = -(azimuth + 90 degrees) is the angle by which the reference turns Heitz's disk axes about
+# the stretched V (definitions.ggx_visible_normal): 0 at -90 (V.x = 0, V.y < 0), 180 degrees at +90 (V.x = 0, V.y > 0), V.x != 0 elsewhere.
+VN_PAIRS = [(0.05, 0.9, 0.0), (0.05, 0.3, 30.0), (0.3, 0.9, 0.0), (0.3, 0.5, 200.0), (0.3, 0.1, 45.0), (1.0, 0.7, 0.0), (1.0, 0.2, 120.0),
+            (0.3, 0.3, -90.0), (1.0, 0.3, 90.0)]
+VN_TEXTBOOK = [(0.3, 0.9, 0.0), (1.0, 0.3, 60.0), (0.05, 0.2, 200.0), (0.3, 0.1, -90.0)]     # section-2 pairs: two at cos V <= 0.3
+VN_N, VN_P = 20000, 1e-6                  # samples per pair; the level of the chi-square test, fixed beforehand
+VN_GRID = 1024                            # (u, v) midpoints a side behind the expected bin probabilities
+VN_HORIZON = 16 * u                       # a rebuilt half vector with |H.z| below this was clamped (the clamp gives H.z = 0, L.z = -V.z exactly; the backend's H is
+                                          # rebuilt from a binary32 direction + V, the definition's H.z is exactly 0; unclamped mass inside the band: about 1e-6 of a cell)
+_vn_cache = {}
+
+
+def vn_view(cos_v, phi_deg):
+    """The binary32 view direction of a pair, as float64; V.x is exactly 0 at +-90 degrees."""
+    s, phi = math.sqrt(1.0 - cos_v * cos_v), math.radians(phi_deg)
+    v = np.array([0.0 if abs(phi_deg) == 90.0 else s * math.cos(phi), s * math.sin(phi), cos_v]).astype(f32).astype(f64)
+    return v / np.linalg.norm(v)
+
+
+def vn_bin(H, edges):
+    """Cell of half vectors H (n, 3): 16 rows in H.z between `edges` x 16 equal sectors of azimuth about the normal, then 16 cells by
+    azimuth for the clamped mass at H.z = 0, then one cell for whatever lies below the surface (nothing does under D7)."""
+    az = np.minimum((16 * (np.arctan2(H[:, 1], H[:, 0]) % (2 * np.pi)) / (2 * np.pi)).astype(int), 15)
+    row = np.searchsorted(edges[1:-1], H[:, 2], side="right")
+    return np.where(H[:, 2] < -VN_HORIZON, 272, np.where(H[:, 2] <= VN_HORIZON, 256 + az, 16 * row + az))
+
+
+def vn_grid_probabilities(alpha, V, edges, n, axis="reference", clamp=True):
+    """Probability of each of the 273 cells under the definition: the share of an n x n midpoint grid over (u, v) that lands in it."""
+    key = (alpha, tuple(V), tuple(edges), n, axis, clamp)
+    if key not in _vn_cache:
+        counts = np.zeros(273)
+        mid = (np.arange(n) + 0.5) / n
+        for lo in range(0, n, 256):
+            uu, vv = np.meshgrid(mid[lo:lo + 256], mid, indexing="ij")
+            H = df.ggx_visible_normal(alpha, V, uu.reshape(-1), vv.reshape(-1), axis=axis, clamp=clamp)[0]
+            counts += np.bincount(vn_bin(H, edges), minlength=273)
+        _vn_cache[key] = counts / (n * n)
+    return _vn_cache[key]
+
+
+def vn_edges(alpha, V, axis="reference"):
+    """Row edges in H.z: the sixteen-quantiles of the definition's own H.z above the horizon (a 256 x 256 grid), so that a narrow lobe
+    (alpha = 0.05: all of it within 1e-3 of H.z = 1) is resolved as well as a wide one.  Fixed by the definition, never by a backend."""
+    mid = (np.arange(256) + 0.5) / 256
+    uu, vv = np.meshgrid(mid, mid, indexing="ij")
+    z = df.ggx_visible_normal(alpha, V, uu.reshape(-1), vv.reshape(-1), axis=axis)[0][:, 2]
+    q = np.quantile(z[z > VN_HORIZON], np.arange(1, 16) / 16.0)
+    return np.concatenate([[0.0], q, [1.0]])
+
+
+def vn_density_probabilities(alpha, V, edges, m):
+    """The same cells under the closed-form density definitions.ggx_vndf: midpoint rule on m x m points of each cell in (polar angle, azimuth)
+    with the solid angle's sine.  The horizon cells carry nothing."""
+    out = np.zeros(273)
+    s = (np.arange(m) + 0.5) / m
+    for row in range(16):
+        t0, t1 = math.acos(edges[row + 1]), math.acos(edges[row])
+        theta = t0 + s * (t1 - t0)
+        for col in range(16):
+            phi = (col + s) * (2 * np.pi / 16)
+            T, P = np.meshgrid(theta, phi, indexing="ij")
+            H = np.stack([np.sin(T) * np.cos(P), np.sin(T) * np.sin(P), np.cos(T)], axis=-1)
+            out[16 * row + col] = (df.ggx_vndf(alpha, V, H) * np.sin(T)).mean() * (t1 - t0) * (2 * np.pi / 16)
+    return out
+
+
+def test_visible_normal_definition():
+    """D7's definition against the textbook, no backend: with Heitz's axes and no clamp the push-forward of the uniform square through
+    definitions.ggx_visible_normal is the visible-normal density G1(V) max(0, V.H) D(H) / V.z, cell by cell of the 16 x 16 grid (no mass
+    below the surface).  Bound on the largest cell difference: twice the change of the grid's cell probabilities from 1024 to 2048 midpoints a
+    side, plus twice the change of the density's cell integrals from 32 to 64 points a side, plus 1e-6 - and that bound is itself below 5 % of
+    a cell's mean mass, so a turned axis (tens of per cent) cannot hide in it.  The reference axis is Heitz's turned by psi = -(azimuth of V
+    + 90 degrees): 0 for V.x = 0 with V.y < 0, where the two agree to rounding; not 0 for V.x != 0; 180 degrees for V.x = 0 with V.y > 0
+    (the warp pushes away from the normal).  The mass the clamp moves onto the horizon is reported per pair.
+    Measured: largest cell difference / bound 0.16, 0.37, 0.18, 0.42 (bound 2.1e-5 ... 1.6e-4 against a mean cell mass of 3.9e-3); the
+    horizon mass under D7 for VN_PAIRS, 0 ... 0.63: DESIGN.md section 2."""
+    figures = {}
+    for alpha, cv, phi in VN_TEXTBOOK:
+        V = vn_view(cv, phi)
+        edges = vn_edges(alpha, V, axis="heitz")
+        p1, p2 = (vn_grid_probabilities(alpha, V, edges, n, axis="heitz", clamp=False) for n in (VN_GRID, 2 * VN_GRID))
+        d1, d2 = (vn_density_probabilities(alpha, V, edges, m) for m in (32, 64))
+        assert p2[256:].sum() == 0.0 and abs(d2.sum() - 1.0) <= 1e-3
+        bound = 2 * np.abs(p2 - p1).max() + 2 * np.abs(d2 - d1).max() + 1e-6
+        worst = float(np.abs(p2 - d2).max())
+        figures[f"a{alpha}_c{cv}_p{phi:g}"] = f"{worst:.2e}/{bound:.2e}"
+        assert bound <= 0.05 / 256 and worst <= bound, (alpha, cv, phi, worst, bound)
+        turned = vn_grid_probabilities(alpha, V, edges, VN_GRID, axis="reference", clamp=False)
+        psi = df.ggx_visible_normal(alpha, V, np.array([0.5]), np.array([0.5]))[1]
+        assert abs(math.remainder(psi + math.radians(phi + 90.0), 2 * math.pi)) < 1e-6
+        if V[0] == 0.0 and V[1] < 0.0:
+            assert abs(psi) <= 1e-12 and np.abs(turned - p1).max() <= 1e-12
+        else:
+            assert abs(psi) > 0.1 and np.abs(turned - p1).max() > 10 * bound
+    uv = np.random.default_rng(5).random((2, 4096))
+    for alpha, cv, phi in VN_PAIRS:
+        V = vn_view(cv, phi)
+        Hr, psi = df.ggx_visible_normal(alpha, V, uv[0], uv[1], axis="reference", clamp=False)
+        Hh = df.ggx_visible_normal(alpha, V, uv[0], uv[1], axis="heitz", clamp=False)[0]
+        if V[0] == 0.0:
+            assert abs(psi) <= 1e-12 if V[1] < 0 else abs(abs(psi) - np.pi) <= 1e-12
+            assert (np.abs(Hr - Hh).max() <= 1e-12) == (V[1] < 0)
+        else:
+            assert abs(math.sin(psi)) > 0.1 and np.abs(Hr - Hh).max() > 0.01
+        assert (Hh[:, 2] > 0).all()
+        figures[f"horizon_a{alpha}_c{cv}_p{phi:g}"] = float(vn_grid_probabilities(alpha, V, vn_edges(alpha, V), VN_GRID)[256:].sum())
+    report("definitions/visible_normal", **figures)
+
+
+def vn_groups(expected):
+    """Cells that expect fewer than 5 counts are pooled into one; if the pool still expects fewer than 5 it joins the smallest other cell.
+    -> group index per cell, number of groups."""
+    small = expected < 5.0
+    order = np.flatnonzero(~small)
+    group = np.full(len(expected), len(order))
+    group[order] = np.arange(len(order))
+    if not small.any():
+        return group, len(order)
+    if expected[small].sum() < 5.0:
+        group[small] = group[order[np.argmin(expected[order])]]
+        return group, len(order)
+    return group, len(order) + 1
+
+
+def vn_chi2(counts, expected):
+    group, k = vn_groups(expected)
+    o, e = np.bincount(group, weights=counts, minlength=k), np.bincount(group, weights=expected, minlength=k)
+    return float(((o - e) ** 2 / e).sum()), k - 1
+
+
+def check_ggx_sample_distribution(be, mirt):
+    """Closure<GGX>::sample, how the sampled normals are DISTRIBUTED: per pair of VN_PAIRS, 20 000 inputs from the project's own PCG, the half
+    vector rebuilt from (V, direction), counted on 16 rows in H.z (the sixteen-quantiles of the definition's H.z) x 16 sectors of azimuth about
+    the normal, plus 16 cells by azimuth for the clamped mass at H.z = 0.  Expected cell probabilities: definitions.ggx_visible_normal with
+    axis="reference" (D7) on a 1024 x 1024 midpoint grid over (u, v); cells that expect fewer than 5 counts are pooled.  Chi-square against
+    the upper p = 1e-6 quantile (fixed beforehand) for the degrees of freedom left, from scipy.stats.chi2.isf where scipy is installed - it
+    is where these figures were taken - and from Wilson & Hilferty otherwise (0.05 ... 0.16 % higher at these degrees of freedom: definitions.chi2_upper).
+    Measured on the oracle, chi-square / threshold (degrees of freedom), in the order of VN_PAIRS: DESIGN.md section 2."""
+    figures = {}
+    for k, (alpha, cv, phi) in enumerate(VN_PAIRS):
+        V = vn_view(cv, phi)
+        r = pcg(mirt, 7000 + k, 2 * VN_N); u0, u1 = r[0::2].copy(), r[1::2].copy()
+        d, e = be.ggx_sample(np.ones((VN_N, 3), dtype=f32), np.full(VN_N, alpha, dtype=f32), np.tile(V.astype(f32), (VN_N, 1)), u0, u1)
+        H = d.astype(f64) + V
+        H = H / np.linalg.norm(H, axis=1, keepdims=True)
+        edges = vn_edges(alpha, V)
+        counts = np.bincount(vn_bin(H, edges), minlength=273)
+        expected = VN_N * vn_grid_probabilities(alpha, V, edges, VN_GRID)
+        chi2, dof = vn_chi2(counts, expected)
+        limit = df.chi2_upper(dof, VN_P)
+        figures[f"a{alpha}_c{cv}_p{phi:g}"] = f"{chi2:.1f}/{limit:.1f}({dof})"
+        assert dof >= 15 and chi2 < limit, (alpha, cv, phi, chi2, limit, dof)
+        assert counts[272] == 0                                                     # the clamp: no half vector below the surface
+        assert abs(counts[256:272].sum() - expected[256:272].sum()) <= SIGMA * math.sqrt(max(expected[256:272].sum(), 1.0))      # the horizon mass as a whole
+    report(f"{be.name}/ggx_sample_distribution", **figures)
+
+
+def test_ggx_sample_distribution(be, mirt):
+    check_ggx_sample_distribution(be, mirt)
+
+
+def test_ggx_sample_distribution_guards():
+    """What makes the chi-square a test of D7, no backend: were the samples drawn with Heitz's axis (or without the clamp) while the cells
+    expect D7, the statistic's noncentrality n sum (p_alt - p)^2 / p over the pooled cells is at least twice the threshold at every pair with
+    V.x != 0 but the nearly symmetric ones (alpha = 0.05, or alpha = 0.3 at cos V = 0.9) - at least three are required.  At psi = 0 the axis
+    cannot show, and does not.  Without the clamp the clamped mass keeps its azimuth and leaves the horizon cells for the one below the
+    surface, which must stay empty: at every pair whose horizon mass expects 5 counts or more, so does that cell.
+    Measured noncentrality / threshold under Heitz's axis, and the horizon mass, per pair: DESIGN.md section 2."""
+    figures, told = {}, 0
+    for alpha, cv, phi in VN_PAIRS:
+        V = vn_view(cv, phi)
+        edges = vn_edges(alpha, V)
+        p = vn_grid_probabilities(alpha, V, edges, VN_GRID)
+        group, k = vn_groups(VN_N * p)
+        limit = df.chi2_upper(k - 1, VN_P)
+        alt = vn_grid_probabilities(alpha, V, edges, VN_GRID, axis="heitz")
+        e, a = np.bincount(group, weights=p, minlength=k), np.bincount(group, weights=alt, minlength=k)
+        ratio = float(VN_N * ((a - e) ** 2 / e).sum() / limit)
+        horizon = float(p[256:272].sum())
+        figures[f"a{alpha}_c{cv}_p{phi:g}"] = f"{ratio:.1f}/{horizon:.4f}"
+        assert p[272] == 0.0
+        if VN_N * horizon >= 5.0:
+            assert VN_N * vn_grid_probabilities(alpha, V, edges, VN_GRID, clamp=False)[272] >= 5.0
+        if V[0] != 0.0:
+            told += ratio >= 2.0
+        elif V[1] < 0.0:
+            assert ratio < 0.01 and horizon == 0.0
+    report("guards/ggx_sample_distribution", told_apart=told, **figures)
+    assert told >= 3
+
+
 # ---- D. camera, sky, resolve ----------------------------------------------------------------------------------------------------
 def turned_camera_scene(mirt):
     """default9 seen through a camera whose orientation is set as a quaternion outright (a roll as well as a turn)."""
@@ -832,14 +1027,16 @@ def df_blockers(blockers):
     return (np.array([c for c, r in blockers], dtype=f64).reshape(-1, 3), np.array([float(f32(r * r)) for c, r in blockers]))
 
 
-def footprint_points(sub=F_SUB):
-    """First hits of the unit sphere on a sub x sub midpoint grid of every pixel's footprint: x = n, (h * w, sub * sub, 3)."""
+def footprint_points(sub=F_SUB, cam=None):
+    """First hits of the unit sphere on a sub x sub midpoint grid of every pixel's footprint: x = n, (h * w, sub * sub, 3).  `cam` = (eye_z,
+    focal) is another camera on the axis (part G3), under which a footprint may leave the sphere: NaN there."""
     s = (np.arange(sub) + 0.5) / sub
     xs = (np.arange(F_W)[None, :, None, None] + s[None, None, :, None]) + np.zeros((F_H, 1, 1, sub))
     ys = (np.arange(F_H)[:, None, None, None] + s[None, None, None, :]) + np.zeros((1, F_W, sub, 1))
-    t, nrm = df.sphere_depth_normal(xs, ys, F_W / 2.0, F_H / 2.0, df.lens_z(F_H, F_FOCAL), F_EYE)
-    assert np.isfinite(t).all()
-    return nrm.reshape(F_H * F_W, sub * sub, 3)
+    eye, focal = (F_EYE, F_FOCAL) if cam is None else cam
+    t, nrm = df.sphere_depth_normal(xs, ys, F_W / 2.0, F_H / 2.0, df.lens_z(F_H, focal), eye)
+    assert cam is not None or np.isfinite(t).all()
+    return np.where(np.isfinite(t)[..., None], nrm, np.nan).reshape(F_H * F_W, sub * sub, 3)
 
 
 # name -> the scene's pieces, MIS, the cells of the cone quadrature, the accumulations (the smallest multiple of 5, from 100, at which
@@ -924,12 +1121,21 @@ def backend_image(res, n_acc):
     return img
 
 
-def guard_first_hits(be, sc, max_bounces):
-    """No camera ray sees anything but the unit sphere (float64 closest hit on the backend's own camera rays), and Q11 cannot bite."""
+def guard_first_hits(be, sc, max_bounces, kept=None):
+    """No camera ray sees anything but the unit sphere (float64 closest hit on the backend's own camera rays), and Q11 cannot bite.  With
+    `kept` (h, w; part G3) that holds for every ray of a kept pixel - the regions are drawn from those alone - while rays of the other pixels
+    may pass the limb, where they meet the black sky: some must, and none of them may be a kept pixel's."""
     p, d = be.raygen(sc, F_W, F_H, 1, max_bounces=max_bounces)
     geo = sc.geometry
     hit = df.closest_hit(p.T.astype(f64), d.T.astype(f64), geo["position"].astype(f64), geo["radius_sq"].astype(f64))
-    assert (hit["prim"] == int(np.flatnonzero((geo["position"] == 0).all(axis=1))[0])).all()
+    unit = int(np.flatnonzero((geo["position"] == 0).all(axis=1))[0])
+    if kept is None:
+        assert (hit["prim"] == unit).all()
+    else:
+        px, py = df.pixel_of_slot(np.arange(p.shape[1]), F_W)
+        k = kept[py, px]
+        assert (hit["prim"][k] == unit).all() and not hit["unsure"][k].any()
+        assert (hit["prim"][~k] == -1).sum() >= 64
     o = ob.Oracle(sc); prims = o.bvh()[1]; o.close()
     assert prims.tobytes() == np.ascontiguousarray(geo).tobytes()                   # tree order = authoring order
 
@@ -1115,3 +1321,326 @@ def test_several_bounces_guards():
     report("guards/F5", q5_off_apart=far_q5, one_bounce_apart=far_direct, dropped_share=on["dropped"])
     assert on["dropped"] > 0.0 and off["dropped"] == 0.0
     assert far_q5 > 2 * SIGMA and far_direct > 2 * SIGMA
+
+
+# ---- G. the GGX closure inside the path -----------------------------------------------------------------------------------------
+# Part F's frame and lights with brdf = 1: the unit sphere is a GGX cap (F0 grey-ish 0.5 - 0.8, roughness 0.548 so that alpha = 0.30).  A black
+# light still reflects Schlick's (1 - cos)^5 under this closure (F0 = 0, alpha = decay[bounce]), so a path that finds it is not ended there:
+# at max_bounces = 2 the only thing that can happen to it is Q5.
+G_F0, G_ROUGH = (0.8, 0.65, 0.5), 0.548
+G_DIFFUSE_F0, G_DIFFUSE_ROUGH = (0.3, 0.9, 0.6), 0.8                   # G2: DIFFUSE's sphere as a coloured, rougher GGX surface
+G_DECAY = (0.0, 0.15, 0.3, 0.45) + (0.5,) * 12                         # G2: the gloss-decay table, non-zero from bounce 1 on
+G_QUAD, G_GRID = (16, 32), 24                                          # cells of the cone quadrature; (u, v) midpoints a side for the drop probability
+G1_ACC = 100                                                           # smallest multiple of 5 at which test_ggx_path_guards holds (cap 1 500)
+G2_ACC, G2_REF = 190, 760                                                # smallest multiple of 5 (sampler: four times as many) at which the decay guard holds
+_g_cache = {}
+
+
+def ggx_scene(mirt, lights, diffuse=(), cam=None, rough=G_ROUGH):
+    sc = lit_scene(mirt, lights, diffuse=[(c, r, (0, 0, 0)) for c, r, _ in diffuse], rho=(0, 0, 0))
+    if cam is not None:
+        sc.camera = mirt.scene.Camera(eye=(0.0, 0.0, cam[0]), direction=(0.0, 0.0, -1.0), focal_length=cam[1], exposure=1.0)
+    sc.material["F0"][0], sc.material["roughness"][0] = G_F0, rough
+    for k, (_, _, (F0, rough)) in enumerate(diffuse):
+        sc.material["F0"][1 + len(lights) + k], sc.material["roughness"][1 + len(lights) + k] = F0, rough
+    return sc
+
+
+def g_view(nrm, eye=F_EYE):
+    """Unit directions from points of the unit sphere (x = n) back to the eye."""
+    v = np.array([0.0, 0.0, eye]) - nrm
+    return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+def g1_expectation(pixels=None, refine=1, axis="reference", clamp=True, closure_pdf="zero", q5=True, cam=None, rough=G_ROUGH, sub=F_SUB):
+    """G1 by quadrature, per pixel (mean over the sub-pixels, variance of the mixture): one path's contribution at max_bounces = 2 is
+    C S with C the light sample's (Le f cos w / 1 drawn with density p_l, w = p_l / max(1e-6, p_l^2 + p_b^2), p_b = 0) and S = 1 unless Q5
+    drops the path, which it does when the closure sample survives the roulette (probability min(1, max(F G2 / G1))) and meets a sphere.
+    The two draws are independent:  E = E[C] (1 - P_drop),  M2 = E[C^2] (1 - P_drop).  E[C], E[C^2] by the cone quadrature of part F,
+    P_drop and the survival probability by a midpoint grid over the (u, v) square through definitions.ggx_visible_normal.
+    -> dict E, var (k, 3), shadow, survive, drop (k,)."""
+    key = (None if pixels is None else tuple(pixels), refine, axis, clamp, closure_pdf, q5, cam, rough, sub)
+    if key in _g_cache:
+        return _g_cache[key]
+    c, r2, Le = df_lights([HIGH])[0]
+    nrm = footprint_points(sub=sub, cam=cam)
+    nrm = nrm if pixels is None else nrm[pixels]
+    assert np.isfinite(nrm).all()
+    eye = F_EYE if cam is None else cam[0]
+    k, q = nrm.shape[:2]
+    g = G_GRID * refine
+    mid = (np.arange(g) + 0.5) / g
+    uu, vv = (a.reshape(-1) for a in np.meshgrid(mid, mid, indexing="ij"))
+    F0 = np.array(G_F0)
+    alpha = float(f32(rough)) ** 2
+    out = dict(E=np.zeros((k, 3)), var=np.zeros((k, 3)), shadow=np.zeros(k), survive=np.zeros(k), drop=np.zeros(k))
+    for lo in range(0, k, 1024 // (sub * sub)):
+        n = nrm[lo:lo + 1024 // (sub * sub)].reshape(-1, 3)
+        m = len(n)
+        P, R = n * (1.0 + df.OFFSET), df.frame_about(n)
+        Vl = np.einsum("nji,nj->ni", R, g_view(n, eye))
+        kc, kd = ("cone", key[0], refine, cam, rough, sub, closure_pdf, lo), ("drop", key[0], refine, cam, rough, sub, axis, clamp, lo)
+        if kc not in _g_cache:                                                      # the light sample: shared by the what-ifs on the bounce
+            dirs, wq, dist, sin2 = df.cone_quadrature(P, c, r2, G_QUAD[0] * refine, G_QUAD[1] * refine)
+            cells = dirs.shape[1]
+            Ll = np.einsum("nji,ncj->nci", R, dirs).reshape(-1, 3)
+            Vc = np.repeat(Vl, cells, axis=0)
+            f = df.ggx_eval_cos(np.tile(F0, (m * cells, 1)), alpha, Ll, Vc)[0]
+            p_l = np.repeat(df.cone_pdf(sin2)[0], cells)
+            p_b = df.ggx_vndf_pdf_of_direction(alpha, Ll, Vc) if closure_pdf == "vndf" else 0.0
+            C = np.where((Ll[:, 2] >= 0.0)[:, None], Le[None, :] * f * (p_l / np.maximum(1e-6, p_l * p_l + p_b * p_b))[:, None], 0.0)
+            mass = (np.repeat(wq, cells) * p_l)[:, None]
+            _g_cache[kc] = ((C * mass).reshape(m, cells, 3).sum(axis=1), (C * C * mass).reshape(m, cells, 3).sum(axis=1), (C.max(axis=1) > 0.0).reshape(m, cells).mean(axis=1))
+        if kd not in _g_cache:                                                      # the bounce: shared by the what-ifs on the light sample
+            H = df.ggx_visible_normal(alpha, Vl[:, None, :], uu[None, :], vv[None, :], axis=axis, clamp=clamp)[0]
+            Vg = np.broadcast_to(Vl[:, None, :], H.shape)
+            L = 2.0 * (H * Vg).sum(axis=-1, keepdims=True) * H - Vg
+            L = (L / np.linalg.norm(L, axis=-1, keepdims=True)).reshape(-1, 3)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                est = np.where((L[:, 2] > 0.0)[:, None], np.nan_to_num(df.ggx_vndf_weight(np.tile(F0, (len(L), 1)), alpha, L, Vg.reshape(-1, 3))[0]), 0.0)
+            live = np.minimum(1.0, est.max(axis=1))
+            Lw = np.einsum("nij,ngj->ngi", R, L.reshape(m, g * g, 3)).reshape(-1, 3)
+            b, oc2, disc = df.sphere_roots(np.repeat(P, g * g, axis=0), Lw, c[None, :], np.array([r2]))
+            meets = (disc[:, 0] >= 0.0) & (b[:, 0] + np.sqrt(np.maximum(disc[:, 0], 0.0)) >= 0.0)
+            _g_cache[kd] = (live.reshape(m, g * g).mean(axis=1), (live * meets).reshape(m, g * g).mean(axis=1))
+        (EC, M2C, shadow), (survive, drop) = _g_cache[kc], _g_cache[kd]
+        drop = drop if q5 else np.zeros(m)
+        E = (EC * (1.0 - drop)[:, None]).reshape(-1, q, 3).mean(axis=1)
+        sl = slice(lo, lo + 1024 // (sub * sub))
+        out["E"][sl] = E
+        out["var"][sl] = (M2C * (1.0 - drop)[:, None]).reshape(-1, q, 3).mean(axis=1) - E * E
+        out["shadow"][sl], out["survive"][sl], out["drop"][sl] = (a.reshape(-1, q).mean(axis=1) for a in (shadow, survive, drop))
+    _g_cache[key] = out
+    return out
+
+
+def g_sampler(lights, diffuse, max_bounces, per_pixel, seed, decay=(), **kw):
+    """path_sampler with the GGX closure from jittered first hits -> per-pixel mean and sample variance (h * w, 3), dropped share, shadow and
+    ray counts per path; once a process."""
+    key = ("g", repr(lights), repr(diffuse), max_bounces, per_pixel, seed, tuple(decay), tuple(sorted(kw.items())))
+    if key not in _sampler_cache:
+        rng = np.random.default_rng(seed)
+        jit = rng.random((F_H, F_W, per_pixel, 2))
+        xs, ys = np.arange(F_W)[None, :, None] + jit[..., 0], np.arange(F_H)[:, None, None] + jit[..., 1]
+        pts = df.sphere_depth_normal(xs, ys, F_W / 2.0, F_H / 2.0, df.lens_z(F_H, F_FOCAL), F_EYE)[1].reshape(-1, 3)
+        scene = sampler_scene(lights, [(c, r, (0, 0, 0)) for c, r, _ in diffuse])
+        scene["F0"] = np.array([G_F0] + [(0, 0, 0)] * len(lights) + [d[2][0] for d in diffuse], dtype=f64)
+        scene["roughness"] = np.array([float(f32(G_ROUGH))] + [0.0] * len(lights) + [float(f32(d[2][1])) for d in diffuse])
+        out = df.path_sampler(scene, pts, pts, 1, max_bounces, rng, brdf=1, view=g_view(pts), decay=decay, **kw)
+        x = out["sum"].reshape(F_H * F_W, per_pixel, 3)
+        mean = x.mean(axis=1)
+        _sampler_cache[key] = dict(E=mean, var=(x * x).mean(axis=1) - mean * mean, dropped=float(out["dropped"].mean()), shadow=float(out["shadow"].mean()),
+                                   rays=float(out["rays"].mean()))
+    return _sampler_cache[key]
+
+
+def test_ggx_sampler_meets_the_quadrature():
+    """G1 stated twice from the float64 map alone: path_sampler's GGX closure (40 paths a pixel, max_bounces = 2) against g1_expectation,
+    regional means within SIGMA of the sampler's own standard error, its dropped share within SIGMA binomial sigma of the quadrature's."""
+    ref, exp = g_sampler([HIGH], (), 2, 40, 2031), g1_expectation()
+    for label, mask in f_regions("F1_high").items():
+        k = mask.reshape(-1)
+        z = (ref["E"][k].mean(axis=0) - exp["E"][k].mean(axis=0)) / (np.sqrt(ref["var"][k].sum(axis=0) / 40) / k.sum())
+        report(f"sampler/G1/{label}", z="/".join(f"{v:+.2f}" for v in z))
+        assert np.abs(z).max() <= SIGMA, (label, z)
+    n = F_W * F_H * 40
+    z_drop = (ref["dropped"] - exp["drop"].mean()) * n / math.sqrt(n * exp["drop"].mean() * (1 - exp["drop"].mean()))
+    report("sampler/G1", dropped=ref["dropped"], expected=float(exp["drop"].mean()), z_drop=float(z_drop))
+    assert abs(z_drop) <= SIGMA and ref["shadow"] == 1.0
+
+
+def check_ggx_direct(be, mirt, variant=0, **render_kw):
+    """G1: the GGX cap under HIGH, max_bounces = 2, brdf = 1, against g1_expectation: regional means within SIGMA standard errors (the
+    definition's variance); `shadow_rays` = n exactly (HIGH is wholly above the horizon and f > 0 there); `rays` = n (1 + P_survive) and
+    `terminated` = n (1 - P_drop) (a dropped path is not counted as terminated) within SIGMA of their Bernoulli sums.
+    Measured on the oracle: DESIGN.md section 2, row G1."""
+    exp, regions = g1_expectation(), f_regions("F1_high")
+    sc = ggx_scene(mirt, [HIGH])
+    guard_first_hits(be, sc, 2)
+    res = be.render(sc, F_W, F_H, G1_ACC, max_bounces=2, variant=variant, brdf=1, **render_kw)
+    img = backend_image(res, G1_ACC)
+    n, zs = F_W * F_H * G1_ACC, {}
+    for label, mask in regions.items():
+        want, se = region_stats(exp, mask, G1_ACC)
+        assert (want > 0).all() and (se / want < 0.01).all(), (label, se / want)
+        zs[label] = [float(v) for v in (img[mask].mean(axis=0) - want) / se]
+    c = res["counters"]
+    z_rays = (c["rays"] - n - G1_ACC * exp["survive"].sum()) / math.sqrt(G1_ACC * (exp["survive"] * (1 - exp["survive"])).sum())
+    z_term = (c["terminated"] - n + G1_ACC * exp["drop"].sum()) / math.sqrt(G1_ACC * (exp["drop"] * (1 - exp["drop"])).sum())
+    report(f"{be.name}/G1/variant{variant}" + "".join(f"/{k}" for k in render_kw), **{f"z_{k}": "/".join(f"{v:+.2f}" for v in z) for k, z in zs.items()},
+           z_rays=float(z_rays), z_terminated=float(z_term), shadow_rays=c["shadow_rays"])
+    for label, z in zs.items():
+        assert max(abs(v) for v in z) <= SIGMA, f"G1/{label}: {z} sigma from the expectation"
+    assert c["shadow_rays"] == n and (exp["shadow"] == 1.0).all()
+    assert abs(z_rays) <= SIGMA and abs(z_term) <= SIGMA, (z_rays, z_term)
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+def test_ggx_direct(be, mirt, variant):
+    check_ggx_direct(be, mirt, variant=variant)
+
+
+def check_ggx_bounces(be, mirt, max_bounces, variant=0):
+    """G2: HIGH plus DIFFUSE's sphere as a coloured GGX surface of another roughness, the gloss-decay table G_DECAY, against path_sampler's GGX
+    closure with the sampler's own variance (as F5): alpha = a^2 + (1 - a^2) decay[bounce], the roulette on coloured throughput, Q5 under GGX
+    (`terminated` against the sampler's dropped share).  Measured on the oracle: DESIGN.md section 2, row G2."""
+    diffuse = [(DIFFUSE[0], DIFFUSE[1], (G_DIFFUSE_F0, G_DIFFUSE_ROUGH))]
+    sc = ggx_scene(mirt, [HIGH], diffuse)
+    guard_first_hits(be, sc, max_bounces)
+    ref = g_sampler([HIGH], diffuse, max_bounces, G2_REF, 4343, decay=G_DECAY)
+    res = be.render(sc, F_W, F_H, G2_ACC, max_bounces=max_bounces, variant=variant, brdf=1, gloss_decay=G_DECAY)
+    img = backend_image(res, G2_ACC)
+    zs = {}
+    for label, mask in f_regions("F1_high").items():
+        k = mask.reshape(-1)
+        se = np.sqrt(ref["var"][k].sum(axis=0) * (1.0 / G2_ACC + 1.0 / G2_REF)) / k.sum()
+        zs[label] = [float(v) for v in (img[mask].mean(axis=0) - ref["E"][k].mean(axis=0)) / se]
+    n, q = F_W * F_H * G2_ACC, ref["dropped"]
+    sigma_term = math.sqrt(n * q * (1 - q) * (1.0 + G2_ACC / G2_REF))
+    z_term = (res["counters"]["terminated"] - n * (1 - q)) / sigma_term if sigma_term > 0 else float(res["counters"]["terminated"] - n)
+    report(f"{be.name}/G2/bounces{max_bounces}/variant{variant}", **{f"z_{k}": "/".join(f"{v:+.2f}" for v in z) for k, z in zs.items()}, dropped_share=q, z_terminated=float(z_term))
+    for label, z in zs.items():
+        assert max(abs(v) for v in z) <= SIGMA, f"G2/{label}: {z} sigma from the sampler"
+    assert abs(z_term) <= SIGMA, z_term
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+@pytest.mark.parametrize("max_bounces", [4, 16])
+def test_ggx_bounces(be, mirt, max_bounces, variant):
+    check_ggx_bounces(be, mirt, max_bounces, variant=variant)
+
+
+def test_ggx_path_guards():
+    """What makes part G a test, from the definitions alone (no backend).  At the chosen counts each alternative lies at least 2 SIGMA from the
+    D7 expectation in some region - or is stated here as one these scenes cannot tell apart under the cap of 1 500 accumulations:
+      G1 (100 accumulations)  the true visible-normal pdf in the MIS weights; no Q5;
+      G2 at 4 bounces (190 against 760 sampler paths; 175 / 700 gave 9.8)  no gloss-decay table;
+      NOT told apart: Heitz's axis (under 0.01 SIGMA-units a root-accumulation in G1: 0.3 sigma at 1 500) and the dropped clamp (exactly 0:
+      no normal is clamped at alpha = 0.30 within 7 degrees of the normal).  The frame shows only near-normal views; the axis and the clamp
+      are held at function level by check_ggx_sample_distribution; G3 (test_ggx_grazing_guards) asks again from a grazing camera.
+    Doubling both quadratures moves no pixel by more than 0.1 of its standard error, nor the subsample's mean by 0.1 of the mean's.
+    Measured: DESIGN.md section 2, rows G."""
+    figures, regs = {}, f_regions("F1_high")
+    base = g1_expectation()
+
+    def g1_apart(n_acc, **alt):
+        other = g1_expectation(**alt)
+        return max(float((np.abs(region_stats(other, m, n_acc)[0] - region_stats(base, m, n_acc)[0]) / region_stats(base, m, n_acc)[1]).max()) for m in regs.values())
+
+    for label, alt in (("true_pdf", dict(closure_pdf="vndf")), ("no_q5", dict(q5=False))):
+        figures[f"G1_{label}"] = g1_apart(G1_ACC, **alt)
+        assert figures[f"G1_{label}"] >= 2 * SIGMA
+    figures["G1_heitz_at_cap"] = g1_apart(1500, axis="heitz")
+    figures["G1_no_clamp_at_cap"] = g1_apart(1500, clamp=False)
+    assert figures["G1_heitz_at_cap"] < 0.5 and figures["G1_no_clamp_at_cap"] == 0.0          # stated, not hidden: these need a wider view
+    some = np.arange(0, F_W * F_H, 61)
+    a, b = g1_expectation(pixels=some), g1_expectation(pixels=some, refine=2)
+    se = np.sqrt(a["var"] / G1_ACC)
+    se_mean = np.sqrt(a["var"].sum(axis=0) / G1_ACC) / len(some)
+    figures["G1_refine"] = float((np.abs(b["E"] - a["E"]) / se).max())
+    figures["G1_refine_mean"] = float((np.abs(b["E"].mean(axis=0) - a["E"].mean(axis=0)) / se_mean).max())
+    assert figures["G1_refine"] <= 0.1 and figures["G1_refine_mean"] <= 0.1
+    assert (base["shadow"] == 1.0).all() and 0.01 < base["drop"].min() and base["drop"].max() - base["drop"].min() > 0.1 and base["survive"].max() < 0.9
+    diffuse = [(DIFFUSE[0], DIFFUSE[1], (G_DIFFUSE_F0, G_DIFFUSE_ROUGH))]
+    on = g_sampler([HIGH], diffuse, 4, G2_REF, 4343, decay=G_DECAY)
+    for label, decay, kw in (("no_decay", (), {}), ("no_q5", G_DECAY, dict(q5=False))):
+        off = g_sampler([HIGH], diffuse, 4, G2_REF, 4343, decay=decay, **kw)
+        far = 0.0
+        for mask in regs.values():
+            k = mask.reshape(-1)
+            se = np.sqrt(on["var"][k].sum(axis=0) * (1.0 / G2_ACC + 1.0 / G2_REF)) / k.sum()
+            far = max(far, float((np.abs(off["E"][k].mean(axis=0) - on["E"][k].mean(axis=0)) / se).max()))
+        figures[f"G2_{label}"] = far
+    figures["G1_drop_share"] = f"{base['drop'].min():.3f}..{base['drop'].max():.3f}"
+    report("guards/G", dropped_share_G2=on["dropped"], **figures)
+    assert figures["G2_no_decay"] >= 2 * SIGMA and on["dropped"] > 0.0
+
+
+# ---- G3. the grazing camera -------------------------------------------------------------------------------------------------------
+# The eye at (0, 0, 3) with the same lens: the limb lies 19.5 degrees off the axis, inside the frame's corners (25.8), and the image shows
+# normals out to the limb's 70.5 degrees.  Kept pixels are those whose whole footprint has normals within 60 degrees of +z; the others -
+# the limb, and the black sky past it - are masked out of the regions by guard_first_hits.  V leaves the normal by up to 79 degrees there,
+# at every azimuth of the local frame.
+G3_CAM = (3.0, 35.0)
+G3_SUB = F_SUB                                                         # sub-pixel grid of the footprint (4 x 4 moves no region's z by more than 0.03)
+G3_ACC = 100                                                           # smallest multiple of 5, from 100, at which the guards that can hold do
+
+
+def g3_kept():
+    """-> kept (h, w) bool, the flat indices of the kept pixels, and per kept pixel the angle of its mean normal to +z and its azimuth (degrees)."""
+    nrm = footprint_points(cam=G3_CAM)
+    s = np.array([0.0, 1.0])
+    xs, ys = np.arange(F_W)[None, :, None, None] + s[None, None, :, None], np.arange(F_H)[:, None, None, None] + s[None, None, None, :]
+    t, corner = df.sphere_depth_normal(xs + np.zeros_like(ys), ys + np.zeros_like(xs), F_W / 2.0, F_H / 2.0, df.lens_z(F_H, G3_CAM[1]), G3_CAM[0])
+    kept = (np.isfinite(t) & (corner[..., 2] >= 0.5)).all(axis=(2, 3))
+    idx = np.flatnonzero(kept.reshape(-1))
+    mean = nrm[idx].mean(axis=1)
+    mean = mean / np.linalg.norm(mean, axis=1, keepdims=True)
+    return kept, idx, np.degrees(np.arccos(mean[:, 2])), np.degrees(np.arctan2(mean[:, 1], mean[:, 0])) % 360.0
+
+
+def g3_regions():
+    """Seventeen named regions over the kept pixels: the cap within 15 degrees of the axis, and eight sectors of azimuth each of the rings of
+    normals 15 - 30 and 30 - 60 degrees off it (a turned axis shows with a sign that changes round the ring, so a whole ring would cancel it)."""
+    _, _, ang, az = g3_kept()
+    regs = {"inner": ang < 15.0}
+    for name, lo, hi in (("mid", 15.0, 30.0), ("outer", 30.0, 61.0)):
+        for k in range(8):
+            regs[f"{name}{k}"] = (ang >= lo) & (ang < hi) & (az >= 45.0 * k) & (az < 45.0 * k + 45.0)
+    return regs
+
+
+def check_ggx_grazing(be, mirt, variant=0):
+    """G3: G1's scene and expectation from the farther eye - normals out to 60 degrees, V tens of degrees off the normal at every azimuth of
+    the local frame, HIGH partly or wholly below the horizon of many pixels - over the kept pixels only; each of the seventeen regions within
+    SIGMA standard errors.  The counters cover the masked pixels too and are not compared.  Measured on the oracle: DESIGN.md, row G3."""
+    kept, idx, ang, _ = g3_kept()
+    exp = g1_expectation(pixels=idx, cam=G3_CAM, sub=G3_SUB)
+    sc = ggx_scene(mirt, [HIGH], cam=G3_CAM)
+    guard_first_hits(be, sc, 2, kept=kept)
+    res = be.render(sc, F_W, F_H, G3_ACC, max_bounces=2, variant=variant, brdf=1)
+    img = backend_image(res, G3_ACC).reshape(-1, 3)[idx]
+    assert ang.max() >= 30.0 and (ang >= 30.0).sum() >= 1024
+    zs = {}
+    for label, mask in g3_regions().items():
+        want, se = region_stats(exp, mask, G3_ACC)
+        assert mask.sum() >= 64 and (want > 0).all()
+        zs[label] = float(((img[mask].mean(axis=0) - want) / se)[np.argmax(np.abs((img[mask].mean(axis=0) - want) / se))])
+    report(f"{be.name}/G3/variant{variant}", **zs)
+    assert max(abs(v) for v in zs.values()) <= SIGMA, zs
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+def test_ggx_grazing(be, mirt, variant):
+    check_ggx_grazing(be, mirt, variant=variant)
+
+
+def test_ggx_grazing_guards():
+    """G3 from the definitions alone.  At 100 accumulations the true visible-normal pdf in the MIS weights and the missing Q5 lie beyond 2 SIGMA
+    in some region.  Heitz's axis and the dropped clamp do NOT, and not at the cap of 1 500 either - stated, with their figures, not raised:
+    at max_bounces = 2 the axis reaches the image only through the probability that Q5 drops the path, which the wide light integrates over
+    (largest region: the figure below, at the cap), and a normal below the surface reflects V below the surface with or without the clamp
+    (weight 0 either way; the difference is exactly 0).  Inside the path these two rest on check_ggx_sample_distribution.
+    Doubling both quadratures moves no kept pixel of a subsample by more than 0.1 of its standard error, nor the subsample's mean."""
+    kept, idx, ang, _ = g3_kept()
+    regs, base, figures = g3_regions(), g1_expectation(pixels=idx, cam=G3_CAM, sub=G3_SUB), {}
+
+    def apart_at(n_acc, **alt):
+        other = g1_expectation(pixels=idx, cam=G3_CAM, sub=G3_SUB, **alt)
+        return max(float((np.abs(region_stats(other, m, n_acc)[0] - region_stats(base, m, n_acc)[0]) / region_stats(base, m, n_acc)[1]).max()) for m in regs.values())
+
+    for label, alt in (("true_pdf", dict(closure_pdf="vndf")), ("no_q5", dict(q5=False))):
+        figures[label] = apart_at(G3_ACC, **alt)
+        assert figures[label] >= 2 * SIGMA
+    figures["heitz_at_cap"], figures["no_clamp_at_cap"] = apart_at(1500, axis="heitz"), apart_at(1500, clamp=False)
+    assert figures["heitz_at_cap"] < 2 * SIGMA and figures["no_clamp_at_cap"] == 0.0
+    some = idx[::37]
+    a, b = g1_expectation(pixels=some, cam=G3_CAM, sub=G3_SUB), g1_expectation(pixels=some, cam=G3_CAM, sub=G3_SUB, refine=2)
+    se = np.sqrt(a["var"] / G3_ACC)
+    figures["refine"] = float((np.abs(b["E"] - a["E"]) / se).max())
+    figures["refine_mean"] = float((np.abs(b["E"].mean(axis=0) - a["E"].mean(axis=0)) / (np.sqrt(a["var"].sum(axis=0) / G3_ACC) / len(some))).max())
+    assert figures["refine"] <= 0.1 and figures["refine_mean"] <= 0.1
+    shares = base["shadow"]
+    figures["shadow_share"] = f"{shares.min():.3f}..{shares.max():.3f}"
+    assert shares.min() < 0.5 and shares.max() == 1.0 and ang.max() >= 55.0
+    report("guards/G3", kept=len(idx), **figures)

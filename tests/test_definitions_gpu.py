@@ -113,6 +113,11 @@ def test_ggx_energy(be, mirt):
     cpu.check_ggx_energy(be, mirt)
 
 
+def test_ggx_sample_distribution(be, mirt):
+    """D7 on the device: debug_math fn 9, nine (alpha, V) pairs of 20 000 samples each against the definition's cell probabilities."""
+    cpu.check_ggx_sample_distribution(be, mirt)
+
+
 # ---- D ----
 def test_raygen(be, mirt):
     cpu.check_raygen(be, mirt)
@@ -206,3 +211,25 @@ def test_direct_lighting_traced_primary_rays(be, mirt, name):
 @pytest.mark.parametrize("max_bounces", [4, 16])
 def test_several_bounces(be, mirt, max_bounces, variant):
     cpu.check_several_bounces(be, mirt, max_bounces, variant=variant)
+
+
+# ---- G ----
+@pytest.mark.parametrize("variant", [0, 1])
+def test_ggx_direct(be, mirt, variant):
+    cpu.check_ggx_direct(be, mirt, variant=variant)
+
+
+def test_ggx_direct_exact_stream_order(be, mirt):
+    """The second user of the per-hit shading text under GGX: k_tile_stream."""
+    cpu.check_ggx_direct(be, mirt, variant=0, exact_stream_order=True)
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+@pytest.mark.parametrize("max_bounces", [4, 16])
+def test_ggx_bounces(be, mirt, max_bounces, variant):
+    cpu.check_ggx_bounces(be, mirt, max_bounces, variant=variant)
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+def test_ggx_grazing(be, mirt, variant):
+    cpu.check_ggx_grazing(be, mirt, variant=variant)
