@@ -907,7 +907,13 @@ MIRT_DI void shadow_finish(const ShadowBuf& sh, const ShadowSink& sink, uint32_t
 // PRIMARY != 0 = bounce 0: the rays are generated from their index (primary_ray), nothing is read; no shadow rays are pending.
 //   kPrimaryAll: every ray i of the batch, numbered 0 .. n_pix * batch_n - 1;  kPrimaryList: every sample of the pixels k_primary_cand
 //   listed at in.a (stream_pixel_list: pixels without a candidate list; closest_queue.n[0] = how many); results are stored under the ray's index.
-constexpr int kPrimaryNone = 0, kPrimaryAll = 1, kPrimaryList = 2;
+//   kPrimaryActive: the camera rays that walk the tree (policy.trace_primary_rays, a lens, a batch below 3, no tree at all) once a tile is frozen
+//   (mirt_freeze_tiles): every sample of the local pixels of the tiles still active, which the host lists when the mask changes and hands over
+//   as kPrimaryList's are (in.a, closest_queue.n[0]), in kPrimaryList's numbering.  It has what kPrimaryList leaves out: the brute-force loop of
+//   a context without a tree, the thin-lens ray, and ctr->rays (n_active x batch_n; no k_primary_hits runs beside it).  Hit records go to
+//   slot * n_pix + pixel as ever; those of frozen pixels are neither written nor read.  Its fat rays are k_trace_fat<., kPrimaryList, LENS>'s.
+constexpr int kPrimaryNone = 0, kPrimaryAll = 1, kPrimaryList = 2, kPrimaryActive = 3;
+constexpr bool primary_listed(int primary) { return primary == kPrimaryList || primary == kPrimaryActive; }
 // kPrimaryList numbering: ray j of n_ov * batch_n is sample slot j / n_ov of the j % n_ov-th listed pixel (slot-major: the lanes of a wave
 // take neighbouring pixels of one accumulation, like everywhere else); returns its index in the batch, slot * n_pix + pixel.
 MIRT_DI uint32_t primary_list_ray(const FrameParams& fp, const uint32_t* __restrict__ ov_pix, uint32_t n_ov, float inv_n_ov, uint32_t j) {
@@ -915,7 +921,15 @@ MIRT_DI uint32_t primary_list_ray(const FrameParams& fp, const uint32_t* __restr
 	const uint32_t slot = udiv_f(j, n_ov, inv_n_ov, k);
 	return slot * fp.n_pix + ov_pix[k];
 }
-// LENS (with kPrimaryAll only): the camera rays are thin-lens rays (lens_camera_ray); candidate lists are neither built nor read under a lens.
+// Ray i of a trace launch, origin and direction: at bounce 0 the camera ray of index i in the batch (slot * n_pix + pixel; a listed launch maps
+// its ray number through primary_list_ray first) — the thin-lens ray or the pinhole ray from cam.pos —, later the two 16-byte loads of stream slot i.
+template <int PRIMARY, bool LENS>
+MIRT_DI void trace_ray(const FrameParams& fp, const LensParams& lens, const StreamBuf& in, uint32_t i, float& px, float& py, float& pz, float& dx, float& dy, float& dz) {
+	if (PRIMARY && LENS) { uint32_t path; lens_camera_ray(fp, lens, i, path, px, py, pz, dx, dy, dz); }
+	else if (PRIMARY) { uint32_t path; primary_ray(fp, i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
+	else { const float4 a = in.a[i], b = in.b[i]; px = a.x; py = a.y; pz = a.z; dx = b.x; dy = b.y; dz = b.z; }
+}
+// LENS (k_trace: with kPrimaryAll and kPrimaryActive): the camera rays are thin-lens rays (lens_camera_ray); candidate lists are neither built nor read under a lens.
 template <bool COUNT, int PRIMARY, bool LENS = false>
 __global__ __launch_bounds__(kTraceBlock, 8) void k_trace(SceneDev sc, FrameParams fp,
                                                        StreamBuf in, HitRec* __restrict__ hit_out,
@@ -923,11 +937,12 @@ __global__ __launch_bounds__(kTraceBlock, 8) void k_trace(SceneDev sc, FramePara
                                                        ShadowBuf sh, ShadowSink sink,
                                                        Queue shadow_queue, uint32_t* shadow_work, FatList fat_closest, FatList fat_shadow,
                                                        DevCounters* ctr, LensParams lens) {
+	static_assert(!LENS || PRIMARY == kPrimaryAll || PRIMARY == kPrimaryActive, "the lens concerns bounce 0 only, and candidate lists are not read under it");
 	extern __shared__ float4 lds[];
-	const uint32_t n_ov = PRIMARY == kPrimaryList ? closest_queue.n[0] : 0u;     // listed pixels (k_primary_cand)
+	const uint32_t n_ov = primary_listed(PRIMARY) ? closest_queue.n[0] : 0u;     // listed pixels (k_primary_cand; the active tiles')
 	const float inv_n_ov = 1.0f / static_cast<float>(n_ov ? n_ov : 1u);
 	if (PRIMARY) closest_queue.n = nullptr;                                    // identity numbering: ray j is slot j
-	const uint32_t nc = PRIMARY == kPrimaryAll ? fp.n_pix * fp.batch_n : PRIMARY == kPrimaryList ? n_ov * fp.batch_n : queue_total(closest_queue), ns = PRIMARY ? 0u : queue_total(shadow_queue);
+	const uint32_t nc = PRIMARY == kPrimaryAll ? fp.n_pix * fp.batch_n : primary_listed(PRIMARY) ? n_ov * fp.batch_n : queue_total(closest_queue), ns = PRIMARY ? 0u : queue_total(shadow_queue);
 	if (nc + ns == 0) return;
 	if (blockIdx.x == 0 && threadIdx.x == 0) {
 		if (nc && PRIMARY != kPrimaryList) atomicAdd(&ctr->rays, static_cast<unsigned long long>(nc));     // (k_primary_hits has counted the whole batch)
@@ -939,12 +954,10 @@ __global__ __launch_bounds__(kTraceBlock, 8) void k_trace(SceneDev sc, FramePara
 		const TraceLds tl = stage_bvh(sc, lds);
 		{
 			auto load_ray = [&](uint32_t i, float& px, float& py, float& pz, float& dx, float& dy, float& dz, float& tf) {
-				if (PRIMARY && LENS) { uint32_t path; lens_camera_ray(fp, lens, i, path, px, py, pz, dx, dy, dz); }
-				else if (PRIMARY) { uint32_t path; primary_ray(fp, PRIMARY == kPrimaryList ? primary_list_ray(fp, stream_pixel_list(in), n_ov, inv_n_ov, i) : i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
-				else { const float4 a = in.a[i], b = in.b[i]; px = a.x; py = a.y; pz = a.z; dx = b.x; dy = b.y; dz = b.z; }
-				tf = MIRT_FLT_MAX;                                                 // hit reset, Renderer.hpp:150-158
+				trace_ray<PRIMARY, LENS>(fp, lens, in, primary_listed(PRIMARY) ? primary_list_ray(fp, stream_pixel_list(in), n_ov, inv_n_ov, i) : i, px, py, pz, dx, dy, dz);
+				tf = MIRT_FLT_MAX;                                                // hit reset, Renderer.hpp:150-158
 			};
-			auto store_result = [&](uint32_t i, const Trav& t, bool) { const uint32_t o = PRIMARY == kPrimaryList ? primary_list_ray(fp, stream_pixel_list(in), n_ov, inv_n_ov, i) : i; hit_out[o] = HitRec{ t.tfar, t.prim }; };
+			auto store_result = [&](uint32_t i, const Trav& t, bool) { const uint32_t o = primary_listed(PRIMARY) ? primary_list_ray(fp, stream_pixel_list(in), n_ov, inv_n_ov, i) : i; hit_out[o] = HitRec{ t.tfar, t.prim }; };
 			trace_queue<kClosest, COUNT>(sc, tl, closest_queue, nc, closest_work, fat_closest, c_nodes, c_spheres, load_ray, store_result);
 		}
 		if (!PRIMARY) {
@@ -960,9 +973,9 @@ __global__ __launch_bounds__(kTraceBlock, 8) void k_trace(SceneDev sc, FramePara
 		const QueueView qs = PRIMARY ? queue_identity(0u) : queue_view(shadow_queue);
 		for (uint32_t base = blockIdx.x * kTraceBlock; base < nc; base += gridDim.x * kTraceBlock) {
 			const bool active = base + threadIdx.x < nc;
-			const uint32_t i = active ? queue_slot(qc, base, base + threadIdx.x) : 0u;
+			const uint32_t i = !active ? 0u : PRIMARY == kPrimaryActive ? primary_list_ray(fp, stream_pixel_list(in), n_ov, inv_n_ov, base + threadIdx.x) : queue_slot(qc, base, base + threadIdx.x);
 			float px = 0, py = 0, pz = 0, dx = 1, dy = 1, dz = 1;
-			if (active) {
+			if (active) {                          // mirrors trace_ray<PRIMARY, LENS> (spelled out: through the call hipcc assigns other registers here)
 				if (PRIMARY && LENS) { uint32_t path; lens_camera_ray(fp, lens, i, path, px, py, pz, dx, dy, dz); }
 				else if (PRIMARY) { uint32_t path; primary_ray(fp, i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
 				else { const float4 a = in.a[i], b = in.b[i]; px = a.x; py = a.y; pz = a.z; dx = b.x; dy = b.y; dz = b.z; }
@@ -1002,9 +1015,7 @@ __global__ __launch_bounds__(1024) void k_trace_fat(SceneDev sc, FrameParams fp,
 	for (uint32_t k = blockIdx.x; k < nc; k += gridDim.x) {
 		const uint32_t i = PRIMARY == kPrimaryList ? primary_list_ray(fp, stream_pixel_list(in), n_ov, inv_n_ov, fat_closest.rays[k]) : fat_closest.rays[k];
 		float px, py, pz, dx, dy, dz;
-		if (PRIMARY && LENS) { uint32_t path; lens_camera_ray(fp, lens, i, path, px, py, pz, dx, dy, dz); }
-		else if (PRIMARY) { uint32_t path; primary_ray(fp, i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
-		else { const float4 a = in.a[i], b = in.b[i]; px = a.x; py = a.y; pz = a.z; dx = b.x; dy = b.y; dz = b.z; }
+		trace_ray<PRIMARY, LENS>(fp, lens, in, i, px, py, pz, dx, dy, dz);
 		float tfar = MIRT_FLT_MAX; int32_t prim = -1;
 		for (uint32_t p = threadIdx.x; p < sc.n_spheres; p += blockDim.x) sphere_closest(sc.spheres[p], static_cast<int32_t>(p), px, py, pz, dx, dy, dz, tfar, prim);
 		// lexicographic (dist, prim) minimum across the workgroup; prim -1 = no hit, always loses (its tfar is FLT_MAX and every hit is < FLT_MAX)
@@ -1040,50 +1051,6 @@ __global__ __launch_bounds__(1024) void k_trace_fat(SceneDev sc, FrameParams fp,
 			if (COUNT) atomicAdd(&ctr->shadow_spheres, static_cast<unsigned long long>(sc.n_spheres));
 		}
 	}
-}
-
-// The camera rays that walk the tree (policy.trace_primary_rays, a lens, a batch below 3, no tree at all) once a tile is frozen
-// (mirt_freeze_tiles): every sample of the pixels listed in active_pix[0 .. n_active) — the local pixels of the tiles still active, listed by
-// the host when the mask changes — in kPrimaryList's numbering (primary_list_ray), with what k_trace<., kPrimaryList> leaves out: the
-// brute-force loop of a context without a tree, the thin-lens ray, and ctr->rays (here n_active x batch_n; no k_primary_hits runs beside it).
-// Hit records go to slot * n_pix + pixel as ever; those of frozen pixels are neither written nor read.  Its fat rays (numbers in this
-// numbering) are k_trace_fat<., kPrimaryList, LENS>'s, with in.a = active_pix.  No shadow rays are pending at bounce 0.
-template <bool COUNT, bool LENS>
-__global__ __launch_bounds__(kTraceBlock, 8) void k_trace_sparse(SceneDev sc, FrameParams fp, const uint32_t* __restrict__ active_pix, uint32_t n_active, HitRec* __restrict__ hit_out,
-                                                              uint32_t* work, FatList fat, DevCounters* ctr, LensParams lens) {
-	extern __shared__ float4 lds[];
-	const uint32_t nc = n_active * fp.batch_n;
-	if (nc == 0) return;
-	const float inv_n_active = 1.0f / static_cast<float>(n_active);
-	if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&ctr->rays, static_cast<unsigned long long>(nc));
-	auto camera = [&](uint32_t i, float& px, float& py, float& pz, float& dx, float& dy, float& dz) {
-		uint32_t path;
-		if (LENS) lens_camera_ray(fp, lens, i, path, px, py, pz, dx, dy, dz);
-		else { primary_ray(fp, i, path, dx, dy, dz); px = fp.cam.pos[0]; py = fp.cam.pos[1]; pz = fp.cam.pos[2]; }
-	};
-	uint32_t c_nodes = 0, c_spheres = 0;
-	if (sc.use_bvh && sc.n_recs != 0) {
-		if (static_cast<uint64_t>(blockIdx.x) * 64u >= nc) return;
-		const TraceLds tl = stage_bvh(sc, lds);
-		auto load_ray = [&](uint32_t j, float& px, float& py, float& pz, float& dx, float& dy, float& dz, float& tf) {
-			camera(primary_list_ray(fp, active_pix, n_active, inv_n_active, j), px, py, pz, dx, dy, dz);
-			tf = MIRT_FLT_MAX;
-		};
-		auto store_result = [&](uint32_t j, const Trav& t, bool) { hit_out[primary_list_ray(fp, active_pix, n_active, inv_n_active, j)] = HitRec{ t.tfar, t.prim }; };
-		trace_queue<kClosest, COUNT>(sc, tl, Queue{ nullptr, 0u }, nc, work, fat, c_nodes, c_spheres, load_ray, store_result);
-	} else {
-		for (uint32_t base = blockIdx.x * kTraceBlock; base < nc; base += gridDim.x * kTraceBlock) {
-			const bool active = base + threadIdx.x < nc;
-			const uint32_t i = active ? primary_list_ray(fp, active_pix, n_active, inv_n_active, base + threadIdx.x) : 0u;
-			float px = 0, py = 0, pz = 0, dx = 1, dy = 1, dz = 1;
-			if (active) camera(i, px, py, pz, dx, dy, dz);
-			float tfar = MIRT_FLT_MAX;
-			int32_t prim = -1;
-			if (sc.use_bvh == 0) traverse_brute<false, COUNT>(sc, lds, active, px, py, pz, dx, dy, dz, tfar, prim, c_spheres);
-			if (active) hit_out[i] = HitRec{ tfar, prim };
-		}
-	}
-	if (COUNT) { wave_sum(c_nodes, &ctr->nodes); wave_sum(c_spheres, &ctr->spheres); }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -142,7 +142,7 @@ struct mirt_ctx {
 	std::vector<uint32_t> frozen_at; // count of a frozen tile
 	uint32_t n_frozen = 0;           // 0: every launch is the one of a context without the feature
 	DeviceBuffer tile_frozen;        // the mask as the sparse kernels read it, one word per local tile
-	DeviceBuffer active_list;        // word 0: local pixels of the active tiles, words 1..: those pixels (k_trace_sparse; k_trace_fat's `listed` count)
+	DeviceBuffer active_list;        // word 0: local pixels of the active tiles, words 1..: those pixels (mirt_freeze_tiles; what k_trace<., kPrimaryActive> traces, list and count as kPrimaryList's)
 	DeviceBuffer tile_counts;        // per-tile counts for the resolves (uploaded by the call that resolves)
 	DeviceBuffer listed_active;      // word 0: count, words 1..: cand_listed ∩ active tiles (k_listed_active), what k_trace<., kPrimaryList> traces once a tile is frozen
 	hipEvent_t listed_built = nullptr; // recorded on the main stream after the latest k_listed_active; batches on other streams wait for it
@@ -501,26 +501,34 @@ SceneDev trace_scene(const mirt_ctx* c) {
 	return sc;
 }
 
-// Every instantiation a launch may pick, by template argument.  kTrace and kPrimaryCand use dynamic LDS: mirt_set_scene raises
-// their limit by walking these tables, so a kernel that can be launched cannot be missed there.
-// Rows indexed by COUNT hold the counting kernels FIRST ([!count]): the order in which k_trace<true, .> and k_trace<false, .> are
-// first named here decides hipcc's register assignment in k_trace<., kPrimaryNone> (same resources, another instruction stream),
-// and with this order the device code is what it has been since the kernels were tuned and measured.
-const decltype(&k_trace<true, kPrimaryNone>) kTrace[2][3] = {            // [!count][primary]
-	{ k_trace<true, kPrimaryNone>, k_trace<true, kPrimaryAll>, k_trace<true, kPrimaryList> },
-	{ k_trace<false, kPrimaryNone>, k_trace<false, kPrimaryAll>, k_trace<false, kPrimaryList> } };
-const decltype(&k_trace_fat<true, kPrimaryNone>) kTraceFat[2][3] = {     // [!count][primary]
-	{ k_trace_fat<true, kPrimaryNone>, k_trace_fat<true, kPrimaryAll>, k_trace_fat<true, kPrimaryList> },
-	{ k_trace_fat<false, kPrimaryNone>, k_trace_fat<false, kPrimaryAll>, k_trace_fat<false, kPrimaryList> } };
+// Every instantiation a launch of the trace stage may pick, by template argument; a combination that does not exist is nullptr (launch_trace
+// refuses it).  k_trace and k_primary_cand use dynamic LDS: plan_trace_lds raises their limit by walking trace_kernel() and kPrimaryCand, so a
+// k_trace that can be launched cannot be missed there.
+// The counting kernels come FIRST ([!count]): the order in which k_trace<true, .> and k_trace<false, .> are first named decides hipcc's register
+// assignment in k_trace<., kPrimaryNone> (same resources, another instruction stream: profiles/trace_launch_refactor.txt), and with this order
+// the device code of every older instantiation is what it has been since the kernels were tuned and measured (profiles/one_trace_kernel.txt).
+constexpr int kPrimaryForms = 4;
+static_assert(kPrimaryNone == 0 && kPrimaryAll == 1 && kPrimaryList == 2 && kPrimaryActive == 3, "the trace tables are indexed by PRIMARY");
+auto trace_kernel(bool count, int primary, bool lens) {
+	static const decltype(&k_trace<true, kPrimaryNone>) table[2][2][kPrimaryForms] = {      // [lens][!count][primary]; kernels.hpp: the lens concerns bounce 0, and no lists are read under it
+		{ { k_trace<true, kPrimaryNone>, k_trace<true, kPrimaryAll>, k_trace<true, kPrimaryList>, k_trace<true, kPrimaryActive> },
+		  { k_trace<false, kPrimaryNone>, k_trace<false, kPrimaryAll>, k_trace<false, kPrimaryList>, k_trace<false, kPrimaryActive> } },
+		{ { nullptr, k_trace<true, kPrimaryAll, true>, nullptr, k_trace<true, kPrimaryActive, true> }, { nullptr, k_trace<false, kPrimaryAll, true>, nullptr, k_trace<false, kPrimaryActive, true> } } };
+	return primary < 0 || primary >= kPrimaryForms ? nullptr : table[lens][!count][primary];
+}
+// kPrimaryActive has no k_trace_fat of its own: its fat rays are kPrimaryList's, over the same list (launch_trace).
+auto trace_fat_kernel(bool count, int primary, bool lens) {
+	using K = decltype(&k_trace_fat<true, kPrimaryNone>);
+	static const K table[2][2][3] = {                                      // [lens][!count][primary]
+		{ { k_trace_fat<true, kPrimaryNone>, k_trace_fat<true, kPrimaryAll>, k_trace_fat<true, kPrimaryList> },
+		  { k_trace_fat<false, kPrimaryNone>, k_trace_fat<false, kPrimaryAll>, k_trace_fat<false, kPrimaryList> } },
+		{ { nullptr, k_trace_fat<true, kPrimaryAll, true>, k_trace_fat<true, kPrimaryList, true> },
+		  { nullptr, k_trace_fat<false, kPrimaryAll, true>, k_trace_fat<false, kPrimaryList, true> } } };
+	if (primary == kPrimaryActive) primary = kPrimaryList;
+	return primary < 0 || primary > kPrimaryList ? K(nullptr) : table[lens][!count][primary];
+}
 const decltype(&k_primary_cand<true>) kPrimaryCand[2] = { k_primary_cand<true>, k_primary_cand<false> };                                    // [!count]
 const decltype(&k_tile_stream<false>) kTileStream[2] = { k_tile_stream<false>, k_tile_stream<true> };                                         // [ggx]
-static_assert(kPrimaryNone == 0 && kPrimaryAll == 1 && kPrimaryList == 2, "kTrace / kTraceFat are indexed by PRIMARY");
-// The thin-lens twins of the bounce-0 trace kernels (mirt_set_lens), named after every table above so that those keep their device code.
-const decltype(&k_trace<true, kPrimaryNone>) kTraceLens[2] = { k_trace<true, kPrimaryAll, true>, k_trace<false, kPrimaryAll, true> };               // [!count]
-const decltype(&k_trace_fat<true, kPrimaryNone>) kTraceFatLens[2] = { k_trace_fat<true, kPrimaryAll, true>, k_trace_fat<false, kPrimaryAll, true> };  // [!count]
-// The camera rays of the active tiles once a tile is frozen (mirt_freeze_tiles); named after every table above, for the same reason.
-const decltype(&k_trace_sparse<true, false>) kTraceSparse[2][2] = { { k_trace_sparse<true, false>, k_trace_sparse<true, true> }, { k_trace_sparse<false, false>, k_trace_sparse<false, true> } };   // [!count][lens]
-const decltype(&k_trace_fat<true, kPrimaryNone>) kTraceFatListLens[2] = { k_trace_fat<true, kPrimaryList, true>, k_trace_fat<false, kPrimaryList, true> };   // [!count]
 
 // One selector per stage that has SPARSE / LENS / RIS instantiations (kernels.hpp), named after the tables above; within each, the
 // instantiations of the default path first.  sparse = a tile is frozen (mirt_freeze_tiles), ris = mirt_set_light_ris above 0 where NEE runs.
@@ -555,26 +563,18 @@ struct TraceLaunch {
 	const uint32_t* listed_pixels;                   // kPrimaryList: count of the pixels listed at in.a (NULL otherwise)
 	DevCounters* ctr;
 };
-// k_trace<count, primary> over n_rays, then (with a tree) the few rays too "fat" for it: brute force, one workgroup each.
-// lens (with kPrimaryAll only): the thin-lens twins.
-void launch_trace(const mirt_ctx* c, hipStream_t st, const SceneDev& sc, const FrameParams& fp, uint64_t n_rays, bool count, int primary, const TraceLaunch& t, bool lens = false) {
-	hipLaunchKernelGGL(lens ? kTraceLens[!count] : kTrace[!count][primary], dim3(trace_grid(c, n_rays)), dim3(kTraceBlock), trace_lds(c), st, sc, fp, t.in, t.hit, t.closest_queue, t.closest_work,
+// k_trace<count, primary, lens> over n_rays, then (with a tree) the few rays too "fat" for it: brute force, one workgroup each.
+// kPrimaryList / kPrimaryActive: t.in.a is the pixel list and t.listed_pixels its count (kernels.hpp stream_pixel_list); lens: at bounce 0 only.
+int launch_trace(mirt_ctx* c, hipStream_t st, const SceneDev& sc, const FrameParams& fp, uint64_t n_rays, bool count, int primary, const TraceLaunch& t, bool lens = false) {
+	const auto trace = trace_kernel(count, primary, lens);
+	const auto fat = trace_fat_kernel(count, primary, lens);
+	if (!trace || !fat) return fail(c, MIRT_ERR_ARG, "no trace kernel for primary = %d%s", primary, lens ? " under a lens" : "");
+	hipLaunchKernelGGL(trace, dim3(trace_grid(c, n_rays)), dim3(kTraceBlock), trace_lds(c), st, sc, fp, t.in, t.hit, t.closest_queue, t.closest_work,
 	                   t.sh, t.sink, t.shadow_queue, t.shadow_work, t.fat_closest, t.fat_shadow, t.ctr, c->lens);
 	// a large scene (100 k spheres: ~100 us per ray) wants as many fat rays in flight as there are (a few hundred per launch); k_trace_fat grid-strides
 	const uint32_t fat_grid = sc.n_spheres > 4096 ? static_cast<uint32_t>(c->n_cu) * 2u : 64u;
-	if (sc.use_bvh) hipLaunchKernelGGL(lens ? kTraceFatLens[!count] : kTraceFat[!count][primary], dim3(fat_grid), dim3(1024), 0, st, sc, fp, t.in, t.hit, t.fat_closest, t.sh, t.sink, t.fat_shadow, t.ctr, t.listed_pixels, c->lens);
-}
-
-// The camera rays of a batch that walk the tree (or the brute-force loop) once a tile is frozen: k_trace_sparse over the active pixels' list, then
-// its fat rays through k_trace_fat's kPrimaryList form, whose list and count are that list and its length.
-void launch_trace_sparse(const mirt_ctx* c, hipStream_t st, const SceneDev& sc, const FrameParams& fp, uint32_t active_pix, bool count, const TraceLaunch& t, bool lens) {
-	const uint32_t* list = c->active_list.as<uint32_t>();
-	hipLaunchKernelGGL(kTraceSparse[!count][lens], dim3(trace_grid(c, static_cast<uint64_t>(active_pix) * fp.batch_n)), dim3(kTraceBlock), trace_lds(c), st, sc, fp, list + 1, active_pix, t.hit,
-	                   t.closest_work, t.fat_closest, t.ctr, c->lens);
-	const uint32_t fat_grid = sc.n_spheres > 4096 ? static_cast<uint32_t>(c->n_cu) * 2u : 64u;
-	StreamBuf listed = t.in;
-	listed.a = reinterpret_cast<float4*>(const_cast<uint32_t*>(list + 1));             // kernels.hpp stream_pixel_list
-	if (sc.use_bvh) hipLaunchKernelGGL(lens ? kTraceFatListLens[!count] : kTraceFat[!count][kPrimaryList], dim3(fat_grid), dim3(1024), 0, st, sc, fp, listed, t.hit, t.fat_closest, t.sh, t.sink, t.fat_shadow, t.ctr, list, c->lens);
+	if (sc.use_bvh) hipLaunchKernelGGL(fat, dim3(fat_grid), dim3(1024), 0, st, sc, fp, t.in, t.hit, t.fat_closest, t.sh, t.sink, t.fat_shadow, t.ctr, t.listed_pixels, c->lens);
+	return MIRT_OK;
 }
 
 // mirt_set_stream_order(1): a batch is ONE launch — the whole bounce loop of a (tile, accumulation) stream runs in one workgroup, in the reference's
@@ -730,15 +730,21 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			  // the adds of bounce-1 that waited for occlusion land in the paths' contribution words before k_shade adds this bounce's terms;
 			  const ShadowSink sink{ contrib, batch_n, fp.pix_bits, nullptr };
 			  StreamBuf rays = in;
-			  // kPrimaryList reads nothing else of the stream: camera rays are functions of their index.  Once a tile is frozen: the listed pixels of the active tiles.
-			  uint32_t* listed_count = (lists && sparse) ? c->listed_active.as<uint32_t>() : cw.listed_pixels();
-			  if (lists) rays.a = reinterpret_cast<float4*>(sparse ? c->listed_active.as<uint32_t>() + 1 : c->cand_listed.as<uint32_t>());   // kernels.hpp stream_pixel_list
-			  const TraceLaunch tl{ rays, sl.hit, lists ? Queue{ listed_count, 0u } : bc.stream_queue(bounce), bc.closest_work(bounce),      // kPrimaryList: n[0] = listed pixels
+			  // A listed launch reads nothing else of the stream: camera rays are functions of their index.  kPrimaryList: the pixels without a candidate
+			  // list (once a tile is frozen: those of them in the active tiles); kPrimaryActive, a tile frozen and no lists: every pixel of the active tiles.
+			  const int primary = bounce != 0 ? kPrimaryNone : lists ? kPrimaryList : sparse ? kPrimaryActive : kPrimaryAll;
+			  uint32_t* listed_count = nullptr;
+			  const uint32_t* list = nullptr;
+			  if (primary == kPrimaryActive) { listed_count = c->active_list.as<uint32_t>(); list = listed_count + 1; }
+			  else if (lists && sparse) { listed_count = c->listed_active.as<uint32_t>(); list = listed_count + 1; }
+			  else if (lists) { listed_count = cw.listed_pixels(); list = c->cand_listed.as<uint32_t>(); }
+			  if (list) rays.a = reinterpret_cast<float4*>(const_cast<uint32_t*>(list));      // kernels.hpp stream_pixel_list
+			  const TraceLaunch tl{ rays, sl.hit, listed_count ? Queue{ listed_count, 0u } : bc.stream_queue(bounce), bc.closest_work(bounce),      // listed: n[0] = listed pixels
 			                        sl.shadow_buf, sink, shadow_pending ? bc.shadow_queue(bounce - 1) : bc.empty_queue(), bc.shadow_work(shadow_pending ? bounce - 1 : 0),
-			                        bc.fat_closest(bounce, fat_lists), bc.fat_shadow(bounce, fat_lists), lists ? listed_count : nullptr, ctr };
-			  // sparse, with lists: k_trace<., kPrimaryList> as ever, over the listed pixels of the active tiles
-			  if (sparse && bounce == 0 && !lists) launch_trace_sparse(c, st, sc, fp, active_pix, count, tl, lens);
-			  else launch_trace(c, st, sc, fp, total, count, lists ? kPrimaryList : bounce == 0 ? kPrimaryAll : kPrimaryNone, tl, bounce == 0 && lens); }
+			                        bc.fat_closest(bounce, fat_lists), bc.fat_shadow(bounce, fat_lists), listed_count, ctr };
+			  // (the grid of a kPrimaryList launch is sized for the whole batch, as ever: its count is known on the device only)
+			  const int r = launch_trace(c, st, sc, fp, primary == kPrimaryActive ? static_cast<uint64_t>(active_pix) * batch_n : total, count, primary, tl, bounce == 0 && lens);
+			  if (r) return r; }
 			if (bounce == 0 && c->aov_on) { const int r = launch_first_hit_aov(c, sl, st, sc, fp); if (r) return r; }
 			{ Bracket t(c, MIRT_K_SHADE, st);
 			  // policy.brdf = 1 (#define BRDF 1): Closure<GGX> with this bounce's gloss decay, passed by value
@@ -942,10 +948,9 @@ int plan_trace_lds(mirt_ctx* c) {
 	const LdsPlan p = lds_plan(c);
 	c->scene.stack16 = p.stack16; c->scene.lds_recs = p.lds_recs; c->scene.lds_spheres = p.lds_spheres;
 	const int lds_max = static_cast<int>(kLdsPerCu);
-	for (const auto& row : kTrace) for (const auto k : row) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-	for (const auto k : kPrimaryCand) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-	for (const auto k : kTraceLens) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-	for (const auto& row : kTraceSparse) for (const auto k : row) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+	for (int k = 0; k < 2 * kPrimaryForms * 2; k++)                               // every (count, primary, lens) that exists
+		if (const auto f = trace_kernel(k & 1, (k >> 1) % kPrimaryForms, k >= 2 * kPrimaryForms)) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+	for (const auto f : kPrimaryCand) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
 	return MIRT_OK;
 }
 
@@ -997,7 +1002,7 @@ int debug_trace(mirt_ctx* c, const char* who, size_t n, const float* p_xyz, cons
 	tl.fat_closest = bc.fat_closest(0, fat.as<uint32_t>()); tl.fat_shadow = bc.fat_shadow(0, fat.as<uint32_t>());
 	tl.ctr = ctr.as<DevCounters>();                                              // scratch: the context's counters stay as they are
 	{ Bracket t(c, MIRT_K_TRACE);                                                // policy.profile: the launch is timed like those of a batch (mirt_get_kernel_times)
-	  launch_trace(c, c->stream, trace_scene(c), FrameParams{}, n, false, kPrimaryNone, tl); }
+	  const int r = launch_trace(c, c->stream, trace_scene(c), FrameParams{}, n, false, kPrimaryNone, tl); if (r) return r; }
 	hipError_t e = hipGetLastError();
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
 	if (e == hipSuccess) e = hipMemcpy(result, res.ptr, result_bytes, hipMemcpyDeviceToHost);

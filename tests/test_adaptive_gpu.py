@@ -15,6 +15,7 @@ import pytest
 import adaptive_twin as at
 import noise_twin as nt
 import oracle_binding as ob
+import test_light_ris_gpu as rg
 from oracle_binding import bits
 
 pytestmark = pytest.mark.gpu
@@ -115,6 +116,8 @@ CONFIGS = {
     "streams 1": dict(streams=1),
     "streams 3, max_batch 2": dict(streams=3, max_batch=2),
     "ggx with decay": dict(brdf=1, gloss_decay=[0.0, 0.3, 0.6]),
+    "count_traffic, trace_primary_rays": dict(count_traffic=True, trace_primary_rays=True),      # k_trace<COUNT = true, kPrimaryActive>, tree walk
+    "count_traffic, no tree": dict(count_traffic=True, use_bvh=False),                           # the same, brute-force loop
 }
 
 
@@ -128,6 +131,24 @@ def test_frozen_tiles_in_every_mode(mirt, plain, name):
     r.Resize(W, H)
     run_schedule(r, ref, list(range(TILES)), what=name)
     r.close()
+
+
+@pytest.mark.parametrize("max_batch", [1, 5])
+@pytest.mark.parametrize("lens", [None, (0.05, 4.0)], ids=["pinhole", "lens"])
+@pytest.mark.parametrize("w,h", [(W, H), (32, 16)])
+def test_counting_camera_rays_of_the_active_tiles(mirt, w, h, lens, max_batch):
+    """k_trace<COUNT = true, kPrimaryActive, LENS>, tree walk and brute-force loop: camera rays only (max_bounces = 1), 5 accumulations, every third
+    tile frozen, 5 more; words, frame, `rays` and `terminated` are the oracle's.  `rays` is then active tiles x 256 x the accumulations issued while
+    they were active.  32 x 16 is two tiles, one of them frozen: with max_batch = 1 a launch is 256 rays — less than a workgroup, every ray in
+    slot 0 of its batch —, with max_batch = 5 it is five slots of one list."""
+    sc, tiles = scene_of(mirt, "default9"), (w // 16) * (h // 16)
+    active = tiles - len(range(0, tiles, 3))
+    kw = dict(lens=lens) if lens else {}
+    route = dict(count_traffic=True, max_batch=max_batch)
+    rg.check_frozen_against_oracle(mirt, sc, ("default9", "camera rays", lens), w, h,
+                                   (("tree", dict(route, use_bvh=True, trace_primary_rays=True)), ("brute", dict(route, use_bvh=False))), max_bounces=1, **kw)
+    want = rg.oracle_states(sc, ("default9", "camera rays", lens), w, h, (5, 10), max_bounces=1, tiles_after=(5, np.flatnonzero(np.arange(tiles) % 3 != 0)), **kw)
+    assert want[5]["counters"]["rays"] + want["active"][ob.TRAV_BRUTE]["rays"] == (tiles * 5 + active * 5) * 256      # what the contexts' `rays` were just compared with
 
 
 def test_frozen_tiles_async_lens_aov_and_wave_kernel(mirt, plain):

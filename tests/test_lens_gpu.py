@@ -234,7 +234,7 @@ def test_whole_path_under_a_lens_is_the_oracle(mirt, name, candidates):
 @pytest.mark.parametrize("candidates", [0, 7])
 @pytest.mark.parametrize("name", list(LENS_PATHS))
 def test_sparse_lens_kernels_are_the_oracle(mirt, name, candidates):
-    """k_trace_sparse<*, LENS> and k_shade<true, GGX, LENS = true, SPARSE = true, RIS>: 5 accumulations, every third tile frozen, 5 more."""
+    """k_trace<*, kPrimaryActive, LENS = true> and k_shade<true, GGX, LENS = true, SPARSE = true, RIS>: 5 accumulations, every third tile frozen, 5 more."""
     make, w, h, _, mb, lens, kw = LENS_PATHS[name]
     rg.check_frozen_against_oracle(mirt, make(mirt), (name, "lens", candidates), w, h, LENS_ROUTES, max_bounces=mb, lens=lens, light_ris=candidates, **kw)
 
