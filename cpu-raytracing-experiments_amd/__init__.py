@@ -111,6 +111,7 @@ def load_library():
         "mirt_set_gloss_decay": [P, vp, u32],
         "mirt_set_stream_order": [P, u32], "mirt_get_stream_order": [P, C.POINTER(u32)],
         "mirt_set_light_ris": [P, u32], "mirt_get_light_ris": [P, C.POINTER(u32)],
+        "mirt_set_transmission": [P, u32], "mirt_get_transmission": [P, C.POINTER(u32)],
         "mirt_resize": [P, u32, u32],
         "mirt_set_tile_range": [P, u32, u32], "mirt_set_tile_rows": [P, u32, u32],
         "mirt_reset": [P],
@@ -165,7 +166,7 @@ def load_library():
         "mirt_group_set_policy": [G, C.POINTER(Policy)],
         "mirt_group_set_gloss_decay": [G, vp, u32],
         "mirt_group_set_stream_order": [G, u32],
-        "mirt_group_set_light_ris": [G, u32],
+        "mirt_group_set_light_ris": [G, u32], "mirt_group_set_transmission": [G, u32],
         "mirt_group_resize": [G, u32, u32],
         "mirt_group_reset": [G],
         "mirt_group_accumulate": [G, u32],
@@ -298,8 +299,10 @@ class _Binding:
         """mirt_<name> or mirt_group_<name> on this object's handle, checked."""
         return self._check(getattr(self._lib, self._prefix + name)(getattr(self, self._handle), *args))
 
-    def _configure(self, gloss_decay, exact_stream_order, aov, light_ris=0):
+    def _configure(self, gloss_decay, exact_stream_order, aov, light_ris=0, transmission=False):
         """The end of both constructors, after the policy is set."""
+        if transmission:
+            self.set_transmission(True)
         if light_ris:
             self.set_light_ris(light_ris)
         if gloss_decay is not None:
@@ -347,6 +350,13 @@ class _Binding:
         0 = off (the default, the uniform draw); at most MAX_LIGHT_RIS; not in exact stream order.  Does not reset the accumulator.
         (A group: on every member.)"""
         self._call("set_light_ris", int(candidates))
+
+    def set_transmission(self, on: bool = True):
+        """True: a material with max(transmission) > 0 is glass — a smooth dielectric interface of index 1 + IOR_minus_one (Snell, unpolarised
+        Fresnel, total internal reflection; the tint transmission / max is applied once per pass through a ball; mirt.h, mirt_set_transmission).
+        False (the default): no kernel reads the two fields, as in the reference.  Shadow rays treat glass as opaque.  Not in exact stream
+        order.  Another estimand, and the accumulator is NOT reset: call Reset().  (A group: on every member.)"""
+        self._call("set_transmission", int(bool(on)))
 
     # -- scene hand-over (Application.cpp:230-234) -------------------------------------------------
     def _hand_over_scene(self, nodes=None):
@@ -546,7 +556,8 @@ class Renderer(_Binding):
     def __init__(self, scene: Scene, device: int = 0, max_bounces: int = 16, buckets: int = 5, mis: bool = True,
                  use_bvh: bool = False, count_traffic: bool = False, profile: bool = False, max_batch: int = 0,
                  allow_half_boxes: bool = True, reference_tree: bool = False, streams: int = 0, gpu_build: bool = False, trace_primary_rays: bool = False,
-                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False, light_ris: int = 0):
+                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False, light_ris: int = 0,
+                 transmission: bool = False):
         self._lib = load_library()
         self._ctx = C.c_void_p()
         self._lens_follows_camera = bool(lens)          # lens=True: the scene camera's f_number / focus_distance / unit_mm drive a thin lens
@@ -560,7 +571,7 @@ class Renderer(_Binding):
                              int(brdf))
         self._call("set_policy", C.byref(self.policy))
         self._call("debug_allow_half_boxes", int(allow_half_boxes))
-        self._configure(gloss_decay, exact_stream_order, aov, light_ris)
+        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission)
 
     def load_tile_counts(self, counts):
         """After load_accumulator: per-tile counts (positive multiples of `buckets`, at most accumulations); tiles below it are frozen."""
@@ -577,6 +588,11 @@ class Renderer(_Binding):
         v = C.c_uint32(0)
         self._call("get_light_ris", C.byref(v))
         return v.value
+
+    def transmission(self) -> bool:
+        v = C.c_uint32(0)
+        self._call("get_transmission", C.byref(v))
+        return bool(v.value)
 
     @property
     def stream_order(self) -> int:
@@ -712,7 +728,8 @@ class GroupRenderer(_Binding):
 
     def __init__(self, scene: Scene, devices=(0,), max_bounces: int = 16, buckets: int = 5, mis: bool = True, use_bvh: bool = True,
                  count_traffic: bool = False, max_batch: int = 0, streams: int = 0, reference_tree: bool = False, gpu_build: bool = False,
-                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False, light_ris: int = 0):
+                 brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False, light_ris: int = 0,
+                 transmission: bool = False):
         self._lib = load_library()
         self._g = C.c_void_p()
         self._lens_follows_camera = bool(lens)
@@ -726,7 +743,7 @@ class GroupRenderer(_Binding):
         self.policy = Policy(max_bounces, buckets, int(mis), int(use_bvh), int(count_traffic), 0, max_batch, int(reference_tree), int(streams), int(gpu_build), 0,
                              int(brdf))
         self._call("set_policy", C.byref(self.policy))
-        self._configure(gloss_decay, exact_stream_order, aov, light_ris)
+        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission)
 
     def light_ris(self) -> int:
         """The members' setting (they all hold the same: set_light_ris sets every one)."""
@@ -735,6 +752,14 @@ class GroupRenderer(_Binding):
         if self._lib.mirt_get_light_ris(ctx, C.byref(v)) < 0:
             raise MirtError("mirt_get_light_ris failed on member 0")
         return v.value
+
+    def transmission(self) -> bool:
+        """The members' setting (they all hold the same: set_transmission sets every one)."""
+        ctx, v = C.c_void_p(), C.c_uint32(0)
+        self._call("member", 0, C.byref(ctx))
+        if self._lib.mirt_get_transmission(ctx, C.byref(v)) < 0:
+            raise MirtError("mirt_get_transmission failed on member 0")
+        return bool(v.value)
 
     def UpdateScene(self):
         self._hand_over_scene()

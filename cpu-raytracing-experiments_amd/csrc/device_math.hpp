@@ -224,6 +224,45 @@ MIRT_DI void ggx_sample(f3 F0, float alpha, f3 Vlocal, float u0, float u1, f3& d
 	estimator = vndf_estimator(F0, alpha, NdotV, NdotL, HdotV);
 }
 
+// ---- dielectric interface (mirt_set_transmission) ------------------------------------------------------------------------------------
+// The reference's Material carries transmission and IOR_minus_one (Primitives.hpp:18-27) and no closure of it reads them: there is no reference
+// text to restate, so this is a definition of the project's own, pinned to float64 Snell / Fresnel by tests/glass_definitions.py through
+// mirt_debug_math fn 11.  Smooth interface between index 1 and index n.  D is the ray's direction and N the unit normal that faces it (c = -N.D > 0),
+// both in ONE frame of the caller's choice, and `dir` comes back in that frame: the shading text passes world-space vectors, so that the path never
+// goes through the hit's tangent frame here — that frame (Sampling.hpp:150-159) is ill-conditioned near N.z = -1 and returns stretched directions
+// there, and a glass ball seen from inside faces the camera with exactly such normals.  fn 11 passes D = -Vl, N = +z.
+// entering: the ray comes from the index-1 side.  s1: the uniform draw that picks reflection (s1 < F) or refraction.  F: the unpolarised Fresnel
+// reflectance; reflected: dir is the mirror direction; tir: because of total internal reflection (then F = 1).
+// Radiance is NOT scaled by 1 / eta^2 on refraction: the factor cancels for every path that enters a ball and leaves it again, and a camera or a
+// light inside glass is not a case the scenes of this project have.
+// Operation order, one binary32 rounding each (this TU is built with -ffp-contract=off):
+//   n == 1 (index-matched):   F = 0, dir = D, bit for bit
+//   r = entering ? 1 / n : n;   c = -dot3(N, D);   sin2_t = (r * r) * (1 - c * c)
+//   mirror = D + (2 * c) * N, component by component
+//   sin2_t >= 1 (total internal reflection):   dir = mirror, F = 1
+//   c_t = sqrt(1 - sin2_t);   rc = r * c;   rct = r * c_t
+//   rs = (rc - c_t) / (rc + c_t);   rp = (c - rct) / (c + rct);   F = 0.5 * (rs * rs + rp * rp)
+//   s1 < F:   dir = mirror
+//   else:     k = rc - c_t;   dir = normalize3(r * D + k * N), component by component
+MIRT_DI void dielectric_interface(f3 D, f3 N, float n, bool entering, float s1, f3& dir, float& F, bool& reflected, bool& tir) {
+	tir = false;
+	if (n == 1.0f) { F = 0.0f; reflected = false; dir = D; return; }
+	const float r = entering ? 1.0f / n : n;
+	const float c = -dot3(N, D);
+	const float sin2_t = (r * r) * (1.0f - c * c);
+	const float c2 = 2.0f * c;
+	const f3 mirror{ D.x + c2 * N.x, D.y + c2 * N.y, D.z + c2 * N.z };
+	if (sin2_t >= 1.0f) { F = 1.0f; reflected = true; tir = true; dir = mirror; return; }
+	const float c_t = __builtin_sqrtf(1.0f - sin2_t);
+	const float rc = r * c, rct = r * c_t;
+	const float rs = (rc - c_t) / (rc + c_t);
+	const float rp = (c - rct) / (c + rct);
+	F = 0.5f * (rs * rs + rp * rp);
+	reflected = s1 < F;
+	const float k = rc - c_t;
+	dir = reflected ? mirror : normalize3(f3{ r * D.x + k * N.x, r * D.y + k * N.y, r * D.z + k * N.z });
+}
+
 MIRT_DI float powerHeuristic(float f, float g) { float f2 = f * f; return f2 / max_sel(1e-6f, f2 + g * g); }   // :241-244
 MIRT_DI float powerHeuristic_over_f(float f, float g) { return f / max_sel(1e-6f, f * f + g * g); }            // :245-247
 MIRT_DI float median3(float a, float b, float c) { return max_sel(min_sel(a, b), min_sel(max_sel(a, b), c)); } // :8-12

@@ -47,6 +47,7 @@ struct SceneDev {
 	const float4* mat_albedo;   // scene.material[].albedo
 	const float4* mat_emission; // scene.material[].emission
 	const float4* hdri;         // sky.hdri_data RGBA
+	const float4* mat_glass;    // scene.material[]: {transmission.rgb, 1 + IOR_minus_one} — read by the GLASS instantiations of k_shade only (mirt_set_transmission)
 	uint32_t n_spheres, n_recs, n_mat, n_lights;
 	uint32_t lds_recs;          // records [0, lds_recs) are staged in LDS by the trace kernels (top of the tree)
 	uint32_t lds_spheres;       // spheres [0, lds_spheres) likewise (all of them, or none)
@@ -67,6 +68,7 @@ struct SceneDev {
 // instead of one dword per member.  40 B per ray.
 struct StreamBuf {
 	float4* a;                  // {p.xyz, bits of path}: path = (batch slot << FrameParams::pix_bits) | local pixel index (tile_local*256 + ID); stands in for pixelID + seed[]
+	                            // (k_shade<GLASS> also sets kViaInterface in this word; no other kernel reads it: k_trace takes p only, and a shadow record gets the bare id)
 	float4* b;                  // {dir.xyz, throughput.r}
 	float2* c;                  // {throughput.g, throughput.b} — read by the hits only (the miss shader scales by throughput.r, Q10)
 	                            // (radiance has no plane: a path's running sum is its word of the contribution buffer, contrib_index)
@@ -874,6 +876,7 @@ MIRT_DI size_t contrib_index(uint32_t batch_n, uint32_t pix_bits, uint32_t path)
 // occ != nullptr (mirt_debug_trace_shadow): only the occlusion flag is stored.
 constexpr uint32_t kDestFull = 0x40000000u;
 constexpr uint32_t kDestPath = 0x3fffffffu;     // path ids use bits 0-29 (batch slot << pix_bits | pixel; capacity check in mirt_capi.hip)
+constexpr uint32_t kViaInterface = 0x80000000u; // k_shade<GLASS>, in a STREAM's path word (StreamBuf::a, never a shadow record's): the ray's direction was sampled by a dielectric interface
 struct ShadowSink {
 	float* contrib;             // the batch's contribution buffer
 	uint32_t batch_n, pix_bits;
@@ -1356,7 +1359,11 @@ MIRT_DI uint32_t block_compact(bool flag, uint32_t value, uint32_t* scratch, uin
 // in the compaction, but read no hit record, emit nothing and store nothing, their path's contribution word included.
 // RIS (mirt_set_light_ris): next event estimation picks its light among ris_m candidates by resampled importance sampling (shade_hit_body.inc) —
 // ris_m is 1 .. MIRT_MAX_LIGHT_RIS, the same for every lane.  The same text, the same launch bounds.
-template <bool FIRST, bool GGX, bool LENS = false, bool SPARSE = false, bool RIS = false>
+// GLASS (mirt_set_transmission, launched only while the scene has a transmissive material): such a material can take the dielectric interface of
+// shade_hit_body.inc, read from s_glass = sc.mat_glass.  pdf_in is recomputed from D (Q8), so "D was sampled by an interface" — an emitter it reaches
+// weighs 1 — travels as kViaInterface in the stream's path word: set where the survivor is stored, taken off where the word is read (phase 2) or
+// turned into a contribution index (phase 1).  GLASS = false reads neither, and is the text as it was.  The same launch bounds.
+template <bool FIRST, bool GGX, bool LENS = false, bool SPARSE = false, bool RIS = false, bool GLASS = false>
 __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
                                                   Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
                                                   const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens, uint32_t ris_m, const uint32_t* __restrict__ tile_frozen) {
@@ -1370,10 +1377,11 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 	__shared__ uint32_t compact_scratch[17];
 	__shared__ uint32_t hit_list[kShadeBlock];
 	__shared__ float4 s_albedo[MIRT_MAX_MATERIALS + 1], s_emission[MIRT_MAX_MATERIALS + 1];      // scene.material: 2 KB, read by every hit (GGX: s_albedo = {F0, roughness})
+	__shared__ float4 s_glass[GLASS ? MIRT_MAX_MATERIALS + 1 : 1];                             // GLASS only (no instruction of the others names it: they get no LDS for it)
 	uint32_t c_term = 0, c_drop = 0, parity = 0;
 	const uint32_t n_units = n_chunks * fp.first_groups;                       // FIRST: pieces of work = (chunk, group of accumulations)
 	if (FIRST ? blockIdx.x >= n_units : blockIdx.x * kShadeBlock >= n) return;
-	for (uint32_t m = threadIdx.x; m < sc.n_mat; m += kShadeBlock) { s_albedo[m] = GGX ? mat_ggx[m] : sc.mat_albedo[m]; s_emission[m] = sc.mat_emission[m]; }
+	for (uint32_t m = threadIdx.x; m < sc.n_mat; m += kShadeBlock) { s_albedo[m] = GGX ? mat_ggx[m] : sc.mat_albedo[m]; s_emission[m] = sc.mat_emission[m]; if (GLASS) s_glass[m] = sc.mat_glass[m]; }
 	__syncthreads();            // the table is read by every wave in phase 2; k_shade<FIRST> reaches no other barrier before that (the early return above is block-uniform)
 
 	// !FIRST: this lane's ray of the stream for the block-iteration at hand, and its hit record: requested one iteration ahead, so that the
@@ -1448,7 +1456,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 							const float4 b = in.b[i];                                      // {dir, throughput.r}
 							const float thr_x = b.w;
 							const f3 sky = sky_eval(sc, b.x, b.y, b.z);
-							float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, __float_as_uint(in.a[i].w));
+							float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, __float_as_uint(in.a[i].w) & (GLASS ? kDestPath : ~0u));
 							w[0] += thr_x * sky.x; w[1] += thr_x * sky.y; w[2] += thr_x * sky.z;
 						}
 					}
@@ -1456,7 +1464,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 				} else if (last_bounce) {
 					c_drop++;                                                         // Q5: still alive after the last bounce -> never accumulated: the word goes back to +0
 					if (!FIRST) {                                                     // (FIRST: W0 is +0)
-						float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, __float_as_uint(in.a[i].w));
+						float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, __float_as_uint(in.a[i].w) & (GLASS ? kDestPath : ~0u));
 						w[0] = 0.0f; w[1] = 0.0f; w[2] = 0.0f;
 					}
 				} else is_hit = true;
@@ -1469,6 +1477,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 
 		// ---- phase 2, one lane per hit ----
 		bool survive = false, has_shadow = false, terminated = false, has_E = false;
+		bool via_interface = false;                                            // GLASS
 		uint32_t path = 0;
 		f3 P{0, 0, 0}, ndir{0, 0, 0}, L{0, 0, 0}, srad{0, 0, 0}, E{0, 0, 0};
 		f3 thr{1.0f, 1.0f, 1.0f};
@@ -1479,10 +1488,12 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 			path = my_path;
 			f3 O_in{0, 0, 0};
 			float pdf_in = 0.0f;
+			bool after_interface = false;                                      // GLASS
 			if (!FIRST) {                                                      // the ray's three records
 				const float4 a = in.a[i], b = in.b[i];
 				const float2 c = in.c[i];
 				O_in = { a.x, a.y, a.z }; path = __float_as_uint(a.w);
+				if (GLASS) { after_interface = (path & kViaInterface) != 0u; path &= kDestPath; }
 				D = { b.x, b.y, b.z };
 				thr = { b.w, c.x, c.y };
 				pdf_in = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, D.z);           // out->pdf of the bounce that sampled D (Q8), bit for bit; Closure<GGX>::pdf = 0
@@ -1503,7 +1514,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 		// record pending sends E along (kDestFull); one without adds E to the path's word here.
 		const bool full = has_shadow & has_E;
 		if (survive) {
-			out.a[slot] = make_float4(P.x, P.y, P.z, __uint_as_float(path));
+			out.a[slot] = make_float4(P.x, P.y, P.z, __uint_as_float(GLASS && via_interface ? path | kViaInterface : path));
 			out.b[slot] = make_float4(ndir.x, ndir.y, ndir.z, thr.x);
 			out.c[slot] = make_float2(thr.y, thr.z);
 		}
@@ -1588,10 +1599,13 @@ MIRT_DI void stream_shade_hit(const SceneDev& sc, const FrameParams& fp, const f
 	float& light_distance = h.light_distance;
 	bool terminated = false;                                                   // here: a shaded hit that does not survive
 	constexpr bool RIS = false; constexpr uint32_t ris_m = 0u;                 // exact stream order replays the reference: one uniform draw
+	constexpr bool GLASS = false, after_interface = false;                     // ... and no closure of the reference reads transmission (mirt_set_transmission excludes this mode)
+	const float4* const s_glass = nullptr; bool via_interface = false;         // named by the GLASS text only: never evaluated here
 #define SHADE_HIT_ORIGIN stream_O
 #define SHADE_HIT_ACC stream_acc
 #define SHADE_HIT_SEED stream_seed
 #include "shade_hit_body.inc"
+	(void)via_interface;
 	if (!terminated) h.thr = thr;                                            // the survivor's throughput
 }
 constexpr uint32_t kStreamPlanes = 13;          // p, dir, throughput, radiance, pixelID
@@ -1895,6 +1909,11 @@ __global__ __launch_bounds__(kBlock) void k_debug_math(int fn, uint32_t n, const
 			out[4 * n + i] = __uint_as_float(rand_bounded_int(s2, __float_as_uint(in[2 * n + i])));
 		} break;
 		case 10: out[i] = sqrt_trav(in[i]); break;
+		case 11: {  // dielectric_interface: in Vl(3), n, entering (!= 0), s1 -> out dir(3), F, reflected, tir
+			f3 d; float F; bool reflected, tir;
+			dielectric_interface(f3{ -in[i], -in[n + i], -in[2 * n + i] }, f3{ 0.0f, 0.0f, 1.0f }, in[3 * n + i], in[4 * n + i] != 0.0f, in[5 * n + i], d, F, reflected, tir);
+			out[i] = d.x; out[n + i] = d.y; out[2 * n + i] = d.z; out[3 * n + i] = F; out[4 * n + i] = reflected ? 1.0f : 0.0f; out[5 * n + i] = tir ? 1.0f : 0.0f;
+		} break;
 		case 8: {   // Closure<GGX>::eval: in F0(3), alpha, L(3), V(3) -> out 3
 			const f3 r = ggx_eval(f3{ in[i], in[n + i], in[2 * n + i] }, in[3 * n + i], f3{ in[4 * n + i], in[5 * n + i], in[6 * n + i] }, f3{ in[7 * n + i], in[8 * n + i], in[9 * n + i] });
 			out[i] = r.x; out[n + i] = r.y; out[2 * n + i] = r.z;

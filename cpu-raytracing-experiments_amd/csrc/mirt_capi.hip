@@ -96,8 +96,11 @@ struct mirt_ctx {
 	bool have_scene = false, have_camera = false;
 
 	// scene
-	DeviceBuffer recs, recs_wide, spheres, prim_mat, light_sphere, light_emit, mat_albedo, mat_emission, mat_ggx, hdri;
+	DeviceBuffer recs, recs_wide, spheres, prim_mat, light_sphere, light_emit, mat_albedo, mat_emission, mat_ggx, mat_glass, hdri;
 	SceneDev scene{};
+	uint32_t transmission = 0;       // mirt_set_transmission: 1 = a transmissive material takes the dielectric interface (the GLASS instantiations of k_shade)
+	std::vector<float4> glass_host;  // the scene's {transmission.rgb, 1 + IOR_minus_one} per material, as uploaded: what the switch validates and looks for glass in
+	bool scene_has_glass = false;    // some material of the scene has max(transmission) > 0: only then does the switch change the kernels launched
 	std::vector<float> gloss_decay;  // gloss_decay_table (Renderer.hpp:212) by bounce, read at launch (mirt_set_gloss_decay); missing entries are 0
 	uint32_t light_ris = 0;          // mirt_set_light_ris: candidates per NEE light pick; 0 = the uniform draw, the kernels without the candidate loop
 	uint32_t stream_order = 0;       // mirt_set_stream_order: 1 = a batch is one k_tile_stream launch (the reference's stream slots and scalar tail, brute force)
@@ -538,7 +541,16 @@ auto primary_hits_kernel(bool count, bool wave, bool sparse) {      // wave: one
 		{ { k_primary_hits<true, true>, k_primary_hits<false, true> }, { k_primary_hits_wave<true, true>, k_primary_hits_wave<false, true> } } };
 	return table[sparse][wave][!count];
 }
-auto shade_kernel(bool first, bool ggx, bool lens, bool sparse, bool ris) {      // lens and sparse concern bounce 0 (first) only
+// glass = mirt_set_transmission while the scene has a transmissive material: the same table over the GLASS instantiations.
+auto shade_kernel(bool first, bool ggx, bool lens, bool sparse, bool ris, bool glass) {      // lens and sparse concern bounce 0 (first) only
+	static const decltype(&k_shade<false, false>) glass_table[2][2][2][3] = {    // [ris][sparse][ggx][first ? 1 + lens : 0]
+		{ { { k_shade<false, false, false, false, false, true>, k_shade<true, false, false, false, false, true>, k_shade<true, false, true, false, false, true> },
+		    { k_shade<false, true, false, false, false, true>, k_shade<true, true, false, false, false, true>, k_shade<true, true, true, false, false, true> } },
+		  { { nullptr, k_shade<true, false, false, true, false, true>, k_shade<true, false, true, true, false, true> }, { nullptr, k_shade<true, true, false, true, false, true>, k_shade<true, true, true, true, false, true> } } },
+		{ { { k_shade<false, false, false, false, true, true>, k_shade<true, false, false, false, true, true>, k_shade<true, false, true, false, true, true> },
+		    { k_shade<false, true, false, false, true, true>, k_shade<true, true, false, false, true, true>, k_shade<true, true, true, false, true, true> } },
+		  { { nullptr, k_shade<true, false, false, true, true, true>, k_shade<true, false, true, true, true, true> }, { nullptr, k_shade<true, true, false, true, true, true>, k_shade<true, true, true, true, true, true> } } } };
+	if (glass) return glass_table[ris][first && sparse][ggx][first ? 1 + lens : 0];
 	static const decltype(&k_shade<false, false>) table[2][2][2][3] = {    // [ris][sparse][ggx][first ? 1 + lens : 0]
 		{ { { k_shade<false, false>, k_shade<true, false>, k_shade<true, false, true> }, { k_shade<false, true>, k_shade<true, true>, k_shade<true, true, true> } },
 		  { { nullptr, k_shade<true, false, false, true>, k_shade<true, false, true, true> }, { nullptr, k_shade<true, true, false, true>, k_shade<true, true, true, true> } } },
@@ -751,7 +763,7 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			  const float decay = bounce < c->gloss_decay.size() ? c->gloss_decay[bounce] : 0.0f;
 			  // mirt_set_light_ris: the candidate loop is worth running only where NEE runs
 			  const uint32_t ris = fp.mis ? c->light_ris : 0u;
-			  hipLaunchKernelGGL(shade_kernel(bounce == 0, c->policy.brdf != 0, lens, sparse, ris != 0), dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
+			  hipLaunchKernelGGL(shade_kernel(bounce == 0, c->policy.brdf != 0, lens, sparse, ris != 0, c->transmission && c->scene_has_glass), dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
 			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, ris, tile_frozen); }
 		}
 	}
@@ -860,13 +872,13 @@ int check_scene_args(mirt_ctx* c, const SceneArgs& a) {
 
 // The scene's tables as the kernels read them (host copies: they outlive the stream synchronisation that ends their uploads).
 struct SceneTables {
-	std::vector<float4> sph, lsp, lem, alb, emi, ggx, sky;
+	std::vector<float4> sph, lsp, lem, alb, emi, ggx, gls, sky;
 	std::vector<int32_t> pm;
 };
 SceneTables flatten_tables(const SceneArgs& a) {
 	SceneTables t;
 	t.sph.resize(a.n_spheres); t.pm.resize(a.n_spheres); t.lsp.resize(a.n_lights); t.lem.resize(a.n_lights);
-	t.alb.resize(a.n_materials); t.emi.resize(a.n_materials); t.ggx.resize(a.n_materials); t.sky.resize(static_cast<size_t>(a.hdri_w) * a.hdri_h);
+	t.alb.resize(a.n_materials); t.emi.resize(a.n_materials); t.ggx.resize(a.n_materials); t.gls.resize(a.n_materials); t.sky.resize(static_cast<size_t>(a.hdri_w) * a.hdri_h);
 	for (uint32_t i = 0; i < a.n_spheres; i++) {
 		t.sph[i] = make_float4(a.bvh_prims[i].position[0], a.bvh_prims[i].position[1], a.bvh_prims[i].position[2], a.bvh_prims[i].radius_sq);
 		t.pm[i] = a.bvh_prims[i].material_ID;
@@ -885,9 +897,28 @@ SceneTables flatten_tables(const SceneArgs& a) {
 		t.alb[i] = make_float4(m.albedo[0], m.albedo[1], m.albedo[2], 0.0f);
 		t.emi[i] = make_float4(m.emission[0], m.emission[1], m.emission[2], 0.0f);
 		t.ggx[i] = make_float4(m.F0[0], m.F0[1], m.F0[2], m.roughness);   // Closure<GGX> (policy.brdf = 1)
+		t.gls[i] = make_float4(m.transmission[0], m.transmission[1], m.transmission[2], 1.0f + m.IOR_minus_one);   // the dielectric interface (mirt_set_transmission)
 	}
 	std::memcpy(t.sky.data(), a.hdri_rgba, t.sky.size() * sizeof(float4));
 	return t;
+}
+
+// mirt_set_transmission(1) asks this of the materials (rows {transmission.rgb, 1 + IOR_minus_one}); with the switch off no kernel reads them and
+// nothing is asked, as ever.  A transmissive material (max(transmission) > 0) needs a finite index above 0.
+int check_glass(mirt_ctx* c, const std::vector<float4>& gls) {
+	for (size_t i = 0; i < gls.size(); i++) {
+		const float t[3] = { gls[i].x, gls[i].y, gls[i].z };
+		for (int k = 0; k < 3; k++)
+			if (!(t[k] >= 0.0f && t[k] <= 1.0f)) return fail(c, MIRT_ERR_ARG, "material %zu: transmission[%d] = %g is not in [0, 1] (mirt_set_transmission is on)", i, k, static_cast<double>(t[k]));
+		const bool transmissive = t[0] > 0.0f || t[1] > 0.0f || t[2] > 0.0f;
+		if (transmissive && !(std::isfinite(gls[i].w) && gls[i].w > 0.0f))
+			return fail(c, MIRT_ERR_ARG, "material %zu is transmissive and its IOR_minus_one = %g is not a finite value above -1 (mirt_set_transmission is on)", i, static_cast<double>(gls[i].w) - 1.0);
+	}
+	return MIRT_OK;
+}
+bool has_glass(const std::vector<float4>& gls) {
+	for (const float4& g : gls) if (g.x > 0.0f || g.y > 0.0f || g.z > 0.0f) return true;
+	return false;
 }
 
 // The records the kernels walk for this scene, uploaded (a host-built tree) or built in place (the GPU LBVH over c->spheres, uploaded by the caller).
@@ -959,7 +990,7 @@ void commit_scene(mirt_ctx* c, const SceneArgs& a, const SceneRecords& t) {
 	s.recs = t.in_recs_wide ? c->recs_wide.as<float4>() : c->recs.as<float4>(); s.spheres = c->spheres.as<float4>(); s.prim_mat = c->prim_mat.as<int32_t>();
 	s.light_sphere = c->light_sphere.as<float4>(); s.light_emit = c->light_emit.as<float4>();
 	s.mat_albedo = c->mat_albedo.as<float4>(); s.mat_emission = c->mat_emission.as<float4>();
-	s.hdri = c->hdri.as<float4>();
+	s.hdri = c->hdri.as<float4>(); s.mat_glass = c->mat_glass.as<float4>();
 	s.n_spheres = a.n_spheres; s.n_recs = t.n_recs; s.n_mat = a.n_materials; s.n_lights = a.n_lights;
 	s.half_boxes = t.is_half ? 1u : 0u;
 	s.wide = t.is_wide ? 1u : 0u;
@@ -1053,7 +1084,7 @@ int mirt_destroy(mirt_ctx* c) {
 	c->slots.clear();
 	for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
 	DeviceBuffer* bufs[] = { &c->recs, &c->recs_wide, &c->spheres, &c->prim_mat, &c->light_sphere, &c->light_emit, &c->mat_albedo, &c->mat_emission,
-	                         &c->mat_ggx, &c->hdri, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
+	                         &c->mat_ggx, &c->mat_glass, &c->hdri, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
 	                         &c->cand, &c->cand_listed, &c->cand_words, &c->noise_rec, &c->noise_hist, &c->noise_above,
 	                         &c->tile_frozen, &c->active_list, &c->tile_counts };
 	for (DeviceBuffer* b : bufs) b->release();
@@ -1076,13 +1107,15 @@ int mirt_set_scene(mirt_ctx* c, const mirt_sphere* geometry, const mirt_sphere* 
 	int r = check_scene_args(c, a); if (r) return r;
 	HIP_TRY(c, hipSetDevice(c->device));
 	const SceneTables t = flatten_tables(a);     // host copies of tables and records: alive until the stream has been synchronised
+	if (c->transmission && (r = check_glass(c, t.gls))) return r;
 	SceneRecords tree;
 	if ((r = upload(c, c->spheres, t.sph)) || (r = build_scene_records(c, a, t.sph, tree)) || (r = upload(c, c->prim_mat, t.pm)) ||
 	    (r = upload(c, c->light_sphere, t.lsp)) || (r = upload(c, c->light_emit, t.lem)) || (r = upload(c, c->mat_albedo, t.alb)) ||
-	    (r = upload(c, c->mat_emission, t.emi)) || (r = upload(c, c->mat_ggx, t.ggx)) || (r = upload(c, c->hdri, t.sky))) return r;
+	    (r = upload(c, c->mat_emission, t.emi)) || (r = upload(c, c->mat_ggx, t.ggx)) || (r = upload(c, c->mat_glass, t.gls)) || (r = upload(c, c->hdri, t.sky))) return r;
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	c->cand_valid = false;                                                             // spheres or tree changed (a node-only update included)
 	commit_scene(c, a, tree);
+	c->glass_host = t.gls; c->scene_has_glass = has_glass(t.gls);
 	if ((r = plan_trace_lds(c))) return r;
 	c->have_scene = true;
 	return MIRT_OK;
@@ -1174,6 +1207,7 @@ int mirt_set_stream_order(mirt_ctx* c, uint32_t exact) {
 	if (exact && lens_on(c)) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which has no lens (Camera.hpp:80-88 ignores it): call mirt_set_lens(ctx, 0, 0) first");
 	if (exact && c->n_frozen) return fail(c, MIRT_ERR_STATE, "exact stream order runs a tile's whole bounce loop in one launch and has no form that skips frozen tiles (%u are frozen): mirt_reset first", c->n_frozen);
 	if (exact && c->light_ris) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which draws its NEE light uniformly (Renderer.hpp:259): call mirt_set_light_ris(ctx, 0) first");
+	if (exact && c->transmission) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, no closure of which reads transmission: call mirt_set_transmission(ctx, 0) first");
 	if (exact && c->aov_on) return fail(c, MIRT_ERR_STATE, "exact stream order keeps no hit records (k_tile_stream runs a tile's whole bounce loop in one launch), so it cannot feed the first-hit AOVs: call mirt_set_aov(ctx, 0) first");
 	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render in the mode they were issued under
 	c->stream_order = exact;
@@ -1189,6 +1223,18 @@ int mirt_set_light_ris(mirt_ctx* c, uint32_t candidates) {
 	c->light_ris = candidates;                                                      // the expectation is the same: no reset; the lists do not depend on it
 	return MIRT_OK;
 }
+// ---- dielectric interface for transmissive materials ---------------------------------------------
+int mirt_set_transmission(mirt_ctx* c, uint32_t on) {
+	if (!c) return MIRT_ERR_ARG;
+	if (on > 1) return fail(c, MIRT_ERR_ARG, "transmission %u is neither 0 (off: transmission and IOR_minus_one are read by no kernel) nor 1 (on)", on);
+	if (on && c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, no closure of which reads transmission: call mirt_set_stream_order(ctx, 0) first");
+	if (on == c->transmission) return MIRT_OK;
+	if (on && c->have_scene) { const int r = check_glass(c, c->glass_host); if (r) return r; }
+	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render under the setting they were issued under
+	c->transmission = on;                                                           // another estimand: the caller resets; the camera-ray lists do not depend on it
+	return MIRT_OK;
+}
+int mirt_get_transmission(const mirt_ctx* c, uint32_t* on) { if (!c || !on) return MIRT_ERR_ARG; *on = c->transmission; return MIRT_OK; }
 int mirt_get_light_ris(const mirt_ctx* c, uint32_t* candidates) { if (!c || !candidates) return MIRT_ERR_ARG; *candidates = c->light_ris; return MIRT_OK; }
 int mirt_get_stream_order(const mirt_ctx* c, uint32_t* exact) { if (!c || !exact) return MIRT_ERR_ARG; *exact = c->stream_order; return MIRT_OK; }
 int mirt_get_policy(const mirt_ctx* c, mirt_policy* p) {
@@ -1619,8 +1665,8 @@ int mirt_debug_trace_shadow(mirt_ctx* c, size_t n, const float* p_xyz, const flo
 
 int mirt_debug_math(mirt_ctx* c, int fn, size_t n, const float* in, float* out) {
 	if (!c) return MIRT_ERR_ARG;
-	static const int n_in[11] = { 1, 2, 1, 2, 2, 6, 8, 3, 10, 9, 1 }, n_out[11] = { 2, 1, 1, 3, 3, 10, 5, 5, 3, 6, 1 };
-	if (fn < 0 || fn > 10 || !in || !out || n == 0 || n >= (1u << 28)) return fail(c, MIRT_ERR_ARG, "bad arguments");
+	static const int n_in[12] = { 1, 2, 1, 2, 2, 6, 8, 3, 10, 9, 1, 6 }, n_out[12] = { 2, 1, 1, 3, 3, 10, 5, 5, 3, 6, 1, 6 };
+	if (fn < 0 || fn > 11 || !in || !out || n == 0 || n >= (1u << 28)) return fail(c, MIRT_ERR_ARG, "bad arguments");
 	HIP_TRY(c, hipSetDevice(c->device));
 	ScopedBuffer din, dout;
 	HIP_TRY(c, din.ensure(n * n_in[fn] * 4)); HIP_TRY(c, dout.ensure(n * n_out[fn] * 4));

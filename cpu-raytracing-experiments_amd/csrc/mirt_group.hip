@@ -216,6 +216,11 @@ int mirt_group_set_light_ris(mirt_group* g, uint32_t candidates) {
 	FOR_MEMBERS_AND_FULL(g, "mirt_set_light_ris", mirt_set_light_ris(ctx, candidates));
 	return MIRT_OK;
 }
+int mirt_group_set_transmission(mirt_group* g, uint32_t on) {
+	if (!g) return MIRT_ERR_ARG;
+	FOR_MEMBERS_AND_FULL(g, "mirt_set_transmission", mirt_set_transmission(ctx, on));
+	return MIRT_OK;
+}
 int mirt_group_pick_focus(mirt_group* g, uint32_t x, uint32_t y, float* distance, float* depth) {
 	if (!g) return MIRT_ERR_ARG;
 	mirt_ctx* ctx = g->members[0];                                                   // one ray: every member holds the whole scene

@@ -5,7 +5,7 @@
 // environment map the way the constructor does (stbi_loadf(..., 4), Application.cpp:225-231); --ambient sets sky.ambient_color, which scales it.
 //
 //   mirt_headless --scene default9|furnace|bvh_test|brdf_test|synthetic:N [--size WxH] [--spp N | --frames N] [--bounces B] [--buckets K] [--brute] [--devices 0,1,..]
-//                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm] [--aov PREFIX] [--light-ris M]
+//                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm] [--aov PREFIX] [--light-ris M] [--transmission]
 //                 [--f-number F] [--focus-distance D] [--unit-mm U] [--focus-pixel X,Y]
 //                 [--until-noise T] [--noise-quantile Q] [--noise-floor F] [--check-every N] [--max-accumulations M] [--noise-out map.pfm]
 //                 [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm]
@@ -25,6 +25,7 @@
 // --brdf 1 renders every hit with the GGX closure (#define BRDF 1, Renderer.hpp:70), --gloss-decay gives its per-bounce table (:212).
 // --exact-stream-order replays the reference's stream slots and its scalar intersection tail (BVH.hpp:270-286; brute force, mirt_set_stream_order).
 // --light-ris M picks the NEE light among M uniform candidates by resampled importance sampling (mirt_set_light_ris; 0 = off, at most 32).
+// --transmission renders the materials that carry a transmission as glass: a smooth dielectric interface of index 1 + IOR_minus_one (mirt_set_transmission).
 // --aov PREFIX sums the first-hit AOVs beside the frame (mirt_set_aov) and writes PREFIX.depth.pfm (one channel, `Pf`), PREFIX.normal.pfm and
 // PREFIX.albedo.pfm (`PF`) after the last frame.
 // --devices: the GPUs the one Renderer object uses (tile rows split over them inside the library, one RCCL gather per frame read).
@@ -47,7 +48,7 @@ static Material make_material(float ar, float ag, float ab, float er = 0, float 
 	m.emission[0] = er; m.emission[1] = eg; m.emission[2] = eb;
 	return m;
 }
-// the members only the GGX closure reads (F0, roughness) and those no closure reads (F80, transmission, IOR_minus_one)
+// the members only the GGX closure reads (F0, roughness), those only the dielectric interface reads (transmission, IOR_minus_one; --transmission) and F80, which nothing reads
 static Material with_ggx(Material m, vec3 F0, vec3 F80, float roughness, vec3 transmission = vec3{ 0, 0, 0 }, float IOR_minus_one = 0.0f) {
 	m.F0[0] = F0.x; m.F0[1] = F0.y; m.F0[2] = F0.z;
 	m.F80[0] = F80.x; m.F80[1] = F80.y; m.F80[2] = F80.z;
@@ -194,6 +195,7 @@ int main(int argc, char** argv) {
 	uint32_t check_every = 0, max_accumulations = 1000;
 	bool adaptive = false;
 	uint32_t min_accumulations = 0, light_ris = 0;
+	bool transmission = false;
 	std::string counts_out;
 	if (argc == 4 && std::string(argv[1]) == "--convert-hdr") {
 		// file-format check without a GPU: read a picture like stbi_loadf does (top-down) and store it again like Image::Store does (which
@@ -222,6 +224,7 @@ int main(int argc, char** argv) {
 		else if (a == "--out") out = next();
 		else if (a == "--aov") aov_prefix = next();
 		else if (a == "--light-ris") light_ris = static_cast<uint32_t>(std::atoi(next()));
+		else if (a == "--transmission") transmission = true;
 		else if (a == "--f-number") { f_number = static_cast<float>(std::atof(next())); lens = true; }
 		else if (a == "--focus-distance") { focus_distance = static_cast<float>(std::atof(next())); lens = true; }
 		else if (a == "--unit-mm") { unit_mm = static_cast<float>(std::atof(next())); lens = true; }
@@ -258,6 +261,7 @@ int main(int argc, char** argv) {
 		renderer.SetStreamOrder(exact_stream_order);
 		if (!aov_prefix.empty()) renderer.SetAOV(true);
 		renderer.SetLightRis(light_ris);
+		renderer.SetTransmission(transmission);
 		// pad the viewport to the tile requirement like UIRender does (Application.cpp:365-372)
 		const uint32_t t = static_cast<uint32_t>(Renderer::RequiredTiling());
 		w = (w + t - 1) & ~(t - 1); h = (h + t - 1) & ~(t - 1);

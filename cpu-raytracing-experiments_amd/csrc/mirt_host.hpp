@@ -191,6 +191,9 @@ public:
 	// The NEE light picked among `candidates` uniform draws by the reference's unused RIS<count> (Sampling.hpp:25-54; mirt.h, mirt_set_light_ris):
 	// 0 = off, the uniform draw of Renderer.hpp:259.  Same expectation, so the accumulator is not reset.
 	void SetLightRis(uint32_t candidates) { check(mirt_group_set_light_ris(group_, candidates), "mirt_group_set_light_ris"); }
+	// Transmissive materials (max(transmission) > 0) take a smooth dielectric interface of index 1 + IOR_minus_one (mirt.h, mirt_set_transmission); off by
+	// default, as in the reference, whose closures read neither field.  Another estimand: Reset() is the caller's to call.  Not in exact stream order.
+	void SetTransmission(bool on) { check(mirt_group_set_transmission(group_, on ? 1u : 0u), "mirt_group_set_transmission"); }
 	// Renderer.hpp:73-434.  Asynchronous: Render() / counters() / the destructor wait for the GPUs; called once per frame the library
 	// still batches the frames between two Render()s that are due (mirt.h, mirt_accumulate_async).
 	void Accumulate(uint32_t n_calls = 1) { check(mirt_group_accumulate_async(group_, n_calls), "mirt_group_accumulate_async"); }

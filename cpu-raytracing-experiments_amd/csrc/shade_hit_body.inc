@@ -5,14 +5,18 @@
 //     test_radiance_in_contrib.py and test_definitions_gpu.py;
 //   * stream_shade_hit (k_tile_stream, exact stream order) — held by tests/test_exact_stream_order.py.
 // The names are k_shade's.  The including scope provides
-//   constants           GGX; RIS (true: the NEE light is picked among ris_m candidates, a uint32_t the scope provides too)
+//   constants           GGX; RIS (true: the NEE light is picked among ris_m candidates, a uint32_t the scope provides too); GLASS (true: a
+//                       transmissive material can take the dielectric interface below, mirt_set_transmission; false: none of that text is compiled in)
 //   read                sc, fp, s_albedo, s_emission (the material tables in LDS), bounce, gloss_decay, light_selection_pdf,
-//                       pdf_in (out->pdf of the bounce that sampled D, Q8), hrec (HitRec), prim (= hrec.prim), D (f3)
+//                       pdf_in (out->pdf of the bounce that sampled D, Q8), hrec (HitRec), prim (= hrec.prim), D (f3);
+//                       GLASS only: s_glass (LDS, {transmission.rgb, 1 + IOR_minus_one} per material) and after_interface (bool: D was sampled
+//                       by a dielectric interface, so no light sample could have produced it)
 //   read and written    thr (f3: the closure's estimator, then the roulette's 1 / (1 - q), in place)
 //   written             P, L, srad, E, ndir (f3), light_distance (float), has_shadow, has_E, terminated, survive (bool; has_E is always
 //                       assigned, the other three flags are only ever set: the scope starts them at false — k_shade's locals do;
 //                       stream_shade_hit binds survive and has_shadow to its StreamHit, which k_tile_stream zeroes before the call); L, light_distance and srad
-//                       are assigned with has_shadow, E with has_E, ndir with survive
+//                       are assigned with has_shadow, E with has_E, ndir with survive; GLASS only: via_interface (bool, only ever set: ndir was
+//                       sampled by the interface — the scope hands it to the next bounce as after_interface)
 //   three expressions   SHADE_HIT_ORIGIN (f3), SHADE_HIT_ACC and SHADE_HIT_SEED (uint32_t): the ray's origin, its accumulation number and
 //                       its seed[ID] (Renderer.hpp:74,107), evaluated where they stand below — k_shade loads and derives them from its
 //                       stream at these points, and its registers depend on that order.  #undef'd at the end of this file.
@@ -26,7 +30,8 @@ const int32_t mat = sc.prim_mat[prim];
 const f3 O = SHADE_HIT_ORIGIN;
 const f3 hit{ O.x + D.x * depth, O.y + D.y * depth, O.z + D.z * depth };
 f3 N = normalize3(f3{ hit.x - hs.x, hit.y - hs.y, hit.z - hs.z });
-if (dot3(N, D) >= 0.0f) N = f3{ -N.x, -N.y, -N.z };
+const bool from_inside = dot3(N, D) >= 0.0f;
+if (from_inside) N = f3{ -N.x, -N.y, -N.z };
 const quat T = tangent_space(N);
 const f3 Vl = to_local(T, f3{ -D.x, -D.y, -D.z });
 P = { hit.x + N.x * 1e-4f, hit.y + N.y * 1e-4f, hit.z + N.z * 1e-4f };
@@ -42,9 +47,29 @@ if (GGX) {                                                         // closure se
 }
 const uint32_t acc = SHADE_HIT_ACC;
 const uint32_t seed = SHADE_HIT_SEED;
+// (The closure stream is hashed here and again in BRDF SAMPLING below, on purpose: the lobe must be known before next event estimation, and the text
+// below stays the one the instantiations without GLASS compile, draw for draw.)
+// DIELECTRIC INTERFACE, lobe choice (no reference text: Renderer.hpp reads neither transmission nor IOR_minus_one).  A material is transmissive
+// when tmax = max(transmission.rgb) > 0.  A hit reached from inside its sphere always takes the interface, one from outside with probability tmax:
+// s0 < tmax, s0 and s1 the 4th and 5th draws of this bounce's closure stream (the first three stay b0, b1 and the roulette's).  Selection
+// probability and lobe weight cancel, so the throughput of neither lobe is reweighted.  Any other hit draws what it draws without GLASS.
+bool interface = false;
+float4 glass = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+float glass_tmax = 0.0f, glass_s1 = 0.0f;
+if (GLASS) {
+	glass = s_glass[mat];
+	glass_tmax = max_sel(glass.x, max_sel(glass.y, glass.z));
+	if (glass_tmax > 0.0f) {
+		uint32_t rng = hash_2d(acc, seed + bounce * 2u + 1u);
+		(void)pcg_generate(rng); (void)pcg_generate(rng); (void)pcg_generate(rng);
+		const float s0 = rand_unit_float(rng);
+		glass_s1 = rand_unit_float(rng);
+		interface = from_inside || s0 < glass_tmax;
+	}
+}
 
 // NEXT EVENT ESTIMATION, Renderer.hpp:247-298
-if (fp.mis) {
+if (fp.mis && !(GLASS && interface)) {                             // the interface is a delta closure: no light sample can meet it
 	uint32_t rng = hash_2d(acc, seed + bounce * 2u);
 	if (RIS) {
 		// RIS<count>, Sampling.hpp:25-54: ris_m candidates from the plain draw's own stream, one kept by a weighted reservoir.  A candidate's weight is
@@ -81,7 +106,8 @@ if (is_emissive) {
 	if (fp.mis && bounce > 0) {
 		const float radius2 = hs.w;
 		const float center_dist2 = depth * (depth + Vl.z * (2.0f * __builtin_sqrtf(radius2))) + radius2;
-		const float weight = powerHeuristic(pdf_in, light_selection_pdf * spherePdf(radius2, center_dist2));
+		float weight = powerHeuristic(pdf_in, light_selection_pdf * spherePdf(radius2, center_dist2));
+		if (GLASS && after_interface) weight = 1.0f;                // the ray left a dielectric interface: the extension ray is the only sampler of this path
 		E = { (thr.x * weight) * em.x, (thr.y * weight) * em.y, (thr.z * weight) * em.z };
 	} else {
 		E = { em.x, em.y, em.z };                                   // Q9: no throughput
@@ -93,7 +119,16 @@ if (is_emissive) {
 	const float b0 = rand_unit_float(rng);
 	const float b1 = rand_unit_float(rng);
 	f3 sd;
-	if (GGX) {                                                      // Closure<GGX>::sample, DataStreams.hpp:200-218
+	if (GLASS && interface) {
+		// entering: the tint transmission / tmax, once per pass through the ball; leaving, reflected or totally reflected: weight 1.
+		// In WORLD space (sd is the next direction itself): the tangent frame is ill-conditioned near N.z = -1 (device_math.hpp)
+		float F; bool reflected, tir;
+		dielectric_interface(D, N, glass.w, !from_inside, glass_s1, sd, F, reflected, tir);
+		if (!reflected) {
+			if (!from_inside) thr = { thr.x * (glass.x / glass_tmax), thr.y * (glass.y / glass_tmax), thr.z * (glass.z / glass_tmax) };
+			P = { hit.x - N.x * 1e-4f, hit.y - N.y * 1e-4f, hit.z - N.z * 1e-4f };
+		}
+	} else if (GGX) {                                                      // Closure<GGX>::sample, DataStreams.hpp:200-218
 		f3 est;
 		ggx_sample(F0, alpha, Vl, b0, b1, sd, est);
 		thr = { thr.x * est.x, thr.y * est.y, thr.z * est.z };
@@ -108,6 +143,7 @@ if (is_emissive) {
 		const float inv = 1.0f / max_sel(MIRT_FLT_EPSILON, 1.0f - q);
 		thr = { thr.x * inv, thr.y * inv, thr.z * inv };
 		ndir = to_world(T, sd);
+		if (GLASS && interface) { ndir = sd; via_interface = true; }
 		survive = true;
 	}
 }

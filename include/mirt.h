@@ -46,7 +46,9 @@ typedef struct mirt_sphere {
 } mirt_sphere;
 
 /* Primitives.hpp:18-27 — alignas(32), 96 B.  The path reads albedo and emission with policy.brdf = 0 (Lambertian), F0, roughness
- * and emission with policy.brdf = 1 (GGX); F80, transmission and IOR_minus_one are read by no closure of the reference. */
+ * and emission with policy.brdf = 1 (GGX).  No closure of the reference reads F80, transmission or IOR_minus_one; transmission and
+ * IOR_minus_one are read by this library's dielectric interface once mirt_set_transmission(ctx, 1) is called (below) and by nothing
+ * otherwise; F80 is read by nothing. */
 typedef struct mirt_material {
 	float albedo[3];
 	float F0[3];
@@ -208,6 +210,38 @@ int mirt_get_stream_order(const mirt_ctx* ctx, uint32_t* exact);
 #define MIRT_MAX_LIGHT_RIS 32u
 int mirt_set_light_ris(mirt_ctx* ctx, uint32_t candidates);
 int mirt_get_light_ris(const mirt_ctx* ctx, uint32_t* candidates);
+
+/* ---- transmission: a smooth dielectric interface for the materials that carry one -----------------------------------------------
+ * The reference's glass materials (Application.cpp:73-74,89-90: transmission, IOR_minus_one) are read by none of its closures, so by default
+ * they render as the Lambertian or GGX balls their other fields describe.  on = 1: a material with tmax = max(transmission.rgb) > 0 is
+ * transmissive, and a hit on it is shaded like this (the definition is this library's own: device_math.hpp dielectric_interface,
+ * shade_hit_body.inc; float64 twin in tests/glass_definitions.py):
+ *   - lobe: a hit reached from INSIDE its sphere (the geometric normal had to be flipped) always takes the interface; one from outside takes
+ *     it when s0 < tmax; otherwise the hit is shaded by the unchanged text (NEE, emissive MIS, the policy's closure, roulette) with no
+ *     reweighting — selection probability and lobe weight cancel, so transmission sweeps continuously from the opaque material to glass.
+ *     s0, s1 are the 4th and 5th draws of the bounce's closure stream hash_2d(acc, seed + 2 * bounce + 1); a hit on any other material
+ *     draws exactly what it draws with the switch off.
+ *   - interface: no next event estimation (a delta closure).  n = 1 + IOR_minus_one, r = entering ? 1 / n : n, c = cos of incidence,
+ *     sin2_t = r^2 (1 - c^2).  sin2_t >= 1: total internal reflection, weight 1.  Else unpolarised Fresnel F = (rs^2 + rp^2) / 2; s1 < F reflects
+ *     (weight 1), otherwise the ray refracts by Snell's law, with weight transmission / tmax when ENTERING and 1 when leaving: the tint is a
+ *     surface tint applied once per pass through the ball, not an absorption along the path inside.  The next origin is the hit moved 1e-4
+ *     along the facing normal (reflection) or against it (refraction).  n == 1 in binary32: F = 0 and the ray keeps its direction bit for bit.
+ *     All of it on world-space vectors: the hit's tangent frame is ill-conditioned near N.z = -1 and is not used here.
+ *     The roulette then runs as ever on the new throughput, with the same third draw.
+ *   - an emitter hit by a ray that left an interface weighs 1 under MIS (E = throughput * emission): no light sample could have made that
+ *     path.  (policy.mis = 0 keeps Q9: E = emission.)  The miss shader is unchanged (Q10).
+ * Not physical, on purpose: no 1 / eta^2 radiance scaling (it cancels for every path that enters a ball and leaves it; a camera inside glass
+ * is not modelled); no medium stack — overlapping spheres are judged by the flipped normal alone; SHADOW RAYS TREAT GLASS AS OPAQUE, as every
+ * sphere: light behind glass arrives only through extension rays (the item above), so there are no caustics by NEE; no roughness, no F80.
+ * The first-hit AOVs are unchanged (albedo / F0 of the first hit).
+ * on = 0 (the default): the same device code as a context that never called this.  on = 1 over a scene WITHOUT a transmissive material
+ * launches that same code too.  Validation, with the switch on only: every transmission component must lie in [0, 1] and a transmissive
+ * material needs a finite IOR_minus_one > -1, else MIRT_ERR_ARG — from mirt_set_scene, and from this call over the current scene (the
+ * switch then stays off).  on > 1: MIRT_ERR_ARG.  Exact stream order and the switch exclude each other: MIRT_ERR_STATE both ways.
+ * Deferred mirt_accumulate_async calls are launched first, under the old setting.  The estimand changes and the accumulator is NOT
+ * reset: the caller does that (mirt_reset).  Combines with the lens, light RIS, AOVs, frozen tiles, the noise estimate, groups and both closures. */
+int mirt_set_transmission(mirt_ctx* ctx, uint32_t on);
+int mirt_get_transmission(const mirt_ctx* ctx, uint32_t* on);
 
 /* Renderer::Resize, Renderer.hpp:53-63: h_tiles = w/16, v_tiles = h/16 (truncating), allocates and zeroes
  * the accumulator, accumulations = 0.  Owns all tiles until mirt_set_tile_range says otherwise. */
@@ -422,6 +456,7 @@ int mirt_group_set_scene(mirt_group* group,
 int mirt_group_set_camera(mirt_group* group, const float pos[3], const float orient_xyzw[4], float half_width, float half_height, float z, float exposure);
 int mirt_group_set_lens(mirt_group* group, float aperture_radius, float focus_depth);   /* mirt_set_lens on every member */
 int mirt_group_set_light_ris(mirt_group* group, uint32_t candidates);             /* mirt_set_light_ris on every member */
+int mirt_group_set_transmission(mirt_group* group, uint32_t on);                   /* mirt_set_transmission on every member (and the gather context) */
 int mirt_group_pick_focus(mirt_group* group, uint32_t x, uint32_t y, float* distance, float* depth);   /* mirt_pick_focus on the first member */
 int mirt_group_set_policy(mirt_group* group, const mirt_policy* policy);
 int mirt_group_set_gloss_decay(mirt_group* group, const float* decay, uint32_t n);
@@ -488,6 +523,8 @@ int mirt_debug_trace_shadow(mirt_ctx* ctx, size_t n, const float* p_xyz, const f
  *     8 Closure<GGX>::eval         [DataStreams.hpp:189-195, Sampling.hpp:272-296]  in: F0(3n),alpha[n],Llocal(3n),Vlocal(3n)  out: 3n
  *     9 Closure<GGX>::sample       [DataStreams.hpp:200-218, Sampling.hpp:254-270,297-309]  in: F0(3n),alpha[n],Vlocal(3n),u0[n],u1[n]  out: 6n (dir, estimator)
  *    10 the sphere tests' sqrt (kernels.hpp sqrt_trav) — must equal IEEE sqrt for every input >= 0   in: x[n]  out: n
+ *    11 dielectric_interface (device_math.hpp; mirt_set_transmission)   in: Vl.x[n], Vl.y[n], Vl.z[n], n_ior[n], entering[n] (!= 0), s1[n]
+ *                                                           out: dir.x, dir.y, dir.z (local), F, reflected (0 / 1), tir (0 / 1)   (6n)
  *       (8, 9: the defined part of the reference's compiled-out GGX closure; not used by the path — DESIGN.md §7)
  */
 int mirt_debug_math(mirt_ctx* ctx, int fn, size_t n, const float* in, float* out);
