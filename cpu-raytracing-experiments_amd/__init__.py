@@ -112,6 +112,7 @@ def load_library():
         "mirt_set_stream_order": [P, u32], "mirt_get_stream_order": [P, C.POINTER(u32)],
         "mirt_set_light_ris": [P, u32], "mirt_get_light_ris": [P, C.POINTER(u32)],
         "mirt_set_transmission": [P, u32], "mirt_get_transmission": [P, C.POINTER(u32)],
+        "mirt_set_sky_sampling": [P, u32], "mirt_get_sky_sampling": [P, C.POINTER(u32)],
         "mirt_resize": [P, u32, u32],
         "mirt_set_tile_range": [P, u32, u32], "mirt_set_tile_rows": [P, u32, u32],
         "mirt_reset": [P],
@@ -149,6 +150,7 @@ def load_library():
         "mirt_debug_math": [P, i32, C.c_size_t, vp, vp],
         "mirt_debug_info": [P, vp],
         "mirt_debug_tree": [P, vp, C.c_size_t, vp],
+        "mirt_debug_sky_table": [P, vp, C.c_size_t, vp],
         "mirt_debug_primary_lists": [P, vp],
         "mirt_debug_primary_counts": [P, vp, C.c_size_t],
         "mirt_debug_allow_half_boxes": [P, i32],
@@ -166,7 +168,7 @@ def load_library():
         "mirt_group_set_policy": [G, C.POINTER(Policy)],
         "mirt_group_set_gloss_decay": [G, vp, u32],
         "mirt_group_set_stream_order": [G, u32],
-        "mirt_group_set_light_ris": [G, u32], "mirt_group_set_transmission": [G, u32],
+        "mirt_group_set_light_ris": [G, u32], "mirt_group_set_transmission": [G, u32], "mirt_group_set_sky_sampling": [G, u32],
         "mirt_group_resize": [G, u32, u32],
         "mirt_group_reset": [G],
         "mirt_group_accumulate": [G, u32],
@@ -299,8 +301,10 @@ class _Binding:
         """mirt_<name> or mirt_group_<name> on this object's handle, checked."""
         return self._check(getattr(self._lib, self._prefix + name)(getattr(self, self._handle), *args))
 
-    def _configure(self, gloss_decay, exact_stream_order, aov, light_ris=0, transmission=False):
+    def _configure(self, gloss_decay, exact_stream_order, aov, light_ris=0, transmission=False, sky_sampling=False):
         """The end of both constructors, after the policy is set."""
+        if sky_sampling:
+            self.set_sky_sampling(True)
         if transmission:
             self.set_transmission(True)
         if light_ris:
@@ -357,6 +361,13 @@ class _Binding:
         False (the default): no kernel reads the two fields, as in the reference.  Shadow rays treat glass as opaque.  Not in exact stream
         order.  Another estimand, and the accumulator is NOT reset: call Reset().  (A group: on every member.)"""
         self._call("set_transmission", int(bool(on)))
+
+    def set_sky_sampling(self, on: bool = True):
+        """True: the environment map is one more light of next event estimation, drawn by importance from a table the GPU builds at every
+        scene hand-over (mirt.h, mirt_set_sky_sampling); the miss shader's share is MIS-weighted against it.  False (the default): the sky is
+        met by extension rays only, as in the reference.  The same expectation with another variance: the accumulator is NOT reset.  No effect
+        without ambient light, with mis=False or over a black map.  Not in exact stream order.  (A group: on every member.)"""
+        self._call("set_sky_sampling", int(bool(on)))
 
     # -- scene hand-over (Application.cpp:230-234) -------------------------------------------------
     def _hand_over_scene(self, nodes=None):
@@ -557,7 +568,7 @@ class Renderer(_Binding):
                  use_bvh: bool = False, count_traffic: bool = False, profile: bool = False, max_batch: int = 0,
                  allow_half_boxes: bool = True, reference_tree: bool = False, streams: int = 0, gpu_build: bool = False, trace_primary_rays: bool = False,
                  brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False, light_ris: int = 0,
-                 transmission: bool = False):
+                 transmission: bool = False, sky_sampling: bool = False):
         self._lib = load_library()
         self._ctx = C.c_void_p()
         self._lens_follows_camera = bool(lens)          # lens=True: the scene camera's f_number / focus_distance / unit_mm drive a thin lens
@@ -571,7 +582,7 @@ class Renderer(_Binding):
                              int(brdf))
         self._call("set_policy", C.byref(self.policy))
         self._call("debug_allow_half_boxes", int(allow_half_boxes))
-        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission)
+        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission, sky_sampling)
 
     def load_tile_counts(self, counts):
         """After load_accumulator: per-tile counts (positive multiples of `buckets`, at most accumulations); tiles below it are frozen."""
@@ -592,6 +603,11 @@ class Renderer(_Binding):
     def transmission(self) -> bool:
         v = C.c_uint32(0)
         self._call("get_transmission", C.byref(v))
+        return bool(v.value)
+
+    def sky_sampling(self) -> bool:
+        v = C.c_uint32(0)
+        self._call("get_sky_sampling", C.byref(v))
         return bool(v.value)
 
     @property
@@ -671,6 +687,19 @@ class Renderer(_Binding):
         self._call("debug_tree", _ptr(words), words.nbytes, info)
         return words, dict(zip(("records", "record_bytes", "layout", "depth"), [int(v) for v in info]))
 
+    def debug_sky_table(self) -> dict:
+        """The sky sampling table (set_sky_sampling), read back from the device as float32 arrays: "marg" [rows] and "rowsum" [rows], the cell
+        edges "tn" and "ts" [rows + 1] (1 - sin el, 1 + sin el), "cond" and "dens" [rows, cols]; "rows", "cols" and "total" (np.float32)."""
+        info = (C.c_uint32 * 4)()
+        self._call("debug_sky_table", None, 0, info)
+        rows, cols, n = int(info[0]), int(info[1]), int(info[3])
+        t = np.zeros(n, dtype=np.float32)
+        self._call("debug_sky_table", _ptr(t), n, info)
+        o = [0, rows, 2 * rows, 3 * rows + 1, 4 * rows + 2, 4 * rows + 2 + rows * cols, n]
+        return {"rows": rows, "cols": cols, "total": np.array([info[2]], dtype=np.uint32).view(np.float32)[0], "words": t,
+                "marg": t[o[0]:o[1]], "rowsum": t[o[1]:o[2]], "tn": t[o[2]:o[3]], "ts": t[o[3]:o[4]],
+                "cond": t[o[4]:o[5]].reshape(rows, cols), "dens": t[o[5]:o[6]].reshape(rows, cols)}
+
     def debug_primary_lists(self) -> list:
         """hist[n] = pixels whose candidate list holds n spheres (n = 0..7), hist[8] = 8 or more, hist[9] = pixels without a list."""
         out = (C.c_uint32 * 10)()
@@ -729,7 +758,7 @@ class GroupRenderer(_Binding):
     def __init__(self, scene: Scene, devices=(0,), max_bounces: int = 16, buckets: int = 5, mis: bool = True, use_bvh: bool = True,
                  count_traffic: bool = False, max_batch: int = 0, streams: int = 0, reference_tree: bool = False, gpu_build: bool = False,
                  brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False, light_ris: int = 0,
-                 transmission: bool = False):
+                 transmission: bool = False, sky_sampling: bool = False):
         self._lib = load_library()
         self._g = C.c_void_p()
         self._lens_follows_camera = bool(lens)
@@ -743,7 +772,7 @@ class GroupRenderer(_Binding):
         self.policy = Policy(max_bounces, buckets, int(mis), int(use_bvh), int(count_traffic), 0, max_batch, int(reference_tree), int(streams), int(gpu_build), 0,
                              int(brdf))
         self._call("set_policy", C.byref(self.policy))
-        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission)
+        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission, sky_sampling)
 
     def light_ris(self) -> int:
         """The members' setting (they all hold the same: set_light_ris sets every one)."""
@@ -759,6 +788,14 @@ class GroupRenderer(_Binding):
         self._call("member", 0, C.byref(ctx))
         if self._lib.mirt_get_transmission(ctx, C.byref(v)) < 0:
             raise MirtError("mirt_get_transmission failed on member 0")
+        return bool(v.value)
+
+    def sky_sampling(self) -> bool:
+        """The members' setting (they all hold the same: set_sky_sampling sets every one)."""
+        ctx, v = C.c_void_p(), C.c_uint32(0)
+        self._call("member", 0, C.byref(ctx))
+        if self._lib.mirt_get_sky_sampling(ctx, C.byref(v)) < 0:
+            raise MirtError("mirt_get_sky_sampling failed on member 0")
         return bool(v.value)
 
     def UpdateScene(self):

@@ -74,6 +74,8 @@ struct StreamBuf {
 	                            // (radiance has no plane: a path's running sum is its word of the contribution buffer, contrib_index)
 	                            // (`pdf` has no plane: Closure::pdf of the sampled direction is (1/pi) max(0, dir.z) of the WORLD-space dir
 	                            //  (Q8, Renderer.hpp:386,401), a function of the stored direction, recomputed by the bounce that needs it)
+	float* w;                   // mirt_set_sky_sampling only (nullptr otherwise, and no other kernel than k_shade<SKY> names it): the MIS weight the miss shader gives
+	                            // thr.r x sky should this ray miss — the power heuristic of the closure's LOCAL pdf of the direction against the sky's (k_shade, SKY)
 };
 // kPrimaryList launches have no ray stream: the words at `a` are the list of pixels instead (k_primary_cand's, or the active tiles' part of it).
 MIRT_DI const uint32_t* stream_pixel_list(const StreamBuf& in) { return reinterpret_cast<const uint32_t*>(in.a); }
@@ -1324,6 +1326,149 @@ MIRT_DI f3 sky_eval(const SceneDev& sc, float x, float y, float z) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// The environment map as a light (mirt_set_sky_sampling; the definition is in mirt.h, "sampling the environment map")
+// ------------------------------------------------------------------------------------------------
+// sky_eval truncates ex = hdri_fw * u and ey = hdri_fh * v, so the image is seen through cols = max(w - 1, 1) by rows = max(h - 1, 1) CELLS: cell
+// (r, c) is ex in [c, c + 1), ey in [r, r + 1) and shows texel (r, c).  The table is one allocation of floats:
+//   marg[rows]        running sums of the row sums: marg[r] = rowsum[0] + ... + rowsum[r]; marg[rows - 1] is the total
+//   rowsum[rows]      the row sums themselves (= the last running sum of each row)
+//   tn[rows + 1]      1 - sin el(k), k = 0 .. rows, el(k) = pi (0.5 - k / rows): the cell edges in latitude, as the distance from y = +1 ...
+//   ts[rows + 1]      1 + sin el(k): ... and from y = -1 (each rounded from float64: near a pole sin el itself would lose the cell to cancellation)
+//   cond[rows * cols] running sums of the importances within each row
+//   dens[rows * cols] p(cell) = I / (Omega * total), in 1 / sr
+struct SkyTable {
+	const float* t;             // nullptr: no table (the switch is off)
+	uint32_t rows, cols;
+	MIRT_DI const float* marg() const { return t; }
+	MIRT_DI const float* rowsum() const { return t + rows; }
+	MIRT_DI const float* tn() const { return t + 2u * rows; }
+	MIRT_DI const float* ts() const { return t + 3u * rows + 1u; }
+	MIRT_DI const float* cond() const { return t + 4u * rows + 2u; }
+	MIRT_DI const float* dens() const { return t + 4u * rows + 2u + static_cast<size_t>(rows) * cols; }
+};
+inline size_t sky_table_floats(uint32_t rows, uint32_t cols) { return 4u * static_cast<size_t>(rows) + 2u + 2u * static_cast<size_t>(rows) * cols; }
+
+// Running sums of n values by one 256-thread workgroup in a FIXED order: thread t owns the K = ceil(n / 256) consecutive values [t K, t K + K) and
+// sums them left to right from +0 (l_j); thread 0 then sums the 256 chunk sums left to right (pre_t = the sum of the chunks before t); the running
+// sum at value t K + j is pre_t + l_j.  The last running sum is therefore pre_255 + chunk sum 255 = the value thread 0's loop ends with: what is
+// returned as the total to every thread.  A value takes at most K - 1 + 255 + 1 additions; no atomics, and the order does not depend on the launch.
+// `in` and `out` may be the same array (a thread reads its own chunk before it writes it).  s_pre = 257 floats of LDS.  All threads, converged.
+constexpr uint32_t kSkyBlock = 256;
+MIRT_DI float sky_block_scan(const float* in, float* out, uint32_t n, float* s_pre) {
+	const uint32_t K = (n + kSkyBlock - 1u) / kSkyBlock;
+	const uint32_t first = threadIdx.x * K;
+	float l = 0.0f;
+	for (uint32_t j = first; j < first + K && j < n; j++) l += in[j];
+	__syncthreads();                                                       // (s_pre may still be read from an earlier scan)
+	s_pre[threadIdx.x + 1u] = l;
+	__syncthreads();
+	if (threadIdx.x == 0) { float run = 0.0f; s_pre[0] = 0.0f; for (uint32_t t = 1; t <= kSkyBlock; t++) { run += s_pre[t]; s_pre[t] = run; } }
+	__syncthreads();
+	if (out) {
+		const float pre = s_pre[threadIdx.x];
+		l = 0.0f;
+		for (uint32_t j = first; j < first + K && j < n; j++) { l += in[j]; out[j] = pre + l; }
+	}
+	return s_pre[kSkyBlock];
+}
+// Pass 1, one workgroup per row of cells: the cell importances I = max(t.r amb.r, t.g amb.g, t.b amb.b) * Omega(r) (RIS's weight rule times the
+// cell's solid angle), left in dens[] for pass 2, and the row's sum.  Omega(r) = (2 pi / cols) (sin el(r) - sin el(r + 1)) and the edge tables come
+// from float64 (the difference of two binary32 sines would lose half the digits at the equator of a 2048-row map), each rounded to binary32 once.
+__global__ __launch_bounds__(kSkyBlock) void k_sky_importance(const float4* __restrict__ hdri, int32_t hdri_w, float amb_r, float amb_g, float amb_b, uint32_t rows, uint32_t cols, float* __restrict__ table) {
+	__shared__ float s_pre[kSkyBlock + 1];
+	const SkyTable sky{ table, rows, cols };
+	const uint32_t r = blockIdx.x;
+	const double half = 0.5 * (3.14159265358979323846 / static_cast<double>(rows));
+	const float omega = static_cast<float>((6.28318530717958647692 / static_cast<double>(cols)) * (2.0 * sin((2.0 * r + 1.0) * half) * sin(half)));
+	if (threadIdx.x == 0) {
+		for (uint32_t k = r; k <= (r + 1u == rows ? rows : r); k++) {         // edge r, and the last row also writes edge `rows`
+			const double sn = sin(k * half), ss = sin((rows - k) * half);
+			table[2u * rows + k] = static_cast<float>(2.0 * sn * sn);
+			table[3u * rows + 1u + k] = static_cast<float>(2.0 * ss * ss);
+		}
+	}
+	float* I = table + (sky.dens() - sky.t) + static_cast<size_t>(r) * cols;
+	const float4* texel = hdri + static_cast<size_t>(r) * static_cast<size_t>(hdri_w);
+	for (uint32_t c = threadIdx.x; c < cols; c += kSkyBlock) {
+		const float4 t = texel[c];
+		I[c] = max_sel(max_sel(t.x * amb_r, t.y * amb_g), t.z * amb_b) * omega;
+	}
+	__syncthreads();
+	const float sum = sky_block_scan(I, nullptr, cols, s_pre);
+	if (threadIdx.x == 0) table[rows + r] = sum;
+}
+// Pass 2, one workgroup per row: every workgroup sums the row sums to the same total (the same order, hence the same word); workgroup 0 also
+// stores their running sums; then the row's own running sums and, from I still in dens[], the densities I / (Omega * total).
+__global__ __launch_bounds__(kSkyBlock) void k_sky_scan(uint32_t rows, uint32_t cols, float* __restrict__ table) {
+	__shared__ float s_pre[kSkyBlock + 1];
+	const SkyTable sky{ table, rows, cols };
+	const uint32_t r = blockIdx.x;
+	const float total = sky_block_scan(sky.rowsum(), r == 0 ? table : nullptr, rows, s_pre);
+	float* I = table + (sky.dens() - sky.t) + static_cast<size_t>(r) * cols;
+	(void)sky_block_scan(I, table + (sky.cond() - sky.t) + static_cast<size_t>(r) * cols, cols, s_pre);
+	const double half = 0.5 * (3.14159265358979323846 / static_cast<double>(rows));
+	const float omega = static_cast<float>((6.28318530717958647692 / static_cast<double>(cols)) * (2.0 * sin((2.0 * r + 1.0) * half) * sin(half)));
+	const float norm = omega * total;
+	__syncthreads();                                                       // the scan's second loop has read every I
+	for (uint32_t c = threadIdx.x; c < cols; c += kSkyBlock) I[c] = I[c] / norm;
+}
+
+// Smallest i in [0, n) with cdf[i] > x; the caller has x < cdf[n - 1].  ~log2(n) dependent loads.
+MIRT_DI uint32_t sky_upper(const float* cdf, uint32_t n, float x) {
+	uint32_t lo = 0u, hi = n - 1u;
+	while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (cdf[mid] > x) hi = mid; else lo = mid + 1u; }
+	return lo;
+}
+MIRT_DI float sky_below(float v) { return __uint_as_float(__float_as_uint(v) - 1u); }     // the binary32 below a positive v
+// sky_sample: (u0, u1) -> a direction and the density q (1 / sr) it was drawn with.  Operation order, one binary32 rounding each:
+//   x = min(u0 * total, below(total));  row = the first r with marg[r] > x;  lo = marg[r - 1] (0 for r = 0)
+//   du = min((x' - lo') / (hi' - lo'), 1 - 2^-24) for the column, from u1, the row's sum and its running sums
+//   the row's remainder is measured from the edge NEARER A POLE, where cos(elevation) = sqrt(t (2 - t)) is ill-conditioned in anything else:
+//     a cell above the equator (the straddling row: the half of it x falls in): dv = min((x - lo) / (hi - lo), 1 - 2^-24) from the upper edge,
+//       t = ta + dv * (tb - ta) over tn (the distance from y = +1), y = 1 - t
+//     a cell below it: dw = (hi - x) / (hi - lo) from the lower edge (> 0: x < hi), t = tb + dw * (ta - tb) over ts (the distance from y = -1), y = t - 1
+//   — either way uniform in sin(elevation)
+//   cos_el = sqrt(t * (2 - t));  phi = ((col - cols / 2) + du) * (2 pi / cols): uniform in azimuth;  dir = (cos_el cos phi, y, cos_el sin phi)
+// — the inverse of the latitude-longitude map of sky_eval (u = 1/2 + atan2(z, x) / 2 pi, v = 1/2 - asin(y) / pi) with exact arc functions.
+// A row or cell whose running sum does not rise is never picked, so q > 0.
+MIRT_DI f3 sky_sample(const SkyTable& sky, float u0, float u1, float& q, uint32_t& row, uint32_t& col) {
+	const float* marg = sky.marg();
+	const float total = marg[sky.rows - 1u];
+	const float x = min_sel(u0 * total, sky_below(total));
+	row = sky_upper(marg, sky.rows, x);
+	const float lo = row ? marg[row - 1u] : 0.0f;
+	const float hi = marg[row];
+	const float* cond = sky.cond() + static_cast<size_t>(row) * sky.cols;
+	const float rowsum = cond[sky.cols - 1u];
+	const float y_ = min_sel(u1 * rowsum, sky_below(rowsum));
+	col = sky_upper(cond, sky.cols, y_);
+	const float lo2 = col ? cond[col - 1u] : 0.0f;
+	const float du = min_sel((y_ - lo2) / (cond[col] - lo2), 0x1.fffffep-1f);
+	q = sky.dens()[static_cast<size_t>(row) * sky.cols + col];
+	const bool north = 2u * row + 1u == sky.rows ? (x - lo) <= (hi - x) : 2u * row + 1u < sky.rows;
+	const float* edge = north ? sky.tn() : sky.ts();
+	const float ta = edge[row], tb = edge[row + 1u];
+	const float t = north ? ta + min_sel((x - lo) / (hi - lo), 0x1.fffffep-1f) * (tb - ta) : tb + ((hi - x) / (hi - lo)) * (ta - tb);
+	const float y = north ? 1.0f - t : t - 1.0f;
+	const float cos_el = __builtin_sqrtf(max_sel(0.0f, t * (2.0f - t)));
+	// (phi through float64 and rounded once: in binary32 the scale 2 pi / cols and the product would each cost up to pi 2^-24 near the meridian)
+	const double dcols = static_cast<double>(sky.cols);
+	const float phi = static_cast<float>(((static_cast<double>(col) - 0.5 * dcols) + static_cast<double>(du)) * (6.28318530717958647692 / dcols));
+	float sn, cs; sincosf(phi, &sn, &cs);
+	return { cos_el * cs, y, cos_el * sn };
+}
+// sky_pdf: the density of the cell that sky_eval's own arithmetic (fast_atan2 / fast_asin) names for the direction — a function of the direction alone, what
+// both MIS weights are formed from.  Texel column w - 1 and row h - 1 (ex = hdri_fw, ey = hdri_fh exactly: measure zero) count as the last cell.
+MIRT_DI float sky_pdf(const SceneDev& sc, const SkyTable& sky, float x, float y, float z, uint32_t& row, uint32_t& col) {
+	const float ex = sc.hdri_fw * (0.5f + MIRT_INV_TWO_PI * fast_atan2(z, x));
+	const float ey = sc.hdri_fh * (0.5f - MIRT_INV_PI * fast_asin(y));
+	const uint32_t c = static_cast<uint32_t>(static_cast<int32_t>(ex)), r = static_cast<uint32_t>(static_cast<int32_t>(ey));
+	col = c < sky.cols ? c : sky.cols - 1u;
+	row = r < sky.rows ? r : sky.rows - 1u;
+	return sky.dens()[static_cast<size_t>(row) * sky.cols + col];
+}
+
+// ------------------------------------------------------------------------------------------------
 // SHADE — closest-hit shader, NEE, emissive, BRDF sample + Russian roulette + compaction, miss, accumulate
 // (Renderer.hpp:169-431).  FIRST = bounce 0: throughput 1 (Renderer.hpp:98-101) without reading it, and the path's contribution
 // word — its radiance for the rest of the batch (contrib_index) — is stored here for every path: +0 and what bounce 0 adds at once.
@@ -1363,16 +1508,19 @@ MIRT_DI uint32_t block_compact(bool flag, uint32_t value, uint32_t* scratch, uin
 // shade_hit_body.inc, read from s_glass = sc.mat_glass.  pdf_in is recomputed from D (Q8), so "D was sampled by an interface" — an emitter it reaches
 // weighs 1 — travels as kViaInterface in the stream's path word: set where the survivor is stored, taken off where the word is read (phase 2) or
 // turned into a contribution index (phase 1).  GLASS = false reads neither, and is the text as it was.  The same launch bounds.
-template <bool FIRST, bool GGX, bool LENS = false, bool SPARSE = false, bool RIS = false, bool GLASS = false>
+// SKY (mirt_set_sky_sampling, launched only while the table's total is above 0, the scene has ambient light and MIS is on): the environment map is
+// light number n_lights of next event estimation, drawn from `sky` (sky_sample) with one shadow ray of tfar = FLT_MAX, and the miss shader weighs
+// thr.r x sky by the MIS weight phase 2 stored for the ray in StreamBuf::w (bounce 0: 1).  SKY = false names neither `sky` nor the plane.
+template <bool FIRST, bool GGX, bool LENS = false, bool SPARSE = false, bool RIS = false, bool GLASS = false, bool SKY = false>
 __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
                                                   Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
-                                                  const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens, uint32_t ris_m, const uint32_t* __restrict__ tile_frozen) {
+                                                  const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens, uint32_t ris_m, const uint32_t* __restrict__ tile_frozen, SkyTable sky) {
 	static_assert(!(LENS || SPARSE) || FIRST, "the lens and the frozen tiles concern bounce 0 only");
 	const QueueView qin = FIRST ? queue_identity(fp.n_pix * fp.batch_n) : queue_view(in_queue);
 	const uint32_t n = qin.pre[kSegs];
 	const uint32_t n_chunks = (fp.n_pix + kShadeBlock - 1u) / kShadeBlock;      // FIRST
 	const bool last_bounce = !(bounce < fp.max_bounces - 1u);                 // Renderer.hpp:358
-	const float light_selection_pdf = 1.0f / static_cast<float>(fp.n_lights);  // Renderer.hpp:78
+	const float light_selection_pdf = 1.0f / static_cast<float>(SKY ? fp.n_lights + 1u : fp.n_lights);  // Renderer.hpp:78 (SKY: the sky is one more light)
 	__shared__ uint32_t append_scratch[72];
 	__shared__ uint32_t compact_scratch[17];
 	__shared__ uint32_t hit_list[kShadeBlock];
@@ -1450,14 +1598,14 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 					// ends: its word holds its result already (ACCUMULATION, Renderer.hpp:424-430, is k_merge_contrib's)
 					if (sc.has_ambient) {
 						if (FIRST) {
-							const f3 sky = sky_eval(sc, my_D.x, my_D.y, my_D.z);
-							W0 = { 0.0f + 1.0f * sky.x, 0.0f + 1.0f * sky.y, 0.0f + 1.0f * sky.z };
+							const f3 env = sky_eval(sc, my_D.x, my_D.y, my_D.z);
+							W0 = { 0.0f + 1.0f * env.x, 0.0f + 1.0f * env.y, 0.0f + 1.0f * env.z };
 						} else {
 							const float4 b = in.b[i];                                      // {dir, throughput.r}
-							const float thr_x = b.w;
-							const f3 sky = sky_eval(sc, b.x, b.y, b.z);
+							const float thr_x = SKY ? b.w * in.w[i] : b.w;                 // SKY: the MIS weight of this direction against the sky's own sampling
+							const f3 env = sky_eval(sc, b.x, b.y, b.z);
 							float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, __float_as_uint(in.a[i].w) & (GLASS ? kDestPath : ~0u));
-							w[0] += thr_x * sky.x; w[1] += thr_x * sky.y; w[2] += thr_x * sky.z;
+							w[0] += thr_x * env.x; w[1] += thr_x * env.y; w[2] += thr_x * env.z;
 						}
 					}
 					c_term++;
@@ -1478,6 +1626,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 		// ---- phase 2, one lane per hit ----
 		bool survive = false, has_shadow = false, terminated = false, has_E = false;
 		bool via_interface = false;                                            // GLASS
+		float miss_w = 1.0f;                                                   // SKY
 		uint32_t path = 0;
 		f3 P{0, 0, 0}, ndir{0, 0, 0}, L{0, 0, 0}, srad{0, 0, 0}, E{0, 0, 0};
 		f3 thr{1.0f, 1.0f, 1.0f};
@@ -1517,6 +1666,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 			out.a[slot] = make_float4(P.x, P.y, P.z, __uint_as_float(GLASS && via_interface ? path | kViaInterface : path));
 			out.b[slot] = make_float4(ndir.x, ndir.y, ndir.z, thr.x);
 			out.c[slot] = make_float2(thr.y, thr.z);
+			if (SKY) out.w[slot] = miss_w;
 		}
 		if (has_shadow) {
 			// the record holds its own ray and its path id (kernels.hpp ShadowBuf): k_trace reads nothing of the surviving ray
@@ -1601,11 +1751,12 @@ MIRT_DI void stream_shade_hit(const SceneDev& sc, const FrameParams& fp, const f
 	constexpr bool RIS = false; constexpr uint32_t ris_m = 0u;                 // exact stream order replays the reference: one uniform draw
 	constexpr bool GLASS = false, after_interface = false;                     // ... and no closure of the reference reads transmission (mirt_set_transmission excludes this mode)
 	const float4* const s_glass = nullptr; bool via_interface = false;         // named by the GLASS text only: never evaluated here
+	constexpr bool SKY = false; const SkyTable sky{}; float miss_w = 1.0f;     // ... and draws its NEE light among the sphere lights only (mirt_set_sky_sampling excludes this mode)
 #define SHADE_HIT_ORIGIN stream_O
 #define SHADE_HIT_ACC stream_acc
 #define SHADE_HIT_SEED stream_seed
 #include "shade_hit_body.inc"
-	(void)via_interface;
+	(void)via_interface; (void)miss_w; (void)sky;
 	if (!terminated) h.thr = thr;                                            // the survivor's throughput
 }
 constexpr uint32_t kStreamPlanes = 13;          // p, dir, throughput, radiance, pixelID
@@ -1924,6 +2075,22 @@ __global__ __launch_bounds__(kBlock) void k_debug_math(int fn, uint32_t n, const
 			out[i] = d.x; out[n + i] = d.y; out[2 * n + i] = d.z; out[3 * n + i] = e.x; out[4 * n + i] = e.y; out[5 * n + i] = e.z;
 		} break;
 		default: break;
+		}
+	}
+}
+// mirt_debug_math fn 12 and 13: the two functions of the context's sky table (mirt_set_sky_sampling), which k_debug_math has no argument for.
+//   12  sky_sample: in u0, u1 -> out dir(3), q, row, column (the last two as floats: exact below 2^24)
+//   13  sky_pdf:    in dir(3) -> out p~, row, column
+__global__ __launch_bounds__(kBlock) void k_debug_sky(int fn, uint32_t n, const float* in, float* out, SceneDev sc, SkyTable sky) {
+	for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+		uint32_t row, col;
+		if (fn == 12) {
+			float q;
+			const f3 d = sky_sample(sky, in[i], in[n + i], q, row, col);
+			out[i] = d.x; out[n + i] = d.y; out[2 * n + i] = d.z; out[3 * n + i] = q; out[4 * n + i] = static_cast<float>(row); out[5 * n + i] = static_cast<float>(col);
+		} else {
+			out[i] = sky_pdf(sc, sky, in[i], in[n + i], in[2 * n + i], row, col);
+			out[n + i] = static_cast<float>(row); out[2 * n + i] = static_cast<float>(col);
 		}
 	}
 }

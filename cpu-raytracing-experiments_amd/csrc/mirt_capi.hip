@@ -62,6 +62,7 @@ struct PipeSlot {
 	DeviceBuffer counts;             // ray queue counters, work counters and fat-ray counts of one batch: addressed through BatchCounters only
 	DeviceBuffer contrib;            // this batch's path radiances, [tile][slot][256][rgb] (kernels.hpp contrib_index)
 	DeviceBuffer fat;                // fat-ray index lists: [closest kFatCapacity][shadow kFatCapacity]
+	DeviceBuffer sky_w;              // mirt_set_sky_sampling(1) only: StreamBuf::w of the two ray streams, one 4-byte plane each
 	hipEvent_t batch_done = nullptr; // recorded on `stream` after the batch's last kernel
 	hipEvent_t merged = nullptr;     // recorded on the main stream after the batch was merged (slot reusable)
 	hipEvent_t aov_done = nullptr;   // mirt_set_aov(1) only: recorded on `stream` after the batch's k_first_hit_aov (created by the first such batch)
@@ -73,7 +74,7 @@ struct PipeSlot {
 	HitRec* hit = nullptr;           // RayStream<>::Hit: one 8-B {tfar, primID} record per ray (two planes' worth of the arena)
 	// Buffers, events and stream.  The caller has synchronised every stream.
 	void release() {
-		arena.release(); counts.release(); contrib.release(); fat.release();
+		arena.release(); counts.release(); contrib.release(); fat.release(); sky_w.release();
 		for (hipEvent_t* e : { &batch_done, &merged, &aov_done }) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
 		if (stream) (void)hipStreamDestroy(stream);
 		stream = nullptr;
@@ -101,6 +102,10 @@ struct mirt_ctx {
 	uint32_t transmission = 0;       // mirt_set_transmission: 1 = a transmissive material takes the dielectric interface (the GLASS instantiations of k_shade)
 	std::vector<float4> glass_host;  // the scene's {transmission.rgb, 1 + IOR_minus_one} per material, as uploaded: what the switch validates and looks for glass in
 	bool scene_has_glass = false;    // some material of the scene has max(transmission) > 0: only then does the switch change the kernels launched
+	uint32_t sky_sampling = 0;       // mirt_set_sky_sampling: 1 = the environment map is one more NEE light (the SKY instantiations of k_shade, while sky_active())
+	DeviceBuffer sky_table;          // its sampling table (kernels.hpp SkyTable), built by build_sky_table beside `hdri`; held only while the switch is on and a scene is set
+	SkyTable sky{};                  // ... as the kernels see it (t = nullptr: none)
+	float sky_total = 0.0f;          // the table's last marginal running sum; 0 (a black map, no ambient light): the switch changes no launch
 	std::vector<float> gloss_decay;  // gloss_decay_table (Renderer.hpp:212) by bounce, read at launch (mirt_set_gloss_decay); missing entries are 0
 	uint32_t light_ris = 0;          // mirt_set_light_ris: candidates per NEE light pick; 0 = the uniform draw, the kernels without the candidate loop
 	uint32_t stream_order = 0;       // mirt_set_stream_order: 1 = a batch is one k_tile_stream launch (the reference's stream slots and scalar tail, brute force)
@@ -325,7 +330,8 @@ int ensure_streams(mirt_ctx* c) {
 	const uint32_t nb = c->policy.max_bounces;
 	const uint32_t want = wanted_slots(c);
 	const size_t acc_bytes = static_cast<size_t>(c->n_tiles) * batch_limit(c) * 3 * kTileSize * sizeof(float);     // contribution buffer: [tile][slot][256][rgb]
-	if (cap == c->capacity && nb == c->arena_bounces && c->slots.size() == want && c->slots[0].contrib.bytes >= acc_bytes) return MIRT_OK;
+	if (cap == c->capacity && nb == c->arena_bounces && c->slots.size() == want && c->slots[0].contrib.bytes >= acc_bytes &&
+	    (c->slots[0].sky_w.ptr != nullptr) == (c->sky_sampling != 0)) return MIRT_OK;
 	HIP_TRY(c, sync_all(c));
 	c->aov_prev = nullptr;                                                   // (every batch has finished; the event's slot may go away below)
 	while (c->slots.size() > want) { c->slots.back().release(); c->slots.pop_back(); }
@@ -345,12 +351,14 @@ int ensure_streams(mirt_ctx* c) {
 		if (e == hipSuccess) { e = sl.counts.ensure(BatchCounters::words(nb) * sizeof(uint32_t)); what = "queue counters"; }
 		if (e == hipSuccess) { e = sl.fat.ensure(2u * kFatCapacity * sizeof(uint32_t)); what = "fat-ray lists"; }
 		if (e == hipSuccess) { e = sl.contrib.ensure(acc_bytes); what = "contribution buffer"; }
+		if (e == hipSuccess && c->sky_sampling) { e = sl.sky_w.ensure(2 * plane_bytes); what = "miss-weight planes"; }
+		if (!c->sky_sampling) sl.sky_w.release();
 		if (e != hipSuccess) {
 			// not enough device memory after all (someone else took it meanwhile — another context or process planning against the same
 			// free memory): halve the automatic batch and plan again
 			(void)hipGetLastError();
 			if (e == hipErrorOutOfMemory && !c->policy.max_batch && batch_limit(c) > batch_floor(c)) {
-				for (PipeSlot& other : c->slots) { other.arena.release(); other.contrib.release(); }
+				for (PipeSlot& other : c->slots) { other.arena.release(); other.contrib.release(); other.sky_w.release(); }
 				c->capacity = 0;
 				c->batch_mem_cap = std::max(batch_limit(c) / 2, batch_floor(c));
 				return ensure_streams(c);
@@ -362,6 +370,7 @@ int ensure_streams(mirt_ctx* c) {
 		for (int b = 0; b < 2; b++) {
 			StreamBuf& s = sl.stream_buf[b];
 			s.a = (float4*)take(4); s.b = (float4*)take(4); s.c = (float2*)take(2);
+			s.w = sl.sky_w.ptr ? reinterpret_cast<float*>(sl.sky_w.as<char>() + b * plane_bytes) : nullptr;
 		}
 		sl.hit = (HitRec*)take(2);                                         // 8 B per ray
 		ShadowBuf& h = sl.shadow_buf;
@@ -473,6 +482,9 @@ bool lens_on(const mirt_ctx* c) { return c->lens.aperture > 0.0f; }
 TileMap tile_map(const mirt_ctx* c) { return TileMap{ c->first_tile, c->run_tiles, c->stride_tiles, c->h_tiles, c->width }; }
 void set_tile_map(mirt_ctx* c, const TileMap& m, uint32_t n_tiles) { c->first_tile = m.first_tile; c->run_tiles = m.run_tiles; c->stride_tiles = m.stride_tiles; c->n_tiles = n_tiles; }
 
+// mirt_set_sky_sampling changes the kernels launched only where its light can be drawn and can carry something.
+bool sky_active(const mirt_ctx* c) { return c->sky_sampling && c->sky.t && c->sky_total > 0.0f && c->policy.mis && c->scene.has_ambient && !c->stream_order; }
+
 FrameParams frame_params(const mirt_ctx* c, uint32_t acc_base, uint32_t batch_n) {
 	FrameParams fp{};
 	const TileMap m = tile_map(c);
@@ -488,7 +500,7 @@ FrameParams frame_params(const mirt_ctx* c, uint32_t acc_base, uint32_t batch_n)
 	fp.max_bounces = c->policy.max_bounces;
 	fp.buckets = c->policy.buckets;
 	fp.n_lights = c->scene.n_lights;
-	fp.mis = (c->policy.mis && c->scene.n_lights > 0) ? 1u : 0u;       // Q12 guard
+	fp.mis = (c->policy.mis && (c->scene.n_lights > 0 || sky_active(c))) ? 1u : 0u;       // Q12 guard (mirt_set_sky_sampling: the sky counts as a light)
 	fp.first_groups = 1;
 	fp.inv_n_pix = fp.n_pix ? 1.0f / static_cast<float>(fp.n_pix) : 0.0f;
 	fp.inv_h_tiles = fp.h_tiles ? 1.0f / static_cast<float>(fp.h_tiles) : 0.0f;
@@ -558,6 +570,20 @@ auto shade_kernel(bool first, bool ggx, bool lens, bool sparse, bool ris, bool g
 		    { k_shade<false, true, false, false, true>, k_shade<true, true, false, false, true>, k_shade<true, true, true, false, true> } },
 		  { { nullptr, k_shade<true, false, false, true, true>, k_shade<true, false, true, true, true> }, { nullptr, k_shade<true, true, false, true, true>, k_shade<true, true, true, true, true> } } } };
 	return table[ris][first && sparse][ggx][first ? 1 + lens : 0];
+}
+// sky = mirt_set_sky_sampling while sky_active(): the same table once more, over the SKY instantiations (named after every older one, above).
+template <bool RIS, bool GLASS>
+auto shade_kernel_sky_of(bool first, bool ggx, bool lens, bool sparse) {
+	static const decltype(&k_shade<false, false>) table[2][2][3] = {       // [sparse][ggx][first ? 1 + lens : 0]
+		{ { k_shade<false, false, false, false, RIS, GLASS, true>, k_shade<true, false, false, false, RIS, GLASS, true>, k_shade<true, false, true, false, RIS, GLASS, true> },
+		  { k_shade<false, true, false, false, RIS, GLASS, true>, k_shade<true, true, false, false, RIS, GLASS, true>, k_shade<true, true, true, false, RIS, GLASS, true> } },
+		{ { nullptr, k_shade<true, false, false, true, RIS, GLASS, true>, k_shade<true, false, true, true, RIS, GLASS, true> },
+		  { nullptr, k_shade<true, true, false, true, RIS, GLASS, true>, k_shade<true, true, true, true, RIS, GLASS, true> } } };
+	return table[first && sparse][ggx][first ? 1 + lens : 0];
+}
+auto shade_kernel_sky(bool first, bool ggx, bool lens, bool sparse, bool ris, bool glass) {
+	return ris ? (glass ? shade_kernel_sky_of<true, true>(first, ggx, lens, sparse) : shade_kernel_sky_of<true, false>(first, ggx, lens, sparse))
+	           : (glass ? shade_kernel_sky_of<false, true>(first, ggx, lens, sparse) : shade_kernel_sky_of<false, false>(first, ggx, lens, sparse));
 }
 auto first_hit_aov_kernel(bool lens, bool sparse) {
 	static const decltype(&k_first_hit_aov<false>) table[2][2] = { { k_first_hit_aov<false>, k_first_hit_aov<true> }, { k_first_hit_aov<false, true>, k_first_hit_aov<true, true> } };   // [sparse][lens]
@@ -763,8 +789,10 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			  const float decay = bounce < c->gloss_decay.size() ? c->gloss_decay[bounce] : 0.0f;
 			  // mirt_set_light_ris: the candidate loop is worth running only where NEE runs
 			  const uint32_t ris = fp.mis ? c->light_ris : 0u;
-			  hipLaunchKernelGGL(shade_kernel(bounce == 0, c->policy.brdf != 0, lens, sparse, ris != 0, c->transmission && c->scene_has_glass), dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
-			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, ris, tile_frozen); }
+			  const bool glass = c->transmission && c->scene_has_glass, sky = sky_active(c);
+			  const auto shade = sky ? shade_kernel_sky(bounce == 0, c->policy.brdf != 0, lens, sparse, ris != 0, glass) : shade_kernel(bounce == 0, c->policy.brdf != 0, lens, sparse, ris != 0, glass);
+			  hipLaunchKernelGGL(shade, dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
+			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, ris, tile_frozen, sky ? c->sky : SkyTable{}); }
 		}
 	}
 	HIP_TRY(c, hipGetLastError());
@@ -920,6 +948,45 @@ bool has_glass(const std::vector<float4>& gls) {
 	for (const float4& g : gls) if (g.x > 0.0f || g.y > 0.0f || g.z > 0.0f) return true;
 	return false;
 }
+
+// mirt_set_sky_sampling(1) asks this of the environment map (binary32, the kernels' own products): every texel that owns a cell has a finite
+// importance max(t.rgb x ambient) >= 0, and the importances' sum stays inside binary32.  With the switch off nothing is asked, as ever.
+int check_sky_texels(mirt_ctx* c, const float4* texels, uint32_t w, uint32_t h, const float amb[3]) {
+	const uint32_t cols = std::max(w, 2u) - 1u, rows = std::max(h, 2u) - 1u;
+	const double pi = 3.14159265358979323846;
+	double sum = 0.0;
+	for (uint32_t r = 0; r < rows; r++) {
+		const double omega = (2.0 * pi / cols) * (std::cos(pi * r / rows) - std::cos(pi * (r + 1) / rows));
+		for (uint32_t x = 0; x < cols; x++) {
+			const float4 t = texels[static_cast<size_t>(r) * w + x];
+			const float p[3] = { t.x * amb[0], t.y * amb[1], t.z * amb[2] };
+			const float m = std::max(std::max(p[0], p[1]), p[2]);
+			if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2])) || m < 0.0f)
+				return fail(c, MIRT_ERR_ARG, "environment map texel (row %u, column %u): importance max(rgb x ambient_color) is negative or not finite (mirt_set_sky_sampling is on)", r, x);
+			sum += static_cast<double>(m) * omega;
+		}
+	}
+	if (!(sum < 0.5 * static_cast<double>(MIRT_FLT_MAX))) return fail(c, MIRT_ERR_ARG, "environment map: the importances sum to %g, beyond binary32 (mirt_set_sky_sampling is on)", sum);
+	return MIRT_OK;
+}
+// The sampling table of the scene's environment map, built on the device from c->hdri (kernels.hpp k_sky_importance, k_sky_scan) on the main
+// stream, which is synchronised before the total is read.  The caller has validated the texels and no batch is in flight.
+int build_sky_table(mirt_ctx* c) {
+	const SceneDev& s = c->scene;
+	const uint32_t cols = static_cast<uint32_t>(std::max(s.hdri_w, 2) - 1), rows = static_cast<uint32_t>(std::max(s.hdri_h, 2) - 1);
+	HIP_TRY(c, c->sky_table.ensure(sky_table_floats(rows, cols) * sizeof(float)));
+	float* t = c->sky_table.as<float>();
+	hipLaunchKernelGGL(k_sky_importance, dim3(rows), dim3(kSkyBlock), 0, c->stream, s.hdri, s.hdri_w, s.ambient[0], s.ambient[1], s.ambient[2], rows, cols, t);
+	hipLaunchKernelGGL(k_sky_scan, dim3(rows), dim3(kSkyBlock), 0, c->stream, rows, cols, t);
+	HIP_TRY(c, hipGetLastError());
+	float total = 0.0f;
+	HIP_TRY(c, hipMemcpyAsync(&total, t + rows - 1, sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	c->sky = SkyTable{ t, rows, cols };
+	c->sky_total = total;
+	return MIRT_OK;
+}
+void drop_sky_table(mirt_ctx* c) { c->sky_table.release(); c->sky = SkyTable{}; c->sky_total = 0.0f; }
 
 // The records the kernels walk for this scene, uploaded (a host-built tree) or built in place (the GPU LBVH over c->spheres, uploaded by the caller).
 struct SceneRecords {
@@ -1084,7 +1151,7 @@ int mirt_destroy(mirt_ctx* c) {
 	c->slots.clear();
 	for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
 	DeviceBuffer* bufs[] = { &c->recs, &c->recs_wide, &c->spheres, &c->prim_mat, &c->light_sphere, &c->light_emit, &c->mat_albedo, &c->mat_emission,
-	                         &c->mat_ggx, &c->mat_glass, &c->hdri, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
+	                         &c->mat_ggx, &c->mat_glass, &c->hdri, &c->sky_table, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
 	                         &c->cand, &c->cand_listed, &c->cand_words, &c->noise_rec, &c->noise_hist, &c->noise_above,
 	                         &c->tile_frozen, &c->active_list, &c->tile_counts };
 	for (DeviceBuffer* b : bufs) b->release();
@@ -1108,6 +1175,7 @@ int mirt_set_scene(mirt_ctx* c, const mirt_sphere* geometry, const mirt_sphere* 
 	HIP_TRY(c, hipSetDevice(c->device));
 	const SceneTables t = flatten_tables(a);     // host copies of tables and records: alive until the stream has been synchronised
 	if (c->transmission && (r = check_glass(c, t.gls))) return r;
+	if (c->sky_sampling && (r = check_sky_texels(c, t.sky.data(), hdri_w, hdri_h, ambient_color))) return r;
 	SceneRecords tree;
 	if ((r = upload(c, c->spheres, t.sph)) || (r = build_scene_records(c, a, t.sph, tree)) || (r = upload(c, c->prim_mat, t.pm)) ||
 	    (r = upload(c, c->light_sphere, t.lsp)) || (r = upload(c, c->light_emit, t.lem)) || (r = upload(c, c->mat_albedo, t.alb)) ||
@@ -1116,6 +1184,7 @@ int mirt_set_scene(mirt_ctx* c, const mirt_sphere* geometry, const mirt_sphere* 
 	c->cand_valid = false;                                                             // spheres or tree changed (a node-only update included)
 	commit_scene(c, a, tree);
 	c->glass_host = t.gls; c->scene_has_glass = has_glass(t.gls);
+	if (c->sky_sampling) { HIP_TRY(c, sync_all(c)); if ((r = build_sky_table(c))) return r; }      // (a batch in flight on another stream may read the old table)
 	if ((r = plan_trace_lds(c))) return r;
 	c->have_scene = true;
 	return MIRT_OK;
@@ -1208,6 +1277,7 @@ int mirt_set_stream_order(mirt_ctx* c, uint32_t exact) {
 	if (exact && c->n_frozen) return fail(c, MIRT_ERR_STATE, "exact stream order runs a tile's whole bounce loop in one launch and has no form that skips frozen tiles (%u are frozen): mirt_reset first", c->n_frozen);
 	if (exact && c->light_ris) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which draws its NEE light uniformly (Renderer.hpp:259): call mirt_set_light_ris(ctx, 0) first");
 	if (exact && c->transmission) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, no closure of which reads transmission: call mirt_set_transmission(ctx, 0) first");
+	if (exact && c->sky_sampling) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which draws its NEE light among the sphere lights only: call mirt_set_sky_sampling(ctx, 0) first");
 	if (exact && c->aov_on) return fail(c, MIRT_ERR_STATE, "exact stream order keeps no hit records (k_tile_stream runs a tile's whole bounce loop in one launch), so it cannot feed the first-hit AOVs: call mirt_set_aov(ctx, 0) first");
 	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render in the mode they were issued under
 	c->stream_order = exact;
@@ -1234,6 +1304,30 @@ int mirt_set_transmission(mirt_ctx* c, uint32_t on) {
 	c->transmission = on;                                                           // another estimand: the caller resets; the camera-ray lists do not depend on it
 	return MIRT_OK;
 }
+// ---- the environment map as one more light of next event estimation ------------------------------
+int mirt_set_sky_sampling(mirt_ctx* c, uint32_t on) {
+	if (!c) return MIRT_ERR_ARG;
+	if (on > 1) return fail(c, MIRT_ERR_ARG, "sky sampling %u is neither 0 (off: the sky is met by extension rays only) nor 1 (on: it is one more light of next event estimation)", on);
+	if (on && c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which draws its NEE light among the sphere lights only: call mirt_set_stream_order(ctx, 0) first");
+	if (on == c->sky_sampling) return MIRT_OK;
+	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render under the setting they were issued under
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, sync_all(c));                                                        // batches in flight read the table and the planes
+	if (on && c->have_scene) {
+		const SceneDev& s = c->scene;
+		std::vector<float4> texels(static_cast<size_t>(s.hdri_w) * s.hdri_h);
+		HIP_TRY(c, hipMemcpy(texels.data(), s.hdri, texels.size() * sizeof(float4), hipMemcpyDeviceToHost));
+		int r = check_sky_texels(c, texels.data(), static_cast<uint32_t>(s.hdri_w), static_cast<uint32_t>(s.hdri_h), s.ambient);
+		if (r || (r = build_sky_table(c))) { drop_sky_table(c); return r; }       // the switch stays off
+	}
+	if (!on) {
+		drop_sky_table(c);
+		for (PipeSlot& sl : c->slots) { sl.sky_w.release(); sl.stream_buf[0].w = sl.stream_buf[1].w = nullptr; }
+	}
+	c->sky_sampling = on;                                                           // the same expectation: no reset; the camera-ray lists do not depend on it
+	return MIRT_OK;
+}
+int mirt_get_sky_sampling(const mirt_ctx* c, uint32_t* on) { if (!c || !on) return MIRT_ERR_ARG; *on = c->sky_sampling; return MIRT_OK; }
 int mirt_get_transmission(const mirt_ctx* c, uint32_t* on) { if (!c || !on) return MIRT_ERR_ARG; *on = c->transmission; return MIRT_OK; }
 int mirt_get_light_ris(const mirt_ctx* c, uint32_t* candidates) { if (!c || !candidates) return MIRT_ERR_ARG; *candidates = c->light_ris; return MIRT_OK; }
 int mirt_get_stream_order(const mirt_ctx* c, uint32_t* exact) { if (!c || !exact) return MIRT_ERR_ARG; *exact = c->stream_order; return MIRT_OK; }
@@ -1665,13 +1759,15 @@ int mirt_debug_trace_shadow(mirt_ctx* c, size_t n, const float* p_xyz, const flo
 
 int mirt_debug_math(mirt_ctx* c, int fn, size_t n, const float* in, float* out) {
 	if (!c) return MIRT_ERR_ARG;
-	static const int n_in[12] = { 1, 2, 1, 2, 2, 6, 8, 3, 10, 9, 1, 6 }, n_out[12] = { 2, 1, 1, 3, 3, 10, 5, 5, 3, 6, 1, 6 };
-	if (fn < 0 || fn > 11 || !in || !out || n == 0 || n >= (1u << 28)) return fail(c, MIRT_ERR_ARG, "bad arguments");
+	static const int n_in[14] = { 1, 2, 1, 2, 2, 6, 8, 3, 10, 9, 1, 6, 2, 3 }, n_out[14] = { 2, 1, 1, 3, 3, 10, 5, 5, 3, 6, 1, 6, 6, 3 };
+	if (fn < 0 || fn > 13 || !in || !out || n == 0 || n >= (1u << 28)) return fail(c, MIRT_ERR_ARG, "bad arguments");
 	HIP_TRY(c, hipSetDevice(c->device));
 	ScopedBuffer din, dout;
 	HIP_TRY(c, din.ensure(n * n_in[fn] * 4)); HIP_TRY(c, dout.ensure(n * n_out[fn] * 4));
 	HIP_TRY(c, hipMemcpy(din.ptr, in, n * n_in[fn] * 4, hipMemcpyHostToDevice));
-	hipLaunchKernelGGL(k_debug_math, dim3(grid_for(c, n)), dim3(kBlock), 0, c->stream, fn, static_cast<uint32_t>(n), din.as<float>(), dout.as<float>());
+	if (fn >= 12 && !(c->sky.t && c->sky_total > 0.0f)) return fail(c, MIRT_ERR_STATE, "debug_math fn %d reads the sky sampling table: mirt_set_sky_sampling(ctx, 1) over a scene whose table has a total above 0 first", fn);
+	if (fn >= 12) hipLaunchKernelGGL(k_debug_sky, dim3(grid_for(c, n)), dim3(kBlock), 0, c->stream, fn, static_cast<uint32_t>(n), din.as<float>(), dout.as<float>(), c->scene, c->sky);
+	else hipLaunchKernelGGL(k_debug_math, dim3(grid_for(c, n)), dim3(kBlock), 0, c->stream, fn, static_cast<uint32_t>(n), din.as<float>(), dout.as<float>());
 	hipError_t e = hipGetLastError();
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
 	if (e == hipSuccess) e = hipMemcpy(out, dout.ptr, n * n_out[fn] * 4, hipMemcpyDeviceToHost);
@@ -1735,6 +1831,19 @@ int mirt_debug_tree(mirt_ctx* c, void* dst, size_t capacity_bytes, uint32_t info
 	HIP_TRY(c, hipSetDevice(c->device));
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	HIP_TRY(c, hipMemcpy(dst, s.recs, bytes, hipMemcpyDeviceToHost));             // the device copy the kernels walk, not SceneRecords' host vectors
+	return MIRT_OK;
+}
+int mirt_debug_sky_table(mirt_ctx* c, float* dst, size_t capacity, uint32_t info[4]) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!info) return fail(c, MIRT_ERR_ARG, "debug_sky_table: info is NULL");
+	if (!c->sky.t) return fail(c, MIRT_ERR_STATE, "there is no sky sampling table: mirt_set_sky_sampling(ctx, 1) and mirt_set_scene first");
+	const size_t floats = sky_table_floats(c->sky.rows, c->sky.cols);
+	info[0] = c->sky.rows; info[1] = c->sky.cols; std::memcpy(&info[2], &c->sky_total, 4); info[3] = static_cast<uint32_t>(floats);
+	if (!dst) return MIRT_OK;
+	if (capacity < floats) return fail(c, MIRT_ERR_ARG, "debug_sky_table: room for %zu floats, the table takes %zu", capacity, floats);
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	HIP_TRY(c, hipMemcpy(dst, c->sky.t, floats * sizeof(float), hipMemcpyDeviceToHost));
 	return MIRT_OK;
 }
 int mirt_debug_allow_half_boxes(mirt_ctx* c, int allow) { if (!c) return MIRT_ERR_ARG; c->allow_half = allow != 0; return MIRT_OK; }

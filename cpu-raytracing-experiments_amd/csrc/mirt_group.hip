@@ -221,6 +221,11 @@ int mirt_group_set_transmission(mirt_group* g, uint32_t on) {
 	FOR_MEMBERS_AND_FULL(g, "mirt_set_transmission", mirt_set_transmission(ctx, on));
 	return MIRT_OK;
 }
+int mirt_group_set_sky_sampling(mirt_group* g, uint32_t on) {
+	if (!g) return MIRT_ERR_ARG;
+	FOR_MEMBERS_AND_FULL(g, "mirt_set_sky_sampling", mirt_set_sky_sampling(ctx, on));       // every member builds its own table, word for word the same (a fixed summation order)
+	return MIRT_OK;
+}
 int mirt_group_pick_focus(mirt_group* g, uint32_t x, uint32_t y, float* distance, float* depth) {
 	if (!g) return MIRT_ERR_ARG;
 	mirt_ctx* ctx = g->members[0];                                                   // one ray: every member holds the whole scene

@@ -194,6 +194,9 @@ public:
 	// Transmissive materials (max(transmission) > 0) take a smooth dielectric interface of index 1 + IOR_minus_one (mirt.h, mirt_set_transmission); off by
 	// default, as in the reference, whose closures read neither field.  Another estimand: Reset() is the caller's to call.  Not in exact stream order.
 	void SetTransmission(bool on) { check(mirt_group_set_transmission(group_, on ? 1u : 0u), "mirt_group_set_transmission"); }
+	// The environment map as one more light of next event estimation (mirt.h, mirt_set_sky_sampling): off by default, as in the reference, where the
+	// sky is met by extension rays only.  Same expectation, so the accumulator is not reset.  Not in exact stream order.
+	void SetSkySampling(bool on) { check(mirt_group_set_sky_sampling(group_, on ? 1u : 0u), "mirt_group_set_sky_sampling"); }
 	// Renderer.hpp:73-434.  Asynchronous: Render() / counters() / the destructor wait for the GPUs; called once per frame the library
 	// still batches the frames between two Render()s that are due (mirt.h, mirt_accumulate_async).
 	void Accumulate(uint32_t n_calls = 1) { check(mirt_group_accumulate_async(group_, n_calls), "mirt_group_accumulate_async"); }

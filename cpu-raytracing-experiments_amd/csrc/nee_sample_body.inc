@@ -2,6 +2,31 @@
 // towards it would carry.  Included as statements by shade_hit_body.inc, once for the plain draw and once inside the RIS candidate loop, so both
 // run ONE text.  Reads selected, u0, u1 and everything shade_hit_body.inc has in scope at that point; a sample that survives every early-out
 // ends in NEE_ACCEPT(direction, distance, radiance), which the including scope defines; one that does not leaves nothing behind.
+// SKY (mirt_set_sky_sampling): light number n_lights is the environment map.  Ld is drawn from the table with density q; p~ = sky_pdf(Ld) is the
+// density both MIS weights are formed from (sky_eval's own cell arithmetic: in its edge bands it may name the neighbour of the cell that was
+// drawn).  Estimator: f L w(p~) / (sel q), with w the power heuristic of sel p~ against the closure's pdf — powerHeuristic_over_f gives w / (sel p~),
+// times p~ / q (1.0f exactly wherever the two cells agree).  L x f is sky_eval(Ld).rgb x (thr.r x f.r): Q10 carried over, the miss shader's
+// red-channel throughput on all three channels, so that the expectation is the plain path's.  One shadow ray, tfar = FLT_MAX.
+if (SKY && selected == static_cast<int32_t>(fp.n_lights)) {
+	do {
+		float sky_q; uint32_t srow, scol;
+		const f3 Ld = sky_sample(sky, u0, u1, sky_q, srow, scol);
+		const f3 Ll = to_local(T, Ld);
+		if (Ll.z < 0.0f) break;
+		float fx;
+		if (GGX) fx = ggx_eval(F0, alpha, Ll, Vl).x;
+		else fx = alb.x * (MIRT_INV_PI * max_sel(0.0f, Ll.z));
+		const f3 Le = sky_eval(sc, Ld.x, Ld.y, Ld.z);
+		const float k = thr.x * fx;
+		f3 rad{ Le.x * k, Le.y * k, Le.z * k };
+		const float sky_p = sky_pdf(sc, sky, Ld.x, Ld.y, Ld.z, srow, scol);
+		const float brdf_pdf = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, Ll.z);
+		const float w = powerHeuristic_over_f(light_selection_pdf * sky_p, brdf_pdf) * (sky_p / sky_q);
+		rad.x *= w; rad.y *= w; rad.z *= w;
+		if (max_sel(max_sel(rad.x, rad.y), rad.z) <= 0.0f) break;
+		NEE_ACCEPT(Ld, MIRT_FLT_MAX, rad)
+	} while (false);
+} else {
 const float4 lp = sc.light_sphere[selected];                    // scene.geometry[lighting_acceleration.prims[selected]]
 const float4 lem = sc.light_emit[selected];                     // its material's emission, and the prim id
 const int32_t light_primID = static_cast<int32_t>(__float_as_uint(lem.w));
@@ -36,3 +61,4 @@ do {
 	if (max_sel(max_sel(rad.x, rad.y), rad.z) <= 0.0f) break;
 	NEE_ACCEPT(Ld, ldist, rad)
 } while (false);
+}

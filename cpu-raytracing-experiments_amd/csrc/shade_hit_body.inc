@@ -6,7 +6,10 @@
 //   * stream_shade_hit (k_tile_stream, exact stream order) — held by tests/test_exact_stream_order.py.
 // The names are k_shade's.  The including scope provides
 //   constants           GGX; RIS (true: the NEE light is picked among ris_m candidates, a uint32_t the scope provides too); GLASS (true: a
-//                       transmissive material can take the dielectric interface below, mirt_set_transmission; false: none of that text is compiled in)
+//                       transmissive material can take the dielectric interface below, mirt_set_transmission; false: none of that text is compiled in);
+//                       SKY (true: the environment map is light number n_lights of next event estimation, mirt_set_sky_sampling — the scope then
+//                       provides sky (SkyTable) and a light_selection_pdf of 1 / (n_lights + 1), and gets miss_w (float) written with survive: the
+//                       MIS weight the miss shader gives thr.r x sky should ndir miss; false: none of that text is compiled in)
 //   read                sc, fp, s_albedo, s_emission (the material tables in LDS), bounce, gloss_decay, light_selection_pdf,
 //                       pdf_in (out->pdf of the bounce that sampled D, Q8), hrec (HitRec), prim (= hrec.prim), D (f3);
 //                       GLASS only: s_glass (LDS, {transmission.rgb, 1 + IOR_minus_one} per material) and after_interface (bool: D was sampled
@@ -79,7 +82,7 @@ if (fp.mis && !(GLASS && interface)) {                             // the interf
 		for (uint32_t cand = 0u; cand < ris_m; cand++) {
 			const float u0 = rand_unit_float(rng);
 			const float u1 = rand_unit_float(rng);
-			const int32_t selected = static_cast<int32_t>(rand_bounded_int(rng, fp.n_lights));
+			const int32_t selected = static_cast<int32_t>(rand_bounded_int(rng, SKY ? fp.n_lights + 1u : fp.n_lights));
 			const float r = rand_unit_float(rng);                      // Reservoir::Update's draw, taken for every candidate
 #define NEE_ACCEPT(Ld, ldist, rad) { const float w = max_sel(max_sel(rad.x, rad.y), rad.z); weight_sum += w; \
 			if (weight_sum == w || r < w / weight_sum) { w_sel = w; L = Ld; light_distance = ldist; srad = rad; } }   /* w > 0 here: the text left on w <= 0; the first positive candidate is taken whatever r (rand_unit_float reaches 1.0f) */
@@ -94,7 +97,7 @@ if (fp.mis && !(GLASS && interface)) {                             // the interf
 	} else {
 		const float u0 = rand_unit_float(rng);
 		const float u1 = rand_unit_float(rng);
-		const int32_t selected = static_cast<int32_t>(rand_bounded_int(rng, fp.n_lights));
+		const int32_t selected = static_cast<int32_t>(rand_bounded_int(rng, SKY ? fp.n_lights + 1u : fp.n_lights));
 #define NEE_ACCEPT(Ld, ldist, rad) has_shadow = true; L = Ld; light_distance = ldist; srad = rad;
 #include "nee_sample_body.inc"
 #undef NEE_ACCEPT
@@ -144,6 +147,14 @@ if (is_emissive) {
 		thr = { thr.x * inv, thr.y * inv, thr.z * inv };
 		ndir = to_world(T, sd);
 		if (GLASS && interface) { ndir = sd; via_interface = true; }
+		if (SKY) {
+			// What the miss shader may keep of thr.r x sky: the power heuristic of the closure's pdf of sd — the LOCAL one: next event estimation
+			// weighs against that, and Q8's world-z pdf_in would break the partition of unity — against sel x the sky's density of ndir.
+			// An interface is a delta closure (no light sample meets it): 1.  Closure<GGX>::pdf is 0: 0, as for the emitters such a ray hits.
+			if (GLASS && interface) miss_w = 1.0f;
+			else if (GGX) miss_w = 0.0f;
+			else { uint32_t prow, pcol; miss_w = powerHeuristic(MIRT_INV_PI * max_sel(0.0f, sd.z), light_selection_pdf * sky_pdf(sc, sky, ndir.x, ndir.y, ndir.z, prow, pcol)); }
+		}
 		survive = true;
 	}
 }

@@ -243,6 +243,45 @@ int mirt_get_light_ris(const mirt_ctx* ctx, uint32_t* candidates);
 int mirt_set_transmission(mirt_ctx* ctx, uint32_t on);
 int mirt_get_transmission(const mirt_ctx* ctx, uint32_t* on);
 
+/* ---- sampling the environment map: the sky as one more light of next event estimation ---------------------------------------------
+ * By default light from the environment map (hdri_rgba x ambient_color) reaches a surface only through an extension ray that misses every
+ * sphere (the miss shader, thr.r x sky: Q10); the reference does no better, and its author's note at Renderer.hpp:260 asks for better light
+ * sampling.  A map with a small bright sun then renders as fireflies.  on = 1, under ambient light and policy.mis = 1: THE SKY IS LIGHT NUMBER
+ * n_lights.  This is this library's own definition (float64 twin: tests/sky_definitions.py).  The expectation is the plain path's; only the
+ * variance changes, so the accumulator is NOT reset.
+ *   The table.  Sky::operator() scales by w - 1 and h - 1 and truncates, so the image is seen through cols = max(w - 1, 1) by rows =
+ *     max(h - 1, 1) CELLS; cell (r, c) is ex in [c, c + 1), ey in [r, r + 1) and shows texel (r, c); the last texel row and column have measure
+ *     zero, and a 1 x 1 map is one cell that covers every direction.  Importance I = max(t.r amb.r, t.g amb.g, t.b amb.b) x Omega(r) (light
+ *     RIS's weight rule times the cell's solid angle), Omega(r) = (2 pi / cols) (sin el(r) - sin el(r + 1)), el(r) = pi (0.5 - r / rows).  Stored:
+ *     running sums of the row sums, running sums within each row, and per cell the density p = I / (Omega x total) in 1 / sr.  Two HIP kernels
+ *     build it at mirt_set_scene while the switch is on, and when the switch is turned on over the current scene: a fixed summation order, no
+ *     floating-point atomics — two builds of one map give the same words, so the members of a group hold identical tables.  Freed by on = 0.
+ *   sky_sample(u0, u1) -> (dir, q): the row by inverting the marginal running sums at u0 x total, the column by inverting the row's at u1 x its
+ *     sum; the rescaled remainders place the sample in the cell uniformly in sin(elevation) and in azimuth, so q = p(cell) is constant over it;
+ *     dir is the inverse of the latitude-longitude map (u = 1/2 + atan2(z, x) / 2 pi, v = 1/2 - asin(y) / pi).  A row or cell whose running sum
+ *     does not rise (below 2^-24 of what precedes it) is never drawn.
+ *   sky_pdf(dir) -> p~: the density of the cell that the LOOKUP's own arithmetic (fast_atan2 / fast_asin, as the miss shader's) names for dir.
+ *     Within the approximations' error of a cell edge this may be the neighbour of the cell that was drawn.  That is intended: the estimator
+ *     divides by q, the density it sampled with, and WEIGHS by p~, a function of the direction alone that next event estimation and the miss
+ *     shader both evaluate — the two MIS weights of any direction add to one, and the estimator is unbiased whatever those bands do.
+ *   Next event estimation draws its light among n_lights + 1 (the same draws: u0, u1, the light, light RIS's r), light_selection_pdf is
+ *     1 / (n_lights + 1) wherever it is read (the emissive-hit weight included), and a scene without a sphere light runs it too.  The sky draw:
+ *     Ld, q = sky_sample(u0, u1); nothing below the shading horizon; radiance sky(Ld).rgb x (thr.r x f.r) — Q10 carried over — times
+ *     w(sel p~, closure pdf) / (sel q) with w the reference's power heuristic; one shadow ray with tfar = FLT_MAX.  Under light RIS a sky candidate
+ *     competes with the sphere candidates by its largest channel: the remedy for "a thousand lights and one sun".
+ *   The miss shader weighs thr.r x sky by the power heuristic of the closure's LOCAL pdf of the direction, (1/pi) max(0, local z), against
+ *     sel x p~: 0 under GGX (its pdf is 0, as for emitters), 1 after a dielectric interface and for camera rays.  The heuristic's 1e-6 floor
+ *     (Sampling.hpp:241-247) loses at most about (pi x 1e-3)^2 of the cosine-weighted energy, where both pdfs are tiny; it is not worked round.
+ * on = 0 (the default): the same device code as a context that never called this.  An all-zero table (a black map, ambient_color = 0),
+ * policy.mis = 0 or no ambient light: accepted, no effect, that same code.  Validation, with the switch on only: a texel that owns a cell and
+ * whose importance is negative or not finite (or a total beyond binary32) is MIRT_ERR_ARG — from mirt_set_scene, and from this call over the
+ * current scene (the switch then stays off).  on > 1: MIRT_ERR_ARG.  Exact stream order and the switch exclude each other: MIRT_ERR_STATE both
+ * ways.  Deferred mirt_accumulate_async calls are launched first, under the old setting.  rays and terminated do not change with the switch;
+ * shadow_rays does.  Combines with both closures, light RIS, transmission, the lens, AOVs, frozen tiles, the noise estimate and groups; the
+ * camera-ray candidate lists stay valid. */
+int mirt_set_sky_sampling(mirt_ctx* ctx, uint32_t on);
+int mirt_get_sky_sampling(const mirt_ctx* ctx, uint32_t* on);
+
 /* Renderer::Resize, Renderer.hpp:53-63: h_tiles = w/16, v_tiles = h/16 (truncating), allocates and zeroes
  * the accumulator, accumulations = 0.  Owns all tiles until mirt_set_tile_range says otherwise. */
 int mirt_resize(mirt_ctx* ctx, uint32_t width, uint32_t height);
@@ -457,6 +496,7 @@ int mirt_group_set_camera(mirt_group* group, const float pos[3], const float ori
 int mirt_group_set_lens(mirt_group* group, float aperture_radius, float focus_depth);   /* mirt_set_lens on every member */
 int mirt_group_set_light_ris(mirt_group* group, uint32_t candidates);             /* mirt_set_light_ris on every member */
 int mirt_group_set_transmission(mirt_group* group, uint32_t on);                   /* mirt_set_transmission on every member (and the gather context) */
+int mirt_group_set_sky_sampling(mirt_group* group, uint32_t on);                   /* mirt_set_sky_sampling on every member (and the gather context) */
 int mirt_group_pick_focus(mirt_group* group, uint32_t x, uint32_t y, float* distance, float* depth);   /* mirt_pick_focus on the first member */
 int mirt_group_set_policy(mirt_group* group, const mirt_policy* policy);
 int mirt_group_set_gloss_decay(mirt_group* group, const float* decay, uint32_t n);
@@ -525,6 +565,8 @@ int mirt_debug_trace_shadow(mirt_ctx* ctx, size_t n, const float* p_xyz, const f
  *    10 the sphere tests' sqrt (kernels.hpp sqrt_trav) — must equal IEEE sqrt for every input >= 0   in: x[n]  out: n
  *    11 dielectric_interface (device_math.hpp; mirt_set_transmission)   in: Vl.x[n], Vl.y[n], Vl.z[n], n_ior[n], entering[n] (!= 0), s1[n]
  *                                                           out: dir.x, dir.y, dir.z (local), F, reflected (0 / 1), tir (0 / 1)   (6n)
+ *    12 sky_sample (kernels.hpp; mirt_set_sky_sampling on over a scene, else MIRT_ERR_STATE)   in: u0[n], u1[n]   out: dir.x, dir.y, dir.z, q, row, column (6n; row and column as floats)
+ *    13 sky_pdf    (likewise)                                                                   in: dir.x[n], dir.y[n], dir.z[n]   out: p~, row, column (3n)
  *       (8, 9: the defined part of the reference's compiled-out GGX closure; not used by the path — DESIGN.md §7)
  */
 int mirt_debug_math(mirt_ctx* ctx, int fn, size_t n, const float* in, float* out);
@@ -538,6 +580,12 @@ int mirt_debug_info(mirt_ctx* ctx, uint32_t out[8]);
  * info[2] layout: 0 f32 child pairs, 1 binary16 child pairs, 2 binary16 records of up to four children, info[3] tree depth.
  * dst == NULL: only `info` is filled.  MIRT_ERR_ARG when capacity_bytes < info[0] * info[1]. */
 int mirt_debug_tree(mirt_ctx* ctx, void* dst, size_t capacity_bytes, uint32_t info[4]);
+/* Read-back of the sky sampling table (mirt_set_sky_sampling), copied from the device after the context's stream has been synchronised.
+ * info[0] rows, info[1] columns (of CELLS), info[2] the bits of the total (the last marginal running sum), info[3] floats in the table.
+ * Layout, in floats: marg[rows], rowsum[rows], tn[rows + 1] (1 - sin el(k)), ts[rows + 1] (1 + sin el(k)), cond[rows][cols], dens[rows][cols].
+ * dst == NULL: only `info` is filled.  `capacity` is in floats: MIRT_ERR_ARG when below info[3].  MIRT_ERR_STATE while there is no table
+ * (the switch is off, or no scene has been set). */
+int mirt_debug_sky_table(mirt_ctx* ctx, float* dst, size_t capacity, uint32_t info[4]);
 /* Length histogram of the per-pixel candidate lists of the current scene / camera / size (policy.trace_primary_rays = 0 path):
  * hist[n] = local pixels whose bundle of camera rays can hit n spheres for n = 0..7, hist[8] = 8 or more (lists hold up to 31), hist[9] = pixels without a list (traced normally). */
 int mirt_debug_primary_lists(mirt_ctx* ctx, uint32_t hist[10]);
