@@ -29,7 +29,8 @@ MIRT_NOT_CONVERGED = 2                            # mirt.h: accumulate_until gav
 NOISE_BINS = 2048                                 # mirt.h MIRT_NOISE_BINS
 AOV_DEPTH, AOV_NORMAL, AOV_ALBEDO = 0, 1, 2       # mirt.h MIRT_AOV_*
 AOV_PLANES = 7
-MAX_LIGHT_RIS = 32                                # mirt.h MIRT_MAX_LIGHT_RIS
+MAX_MATERIALS = 63                                # mirt.h MIRT_MAX_MATERIALS
+MAX_LIGHT_RIS = 32                              # mirt.h MIRT_MAX_LIGHT_RIS
 KERNEL_CLASSES = ("raygen", "trace", "shade", "shadow", "resolve")
 
 
@@ -113,6 +114,7 @@ def load_library():
         "mirt_set_light_ris": [P, u32], "mirt_get_light_ris": [P, C.POINTER(u32)],
         "mirt_set_transmission": [P, u32], "mirt_get_transmission": [P, C.POINTER(u32)],
         "mirt_set_sky_sampling": [P, u32], "mirt_get_sky_sampling": [P, C.POINTER(u32)],
+        "mirt_set_material_closures": [P, vp, u32], "mirt_get_material_closures": [P, vp, u32, C.POINTER(u32), C.POINTER(u32)],
         "mirt_resize": [P, u32, u32],
         "mirt_set_tile_range": [P, u32, u32], "mirt_set_tile_rows": [P, u32, u32],
         "mirt_reset": [P],
@@ -169,6 +171,7 @@ def load_library():
         "mirt_group_set_gloss_decay": [G, vp, u32],
         "mirt_group_set_stream_order": [G, u32],
         "mirt_group_set_light_ris": [G, u32], "mirt_group_set_transmission": [G, u32], "mirt_group_set_sky_sampling": [G, u32],
+        "mirt_group_set_material_closures": [G, vp, u32],
         "mirt_group_resize": [G, u32, u32],
         "mirt_group_reset": [G],
         "mirt_group_accumulate": [G, u32],
@@ -255,6 +258,17 @@ def _lens_arguments(camera: Camera, aperture_radius, focus_depth):
     return float(np.float32(a)), float(np.float32(d))
 
 
+def _closure_table(closures) -> np.ndarray:
+    """The table mirt_set_material_closures takes, validated before any call into the library: at most MAX_MATERIALS entries, each 0 or 1."""
+    t = [] if closures is None else list(closures)
+    if len(t) > MAX_MATERIALS:
+        raise ValueError(f"material_closures holds {len(t)} entries; a scene has at most {MAX_MATERIALS} materials")
+    for m, v in enumerate(t):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v not in (0, 1):
+            raise ValueError(f"material_closures[{m}] = {v!r} is neither 0 (Lambertian) nor 1 (GGX)")
+    return np.ascontiguousarray(t, dtype=np.uint8)
+
+
 def noise_quantile(hist, q: float):
     """mirt_noise_quantile (host code, no GPU): the UPPER EDGE of the histogram bin that holds the q-quantile (q in (0, 1]) of the usable
     pixels — at most 12.5 % above the quantile itself.  None for an empty histogram."""
@@ -301,8 +315,10 @@ class _Binding:
         """mirt_<name> or mirt_group_<name> on this object's handle, checked."""
         return self._check(getattr(self._lib, self._prefix + name)(getattr(self, self._handle), *args))
 
-    def _configure(self, gloss_decay, exact_stream_order, aov, light_ris=0, transmission=False, sky_sampling=False):
+    def _configure(self, gloss_decay, exact_stream_order, aov, light_ris=0, transmission=False, sky_sampling=False, material_closures=None):
         """The end of both constructors, after the policy is set."""
+        if material_closures is not None:
+            self.set_material_closures(material_closures)
         if sky_sampling:
             self.set_sky_sampling(True)
         if transmission:
@@ -368,6 +384,21 @@ class _Binding:
         met by extension rays only, as in the reference.  The same expectation with another variance: the accumulator is NOT reset.  No effect
         without ambient light, with mis=False or over a black map.  Not in exact stream order.  (A group: on every member.)"""
         self._call("set_sky_sampling", int(bool(on)))
+
+    def set_material_closures(self, closures=None):
+        """closures[m] = 0 (Lambertian) or 1 (GGX) for material m, so that both kinds share a scene (mirt.h, mirt_set_material_closures); materials
+        beyond the list take the policy's brdf.  None or an empty sequence removes the table (the default).  While every material of the scene
+        ends up with one closure the kernels of that brdf run; otherwise the MIXED ones (material_closures() tells which).  Not in exact stream
+        order.  Another estimand, and the accumulator is NOT reset: call Reset().  (A group: on every member.)"""
+        t = _closure_table(closures)
+        self._call("set_material_closures", _ptr(t) if len(t) else None, len(t))
+
+    def _material_closures_of(self, ctx):
+        out = np.zeros(MAX_MATERIALS, dtype=np.uint8)
+        n, mixed = C.c_uint32(0), C.c_uint32(0)
+        if self._lib.mirt_get_material_closures(ctx, _ptr(out), len(out), C.byref(n), C.byref(mixed)) < 0:
+            raise MirtError("mirt_get_material_closures failed")
+        return [int(v) for v in out[: n.value]], bool(mixed.value)
 
     # -- scene hand-over (Application.cpp:230-234) -------------------------------------------------
     def _hand_over_scene(self, nodes=None):
@@ -568,7 +599,9 @@ class Renderer(_Binding):
                  use_bvh: bool = False, count_traffic: bool = False, profile: bool = False, max_batch: int = 0,
                  allow_half_boxes: bool = True, reference_tree: bool = False, streams: int = 0, gpu_build: bool = False, trace_primary_rays: bool = False,
                  brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False, light_ris: int = 0,
-                 transmission: bool = False, sky_sampling: bool = False):
+                 transmission: bool = False, sky_sampling: bool = False, material_closures=None):
+        if material_closures is not None:
+            _closure_table(material_closures)           # a bad table is refused before the library is loaded or a device touched
         self._lib = load_library()
         self._ctx = C.c_void_p()
         self._lens_follows_camera = bool(lens)          # lens=True: the scene camera's f_number / focus_distance / unit_mm drive a thin lens
@@ -582,7 +615,7 @@ class Renderer(_Binding):
                              int(brdf))
         self._call("set_policy", C.byref(self.policy))
         self._call("debug_allow_half_boxes", int(allow_half_boxes))
-        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission, sky_sampling)
+        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission, sky_sampling, material_closures)
 
     def load_tile_counts(self, counts):
         """After load_accumulator: per-tile counts (positive multiples of `buckets`, at most accumulations); tiles below it are frozen."""
@@ -609,6 +642,10 @@ class Renderer(_Binding):
         v = C.c_uint32(0)
         self._call("get_sky_sampling", C.byref(v))
         return bool(v.value)
+
+    def material_closures(self):
+        """(table, mixed): the table set_material_closures left, and whether the current scene's materials make the next launch a MIXED one."""
+        return self._material_closures_of(self._ctx)
 
     @property
     def stream_order(self) -> int:
@@ -758,7 +795,9 @@ class GroupRenderer(_Binding):
     def __init__(self, scene: Scene, devices=(0,), max_bounces: int = 16, buckets: int = 5, mis: bool = True, use_bvh: bool = True,
                  count_traffic: bool = False, max_batch: int = 0, streams: int = 0, reference_tree: bool = False, gpu_build: bool = False,
                  brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False, light_ris: int = 0,
-                 transmission: bool = False, sky_sampling: bool = False):
+                 transmission: bool = False, sky_sampling: bool = False, material_closures=None):
+        if material_closures is not None:
+            _closure_table(material_closures)           # a bad table is refused before the library is loaded or a device touched
         self._lib = load_library()
         self._g = C.c_void_p()
         self._lens_follows_camera = bool(lens)
@@ -772,7 +811,7 @@ class GroupRenderer(_Binding):
         self.policy = Policy(max_bounces, buckets, int(mis), int(use_bvh), int(count_traffic), 0, max_batch, int(reference_tree), int(streams), int(gpu_build), 0,
                              int(brdf))
         self._call("set_policy", C.byref(self.policy))
-        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission, sky_sampling)
+        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission, sky_sampling, material_closures)
 
     def light_ris(self) -> int:
         """The members' setting (they all hold the same: set_light_ris sets every one)."""
@@ -797,6 +836,12 @@ class GroupRenderer(_Binding):
         if self._lib.mirt_get_sky_sampling(ctx, C.byref(v)) < 0:
             raise MirtError("mirt_get_sky_sampling failed on member 0")
         return bool(v.value)
+
+    def material_closures(self):
+        """(table, mixed) of the members (they all hold the same: set_material_closures sets every one)."""
+        ctx = C.c_void_p()
+        self._call("member", 0, C.byref(ctx))
+        return self._material_closures_of(ctx)
 
     def UpdateScene(self):
         self._hand_over_scene()

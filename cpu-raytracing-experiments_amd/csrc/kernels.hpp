@@ -68,7 +68,7 @@ struct SceneDev {
 // instead of one dword per member.  40 B per ray.
 struct StreamBuf {
 	float4* a;                  // {p.xyz, bits of path}: path = (batch slot << FrameParams::pix_bits) | local pixel index (tile_local*256 + ID); stands in for pixelID + seed[]
-	                            // (k_shade<GLASS> also sets kViaInterface in this word; no other kernel reads it: k_trace takes p only, and a shadow record gets the bare id)
+	                            // (k_shade<GLASS> also sets kViaInterface in this word, k_shade<MIXED> kSampledGGX; no other kernel reads it: k_trace takes p only, and a shadow record gets the bare id)
 	float4* b;                  // {dir.xyz, throughput.r}
 	float2* c;                  // {throughput.g, throughput.b} — read by the hits only (the miss shader scales by throughput.r, Q10)
 	                            // (radiance has no plane: a path's running sum is its word of the contribution buffer, contrib_index)
@@ -878,6 +878,7 @@ MIRT_DI size_t contrib_index(uint32_t batch_n, uint32_t pix_bits, uint32_t path)
 // occ != nullptr (mirt_debug_trace_shadow): only the occlusion flag is stored.
 constexpr uint32_t kDestFull = 0x40000000u;
 constexpr uint32_t kDestPath = 0x3fffffffu;     // path ids use bits 0-29 (batch slot << pix_bits | pixel; capacity check in mirt_capi.hip)
+constexpr uint32_t kSampledGGX = 0x40000000u;   // k_shade<MIXED>, in a STREAM's path word only (kDestFull, the same bit, lives in shadow records only): the ray's direction was sampled by Closure<GGX>
 constexpr uint32_t kViaInterface = 0x80000000u; // k_shade<GLASS>, in a STREAM's path word (StreamBuf::a, never a shadow record's): the ray's direction was sampled by a dielectric interface
 struct ShadowSink {
 	float* contrib;             // the batch's contribution buffer
@@ -1511,11 +1512,18 @@ MIRT_DI uint32_t block_compact(bool flag, uint32_t value, uint32_t* scratch, uin
 // SKY (mirt_set_sky_sampling, launched only while the table's total is above 0, the scene has ambient light and MIS is on): the environment map is
 // light number n_lights of next event estimation, drawn from `sky` (sky_sample) with one shadow ray of tfar = FLT_MAX, and the miss shader weighs
 // thr.r x sky by the MIS weight phase 2 stored for the ray in StreamBuf::w (bounce 0: 1).  SKY = false names neither `sky` nor the plane.
-template <bool FIRST, bool GGX, bool LENS = false, bool SPARSE = false, bool RIS = false, bool GLASS = false, bool SKY = false>
+// MIXED (mirt_set_material_closures, launched only while the scene's materials do not all take one closure; GGX = false): a hit is shaded by the
+// closure of its material — bit `mat` of closure_mask (MIRT_MAX_MATERIALS is 63), a kernel argument, so it stays in a scalar register pair — in one
+// wave without sorting: a wave with hits of both kinds runs both branches.  Both tables are staged: s_albedo = sc.mat_albedo, s_ggx = mat_ggx.
+// Q8's pdf_in belongs to the closure that SAMPLED the ray, so "sampled by Closure<GGX>" travels as kSampledGGX in the stream's path word, as
+// kViaInterface does.  MIXED = false names neither the mask nor s_ggx, and is the text as it was.  The same launch bounds.
+template <bool FIRST, bool GGX, bool LENS = false, bool SPARSE = false, bool RIS = false, bool GLASS = false, bool SKY = false, bool MIXED = false>
 __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
                                                   Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
-                                                  const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens, uint32_t ris_m, const uint32_t* __restrict__ tile_frozen, SkyTable sky) {
+                                                  const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens, uint32_t ris_m, const uint32_t* __restrict__ tile_frozen, SkyTable sky,
+                                                  unsigned long long closure_mask) {
 	static_assert(!(LENS || SPARSE) || FIRST, "the lens and the frozen tiles concern bounce 0 only");
+	static_assert(!(MIXED && GGX), "MIXED takes the closure from the material: it is instantiated with GGX = false");
 	const QueueView qin = FIRST ? queue_identity(fp.n_pix * fp.batch_n) : queue_view(in_queue);
 	const uint32_t n = qin.pre[kSegs];
 	const uint32_t n_chunks = (fp.n_pix + kShadeBlock - 1u) / kShadeBlock;      // FIRST
@@ -1526,10 +1534,11 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 	__shared__ uint32_t hit_list[kShadeBlock];
 	__shared__ float4 s_albedo[MIRT_MAX_MATERIALS + 1], s_emission[MIRT_MAX_MATERIALS + 1];      // scene.material: 2 KB, read by every hit (GGX: s_albedo = {F0, roughness})
 	__shared__ float4 s_glass[GLASS ? MIRT_MAX_MATERIALS + 1 : 1];                             // GLASS only (no instruction of the others names it: they get no LDS for it)
+	__shared__ float4 s_ggx[MIXED ? MIRT_MAX_MATERIALS + 1 : 1];                               // MIXED only, likewise: {F0, roughness} beside s_albedo = {albedo}
 	uint32_t c_term = 0, c_drop = 0, parity = 0;
 	const uint32_t n_units = n_chunks * fp.first_groups;                       // FIRST: pieces of work = (chunk, group of accumulations)
 	if (FIRST ? blockIdx.x >= n_units : blockIdx.x * kShadeBlock >= n) return;
-	for (uint32_t m = threadIdx.x; m < sc.n_mat; m += kShadeBlock) { s_albedo[m] = GGX ? mat_ggx[m] : sc.mat_albedo[m]; s_emission[m] = sc.mat_emission[m]; if (GLASS) s_glass[m] = sc.mat_glass[m]; }
+	for (uint32_t m = threadIdx.x; m < sc.n_mat; m += kShadeBlock) { s_albedo[m] = GGX ? mat_ggx[m] : sc.mat_albedo[m]; s_emission[m] = sc.mat_emission[m]; if (GLASS) s_glass[m] = sc.mat_glass[m]; if (MIXED) s_ggx[m] = mat_ggx[m]; }
 	__syncthreads();            // the table is read by every wave in phase 2; k_shade<FIRST> reaches no other barrier before that (the early return above is block-uniform)
 
 	// !FIRST: this lane's ray of the stream for the block-iteration at hand, and its hit record: requested one iteration ahead, so that the
@@ -1604,7 +1613,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 							const float4 b = in.b[i];                                      // {dir, throughput.r}
 							const float thr_x = SKY ? b.w * in.w[i] : b.w;                 // SKY: the MIS weight of this direction against the sky's own sampling
 							const f3 env = sky_eval(sc, b.x, b.y, b.z);
-							float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, __float_as_uint(in.a[i].w) & (GLASS ? kDestPath : ~0u));
+							float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, __float_as_uint(in.a[i].w) & ((GLASS || MIXED) ? kDestPath : ~0u));
 							w[0] += thr_x * env.x; w[1] += thr_x * env.y; w[2] += thr_x * env.z;
 						}
 					}
@@ -1612,7 +1621,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 				} else if (last_bounce) {
 					c_drop++;                                                         // Q5: still alive after the last bounce -> never accumulated: the word goes back to +0
 					if (!FIRST) {                                                     // (FIRST: W0 is +0)
-						float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, __float_as_uint(in.a[i].w) & (GLASS ? kDestPath : ~0u));
+						float* w = contrib + contrib_index(fp.batch_n, fp.pix_bits, __float_as_uint(in.a[i].w) & ((GLASS || MIXED) ? kDestPath : ~0u));
 						w[0] = 0.0f; w[1] = 0.0f; w[2] = 0.0f;
 					}
 				} else is_hit = true;
@@ -1626,6 +1635,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 		// ---- phase 2, one lane per hit ----
 		bool survive = false, has_shadow = false, terminated = false, has_E = false;
 		bool via_interface = false;                                            // GLASS
+		bool sampled_ggx = false;                                              // MIXED
 		float miss_w = 1.0f;                                                   // SKY
 		uint32_t path = 0;
 		f3 P{0, 0, 0}, ndir{0, 0, 0}, L{0, 0, 0}, srad{0, 0, 0}, E{0, 0, 0};
@@ -1638,14 +1648,17 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 			f3 O_in{0, 0, 0};
 			float pdf_in = 0.0f;
 			bool after_interface = false;                                      // GLASS
+			bool after_ggx = GGX;                                              // MIXED: D was sampled by Closure<GGX> (kSampledGGX); otherwise every D was, or none
 			if (!FIRST) {                                                      // the ray's three records
 				const float4 a = in.a[i], b = in.b[i];
 				const float2 c = in.c[i];
 				O_in = { a.x, a.y, a.z }; path = __float_as_uint(a.w);
-				if (GLASS) { after_interface = (path & kViaInterface) != 0u; path &= kDestPath; }
+				if (MIXED) after_ggx = (path & kSampledGGX) != 0u;
+				if (GLASS) after_interface = (path & kViaInterface) != 0u;
+				if (GLASS || MIXED) path &= kDestPath;
 				D = { b.x, b.y, b.z };
 				thr = { b.w, c.x, c.y };
-				pdf_in = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, D.z);           // out->pdf of the bounce that sampled D (Q8), bit for bit; Closure<GGX>::pdf = 0
+				pdf_in = after_ggx ? 0.0f : MIRT_INV_PI * max_sel(0.0f, D.z);     // out->pdf of the bounce that sampled D (Q8), bit for bit; Closure<GGX>::pdf = 0
 			}
 			const HitRec hrec = FIRST ? HitRec{ my_tfar, my_prim } : hit_in[i];
 			const int32_t prim = hrec.prim;
@@ -1663,7 +1676,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 		// record pending sends E along (kDestFull); one without adds E to the path's word here.
 		const bool full = has_shadow & has_E;
 		if (survive) {
-			out.a[slot] = make_float4(P.x, P.y, P.z, __uint_as_float(GLASS && via_interface ? path | kViaInterface : path));
+			out.a[slot] = make_float4(P.x, P.y, P.z, __uint_as_float((GLASS && via_interface ? path | kViaInterface : path) | (MIXED && sampled_ggx ? kSampledGGX : 0u)));
 			out.b[slot] = make_float4(ndir.x, ndir.y, ndir.z, thr.x);
 			out.c[slot] = make_float2(thr.y, thr.z);
 			if (SKY) out.w[slot] = miss_w;
@@ -1751,12 +1764,14 @@ MIRT_DI void stream_shade_hit(const SceneDev& sc, const FrameParams& fp, const f
 	constexpr bool RIS = false; constexpr uint32_t ris_m = 0u;                 // exact stream order replays the reference: one uniform draw
 	constexpr bool GLASS = false, after_interface = false;                     // ... and no closure of the reference reads transmission (mirt_set_transmission excludes this mode)
 	const float4* const s_glass = nullptr; bool via_interface = false;         // named by the GLASS text only: never evaluated here
+	constexpr bool MIXED = false; constexpr unsigned long long closure_mask = 0ull;   // ... and takes every closure from policy.brdf (mirt_set_material_closures excludes this mode)
+	const float4* const s_ggx = nullptr; bool sampled_ggx = false;             // named by the MIXED text only: never evaluated here
 	constexpr bool SKY = false; const SkyTable sky{}; float miss_w = 1.0f;     // ... and draws its NEE light among the sphere lights only (mirt_set_sky_sampling excludes this mode)
 #define SHADE_HIT_ORIGIN stream_O
 #define SHADE_HIT_ACC stream_acc
 #define SHADE_HIT_SEED stream_seed
 #include "shade_hit_body.inc"
-	(void)via_interface; (void)miss_w; (void)sky;
+	(void)via_interface; (void)miss_w; (void)sky; (void)sampled_ggx; (void)s_ggx;
 	if (!terminated) h.thr = thr;                                            // the survivor's throughput
 }
 constexpr uint32_t kStreamPlanes = 13;          // p, dir, throughput, radiance, pixelID

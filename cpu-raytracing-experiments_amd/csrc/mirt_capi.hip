@@ -106,6 +106,12 @@ struct mirt_ctx {
 	DeviceBuffer sky_table;          // its sampling table (kernels.hpp SkyTable), built by build_sky_table beside `hdri`; held only while the switch is on and a scene is set
 	SkyTable sky{};                  // ... as the kernels see it (t = nullptr: none)
 	float sky_total = 0.0f;          // the table's last marginal running sum; 0 (a black map, no ambient light): the switch changes no launch
+	// mirt_set_material_closures: closure (0 Lambertian, 1 GGX) of material m; a material at or beyond its end takes policy.brdf.  Empty (the default):
+	// every launch is the one of a context without the call.  What a launch does with it is closure_plan()'s to say, and nobody else's.
+	std::vector<uint8_t> closures;
+	std::vector<float4> alb_host, ggx_host;   // the scene's {albedo} and {F0, roughness} rows as uploaded: what the merged colour table below is made from
+	DeviceBuffer mat_merged;         // MIXED only: per material the colour of its closure, for k_first_hit_aov; uploaded by the first launch that reads it after a change
+	bool mat_merged_valid = false;
 	std::vector<float> gloss_decay;  // gloss_decay_table (Renderer.hpp:212) by bounce, read at launch (mirt_set_gloss_decay); missing entries are 0
 	uint32_t light_ris = 0;          // mirt_set_light_ris: candidates per NEE light pick; 0 = the uniform draw, the kernels without the candidate loop
 	uint32_t stream_order = 0;       // mirt_set_stream_order: 1 = a batch is one k_tile_stream launch (the reference's stream slots and scalar tail, brute force)
@@ -485,6 +491,24 @@ void set_tile_map(mirt_ctx* c, const TileMap& m, uint32_t n_tiles) { c->first_ti
 // mirt_set_sky_sampling changes the kernels launched only where its light can be drawn and can carry something.
 bool sky_active(const mirt_ctx* c) { return c->sky_sampling && c->sky.t && c->sky_total > 0.0f && c->policy.mis && c->scene.has_ambient && !c->stream_order; }
 
+// The launch rule of mirt_set_material_closures.  The effective closure of material m is closures[m], or policy.brdf at and beyond the table's end.
+// If materials 0 .. n_mat - 1 of the scene all take closure k, the kernels of policy.brdf = k are launched (mixed = false, ggx = k): the same device
+// code, hence that policy's words.  Otherwise the MIXED instantiations run with `mask` (bit m = material m is GGX).  The material LIST decides, not
+// which materials the spheres use.  Exact stream order excludes a table (both setters), so k_tile_stream only ever sees policy.brdf.
+struct ClosurePlan { bool mixed, ggx; unsigned long long mask; };
+ClosurePlan closure_plan(const mirt_ctx* c) {
+	const bool policy_ggx = c->policy.brdf != 0;
+	if (c->closures.empty() || !c->have_scene) return ClosurePlan{ false, policy_ggx, 0ull };
+	unsigned long long mask = 0ull;
+	const uint32_t n_mat = c->scene.n_mat;                                    // 1 .. MIRT_MAX_MATERIALS (63): every bit index is below 64
+	for (uint32_t m = 0; m < n_mat; m++)
+		if (m < c->closures.size() ? c->closures[m] != 0 : policy_ggx) mask |= 1ull << m;
+	const unsigned long long all = (1ull << n_mat) - 1ull;
+	if (mask == 0ull) return ClosurePlan{ false, false, 0ull };
+	if (mask == all) return ClosurePlan{ false, true, 0ull };
+	return ClosurePlan{ true, false, mask };
+}
+
 FrameParams frame_params(const mirt_ctx* c, uint32_t acc_base, uint32_t batch_n) {
 	FrameParams fp{};
 	const TileMap m = tile_map(c);
@@ -585,6 +609,27 @@ auto shade_kernel_sky(bool first, bool ggx, bool lens, bool sparse, bool ris, bo
 	return ris ? (glass ? shade_kernel_sky_of<true, true>(first, ggx, lens, sparse) : shade_kernel_sky_of<true, false>(first, ggx, lens, sparse))
 	           : (glass ? shade_kernel_sky_of<false, true>(first, ggx, lens, sparse) : shade_kernel_sky_of<false, false>(first, ggx, lens, sparse));
 }
+// mixed = mirt_set_material_closures while closure_plan() says so: the MIXED instantiations (GGX = false), over the reachable forms — five of
+// [sparse][first ? 1 + lens : 0], times RIS, GLASS and SKY.  Named after every older instantiation, above, so that those keep their device code.
+template <bool RIS, bool GLASS, bool SKY>
+auto shade_kernel_mixed_of(bool first, bool lens, bool sparse) {
+	static const decltype(&k_shade<false, false>) table[2][3] = {          // [sparse][first ? 1 + lens : 0]
+		{ k_shade<false, false, false, false, RIS, GLASS, SKY, true>, k_shade<true, false, false, false, RIS, GLASS, SKY, true>, k_shade<true, false, true, false, RIS, GLASS, SKY, true> },
+		{ nullptr, k_shade<true, false, false, true, RIS, GLASS, SKY, true>, k_shade<true, false, true, true, RIS, GLASS, SKY, true> } };
+	return table[first && sparse][first ? 1 + lens : 0];
+}
+auto shade_kernel_mixed(bool first, bool lens, bool sparse, bool ris, bool glass, bool sky) {
+	switch ((ris ? 4 : 0) | (glass ? 2 : 0) | (sky ? 1 : 0)) {
+	case 0: return shade_kernel_mixed_of<false, false, false>(first, lens, sparse);
+	case 1: return shade_kernel_mixed_of<false, false, true>(first, lens, sparse);
+	case 2: return shade_kernel_mixed_of<false, true, false>(first, lens, sparse);
+	case 3: return shade_kernel_mixed_of<false, true, true>(first, lens, sparse);
+	case 4: return shade_kernel_mixed_of<true, false, false>(first, lens, sparse);
+	case 5: return shade_kernel_mixed_of<true, false, true>(first, lens, sparse);
+	case 6: return shade_kernel_mixed_of<true, true, false>(first, lens, sparse);
+	default: return shade_kernel_mixed_of<true, true, true>(first, lens, sparse);
+	}
+}
 auto first_hit_aov_kernel(bool lens, bool sparse) {
 	static const decltype(&k_first_hit_aov<false>) table[2][2] = { { k_first_hit_aov<false>, k_first_hit_aov<true> }, { k_first_hit_aov<false, true>, k_first_hit_aov<true, true> } };   // [sparse][lens]
 	return table[sparse][lens];
@@ -664,7 +709,17 @@ int launch_first_hit_aov(mirt_ctx* c, PipeSlot& sl, hipStream_t st, const SceneD
 	}
 	{ Bracket t(c, MIRT_K_RESOLVE, st);
 	  const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(fp.n_pix) + kBlock - 1) / kBlock, static_cast<uint64_t>(c->n_cu) * 64u));
-	  const float4* colour = c->policy.brdf ? c->mat_ggx.as<float4>() : c->scene.mat_albedo;
+	  // the closure colour of the first hit: albedo under Lambertian, F0 under GGX; MIXED: one merged table, per material the row of its closure
+	  const ClosurePlan plan = closure_plan(c);
+	  if (plan.mixed && !c->mat_merged_valid) {
+	    std::vector<float4> merged(c->scene.n_mat);
+	    for (uint32_t m = 0; m < c->scene.n_mat; m++) merged[m] = ((plan.mask >> m) & 1ull) ? c->ggx_host[m] : c->alb_host[m];
+	    HIP_TRY(c, sync_all(c));                                                  // (batches in flight on other streams may still read the old table)
+	    HIP_TRY(c, c->mat_merged.ensure(merged.size() * sizeof(float4)));
+	    HIP_TRY(c, hipMemcpy(c->mat_merged.ptr, merged.data(), merged.size() * sizeof(float4), hipMemcpyHostToDevice));
+	    c->mat_merged_valid = true;
+	  }
+	  const float4* colour = plan.mixed ? c->mat_merged.as<float4>() : plan.ggx ? c->mat_ggx.as<float4>() : c->scene.mat_albedo;
 	  hipLaunchKernelGGL(first_hit_aov_kernel(lens_on(c), c->n_frozen != 0), dim3(grid), dim3(kBlock), 0, st, sc, fp, sl.hit, colour, c->aov.as<float>(), c->lens, c->tile_frozen.as<uint32_t>()); }
 	if (pipelined) { HIP_TRY(c, hipEventRecord(sl.aov_done, st)); c->aov_prev = sl.aov_done; }
 	return MIRT_OK;
@@ -790,9 +845,12 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			  // mirt_set_light_ris: the candidate loop is worth running only where NEE runs
 			  const uint32_t ris = fp.mis ? c->light_ris : 0u;
 			  const bool glass = c->transmission && c->scene_has_glass, sky = sky_active(c);
-			  const auto shade = sky ? shade_kernel_sky(bounce == 0, c->policy.brdf != 0, lens, sparse, ris != 0, glass) : shade_kernel(bounce == 0, c->policy.brdf != 0, lens, sparse, ris != 0, glass);
+			  // mirt_set_material_closures: the kernels of the one closure every material takes, or the MIXED ones
+			  const ClosurePlan plan = closure_plan(c);
+			  const auto shade = plan.mixed ? shade_kernel_mixed(bounce == 0, lens, sparse, ris != 0, glass, sky)
+			                   : sky ? shade_kernel_sky(bounce == 0, plan.ggx, lens, sparse, ris != 0, glass) : shade_kernel(bounce == 0, plan.ggx, lens, sparse, ris != 0, glass);
 			  hipLaunchKernelGGL(shade, dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
-			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, ris, tile_frozen, sky ? c->sky : SkyTable{}); }
+			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, ris, tile_frozen, sky ? c->sky : SkyTable{}, plan.mask); }
 		}
 	}
 	HIP_TRY(c, hipGetLastError());
@@ -1151,7 +1209,7 @@ int mirt_destroy(mirt_ctx* c) {
 	c->slots.clear();
 	for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
 	DeviceBuffer* bufs[] = { &c->recs, &c->recs_wide, &c->spheres, &c->prim_mat, &c->light_sphere, &c->light_emit, &c->mat_albedo, &c->mat_emission,
-	                         &c->mat_ggx, &c->mat_glass, &c->hdri, &c->sky_table, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
+	                         &c->mat_ggx, &c->mat_glass, &c->mat_merged, &c->hdri, &c->sky_table, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
 	                         &c->cand, &c->cand_listed, &c->cand_words, &c->noise_rec, &c->noise_hist, &c->noise_above,
 	                         &c->tile_frozen, &c->active_list, &c->tile_counts };
 	for (DeviceBuffer* b : bufs) b->release();
@@ -1184,6 +1242,7 @@ int mirt_set_scene(mirt_ctx* c, const mirt_sphere* geometry, const mirt_sphere* 
 	c->cand_valid = false;                                                             // spheres or tree changed (a node-only update included)
 	commit_scene(c, a, tree);
 	c->glass_host = t.gls; c->scene_has_glass = has_glass(t.gls);
+	c->alb_host = t.alb; c->ggx_host = t.ggx; c->mat_merged_valid = false;
 	if (c->sky_sampling) { HIP_TRY(c, sync_all(c)); if ((r = build_sky_table(c))) return r; }      // (a batch in flight on another stream may read the old table)
 	if ((r = plan_trace_lds(c))) return r;
 	c->have_scene = true;
@@ -1253,6 +1312,7 @@ int mirt_set_policy(mirt_ctx* c, const mirt_policy* p) {
 	// what decides the tree the lists were collected from, or whether lists are used at all
 	if (p->use_bvh != c->policy.use_bvh || p->gpu_build != c->policy.gpu_build || p->reference_tree != c->policy.reference_tree || p->trace_primary_rays != c->policy.trace_primary_rays)
 		c->cand_valid = false;
+	if (p->brdf != c->policy.brdf) c->mat_merged_valid = false;                     // (the closure of the materials beyond the table's end)
 	c->policy = *p;
 	if (replan) c->planned_for = 0;
 	if (realloc_acc && c->n_tiles) { int r = alloc_accumulator(c); if (r) return r; }
@@ -1278,6 +1338,7 @@ int mirt_set_stream_order(mirt_ctx* c, uint32_t exact) {
 	if (exact && c->light_ris) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which draws its NEE light uniformly (Renderer.hpp:259): call mirt_set_light_ris(ctx, 0) first");
 	if (exact && c->transmission) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, no closure of which reads transmission: call mirt_set_transmission(ctx, 0) first");
 	if (exact && c->sky_sampling) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which draws its NEE light among the sphere lights only: call mirt_set_sky_sampling(ctx, 0) first");
+	if (exact && !c->closures.empty()) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, every closure of which is policy.brdf's (Renderer.hpp:70): call mirt_set_material_closures(ctx, NULL, 0) first");
 	if (exact && c->aov_on) return fail(c, MIRT_ERR_STATE, "exact stream order keeps no hit records (k_tile_stream runs a tile's whole bounce loop in one launch), so it cannot feed the first-hit AOVs: call mirt_set_aov(ctx, 0) first");
 	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render in the mode they were issued under
 	c->stream_order = exact;
@@ -1302,6 +1363,29 @@ int mirt_set_transmission(mirt_ctx* c, uint32_t on) {
 	if (on && c->have_scene) { const int r = check_glass(c, c->glass_host); if (r) return r; }
 	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render under the setting they were issued under
 	c->transmission = on;                                                           // another estimand: the caller resets; the camera-ray lists do not depend on it
+	return MIRT_OK;
+}
+// ---- per-material closures ---------------------------------------------------------------------
+int mirt_set_material_closures(mirt_ctx* c, const uint8_t* closure, uint32_t n) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!closure) n = 0;
+	if (n > MIRT_MAX_MATERIALS) return fail(c, MIRT_ERR_ARG, "material closures: %u entries (at most %u, MIRT_MAX_MATERIALS)", n, MIRT_MAX_MATERIALS);
+	for (uint32_t m = 0; m < n; m++)
+		if (closure[m] > 1) return fail(c, MIRT_ERR_ARG, "material closures: closure[%u] = %u is neither 0 (Lambertian) nor 1 (GGX)", m, closure[m]);
+	if (n && c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, every closure of which is policy.brdf's (Renderer.hpp:70): call mirt_set_stream_order(ctx, 0) first");
+	if (n == c->closures.size() && (n == 0 || std::memcmp(c->closures.data(), closure, n) == 0)) return MIRT_OK;
+	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render under the table they were issued under
+	c->closures.assign(closure, closure + n);                                       // another estimand: the caller resets; the camera-ray lists do not depend on it
+	c->mat_merged_valid = false;
+	return MIRT_OK;
+}
+int mirt_get_material_closures(const mirt_ctx* c, uint8_t* closure_out, uint32_t capacity, uint32_t* n, uint32_t* mixed) {
+	if (!c || !n || !mixed) return MIRT_ERR_ARG;
+	const uint32_t have = static_cast<uint32_t>(c->closures.size());
+	*n = have;
+	*mixed = closure_plan(c).mixed ? 1u : 0u;
+	if (have && (!closure_out || capacity < have)) return closure_out ? MIRT_ERR_ARG : MIRT_OK;    // closure_out = NULL: only the two counts are asked for
+	if (have) std::memcpy(closure_out, c->closures.data(), have);
 	return MIRT_OK;
 }
 // ---- the environment map as one more light of next event estimation ------------------------------

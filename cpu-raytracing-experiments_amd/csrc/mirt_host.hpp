@@ -197,6 +197,11 @@ public:
 	// The environment map as one more light of next event estimation (mirt.h, mirt_set_sky_sampling): off by default, as in the reference, where the
 	// sky is met by extension rays only.  Same expectation, so the accumulator is not reset.  Not in exact stream order.
 	void SetSkySampling(bool on) { check(mirt_group_set_sky_sampling(group_, on ? 1u : 0u), "mirt_group_set_sky_sampling"); }
+	// Per-material closures (mirt.h, mirt_set_material_closures): closure[m] = 0 (Lambertian) or 1 (GGX) for material m; an empty table (the default)
+	// leaves every material on policy.brdf, as do the materials beyond its end.  Another estimand: Reset() is the caller's to call.  Not in exact stream order.
+	void SetMaterialClosures(const std::vector<uint8_t>& closure) {
+		check(mirt_group_set_material_closures(group_, closure.data(), static_cast<uint32_t>(closure.size())), "mirt_group_set_material_closures");
+	}
 	// Renderer.hpp:73-434.  Asynchronous: Render() / counters() / the destructor wait for the GPUs; called once per frame the library
 	// still batches the frames between two Render()s that are due (mirt.h, mirt_accumulate_async).
 	void Accumulate(uint32_t n_calls = 1) { check(mirt_group_accumulate_async(group_, n_calls), "mirt_group_accumulate_async"); }

@@ -14,13 +14,13 @@ if (SKY && selected == static_cast<int32_t>(fp.n_lights)) {
 		const f3 Ll = to_local(T, Ld);
 		if (Ll.z < 0.0f) break;
 		float fx;
-		if (GGX) fx = ggx_eval(F0, alpha, Ll, Vl).x;
+		if (ggx_hit) fx = ggx_eval(F0, alpha, Ll, Vl).x;
 		else fx = alb.x * (MIRT_INV_PI * max_sel(0.0f, Ll.z));
 		const f3 Le = sky_eval(sc, Ld.x, Ld.y, Ld.z);
 		const float k = thr.x * fx;
 		f3 rad{ Le.x * k, Le.y * k, Le.z * k };
 		const float sky_p = sky_pdf(sc, sky, Ld.x, Ld.y, Ld.z, srow, scol);
-		const float brdf_pdf = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, Ll.z);
+		const float brdf_pdf = ggx_hit ? 0.0f : MIRT_INV_PI * max_sel(0.0f, Ll.z);
 		const float w = powerHeuristic_over_f(light_selection_pdf * sky_p, brdf_pdf) * (sky_p / sky_q);
 		rad.x *= w; rad.y *= w; rad.z *= w;
 		if (max_sel(max_sel(rad.x, rad.y), rad.z) <= 0.0f) break;
@@ -47,7 +47,7 @@ do {
 	const f3 Ll = to_local(T, Ld);
 	if (Ll.z < 0.0f) break;
 	f3 rad{ lem.x * thr.x, lem.y * thr.y, lem.z * thr.z };
-	if (GGX) {  // Closure<GGX>::eval, DataStreams.hpp:189-195
+	if (ggx_hit) {  // Closure<GGX>::eval, DataStreams.hpp:189-195
 		const f3 f = ggx_eval(F0, alpha, Ll, Vl);
 		rad.x *= f.x; rad.y *= f.y; rad.z *= f.z;
 	} else {    // Closure<LambertianDiffuse>::eval, DataStreams.hpp:169-172
@@ -55,7 +55,7 @@ do {
 		rad.x *= alb.x * f; rad.y *= alb.y * f; rad.z *= alb.z * f;
 	}
 	lpdf *= light_selection_pdf;
-	const float brdf_pdf = GGX ? 0.0f : MIRT_INV_PI * max_sel(0.0f, Ll.z);  // DataStreams.hpp:173-176 / :196-198
+	const float brdf_pdf = ggx_hit ? 0.0f : MIRT_INV_PI * max_sel(0.0f, Ll.z);  // DataStreams.hpp:173-176 / :196-198
 	const float w = powerHeuristic_over_f(lpdf, brdf_pdf);
 	rad.x *= w; rad.y *= w; rad.z *= w;
 	if (max_sel(max_sel(rad.x, rad.y), rad.z) <= 0.0f) break;

@@ -5,7 +5,9 @@
 //     test_radiance_in_contrib.py and test_definitions_gpu.py;
 //   * stream_shade_hit (k_tile_stream, exact stream order) — held by tests/test_exact_stream_order.py.
 // The names are k_shade's.  The including scope provides
-//   constants           GGX; RIS (true: the NEE light is picked among ris_m candidates, a uint32_t the scope provides too); GLASS (true: a
+//   constants           GGX; MIXED (true: the closure is the hit material's — ggx_hit below is bit `mat` of closure_mask, a uint64_t the scope provides
+//                       too, and the GGX rows {F0, roughness} are read from s_ggx (LDS) beside s_albedo, mirt_set_material_closures; false: ggx_hit is
+//                       the constant GGX and none of that is named by an instruction); RIS (true: the NEE light is picked among ris_m candidates, a uint32_t the scope provides too); GLASS (true: a
 //                       transmissive material can take the dielectric interface below, mirt_set_transmission; false: none of that text is compiled in);
 //                       SKY (true: the environment map is light number n_lights of next event estimation, mirt_set_sky_sampling — the scope then
 //                       provides sky (SkyTable) and a light_selection_pdf of 1 / (n_lights + 1), and gets miss_w (float) written with survive: the
@@ -19,7 +21,8 @@
 //                       assigned, the other three flags are only ever set: the scope starts them at false — k_shade's locals do;
 //                       stream_shade_hit binds survive and has_shadow to its StreamHit, which k_tile_stream zeroes before the call); L, light_distance and srad
 //                       are assigned with has_shadow, E with has_E, ndir with survive; GLASS only: via_interface (bool, only ever set: ndir was
-//                       sampled by the interface — the scope hands it to the next bounce as after_interface)
+//                       sampled by the interface — the scope hands it to the next bounce as after_interface); MIXED only: sampled_ggx (bool, assigned
+//                       with survive: ndir was sampled by Closure<GGX> — the scope hands it to the next bounce, whose pdf_in is then 0)
 //   three expressions   SHADE_HIT_ORIGIN (f3), SHADE_HIT_ACC and SHADE_HIT_SEED (uint32_t): the ray's origin, its accumulation number and
 //                       its seed[ID] (Renderer.hpp:74,107), evaluated where they stand below — k_shade loads and derives them from its
 //                       stream at these points, and its registers depend on that order.  #undef'd at the end of this file.
@@ -39,11 +42,12 @@ const quat T = tangent_space(N);
 const f3 Vl = to_local(T, f3{ -D.x, -D.y, -D.z });
 P = { hit.x + N.x * 1e-4f, hit.y + N.y * 1e-4f, hit.z + N.z * 1e-4f };
 const float4 em = s_emission[mat];
-const float4 alb = s_albedo[mat];
+const bool ggx_hit = MIXED ? ((closure_mask >> mat) & 1ull) != 0ull : GGX;      // the closure that shades this hit: the material's (MIXED) or the frame's
+const float4 alb = (MIXED && ggx_hit) ? s_ggx[mat] : s_albedo[mat];
 const bool is_emissive = max_sel(em.x, max_sel(em.y, em.z)) > MIRT_FLT_EPSILON;
 f3 F0{0.0f, 0.0f, 0.0f};
 float alpha = 0.0f;
-if (GGX) {                                                         // closure set-up, Renderer.hpp:210-212
+if (ggx_hit) {                                                     // closure set-up, Renderer.hpp:210-212
 	F0 = { alb.x, alb.y, alb.z };
 	float a = alb.w; a *= a;
 	alpha = a + (1.0f - a) * gloss_decay;
@@ -131,7 +135,7 @@ if (is_emissive) {
 			if (!from_inside) thr = { thr.x * (glass.x / glass_tmax), thr.y * (glass.y / glass_tmax), thr.z * (glass.z / glass_tmax) };
 			P = { hit.x - N.x * 1e-4f, hit.y - N.y * 1e-4f, hit.z - N.z * 1e-4f };
 		}
-	} else if (GGX) {                                                      // Closure<GGX>::sample, DataStreams.hpp:200-218
+	} else if (ggx_hit) {                                                  // Closure<GGX>::sample, DataStreams.hpp:200-218
 		f3 est;
 		ggx_sample(F0, alpha, Vl, b0, b1, sd, est);
 		thr = { thr.x * est.x, thr.y * est.y, thr.z * est.z };
@@ -147,12 +151,13 @@ if (is_emissive) {
 		thr = { thr.x * inv, thr.y * inv, thr.z * inv };
 		ndir = to_world(T, sd);
 		if (GLASS && interface) { ndir = sd; via_interface = true; }
+		if (MIXED) sampled_ggx = ggx_hit;                           // Q8: pdf_in of an emitter this ray hits belongs to the closure that sampled it
 		if (SKY) {
 			// What the miss shader may keep of thr.r x sky: the power heuristic of the closure's pdf of sd — the LOCAL one: next event estimation
 			// weighs against that, and Q8's world-z pdf_in would break the partition of unity — against sel x the sky's density of ndir.
 			// An interface is a delta closure (no light sample meets it): 1.  Closure<GGX>::pdf is 0: 0, as for the emitters such a ray hits.
 			if (GLASS && interface) miss_w = 1.0f;
-			else if (GGX) miss_w = 0.0f;
+			else if (ggx_hit) miss_w = 0.0f;
 			else { uint32_t prow, pcol; miss_w = powerHeuristic(MIRT_INV_PI * max_sel(0.0f, sd.z), light_selection_pdf * sky_pdf(sc, sky, ndir.x, ndir.y, ndir.z, prow, pcol)); }
 		}
 		survive = true;

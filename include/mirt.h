@@ -243,6 +243,35 @@ int mirt_get_light_ris(const mirt_ctx* ctx, uint32_t* candidates);
 int mirt_set_transmission(mirt_ctx* ctx, uint32_t on);
 int mirt_get_transmission(const mirt_ctx* ctx, uint32_t* on);
 
+/* ---- per-material closures: Lambertian and GGX materials in one scene ---------------------------------------------------------------
+ * policy.brdf mirrors the reference's `#define BRDF` (Renderer.hpp:70): a frame is all Closure<LambertianDiffuse> or all Closure<GGX>, although
+ * every mirt_material carries the fields of both.  closure[m], for material m, is 0 (Lambertian) or 1 (GGX); n <= MIRT_MAX_MATERIALS.  Any other
+ * value, or a larger n, returns MIRT_ERR_ARG and changes nothing.  closure = NULL or n = 0 removes the table — the default: the same device
+ * code as a context that never called this, every material taking policy.brdf.  Materials at index n or above take policy.brdf.  The table
+ * survives mirt_set_scene and mirt_set_policy, like the gloss decay table.
+ * Shading rule: a hit on material m is shaded, draw for draw, as policy.brdf = closure[m] shades it —
+ *   - colour and set-up: albedo (Lambertian); F0 with alpha = r^2 + (1 - r^2) gloss_decay[bounce] (GGX);
+ *   - the closure's eval in next event estimation, for sphere lights and the sky, under light RIS too;
+ *   - the closure's pdf in the light sample's MIS weight: cos / pi (Lambertian), 0 (GGX);
+ *   - the closure sample;
+ *   - with sky sampling, the miss weight: the Lambertian heuristic, or 0 for GGX.
+ *   The roulette and the dielectric interface of mirt_set_transmission are untouched.  No new estimator: every term is one of the two texts.
+ *   pdf_in of an emitter hit (Q8) belongs to the closure that SAMPLED the ray: (1 / pi) max(0, D.z) after a Lambertian hit, 0 after a GGX hit —
+ *   whatever the emitter's own material says.  "Sampled by GGX" travels with the surviving ray (bit 30 of the stream's path word).
+ * Launch rule: if the effective closures of materials 0 .. n_materials - 1 of the current scene all equal k, the kernels of policy.brdf = k are
+ *   launched — the same device code, that policy's words — and *mixed = 0.  Otherwise the MIXED kernels run (both branches in one wave, no
+ *   sorting by material) and *mixed = 1.  The material LIST decides, not which materials the spheres use: an unused material of the other kind
+ *   forces MIXED.  Without a scene *mixed = 0.
+ * First-hit AOVs: the albedo plane holds albedo for a Lambertian material and F0 for a GGX one.
+ * The estimand changes and the accumulator is NOT reset: the caller does that (mirt_reset).  Deferred mirt_accumulate_async calls are launched
+ * first, under the old table.  Exact stream order and a non-empty table exclude each other: a non-empty table under stream order 1, and
+ * mirt_set_stream_order(ctx, 1) with a non-empty table, return MIRT_ERR_STATE.  Combines with the lens, frozen tiles, light RIS, transmission,
+ * sky sampling, AOVs, the noise estimate and groups; the camera-ray candidate lists stay valid.
+ * mirt_get_material_closures: *n = entries of the table, *mixed as above; the table is copied to closure_out when capacity >= *n (closure_out
+ * = NULL asks for the two numbers only; a non-NULL closure_out that is too small is MIRT_ERR_ARG). */
+int mirt_set_material_closures(mirt_ctx* ctx, const uint8_t* closure, uint32_t n);
+int mirt_get_material_closures(const mirt_ctx* ctx, uint8_t* closure_out, uint32_t capacity, uint32_t* n, uint32_t* mixed);
+
 /* ---- sampling the environment map: the sky as one more light of next event estimation ---------------------------------------------
  * By default light from the environment map (hdri_rgba x ambient_color) reaches a surface only through an extension ray that misses every
  * sphere (the miss shader, thr.r x sky: Q10); the reference does no better, and its author's note at Renderer.hpp:260 asks for better light
@@ -497,6 +526,7 @@ int mirt_group_set_lens(mirt_group* group, float aperture_radius, float focus_de
 int mirt_group_set_light_ris(mirt_group* group, uint32_t candidates);             /* mirt_set_light_ris on every member */
 int mirt_group_set_transmission(mirt_group* group, uint32_t on);                   /* mirt_set_transmission on every member (and the gather context) */
 int mirt_group_set_sky_sampling(mirt_group* group, uint32_t on);                   /* mirt_set_sky_sampling on every member (and the gather context) */
+int mirt_group_set_material_closures(mirt_group* group, const uint8_t* closure, uint32_t n);   /* mirt_set_material_closures on every member (and the gather context) */
 int mirt_group_pick_focus(mirt_group* group, uint32_t x, uint32_t y, float* distance, float* depth);   /* mirt_pick_focus on the first member */
 int mirt_group_set_policy(mirt_group* group, const mirt_policy* policy);
 int mirt_group_set_gloss_decay(mirt_group* group, const float* decay, uint32_t n);
