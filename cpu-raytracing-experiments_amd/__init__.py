@@ -114,6 +114,7 @@ def load_library():
         "mirt_set_light_ris": [P, u32], "mirt_get_light_ris": [P, C.POINTER(u32)],
         "mirt_set_transmission": [P, u32], "mirt_get_transmission": [P, C.POINTER(u32)],
         "mirt_set_sky_sampling": [P, u32], "mirt_get_sky_sampling": [P, C.POINTER(u32)],
+        "mirt_set_ggx_pdf": [P, u32], "mirt_get_ggx_pdf": [P, C.POINTER(u32)],
         "mirt_set_material_closures": [P, vp, u32], "mirt_get_material_closures": [P, vp, u32, C.POINTER(u32), C.POINTER(u32)],
         "mirt_resize": [P, u32, u32],
         "mirt_set_tile_range": [P, u32, u32], "mirt_set_tile_rows": [P, u32, u32],
@@ -171,6 +172,7 @@ def load_library():
         "mirt_group_set_gloss_decay": [G, vp, u32],
         "mirt_group_set_stream_order": [G, u32],
         "mirt_group_set_light_ris": [G, u32], "mirt_group_set_transmission": [G, u32], "mirt_group_set_sky_sampling": [G, u32],
+        "mirt_group_set_ggx_pdf": [G, u32],
         "mirt_group_set_material_closures": [G, vp, u32],
         "mirt_group_resize": [G, u32, u32],
         "mirt_group_reset": [G],
@@ -315,8 +317,10 @@ class _Binding:
         """mirt_<name> or mirt_group_<name> on this object's handle, checked."""
         return self._check(getattr(self._lib, self._prefix + name)(getattr(self, self._handle), *args))
 
-    def _configure(self, gloss_decay, exact_stream_order, aov, light_ris=0, transmission=False, sky_sampling=False, material_closures=None):
+    def _configure(self, gloss_decay, exact_stream_order, aov, light_ris=0, transmission=False, sky_sampling=False, material_closures=None, ggx_pdf=False):
         """The end of both constructors, after the policy is set."""
+        if ggx_pdf:
+            self.set_ggx_pdf(True)
         if material_closures is not None:
             self.set_material_closures(material_closures)
         if sky_sampling:
@@ -384,6 +388,14 @@ class _Binding:
         met by extension rays only, as in the reference.  The same expectation with another variance: the accumulator is NOT reset.  No effect
         without ambient light, with mis=False or over a black map.  Not in exact stream order.  (A group: on every member.)"""
         self._call("set_sky_sampling", int(bool(on)))
+
+    def set_ggx_pdf(self, on: bool = True):
+        """True: wherever Closure<GGX> shades a hit its pdf is the visible-normal density (Heitz 2018 eq. 17; mirt.h, mirt_set_ggx_pdf) instead of
+        the reference's 0 - in next event estimation's MIS weight, at an emitter the sampled ray hits and, under sky sampling, at the sky it
+        misses into - so emitters and the sky are weighed two ways on GGX surfaces.  The closure sample, the roulette and the traversal read
+        nothing new: rays, terminated and dropped do not change.  False (the default): the reference's 0.  No effect while no material ends up
+        GGX.  Formally another estimator, and the accumulator is NOT reset: call Reset().  Not in exact stream order.  (A group: on every member.)"""
+        self._call("set_ggx_pdf", int(bool(on)))
 
     def set_material_closures(self, closures=None):
         """closures[m] = 0 (Lambertian) or 1 (GGX) for material m, so that both kinds share a scene (mirt.h, mirt_set_material_closures); materials
@@ -599,7 +611,7 @@ class Renderer(_Binding):
                  use_bvh: bool = False, count_traffic: bool = False, profile: bool = False, max_batch: int = 0,
                  allow_half_boxes: bool = True, reference_tree: bool = False, streams: int = 0, gpu_build: bool = False, trace_primary_rays: bool = False,
                  brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False, light_ris: int = 0,
-                 transmission: bool = False, sky_sampling: bool = False, material_closures=None):
+                 transmission: bool = False, sky_sampling: bool = False, material_closures=None, ggx_pdf: bool = False):
         if material_closures is not None:
             _closure_table(material_closures)           # a bad table is refused before the library is loaded or a device touched
         self._lib = load_library()
@@ -615,7 +627,7 @@ class Renderer(_Binding):
                              int(brdf))
         self._call("set_policy", C.byref(self.policy))
         self._call("debug_allow_half_boxes", int(allow_half_boxes))
-        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission, sky_sampling, material_closures)
+        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission, sky_sampling, material_closures, ggx_pdf)
 
     def load_tile_counts(self, counts):
         """After load_accumulator: per-tile counts (positive multiples of `buckets`, at most accumulations); tiles below it are frozen."""
@@ -641,6 +653,11 @@ class Renderer(_Binding):
     def sky_sampling(self) -> bool:
         v = C.c_uint32(0)
         self._call("get_sky_sampling", C.byref(v))
+        return bool(v.value)
+
+    def ggx_pdf(self) -> bool:
+        v = C.c_uint32(0)
+        self._call("get_ggx_pdf", C.byref(v))
         return bool(v.value)
 
     def material_closures(self):
@@ -795,7 +812,7 @@ class GroupRenderer(_Binding):
     def __init__(self, scene: Scene, devices=(0,), max_bounces: int = 16, buckets: int = 5, mis: bool = True, use_bvh: bool = True,
                  count_traffic: bool = False, max_batch: int = 0, streams: int = 0, reference_tree: bool = False, gpu_build: bool = False,
                  brdf: int = 0, gloss_decay=None, exact_stream_order: bool = False, aov: bool = False, lens: bool = False, light_ris: int = 0,
-                 transmission: bool = False, sky_sampling: bool = False, material_closures=None):
+                 transmission: bool = False, sky_sampling: bool = False, material_closures=None, ggx_pdf: bool = False):
         if material_closures is not None:
             _closure_table(material_closures)           # a bad table is refused before the library is loaded or a device touched
         self._lib = load_library()
@@ -811,7 +828,7 @@ class GroupRenderer(_Binding):
         self.policy = Policy(max_bounces, buckets, int(mis), int(use_bvh), int(count_traffic), 0, max_batch, int(reference_tree), int(streams), int(gpu_build), 0,
                              int(brdf))
         self._call("set_policy", C.byref(self.policy))
-        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission, sky_sampling, material_closures)
+        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission, sky_sampling, material_closures, ggx_pdf)
 
     def light_ris(self) -> int:
         """The members' setting (they all hold the same: set_light_ris sets every one)."""
@@ -835,6 +852,14 @@ class GroupRenderer(_Binding):
         self._call("member", 0, C.byref(ctx))
         if self._lib.mirt_get_sky_sampling(ctx, C.byref(v)) < 0:
             raise MirtError("mirt_get_sky_sampling failed on member 0")
+        return bool(v.value)
+
+    def ggx_pdf(self) -> bool:
+        """The members' setting (they all hold the same: set_ggx_pdf sets every one)."""
+        ctx, v = C.c_void_p(), C.c_uint32(0)
+        self._call("member", 0, C.byref(ctx))
+        if self._lib.mirt_get_ggx_pdf(ctx, C.byref(v)) < 0:
+            raise MirtError("mirt_get_ggx_pdf failed on member 0")
         return bool(v.value)
 
     def material_closures(self):

@@ -209,6 +209,22 @@ MIRT_DI f3 ggx_eval(f3 F0, float alpha, f3 Llocal, f3 Vlocal) {                 
 	const float NdotH = max_sel(0.0f, Hn.z), HdotV = max_sel(0.0f, dot3(Hn, Vlocal));
 	return microfacet_brdf(F0, alpha, NdotV, NdotL, NdotH, HdotV);
 }
+// mirt_set_ggx_pdf: the pdf Closure<GGX>::pdf (DataStreams.hpp:196-198, "TODO", returns 0) would be — the density per solid angle of L of the
+// reflection of V about a visible normal, Heitz 2018 eq. 17, G1(V) D(H) / (4 V.z), with the alpha^2 floor microfacet_brdf gives D.  No reference
+// text: pinned to tests/definitions.py ggx_vndf_pdf_of_direction through mirt_debug_math fn 14.  A function of (alpha, L, V) alone: next event
+// estimation, the emitter hit and the miss shader all weigh with this one number.  0 — never NaN or inf — for L at or below the surface, for V.z <= 0
+// and where V.z^2 underflows: the guards stand before every division.  H, N.H^2 and D are spelt as ggx_eval spells them and G1(V) as
+// smith_g2_over_g1 does, so that beside either the compiler keeps one copy.  Operation order: (G1 * D) / (4 * V.z).
+MIRT_DI float ggx_pdf(float alpha, f3 Llocal, f3 Vlocal) {
+	const float NdotV = max_sel(0.0f, Vlocal.z);
+	const float NdotV2 = NdotV * NdotV;
+	if (!(Llocal.z > 0.0f && NdotV2 > 0.0f)) return 0.0f;
+	const f3 Hn = normalize3(f3{ Llocal.x + Vlocal.x, Llocal.y + Vlocal.y, Llocal.z + Vlocal.z });      // (L.z + V.z > 0: the length is not 0)
+	const float NdotH = max_sel(0.0f, Hn.z);
+	if (!(NdotH > 0.0f)) return 0.0f;
+	const float alpha2 = alpha * alpha;
+	return (G1_GGX(alpha2, NdotV2) * GGX_D(max_sel(0.00001f, alpha2), NdotH * NdotH)) / (4.0f * NdotV);
+}
 MIRT_DI void ggx_sample(f3 F0, float alpha, f3 Vlocal, float u0, float u1, f3& dir, f3& estimator) {   // Closure<GGX>::sample, DataStreams.hpp:200-218
 	const float NdotV = max_sel(0.0f, Vlocal.z);
 	float HdotV;

@@ -76,6 +76,9 @@ struct StreamBuf {
 	                            //  (Q8, Renderer.hpp:386,401), a function of the stored direction, recomputed by the bounce that needs it)
 	float* w;                   // mirt_set_sky_sampling only (nullptr otherwise, and no other kernel than k_shade<SKY> names it): the MIS weight the miss shader gives
 	                            // thr.r x sky should this ray miss — the power heuristic of the closure's LOCAL pdf of the direction against the sky's (k_shade, SKY)
+	                            // (mirt_set_ggx_pdf adds one more 4-byte plane per stream, out->pdf of the closure sample that made the ray.  It is NOT a member: this
+	                            //  struct is an argument of every trace kernel too, and growing it moves their and the SKY kernels' scalar registers.  k_shade takes
+	                            //  the two planes as its last arguments, pdf_plane_in / pdf_plane_out, which only its PDF instantiations name.)
 };
 // kPrimaryList launches have no ray stream: the words at `a` are the list of pixels instead (k_primary_cand's, or the active tiles' part of it).
 MIRT_DI const uint32_t* stream_pixel_list(const StreamBuf& in) { return reinterpret_cast<const uint32_t*>(in.a); }
@@ -1517,13 +1520,20 @@ MIRT_DI uint32_t block_compact(bool flag, uint32_t value, uint32_t* scratch, uin
 // wave without sorting: a wave with hits of both kinds runs both branches.  Both tables are staged: s_albedo = sc.mat_albedo, s_ggx = mat_ggx.
 // Q8's pdf_in belongs to the closure that SAMPLED the ray, so "sampled by Closure<GGX>" travels as kSampledGGX in the stream's path word, as
 // kViaInterface does.  MIXED = false names neither the mask nor s_ggx, and is the text as it was.  The same launch bounds.
-template <bool FIRST, bool GGX, bool LENS = false, bool SPARSE = false, bool RIS = false, bool GLASS = false, bool SKY = false, bool MIXED = false>
+// PDF (mirt_set_ggx_pdf, launched only while some material of the scene ends up GGX: with GGX or MIXED, never the all-Lambertian form): Closure<GGX>::pdf
+// is ggx_pdf instead of 0 in the three MIS weights that read it — next event estimation's, the emitter hit's and (SKY) the miss shader's.  The
+// emitter hit's is p~ of the hit that SAMPLED the ray, so it travels in a plane beside the stream (pdf_plane_out, indexed as `out` is; pdf_plane_in
+// as `in` is; nullptr without the switch): written with the survivor, read back as pdf_in in phase 2
+// (a Lambertian-sampled ray stores Q8's word there, the bits it would otherwise recompute).  The closure sample, its estimator and the roulette
+// read nothing new.  PDF = false names neither ggx_pdf nor the plane, and is the text as it was.  The same launch bounds.
+template <bool FIRST, bool GGX, bool LENS = false, bool SPARSE = false, bool RIS = false, bool GLASS = false, bool SKY = false, bool MIXED = false, bool PDF = false>
 __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
                                                   Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
                                                   const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens, uint32_t ris_m, const uint32_t* __restrict__ tile_frozen, SkyTable sky,
-                                                  unsigned long long closure_mask) {
+                                                  unsigned long long closure_mask, const float* __restrict__ pdf_plane_in, float* __restrict__ pdf_plane_out) {
 	static_assert(!(LENS || SPARSE) || FIRST, "the lens and the frozen tiles concern bounce 0 only");
 	static_assert(!(MIXED && GGX), "MIXED takes the closure from the material: it is instantiated with GGX = false");
+	static_assert(!PDF || GGX || MIXED, "the GGX pdf concerns hits that Closure<GGX> shades: the all-Lambertian form has no PDF instantiation");
 	const QueueView qin = FIRST ? queue_identity(fp.n_pix * fp.batch_n) : queue_view(in_queue);
 	const uint32_t n = qin.pre[kSegs];
 	const uint32_t n_chunks = (fp.n_pix + kShadeBlock - 1u) / kShadeBlock;      // FIRST
@@ -1637,6 +1647,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 		bool via_interface = false;                                            // GLASS
 		bool sampled_ggx = false;                                              // MIXED
 		float miss_w = 1.0f;                                                   // SKY
+		float pdf_out = 0.0f;                                                  // PDF
 		uint32_t path = 0;
 		f3 P{0, 0, 0}, ndir{0, 0, 0}, L{0, 0, 0}, srad{0, 0, 0}, E{0, 0, 0};
 		f3 thr{1.0f, 1.0f, 1.0f};
@@ -1659,6 +1670,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 				D = { b.x, b.y, b.z };
 				thr = { b.w, c.x, c.y };
 				pdf_in = after_ggx ? 0.0f : MIRT_INV_PI * max_sel(0.0f, D.z);     // out->pdf of the bounce that sampled D (Q8), bit for bit; Closure<GGX>::pdf = 0
+				if (PDF) pdf_in = pdf_plane_in[i];                                       // ... unless the sampling bounce stored it (mirt_set_ggx_pdf)
 			}
 			const HitRec hrec = FIRST ? HitRec{ my_tfar, my_prim } : hit_in[i];
 			const int32_t prim = hrec.prim;
@@ -1680,6 +1692,7 @@ __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FramePara
 			out.b[slot] = make_float4(ndir.x, ndir.y, ndir.z, thr.x);
 			out.c[slot] = make_float2(thr.y, thr.z);
 			if (SKY) out.w[slot] = miss_w;
+			if (PDF) pdf_plane_out[slot] = pdf_out;
 		}
 		if (has_shadow) {
 			// the record holds its own ray and its path id (kernels.hpp ShadowBuf): k_trace reads nothing of the surviving ray
@@ -1767,11 +1780,12 @@ MIRT_DI void stream_shade_hit(const SceneDev& sc, const FrameParams& fp, const f
 	constexpr bool MIXED = false; constexpr unsigned long long closure_mask = 0ull;   // ... and takes every closure from policy.brdf (mirt_set_material_closures excludes this mode)
 	const float4* const s_ggx = nullptr; bool sampled_ggx = false;             // named by the MIXED text only: never evaluated here
 	constexpr bool SKY = false; const SkyTable sky{}; float miss_w = 1.0f;     // ... and draws its NEE light among the sphere lights only (mirt_set_sky_sampling excludes this mode)
+	constexpr bool PDF = false; float pdf_out = 0.0f;                          // ... and Closure<GGX>::pdf is the reference's 0 (mirt_set_ggx_pdf excludes this mode)
 #define SHADE_HIT_ORIGIN stream_O
 #define SHADE_HIT_ACC stream_acc
 #define SHADE_HIT_SEED stream_seed
 #include "shade_hit_body.inc"
-	(void)via_interface; (void)miss_w; (void)sky; (void)sampled_ggx; (void)s_ggx;
+	(void)via_interface; (void)miss_w; (void)sky; (void)sampled_ggx; (void)s_ggx; (void)pdf_out;
 	if (!terminated) h.thr = thr;                                            // the survivor's throughput
 }
 constexpr uint32_t kStreamPlanes = 13;          // p, dir, throughput, radiance, pixelID
@@ -2108,6 +2122,11 @@ __global__ __launch_bounds__(kBlock) void k_debug_sky(int fn, uint32_t n, const 
 			out[n + i] = static_cast<float>(row); out[2 * n + i] = static_cast<float>(col);
 		}
 	}
+}
+// mirt_debug_math fn 14: ggx_pdf (mirt_set_ggx_pdf).  in: alpha, L(3), V(3) -> out p~.  A kernel of its own, so that k_debug_math stays the code it was.
+__global__ __launch_bounds__(kBlock) void k_debug_ggx_pdf(uint32_t n, const float* in, float* out) {
+	for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock)
+		out[i] = ggx_pdf(in[i], f3{ in[n + i], in[2 * n + i], in[3 * n + i] }, f3{ in[4 * n + i], in[5 * n + i], in[6 * n + i] });
 }
 
 } // namespace mirt

@@ -63,6 +63,8 @@ struct PipeSlot {
 	DeviceBuffer contrib;            // this batch's path radiances, [tile][slot][256][rgb] (kernels.hpp contrib_index)
 	DeviceBuffer fat;                // fat-ray index lists: [closest kFatCapacity][shadow kFatCapacity]
 	DeviceBuffer sky_w;              // mirt_set_sky_sampling(1) only: StreamBuf::w of the two ray streams, one 4-byte plane each
+	DeviceBuffer pdf_p;              // mirt_set_ggx_pdf(1) only: one more 4-byte plane for each of the two ray streams (k_shade's pdf_plane_in / pdf_plane_out)
+	float* pdf_plane[2]{};           // ... the plane of stream_buf[b]; nullptr while the switch is off
 	hipEvent_t batch_done = nullptr; // recorded on `stream` after the batch's last kernel
 	hipEvent_t merged = nullptr;     // recorded on the main stream after the batch was merged (slot reusable)
 	hipEvent_t aov_done = nullptr;   // mirt_set_aov(1) only: recorded on `stream` after the batch's k_first_hit_aov (created by the first such batch)
@@ -74,7 +76,7 @@ struct PipeSlot {
 	HitRec* hit = nullptr;           // RayStream<>::Hit: one 8-B {tfar, primID} record per ray (two planes' worth of the arena)
 	// Buffers, events and stream.  The caller has synchronised every stream.
 	void release() {
-		arena.release(); counts.release(); contrib.release(); fat.release(); sky_w.release();
+		arena.release(); counts.release(); contrib.release(); fat.release(); sky_w.release(); pdf_p.release();
 		for (hipEvent_t* e : { &batch_done, &merged, &aov_done }) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
 		if (stream) (void)hipStreamDestroy(stream);
 		stream = nullptr;
@@ -105,6 +107,7 @@ struct mirt_ctx {
 	uint32_t sky_sampling = 0;       // mirt_set_sky_sampling: 1 = the environment map is one more NEE light (the SKY instantiations of k_shade, while sky_active())
 	DeviceBuffer sky_table;          // its sampling table (kernels.hpp SkyTable), built by build_sky_table beside `hdri`; held only while the switch is on and a scene is set
 	SkyTable sky{};                  // ... as the kernels see it (t = nullptr: none)
+	uint32_t ggx_pdf = 0;            // mirt_set_ggx_pdf: 1 = Closure<GGX>::pdf is ggx_pdf in the MIS weights (the PDF instantiations of k_shade, while a material of the scene ends up GGX)
 	float sky_total = 0.0f;          // the table's last marginal running sum; 0 (a black map, no ambient light): the switch changes no launch
 	// mirt_set_material_closures: closure (0 Lambertian, 1 GGX) of material m; a material at or beyond its end takes policy.brdf.  Empty (the default):
 	// every launch is the one of a context without the call.  What a launch does with it is closure_plan()'s to say, and nobody else's.
@@ -303,7 +306,7 @@ uint32_t wanted_slots(const mirt_ctx* c) {
 // Device bytes of the batches in flight for the current plan (ray streams + contribution buffers).
 uint64_t streams_bytes(const mirt_ctx* c) {
 	const uint64_t rays = static_cast<uint64_t>(c->n_tiles) * kTileSize * batch_limit(c);
-	return wanted_slots(c) * (rays * 4u * kStreamPlanes + rays * 12u);
+	return wanted_slots(c) * (rays * 4u * (kStreamPlanes + (c->ggx_pdf ? 2u : 0u)) + rays * 12u);      // mirt_set_ggx_pdf: the closure-pdf plane of both streams, 4 B per ray each
 }
 
 // Automatic batch size: as large as kBatchRays asks, but within 80 % of the device memory that is free plus what this context's own ray
@@ -337,7 +340,7 @@ int ensure_streams(mirt_ctx* c) {
 	const uint32_t want = wanted_slots(c);
 	const size_t acc_bytes = static_cast<size_t>(c->n_tiles) * batch_limit(c) * 3 * kTileSize * sizeof(float);     // contribution buffer: [tile][slot][256][rgb]
 	if (cap == c->capacity && nb == c->arena_bounces && c->slots.size() == want && c->slots[0].contrib.bytes >= acc_bytes &&
-	    (c->slots[0].sky_w.ptr != nullptr) == (c->sky_sampling != 0)) return MIRT_OK;
+	    (c->slots[0].sky_w.ptr != nullptr) == (c->sky_sampling != 0) && (c->slots[0].pdf_p.ptr != nullptr) == (c->ggx_pdf != 0)) return MIRT_OK;
 	HIP_TRY(c, sync_all(c));
 	c->aov_prev = nullptr;                                                   // (every batch has finished; the event's slot may go away below)
 	while (c->slots.size() > want) { c->slots.back().release(); c->slots.pop_back(); }
@@ -359,12 +362,14 @@ int ensure_streams(mirt_ctx* c) {
 		if (e == hipSuccess) { e = sl.contrib.ensure(acc_bytes); what = "contribution buffer"; }
 		if (e == hipSuccess && c->sky_sampling) { e = sl.sky_w.ensure(2 * plane_bytes); what = "miss-weight planes"; }
 		if (!c->sky_sampling) sl.sky_w.release();
+		if (e == hipSuccess && c->ggx_pdf) { e = sl.pdf_p.ensure(2 * plane_bytes); what = "closure-pdf planes"; }
+		if (!c->ggx_pdf) sl.pdf_p.release();
 		if (e != hipSuccess) {
 			// not enough device memory after all (someone else took it meanwhile — another context or process planning against the same
 			// free memory): halve the automatic batch and plan again
 			(void)hipGetLastError();
 			if (e == hipErrorOutOfMemory && !c->policy.max_batch && batch_limit(c) > batch_floor(c)) {
-				for (PipeSlot& other : c->slots) { other.arena.release(); other.contrib.release(); other.sky_w.release(); }
+				for (PipeSlot& other : c->slots) { other.arena.release(); other.contrib.release(); other.sky_w.release(); other.pdf_p.release(); }
 				c->capacity = 0;
 				c->batch_mem_cap = std::max(batch_limit(c) / 2, batch_floor(c));
 				return ensure_streams(c);
@@ -377,6 +382,7 @@ int ensure_streams(mirt_ctx* c) {
 			StreamBuf& s = sl.stream_buf[b];
 			s.a = (float4*)take(4); s.b = (float4*)take(4); s.c = (float2*)take(2);
 			s.w = sl.sky_w.ptr ? reinterpret_cast<float*>(sl.sky_w.as<char>() + b * plane_bytes) : nullptr;
+			sl.pdf_plane[b] = sl.pdf_p.ptr ? reinterpret_cast<float*>(sl.pdf_p.as<char>() + b * plane_bytes) : nullptr;
 		}
 		sl.hit = (HitRec*)take(2);                                         // 8 B per ray
 		ShadowBuf& h = sl.shadow_buf;
@@ -630,6 +636,32 @@ auto shade_kernel_mixed(bool first, bool lens, bool sparse, bool ris, bool glass
 	default: return shade_kernel_mixed_of<true, true, true>(first, lens, sparse);
 	}
 }
+// pdf = mirt_set_ggx_pdf while closure_plan() leaves a GGX material: the PDF instantiations — the five reachable forms of [sparse][first ? 1 + lens : 0]
+// times RIS, GLASS and SKY, once with GGX = true and once with MIXED = true (80; the all-Lambertian form has none).  Named after every older
+// instantiation, above, so that those keep their device code.
+template <bool RIS, bool GLASS, bool SKY, bool MIXED>
+auto shade_kernel_pdf_of(bool first, bool lens, bool sparse) {
+	static const decltype(&k_shade<false, false>) table[2][3] = {          // [sparse][first ? 1 + lens : 0]
+		{ k_shade<false, !MIXED, false, false, RIS, GLASS, SKY, MIXED, true>, k_shade<true, !MIXED, false, false, RIS, GLASS, SKY, MIXED, true>, k_shade<true, !MIXED, true, false, RIS, GLASS, SKY, MIXED, true> },
+		{ nullptr, k_shade<true, !MIXED, false, true, RIS, GLASS, SKY, MIXED, true>, k_shade<true, !MIXED, true, true, RIS, GLASS, SKY, MIXED, true> } };
+	return table[first && sparse][first ? 1 + lens : 0];
+}
+template <bool MIXED>
+auto shade_kernel_pdf_by(bool first, bool lens, bool sparse, bool ris, bool glass, bool sky) {
+	switch ((ris ? 4 : 0) | (glass ? 2 : 0) | (sky ? 1 : 0)) {
+	case 0: return shade_kernel_pdf_of<false, false, false, MIXED>(first, lens, sparse);
+	case 1: return shade_kernel_pdf_of<false, false, true, MIXED>(first, lens, sparse);
+	case 2: return shade_kernel_pdf_of<false, true, false, MIXED>(first, lens, sparse);
+	case 3: return shade_kernel_pdf_of<false, true, true, MIXED>(first, lens, sparse);
+	case 4: return shade_kernel_pdf_of<true, false, false, MIXED>(first, lens, sparse);
+	case 5: return shade_kernel_pdf_of<true, false, true, MIXED>(first, lens, sparse);
+	case 6: return shade_kernel_pdf_of<true, true, false, MIXED>(first, lens, sparse);
+	default: return shade_kernel_pdf_of<true, true, true, MIXED>(first, lens, sparse);
+	}
+}
+auto shade_kernel_pdf(bool first, bool mixed, bool lens, bool sparse, bool ris, bool glass, bool sky) {
+	return mixed ? shade_kernel_pdf_by<true>(first, lens, sparse, ris, glass, sky) : shade_kernel_pdf_by<false>(first, lens, sparse, ris, glass, sky);
+}
 auto first_hit_aov_kernel(bool lens, bool sparse) {
 	static const decltype(&k_first_hit_aov<false>) table[2][2] = { { k_first_hit_aov<false>, k_first_hit_aov<true> }, { k_first_hit_aov<false, true>, k_first_hit_aov<true, true> } };   // [sparse][lens]
 	return table[sparse][lens];
@@ -847,10 +879,14 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			  const bool glass = c->transmission && c->scene_has_glass, sky = sky_active(c);
 			  // mirt_set_material_closures: the kernels of the one closure every material takes, or the MIXED ones
 			  const ClosurePlan plan = closure_plan(c);
-			  const auto shade = plan.mixed ? shade_kernel_mixed(bounce == 0, lens, sparse, ris != 0, glass, sky)
+			  // mirt_set_ggx_pdf: only where Closure<GGX> shades a hit; an all-Lambertian plan launches what it launched without the switch
+			  const bool pdf = c->ggx_pdf && (plan.mixed || plan.ggx);
+			  const auto shade = pdf ? shade_kernel_pdf(bounce == 0, plan.mixed, lens, sparse, ris != 0, glass, sky)
+			                   : plan.mixed ? shade_kernel_mixed(bounce == 0, lens, sparse, ris != 0, glass, sky)
 			                   : sky ? shade_kernel_sky(bounce == 0, plan.ggx, lens, sparse, ris != 0, glass) : shade_kernel(bounce == 0, plan.ggx, lens, sparse, ris != 0, glass);
 			  hipLaunchKernelGGL(shade, dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
-			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, ris, tile_frozen, sky ? c->sky : SkyTable{}, plan.mask); }
+			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, ris, tile_frozen, sky ? c->sky : SkyTable{}, plan.mask,
+			                     pdf ? sl.pdf_plane[bounce & 1u] : nullptr, pdf ? sl.pdf_plane[(bounce & 1u) ^ 1u] : nullptr); }
 		}
 	}
 	HIP_TRY(c, hipGetLastError());
@@ -1338,6 +1374,7 @@ int mirt_set_stream_order(mirt_ctx* c, uint32_t exact) {
 	if (exact && c->light_ris) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which draws its NEE light uniformly (Renderer.hpp:259): call mirt_set_light_ris(ctx, 0) first");
 	if (exact && c->transmission) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, no closure of which reads transmission: call mirt_set_transmission(ctx, 0) first");
 	if (exact && c->sky_sampling) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which draws its NEE light among the sphere lights only: call mirt_set_sky_sampling(ctx, 0) first");
+	if (exact && c->ggx_pdf) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, whose Closure<GGX>::pdf is 0 (DataStreams.hpp:196-198): call mirt_set_ggx_pdf(ctx, 0) first");
 	if (exact && !c->closures.empty()) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, every closure of which is policy.brdf's (Renderer.hpp:70): call mirt_set_material_closures(ctx, NULL, 0) first");
 	if (exact && c->aov_on) return fail(c, MIRT_ERR_STATE, "exact stream order keeps no hit records (k_tile_stream runs a tile's whole bounce loop in one launch), so it cannot feed the first-hit AOVs: call mirt_set_aov(ctx, 0) first");
 	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render in the mode they were issued under
@@ -1411,6 +1448,23 @@ int mirt_set_sky_sampling(mirt_ctx* c, uint32_t on) {
 	c->sky_sampling = on;                                                           // the same expectation: no reset; the camera-ray lists do not depend on it
 	return MIRT_OK;
 }
+// ---- the GGX closure's pdf in the MIS weights -----------------------------------------------------
+int mirt_set_ggx_pdf(mirt_ctx* c, uint32_t on) {
+	if (!c) return MIRT_ERR_ARG;
+	if (on > 1) return fail(c, MIRT_ERR_ARG, "ggx pdf %u is neither 0 (off: Closure<GGX>::pdf is the reference's 0) nor 1 (on: the visible-normal density, in every MIS weight that reads it)", on);
+	if (on && c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, whose Closure<GGX>::pdf is 0 (DataStreams.hpp:196-198): call mirt_set_stream_order(ctx, 0) first");
+	if (on == c->ggx_pdf) return MIRT_OK;
+	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render under the setting they were issued under
+	if (!on) {
+		HIP_TRY(c, hipSetDevice(c->device));
+		HIP_TRY(c, sync_all(c));                                                    // batches in flight write the planes
+		for (PipeSlot& sl : c->slots) { sl.pdf_p.release(); sl.pdf_plane[0] = sl.pdf_plane[1] = nullptr; }
+	}
+	c->ggx_pdf = on;                                                                // formally another estimator: the caller resets; the camera-ray lists do not depend on it
+	c->planned_for = 0;                                                             // the planes count in the automatic batch plan (streams_bytes)
+	return MIRT_OK;
+}
+int mirt_get_ggx_pdf(const mirt_ctx* c, uint32_t* on) { if (!c || !on) return MIRT_ERR_ARG; *on = c->ggx_pdf; return MIRT_OK; }
 int mirt_get_sky_sampling(const mirt_ctx* c, uint32_t* on) { if (!c || !on) return MIRT_ERR_ARG; *on = c->sky_sampling; return MIRT_OK; }
 int mirt_get_transmission(const mirt_ctx* c, uint32_t* on) { if (!c || !on) return MIRT_ERR_ARG; *on = c->transmission; return MIRT_OK; }
 int mirt_get_light_ris(const mirt_ctx* c, uint32_t* candidates) { if (!c || !candidates) return MIRT_ERR_ARG; *candidates = c->light_ris; return MIRT_OK; }
@@ -1843,14 +1897,16 @@ int mirt_debug_trace_shadow(mirt_ctx* c, size_t n, const float* p_xyz, const flo
 
 int mirt_debug_math(mirt_ctx* c, int fn, size_t n, const float* in, float* out) {
 	if (!c) return MIRT_ERR_ARG;
-	static const int n_in[14] = { 1, 2, 1, 2, 2, 6, 8, 3, 10, 9, 1, 6, 2, 3 }, n_out[14] = { 2, 1, 1, 3, 3, 10, 5, 5, 3, 6, 1, 6, 6, 3 };
-	if (fn < 0 || fn > 13 || !in || !out || n == 0 || n >= (1u << 28)) return fail(c, MIRT_ERR_ARG, "bad arguments");
+	static const int n_in[15] = { 1, 2, 1, 2, 2, 6, 8, 3, 10, 9, 1, 6, 2, 3, 7 }, n_out[15] = { 2, 1, 1, 3, 3, 10, 5, 5, 3, 6, 1, 6, 6, 3, 1 };
+	if (fn < 0 || fn > 14 || !in || !out || n == 0 || n >= (1u << 28)) return fail(c, MIRT_ERR_ARG, "bad arguments");
 	HIP_TRY(c, hipSetDevice(c->device));
 	ScopedBuffer din, dout;
 	HIP_TRY(c, din.ensure(n * n_in[fn] * 4)); HIP_TRY(c, dout.ensure(n * n_out[fn] * 4));
 	HIP_TRY(c, hipMemcpy(din.ptr, in, n * n_in[fn] * 4, hipMemcpyHostToDevice));
-	if (fn >= 12 && !(c->sky.t && c->sky_total > 0.0f)) return fail(c, MIRT_ERR_STATE, "debug_math fn %d reads the sky sampling table: mirt_set_sky_sampling(ctx, 1) over a scene whose table has a total above 0 first", fn);
-	if (fn >= 12) hipLaunchKernelGGL(k_debug_sky, dim3(grid_for(c, n)), dim3(kBlock), 0, c->stream, fn, static_cast<uint32_t>(n), din.as<float>(), dout.as<float>(), c->scene, c->sky);
+	const bool sky_fn = fn == 12 || fn == 13;
+	if (sky_fn && !(c->sky.t && c->sky_total > 0.0f)) return fail(c, MIRT_ERR_STATE, "debug_math fn %d reads the sky sampling table: mirt_set_sky_sampling(ctx, 1) over a scene whose table has a total above 0 first", fn);
+	if (fn == 14) hipLaunchKernelGGL(k_debug_ggx_pdf, dim3(grid_for(c, n)), dim3(kBlock), 0, c->stream, static_cast<uint32_t>(n), din.as<float>(), dout.as<float>());
+	else if (sky_fn) hipLaunchKernelGGL(k_debug_sky, dim3(grid_for(c, n)), dim3(kBlock), 0, c->stream, fn, static_cast<uint32_t>(n), din.as<float>(), dout.as<float>(), c->scene, c->sky);
 	else hipLaunchKernelGGL(k_debug_math, dim3(grid_for(c, n)), dim3(kBlock), 0, c->stream, fn, static_cast<uint32_t>(n), din.as<float>(), dout.as<float>());
 	hipError_t e = hipGetLastError();
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);

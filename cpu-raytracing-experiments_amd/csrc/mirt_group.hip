@@ -226,6 +226,11 @@ int mirt_group_set_sky_sampling(mirt_group* g, uint32_t on) {
 	FOR_MEMBERS_AND_FULL(g, "mirt_set_sky_sampling", mirt_set_sky_sampling(ctx, on));       // every member builds its own table, word for word the same (a fixed summation order)
 	return MIRT_OK;
 }
+int mirt_group_set_ggx_pdf(mirt_group* g, uint32_t on) {
+	if (!g) return MIRT_ERR_ARG;
+	FOR_MEMBERS_AND_FULL(g, "mirt_set_ggx_pdf", mirt_set_ggx_pdf(ctx, on));
+	return MIRT_OK;
+}
 int mirt_group_set_material_closures(mirt_group* g, const uint8_t* closure, uint32_t n) {
 	if (!g) return MIRT_ERR_ARG;
 	FOR_MEMBERS_AND_FULL(g, "mirt_set_material_closures", mirt_set_material_closures(ctx, closure, n));   // the gather context too: its first-hit AOV colour follows the table

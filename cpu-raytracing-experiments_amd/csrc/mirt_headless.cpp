@@ -5,7 +5,7 @@
 // environment map the way the constructor does (stbi_loadf(..., 4), Application.cpp:225-231); --ambient sets sky.ambient_color, which scales it.
 //
 //   mirt_headless --scene default9|furnace|bvh_test|brdf_test|synthetic:N [--size WxH] [--spp N | --frames N] [--bounces B] [--buckets K] [--brute] [--devices 0,1,..]
-//                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm] [--aov PREFIX] [--light-ris M] [--transmission] [--sky-sampling] [--closures 0,1,1,...]
+//                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm] [--aov PREFIX] [--light-ris M] [--transmission] [--sky-sampling] [--closures 0,1,1,...] [--ggx-pdf]
 //                 [--f-number F] [--focus-distance D] [--unit-mm U] [--focus-pixel X,Y]
 //                 [--until-noise T] [--noise-quantile Q] [--noise-floor F] [--check-every N] [--max-accumulations M] [--noise-out map.pfm]
 //                 [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm]
@@ -27,6 +27,7 @@
 // --light-ris M picks the NEE light among M uniform candidates by resampled importance sampling (mirt_set_light_ris; 0 = off, at most 32).
 // --transmission renders the materials that carry a transmission as glass: a smooth dielectric interface of index 1 + IOR_minus_one (mirt_set_transmission).
 // --sky-sampling makes the environment map (--hdri, --ambient) one more light of next event estimation, drawn by importance (mirt_set_sky_sampling).
+// --ggx-pdf gives the GGX closure its visible-normal pdf in the MIS weights: emitters and the sampled sky are weighed two ways on GGX surfaces (mirt_set_ggx_pdf).
 // --closures 0,1,1,... gives the closure per material, 0 Lambertian and 1 GGX, so that both kinds share a scene; materials beyond the list take --brdf (mirt_set_material_closures).
 // --aov PREFIX sums the first-hit AOVs beside the frame (mirt_set_aov) and writes PREFIX.depth.pfm (one channel, `Pf`), PREFIX.normal.pfm and
 // PREFIX.albedo.pfm (`PF`) after the last frame.
@@ -197,7 +198,7 @@ int main(int argc, char** argv) {
 	uint32_t check_every = 0, max_accumulations = 1000;
 	bool adaptive = false;
 	uint32_t min_accumulations = 0, light_ris = 0;
-	bool transmission = false, sky_sampling = false;
+	bool transmission = false, sky_sampling = false, ggx_pdf = false;
 	std::vector<uint8_t> closures;
 	std::string counts_out;
 	if (argc == 4 && std::string(argv[1]) == "--convert-hdr") {
@@ -216,12 +217,13 @@ int main(int argc, char** argv) {
 		if (a == "--help") {             // before any device is touched
 			std::puts("mirt_headless --scene default9|furnace|bvh_test|brdf_test|synthetic:N [--size WxH] [--spp N | --frames N] [--bounces B] [--buckets K] [--brute] [--devices 0,1,..]\n"
 			          "              [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm] [--aov PREFIX]\n"
-			          "              [--light-ris M] [--transmission] [--sky-sampling] [--closures 0,1,1,...]\n"
+			          "              [--light-ris M] [--transmission] [--sky-sampling] [--closures 0,1,1,...] [--ggx-pdf]\n"
 			          "              [--f-number F] [--focus-distance D] [--unit-mm U] [--focus-pixel X,Y]\n"
 			          "              [--until-noise T] [--noise-quantile Q] [--noise-floor F] [--check-every N] [--max-accumulations M] [--noise-out map.pfm]\n"
 			          "              [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm]\n"
 			          "mirt_headless --convert-hdr in.hdr out.hdr\n"
 			          "  --sky-sampling  the environment map (--hdri, --ambient) is one more light of next event estimation, drawn by importance (mirt_set_sky_sampling)\n"
+			          "  --ggx-pdf  the GGX closure's visible-normal pdf in the MIS weights: emitters and the sampled sky are weighed two ways on GGX surfaces (mirt_set_ggx_pdf)\n"
 			          "  --light-ris M   the NEE light is picked among M candidates by resampled importance sampling (mirt_set_light_ris)\n"
 			          "  --transmission  materials that carry a transmission render as glass (mirt_set_transmission)\n"
 			          "  --closures LIST the closure of material 0, 1, ...: 0 Lambertian, 1 GGX; materials beyond the list take --brdf (mirt_set_material_closures)");
@@ -243,6 +245,7 @@ int main(int argc, char** argv) {
 		else if (a == "--light-ris") light_ris = static_cast<uint32_t>(std::atoi(next()));
 		else if (a == "--transmission") transmission = true;
 		else if (a == "--sky-sampling") sky_sampling = true;
+		else if (a == "--ggx-pdf") ggx_pdf = true;
 		else if (a == "--closures") { for (const char* p = next(); *p;) { const int v = std::atoi(p); closures.push_back(static_cast<uint8_t>(v < 0 || v > 255 ? 255 : v)); while (*p && *p != ',') p++; if (*p == ',') p++; } }
 		else if (a == "--f-number") { f_number = static_cast<float>(std::atof(next())); lens = true; }
 		else if (a == "--focus-distance") { focus_distance = static_cast<float>(std::atof(next())); lens = true; }
@@ -282,6 +285,7 @@ int main(int argc, char** argv) {
 		renderer.SetLightRis(light_ris);
 		renderer.SetTransmission(transmission);
 		renderer.SetSkySampling(sky_sampling);
+		renderer.SetGgxPdf(ggx_pdf);
 		renderer.SetMaterialClosures(closures);
 		// pad the viewport to the tile requirement like UIRender does (Application.cpp:365-372)
 		const uint32_t t = static_cast<uint32_t>(Renderer::RequiredTiling());

@@ -197,6 +197,10 @@ public:
 	// The environment map as one more light of next event estimation (mirt.h, mirt_set_sky_sampling): off by default, as in the reference, where the
 	// sky is met by extension rays only.  Same expectation, so the accumulator is not reset.  Not in exact stream order.
 	void SetSkySampling(bool on) { check(mirt_group_set_sky_sampling(group_, on ? 1u : 0u), "mirt_group_set_sky_sampling"); }
+	// The GGX closure's pdf in the MIS weights (mirt.h, mirt_set_ggx_pdf): off by default, as in the reference, whose Closure<GGX>::pdf returns 0.
+	// On: emitters and (under sky sampling) the sky are weighed two ways on GGX surfaces.  Formally another estimator: Reset() is the caller's to call.
+	// Not in exact stream order.
+	void SetGgxPdf(bool on) { check(mirt_group_set_ggx_pdf(group_, on ? 1u : 0u), "mirt_group_set_ggx_pdf"); }
 	// Per-material closures (mirt.h, mirt_set_material_closures): closure[m] = 0 (Lambertian) or 1 (GGX) for material m; an empty table (the default)
 	// leaves every material on policy.brdf, as do the materials beyond its end.  Another estimand: Reset() is the caller's to call.  Not in exact stream order.
 	void SetMaterialClosures(const std::vector<uint8_t>& closure) {

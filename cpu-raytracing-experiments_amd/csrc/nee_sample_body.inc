@@ -7,6 +7,7 @@
 // drawn).  Estimator: f L w(p~) / (sel q), with w the power heuristic of sel p~ against the closure's pdf — powerHeuristic_over_f gives w / (sel p~),
 // times p~ / q (1.0f exactly wherever the two cells agree).  L x f is sky_eval(Ld).rgb x (thr.r x f.r): Q10 carried over, the miss shader's
 // red-channel throughput on all three channels, so that the expectation is the plain path's.  One shadow ray, tfar = FLT_MAX.
+// PDF (mirt_set_ggx_pdf): a GGX hit's closure pdf in both power heuristics is ggx_pdf(alpha, Ll, Vl) instead of 0; light RIS reads nothing new (its weights come from rad).
 if (SKY && selected == static_cast<int32_t>(fp.n_lights)) {
 	do {
 		float sky_q; uint32_t srow, scol;
@@ -20,7 +21,7 @@ if (SKY && selected == static_cast<int32_t>(fp.n_lights)) {
 		const float k = thr.x * fx;
 		f3 rad{ Le.x * k, Le.y * k, Le.z * k };
 		const float sky_p = sky_pdf(sc, sky, Ld.x, Ld.y, Ld.z, srow, scol);
-		const float brdf_pdf = ggx_hit ? 0.0f : MIRT_INV_PI * max_sel(0.0f, Ll.z);
+		const float brdf_pdf = ggx_hit ? (PDF ? ggx_pdf(alpha, Ll, Vl) : 0.0f) : MIRT_INV_PI * max_sel(0.0f, Ll.z);   // PDF: mirt_set_ggx_pdf
 		const float w = powerHeuristic_over_f(light_selection_pdf * sky_p, brdf_pdf) * (sky_p / sky_q);
 		rad.x *= w; rad.y *= w; rad.z *= w;
 		if (max_sel(max_sel(rad.x, rad.y), rad.z) <= 0.0f) break;
@@ -55,7 +56,7 @@ do {
 		rad.x *= alb.x * f; rad.y *= alb.y * f; rad.z *= alb.z * f;
 	}
 	lpdf *= light_selection_pdf;
-	const float brdf_pdf = ggx_hit ? 0.0f : MIRT_INV_PI * max_sel(0.0f, Ll.z);  // DataStreams.hpp:173-176 / :196-198
+	const float brdf_pdf = ggx_hit ? (PDF ? ggx_pdf(alpha, Ll, Vl) : 0.0f) : MIRT_INV_PI * max_sel(0.0f, Ll.z);  // DataStreams.hpp:173-176 / :196-198 (0, "TODO"); PDF: mirt_set_ggx_pdf
 	const float w = powerHeuristic_over_f(lpdf, brdf_pdf);
 	rad.x *= w; rad.y *= w; rad.z *= w;
 	if (max_sel(max_sel(rad.x, rad.y), rad.z) <= 0.0f) break;

@@ -11,7 +11,10 @@
 //                       transmissive material can take the dielectric interface below, mirt_set_transmission; false: none of that text is compiled in);
 //                       SKY (true: the environment map is light number n_lights of next event estimation, mirt_set_sky_sampling — the scope then
 //                       provides sky (SkyTable) and a light_selection_pdf of 1 / (n_lights + 1), and gets miss_w (float) written with survive: the
-//                       MIS weight the miss shader gives thr.r x sky should ndir miss; false: none of that text is compiled in)
+//                       MIS weight the miss shader gives thr.r x sky should ndir miss; false: none of that text is compiled in);
+//                       PDF (true: mirt_set_ggx_pdf — a GGX hit's closure pdf is ggx_pdf(alpha, L, Vl) where it is 0 otherwise: in next event estimation's
+//                       two heuristics and in miss_w; the scope gets pdf_out (float) written with survive, the pdf_in of the bounce that will shade
+//                       ndir, and itself passes as pdf_in what the sampling bounce left there; false: none of that text is compiled in)
 //   read                sc, fp, s_albedo, s_emission (the material tables in LDS), bounce, gloss_decay, light_selection_pdf,
 //                       pdf_in (out->pdf of the bounce that sampled D, Q8), hrec (HitRec), prim (= hrec.prim), D (f3);
 //                       GLASS only: s_glass (LDS, {transmission.rgb, 1 + IOR_minus_one} per material) and after_interface (bool: D was sampled
@@ -152,12 +155,21 @@ if (is_emissive) {
 		ndir = to_world(T, sd);
 		if (GLASS && interface) { ndir = sd; via_interface = true; }
 		if (MIXED) sampled_ggx = ggx_hit;                           // Q8: pdf_in of an emitter this ray hits belongs to the closure that sampled it
+		if (PDF) {
+			// mirt_set_ggx_pdf: the pdf_in of the next bounce travels with the ray.  A GGX hit: p~ of sd, from THIS hit's alpha and Vl — nothing of it
+			// can be recomputed from ndir.  A Lambertian hit: Q8's word, (1 / pi) max(0, world z) of ndir as stored, the bits the next bounce would
+			// recompute.  An interface: never read (after_interface makes the weight 1).
+			if (GLASS && interface) pdf_out = 0.0f;
+			else if (ggx_hit) pdf_out = ggx_pdf(alpha, sd, Vl);
+			else pdf_out = MIRT_INV_PI * max_sel(0.0f, ndir.z);
+		}
 		if (SKY) {
 			// What the miss shader may keep of thr.r x sky: the power heuristic of the closure's pdf of sd — the LOCAL one: next event estimation
 			// weighs against that, and Q8's world-z pdf_in would break the partition of unity — against sel x the sky's density of ndir.
-			// An interface is a delta closure (no light sample meets it): 1.  Closure<GGX>::pdf is 0: 0, as for the emitters such a ray hits.
+			// An interface is a delta closure (no light sample meets it): 1.  Closure<GGX>::pdf is 0: 0, as for the emitters such a ray hits —
+			// unless PDF (mirt_set_ggx_pdf): then the heuristic of p~, as for those emitters too.
 			if (GLASS && interface) miss_w = 1.0f;
-			else if (ggx_hit) miss_w = 0.0f;
+			else if (ggx_hit) { uint32_t prow, pcol; miss_w = PDF ? powerHeuristic(pdf_out, light_selection_pdf * sky_pdf(sc, sky, ndir.x, ndir.y, ndir.z, prow, pcol)) : 0.0f; }   // PDF: next event estimation weighs against the same p~
 			else { uint32_t prow, pcol; miss_w = powerHeuristic(MIRT_INV_PI * max_sel(0.0f, sd.z), light_selection_pdf * sky_pdf(sc, sky, ndir.x, ndir.y, ndir.z, prow, pcol)); }
 		}
 		survive = true;

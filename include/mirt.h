@@ -311,6 +311,36 @@ int mirt_get_material_closures(const mirt_ctx* ctx, uint8_t* closure_out, uint32
 int mirt_set_sky_sampling(mirt_ctx* ctx, uint32_t on);
 int mirt_get_sky_sampling(const mirt_ctx* ctx, uint32_t* on);
 
+/* ---- the GGX closure's pdf: two-way MIS for emitters and the sky on GGX surfaces ----------------------------------------------------
+ * Closure<GGX>::pdf returns 0 in the reference ("TODO", DataStreams.hpp:196-198), and so it does here by default: on a GGX surface a ray the
+ * closure sampled weighs powerHeuristic(0, .) = 0 at the emitter it hits — and, under sky sampling, at the sky it misses into — so every photon
+ * arrives through next event estimation alone, weighted 1 / light_pdf.  On a low-roughness lobe that is the firefly case MIS exists for.
+ * on = 1: wherever a hit is shaded by Closure<GGX> (policy.brdf = 1, or the material's closure under mirt_set_material_closures) the closure's
+ * pdf is, in binary32 on local-frame vectors (normal = +z),
+ *     p~(alpha, L, V) = (L.z > 0 && V.z > 0 && H.z > 0) ? G1_GGX(alpha^2, V.z^2) GGX_D(max(1e-5, alpha^2), H.z^2) / (4 V.z) : 0,   H = normalize(L + V)
+ *   — Heitz 2018 eq. 17 with the D-floor microfacet_brdf already applies; float64 statement: tests/definitions.py ggx_vndf_pdf_of_direction.
+ *   A V.z whose square underflows counts as V.z = 0.  Three places read it, and nothing else changes:
+ *   1. next event estimation, sphere lights and the sky row: the closure pdf in the light sample's power heuristic is p~(alpha, Ll, Vl).  Light
+ *      RIS reads nothing new (its weights come from the weighted radiance).
+ *   2. the emitter hit: pdf_in of a ray that a GGX hit sampled is p~(alpha, sampled direction, Vl) of THAT hit.  It travels with the ray, in a
+ *      4-byte plane per ray stream that is allocated only while the switch is on (the automatic batch plan counts it).  A Lambertian-sampled ray
+ *      keeps Q8's word, (1 / pi) max(0, D.z) in world z, bit for bit; after a dielectric interface the weight stays 1.
+ *   3. under sky sampling, the miss weight of a ray a GGX hit sampled: powerHeuristic(p~, sel x sky_pdf(dir)) instead of 0.
+ *   p~ is a function of the direction alone and all three evaluate it, so each pair of MIS weights adds to one — the sky_pdf argument above —
+ *   although the reference's sampler (turned axes and a clamp: DESIGN.md D7) is not exactly the visible-normal density, and also at alpha = 0,
+ *   where the floor makes p~ large and finite: the mirror needs no special case.
+ * The closure's sample, its estimator F G2 / G1, its eval, the roulette and the traversal read nothing new: rays, terminated and dropped are
+ * word for word those of the switch off; shadow_rays may differ (a light sample whose weighted radiance rounds to 0 casts no ray).  The
+ * estimand moves only by what the heuristic's 1e-6 floor and D7 allow, but it is formally another estimator, and the accumulator is NOT
+ * reset: the caller does that (mirt_reset).
+ * on = 0 (the default): the same device code as a context that never called this.  on = 1 while no material of the current scene ends up
+ * GGX (policy.brdf = 0 without a table, or a table that makes every material Lambertian): that same code too.  on > 1: MIRT_ERR_ARG.  Exact
+ * stream order and the switch exclude each other: MIRT_ERR_STATE both ways.  Deferred mirt_accumulate_async calls are launched first, under the
+ * old setting.  Combines with the lens, frozen tiles, light RIS, transmission, sky sampling, per-material closures, AOVs, the noise estimate
+ * and groups; the camera-ray candidate lists stay valid. */
+int mirt_set_ggx_pdf(mirt_ctx* ctx, uint32_t on);
+int mirt_get_ggx_pdf(const mirt_ctx* ctx, uint32_t* on);
+
 /* Renderer::Resize, Renderer.hpp:53-63: h_tiles = w/16, v_tiles = h/16 (truncating), allocates and zeroes
  * the accumulator, accumulations = 0.  Owns all tiles until mirt_set_tile_range says otherwise. */
 int mirt_resize(mirt_ctx* ctx, uint32_t width, uint32_t height);
@@ -526,6 +556,7 @@ int mirt_group_set_lens(mirt_group* group, float aperture_radius, float focus_de
 int mirt_group_set_light_ris(mirt_group* group, uint32_t candidates);             /* mirt_set_light_ris on every member */
 int mirt_group_set_transmission(mirt_group* group, uint32_t on);                   /* mirt_set_transmission on every member (and the gather context) */
 int mirt_group_set_sky_sampling(mirt_group* group, uint32_t on);                   /* mirt_set_sky_sampling on every member (and the gather context) */
+int mirt_group_set_ggx_pdf(mirt_group* group, uint32_t on);                        /* mirt_set_ggx_pdf on every member (and the gather context) */
 int mirt_group_set_material_closures(mirt_group* group, const uint8_t* closure, uint32_t n);   /* mirt_set_material_closures on every member (and the gather context) */
 int mirt_group_pick_focus(mirt_group* group, uint32_t x, uint32_t y, float* distance, float* depth);   /* mirt_pick_focus on the first member */
 int mirt_group_set_policy(mirt_group* group, const mirt_policy* policy);
@@ -597,6 +628,7 @@ int mirt_debug_trace_shadow(mirt_ctx* ctx, size_t n, const float* p_xyz, const f
  *                                                           out: dir.x, dir.y, dir.z (local), F, reflected (0 / 1), tir (0 / 1)   (6n)
  *    12 sky_sample (kernels.hpp; mirt_set_sky_sampling on over a scene, else MIRT_ERR_STATE)   in: u0[n], u1[n]   out: dir.x, dir.y, dir.z, q, row, column (6n; row and column as floats)
  *    13 sky_pdf    (likewise)                                                                   in: dir.x[n], dir.y[n], dir.z[n]   out: p~, row, column (3n)
+ *    14 ggx_pdf    (device_math.hpp; mirt_set_ggx_pdf — needs no switch)                         in: alpha[n], Llocal(3n), Vlocal(3n)   out: p~ (n)
  *       (8, 9: the defined part of the reference's compiled-out GGX closure; not used by the path — DESIGN.md §7)
  */
 int mirt_debug_math(mirt_ctx* ctx, int fn, size_t n, const float* in, float* out);

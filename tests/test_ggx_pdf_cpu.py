@@ -1,0 +1,122 @@
+"""mirt_set_ggx_pdf, the float64 side (no backend): what definitions.ggx_vndf_pdf_of_direction integrates to, and the guards that make the GPU tests
+of test_ggx_pdf_gpu.py tests — from definitions.path_sampler and g1_expectation alone.
+ 1  normalisation by two independent quadratures;   2  the guards of GPU tests 4 - 6;   3  the interface is declared in every layer."""
+import os
+import re
+
+import numpy as np
+
+import definitions as df
+import ggx_pdf_definitions as gp
+import test_definitions_cpu as cpu
+from test_definitions_cpu import ggx_scene, g1_expectation, g_sampler, f_regions, region_stats, SIGMA, G1_ACC, G2_ACC, G2_REF, F_W, F_H, HIGH, DIFFUSE, G_DECAY, report
+
+# ---- what the GPU tests run with (imported there) -----------------------------------------------------------------------------------
+LOW_ROUGH = 0.3                           # test 5's cap: alpha = 0.09.  Sampler ratio of per-path variances zero / vndf: 9.0 (0.2 gives 57, 0.15 gives 219)
+LOW_ROUGH_RATIO = 4.0                     # what the issue asks of that ratio at least
+LOW_ACC, LOW_REF = 200, 60                # accumulations of the backend; paths a pixel of the float64 sampler (both estimators, seed 77)
+LOW_BOUNCES = 3
+
+
+def low_samplers():
+    return {k: gp.rough_sampler(LOW_ROUGH, [HIGH], LOW_BOUNCES, LOW_REF, 77, k) for k in ("zero", "vndf")}
+
+
+# ---- 1 ------------------------------------------------------------------------------------------------------------------------------
+def test_normalisation():
+    """For alpha in {0.02, 0.1, 0.3, 0.7, 1} and V at 0, 45 and 80 degrees from the normal: the pdf's integral over the directions L (a polar grid
+    about the mirror direction) is at most 1 and equals 1 minus the mass the visible-normal density puts on normals whose reflection falls at or
+    below the surface (a polar grid about the normal; its own total is 1).  Tolerance QUAD_TOL = 1e-3, set by doubling: at QUAD_N = 768 x 384
+    doubling both ways moves none of the 45 sums by more than a tenth of it (measured: 8.7e-5, the lost mass at alpha = 1, 80 degrees).
+    The lost mass is no rounding matter: 0.04 % at alpha = 0.02 and half of everything at alpha = 1 seen along the normal — the closure's
+    estimator gives those samples weight 0 (L.z <= 0), the pdf gives those directions density 0."""
+    worst_move, worst_gap, rows = 0.0, 0.0, []
+    double = (2 * gp.QUAD_N[0], 2 * gp.QUAD_N[1])
+    for alpha in gp.ALPHAS:
+        for deg in gp.VIEW_DEGREES:
+            V = gp.view(deg)
+            mass, (total, lost) = gp.pdf_mass_over_directions(alpha, V), gp.vndf_mass_over_normals(alpha, V)
+            mass2, (total2, lost2) = gp.pdf_mass_over_directions(alpha, V, double), gp.vndf_mass_over_normals(alpha, V, double)
+            worst_move = max(worst_move, abs(mass2 - mass), abs(total2 - total), abs(lost2 - lost))
+            worst_gap = max(worst_gap, abs(mass - (1.0 - lost)))
+            rows.append((alpha, deg, mass, lost))
+            assert mass <= 1.0 + gp.QUAD_TOL, (alpha, deg, mass)
+            assert abs(total - 1.0) <= gp.QUAD_TOL, (alpha, deg, total)
+            assert abs(mass - (1.0 - lost)) <= gp.QUAD_TOL, (alpha, deg, mass, lost)
+    report("ggx_pdf/normalisation", grid=gp.QUAD_N, worst_move_on_doubling=worst_move, worst_gap=worst_gap,
+           mass="; ".join(f"a={a} {d:.0f}deg {m:.4f}" for a, d, m, _ in rows))
+    assert worst_move <= gp.QUAD_TOL / 10.0, worst_move
+    assert min(l for *_, l in rows) > 0.0 and max(l for *_, l in rows) > 0.4
+
+
+def test_pdf_guards_and_mirror():
+    """The definition's own edges in float64: 0 for L at or below the surface; at alpha = 0 the floor on D's alpha^2 keeps the value finite,
+    1 / (4 pi 1e-5 V.z) along the mirror direction (G1 = 1), so the mirror needs no special case."""
+    V = gp.view(30.0)[None, :]
+    L = np.array([[0.3, 0.1, -0.2], [1.0, 0.0, 0.0]]); L /= np.linalg.norm(L, axis=1, keepdims=True)
+    assert (df.ggx_vndf_pdf_of_direction(0.3, L, np.repeat(V, 2, axis=0)) == 0.0).all()
+    mirror = V * np.array([-1.0, -1.0, 1.0])
+    got = float(df.ggx_vndf_pdf_of_direction(0.0, mirror, V)[0])
+    assert np.isfinite(got) and abs(got * 4.0 * np.pi * 1e-5 * V[0, 2] - 1.0) < 1e-9
+
+
+# ---- 2 ------------------------------------------------------------------------------------------------------------------------------
+def test_gpu_test_guards():
+    """What makes tests 4 - 6 of test_ggx_pdf_gpu.py tests, from path_sampler and g1_expectation alone.
+      G1 at G1_ACC = 100 accumulations: the "vndf" and "zero" expectations lie at least 2 SIGMA apart in some region (measured 101: DESIGN.md
+        section 2, row G1) — the render with the switch on cannot meet the one and the render with it off the other by chance.
+      G2 at G2_ACC / G2_REF = 190 / 760, the counts test_ggx_bounces runs with: under the gloss-decay table the two samplers lie more than SIGMA
+        apart (6.7 standard errors), so a render that meets the one misses the other; the margin of 2 SIGMA is G1's alone.
+      The low-roughness cap, roughness LOW_ROUGH = 0.3 under HIGH at max_bounces = 3: the sampler's per-path variance under "zero" is at least
+        LOW_ROUGH_RATIO = 4 times that under "vndf" (measured 9.0), and the two expectations agree within SIGMA of the samplers' own error.
+      The sampler meets its own quadrature with "vndf", in the manner of test_ggx_sampler_meets_the_quadrature."""
+    regs, figures = f_regions("F1_high"), {}
+    zero, vndf = g1_expectation(), g1_expectation(closure_pdf="vndf")
+    figures["G1_apart"] = max(float((np.abs(region_stats(vndf, m, G1_ACC)[0] - region_stats(zero, m, G1_ACC)[0]) / region_stats(zero, m, G1_ACC)[1]).max()) for m in regs.values())
+    assert figures["G1_apart"] >= 2 * SIGMA
+    for label, mask in regs.items():                                                 # the expectation test 4 holds the switch-on render to has a usable error bar
+        want, se = region_stats(vndf, mask, G1_ACC)
+        assert (want > 0).all() and (se / want < 0.01).all(), (label, se / want)
+    assert (vndf["shadow"] == 1.0).all()
+    assert np.array_equal(vndf["survive"], zero["survive"]) and np.array_equal(vndf["drop"], zero["drop"])      # the closure sample reads nothing new
+    ref = g_sampler([HIGH], (), 2, 40, 2031, closure_pdf="vndf")
+    for label, mask in regs.items():
+        k = mask.reshape(-1)
+        z = (ref["E"][k].mean(axis=0) - vndf["E"][k].mean(axis=0)) / (np.sqrt(ref["var"][k].sum(axis=0) / 40) / k.sum())
+        report(f"ggx_pdf/sampler/G1/{label}", z="/".join(f"{v:+.2f}" for v in z))
+        assert np.abs(z).max() <= SIGMA, (label, z)
+    diffuse = [(DIFFUSE[0], DIFFUSE[1], (cpu.G_DIFFUSE_F0, cpu.G_DIFFUSE_ROUGH))]
+    on, off = g_sampler([HIGH], diffuse, 4, G2_REF, 4343, decay=G_DECAY, closure_pdf="vndf"), g_sampler([HIGH], diffuse, 4, G2_REF, 4343, decay=G_DECAY)
+    far = 0.0
+    for mask in regs.values():
+        k = mask.reshape(-1)
+        se = np.sqrt(on["var"][k].sum(axis=0) * (1.0 / G2_ACC + 1.0 / G2_REF)) / k.sum()
+        far = max(far, float((np.abs(off["E"][k].mean(axis=0) - on["E"][k].mean(axis=0)) / se).max()))
+    figures["G2_apart"] = far                                                        # measured 6.7: beyond SIGMA, short of the 2 SIGMA that G1 has — G1 is the frame that tells the two apart
+    assert far > SIGMA
+    low = low_samplers()
+    figures["low_var_zero"], figures["low_var_vndf"] = float(low["zero"]["var"].mean()), float(low["vndf"]["var"].mean())
+    figures["low_ratio"] = figures["low_var_zero"] / figures["low_var_vndf"]
+    assert figures["low_ratio"] >= LOW_ROUGH_RATIO
+    for label, mask in regs.items():
+        k = mask.reshape(-1)
+        se = np.sqrt((low["zero"]["var"][k].sum(axis=0) + low["vndf"]["var"][k].sum(axis=0)) / LOW_REF) / k.sum()
+        z = (low["vndf"]["E"][k].mean(axis=0) - low["zero"]["E"][k].mean(axis=0)) / se
+        figures[f"low_z_{label}"] = "/".join(f"{v:+.2f}" for v in z)
+        assert np.abs(z).max() <= SIGMA, (label, z)
+    assert LOW_ACC <= 200 and LOW_ACC % 5 == 0 and G1_ACC <= 200 and G2_ACC <= 200
+    report("ggx_pdf/guards", **figures)
+
+
+# ---- 3 ------------------------------------------------------------------------------------------------------------------------------
+def test_interface_is_declared_in_every_layer(mirt):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "mirt.h")).read()
+    for name in ("mirt_set_ggx_pdf", "mirt_get_ggx_pdf", "mirt_group_set_ggx_pdf"):
+        assert re.search(r"\bint " + name + r"\(", header), name
+    assert "SetGgxPdf" in open(os.path.join(mirt.CSRC, "mirt_host.hpp")).read()
+    assert "--ggx-pdf" in open(os.path.join(mirt.CSRC, "mirt_headless.cpp")).read()
+    for cls in (mirt.Renderer, mirt.GroupRenderer):
+        assert callable(getattr(cls, "set_ggx_pdf")) and callable(getattr(cls, "ggx_pdf"))
+    kernels = open(os.path.join(mirt.CSRC, "kernels.hpp")).read()
+    assert "static_assert(!PDF || GGX || MIXED" in kernels
