@@ -1526,14 +1526,37 @@ MIRT_DI uint32_t block_compact(bool flag, uint32_t value, uint32_t* scratch, uin
 // as `in` is; nullptr without the switch): written with the survivor, read back as pdf_in in phase 2
 // (a Lambertian-sampled ray stores Q8's word there, the bits it would otherwise recompute).  The closure sample, its estimator and the roulette
 // read nothing new.  PDF = false names neither ggx_pdf nor the plane, and is the text as it was.  The same launch bounds.
+//
+// ShadeForm: k_shade's nine template arguments as one value, in their order — what the host decides per launch (mirt_capi.hip shade_form) and
+// looks up in its table of instantiations (shade_kernel).  valid() is the one statement of which combinations exist: 5 bounce forms (later
+// bounce; bounce 0, with the lens, with frozen tiles, with both) x 8 of (RIS, GLASS, SKY) x 5 of closure and pdf (Lambertian, GGX, MIXED, GGX + PDF,
+// MIXED + PDF).  A new switch is one more member, one more bit and, if it cannot stand alone, one more term of valid().
+struct ShadeForm {
+	bool first, ggx, lens, sparse, ris, glass, sky, mixed, pdf;
+	static constexpr uint32_t kBits = 9u;
+	constexpr uint32_t bits() const {
+		return uint32_t(first) | uint32_t(ggx) << 1 | uint32_t(lens) << 2 | uint32_t(sparse) << 3 | uint32_t(ris) << 4 | uint32_t(glass) << 5 | uint32_t(sky) << 6 | uint32_t(mixed) << 7 | uint32_t(pdf) << 8;
+	}
+	static constexpr ShadeForm from_bits(uint32_t b) {
+		return ShadeForm{ (b & 1u) != 0, (b >> 1 & 1u) != 0, (b >> 2 & 1u) != 0, (b >> 3 & 1u) != 0, (b >> 4 & 1u) != 0, (b >> 5 & 1u) != 0, (b >> 6 & 1u) != 0, (b >> 7 & 1u) != 0, (b >> 8 & 1u) != 0 };
+	}
+	constexpr bool valid() const { return (!(lens || sparse) || first) && !(mixed && ggx) && (!pdf || ggx || mixed); }
+};
+constexpr uint32_t shade_forms_valid() {
+	uint32_t n = 0;
+	for (uint32_t b = 0; b < (1u << ShadeForm::kBits); b++) n += ShadeForm::from_bits(b).valid() && ShadeForm::from_bits(b).bits() == b;
+	return n;
+}
+static_assert(shade_forms_valid() == 200u, "k_shade has 5 bounce forms x 8 of (RIS, GLASS, SKY) x 5 of closure and pdf = 200 instantiations");
 template <bool FIRST, bool GGX, bool LENS = false, bool SPARSE = false, bool RIS = false, bool GLASS = false, bool SKY = false, bool MIXED = false, bool PDF = false>
 __global__ __launch_bounds__(kShadeBlock, 6) void k_shade(SceneDev sc, FrameParams fp, StreamBuf in, const HitRec* __restrict__ hit_in, StreamBuf out, ShadowBuf sh, uint32_t bounce,
                                                   Queue in_queue, Queue next_queue, Queue shadow_queue, float* __restrict__ contrib, DevCounters* ctr,
                                                   const float4* __restrict__ mat_ggx, float gloss_decay, LensParams lens, uint32_t ris_m, const uint32_t* __restrict__ tile_frozen, SkyTable sky,
                                                   unsigned long long closure_mask, const float* __restrict__ pdf_plane_in, float* __restrict__ pdf_plane_out) {
-	static_assert(!(LENS || SPARSE) || FIRST, "the lens and the frozen tiles concern bounce 0 only");
-	static_assert(!(MIXED && GGX), "MIXED takes the closure from the material: it is instantiated with GGX = false");
-	static_assert(!PDF || GGX || MIXED, "the GGX pdf concerns hits that Closure<GGX> shades: the all-Lambertian form has no PDF instantiation");
+	static_assert(ShadeForm{ FIRST, GGX, LENS, SPARSE, RIS, GLASS, SKY, MIXED, PDF }.valid(),
+	              "the lens and the frozen tiles concern bounce 0 only; "
+	              "MIXED takes the closure from the material: it is instantiated with GGX = false; "
+	              "the GGX pdf concerns hits that Closure<GGX> shades: the all-Lambertian form has no PDF instantiation");
 	const QueueView qin = FIRST ? queue_identity(fp.n_pix * fp.batch_n) : queue_view(in_queue);
 	const uint32_t n = qin.pre[kSegs];
 	const uint32_t n_chunks = (fp.n_pix + kShadeBlock - 1u) / kShadeBlock;      // FIRST

@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 using namespace mirt;
@@ -583,84 +584,43 @@ auto primary_hits_kernel(bool count, bool wave, bool sparse) {      // wave: one
 		{ { k_primary_hits<true, true>, k_primary_hits<false, true> }, { k_primary_hits_wave<true, true>, k_primary_hits_wave<false, true> } } };
 	return table[sparse][wave][!count];
 }
-// glass = mirt_set_transmission while the scene has a transmissive material: the same table over the GLASS instantiations.
-auto shade_kernel(bool first, bool ggx, bool lens, bool sparse, bool ris, bool glass) {      // lens and sparse concern bounce 0 (first) only
-	static const decltype(&k_shade<false, false>) glass_table[2][2][2][3] = {    // [ris][sparse][ggx][first ? 1 + lens : 0]
-		{ { { k_shade<false, false, false, false, false, true>, k_shade<true, false, false, false, false, true>, k_shade<true, false, true, false, false, true> },
-		    { k_shade<false, true, false, false, false, true>, k_shade<true, true, false, false, false, true>, k_shade<true, true, true, false, false, true> } },
-		  { { nullptr, k_shade<true, false, false, true, false, true>, k_shade<true, false, true, true, false, true> }, { nullptr, k_shade<true, true, false, true, false, true>, k_shade<true, true, true, true, false, true> } } },
-		{ { { k_shade<false, false, false, false, true, true>, k_shade<true, false, false, false, true, true>, k_shade<true, false, true, false, true, true> },
-		    { k_shade<false, true, false, false, true, true>, k_shade<true, true, false, false, true, true>, k_shade<true, true, true, false, true, true> } },
-		  { { nullptr, k_shade<true, false, false, true, true, true>, k_shade<true, false, true, true, true, true> }, { nullptr, k_shade<true, true, false, true, true, true>, k_shade<true, true, true, true, true, true> } } } };
-	if (glass) return glass_table[ris][first && sparse][ggx][first ? 1 + lens : 0];
-	static const decltype(&k_shade<false, false>) table[2][2][2][3] = {    // [ris][sparse][ggx][first ? 1 + lens : 0]
-		{ { { k_shade<false, false>, k_shade<true, false>, k_shade<true, false, true> }, { k_shade<false, true>, k_shade<true, true>, k_shade<true, true, true> } },
-		  { { nullptr, k_shade<true, false, false, true>, k_shade<true, false, true, true> }, { nullptr, k_shade<true, true, false, true>, k_shade<true, true, true, true> } } },
-		{ { { k_shade<false, false, false, false, true>, k_shade<true, false, false, false, true>, k_shade<true, false, true, false, true> },
-		    { k_shade<false, true, false, false, true>, k_shade<true, true, false, false, true>, k_shade<true, true, true, false, true> } },
-		  { { nullptr, k_shade<true, false, false, true, true>, k_shade<true, false, true, true, true> }, { nullptr, k_shade<true, true, false, true, true>, k_shade<true, true, true, true, true> } } } };
-	return table[ris][first && sparse][ggx][first ? 1 + lens : 0];
+// k_shade: every instantiation there is, generated from ShadeForm::valid() (kernels.hpp) and indexed by ShadeForm::bits(); a form that does not
+// exist is never instantiated and is nullptr (launch_batch refuses it).  The pack names the instantiations in the order of their bits, FIRST the
+// least significant: with this order the device code of all 251 kernels of this file is what it was under the hand-written tables
+// (profiles/shade_form_table.txt; compare again with profiles/compare_kernels.py when a bit is added, the order of first naming has moved hipcc's
+// register assignment before — see the trace tables above).
+using ShadeKernel = decltype(&k_shade<false, false>);
+template <uint32_t BITS>
+constexpr ShadeKernel shade_entry() {
+	constexpr ShadeForm f = ShadeForm::from_bits(BITS);
+	if constexpr (f.valid()) return &k_shade<f.first, f.ggx, f.lens, f.sparse, f.ris, f.glass, f.sky, f.mixed, f.pdf>;
+	else return nullptr;
 }
-// sky = mirt_set_sky_sampling while sky_active(): the same table once more, over the SKY instantiations (named after every older one, above).
-template <bool RIS, bool GLASS>
-auto shade_kernel_sky_of(bool first, bool ggx, bool lens, bool sparse) {
-	static const decltype(&k_shade<false, false>) table[2][2][3] = {       // [sparse][ggx][first ? 1 + lens : 0]
-		{ { k_shade<false, false, false, false, RIS, GLASS, true>, k_shade<true, false, false, false, RIS, GLASS, true>, k_shade<true, false, true, false, RIS, GLASS, true> },
-		  { k_shade<false, true, false, false, RIS, GLASS, true>, k_shade<true, true, false, false, RIS, GLASS, true>, k_shade<true, true, true, false, RIS, GLASS, true> } },
-		{ { nullptr, k_shade<true, false, false, true, RIS, GLASS, true>, k_shade<true, false, true, true, RIS, GLASS, true> },
-		  { nullptr, k_shade<true, true, false, true, RIS, GLASS, true>, k_shade<true, true, true, true, RIS, GLASS, true> } } };
-	return table[first && sparse][ggx][first ? 1 + lens : 0];
+template <uint32_t... BITS>
+ShadeKernel shade_kernel(ShadeForm f, std::integer_sequence<uint32_t, BITS...>) {
+	static const ShadeKernel table[] = { shade_entry<BITS>()... };
+	return table[f.bits()];
 }
-auto shade_kernel_sky(bool first, bool ggx, bool lens, bool sparse, bool ris, bool glass) {
-	return ris ? (glass ? shade_kernel_sky_of<true, true>(first, ggx, lens, sparse) : shade_kernel_sky_of<true, false>(first, ggx, lens, sparse))
-	           : (glass ? shade_kernel_sky_of<false, true>(first, ggx, lens, sparse) : shade_kernel_sky_of<false, false>(first, ggx, lens, sparse));
-}
-// mixed = mirt_set_material_closures while closure_plan() says so: the MIXED instantiations (GGX = false), over the reachable forms — five of
-// [sparse][first ? 1 + lens : 0], times RIS, GLASS and SKY.  Named after every older instantiation, above, so that those keep their device code.
-template <bool RIS, bool GLASS, bool SKY>
-auto shade_kernel_mixed_of(bool first, bool lens, bool sparse) {
-	static const decltype(&k_shade<false, false>) table[2][3] = {          // [sparse][first ? 1 + lens : 0]
-		{ k_shade<false, false, false, false, RIS, GLASS, SKY, true>, k_shade<true, false, false, false, RIS, GLASS, SKY, true>, k_shade<true, false, true, false, RIS, GLASS, SKY, true> },
-		{ nullptr, k_shade<true, false, false, true, RIS, GLASS, SKY, true>, k_shade<true, false, true, true, RIS, GLASS, SKY, true> } };
-	return table[first && sparse][first ? 1 + lens : 0];
-}
-auto shade_kernel_mixed(bool first, bool lens, bool sparse, bool ris, bool glass, bool sky) {
-	switch ((ris ? 4 : 0) | (glass ? 2 : 0) | (sky ? 1 : 0)) {
-	case 0: return shade_kernel_mixed_of<false, false, false>(first, lens, sparse);
-	case 1: return shade_kernel_mixed_of<false, false, true>(first, lens, sparse);
-	case 2: return shade_kernel_mixed_of<false, true, false>(first, lens, sparse);
-	case 3: return shade_kernel_mixed_of<false, true, true>(first, lens, sparse);
-	case 4: return shade_kernel_mixed_of<true, false, false>(first, lens, sparse);
-	case 5: return shade_kernel_mixed_of<true, false, true>(first, lens, sparse);
-	case 6: return shade_kernel_mixed_of<true, true, false>(first, lens, sparse);
-	default: return shade_kernel_mixed_of<true, true, true>(first, lens, sparse);
-	}
-}
-// pdf = mirt_set_ggx_pdf while closure_plan() leaves a GGX material: the PDF instantiations — the five reachable forms of [sparse][first ? 1 + lens : 0]
-// times RIS, GLASS and SKY, once with GGX = true and once with MIXED = true (80; the all-Lambertian form has none).  Named after every older
-// instantiation, above, so that those keep their device code.
-template <bool RIS, bool GLASS, bool SKY, bool MIXED>
-auto shade_kernel_pdf_of(bool first, bool lens, bool sparse) {
-	static const decltype(&k_shade<false, false>) table[2][3] = {          // [sparse][first ? 1 + lens : 0]
-		{ k_shade<false, !MIXED, false, false, RIS, GLASS, SKY, MIXED, true>, k_shade<true, !MIXED, false, false, RIS, GLASS, SKY, MIXED, true>, k_shade<true, !MIXED, true, false, RIS, GLASS, SKY, MIXED, true> },
-		{ nullptr, k_shade<true, !MIXED, false, true, RIS, GLASS, SKY, MIXED, true>, k_shade<true, !MIXED, true, true, RIS, GLASS, SKY, MIXED, true> } };
-	return table[first && sparse][first ? 1 + lens : 0];
-}
-template <bool MIXED>
-auto shade_kernel_pdf_by(bool first, bool lens, bool sparse, bool ris, bool glass, bool sky) {
-	switch ((ris ? 4 : 0) | (glass ? 2 : 0) | (sky ? 1 : 0)) {
-	case 0: return shade_kernel_pdf_of<false, false, false, MIXED>(first, lens, sparse);
-	case 1: return shade_kernel_pdf_of<false, false, true, MIXED>(first, lens, sparse);
-	case 2: return shade_kernel_pdf_of<false, true, false, MIXED>(first, lens, sparse);
-	case 3: return shade_kernel_pdf_of<false, true, true, MIXED>(first, lens, sparse);
-	case 4: return shade_kernel_pdf_of<true, false, false, MIXED>(first, lens, sparse);
-	case 5: return shade_kernel_pdf_of<true, false, true, MIXED>(first, lens, sparse);
-	case 6: return shade_kernel_pdf_of<true, true, false, MIXED>(first, lens, sparse);
-	default: return shade_kernel_pdf_of<true, true, true, MIXED>(first, lens, sparse);
-	}
-}
-auto shade_kernel_pdf(bool first, bool mixed, bool lens, bool sparse, bool ris, bool glass, bool sky) {
-	return mixed ? shade_kernel_pdf_by<true>(first, lens, sparse, ris, glass, sky) : shade_kernel_pdf_by<false>(first, lens, sparse, ris, glass, sky);
+ShadeKernel shade_kernel(ShadeForm f) { return shade_kernel(f, std::make_integer_sequence<uint32_t, 1u << ShadeForm::kBits>{}); }
+// The k_shade of one bounce of a batch: the one place where a switch of the context turns into a template argument.  What the launch passes for
+// a flag's arguments (ris_m, the sky table, the pdf planes) it reads from this value too.
+ShadeForm shade_form(const mirt_ctx* c, const FrameParams& fp, const ClosurePlan& plan, uint32_t bounce, bool lens, bool sparse) {
+	ShadeForm f{};
+	f.first = bounce == 0;
+	// lens and sparse (a tile is frozen, mirt_freeze_tiles) concern bounce 0 only
+	f.lens = f.first && lens;
+	f.sparse = f.first && sparse;
+	// mirt_set_light_ris: the candidate loop is worth running only where NEE runs
+	f.ris = fp.mis && c->light_ris;
+	// mirt_set_transmission: only while the scene has a transmissive material
+	f.glass = c->transmission && c->scene_has_glass;
+	// mirt_set_sky_sampling: only where the sky's light can be drawn and can carry something
+	f.sky = sky_active(c);
+	// mirt_set_material_closures: the kernels of the one closure every material takes, or the MIXED ones
+	f.mixed = plan.mixed; f.ggx = plan.ggx;
+	// mirt_set_ggx_pdf: only where Closure<GGX> shades a hit; an all-Lambertian plan launches what it launched without the switch
+	f.pdf = c->ggx_pdf && (plan.mixed || plan.ggx);
+	return f;
 }
 auto first_hit_aov_kernel(bool lens, bool sparse) {
 	static const decltype(&k_first_hit_aov<false>) table[2][2] = { { k_first_hit_aov<false>, k_first_hit_aov<true> }, { k_first_hit_aov<false, true>, k_first_hit_aov<true, true> } };   // [sparse][lens]
@@ -874,19 +834,14 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			{ Bracket t(c, MIRT_K_SHADE, st);
 			  // policy.brdf = 1 (#define BRDF 1): Closure<GGX> with this bounce's gloss decay, passed by value
 			  const float decay = bounce < c->gloss_decay.size() ? c->gloss_decay[bounce] : 0.0f;
-			  // mirt_set_light_ris: the candidate loop is worth running only where NEE runs
-			  const uint32_t ris = fp.mis ? c->light_ris : 0u;
-			  const bool glass = c->transmission && c->scene_has_glass, sky = sky_active(c);
-			  // mirt_set_material_closures: the kernels of the one closure every material takes, or the MIXED ones
 			  const ClosurePlan plan = closure_plan(c);
-			  // mirt_set_ggx_pdf: only where Closure<GGX> shades a hit; an all-Lambertian plan launches what it launched without the switch
-			  const bool pdf = c->ggx_pdf && (plan.mixed || plan.ggx);
-			  const auto shade = pdf ? shade_kernel_pdf(bounce == 0, plan.mixed, lens, sparse, ris != 0, glass, sky)
-			                   : plan.mixed ? shade_kernel_mixed(bounce == 0, lens, sparse, ris != 0, glass, sky)
-			                   : sky ? shade_kernel_sky(bounce == 0, plan.ggx, lens, sparse, ris != 0, glass) : shade_kernel(bounce == 0, plan.ggx, lens, sparse, ris != 0, glass);
+			  const ShadeForm form = shade_form(c, fp, plan, bounce, lens, sparse);
+			  const auto shade = shade_kernel(form);
+			  if (!shade) return fail(c, MIRT_ERR_ARG, "no shade kernel for the form first %d ggx %d lens %d sparse %d ris %d glass %d sky %d mixed %d pdf %d",
+			                          form.first, form.ggx, form.lens, form.sparse, form.ris, form.glass, form.sky, form.mixed, form.pdf);
 			  hipLaunchKernelGGL(shade, dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
-			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, ris, tile_frozen, sky ? c->sky : SkyTable{}, plan.mask,
-			                     pdf ? sl.pdf_plane[bounce & 1u] : nullptr, pdf ? sl.pdf_plane[(bounce & 1u) ^ 1u] : nullptr); }
+			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, form.ris ? c->light_ris : 0u, tile_frozen,
+			                     form.sky ? c->sky : SkyTable{}, plan.mask, form.pdf ? sl.pdf_plane[bounce & 1u] : nullptr, form.pdf ? sl.pdf_plane[(bounce & 1u) ^ 1u] : nullptr); }
 		}
 	}
 	HIP_TRY(c, hipGetLastError());

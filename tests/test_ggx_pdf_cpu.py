@@ -119,4 +119,6 @@ def test_interface_is_declared_in_every_layer(mirt):
     for cls in (mirt.Renderer, mirt.GroupRenderer):
         assert callable(getattr(cls, "set_ggx_pdf")) and callable(getattr(cls, "ggx_pdf"))
     kernels = open(os.path.join(mirt.CSRC, "kernels.hpp")).read()
-    assert "static_assert(!PDF || GGX || MIXED" in kernels
+    # the all-Lambertian form has no PDF instantiation: ShadeForm::valid() states the rule, k_shade asserts it on its own arguments
+    assert re.search(r"constexpr bool valid\(\) const \{[^}]*\(!pdf \|\| ggx \|\| mixed\)", kernels)
+    assert "static_assert(ShadeForm{ FIRST, GGX, LENS, SPARSE, RIS, GLASS, SKY, MIXED, PDF }.valid()" in kernels
