@@ -33,6 +33,11 @@ MAX_MATERIALS = 63                                # mirt.h MIRT_MAX_MATERIALS
 MAX_LIGHT_RIS = 32                              # mirt.h MIRT_MAX_LIGHT_RIS
 KERNEL_CLASSES = ("raygen", "trace", "shade", "shadow", "resolve")
 
+# The switches on the per-hit shading, each stated once: (name, kind, constructor default), in the order the constructors apply them.  bool and int are
+# one uint32 in the C-ABI; list is a table of one byte per material.  From a row follow the signatures of mirt_set_X, mirt_get_X and mirt_group_set_X
+# (load_library), the getter X() of both renderers (_Binding) and what _configure does with the constructors' keyword X.
+_SWITCHES = (("ggx_pdf", bool, False), ("material_closures", list, None), ("sky_sampling", bool, False), ("transmission", bool, False), ("light_ris", int, 0))
+
 
 class MirtError(RuntimeError):
     pass
@@ -111,11 +116,6 @@ def load_library():
         "mirt_get_policy": [P, C.POINTER(Policy)],
         "mirt_set_gloss_decay": [P, vp, u32],
         "mirt_set_stream_order": [P, u32], "mirt_get_stream_order": [P, C.POINTER(u32)],
-        "mirt_set_light_ris": [P, u32], "mirt_get_light_ris": [P, C.POINTER(u32)],
-        "mirt_set_transmission": [P, u32], "mirt_get_transmission": [P, C.POINTER(u32)],
-        "mirt_set_sky_sampling": [P, u32], "mirt_get_sky_sampling": [P, C.POINTER(u32)],
-        "mirt_set_ggx_pdf": [P, u32], "mirt_get_ggx_pdf": [P, C.POINTER(u32)],
-        "mirt_set_material_closures": [P, vp, u32], "mirt_get_material_closures": [P, vp, u32, C.POINTER(u32), C.POINTER(u32)],
         "mirt_resize": [P, u32, u32],
         "mirt_set_tile_range": [P, u32, u32], "mirt_set_tile_rows": [P, u32, u32],
         "mirt_reset": [P],
@@ -171,9 +171,6 @@ def load_library():
         "mirt_group_set_policy": [G, C.POINTER(Policy)],
         "mirt_group_set_gloss_decay": [G, vp, u32],
         "mirt_group_set_stream_order": [G, u32],
-        "mirt_group_set_light_ris": [G, u32], "mirt_group_set_transmission": [G, u32], "mirt_group_set_sky_sampling": [G, u32],
-        "mirt_group_set_ggx_pdf": [G, u32],
-        "mirt_group_set_material_closures": [G, vp, u32],
         "mirt_group_resize": [G, u32, u32],
         "mirt_group_reset": [G],
         "mirt_group_accumulate": [G, u32],
@@ -199,6 +196,10 @@ def load_library():
         "mirt_group_accumulate_adaptive": [G, C.POINTER(StopRule), u32, C.POINTER(AdaptiveReport)],
         "mirt_group_rccl_selftest": [i32, C.c_size_t],
     })
+    for name, kind, _ in _SWITCHES:
+        value = [vp, u32] if kind is list else [u32]
+        sigs["mirt_set_" + name], sigs["mirt_group_set_" + name] = [P] + value, [G] + value
+        sigs["mirt_get_" + name] = [P, vp, u32, C.POINTER(u32), C.POINTER(u32)] if kind is list else [P, C.POINTER(u32)]
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)      # AttributeError if the library does not export a declared symbol
         fn.argtypes = argtypes
@@ -317,18 +318,15 @@ class _Binding:
         """mirt_<name> or mirt_group_<name> on this object's handle, checked."""
         return self._check(getattr(self._lib, self._prefix + name)(getattr(self, self._handle), *args))
 
-    def _configure(self, gloss_decay, exact_stream_order, aov, light_ris=0, transmission=False, sky_sampling=False, material_closures=None, ggx_pdf=False):
-        """The end of both constructors, after the policy is set."""
-        if ggx_pdf:
-            self.set_ggx_pdf(True)
-        if material_closures is not None:
-            self.set_material_closures(material_closures)
-        if sky_sampling:
-            self.set_sky_sampling(True)
-        if transmission:
-            self.set_transmission(True)
-        if light_ris:
-            self.set_light_ris(light_ris)
+    def _configure(self, *, gloss_decay, exact_stream_order, aov, **switches):
+        """The end of both constructors, after the policy is set: the rows of _SWITCHES by keyword, in the table's order (a switch left off and a
+        table left out are not set), then the rest."""
+        for name, kind, _ in _SWITCHES:
+            value = switches.pop(name)                     # KeyError: a constructor that does not pass a row on
+            if value is not None and (kind is list or value):
+                getattr(self, "set_" + name)(value)
+        if switches:
+            raise TypeError(f"not in _SWITCHES: {sorted(switches)}")
         if gloss_decay is not None:
             self.set_gloss_decay(gloss_decay)
         if exact_stream_order:
@@ -405,12 +403,24 @@ class _Binding:
         t = _closure_table(closures)
         self._call("set_material_closures", _ptr(t) if len(t) else None, len(t))
 
-    def _material_closures_of(self, ctx):
+    # -- getters: read from "the context to ask", self._asked() — a renderer's own, or member 0 of a group (its setters set every member alike) --
+    def _get(self, name, *out):
+        """mirt_get_<name> of the context to ask."""
+        if getattr(self._lib, "mirt_get_" + name)(self._asked(), *out) < 0:
+            raise MirtError(f"mirt_get_{name} failed")
+
+    def material_closures(self):
+        """(table, mixed): the table set_material_closures left, and whether the current scene's materials make the next launch a MIXED one."""
         out = np.zeros(MAX_MATERIALS, dtype=np.uint8)
         n, mixed = C.c_uint32(0), C.c_uint32(0)
-        if self._lib.mirt_get_material_closures(ctx, _ptr(out), len(out), C.byref(n), C.byref(mixed)) < 0:
-            raise MirtError("mirt_get_material_closures failed")
+        self._get("material_closures", _ptr(out), len(out), C.byref(n), C.byref(mixed))
         return [int(v) for v in out[: n.value]], bool(mixed.value)
+
+    def lens(self):
+        """(aperture_radius, focus_depth) in effect."""
+        a, d = C.c_float(0), C.c_float(0)
+        self._get("lens", C.byref(a), C.byref(d))
+        return a.value, d.value
 
     # -- scene hand-over (Application.cpp:230-234) -------------------------------------------------
     def _hand_over_scene(self, nodes=None):
@@ -599,6 +609,20 @@ class _Binding:
         return c.as_dict()
 
 
+def _switch_getter(name, kind):
+    def get(self):
+        v = C.c_uint32(0)
+        self._get(name, C.byref(v))
+        return kind(v.value)
+    get.__name__, get.__qualname__, get.__doc__ = name, "_Binding." + name, f"What set_{name} left (a group: its members', which all hold the same)."
+    return get
+
+
+for _name, _kind, _ in _SWITCHES:                          # light_ris() -> int, transmission() -> bool, ...; the table's getter is material_closures()
+    if _kind is not list:
+        setattr(_Binding, _name, _switch_getter(_name, _kind))
+
+
 class Renderer(_Binding):
     """Mirror of the reference's ``Renderer<Policy>`` (Renderer.hpp:28-68) over the C-ABI.
 
@@ -627,7 +651,11 @@ class Renderer(_Binding):
                              int(brdf))
         self._call("set_policy", C.byref(self.policy))
         self._call("debug_allow_half_boxes", int(allow_half_boxes))
-        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission, sky_sampling, material_closures, ggx_pdf)
+        self._configure(gloss_decay=gloss_decay, exact_stream_order=exact_stream_order, aov=aov, light_ris=light_ris, transmission=transmission,
+                        sky_sampling=sky_sampling, material_closures=material_closures, ggx_pdf=ggx_pdf)
+
+    def _asked(self):
+        return self._ctx
 
     def load_tile_counts(self, counts):
         """After load_accumulator: per-tile counts (positive multiples of `buckets`, at most accumulations); tiles below it are frozen."""
@@ -640,30 +668,6 @@ class Renderer(_Binding):
         self._call("get_policy", C.byref(p))
         return {name: int(getattr(p, name)) for name, _ in Policy._fields_ if not name.startswith("_")}
 
-    def light_ris(self) -> int:
-        v = C.c_uint32(0)
-        self._call("get_light_ris", C.byref(v))
-        return v.value
-
-    def transmission(self) -> bool:
-        v = C.c_uint32(0)
-        self._call("get_transmission", C.byref(v))
-        return bool(v.value)
-
-    def sky_sampling(self) -> bool:
-        v = C.c_uint32(0)
-        self._call("get_sky_sampling", C.byref(v))
-        return bool(v.value)
-
-    def ggx_pdf(self) -> bool:
-        v = C.c_uint32(0)
-        self._call("get_ggx_pdf", C.byref(v))
-        return bool(v.value)
-
-    def material_closures(self):
-        """(table, mixed): the table set_material_closures left, and whether the current scene's materials make the next launch a MIXED one."""
-        return self._material_closures_of(self._ctx)
-
     @property
     def stream_order(self) -> int:
         v = C.c_uint32(0)
@@ -674,12 +678,6 @@ class Renderer(_Binding):
         """Hands the scene over again (after an edit).  `nodes`: a caller-made tree over the reference-order prims instead of the
         reference builder's (BVH.hpp:18-31 layout, children at first_id / first_id+1, leaves first_id..first_id+prim_count-1)."""
         self._hand_over_scene(nodes)
-
-    def lens(self):
-        """(aperture_radius, focus_depth) in effect."""
-        a, d = C.c_float(0), C.c_float(0)
-        self._call("get_lens", C.byref(a), C.byref(d))
-        return a.value, d.value
 
     @staticmethod
     def RequiredTiling() -> int:          # Renderer.hpp:36
@@ -828,56 +826,16 @@ class GroupRenderer(_Binding):
         self.policy = Policy(max_bounces, buckets, int(mis), int(use_bvh), int(count_traffic), 0, max_batch, int(reference_tree), int(streams), int(gpu_build), 0,
                              int(brdf))
         self._call("set_policy", C.byref(self.policy))
-        self._configure(gloss_decay, exact_stream_order, aov, light_ris, transmission, sky_sampling, material_closures, ggx_pdf)
+        self._configure(gloss_decay=gloss_decay, exact_stream_order=exact_stream_order, aov=aov, light_ris=light_ris, transmission=transmission,
+                        sky_sampling=sky_sampling, material_closures=material_closures, ggx_pdf=ggx_pdf)
 
-    def light_ris(self) -> int:
-        """The members' setting (they all hold the same: set_light_ris sets every one)."""
-        ctx, v = C.c_void_p(), C.c_uint32(0)
-        self._call("member", 0, C.byref(ctx))
-        if self._lib.mirt_get_light_ris(ctx, C.byref(v)) < 0:
-            raise MirtError("mirt_get_light_ris failed on member 0")
-        return v.value
-
-    def transmission(self) -> bool:
-        """The members' setting (they all hold the same: set_transmission sets every one)."""
-        ctx, v = C.c_void_p(), C.c_uint32(0)
-        self._call("member", 0, C.byref(ctx))
-        if self._lib.mirt_get_transmission(ctx, C.byref(v)) < 0:
-            raise MirtError("mirt_get_transmission failed on member 0")
-        return bool(v.value)
-
-    def sky_sampling(self) -> bool:
-        """The members' setting (they all hold the same: set_sky_sampling sets every one)."""
-        ctx, v = C.c_void_p(), C.c_uint32(0)
-        self._call("member", 0, C.byref(ctx))
-        if self._lib.mirt_get_sky_sampling(ctx, C.byref(v)) < 0:
-            raise MirtError("mirt_get_sky_sampling failed on member 0")
-        return bool(v.value)
-
-    def ggx_pdf(self) -> bool:
-        """The members' setting (they all hold the same: set_ggx_pdf sets every one)."""
-        ctx, v = C.c_void_p(), C.c_uint32(0)
-        self._call("member", 0, C.byref(ctx))
-        if self._lib.mirt_get_ggx_pdf(ctx, C.byref(v)) < 0:
-            raise MirtError("mirt_get_ggx_pdf failed on member 0")
-        return bool(v.value)
-
-    def material_closures(self):
-        """(table, mixed) of the members (they all hold the same: set_material_closures sets every one)."""
+    def _asked(self):
         ctx = C.c_void_p()
         self._call("member", 0, C.byref(ctx))
-        return self._material_closures_of(ctx)
+        return ctx
 
     def UpdateScene(self):
         self._hand_over_scene()
-
-    def lens(self):
-        """(aperture_radius, focus_depth) in effect (the first member's; all members hold the same)."""
-        ctx = C.c_void_p()
-        self._call("member", 0, C.byref(ctx))
-        a, d = C.c_float(0), C.c_float(0)
-        self._lib.mirt_get_lens(ctx, C.byref(a), C.byref(d))
-        return a.value, d.value
 
     read_aov = _Binding.aov
 

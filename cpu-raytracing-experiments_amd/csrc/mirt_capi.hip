@@ -1157,6 +1157,55 @@ int debug_trace(mirt_ctx* c, const char* who, size_t n, const float* p_xyz, cons
 	return MIRT_OK;
 }
 
+// ---- what exact stream order excludes (DESIGN.md "One switch table in the host layers") ------------------------------------------
+// One row per feature that mirt_set_stream_order(ctx, 1) cannot run with.  The exclusion is a rule about pairs, and both directions of every
+// pair read this table and nothing else: mirt_set_stream_order(ctx, 1) refuses with the first row that is on (refuse_exact_order), and a
+// feature's entry point asked to turn the feature on under exact order refuses with its own row (refuse_under_exact_order).
+struct ExactExcludes {
+	uint32_t (*on)(const mirt_ctx*);   // 0 = off in this context; otherwise how much of it there is
+	const char* why;                   // the message is "exact stream order <why>: <the call that lifts the refusal> first"
+	const char* off;                   // what turns the feature off: a format that may print on()
+};
+enum ExactRow { X_LENS, X_FROZEN, X_LIGHT_RIS, X_TRANSMISSION, X_SKY_SAMPLING, X_GGX_PDF, X_CLOSURES, X_AOV, X_ROWS };
+const ExactExcludes kExactExcludes[X_ROWS] = {
+	/* X_LENS */         { [](const mirt_ctx* c) -> uint32_t { return lens_on(c); }, "replays the reference, which has no lens (Camera.hpp:80-88 ignores it)", "call mirt_set_lens(ctx, 0, 0)" },
+	/* X_FROZEN */       { [](const mirt_ctx* c) { return c->n_frozen; }, "runs a tile's whole bounce loop in one launch and has no form that skips frozen tiles", "%u are frozen, mirt_reset" },
+	/* X_LIGHT_RIS */    { [](const mirt_ctx* c) { return c->light_ris; }, "replays the reference, which draws its NEE light uniformly (Renderer.hpp:259)", "call mirt_set_light_ris(ctx, 0)" },
+	/* X_TRANSMISSION */ { [](const mirt_ctx* c) { return c->transmission; }, "replays the reference, no closure of which reads transmission", "call mirt_set_transmission(ctx, 0)" },
+	/* X_SKY_SAMPLING */ { [](const mirt_ctx* c) { return c->sky_sampling; }, "replays the reference, which draws its NEE light among the sphere lights only", "call mirt_set_sky_sampling(ctx, 0)" },
+	/* X_GGX_PDF */      { [](const mirt_ctx* c) { return c->ggx_pdf; }, "replays the reference, whose Closure<GGX>::pdf is 0 (DataStreams.hpp:196-198)", "call mirt_set_ggx_pdf(ctx, 0)" },
+	/* X_CLOSURES */     { [](const mirt_ctx* c) { return static_cast<uint32_t>(c->closures.size()); }, "replays the reference, every closure of which is policy.brdf's (Renderer.hpp:70)", "call mirt_set_material_closures(ctx, NULL, 0)" },
+	/* X_AOV */          { [](const mirt_ctx* c) { return c->aov_on; }, "keeps no hit records (k_tile_stream runs a tile's whole bounce loop in one launch), so it cannot feed the first-hit AOVs", "call mirt_set_aov(ctx, 0)" },
+};
+int refuse_exact_order(mirt_ctx* c) {
+	for (const ExactExcludes& x : kExactExcludes) if (const uint32_t n = x.on(c)) {
+		char off[96];
+		snprintf(off, sizeof off, x.off, n);
+		return fail(c, MIRT_ERR_STATE, "exact stream order %s: %s first", x.why, off);
+	}
+	return MIRT_OK;
+}
+int refuse_under_exact_order(mirt_ctx* c, ExactRow row) {
+	return c->stream_order ? fail(c, MIRT_ERR_STATE, "exact stream order %s: call mirt_set_stream_order(ctx, 0) first", kExactExcludes[row].why) : MIRT_OK;
+}
+
+// The preamble of a scalar switch's setter, in the order every one of them keeps: NULL, range (`range_fmt` prints value and max), refusal under exact
+// stream order, a value the context already holds (kHeld: nothing is flushed and the setter returns MIRT_OK), the switch's own validation, and the
+// flush: deferred accumulations render under the setting they were issued under.  What comes after BEGIN_SWITCH is the setter's own.
+constexpr int kHeld = 1;
+int begin_switch(mirt_ctx* c, uint32_t mirt_ctx::* field, uint32_t value, uint32_t max, const char* range_fmt, ExactRow row, int (*validate)(mirt_ctx*, uint32_t) = nullptr) {
+	if (!c) return MIRT_ERR_ARG;
+	if (value > max) return fail(c, MIRT_ERR_ARG, range_fmt, value, max);
+	int r;
+	if (value && (r = refuse_under_exact_order(c, row))) return r;
+	if (value == c->*field) return kHeld;
+	if (validate && (r = validate(c, value))) return r;
+	return flush_deferred(c);
+}
+#define BEGIN_SWITCH(...) do { const int _r = begin_switch(__VA_ARGS__); if (_r) return _r == kHeld ? MIRT_OK : _r; } while (0)
+// The getters of the uint32 switches; the exported symbols are exactly those of mirt.h.
+#define SWITCH_GETTER(name, field) int mirt_get_##name(const mirt_ctx* c, uint32_t* value) { if (!c || !value) return MIRT_ERR_ARG; *value = c->field; return MIRT_OK; }
+
 } // namespace
 
 extern "C" {
@@ -1262,7 +1311,7 @@ int mirt_set_lens(mirt_ctx* c, float aperture_radius, float focus_depth) {
 	if (!std::isfinite(aperture_radius) || !std::isfinite(focus_depth)) return fail(c, MIRT_ERR_ARG, "lens: aperture_radius %g / focus_depth %g must be finite", static_cast<double>(aperture_radius), static_cast<double>(focus_depth));
 	if (aperture_radius < 0.0f) return fail(c, MIRT_ERR_ARG, "lens: aperture_radius %g is negative", static_cast<double>(aperture_radius));
 	if (aperture_radius > 0.0f && !(focus_depth > 0.0f)) return fail(c, MIRT_ERR_ARG, "lens: focus_depth %g must be above 0 with an open aperture", static_cast<double>(focus_depth));
-	if (aperture_radius > 0.0f && c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which has no lens (Camera.hpp:80-88 ignores it): call mirt_set_stream_order(ctx, 0) first");
+	if (aperture_radius > 0.0f) { const int r = refuse_under_exact_order(c, X_LENS); if (r) return r; }
 	if (aperture_radius == c->lens.aperture && focus_depth == c->lens.focus_depth) return MIRT_OK;
 	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render under the lens they were issued under
 	c->lens.aperture = aperture_radius; c->lens.focus_depth = focus_depth;
@@ -1324,36 +1373,21 @@ int mirt_set_stream_order(mirt_ctx* c, uint32_t exact) {
 	if (!c) return MIRT_ERR_ARG;
 	if (exact > 1) return fail(c, MIRT_ERR_ARG, "stream order %u is neither 0 (any order, FMA form for every ray) nor 1 (the reference's slots and scalar tail)", exact);
 	if (exact == c->stream_order) return MIRT_OK;
-	if (exact && lens_on(c)) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which has no lens (Camera.hpp:80-88 ignores it): call mirt_set_lens(ctx, 0, 0) first");
-	if (exact && c->n_frozen) return fail(c, MIRT_ERR_STATE, "exact stream order runs a tile's whole bounce loop in one launch and has no form that skips frozen tiles (%u are frozen): mirt_reset first", c->n_frozen);
-	if (exact && c->light_ris) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which draws its NEE light uniformly (Renderer.hpp:259): call mirt_set_light_ris(ctx, 0) first");
-	if (exact && c->transmission) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, no closure of which reads transmission: call mirt_set_transmission(ctx, 0) first");
-	if (exact && c->sky_sampling) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which draws its NEE light among the sphere lights only: call mirt_set_sky_sampling(ctx, 0) first");
-	if (exact && c->ggx_pdf) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, whose Closure<GGX>::pdf is 0 (DataStreams.hpp:196-198): call mirt_set_ggx_pdf(ctx, 0) first");
-	if (exact && !c->closures.empty()) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, every closure of which is policy.brdf's (Renderer.hpp:70): call mirt_set_material_closures(ctx, NULL, 0) first");
-	if (exact && c->aov_on) return fail(c, MIRT_ERR_STATE, "exact stream order keeps no hit records (k_tile_stream runs a tile's whole bounce loop in one launch), so it cannot feed the first-hit AOVs: call mirt_set_aov(ctx, 0) first");
+	if (exact) { const int r = refuse_exact_order(c); if (r) return r; }
 	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render in the mode they were issued under
 	c->stream_order = exact;
 	return MIRT_OK;
 }
 // ---- NEE light by resampled importance sampling -------------------------------------------------
 int mirt_set_light_ris(mirt_ctx* c, uint32_t candidates) {
-	if (!c) return MIRT_ERR_ARG;
-	if (candidates > MIRT_MAX_LIGHT_RIS) return fail(c, MIRT_ERR_ARG, "light RIS: %u candidates (0 = off, at most %u)", candidates, MIRT_MAX_LIGHT_RIS);
-	if (candidates && c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which draws its NEE light uniformly (Renderer.hpp:259): call mirt_set_stream_order(ctx, 0) first");
-	if (candidates == c->light_ris) return MIRT_OK;
-	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render under the setting they were issued under
+	BEGIN_SWITCH(c, &mirt_ctx::light_ris, candidates, MIRT_MAX_LIGHT_RIS, "light RIS: %u candidates (0 = off, at most %u)", X_LIGHT_RIS);
 	c->light_ris = candidates;                                                      // the expectation is the same: no reset; the lists do not depend on it
 	return MIRT_OK;
 }
 // ---- dielectric interface for transmissive materials ---------------------------------------------
 int mirt_set_transmission(mirt_ctx* c, uint32_t on) {
-	if (!c) return MIRT_ERR_ARG;
-	if (on > 1) return fail(c, MIRT_ERR_ARG, "transmission %u is neither 0 (off: transmission and IOR_minus_one are read by no kernel) nor 1 (on)", on);
-	if (on && c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, no closure of which reads transmission: call mirt_set_stream_order(ctx, 0) first");
-	if (on == c->transmission) return MIRT_OK;
-	if (on && c->have_scene) { const int r = check_glass(c, c->glass_host); if (r) return r; }
-	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render under the setting they were issued under
+	BEGIN_SWITCH(c, &mirt_ctx::transmission, on, 1u, "transmission %u is neither 0 (off: transmission and IOR_minus_one are read by no kernel) nor 1 (on)", X_TRANSMISSION,
+	             [](mirt_ctx* c, uint32_t on) { return on && c->have_scene ? check_glass(c, c->glass_host) : MIRT_OK; });
 	c->transmission = on;                                                           // another estimand: the caller resets; the camera-ray lists do not depend on it
 	return MIRT_OK;
 }
@@ -1364,7 +1398,7 @@ int mirt_set_material_closures(mirt_ctx* c, const uint8_t* closure, uint32_t n) 
 	if (n > MIRT_MAX_MATERIALS) return fail(c, MIRT_ERR_ARG, "material closures: %u entries (at most %u, MIRT_MAX_MATERIALS)", n, MIRT_MAX_MATERIALS);
 	for (uint32_t m = 0; m < n; m++)
 		if (closure[m] > 1) return fail(c, MIRT_ERR_ARG, "material closures: closure[%u] = %u is neither 0 (Lambertian) nor 1 (GGX)", m, closure[m]);
-	if (n && c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, every closure of which is policy.brdf's (Renderer.hpp:70): call mirt_set_stream_order(ctx, 0) first");
+	if (n) { const int r = refuse_under_exact_order(c, X_CLOSURES); if (r) return r; }
 	if (n == c->closures.size() && (n == 0 || std::memcmp(c->closures.data(), closure, n) == 0)) return MIRT_OK;
 	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render under the table they were issued under
 	c->closures.assign(closure, closure + n);                                       // another estimand: the caller resets; the camera-ray lists do not depend on it
@@ -1382,11 +1416,7 @@ int mirt_get_material_closures(const mirt_ctx* c, uint8_t* closure_out, uint32_t
 }
 // ---- the environment map as one more light of next event estimation ------------------------------
 int mirt_set_sky_sampling(mirt_ctx* c, uint32_t on) {
-	if (!c) return MIRT_ERR_ARG;
-	if (on > 1) return fail(c, MIRT_ERR_ARG, "sky sampling %u is neither 0 (off: the sky is met by extension rays only) nor 1 (on: it is one more light of next event estimation)", on);
-	if (on && c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, which draws its NEE light among the sphere lights only: call mirt_set_stream_order(ctx, 0) first");
-	if (on == c->sky_sampling) return MIRT_OK;
-	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render under the setting they were issued under
+	BEGIN_SWITCH(c, &mirt_ctx::sky_sampling, on, 1u, "sky sampling %u is neither 0 (off: the sky is met by extension rays only) nor 1 (on: it is one more light of next event estimation)", X_SKY_SAMPLING);
 	HIP_TRY(c, hipSetDevice(c->device));
 	HIP_TRY(c, sync_all(c));                                                        // batches in flight read the table and the planes
 	if (on && c->have_scene) {
@@ -1405,11 +1435,7 @@ int mirt_set_sky_sampling(mirt_ctx* c, uint32_t on) {
 }
 // ---- the GGX closure's pdf in the MIS weights -----------------------------------------------------
 int mirt_set_ggx_pdf(mirt_ctx* c, uint32_t on) {
-	if (!c) return MIRT_ERR_ARG;
-	if (on > 1) return fail(c, MIRT_ERR_ARG, "ggx pdf %u is neither 0 (off: Closure<GGX>::pdf is the reference's 0) nor 1 (on: the visible-normal density, in every MIS weight that reads it)", on);
-	if (on && c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order replays the reference, whose Closure<GGX>::pdf is 0 (DataStreams.hpp:196-198): call mirt_set_stream_order(ctx, 0) first");
-	if (on == c->ggx_pdf) return MIRT_OK;
-	{ const int fr = flush_deferred(c); if (fr) return fr; }                        // deferred accumulations render under the setting they were issued under
+	BEGIN_SWITCH(c, &mirt_ctx::ggx_pdf, on, 1u, "ggx pdf %u is neither 0 (off: Closure<GGX>::pdf is the reference's 0) nor 1 (on: the visible-normal density, in every MIS weight that reads it)", X_GGX_PDF);
 	if (!on) {
 		HIP_TRY(c, hipSetDevice(c->device));
 		HIP_TRY(c, sync_all(c));                                                    // batches in flight write the planes
@@ -1419,11 +1445,8 @@ int mirt_set_ggx_pdf(mirt_ctx* c, uint32_t on) {
 	c->planned_for = 0;                                                             // the planes count in the automatic batch plan (streams_bytes)
 	return MIRT_OK;
 }
-int mirt_get_ggx_pdf(const mirt_ctx* c, uint32_t* on) { if (!c || !on) return MIRT_ERR_ARG; *on = c->ggx_pdf; return MIRT_OK; }
-int mirt_get_sky_sampling(const mirt_ctx* c, uint32_t* on) { if (!c || !on) return MIRT_ERR_ARG; *on = c->sky_sampling; return MIRT_OK; }
-int mirt_get_transmission(const mirt_ctx* c, uint32_t* on) { if (!c || !on) return MIRT_ERR_ARG; *on = c->transmission; return MIRT_OK; }
-int mirt_get_light_ris(const mirt_ctx* c, uint32_t* candidates) { if (!c || !candidates) return MIRT_ERR_ARG; *candidates = c->light_ris; return MIRT_OK; }
-int mirt_get_stream_order(const mirt_ctx* c, uint32_t* exact) { if (!c || !exact) return MIRT_ERR_ARG; *exact = c->stream_order; return MIRT_OK; }
+SWITCH_GETTER(ggx_pdf, ggx_pdf) SWITCH_GETTER(sky_sampling, sky_sampling) SWITCH_GETTER(transmission, transmission) SWITCH_GETTER(light_ris, light_ris)
+SWITCH_GETTER(stream_order, stream_order)
 int mirt_get_policy(const mirt_ctx* c, mirt_policy* p) {
 	if (!c || !p) return MIRT_ERR_ARG;
 	*p = c->policy;
@@ -1542,7 +1565,7 @@ int mirt_set_aov(mirt_ctx* c, uint32_t on) {
 	if (on > 1) return fail(c, MIRT_ERR_ARG, "aov %u is neither 0 (off) nor 1 (sum depth, normal and albedo of every camera ray)", on);
 	if (on == c->aov_on) return MIRT_OK;
 	if (on) {
-		if (c->stream_order) return fail(c, MIRT_ERR_STATE, "first-hit AOVs read the hit records of the wavefront pipeline; exact stream order (k_tile_stream) keeps none: call mirt_set_stream_order(ctx, 0) first");
+		{ const int r = refuse_under_exact_order(c, X_AOV); if (r) return r; }
 		if (c->accumulations + c->deferred) return fail(c, MIRT_ERR_STATE, "AOVs can be turned on only before the first accumulation (%u issued): the sums would cover fewer samples than the frame; mirt_reset first", c->accumulations + c->deferred);
 		HIP_TRY(c, hipSetDevice(c->device));
 		HIP_TRY(c, sync_all(c));
@@ -1557,7 +1580,7 @@ int mirt_set_aov(mirt_ctx* c, uint32_t on) {
 	c->aov.release();
 	return MIRT_OK;
 }
-int mirt_get_aov(const mirt_ctx* c, uint32_t* on) { if (!c || !on) return MIRT_ERR_ARG; *on = c->aov_on; return MIRT_OK; }
+SWITCH_GETTER(aov, aov_on)
 int mirt_aov_floats(const mirt_ctx* c, size_t* n) { if (!c || !n) return MIRT_ERR_ARG; *n = aov_floats(c); return MIRT_OK; }
 int mirt_read_aov(mirt_ctx* c, float* dst) {
 	if (!c || !dst) return MIRT_ERR_ARG;
@@ -1705,7 +1728,7 @@ int mirt_freeze_tiles(mirt_ctx* c, const uint8_t* freeze, size_t n_local_tiles) 
 	int r = check_ready(c); if (r) return r;
 	if (!freeze && n_local_tiles) return fail(c, MIRT_ERR_ARG, "freeze is NULL");
 	if (n_local_tiles != c->n_tiles) return fail(c, MIRT_ERR_ARG, "freeze_tiles: a mask of %zu tiles, the context owns %u", n_local_tiles, c->n_tiles);
-	if (c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order runs a tile's whole bounce loop in one launch and has no form that skips frozen tiles: call mirt_set_stream_order(ctx, 0) first");
+	if ((r = refuse_under_exact_order(c, X_FROZEN))) return r;
 	const uint32_t issued = c->accumulations + c->deferred, k = c->policy.buckets;
 	if (issued == 0) return fail(c, MIRT_ERR_STATE, "nothing accumulated yet: a frozen tile would hold no sample");
 	if (issued % k != 0) return fail(c, MIRT_ERR_STATE, "%u accumulations so far: not a multiple of buckets (%u); a frozen tile must stay resolvable", issued, k);
@@ -1748,7 +1771,7 @@ int mirt_load_tile_counts(mirt_ctx* c, const uint32_t* counts, size_t n_local_ti
 			return fail(c, MIRT_ERR_ARG, "load_tile_counts: tile %u has count %u; every count is a positive multiple of buckets (%u) and at most accumulations (%u)", t, counts[t], k, c->accumulations);
 		any = any || counts[t] < c->accumulations;
 	}
-	if (any && c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order has no form that skips frozen tiles: call mirt_set_stream_order(ctx, 0) first");
+	if (any) { const int r = refuse_under_exact_order(c, X_FROZEN); if (r) return r; }
 	clear_freezes(c);
 	if (!any) return MIRT_OK;
 	c->frozen.assign(c->n_tiles, 0); c->frozen_at.assign(c->n_tiles, 0u);
@@ -1761,7 +1784,7 @@ int mirt_accumulate_adaptive(mirt_ctx* c, const mirt_stop_rule* rule, uint32_t m
 	const uint32_t k = c->policy.buckets;
 	char why[256];
 	if ((r = mirt_noise_host::check_stop_rule(rule, k, c->accumulations + c->deferred, why, sizeof why))) return fail(c, r, "%s", why);
-	if (c->stream_order) return fail(c, MIRT_ERR_STATE, "exact stream order has no form that skips frozen tiles: call mirt_set_stream_order(ctx, 0) first");
+	if ((r = refuse_under_exact_order(c, X_FROZEN))) return r;
 	return mirt_noise_host::accumulate_adaptive(rule, k, min_accumulations, c->n_tiles,
 		[&](uint32_t* a) { return mirt_get_accumulations(c, a); },
 		[&](uint32_t n) { return mirt_accumulate(c, n); },

@@ -100,6 +100,8 @@ int gfail(mirt_group* g, int code, const char* fmt, ...) {
 #define FULL_TRY(g, what, call) do { const int _rc = (call); if (_rc < 0) return gfail((g), _rc, "%s on the gather context: %s", (what), mirt_last_error((g)->full)); } while (0)
 // Runs `call` on every member, then on the gather context if the group has one.
 #define FOR_MEMBERS_AND_FULL(g, what, call) do { FOR_MEMBERS(g, what, call); if ((g)->full) { mirt_ctx* ctx = (g)->full; FULL_TRY(g, what, call); } } while (0)
+// An entry point that does nothing but that: mirt_group_<name> with the parameter list `params` runs mirt_<name> with `args` (ctx = the context).
+#define GROUP_FORWARD(name, params, args) int mirt_group_##name params { if (!g) return MIRT_ERR_ARG; FOR_MEMBERS_AND_FULL(g, "mirt_" #name, mirt_##name args); return MIRT_OK; }
 // A group of one is its member: `call` on it is the whole entry point, and the member's error text the group's.
 #define RETURN_IF_SINGLE(g, call) do { if ((g)->members.size() == 1) { mirt_ctx* ctx = (g)->members[0]; const int _rc = (call); return _rc < 0 ? gfail((g), _rc, "%s", mirt_last_error(ctx)) : _rc; } } while (0)
 #define GHIP(g, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return gfail((g), MIRT_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); } while (0)
@@ -191,51 +193,15 @@ int mirt_group_set_scene(mirt_group* g, const mirt_sphere* geometry, const mirt_
 	if (g->full) FULL_TRY(g, "mirt_set_scene", mirt_set_scene(g->full, nullptr, nullptr, 0, nullptr, 0, materials, n_materials, nullptr, 0, ambient_color, hdri_rgba, hdri_w, hdri_h));
 	return MIRT_OK;
 }
-int mirt_group_set_camera(mirt_group* g, const float pos[3], const float orient_xyzw[4], float half_width, float half_height, float z, float exposure) {
-	if (!g) return MIRT_ERR_ARG;
-	FOR_MEMBERS_AND_FULL(g, "mirt_set_camera", mirt_set_camera(ctx, pos, orient_xyzw, half_width, half_height, z, exposure));
-	return MIRT_OK;
-}
-int mirt_group_set_gloss_decay(mirt_group* g, const float* decay, uint32_t n) {
-	if (!g) return MIRT_ERR_ARG;
-	FOR_MEMBERS_AND_FULL(g, "mirt_set_gloss_decay", mirt_set_gloss_decay(ctx, decay, n));
-	return MIRT_OK;
-}
-int mirt_group_set_stream_order(mirt_group* g, uint32_t exact) {
-	if (!g) return MIRT_ERR_ARG;
-	FOR_MEMBERS_AND_FULL(g, "mirt_set_stream_order", mirt_set_stream_order(ctx, exact));
-	return MIRT_OK;
-}
-int mirt_group_set_lens(mirt_group* g, float aperture_radius, float focus_depth) {
-	if (!g) return MIRT_ERR_ARG;
-	FOR_MEMBERS_AND_FULL(g, "mirt_set_lens", mirt_set_lens(ctx, aperture_radius, focus_depth));
-	return MIRT_OK;
-}
-int mirt_group_set_light_ris(mirt_group* g, uint32_t candidates) {
-	if (!g) return MIRT_ERR_ARG;
-	FOR_MEMBERS_AND_FULL(g, "mirt_set_light_ris", mirt_set_light_ris(ctx, candidates));
-	return MIRT_OK;
-}
-int mirt_group_set_transmission(mirt_group* g, uint32_t on) {
-	if (!g) return MIRT_ERR_ARG;
-	FOR_MEMBERS_AND_FULL(g, "mirt_set_transmission", mirt_set_transmission(ctx, on));
-	return MIRT_OK;
-}
-int mirt_group_set_sky_sampling(mirt_group* g, uint32_t on) {
-	if (!g) return MIRT_ERR_ARG;
-	FOR_MEMBERS_AND_FULL(g, "mirt_set_sky_sampling", mirt_set_sky_sampling(ctx, on));       // every member builds its own table, word for word the same (a fixed summation order)
-	return MIRT_OK;
-}
-int mirt_group_set_ggx_pdf(mirt_group* g, uint32_t on) {
-	if (!g) return MIRT_ERR_ARG;
-	FOR_MEMBERS_AND_FULL(g, "mirt_set_ggx_pdf", mirt_set_ggx_pdf(ctx, on));
-	return MIRT_OK;
-}
-int mirt_group_set_material_closures(mirt_group* g, const uint8_t* closure, uint32_t n) {
-	if (!g) return MIRT_ERR_ARG;
-	FOR_MEMBERS_AND_FULL(g, "mirt_set_material_closures", mirt_set_material_closures(ctx, closure, n));   // the gather context too: its first-hit AOV colour follows the table
-	return MIRT_OK;
-}
+GROUP_FORWARD(set_camera, (mirt_group* g, const float pos[3], const float orient_xyzw[4], float half_width, float half_height, float z, float exposure), (ctx, pos, orient_xyzw, half_width, half_height, z, exposure))
+GROUP_FORWARD(set_gloss_decay, (mirt_group* g, const float* decay, uint32_t n), (ctx, decay, n))
+GROUP_FORWARD(set_stream_order, (mirt_group* g, uint32_t exact), (ctx, exact))
+GROUP_FORWARD(set_lens, (mirt_group* g, float aperture_radius, float focus_depth), (ctx, aperture_radius, focus_depth))
+GROUP_FORWARD(set_light_ris, (mirt_group* g, uint32_t candidates), (ctx, candidates))
+GROUP_FORWARD(set_transmission, (mirt_group* g, uint32_t on), (ctx, on))
+GROUP_FORWARD(set_sky_sampling, (mirt_group* g, uint32_t on), (ctx, on))                         // every member builds its own table, word for word the same (a fixed summation order)
+GROUP_FORWARD(set_ggx_pdf, (mirt_group* g, uint32_t on), (ctx, on))
+GROUP_FORWARD(set_material_closures, (mirt_group* g, const uint8_t* closure, uint32_t n), (ctx, closure, n))   // the gather context too: its first-hit AOV colour follows the table
 int mirt_group_pick_focus(mirt_group* g, uint32_t x, uint32_t y, float* distance, float* depth) {
 	if (!g) return MIRT_ERR_ARG;
 	mirt_ctx* ctx = g->members[0];                                                   // one ray: every member holds the whole scene
