@@ -82,6 +82,15 @@ class AdaptiveReport(C.Structure):
                 ("last", NoiseStats)]
 
 
+class DenoiseParams(C.Structure):
+    """mirt_denoise_params"""
+    _fields_ = [("iterations", C.c_uint32), ("normal_squarings", C.c_uint32), ("demodulate", C.c_uint32), ("sigma_lum", C.c_float), ("sigma_depth", C.c_float),
+                ("lum_floor", C.c_float), ("albedo_floor", C.c_float)]
+
+    def as_dict(self):
+        return {n: (int if t is C.c_uint32 else float)(getattr(self, n)) for n, t in self._fields_}
+
+
 def build(force: bool = False) -> str:
     """Compile csrc/ for gfx950 with hipcc (cross-compiles without a GPU)."""
     args = ["make", "-C", CSRC]
@@ -134,7 +143,9 @@ def load_library():
         "mirt_aov_device": [P, C.POINTER(vp), C.POINTER(C.c_size_t)],
         "mirt_load_aov": [P, vp, i32],
         "mirt_render_aov": [P, i32, vp],
-        "mirt_noise": [P, f, vp, vp, vp, C.POINTER(NoiseStats)],
+        "mirt_atrous_defaults": [C.POINTER(DenoiseParams)],
+        "mirt_render_atrous": [P, C.POINTER(DenoiseParams), vp],
+        "mirt_noise":[P, f, vp, vp, vp, C.POINTER(NoiseStats)],
         "mirt_noise_quantile": [vp, C.c_double, C.POINTER(f)],
         "mirt_accumulate_until": [P, C.POINTER(StopRule), C.POINTER(NoiseStats), C.POINTER(u32)],
         "mirt_freeze_tiles": [P, vp, C.c_size_t],
@@ -187,6 +198,7 @@ def load_library():
         "mirt_group_aov_floats": [G, C.POINTER(C.c_size_t)],
         "mirt_group_read_aov": [G, vp],
         "mirt_group_render_aov": [G, i32, vp],
+        "mirt_group_render_atrous": [G, C.POINTER(DenoiseParams), vp],
         "mirt_group_noise": [G, f, vp, vp, vp, C.POINTER(NoiseStats)],
         "mirt_group_accumulate_until": [G, C.POINTER(StopRule), C.POINTER(NoiseStats), C.POINTER(u32)],
         "mirt_group_freeze_tiles": [G, vp, C.c_size_t],
@@ -284,6 +296,26 @@ def noise_quantile(hist, q: float):
     if rc < 0:
         raise MirtError(f"mirt_noise_quantile failed ({rc}): q = {q} is not in (0, 1]")
     return v.value if rc == MIRT_OK else None
+
+
+def denoise_defaults() -> dict:
+    """mirt_atrous_defaults (host code, no GPU): the parameters render_denoised() starts from, by name."""
+    p = DenoiseParams()
+    rc = load_library().mirt_atrous_defaults(C.byref(p))
+    if rc != MIRT_OK:
+        raise MirtError(f"mirt_atrous_defaults failed ({rc})")
+    return p.as_dict()
+
+
+def _denoise_params(params: dict) -> DenoiseParams:
+    """The defaults with the caller's keywords laid over them; an unknown keyword is a TypeError before any call into the library."""
+    d = denoise_defaults()
+    unknown = sorted(set(params) - set(d))
+    if unknown:
+        raise TypeError(f"not a denoise parameter: {unknown} (known: {sorted(d)})")
+    d.update(params)
+    return DenoiseParams(int(d["iterations"]), int(d["normal_squarings"]), int(d["demodulate"]), float(d["sigma_lum"]), float(d["sigma_depth"]),
+                         float(d["lum_floor"]), float(d["albedo_floor"]))
 
 
 def adaptive_select(tiles, above, frozen=None, quantile: float = 0.95) -> np.ndarray:
@@ -530,6 +562,23 @@ class _Binding:
         before the first accumulation."""
         img = _aov_image(self.height, self.width, which, out)
         return img if self._call("render_aov", int(which), _ptr(img)) == MIRT_OK else None
+
+    # -- denoised resolve (mirt.h "variance-guided à-trous denoised resolve") -----------------------------------
+    denoise_defaults = staticmethod(denoise_defaults)
+
+    def render_denoised(self, out: np.ndarray = None, **params):
+        """The frame Render() resolves, filtered by an edge-avoiding à-trous wavelet that the first-hit AOVs and each pixel's own bucket variance
+        guide (mirt_render_atrous): (height, width, 4) float32, ACES applied last, A = 1.  Keywords are the fields of mirt_denoise_params laid
+        over denoise_defaults(): iterations, normal_squarings, demodulate, sigma_lum, sigma_depth, lum_floor, albedo_floor.  Needs AOVs on,
+        buckets >= 2 and a context that owns the whole image (a group: gathers first).  None, and `out` untouched, while Render() would return
+        False.  Changes no state."""
+        shape = (self.height, self.width, 4)
+        if out is None:
+            out = np.zeros(shape, dtype=np.float32)
+        elif out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
+        p = _denoise_params(params)
+        return out if self._call("render_atrous", C.byref(p), _ptr(out)) == MIRT_OK else None
 
     # -- noise estimate (mirt.h "per-pixel noise estimate") ----------------------------------------------------
     noise_quantile = staticmethod(noise_quantile)

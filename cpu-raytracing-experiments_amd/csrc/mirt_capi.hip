@@ -9,6 +9,7 @@
 // MIRT_ERR_NO_DEVICE / MIRT_ERR_HIP otherwise.
 #include "../../include/mirt.h"
 #include "kernels.hpp"
+#include "denoise.hpp"
 #include "bvh_layout.hpp"
 #include "bvh_build.hpp"
 #include "lbvh_build.hpp"
@@ -146,6 +147,7 @@ struct mirt_ctx {
 	DeviceBuffer counters;           // DevCounters
 	DeviceBuffer noise_above;        // mirt_tile_above: one count per local tile
 	DeviceBuffer noise_rec, noise_hist;   // mirt_noise: one float4 record per local tile, MIRT_NOISE_BINS histogram words (allocated by the first call)
+	DeviceBuffer dn_cv[2], dn_gd, dn_mu;  // mirt_render_atrous (denoise.hpp): full-image float4 buffers, cv ping-pong; allocated by the first call, released by mirt_resize
 	std::vector<PipeSlot> slots;     // batches in flight (policy.streams)
 	uint64_t planned_for = 0;        // local pixel count batch_mem_cap was planned for (0 = plan again)
 	uint32_t batch_mem_cap = 256;     // accumulations per batch the device memory allows (lowered by ensure_streams when the plan does not fit)
@@ -172,6 +174,7 @@ struct mirt_ctx {
 	// MIRT_TUNE_SHADE_WGS = workgroups per CU, MIRT_TUNE_CHUNK = rays per work reservation, MIRT_TUNE_LEAF_BATCH = lanes at a leaf that
 	// trigger a leaf pass, MIRT_TUNE_REFILL_IDLE = idle lanes that trigger a refill.  They never change results.
 	uint32_t tune_trace_wgs = 2, tune_shade_wgs = 3, tune_chunk = kChunkMax, tune_leaf_batch = kLeafBatch, tune_refill_idle = kRefillIdle, tune_wide = 1;
+	uint32_t tune_denoise_staged = kAtrousStagedMaxStep;   // MIRT_TUNE_DENOISE_STAGED: largest a-trous step whose pass stages its block in LDS (0: none do; profiles/denoise.txt)
 	bool debug_poison_contrib = false;   // MIRT_DEBUG_POISON_CONTRIB=1: fill every contribution buffer with a NaN pattern before each batch (tests: every word is written)
 	// profiling
 	std::vector<TimedLaunch> pending;
@@ -1225,6 +1228,7 @@ int mirt_create(int device, mirt_ctx** out) {
 	c->device = device;
 	if (const char* e = std::getenv("MIRT_TUNE_CHUNK")) c->tune_chunk = static_cast<uint32_t>(std::min(std::max(std::atoi(e), 64), 65536)) & ~63u;
 	if (const char* e = std::getenv("MIRT_TUNE_REFILL_IDLE")) c->tune_refill_idle = static_cast<uint32_t>(std::min(std::max(std::atoi(e), 1), 64));
+	if (const char* e = std::getenv("MIRT_TUNE_DENOISE_STAGED")) c->tune_denoise_staged = static_cast<uint32_t>(std::min(std::max(std::atoi(e), 0), static_cast<int>(kAtrousStagedMaxStep)));
 	if (const char* e = std::getenv("MIRT_TUNE_WIDE")) c->tune_wide = std::atoi(e) != 0 ? 1u : 0u;
 	if (const char* e = std::getenv("MIRT_TUNE_LEAF_BATCH")) c->tune_leaf_batch = static_cast<uint32_t>(std::min(std::max(std::atoi(e), 1), 64));
 	if (const char* e = std::getenv("MIRT_TUNE_TRACE_WGS")) c->tune_trace_wgs = std::atoi(e) == 1 ? 1u : 2u;
@@ -1251,7 +1255,7 @@ int mirt_destroy(mirt_ctx* c) {
 	DeviceBuffer* bufs[] = { &c->recs, &c->recs_wide, &c->spheres, &c->prim_mat, &c->light_sphere, &c->light_emit, &c->mat_albedo, &c->mat_emission,
 	                         &c->mat_ggx, &c->mat_glass, &c->mat_merged, &c->hdri, &c->sky_table, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
 	                         &c->cand, &c->cand_listed, &c->cand_words, &c->noise_rec, &c->noise_hist, &c->noise_above,
-	                         &c->tile_frozen, &c->active_list, &c->tile_counts };
+	                         &c->dn_cv[0], &c->dn_cv[1], &c->dn_gd, &c->dn_mu, &c->tile_frozen, &c->active_list, &c->tile_counts };
 	for (DeviceBuffer* b : bufs) b->release();
 	if (c->frame_host) (void)hipHostFree(c->frame_host);
 	if (c->cand_built) (void)hipEventDestroy(c->cand_built);
@@ -1462,6 +1466,7 @@ int mirt_resize(mirt_ctx* c, uint32_t width, uint32_t height) {
 	{ const int dr = drop_and_wait(c); if (dr) return dr; }                         // the accumulator is about to be zeroed (Renderer.hpp:61-62)
 	c->width = width; c->height = height;
 	c->cand_valid = false;                                                             // other pixels
+	for (DeviceBuffer* b : { &c->dn_cv[0], &c->dn_cv[1], &c->dn_gd, &c->dn_mu }) b->release();   // mirt_render_atrous allocates them again at the new size
 	c->h_tiles = width / MIRT_TILE_ROOT; c->v_tiles = height / MIRT_TILE_ROOT;          // Renderer.hpp:59-60
 	set_tile_map(c, TileMap::of_range(0u, c->h_tiles, width), c->h_tiles * c->v_tiles);
 	HIP_TRY(c, c->framebuffer.ensure(std::max<size_t>(static_cast<size_t>(width) * height, 1) * sizeof(float4)));
@@ -1651,6 +1656,66 @@ int mirt_render(mirt_ctx* c, float* rgba_host) {
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	if (whole) std::memcpy(rgba_host, c->frame_host, frame_floats * sizeof(float));   // every pixel is this context's
 	else copy_owned_tiles(tile_map(c), c->n_tiles, 4u, c->frame_host, rgba_host);                 // only this context's tiles
+	return MIRT_OK;
+}
+
+// ---- variance-guided a-trous denoised resolve (denoise.hpp; the definition is in mirt.h) ------------------------------------------
+int mirt_atrous_defaults(mirt_denoise_params* out) {
+	if (!out) return MIRT_ERR_ARG;
+	*out = mirt_denoise_params{ 5u, 5u, 1u, 4.0f, 0.05f, 1e-4f, 1.0f / 256.0f };
+	return MIRT_OK;
+}
+
+int mirt_render_atrous(mirt_ctx* c, const mirt_denoise_params* p, float* rgba_host) {
+	int r = check_ready(c); if (r) return r;
+	if (!p) return fail(c, MIRT_ERR_ARG, "params is NULL");
+	if (!rgba_host) return fail(c, MIRT_ERR_ARG, "rgba_host is NULL");
+	if (p->iterations > 8u || p->normal_squarings > 8u || p->demodulate > 1u)
+		return fail(c, MIRT_ERR_ARG, "denoise: iterations %u and normal_squarings %u must be 0..8, demodulate %u 0 or 1", p->iterations, p->normal_squarings, p->demodulate);
+	if (!mirt_noise_host::finite_nonneg(p->sigma_lum) || !mirt_noise_host::finite_nonneg(p->sigma_depth))
+		return fail(c, MIRT_ERR_ARG, "denoise: sigma_lum %g and sigma_depth %g must be finite and >= 0", static_cast<double>(p->sigma_lum), static_cast<double>(p->sigma_depth));
+	if (!std::isfinite(p->lum_floor) || !(p->lum_floor > 0.0f)) return fail(c, MIRT_ERR_ARG, "denoise: lum_floor %g must be finite and > 0", static_cast<double>(p->lum_floor));
+	if (!std::isfinite(p->albedo_floor)) return fail(c, MIRT_ERR_ARG, "denoise: albedo_floor is not finite");
+	const uint32_t k = c->policy.buckets;
+	if (!c->aov_on) return fail(c, MIRT_ERR_STATE, "denoise: AOVs are off (mirt_set_aov)");
+	if (k < 2u) return fail(c, MIRT_ERR_STATE, "denoise: the variance guide needs buckets >= 2, the policy has %u", k);
+	if (c->first_tile != 0u || c->stride_tiles != 0u || c->n_tiles != c->h_tiles * c->v_tiles)
+		return fail(c, MIRT_ERR_STATE, "denoise: the context owns %u of the image's %u tiles; the stencil reads across tile borders, so it needs all of them", c->n_tiles, c->h_tiles * c->v_tiles);
+	const uint32_t issued = c->accumulations + c->deferred;
+	if (issued == 0 || (issued % k) != 0) return MIRT_NOT_READY;                                    // as mirt_render
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }
+	if (c->n_tiles == 0) return MIRT_OK;
+	const float scale = c->camera.exposure / static_cast<float>(c->accumulations / k);              // Renderer.hpp:439, as mirt_render
+	const uint32_t n_pix = c->n_tiles * kTileSize;
+	const size_t image_bytes = static_cast<size_t>(c->width) * c->height * sizeof(float4);
+	for (DeviceBuffer* b : { &c->dn_cv[0], &c->dn_cv[1], &c->dn_gd, &c->dn_mu }) HIP_TRY(c, b->ensure(image_bytes));
+	const uint32_t* counts = nullptr;
+	if ((r = upload_tile_counts(c, &counts))) return r;
+	const TileMap m = tile_map(c);
+	{ Bracket t(c, MIRT_K_RESOLVE);
+	  hipLaunchKernelGGL(k_denoise_prepare, dim3(c->n_tiles), dim3(kTileSize), 0, c->stream, c->accumulator.as<float>(), c->aov.as<float>(), c->dn_cv[0].as<float4>(),
+	                     c->dn_gd.as<float4>(), c->dn_mu.as<float4>(), m, k, scale, static_cast<float>(c->accumulations), counts, c->camera.exposure, p->demodulate, p->albedo_floor); }
+	HIP_TRY(c, hipGetLastError());
+	const DenoiseDev dev{ p->sigma_lum, p->sigma_depth, p->lum_floor, p->normal_squarings };
+	uint32_t cur = 0;
+	for (uint32_t i = 0; i < p->iterations; i++, cur ^= 1u) {
+		const uint32_t step = 1u << i;
+		const bool staged = step <= c->tune_denoise_staged;
+		Bracket t(c, MIRT_K_RESOLVE);
+		hipLaunchKernelGGL(staged ? k_atrous<true> : k_atrous<false>, dim3(c->h_tiles, c->v_tiles), dim3(kAtrousBlock * kAtrousBlock), 0, c->stream,
+		                   c->dn_cv[cur].as<float4>(), c->dn_gd.as<float4>(), c->dn_cv[cur ^ 1u].as<float4>(), c->width, c->h_tiles * kAtrousBlock, c->v_tiles * kAtrousBlock, step, dev);
+	}
+	HIP_TRY(c, hipGetLastError());
+	{ Bracket t(c, MIRT_K_RESOLVE);
+	  hipLaunchKernelGGL(k_denoise_finish, dim3(grid_for(c, n_pix)), dim3(kBlock), 0, c->stream, c->dn_cv[cur].as<float4>(), c->dn_mu.as<float4>(), c->framebuffer.as<float4>(), n_pix, m); }
+	HIP_TRY(c, hipGetLastError());
+	// the frame leaves as mirt_render's does (the framebuffer is scratch: every resolve writes all of the context's tiles before it is read)
+	const size_t frame_floats = static_cast<size_t>(c->width) * c->height * 4;
+	const bool whole = c->width == c->h_tiles * MIRT_TILE_ROOT && c->height == c->v_tiles * MIRT_TILE_ROOT;
+	HIP_TRY(c, hipMemcpyAsync(c->frame_host, c->framebuffer.ptr, frame_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	if (whole) std::memcpy(rgba_host, c->frame_host, frame_floats * sizeof(float));
+	else copy_owned_tiles(m, c->n_tiles, 4u, c->frame_host, rgba_host);
 	return MIRT_OK;
 }
 

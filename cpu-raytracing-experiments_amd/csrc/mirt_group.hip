@@ -554,5 +554,18 @@ int mirt_group_render(mirt_group* g, float* rgba_host) {
 	const int rr = mirt_render(g->full, rgba_host);
 	return rr < 0 ? gfail(g, rr, "mirt_render on the gather context: %s", mirt_last_error(g->full)) : rr;
 }
+// Gathers as mirt_group_render does; the gather context then holds the accumulator, the AOV slab and the counts of the whole image.
+int mirt_group_render_atrous(mirt_group* g, const mirt_denoise_params* params, float* rgba_host) {
+	if (!g || !params || !rgba_host) return MIRT_ERR_ARG;
+	RETURN_IF_SINGLE(g, mirt_render_atrous(ctx, params, rgba_host));
+	if (!g->aov) return gfail(g, MIRT_ERR_STATE, "denoise: AOVs are off (mirt_group_set_aov)");
+	if (g->buckets < 2u) return gfail(g, MIRT_ERR_STATE, "denoise: the variance guide needs buckets >= 2, the policy has %u", g->buckets);
+	const uint32_t acc = accumulations_of(g);
+	if (acc == 0 || acc % g->buckets != 0) return MIRT_NOT_READY;       // as mirt_group_render: nothing is gathered for a frame that is not due
+	const int rc = mirt_group_gather(g);
+	if (rc) return rc;
+	const int rr = mirt_render_atrous(g->full, params, rgba_host);      // the argument rules are the gather context's
+	return rr < 0 ? gfail(g, rr, "mirt_render_atrous on the gather context: %s", mirt_last_error(g->full)) : rr;
+}
 
 } // extern "C"

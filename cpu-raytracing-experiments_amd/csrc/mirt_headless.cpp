@@ -8,7 +8,9 @@
 //                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm] [--aov PREFIX] [--light-ris M] [--transmission] [--sky-sampling] [--closures 0,1,1,...] [--ggx-pdf]
 //                 [--f-number F] [--focus-distance D] [--unit-mm U] [--focus-pixel X,Y]
 //                 [--until-noise T] [--noise-quantile Q] [--noise-floor F] [--check-every N] [--max-accumulations M] [--noise-out map.pfm]
-//                 [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm]
+//                 [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm] [--denoise [ITERATIONS]] [--denoise-plain-out plain.hdr|plain.pfm]
+// --denoise writes to --out the variance-guided à-trous denoised resolve of the last frame (mirt_render_atrous with its defaults; ITERATIONS, 0 .. 8,
+// replaces their pass count) instead of the plain one; it implies the first-hit AOVs, which guide it.  --denoise-plain-out writes the plain frame beside it.
 // --adaptive T renders with per-tile adaptive sampling (mirt_accumulate_adaptive): like --until-noise, but every 16 x 16 tile stops taking samples
 // as soon as ITS Q-quantile is <= T (not before --min-accumulations, default 0); ends when every tile has stopped or at --max-accumulations.
 // --counts-out writes the per-pixel sample count (each tile's count, painted over its pixels) as a one-channel PFM.  Adds a line
@@ -200,7 +202,9 @@ int main(int argc, char** argv) {
 	uint32_t min_accumulations = 0, light_ris = 0;
 	bool transmission = false, sky_sampling = false, ggx_pdf = false;
 	std::vector<uint8_t> closures;
-	std::string counts_out;
+	std::string counts_out, plain_out;
+	bool denoise = false;
+	int denoise_iterations = -1;                                               // -1: the default
 	if (argc == 4 && std::string(argv[1]) == "--convert-hdr") {
 		// file-format check without a GPU: read a picture like stbi_loadf does (top-down) and store it again like Image::Store does (which
 		// flips, so the rows are handed over bottom-up): the output decodes to the same texels
@@ -220,12 +224,13 @@ int main(int argc, char** argv) {
 			          "              [--light-ris M] [--transmission] [--sky-sampling] [--closures 0,1,1,...] [--ggx-pdf]\n"
 			          "              [--f-number F] [--focus-distance D] [--unit-mm U] [--focus-pixel X,Y]\n"
 			          "              [--until-noise T] [--noise-quantile Q] [--noise-floor F] [--check-every N] [--max-accumulations M] [--noise-out map.pfm]\n"
-			          "              [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm]\n"
+			          "              [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm] [--denoise [ITERATIONS]] [--denoise-plain-out FILE]\n"
 			          "mirt_headless --convert-hdr in.hdr out.hdr\n"
 			          "  --sky-sampling  the environment map (--hdri, --ambient) is one more light of next event estimation, drawn by importance (mirt_set_sky_sampling)\n"
 			          "  --ggx-pdf  the GGX closure's visible-normal pdf in the MIS weights: emitters and the sampled sky are weighed two ways on GGX surfaces (mirt_set_ggx_pdf)\n"
 			          "  --light-ris M   the NEE light is picked among M candidates by resampled importance sampling (mirt_set_light_ris)\n"
 			          "  --transmission  materials that carry a transmission render as glass (mirt_set_transmission)\n"
+			          "  --denoise [N]   --out receives the variance-guided a-trous denoised resolve (N passes, default 5; implies the first-hit AOVs); --denoise-plain-out FILE: the plain frame\n"
 			          "  --closures LIST the closure of material 0, 1, ...: 0 Lambertian, 1 GGX; materials beyond the list take --brdf (mirt_set_material_closures)");
 			return 0;
 		}
@@ -260,6 +265,8 @@ int main(int argc, char** argv) {
 		else if (a == "--adaptive") { noise_target = static_cast<float>(std::atof(next())); adaptive = noise_report = true; }
 		else if (a == "--min-accumulations") min_accumulations = static_cast<uint32_t>(std::atoi(next()));
 		else if (a == "--counts-out") counts_out = next();
+		else if (a == "--denoise") { denoise = true; if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoise_iterations = std::atoi(argv[++i]); }
+		else if (a == "--denoise-plain-out") { plain_out = next(); denoise = true; }
 		else if (a == "--devices") { devices.clear(); for (const char* p = next(); *p;) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p == ',') p++; } if (devices.empty()) return 2; }
 		else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
 	}
@@ -281,7 +288,7 @@ int main(int argc, char** argv) {
 		Renderer renderer{ scene, policy, devices };
 		renderer.SetGlossDecay(gloss_decay);
 		renderer.SetStreamOrder(exact_stream_order);
-		if (!aov_prefix.empty()) renderer.SetAOV(true);
+		if (!aov_prefix.empty() || denoise) renderer.SetAOV(true);
 		renderer.SetLightRis(light_ris);
 		renderer.SetTransmission(transmission);
 		renderer.SetSkySampling(sky_sampling);
@@ -342,11 +349,22 @@ int main(int argc, char** argv) {
 		            scene_name.c_str(), scene.geometry.size(), scene.acceleration_structure.nodes.size(), scene.lighting_acceleration.prims.size(), w, h,
 		            renderer.accumulations(), (unsigned long long)c.rays, (unsigned long long)c.shadow_rays, (unsigned long long)c.terminated,
 		            (unsigned long long)c.dropped, sec, c.rays / sec / 1e6, (unsigned long long)hsh, have_frame ? "true" : "false", frames_due.c_str(), (unsigned long long)frame_hsh, devices.size(), renderer.gather_ms());
-		if (!out.empty() && have_frame) {
-			const bool as_hdr = out.size() >= 4 && out.compare(out.size() - 4, 4, ".hdr") == 0;
-			const bool ok = as_hdr ? mirt_hdr::write_flipped(out, renderer.GetFrame().data(), w, h) : write_pfm(out, renderer.GetFrame(), w, h);
-			if (!ok) { std::fprintf(stderr, "cannot write %s\n", out.c_str()); return 1; }
+		auto write_frame = [&](const std::string& path, const std::vector<float>& frame) {
+			const bool as_hdr = path.size() >= 4 && path.compare(path.size() - 4, 4, ".hdr") == 0;
+			const bool ok = as_hdr ? mirt_hdr::write_flipped(path, frame.data(), w, h) : write_pfm(path, frame, w, h);
+			if (!ok) std::fprintf(stderr, "cannot write %s\n", path.c_str());
+			return ok;
+		};
+		if (denoise && have_frame) {                                   // the denoised resolve of the accumulator the last frame shows
+			mirt_denoise_params dp = Renderer::DenoiseDefaults();
+			if (denoise_iterations >= 0) dp.iterations = static_cast<uint32_t>(denoise_iterations);
+			const std::vector<float> filtered = renderer.RenderDenoised(dp);
+			if (filtered.empty()) { std::fprintf(stderr, "mirt_headless: no denoised frame: %u accumulations are not a positive multiple of %u buckets\n", renderer.accumulations(), policy.buckets); return 1; }
+			std::printf("{\"denoise\": {\"iterations\": %u, \"frame_fnv1a\": \"%016llx\"}}\n", dp.iterations, (unsigned long long)fnv1a(filtered));
+			if (!out.empty() && !write_frame(out, filtered)) return 1;
+			if (!plain_out.empty() && !write_frame(plain_out, renderer.GetFrame())) return 1;
 		}
+		else if (!out.empty() && have_frame && !write_frame(out, renderer.GetFrame())) return 1;
 		if (!aov_prefix.empty()) {
 			const struct { int which; const char* name; uint32_t channels; } outputs[3] = { { MIRT_AOV_DEPTH, "depth", 1 }, { MIRT_AOV_NORMAL, "normal", 3 }, { MIRT_AOV_ALBEDO, "albedo", 3 } };
 			for (const auto& o : outputs) {

@@ -241,6 +241,17 @@ public:
 		if (rc != MIRT_OK) img.clear();
 		return img;
 	}
+	// Variance-guided à-trous denoised resolve (mirt.h, mirt_render_atrous): the frame Render() resolves, filtered under the guidance of the first-hit
+	// AOVs and each pixel's own bucket variance.  Needs SetAOV(true) and buckets >= 2; changes no state.  width * height * 4 floats, row 0 = y 0;
+	// empty while Render() would return false.
+	static mirt_denoise_params DenoiseDefaults() { mirt_denoise_params p{}; mirt_atrous_defaults(&p); return p; }
+	std::vector<float> RenderDenoised(const mirt_denoise_params& params = DenoiseDefaults()) {
+		std::vector<float> img(static_cast<size_t>(width) * height * 4, 0.0f);
+		const int rc = mirt_group_render_atrous(group_, &params, img.data());
+		check(rc, "mirt_group_render_atrous");
+		if (rc != MIRT_OK) img.clear();
+		return img;
+	}
 	// Per-pixel noise estimate from the buckets (mirt.h, mirt_noise): the relative standard error of the mean of the bucket means, read from the
 	// members' own slabs without a gather.  ready = false (and nothing filled) while accumulations is 0 or not a multiple of `buckets`.
 	struct NoiseResult {

@@ -524,6 +524,66 @@ typedef struct mirt_adaptive_report {
  * in exact stream order.  report may be NULL. */
 int mirt_accumulate_adaptive(mirt_ctx* ctx, const mirt_stop_rule* rule, uint32_t min_accumulations, mirt_adaptive_report* report);
 
+/* ---- variance-guided à-trous denoised resolve from the buckets and the first-hit AOVs ------------------------------------------------
+ * A second resolve beside mirt_render: an edge-avoiding à-trous wavelet filter (Dammertz et al. 2010) over the median-of-buckets frame, guided
+ * by the first-hit AOVs and, as in SVGF (Schied et al. 2017), by each pixel's own variance — here the spread of its buckets, the quantity of
+ * mirt_noise — so that a converged pixel is left alone and a noisy one is smoothed.  The reference has no denoiser; nothing of it is replayed.
+ * It READS the accumulator slab, the AOV slab and the per-tile counts and changes no state (accumulator, AOVs, counters, frozen tiles; what
+ * mirt_render returns afterwards).  It writes what mirt_render writes: RGBA f32, row-major, row 0 = y 0, ACES applied last, A = 1.
+ * THE DEFINITION.  Every operation binary32, one rounding each, unfused, in the stated order, IEEE division and square root; the exponentials
+ * of the two papers are replaced by Cauchy falloffs 1 / (1 + t t), so that no operation is left to a library.  lum(r, g, b) =
+ * (0.2126f * r + 0.7152f * g) + 0.0722f * b.  "The image" is the w x h pixels its tiles cover (w = 16 (width / 16), h = 16 (height / 16)).
+ * For pixel p, n = its tile's sample count (mirt_tile_counts), k = buckets, scale = exposure / (float)(n / k):
+ *   1. signal     s_c = scale * median_k(the k bucket words of channel c): mirt_render's operations up to, not including, the tonemapping.
+ *   2. variance   y_j, mean and var exactly as mirt_noise defines them (above); v = var / (float)k, the variance of the mean.
+ *   3. guides     mirt_render_aov's three outputs: z = depth_sum / (float)n;  N = normalize(normal_sum), (0,0,0) where the sum has no length;
+ *                 a_c = albedo_sum_c / (float)n.
+ *   4. modulator  m_c = (demodulate && a_c >= albedo_floor) ? a_c : 1.0f;   x_c = s_c / m_c;   lm = lum(m_r, m_g, m_b);   v = v / (lm * lm).
+ *   5. usability  p is USABLE when x_r, x_g, x_b, v, z, N.x, N.y, N.z are all finite and v >= 0.  Decided here, once; it never changes.  An
+ *                 unusable pixel is never taken as a tap, and as a centre it passes through every step: its output is tonemapping(s), the word
+ *                 mirt_render writes.
+ *   6. iteration  i = 0 .. iterations - 1, step = 1 << i, from buffer A (x, v) into buffer B, then the two swap.  For a usable centre p:
+ *        gv   the smoothed variance: the kernel (1/16 1/8 1/16; 1/8 1/4 1/8; 1/16 1/8 1/16) over the current v of the pixels at distance 1 —
+ *             never at distance `step` — that are inside the image, usable and, the centre aside, turned the same way (nn > 0, or all six normal
+ *             components zero; nn as below: variance does not cross a crease or a silhouette), dy = -1 .. 1 outside, dx = -1 .. 1 inside:
+ *             G = (((g_0 v_0) + g_1 v_1) + ...), K = ((g_0 + g_1) + ...), each sum starting from the first pixel taken; gv = G / K.
+ *        sd   = sigma_lum * sqrt(gv) + lum_floor;      l_p = lum(x_p).
+ *        taps (dy, dx), dy = -2 .. 2 outside, dx = -2 .. 2 inside, q = p + step * (dx, dy); a q outside the image or unusable is skipped.
+ *             h = (1/16, 1/4, 3/8, 1/4, 1/16).  The centre tap: w = 9/64.  Any other tap:
+ *               nn = (N_p.x * N_q.x + N_p.y * N_q.y) + N_p.z * N_q.z
+ *               wn = 1 when all six normal components are zero (two miss pixels); else wn = (nn > 0 ? nn : 0), then normal_squarings times wn = wn * wn
+ *               tz = fabsf(z_p - z_q) / (sigma_depth * ((z_p < z_q ? z_q : z_p) * (float)(step * max(|dx|, |dy|))) + FLT_MIN)
+ *               tl = fabsf(l_p - lum(x_q)) / sd
+ *               w  = (((h[dy] * h[dx]) * wn) * (1.0f / (1.0f + tz * tz))) * (1.0f / (1.0f + tl * tl))
+ *             W = ((w_0 + w_1) + ...),  X_c = ((w_0 x_0c + w_1 x_1c) + ...),  V = (((w_0 w_0) v_0 + (w_1 w_1) v_1) + ...), each sum starting
+ *             from the first tap taken.  x'_c = X_c / W;  v' = V / (W * W).  W >= 9/64: the centre tap is always taken.
+ *   7. output     out_c = x_c * m_c, tonemapping(out), A = 1.
+ * sigma_depth is the relative change of depth allowed per pixel of tap distance; sigma_lum counts standard deviations of the pixel.
+ * TWO CONSEQUENCES the tests rest on: (a) iterations = 0 with demodulate = 0 writes mirt_render's frame word for word (m = 1: s / 1 and s * 1
+ * are s).  (b) The result is a function of the two slabs and the counts alone: it does not depend on policy.max_batch / streams, on the tree,
+ * or on how the slabs got there — rendered, loaded (mirt_load_accumulator, mirt_load_aov, mirt_load_tile_counts) or gathered by a group.
+ * iterations and normal_squarings in 0 .. 8, demodulate 0 or 1, sigma_lum and sigma_depth finite and >= 0, lum_floor finite and > 0, albedo_floor
+ * finite, no NULL pointer: else MIRT_ERR_ARG.  MIRT_ERR_STATE while AOVs are off, with buckets < 2, and for a context that does not own every
+ * tile of the image: a 5 x 5 stencil at step 16 reads 32 pixels into its neighbours' tiles, so a partial context is refused, not approximated
+ * (a group resolves on its gather context).  Exact stream order has no AOVs, hence MIRT_ERR_STATE there too.  Then MIRT_NOT_READY, with rgba_host
+ * untouched, under mirt_render's condition.  Launches anything deferred and waits for the GPU first; kernel time is booked under MIRT_K_RESOLVE.
+ * Scratch: four float4 images (x and v twice, the guides, the modulator), allocated by the first call, released by mirt_resize and mirt_destroy —
+ * 4 x 268 MB at 4096 x 4096.  Kernels: csrc/denoise.hpp; binary32 numpy twin: tests/denoise_twin.py. */
+typedef struct mirt_denoise_params {
+	uint32_t iterations;        /* 0..8 à-trous passes, step 1, 2, 4, ...; 0 = no filtering */
+	uint32_t normal_squarings;  /* 0..8: normal weight = max(0, n_p.n_q)^(2^this) */
+	uint32_t demodulate;        /* 0 / 1: filter colour / albedo, multiply back afterwards */
+	float    sigma_lum;         /* luminance stop, in standard deviations of the pixel */
+	float    sigma_depth;       /* depth stop: relative depth change allowed per pixel of tap distance */
+	float    lum_floor;         /* > 0: added to the luminance denominator */
+	float    albedo_floor;      /* a channel is demodulated only where its albedo >= this */
+} mirt_denoise_params;
+/* (The entry points are named after the filter, not after what it removes: the noise section's set of entry points is closed and pinned by its
+ * interface test, as mirt_tile_above's note says.  The host layers call them render_denoised / denoise_defaults.)
+ * Pure host code, no context: iterations 5, normal_squarings 5, demodulate 1, sigma_lum 4, sigma_depth 0.05, lum_floor 1e-4, albedo_floor 1/256. */
+int mirt_atrous_defaults(mirt_denoise_params* out);
+int mirt_render_atrous(mirt_ctx* ctx, const mirt_denoise_params* params, float* rgba_host);
+
 int mirt_get_counters(mirt_ctx* ctx, mirt_counters* out);
 int mirt_get_kernel_times(mirt_ctx* ctx, mirt_kernel_times* out, int reset);
 /* HIP stream the context launches on (hipStream_t), for callers that time with their own events. */
@@ -584,6 +644,10 @@ int mirt_group_set_aov(mirt_group* group, uint32_t on);                         
 int mirt_group_aov_floats(const mirt_group* group, size_t* n_floats);            /* of the whole image: tiles x 7 x 256; 0 while off */
 int mirt_group_read_aov(mirt_group* group, float* host_dst);                     /* whole image, [tile][plane 0..6][256] in LaunchIndex order */
 int mirt_group_render_aov(mirt_group* group, int which, float* out);             /* mirt_render_aov of the whole frame */
+/* mirt_render_atrous of the whole frame: gathers as mirt_group_render does, then resolves on the gather context, which holds the accumulator,
+ * the AOV slab and the per-tile counts of the whole image — the single context's words.  MIRT_ERR_STATE (AOVs off, buckets < 2) and MIRT_NOT_READY
+ * are decided before the gather; the argument rules are then the gather context's. */
+int mirt_group_render_atrous(mirt_group* group, const mirt_denoise_params* params, float* rgba_host);
 /* mirt_noise / mirt_accumulate_until of the whole image.  NO gather: every member runs mirt_noise on its own slab; histograms and counts add
  * as integers, the maximum is exact, the members' tile records are un-interleaved on the host into LaunchIndex order (tile_out: 4 floats per
  * tile of the image), each member writes its own tiles of map_out, and the mean is the double sum over those records in LaunchIndex order.
