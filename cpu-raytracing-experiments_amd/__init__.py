@@ -91,6 +91,22 @@ class DenoiseParams(C.Structure):
         return {n: (int if t is C.c_uint32 else float)(getattr(self, n)) for n, t in self._fields_}
 
 
+class TemporalParams(C.Structure):
+    """mirt_temporal_params"""
+    _fields_ = [("max_ratio", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float), ("update", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: (int if t is C.c_uint32 else float)(getattr(self, n)) for n, t in self._fields_}
+
+
+class TemporalStats(C.Structure):
+    """mirt_temporal_stats"""
+    _fields_ = [(n, C.c_uint64) for n in ("reprojected", "no_history", "outside", "rejected", "unusable")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 def build(force: bool = False) -> str:
     """Compile csrc/ for gfx950 with hipcc (cross-compiles without a GPU)."""
     args = ["make", "-C", CSRC]
@@ -145,6 +161,10 @@ def load_library():
         "mirt_render_aov": [P, i32, vp],
         "mirt_atrous_defaults": [C.POINTER(DenoiseParams)],
         "mirt_render_atrous": [P, C.POINTER(DenoiseParams), vp],
+        "mirt_temporal_defaults": [C.POINTER(TemporalParams)],
+        "mirt_render_temporal": [P, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), vp, vp, C.POINTER(TemporalStats)],
+        "mirt_drop_history": [P],
+        "mirt_history_info": [P, C.POINTER(u32), C.POINTER(C.c_uint64)],
         "mirt_noise":[P, f, vp, vp, vp, C.POINTER(NoiseStats)],
         "mirt_noise_quantile": [vp, C.c_double, C.POINTER(f)],
         "mirt_accumulate_until": [P, C.POINTER(StopRule), C.POINTER(NoiseStats), C.POINTER(u32)],
@@ -199,6 +219,9 @@ def load_library():
         "mirt_group_read_aov": [G, vp],
         "mirt_group_render_aov": [G, i32, vp],
         "mirt_group_render_atrous": [G, C.POINTER(DenoiseParams), vp],
+        "mirt_group_render_temporal": [G, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), vp, vp, C.POINTER(TemporalStats)],
+        "mirt_group_drop_history": [G],
+        "mirt_group_history_info": [G, C.POINTER(u32), C.POINTER(C.c_uint64)],
         "mirt_group_noise": [G, f, vp, vp, vp, C.POINTER(NoiseStats)],
         "mirt_group_accumulate_until": [G, C.POINTER(StopRule), C.POINTER(NoiseStats), C.POINTER(u32)],
         "mirt_group_freeze_tiles": [G, vp, C.c_size_t],
@@ -316,6 +339,23 @@ def _denoise_params(params: dict) -> DenoiseParams:
     d.update(params)
     return DenoiseParams(int(d["iterations"]), int(d["normal_squarings"]), int(d["demodulate"]), float(d["sigma_lum"]), float(d["sigma_depth"]),
                          float(d["lum_floor"]), float(d["albedo_floor"]))
+
+
+def temporal_defaults() -> dict:
+    """mirt_temporal_defaults (host code, no GPU): the temporal parameters render_temporal() starts from, by name."""
+    p = TemporalParams()
+    rc = load_library().mirt_temporal_defaults(C.byref(p))
+    if rc != MIRT_OK:
+        raise MirtError(f"mirt_temporal_defaults failed ({rc})")
+    return p.as_dict()
+
+
+def _split_temporal_params(params: dict):
+    """render_temporal's keywords -> (mirt_denoise_params, mirt_temporal_params): each name belongs to exactly one of the two sets of defaults."""
+    t = temporal_defaults()
+    own = {k: params[k] for k in params if k in t}
+    t.update(own)
+    return _denoise_params({k: v for k, v in params.items() if k not in own}), TemporalParams(float(t["max_ratio"]), float(t["depth_tol"]), float(t["normal_min"]), int(t["update"]))
 
 
 def adaptive_select(tiles, above, frozen=None, quantile: float = 0.95) -> np.ndarray:
@@ -579,6 +619,40 @@ class _Binding:
             raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
         p = _denoise_params(params)
         return out if self._call("render_atrous", C.byref(p), _ptr(out)) == MIRT_OK else None
+
+    # -- temporal history (mirt.h "temporal history for the denoised resolve") ---------------------------------------
+    temporal_defaults = staticmethod(temporal_defaults)
+
+    def render_temporal(self, out: np.ndarray = None, want_len: bool = False, want_stats: bool = False, **params):
+        """render_denoised() through a history that survives Reset() and camera moves (mirt_render_temporal): the last call's pre-filter result
+        is reprojected through the first-hit depth into the current view, what fails the depth / normal test is rejected, the rest is blended
+        with the new samples by sample count, and the à-trous passes run on the blend.  Keywords: those of render_denoised() plus max_ratio,
+        depth_tol, normal_min, update (temporal_defaults()).  Returns the frame; with want_len / want_stats a tuple (frame[, history_len (height,
+        width) f32][, stats dict: reprojected, no_history, outside, rejected, unusable]).  None, and nothing written, while Render() would
+        return False.  The shading switches do not drop the history: after changing the estimand call drop_history().  (A group: on the
+        gather context, after a gather.)"""
+        shape = (self.height, self.width, 4)
+        if out is None:
+            out = np.zeros(shape, dtype=np.float32)
+        elif out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
+        dp, tp = _split_temporal_params(params)
+        length = np.zeros(shape[:2], dtype=np.float32) if want_len else None
+        st = TemporalStats()
+        if self._call("render_temporal", C.byref(dp), C.byref(tp), _ptr(out), _ptr(length) if want_len else None, C.byref(st)) != MIRT_OK:
+            return None
+        extra = ([length] if want_len else []) + ([st.as_dict()] if want_stats else [])
+        return (out, *extra) if extra else out
+
+    def drop_history(self):
+        """Forget the history of render_temporal() (mirt_drop_history); the next call starts from the frame's own samples."""
+        self._call("drop_history")
+
+    def history_info(self) -> dict:
+        """{"valid": a history is held, "bytes": device bytes of its three images} (mirt_history_info)."""
+        valid, nbytes = C.c_uint32(0), C.c_uint64(0)
+        self._call("history_info", C.byref(valid), C.byref(nbytes))
+        return {"valid": bool(valid.value), "bytes": int(nbytes.value)}
 
     # -- noise estimate (mirt.h "per-pixel noise estimate") ----------------------------------------------------
     noise_quantile = staticmethod(noise_quantile)

@@ -10,6 +10,7 @@
 #include "../../include/mirt.h"
 #include "kernels.hpp"
 #include "denoise.hpp"
+#include "temporal.hpp"
 #include "bvh_layout.hpp"
 #include "bvh_build.hpp"
 #include "lbvh_build.hpp"
@@ -148,6 +149,13 @@ struct mirt_ctx {
 	DeviceBuffer noise_above;        // mirt_tile_above: one count per local tile
 	DeviceBuffer noise_rec, noise_hist;   // mirt_noise: one float4 record per local tile, MIRT_NOISE_BINS histogram words (allocated by the first call)
 	DeviceBuffer dn_cv[2], dn_gd, dn_mu;  // mirt_render_atrous (denoise.hpp): full-image float4 buffers, cv ping-pong; allocated by the first call, released by mirt_resize
+	// mirt_render_temporal (temporal.hpp): the history — (x, v), the guides and the length in samples of the last call with update = 1, the camera
+	// and the demodulation settings it was taken under — plus one float image of scratch for the lengths a call writes and the five class counts.
+	DeviceBuffer th_x, th_g, th_n, th_len, th_stats;
+	bool th_valid = false;
+	CameraParams th_cam{};
+	uint32_t th_demodulate = 0, th_width = 0, th_height = 0;
+	float th_albedo_floor = 0.0f;
 	std::vector<PipeSlot> slots;     // batches in flight (policy.streams)
 	uint64_t planned_for = 0;        // local pixel count batch_mem_cap was planned for (0 = plan again)
 	uint32_t batch_mem_cap = 256;     // accumulations per batch the device memory allows (lowered by ensure_streams when the plan does not fit)
@@ -496,6 +504,11 @@ bool lens_on(const mirt_ctx* c) { return c->lens.aperture > 0.0f; }
 
 // The context's n_tiles local tiles in the image (tile_map.hpp).
 TileMap tile_map(const mirt_ctx* c) { return TileMap{ c->first_tile, c->run_tiles, c->stride_tiles, c->h_tiles, c->width }; }
+// The history of mirt_render_temporal goes (mirt.h "history lifetime").  The caller has made the context's device the current one.
+void drop_history(mirt_ctx* c) {
+	for (DeviceBuffer* b : { &c->th_x, &c->th_g, &c->th_n, &c->th_len }) b->release();
+	c->th_valid = false;
+}
 void set_tile_map(mirt_ctx* c, const TileMap& m, uint32_t n_tiles) { c->first_tile = m.first_tile; c->run_tiles = m.run_tiles; c->stride_tiles = m.stride_tiles; c->n_tiles = n_tiles; }
 
 // mirt_set_sky_sampling changes the kernels launched only where its light can be drawn and can carry something.
@@ -1255,7 +1268,8 @@ int mirt_destroy(mirt_ctx* c) {
 	DeviceBuffer* bufs[] = { &c->recs, &c->recs_wide, &c->spheres, &c->prim_mat, &c->light_sphere, &c->light_emit, &c->mat_albedo, &c->mat_emission,
 	                         &c->mat_ggx, &c->mat_glass, &c->mat_merged, &c->hdri, &c->sky_table, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
 	                         &c->cand, &c->cand_listed, &c->cand_words, &c->noise_rec, &c->noise_hist, &c->noise_above,
-	                         &c->dn_cv[0], &c->dn_cv[1], &c->dn_gd, &c->dn_mu, &c->tile_frozen, &c->active_list, &c->tile_counts };
+	                         &c->dn_cv[0], &c->dn_cv[1], &c->dn_gd, &c->dn_mu, &c->tile_frozen, &c->active_list, &c->tile_counts,
+	                         &c->th_x, &c->th_g, &c->th_n, &c->th_len, &c->th_stats };
 	for (DeviceBuffer* b : bufs) b->release();
 	if (c->frame_host) (void)hipHostFree(c->frame_host);
 	if (c->cand_built) (void)hipEventDestroy(c->cand_built);
@@ -1285,6 +1299,7 @@ int mirt_set_scene(mirt_ctx* c, const mirt_sphere* geometry, const mirt_sphere* 
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	c->cand_valid = false;                                                             // spheres or tree changed (a node-only update included)
 	commit_scene(c, a, tree);
+	drop_history(c);                                                                   // other surfaces: nothing of the old view may be reprojected onto them
 	c->glass_host = t.gls; c->scene_has_glass = has_glass(t.gls);
 	c->alb_host = t.alb; c->ggx_host = t.ggx; c->mat_merged_valid = false;
 	if (c->sky_sampling) { HIP_TRY(c, sync_all(c)); if ((r = build_sky_table(c))) return r; }      // (a batch in flight on another stream may read the old table)
@@ -1359,6 +1374,7 @@ int mirt_set_policy(mirt_ctx* c, const mirt_policy* p) {
 	if (p->brdf != c->policy.brdf) c->mat_merged_valid = false;                     // (the closure of the materials beyond the table's end)
 	c->policy = *p;
 	if (replan) c->planned_for = 0;
+	if (realloc_acc) drop_history(c);                                               // its lengths count samples of another bucket layout
 	if (realloc_acc && c->n_tiles) { int r = alloc_accumulator(c); if (r) return r; }
 	return MIRT_OK;
 }
@@ -1467,6 +1483,7 @@ int mirt_resize(mirt_ctx* c, uint32_t width, uint32_t height) {
 	c->width = width; c->height = height;
 	c->cand_valid = false;                                                             // other pixels
 	for (DeviceBuffer* b : { &c->dn_cv[0], &c->dn_cv[1], &c->dn_gd, &c->dn_mu }) b->release();   // mirt_render_atrous allocates them again at the new size
+	drop_history(c);                                                                   // another image
 	c->h_tiles = width / MIRT_TILE_ROOT; c->v_tiles = height / MIRT_TILE_ROOT;          // Renderer.hpp:59-60
 	set_tile_map(c, TileMap::of_range(0u, c->h_tiles, width), c->h_tiles * c->v_tiles);
 	HIP_TRY(c, c->framebuffer.ensure(std::max<size_t>(static_cast<size_t>(width) * height, 1) * sizeof(float4)));
@@ -1486,6 +1503,7 @@ int mirt_set_tile_range(mirt_ctx* c, uint32_t first_tile, uint32_t n_tiles) {
 	if (static_cast<uint64_t>(first_tile) + n_tiles > all) return fail(c, MIRT_ERR_ARG, "tile range [%u,+%u) exceeds %llu tiles", first_tile, n_tiles, (unsigned long long)all);
 	{ const int dr = drop_and_wait(c); if (dr) return dr; }                         // zeroes the accumulator
 	set_tile_map(c, TileMap::of_range(first_tile, c->h_tiles, c->width), n_tiles);
+	drop_history(c);
 	c->cand_valid = false;                                                             // other local pixels
 	return alloc_accumulator(c);
 }
@@ -1495,6 +1513,7 @@ int mirt_set_tile_rows(mirt_ctx* c, uint32_t first_row, uint32_t row_stride) {
 	if (row_stride == 0) return fail(c, MIRT_ERR_ARG, "row_stride must be at least 1");
 	{ const int dr = drop_and_wait(c); if (dr) return dr; }                         // zeroes the accumulator
 	set_tile_map(c, TileMap::of_rows(first_row, row_stride, c->h_tiles, c->width), TileMap::tile_rows_owned(c->v_tiles, first_row, row_stride) * c->h_tiles);
+	drop_history(c);
 	c->cand_valid = false;                                                             // other local pixels
 	return alloc_accumulator(c);
 }
@@ -1666,9 +1685,23 @@ int mirt_atrous_defaults(mirt_denoise_params* out) {
 	return MIRT_OK;
 }
 
-int mirt_render_atrous(mirt_ctx* c, const mirt_denoise_params* p, float* rgba_host) {
+} // extern "C"
+namespace {
+bool unit_orient(const CameraParams& cam) {      // the condition the camera-ray candidate lists put on view.orient (launch_batch)
+	const float qn = cam.orient[0] * cam.orient[0] + cam.orient[1] * cam.orient[1] + cam.orient[2] * cam.orient[2] + cam.orient[3] * cam.orient[3];
+	return std::fabs(qn - 1.0f) < 1e-4f;
+}
+// mirt_render_atrous (tp == NULL: the launches and the words it has always had) and mirt_render_temporal (tp given: k_reproject between the
+// prepare and the first pass, and the history).
+int filtered_resolve(mirt_ctx* c, const mirt_denoise_params* p, const mirt_temporal_params* tp, float* rgba_host, float* history_len, mirt_temporal_stats* stats) {
 	int r = check_ready(c); if (r) return r;
 	if (!p) return fail(c, MIRT_ERR_ARG, "params is NULL");
+	if (tp) {
+		if (!mirt_noise_host::finite_nonneg(tp->max_ratio) || !mirt_noise_host::finite_nonneg(tp->depth_tol))
+			return fail(c, MIRT_ERR_ARG, "temporal: max_ratio %g and depth_tol %g must be finite and >= 0", static_cast<double>(tp->max_ratio), static_cast<double>(tp->depth_tol));
+		if (!(tp->normal_min >= -1.0f && tp->normal_min <= 1.0f)) return fail(c, MIRT_ERR_ARG, "temporal: normal_min %g must lie in [-1, 1]", static_cast<double>(tp->normal_min));
+		if (tp->update > 1u) return fail(c, MIRT_ERR_ARG, "temporal: update %u is neither 0 nor 1", tp->update);
+	}
 	if (!rgba_host) return fail(c, MIRT_ERR_ARG, "rgba_host is NULL");
 	if (p->iterations > 8u || p->normal_squarings > 8u || p->demodulate > 1u)
 		return fail(c, MIRT_ERR_ARG, "denoise: iterations %u and normal_squarings %u must be 0..8, demodulate %u 0 or 1", p->iterations, p->normal_squarings, p->demodulate);
@@ -1696,26 +1729,103 @@ int mirt_render_atrous(mirt_ctx* c, const mirt_denoise_params* p, float* rgba_ho
 	  hipLaunchKernelGGL(k_denoise_prepare, dim3(c->n_tiles), dim3(kTileSize), 0, c->stream, c->accumulator.as<float>(), c->aov.as<float>(), c->dn_cv[0].as<float4>(),
 	                     c->dn_gd.as<float4>(), c->dn_mu.as<float4>(), m, k, scale, static_cast<float>(c->accumulations), counts, c->camera.exposure, p->demodulate, p->albedo_floor); }
 	HIP_TRY(c, hipGetLastError());
+	// The passes go from `src` to `dst`; the two swap, and the buffer that becomes free after the first pass is `spare`.  Plain: cv[0] -> cv[1] -> cv[0].
+	// Temporal: k_reproject writes the blend into cv[1], which the passes only read when it is to become the history (update = 1: the old history's
+	// (x, v) image is the spare then, free as soon as k_reproject has read it).
+	float4 *src = c->dn_cv[0].as<float4>(), *dst = c->dn_cv[1].as<float4>(), *spare = c->dn_cv[0].as<float4>();
+	if (tp) {
+		const size_t len_bytes = static_cast<size_t>(c->width) * c->height * sizeof(float);
+		HIP_TRY(c, c->th_len.ensure(len_bytes));
+		HIP_TRY(c, c->th_stats.ensure(kTemporalStatSlots * kTemporalStatPitch * sizeof(unsigned long long)));
+		if (tp->update) { HIP_TRY(c, c->th_x.ensure(image_bytes)); HIP_TRY(c, c->th_g.ensure(image_bytes)); HIP_TRY(c, c->th_n.ensure(len_bytes)); }
+		HIP_TRY(c, hipMemsetAsync(c->th_stats.ptr, 0, kTemporalStatSlots * kTemporalStatPitch * sizeof(unsigned long long), c->stream));
+		TemporalDev td{};
+		td.cam = c->camera; td.prev = c->th_cam;
+		td.max_ratio = tp->max_ratio; td.depth_tol = tp->depth_tol; td.normal_min = tp->normal_min;
+		// the call takes the history when there is one, of this image and these demodulation settings, and both cameras rotate
+		// (x carries the exposure it was resolved under: a history of another exposure word is in other units)
+		td.take = (c->th_valid && tp->max_ratio > 0.0f && c->th_width == c->width && c->th_height == c->height && c->th_demodulate == p->demodulate &&
+		           std::memcmp(&c->th_albedo_floor, &p->albedo_floor, sizeof(float)) == 0 && std::memcmp(&c->th_cam.exposure, &c->camera.exposure, sizeof(float)) == 0 &&
+		           unit_orient(c->camera) && unit_orient(c->th_cam)) ? 1u : 0u;
+		td.identity = std::memcmp(&c->camera, &c->th_cam, sizeof(CameraParams)) == 0 ? 1u : 0u;
+		if (!td.take) td.prev = c->camera;
+		{ Bracket t(c, MIRT_K_RESOLVE);
+		  hipLaunchKernelGGL(k_reproject, dim3(c->h_tiles, c->v_tiles), dim3(kAtrousBlock * kAtrousBlock), 0, c->stream, c->dn_cv[0].as<float4>(), c->dn_gd.as<float4>(),
+		                     c->th_x.as<float4>(), c->th_g.as<float4>(), c->th_n.as<float>(), c->dn_cv[1].as<float4>(), c->th_len.as<float>(), c->th_stats.as<unsigned long long>(),
+		                     c->width, c->h_tiles * kAtrousBlock, c->v_tiles * kAtrousBlock, counts, c->accumulations, td); }
+		HIP_TRY(c, hipGetLastError());
+		src = c->dn_cv[1].as<float4>(); dst = c->dn_cv[0].as<float4>();
+		spare = tp->update ? c->th_x.as<float4>() : c->dn_cv[1].as<float4>();
+	}
+	// From the second pass on, update = 1 writes into the old history's (x, v) image: a HIP error between here and the renaming below would
+	// leave a history that claims to be valid over a scratch image, so such a return drops it (mirt.h, step 4).
+	struct DropOnError { mirt_ctx* c; bool armed; ~DropOnError() { if (armed) c->th_valid = false; } } guard{ c, tp && tp->update && p->iterations >= 2u };
 	const DenoiseDev dev{ p->sigma_lum, p->sigma_depth, p->lum_floor, p->normal_squarings };
-	uint32_t cur = 0;
-	for (uint32_t i = 0; i < p->iterations; i++, cur ^= 1u) {
+	for (uint32_t i = 0; i < p->iterations; i++) {
 		const uint32_t step = 1u << i;
 		const bool staged = step <= c->tune_denoise_staged;
 		Bracket t(c, MIRT_K_RESOLVE);
 		hipLaunchKernelGGL(staged ? k_atrous<true> : k_atrous<false>, dim3(c->h_tiles, c->v_tiles), dim3(kAtrousBlock * kAtrousBlock), 0, c->stream,
-		                   c->dn_cv[cur].as<float4>(), c->dn_gd.as<float4>(), c->dn_cv[cur ^ 1u].as<float4>(), c->width, c->h_tiles * kAtrousBlock, c->v_tiles * kAtrousBlock, step, dev);
+		                   src, c->dn_gd.as<float4>(), dst, c->width, c->h_tiles * kAtrousBlock, c->v_tiles * kAtrousBlock, step, dev);
+		float4* const next = i == 0u ? spare : src;
+		src = dst; dst = next;
 	}
 	HIP_TRY(c, hipGetLastError());
 	{ Bracket t(c, MIRT_K_RESOLVE);
-	  hipLaunchKernelGGL(k_denoise_finish, dim3(grid_for(c, n_pix)), dim3(kBlock), 0, c->stream, c->dn_cv[cur].as<float4>(), c->dn_mu.as<float4>(), c->framebuffer.as<float4>(), n_pix, m); }
+	  hipLaunchKernelGGL(k_denoise_finish, dim3(grid_for(c, n_pix)), dim3(kBlock), 0, c->stream, src, c->dn_mu.as<float4>(), c->framebuffer.as<float4>(), n_pix, m); }
 	HIP_TRY(c, hipGetLastError());
 	// the frame leaves as mirt_render's does (the framebuffer is scratch: every resolve writes all of the context's tiles before it is read)
 	const size_t frame_floats = static_cast<size_t>(c->width) * c->height * 4;
 	const bool whole = c->width == c->h_tiles * MIRT_TILE_ROOT && c->height == c->v_tiles * MIRT_TILE_ROOT;
 	HIP_TRY(c, hipMemcpyAsync(c->frame_host, c->framebuffer.ptr, frame_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	std::vector<float> len_host;
+	unsigned long long class_counts[kTemporalClasses] = {};
+	std::vector<unsigned long long> count_slots(tp ? kTemporalStatSlots * kTemporalStatPitch : 0u);
+	if (tp) {
+		if (history_len) { len_host.resize(static_cast<size_t>(c->width) * c->height); HIP_TRY(c, hipMemcpyAsync(len_host.data(), c->th_len.ptr, len_host.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream)); }
+		HIP_TRY(c, hipMemcpyAsync(count_slots.data(), c->th_stats.ptr, count_slots.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+	}
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	if (whole) std::memcpy(rgba_host, c->frame_host, frame_floats * sizeof(float));
 	else copy_owned_tiles(m, c->n_tiles, 4u, c->frame_host, rgba_host);
+	if (tp) {
+		if (history_len) copy_owned_tiles(m, c->n_tiles, 1u, len_host.data(), history_len);
+		for (uint32_t s = 0; s < kTemporalStatSlots; s++) for (uint32_t k = 0; k < kTemporalClasses; k++) class_counts[k] += count_slots[s * kTemporalStatPitch + k];
+		if (stats) *stats = mirt_temporal_stats{ class_counts[kTemporalReprojected], class_counts[kTemporalNoHistory], class_counts[kTemporalOutside], class_counts[kTemporalRejected], class_counts[kTemporalUnusable] };
+		if (tp->update) {                                                             // step 4: the blend, this call's guides and the lengths ARE the history now; the old ones are scratch
+			std::swap(c->th_x, c->dn_cv[1]); std::swap(c->th_g, c->dn_gd); std::swap(c->th_n, c->th_len);
+			c->th_cam = c->camera; c->th_demodulate = p->demodulate; c->th_albedo_floor = p->albedo_floor; c->th_width = c->width; c->th_height = c->height;
+			c->th_valid = true;
+		}
+	}
+	guard.armed = false;
+	return MIRT_OK;
+}
+} // namespace
+extern "C" {
+
+int mirt_render_atrous(mirt_ctx* c, const mirt_denoise_params* p, float* rgba_host) { return filtered_resolve(c, p, nullptr, rgba_host, nullptr, nullptr); }
+
+// ---- temporal history for the denoised resolve (temporal.hpp; the definition is in mirt.h) -----------------------------------------
+int mirt_temporal_defaults(mirt_temporal_params* out) {
+	if (!out) return MIRT_ERR_ARG;
+	*out = mirt_temporal_params{ 7.0f, 0.02f, 0.9f, 1u };
+	return MIRT_OK;
+}
+int mirt_render_temporal(mirt_ctx* c, const mirt_denoise_params* p, const mirt_temporal_params* tp, float* rgba_host, float* history_len, mirt_temporal_stats* stats) {
+	if (c && !tp) return fail(c, MIRT_ERR_ARG, "temporal params is NULL");
+	return filtered_resolve(c, p, tp, rgba_host, history_len, stats);
+}
+int mirt_drop_history(mirt_ctx* c) {
+	if (!c) return MIRT_ERR_ARG;
+	HIP_TRY(c, hipSetDevice(c->device));
+	drop_history(c);
+	return MIRT_OK;
+}
+int mirt_history_info(const mirt_ctx* c, uint32_t* valid, uint64_t* bytes) {
+	if (!c || !valid || !bytes) return MIRT_ERR_ARG;
+	*valid = c->th_valid ? 1u : 0u;
+	*bytes = static_cast<uint64_t>(c->th_x.bytes) + c->th_g.bytes + c->th_n.bytes;
 	return MIRT_OK;
 }
 

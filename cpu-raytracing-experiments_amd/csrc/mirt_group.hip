@@ -567,5 +567,28 @@ int mirt_group_render_atrous(mirt_group* g, const mirt_denoise_params* params, f
 	const int rr = mirt_render_atrous(g->full, params, rgba_host);      // the argument rules are the gather context's
 	return rr < 0 ? gfail(g, rr, "mirt_render_atrous on the gather context: %s", mirt_last_error(g->full)) : rr;
 }
+// Likewise; the history is the gather context's own state (a group of one: its member's).
+int mirt_group_render_temporal(mirt_group* g, const mirt_denoise_params* params, const mirt_temporal_params* temporal, float* rgba_host, float* history_len, mirt_temporal_stats* stats) {
+	if (!g || !params || !temporal || !rgba_host) return MIRT_ERR_ARG;
+	RETURN_IF_SINGLE(g, mirt_render_temporal(ctx, params, temporal, rgba_host, history_len, stats));
+	if (!g->aov) return gfail(g, MIRT_ERR_STATE, "temporal: AOVs are off (mirt_group_set_aov)");
+	if (g->buckets < 2u) return gfail(g, MIRT_ERR_STATE, "temporal: the variance guide needs buckets >= 2, the policy has %u", g->buckets);
+	const uint32_t acc = accumulations_of(g);
+	if (acc == 0 || acc % g->buckets != 0) return MIRT_NOT_READY;       // as mirt_group_render: nothing is gathered for a frame that is not due
+	const int rc = mirt_group_gather(g);
+	if (rc) return rc;
+	const int rr = mirt_render_temporal(g->full, params, temporal, rgba_host, history_len, stats);
+	return rr < 0 ? gfail(g, rr, "mirt_render_temporal on the gather context: %s", mirt_last_error(g->full)) : rr;
+}
+int mirt_group_drop_history(mirt_group* g) {
+	if (!g) return MIRT_ERR_ARG;
+	mirt_ctx* ctx = g->full ? g->full : g->members[0];
+	const int rc = mirt_drop_history(ctx);
+	return rc < 0 ? gfail(g, rc, "mirt_drop_history: %s", mirt_last_error(ctx)) : rc;
+}
+int mirt_group_history_info(const mirt_group* g, uint32_t* valid, uint64_t* bytes) {
+	if (!g) return MIRT_ERR_ARG;
+	return mirt_history_info(g->full ? g->full : g->members[0], valid, bytes);
+}
 
 } // extern "C"

@@ -8,7 +8,7 @@
 //                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm] [--aov PREFIX] [--light-ris M] [--transmission] [--sky-sampling] [--closures 0,1,1,...] [--ggx-pdf]
 //                 [--f-number F] [--focus-distance D] [--unit-mm U] [--focus-pixel X,Y]
 //                 [--until-noise T] [--noise-quantile Q] [--noise-floor F] [--check-every N] [--max-accumulations M] [--noise-out map.pfm]
-//                 [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm] [--denoise [ITERATIONS]] [--denoise-plain-out plain.hdr|plain.pfm]
+//                 [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm] [--denoise [ITERATIONS]] [--denoise-plain-out plain.hdr|plain.pfm] [--temporal [MAX_RATIO]] [--orbit DEG]
 // --denoise writes to --out the variance-guided à-trous denoised resolve of the last frame (mirt_render_atrous with its defaults; ITERATIONS, 0 .. 8,
 // replaces their pass count) instead of the plain one; it implies the first-hit AOVs, which guide it.  --denoise-plain-out writes the plain frame beside it.
 // --adaptive T renders with per-tile adaptive sampling (mirt_accumulate_adaptive): like --until-noise, but every 16 x 16 tile stops taking samples
@@ -205,6 +205,8 @@ int main(int argc, char** argv) {
 	std::string counts_out, plain_out;
 	bool denoise = false;
 	int denoise_iterations = -1;                                               // -1: the default
+	bool temporal = false;
+	float temporal_ratio = -1.0f, orbit_deg = 0.0f;                            // -1: the default max_ratio
 	if (argc == 4 && std::string(argv[1]) == "--convert-hdr") {
 		// file-format check without a GPU: read a picture like stbi_loadf does (top-down) and store it again like Image::Store does (which
 		// flips, so the rows are handed over bottom-up): the output decodes to the same texels
@@ -225,12 +227,15 @@ int main(int argc, char** argv) {
 			          "              [--f-number F] [--focus-distance D] [--unit-mm U] [--focus-pixel X,Y]\n"
 			          "              [--until-noise T] [--noise-quantile Q] [--noise-floor F] [--check-every N] [--max-accumulations M] [--noise-out map.pfm]\n"
 			          "              [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm] [--denoise [ITERATIONS]] [--denoise-plain-out FILE]\n"
+			          "              [--temporal [MAX_RATIO]] [--orbit DEG]\n"
 			          "mirt_headless --convert-hdr in.hdr out.hdr\n"
 			          "  --sky-sampling  the environment map (--hdri, --ambient) is one more light of next event estimation, drawn by importance (mirt_set_sky_sampling)\n"
 			          "  --ggx-pdf  the GGX closure's visible-normal pdf in the MIS weights: emitters and the sampled sky are weighed two ways on GGX surfaces (mirt_set_ggx_pdf)\n"
 			          "  --light-ris M   the NEE light is picked among M candidates by resampled importance sampling (mirt_set_light_ris)\n"
 			          "  --transmission  materials that carry a transmission render as glass (mirt_set_transmission)\n"
 			          "  --denoise [N]   --out receives the variance-guided a-trous denoised resolve (N passes, default 5; implies the first-hit AOVs); --denoise-plain-out FILE: the plain frame\n"
+			          "  --temporal [R]  every frame of --frames is `buckets` accumulations resolved through the temporal history (mirt_render_temporal; R = max_ratio, default 7; implies the AOVs); --out receives the last one\n"
+			          "  --orbit DEG     after every frame the camera yaws DEG degrees about the scene's centre and the accumulator is reset, as the reference does on a camera move (frames of `buckets` accumulations)\n"
 			          "  --closures LIST the closure of material 0, 1, ...: 0 Lambertian, 1 GGX; materials beyond the list take --brdf (mirt_set_material_closures)");
 			return 0;
 		}
@@ -267,6 +272,8 @@ int main(int argc, char** argv) {
 		else if (a == "--counts-out") counts_out = next();
 		else if (a == "--denoise") { denoise = true; if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoise_iterations = std::atoi(argv[++i]); }
 		else if (a == "--denoise-plain-out") { plain_out = next(); denoise = true; }
+		else if (a == "--temporal") { temporal = true; if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) temporal_ratio = static_cast<float>(std::atof(argv[++i])); }
+		else if (a == "--orbit") orbit_deg = static_cast<float>(std::atof(next()));
 		else if (a == "--devices") { devices.clear(); for (const char* p = next(); *p;) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p == ',') p++; } if (devices.empty()) return 2; }
 		else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
 	}
@@ -288,7 +295,7 @@ int main(int argc, char** argv) {
 		Renderer renderer{ scene, policy, devices };
 		renderer.SetGlossDecay(gloss_decay);
 		renderer.SetStreamOrder(exact_stream_order);
-		if (!aov_prefix.empty() || denoise) renderer.SetAOV(true);
+		if (!aov_prefix.empty() || denoise || temporal) renderer.SetAOV(true);
 		renderer.SetLightRis(light_ris);
 		renderer.SetTransmission(transmission);
 		renderer.SetSkySampling(sky_sampling);
@@ -313,6 +320,7 @@ int main(int argc, char** argv) {
 
 		const auto t0 = std::chrono::steady_clock::now();
 		bool have_frame = false;
+		std::vector<float> temporal_frame;                             // --temporal: the last frame resolved through the history
 		std::string frames_due;                                        // 1-based frame numbers on which Render() produced output
 		Renderer::UntilResult until{};
 		Renderer::AdaptiveResult adapt{};
@@ -325,6 +333,39 @@ int main(int argc, char** argv) {
 			const mirt_stop_rule rule{ noise_target, noise_quantile, noise_floor, check_every ? check_every : 4u * policy.buckets, max_accumulations };
 			until = renderer.AccumulateUntil(rule);
 			if (renderer.Render()) { have_frame = true; frames_due = std::to_string(renderer.accumulations()); }
+		}
+		else if (temporal || orbit_deg != 0.0f) {
+			// A moving camera: every frame is `buckets` accumulations (the fewest Render() resolves), then the camera yaws about the scene's centre
+			// and the accumulator is reset, as the reference does on every move (Application.cpp:309-333).  --temporal resolves each frame through
+			// the history, which survives the reset.
+			vec3 centre{};
+			for (const auto& sp : scene.geometry) { centre.x += sp.position[0]; centre.y += sp.position[1]; centre.z += sp.position[2]; }
+			if (!scene.geometry.empty()) { const float inv = 1.0f / static_cast<float>(scene.geometry.size()); centre.x *= inv; centre.y *= inv; centre.z *= inv; }
+			const float half = orbit_deg * 0.5f * 3.14159265358979f / 180.0f, sy = std::sin(half), cy = std::cos(half), s2 = 2.0f * sy * cy, c2 = cy * cy - sy * sy;
+			mirt_denoise_params dp = Renderer::DenoiseDefaults();
+			if (denoise_iterations >= 0) dp.iterations = static_cast<uint32_t>(denoise_iterations);
+			mirt_temporal_params tp = Renderer::TemporalDefaults();
+			if (temporal_ratio >= 0.0f) tp.max_ratio = temporal_ratio;
+			for (uint32_t frame = 0; frame < spp; frame++) {
+				renderer.Accumulate(policy.buckets);
+				if (renderer.Render()) { have_frame = true; frames_due += (frames_due.empty() ? "" : ", ") + std::to_string(frame + 1); }
+				if (temporal) {
+					mirt_temporal_stats st{};
+					temporal_frame = renderer.RenderTemporal(dp, tp, nullptr, &st);
+					std::printf("{\"temporal\": {\"frame\": %u, \"reprojected\": %llu, \"no_history\": %llu, \"outside\": %llu, \"rejected\": %llu, \"unusable\": %llu, \"frame_fnv1a\": \"%016llx\"}}\n", frame + 1,
+					            (unsigned long long)st.reprojected, (unsigned long long)st.no_history, (unsigned long long)st.outside, (unsigned long long)st.rejected, (unsigned long long)st.unusable,
+					            (unsigned long long)fnv1a(temporal_frame));
+				}
+				if (orbit_deg != 0.0f && frame + 1 < spp) {                 // yaw by the quaternion (0, sy, 0, cy): the position about the centre, the orientation with it
+					Camera& cam = scene.camera;
+					const float dx = cam.pos.x - centre.x, dz = cam.pos.z - centre.z;
+					cam.pos.x = centre.x + (c2 * dx + s2 * dz); cam.pos.z = centre.z + (c2 * dz - s2 * dx);
+					const quat o = cam.orient;
+					cam.orient = quat{ cy * o.x + sy * o.z, cy * o.y + sy * o.w, cy * o.z - sy * o.x, cy * o.w - sy * o.y };
+					renderer.CameraChanged();
+					renderer.ResetAccumulator();
+				}
+			}
 		}
 		else for (uint32_t frame = 0; frame < spp; frame++) {          // one UIRender per frame: Accumulate(); Render();  (Application.cpp:379-380)
 			renderer.Accumulate();
@@ -355,7 +396,8 @@ int main(int argc, char** argv) {
 			if (!ok) std::fprintf(stderr, "cannot write %s\n", path.c_str());
 			return ok;
 		};
-		if (denoise && have_frame) {                                   // the denoised resolve of the accumulator the last frame shows
+		if (temporal && !temporal_frame.empty()) { if (!out.empty() && !write_frame(out, temporal_frame)) return 1; }      // --temporal decides what --out receives, --denoise or not
+		else if (denoise && have_frame) {                              // the denoised resolve of the accumulator the last frame shows
 			mirt_denoise_params dp = Renderer::DenoiseDefaults();
 			if (denoise_iterations >= 0) dp.iterations = static_cast<uint32_t>(denoise_iterations);
 			const std::vector<float> filtered = renderer.RenderDenoised(dp);

@@ -252,6 +252,20 @@ public:
 		if (rc != MIRT_OK) img.clear();
 		return img;
 	}
+	// Temporal history for the denoised resolve (mirt.h, mirt_render_temporal): RenderDenoised() through a history that survives ResetAccumulator() and
+	// camera moves — reprojected through the first-hit depth, rejected where depth or normal disagree, blended by sample count, then filtered.
+	// history_len / stats may be NULL.  The shading switches do not drop the history: after changing the estimand call DropHistory().
+	static mirt_temporal_params TemporalDefaults() { mirt_temporal_params p{}; mirt_temporal_defaults(&p); return p; }
+	std::vector<float> RenderTemporal(const mirt_denoise_params& params = DenoiseDefaults(), const mirt_temporal_params& temporal = TemporalDefaults(),
+	                                  std::vector<float>* history_len = nullptr, mirt_temporal_stats* stats = nullptr) {
+		std::vector<float> img(static_cast<size_t>(width) * height * 4, 0.0f);
+		if (history_len) history_len->assign(static_cast<size_t>(width) * height, 0.0f);
+		const int rc = mirt_group_render_temporal(group_, &params, &temporal, img.data(), history_len ? history_len->data() : nullptr, stats);
+		check(rc, "mirt_group_render_temporal");
+		if (rc != MIRT_OK) img.clear();
+		return img;
+	}
+	void DropHistory() { check(mirt_group_drop_history(group_), "mirt_group_drop_history"); }
 	// Per-pixel noise estimate from the buckets (mirt.h, mirt_noise): the relative standard error of the mean of the bucket means, read from the
 	// members' own slabs without a gather.  ready = false (and nothing filled) while accumulations is 0 or not a multiple of `buckets`.
 	struct NoiseResult {

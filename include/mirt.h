@@ -584,6 +584,80 @@ typedef struct mirt_denoise_params {
 int mirt_atrous_defaults(mirt_denoise_params* out);
 int mirt_render_atrous(mirt_ctx* ctx, const mirt_denoise_params* params, float* rgba_host);
 
+/* ---- temporal history for the denoised resolve: reproject the last view's result across a camera move -----------------------------------
+ * A third resolve.  The reference calls Accumulate(); Render(); once per frame and resets the accumulator on every camera move
+ * (Application.cpp:309-333,379-380): after each move the frame holds `buckets` samples again, although most surfaces it shows were seen before.
+ * This resolve keeps the last call's demodulated signal, its variance and its guides as a HISTORY, reprojects it through the first-hit depth
+ * into the new view, rejects what does not match, blends the survivors with the new samples by sample count, and runs the à-trous passes above
+ * on the blend (the temporal half of SVGF, Schied et al. 2017).  The reference has none of this; nothing of it is replayed.
+ * It READS the accumulator slab, the AOV slab and the per-tile counts, as mirt_render_atrous does, and changes no renderer state except its own
+ * history (accumulator, AOVs, counters, frozen tiles and what mirt_render returns afterwards are untouched).
+ * THE DEFINITION.  Every operation binary32, one rounding each, unfused, in the stated order, IEEE division and square root.  dot(a, b) =
+ * (a.x * b.x + a.y * b.y) + a.z * b.z.  w, h, "the image", n (the pixel's tile count), x_c, v, N, z, m_c, usable: as in the à-trous definition.
+ *   1. prepare    steps 1-5 of mirt_render_atrous, unchanged.
+ *   2. reproject  The history holds hx = (x, v), hg = (N, z) and usability, hn = its length in samples, per pixel, the camera `prev` it was taken
+ *                 under, and the demodulate / albedo_floor it was taken with.  THE CALL TAKES THE HISTORY when one exists, max_ratio > 0, the
+ *                 history is of this image size, of these demodulate / albedo_floor words and of this camera's exposure word (x is in exposure-scaled
+ *                 units), and both cameras satisfy | |q|^2 - 1 | < 1e-4
+ *                 (|q|^2 = ((x x + y y) + z z) + w w: the condition of the candidate lists).  Otherwise every usable pixel is `no_history`.
+ *                 For a usable centre p = (px, py) whose N is not all zero (a miss has no surface to follow; it is `no_history`), cam = this call's camera:
+ *        d  = camera_ray_dir(cam, px, py, 0.5f, 0.5f)       (Camera.hpp:80-88 as device_math.hpp spells it)
+ *        P  = cam.pos + d * z          (per component: one product, one sum);      r = P - prev.pos;      z' = sqrt(dot(r, r))
+ *        q  = the rotation of camera_ray_dir, inverted: r + ((uv * w) + uuv) * 2 per component with qv = -prev.orient.xyz, w = prev.orient.w,
+ *             uv = cross(qv, r), uuv = cross(qv, uv)    (device_math.hpp camera_axis with the vector part negated)
+ *        q.z / prev.z <= 0: the point lies behind the history's camera, p is `outside`.  Else t = prev.z / q.z,
+ *        fx = (q.x * t + prev.half_width) - 0.5f,   fy = (q.y * t + prev.half_height) - 0.5f.
+ *        EXCEPTION: when cam equals prev word for word (all eleven words) the map is the identity by definition: fx = (float)px, fy = (float)py, z' = z.
+ *        ix = floorf(fx), wx = fx - ix, ux = 1.0f - wx; likewise iy, wy, uy.  Taps (i, j) = (0,0), (1,0), (0,1), (1,1) at pixel (ix + i, iy + j) with
+ *        b = (i ? wx : ux) * (j ? wy : uy).  (No tap is in the image unless -1 <= ix <= w - 1 and -1 <= iy <= h - 1; a NaN or infinite fx, fy fails that.)
+ *        A tap is TAKEN when it is inside the image, usable in the history with hn > 0, fabsf(z_tap - z') <= depth_tol * z', and
+ *        dot(N_p, N_tap) >= normal_min.  B = ((b_0 + b_1) + ...), X_c = ((b_0 x_0c + b_1 x_1c) + ...), V = ((b_0 v_0 + ...)), L = ((b_0 hn_0 + ...)),
+ *        each sum starting from the first tap taken.  xh_c = X_c / B, vh = V / B, nh = L / B.
+ *        Class: no tap inside the image: `outside`; else no tap taken, or B == 0: `rejected`; else `reprojected`.
+ *   3. blend      for a reprojected pixel: cap = max_ratio * (float)n; nh = cap < nh ? cap : nh; a = (float)n / ((float)n + nh);
+ *                 x_c = xh_c + a * (x_c - xh_c);  v = (a * a) * v + ((1.0f - a) * (1.0f - a)) * vh;  len = (float)n + nh.
+ *                 Every other usable pixel keeps x, v and has len = (float)n.  An unusable pixel passes through as in the à-trous definition; len = 0.
+ *   4. history    with update = 1 the blended (x, v), this call's guides and usability, len, cam and demodulate / albedo_floor become the history
+ *                 — the blend BEFORE any filtering, so that spatial blur never compounds over frames.  A call that returns an error or
+ *                 MIRT_NOT_READY leaves the history as it was — with one exception: MIRT_ERR_HIP from a call with update = 1 and iterations >= 2 may
+ *                 come after the old history's image was used as scratch; that return drops the history (mirt_history_info: valid = 0).
+ *   5. filter     steps 6-7 of the à-trous definition on the blend.
+ * CONSEQUENCES the tests rest on: (a) a call that takes no history writes mirt_render_atrous's frame word for word.  (b) Under the identity map over
+ * the slabs the history was taken from, xh = x (b_0 = 1: x * 1 / 1), so x is unchanged word for word and len = n + min(hn, max_ratio n).  (c) The
+ * result is a function of the two slabs, the counts, the camera and the history alone.
+ * LIFETIME.  The history is allocated by the first call with update = 1 and is kept across mirt_reset, mirt_set_camera and mirt_set_lens — that is
+ * its purpose.  It is dropped by mirt_drop_history, mirt_set_scene, mirt_resize, mirt_set_tile_range, mirt_set_tile_rows, a mirt_set_policy that
+ * changes `buckets`, and mirt_destroy.  THE SHADING SWITCHES DO NOT DROP IT (light RIS, transmission, sky sampling, closures, the GGX pdf, the
+ * gloss decay table, the lens): a caller who changes the estimand calls mirt_drop_history, as it calls mirt_reset.  Under a thin lens the
+ * reprojection still follows the pinhole centre ray of the pixel and the summed first-hit depth: out of focus it reprojects a blur, not a surface.
+ * A change of exposure needs no drop: a history of another exposure word is ignored for the call, as one of another demodulation is.  Memory: two float4 images and
+ * one float image while a history is held (36 B per pixel: 604 MB at 4096 x 4096), one more float image of scratch for a call's lengths (67 MB),
+ * beside the four scratch images of mirt_render_atrous.
+ * Errors and preconditions are exactly mirt_render_atrous's (arguments, then AOVs on, buckets >= 2, the whole image in one context, hence no exact
+ * stream order, then MIRT_NOT_READY under mirt_render's condition, rgba_host untouched); in addition MIRT_ERR_ARG when max_ratio or depth_tol is
+ * negative or not finite, normal_min is outside [-1, 1], update > 1, or temporal is NULL.  Kernel time is booked under MIRT_K_RESOLVE.
+ * history_len (or NULL): width * height floats, row-major, `len` of every pixel of the image (pixels no tile covers are left untouched).
+ * Kernel: csrc/temporal.hpp (k_reproject); binary32 numpy twin: tests/temporal_twin.py; float64 definition: tests/temporal_definitions.py. */
+typedef struct mirt_temporal_params {
+	float    max_ratio;     /* >= 0: history may weigh at most max_ratio x the pixel's own sample count; 0 = take no history */
+	float    depth_tol;     /* >= 0: a tap is taken when |z_tap - z'| <= depth_tol * z' */
+	float    normal_min;    /* in [-1, 1]: ... and dot(N_p, N_tap) >= normal_min */
+	uint32_t update;        /* 0 / 1: write this call's blend as the new history */
+} mirt_temporal_params;
+typedef struct mirt_temporal_stats {   /* pixels of the image; the five sum to w * h */
+	uint64_t reprojected;   /* blended with history */
+	uint64_t no_history;    /* usable, but step 2 does not apply: the call takes no history, or the centre is a miss (N all zero) */
+	uint64_t outside;       /* every tap outside the history's image, or the point behind its camera */
+	uint64_t rejected;      /* some tap inside the image, none taken (depth, normal, unusable or empty history there), or B == 0 */
+	uint64_t unusable;      /* step 5 of the à-trous definition */
+} mirt_temporal_stats;
+int mirt_temporal_defaults(mirt_temporal_params* out);   /* pure host code, no context: max_ratio 7, depth_tol 0.02, normal_min 0.9, update 1 */
+int mirt_render_temporal(mirt_ctx* ctx, const mirt_denoise_params* params, const mirt_temporal_params* temporal,
+                         float* rgba_host, float* history_len, mirt_temporal_stats* stats /* or NULL */);
+int mirt_drop_history(mirt_ctx* ctx);
+/* *valid = 1 while a history is held; *bytes = device bytes of its three images (0 after a drop). */
+int mirt_history_info(const mirt_ctx* ctx, uint32_t* valid, uint64_t* bytes);
+
 int mirt_get_counters(mirt_ctx* ctx, mirt_counters* out);
 int mirt_get_kernel_times(mirt_ctx* ctx, mirt_kernel_times* out, int reset);
 /* HIP stream the context launches on (hipStream_t), for callers that time with their own events. */
@@ -648,6 +722,13 @@ int mirt_group_render_aov(mirt_group* group, int which, float* out);            
  * the AOV slab and the per-tile counts of the whole image — the single context's words.  MIRT_ERR_STATE (AOVs off, buckets < 2) and MIRT_NOT_READY
  * are decided before the gather; the argument rules are then the gather context's. */
 int mirt_group_render_atrous(mirt_group* group, const mirt_denoise_params* params, float* rgba_host);
+/* mirt_render_temporal of the whole frame, likewise: the history lives on the gather context (a group of one: on its member), which follows
+ * mirt_group_set_camera as the members do, so the words are the single context's.  mirt_group_set_scene, mirt_group_resize and a
+ * mirt_group_set_policy that changes `buckets` drop it, as their namesakes do; mirt_group_drop_history and mirt_group_history_info act on it. */
+int mirt_group_render_temporal(mirt_group* group, const mirt_denoise_params* params, const mirt_temporal_params* temporal,
+                               float* rgba_host, float* history_len, mirt_temporal_stats* stats);
+int mirt_group_drop_history(mirt_group* group);
+int mirt_group_history_info(const mirt_group* group, uint32_t* valid, uint64_t* bytes);
 /* mirt_noise / mirt_accumulate_until of the whole image.  NO gather: every member runs mirt_noise on its own slab; histograms and counts add
  * as integers, the maximum is exact, the members' tile records are un-interleaved on the host into LaunchIndex order (tile_out: 4 floats per
  * tile of the image), each member writes its own tiles of map_out, and the mean is the double sum over those records in LaunchIndex order.
