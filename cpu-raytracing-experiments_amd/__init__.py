@@ -99,6 +99,16 @@ class TemporalParams(C.Structure):
         return {n: (int if t is C.c_uint32 else float)(getattr(self, n)) for n, t in self._fields_}
 
 
+class SunSkyParams(C.Structure):
+    """mirt_sun_sky_params"""
+    _fields_ = [("sun_dir", C.c_float * 3), ("turbidity", C.c_float), ("sun_radius", C.c_float), ("sky_scale", C.c_float), ("sun_scale", C.c_float),
+                ("ground", C.c_float * 3), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+    def as_dict(self):
+        return {"sun_dir": tuple(self.sun_dir), "turbidity": self.turbidity, "sun_radius": self.sun_radius, "sky_scale": self.sky_scale,
+                "sun_scale": self.sun_scale, "ground": tuple(self.ground), "width": int(self.width), "height": int(self.height)}
+
+
 class TemporalStats(C.Structure):
     """mirt_temporal_stats"""
     _fields_ = [(n, C.c_uint64) for n in ("reprojected", "no_history", "outside", "rejected", "unusable")]
@@ -175,6 +185,10 @@ def load_library():
         "mirt_tile_above": [P, f, f, vp, C.c_size_t],
         "mirt_adaptive_select": [vp, vp, vp, C.c_size_t, C.c_double, vp],
         "mirt_accumulate_adaptive": [P, C.POINTER(StopRule), u32, C.POINTER(AdaptiveReport)],
+        "mirt_set_environment": [P, vp, vp, u32, u32],
+        "mirt_read_environment": [P, vp, C.c_size_t, vp],
+        "mirt_sun_sky_defaults": [C.POINTER(SunSkyParams)],
+        "mirt_set_sun_sky": [P, C.POINTER(SunSkyParams)],
         "mirt_get_counters": [P, C.POINTER(Counters)],
         "mirt_get_kernel_times": [P, C.POINTER(KernelTimes), i32],
         "mirt_get_stream": [P, C.POINTER(vp)],
@@ -199,6 +213,8 @@ def load_library():
         "mirt_group_set_camera": [G, vp, vp, f, f, f, f],
         "mirt_group_set_lens": [G, f, f],
         "mirt_group_pick_focus": [G, u32, u32, C.POINTER(f), C.POINTER(f)],
+        "mirt_group_set_environment": [G, vp, vp, u32, u32],
+        "mirt_group_set_sun_sky": [G, C.POINTER(SunSkyParams)],
         "mirt_group_set_policy": [G, C.POINTER(Policy)],
         "mirt_group_set_gloss_decay": [G, vp, u32],
         "mirt_group_set_stream_order": [G, u32],
@@ -358,6 +374,27 @@ def _split_temporal_params(params: dict):
     return _denoise_params({k: v for k, v in params.items() if k not in own}), TemporalParams(float(t["max_ratio"]), float(t["depth_tol"]), float(t["normal_min"]), int(t["update"]))
 
 
+def sun_sky_defaults() -> dict:
+    """mirt_sun_sky_defaults (host code, no GPU): the parameters set_sun_sky() starts from, by name — starting values and design choices."""
+    p = SunSkyParams()
+    rc = load_library().mirt_sun_sky_defaults(C.byref(p))
+    if rc != MIRT_OK:
+        raise MirtError(f"mirt_sun_sky_defaults failed ({rc})")
+    return p.as_dict()
+
+
+def _sun_sky_params(params: dict) -> SunSkyParams:
+    """The defaults with the caller's keywords laid over them; an unknown keyword is a TypeError before any call into the library."""
+    d = sun_sky_defaults()
+    unknown = sorted(set(params) - set(d))
+    if unknown:
+        raise TypeError(f"not a sun and sky parameter: {unknown} (known: {sorted(d)})")
+    d.update(params)
+    vec = lambda v: (C.c_float * 3)(*[float(x) for x in v])
+    return SunSkyParams(vec(d["sun_dir"]), float(d["turbidity"]), float(d["sun_radius"]), float(d["sky_scale"]), float(d["sun_scale"]), vec(d["ground"]),
+                        int(d["width"]), int(d["height"]))
+
+
 def adaptive_select(tiles, above, frozen=None, quantile: float = 0.95) -> np.ndarray:
     """mirt_adaptive_select (host code, no GPU): from noise()["tiles"] and noise_above() the mask of tiles to freeze — a tile not yet frozen
     freezes when it has no non-finite pixel and above <= floor((1 - quantile) * usable); tiles already in `frozen` are passed through as 1."""
@@ -508,7 +545,46 @@ class _Binding:
         lights = self.lights if len(self.lights) else np.zeros(1, dtype=np.int32)
         self._call("set_scene", _ptr(self.geometry), _ptr(self.prims), len(self.geometry), _ptr(self.nodes), len(self.nodes),
                    _ptr(self.material), len(self.material), _ptr(lights), len(self.lights), _ptr(amb), _ptr(hdri), hdri.shape[1], hdri.shape[0])
+        self._ambient = amb.reshape(-1).copy()             # what environment() reports: the library keeps it and has no getter for it
         self.UpdateCamera()
+
+    # -- the environment on its own (mirt.h "replacing the environment map on its own", "analytic sun and sky") -------------------
+    sun_sky_defaults = staticmethod(sun_sky_defaults)
+
+    def set_environment(self, ambient=None, hdri=None):
+        """The reference's SceneUpdate::Ambient (mirt_set_environment): replaces the ambient colour (None: the scene's) and the environment map
+        (`hdri` [h, w, 4] float32; None keeps the map in place) and nothing else — no tree rebuild, the camera-ray lists and the temporal history
+        stay.  The environment is part of the estimand and the accumulator is NOT reset: call ResetAccumulator(), and drop_history() where one is
+        kept.  The scene object is not written: UpdateScene() hands its own sky over again.  (A group: on every member.)"""
+        amb = np.ascontiguousarray(self.scene.ambient if ambient is None else ambient, dtype=np.float32).reshape(-1)
+        if amb.size != 3:
+            raise ValueError("ambient must hold three floats")
+        if hdri is None:
+            self._call("set_environment", _ptr(amb), None, 0, 0)
+        else:
+            m = np.ascontiguousarray(hdri, dtype=np.float32)
+            if m.ndim != 3 or m.shape[2] != 4:
+                raise ValueError("hdri must be an array of shape (height, width, 4)")
+            self._call("set_environment", _ptr(amb), _ptr(m), m.shape[1], m.shape[0])
+        self._ambient = amb.copy()
+
+    def set_sun_sky(self, **params):
+        """A Preetham daylight sky and a sun disc, baked on the GPU into the environment map under the ambient colour in place (mirt_set_sun_sky);
+        keywords: the fields of sun_sky_defaults() (sun_dir towards the sun with y up, turbidity 2..10, sun_radius, sky_scale, sun_scale, ground,
+        width, height), each defaulting to that value.  Everything set_environment says holds.  (A group: every member bakes its own map.)"""
+        self._call("set_sun_sky", C.byref(_sun_sky_params(params)))
+
+    def environment(self):
+        """(ambient, map [h, w, 4] float32, baked): the ambient colour last handed over by this object, the environment map the kernels read, copied
+        from the device (a group: member 0's), and whether set_sun_sky baked it (mirt_read_environment)."""
+        info = (C.c_uint32 * 4)()
+        ctx = self._asked()
+        if self._lib.mirt_read_environment(ctx, None, 0, info) < 0:
+            raise MirtError("mirt_read_environment failed: " + self._lib.mirt_last_error(ctx).decode())
+        m = np.zeros((info[1], info[0], 4), dtype=np.float32)
+        if self._lib.mirt_read_environment(ctx, _ptr(m), m.size, info) < 0:
+            raise MirtError("mirt_read_environment failed: " + self._lib.mirt_last_error(ctx).decode())
+        return self._ambient.copy(), m, bool(info[2])
 
     def UpdateCamera(self):
         cam: Camera = self.scene.camera

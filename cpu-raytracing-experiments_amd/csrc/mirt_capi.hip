@@ -11,6 +11,7 @@
 #include "kernels.hpp"
 #include "denoise.hpp"
 #include "temporal.hpp"
+#include "sun_sky.hpp"
 #include "bvh_layout.hpp"
 #include "bvh_build.hpp"
 #include "lbvh_build.hpp"
@@ -104,6 +105,7 @@ struct mirt_ctx {
 	// scene
 	DeviceBuffer recs, recs_wide, spheres, prim_mat, light_sphere, light_emit, mat_albedo, mat_emission, mat_ggx, mat_glass, hdri;
 	SceneDev scene{};
+	bool env_baked = false;          // the environment map in `hdri` was written by k_sun_sky (mirt_set_sun_sky), not handed over by the caller
 	uint32_t transmission = 0;       // mirt_set_transmission: 1 = a transmissive material takes the dielectric interface (the GLASS instantiations of k_shade)
 	std::vector<float4> glass_host;  // the scene's {transmission.rgb, 1 + IOR_minus_one} per material, as uploaded: what the switch validates and looks for glass in
 	bool scene_has_glass = false;    // some material of the scene has max(transmission) > 0: only then does the switch change the kernels launched
@@ -1305,6 +1307,7 @@ int mirt_set_scene(mirt_ctx* c, const mirt_sphere* geometry, const mirt_sphere* 
 	if (c->sky_sampling) { HIP_TRY(c, sync_all(c)); if ((r = build_sky_table(c))) return r; }      // (a batch in flight on another stream may read the old table)
 	if ((r = plan_trace_lds(c))) return r;
 	c->have_scene = true;
+	c->env_baked = false;
 	return MIRT_OK;
 }
 
@@ -2138,6 +2141,81 @@ int mirt_debug_sky_table(mirt_ctx* c, float* dst, size_t capacity, uint32_t info
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	HIP_TRY(c, hipMemcpy(dst, c->sky.t, floats * sizeof(float), hipMemcpyDeviceToHost));
 	return MIRT_OK;
+}
+// ---- the Ambient update: the environment alone (mirt.h "replacing the environment map on its own") ----------------------------
+// What mirt_set_environment and mirt_set_sun_sky share.  `texels` (w x h, validated by the caller's rules below) are uploaded, or, with bake != NULL,
+// written by k_sun_sky on the main stream.  Nothing but the environment changes: the tree, the candidate lists, the LDS plan and the history stay.
+static int replace_environment(mirt_ctx* c, const float amb[3], const float4* texels, uint32_t w, uint32_t h, const mirt_sun_sky::Args* bake) {
+	const size_t n = static_cast<size_t>(w) * h;
+	const bool new_map = texels || bake;
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }                      // batches in flight read the old map and the old table
+	if (c->sky_sampling && !bake) {                                               // before anything is changed (a baked map is finite and non-negative by construction)
+		std::vector<float4> old;
+		if (!texels) {                                                            // the ambient-only form validates the map it keeps
+			w = static_cast<uint32_t>(c->scene.hdri_w); h = static_cast<uint32_t>(c->scene.hdri_h);
+			old.resize(static_cast<size_t>(w) * h);
+			HIP_TRY(c, hipMemcpy(old.data(), c->scene.hdri, old.size() * sizeof(float4), hipMemcpyDeviceToHost));
+		}
+		const int r = check_sky_texels(c, texels ? texels : old.data(), w, h, amb);
+		if (r) return r;
+	}
+	if (new_map) {
+		DeviceBuffer fresh;                                                       // a larger map goes to a new allocation first: a failure leaves the old one in place
+		DeviceBuffer& dst = n * sizeof(float4) > c->hdri.bytes ? fresh : c->hdri;
+		HIP_TRY(c, dst.ensure(n * sizeof(float4)));
+		hipError_t e = hipSuccess;
+		if (bake) {
+			hipLaunchKernelGGL(k_sun_sky, dim3(static_cast<uint32_t>((n + kSunSkyBlock - 1u) / kSunSkyBlock)), dim3(kSunSkyBlock), 0, c->stream, *bake, dst.as<float4>());
+			e = hipGetLastError();
+		} else e = hipMemcpyAsync(dst.ptr, texels, n * sizeof(float4), hipMemcpyHostToDevice, c->stream);
+		if (e == hipSuccess) e = hipStreamSynchronize(c->stream);                 // host buffers are copied, never retained
+		if (e != hipSuccess) { fresh.release(); return fail(c, MIRT_ERR_HIP, "environment map: %s", hipGetErrorString(e)); }
+		if (&dst == &fresh) { c->hdri.release(); c->hdri = fresh; }
+		SceneDev& s = c->scene;
+		s.hdri = c->hdri.as<float4>();
+		s.hdri_w = static_cast<int32_t>(w); s.hdri_h = static_cast<int32_t>(h);
+		s.hdri_fw = static_cast<float>(static_cast<int32_t>(w) - 1);              // as commit_scene
+		s.hdri_fh = static_cast<float>(static_cast<int32_t>(h) - 1);
+		c->env_baked = bake != nullptr;
+	}
+	{ SceneDev& s = c->scene;
+	  for (int k = 0; k < 3; k++) s.ambient[k] = amb[k];
+	  const float x = amb[0], y = amb[1], z = amb[2];
+	  const float m1 = (y < z) ? z : y; const float m0 = (x < m1) ? m1 : x; s.has_ambient = (m0 > 0.0f) ? 1u : 0u; }   // Renderer.hpp:79, as commit_scene
+	if (c->sky_sampling) { const int r = build_sky_table(c); if (r) return r; }
+	return MIRT_OK;
+}
+int mirt_set_environment(mirt_ctx* c, const float ambient_color[3], const float* hdri_rgba, uint32_t w, uint32_t h) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!ambient_color) return fail(c, MIRT_ERR_ARG, "ambient_color is NULL");
+	const bool keep = !hdri_rgba && w == 0 && h == 0;
+	if (!keep && (!hdri_rgba || w == 0 || h == 0)) return fail(c, MIRT_ERR_ARG, "the environment needs an hdri of at least 1x1, or NULL with 0 x 0 to keep the current one");
+	if (!c->have_scene) return fail(c, MIRT_ERR_STATE, "mirt_set_environment replaces the environment of a scene: mirt_set_scene first");
+	return replace_environment(c, ambient_color, reinterpret_cast<const float4*>(hdri_rgba), w, h, nullptr);
+}
+int mirt_read_environment(mirt_ctx* c, float* rgba_out, size_t capacity_floats, uint32_t info[4]) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!info) return fail(c, MIRT_ERR_ARG, "read_environment: info is NULL");
+	if (!c->have_scene) return fail(c, MIRT_ERR_STATE, "there is no environment: mirt_set_scene first");
+	const SceneDev& s = c->scene;
+	const size_t floats = static_cast<size_t>(s.hdri_w) * static_cast<size_t>(s.hdri_h) * 4u;
+	info[0] = static_cast<uint32_t>(s.hdri_w); info[1] = static_cast<uint32_t>(s.hdri_h); info[2] = c->env_baked ? 1u : 0u; info[3] = 0u;
+	if (!rgba_out) return MIRT_OK;
+	if (capacity_floats < floats) return fail(c, MIRT_ERR_ARG, "read_environment: room for %zu floats, the map takes %zu", capacity_floats, floats);
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	HIP_TRY(c, hipMemcpy(rgba_out, s.hdri, floats * sizeof(float), hipMemcpyDeviceToHost));
+	return MIRT_OK;
+}
+int mirt_sun_sky_defaults(mirt_sun_sky_params* out) { return mirt_sun_sky::defaults(out); }
+int mirt_set_sun_sky(mirt_ctx* c, const mirt_sun_sky_params* p) {
+	if (!c) return MIRT_ERR_ARG;
+	char msg[160];
+	if (const int r = mirt_sun_sky::check(p, msg, sizeof msg)) return fail(c, r, "%s", msg);
+	if (!c->have_scene) return fail(c, MIRT_ERR_STATE, "mirt_set_sun_sky replaces the environment of a scene: mirt_set_scene first");
+	const mirt_sun_sky::Args a = mirt_sun_sky::args(*p);
+	const float amb[3] = { c->scene.ambient[0], c->scene.ambient[1], c->scene.ambient[2] };
+	return replace_environment(c, amb, nullptr, p->width, p->height, &a);
 }
 int mirt_debug_allow_half_boxes(mirt_ctx* c, int allow) { if (!c) return MIRT_ERR_ARG; c->allow_half = allow != 0; return MIRT_OK; }
 

@@ -201,6 +201,8 @@ GROUP_FORWARD(set_light_ris, (mirt_group* g, uint32_t candidates), (ctx, candida
 GROUP_FORWARD(set_transmission, (mirt_group* g, uint32_t on), (ctx, on))
 GROUP_FORWARD(set_sky_sampling, (mirt_group* g, uint32_t on), (ctx, on))                         // every member builds its own table, word for word the same (a fixed summation order)
 GROUP_FORWARD(set_ggx_pdf, (mirt_group* g, uint32_t on), (ctx, on))
+GROUP_FORWARD(set_environment, (mirt_group* g, const float ambient_color[3], const float* hdri_rgba, uint32_t w, uint32_t h), (ctx, ambient_color, hdri_rgba, w, h))
+GROUP_FORWARD(set_sun_sky, (mirt_group* g, const mirt_sun_sky_params* params), (ctx, params))     // every member bakes its own map, word for word the same (a fixed order, no atomics)
 GROUP_FORWARD(set_material_closures, (mirt_group* g, const uint8_t* closure, uint32_t n), (ctx, closure, n))   // the gather context too: its first-hit AOV colour follows the table
 int mirt_group_pick_focus(mirt_group* g, uint32_t x, uint32_t y, float* distance, float* depth) {
 	if (!g) return MIRT_ERR_ARG;

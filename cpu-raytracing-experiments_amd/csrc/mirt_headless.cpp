@@ -207,6 +207,10 @@ int main(int argc, char** argv) {
 	int denoise_iterations = -1;                                               // -1: the default
 	bool temporal = false;
 	float temporal_ratio = -1.0f, orbit_deg = 0.0f;                            // -1: the default max_ratio
+	bool sun_sky = false;
+	float sun_elevation = 0.0f, sun_azimuth = 0.0f, sun_turbidity = -1.0f, sun_orbit_deg = 0.0f;   // turbidity -1: the default
+	uint32_t env_w = 0, env_h = 0;                                             // 0: the default map size
+	std::string env_out;
 	if (argc == 4 && std::string(argv[1]) == "--convert-hdr") {
 		// file-format check without a GPU: read a picture like stbi_loadf does (top-down) and store it again like Image::Store does (which
 		// flips, so the rows are handed over bottom-up): the output decodes to the same texels
@@ -228,6 +232,7 @@ int main(int argc, char** argv) {
 			          "              [--until-noise T] [--noise-quantile Q] [--noise-floor F] [--check-every N] [--max-accumulations M] [--noise-out map.pfm]\n"
 			          "              [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm] [--denoise [ITERATIONS]] [--denoise-plain-out FILE]\n"
 			          "              [--temporal [MAX_RATIO]] [--orbit DEG]\n"
+		          "              [--sun-sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY]] [--env-size WxH] [--env-out env.hdr] [--sun-orbit DEG]\n"
 			          "mirt_headless --convert-hdr in.hdr out.hdr\n"
 			          "  --sky-sampling  the environment map (--hdri, --ambient) is one more light of next event estimation, drawn by importance (mirt_set_sky_sampling)\n"
 			          "  --ggx-pdf  the GGX closure's visible-normal pdf in the MIS weights: emitters and the sampled sky are weighed two ways on GGX surfaces (mirt_set_ggx_pdf)\n"
@@ -236,7 +241,11 @@ int main(int argc, char** argv) {
 			          "  --denoise [N]   --out receives the variance-guided a-trous denoised resolve (N passes, default 5; implies the first-hit AOVs); --denoise-plain-out FILE: the plain frame\n"
 			          "  --temporal [R]  every frame of --frames is `buckets` accumulations resolved through the temporal history (mirt_render_temporal; R = max_ratio, default 7; implies the AOVs); --out receives the last one\n"
 			          "  --orbit DEG     after every frame the camera yaws DEG degrees about the scene's centre and the accumulator is reset, as the reference does on a camera move (frames of `buckets` accumulations)\n"
-			          "  --closures LIST the closure of material 0, 1, ...: 0 Lambertian, 1 GGX; materials beyond the list take --brdf (mirt_set_material_closures)");
+			          "  --sun-sky E,A[,T]  the environment map is a Preetham sky of turbidity T with a sun disc at elevation E and azimuth A degrees, baked on the GPU under --ambient (mirt_set_sun_sky)\n"
+		          "  --env-size WxH  texels of the map --sun-sky bakes (mirt_sun_sky_defaults: 1025x513)\n"
+		          "  --env-out FILE  the environment map the kernels read, written as Radiance .hdr (mirt_read_environment)\n"
+		          "  --sun-orbit DEG with --sun-sky and --frames: after every frame of `buckets` accumulations the sun turns DEG degrees about the vertical and the accumulator is reset (mirt_set_sun_sky alone: no mirt_set_scene)\n"
+		          "  --closures LIST the closure of material 0, 1, ...: 0 Lambertian, 1 GGX; materials beyond the list take --brdf (mirt_set_material_closures)");
 			return 0;
 		}
 		else if (a == "--scene") scene_name = next();
@@ -274,6 +283,10 @@ int main(int argc, char** argv) {
 		else if (a == "--denoise-plain-out") { plain_out = next(); denoise = true; }
 		else if (a == "--temporal") { temporal = true; if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) temporal_ratio = static_cast<float>(std::atof(argv[++i])); }
 		else if (a == "--orbit") orbit_deg = static_cast<float>(std::atof(next()));
+		else if (a == "--sun-sky") { const int got = std::sscanf(next(), "%f,%f,%f", &sun_elevation, &sun_azimuth, &sun_turbidity); if (got < 2) return 2; sun_sky = true; }
+		else if (a == "--env-size") { if (std::sscanf(next(), "%ux%u", &env_w, &env_h) != 2) return 2; }
+		else if (a == "--env-out") env_out = next();
+		else if (a == "--sun-orbit") sun_orbit_deg = static_cast<float>(std::atof(next()));
 		else if (a == "--devices") { devices.clear(); for (const char* p = next(); *p;) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p == ',') p++; } if (devices.empty()) return 2; }
 		else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
 	}
@@ -307,6 +320,19 @@ int main(int argc, char** argv) {
 		scene.camera.Resize(w, h);                                     // Application.cpp:375-376
 		renderer.SceneChanged();
 		renderer.Resize(w, h);
+		mirt_sun_sky_params sun = Renderer::SunSkyDefaults();
+		auto aim_sun = [&]() {                                          // elevation and azimuth in degrees -> the direction towards the sun, y up
+			const double el = sun_elevation * 3.14159265358979323846 / 180.0, az = sun_azimuth * 3.14159265358979323846 / 180.0;
+			sun.sun_dir[0] = static_cast<float>(std::cos(el) * std::cos(az)); sun.sun_dir[1] = static_cast<float>(std::sin(el)); sun.sun_dir[2] = static_cast<float>(std::cos(el) * std::sin(az));
+			if (sun_elevation == 90.0f) { sun.sun_dir[0] = sun.sun_dir[2] = 0.0f; }
+			if (sun_elevation == 0.0f) sun.sun_dir[1] = 0.0f;
+			renderer.SetSunSky(sun);
+		};
+		if (sun_sky) {                                                  // the Ambient update: after SceneChanged(), which handed over scene.sky
+			if (sun_turbidity >= 0.0f) sun.turbidity = sun_turbidity;
+			if (env_w) { sun.width = env_w; sun.height = env_h; }
+			aim_sun();
+		}
 		if (lens) {
 			scene.camera.f_number = f_number; scene.camera.focus_distance = focus_distance; scene.camera.unit_mm = unit_mm;
 			if (pick) {                                                     // pick, then set (Application.cpp:298-299)
@@ -333,6 +359,15 @@ int main(int argc, char** argv) {
 			const mirt_stop_rule rule{ noise_target, noise_quantile, noise_floor, check_every ? check_every : 4u * policy.buckets, max_accumulations };
 			until = renderer.AccumulateUntil(rule);
 			if (renderer.Render()) { have_frame = true; frames_due = std::to_string(renderer.accumulations()); }
+		}
+		else if (sun_sky && sun_orbit_deg != 0.0f) {
+			// A moving sun: every frame is `buckets` accumulations; then the sun turns about the vertical through SetSunSky alone — no SceneChanged(),
+			// no tree rebuild — and the accumulator is reset, as on any edit (Application.cpp:503-510).
+			for (uint32_t frame = 0; frame < spp; frame++) {
+				renderer.Accumulate(policy.buckets);
+				if (renderer.Render()) { have_frame = true; frames_due += (frames_due.empty() ? "" : ", ") + std::to_string(frame + 1); }
+				if (frame + 1 < spp) { sun_azimuth += sun_orbit_deg; aim_sun(); renderer.ResetAccumulator(); }
+			}
 		}
 		else if (temporal || orbit_deg != 0.0f) {
 			// A moving camera: every frame is `buckets` accumulations (the fewest Render() resolves), then the camera yaws about the scene's centre
@@ -407,6 +442,11 @@ int main(int argc, char** argv) {
 			if (!plain_out.empty() && !write_frame(plain_out, renderer.GetFrame())) return 1;
 		}
 		else if (!out.empty() && have_frame && !write_frame(out, renderer.GetFrame())) return 1;
+		if (!env_out.empty()) {
+			const Renderer::Environment env = renderer.ReadEnvironment();
+			std::printf("{\"environment\": {\"width\": %u, \"height\": %u, \"baked\": %s, \"fnv1a\": \"%016llx\"}}\n", env.width, env.height, env.baked ? "true" : "false", (unsigned long long)fnv1a(env.rgba));
+			if (!mirt_hdr::write_flipped(env_out, env.rgba.data(), env.width, env.height)) { std::fprintf(stderr, "cannot write %s\n", env_out.c_str()); return 1; }
+		}
 		if (!aov_prefix.empty()) {
 			const struct { int which; const char* name; uint32_t channels; } outputs[3] = { { MIRT_AOV_DEPTH, "depth", 1 }, { MIRT_AOV_NORMAL, "normal", 3 }, { MIRT_AOV_ALBEDO, "albedo", 3 } };
 			for (const auto& o : outputs) {

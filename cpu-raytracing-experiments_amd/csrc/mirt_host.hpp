@@ -197,6 +197,29 @@ public:
 	// The environment map as one more light of next event estimation (mirt.h, mirt_set_sky_sampling): off by default, as in the reference, where the
 	// sky is met by extension rays only.  Same expectation, so the accumulator is not reset.  Not in exact stream order.
 	void SetSkySampling(bool on) { check(mirt_group_set_sky_sampling(group_, on ? 1u : 0u), "mirt_group_set_sky_sampling"); }
+	// SceneUpdate::Ambient (Application.cpp:335-347,503; mirt.h, mirt_set_environment): scene.sky alone is handed over again — no tree rebuild, the
+	// camera-ray lists and the temporal history stay.  The environment is part of the estimand: ResetAccumulator() is the caller's to call.
+	void SetEnvironment() {
+		const Sky& k = scene.sky;
+		check(mirt_group_set_environment(group_, k.ambient_color, k.hdri_data.data(), static_cast<uint32_t>(k.hdri_width), static_cast<uint32_t>(k.hdri_height)), "mirt_group_set_environment");
+	}
+	// A Preetham sky and a sun disc baked on the device into the environment map, under scene.sky.ambient_color as last handed over (mirt.h,
+	// mirt_set_sun_sky).  scene.sky's own texels are not touched: SceneChanged() hands them over again.
+	static mirt_sun_sky_params SunSkyDefaults() { mirt_sun_sky_params p{}; mirt_sun_sky_defaults(&p); return p; }
+	void SetSunSky(const mirt_sun_sky_params& params) { check(mirt_group_set_sun_sky(group_, &params), "mirt_group_set_sun_sky"); }
+	// The map the kernels read (the first member's; every member holds the same words), RGBA f32 rows (mirt.h, mirt_read_environment).
+	struct Environment { uint32_t width = 0, height = 0; bool baked = false; std::vector<float> rgba; };
+	Environment ReadEnvironment() {
+		mirt_ctx* ctx = nullptr;
+		check(mirt_group_member(group_, 0, &ctx), "mirt_group_member");
+		uint32_t info[4] = {};
+		Environment e;
+		if (mirt_read_environment(ctx, nullptr, 0, info) < 0) throw std::runtime_error(std::string("mirt_read_environment: ") + mirt_last_error(ctx));
+		e.width = info[0]; e.height = info[1]; e.baked = info[2] != 0;
+		e.rgba.resize(static_cast<size_t>(e.width) * e.height * 4);
+		if (mirt_read_environment(ctx, e.rgba.data(), e.rgba.size(), info) < 0) throw std::runtime_error(std::string("mirt_read_environment: ") + mirt_last_error(ctx));
+		return e;
+	}
 	// The GGX closure's pdf in the MIS weights (mirt.h, mirt_set_ggx_pdf): off by default, as in the reference, whose Closure<GGX>::pdf returns 0.
 	// On: emitters and (under sky sampling) the sky are weighed two ways on GGX surfaces.  Formally another estimator: Reset() is the caller's to call.
 	// Not in exact stream order.

@@ -341,6 +341,84 @@ int mirt_get_sky_sampling(const mirt_ctx* ctx, uint32_t* on);
 int mirt_set_ggx_pdf(mirt_ctx* ctx, uint32_t on);
 int mirt_get_ggx_pdf(const mirt_ctx* ctx, uint32_t* on);
 
+/* ---- replacing the environment map on its own: the reference's SceneUpdate::Ambient ---------------------------------------------------
+ * The reference tracks an edit of the sky apart from Geometry and Material (Application.cpp:335-347,503).  mirt_set_environment replaces the
+ * environment map, its size and ambient_color exactly as mirt_set_scene would set them, and touches NOTHING else: the tree is not rebuilt, the
+ * camera-ray candidate lists stay valid, the LDS plan stays, the temporal history is NOT dropped.  After it, accumulator, frame, AOVs and counters
+ * equal, word for word, those of a fresh mirt_set_scene with the same scene and this environment — with sky sampling off and on (the table is
+ * rebuilt: the same words).  The environment is part of the estimand and the accumulator is NOT reset: as with the shading switches, the caller
+ * calls mirt_reset, and mirt_drop_history where it keeps a history.
+ * hdri_rgba = NULL with w = h = 0 keeps the map and changes only ambient_color; otherwise hdri_rgba is w x h RGBA f32 texels, >= 1 x 1, copied.
+ * Needs an earlier mirt_set_scene: else MIRT_ERR_STATE.  Deferred mirt_accumulate_async calls are launched first, under the old environment, and
+ * every stream is waited for before the map is overwritten.  With sky sampling on the new texels (the kept ones under the new ambient_color) pass
+ * mirt_set_sky_sampling's validation BEFORE anything is changed: on MIRT_ERR_ARG the old environment is in place, bit for bit.  Allowed in exact
+ * stream order: the map is data. */
+int mirt_set_environment(mirt_ctx* ctx, const float ambient_color[3], const float* hdri_rgba, uint32_t w, uint32_t h);
+/* The map the kernels read, copied from the device after the context's stream has been synchronised.  info[0] width, info[1] height, info[2] 1 if
+ * the map was baked by mirt_set_sun_sky and 0 if a caller handed it over, info[3] 0.  rgba_out == NULL: only `info` is filled.  MIRT_ERR_ARG when
+ * capacity_floats < 4 * width * height; MIRT_ERR_STATE before mirt_set_scene. */
+int mirt_read_environment(mirt_ctx* ctx, float* rgba_out, size_t capacity_floats, uint32_t info[4]);
+
+/* ---- analytic sun and sky: a Preetham daylight sky and a sun disc, baked on the device into the environment map -------------------------
+ * mirt_set_sun_sky is mirt_set_environment with the context's current ambient_color and a map of width x height texels that kernel k_sun_sky
+ * (csrc/sun_sky.hpp) writes straight into the context's buffer: no host image, no upload.  Everything above holds (nothing else is touched; the
+ * caller resets).  The reference has no procedural sky; nothing of it is replayed.  Model: Preetham, Shirley, Smits 1999 for the sky; for the disc
+ * an extraterrestrial radiance of 1.9e6 kcd/m^2 behind Rayleigh and aerosol optical depths at the Kasten-Young air mass.
+ * THE DEFINITION — this text is the authority; float64 statement and binary32 numpy twin: tests/sun_sky_definitions.py.
+ *   Cells.  They are sky_eval's own (see "sampling the environment map"): cols = w - 1, rows = h - 1.  Texel (r, c), r < rows, c < cols, is seen
+ *     through azimuth phi in 2 pi (c / cols - 1/2) + [0, 2 pi / cols) and elevation between el(r) and el(r + 1), el(k) = pi (1/2 - k / rows).  Texel
+ *     column w - 1 is computed as column 0 and texel row h - 1 as row rows - 1 (what sky_eval reads when ex == fw or ey == fh): the same words.
+ *   Sub-samples.  A texel is the mean of a fixed 4 x 4 grid, midpoints in sin(el) and in phi, so each carries the same solid angle: i = 0..3 from
+ *     the upper edge down (outer), j = 0..3 in rising phi (inner); sum = (((v_00 + v_01) + v_02) + ...), texel = sum * 0.0625f, alpha = 1.
+ *     phi_j = PI_F * ((float)(8 c + 2 j + 1 - 4 cols) / (float)(4 cols))            (the integer is exact; PI_F = 3.14159274f)
+ *     edge(k) = 2.0f * (h * h), h = sinf(1.57079637f * ((float)k / (float)rows))     (= 1 - sin el(k), the distance from the pole)
+ *     a cell with 2 r + 1 <= rows is measured from y = +1: ta = edge(r), tb = edge(r + 1), t_i = ta + ((2 i + 1) / 8) * (tb - ta), y = 1.0f - t_i;
+ *     any other from y = -1: ta = edge(rows - r), tb = edge(rows - r - 1), the same t_i, y = t_i - 1.0f.   ce = sqrtf(t_i * (2.0f - t_i)).
+ *     d = (ce * cosf(phi_j), y, ce * sinf(phi_j)): the inverse of sky_eval's map u = 1/2 + fast_atan2(d.z, d.x) / 2 pi, v = 1/2 - fast_asin(d.y) / pi;
+ *     fast_atan2(z, x) is the angle of (x, z) from +x towards +z, in (-pi, pi].
+ *   Sky.  e = d above the horizon; where y < 0, e = (cosf(phi_j), 0, sinf(phi_j)), the foot of d on the horizon, and the result is multiplied by
+ *     `ground`: the lower hemisphere is the horizon ring, tinted.  ct = max(e.y, 1/64).  gamma = 2.0f * atan2f(|e - sun|, |e + sun|) (lengths by
+ *     dot3 and sqrtf: the angle between e and the sun without the cancellation of acos near 0 and pi); cg = dot3(e, sun).  For each of Y, x, y,
+ *     with A..E the Perez coefficients:  F = (1.0f + A * expf(B / ct)) * ((1.0f + C * expf(D * gamma)) + E * (cg * cg));  value = (zenith * F) * inv_F0,
+ *     inv_F0 = 1 / F(0, theta_s).  X = (x / y) * Y;  Z = (((1.0f - x) - y) / y) * Y;  linear Rec.709:
+ *       R = (3.2404542f X + -1.5371385f Y) + -0.4985314f Z;  G = (-0.9692660f X + 1.8760108f Y) + 0.0415560f Z;  B = (0.0556434f X + -0.2040259f Y) + 1.0572252f Z
+ *     each clamped below at 0, times sky_scale, times ground where y < 0.
+ *     Coefficients, linear in the turbidity T:
+ *       Y: A = 0.1787 T - 1.4630, B = -0.3554 T + 0.4275, C = -0.0227 T + 5.3251, D = 0.1206 T - 2.5771, E = -0.0670 T + 0.3703
+ *       x: A = -0.0193 T - 0.2592, B = -0.0665 T + 0.0008, C = -0.0004 T + 0.2125, D = -0.0641 T - 0.8989, E = -0.0033 T + 0.0452
+ *       y: A = -0.0167 T - 0.2608, B = -0.0950 T + 0.0092, C = -0.0079 T + 0.2102, D = -0.0441 T - 1.6537, E = -0.0109 T + 0.0529
+ *     Zenith: Y_z = (4.0453 T - 4.9710) tan(chi) - 0.2155 T + 2.4192 kcd/m^2, chi = (4/9 - T/120)(pi - 2 theta_s);  x_z = [T^2 T 1] M_x [theta_s^3
+ *       theta_s^2 theta_s 1]^T, y_z likewise, with rows
+ *       M_x: (0.00166, -0.00375, 0.00209, 0), (-0.02903, 0.06377, -0.03202, 0.00394), (0.11693, -0.21196, 0.06052, 0.25886)
+ *       M_y: (0.00275, -0.00610, 0.00317, 0), (-0.04214, 0.08970, -0.04153, 0.00516), (0.15346, -0.26756, 0.06670, 0.26688)
+ *   Sun.  L_rgb = sun_scale * 1.9e6 * exp(-tau m) at 0.68, 0.55, 0.44 um, tau = 0.008735 lambda^-4.08 + (0.04608 T - 0.04586) lambda^-1.3,
+ *     m = 1 / (cos theta_s + 0.50572 (96.07995 - theta_s in degrees)^-1.6364).  Added to EVERY sub-sample, below the horizon too and untinted, with weight
+ *     clamp((cos g - cos a) / (cos 0.9 a - cos a), 0, 1), a = sun_radius, g the angle between d and the sun, evaluated as
+ *       wgt = min(max(0, (edge_a - 0.5f * dot3(d - sun, d - sun)) * ramp_inv), 1),   edge_a = 1 - cos a,  ramp_inv = 1 / (cos 0.9 a - cos a)
+ *     (1 - cos g = |d - sun|^2 / 2 for unit vectors: the ramp is 34 binary32 steps of cos g wide at the default radius, and this form does not
+ *     lose them).  The linear limb is deliberate: a hard edge would let one rounding flip a sub-sample between the kernel and its float64
+ *     statement; with the ramp every texel is a continuous function of its inputs and one bound holds for all of them.
+ *   Host.  Everything that depends on the sun alone is computed once on the host in float64, rounded to binary32 once and passed to the kernel: the
+ *     unit sun_dir, the fifteen coefficients, the three inv_F0, Y_z, x_z, y_z, L_rgb, edge_a and ramp_inv (csrc/sun_sky_host.hpp).  The device needs
+ *     no pow and no tan: per texel eight sinf / cosf for phi and two sinf for the edges, per sub-sample one atan2f, six expf, three sqrtf and the
+ *     divisions — the device library's full-precision functions, IEEE division and square root, nothing fused.
+ * One thread per texel, a fixed order, no atomics: two bakes of the same parameters give the same words, on every device of a group.
+ * MIRT_ERR_ARG, nothing changed: params NULL, a field not finite, sun_dir of zero length or with y < 0 (twilight is not modelled), turbidity outside
+ * [2, 10], sun_radius outside (0, 0.1], a negative scale, width or height below 2 or above 32768.  MIRT_ERR_STATE before mirt_set_scene.
+ * mirt_sun_sky_defaults (pure host code, no context): sun_dir (0.3, 0.9, 0.3), turbidity 3, sun_radius 0.00465, sky_scale = sun_scale = 0.1 (one
+ * render unit per 10 kcd/m^2), ground 0.1, 1025 x 513 texels.  Starting values and design choices, not measurements. */
+typedef struct mirt_sun_sky_params {
+	float    sun_dir[3];     /* towards the sun, world space, y up as sky_eval has it; normalised by the library; y >= 0 */
+	float    turbidity;      /* 2 .. 10 */
+	float    sun_radius;     /* angular radius in rad, in (0, 0.1]; default 0.00465 */
+	float    sky_scale;      /* render units per kcd/m^2 of sky luminance, >= 0 */
+	float    sun_scale;      /* the same for the disc; 0 = no disc */
+	float    ground[3];      /* tint of the lower hemisphere */
+	uint32_t width, height;  /* texels of the baked map, each in [2, 32768] */
+} mirt_sun_sky_params;
+int mirt_sun_sky_defaults(mirt_sun_sky_params* out);
+int mirt_set_sun_sky(mirt_ctx* ctx, const mirt_sun_sky_params* params);
+
 /* Renderer::Resize, Renderer.hpp:53-63: h_tiles = w/16, v_tiles = h/16 (truncating), allocates and zeroes
  * the accumulator, accumulations = 0.  Owns all tiles until mirt_set_tile_range says otherwise. */
 int mirt_resize(mirt_ctx* ctx, uint32_t width, uint32_t height);
@@ -692,6 +770,8 @@ int mirt_group_set_transmission(mirt_group* group, uint32_t on);                
 int mirt_group_set_sky_sampling(mirt_group* group, uint32_t on);                   /* mirt_set_sky_sampling on every member (and the gather context) */
 int mirt_group_set_ggx_pdf(mirt_group* group, uint32_t on);                        /* mirt_set_ggx_pdf on every member (and the gather context) */
 int mirt_group_set_material_closures(mirt_group* group, const uint8_t* closure, uint32_t n);   /* mirt_set_material_closures on every member (and the gather context) */
+int mirt_group_set_environment(mirt_group* group, const float ambient_color[3], const float* hdri_rgba, uint32_t w, uint32_t h);   /* mirt_set_environment on every member (and the gather context) */
+int mirt_group_set_sun_sky(mirt_group* group, const mirt_sun_sky_params* params);   /* mirt_set_sun_sky on every member (and the gather context): each bakes its own map, the same words */
 int mirt_group_pick_focus(mirt_group* group, uint32_t x, uint32_t y, float* distance, float* depth);   /* mirt_pick_focus on the first member */
 int mirt_group_set_policy(mirt_group* group, const mirt_policy* policy);
 int mirt_group_set_gloss_decay(mirt_group* group, const float* decay, uint32_t n);
