@@ -189,6 +189,7 @@ def load_library():
         "mirt_read_environment": [P, vp, C.c_size_t, vp],
         "mirt_sun_sky_defaults": [C.POINTER(SunSkyParams)],
         "mirt_set_sun_sky": [P, C.POINTER(SunSkyParams)],
+        "mirt_update_spheres": [P, u32, vp, vp, vp],
         "mirt_get_counters": [P, C.POINTER(Counters)],
         "mirt_get_kernel_times": [P, C.POINTER(KernelTimes), i32],
         "mirt_get_stream": [P, C.POINTER(vp)],
@@ -215,6 +216,7 @@ def load_library():
         "mirt_group_pick_focus": [G, u32, u32, C.POINTER(f), C.POINTER(f)],
         "mirt_group_set_environment": [G, vp, vp, u32, u32],
         "mirt_group_set_sun_sky": [G, C.POINTER(SunSkyParams)],
+        "mirt_group_update_spheres": [G, u32, vp, vp, vp],
         "mirt_group_set_policy": [G, C.POINTER(Policy)],
         "mirt_group_set_gloss_decay": [G, vp, u32],
         "mirt_group_set_stream_order": [G, u32],
@@ -293,6 +295,23 @@ def light_list(geometry: np.ndarray, material: np.ndarray) -> np.ndarray:
     if rc != MIRT_OK:
         raise MirtError(f"mirt_light_list failed ({rc})")
     return out[: n.value].copy()
+
+
+def geometry_to_bvh_order(geometry: np.ndarray, prims: np.ndarray) -> np.ndarray:
+    """perm with prims[perm[g]] == geometry[g], row for row (32-byte SPHERE rows compared as bytes): where authoring-order sphere g sits in the
+    BVH-order array hit.primID refers to.  Identical rows are interchangeable, so any bijection among them is right; here the k-th of a run of
+    equal rows in `geometry` goes to the k-th of that run in `prims`.  Pure numpy, no GPU.  ValueError unless one is a permutation of the other."""
+    g = np.ascontiguousarray(geometry, dtype=SPHERE)
+    p = np.ascontiguousarray(prims, dtype=SPHERE)
+    if g.shape != p.shape or g.ndim != 1:
+        raise ValueError(f"geometry {g.shape} and prims {p.shape} must be two 1-D arrays of one length")
+    gw, pw = g.view(np.uint64).reshape(len(g), 4), p.view(np.uint64).reshape(len(p), 4)
+    og, op = np.lexsort(gw.T[::-1]), np.lexsort(pw.T[::-1])             # stable: equal rows keep their order
+    if not np.array_equal(gw[og], pw[op]):
+        raise ValueError("prims is not a permutation of geometry's rows")
+    perm = np.empty(len(g), dtype=np.uint32)
+    perm[og] = op
+    return perm
 
 
 def _aov_image(height: int, width: int, which: int, out):
@@ -532,13 +551,16 @@ class _Binding:
         return a.value, d.value
 
     # -- scene hand-over (Application.cpp:230-234) -------------------------------------------------
-    def _hand_over_scene(self, nodes=None):
+    def _hand_over_scene(self, nodes=None, prims=None):
         s = self.scene
-        self.geometry = np.ascontiguousarray(s.geometry, dtype=SPHERE)
+        self.geometry = np.array(s.geometry, dtype=SPHERE, order="C")        # a copy of this object's own: update_spheres edits it, not the scene
         self.material = np.ascontiguousarray(s.material, dtype=MATERIAL)
         self.nodes, self.prims = bvh_build(self.geometry)
         if nodes is not None:
             self.nodes = np.ascontiguousarray(nodes, dtype=NODE)
+        if prims is not None:
+            self.prims = np.array(prims, dtype=SPHERE, order="C")
+        self._bvh_of_geometry = geometry_to_bvh_order(self.geometry, self.prims)   # once per hand-over: what update_spheres addresses the BVH order with
         self.lights = light_list(self.geometry, self.material)
         hdri = np.ascontiguousarray(s.hdri, dtype=np.float32)
         amb = np.ascontiguousarray(s.ambient, dtype=np.float32)
@@ -547,6 +569,27 @@ class _Binding:
                    _ptr(self.material), len(self.material), _ptr(lights), len(self.lights), _ptr(amb), _ptr(hdri), hdri.shape[1], hdri.shape[0])
         self._ambient = amb.reshape(-1).copy()             # what environment() reports: the library keeps it and has no getter for it
         self.UpdateCamera()
+
+    # -- spheres moved in place (mirt.h "moving spheres in place") ------------------------------------------------------------------
+    def update_spheres(self, indices, position=None, radius_sq=None):
+        """The reference's SceneUpdate::Geometry for spheres that keep their place (mirt_update_spheres): geometry-order spheres `indices` (what an
+        editor holds) take `position` [n, 3] and `radius_sq` [n]; None keeps each sphere's current value.  The traversal tree keeps its topology
+        and gets new boxes on the GPU: no rebuild, no re-upload; the BVH order stays the one handed over.  Geometry is part of the estimand and
+        the accumulator is NOT reset: call ResetAccumulator().  The temporal history is dropped.  self.geometry and self.prims are edited in
+        step; the scene object is not written: UpdateScene() hands its own geometry over again.  (A group: on every member.)"""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        n_spheres = len(self.geometry)
+        if len(idx) and (idx.min() < 0 or idx.max() >= n_spheres):
+            raise ValueError(f"sphere index out of range: the scene has {n_spheres} spheres")
+        g = idx.astype(np.uint32)
+        packet = np.empty((len(g), 4), dtype=np.float32)
+        packet[:, :3] = self.geometry["position"][g] if position is None else np.asarray(position, dtype=np.float32).reshape(len(g), 3)
+        packet[:, 3] = self.geometry["radius_sq"][g] if radius_sq is None else np.asarray(radius_sq, dtype=np.float32).reshape(len(g))
+        b = np.ascontiguousarray(self._bvh_of_geometry[g])
+        self._call("update_spheres", len(g), _ptr(b) if len(g) else None, _ptr(g) if len(g) else None, _ptr(packet) if len(g) else None)
+        for arr, at in ((self.geometry, g), (self.prims, b)):                # only an edit the library accepted becomes this object's
+            arr["position"][at] = packet[:, :3]
+            arr["radius_sq"][at] = packet[:, 3]
 
     # -- the environment on its own (mirt.h "replacing the environment map on its own", "analytic sun and sky") -------------------
     sun_sky_defaults = staticmethod(sun_sky_defaults)
@@ -873,10 +916,11 @@ class Renderer(_Binding):
         self._call("get_stream_order", C.byref(v))
         return v.value
 
-    def UpdateScene(self, nodes=None):
+    def UpdateScene(self, nodes=None, prims=None):
         """Hands the scene over again (after an edit).  `nodes`: a caller-made tree over the reference-order prims instead of the
-        reference builder's (BVH.hpp:18-31 layout, children at first_id / first_id+1, leaves first_id..first_id+prim_count-1)."""
-        self._hand_over_scene(nodes)
+        reference builder's (BVH.hpp:18-31 layout, children at first_id / first_id+1, leaves first_id..first_id+prim_count-1).
+        `prims`: a caller-made BVH-order array (a permutation of the geometry's rows) instead of the reference builder's."""
+        self._hand_over_scene(nodes, prims)
 
     @staticmethod
     def RequiredTiling() -> int:          # Renderer.hpp:36

@@ -27,13 +27,13 @@
 #include <string>
 
 #include "lbvh_build.hpp"
+#include "box_device.hpp"
 
 namespace mirt_gpu {
 namespace {
 
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kLeafBit = 0x80000000u;
-constexpr float kPadRel = 0x1p-18f;                     // bvh_layout.hpp kPadRel
 
 __device__ __forceinline__ uint32_t ordered_bits(float f) {               // monotone float -> uint
 	const uint32_t b = __float_as_uint(f);
@@ -42,31 +42,14 @@ __device__ __forceinline__ uint32_t ordered_bits(float f) {               // mon
 __device__ __forceinline__ float from_ordered(uint32_t u) {
 	return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
-__device__ __forceinline__ float next_up(float x) {                       // finite x
-	if (x == 0.0f) return __uint_as_float(1u);
-	uint32_t b = __float_as_uint(x);
-	return __uint_as_float(x > 0.0f ? b + 1u : b - 1u);
-}
-__device__ __forceinline__ float next_down(float x) { return -next_up(-x); }
-
-struct Box { float lo[3], hi[3]; };
+using mirt_box::Box; using mirt_box::box_union; using mirt_box::half_down; using mirt_box::half_up;   // box_device.hpp: shared with the refit
 
 // Leaf boxes as in mirt_host::build_records, plus a histogram of the radii's binary exponents (integer atomics: the same tree every run).
 __global__ __launch_bounds__(kBlock) void k_leaf_boxes(const float4* __restrict__ spheres, uint32_t n, Box* __restrict__ leaf_box, uint32_t* __restrict__ exp_hist /* [256] */) {
 	const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
 	if (i >= n) return;
-	const float4 s = spheres[i];
-	const float c[3] = { s.x, s.y, s.z };
-	const float r = __builtin_sqrtf(s.w);
-	float amax = fabsf(c[0]);
-	if (amax < fabsf(c[1])) amax = fabsf(c[1]);
-	if (amax < fabsf(c[2])) amax = fabsf(c[2]);
-	const float pad = kPadRel * (amax + r);
-	Box b;
-	for (int a = 0; a < 3; a++) {
-		b.lo[a] = next_down((c[a] - r) - pad);
-		b.hi[a] = next_up((c[a] + r) + pad);
-	}
+	float r;
+	const Box b = mirt_box::sphere_leaf_box(spheres[i], &r);
 	leaf_box[i] = b;
 	atomicAdd(&exp_hist[(__float_as_uint(r) >> 23) & 0xffu], 1u);
 }
@@ -145,11 +128,6 @@ __global__ __launch_bounds__(kBlock) void k_karras(const uint64_t* __restrict__ 
 	if (i == 0) parent_of_inner[0] = 0xffffffffu;
 }
 
-__device__ __forceinline__ Box box_union(const Box& x, const Box& y) {
-	Box b;
-	for (int a = 0; a < 3; a++) { b.lo[a] = (y.lo[a] < x.lo[a]) ? y.lo[a] : x.lo[a]; b.hi[a] = (x.hi[a] < y.hi[a]) ? y.hi[a] : x.hi[a]; }
-	return b;
-}
 // Bottom-up: one thread per leaf climbs; the second thread to reach a node owns it (both child boxes are then complete).
 __global__ __launch_bounds__(kBlock) void k_inner_boxes(const uint64_t* __restrict__ keys, uint32_t n, const uint32_t* __restrict__ child0, const uint32_t* __restrict__ child1,
                                                         const uint32_t* __restrict__ parent_of_inner, const uint32_t* __restrict__ parent_of_leaf,
@@ -191,12 +169,6 @@ __global__ __launch_bounds__(kBlock) void k_record_index(uint32_t n_inner, const
 __device__ __forceinline__ float half_area(const Box& b) {
 	const float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
 	return (dx * dy + dy * dz) + dz * dx;
-}
-__device__ __forceinline__ uint32_t half_down(float f) {                  // largest binary16 <= f
-	return static_cast<uint32_t>(__half_as_ushort(__float2half_rd(f)));
-}
-__device__ __forceinline__ uint32_t half_up(float f) {
-	return static_cast<uint32_t>(__half_as_ushort(__float2half_ru(f)));
 }
 // One child-pair record per inner node, in the layouts of bvh_layout.hpp (64-B f32 and 32-B binary16).
 __global__ __launch_bounds__(kBlock) void k_emit_records(const uint64_t* __restrict__ keys, uint32_t n_inner, const uint32_t* __restrict__ child0, const uint32_t* __restrict__ child1,

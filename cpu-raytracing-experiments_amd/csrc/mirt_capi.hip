@@ -12,6 +12,8 @@
 #include "denoise.hpp"
 #include "temporal.hpp"
 #include "sun_sky.hpp"
+#include "refit.hpp"
+#include "scene_update_host.hpp"
 #include "bvh_layout.hpp"
 #include "bvh_build.hpp"
 #include "lbvh_build.hpp"
@@ -105,6 +107,12 @@ struct mirt_ctx {
 	// scene
 	DeviceBuffer recs, recs_wide, spheres, prim_mat, light_sphere, light_emit, mat_albedo, mat_emission, mat_ggx, mat_glass, hdri;
 	SceneDev scene{};
+	// mirt_update_spheres: what the refit reads besides the records (refit.hpp RefitLinks; one allocation, built from the records by the first refit of a
+	// tree, invalidated by mirt_set_scene), the uploaded edit list, and the host side of the light table (ids and rows as mirt_set_scene flattened them)
+	DeviceBuffer refit_links, refit_edits;
+	bool refit_links_valid = false;
+	std::vector<int32_t> light_ids;
+	std::vector<float4> light_sphere_host;
 	bool env_baked = false;          // the environment map in `hdri` was written by k_sun_sky (mirt_set_sun_sky), not handed over by the caller
 	uint32_t transmission = 0;       // mirt_set_transmission: 1 = a transmissive material takes the dielectric interface (the GLASS instantiations of k_shade)
 	std::vector<float4> glass_host;  // the scene's {transmission.rgb, 1 + IOR_minus_one} per material, as uploaded: what the switch validates and looks for glass in
@@ -1268,7 +1276,7 @@ int mirt_destroy(mirt_ctx* c) {
 	c->slots.clear();
 	for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
 	DeviceBuffer* bufs[] = { &c->recs, &c->recs_wide, &c->spheres, &c->prim_mat, &c->light_sphere, &c->light_emit, &c->mat_albedo, &c->mat_emission,
-	                         &c->mat_ggx, &c->mat_glass, &c->mat_merged, &c->hdri, &c->sky_table, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
+	                         &c->mat_ggx, &c->mat_glass, &c->mat_merged, &c->hdri, &c->refit_links, &c->refit_edits, &c->sky_table, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
 	                         &c->cand, &c->cand_listed, &c->cand_words, &c->noise_rec, &c->noise_hist, &c->noise_above,
 	                         &c->dn_cv[0], &c->dn_cv[1], &c->dn_gd, &c->dn_mu, &c->tile_frozen, &c->active_list, &c->tile_counts,
 	                         &c->th_x, &c->th_g, &c->th_n, &c->th_len, &c->th_stats };
@@ -1308,6 +1316,8 @@ int mirt_set_scene(mirt_ctx* c, const mirt_sphere* geometry, const mirt_sphere* 
 	if ((r = plan_trace_lds(c))) return r;
 	c->have_scene = true;
 	c->env_baked = false;
+	c->refit_links_valid = false;                                                      // another tree
+	c->light_ids.assign(lights, lights + n_lights); c->light_sphere_host = t.lsp;      // what mirt_update_spheres patches
 	return MIRT_OK;
 }
 
@@ -2220,3 +2230,63 @@ int mirt_set_sun_sky(mirt_ctx* c, const mirt_sun_sky_params* p) {
 int mirt_debug_allow_half_boxes(mirt_ctx* c, int allow) { if (!c) return MIRT_ERR_ARG; c->allow_half = allow != 0; return MIRT_OK; }
 
 } // extern "C"
+
+// ---- the Geometry update: spheres moved in place (mirt.h "moving spheres in place") ------------------------------------------------------
+namespace {
+// The links of the tree in place (refit.hpp), carved from c->refit_links: built by one kernel the first time a tree is refitted.
+RefitLinks refit_links_of(mirt_ctx* c) {
+	const size_t nr = c->scene.n_recs, np = c->scene.n_spheres;
+	RefitLinks l;
+	l.parent = c->refit_links.as<uint32_t>(); l.used = l.parent + nr; l.leaf_rec = l.used + nr; l.arrivals = l.leaf_rec + np;
+	l.box = reinterpret_cast<mirt_box::Box*>(l.arrivals + nr);
+	return l;
+}
+template <int L> void launch_refit(mirt_ctx* c, const RefitLinks& l, bool links) {
+	const SceneDev& s = c->scene;
+	uint4* recs = reinterpret_cast<uint4*>(const_cast<float4*>(s.recs));       // c->recs or c->recs_wide: this context's own allocation
+	if (links) hipLaunchKernelGGL(k_refit_links<L>, dim3((s.n_recs + kRefitBlock - 1u) / kRefitBlock), dim3(kRefitBlock), 0, c->stream, recs, s.n_recs, s.n_spheres, l);
+	else hipLaunchKernelGGL(k_refit<L>, dim3((s.n_spheres + kRefitBlock - 1u) / kRefitBlock), dim3(kRefitBlock), 0, c->stream, recs, s.n_recs, s.spheres, s.n_spheres, l);
+}
+void launch_refit(mirt_ctx* c, const RefitLinks& l, bool links) {
+	if (c->scene.wide) launch_refit<kRefitWide>(c, l, links);
+	else if (c->scene.half_boxes) launch_refit<kRefitHalf>(c, l, links);
+	else launch_refit<kRefitF32>(c, l, links);
+}
+} // namespace
+
+extern "C" int mirt_update_spheres(mirt_ctx* c, uint32_t n, const uint32_t* bvh_index, const uint32_t* geometry_index, const float* xyz_rsq) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!c->have_scene) return fail(c, MIRT_ERR_STATE, "mirt_update_spheres moves spheres of a scene: mirt_set_scene first");
+	SceneDev& s = c->scene;
+	{ char msg[320];                                                             // before anything changes: a refused call leaves every word in place
+	  if (const int r = mirt_scene_update::check(n, bvh_index, geometry_index, xyz_rsq, s.n_spheres, s.half_boxes != 0, msg, sizeof msg)) return fail(c, r, "%s", msg); }
+	if (n == 0) return MIRT_OK;
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }                      // deferred accumulations and batches in flight see the old geometry
+	// the edit list, then the scatter into c->spheres
+	const size_t index_bytes = (static_cast<size_t>(n) * 4u + 15u) & ~static_cast<size_t>(15u);
+	HIP_TRY(c, c->refit_edits.ensure(index_bytes + static_cast<size_t>(n) * sizeof(float4)));
+	uint32_t* d_index = c->refit_edits.as<uint32_t>();
+	float4* d_packet = reinterpret_cast<float4*>(static_cast<char*>(c->refit_edits.ptr) + index_bytes);
+	const size_t nr = s.n_recs, np = s.n_spheres;
+	if (!c->refit_links_valid) HIP_TRY(c, c->refit_links.ensure((3u * nr + np) * 4u + nr * sizeof(mirt_box::Box)));
+	const RefitLinks l = refit_links_of(c);
+	HIP_TRY(c, hipMemcpyAsync(d_index, bvh_index, static_cast<size_t>(n) * 4u, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(c, hipMemcpyAsync(d_packet, xyz_rsq, static_cast<size_t>(n) * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+	hipLaunchKernelGGL(k_update_spheres, dim3((n + kRefitBlock - 1u) / kRefitBlock), dim3(kRefitBlock), 0, c->stream, n, d_index, d_packet, c->spheres.as<float4>(), s.n_spheres);
+	// every box of the records, over the topology in place
+	if (nr) {
+		if (!c->refit_links_valid) launch_refit(c, l, true);
+		HIP_TRY(c, hipMemsetAsync(l.arrivals, 0, nr * 4u, c->stream));
+		launch_refit(c, l, false);
+	}
+	HIP_TRY(c, hipGetLastError());
+	// next event estimation reads the lights' spheres from a table of its own
+	if (mirt_scene_update::patch_lights(c->light_ids.data(), static_cast<uint32_t>(c->light_ids.size()), n, geometry_index, xyz_rsq, s.n_spheres,
+	                                    reinterpret_cast<float*>(c->light_sphere_host.data())))
+		{ const int r = upload(c, c->light_sphere, c->light_sphere_host); if (r) return r; }
+	HIP_TRY(c, hipStreamSynchronize(c->stream));                                  // host buffers are copied, never retained
+	c->refit_links_valid = true;
+	c->cand_valid = false;                                                        // the camera-ray lists name the spheres of the old positions
+	drop_history(c);                                                              // surfaces moved: nothing of the old view may be reprojected onto them
+	return MIRT_OK;
+}

@@ -203,7 +203,14 @@ GROUP_FORWARD(set_sky_sampling, (mirt_group* g, uint32_t on), (ctx, on))        
 GROUP_FORWARD(set_ggx_pdf, (mirt_group* g, uint32_t on), (ctx, on))
 GROUP_FORWARD(set_environment, (mirt_group* g, const float ambient_color[3], const float* hdri_rgba, uint32_t w, uint32_t h), (ctx, ambient_color, hdri_rgba, w, h))
 GROUP_FORWARD(set_sun_sky, (mirt_group* g, const mirt_sun_sky_params* params), (ctx, params))     // every member bakes its own map, word for word the same (a fixed order, no atomics)
-GROUP_FORWARD(set_material_closures, (mirt_group* g, const uint8_t* closure, uint32_t n), (ctx, closure, n))   // the gather context too: its first-hit AOV colour follows the table
+// The members only: the gather context was handed a scene without geometry (mirt_group_set_scene), so there is nothing of it to move.
+int mirt_group_update_spheres(mirt_group* g, uint32_t n, const uint32_t* bvh_index, const uint32_t* geometry_index, const float* xyz_rsq) {
+	if (!g) return MIRT_ERR_ARG;
+	FOR_MEMBERS(g, "mirt_update_spheres", mirt_update_spheres(ctx, n, bvh_index, geometry_index, xyz_rsq));
+	if (g->full && n) FULL_TRY(g, "mirt_drop_history", mirt_drop_history(g->full));   // its history shows the surfaces where they were
+	return MIRT_OK;
+}
+GROUP_FORWARD(set_material_closures,(mirt_group* g, const uint8_t* closure, uint32_t n), (ctx, closure, n))   // the gather context too: its first-hit AOV colour follows the table
 int mirt_group_pick_focus(mirt_group* g, uint32_t x, uint32_t y, float* distance, float* depth) {
 	if (!g) return MIRT_ERR_ARG;
 	mirt_ctx* ctx = g->members[0];                                                   // one ray: every member holds the whole scene

@@ -211,6 +211,8 @@ int main(int argc, char** argv) {
 	float sun_elevation = 0.0f, sun_azimuth = 0.0f, sun_turbidity = -1.0f, sun_orbit_deg = 0.0f;   // turbidity -1: the default
 	uint32_t env_w = 0, env_h = 0;                                             // 0: the default map size
 	std::string env_out;
+	struct SphereMove { uint32_t index; float step[3]; };                       // --move-sphere: geometry-order sphere `index` moves by `step` between frames
+	std::vector<SphereMove> moves;
 	if (argc == 4 && std::string(argv[1]) == "--convert-hdr") {
 		// file-format check without a GPU: read a picture like stbi_loadf does (top-down) and store it again like Image::Store does (which
 		// flips, so the rows are handed over bottom-up): the output decodes to the same texels
@@ -233,6 +235,7 @@ int main(int argc, char** argv) {
 			          "              [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm] [--denoise [ITERATIONS]] [--denoise-plain-out FILE]\n"
 			          "              [--temporal [MAX_RATIO]] [--orbit DEG]\n"
 		          "              [--sun-sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY]] [--env-size WxH] [--env-out env.hdr] [--sun-orbit DEG]\n"
+		          "              [--move-sphere I:DX,DY,DZ]...\n"
 			          "mirt_headless --convert-hdr in.hdr out.hdr\n"
 			          "  --sky-sampling  the environment map (--hdri, --ambient) is one more light of next event estimation, drawn by importance (mirt_set_sky_sampling)\n"
 			          "  --ggx-pdf  the GGX closure's visible-normal pdf in the MIS weights: emitters and the sampled sky are weighed two ways on GGX surfaces (mirt_set_ggx_pdf)\n"
@@ -245,6 +248,7 @@ int main(int argc, char** argv) {
 		          "  --env-size WxH  texels of the map --sun-sky bakes (mirt_sun_sky_defaults: 1025x513)\n"
 		          "  --env-out FILE  the environment map the kernels read, written as Radiance .hdr (mirt_read_environment)\n"
 		          "  --sun-orbit DEG with --sun-sky and --frames: after every frame of `buckets` accumulations the sun turns DEG degrees about the vertical and the accumulator is reset (mirt_set_sun_sky alone: no mirt_set_scene)\n"
+		          "  --move-sphere I:DX,DY,DZ  with --frames: before every frame after the first, geometry-order sphere I moves by (DX, DY, DZ) and the accumulator is reset; the tree in place is refitted on the GPU (mirt_update_spheres alone: no mirt_set_scene).  Repeatable\n"
 		          "  --closures LIST the closure of material 0, 1, ...: 0 Lambertian, 1 GGX; materials beyond the list take --brdf (mirt_set_material_closures)");
 			return 0;
 		}
@@ -286,6 +290,7 @@ int main(int argc, char** argv) {
 		else if (a == "--sun-sky") { const int got = std::sscanf(next(), "%f,%f,%f", &sun_elevation, &sun_azimuth, &sun_turbidity); if (got < 2) return 2; sun_sky = true; }
 		else if (a == "--env-size") { if (std::sscanf(next(), "%ux%u", &env_w, &env_h) != 2) return 2; }
 		else if (a == "--env-out") env_out = next();
+		else if (a == "--move-sphere") { SphereMove m{}; if (std::sscanf(next(), "%u:%f,%f,%f", &m.index, &m.step[0], &m.step[1], &m.step[2]) != 4) return 2; moves.push_back(m); }
 		else if (a == "--sun-orbit") sun_orbit_deg = static_cast<float>(std::atof(next()));
 		else if (a == "--devices") { devices.clear(); for (const char* p = next(); *p;) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p == ',') p++; } if (devices.empty()) return 2; }
 		else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -367,6 +372,28 @@ int main(int argc, char** argv) {
 				renderer.Accumulate(policy.buckets);
 				if (renderer.Render()) { have_frame = true; frames_due += (frames_due.empty() ? "" : ", ") + std::to_string(frame + 1); }
 				if (frame + 1 < spp) { sun_azimuth += sun_orbit_deg; aim_sun(); renderer.ResetAccumulator(); }
+			}
+		}
+		else if (!moves.empty()) {
+			// A drag: every frame is `buckets` accumulations; then the spheres move in both of the scene's arrays and UpdateSpheres hands those rows over
+			// alone — no RebuildAcceleration(), no SceneChanged(): the tree in place is refitted — and the accumulator is reset (Application.cpp:466-468,510).
+			std::vector<uint32_t> geometry_index, bvh_index;
+			for (const SphereMove& m : moves) {
+				if (m.index >= scene.geometry.size()) { std::fprintf(stderr, "--move-sphere %u: the scene has %zu spheres\n", m.index, scene.geometry.size()); return 2; }
+				geometry_index.push_back(m.index); bvh_index.push_back(renderer.BvhIndexOf(m.index));
+			}
+			for (uint32_t frame = 0; frame < spp; frame++) {
+				renderer.Accumulate(policy.buckets);
+				if (renderer.Render()) { have_frame = true; frames_due += (frames_due.empty() ? "" : ", ") + std::to_string(frame + 1); }
+				if (frame + 1 < spp) {
+					for (size_t k = 0; k < moves.size(); k++) {
+						Sphere& g = scene.geometry[geometry_index[k]];
+						for (int a = 0; a < 3; a++) g.position[a] += moves[k].step[a];
+						scene.acceleration_structure.prims[bvh_index[k]] = g;
+					}
+					renderer.UpdateSpheres(bvh_index, geometry_index);
+					renderer.ResetAccumulator();
+				}
 			}
 		}
 		else if (temporal || orbit_deg != 0.0f) {

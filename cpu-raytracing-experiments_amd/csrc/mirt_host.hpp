@@ -11,6 +11,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -219,6 +220,26 @@ public:
 		e.rgba.resize(static_cast<size_t>(e.width) * e.height * 4);
 		if (mirt_read_environment(ctx, e.rgba.data(), e.rgba.size(), info) < 0) throw std::runtime_error(std::string("mirt_read_environment: ") + mirt_last_error(ctx));
 		return e;
+	}
+	// SceneUpdate::Geometry for spheres that keep their place (Application.cpp:466-468; mirt.h, mirt_update_spheres): the caller has written the new
+	// centre and radius_sq into scene.geometry[geometry_index[i]] and into scene.acceleration_structure.prims[bvh_index[i]], the same sphere in the
+	// order hit.primID refers to (BvhIndexOf finds it); those rows alone are handed over and the tree in place is refitted on the GPU — no
+	// RebuildAcceleration(), no SceneChanged().  Geometry is part of the estimand: ResetAccumulator() is the caller's to call.
+	void UpdateSpheres(const std::vector<uint32_t>& bvh_index, const std::vector<uint32_t>& geometry_index) {
+		if (bvh_index.size() != geometry_index.size()) throw std::runtime_error("UpdateSpheres: one bvh_index per geometry_index");
+		std::vector<float> packet;
+		packet.reserve(4 * geometry_index.size());
+		for (const uint32_t g : geometry_index) {
+			const Sphere& s = scene.geometry.at(g);
+			packet.insert(packet.end(), { s.position[0], s.position[1], s.position[2], s.radius_sq });
+		}
+		check(mirt_group_update_spheres(group_, static_cast<uint32_t>(geometry_index.size()), bvh_index.data(), geometry_index.data(), packet.data()), "mirt_group_update_spheres");
+	}
+	// Where scene.geometry[g] sits in scene.acceleration_structure.prims: the first row with the same 32 bytes (identical rows are interchangeable).
+	uint32_t BvhIndexOf(uint32_t g) const {
+		const std::vector<Sphere>& prims = scene.acceleration_structure.prims;
+		for (size_t b = 0; b < prims.size(); b++) if (std::memcmp(&prims[b], &scene.geometry.at(g), sizeof(Sphere)) == 0) return static_cast<uint32_t>(b);
+		throw std::runtime_error("BvhIndexOf: scene.acceleration_structure.prims does not hold that sphere (RebuildAcceleration() first)");
 	}
 	// The GGX closure's pdf in the MIS weights (mirt.h, mirt_set_ggx_pdf): off by default, as in the reference, whose Closure<GGX>::pdf returns 0.
 	// On: emitters and (under sky sampling) the sky are weighed two ways on GGX surfaces.  Formally another estimator: Reset() is the caller's to call.

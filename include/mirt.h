@@ -419,6 +419,36 @@ typedef struct mirt_sun_sky_params {
 int mirt_sun_sky_defaults(mirt_sun_sky_params* out);
 int mirt_set_sun_sky(mirt_ctx* ctx, const mirt_sun_sky_params* params);
 
+/* ---- moving spheres in place: the reference's SceneUpdate::Geometry without a rebuild ---------------------------------------------------
+ * The reference's editor drags or resizes a sphere (Application.cpp:466-468) and rebuilds its BVH on the host (:508).  mirt_update_spheres is
+ * that edit for spheres that keep their place in both arrays: sphere bvh_index[i] of the BVH-order array hit.primID refers to — the same sphere
+ * as geometry_index[i] of the authoring-order geometry — takes centre and radius_sq xyz_rsq[4 i .. 4 i + 3].  NOTHING else changes: the order of
+ * both arrays, the material ids, the materials, the light list and the environment stay; no other sphere is uploaded again, no tree is built, no
+ * environment map is uploaded.  THE CALLER'S BVH ORDER IS KEPT.  The order is part of the result (Renderer.hpp:261-263 compares hit.primID with
+ * geometry-order light ids), so the update renders the scene "old order, new spheres" — a valid Scene, not necessarily the order the
+ * reference's builder would pick after the move.  After it, accumulator, frame, AOVs and the rays, shadow_rays, terminated and dropped counters
+ * equal, word for word, those of a fresh context given mirt_set_scene with the edited geometry and bvh_prims IN THE SAME ORDER, the same nodes and
+ * everything else unchanged — under every policy and in exact stream order.  The nodes and spheres counters of count_traffic may differ: they
+ * describe the tree, and the tree in place keeps its topology (DESIGN.md "Traversal semantics": results do not depend on it).
+ * Geometry is part of the estimand and the accumulator is NOT reset: the caller calls mirt_reset, as Application.cpp:510 does.
+ * Deferred mirt_accumulate_async calls are launched first, under the old geometry, and every stream is waited for.  Then: the edited rows of
+ * the sphere table are scattered (k_update_spheres); EVERY box of the records the kernels walk is recomputed on the device over the topology in
+ * place (k_refit, csrc/refit.hpp) — leaf boxes as mirt_set_scene makes them, r = sqrt(radius_sq), pad = 2^-18 (max|c| + r), one binary32 step
+ * outward; inner boxes their unions; binary16 planes rounded outward — which are the words a fresh build over that topology writes; the row of
+ * every light whose geometry id is edited is replaced; the camera-ray candidate lists are rebuilt by the next batch; the temporal history is
+ * dropped (surfaces moved).  Not touched: the material tables, the environment and its sampling table, the LDS plan, the switches.
+ * How far a tree may be refitted before mirt_set_scene pays is the caller's decision (DESIGN.md section 4 has measurements).
+ * Everything is checked BEFORE anything changes — a refused call leaves every word in place:  MIRT_ERR_STATE before mirt_set_scene;
+ * MIRT_ERR_ARG for a NULL array with n > 0, an index >= n_spheres, a bvh_index or a geometry_index that occurs twice in one call, a value that
+ * is not finite or radius_sq < 0 (mirt_set_scene's rules);  MIRT_ERR_STATE when the records in place are binary16 (child-pair or 4-wide) and an
+ * edited sphere does not fit them — a coordinate beyond 60000 or a diameter under 8 binary16 steps at its magnitude, the rule mirt_set_scene
+ * applies per sphere when it chooses the layout: a refit does not change layouts, call mirt_set_scene.  With f32 records the same edit is
+ * accepted.  n = 0: MIRT_OK, nothing done. */
+int mirt_update_spheres(mirt_ctx* ctx, uint32_t n,
+                        const uint32_t* bvh_index,       /* index into the BVH-order prims hit.primID refers to */
+                        const uint32_t* geometry_index,  /* index of the same sphere in the authoring-order geometry */
+                        const float*    xyz_rsq);        /* n x {position.x, .y, .z, radius_sq} */
+
 /* Renderer::Resize, Renderer.hpp:53-63: h_tiles = w/16, v_tiles = h/16 (truncating), allocates and zeroes
  * the accumulator, accumulations = 0.  Owns all tiles until mirt_set_tile_range says otherwise. */
 int mirt_resize(mirt_ctx* ctx, uint32_t width, uint32_t height);
@@ -772,6 +802,7 @@ int mirt_group_set_ggx_pdf(mirt_group* group, uint32_t on);                     
 int mirt_group_set_material_closures(mirt_group* group, const uint8_t* closure, uint32_t n);   /* mirt_set_material_closures on every member (and the gather context) */
 int mirt_group_set_environment(mirt_group* group, const float ambient_color[3], const float* hdri_rgba, uint32_t w, uint32_t h);   /* mirt_set_environment on every member (and the gather context) */
 int mirt_group_set_sun_sky(mirt_group* group, const mirt_sun_sky_params* params);   /* mirt_set_sun_sky on every member (and the gather context): each bakes its own map, the same words */
+int mirt_group_update_spheres(mirt_group* group, uint32_t n, const uint32_t* bvh_index, const uint32_t* geometry_index, const float* xyz_rsq);   /* mirt_update_spheres on every member (the gather context holds no geometry) */
 int mirt_group_pick_focus(mirt_group* group, uint32_t x, uint32_t y, float* distance, float* depth);   /* mirt_pick_focus on the first member */
 int mirt_group_set_policy(mirt_group* group, const mirt_policy* policy);
 int mirt_group_set_gloss_decay(mirt_group* group, const float* decay, uint32_t n);
