@@ -190,6 +190,8 @@ def load_library():
         "mirt_sun_sky_defaults": [C.POINTER(SunSkyParams)],
         "mirt_set_sun_sky": [P, C.POINTER(SunSkyParams)],
         "mirt_update_spheres": [P, u32, vp, vp, vp],
+        "mirt_update_materials": [P, u32, vp, vp, u32, vp, vp, vp],
+        "mirt_debug_lights": [P, vp, vp, vp, C.c_size_t, vp],
         "mirt_get_counters": [P, C.POINTER(Counters)],
         "mirt_get_kernel_times": [P, C.POINTER(KernelTimes), i32],
         "mirt_get_stream": [P, C.POINTER(vp)],
@@ -217,6 +219,7 @@ def load_library():
         "mirt_group_set_environment": [G, vp, vp, u32, u32],
         "mirt_group_set_sun_sky": [G, C.POINTER(SunSkyParams)],
         "mirt_group_update_spheres": [G, u32, vp, vp, vp],
+        "mirt_group_update_materials": [G, u32, vp, vp, u32, vp, vp, vp],
         "mirt_group_set_policy": [G, C.POINTER(Policy)],
         "mirt_group_set_gloss_decay": [G, vp, u32],
         "mirt_group_set_stream_order": [G, u32],
@@ -340,6 +343,33 @@ def _closure_table(closures) -> np.ndarray:
         if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v not in (0, 1):
             raise ValueError(f"material_closures[{m}] = {v!r} is neither 0 (Lambertian) nor 1 (GGX)")
     return np.ascontiguousarray(t, dtype=np.uint8)
+
+
+def _index_value_pair(arg, dtype, what: str):
+    """update_materials' two arguments: None, a mapping index -> value or a pair (indices, values) -> (int64 indices, C-contiguous values of `dtype`),
+    one value per index; refused before any call into the library otherwise."""
+    if arg is None:
+        idx, val = [], []
+    elif hasattr(arg, "keys"):
+        idx, val = list(arg.keys()), [arg[k] for k in arg.keys()]
+    else:
+        try:
+            idx, val = arg
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} must be a mapping index -> value or a pair (indices, values)") from None
+    idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+    if len(idx) == 0:
+        return idx, np.zeros(0, dtype=dtype)
+    if isinstance(val, np.ndarray):
+        val = val.astype(dtype, copy=False).reshape(-1)
+    elif np.dtype(dtype).fields:                                         # rows of a structured dtype: records, or tuples field by field
+        val = np.array([v if isinstance(v, np.void) else tuple(v) for v in val], dtype=dtype)
+    else:
+        val = np.asarray(val).astype(dtype).reshape(-1)
+    val = np.ascontiguousarray(val, dtype=dtype)
+    if len(val) != len(idx):
+        raise ValueError(f"{what}: {len(idx)} indices and {len(val)} values")
+    return idx, val
 
 
 def noise_quantile(hist, q: float):
@@ -554,7 +584,7 @@ class _Binding:
     def _hand_over_scene(self, nodes=None, prims=None):
         s = self.scene
         self.geometry = np.array(s.geometry, dtype=SPHERE, order="C")        # a copy of this object's own: update_spheres edits it, not the scene
-        self.material = np.ascontiguousarray(s.material, dtype=MATERIAL)
+        self.material = np.array(s.material, dtype=MATERIAL, order="C")      # likewise: update_materials edits it
         self.nodes, self.prims = bvh_build(self.geometry)
         if nodes is not None:
             self.nodes = np.ascontiguousarray(nodes, dtype=NODE)
@@ -590,6 +620,42 @@ class _Binding:
         for arr, at in ((self.geometry, g), (self.prims, b)):                # only an edit the library accepted becomes this object's
             arr["position"][at] = packet[:, :3]
             arr["radius_sq"][at] = packet[:, 3]
+
+    # -- materials edited in place (mirt.h "updating materials in place") -----------------------------------------------------------
+    def update_materials(self, materials=None, sphere_materials=None):
+        """The reference's SceneUpdate::Material (mirt_update_materials).  `materials`: material index -> row of the MATERIAL dtype, as a mapping
+        or a pair (indices, rows); `sphere_materials`: geometry-order sphere index -> material id, as a mapping or a pair (indices, ids).  Either
+        may be None or empty.  No rebuild, no re-upload of the spheres: the material tables are replaced, the ids scattered and the light list
+        regenerated on the GPU by the reference's rule; the camera-ray lists and the temporal history stay.  Materials are part of the estimand
+        and the accumulator is NOT reset: call ResetAccumulator(), and drop_history() where one is kept.  self.material, self.geometry,
+        self.prims and self.lights are edited in step; the scene object is not written.  (A group: on every member.)"""
+        m_idx, m_rows = _index_value_pair(materials, MATERIAL, "materials")
+        s_idx, s_ids = _index_value_pair(sphere_materials, np.int32, "sphere_materials")
+        for what, idx, limit in (("material", m_idx, len(self.material)), ("sphere", s_idx, len(self.geometry))):
+            if len(idx) and (idx.min() < 0 or idx.max() >= limit):
+                raise ValueError(f"{what} index out of range: the scene has {limit}")
+        mi, g = m_idx.astype(np.uint32), s_idx.astype(np.uint32)
+        b = np.ascontiguousarray(self._bvh_of_geometry[g])
+        opt = lambda a: _ptr(a) if len(a) else None
+        self._call("update_materials", len(mi), opt(mi), opt(m_rows), len(g), opt(b), opt(g), opt(s_ids))
+        self.material[mi] = m_rows                                             # only an edit the library accepted becomes this object's
+        self.geometry["material_ID"][g] = s_ids
+        self.prims["material_ID"][b] = s_ids
+        self.lights = light_list(self.geometry, self.material)
+
+    def lights_table(self) -> dict:
+        """The two per-light tables next event estimation samples, read back from the device (mirt_debug_lights; a group: member 0's): "ids" [n]
+        int32 geometry ids, "sphere" [n, 4] and "emit" [n, 4] float32 (emit[:, 3] holds the id's bits), "n_lights", and the compaction's shape
+        "block" (spheres per workgroup) and "scan_pass" (workgroup totals per pass of the scan)."""
+        info = (C.c_uint32 * 4)()
+        ctx = self._asked()
+        if self._lib.mirt_debug_lights(ctx, None, None, None, 0, info) < 0:
+            raise MirtError("mirt_debug_lights failed: " + self._lib.mirt_last_error(ctx).decode())
+        n = int(info[0])
+        ids, sphere, emit = np.zeros(n, dtype=np.int32), np.zeros((n, 4), dtype=np.float32), np.zeros((n, 4), dtype=np.float32)
+        if n and self._lib.mirt_debug_lights(ctx, _ptr(ids), _ptr(sphere), _ptr(emit), n, info) < 0:
+            raise MirtError("mirt_debug_lights failed: " + self._lib.mirt_last_error(ctx).decode())
+        return {"ids": ids, "sphere": sphere, "emit": emit, "n_lights": n, "block": int(info[1]), "scan_pass": int(info[2])}
 
     # -- the environment on its own (mirt.h "replacing the environment map on its own", "analytic sun and sky") -------------------
     sun_sky_defaults = staticmethod(sun_sky_defaults)

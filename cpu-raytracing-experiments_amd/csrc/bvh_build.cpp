@@ -196,9 +196,7 @@ extern "C" int mirt_light_list(const mirt_sphere* geometry, uint32_t n, const mi
 	for (uint32_t i = 0; i < n; i++) {                                                 // Scene.hpp:13-15
 		const int32_t m = geometry[i].material_ID;
 		if (m < 0 || static_cast<uint32_t>(m) >= n_materials) return MIRT_ERR_ARG;
-		const float* e = materials[m].emission;
-		const float energy = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];               // glm::dot(em, em)
-		if (energy > 0.0f) lights_out[count++] = static_cast<int32_t>(i);
+		if (mirt_host::emits(materials[m].emission)) lights_out[count++] = static_cast<int32_t>(i);   // glm::dot(em, em) > 0 (bvh_build.hpp)
 	}
 	*n_lights_out = count;
 	return MIRT_OK;

@@ -13,6 +13,7 @@
 #include "temporal.hpp"
 #include "sun_sky.hpp"
 #include "refit.hpp"
+#include "light_list.hpp"
 #include "scene_update_host.hpp"
 #include "bvh_layout.hpp"
 #include "bvh_build.hpp"
@@ -113,6 +114,10 @@ struct mirt_ctx {
 	bool refit_links_valid = false;
 	std::vector<int32_t> light_ids;
 	std::vector<float4> light_sphere_host;
+	// mirt_update_materials: the authoring-order geometry on the device (light_list.hpp GeometryTable: what the light tables are regenerated from; uploaded
+	// by mirt_set_scene, kept current by both updates), the workgroup totals of the compaction with the count behind them, and the emission rows as uploaded
+	DeviceBuffer geo_sphere, geo_mat, light_scan;
+	std::vector<float4> emi_host;
 	bool env_baked = false;          // the environment map in `hdri` was written by k_sun_sky (mirt_set_sun_sky), not handed over by the caller
 	uint32_t transmission = 0;       // mirt_set_transmission: 1 = a transmissive material takes the dielectric interface (the GLASS instantiations of k_shade)
 	std::vector<float4> glass_host;  // the scene's {transmission.rgb, 1 + IOR_minus_one} per material, as uploaded: what the switch validates and looks for glass in
@@ -975,16 +980,19 @@ int check_scene_args(mirt_ctx* c, const SceneArgs& a) {
 
 // The scene's tables as the kernels read them (host copies: they outlive the stream synchronisation that ends their uploads).
 struct SceneTables {
-	std::vector<float4> sph, lsp, lem, alb, emi, ggx, gls, sky;
-	std::vector<int32_t> pm;
+	std::vector<float4> sph, lsp, lem, alb, emi, ggx, gls, sky, gsp;
+	std::vector<int32_t> pm, gpm;
 };
 SceneTables flatten_tables(const SceneArgs& a) {
 	SceneTables t;
 	t.sph.resize(a.n_spheres); t.pm.resize(a.n_spheres); t.lsp.resize(a.n_lights); t.lem.resize(a.n_lights);
+	t.gsp.resize(a.n_spheres); t.gpm.resize(a.n_spheres);
 	t.alb.resize(a.n_materials); t.emi.resize(a.n_materials); t.ggx.resize(a.n_materials); t.gls.resize(a.n_materials); t.sky.resize(static_cast<size_t>(a.hdri_w) * a.hdri_h);
 	for (uint32_t i = 0; i < a.n_spheres; i++) {
 		t.sph[i] = make_float4(a.bvh_prims[i].position[0], a.bvh_prims[i].position[1], a.bvh_prims[i].position[2], a.bvh_prims[i].radius_sq);
 		t.pm[i] = a.bvh_prims[i].material_ID;
+		t.gsp[i] = make_float4(a.geometry[i].position[0], a.geometry[i].position[1], a.geometry[i].position[2], a.geometry[i].radius_sq);   // light_list.hpp GeometryTable
+		t.gpm[i] = a.geometry[i].material_ID;
 	}
 	// NEE reads scene.geometry[light], then material[geometry[light].material_ID].emission (Renderer.hpp:261-263,283):
 	// flattened to one table per light so the kernel makes two independent loads instead of four dependent ones
@@ -1008,15 +1016,10 @@ SceneTables flatten_tables(const SceneArgs& a) {
 
 // mirt_set_transmission(1) asks this of the materials (rows {transmission.rgb, 1 + IOR_minus_one}); with the switch off no kernel reads them and
 // nothing is asked, as ever.  A transmissive material (max(transmission) > 0) needs a finite index above 0.
+// The rule itself is scene_update_host.hpp's check_glass_rows: mirt_update_materials asks it of the table an edit would leave.
 int check_glass(mirt_ctx* c, const std::vector<float4>& gls) {
-	for (size_t i = 0; i < gls.size(); i++) {
-		const float t[3] = { gls[i].x, gls[i].y, gls[i].z };
-		for (int k = 0; k < 3; k++)
-			if (!(t[k] >= 0.0f && t[k] <= 1.0f)) return fail(c, MIRT_ERR_ARG, "material %zu: transmission[%d] = %g is not in [0, 1] (mirt_set_transmission is on)", i, k, static_cast<double>(t[k]));
-		const bool transmissive = t[0] > 0.0f || t[1] > 0.0f || t[2] > 0.0f;
-		if (transmissive && !(std::isfinite(gls[i].w) && gls[i].w > 0.0f))
-			return fail(c, MIRT_ERR_ARG, "material %zu is transmissive and its IOR_minus_one = %g is not a finite value above -1 (mirt_set_transmission is on)", i, static_cast<double>(gls[i].w) - 1.0);
-	}
+	char msg[256];
+	if (const int r = mirt_scene_update::check_glass_rows(reinterpret_cast<const float*>(gls.data()), gls.size(), msg, sizeof msg)) return fail(c, r, "%s", msg);
 	return MIRT_OK;
 }
 bool has_glass(const std::vector<float4>& gls) {
@@ -1276,7 +1279,7 @@ int mirt_destroy(mirt_ctx* c) {
 	c->slots.clear();
 	for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
 	DeviceBuffer* bufs[] = { &c->recs, &c->recs_wide, &c->spheres, &c->prim_mat, &c->light_sphere, &c->light_emit, &c->mat_albedo, &c->mat_emission,
-	                         &c->mat_ggx, &c->mat_glass, &c->mat_merged, &c->hdri, &c->refit_links, &c->refit_edits, &c->sky_table, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
+	                         &c->mat_ggx, &c->mat_glass, &c->mat_merged, &c->hdri, &c->refit_links, &c->refit_edits, &c->geo_sphere, &c->geo_mat, &c->light_scan, &c->sky_table, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
 	                         &c->cand, &c->cand_listed, &c->cand_words, &c->noise_rec, &c->noise_hist, &c->noise_above,
 	                         &c->dn_cv[0], &c->dn_cv[1], &c->dn_gd, &c->dn_mu, &c->tile_frozen, &c->active_list, &c->tile_counts,
 	                         &c->th_x, &c->th_g, &c->th_n, &c->th_len, &c->th_stats };
@@ -1305,13 +1308,14 @@ int mirt_set_scene(mirt_ctx* c, const mirt_sphere* geometry, const mirt_sphere* 
 	SceneRecords tree;
 	if ((r = upload(c, c->spheres, t.sph)) || (r = build_scene_records(c, a, t.sph, tree)) || (r = upload(c, c->prim_mat, t.pm)) ||
 	    (r = upload(c, c->light_sphere, t.lsp)) || (r = upload(c, c->light_emit, t.lem)) || (r = upload(c, c->mat_albedo, t.alb)) ||
-	    (r = upload(c, c->mat_emission, t.emi)) || (r = upload(c, c->mat_ggx, t.ggx)) || (r = upload(c, c->mat_glass, t.gls)) || (r = upload(c, c->hdri, t.sky))) return r;
+	    (r = upload(c, c->mat_emission, t.emi)) || (r = upload(c, c->mat_ggx, t.ggx)) || (r = upload(c, c->mat_glass, t.gls)) || (r = upload(c, c->hdri, t.sky)) ||
+	    (r = upload(c, c->geo_sphere, t.gsp)) || (r = upload(c, c->geo_mat, t.gpm))) return r;
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	c->cand_valid = false;                                                             // spheres or tree changed (a node-only update included)
 	commit_scene(c, a, tree);
 	drop_history(c);                                                                   // other surfaces: nothing of the old view may be reprojected onto them
 	c->glass_host = t.gls; c->scene_has_glass = has_glass(t.gls);
-	c->alb_host = t.alb; c->ggx_host = t.ggx; c->mat_merged_valid = false;
+	c->alb_host = t.alb; c->ggx_host = t.ggx; c->emi_host = t.emi; c->mat_merged_valid = false;
 	if (c->sky_sampling) { HIP_TRY(c, sync_all(c)); if ((r = build_sky_table(c))) return r; }      // (a batch in flight on another stream may read the old table)
 	if ((r = plan_trace_lds(c))) return r;
 	c->have_scene = true;
@@ -2262,17 +2266,19 @@ extern "C" int mirt_update_spheres(mirt_ctx* c, uint32_t n, const uint32_t* bvh_
 	  if (const int r = mirt_scene_update::check(n, bvh_index, geometry_index, xyz_rsq, s.n_spheres, s.half_boxes != 0, msg, sizeof msg)) return fail(c, r, "%s", msg); }
 	if (n == 0) return MIRT_OK;
 	{ const int fr = flush_and_wait(c); if (fr) return fr; }                      // deferred accumulations and batches in flight see the old geometry
-	// the edit list, then the scatter into c->spheres
-	const size_t index_bytes = (static_cast<size_t>(n) * 4u + 15u) & ~static_cast<size_t>(15u);
+	// the edit list, then the scatter into c->spheres and into the geometry-order table (what mirt_update_materials regenerates the light tables from)
+	const size_t index_bytes = (static_cast<size_t>(n) * 8u + 15u) & ~static_cast<size_t>(15u);
 	HIP_TRY(c, c->refit_edits.ensure(index_bytes + static_cast<size_t>(n) * sizeof(float4)));
 	uint32_t* d_index = c->refit_edits.as<uint32_t>();
+	uint32_t* d_geo_index = d_index + n;
 	float4* d_packet = reinterpret_cast<float4*>(static_cast<char*>(c->refit_edits.ptr) + index_bytes);
 	const size_t nr = s.n_recs, np = s.n_spheres;
 	if (!c->refit_links_valid) HIP_TRY(c, c->refit_links.ensure((3u * nr + np) * 4u + nr * sizeof(mirt_box::Box)));
 	const RefitLinks l = refit_links_of(c);
 	HIP_TRY(c, hipMemcpyAsync(d_index, bvh_index, static_cast<size_t>(n) * 4u, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(c, hipMemcpyAsync(d_geo_index, geometry_index, static_cast<size_t>(n) * 4u, hipMemcpyHostToDevice, c->stream));
 	HIP_TRY(c, hipMemcpyAsync(d_packet, xyz_rsq, static_cast<size_t>(n) * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-	hipLaunchKernelGGL(k_update_spheres, dim3((n + kRefitBlock - 1u) / kRefitBlock), dim3(kRefitBlock), 0, c->stream, n, d_index, d_packet, c->spheres.as<float4>(), s.n_spheres);
+	hipLaunchKernelGGL(k_update_spheres, dim3((n + kRefitBlock - 1u) / kRefitBlock), dim3(kRefitBlock), 0, c->stream, n, d_index, d_geo_index, d_packet, c->spheres.as<float4>(), c->geo_sphere.as<float4>(), s.n_spheres);
 	// every box of the records, over the topology in place
 	if (nr) {
 		if (!c->refit_links_valid) launch_refit(c, l, true);
@@ -2288,5 +2294,113 @@ extern "C" int mirt_update_spheres(mirt_ctx* c, uint32_t n, const uint32_t* bvh_
 	c->refit_links_valid = true;
 	c->cand_valid = false;                                                        // the camera-ray lists name the spheres of the old positions
 	drop_history(c);                                                              // surfaces moved: nothing of the old view may be reprojected onto them
+	return MIRT_OK;
+}
+
+// ---- the Material update: materials edited in place (mirt.h "updating materials in place") ------------------------------------------------
+namespace {
+// light_sphere / light_emit, light_ids and scene.n_lights from the geometry-order table and the emission rows in place: the reference's
+// LightingAcceleration constructor as an ordered compaction on the device (light_list.hpp).  No batch is in flight (the caller has waited).
+int regenerate_lights(mirt_ctx* c) {
+	SceneDev& s = c->scene;
+	const uint32_t n = s.n_spheres, n_blocks = (n + kLightBlock - 1u) / kLightBlock;
+	uint32_t n_lights = 0;
+	if (n) {
+		const uint64_t mask = mirt_scene_update::emit_mask(reinterpret_cast<const float*>(c->emi_host.data()), s.n_mat);
+		HIP_TRY(c, c->light_scan.ensure((static_cast<size_t>(n_blocks) + 1u) * 4u));
+		uint32_t* totals = c->light_scan.as<uint32_t>();
+		uint32_t* count = totals + n_blocks;
+		const GeometryTable geo{ c->geo_sphere.as<float4>(), c->geo_mat.as<int32_t>() };
+		hipLaunchKernelGGL(k_light_count, dim3(n_blocks), dim3(kLightBlock), 0, c->stream, geo.material, n, mask, totals);
+		hipLaunchKernelGGL(k_light_scan, dim3(1), dim3(kLightScanPass), 0, c->stream, totals, n_blocks, count);
+		HIP_TRY(c, hipGetLastError());
+		HIP_TRY(c, hipMemcpyAsync(&n_lights, count, 4, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(c, hipStreamSynchronize(c->stream));
+		if (n_lights > n) return fail(c, MIRT_ERR_HIP, "update_materials: the light count read back (%u) exceeds the scene's %u spheres", n_lights, n);
+		// the tables grow to the new count before the scatter (nothing reads the old rows: they are rewritten whole)
+		HIP_TRY(c, c->light_sphere.ensure(std::max<size_t>(n_lights, 1) * sizeof(float4)));
+		HIP_TRY(c, c->light_emit.ensure(std::max<size_t>(n_lights, 1) * sizeof(float4)));
+		if (n_lights) {
+			hipLaunchKernelGGL(k_light_scatter, dim3(n_blocks), dim3(kLightBlock), 0, c->stream, geo, n, mask, totals, c->mat_emission.as<float4>(),
+			                   c->light_sphere.as<float4>(), c->light_emit.as<float4>(), n_lights);
+			HIP_TRY(c, hipGetLastError());
+		}
+	}
+	// the ids and the rows, as mirt_update_spheres' patch_lights wants them
+	std::vector<float4> emit(n_lights);
+	c->light_sphere_host.resize(n_lights);
+	c->light_ids.resize(n_lights);
+	if (n_lights) {
+		HIP_TRY(c, hipMemcpyAsync(emit.data(), c->light_emit.ptr, static_cast<size_t>(n_lights) * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(c, hipMemcpyAsync(c->light_sphere_host.data(), c->light_sphere.ptr, static_cast<size_t>(n_lights) * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(c, hipStreamSynchronize(c->stream));
+	}
+	for (uint32_t l = 0; l < n_lights; l++) std::memcpy(&c->light_ids[l], &emit[l].w, 4);
+	s.light_sphere = c->light_sphere.as<float4>(); s.light_emit = c->light_emit.as<float4>();
+	s.n_lights = n_lights;                                                         // fp.n_lights, fp.mis and the sky's light number follow per launch
+	return MIRT_OK;
+}
+} // namespace
+
+extern "C" int mirt_update_materials(mirt_ctx* c, uint32_t n_rows, const uint32_t* material_index, const mirt_material* rows,
+                                     uint32_t n_assign, const uint32_t* bvh_index, const uint32_t* geometry_index, const int32_t* material_ID) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!c->have_scene) return fail(c, MIRT_ERR_STATE, "mirt_update_materials edits the materials of a scene: mirt_set_scene first");
+	SceneDev& s = c->scene;
+	{ char msg[320];                                                             // before anything changes: a refused call leaves every word in place
+	  if (const int r = mirt_scene_update::check_materials(n_rows, material_index, rows, n_assign, bvh_index, geometry_index, material_ID, s.n_spheres, s.n_mat,
+	                                                       c->transmission != 0, reinterpret_cast<const float*>(c->glass_host.data()), msg, sizeof msg)) return fail(c, r, "%s", msg); }
+	if (n_rows == 0 && n_assign == 0) return MIRT_OK;
+	{ const int fr = flush_and_wait(c); if (fr) return fr; }                      // deferred accumulations and batches in flight see the old materials
+	// the kept host rows, as flatten_tables makes them, and the four small tables again (at most 63 rows each: no kernel)
+	for (uint32_t i = 0; i < n_rows; i++) {
+		const mirt_material& m = rows[i];
+		const uint32_t k = material_index[i];
+		c->alb_host[k] = make_float4(m.albedo[0], m.albedo[1], m.albedo[2], 0.0f);
+		c->emi_host[k] = make_float4(m.emission[0], m.emission[1], m.emission[2], 0.0f);
+		c->ggx_host[k] = make_float4(m.F0[0], m.F0[1], m.F0[2], m.roughness);
+		c->glass_host[k] = make_float4(m.transmission[0], m.transmission[1], m.transmission[2], 1.0f + m.IOR_minus_one);
+	}
+	int r;
+	if (n_rows && ((r = upload(c, c->mat_albedo, c->alb_host)) || (r = upload(c, c->mat_emission, c->emi_host)) || (r = upload(c, c->mat_ggx, c->ggx_host)) ||
+	               (r = upload(c, c->mat_glass, c->glass_host)))) return r;
+	// the re-assigned spheres, in both orders
+	if (n_assign) {
+		const size_t words = static_cast<size_t>(n_assign);
+		HIP_TRY(c, c->refit_edits.ensure(3u * words * 4u));
+		uint32_t* d_bvh = c->refit_edits.as<uint32_t>();
+		uint32_t* d_geo = d_bvh + words;
+		int32_t* d_mat = reinterpret_cast<int32_t*>(d_geo + words);
+		HIP_TRY(c, hipMemcpyAsync(d_bvh, bvh_index, words * 4u, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(c, hipMemcpyAsync(d_geo, geometry_index, words * 4u, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(c, hipMemcpyAsync(d_mat, material_ID, words * 4u, hipMemcpyHostToDevice, c->stream));
+		hipLaunchKernelGGL(k_assign_materials, dim3((n_assign + kLightBlock - 1u) / kLightBlock), dim3(kLightBlock), 0, c->stream, n_assign, d_bvh, d_geo, d_mat,
+		                   c->prim_mat.as<int32_t>(), GeometryTable{ c->geo_sphere.as<float4>(), c->geo_mat.as<int32_t>() }, s.n_spheres);
+		HIP_TRY(c, hipGetLastError());
+	}
+	if ((r = regenerate_lights(c))) return r;
+	HIP_TRY(c, hipStreamSynchronize(c->stream));                                  // host buffers are copied, never retained
+	c->scene_has_glass = has_glass(c->glass_host);                                // with the transmission switch on, the GLASS kernels start or stop being launched
+	c->mat_merged_valid = false;                                                  // the next MIXED launch uploads the new colours
+	return MIRT_OK;                                                               // (closure_plan() reads the material count and the closure table: neither changed)
+}
+
+extern "C" int mirt_debug_lights(mirt_ctx* c, int32_t* ids_out, float* sphere_rows_out, float* emit_rows_out, size_t capacity_lights, uint32_t info[4]) {
+	if (!c) return MIRT_ERR_ARG;
+	if (!info) return fail(c, MIRT_ERR_ARG, "debug_lights: info is NULL");
+	if (!c->have_scene) return fail(c, MIRT_ERR_STATE, "there are no light tables: mirt_set_scene first");
+	const SceneDev& s = c->scene;
+	const size_t n = s.n_lights;
+	info[0] = s.n_lights; info[1] = kLightBlock; info[2] = kLightScanPass; info[3] = 0u;
+	if (!ids_out && !sphere_rows_out && !emit_rows_out) return MIRT_OK;
+	if (capacity_lights < n) return fail(c, MIRT_ERR_ARG, "debug_lights: room for %zu lights, the scene has %zu", capacity_lights, n);
+	if (n == 0) return MIRT_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	std::vector<float4> emit(n);
+	HIP_TRY(c, hipMemcpy(emit.data(), s.light_emit, n * sizeof(float4), hipMemcpyDeviceToHost));   // the device copies next event estimation samples
+	if (emit_rows_out) std::memcpy(emit_rows_out, emit.data(), n * sizeof(float4));
+	if (ids_out) for (size_t l = 0; l < n; l++) std::memcpy(&ids_out[l], &emit[l].w, 4);
+	if (sphere_rows_out) HIP_TRY(c, hipMemcpy(sphere_rows_out, s.light_sphere, n * sizeof(float4), hipMemcpyDeviceToHost));
 	return MIRT_OK;
 }

@@ -210,6 +210,15 @@ int mirt_group_update_spheres(mirt_group* g, uint32_t n, const uint32_t* bvh_ind
 	if (g->full && n) FULL_TRY(g, "mirt_drop_history", mirt_drop_history(g->full));   // its history shows the surfaces where they were
 	return MIRT_OK;
 }
+// Every member, and the material rows on the gather context too: mirt_group_set_scene handed it the material tables (its first-hit AOV colour
+// and its glass check read them) but no geometry, so there is no sphere of its to re-assign.
+int mirt_group_update_materials(mirt_group* g, uint32_t n_rows, const uint32_t* material_index, const mirt_material* rows,
+                                uint32_t n_assign, const uint32_t* bvh_index, const uint32_t* geometry_index, const int32_t* material_ID) {
+	if (!g) return MIRT_ERR_ARG;
+	FOR_MEMBERS(g, "mirt_update_materials", mirt_update_materials(ctx, n_rows, material_index, rows, n_assign, bvh_index, geometry_index, material_ID));
+	if (g->full && n_rows) FULL_TRY(g, "mirt_update_materials", mirt_update_materials(g->full, n_rows, material_index, rows, 0, nullptr, nullptr, nullptr));
+	return MIRT_OK;
+}
 GROUP_FORWARD(set_material_closures,(mirt_group* g, const uint8_t* closure, uint32_t n), (ctx, closure, n))   // the gather context too: its first-hit AOV colour follows the table
 int mirt_group_pick_focus(mirt_group* g, uint32_t x, uint32_t y, float* distance, float* depth) {
 	if (!g) return MIRT_ERR_ARG;

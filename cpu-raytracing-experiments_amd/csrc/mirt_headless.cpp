@@ -213,6 +213,10 @@ int main(int argc, char** argv) {
 	std::string env_out;
 	struct SphereMove { uint32_t index; float step[3]; };                       // --move-sphere: geometry-order sphere `index` moves by `step` between frames
 	std::vector<SphereMove> moves;
+	struct EmissionEdit { uint32_t material; float rgb[3]; };                   // --set-emission: material `material` emits `rgb` from the second frame on
+	struct MaterialAssign { uint32_t index; uint32_t material; };               // --sphere-material: geometry-order sphere `index` takes material `material`
+	std::vector<EmissionEdit> emissions;
+	std::vector<MaterialAssign> assigns;
 	if (argc == 4 && std::string(argv[1]) == "--convert-hdr") {
 		// file-format check without a GPU: read a picture like stbi_loadf does (top-down) and store it again like Image::Store does (which
 		// flips, so the rows are handed over bottom-up): the output decodes to the same texels
@@ -235,7 +239,7 @@ int main(int argc, char** argv) {
 			          "              [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm] [--denoise [ITERATIONS]] [--denoise-plain-out FILE]\n"
 			          "              [--temporal [MAX_RATIO]] [--orbit DEG]\n"
 		          "              [--sun-sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY]] [--env-size WxH] [--env-out env.hdr] [--sun-orbit DEG]\n"
-		          "              [--move-sphere I:DX,DY,DZ]...\n"
+		          "              [--move-sphere I:DX,DY,DZ]... [--set-emission M:R,G,B]... [--sphere-material I:M]...\n"
 			          "mirt_headless --convert-hdr in.hdr out.hdr\n"
 			          "  --sky-sampling  the environment map (--hdri, --ambient) is one more light of next event estimation, drawn by importance (mirt_set_sky_sampling)\n"
 			          "  --ggx-pdf  the GGX closure's visible-normal pdf in the MIS weights: emitters and the sampled sky are weighed two ways on GGX surfaces (mirt_set_ggx_pdf)\n"
@@ -249,6 +253,8 @@ int main(int argc, char** argv) {
 		          "  --env-out FILE  the environment map the kernels read, written as Radiance .hdr (mirt_read_environment)\n"
 		          "  --sun-orbit DEG with --sun-sky and --frames: after every frame of `buckets` accumulations the sun turns DEG degrees about the vertical and the accumulator is reset (mirt_set_sun_sky alone: no mirt_set_scene)\n"
 		          "  --move-sphere I:DX,DY,DZ  with --frames: before every frame after the first, geometry-order sphere I moves by (DX, DY, DZ) and the accumulator is reset; the tree in place is refitted on the GPU (mirt_update_spheres alone: no mirt_set_scene).  Repeatable\n"
+		          "  --set-emission M:R,G,B  with --frames: before every frame after the first, material M emits (R, G, B) and the accumulator is reset; the material tables are replaced and the light list is regenerated on the GPU (mirt_update_materials alone: no mirt_set_scene).  Repeatable\n"
+		          "  --sphere-material I:M  likewise: geometry-order sphere I takes material M (mirt_update_materials).  Repeatable\n"
 		          "  --closures LIST the closure of material 0, 1, ...: 0 Lambertian, 1 GGX; materials beyond the list take --brdf (mirt_set_material_closures)");
 			return 0;
 		}
@@ -291,6 +297,8 @@ int main(int argc, char** argv) {
 		else if (a == "--env-size") { if (std::sscanf(next(), "%ux%u", &env_w, &env_h) != 2) return 2; }
 		else if (a == "--env-out") env_out = next();
 		else if (a == "--move-sphere") { SphereMove m{}; if (std::sscanf(next(), "%u:%f,%f,%f", &m.index, &m.step[0], &m.step[1], &m.step[2]) != 4) return 2; moves.push_back(m); }
+		else if (a == "--set-emission") { EmissionEdit e{}; if (std::sscanf(next(), "%u:%f,%f,%f", &e.material, &e.rgb[0], &e.rgb[1], &e.rgb[2]) != 4) return 2; emissions.push_back(e); }
+		else if (a == "--sphere-material") { MaterialAssign m{}; if (std::sscanf(next(), "%u:%u", &m.index, &m.material) != 2) return 2; assigns.push_back(m); }
 		else if (a == "--sun-orbit") sun_orbit_deg = static_cast<float>(std::atof(next()));
 		else if (a == "--devices") { devices.clear(); for (const char* p = next(); *p;) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p == ',') p++; } if (devices.empty()) return 2; }
 		else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -374,13 +382,24 @@ int main(int argc, char** argv) {
 				if (frame + 1 < spp) { sun_azimuth += sun_orbit_deg; aim_sun(); renderer.ResetAccumulator(); }
 			}
 		}
-		else if (!moves.empty()) {
+		else if (!moves.empty() || !emissions.empty() || !assigns.empty()) {
 			// A drag: every frame is `buckets` accumulations; then the spheres move in both of the scene's arrays and UpdateSpheres hands those rows over
 			// alone — no RebuildAcceleration(), no SceneChanged(): the tree in place is refitted — and the accumulator is reset (Application.cpp:466-468,510).
 			std::vector<uint32_t> geometry_index, bvh_index;
 			for (const SphereMove& m : moves) {
 				if (m.index >= scene.geometry.size()) { std::fprintf(stderr, "--move-sphere %u: the scene has %zu spheres\n", m.index, scene.geometry.size()); return 2; }
 				geometry_index.push_back(m.index); bvh_index.push_back(renderer.BvhIndexOf(m.index));
+			}
+			// A material edit (Application.cpp:470-485): the emissions and the material ids are written into the scene's arrays and UpdateMaterials hands
+			// those rows and ids over alone; the light list is regenerated on the GPU.  The edit is absolute: applied again before every later frame.
+			std::vector<uint32_t> material_index, assign_geometry, assign_bvh;
+			for (const EmissionEdit& e : emissions) {
+				if (e.material >= scene.material.size()) { std::fprintf(stderr, "--set-emission %u: the scene has %zu materials\n", e.material, scene.material.size()); return 2; }
+				material_index.push_back(e.material);
+			}
+			for (const MaterialAssign& m : assigns) {
+				if (m.index >= scene.geometry.size() || m.material >= scene.material.size()) { std::fprintf(stderr, "--sphere-material %u:%u: the scene has %zu spheres and %zu materials\n", m.index, m.material, scene.geometry.size(), scene.material.size()); return 2; }
+				assign_geometry.push_back(m.index); assign_bvh.push_back(renderer.BvhIndexOf(m.index));
 			}
 			for (uint32_t frame = 0; frame < spp; frame++) {
 				renderer.Accumulate(policy.buckets);
@@ -391,7 +410,15 @@ int main(int argc, char** argv) {
 						for (int a = 0; a < 3; a++) g.position[a] += moves[k].step[a];
 						scene.acceleration_structure.prims[bvh_index[k]] = g;
 					}
-					renderer.UpdateSpheres(bvh_index, geometry_index);
+					if (!moves.empty()) renderer.UpdateSpheres(bvh_index, geometry_index);
+					if (!material_index.empty() || !assign_geometry.empty()) {
+						for (const EmissionEdit& e : emissions) for (int a = 0; a < 3; a++) scene.material[e.material].emission[a] = e.rgb[a];
+						for (size_t k = 0; k < assigns.size(); k++) {
+							scene.geometry[assign_geometry[k]].material_ID = static_cast<int32_t>(assigns[k].material);
+							scene.acceleration_structure.prims[assign_bvh[k]].material_ID = static_cast<int32_t>(assigns[k].material);
+						}
+						renderer.UpdateMaterials(material_index, assign_bvh, assign_geometry);
+					}
 					renderer.ResetAccumulator();
 				}
 			}

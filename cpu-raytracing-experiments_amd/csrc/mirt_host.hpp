@@ -235,6 +235,22 @@ public:
 		}
 		check(mirt_group_update_spheres(group_, static_cast<uint32_t>(geometry_index.size()), bvh_index.data(), geometry_index.data(), packet.data()), "mirt_group_update_spheres");
 	}
+	// SceneUpdate::Material (Application.cpp:470-485,509; mirt.h, mirt_update_materials): the caller has edited scene.material[material_index[i]] and
+	// written the new material_ID into scene.geometry[geometry_index[i]] and scene.acceleration_structure.prims[bvh_index[i]] (the same sphere;
+	// BvhIndexOf finds it BEFORE the id is written); those rows and ids alone are handed over, and the light list is regenerated on the GPU by the
+	// reference's rule — no RebuildAcceleration(), no SceneChanged().  scene.lighting_acceleration is the caller's: it is not read here and goes
+	// stale until the caller rebuilds it.  Materials are part of the estimand: ResetAccumulator() is the caller's to call; the temporal history is kept.
+	void UpdateMaterials(const std::vector<uint32_t>& material_index, const std::vector<uint32_t>& bvh_index = {}, const std::vector<uint32_t>& geometry_index = {}) {
+		if (bvh_index.size() != geometry_index.size()) throw std::runtime_error("UpdateMaterials: one bvh_index per geometry_index");
+		std::vector<Material> rows;
+		rows.reserve(material_index.size());
+		for (const uint32_t m : material_index) rows.push_back(scene.material.at(m));
+		std::vector<int32_t> ids;
+		ids.reserve(geometry_index.size());
+		for (const uint32_t g : geometry_index) ids.push_back(scene.geometry.at(g).material_ID);
+		check(mirt_group_update_materials(group_, static_cast<uint32_t>(rows.size()), material_index.data(), rows.data(),
+		                                  static_cast<uint32_t>(ids.size()), bvh_index.data(), geometry_index.data(), ids.data()), "mirt_group_update_materials");
+	}
 	// Where scene.geometry[g] sits in scene.acceleration_structure.prims: the first row with the same 32 bytes (identical rows are interchangeable).
 	uint32_t BvhIndexOf(uint32_t g) const {
 		const std::vector<Sphere>& prims = scene.acceleration_structure.prims;

@@ -5,7 +5,7 @@
 // monotone, so rounding the union equals the union of the rounded).  The three layouts of bvh_layout.hpp are one form here: a record of 2 or
 // 4 slots, each unused, a leaf (kLeafBit | prim) or a record index; whichever builder made them (host SAH, the caller's tree, the GPU LBVH).
 //
-//   k_update_spheres   scatters the edited {centre, radius_sq} packets into the sphere table.
+//   k_update_spheres   scatters the edited {centre, radius_sq} packets into the sphere table and into the geometry-order table.
 //   k_refit_links      once per tree: every record's parent and number of used slots, every prim's leaf record, read from the records.
 //   k_refit            one thread per prim climbs from its leaf record; the last of a record's used slots to arrive owns the record
 //                      (lbvh_build.hip k_inner_boxes' arrival counters), rewrites it whole and leaves its binary32 union for the parent.
@@ -63,11 +63,14 @@ template <int L> struct RefitRecord {
 	}
 };
 
-__global__ __launch_bounds__(kRefitBlock) void k_update_spheres(uint32_t n, const uint32_t* __restrict__ index, const float4* __restrict__ packet, float4* __restrict__ spheres, uint32_t n_spheres) {
+__global__ __launch_bounds__(kRefitBlock) void k_update_spheres(uint32_t n, const uint32_t* __restrict__ index, const uint32_t* __restrict__ geometry_index, const float4* __restrict__ packet,
+                                                                float4* __restrict__ spheres, float4* __restrict__ geometry_spheres, uint32_t n_spheres) {
 	const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
 	if (i >= n) return;
-	const uint32_t j = index[i];
-	if (j < n_spheres) spheres[j] = packet[i];                               // (validated on the host; distinct indices: no two threads share a row)
+	const uint32_t j = index[i], g = geometry_index[i];
+	const float4 p = packet[i];
+	if (j < n_spheres) spheres[j] = p;                                       // (validated on the host; distinct indices: no two threads share a row)
+	if (g < n_spheres) geometry_spheres[g] = p;                              // the same sphere in authoring order (light_list.hpp GeometryTable)
 }
 
 // One thread per record.  A validated tree points at every record but the first exactly once and holds every prim in exactly one leaf, so

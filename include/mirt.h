@@ -449,6 +449,36 @@ int mirt_update_spheres(mirt_ctx* ctx, uint32_t n,
                         const uint32_t* geometry_index,  /* index of the same sphere in the authoring-order geometry */
                         const float*    xyz_rsq);        /* n x {position.x, .y, .z, radius_sq} */
 
+/* ---- updating materials in place: the reference's SceneUpdate::Material without a rebuild ---------------------------------------------
+ * Every colour picker and slider of the reference's material panel (Application.cpp:477-485: albedo, F0, emission, transmission, roughness,
+ * IOR) and the sphere's material selector (:470, geometry[i].material_ID) raise SceneUpdate::Material, on which the reference rebuilds its
+ * LightingAcceleration (:347,509; Scene.hpp:12-16).  mirt_update_materials is that edit:  material material_index[i] := rows[i] (n_rows of
+ * them), and sphere bvh_index[i] of the BVH-order array — the same sphere as geometry_index[i] of the authoring-order geometry, as in
+ * mirt_update_spheres — takes material material_ID[i] (n_assign of them).  Either half may be empty.  THE NUMBER OF MATERIALS CANNOT CHANGE.
+ * After it, accumulator, frame, AOVs and the rays, shadow_rays, terminated and dropped counters equal, word for word, those of a fresh
+ * context given mirt_set_scene with the edited materials, the edited material_IDs in geometry and bvh_prims IN THE SAME ORDER, the same nodes,
+ * the same environment and lights = mirt_light_list(edited geometry, edited materials) — under every policy, both closures, a closure table,
+ * transmission, sky sampling, light RIS, the GGX pdf, the lens, frozen tiles, and in exact stream order.  THE LIGHT LIST IS ALWAYS REPLACED BY
+ * THE REFERENCE'S RULE, even if mirt_set_scene was handed another list: an edited emission or material_ID creates and removes lights, so the
+ * two per-light tables of next event estimation are regenerated on the device in geometry order (csrc/light_list.hpp: an ordered stream
+ * compaction over a geometry-order copy of the spheres that mirt_set_scene uploads and both updates keep current; whether a material emits
+ * is decided per material on the host by the expression of mirt_light_list, (e0 e0 + e1 e1) + e2 e2 > 0 in binary32), and n_lights moves —
+ * with it the Q12 MIS guard, the sky's light number under sky sampling and light RIS's candidate range.
+ * Materials are part of the estimand and the accumulator is NOT reset: the caller calls mirt_reset, as Application.cpp:510 does.  Deferred
+ * mirt_accumulate_async calls are launched first, under the old materials, and every stream is waited for.
+ * Not touched: the spheres' positions, the records, the refit links, the camera-ray candidate lists (they name spheres, not materials), the
+ * LDS plan, the environment and its sampling table, the closure table (mirt_set_material_closures).  KEPT: the temporal history — surfaces did
+ * not move; as with the environment and the shading switches the caller calls mirt_drop_history beside mirt_reset.
+ * Everything is checked BEFORE anything changes — a refused call leaves every word in place:  MIRT_ERR_STATE before mirt_set_scene;
+ * MIRT_ERR_ARG for a NULL array with a non-zero count, a material_index >= n_materials or one that occurs twice in one call, a bvh_index or
+ * geometry_index >= n_spheres or one that occurs twice in one call, a material_ID outside [0, n_materials), and, with mirt_set_transmission
+ * on, a RESULTING material table that breaks its rules (transmission in [0, 1], a finite IOR above 0 for a transmissive material).  Material
+ * values are otherwise not validated, as in mirt_set_scene.  Both counts 0: MIRT_OK, nothing done. */
+int mirt_update_materials(mirt_ctx* ctx,
+                          uint32_t n_rows,   const uint32_t* material_index, const mirt_material* rows,   /* material material_index[i] := rows[i] */
+                          uint32_t n_assign, const uint32_t* bvh_index, const uint32_t* geometry_index,   /* the same sphere in both orders */
+                                             const int32_t*  material_ID);                                /* ... takes this material */
+
 /* Renderer::Resize, Renderer.hpp:53-63: h_tiles = w/16, v_tiles = h/16 (truncating), allocates and zeroes
  * the accumulator, accumulations = 0.  Owns all tiles until mirt_set_tile_range says otherwise. */
 int mirt_resize(mirt_ctx* ctx, uint32_t width, uint32_t height);
@@ -803,6 +833,8 @@ int mirt_group_set_material_closures(mirt_group* group, const uint8_t* closure, 
 int mirt_group_set_environment(mirt_group* group, const float ambient_color[3], const float* hdri_rgba, uint32_t w, uint32_t h);   /* mirt_set_environment on every member (and the gather context) */
 int mirt_group_set_sun_sky(mirt_group* group, const mirt_sun_sky_params* params);   /* mirt_set_sun_sky on every member (and the gather context): each bakes its own map, the same words */
 int mirt_group_update_spheres(mirt_group* group, uint32_t n, const uint32_t* bvh_index, const uint32_t* geometry_index, const float* xyz_rsq);   /* mirt_update_spheres on every member (the gather context holds no geometry) */
+int mirt_group_update_materials(mirt_group* group, uint32_t n_rows, const uint32_t* material_index, const mirt_material* rows,
+                                uint32_t n_assign, const uint32_t* bvh_index, const uint32_t* geometry_index, const int32_t* material_ID);   /* mirt_update_materials on every member; the material rows on the gather context too (it holds the material tables, no geometry) */
 int mirt_group_pick_focus(mirt_group* group, uint32_t x, uint32_t y, float* distance, float* depth);   /* mirt_pick_focus on the first member */
 int mirt_group_set_policy(mirt_group* group, const mirt_policy* policy);
 int mirt_group_set_gloss_decay(mirt_group* group, const float* decay, uint32_t n);
@@ -904,6 +936,13 @@ int mirt_debug_tree(mirt_ctx* ctx, void* dst, size_t capacity_bytes, uint32_t in
  * dst == NULL: only `info` is filled.  `capacity` is in floats: MIRT_ERR_ARG when below info[3].  MIRT_ERR_STATE while there is no table
  * (the switch is off, or no scene has been set). */
 int mirt_debug_sky_table(mirt_ctx* ctx, float* dst, size_t capacity, uint32_t info[4]);
+/* Read-back of the two per-light tables next event estimation samples, copied from the device after the context's stream has been synchronised
+ * (as mirt_set_scene flattened the caller's list, or as mirt_update_materials regenerated them).  ids_out[l]: the geometry id of light l;
+ * sphere_rows_out: 4 floats per light {centre, radius_sq}; emit_rows_out: 4 floats per light {emission.rgb of its material, the bits of its id}.
+ * info[0] n_lights, info[1] spheres per workgroup of the compaction, info[2] workgroups one pass of its totals scan covers, info[3] 0.
+ * All three pointers NULL: only `info` is filled; any of them may be NULL.  MIRT_ERR_ARG when capacity_lights < n_lights; MIRT_ERR_STATE before
+ * mirt_set_scene. */
+int mirt_debug_lights(mirt_ctx* ctx, int32_t* ids_out, float* sphere_rows_out, float* emit_rows_out, size_t capacity_lights, uint32_t info[4]);
 /* Length histogram of the per-pixel candidate lists of the current scene / camera / size (policy.trace_primary_rays = 0 path):
  * hist[n] = local pixels whose bundle of camera rays can hit n spheres for n = 0..7, hist[8] = 8 or more (lists hold up to 31), hist[9] = pixels without a list (traced normally). */
 int mirt_debug_primary_lists(mirt_ctx* ctx, uint32_t hist[10]);
