@@ -196,7 +196,7 @@ struct mirt_ctx {
 	// launch-shape knobs for measurements (profiles/gpu_cycle.sh A/B runs), read from the environment at mirt_create: MIRT_TUNE_TRACE_WGS /
 	// MIRT_TUNE_SHADE_WGS = workgroups per CU, MIRT_TUNE_CHUNK = rays per work reservation, MIRT_TUNE_LEAF_BATCH = lanes at a leaf that
 	// trigger a leaf pass, MIRT_TUNE_REFILL_IDLE = idle lanes that trigger a refill.  They never change results.
-	uint32_t tune_trace_wgs = 2, tune_shade_wgs = 3, tune_chunk = kChunkMax, tune_leaf_batch = kLeafBatch, tune_refill_idle = kRefillIdle, tune_wide = 1;
+	uint32_t tune_trace_wgs = 2, tune_shade_wgs = 0, tune_chunk = kChunkMax, tune_leaf_batch = kLeafBatch, tune_refill_idle = kRefillIdle, tune_wide = 1;
 	uint32_t tune_denoise_staged = kAtrousStagedMaxStep;   // MIRT_TUNE_DENOISE_STAGED: largest a-trous step whose pass stages its block in LDS (0: none do; profiles/denoise.txt)
 	bool debug_poison_contrib = false;   // MIRT_DEBUG_POISON_CONTRIB=1: fill every contribution buffer with a NaN pattern before each batch (tests: every word is written)
 	// profiling
@@ -624,8 +624,9 @@ using ShadeKernel = decltype(&k_shade<false, false>);
 template <uint32_t BITS>
 constexpr ShadeKernel shade_entry() {
 	constexpr ShadeForm f = ShadeForm::from_bits(BITS);
-	if constexpr (f.valid()) return &k_shade<f.first, f.ggx, f.lens, f.sparse, f.ris, f.glass, f.sky, f.mixed, f.pdf>;
-	else return nullptr;
+	if constexpr (!f.valid()) return nullptr;
+	else if constexpr (shade_waves(f) == 8u) return &k_shade<ShadeWaves8, f.first, f.ggx, f.lens, f.sparse, f.ris, f.glass, f.sky, f.mixed, f.pdf>;
+	else return &k_shade<f.first, f.ggx, f.lens, f.sparse, f.ris, f.glass, f.sky, f.mixed, f.pdf>;
 }
 template <uint32_t... BITS>
 ShadeKernel shade_kernel(ShadeForm f, std::integer_sequence<uint32_t, BITS...>) {
@@ -786,8 +787,15 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 	uint32_t* fat_lists = sl.fat.as<uint32_t>();
 	const SceneDev sc = trace_scene(c);
 	const bool count = c->policy.count_traffic != 0;
-	const uint32_t sgrid = static_cast<uint32_t>(std::min<uint64_t>((total + kShadeBlock - 1) / kShadeBlock, static_cast<uint64_t>(c->n_cu) * c->tune_shade_wgs));     // three 512-thread workgroups are resident per CU (k_shade: ~80 VGPRs); more only adds passes
-	{	// k_shade<FIRST> hands out (512-pixel chunk, group of accumulations) pieces: at least ~8 per workgroup, so that a small image loads the grid evenly
+	// k_shade's grid: as many 512-thread workgroups as are resident per CU at the launched form's waves per SIMD (shade_waves: three at 6, four at 8); more only adds passes
+	// (tune_shade_wgs, MIRT_TUNE_SHADE_WGS: one figure for every form instead, for sweeps; 0 = follow the form)
+	const ClosurePlan plan = closure_plan(c);
+	const auto shade_grid = [&](const ShadeForm& f) {
+		const uint32_t wgs = c->tune_shade_wgs ? c->tune_shade_wgs : shade_waves(f) * 4u / (kShadeBlock / 64u);
+		return static_cast<uint32_t>(std::min<uint64_t>((total + kShadeBlock - 1) / kShadeBlock, static_cast<uint64_t>(c->n_cu) * wgs));
+	};
+	{	// k_shade<FIRST> hands out (512-pixel chunk, group of accumulations) pieces: at least ~8 per workgroup of bounce 0's grid, so that a small image loads the grid evenly
+		const uint32_t sgrid = shade_grid(shade_form(c, fp, plan, 0, lens, sparse));
 		const uint64_t n_chunks = (static_cast<uint64_t>(fp.n_pix) + kShadeBlock - 1) / kShadeBlock;
 		const uint64_t want = (8ull * sgrid + n_chunks - 1) / n_chunks;
 		fp.first_groups = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(want, 1), batch_n));
@@ -865,12 +873,11 @@ int launch_batch(mirt_ctx* c, uint32_t batch_n) {
 			{ Bracket t(c, MIRT_K_SHADE, st);
 			  // policy.brdf = 1 (#define BRDF 1): Closure<GGX> with this bounce's gloss decay, passed by value
 			  const float decay = bounce < c->gloss_decay.size() ? c->gloss_decay[bounce] : 0.0f;
-			  const ClosurePlan plan = closure_plan(c);
 			  const ShadeForm form = shade_form(c, fp, plan, bounce, lens, sparse);
 			  const auto shade = shade_kernel(form);
 			  if (!shade) return fail(c, MIRT_ERR_ARG, "no shade kernel for the form first %d ggx %d lens %d sparse %d ris %d glass %d sky %d mixed %d pdf %d",
 			                          form.first, form.ggx, form.lens, form.sparse, form.ris, form.glass, form.sky, form.mixed, form.pdf);
-			  hipLaunchKernelGGL(shade, dim3(sgrid), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
+			  hipLaunchKernelGGL(shade, dim3(shade_grid(form)), dim3(kShadeBlock), 0, st, sc, fp, in, sl.hit, out, sl.shadow_buf, bounce,
 			                     bc.stream_queue(bounce), bc.stream_queue(bounce + 1), bc.shadow_queue(bounce), contrib, ctr, mat_ggx, decay, c->lens, form.ris ? c->light_ris : 0u, tile_frozen,
 			                     form.sky ? c->sky : SkyTable{}, plan.mask, form.pdf ? sl.pdf_plane[bounce & 1u] : nullptr, form.pdf ? sl.pdf_plane[(bounce & 1u) ^ 1u] : nullptr); }
 		}

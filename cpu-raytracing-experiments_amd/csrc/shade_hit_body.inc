@@ -1,7 +1,7 @@
 // The per-hit shading, Renderer.hpp:169-404: closest-hit shader, next event estimation, emissive MIS, the closure sample and the Russian
 // roulette for one ray that hit `hrec.prim` at `hrec.tfar`.  ONE text, included as statements (not a function: see DESIGN.md,
 // "One per-hit shading text") by its two users in kernels.hpp:
-//   * k_shade, phase 2 — held to the oracle bit for bit by tests/test_gpu_parity.py, test_ggx_gpu.py, test_lens_gpu.py,
+//   * k_shade, phase 2 (shade_kernel_body.inc, the body of both of its overloads) — held to the oracle bit for bit by tests/test_gpu_parity.py, test_ggx_gpu.py, test_lens_gpu.py,
 //     test_radiance_in_contrib.py and test_definitions_gpu.py;
 //   * stream_shade_hit (k_tile_stream, exact stream order) — held by tests/test_exact_stream_order.py.
 // The names are k_shade's.  The including scope provides
