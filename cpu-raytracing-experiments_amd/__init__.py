@@ -175,6 +175,9 @@ def load_library():
         "mirt_render_temporal": [P, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), vp, vp, C.POINTER(TemporalStats)],
         "mirt_drop_history": [P],
         "mirt_history_info": [P, C.POINTER(u32), C.POINTER(C.c_uint64)],
+        "mirt_id_map": [P, vp, vp],
+        "mirt_set_sphere_motion": [P, u32], "mirt_get_sphere_motion": [P, C.POINTER(u32)],
+        "mirt_set_motion_geometry": [P, P],
         "mirt_noise":[P, f, vp, vp, vp, C.POINTER(NoiseStats)],
         "mirt_noise_quantile": [vp, C.c_double, C.POINTER(f)],
         "mirt_accumulate_until": [P, C.POINTER(StopRule), C.POINTER(NoiseStats), C.POINTER(u32)],
@@ -243,6 +246,8 @@ def load_library():
         "mirt_group_render_temporal": [G, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), vp, vp, C.POINTER(TemporalStats)],
         "mirt_group_drop_history": [G],
         "mirt_group_history_info": [G, C.POINTER(u32), C.POINTER(C.c_uint64)],
+        "mirt_group_set_sphere_motion": [G, u32],
+        "mirt_group_id_map": [G, vp, vp],
         "mirt_group_noise": [G, f, vp, vp, vp, C.POINTER(NoiseStats)],
         "mirt_group_accumulate_until": [G, C.POINTER(StopRule), C.POINTER(NoiseStats), C.POINTER(u32)],
         "mirt_group_freeze_tiles": [G, vp, C.c_size_t],
@@ -315,6 +320,18 @@ def geometry_to_bvh_order(geometry: np.ndarray, prims: np.ndarray) -> np.ndarray
     perm = np.empty(len(g), dtype=np.uint32)
     perm[og] = op
     return perm
+
+
+def id_map_to_geometry_order(prim: np.ndarray, bvh_of_geometry: np.ndarray) -> np.ndarray:
+    """An id map in BVH order (mirt_id_map) -> the same map in authoring order: bvh_of_geometry[g] is where geometry-order sphere g sits in the
+    BVH-order array (geometry_to_bvh_order), so pixel value b becomes the g with bvh_of_geometry[g] == b; -1 (a miss) stays -1.  Pure numpy."""
+    perm = np.asarray(bvh_of_geometry, dtype=np.int64).reshape(-1)
+    inverse = np.full(len(perm) + 1, -1, dtype=np.int32)                 # the last row answers -1
+    inverse[perm] = np.arange(len(perm), dtype=np.int32)
+    prim = np.asarray(prim, dtype=np.int32)
+    if prim.size and (prim.min() < -1 or prim.max() >= len(perm)):
+        raise ValueError(f"id map holds ids outside -1 .. {len(perm) - 1}")
+    return inverse[prim]
 
 
 def _aov_image(height: int, width: int, which: int, out):
@@ -605,7 +622,7 @@ class _Binding:
         """The reference's SceneUpdate::Geometry for spheres that keep their place (mirt_update_spheres): geometry-order spheres `indices` (what an
         editor holds) take `position` [n, 3] and `radius_sq` [n]; None keeps each sphere's current value.  The traversal tree keeps its topology
         and gets new boxes on the GPU: no rebuild, no re-upload; the BVH order stays the one handed over.  Geometry is part of the estimand and
-        the accumulator is NOT reset: call ResetAccumulator().  The temporal history is dropped.  self.geometry and self.prims are edited in
+        the accumulator is NOT reset: call ResetAccumulator().  The temporal history is dropped unless set_history_motion() is on.  self.geometry and self.prims are edited in
         step; the scene object is not written: UpdateScene() hands its own geometry over again.  (A group: on every member.)"""
         idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
         n_spheres = len(self.geometry)
@@ -833,8 +850,33 @@ class _Binding:
         """Forget the history of render_temporal() (mirt_drop_history); the next call starts from the frame's own samples."""
         self._call("drop_history")
 
+    def set_history_motion(self, on: bool = True):
+        """True: update_spheres() keeps the temporal history: it carries the id map and the sphere table it was taken under, and render_temporal()
+        carries a moved sphere's pixels back to where the sphere was; a tap is taken only where the history shows the same sphere
+        (mirt_set_sphere_motion).  False (the default): update_spheres() drops the history.  Any change drops it.  (A group: on every member.)"""
+        self._call("set_sphere_motion", int(bool(on)))
+
+    def history_motion(self) -> bool:
+        """What set_history_motion left (a group: its members', which all hold the same)."""
+        v = C.c_uint32(0)
+        self._get("sphere_motion", C.byref(v))
+        return bool(v.value)
+
+    def id_map(self, order: str = "bvh"):
+        """(prim, distance), each (height, width): per pixel of the whole image the sphere the un-jittered pinhole ray through the pixel centre
+        meets first, -1 for none, and how far away, inf on a miss (mirt_id_map): pick_focus() for every pixel in one launch.  order="bvh": ids into
+        self.prims, what hit.primID refers to; order="geometry": ids into self.geometry, what update_spheres() takes (translated on the host).
+        Changes no state.  (A group: on the context render_temporal() resolves on.)"""
+        if order not in ("bvh", "geometry"):
+            raise ValueError(f"order must be 'bvh' or 'geometry', not {order!r}")
+        prim = np.full((self.height, self.width), -1, dtype=np.int32)
+        dist = np.zeros((self.height, self.width), dtype=np.float32)
+        if prim.size:
+            self._call("id_map", _ptr(prim), _ptr(dist))
+        return (prim if order == "bvh" else id_map_to_geometry_order(prim, self._bvh_of_geometry)), dist
+
     def history_info(self) -> dict:
-        """{"valid": a history is held, "bytes": device bytes of its three images} (mirt_history_info)."""
+        """{"valid": a history is held, "bytes": device bytes of its images} (mirt_history_info)."""
         valid, nbytes = C.c_uint32(0), C.c_uint64(0)
         self._call("history_info", C.byref(valid), C.byref(nbytes))
         return {"valid": bool(valid.value), "bytes": int(nbytes.value)}

@@ -11,6 +11,7 @@
 #include "kernels.hpp"
 #include "denoise.hpp"
 #include "temporal.hpp"
+#include "id_map.hpp"
 #include "sun_sky.hpp"
 #include "refit.hpp"
 #include "light_list.hpp"
@@ -171,6 +172,14 @@ struct mirt_ctx {
 	CameraParams th_cam{};
 	uint32_t th_demodulate = 0, th_width = 0, th_height = 0;
 	float th_albedo_floor = 0.0f;
+	// mirt_set_sphere_motion(1): the history also carries the id map of the call that wrote it (th_id; th_id_cur: this call's, renamed with update = 1 as
+	// the guides are) and the sphere table it was taken under (th_snap, copied when a call with update = 1 finds the table changed since the last copy:
+	// spheres_gen of the geometry context counts its mirt_update_spheres calls).  id_out / id_words: mirt_id_map's two planes and k_id_map's counter words.
+	uint32_t history_motion = 0;
+	DeviceBuffer th_id, th_id_cur, th_snap, id_out, id_words;
+	bool th_snap_valid = false;
+	uint64_t th_snap_gen = 0, spheres_gen = 0;
+	mirt_ctx* motion_geometry = nullptr;   // mirt_set_motion_geometry: the context whose scene the id map and the sphere tables are read from (NULL: this one)
 	std::vector<PipeSlot> slots;     // batches in flight (policy.streams)
 	uint64_t planned_for = 0;        // local pixel count batch_mem_cap was planned for (0 = plan again)
 	uint32_t batch_mem_cap = 256;     // accumulations per batch the device memory allows (lowered by ensure_streams when the plan does not fit)
@@ -521,8 +530,8 @@ bool lens_on(const mirt_ctx* c) { return c->lens.aperture > 0.0f; }
 TileMap tile_map(const mirt_ctx* c) { return TileMap{ c->first_tile, c->run_tiles, c->stride_tiles, c->h_tiles, c->width }; }
 // The history of mirt_render_temporal goes (mirt.h "history lifetime").  The caller has made the context's device the current one.
 void drop_history(mirt_ctx* c) {
-	for (DeviceBuffer* b : { &c->th_x, &c->th_g, &c->th_n, &c->th_len }) b->release();
-	c->th_valid = false;
+	for (DeviceBuffer* b : { &c->th_x, &c->th_g, &c->th_n, &c->th_len, &c->th_id, &c->th_id_cur, &c->th_snap }) b->release();
+	c->th_valid = false; c->th_snap_valid = false;
 }
 void set_tile_map(mirt_ctx* c, const TileMap& m, uint32_t n_tiles) { c->first_tile = m.first_tile; c->run_tiles = m.run_tiles; c->stride_tiles = m.stride_tiles; c->n_tiles = n_tiles; }
 
@@ -1134,6 +1143,7 @@ int plan_trace_lds(mirt_ctx* c) {
 	for (int k = 0; k < 2 * kPrimaryForms * 2; k++)                               // every (count, primary, lens) that exists
 		if (const auto f = trace_kernel(k & 1, (k >> 1) % kPrimaryForms, k >= 2 * kPrimaryForms)) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
 	for (const auto f : kPrimaryCand) HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+	HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_id_map), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
 	return MIRT_OK;
 }
 
@@ -1190,6 +1200,21 @@ int debug_trace(mirt_ctx* c, const char* who, size_t n, const float* p_xyz, cons
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
 	if (e == hipSuccess) e = hipMemcpy(result, res.ptr, result_bytes, hipMemcpyDeviceToHost);
 	if (e != hipSuccess) return fail(c, MIRT_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+	return MIRT_OK;
+}
+
+// k_id_map (id_map.hpp) over the whole image of `c`, on c's stream, through the scene, the traversal settings and the camera of `gs` (c itself, or
+// the geometry context of mirt_set_motion_geometry: same device).  Either plane may be NULL.  The caller has made the device current.
+int launch_id_map(mirt_ctx* c, const mirt_ctx* gs, int32_t* prim_dev, float* dist_dev) {
+	const uint64_t n = static_cast<uint64_t>(c->width) * c->height;
+	if (n == 0) return MIRT_OK;
+	if (n >= (1ull << 31)) return fail(c, MIRT_ERR_ARG, "id map: %u x %u pixels do not fit a 31-bit pixel index", c->width, c->height);
+	HIP_TRY(c, c->id_words.ensure(2 * sizeof(uint32_t)));
+	HIP_TRY(c, hipMemsetAsync(c->id_words.ptr, 0, 2 * sizeof(uint32_t), c->stream));
+	const IdMapDev p{ gs->camera, c->width, static_cast<uint32_t>(n), 1.0f / static_cast<float>(c->width) };
+	{ Bracket t(c, MIRT_K_RESOLVE);
+	  hipLaunchKernelGGL(k_id_map, dim3(trace_grid(gs, n)), dim3(kTraceBlock), trace_lds(gs), c->stream, trace_scene(gs), p, prim_dev, dist_dev, c->id_words.as<uint32_t>()); }
+	HIP_TRY(c, hipGetLastError());
 	return MIRT_OK;
 }
 
@@ -1289,7 +1314,7 @@ int mirt_destroy(mirt_ctx* c) {
 	                         &c->mat_ggx, &c->mat_glass, &c->mat_merged, &c->hdri, &c->refit_links, &c->refit_edits, &c->geo_sphere, &c->geo_mat, &c->light_scan, &c->sky_table, &c->accumulator, &c->aov, &c->framebuffer, &c->counters, &c->gloss_decay_dev,
 	                         &c->cand, &c->cand_listed, &c->cand_words, &c->noise_rec, &c->noise_hist, &c->noise_above,
 	                         &c->dn_cv[0], &c->dn_cv[1], &c->dn_gd, &c->dn_mu, &c->tile_frozen, &c->active_list, &c->tile_counts,
-	                         &c->th_x, &c->th_g, &c->th_n, &c->th_len, &c->th_stats };
+	                         &c->th_x, &c->th_g, &c->th_n, &c->th_len, &c->th_stats, &c->th_id, &c->th_id_cur, &c->th_snap, &c->id_out, &c->id_words };
 	for (DeviceBuffer* b : bufs) b->release();
 	if (c->frame_host) (void)hipHostFree(c->frame_host);
 	if (c->cand_built) (void)hipEventDestroy(c->cand_built);
@@ -1508,6 +1533,7 @@ int mirt_resize(mirt_ctx* c, uint32_t width, uint32_t height) {
 	c->cand_valid = false;                                                             // other pixels
 	for (DeviceBuffer* b : { &c->dn_cv[0], &c->dn_cv[1], &c->dn_gd, &c->dn_mu }) b->release();   // mirt_render_atrous allocates them again at the new size
 	drop_history(c);                                                                   // another image
+	c->id_out.release();
 	c->h_tiles = width / MIRT_TILE_ROOT; c->v_tiles = height / MIRT_TILE_ROOT;          // Renderer.hpp:59-60
 	set_tile_map(c, TileMap::of_range(0u, c->h_tiles, width), c->h_tiles * c->v_tiles);
 	HIP_TRY(c, c->framebuffer.ensure(std::max<size_t>(static_cast<size_t>(width) * height, 1) * sizeof(float4)));
@@ -1711,6 +1737,15 @@ int mirt_atrous_defaults(mirt_denoise_params* out) {
 
 } // extern "C"
 namespace {
+const mirt_ctx* motion_geometry_of(const mirt_ctx* c) { return c->motion_geometry ? c->motion_geometry : c; }
+// The geometry context of a call that needs the id map: a scene, on this device, showing this camera (the group keeps all three in step).
+int check_motion_geometry(mirt_ctx* c, const mirt_ctx* gs) {
+	if (gs == c) return MIRT_OK;
+	if (!gs->have_scene || !gs->have_camera) return fail(c, MIRT_ERR_STATE, "history motion: the geometry context has no scene or no camera");
+	if (gs->device != c->device) return fail(c, MIRT_ERR_STATE, "history motion: the geometry context is on device %d, this one on device %d", gs->device, c->device);
+	if (std::memcmp(&gs->camera, &c->camera, sizeof(CameraParams)) != 0) return fail(c, MIRT_ERR_STATE, "history motion: the geometry context shows another camera");
+	return MIRT_OK;
+}
 bool unit_orient(const CameraParams& cam) {      // the condition the camera-ray candidate lists put on view.orient (launch_batch)
 	const float qn = cam.orient[0] * cam.orient[0] + cam.orient[1] * cam.orient[1] + cam.orient[2] * cam.orient[2] + cam.orient[3] * cam.orient[3];
 	return std::fabs(qn - 1.0f) < 1e-4f;
@@ -1742,6 +1777,9 @@ int filtered_resolve(mirt_ctx* c, const mirt_denoise_params* p, const mirt_tempo
 	if (issued == 0 || (issued % k) != 0) return MIRT_NOT_READY;                                    // as mirt_render
 	{ const int fr = flush_and_wait(c); if (fr) return fr; }
 	if (c->n_tiles == 0) return MIRT_OK;
+	// mirt_set_sphere_motion: where the id map and the sphere tables come from (this context, or the one mirt_set_motion_geometry named)
+	const mirt_ctx* gs = motion_geometry_of(c);
+	if (tp && c->history_motion && (r = check_motion_geometry(c, gs))) return r;
 	const float scale = c->camera.exposure / static_cast<float>(c->accumulations / k);              // Renderer.hpp:439, as mirt_render
 	const uint32_t n_pix = c->n_tiles * kTileSize;
 	const size_t image_bytes = static_cast<size_t>(c->width) * c->height * sizeof(float4);
@@ -1773,11 +1811,27 @@ int filtered_resolve(mirt_ctx* c, const mirt_denoise_params* p, const mirt_tempo
 		           unit_orient(c->camera) && unit_orient(c->th_cam)) ? 1u : 0u;
 		td.identity = std::memcmp(&c->camera, &c->th_cam, sizeof(CameraParams)) == 0 ? 1u : 0u;
 		if (!td.take) td.prev = c->camera;
-		{ Bracket t(c, MIRT_K_RESOLVE);
-		  hipLaunchKernelGGL(k_reproject, dim3(c->h_tiles, c->v_tiles), dim3(kAtrousBlock * kAtrousBlock), 0, c->stream, c->dn_cv[0].as<float4>(), c->dn_gd.as<float4>(),
-		                     c->th_x.as<float4>(), c->th_g.as<float4>(), c->th_n.as<float>(), c->dn_cv[1].as<float4>(), c->th_len.as<float>(), c->th_stats.as<unsigned long long>(),
-		                     c->width, c->h_tiles * kAtrousBlock, c->v_tiles * kAtrousBlock, counts, c->accumulations, td); }
+		if (c->history_motion) {
+			// the id map of this camera first, then the MOTION instantiation: the pixel's sphere, the table now and the table the history was taken under
+			const size_t id_bytes = static_cast<size_t>(c->width) * c->height * sizeof(int32_t);
+			HIP_TRY(c, c->th_id_cur.ensure(id_bytes));
+			if (tp->update) { HIP_TRY(c, c->th_id.ensure(id_bytes)); HIP_TRY(c, c->th_snap.ensure(std::max<size_t>(gs->scene.n_spheres, 1) * sizeof(float4))); }
+			if ((r = launch_id_map(c, gs, c->th_id_cur.as<int32_t>(), nullptr))) return r;
+			const MotionDev<true> mo{ c->th_id_cur.as<int32_t>(), c->th_id.as<int32_t>(), gs->scene.spheres, c->th_snap.as<float4>() };
+			Bracket t(c, MIRT_K_RESOLVE);
+			hipLaunchKernelGGL(k_reproject<true>, dim3(c->h_tiles, c->v_tiles), dim3(kAtrousBlock * kAtrousBlock), 0, c->stream, c->dn_cv[0].as<float4>(), c->dn_gd.as<float4>(),
+			                   c->th_x.as<float4>(), c->th_g.as<float4>(), c->th_n.as<float>(), c->dn_cv[1].as<float4>(), c->th_len.as<float>(), c->th_stats.as<unsigned long long>(),
+			                   c->width, c->h_tiles * kAtrousBlock, c->v_tiles * kAtrousBlock, counts, c->accumulations, td, mo);
+		} else {
+			Bracket t(c, MIRT_K_RESOLVE);
+			hipLaunchKernelGGL(k_reproject<false>, dim3(c->h_tiles, c->v_tiles), dim3(kAtrousBlock * kAtrousBlock), 0, c->stream, c->dn_cv[0].as<float4>(), c->dn_gd.as<float4>(),
+			                   c->th_x.as<float4>(), c->th_g.as<float4>(), c->th_n.as<float>(), c->dn_cv[1].as<float4>(), c->th_len.as<float>(), c->th_stats.as<unsigned long long>(),
+			                   c->width, c->h_tiles * kAtrousBlock, c->v_tiles * kAtrousBlock, counts, c->accumulations, td, MotionDev<false>{});
+		}
 		HIP_TRY(c, hipGetLastError());
+		// the snapshot follows the table once the kernel has read the old one (stream order); skipped while no mirt_update_spheres came since the last copy
+		if (c->history_motion && tp->update && gs->scene.n_spheres && (!c->th_snap_valid || c->th_snap_gen != gs->spheres_gen))
+			HIP_TRY(c, hipMemcpyAsync(c->th_snap.ptr, gs->scene.spheres, static_cast<size_t>(gs->scene.n_spheres) * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
 		src = c->dn_cv[1].as<float4>(); dst = c->dn_cv[0].as<float4>();
 		spare = tp->update ? c->th_x.as<float4>() : c->dn_cv[1].as<float4>();
 	}
@@ -1819,6 +1873,7 @@ int filtered_resolve(mirt_ctx* c, const mirt_denoise_params* p, const mirt_tempo
 		if (tp->update) {                                                             // step 4: the blend, this call's guides and the lengths ARE the history now; the old ones are scratch
 			std::swap(c->th_x, c->dn_cv[1]); std::swap(c->th_g, c->dn_gd); std::swap(c->th_n, c->th_len);
 			c->th_cam = c->camera; c->th_demodulate = p->demodulate; c->th_albedo_floor = p->albedo_floor; c->th_width = c->width; c->th_height = c->height;
+			if (c->history_motion) { std::swap(c->th_id, c->th_id_cur); c->th_snap_valid = true; c->th_snap_gen = gs->spheres_gen; }   // this call's id map IS the history's id plane now
 			c->th_valid = true;
 		}
 	}
@@ -1849,7 +1904,46 @@ int mirt_drop_history(mirt_ctx* c) {
 int mirt_history_info(const mirt_ctx* c, uint32_t* valid, uint64_t* bytes) {
 	if (!c || !valid || !bytes) return MIRT_ERR_ARG;
 	*valid = c->th_valid ? 1u : 0u;
-	*bytes = static_cast<uint64_t>(c->th_x.bytes) + c->th_g.bytes + c->th_n.bytes;
+	*bytes = static_cast<uint64_t>(c->th_x.bytes) + c->th_g.bytes + c->th_n.bytes + c->th_id.bytes + c->th_snap.bytes;   // the last two: mirt_set_sphere_motion(1) only
+	return MIRT_OK;
+}
+
+// ---- first-hit id map, and the history kept across sphere moves (id_map.hpp, temporal.hpp; the definitions are in mirt.h) -------------
+int mirt_id_map(mirt_ctx* c, int32_t* prim_out, float* distance_out) {
+	int r = check_ready(c); if (r) return r;
+	const mirt_ctx* gs = motion_geometry_of(c);
+	if ((r = check_motion_geometry(c, gs))) return r;
+	const size_t n = static_cast<size_t>(c->width) * c->height;
+	if (n == 0 || (!prim_out && !distance_out)) return MIRT_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, c->id_out.ensure(n * (sizeof(int32_t) + sizeof(float))));
+	int32_t* prim_dev = c->id_out.as<int32_t>();
+	float* dist_dev = reinterpret_cast<float*>(prim_dev + n);
+	if ((r = launch_id_map(c, gs, prim_out ? prim_dev : nullptr, distance_out ? dist_dev : nullptr))) return r;   // reads the scene and the camera, writes two planes of its own
+	if (prim_out) HIP_TRY(c, hipMemcpyAsync(prim_out, prim_dev, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+	if (distance_out) HIP_TRY(c, hipMemcpyAsync(distance_out, dist_dev, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	return MIRT_OK;
+}
+int mirt_set_sphere_motion(mirt_ctx* c, uint32_t on) {
+	if (!c) return MIRT_ERR_ARG;
+	if (on > 1u) return fail(c, MIRT_ERR_ARG, "history motion %u is neither 0 nor 1", on);
+	if (on == c->history_motion) return MIRT_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	drop_history(c);                                                                   // a history without an id plane cannot be taken with one, and the reverse
+	c->history_motion = on;
+	return MIRT_OK;
+}
+int mirt_get_sphere_motion(const mirt_ctx* c, uint32_t* on) { if (!c || !on) return MIRT_ERR_ARG; *on = c->history_motion; return MIRT_OK; }
+int mirt_set_motion_geometry(mirt_ctx* c, mirt_ctx* geometry) {
+	if (!c) return MIRT_ERR_ARG;
+	geometry = geometry == c ? nullptr : geometry;
+	if (geometry == c->motion_geometry) return MIRT_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	drop_history(c);                                                                   // ids of another scene
+	c->motion_geometry = geometry;
 	return MIRT_OK;
 }
 
@@ -2300,7 +2394,8 @@ extern "C" int mirt_update_spheres(mirt_ctx* c, uint32_t n, const uint32_t* bvh_
 	HIP_TRY(c, hipStreamSynchronize(c->stream));                                  // host buffers are copied, never retained
 	c->refit_links_valid = true;
 	c->cand_valid = false;                                                        // the camera-ray lists name the spheres of the old positions
-	drop_history(c);                                                              // surfaces moved: nothing of the old view may be reprojected onto them
+	c->spheres_gen++;                                                             // a history kept under mirt_set_sphere_motion compares its snapshot with the table as it is now
+	if (!c->history_motion) drop_history(c);                                      // surfaces moved: nothing of the old view may be reprojected onto them
 	return MIRT_OK;
 }
 

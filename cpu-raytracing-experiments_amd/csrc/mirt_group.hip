@@ -153,6 +153,7 @@ int mirt_group_create(const int* devices, int n, mirt_group** out) {
 	if (n > 1) {
 		const int rc = mirt_create(devices[0], &g->full);
 		if (rc != MIRT_OK) return bail(rc, std::string("mirt_create(gather context): ") + mirt_last_error(nullptr));
+		(void)mirt_set_motion_geometry(g->full, g->members[0]);                   // the gather context holds no geometry: its id map (mirt_set_sphere_motion) is made from the first member's, on the same device
 		g->staging.assign(n, nullptr); g->staging_bytes.assign(n, 0);
 		g->aov_staging.assign(n, nullptr); g->aov_staging_bytes.assign(n, 0);
 		if (g->distinct) {
@@ -207,7 +208,9 @@ GROUP_FORWARD(set_sun_sky, (mirt_group* g, const mirt_sun_sky_params* params), (
 int mirt_group_update_spheres(mirt_group* g, uint32_t n, const uint32_t* bvh_index, const uint32_t* geometry_index, const float* xyz_rsq) {
 	if (!g) return MIRT_ERR_ARG;
 	FOR_MEMBERS(g, "mirt_update_spheres", mirt_update_spheres(ctx, n, bvh_index, geometry_index, xyz_rsq));
-	if (g->full && n) FULL_TRY(g, "mirt_drop_history", mirt_drop_history(g->full));   // its history shows the surfaces where they were
+	uint32_t motion = 0;
+	if (g->full) (void)mirt_get_sphere_motion(g->full, &motion);
+	if (g->full && n && !motion) FULL_TRY(g, "mirt_drop_history", mirt_drop_history(g->full));   // its history shows the surfaces where they were (mirt_set_sphere_motion: it follows them)
 	return MIRT_OK;
 }
 // Every member, and the material rows on the gather context too: mirt_group_set_scene handed it the material tables (its first-hit AOV colour
@@ -607,6 +610,13 @@ int mirt_group_drop_history(mirt_group* g) {
 int mirt_group_history_info(const mirt_group* g, uint32_t* valid, uint64_t* bytes) {
 	if (!g) return MIRT_ERR_ARG;
 	return mirt_history_info(g->full ? g->full : g->members[0], valid, bytes);
+}
+GROUP_FORWARD(set_sphere_motion, (mirt_group* g, uint32_t on), (ctx, on))
+int mirt_group_id_map(mirt_group* g, int32_t* prim_out, float* distance_out) {
+	if (!g) return MIRT_ERR_ARG;
+	mirt_ctx* ctx = g->full ? g->full : g->members[0];                               // the context mirt_group_render_temporal resolves on
+	const int rc = mirt_id_map(ctx, prim_out, distance_out);
+	return rc < 0 ? gfail(g, rc, "mirt_id_map: %s", mirt_last_error(ctx)) : rc;
 }
 
 } // extern "C"

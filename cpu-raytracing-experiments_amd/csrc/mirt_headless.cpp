@@ -8,7 +8,7 @@
 //                 [--hdri env.hdr] [--ambient A] [--brdf 0|1] [--gloss-decay a,b,...] [--exact-stream-order] [--out frame.hdr|frame.pfm] [--aov PREFIX] [--light-ris M] [--transmission] [--sky-sampling] [--closures 0,1,1,...] [--ggx-pdf]
 //                 [--f-number F] [--focus-distance D] [--unit-mm U] [--focus-pixel X,Y]
 //                 [--until-noise T] [--noise-quantile Q] [--noise-floor F] [--check-every N] [--max-accumulations M] [--noise-out map.pfm]
-//                 [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm] [--denoise [ITERATIONS]] [--denoise-plain-out plain.hdr|plain.pfm] [--temporal [MAX_RATIO]] [--orbit DEG]
+//                 [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm] [--denoise [ITERATIONS]] [--denoise-plain-out plain.hdr|plain.pfm] [--temporal [MAX_RATIO]] [--orbit DEG] [--history-motion] [--ids-out ids.pfm]
 // --denoise writes to --out the variance-guided à-trous denoised resolve of the last frame (mirt_render_atrous with its defaults; ITERATIONS, 0 .. 8,
 // replaces their pass count) instead of the plain one; it implies the first-hit AOVs, which guide it.  --denoise-plain-out writes the plain frame beside it.
 // --adaptive T renders with per-tile adaptive sampling (mirt_accumulate_adaptive): like --until-noise, but every 16 x 16 tile stops taking samples
@@ -205,7 +205,8 @@ int main(int argc, char** argv) {
 	std::string counts_out, plain_out;
 	bool denoise = false;
 	int denoise_iterations = -1;                                               // -1: the default
-	bool temporal = false;
+	bool temporal = false, history_motion = false;
+	std::string ids_out;
 	float temporal_ratio = -1.0f, orbit_deg = 0.0f;                            // -1: the default max_ratio
 	bool sun_sky = false;
 	float sun_elevation = 0.0f, sun_azimuth = 0.0f, sun_turbidity = -1.0f, sun_orbit_deg = 0.0f;   // turbidity -1: the default
@@ -237,7 +238,7 @@ int main(int argc, char** argv) {
 			          "              [--f-number F] [--focus-distance D] [--unit-mm U] [--focus-pixel X,Y]\n"
 			          "              [--until-noise T] [--noise-quantile Q] [--noise-floor F] [--check-every N] [--max-accumulations M] [--noise-out map.pfm]\n"
 			          "              [--adaptive T] [--min-accumulations N] [--counts-out counts.pfm] [--denoise [ITERATIONS]] [--denoise-plain-out FILE]\n"
-			          "              [--temporal [MAX_RATIO]] [--orbit DEG]\n"
+			          "              [--temporal [MAX_RATIO]] [--orbit DEG] [--history-motion] [--ids-out ids.pfm]\n"
 		          "              [--sun-sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY]] [--env-size WxH] [--env-out env.hdr] [--sun-orbit DEG]\n"
 		          "              [--move-sphere I:DX,DY,DZ]... [--set-emission M:R,G,B]... [--sphere-material I:M]...\n"
 			          "mirt_headless --convert-hdr in.hdr out.hdr\n"
@@ -247,7 +248,9 @@ int main(int argc, char** argv) {
 			          "  --transmission  materials that carry a transmission render as glass (mirt_set_transmission)\n"
 			          "  --denoise [N]   --out receives the variance-guided a-trous denoised resolve (N passes, default 5; implies the first-hit AOVs); --denoise-plain-out FILE: the plain frame\n"
 			          "  --temporal [R]  every frame of --frames is `buckets` accumulations resolved through the temporal history (mirt_render_temporal; R = max_ratio, default 7; implies the AOVs); --out receives the last one\n"
-			          "  --orbit DEG     after every frame the camera yaws DEG degrees about the scene's centre and the accumulator is reset, as the reference does on a camera move (frames of `buckets` accumulations)\n"
+			          "  --history-motion  with --temporal and --move-sphere: the history survives the moves; it carries the id map and the sphere table it was taken under (mirt_set_sphere_motion)\n"
+		          "  --ids-out FILE  the first-hit id map of the last view as a one-channel .pfm: the BVH-order sphere every pixel centre shows, as a float, -1 for none (mirt_id_map)\n"
+		          "  --orbit DEG     after every frame the camera yaws DEG degrees about the scene's centre and the accumulator is reset, as the reference does on a camera move (frames of `buckets` accumulations)\n"
 			          "  --sun-sky E,A[,T]  the environment map is a Preetham sky of turbidity T with a sun disc at elevation E and azimuth A degrees, baked on the GPU under --ambient (mirt_set_sun_sky)\n"
 		          "  --env-size WxH  texels of the map --sun-sky bakes (mirt_sun_sky_defaults: 1025x513)\n"
 		          "  --env-out FILE  the environment map the kernels read, written as Radiance .hdr (mirt_read_environment)\n"
@@ -292,6 +295,8 @@ int main(int argc, char** argv) {
 		else if (a == "--denoise") { denoise = true; if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoise_iterations = std::atoi(argv[++i]); }
 		else if (a == "--denoise-plain-out") { plain_out = next(); denoise = true; }
 		else if (a == "--temporal") { temporal = true; if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) temporal_ratio = static_cast<float>(std::atof(argv[++i])); }
+		else if (a == "--history-motion") history_motion = true;
+		else if (a == "--ids-out") ids_out = next();
 		else if (a == "--orbit") orbit_deg = static_cast<float>(std::atof(next()));
 		else if (a == "--sun-sky") { const int got = std::sscanf(next(), "%f,%f,%f", &sun_elevation, &sun_azimuth, &sun_turbidity); if (got < 2) return 2; sun_sky = true; }
 		else if (a == "--env-size") { if (std::sscanf(next(), "%ux%u", &env_w, &env_h) != 2) return 2; }
@@ -327,6 +332,7 @@ int main(int argc, char** argv) {
 		renderer.SetSkySampling(sky_sampling);
 		renderer.SetGgxPdf(ggx_pdf);
 		renderer.SetMaterialClosures(closures);
+		if (history_motion) renderer.SetHistoryMotion(true);
 		// pad the viewport to the tile requirement like UIRender does (Application.cpp:365-372)
 		const uint32_t t = static_cast<uint32_t>(Renderer::RequiredTiling());
 		w = (w + t - 1) & ~(t - 1); h = (h + t - 1) & ~(t - 1);
@@ -401,9 +407,21 @@ int main(int argc, char** argv) {
 				if (m.index >= scene.geometry.size() || m.material >= scene.material.size()) { std::fprintf(stderr, "--sphere-material %u:%u: the scene has %zu spheres and %zu materials\n", m.index, m.material, scene.geometry.size(), scene.material.size()); return 2; }
 				assign_geometry.push_back(m.index); assign_bvh.push_back(renderer.BvhIndexOf(m.index));
 			}
+			// --temporal resolves each frame through the history; UpdateSpheres drops it unless --history-motion lets it follow the spheres.
+			mirt_denoise_params dp = Renderer::DenoiseDefaults();
+			if (denoise_iterations >= 0) dp.iterations = static_cast<uint32_t>(denoise_iterations);
+			mirt_temporal_params tp = Renderer::TemporalDefaults();
+			if (temporal_ratio >= 0.0f) tp.max_ratio = temporal_ratio;
 			for (uint32_t frame = 0; frame < spp; frame++) {
 				renderer.Accumulate(policy.buckets);
 				if (renderer.Render()) { have_frame = true; frames_due += (frames_due.empty() ? "" : ", ") + std::to_string(frame + 1); }
+				if (temporal) {
+					mirt_temporal_stats st{};
+					temporal_frame = renderer.RenderTemporal(dp, tp, nullptr, &st);
+					std::printf("{\"temporal\": {\"frame\": %u, \"reprojected\": %llu, \"no_history\": %llu, \"outside\": %llu, \"rejected\": %llu, \"unusable\": %llu, \"frame_fnv1a\": \"%016llx\"}}\n", frame + 1,
+					            (unsigned long long)st.reprojected, (unsigned long long)st.no_history, (unsigned long long)st.outside, (unsigned long long)st.rejected, (unsigned long long)st.unusable,
+					            (unsigned long long)fnv1a(temporal_frame));
+				}
 				if (frame + 1 < spp) {
 					for (size_t k = 0; k < moves.size(); k++) {
 						Sphere& g = scene.geometry[geometry_index[k]];
@@ -496,6 +514,12 @@ int main(int argc, char** argv) {
 			if (!plain_out.empty() && !write_frame(plain_out, renderer.GetFrame())) return 1;
 		}
 		else if (!out.empty() && have_frame && !write_frame(out, renderer.GetFrame())) return 1;
+		if (!ids_out.empty()) {
+			const Renderer::IdMapResult ids = renderer.IdMap();
+			std::vector<float> img(ids.prim.size());
+			for (size_t k = 0; k < img.size(); k++) img[k] = static_cast<float>(ids.prim[k]);
+			if (!write_pfm_planes(ids_out, img, w, h, 1)) { std::fprintf(stderr, "cannot write %s\n", ids_out.c_str()); return 1; }
+		}
 		if (!env_out.empty()) {
 			const Renderer::Environment env = renderer.ReadEnvironment();
 			std::printf("{\"environment\": {\"width\": %u, \"height\": %u, \"baked\": %s, \"fnv1a\": \"%016llx\"}}\n", env.width, env.height, env.baked ? "true" : "false", (unsigned long long)fnv1a(env.rgba));

@@ -326,6 +326,19 @@ public:
 		return img;
 	}
 	void DropHistory() { check(mirt_group_drop_history(group_), "mirt_group_drop_history"); }
+	// Keeping the history across sphere moves (mirt.h, mirt_set_sphere_motion): on, UpdateSpheres() no longer drops the history; it carries the id
+	// map and the sphere table it was taken under, and RenderTemporal() carries a moved sphere's pixels back to where the sphere was.  A change drops it.
+	void SetHistoryMotion(bool on) { check(mirt_group_set_sphere_motion(group_, on ? 1u : 0u), "mirt_group_set_sphere_motion"); }
+	// First-hit id map (mirt.h, mirt_id_map): per pixel of the whole image, row 0 = y 0, the BVH-order sphere (scene.acceleration_structure.prims) the
+	// un-jittered pinhole ray through the pixel centre meets first, -1 for none, and its distance (INFINITY on a miss).  Changes no state.
+	struct IdMapResult { std::vector<int32_t> prim; std::vector<float> distance; };
+	IdMapResult IdMap() {
+		IdMapResult m;
+		m.prim.assign(static_cast<size_t>(width) * height, -1);
+		m.distance.assign(static_cast<size_t>(width) * height, 0.0f);
+		check(mirt_group_id_map(group_, m.prim.data(), m.distance.data()), "mirt_group_id_map");
+		return m;
+	}
 	// Per-pixel noise estimate from the buckets (mirt.h, mirt_noise): the relative standard error of the mean of the bucket means, read from the
 	// members' own slabs without a gather.  ready = false (and nothing filled) while accumulations is 0 or not a multiple of `buckets`.
 	struct NoiseResult {

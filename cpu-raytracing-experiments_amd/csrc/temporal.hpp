@@ -33,11 +33,25 @@ struct TemporalDev {
 constexpr uint32_t kTemporalStatSlots = 256u, kTemporalStatPitch = 16u;      // copies of the five counts; 64-bit words between two copies (128 B)
 enum : uint32_t { kTemporalReprojected = 0u, kTemporalNoHistory = 1u, kTemporalOutside = 2u, kTemporalRejected = 3u, kTemporalUnusable = 4u, kTemporalClasses = 5u };
 
+// OBJECT MOTION (mirt_set_sphere_motion, mirt.h "keeping the history across sphere moves"): what k_reproject<true> reads besides — this call's id map
+// (id_map.hpp: the BVH-order sphere of every pixel centre, -1 for none), the id plane of the call that wrote the history, the sphere table now
+// and the snapshot of it the history was taken under.  A pixel whose sphere's four words differ between the two tables is carried back to where
+// that point of the sphere was (translation and uniform scale: normals keep), and a tap is taken only where the history shows the same sphere.
+// The plain instantiation is handed an empty struct as its last argument and names none of this: its device code is what it was before the template.
+template <bool MOTION> struct MotionDev {};
+template <> struct MotionDev<true> {
+	const int32_t* __restrict__ ids;       // this call's id map
+	const int32_t* __restrict__ hist_ids;  // the history's
+	const float4* __restrict__ now;        // {pos, radius_sq} by BVH-order id, now ...
+	const float4* __restrict__ then;       // ... and when the history was written
+};
+
 // The image is w_img x h_img pixels (whole tiles) in rows of `width` pixels; the grid is its 16 x 16 blocks, block (bx, by) = tile by * gridDim.x + bx.
+template <bool MOTION>
 __global__ __launch_bounds__(kAtrousBlock * kAtrousBlock) void k_reproject(const float4* __restrict__ cv_in, const float4* __restrict__ gd, const float4* __restrict__ hx,
                                                                             const float4* __restrict__ hg, const float* __restrict__ hn, float4* __restrict__ cv_out,
                                                                             float* __restrict__ len_out, unsigned long long* __restrict__ stats, uint32_t width, uint32_t w_img,
-                                                                            uint32_t h_img, const uint32_t* __restrict__ tile_counts, uint32_t count_all, TemporalDev p) {
+                                                                            uint32_t h_img, const uint32_t* __restrict__ tile_counts, uint32_t count_all, TemporalDev p, MotionDev<MOTION> mo) {
 	const uint32_t lx = threadIdx.x & 15u, ly = threadIdx.x >> 4;
 	const int32_t px = static_cast<int32_t>(blockIdx.x * kAtrousBlock + lx), py = static_cast<int32_t>(blockIdx.y * kAtrousBlock + ly);
 	const size_t at = static_cast<size_t>(py) * width + static_cast<size_t>(px);
@@ -50,9 +64,28 @@ __global__ __launch_bounds__(kAtrousBlock * kAtrousBlock) void k_reproject(const
 	else if (p.take && !(g.x == 0.0f && g.y == 0.0f && g.z == 0.0f)) {
 		float fx = static_cast<float>(px), fy = static_cast<float>(py), zr = g.w;            // the identity map
 		bool behind = false;
-		if (!p.identity) {
+		// MOTION: the pixel's sphere and whether it moved (any of its four words differs between the two tables); a moved sphere has no identity map
+		int32_t id = -1;
+		bool moved = false, scaled = false;
+		float4 now{}, then{};
+		if constexpr (MOTION) {
+			id = mo.ids[at];
+			if (id >= 0) {
+				now = mo.now[id]; then = mo.then[id];
+				scaled = __float_as_uint(now.w) != __float_as_uint(then.w);
+				moved = scaled || __float_as_uint(now.x) != __float_as_uint(then.x) || __float_as_uint(now.y) != __float_as_uint(then.y) || __float_as_uint(now.z) != __float_as_uint(then.z);
+			}
+		}
+		if (!p.identity || (MOTION && moved)) {
 			const f3 d = camera_ray_dir(p.cam, px, py, 0.5f, 0.5f);
-			const f3 P{ p.cam.pos[0] + d.x * g.w, p.cam.pos[1] + d.y * g.w, p.cam.pos[2] + d.z * g.w };
+			f3 P{ p.cam.pos[0] + d.x * g.w, p.cam.pos[1] + d.y * g.w, p.cam.pos[2] + d.z * g.w };
+			if constexpr (MOTION) {
+				if (moved) {                                                                      // P' = c0 + (P - c) * s: the same point of the sphere, where it was
+					f3 o{ P.x - now.x, P.y - now.y, P.z - now.z };
+					if (scaled && now.w > 0.0f) { const float s = __builtin_sqrtf(then.w / now.w); o.x = o.x * s; o.y = o.y * s; o.z = o.z * s; }
+					P.x = then.x + o.x; P.y = then.y + o.y; P.z = then.z + o.z;
+				}
+			}
 			const f3 r{ P.x - p.prev.pos[0], P.y - p.prev.pos[1], P.z - p.prev.pos[2] };
 			zr = __builtin_sqrtf(dot3(r, r));
 			const float conj[4] = { -p.prev.orient[0], -p.prev.orient[1], -p.prev.orient[2], p.prev.orient[3] };
@@ -84,6 +117,7 @@ __global__ __launch_bounds__(kAtrousBlock * kAtrousBlock) void k_reproject(const
 					if (!dn_usable(tg) || !(tn > 0.0f)) continue;
 					if (!(__builtin_fabsf(tg.w - zr) <= p.depth_tol * zr)) continue;
 					if (!((g.x * tg.x + g.y * tg.y) + g.z * tg.z >= p.normal_min)) continue;
+					if constexpr (MOTION) { if (mo.hist_ids[q] != id) continue; }                 // another surface stood there: what a moving ball uncovers is `rejected`
 					const float4 tc = hx[q];
 					const float b = (i ? wx : ux) * (j ? wy : uy);
 					B = first ? b : B + b;

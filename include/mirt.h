@@ -436,7 +436,7 @@ int mirt_set_sun_sky(mirt_ctx* ctx, const mirt_sun_sky_params* params);
  * place (k_refit, csrc/refit.hpp) — leaf boxes as mirt_set_scene makes them, r = sqrt(radius_sq), pad = 2^-18 (max|c| + r), one binary32 step
  * outward; inner boxes their unions; binary16 planes rounded outward — which are the words a fresh build over that topology writes; the row of
  * every light whose geometry id is edited is replaced; the camera-ray candidate lists are rebuilt by the next batch; the temporal history is
- * dropped (surfaces moved).  Not touched: the material tables, the environment and its sampling table, the LDS plan, the switches.
+ * dropped (surfaces moved) unless mirt_set_sphere_motion is on, which follows the move instead.  Not touched: the material tables, the environment and its sampling table, the LDS plan, the switches.
  * How far a tree may be refitted before mirt_set_scene pays is the caller's decision (DESIGN.md section 4 has measurements).
  * Everything is checked BEFORE anything changes — a refused call leaves every word in place:  MIRT_ERR_STATE before mirt_set_scene;
  * MIRT_ERR_ARG for a NULL array with n > 0, an index >= n_spheres, a bvh_index or a geometry_index that occurs twice in one call, a value that
@@ -796,6 +796,54 @@ int mirt_drop_history(mirt_ctx* ctx);
 /* *valid = 1 while a history is held; *bytes = device bytes of its three images (0 after a drop). */
 int mirt_history_info(const mirt_ctx* ctx, uint32_t* valid, uint64_t* bytes);
 
+/* ---- first-hit id map: which sphere every pixel shows ---------------------------------------------------------------------------------
+ * What mirt_pick_focus finds for one pixel, for every pixel of the image in one launch: pixel (x, y), row-major in rows of `width`, over the
+ * WHOLE image whether this context owns the tile or not, holds the first hit of the un-jittered pinhole ray through the pixel centre (samples
+ * 0.5, 0.5; lens or no lens) through the closest-hit traversal the context is configured with (every record layout, f32 records, use_bvh = 0,
+ * reference_tree = 1; a non-unit quaternion is fine: the ray walks the tree).  prim_out: the BVH-order id hit.primID refers to, -1 on a miss;
+ * distance_out: tfar, INFINITY on a miss.  Either may be NULL.  The editor's "active sphere" (Application.cpp:466-470) is prim_out at the
+ * cursor; mirt_update_spheres takes that id as its bvh_index.
+ * It changes no state: accumulator, AOVs, counters (`rays` included), lists and history are untouched; it only reads, so exact stream order
+ * allows it.  MIRT_ERR_STATE before a scene, a camera or a size is set; MIRT_ERR_ARG when width * height does not fit 31 bits.  Kernel time
+ * is booked under MIRT_K_RESOLVE.  Kernel: csrc/id_map.hpp (k_id_map): the rays are generated from the pixel index, no ray stream exists. */
+int mirt_id_map(mirt_ctx* ctx, int32_t* prim_out /* w*h or NULL */, float* distance_out /* w*h or NULL */);
+
+/* ---- keeping the history across sphere moves: id map and object motion -----------------------------------------------------------------
+ * mirt_update_spheres drops the temporal history, because the reprojection above follows the camera only.  With this switch on (0 / 1, default
+ * 0; another value: MIRT_ERR_ARG) it does not (it still does everything else it does), and the history carries two more things: an ID PLANE
+ * (int32 per pixel: the id map of the call that wrote it) and a SPHERE SNAPSHOT (the BVH-order {pos, radius_sq} table the history was taken
+ * under, 16 B per sphere, as it already carries the camera).  mirt_render_temporal then computes the id map of the current camera before step 2
+ * and runs k_reproject<MOTION>.  With the switch off every kernel launched and every word written is what it is without this section.
+ * THE DEFINITION, in the style of step 2 above: binary32, one rounding per operation, unfused, in this order.  For a usable centre p with guides
+ * (N, z) and i = the id map's word at p, P = cam.pos + d * z as in step 2.  now = spheres[i] = (c, rsq), then = snapshot[i] = (c0, rsq0).  The
+ * sphere has MOVED when i >= 0 and any of the four words differ.
+ *   not moved, or i < 0:  the map is step 2's, the identity exception included.
+ *   moved:                o = P - c per component;  if the rsq words differ and rsq > 0: s = sqrtf(rsq0 / rsq), o = o * s per component;
+ *                         P' = c0 + o per component;  r = P' - prev.pos, and on from there exactly as step 2 (z', q, behind, t, fx, fy).  The
+ *                         identity exception does NOT apply.  Normals need no map: translation and uniform scale keep them.
+ *   taps:                 a tap is taken when step 2's four conditions hold AND the history's id word at the tap equals i (-1 equals -1).  What
+ *                         a moving ball uncovers therefore does not inherit the ball's history: those pixels are `rejected`.  THIS HOLDS WITH
+ *                         THE SWITCH ON EVEN WHEN NOTHING MOVED: a tap across a silhouette, which depth and normal might let pass, is not taken.
+ *   history write:        with update = 1 the call's id map becomes the history's id plane (renamed as the guides are, not copied), and the
+ *                         snapshot is copied device to device from the table in place — skipped while no mirt_update_spheres came since the last
+ *                         copy.  Several updates between two history writes need no bookkeeping: the map compares "now" with "then".  A call with
+ *                         update = 0 changes neither.
+ * Blend, filter and the statistics classes are unchanged.  Consequence (b) stands (the id plane of the history equals the id map there).
+ * Consequence (c) becomes: the result is a function of the two slabs, the counts, the two cameras, the history, the id map and the two sphere
+ * tables alone.
+ * LIFETIME.  Any change of the switch drops the history; mirt_set_scene drops it as ever (ids change meaning); mirt_update_materials keeps it.
+ * mirt_history_info counts the id plane and the snapshot (4 B per pixel + 16 B per sphere) only while the switch is on.  One more int32 image of
+ * scratch holds a call's own id map.  The preconditions of mirt_render_temporal are unchanged.
+ * mirt_set_motion_geometry: the context whose scene, traversal settings and sphere table the id map of `ctx` is made from (NULL or ctx itself:
+ * its own, the default).  For a context that resolves frames it does not trace — the gather context of a group holds no geometry — ; both must
+ * be on one device and show the same camera words when a call needs the map (MIRT_ERR_STATE otherwise).  `geometry` must outlive `ctx` or be
+ * reset first.  A change drops the history.
+ * Kernel: csrc/temporal.hpp (k_reproject<true>); binary32 numpy twin: tests/temporal_motion_twin.py; float64 definition:
+ * tests/temporal_motion_definitions.py. */
+int mirt_set_sphere_motion(mirt_ctx* ctx, uint32_t on);
+int mirt_get_sphere_motion(const mirt_ctx* ctx, uint32_t* on);
+int mirt_set_motion_geometry(mirt_ctx* ctx, mirt_ctx* geometry);
+
 int mirt_get_counters(mirt_ctx* ctx, mirt_counters* out);
 int mirt_get_kernel_times(mirt_ctx* ctx, mirt_kernel_times* out, int reset);
 /* HIP stream the context launches on (hipStream_t), for callers that time with their own events. */
@@ -872,6 +920,10 @@ int mirt_group_render_temporal(mirt_group* group, const mirt_denoise_params* par
                                float* rgba_host, float* history_len, mirt_temporal_stats* stats);
 int mirt_group_drop_history(mirt_group* group);
 int mirt_group_history_info(const mirt_group* group, uint32_t* valid, uint64_t* bytes);
+/* mirt_set_sphere_motion on every member and the gather context (whose id map is made from the first member's geometry: mirt_set_motion_geometry);
+ * mirt_group_update_spheres then keeps the history.  mirt_group_id_map: mirt_id_map on the context mirt_group_render_temporal resolves on. */
+int mirt_group_set_sphere_motion(mirt_group* group, uint32_t on);
+int mirt_group_id_map(mirt_group* group, int32_t* prim_out, float* distance_out);
 /* mirt_noise / mirt_accumulate_until of the whole image.  NO gather: every member runs mirt_noise on its own slab; histograms and counts add
  * as integers, the maximum is exact, the members' tile records are un-interleaved on the host into LaunchIndex order (tile_out: 4 floats per
  * tile of the image), each member writes its own tiles of map_out, and the mean is the double sum over those records in LaunchIndex order.
