@@ -518,7 +518,10 @@ int mirt_load_accumulator(mirt_ctx* ctx, const float* src, int src_is_device, ui
 
 /* Renderer::Render, Renderer.hpp:436-478: median over buckets * exposure/(accumulations/buckets), ACES tonemap,
  * RGBA f32 row-major width*height (row 0 = y 0), A = 1.  Returns MIRT_NOT_READY and leaves rgba_host untouched
- * when accumulations % buckets != 0.  Only the context's own tiles are written. */
+ * when accumulations % buckets != 0.  Only the context's own tiles are written: pixels of other contexts' tiles, and the pixels no
+ * tile owns when width or height is no multiple of 16 (columns 16 (width / 16) .. width - 1, rows 16 (height / 16) .. height - 1), are
+ * left as the caller handed them.  That is the rule of every resolve below (mirt_render_aov, mirt_noise's map, mirt_render_atrous,
+ * mirt_render_temporal's frame and history_len, and their mirt_group_* namesakes); mirt_id_map alone covers all width x height pixels. */
 int mirt_render(mirt_ctx* ctx, float* rgba_host);
 
 /* ---- first-hit AOVs: depth, normal and albedo of the camera rays, summed beside the accumulator ---------------------
@@ -704,7 +707,8 @@ int mirt_accumulate_adaptive(mirt_ctx* ctx, const mirt_stop_rule* rule, uint32_t
  * finite, no NULL pointer: else MIRT_ERR_ARG.  MIRT_ERR_STATE while AOVs are off, with buckets < 2, and for a context that does not own every
  * tile of the image: a 5 x 5 stencil at step 16 reads 32 pixels into its neighbours' tiles, so a partial context is refused, not approximated
  * (a group resolves on its gather context).  Exact stream order has no AOVs, hence MIRT_ERR_STATE there too.  Then MIRT_NOT_READY, with rgba_host
- * untouched, under mirt_render's condition.  Launches anything deferred and waits for the GPU first; kernel time is booked under MIRT_K_RESOLVE.
+ * untouched, under mirt_render's condition.  Pixels outside "the image" of the definition (no tile owns them) are never read as taps and never
+ * written: rgba_host keeps there what the caller handed over.  Launches anything deferred and waits for the GPU first; kernel time is booked under MIRT_K_RESOLVE.
  * Scratch: four float4 images (x and v twice, the guides, the modulator), allocated by the first call, released by mirt_resize and mirt_destroy —
  * 4 x 268 MB at 4096 x 4096.  Kernels: csrc/denoise.hpp; binary32 numpy twin: tests/denoise_twin.py. */
 typedef struct mirt_denoise_params {
@@ -774,7 +778,8 @@ int mirt_render_atrous(mirt_ctx* ctx, const mirt_denoise_params* params, float* 
  * Errors and preconditions are exactly mirt_render_atrous's (arguments, then AOVs on, buckets >= 2, the whole image in one context, hence no exact
  * stream order, then MIRT_NOT_READY under mirt_render's condition, rgba_host untouched); in addition MIRT_ERR_ARG when max_ratio or depth_tol is
  * negative or not finite, normal_min is outside [-1, 1], update > 1, or temporal is NULL.  Kernel time is booked under MIRT_K_RESOLVE.
- * history_len (or NULL): width * height floats, row-major, `len` of every pixel of the image (pixels no tile covers are left untouched).
+ * history_len (or NULL): width * height floats, row-major, `len` of every pixel of the image (pixels no tile covers are left untouched, in
+ * history_len and in rgba_host alike; a point that projects onto such a pixel of the history is `outside`: the history's image is w x h too).
  * Kernel: csrc/temporal.hpp (k_reproject); binary32 numpy twin: tests/temporal_twin.py; float64 definition: tests/temporal_definitions.py. */
 typedef struct mirt_temporal_params {
 	float    max_ratio;     /* >= 0: history may weigh at most max_ratio x the pixel's own sample count; 0 = take no history */
@@ -900,7 +905,7 @@ int mirt_group_gather(mirt_group* group);
 int mirt_group_last_gather_ms(const mirt_group* group, double* ms);              /* device time of the last gather incl. un-interleave */
 int mirt_group_accumulator_floats(const mirt_group* group, size_t* n_floats);    /* of the whole image */
 int mirt_group_read_accumulator(mirt_group* group, float* host_dst);             /* whole image, [tile][bucket][r,g,b][256] in LaunchIndex order */
-int mirt_group_render(mirt_group* group, float* rgba_host);                      /* Renderer::Render of the whole frame; MIRT_NOT_READY as mirt_render */
+int mirt_group_render(mirt_group* group, float* rgba_host);                      /* Renderer::Render of the whole frame; MIRT_NOT_READY as mirt_render; pixels no tile owns are left as handed over, as by mirt_render */
 /* First-hit AOVs of the whole image.  mirt_group_gather moves the members' AOV slabs in the same exchange as their accumulator slabs
  * and un-interleaves them with the same tile-row mapping; the sums equal the single-context ones bit for bit.  Both branches of the
  * exchange carry them — device copies when one device is named several times, RCCL between distinct devices — but only the first

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 using namespace mirt;
@@ -56,9 +57,48 @@ static int check_copy(const TileMap& m, uint32_t n_tiles, uint32_t v_tiles, cons
 	return 0;
 }
 
+// An image of width x height pixels that is no whole number of tiles (70 x 40: 4 x 2 tiles, 6 columns and 8 rows that no tile owns): pixel_offset
+// of every pixel of every tile against a plain double loop over the image, and copy_owned_tiles into an exactly-sized width x height buffer, for the
+// whole image and for every interleaving of the tile rows by 1..3: every pixel of an owned tile is copied, the remainder and the others' tiles are not.
+static int check_ragged(uint32_t width, uint32_t height) {
+	const uint32_t h_tiles = width / 16u, v_tiles = height / 16u;
+	int bad = 0;
+	for (uint32_t stride = 1; stride <= 3; stride++)
+		for (uint32_t first_row = 0; first_row < stride; first_row++) {
+			const TileMap m = TileMap::of_rows(first_row, stride, h_tiles, width);
+			const uint32_t n_tiles = TileMap::tile_rows_owned(v_tiles, first_row, stride) * h_tiles;
+			std::vector<uint32_t> local_of(static_cast<size_t>(width) * height, UINT32_MAX);     // the double loop: which local tile owns pixel (x, y)
+			uint32_t local = 0;
+			for (uint32_t ty = first_row; ty < v_tiles; ty += stride)
+				for (uint32_t tx = 0; tx < h_tiles; tx++, local++)
+					for (uint32_t y = 16u * ty; y < 16u * ty + 16u; y++)
+						for (uint32_t x = 16u * tx; x < 16u * tx + 16u; x++) {
+							local_of[static_cast<size_t>(y) * width + x] = local;
+							const uint32_t ID = (y - 16u * ty) * 16u + (x - 16u * tx);
+							for (uint32_t ch : { 1u, 3u, 4u })
+								if (m.pixel_offset(local, ID, ch) != (static_cast<size_t>(y) * width + x) * ch) bad += fail("ragged pixel_offset", m, x, y);
+						}
+			if (local != n_tiles) bad += fail("ragged tile count", m, local, n_tiles);
+			for (uint32_t ch : { 1u, 3u, 4u }) {
+				const size_t n = static_cast<size_t>(width) * height * ch;
+				float* from = new float[n];
+				float* to = new float[n];
+				for (size_t i = 0; i < n; i++) { from[i] = static_cast<float>(i + 1); to[i] = -7.0f; }
+				copy_owned_tiles(m, n_tiles, ch, from, to);
+				for (size_t i = 0; i < n && !bad; i++)
+					if (to[i] != (local_of[i / ch] != UINT32_MAX ? from[i] : -7.0f)) bad += fail("ragged copy_owned_tiles", m, static_cast<uint32_t>((i / ch) % width), static_cast<uint32_t>((i / ch) / width));
+				delete[] from;
+				delete[] to;
+			}
+		}
+	if (!bad) std::printf("ragged %u %u ok\n", width, height);
+	return bad;
+}
+
 int main() {
 	int bad = 0;
 	size_t cases = 0;
+	for (const auto& size : { std::pair<uint32_t, uint32_t>{ 70u, 40u }, { 40u, 70u }, { 17u, 16u }, { 16u, 31u }, { 79u, 33u } }) { bad += check_ragged(size.first, size.second); cases++; }
 	for (uint32_t h_tiles = 1; h_tiles <= 5; h_tiles++)
 		for (uint32_t v_tiles = 0; v_tiles <= 7; v_tiles++)
 			for (uint32_t width : { 16u * h_tiles, 16u * h_tiles + 8u }) {

@@ -114,9 +114,10 @@ def render(acc, aov, counts, exposure, dparams, tparams, width, height, cam, his
     dp.update(dparams)
     tp = dict(DEFAULTS)
     tp.update(tparams)
-    ids = np.ascontiguousarray(ids, dtype=np.int32)
     spheres = np.array(spheres, dtype=f32).reshape(-1, 4)
     st = dt.prepare(acc, aov, counts, exposure, dp, width, height)
+    h_img, w_img = st["v"].shape                                                  # mirt_id_map covers width x height; the history's id plane is read over the tiled pixels
+    ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32)[:h_img, :w_img])
     n_img = dt.to_image(np.repeat(np.asarray(counts, dtype=np.uint32).reshape(-1, 1), 256, axis=1), width, height).astype(f32)
     st["x"], st["v"], length, cls = reproject_blend(st, n_img, cam, hist, dp, tp, ids, spheres)
     if int(tp["update"]):
