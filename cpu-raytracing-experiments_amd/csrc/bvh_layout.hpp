@@ -119,14 +119,14 @@ inline void split_multi_prim_leaves(std::vector<mirt_bvh_node>& nodes) {
 
 // binary16 is adequate for a child box unless a coordinate lies beyond +-60000 (amax: the largest magnitude), or it is a leaf box whose
 // smallest extent is under 8 quantisation steps (the box would grow by more than ~25 %).  Also asked for the sphere-derived leaf
-// boxes of a GPU-built tree (mirt_capi.hip), which never pass through build_half_records.
+// boxes of a GPU-built tree (mirt_launch.hip), which never pass through build_half_records.
 inline bool half_box_adequate(float amax, float min_extent, bool leaf) {
 	if (amax > 60000.0f) return false;
 	return !(leaf && min_extent < 8.0f * half_ulp_at(amax));
 }
 
 // 32-B half-precision records from the 64-B ones.  Returns false (and leaves `out` empty) when binary16 is not adequate for
-// some child box.  (With more than 32768 records or spheres the traversal stack keeps u32 entries, see mirt_capi.hip.)
+// some child box.  (With more than 32768 records or spheres the traversal stack keeps u32 entries, see mirt_launch.hip.)
 inline bool build_half_records(const std::vector<float>& recs, std::vector<uint32_t>& out) {
 	out.clear();
 	const size_t n = recs.size() / 16;

@@ -14,7 +14,7 @@
 // row-segment load per wave: read straight from global memory.  Both variants evaluate the same text, fetch() aside, so they give the same words
 // (which of them runs is a launch choice: profiles/denoise.txt).
 #pragma once
-#include "kernels.hpp"
+#include "resolve.hpp"
 
 #include <float.h>
 
@@ -22,8 +22,7 @@ namespace mirt {
 
 struct DenoiseDev { float sigma_lum, sigma_depth, lum_floor; uint32_t normal_squarings; };
 
-constexpr uint32_t kAtrousBlock = 16u;                     // pixels a side: a tile of the image
-constexpr uint32_t kAtrousStagedMaxStep = 2u;
+// kAtrousBlock (pixels a side: a tile of the image) and kAtrousStagedMaxStep: kernel_types.hpp, where the context reads its default from
 constexpr uint32_t kAtrousStagedSide = kAtrousBlock + 4u * kAtrousStagedMaxStep;    // block + 2 * step of halo on either side
 
 MIRT_DI bool dn_finite(float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; }

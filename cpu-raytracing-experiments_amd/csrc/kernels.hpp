@@ -26,94 +26,12 @@
 #include "device_math.hpp"
 #include "hits_wave_map.hpp"
 #include "tile_map.hpp"
+#include "kernel_types.hpp"
 
 namespace mirt {
 
-constexpr uint32_t kBlock = 256;
-constexpr uint32_t kShadeBlock = 512;           // shade: 73-80 VGPRs = 24 waves per CU = three 8-wave workgroups; k_shade<ShadeWaves8, ...> (shade_waves): 64 VGPRs = a fourth (forced to 64 with packed FP32 selected: 15-28 spills, 92 -> 109 ms per cfg4 step; 1024-thread workgroups: one per CU, every barrier stalls the CU)
-constexpr uint32_t kTraceBlock = 1024;          // trace kernels: one workgroup per CU stages the BVH into LDS once per launch
-constexpr uint32_t kLdsStack = 16;              // traversal-stack entries per lane kept in LDS (deeper ones spill to scratch)
-constexpr uint32_t kLdsStackWide = 12;          // ... with binary16 records but u32 entries (> 32768 records or spheres): 48 KB, so that two workgroups still share a CU
-constexpr uint32_t kLeafBit = 0x80000000u;      // child reference flag (bvh_layout.hpp)
-constexpr uint32_t kStack = 64;                 // Stack<StackFrame,64>, BVH.hpp:321
-constexpr uint32_t kDestAccum = 0x80000000u;    // shadow-entry destination flag: the path ended at this hit (counted as terminated once its shadow ray is done)
-
-struct SceneDev {
-	const float4* recs;         // GPU-internal child-pair records, 4 float4 each, breadth-first (bvh_layout.hpp)
-	const float4* spheres;      // acceleration_structure.prims (BVH order): {pos.xyz, radius_sq}
-	const int32_t* prim_mat;    //   "  material_ID
-	const float4* light_sphere; // per light (lighting_acceleration.prims order): scene.geometry[light] = {pos.xyz, radius_sq} (Renderer.hpp:261-262)
-	const float4* light_emit;   //   "   {emission of its material .xyz, bits of the geometry-order prim id} (Renderer.hpp:263,283)
-	const float4* mat_albedo;   // scene.material[].albedo
-	const float4* mat_emission; // scene.material[].emission
-	const float4* hdri;         // sky.hdri_data RGBA
-	const float4* mat_glass;    // scene.material[]: {transmission.rgb, 1 + IOR_minus_one} — read by the GLASS instantiations of k_shade only (mirt_set_transmission)
-	uint32_t n_spheres, n_recs, n_mat, n_lights;
-	uint32_t lds_recs;          // records [0, lds_recs) are staged in LDS by the trace kernels (top of the tree)
-	uint32_t lds_spheres;       // spheres [0, lds_spheres) likewise (all of them, or none)
-	uint32_t half_boxes;        // 1: recs are the 32-B binary16 records (2 float4 each)
-	uint32_t wide;              // 1 (with half_boxes): recs are 64-B binary16 records of up to FOUR children (bvh_layout.hpp build_wide_half_records)
-	uint32_t chunk_max;         // rays per reservation from a launch's work counter, upper limit (pick_chunk)
-	uint32_t leaf_batch;        // lanes of a wave that must stand at a leaf before it runs a leaf pass (trace_persistent)
-	uint32_t refill_idle;       // idle lanes of a wave that trigger a refill (trace_persistent)
-	uint32_t stack16;           // 1: record and prim indices fit 15 bits and the LDS stack holds u16 entries (binary16 records, <= 32768 records and spheres)
-	float ambient[3];
-	int32_t hdri_w, hdri_h;
-	float hdri_fw, hdri_fh;
-	uint32_t has_ambient;       // Renderer.hpp:79
-	uint32_t use_bvh;
-};
-
-// RayStream<>::Buffer, DataStreams.hpp:75-88 — 16-byte records, `capacity` rays per plane: a lane moves a ray with two dwordx4 (and one dwordx2)
-// instead of one dword per member.  40 B per ray.
-struct StreamBuf {
-	float4* a;                  // {p.xyz, bits of path}: path = (batch slot << FrameParams::pix_bits) | local pixel index (tile_local*256 + ID); stands in for pixelID + seed[]
-	                            // (k_shade<GLASS> also sets kViaInterface in this word, k_shade<MIXED> kSampledGGX; no other kernel reads it: k_trace takes p only, and a shadow record gets the bare id)
-	float4* b;                  // {dir.xyz, throughput.r}
-	float2* c;                  // {throughput.g, throughput.b} — read by the hits only (the miss shader scales by throughput.r, Q10)
-	                            // (radiance has no plane: a path's running sum is its word of the contribution buffer, contrib_index)
-	                            // (`pdf` has no plane: Closure::pdf of the sampled direction is (1/pi) max(0, dir.z) of the WORLD-space dir
-	                            //  (Q8, Renderer.hpp:386,401), a function of the stored direction, recomputed by the bounce that needs it)
-	float* w;                   // mirt_set_sky_sampling only (nullptr otherwise, and no other kernel than k_shade<SKY> names it): the MIS weight the miss shader gives
-	                            // thr.r x sky should this ray miss — the power heuristic of the closure's LOCAL pdf of the direction against the sky's (k_shade, SKY)
-	                            // (mirt_set_ggx_pdf adds one more 4-byte plane per stream, out->pdf of the closure sample that made the ray.  It is NOT a member: this
-	                            //  struct is an argument of every trace kernel too, and growing it moves their and the SKY kernels' scalar registers.  k_shade takes
-	                            //  the two planes as its last arguments, pdf_plane_in / pdf_plane_out, which only its PDF instantiations name.)
-};
 // kPrimaryList launches have no ray stream: the words at `a` are the list of pixels instead (k_primary_cand's, or the active tiles' part of it).
 MIRT_DI const uint32_t* stream_pixel_list(const StreamBuf& in) { return reinterpret_cast<const uint32_t*>(in.a); }
-// RayStream<>::ShadowStream, DataStreams.hpp:113-126, plus the deferred-add operands.  A record holds its own ray — k_trace's refill is two
-// independent dwordx4 — and is 48 B for the common case (64 B with the emissive add); the path radiance waits in the path's contribution word.
-struct ShadowBuf {
-	float4* a;                  // {origin.xyz, tfar}
-	float4* b;                  // {dir.xyz, bits of dest}: dest = path id | kDestAccum (the path ended at this hit) | kDestFull
-	float4* c;                  // {NEE radiance carried by the shadow ray, unused}
-	float4* d;                  // kDestFull records only: {emissive add of this bounce, unused}
-};
-struct FrameParams {
-	CameraParams cam;
-	uint32_t h_tiles;           // Renderer.hpp:59
-	uint32_t first_tile;        // first global LaunchIndex owned by this context
-	uint32_t run_tiles;         // the context owns runs of run_tiles consecutive LaunchIndices, stride_tiles apart (interleaved tile rows,
-	uint32_t stride_tiles;      // mirt_set_tile_rows); stride_tiles = 0: one contiguous range (mirt_set_tile_range)
-	uint32_t n_pix;             // local pixels = local tiles * 256
-	uint32_t pix_bits;          // a path id is (batch slot << pix_bits) | local pixel, below 2^30: the fewer pixels a context owns, the more
-	uint32_t pix_mask;          // accumulations fit a batch ((1 << pix_bits) - 1)
-	uint32_t acc_base;          // `accumulations` before this batch
-	uint32_t batch_n;           // accumulations in flight in this batch = slots of its contribution buffer [tile][slot][256][rgb]
-	uint32_t max_bounces;
-	uint32_t buckets;
-	uint32_t mis;               // MIS && light_count > 0 (Q12 guard)
-	uint32_t n_lights;
-	uint32_t first_groups;      // k_shade<FIRST>: a chunk of 512 pixels x the batch's accumulations is handed out in this many pieces (small images: enough pieces for an even load)
-	float inv_n_pix, inv_h_tiles, inv_run_tiles;   // 1/n_pix, 1/h_tiles, 1/run_tiles for udiv_f (no integer division in the kernels)
-};
-// RayStream<>::Hit, DataStreams.hpp:90-111 (tfar, primID; matID is looked up by the shader): ONE 8-B record per ray, written by the lane that finished
-// the ray and read back by k_shade with one instruction each (two dword planes until round 3: two scattered 4-B stores and loads per ray).
-struct alignas(8) HitRec { float tfar; int32_t prim; };
-struct DevCounters {
-	unsigned long long rays, shadow_rays, nodes, spheres, shadow_nodes, shadow_spheres, terminated, dropped;
-};
 
 // ------------------------------------------------------------------------------------------------
 // wave64 helpers
@@ -140,9 +58,6 @@ MIRT_DI void wave_sum(unsigned long long v, unsigned long long* counter) {     /
 // of a 4096x4096 batch (164 k appends).  A segment receives at most ceil(T / kSegs) iterations of <= 512 rays, T =
 // ceil(input rays / 512), hence seg_cap = ceil(ceil(capacity / 512) / kSegs) * 512 never overflows.  Consumers number the
 // rays 0 .. total-1 across the segments in order (queue_view / queue_slot); per-path results do not depend on slot order.
-constexpr uint32_t kSegs = 8;
-constexpr uint32_t kSegPitch = 32;              // u32 words between two segment counters (128 B)
-struct Queue { uint32_t* n; uint32_t seg_cap; };  // n[k * kSegPitch] = rays in segment k
 struct QueueView { uint32_t pre[kSegs + 1]; uint32_t seg_cap; };     // pre[k] = rays before segment k, pre[kSegs] = total
 MIRT_DI QueueView queue_view(const Queue& q) {
 	QueueView v; v.seg_cap = q.seg_cap; v.pre[0] = 0;
@@ -595,11 +510,7 @@ MIRT_DI void leaf_step(const SceneDev& sc, const TraceLds lds, Trav& t, TravSpil
 // [wbeg, wend) that it reserves from a per-launch work counter (one atomic per kChunk rays); whenever at least
 // kRefillIdle lanes are idle they are given the next rays of the window — slot = wbeg + rank among idle lanes, from a
 // wave64 ballot + mbcnt prefix sum — and the wave goes back to stepping all lanes together.
-constexpr uint32_t kChunkMax = 512;    // default of SceneDev::chunk_max.  Measured (k_trace ms per step, 256 / 512 / 4096): cfg2 14.9 / 13.6 / 14.1, cfg4 - / 381.5 / 402.3 (larger chunks: uneven tails)
-constexpr uint32_t kLeafBatch = 16;    // default of SceneDev::leaf_batch.  Measured (k_trace ms per cfg4 step; 8 / 16 / 24 / 32 / 40): 252.9 / 247.7 / 253.1 / 274.2 / 314.8; before the split 284.9
-constexpr uint32_t kRefillIdle = 32;   // measured on cfg2: 8 -> 15.3 ms of trace per step, 16 -> 13.9, 24..40 -> 13.5 (a refill runs the ~200-instruction ray set-up on the whole wave)
 constexpr uint32_t kNone = 0xffffffffu;
-struct FatList { uint32_t* count; uint32_t* rays; uint32_t capacity; };
 // [beg, end): ray numbers the wave still has to hand out, all in one queue segment (slot = number + offset); [end, chunk_end):
 // the rest of the reserved chunk, in later segments.
 struct WaveWindow { uint32_t beg, end, chunk_end, offset, chunk; bool more; };
@@ -705,7 +616,6 @@ MIRT_DI void trace_persistent(const SceneDev& sc, const TraceLds tl, const Queue
 
 // Brute force over all prims (the reference as shipped, BVH.hpp:312 / :365), sphere packets staged
 // through LDS one chunk at a time by the whole workgroup.
-constexpr uint32_t kBruteChunk = 1024;   // 16 KiB of float4
 template <bool ANYHIT, bool COUNT>
 MIRT_DI bool traverse_brute(const SceneDev& sc, float4* lds, bool active, float px, float py, float pz, float dx, float dy, float dz,
                             float& tfar, int32_t& primID, uint32_t& n_spheres) {
@@ -880,7 +790,7 @@ MIRT_DI size_t contrib_index(uint32_t batch_n, uint32_t pix_bits, uint32_t path)
 // The record carries the path id in every case, so nothing here is found through another stream.
 // occ != nullptr (mirt_debug_trace_shadow): only the occlusion flag is stored.
 constexpr uint32_t kDestFull = 0x40000000u;
-constexpr uint32_t kDestPath = 0x3fffffffu;     // path ids use bits 0-29 (batch slot << pix_bits | pixel; capacity check in mirt_capi.hip)
+constexpr uint32_t kDestPath = 0x3fffffffu;     // path ids use bits 0-29 (batch slot << pix_bits | pixel; capacity check in mirt_launch.hip)
 constexpr uint32_t kSampledGGX = 0x40000000u;   // k_shade<MIXED>, in a STREAM's path word only (kDestFull, the same bit, lives in shadow records only): the ray's direction was sampled by Closure<GGX>
 constexpr uint32_t kViaInterface = 0x80000000u; // k_shade<GLASS>, in a STREAM's path word (StreamBuf::a, never a shadow record's): the ray's direction was sampled by a dielectric interface
 struct ShadowSink {
@@ -1265,8 +1175,6 @@ __global__ __launch_bounds__(kBlock) void k_primary_hits_wave(SceneDev sc, Frame
 // are fetched again only when the prim differs from the previous sample's (the samples of a pixel mostly hit the same sphere).
 // The hit arithmetic is the closest-hit shader's of k_shade, operation for operation.  Counts nothing into DevCounters.
 // ------------------------------------------------------------------------------------------------
-constexpr uint32_t kAovPlanes = 7;
-constexpr float kAovMissDepth = 1e4f;             // Renderer.hpp:228
 // LENS: the sample's thin-lens ray (lens_ray) instead of the pinhole ray — origin and direction both differ per sample.
 // SPARSE: the sums of a frozen tile stop with its accumulator (its hit records are not written either).
 template <bool LENS, bool SPARSE = false>
@@ -1300,24 +1208,6 @@ __global__ __launch_bounds__(kBlock) void k_first_hit_aov(SceneDev sc, FramePara
 		for (uint32_t k = 0; k < kAovPlanes; k++) w[k * kTileSize] = sum[k];
 	}
 }
-// mirt_render_aov: one of the three outputs of the slab above, row-major over the image (row 0 = y 0), 1 (depth) or 3 floats per pixel.
-// Depth and colour: sum / accumulations; normal: normalize3(sum), (0,0,0) where the sum has no length.  IEEE division and sqrt.
-constexpr int kAovDepth = 0, kAovNormal = 1, kAovAlbedo = 2;
-__global__ __launch_bounds__(kBlock) void k_resolve_aov(const float* __restrict__ aov, float* __restrict__ out, uint32_t n_pix, TileMap tiles, int which, float accumulations_all,
-                                                           const uint32_t* __restrict__ tile_counts) {
-	for (uint32_t pix = blockIdx.x * kBlock + threadIdx.x; pix < n_pix; pix += gridDim.x * kBlock) {
-		const float accumulations = tile_counts ? static_cast<float>(tile_counts[pix >> 8]) : accumulations_all;     // a context with frozen tiles: each tile at its own count
-		const float* src = aov + static_cast<size_t>(pix >> 8) * (kAovPlanes * kTileSize) + (pix & 255u);
-		const size_t at = tiles.pixel_offset(pix >> 8, pix & 255u, 1u);
-		if (which == kAovDepth) { out[at] = src[0] / accumulations; continue; }
-		const uint32_t first = which == kAovNormal ? 1u : 4u;
-		f3 v{ src[first * kTileSize], src[(first + 1u) * kTileSize], src[(first + 2u) * kTileSize] };
-		if (which == kAovNormal) v = dot3(v, v) == 0.0f ? f3{ 0.0f, 0.0f, 0.0f } : normalize3(v);
-		else v = { v.x / accumulations, v.y / accumulations, v.z / accumulations };
-		out[at * 3u] = v.x; out[at * 3u + 1u] = v.y; out[at * 3u + 2u] = v.z;
-	}
-}
-
 // ------------------------------------------------------------------------------------------------
 // Accumulator addressing — AccumulationTile<k>, Renderer.hpp:43-46,84: [tile][bucket][r,g,b][256]
 // ------------------------------------------------------------------------------------------------
@@ -1340,17 +1230,6 @@ MIRT_DI f3 sky_eval(const SceneDev& sc, float x, float y, float z) {
 //   ts[rows + 1]      1 + sin el(k): ... and from y = -1 (each rounded from float64: near a pole sin el itself would lose the cell to cancellation)
 //   cond[rows * cols] running sums of the importances within each row
 //   dens[rows * cols] p(cell) = I / (Omega * total), in 1 / sr
-struct SkyTable {
-	const float* t;             // nullptr: no table (the switch is off)
-	uint32_t rows, cols;
-	MIRT_DI const float* marg() const { return t; }
-	MIRT_DI const float* rowsum() const { return t + rows; }
-	MIRT_DI const float* tn() const { return t + 2u * rows; }
-	MIRT_DI const float* ts() const { return t + 3u * rows + 1u; }
-	MIRT_DI const float* cond() const { return t + 4u * rows + 2u; }
-	MIRT_DI const float* dens() const { return t + 4u * rows + 2u + static_cast<size_t>(rows) * cols; }
-};
-inline size_t sky_table_floats(uint32_t rows, uint32_t cols) { return 4u * static_cast<size_t>(rows) + 2u + 2u * static_cast<size_t>(rows) * cols; }
 
 // Running sums of n values by one 256-thread workgroup in a FIXED order: thread t owns the K = ceil(n / 256) consecutive values [t K, t K + K) and
 // sums them left to right from +0 (l_j); thread 0 then sums the 256 chunk sums left to right (pre_t = the sum of the chunks before t); the running
@@ -1527,7 +1406,7 @@ MIRT_DI uint32_t block_compact(bool flag, uint32_t value, uint32_t* scratch, uin
 // (a Lambertian-sampled ray stores Q8's word there, the bits it would otherwise recompute).  The closure sample, its estimator and the roulette
 // read nothing new.  PDF = false names neither ggx_pdf nor the plane, and is the text as it was.  The same launch bounds.
 //
-// ShadeForm: k_shade's nine template arguments as one value, in their order — what the host decides per launch (mirt_capi.hip shade_form) and
+// ShadeForm: k_shade's nine template arguments as one value, in their order — what the host decides per launch (mirt_launch.hip shade_form) and
 // looks up in its table of instantiations (shade_kernel).  valid() is the one statement of which combinations exist: 5 bounce forms (later
 // bounce; bounce 0, with the lens, with frozen tiles, with both) x 8 of (RIS, GLASS, SKY) x 5 of closure and pdf (Lambertian, GGX, MIXED, GGX + PDF,
 // MIXED + PDF).  A new switch is one more member, one more bit and, if it cannot stand alone, one more term of valid().
@@ -1555,7 +1434,7 @@ static_assert(shade_forms_valid() == 200u, "k_shade has 5 bounce forms x 8 of (R
 // operations in the same order, one lane-wide instruction each — target("no-packed-fp32-ops").  A kernel whose target features differ from its
 // callees' gets none of them inlined unless they are always_inline: MIRT_DI functions are, the HIP headers' __float_as_uint, make_float4,
 // __syncthreads ... are not and became real calls (s_swappc_b64, each waiting for every load in flight), hence `flatten`, which inlines every call
-// the kernel's own text makes.  The listing of these two kernels must hold no s_swappc (profiles/shade_occupancy.txt; Makefile, mirt_capi.o).
+// the kernel's own text makes.  The listing of these two kernels must hold no s_swappc (profiles/shade_occupancy.txt; Makefile, mirt_launch.o).
 // Bounce 0 is bound by VALU issue and keeps its packed instructions; the other later-bounce forms were not measured: they stay k_shade, as they were.
 constexpr uint32_t shade_waves(ShadeForm f) { return (f.first || f.lens || f.sparse || f.ris || f.glass || f.sky || f.mixed || f.pdf) ? 6u : 8u; }
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1793,7 +1672,7 @@ __global__ __launch_bounds__(kTileSize, 4) void k_tile_stream(SceneDev sc, Frame
 }
 
 // In-order merge of one batch's contribution buffer ([tile][slot][256][rgb], slot = accumulation index inside the batch; see
-// contrib_index) into the accumulator ([tile][bucket][rgb][256]; see launch_batch in mirt_capi.hip): exactly the
+// contrib_index) into the accumulator ([tile][bucket][rgb][256]; see launch_batch in mirt_launch.hip): exactly the
 // `output_color[px] += radiance` of Renderer.hpp:427-429, one add per (pixel, bucket) per Accumulate() call.  Accumulation
 // acc_base+k+1 lands in bucket (acc_base+k+1) % buckets (Renderer.hpp:82); each accumulator word is owned by one thread, which
 // applies that bucket's contributions in ascending k, i.e. in accumulation order.  A thread owns 4 pixels of a tile: per slot it
@@ -1823,106 +1702,6 @@ __global__ __launch_bounds__(kBlock) void k_merge_contrib(float4* __restrict__ a
 			dst[0] = r; dst[kQuads] = g; dst[2u * kQuads] = b;
 		}
 	}
-}
-
-// ------------------------------------------------------------------------------------------------
-// MEDIAN OF MEANS & TONEMAPPING — Renderer::Render, Renderer.hpp:436-478
-// ------------------------------------------------------------------------------------------------
-MIRT_DI float median_k(float* v, uint32_t k) {
-	if (k == 5) return median5(v[0], v[1], v[2], v[3], v[4]);               // the reference network, Sampling.hpp:13-21
-	for (uint32_t a = 1; a < k; a++) {                                      // generalisation (Q19): insertion sort
-		float key = v[a]; int b = static_cast<int>(a) - 1;
-		while (b >= 0 && key < v[b]) { v[b + 1] = v[b]; b--; }
-		v[b + 1] = key;
-	}
-	return (k & 1u) ? v[k / 2] : (v[k / 2 - 1] + v[k / 2]) * 0.5f;
-}
-// tile_counts (NULL for a context without a frozen tile): every tile at its own sample count — scale = exposure / (float)(count / buckets), the
-// binary32 operations the host forms scale_all with.  The same in k_noise and k_resolve_aov.
-__global__ __launch_bounds__(kBlock) void k_resolve(const float* __restrict__ accum, float4* __restrict__ fb, uint32_t n_pix, TileMap tiles, uint32_t buckets, float scale_all,
-                                                    const uint32_t* __restrict__ tile_counts, float exposure) {
-	for (uint32_t pix = blockIdx.x * kBlock + threadIdx.x; pix < n_pix; pix += gridDim.x * kBlock) {
-		const float scale = tile_counts ? exposure / static_cast<float>(tile_counts[pix >> 8] / buckets) : scale_all;
-		const float* src = accum + static_cast<size_t>(pix >> 8) * buckets * 3u * kTileSize + (pix & 255u);
-		float ch[3];
-		for (uint32_t c = 0; c < 3; c++) {
-			float v[16];
-			for (uint32_t b = 0; b < 16; b++) if (b < buckets) v[b] = src[(static_cast<size_t>(b) * 3u + c) * kTileSize];
-			ch[c] = scale * median_k(v, buckets);                               // Renderer.hpp:453-455
-		}
-		tonemapping(ch[0], ch[1], ch[2]);                                       // Renderer.hpp:461
-		fb[tiles.pixel_offset(pix >> 8, pix & 255u, 1u)] = make_float4(ch[0], ch[1], ch[2], 1.0f);   // Renderer.hpp:447,465
-	}
-}
-
-// ------------------------------------------------------------------------------------------------
-// NOISE ESTIMATE — mirt_noise (mirt.h, "per-pixel noise estimate"): the relative standard error of the mean of the bucket means
-// ------------------------------------------------------------------------------------------------
-// One 256-thread workgroup per owned tile, lane ID = pixel ID: the coalesced plane reads of k_resolve.  Per pixel the quantity of mirt.h, one
-// rounding per operation in the stated order (-ffp-contract=off; IEEE division and square root).  A pixel is usable when the word of e is
-// below 0x7f800000 (finite, sign bit clear); only usable pixels enter what follows:
-//   tile maximum   on the words (for non-negative floats the order of the words is the order of the values): a wave64 xor-butterfly, then
-//                  the four wave partials through LDS — exact, whatever the order;
-//   tile sum       FIXED ORDER: inside a wave the xor-butterfly with strides 32, 16, 8, 4, 2, 1 — at each step a lane adds its partner's
-//                  partial to its own (a + b = b + a, so both lanes of a pair hold the same word), i.e. a balanced binary tree over the 64
-//                  lanes with the pairs (l, l ^ 32) at its leaves; then ((w0 + w1) + w2) + w3 over the four waves; unusable pixels add +0;
-//   tile record    {max, sum / count (0 when count = 0), count, 256 - count} as four floats;
-//   histogram      bin = word >> 20 (< 2040 for a usable pixel): LDS uint32 atomics, then the non-zero bins are added to the 2048-word
-//                  device histogram with integer atomics — integer adds, so the result does not depend on scheduling.
-constexpr uint32_t kNoiseBins = 2048u;
-constexpr uint32_t kNoiseUsableBelow = 0x7f800000u;
-constexpr uint32_t kNoiseMaxBuckets = 16u;     // one y_j per register; mirt_noise asserts that MIRT_MAX_BUCKETS fits
-__global__ __launch_bounds__(kTileSize) void k_noise(const float* __restrict__ accum, float* __restrict__ map, float4* __restrict__ tile_rec, uint32_t* __restrict__ hist,
-                                                     TileMap tiles, uint32_t buckets, float scale_all, float floor_,
-                                                     const uint32_t* __restrict__ tile_counts, float exposure, uint32_t* __restrict__ above, float target) {
-	__shared__ uint32_t bins[kNoiseBins];
-	__shared__ uint32_t w_max[kTileSize / 64u], w_cnt[kTileSize / 64u], w_above[kTileSize / 64u];
-	__shared__ float w_sum[kTileSize / 64u];
-	const uint32_t local = blockIdx.x, ID = threadIdx.x;
-	const float scale = tile_counts ? exposure / static_cast<float>(tile_counts[local] / buckets) : scale_all;
-	for (uint32_t b = ID; b < kNoiseBins; b += kTileSize) bins[b] = 0u;
-	const float* src = accum + static_cast<size_t>(local) * buckets * 3u * kTileSize + ID;
-	float y[kNoiseMaxBuckets];
-	float sum = 0.0f;
-	for (uint32_t j = 0; j < kNoiseMaxBuckets; j++) if (j < buckets) {
-		const float r = src[(static_cast<size_t>(j) * 3u) * kTileSize], g = src[(static_cast<size_t>(j) * 3u + 1u) * kTileSize], b = src[(static_cast<size_t>(j) * 3u + 2u) * kTileSize];
-		y[j] = scale * ((0.2126f * r + 0.7152f * g) + 0.0722f * b);
-		sum = j ? sum + y[j] : y[j];
-	}
-	const float mean = sum / static_cast<float>(buckets);
-	float ss = 0.0f;
-	for (uint32_t j = 0; j < kNoiseMaxBuckets; j++) if (j < buckets) {
-		const float d = y[j] - mean;
-		ss = j ? ss + d * d : d * d;
-	}
-	const float var = ss / static_cast<float>(buckets - 1u);
-	const float se = __builtin_sqrtf(var / static_cast<float>(buckets));
-	const float denom = mean + floor_;
-	const float e = denom == 0.0f ? 0.0f : se / denom;
-	if (map) map[tiles.pixel_offset(local, ID, 1u)] = e;
-	const uint32_t word = __float_as_uint(e);
-	const bool usable = word < kNoiseUsableBelow;
-	uint32_t m = usable ? word : 0u;
-	float s = usable ? e : 0.0f;
-	for (int off = 32; off > 0; off >>= 1) {
-		m = max(m, static_cast<uint32_t>(__shfl_xor(static_cast<int>(m), off, 64)));
-		s = s + __shfl_xor(s, off, 64);
-	}
-	const unsigned long long usable_m = __ballot(usable);
-	const unsigned long long above_m = __ballot(usable && e > target);         // above[tile] (mirt_tile_above): usable pixels with e > target
-	const uint32_t wave = ID >> 6;
-	if ((ID & 63u) == 0u) { w_max[wave] = m; w_sum[wave] = s; w_cnt[wave] = static_cast<uint32_t>(__popcll(usable_m)); w_above[wave] = static_cast<uint32_t>(__popcll(above_m)); }
-	__syncthreads();                                                          // bins are zero, wave partials are written
-	if (usable) atomicAdd(&bins[word >> 20], 1u);
-	if (ID == 0u) {
-		const uint32_t t_max = max(max(w_max[0], w_max[1]), max(w_max[2], w_max[3]));
-		const float t_sum = ((w_sum[0] + w_sum[1]) + w_sum[2]) + w_sum[3];
-		const uint32_t n = (w_cnt[0] + w_cnt[1]) + (w_cnt[2] + w_cnt[3]);
-		tile_rec[local] = make_float4(__uint_as_float(t_max), n ? t_sum / static_cast<float>(n) : 0.0f, static_cast<float>(n), static_cast<float>(kTileSize - n));
-		if (above) above[local] = (w_above[0] + w_above[1]) + (w_above[2] + w_above[3]);
-	}
-	__syncthreads();
-	for (uint32_t b = ID; b < kNoiseBins; b += kTileSize) { const uint32_t v = bins[b]; if (v) atomicAdd(&hist[b], v); }
 }
 
 // ------------------------------------------------------------------------------------------------

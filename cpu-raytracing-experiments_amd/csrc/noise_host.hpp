@@ -1,5 +1,5 @@
 // noise_host.hpp — the host arithmetic of the noise estimate (include/mirt.h, "per-pixel noise estimate"), shared by the single-context
-// entry points (mirt_capi.hip) and their group twins (mirt_group.hip) so that both form the same sums in the same order.  Host-only code.
+// entry points (mirt_resolve.hip) and their group twins (mirt_group.hip) so that both form the same sums in the same order.  Host-only code.
 #pragma once
 #include "../../include/mirt.h"
 

@@ -20,7 +20,7 @@ constexpr uint32_t kRefitNoParent = 0xffffffffu;
 constexpr uint32_t kRefitLeafBit = 0x80000000u;          // bvh_layout.hpp kLeafBit
 constexpr int kRefitF32 = 0, kRefitHalf = 1, kRefitWide = 2;   // mirt_debug_tree's layout numbers
 
-// What a refit reads besides the records: one allocation, laid out by the host (mirt_capi.hip refit_links).
+// What a refit reads besides the records: one allocation, laid out by the host (mirt_launch.hip refit_links).
 struct RefitLinks {
 	uint32_t* parent;        // [n_recs] the record whose slot points at this one; kRefitNoParent for record 0
 	uint32_t* used;          // [n_recs] used slots

@@ -5,7 +5,7 @@
 // with z = NaN marking an unusable pixel, and one float per pixel for the history length.
 // THE HISTORY WRITE IS THE BLEND: the kernel writes the blended (x, v) and the length ONCE, into buffers the history does not occupy (a tap reads
 // any pixel of the old history while other workgroups write, so it cannot be updated in place); with update = 1 the host then renames them — they
-// become the history, the old history's become scratch (mirt_capi.hip, mirt_render_temporal).  The guides of a call are the history's guides
+// become the history, the old history's become scratch (mirt_resolve.hip, mirt_render_temporal).  The guides of a call are the history's guides
 // unchanged, so that plane is renamed too and nothing is copied.  The a-trous passes read the blend and never write it: spatial blur does not
 // compound over frames.
 // NO LDS STAGING, and why: per pixel the kernel gathers 2 x 2 taps of two float4 images and one float image (eight float4 gathers, four scalars).

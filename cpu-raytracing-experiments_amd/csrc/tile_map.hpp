@@ -1,8 +1,8 @@
 // Which tiles of the image a context owns, and where their pixels lie in it — the one statement of the rule, for host and device.
 // A context owns runs of run_tiles consecutive LaunchIndices (Renderer.hpp:75,84-88), stride_tiles apart, starting at first_tile; its local
 // tile t is the t-th of them in ascending order; a tile is 16 x 16 pixels, tile T at x = 16 (T % h_tiles), y = 16 (T / h_tiles) of an image
-// `width` pixels wide.  Plain constexpr and inline functions, no HIP: k_resolve, k_resolve_aov and k_noise (kernels.hpp), the host layer
-// (mirt_capi.hip, mirt_group.hip) and the host-only check tests/native/tile_map_check.cpp, built under sanitizers, evaluate the same text.
+// `width` pixels wide.  Plain constexpr and inline functions, no HIP: k_resolve, k_resolve_aov and k_noise (resolve.hpp), the host layer
+// (mirt_capi.hip, mirt_resolve.hip, mirt_group.hip) and the host-only check tests/native/tile_map_check.cpp, built under sanitizers, evaluate the same text.
 // (The trace and shade kernels keep FrameParams and its global_tile with udiv_f: the hot-path form of the same rule.)
 #pragma once
 #include <stddef.h>

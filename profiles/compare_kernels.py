@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
-"""Per-kernel comparison of two builds of mirt_capi.hip: resources and instruction streams (the method of profiles/one_kernel_per_stage.txt).
+"""Per-kernel comparison of two builds of the kernel-holding units: resources and instruction streams (the method of profiles/one_kernel_per_stage.txt).
 
-    make -C cpu-raytracing-experiments_amd/csrc asm 2> remarks.log      (at each commit; keep mirt_gfx950.s and the log)
+    make -C cpu-raytracing-experiments_amd/csrc asm 2> remarks.log      (at each commit; keep the mirt_*_gfx950.s listings and the log)
     python profiles/compare_kernels.py parent.s change.s parent_remarks.log change_remarks.log [--all] [--order]
 
-Kernels are the functions the -Rpass-analysis=kernel-resource-usage remarks name; they pair by (demangled) name.  Per kernel: the resource block
+Each of the four arguments may be several files joined by commas (a side built from several units: mirt_launch_gfx950.s,mirt_resolve_gfx950.s);
+kernels pair by name across the union of a side's files.  Kernels are the functions the -Rpass-analysis=kernel-resource-usage remarks name; they pair by (demangled) name.  Per kernel: the resource block
 of the remarks — VGPRs, AGPRs, TotalSGPRs, VGPRs spilled, SGPRs spilled, scratch B/lane, LDS B/block, occupancy waves/SIMD — and the text between
 the function's label and .Lfunc_end (the instructions and the kernel descriptor's .amdhsa_ lines) with comment lines, trailing comments and
 blank lines stripped and .LBBn_m label numbers normalised.  Prints the rows that differ (--all: every row) and a summary; --order also prints where each list of kernels first differs in
-the order of emission.  Exit status 1 if a name is unpaired or a resource figure differs.  Host-only: plain Python, c++filt if there is one."""
+the order of emission (several files on a side: each listing of the change against the parent's order of the kernels it holds).  Exit status 1 if a name is unpaired or a resource figure differs.  Host-only: plain Python, c++filt if there is one."""
 import argparse
 import re
 import shutil
@@ -36,10 +37,15 @@ def demangle(names):
     return short
 
 
+def lines_of(paths):
+    for path in paths.split(","):
+        yield from open(path, errors="replace")
+
+
 def resources(log):
     """{mangled name: tuple of FIELDS} in the order of the remarks."""
     res, cur = {}, None
-    for line in open(log, errors="replace"):
+    for line in lines_of(log):
         m = re.search(r"remark: Function Name: (\S+)", line)
         if m:
             cur = m.group(1)
@@ -54,7 +60,7 @@ def resources(log):
 def streams(listing, kernels):
     """{mangled name: list of instruction lines}, labels normalised per function."""
     out, cur, body = {}, None, None
-    for line in open(listing, errors="replace"):
+    for line in lines_of(listing):
         if cur is None:
             m = re.match(r"^(\S+):\s*; @\1\s*$", line)
             if m and m.group(1) in kernels:
@@ -106,9 +112,12 @@ def main():
             print(f"  {label}: {n}")
     print(f"{same} pairs identical in resources and instruction stream, {res_diff} with a resource difference, {stream_diff} with a stream difference.")
     if a.order:
-        op, oc = [names[n] for n in rp], [names[n] for n in rc]
-        i = next((i for i, (x, y) in enumerate(zip(op, oc)) if x != y), None)
-        print("order of emission: " + ("the same" if i is None and len(op) == len(oc) else f"first differs at position {i}: {op[i]} | {oc[i]}"))
+        for listing in a.change_s.split(",") if "," in a.change_s + a.parent_s else [None]:
+            held = rc if listing is None else streams(listing, rc)
+            op, oc = [names[n] for n in rp if listing is None or n in held], [names[n] for n in rc if n in held]
+            i = next((i for i, (x, y) in enumerate(zip(op, oc)) if x != y), None)
+            print("order of emission" + ("" if listing is None else f" ({listing}, {len(oc)} kernels)") + ": "
+                  + ("the same" if i is None and len(op) == len(oc) else f"first differs at position {i}: {op[i]} | {oc[i]}" if i is not None else "one list is a prefix of the other"))
     return 1 if only_p or only_c or res_diff else 0
 
 

@@ -20,7 +20,7 @@ def lum(r, g, b):
     return (nt.LUMA[0] * r + nt.LUMA[1] * g) + nt.LUMA[2] * b
 
 
-# ---- mirt_render's own operations (kernels.hpp median_k, device_math.hpp tonemapping) -----------------------------------------------------
+# ---- mirt_render's own operations (resolve.hpp median_k, device_math.hpp tonemapping) -----------------------------------------------------
 def _max_sel(a, b):
     return np.where(a < b, b, a)
 

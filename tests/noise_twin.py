@@ -1,4 +1,4 @@
-"""Binary32 numpy twin of the noise estimate (include/mirt.h, "per-pixel noise estimate"; kernels.hpp k_noise), restated here:
+"""Binary32 numpy twin of the noise estimate (include/mirt.h, "per-pixel noise estimate"; resolve.hpp k_noise), restated here:
 
 for a pixel with bucket words r_j, g_j, b_j (j = 0 .. k-1, k >= 2) and scale = exposure / (float)(accumulations / k), every operation
 binary32, one rounding each, in this order:

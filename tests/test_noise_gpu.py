@@ -1,4 +1,4 @@
-"""The noise estimate on the GPU (mirt_noise, mirt_accumulate_until and their group twins; kernels.hpp k_noise) against the binary32 numpy
+"""The noise estimate on the GPU (mirt_noise, mirt_accumulate_until and their group twins; resolve.hpp k_noise) against the binary32 numpy
 twin of noise_twin.py, which restates the quantity of include/mirt.h:
 
     y_j = scale * ((0.2126f * r_j + 0.7152f * g_j) + 0.0722f * b_j),  mean = (((y_0 + y_1) + ...) / (float)k,  d_j = y_j - mean,

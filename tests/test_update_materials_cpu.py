@@ -134,8 +134,8 @@ def test_update_materials_is_declared_at_every_layer(mirt):
     assert "void UpdateMaterials(" in host and "mirt_group_update_materials(" in host
     headless = open(os.path.join(mirt.CSRC, "mirt_headless.cpp")).read()
     assert '"--set-emission"' in headless and '"--sphere-material"' in headless
-    capi = open(os.path.join(mirt.CSRC, "mirt_capi.hip")).read()
-    assert '#include "light_list.hpp"' in capi and "check_materials(" in capi
+    launch, capi = open(os.path.join(mirt.CSRC, "mirt_launch.hip")).read(), open(os.path.join(mirt.CSRC, "mirt_capi.hip")).read()
+    assert '#include "light_list.hpp"' in launch and "check_materials(" in capi
     kernels = open(os.path.join(mirt.CSRC, "light_list.hpp")).read()
     for name in ("k_assign_materials", "k_light_count", "k_light_scan", "k_light_scatter", "__ballot(", "__popcll("):
         assert name in kernels, name

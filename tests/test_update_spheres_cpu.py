@@ -109,8 +109,8 @@ def test_update_spheres_is_declared_at_every_layer(mirt):
     assert "void UpdateSpheres(" in host and "mirt_group_update_spheres(" in host
     headless = open(os.path.join(mirt.CSRC, "mirt_headless.cpp")).read()
     assert '"--move-sphere"' in headless
-    capi = open(os.path.join(mirt.CSRC, "mirt_capi.hip")).read()
-    assert '#include "refit.hpp"' in capi and '#include "scene_update_host.hpp"' in capi
+    launch, capi = open(os.path.join(mirt.CSRC, "mirt_launch.hip")).read(), open(os.path.join(mirt.CSRC, "mirt_capi.hip")).read()
+    assert '#include "refit.hpp"' in launch and '#include "scene_update_host.hpp"' in capi
     # the leaf box is stated once on the device and shared by the builder and the refit
     for name in ("lbvh_build.hip", "refit.hpp"):
         text = open(os.path.join(mirt.CSRC, name)).read()

@@ -1,6 +1,6 @@
 """The traversal and the camera rays' candidate lists over a sweep of views and scales.
 
-The candidate lists (kernels.hpp kCollect, collect_leaf, k_primary_cand, k_primary_hits; mirt_capi.hip bundle_half_angle) are complete only
+The candidate lists (kernels.hpp kCollect, collect_leaf, k_primary_cand, k_primary_hits; mirt_launch.hip bundle_half_angle) are complete only
 while several hand-chosen margins hold together, and they have no CPU twin; the binary16 boxes (bvh_layout.hpp half_box_adequate,
 float_to_half_down / up) and sqrt_trav's slow branch are reached by the other suites only in passing.  Here one seeded cloud of spheres is
 seen along every axis, rolled, from inside, from a sphere's centre and surface, from 2000 units away, through focal lengths of 3 to 2000,

@@ -11,7 +11,7 @@ f32 = np.float32
 W, H, N_ACC, MAX_BOUNCES, BUCKETS = 64, 48, 5, 3, 5
 CLOUD_SEED, SCALED_SEED = 11, 12
 BIG_CENTRE, BIG_RADIUS = (1.75, -2.25, 0.75), 2.0             # the sphere the "inside a sphere" views sit in; nothing else reaches into it
-ROUTE_LIMIT = 1e-4                                            # mirt_capi.hip launch_batch: ||q|^2 - 1| >= 1e-4 -> no lists, every camera ray walks the tree
+ROUTE_LIMIT = 1e-4                                            # mirt_launch.hip launch_batch: ||q|^2 - 1| >= 1e-4 -> no lists, every camera ray walks the tree
 BUNDLE_MARGIN = 0.01                                          # bundle_half_angle: 0.7072 / |z| * 1.01
 
 
